@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 cp audio-pathtracer_amd/libfrequensee.so /tmp/base.so
 for v in base "$@" base; do
   if [ $v = base ]; then cp /tmp/base.so audio-pathtracer_amd/libfrequensee.so; else cp tools/tmp/$v/libfrequensee.so audio-pathtracer_amd/libfrequensee.so; fi
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --steps ${AB_STEPS:-100} --warmup 10 2>/tmp/o.err > /tmp/o.json || { echo "$v failed"; tail -3 /tmp/o.err; continue; }
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --steps ${AB_STEPS:-100} --warmup 10 2>/tmp/o.err > /tmp/o.json || { echo "$v failed"; tail -3 /tmp/o.err; continue; }
   cp /tmp/o.json gpurun_out/ab_extra_$v.json
   python3 - "$v" <<'PY' | tee -a gpurun_out/ab_builds_extra.jsonl
 import json,sys

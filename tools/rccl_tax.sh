@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 out=gpurun_out
 for mode in plain reduce plain reduce; do
   if [ $mode = reduce ]; then export FS_BENCH_FORCE_REDUCE=1; else unset FS_BENCH_FORCE_REDUCE; fi
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-extra --steps 300 --warmup 20 2>/tmp/o.err > /tmp/o.json || { echo "$mode failed"; tail -3 /tmp/o.err; continue; }
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-extra --steps 300 --warmup 20 2>/tmp/o.err > /tmp/o.json || { echo "$mode failed"; tail -3 /tmp/o.err; continue; }
   python3 - "$mode" <<'PY'
 import json,sys
 j=json.load(open('/tmp/o.json')); print(sys.argv[1], 'ms', round(j['ms_per_step'],4), 'Mrays/s', round(j['value']/1e6,1), {k: round(v,4) for k,v in j['kernel_ms'].items()})

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The driver's bench command several times in a row INSIDE ONE LEASE (fresh process each, with --no-cpu-baseline --no-extra): value,
+"""The driver's bench command several times in a row INSIDE ONE LEASE (fresh process each, with --full --no-cpu-baseline --no-extra): value,
 ms per step and the launch period — a 20-step timed region is 6 ms, so anything that stalls the producer once shows.
 NOT the driver's situation: the driver's process is the first GPU work of a fresh lease and runs the command without
 the two switches — tools/fresh_lease_driver_bench.sh (+ tools/fresh_lease_summary.py) reproduces that, one gpurun lease per run.
@@ -15,7 +15,7 @@ env = dict(os.environ)
 env.update(dict(a.split("=", 1) for a in sys.argv[2:]))
 vals = []
 for i in range(runs):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-extra"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extra"],
                        capture_output=True, text=True, timeout=300, env=env)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not line:
