@@ -33,6 +33,7 @@ FLAG_MIS_BALANCE = 32
 FLAG_MATERIAL_LOBES = 64
 FLAG_ACCUMULATE_ENERGY = 128
 FLAG_DOUBLE_POSITIONS = 256
+FLAG_SPECTRAL_IR = 512   # reconstruct calls: the channel view as per-band noise carriers x band envelopes (include/frequensee.h)
 NO_OBJECT = 0xFFFFFFFF
 
 # every symbol include/frequensee.h declares (tests check the library exports all of them)
@@ -51,6 +52,7 @@ EXPORTS = [
     "fs_apply_material_fd", "fs_energy_handoff", "fs_scene_update_triangles", "fs_scene_refit", "fs_set_impulse_response",
     "fs_scene_commit_fast", "fs_comm_unique_id", "fs_comm_init", "fs_comm_attach", "fs_comm_detach", "fs_comm_info", "fs_comm_enable_oneshot", "fs_shard_range",
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
+    "fs_set_band_edges",
 ]
 COMM_ID_BYTES = 128
 ERR_COMM = 8
@@ -275,6 +277,7 @@ def load():
         "fs_set_pipelining": (C.c_int, [vp, i32]),
         "fs_set_walk_stages": (C.c_int, [vp, vp, i32]),
         "fs_set_frames_per_launch": (C.c_int, [vp, i32]),
+        "fs_set_band_edges": (C.c_int, [vp, vp, i32]),
         "fs_submit": (C.c_int, [vp]),
         "fs_scene_commit_progressive": (C.c_int, [vp]),
         "fs_scene_refine_pending": (C.c_int, [vp, C.POINTER(i32)]),

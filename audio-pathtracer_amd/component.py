@@ -130,6 +130,14 @@ class Context:
         arr = np.asarray(list(bounds), dtype=np.int32)
         self.check(self.lib.fs_set_walk_stages(self.h, arr.ctypes.data_as(C.c_void_p) if arr.size else None, int(arr.size)))
 
+    def set_band_edges(self, edges=None):
+        """fs_set_band_edges: the num_bands - 1 crossovers (Hz) of FLAG_SPECTRAL_IR's bands; None = the default octave edges"""
+        if edges is None:
+            self.check(self.lib.fs_set_band_edges(self.h, None, 0))
+            return
+        arr = np.ascontiguousarray(np.asarray(list(edges), dtype=np.float32))
+        self.check(self.lib.fs_set_band_edges(self.h, arr.ctypes.data_as(C.c_void_p) if arr.size else None, int(arr.size)))
+
     def submit(self):
         self.check(self.lib.fs_submit(self.h))
 

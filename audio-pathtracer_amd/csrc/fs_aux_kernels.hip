@@ -13,21 +13,33 @@ namespace {
 //   per kChunk-sample chunk after a kWarm-sample warm-up: 0.75^96 ~ 1e-12 is far below fp32 resolution.
 //   The interpolated sample x[i] is produced incrementally (bin / in-bin counters), no division by spb.
 // ---------------------------------------------------------------------------------------------------
+// SPECTRAL (FS_FLAG_SPECTRAL_IR, its own instantiation: the default one does not change): row B is the spectral channel
+// (reconstruct_spectral_row) where a carrier set is given
+template <bool SPECTRAL>
 __global__ __launch_bounds__(kBlock) void reconstruct_kernel(const float* __restrict__ energy, int B, int nb,
                                                              int num_samples, int spb, float* __restrict__ ir_bands,
-                                                             float* __restrict__ ir_mono) {
+                                                             float* __restrict__ ir_mono, const float* __restrict__ carrier) {
     extern __shared__ __attribute__((aligned(16))) float s_amp[];  // reconstruct_body_fast's layout
+    if (SPECTRAL && (int)blockIdx.y == B) {
+        reconstruct_spectral_row((int)blockIdx.x, energy, B, nb, num_samples, spb, ir_bands, ir_mono, s_amp, nullptr, nullptr, carrier);
+        return;
+    }
     reconstruct_body_fast((int)blockIdx.y, (int)blockIdx.x, energy, B, nb, num_samples, spb, ir_bands, ir_mono, s_amp, nullptr);
 }
 
 // many sources' reconstructs as one launch: block -> (item, row, block of chunks); the table lives in pinned host memory
+template <bool SPECTRAL>
 __global__ __launch_bounds__(kBlock) void reconstruct_batch_kernel(const ReconItem* __restrict__ table, int B, int nb, int num_samples,
-                                                                   uint32_t cb, PublishWord pub) {
+                                                                   uint32_t cb, PublishWord pub, const float* __restrict__ carrier) {
     extern __shared__ __attribute__((aligned(16))) float s_rb[];  // reconstruct_body_fast's layout
     const uint32_t per_item = (uint32_t)(B + 1) * cb;
     const uint32_t item = blockIdx.x / per_item, in_item = blockIdx.x - item * per_item;
     const ReconItem it = table[item];
-    reconstruct_body_fast((int)(in_item / cb), (int)(in_item % cb), it.energy, B, nb, num_samples, it.spb, it.ir_bands, it.ir_mono, s_rb, it.host, it.mask);
+    if (SPECTRAL && (int)(in_item / cb) == B && it.spectral)
+        reconstruct_spectral_row((int)(in_item % cb), it.energy, B, nb, num_samples, it.spb, it.ir_bands, it.ir_mono, s_rb, it.host, it.mask,
+                                 carrier);
+    else
+        reconstruct_body_fast((int)(in_item / cb), (int)(in_item % cb), it.energy, B, nb, num_samples, it.spb, it.ir_bands, it.ir_mono, s_rb, it.host, it.mask);
     publish_arrive(pub.tickets, gridDim.x, pub.host_word, pub.id);
 }
 
@@ -373,22 +385,35 @@ __global__ void add_energy_kernel(float* row, int nb, float delay, float e) {
 }  // namespace
 
 void launch_reconstruct(const float* energy, int B, int num_bins, int sample_rate, int num_samples, int spb,
-                        float* ir_bands, float* ir_mono, hipStream_t s) {
+                        float* ir_bands, float* ir_mono, hipStream_t s, const float* carrier) {
     (void)sample_rate;
     int chunks = (num_samples + kChunk - 1) / kChunk;
     dim3 grid((chunks + kBlock - 1) / kBlock, B + 1);
     const size_t lds = sizeof(float) * ((size_t)num_bins + (size_t)kBlock * kChunk + kWarm + (size_t)kBlock * (kChunk + 1));
-    allow_lds(reconstruct_kernel, lds);
-    hipLaunchKernelGGL(reconstruct_kernel, grid, dim3(kBlock), lds, s, energy, B, num_bins, num_samples, spb, ir_bands, ir_mono);
+    if (carrier) {
+        allow_lds(reconstruct_kernel<true>, lds);
+        hipLaunchKernelGGL(reconstruct_kernel<true>, grid, dim3(kBlock), lds, s, energy, B, num_bins, num_samples, spb, ir_bands, ir_mono, carrier);
+    } else {
+        allow_lds(reconstruct_kernel<false>, lds);
+        hipLaunchKernelGGL(reconstruct_kernel<false>, grid, dim3(kBlock), lds, s, energy, B, num_bins, num_samples, spb, ir_bands, ir_mono, nullptr);
+    }
 }
 
-void launch_reconstruct_batch(const ReconItem* table, int count, int B, int num_bins, int num_samples, hipStream_t s, const PublishWord& pub) {
+void launch_reconstruct_batch(const ReconItem* table, int count, int B, int num_bins, int num_samples, hipStream_t s, const PublishWord& pub,
+                              const float* carrier) {
     if (count <= 0) return;
     const uint32_t chunks = (uint32_t)((num_samples + kChunk - 1) / kChunk), cb = (chunks + kBlock - 1) / kBlock;
     const size_t lds = sizeof(float) * ((size_t)num_bins + (size_t)kBlock * kChunk + kWarm + (size_t)kBlock * (kChunk + 1));
-    allow_lds(reconstruct_batch_kernel, lds);
-    hipLaunchKernelGGL(reconstruct_batch_kernel, dim3((uint32_t)count * (uint32_t)(B + 1) * cb), dim3(kBlock), lds, s, table, B, num_bins,
-                       num_samples, cb, pub);
+    bool spectral = false;   // (the table is pinned host memory the host has just written)
+    for (int i = 0; i < count && carrier != nullptr; ++i) spectral = spectral || table[i].spectral != 0;
+    const dim3 grid((uint32_t)count * (uint32_t)(B + 1) * cb);
+    if (spectral) {
+        allow_lds(reconstruct_batch_kernel<true>, lds);
+        hipLaunchKernelGGL(reconstruct_batch_kernel<true>, grid, dim3(kBlock), lds, s, table, B, num_bins, num_samples, cb, pub, carrier);
+    } else {
+        allow_lds(reconstruct_batch_kernel<false>, lds);
+        hipLaunchKernelGGL(reconstruct_batch_kernel<false>, grid, dim3(kBlock), lds, s, table, B, num_bins, num_samples, cb, pub, nullptr);
+    }
 }
 
 void launch_trace_rays(const DeviceScene& sc_in, const float* o, const float* d, const float* tmax, int N, int any_hit,

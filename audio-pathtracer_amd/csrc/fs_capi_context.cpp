@@ -434,7 +434,7 @@ int check_params(fs_context* ctx, const fs_params* p) {
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "listener_radius / source_radius must be finite and >= 0");
     if (!(p->dist_divisor > 0.f) || !(p->sound_speed > 0.f))
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "dist_divisor and sound_speed must be positive");
-    return FS_OK;
+    return check_spectral(ctx, p);
 }
 
 }  // namespace fsi
@@ -680,6 +680,7 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->h_fft_stage) (void)hipHostFree(ctx->h_fft_stage);
         if (ctx->d_batch) (void)hipFree(ctx->d_batch);
         if (ctx->d_build) (void)hipFree(ctx->d_build);
+        if (ctx->d_carrier) (void)hipFree(ctx->d_carrier);
         if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
         for (hipEvent_t e : ctx->ev_batch) if (e) (void)hipEventDestroy(e);
     }

@@ -16,6 +16,7 @@ int fs_reconstruct_impulse_response_async(fs_context* ctx, fs_source h, const fs
     if (!p) { fs_params_default(&def); p = &def; }
     if (p->struct_size != sizeof(fs_params)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_params.struct_size mismatch");
     if (p->samples_per_bin < 0 || p->samples_per_bin > 32767) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "samples_per_bin out of range (0 = from the configuration, else 1 .. 32767)");
+    { const int sc = check_spectral(ctx, p); if (sc) return sc; }
     // grouped frames: the source's current frame still waits for its launch — the reconstruct is recorded with it
     for (size_t k = ctx->group.size(); k-- > 0;) {
         fs_context::GroupEntry& e = ctx->group[k];
@@ -63,6 +64,7 @@ int fs_reconstruct_impulse_response_batch_async(fs_context* ctx, const fs_source
     if (!p) { fs_params_default(&def); p = &def; }
     if (p->struct_size != sizeof(fs_params)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_params.struct_size mismatch");
     if (p->samples_per_bin < 0 || p->samples_per_bin > 32767) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "samples_per_bin out of range (0 = from the configuration, else 1 .. 32767)");
+    { const int sc = check_spectral(ctx, p); if (sc) return sc; }
     std::vector<Source*> srcs((size_t)count);
     for (int32_t i = 0; i < count; ++i) {
         srcs[(size_t)i] = get_source(ctx, sources[i]);
@@ -90,6 +92,7 @@ int fs_update_sources(fs_context* ctx, const fs_source* sources, int32_t count, 
     if (!p) { fs_params_default(&def); p = &def; }
     if (p->struct_size != sizeof(fs_params)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_params.struct_size mismatch");
     if (p->samples_per_bin < 0 || p->samples_per_bin > 32767) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "samples_per_bin out of range (0 = from the configuration, else 1 .. 32767)");
+    { const int sc = check_spectral(ctx, p); if (sc) return sc; }
     std::vector<Source*> srcs((size_t)count);
     int rc = FS_OK;
     // depth = 0 only: a tick whose record store overflowed is traced and reconstructed again (up to 4 attempts; the store has been
@@ -145,6 +148,33 @@ int fs_set_impulse_response(fs_context* ctx, fs_source h, const float* ir, int32
     s->pub_word[slot] = 0; s->pub_batch[slot] = 0; s->seq_of[slot] = seq; s->enqueued = seq; s->cur_pub_seq = seq; s->dev_ir_word = 0;
     FS_HIP(ctx, hipStreamSynchronize(tail));   // `ir` is the caller's memory
     poll_published(ctx, s);
+    return FS_OK;
+}
+
+// FS_FLAG_SPECTRAL_IR's crossovers.  The context drains first (no frame in flight sees a half-built carrier set); the carriers are
+// built again at the next spectral reconstruct.
+int fs_set_band_edges(fs_context* ctx, const float* edges_hz, int32_t count) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    const int B = ctx->cfg.num_bands;
+    std::vector<double> edges;
+    if (edges_hz != nullptr || count != 0) {   // (NULL, 0: the defaults)
+        if (edges_hz == nullptr || count != B - 1)
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_set_band_edges: give num_bands - 1 = " + std::to_string(B - 1) +
+                                                          " inner edges in Hz, or NULL and 0 for the defaults");
+        for (int32_t i = 0; i < count; ++i) {
+            if (!std::isfinite(edges_hz[i]) || (i > 0 && !(edges_hz[i] > edges_hz[i - 1])))
+                return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_set_band_edges: the edges must be finite and strictly ascending");
+            edges.push_back((double)edges_hz[i]);
+        }
+        const int rc = check_band_edges(ctx, edges.data(), "fs_set_band_edges");
+        if (rc) return rc;
+    }
+    if (ctx->device_ok) {
+        const int rc = fs_synchronize(ctx);
+        if (rc) return rc;
+        if (ctx->d_carrier) { FS_HIP(ctx, hipFree(ctx->d_carrier)); ctx->d_carrier = nullptr; }
+    }
+    ctx->band_edges = edges;
     return FS_OK;
 }
 

@@ -58,6 +58,111 @@ static int acquire_recon_tab(fs_context* ctx, unsigned* slot_out) {
     return FS_OK;
 }
 
+// ---- FS_FLAG_SPECTRAL_IR: the band carriers (definition: DESIGN.md section 8, "Spectral impulse responses") ----
+static int carrier_log(const fs_context* ctx) {   // K = 2^n = the smallest power of two >= N
+    int n = 0;
+    while (n < 31 && (1ll << n) < (long long)ctx->num_samples) ++n;
+    return n;
+}
+// bins [lo[b], lo[b+1]) of K/2 belong to band b: the first bin whose frequency k fs / K (double) reaches the band's lower edge
+static bool band_bins(const fs_context* ctx, const double* inner, CarrierBands* out) {
+    const int B = ctx->cfg.num_bands, n = carrier_log(ctx);
+    const long long K = 1ll << n, half = K / 2;
+    const double fs = (double)ctx->cfg.sample_rate;
+    out->lo[0] = 1; out->lo[B] = (int32_t)half;
+    for (int b = 1; b < B; ++b) {
+        const double edge = inner[b - 1];
+        if (!(edge > 0.0) || !(edge < fs / 2.0)) return false;
+        long long k = (long long)std::ceil(edge * (double)K / fs);
+        while (k > 0 && (double)(k - 1) * fs / (double)K >= edge) --k;
+        while ((double)k * fs / (double)K < edge) ++k;
+        out->lo[b] = (int32_t)std::min(std::max(k, 1ll), half);
+    }
+    for (int b = 0; b < B; ++b)
+        if (out->lo[b + 1] <= out->lo[b]) return false;   // every band at least one bin (also: strictly ascending edges)
+    return true;
+}
+static std::vector<double> effective_edges(const fs_context* ctx) {
+    if (!ctx->band_edges.empty()) return ctx->band_edges;
+    std::vector<double> e;
+    for (int b = 1; b < ctx->cfg.num_bands; ++b) e.push_back(125.0 * std::pow(2.0, (double)b - 0.5));   // octave bands centred at 125, 250, ... Hz
+    return e;
+}
+
+int check_band_edges(fs_context* ctx, const double* edges, const char* what) {
+    if (carrier_log(ctx) > kCarrierMaxLog)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, std::string(what) + ": the carriers of " + std::to_string(ctx->num_samples) +
+                                                      "-sample impulse responses exceed the largest FFT (2^24 points); fs_set_band_edges cannot change that");
+    const std::vector<double> def = effective_edges(ctx);
+    CarrierBands cb{};
+    if (!band_bins(ctx, edges ? edges : def.data(), &cb))
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, std::string(what) + ": every band edge must lie in (0, sample_rate / 2), ascending, and every "
+                                                      "band must hold at least one FFT bin of " + std::to_string(ctx->cfg.sample_rate) + " / " +
+                                                      std::to_string(1ll << carrier_log(ctx)) + " Hz" +
+                                                      (edges || !ctx->band_edges.empty() ? std::string() :
+                                                       std::string(" — the default octave edges do not fit this sample rate: give edges with fs_set_band_edges")));
+    return FS_OK;
+}
+
+int check_spectral(fs_context* ctx, const fs_params* p) {
+    if (!(p->flags & FS_FLAG_SPECTRAL_IR)) return FS_OK;
+    return check_band_edges(ctx, nullptr, "FS_FLAG_SPECTRAL_IR");
+}
+
+// The build: on the compute stream, waited for here (once per context and band-edge setting; the work buffers are freed behind it)
+static int build_carriers(fs_context* ctx) {
+    const int B = ctx->cfg.num_bands, n = carrier_log(ctx), N = ctx->num_samples, ld = carrier_stride(N);
+    const size_t K = (size_t)1 << n;
+    const std::vector<double> edges = effective_edges(ctx);
+    CarrierBands bands{};
+    if (!band_bins(ctx, edges.data(), &bands)) return check_band_edges(ctx, nullptr, "FS_FLAG_SPECTRAL_IR");
+    std::vector<float2> w(std::max<size_t>(K / 2, 1));   // W[k] = exp(-2 pi i k / K) in double
+    for (size_t k = 0; k < K / 2; ++k) {
+        const double a = -2.0 * 3.14159265358979323846 * (double)k / (double)K;
+        w[k] = make_float2((float)std::cos(a), (float)std::sin(a));
+    }
+    if (K < 2) w[0] = make_float2(1.f, 0.f);
+    float2 *X = nullptr, *y = nullptr, *W = nullptr;
+    float *zeros = nullptr, *out = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipError_t e = hipSetDevice(ctx->cfg.device);
+    if (e == hipSuccess) e = hipMalloc((void**)&out, sizeof(float) * (size_t)B * (size_t)ld);
+    if (e == hipSuccess) e = hipMalloc((void**)&X, sizeof(float2) * (size_t)B * K);
+    if (e == hipSuccess) e = hipMalloc((void**)&y, sizeof(float2) * (size_t)B * K);
+    if (e == hipSuccess) e = hipMalloc((void**)&W, sizeof(float2) * w.size());
+    if (e == hipSuccess) e = hipMalloc((void**)&zeros, sizeof(float) * (K / 2 + 1));
+    if (e == hipSuccess) e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipMemcpyAsync(W, w.data(), sizeof(float2) * w.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(zeros, 0, sizeof(float) * (K / 2 + 1), ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], ctx->stream);
+    if (e == hipSuccess) {
+        launch_build_carriers(B, n, N, ld, bands, X, y, W, zeros, out, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (w is a local; the work buffers go next)
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
+    for (void* q : {(void*)X, (void*)y, (void*)W, (void*)zeros}) if (q) (void)hipFree(q);
+    if (e != hipSuccess) {
+        if (out) (void)hipFree(out);
+        return ctx->hip_fail(e, "FS_FLAG_SPECTRAL_IR: building the band carriers");
+    }
+    ctx->d_carrier = out;
+    ctx->carrier_build_ms = ms;
+    return FS_OK;
+}
+
+int carrier_for(fs_context* ctx, const fs_params* p, const float** out) {
+    *out = nullptr;
+    if (!(p->flags & FS_FLAG_SPECTRAL_IR)) return FS_OK;
+    if (!ctx->d_carrier) { const int rc = build_carriers(ctx); if (rc) return rc; }
+    *out = ctx->d_carrier;
+    return FS_OK;
+}
+
 static int spb_of(const fs_context* ctx, const fs_params& p) {
     return p.samples_per_bin > 0 ? p.samples_per_bin : (int)std::ceil(ctx->cfg.bin_duration * (float)ctx->cfg.sample_rate);   // FSAC.cpp:324
 }
@@ -85,12 +190,19 @@ int owed_prepare(fs_context* ctx, FrameParts& fp, OwedLaunch& ol) {
         const int br = ir_ring_backpressure(ctx, s, more);
         if (br) { ol.owed.clear(); return br; }
     }
+    const float* carrier = nullptr;   // (built before any mutex is taken: the first build waits for the GPU)
+    for (const fs_context::ReconOwed& o : ol.owed) {
+        if (carrier || !(o.p.flags & FS_FLAG_SPECTRAL_IR)) continue;
+        const int cr = carrier_for(ctx, &o.p, &carrier);
+        if (cr) { ol.owed.clear(); return cr; }
+    }
     { const int ar = acquire_recon_tab(ctx, &ol.tab_slot); if (ar) { ol.owed.clear(); return ar; } }
     ReconItem* tab = ctx->h_recon_tab + (size_t)ol.tab_slot * fs_context::kReconTabItems;
     auto bail = [&](int rc) { ol.owed.clear(); ol.seq.clear(); ol.newest.clear(); ol.locks.clear(); fp.num_recon = 0; return rc; };
 #define FS_OWED_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bail(ctx->hip_fail(e_, #call)); } while (0)
     for (Source* s : distinct) ol.locks.emplace_back(s->ir_mu);
     fp.num_recon = 0; fp.recon_tab = tab; fp.recon_B = B; fp.recon_nb = ctx->num_bins; fp.recon_samples = ctx->num_samples;
+    fp.recon_carrier = carrier;   // (nullptr unless some item is spectral)
     ol.pub = next_pub_word(ctx);
     fp.pub = ol.pub;
     for (size_t i = 0; i < ol.owed.size(); ++i) {
@@ -108,7 +220,8 @@ int owed_prepare(fs_context* ctx, FrameParts& fp, OwedLaunch& ol) {
         ol.seq.push_back(seq); ol.newest.push_back(later ? 0 : 1);
         ReconItem& r = tab[fp.num_recon++];
         r.energy = s->d_energy[o.cur]; r.ir_bands = later ? nullptr : s->d_ir_bands; r.ir_mono = later ? nullptr : s->d_ir_mono;
-        r.host = s->h_ir[slot]; r.mask = slot_mask_ptr(ctx, s, slot); r.spb = spb_of(ctx, o.p); r.pad = 0;
+        r.host = s->h_ir[slot]; r.mask = slot_mask_ptr(ctx, s, slot); r.spb = spb_of(ctx, o.p);
+        r.spectral = (o.p.flags & FS_FLAG_SPECTRAL_IR) ? 1 : 0;
     }
 #undef FS_OWED_HIP
     ctx->recon_owed.erase(ctx->recon_owed.begin(), ctx->recon_owed.begin() + (long)take);
@@ -121,7 +234,7 @@ int owed_publish(fs_context* ctx, OwedLaunch& ol, bool launched_fused) {
     const int B = ctx->cfg.num_bands;
     if (!launched_fused) {   // no fused form for this launch: the same table through the batch kernel, on the compute stream
         launch_reconstruct_batch(ctx->h_recon_tab + (size_t)ol.tab_slot * fs_context::kReconTabItems, (int)ol.owed.size(), B, ctx->num_bins,
-                                 ctx->num_samples, ctx->stream, ol.pub);
+                                 ctx->num_samples, ctx->stream, ol.pub, ctx->d_carrier);
         FS_HIP(ctx, hipGetLastError());
     }
     ctx->recon_tab_word[ol.tab_slot] = ol.pub.id;          // the slot's reader: this launch
@@ -178,6 +291,8 @@ int reconstruct_now(fs_context* ctx, Source* s, const fs_params* p) {
     if (ctx->cfg.world_size > 1 && !s->reduced && !s->handed_off)
         return ctx->fail(FS_ERR_COMM, "world_size > 1: the energy buffer holds this rank's partial sums only — attach a "
                                       "communicator (fs_comm_init) or reduce it behind fs_energy_handoff before reconstructing");
+    const float* carrier = nullptr;
+    { const int cr = carrier_for(ctx, p, &carrier); if (cr) return cr; }
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const int B = ctx->cfg.num_bands;
     int spb = p->samples_per_bin > 0 ? p->samples_per_bin
@@ -214,7 +329,7 @@ int reconstruct_now(fs_context* ctx, Source* s, const fs_params* p) {
         // deterministic mode: the collective summed the fixed-point histogram; round it to fp32 once, now
         if (s->cur_fixed && !s->reduced) launch_fixed_to_energy(s->d_fixed[s->cur], s->energy(), B * ctx->num_bins, tail);
         launch_reconstruct(s->energy(), B, ctx->num_bins, ctx->cfg.sample_rate, ctx->num_samples, spb, s->d_ir_bands,
-                           s->d_ir_mono, tail);
+                           s->d_ir_mono, tail, carrier);
         FS_HIP(ctx, hipGetLastError());
         FS_HIP(ctx, hipEventRecord(s->ev_rec[s->cur], tail));
         s->rec_recorded[s->cur] = true; s->rec_batch[s->cur] = 0; s->rec_on_compute[s->cur] = false;
@@ -265,6 +380,8 @@ int reconstruct_batch(fs_context* ctx, Source* const* srcs, int count, const fs_
         for (int i = 0; i < count; ++i) { const int rc = reconstruct_now(ctx, srcs[i], p); if (rc) return rc; }
         return FS_OK;
     }
+    const float* carrier = nullptr;
+    { const int cr = carrier_for(ctx, p, &carrier); if (cr) return cr; }
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const int B = ctx->cfg.num_bands;
     const int spb = p->samples_per_bin > 0 ? p->samples_per_bin : (int)std::ceil(ctx->cfg.bin_duration * (float)ctx->cfg.sample_rate);  // FSAC.cpp:324
@@ -303,9 +420,9 @@ int reconstruct_batch(fs_context* ctx, Source* const* srcs, int count, const fs_
             const int slot = (int)(seq % kIrRing);
             tab[i].energy = s->energy(); tab[i].ir_bands = s->d_ir_bands; tab[i].ir_mono = s->d_ir_mono; tab[i].host = s->h_ir[slot];
             tab[i].mask = slot_mask_ptr(ctx, s, slot);
-            tab[i].spb = spb; tab[i].pad = 0;
+            tab[i].spb = spb; tab[i].spectral = carrier != nullptr ? 1 : 0;
         }
-        launch_reconstruct_batch(tab, n, B, ctx->num_bins, ctx->num_samples, tail, pub);
+        launch_reconstruct_batch(tab, n, B, ctx->num_bins, ctx->num_samples, tail, pub, carrier);
         FS_HIP(ctx, hipGetLastError());
         if (on_compute) {
             ctx->pub_issued = pub.id;

@@ -207,6 +207,11 @@ struct fs_context {
     size_t fft_stage_floats = 0;
     hipGraphExec_t fft_graph = nullptr;
     int fft_graph_n = -1, fft_graph_l = -1;
+    // FS_FLAG_SPECTRAL_IR: the band edges (fs_set_band_edges: the B - 1 inner ones, ascending; empty = the defaults) and the
+    // carriers built from them (fs_capi_publish.cpp: carrier_for — lazily, before the first spectral reconstruct)
+    std::vector<double> band_edges;
+    float* d_carrier = nullptr;          // [B][carrier_stride(num_samples)] fp32
+    float carrier_build_ms = 0.0f;       // device time of the last build (HIP events)
     HostBVH bvh;
 
     float listener[3] = {0, 0, 0};
@@ -437,6 +442,12 @@ int ensure_state(fs_context* ctx, uint32_t n_local, int levels, bool unbounded, 
 int auto_rays_per_wave(unsigned long long lanes, int depth, unsigned long long waves = 0);
 int auto_pairs_per_wave(unsigned long long pairs);
 int check_params(fs_context* ctx, const fs_params* p);
+// FS_FLAG_SPECTRAL_IR: can this context build its carriers (K within the FFT, every band at least one bin under Nyquist)?
+// edges: the B - 1 inner edges to check (nullptr: the context's own, or the defaults).  FS_OK, or the failure reported.
+int check_band_edges(fs_context* ctx, const double* edges, const char* what);
+int check_spectral(fs_context* ctx, const fs_params* p);
+// the carrier set a reconstruct with these params uses: nullptr without FS_FLAG_SPECTRAL_IR; built (and waited for) on first use
+int carrier_for(fs_context* ctx, const fs_params* p, const float** out);
 
 // ---- fs_capi_scene.cpp --------------------------------------------------------------------------------------------
 // fs_scene_commit_progressive: swap the finished background tree in; drop / wait for a background build

@@ -12,6 +12,7 @@
 // launch); wider spans are one global pass each.  For the plugin's block sizes (N <= 65536) that is
 // 1 + 5 + 1 launches forward and the same inverse, the three inverse transforms batched over blockIdx.y.
 // Twiddles come from a table computed in double precision on the host (W[k] = exp(-2 pi i k / N), k < N/2).
+// The inverse passes also build the band carriers of FS_FLAG_SPECTRAL_IR (launch_build_carriers, at the end of the file).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -151,6 +152,46 @@ __global__ __launch_bounds__(kFftBlock) void fft_dit_global(float2* __restrict__
     }
 }
 
+// ---- FS_FLAG_SPECTRAL_IR: the band carriers (launch_build_carriers).  blockIdx.y = band ----
+// splitmix64 (Steele, Lea, Flood 2014): the bin's phase from its index alone
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// the band's one-sided spectrum in bit-reversed order: position p holds bin k = brev(p); bins [lo_b, lo_{b+1}) of the band
+// get exp(i phi_k), phi_k = 2 pi (splitmix64(kCarrierSeed + k) >> 40) 2^-24 (cos / sin in double), every other bin 0
+__global__ __launch_bounds__(kFftBlock) void carrier_spectrum(float2* __restrict__ X, int n, CarrierBands bands) {
+    const uint32_t p = blockIdx.x * kFftBlock + threadIdx.x;
+    if (p >= (1u << n)) return;
+    const int b = blockIdx.y;
+    const uint32_t k = __brev(p) >> (32 - n);
+    float2 v = make_float2(0.0f, 0.0f);
+    if ((int)k >= bands.lo[b] && (int)k < bands.lo[b + 1]) {
+        const double turns = (double)(uint32_t)(splitmix64(kCarrierSeed + k) >> 40) * 0x1p-24;   // (exact)
+        double sn, cs;
+        sincospi(2.0 * turns, &sn, &cs);
+        v = make_float2((float)cs, (float)sn);
+    }
+    X[((size_t)b << n) + p] = v;
+}
+// c_b = r_b sqrt(N / sum_{n<N} r_b^2), in place (the sum in double, one workgroup per band); the row's padding up to ld is zeroed
+__global__ __launch_bounds__(kFftBlock) void carrier_normalise(float* __restrict__ c, int N, int ld) {
+    __shared__ double s_sum[kFftBlock];
+    float* row = c + (size_t)blockIdx.x * ld;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < N; i += kFftBlock) acc += (double)row[i] * (double)row[i];
+    s_sum[threadIdx.x] = acc;
+    for (int w = kFftBlock / 2; w > 0; w >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < w) s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+    }
+    __syncthreads();
+    const float g = s_sum[0] > 0.0 ? (float)sqrt((double)N / s_sum[0]) : 0.0f;
+    for (int i = threadIdx.x; i < ld; i += kFftBlock) row[i] = i < N ? row[i] * g : 0.0f;
+}
+
 }  // namespace
 
 // x: [N] complex work buffer, y: [3][N], W: [max(N/2,1)] twiddles, resp: absorption | transmission | scattering
@@ -173,6 +214,31 @@ void launch_apply_material_fd(const float* in, int L, int n, float2* x, float2* 
                        resp + 2 * bins, W, n, c, L, out, scale);
     for (int ls = c; ls < n; ++ls)
         hipLaunchKernelGGL(fft_dit_global, dim3(half_blocks, 3), dim3(kFftBlock), 0, s, y, W, n, ls, L, out, scale);
+}
+
+}  // namespace fs
+
+namespace fs {
+
+// The band carriers of FS_FLAG_SPECTRAL_IR: r_b[t] = sum_{k in band b} cos(2 pi k t / K + phi_k), t < N, K = 2^n >= N — the real
+// part of the inverse DFT of the band's unit-magnitude random-phase one-sided spectrum — through the material filter's own inverse
+// passes (gains all 1: alpha = sigma = 0 from `zeros`; which = 0 per band for the LDS pass, whose input is one array; the global
+// passes batched over the bands on blockIdx.y), then scaled to a mean square of 1 over the IR.  X, y: [B][K] complex work buffers,
+// W: [max(K/2,1)] twiddles (exp(-2 pi i k / K), double precision on the host), zeros: [K/2 + 1], out: [B][ld] (ld >= N, ld <= K or
+// the row is zero-padded).
+void launch_build_carriers(int B, int n, int N, int ld, const CarrierBands& bands, float2* X, float2* y, const float2* W,
+                           const float* zeros, float* out, hipStream_t s) {
+    const int K = 1 << n;
+    const int c = n < kFftChunkLog ? n : kFftChunkLog;
+    const size_t lds = sizeof(float2) << c;
+    hipLaunchKernelGGL(carrier_spectrum, dim3((unsigned)((K + kFftBlock - 1) / kFftBlock), (unsigned)B), dim3(kFftBlock), 0, s, X, n, bands);
+    for (int b = 0; b < B; ++b)
+        hipLaunchKernelGGL(fft_dit_local, dim3(1u << (n - c), 1), dim3(kFftBlock), lds, s, X + ((size_t)b << n), y + ((size_t)b << n),
+                           zeros, zeros, zeros, W, n, c, ld, out + (size_t)b * ld, 1.0f);
+    const unsigned half_blocks = (unsigned)(((K >> 1) + kFftBlock - 1) / kFftBlock);
+    for (int ls = c; ls < n; ++ls)
+        hipLaunchKernelGGL(fft_dit_global, dim3(half_blocks, (unsigned)B), dim3(kFftBlock), 0, s, y, W, n, ls, ld, out, 1.0f);
+    hipLaunchKernelGGL(carrier_normalise, dim3((unsigned)B), dim3(kFftBlock), 0, s, out, N, ld);
 }
 
 }  // namespace fs

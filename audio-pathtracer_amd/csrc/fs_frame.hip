@@ -62,6 +62,7 @@ struct FrameArgs {
     int recon_B, recon_nb, recon_samples; uint32_t recon_cb;
     PublishWord pub;
     uint32_t connect_first;   // the connect part takes the FIRST workgroups of the grid (see FS_LAUNCH_FRAME)
+    const float* recon_carrier;   // FS_FLAG_SPECTRAL_IR: the carrier set of the items marked spectral (the SPECTRAL instantiation)
 };
 static_assert(sizeof(FrameArgs) + sizeof(DeviceScene) <= 4096, "kernel arguments are limited to 4 KB");
 
@@ -70,7 +71,9 @@ static_assert(sizeof(FrameArgs) + sizeof(DeviceScene) <= 4096, "kernel arguments
 #ifndef FS_FRAME_MIN_WAVES
 #define FS_FRAME_MIN_WAVES 4
 #endif
-template <int B, bool BATCH>
+// SPECTRAL: some reconstruct item has a carrier set (FS_FLAG_SPECTRAL_IR): its channel row is reconstruct_spectral_row, as in the
+// reconstruct-only kernels.  An instantiation of its own: the default ones keep their registers, LDS and code.
+template <int B, bool BATCH, bool SPECTRAL>
 __global__ __launch_bounds__(kBlock, FS_FRAME_MIN_WAVES) void frame_kernel(DeviceScene sc, FrameArgs a) {
     uint32_t b = blockIdx.x;
     if (a.connect_first) {
@@ -110,23 +113,34 @@ __global__ __launch_bounds__(kBlock, FS_FRAME_MIN_WAVES) void frame_kernel(Devic
         const uint32_t item = rb / per_item, in_item = rb - item * per_item;
         const ReconItem it = a.recon_tab[item];
         float* const s_amp = reinterpret_cast<float*>(s_dyn_r);
+        if (SPECTRAL && in_item / a.recon_cb == (uint32_t)a.recon_B && it.spectral) {
+            reconstruct_spectral_row((int)(in_item % a.recon_cb), it.energy, a.recon_B, a.recon_nb, a.recon_samples, it.spb, it.ir_bands,
+                                     it.ir_mono, s_amp, it.host, it.mask, a.recon_carrier);
+            publish_arrive(a.pub.tickets, (uint32_t)a.num_recon * per_item, a.pub.host_word, a.pub.id);
+            return;
+        }
         reconstruct_body((int)(in_item / a.recon_cb), (int)(in_item % a.recon_cb), it.energy, a.recon_B, a.recon_nb, a.recon_samples, it.spb,
                          it.ir_bands, it.ir_mono, s_amp, it.host, s_amp + a.recon_nb, it.mask);
         publish_arrive(a.pub.tickets, (uint32_t)a.num_recon * per_item, a.pub.host_word, a.pub.id);
     }
 }
 
-template <int B>
+template <int B, bool SPECTRAL>
 void launch_frame_t(const DeviceScene& sc_in, uint32_t blocks, size_t lds, const FrameArgs& a, bool batch, hipStream_t s) {
     DeviceScene sc = sc_in;
     if (!attach_deep(sc, blocks)) return;
     if (batch) {
-        allow_lds(frame_kernel<B, true>, lds);
-        hipLaunchKernelGGL((frame_kernel<B, true>), dim3(blocks), dim3(kBlock), lds, s, sc, a);
+        allow_lds(frame_kernel<B, true, SPECTRAL>, lds);
+        hipLaunchKernelGGL((frame_kernel<B, true, SPECTRAL>), dim3(blocks), dim3(kBlock), lds, s, sc, a);
     } else {
-        allow_lds(frame_kernel<B, false>, lds);
-        hipLaunchKernelGGL((frame_kernel<B, false>), dim3(blocks), dim3(kBlock), lds, s, sc, a);
+        allow_lds(frame_kernel<B, false, SPECTRAL>, lds);
+        hipLaunchKernelGGL((frame_kernel<B, false, SPECTRAL>), dim3(blocks), dim3(kBlock), lds, s, sc, a);
     }
+}
+template <int B>
+void launch_frame_b(const DeviceScene& sc, uint32_t blocks, size_t lds, const FrameArgs& a, bool batch, bool spectral, hipStream_t s) {
+    if (spectral) launch_frame_t<B, true>(sc, blocks, lds, a, batch, s);
+    else launch_frame_t<B, false>(sc, blocks, lds, a, batch, s);
 }
 
 }  // namespace
@@ -195,15 +209,19 @@ bool FS_LAUNCH_FRAME(int B, const DeviceScene& sc, const FrameParts& f, hipStrea
         a.recon_cb = (chunks + kBlock - 1) / kBlock;
         blocks += (uint32_t)f.num_recon * (uint32_t)(f.recon_B + 1) * a.recon_cb;
         lds = std::max(lds, sizeof(float) * ((size_t)f.recon_nb + (size_t)kBlock * (kChunk + 1)));   // the amplitudes | the block's samples staged for 16-byte stores
+        a.recon_carrier = f.recon_carrier;
+        if (f.recon_carrier)   // reconstruct_spectral_row: reconstruct_body_fast's layout
+            lds = std::max(lds, sizeof(float) * ((size_t)f.recon_nb + (size_t)kBlock * kChunk + kWarm + (size_t)kBlock * (kChunk + 1)));
     }
     if (blocks == 0) return false;
     if (blocks_only) { *blocks_only = blocks; return true; }
     const bool batch = f.has_connect && f.energy_tab;
+    const bool spectral = f.num_recon > 0 && f.recon_carrier != nullptr;
     switch (B) {   // the band counts in use; 0 = kp.num_bands at run time (fs_connect.hip)
-        case 1: launch_frame_t<1>(sc, blocks, lds, a, batch, s); break;
-        case 4: launch_frame_t<4>(sc, blocks, lds, a, batch, s); break;
-        case 8: launch_frame_t<8>(sc, blocks, lds, a, batch, s); break;
-        default: launch_frame_t<0>(sc, blocks, lds, a, batch, s); break;
+        case 1: launch_frame_b<1>(sc, blocks, lds, a, batch, spectral, s); break;
+        case 4: launch_frame_b<4>(sc, blocks, lds, a, batch, spectral, s); break;
+        case 8: launch_frame_b<8>(sc, blocks, lds, a, batch, spectral, s); break;
+        default: launch_frame_b<0>(sc, blocks, lds, a, batch, spectral, s); break;
     }
     return true;
 }

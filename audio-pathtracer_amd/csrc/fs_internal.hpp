@@ -322,6 +322,7 @@ struct FrameParts {
     int num_recon = 0;
     const struct ReconItem* recon_tab = nullptr;
     int recon_B = 0, recon_nb = 0, recon_samples = 0;
+    const float* recon_carrier = nullptr;   // the context's carriers if some item is spectral: the fused kernel's spectral instantiation
     // the publish of those host slots (fs_device.hpp: publish_arrive): the ticket cell, the pinned host word, this launch's id (tickets == nullptr: by an event)
     PublishWord pub;
 };
@@ -346,16 +347,21 @@ void launch_connect(int B, const DeviceScene& sc, const KParams& kp, const Subpa
 void launch_connect_all(int B, const DeviceScene& sc, const KParams& kp, const SubpathState& st, float* energy,
                         unsigned long long* fixed, unsigned* queue_head, hipStream_t s);
 void launch_fixed_to_energy(const unsigned long long* fixed, float* energy, int words, hipStream_t s);
+// carrier != nullptr (FS_FLAG_SPECTRAL_IR): row B is the spectral channel from the [B][carrier_stride] carrier set (fs_device.hpp:
+// reconstruct_spectral_row); the band rows are the same either way
 void launch_reconstruct(const float* energy, int B, int num_bins, int sample_rate, int num_samples, int spb,
-                        float* ir_bands, float* ir_mono, hipStream_t s);
+                        float* ir_bands, float* ir_mono, hipStream_t s, const float* carrier = nullptr);
 // ReconstructImpulseResponse of MANY sources as one launch (fs_reconstruct_impulse_response_batch_async): a table of items in
 // pinned host memory (read by the kernel as it stands); host != nullptr: the channel view is also written straight into
 // that pinned host buffer (the publish: 16-byte stores, a block's 4 096 samples staged in LDS) — no copy command per source.
 // mask (optional): the device word that says which 4 096-sample blocks of the host slot may hold non-zero samples (bit b = block b):
 // a block whose samples are all exactly zero is not written across the bus again when the slot's block is known to be zero.
-struct ReconItem { const float* energy; float* ir_bands; float* ir_mono; float* host; uint32_t* mask; int32_t spb; int32_t pad; };
+// spectral != 0 (FS_FLAG_SPECTRAL_IR): the item's channel row is the spectral IR from the launch's carrier set; 0 = the band mean
+struct ReconItem { const float* energy; float* ir_bands; float* ir_mono; float* host; uint32_t* mask; int32_t spb; int32_t spectral; };
 // pub.tickets != nullptr: the launch announces its own completion in the context's pinned host word (publish_arrive)
-void launch_reconstruct_batch(const ReconItem* table, int count, int B, int num_bins, int num_samples, hipStream_t s, const PublishWord& pub = PublishWord());
+// carrier: the context's carrier set (FS_FLAG_SPECTRAL_IR) for the items marked spectral (nullptr: none is)
+void launch_reconstruct_batch(const ReconItem* table, int count, int B, int num_bins, int num_samples, hipStream_t s, const PublishWord& pub = PublishWord(),
+                              const float* carrier = nullptr);
 void launch_trace_rays(const DeviceScene& sc, const float* o, const float* d, const float* tmax, int N, int any_hit,
                        int32_t* hit, float* t, int32_t* tri, float* normal, hipStream_t s);
 // rays_per_wave < 64: sparse waves whose other lanes help with every closest-hit query; 64 = one ray per lane
@@ -409,5 +415,15 @@ bool launch_device_build(const float* xyz, const uint16_t* mat, const uint32_t* 
 constexpr int kFftChunkLog = 11;     // FFT stages with spans below 2^11 points run inside LDS
 void launch_apply_material_fd(const float* in, int L, int n, float2* x, float2* y, const float2* W, const float* resp,
                               float* out, hipStream_t s);
+// FS_FLAG_SPECTRAL_IR (fs_fft.hip): the per-band noise carriers the spectral channel row is built from.  Bin k in [1, K/2) of a
+// K = 2^n point spectrum belongs to band b when lo[b] <= k < lo[b + 1] (host-side, from the band edges in double); its phase is
+// 2 pi (splitmix64(kCarrierSeed + k) >> 40) 2^-24.  out: [B][ld] fp32, ld = carrier_stride(N) (below)
+constexpr uint64_t kCarrierSeed = 0x5EED;
+constexpr int kCarrierMaxLog = 24;   // K <= 2^24 (the material filter's largest transform)
+struct CarrierBands { int32_t lo[FS_MAX_BANDS + 1]; };
+// a carrier row's length: N rounded up to 64 samples (a whole number of the reconstruct's chunks: 16-byte loads of a thread's own)
+__host__ __device__ constexpr int carrier_stride(int num_samples) { return (num_samples + 63) / 64 * 64; }
+void launch_build_carriers(int B, int n, int N, int ld, const CarrierBands& bands, float2* X, float2* y, const float2* W,
+                           const float* zeros, float* out, hipStream_t s);
 
 }  // namespace fs

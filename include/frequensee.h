@@ -45,7 +45,7 @@
  *             fs_scene_refine_wait fs_scene_update_triangles fs_scene_refit
  *             fs_compute_energy_response_async fs_compute_energy_response_batch_async
  *             fs_reconstruct_impulse_response_async fs_reconstruct_impulse_response_batch_async fs_synchronize fs_submit
- *             fs_set_pipelining fs_set_walk_stages fs_set_frames_per_launch
+ *             fs_set_pipelining fs_set_walk_stages fs_set_frames_per_launch fs_set_band_edges
  *             fs_energy_device_ptr fs_energy_handoff fs_shard_range fs_comm_unique_id fs_comm_init fs_comm_attach
  *             fs_comm_enable_oneshot fs_comm_detach fs_comm_info fs_peers_init fs_peers_detach fs_gather_energy fs_gather_energy_async
  *             fs_copy_band_impulse_response fs_set_impulse_response fs_trace_rays
@@ -130,6 +130,15 @@ enum {
                                              * starts from the float-rounded node as before.  Bit-for-bit the oracle's double-position
                                              * build (oracle/Makefile target dpos).  Costs a few % of the walk; such frames are never
                                              * held by fs_set_pipelining.  Not combinable with the lobe / all-connections modes. */
+#define FS_FLAG_SPECTRAL_IR 512u           /* read by the RECONSTRUCT calls (fs_reconstruct_impulse_response[_async], _batch_async,
+                                             * fs_update_sources): the channel view becomes a broadband IR whose spectrum follows the
+                                             * per-band energies, y[n] = (1/sqrt(B)) sum_b env_b[n] c_b[n] — env_b = band row b (unchanged,
+                                             * fs_copy_band_impulse_response), c_b = band-limited noise of unit mean square: the real part
+                                             * of the inverse FFT (K = next power of two >= fs_num_samples) of the band's bins with unit
+                                             * magnitude and phase 2 pi (splitmix64(0x5EED + k) >> 40) 2^-24.  Bands: the crossovers of
+                                             * fs_set_band_edges, by default octaves centred at 125, 250, ... Hz (edges 125 * 2^(b - 0.5)).
+                                             * Every consumer of the channel view (ring, reverb, export) gets it.  Rejected when the
+                                             * edges do not fit under sample_rate / 2.  The carriers are built once per context. */
 #define FS_FLAG_DETERMINISTIC 8u            /* deposits are summed as 64-bit integers of 2^-40 energy quanta: the
                                              * histogram no longer depends on the order of the atomics, so it is bit-identical
                                              * from run to run and for every split of the pairs over GPUs (sum-reduce the u64
@@ -411,6 +420,10 @@ int fs_reconstruct_impulse_response_async(fs_context* ctx, fs_source src, const 
  * stream wait, a kernel, a copy and three event records (32 sources: 2.8 ms per tick against 0.9 ms). */
 int fs_reconstruct_impulse_response_batch_async(fs_context* ctx, const fs_source* sources, int32_t count, const fs_params* params);
 int fs_synchronize(fs_context* ctx);
+/* FS_FLAG_SPECTRAL_IR's crossovers: count == num_bands - 1 inner edges in Hz, strictly ascending, in (0, sample_rate / 2), every
+ * band at least one FFT bin wide (sample_rate / K Hz); edges_hz == NULL and count == 0 restore the defaults.  Drains the context
+ * (as fs_synchronize) and rebuilds the carriers at the next spectral reconstruct. */
+int fs_set_band_edges(fs_context* ctx, const float* edges_hz, int32_t count);
 /* UpdateSources (ARTS.cpp:100-126) as the game thread runs it: one UpdateSource (:128-195) for every listed source — trace,
  * deposit, reconstruct — and every IR is in its published host buffer when the call returns.  = the batched compute call +
  * the batched reconstruct + fs_synchronize, with the reconstructs riding on the compute stream (nothing else to overlap
