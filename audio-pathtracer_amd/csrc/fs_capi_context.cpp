@@ -105,8 +105,8 @@ bool slot_published(fs_context* ctx, Source* s, int slot) {
 }
 // ---- zero-block masks of the host ring slots (fs_context::d_slot_masks) -----------------------------------------------------
 static bool slot_masks_usable(const fs_context* ctx, const Source* s) {
-    // (a mask word has 32 bits: one per block of kBlock * kChunk = 4 096 samples)
-    return ctx->d_slot_masks != nullptr && s->mask_index >= 0 && s->mask_index < kMaxMaskSources && ctx->num_samples <= 32 * 4096;
+    // (a mask word has 32 bits: one per reconstruct block of kReconBlockSamples)
+    return ctx->d_slot_masks != nullptr && s->mask_index >= 0 && s->mask_index < kMaxMaskSources && ctx->num_samples <= 32 * kReconBlockSamples;
 }
 uint32_t* slot_mask_ptr(const fs_context* ctx, const Source* s, int slot) {
     return slot_masks_usable(ctx, s) ? ctx->d_slot_masks + (size_t)s->mask_index * kIrRing + (size_t)slot : nullptr;

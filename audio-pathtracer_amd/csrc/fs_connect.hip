@@ -1,6 +1,7 @@
 // fs_connect.hip — ConnectSubpaths + EvaluatePath + deposit kernels (AudioRayTracingSubsystem.cpp:235-277, 360-420;
 // FrequenSeeAudioComponent.h:87-91), the all-prefix variant (draft :518-546, row f3) and the fixed-point rounding pass.
-#include "fs_device.hpp"
+#include "fs_dev_connect.hpp"
+#include "fs_launch.hpp"
 
 namespace fs {
 namespace {
@@ -221,9 +222,10 @@ __global__ __launch_bounds__(kBlock) void fixed_to_energy_kernel(const unsigned 
     if (i < words) energy[i] = (float)((double)fixed[i] * (1.0 / kFixedScale));
 }
 
-#ifndef FS_CONNECT_AHEAD_N
-#define FS_CONNECT_AHEAD_N 4
-#endif
+// segment records a lane requests at once when it evaluates an uncapped walk's path alone (connect_body's AHEAD; eight in
+// flight measured too: DESIGN.md section 8, profiles/r05_connect_records_ahead.jsonl)
+constexpr int kConnectAhead = 4;
+
 template <int B>
 void launch_connect_t(const DeviceScene& sc_in, const KParams& kp, const SubpathState& st, float* energy,
                       unsigned long long* fixed, unsigned* queue_head, int pairs_per_wave, float* const* energy_tab,
@@ -259,16 +261,16 @@ void launch_connect_t(const DeviceScene& sc_in, const KParams& kp, const Subpath
         return;
     }
     // uncapped walks (the waited-for frames; the pipelined ones connect inside the fused launch): paths of up to a few hundred
-    // segments, evaluated by ONE lane when the wave is dense — four records in flight (connect_body's AHEAD)
+    // segments, evaluated by ONE lane when the wave is dense — kConnectAhead records in flight (connect_body's AHEAD)
     static const int ahead = std::getenv("FS_CONNECT_AHEAD") ? std::atoi(std::getenv("FS_CONNECT_AHEAD")) : 4;   // (0 / 1: one at a time)
     if (st.over_levels != 0 && !kp.lobes && !kp.count && ahead > 1) {
         if (batch) {
-            allow_lds(connect_kernel<B, 0, true, false, false, FS_CONNECT_AHEAD_N>, lds);
-            hipLaunchKernelGGL((connect_kernel<B, 0, true, false, false, FS_CONNECT_AHEAD_N>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed, queue_head,
+            allow_lds(connect_kernel<B, 0, true, false, false, kConnectAhead>, lds);
+            hipLaunchKernelGGL((connect_kernel<B, 0, true, false, false, kConnectAhead>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed, queue_head,
                                pairs_per_wave, energy_tab, fixed_tab);
         } else {
-            allow_lds(connect_kernel<B, 0, false, false, false, FS_CONNECT_AHEAD_N>, lds);
-            hipLaunchKernelGGL((connect_kernel<B, 0, false, false, false, FS_CONNECT_AHEAD_N>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed, queue_head,
+            allow_lds(connect_kernel<B, 0, false, false, false, kConnectAhead>, lds);
+            hipLaunchKernelGGL((connect_kernel<B, 0, false, false, false, kConnectAhead>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed, queue_head,
                                pairs_per_wave, energy_tab, fixed_tab);
         }
         return;

@@ -111,7 +111,7 @@ struct Source {
     int mask_index = -1;        // this source's row of fs_context::d_slot_masks (its handle; -1: none — every block is always written)
     hipEvent_t ev[kIrRing] = {};
     // How ring slot `slot` is known to be published, in this order: pub_word[slot] != 0 — a launch on the COMPUTE stream whose
-    // reconstruct workgroups wrote the slot themselves and whose id appears in fs_context::h_pub_word (publish_arrive, fs_device.hpp:
+    // reconstruct workgroups wrote the slot themselves and whose id appears in fs_context::h_pub_word (publish_arrive, fs_dev_recon.hpp:
     // no event, nothing on the tail stream); pub_batch[slot] != 0 — a batched reconstruct on the TAIL stream, one event for all its
     // sources (fs_context::tail_batch_ev); else the slot's own event ev[slot] behind a copy command on the tail stream.
     // rec_batch[i] != 0 names the tail batch whose event stands for ev_rec[i]; rec_on_compute[i]: the reconstruct ran on the compute
@@ -295,7 +295,7 @@ struct fs_context {
     // Publishes of the compute stream (fused reconstruct parts, batches behind a tick or a flush): the launch writes the ring slots
     // and then its id into *h_pub_word (pinned, coherent) — see Source::pub_word.  pub_issued = id of the newest such launch.
     unsigned* d_pub_tickets = nullptr;             // device: the ticket cell of publish_arrive (re-armed by the launch that used it)
-    // zero-block masks of the sources' host ring slots (fs_device.hpp: host_block_wanted): [kMaxMaskSources][kIrRing] words on the
+    // zero-block masks of the sources' host ring slots (fs_dev_recon.hpp: host_block_wanted): [kMaxMaskSources][kIrRing] words on the
     // device, bit b of word (source, slot) = block b of that slot may hold non-zero samples.  Kept by the reconstruct kernels; a
     // copy command into a slot (reconstruct_now, fs_set_impulse_response) sets the slot's word to all ones behind itself.
     uint32_t* d_slot_masks = nullptr;

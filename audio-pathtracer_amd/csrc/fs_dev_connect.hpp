@@ -1,0 +1,327 @@
+// fs_dev_connect.hpp — the connect pass: ConnectSubpaths + EvaluatePath + clamp / gain + deposit (connect_body).
+#pragma once
+#include "fs_dev_walk.hpp"
+
+namespace fs {
+namespace {
+
+// ---------------------------------------------------------------------------------------------------
+// connect_kernel: ConnectSubpaths + EvaluatePath + clamp/gain + deposit
+// ---------------------------------------------------------------------------------------------------
+// pairs_per_wave < 64: sparse waves for small frames — a wave owns that many pairs (its first lanes), the other
+// lanes only help with the shared visibility queries (a frame of a few thousand pairs is otherwise a few waves
+// waiting for their longest traversal).
+// BATCH: a batched frame (fs_compute_energy_response_batch): the pairs of several sources lie end to end
+// (kp.pairs_per_source each) and every source has its own energy buffer (energy_tab / fixed_tab); a workgroup
+// takes (source, chunk) items and flushes its LDS histogram whenever the source changes.
+// AHEAD (the connect kernels of uncapped walks that are waited for): a lane that evaluates its pair's path alone requests the
+// records of AHEAD segments at once and applies them in path order — the same operations in the same order.  The records of a
+// walk lie a whole level apart ([step][slot]): one at a time, every segment of a 100-segment path waited for its own miss.
+// (Also measured: the paths of 40 segments or more evaluated by the whole wave, as a sparse wave does for every path — no gain
+// on top of this: 88 -> 92 us at cfg3's size.  With the records ahead the longest path is no longer what the pass waits for.)
+template <int B, int LOBES, bool BATCH, bool COUNT, bool EXT = false, int AHEAD = 1>
+__device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t nblocks, const DeviceScene& sc,
+                                             const KParams& kp, const SubpathState& st, float* __restrict__ energy,
+                                             unsigned long long* __restrict__ fixed, unsigned* queue_head,
+                                             const int pairs_per_wave, float* const* __restrict__ energy_tab,
+                                             unsigned long long* const* __restrict__ fixed_tab) {
+    extern __shared__ __attribute__((aligned(16))) int s_dyn[];   // [stack_rows][kBlock] stack | [B][hist_window] histogram
+    int* s_stack = s_dyn;
+    float* s_hist = reinterpret_cast<float*>(s_dyn + (size_t)sc.stack_rows * kBlock);
+    const int nb = kp.num_bins, W = kp.hist_window, NB = band_count<B>(kp);   // LDS histogram = the first W bins of every band (see KParams)
+    int* s_share = reinterpret_cast<int*>(s_hist + (size_t)NB * W);   // work-sharing area of trav_any_shared
+    __shared__ int s_lo, s_hi;
+    __shared__ unsigned s_dep, s_tst, s_sgs;
+#ifdef FS_WAVE_TIMELINE
+    unsigned long long tl[6] = {__builtin_amdgcn_s_memrealtime(), 0, 0, 0, 0, 0};
+#endif
+    for (int i = threadIdx.x; i < NB * W; i += kBlock) s_hist[i] = 0.0f;
+    if (threadIdx.x == 0) { s_lo = nb; s_hi = -1; s_dep = 0u; s_tst = 0u; s_sgs = 0u; }
+    // this frame's walk is over: rearm the frame scratch (queue head, plan counts and cursors) for the next one
+    if (bid == 0u)
+        for (int i = threadIdx.x; i < 1 + 2 * kPlanBuckets; i += kBlock) queue_head[i] = 0u;
+    __syncthreads();
+
+    const uint32_t n = kp.num_local;
+    const uint32_t total = 2u * n;
+    unsigned my_deposits = 0, my_tested = 0, my_segments = 0;
+    uint32_t cnt_nv = 0u, cnt_nt = 0u;
+    // whole workgroups step through the pairs: every lane of a wave takes part in the shared visibility queries,
+    // also the ones without a pair or without a segment to test
+    const uint32_t ppw = (uint32_t)pairs_per_wave, per_block = ppw * (kBlock / 64);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+
+    // one chunk of per_block pairs [first, first + per_block) clipped to `end`, deposits into s_hist / fixed_dst
+    auto chunk = [&](uint32_t first, uint32_t end, unsigned long long* fixed_dst, float* far_dst) {
+        const uint32_t li = first + wave * ppw + lane;
+        const bool active = lane < ppw && li < end;
+        const uint32_t lc = active ? li : 0u;
+        const uint32_t sf = slot_of(st, lc), sl = slot_of(st, n + lc);   // where the walk left the two subpaths of the pair
+        const float4 F = st.end_pos[sf];
+        const uint2 Fm = st.end_misc[sf];
+        const float4 L = st.end_pos[sl];
+        const uint2 Lm = st.end_misc[sl];
+        // visibility F_k -> B_m - 0.1 * unit(B_m - F_k) (ARTS.cpp:252-254); visible iff NO hit
+        float dx = L.x - F.x, dy = L.y - F.y, dz = L.z - F.z;
+        float l2 = dx * dx + dy * dy + dz * dz;
+        float len = sqrtf(l2);
+        float inv = 1.0f / len;
+        float tmax = len - kp.connect_pullback;
+        float ux = dx * inv, uy = dy * inv, uz = dz * inv;
+        float conn_nd = 0.0f;       // FS_FLAG_DOUBLE_POSITIONS: the connection segment's scaled length, from the double end points
+        if (EXT && kp.dpos) {       // (wave-uniform) FVector end points: difference, length and unit direction in double
+            const double* Fd = st.end_posd + 3 * (size_t)sf;
+            const double* Ld = st.end_posd + 3 * (size_t)sl;
+            const double ex = Ld[0] - Fd[0], ey = Ld[1] - Fd[1], ez = Ld[2] - Fd[2];
+            const double e2 = ex * ex + ey * ey + ez * ez;
+            const double elen = sqrt(e2), einv = 1.0 / elen;
+            l2 = e2 > 1e-8f ? 1.0f : 0.0f;                       // only its comparison with 1e-8 is used below
+            ux = (float)(ex * einv); uy = (float)(ey * einv); uz = (float)(ez * einv);
+            tmax = (float)(elen - kp.connect_pullback);
+            conn_nd = (float)(elen / (double)kp.dist_divisor);
+        }
+        bool has_ray = active && (l2 > 1e-8f) && (tmax > 0.0f);
+        Ray ray = make_ray(F.x, F.y, F.z, ux, uy, uz);
+        // ConnectSubpaths ignores no actor (ARTS.cpp:252-254): the end points' collision spheres block
+        bool sphere_blocked = false;
+        if (EXT && has_ray && (kp.listener_radius > 0.0f || kp.source_radius > 0.0f)) {
+            float ts;
+            if (kp.listener_radius > 0.0f && sphere_hit(ray, kp.lis, kp.listener_radius, tmax, ts)) sphere_blocked = true;
+            if (kp.source_radius > 0.0f) {
+                float c[3] = {kp.src[0], kp.src[1], kp.src[2]};
+                if (kp.src_table) { const uint32_t sid = lc / kp.pairs_per_source; c[0] = kp.src_table[4 * sid]; c[1] = kp.src_table[4 * sid + 1]; c[2] = kp.src_table[4 * sid + 2]; }
+                if (sphere_hit(ray, c, kp.source_radius, tmax, ts)) sphere_blocked = true;
+            }
+            if (sphere_blocked) has_ray = false;   // settled without a traversal
+        }
+#ifdef FS_WAVE_TIMELINE
+        if (!tl[1]) tl[1] = __builtin_amdgcn_s_memrealtime();   // first chunk: set-up and end-state loads done
+#endif
+        my_tested += active ? 1u : 0u;                                // one ConnectSubpaths per pair (ARTS.cpp:232 counts the connected ones)
+        my_segments += active ? Fm.y + Lm.y : 0u;                     // the steps the two walks TOOK (each wrote its own count with its end state)
+        const bool hit = trav_any_shared<COUNT>(sc, has_ray, ray, tmax, &s_stack[threadIdx.x], s_share, &cnt_nv, &cnt_nt);
+#ifdef FS_WAVE_TIMELINE
+        if (!tl[2]) tl[2] = __builtin_amdgcn_s_memrealtime();   // first chunk: visibility queries done
+#endif
+        float E[Bands<B>::kMax];
+#pragma unroll
+        for (int b = 0; b < Bands<B>::kMax; ++b) E[b] = 1.0f;
+        float sd = 0.0f;
+        // one lane evaluates its pair's connected path alone: EvaluatePath over F0..Fk, Bm..B0 (ARTS.cpp:262-267, 360-420), in path order
+        auto eval_alone = [&]() {
+        const int kf = (int)Fm.y, kl = (int)Lm.y;
+        if (AHEAD > 1) {
+            for (int j0 = 0; j0 < kf; j0 += AHEAD) {                      // source-side segments F_j -> F_j+1, AHEAD records in flight
+                float2 np[AHEAD];
+                uint32_t mt[AHEAD];
+#pragma unroll
+                for (int u = 0; u < AHEAD; ++u) { const int j = min(j0 + u, kf - 1); np[u] = load_np(st, total, j, sf); mt[u] = load_mat(st, total, j, sf); }
+#pragma unroll
+                for (int u = 0; u < AHEAD; ++u)
+                    if (j0 + u < kf) { sd += np[u].x; apply_segment<B, LOBES>(E, np[u].x, mt[u], np[u].y, kp, sc); }
+            }
+        } else
+        for (int j = 0; j < kf; ++j) {                                // source-side segments F_j -> F_j+1
+            const float2 np = load_np(st, total, j, sf);
+            sd += np.x;                                               // ARTS.cpp:374
+            apply_segment<B, LOBES>(E, np.x, load_mat(st, total, j, sf), np.y, kp, sc);
+        }
+        {                                                             // connection segment: F_k's material/prob
+            float dist = sqrtf(l2);
+            float nd = (EXT && kp.dpos) ? conn_nd : dist / kp.dist_divisor;
+            sd += nd;
+            apply_segment<B, LOBES>(E, nd, Fm.x, F.w, kp, sc);
+        }
+        if (AHEAD > 1) {
+            for (int j0 = kl - 1; j0 >= 0; j0 -= AHEAD) {                 // listener-side segments B_j+1 -> B_j
+                float2 np[AHEAD];
+                uint32_t mt[AHEAD];
+#pragma unroll
+                for (int u = 0; u < AHEAD; ++u) { const int j = max(j0 - u, 0); np[u] = load_np(st, total, j, sl); mt[u] = load_mat(st, total, j, sl); }
+#pragma unroll
+                for (int u = 0; u < AHEAD; ++u)
+                    if (j0 - u >= 0) { sd += np[u].x; apply_segment<B, LOBES>(E, np[u].x, mt[u], np[u].y, kp, sc); }
+            }
+        } else
+        for (int j = kl - 1; j >= 0; --j) {                           // listener-side segments B_j+1 -> B_j
+            const float2 np = load_np(st, total, j, sl);
+            sd += np.x;
+            apply_segment<B, LOBES>(E, np.x, load_mat(st, total, j, sl), np.y, kp, sc);
+        }
+        };
+        if (ppw == 1u || (ppw <= 8u && st.over_levels != 0)) {
+            // Few pairs per wave (the reference's own frames: one; ticks of several sources with uncapped walks: up to eight, of
+            // which a fifth connect — and a connected path of uncapped walks has up to a few hundred segments, 40 us of ONE
+            // lane's time at 160): the wave's 64 lanes evaluate a connected path together — lane i the factors of segment i
+            // (64 segments per round), then every lane runs the same product over them in path order, the factors read across
+            // with v_readlane — one connected pair of the wave after the other; the pair's own lane keeps the result and deposits.
+            bool go = active && !hit && !sphere_blocked;
+            if (go && st.over_levels && !(rec_fits(st, (int)Fm.y - 1, sf) && rec_fits(st, (int)Lm.y - 1, sl))) go = false;
+            unsigned long long todo = __ballot(go);
+            if (todo == 0ull) return;
+            const float my_nd = (EXT && kp.dpos) ? conn_nd : sqrtf(l2) / kp.dist_divisor;
+            while (todo != 0ull) {                                       // (wave-uniform)
+                const int o = __ffsll((long long)todo) - 1;
+                todo &= todo - 1ull;
+                const int kf = __builtin_amdgcn_readlane((int)Fm.y, o), kl = __builtin_amdgcn_readlane((int)Lm.y, o);
+                const uint32_t usf = (uint32_t)__builtin_amdgcn_readlane((int)sf, o), usl = (uint32_t)__builtin_amdgcn_readlane((int)sl, o);
+                const float c_nd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_nd), o));
+                const uint32_t c_mat = (uint32_t)__builtin_amdgcn_readlane((int)Fm.x, o);
+                const float c_prob = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(F.w), o));
+                const int segs = kf + 1 + kl;
+                float Et[Bands<B>::kMax];
+#pragma unroll
+                for (int b = 0; b < Bands<B>::kMax; ++b) Et[b] = 1.0f;
+                float sdt = 0.0f;
+                for (int base = 0; base < segs; base += 64) {
+                    const int i = base + (int)lane;
+                    float nd = 0.0f, prob = 1.0f;
+                    uint32_t mat = kNoMat;
+                    if (i < kf) {                                            // source-side segment F_i -> F_i+1
+                        const float2 np = load_np(st, total, i, usf);
+                        nd = np.x; prob = np.y; mat = load_mat(st, total, i, usf);
+                    } else if (i == kf) {                                    // connection segment: F_k's material / prob
+                        nd = c_nd; prob = c_prob; mat = c_mat;
+                    } else if (i < segs) {                                   // listener-side segment B_j+1 -> B_j, j = kl - 1 .. 0
+                        const int j = kl - 1 - (i - kf - 1);
+                        const float2 np = load_np(st, total, j, usl);
+                        nd = np.x; prob = np.y; mat = load_mat(st, total, j, usl);
+                    }
+                    SegFactors<B> f;
+                    segment_factors<B, LOBES>(f, nd, mat, prob, kp, sc);
+                    const int cnt = min(64, segs - base);
+                    for (int q = 0; q < cnt; ++q) {                          // (wave-uniform: the product in path order, in every lane alike)
+                        sdt += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nd), q));                 // ARTS.cpp:374
+                        if (!__builtin_amdgcn_readlane((int)f.live, q)) continue;
+                        const float geo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f.geo), q));
+                        const float pw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f.pw), q));
+#pragma unroll
+                        for (int b = 0; b < Bands<B>::kMax; ++b) {
+                            if (B == 0 && b >= NB) break;
+                            float e = Et[b];
+                            e *= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f.bsdf[b]), q));
+                            e *= geo;
+                            e *= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f.ex[b]), q));
+                            e /= pw;
+                            Et[b] = e;
+                        }
+                    }
+                }
+                if ((int)lane == o) {
+#pragma unroll
+                    for (int b = 0; b < Bands<B>::kMax; ++b) E[b] = Et[b];
+                    sd = sdt;
+                }
+            }
+            if (!go) return;
+            ++my_deposits;
+        } else {
+        if (!active || hit || sphere_blocked) return;
+        // depth = 0 only: a walk that outlived the record store has raised the overflow word — the frame is void and will
+        // be traced again (FS_ERR_OVERFLOW); its pair must not be evaluated, the records it would read do not exist
+        if (st.over_levels && !(rec_fits(st, (int)Fm.y - 1, sf) && rec_fits(st, (int)Lm.y - 1, sl))) return;
+        ++my_deposits;
+        eval_alone();
+        }
+        float delay = sd / kp.sound_speed;                            // ARTS.cpp:419
+        float x = (delay * 1000.f) / 1.0f;                            // FSAC.h:89, BinSizeMs = 1
+        float fl = floorf(x);
+        int bin = !(fl > 0.0f) ? 0 : (fl >= (float)(nb - 1) ? nb - 1 : (int)fl);
+        const bool near = bin < W;
+        if (!fixed_dst && near) {
+            atomicMin(&s_lo, bin);
+            atomicMax(&s_hi, bin);
+        }
+#pragma unroll
+        for (int b = 0; b < Bands<B>::kMax; ++b) {
+            if (B == 0 && b >= NB) break;
+            float e = E[b];
+            e = (e < kp.energy_clamp) ? e : kp.energy_clamp;          // FMath::Min ARTS.cpp:410
+            e *= kp.energy_gain;                                      // ARTS.cpp:413
+            e *= kp.norm;                                             // ARTS.cpp:164-170
+            if (fixed_dst)   // deterministic mode: integer sum of 2^-40 quanta — exact, so order- and shard-independent
+                atomicAdd(&fixed_dst[b * nb + bin], (unsigned long long)__double2ll_rn((double)e * kFixedScale));
+            else if (near)
+                atomicAdd(&s_hist[b * W + bin], e);                   // ds_add_f32
+            else
+                atomicAdd(&far_dst[b * nb + bin], e);                 // beyond the LDS window: global_atomic_add_f32
+        }
+    };
+    // LDS histogram -> one source's energy buffer (touched bin range only); clear = rearm it for the next source
+    auto flush = [&](float* dst, bool clear) {
+        __syncthreads();
+        const int lo = s_lo, hi = s_hi;
+        if (hi >= lo) {
+            const int span = hi - lo + 1;
+            for (int i = threadIdx.x; i < NB * span; i += kBlock) {
+                int b = i / span, bin = lo + (i - b * span);
+                float v = s_hist[b * W + bin];
+                if (v != 0.0f) atomicAdd(&dst[b * nb + bin], v);      // global_atomic_add_f32
+                if (clear) s_hist[b * W + bin] = 0.0f;
+            }
+        }
+        if (clear) {
+            __syncthreads();
+            if (threadIdx.x == 0) { s_lo = nb; s_hi = -1; }
+            __syncthreads();
+        }
+    };
+
+    if (BATCH) {
+        const uint32_t nps = kp.pairs_per_source, sources = n / nps;
+        const uint32_t chunks = (nps + per_block - 1) / per_block;   // per source
+        int cur = -1;
+        for (uint32_t it = bid; it < chunks * sources; it += nblocks) {
+            const uint32_t sid = it / chunks;
+            if ((int)sid != cur) {
+                if (cur >= 0 && !fixed_tab) flush(energy_tab[cur], true);
+                cur = (int)sid;
+            }
+            chunk(sid * nps + (it - sid * chunks) * per_block, (sid + 1) * nps, fixed_tab ? fixed_tab[sid] : nullptr,
+                  energy_tab[sid]);
+        }
+        if (cur >= 0 && !fixed_tab) flush(energy_tab[cur], false);
+    } else {
+        for (uint32_t base = bid * per_block; base < n; base += nblocks * per_block) chunk(base, n, fixed, energy);
+    }
+#ifdef FS_WAVE_TIMELINE
+    tl[3] = __builtin_amdgcn_s_memrealtime();   // all chunks evaluated and deposited into LDS
+#endif
+    if (COUNT) add_fetch_counts(queue_head, 5, cnt_nv, cnt_nt);
+    {   // work counters: summed per wave, then per workgroup in LDS — one global atomic per workgroup (thousands of
+        // atomics on one address cost the kernel ~10 %)
+        unsigned d = my_deposits, t = my_tested, g = my_segments;
+        for (int o = 32; o > 0; o >>= 1) { d += __shfl_down(d, o); t += __shfl_down(t, o); g += __shfl_down(g, o); }
+        if ((threadIdx.x & 63u) == 0u && d) atomicAdd(&s_dep, d);
+        if ((threadIdx.x & 63u) == 0u && t) atomicAdd(&s_tst, t);
+        if ((threadIdx.x & 63u) == 0u && g) atomicAdd(&s_sgs, g);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long* counters = reinterpret_cast<unsigned long long*>(queue_head + kCounterWord);
+        if (s_dep) atomicAdd(&counters[2], (unsigned long long)s_dep);
+        if (s_tst) atomicAdd(&counters[1], (unsigned long long)s_tst);   // the pairs this workgroup's lanes tested
+        if (s_sgs) atomicAdd(&counters[0], (unsigned long long)s_sgs);   // fs_stats.segments: observed (planned: counters[7], by the plan pass)
+    }
+    if (!BATCH) {
+        const int lo = s_lo, hi = s_hi;
+        if (hi >= lo) {
+            const int span = hi - lo + 1;
+            for (int i = threadIdx.x; i < NB * span; i += kBlock) {
+                int b = i / span, bin = lo + (i - b * span);
+                float v = s_hist[b * W + bin];
+                if (v != 0.0f) atomicAdd(&energy[b * nb + bin], v);       // global_atomic_add_f32
+            }
+        }
+    }
+#ifdef FS_WAVE_TIMELINE
+    if ((threadIdx.x & 63u) == 0u && g_conn_buf) {
+        unsigned long long* o = g_conn_buf + 8ull * (bid * (kBlock / 64) + (threadIdx.x >> 6));
+        o[0] = tl[0]; o[1] = tl[1]; o[2] = tl[2]; o[3] = tl[3]; o[4] = __builtin_amdgcn_s_memrealtime();
+        o[5] = my_deposits; o[6] = 0; o[7] = 0;
+    }
+#endif
+}
+
+}  // namespace
+}  // namespace fs

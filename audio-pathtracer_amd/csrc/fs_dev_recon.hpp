@@ -1,0 +1,342 @@
+// fs_dev_recon.hpp — ReconstructImpulseResponse on the device, the spectral channel row, the zero-block votes of the
+// host ring slots and the publish of a launch's host slots.
+#pragma once
+#include "fs_dev_common.hpp"
+
+namespace fs {
+namespace {
+
+// ReconstructImpulseResponse (FSAC.cpp:320-380) for one row (band, or row B = the band mean = the channel view) and one block
+// of kBlock chunks of kChunk samples; s_amp: [nb] floats of LDS.  Shared by reconstruct_kernel (tail stream) and the
+// reconstruct part of the fused frame kernel (fs_frame.hip).
+constexpr int kWarm = 96;
+// A publish without the host's help: the reconstruct workgroups of a launch write the channel views straight into the sources'
+// pinned host ring slots; every one of them, once its stores have been acknowledged, takes a ticket, and the workgroup that takes
+// the last one stores the launch's id into the context's pinned host word — fs_get_impulse_response* and the ring's back-pressure
+// read that word: no event, no copy command, no second stream (fs_capi_publish.cpp: owed_publish).  The ticket cell re-arms itself.
+// The samples go to the host with SYSTEM-scope stores (store_sys: sc0 sc1 — written through to the host before they are
+// acknowledged), so a wave whose store counter has run out (s_waitcnt vmcnt(0): on gfx9 stores count there too) knows that its
+// samples are where the host reads them; the barrier collects the workgroup's waves, the tickets the launch's workgroups, and the
+// word — a system-scope store as well — is issued only then: it can never overtake the samples.  Two things that do NOT work:
+// plain stores + the counter (the word overtook the samples: tests/test_round3.py's stream of grouped frames read 6 of 7
+// publishes too early — plain stores to fine-grained memory are acknowledged by the L2, not by the host), and a system-scope
+// FENCE per wave (__threadfence_system(): correct, but it also writes back every dirty L2 line of the chip each time: the 3 072
+// reconstruct workgroups of a 128-source tick paid 0.27 ms for it, the fused frame kernel 3 %).
+__device__ __forceinline__ void store_sys(float* p, const float4 v) {   // 16 bytes, system scope (p 16-byte aligned)
+    typedef float sys_v4f __attribute__((ext_vector_type(4)));
+    const sys_v4f x = {v.x, v.y, v.z, v.w};
+    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(p), "v"(x) : "memory");
+}
+__device__ __forceinline__ void store_sys(float* p, const float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+__device__ __forceinline__ void publish_arrive(unsigned* __restrict__ tickets, unsigned total, unsigned long long* __restrict__ host_word,
+                                               unsigned long long id) {
+    if (tickets == nullptr) return;                       // (uniform: this launch is published through an event)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned t = __hip_atomic_fetch_add(tickets, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (t + 1u == total) {
+            __hip_atomic_store(tickets, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the next launch of the stream starts behind this one)
+            __hip_atomic_store(host_word, id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// host_out (optional, row B only): the block's samples also go to that pinned host buffer, staged in `s_stage`
+// (kBlock x (kChunk + 1) floats of LDS) and written with one 16-byte store per lane and instruction.
+// ir_bands == nullptr (a frame whose IR is superseded within its own launch): only the channel row is produced, for the host.
+// The zero-block rule of the host slot (slot_mask: one device word per ring slot, bit b = block b of the slot may hold non-zero
+// samples).  A block none of whose reachable amplitudes (its bins, the bin before, the kWarm run-in) is non-zero produces exact
+// zeros: it is written across the bus only if the slot still holds something else there.  A room's IR ends after 60 - 230 of the
+// 1000 bins: 9 - 10 of a slot's 12 blocks stay on the device side of the bus (the 128-source tick wrote 24.6 MB per tick).
+// Returns whether this workgroup must write its block to the host; every thread of the workgroup must call it.
+// (the two halves of the rule: this thread's share of the reach test, then the workgroup's vote and the mask bit)
+__device__ __forceinline__ bool block_reach_nonzero(const float* s_amp, int nb, int spb, int base) {
+    const int b0 = max((base - kWarm) / spb - 1, 0), b1 = min((base + kReconBlockSamples - 1) / spb, nb - 1);
+    bool nz = false;
+    for (int b = b0 + (int)threadIdx.x; b <= b1; b += kBlock) nz = nz || s_amp[b] != 0.0f;
+    return nz;
+}
+__device__ __forceinline__ bool host_block_vote(bool nz, int block, uint32_t* __restrict__ slot_mask) {
+    const bool any = __syncthreads_or(nz ? 1 : 0) != 0;
+    const uint32_t bit = 1u << block;
+    const bool dirty = (__hip_atomic_load(slot_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) != 0u;   // (only this workgroup touches this bit)
+    __syncthreads();                                        // (everybody has read the word before thread 0 rewrites it)
+    if (threadIdx.x == 0) {
+        if (any && !dirty) __hip_atomic_fetch_or(slot_mask, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!any && dirty) __hip_atomic_fetch_and(slot_mask, ~bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return any || dirty;
+}
+__device__ __forceinline__ bool host_block_wanted(const float* s_amp, int nb, int spb, int base, int block, uint32_t* __restrict__ slot_mask) {
+    if (slot_mask == nullptr) return true;
+    return host_block_vote(block_reach_nonzero(s_amp, nb, spb, base), block, slot_mask);
+}
+
+__device__ __forceinline__ void reconstruct_body(const int row, const int chunk_block, const float* __restrict__ energy, int B, int nb,
+                                                 int num_samples, int spb, float* __restrict__ ir_bands,
+                                                 float* __restrict__ ir_mono, float* s_amp, float* host_out = nullptr,
+                                                 float* s_stage = nullptr, uint32_t* __restrict__ slot_mask = nullptr) {
+    const float Pi4 = sqrtf(4.0f * kPi);                           // FSAC.cpp:323
+    if (ir_bands == nullptr && (row < B || host_out == nullptr)) return;   // (uniform) nobody wants this row
+    for (int i = threadIdx.x; i < nb; i += kBlock) {
+        float e;
+        if (row < B) e = energy[row * nb + i];
+        else {
+            float s = 0.f;
+            for (int b = 0; b < B; ++b) s += energy[b * nb + i];
+            e = s / (float)B;
+        }
+        float a = 0.0f;
+        if (fabsf(e) >= 1e-6f) a = e / sqrtf(e * Pi4);             // FSAC.cpp:343-345
+        s_amp[i] = a;
+    }
+    __syncthreads();
+    const int chunk = chunk_block * kBlock + threadIdx.x;
+    const int s0 = chunk * kChunk;
+    bool to_host = host_out != nullptr && row == B;         // (uniform for the workgroup)
+    if (to_host) to_host = host_block_wanted(s_amp, nb, spb, chunk_block * kBlock * kChunk, chunk_block, slot_mask);
+    const bool staged = s_stage != nullptr;                 // (uniform) the block's samples leave through LDS: 16-byte stores of consecutive lanes
+    if (s0 >= num_samples && !staged) return;
+    float* out = ir_bands == nullptr ? nullptr : (row < B ? ir_bands + (size_t)row * num_samples : ir_mono);   // (nullptr: staged, host only)
+    const int s1 = min(s0 + kChunk, num_samples);        // (a thread beyond the end: an empty range, it only joins the barrier below)
+    const int i0 = s0 < num_samples ? max(s0 - kWarm, 0) : s1;
+    int bin = i0 / spb;
+    int bs = i0 - bin * spb;
+    float cur = bin < nb ? s_amp[bin] : 0.0f;
+    float prev = bin == 0 ? cur : (bin - 1 < nb ? s_amp[bin - 1] : 0.0f);   // FSAC.cpp:347-355
+    const float fspb = (float)spb;
+    float y = 0.0f;
+    for (int i = i0; i < s1; ++i) {
+        float x = 0.0f;
+        if (bin < nb) {
+            float wgt = (float)bs / fspb;                           // FSAC.cpp:359
+            float a = (1.0f - wgt) * prev;
+            float b = wgt * cur;
+            x = a + b;                                              // FSAC.cpp:360
+        }
+        if (i == 0) {
+            y = x;                                                  // Filtered[0] = IR[0] FSAC.cpp:371
+        } else {
+            float a = 0.25f * x;
+            float b = (1.0f - 0.25f) * y;
+            y = a + b;                                              // FSAC.cpp:374
+        }
+        if (i >= s0) {
+            // (a thread's own 16 samples lie 64 bytes from its neighbour's: stored one by one, every store instruction of a wave
+            // touches 64 lines — 20 of the 26 us of a one-source reconstruct, the same again for the host copy)
+            if (staged) s_stage[threadIdx.x * (kChunk + 1) + (i - s0)] = y;   // (+ 1: conflict-free rows)
+            else if (out) out[i] = y;
+        }
+        if (++bs == spb) {
+            bs = 0;
+            ++bin;
+            prev = cur;
+            cur = bin < nb ? s_amp[bin] : 0.0f;
+        }
+    }
+    if (staged) {   // the block's kBlock * kChunk consecutive samples, 16 bytes per lane: to the device array, and the channel row to the host slot
+        __syncthreads();
+        const int base = chunk_block * kBlock * kChunk;
+        for (int v = threadIdx.x; v < kBlock * kChunk / 4; v += kBlock) {
+            const int s = 4 * v;
+            if (base + s + 3 < num_samples) {
+                float4 o;   // (sample s of the block lives in row s / kChunk of kChunk + 1 words)
+                o.x = s_stage[s + s / kChunk]; o.y = s_stage[s + 1 + (s + 1) / kChunk];
+                o.z = s_stage[s + 2 + (s + 2) / kChunk]; o.w = s_stage[s + 3 + (s + 3) / kChunk];
+                if (out) *reinterpret_cast<float4*>(out + base + s) = o;
+                if (to_host) store_sys(host_out + base + s, o);
+            } else {
+                for (int e = 0; e < 4; ++e)
+                    if (base + s + e < num_samples) {
+                        const float y1 = s_stage[s + e + (s + e) / kChunk];
+                        if (out) out[base + s + e] = y1;
+                        if (to_host) store_sys(host_out + base + s + e, y1);
+                    }
+            }
+        }
+    }
+}
+
+// The same reconstruct for the kernels that only reconstruct (reconstruct_kernel, reconstruct_batch_kernel), in two phases.  In
+// reconstruct_body a thread's 16 samples cost it a chain of 16 + kWarm interpolated samples — a division, four branches and
+// their bookkeeping each, ~ 60 instructions a sample on a wave that is alone on its SIMD: 20 of the 26 us of a one-source
+// reconstruct (the stores, scattered or not, to the device or to the host, were 2 of them: profiles/r04 notes in DESIGN.md).
+// Here every interpolated sample of the block (and of the kWarm before it) is computed ONCE, by the thread that owns it, into
+// LDS; the filter chain then reads them: three arithmetic instructions a sample.  The same operations on the same operands in
+// the same order as reconstruct_body: the same bits.
+// LDS: s_amp [nb] | s_x [kBlock * kChunk + kWarm] | s_stage [kBlock][kChunk + 1].
+
+// The phases of reconstruct_body_fast, shared with the spectral channel row (reconstruct_spectral_row) so that its band envelopes
+// are the band rows' own bits.  The amplitudes of one row: row < B a band, row == B the band mean.
+__device__ __forceinline__ void recon_amplitudes(const int row, const float* __restrict__ energy, int B, int nb, float* s_amp) {
+    const float Pi4 = sqrtf(4.0f * kPi);                           // FSAC.cpp:323
+    for (int i = threadIdx.x; i < nb; i += kBlock) {
+        float e;
+        if (row < B) e = energy[row * nb + i];
+        else {
+            float s = 0.f;
+            for (int b = 0; b < B; ++b) s += energy[b * nb + i];
+            e = s / (float)B;
+        }
+        float a = 0.0f;
+        if (fabsf(e) >= 1e-6f) a = e / sqrtf(e * Pi4);             // FSAC.cpp:343-345
+        s_amp[i] = a;
+    }
+}
+// phase 1: the interpolated samples x[base - kWarm .. base + kBlock * kChunk) -> s_x[0 ..): thread t its own kChunk, and the
+// first kWarm threads one sample each of the run-in (samples before 0 do not exist: never read)
+__device__ __forceinline__ void recon_interpolate(const int base, int nb, int spb, const float* s_amp, float* s_x) {
+    const float fspb = (float)spb;
+    auto interp = [&](int i) {
+        const int bin = i / spb, bs = i - bin * spb;
+        float x = 0.0f;
+        if (bin < nb) {
+            const float cur = s_amp[bin];
+            const float prev = bin == 0 ? cur : s_amp[bin - 1];         // FSAC.cpp:347-355
+            const float wgt = (float)bs / fspb;                          // FSAC.cpp:359
+            const float a = (1.0f - wgt) * prev;
+            const float b = wgt * cur;
+            x = a + b;                                                   // FSAC.cpp:360
+        }
+        return x;
+    };
+    const int s0 = base + (int)threadIdx.x * kChunk;
+    int bin = s0 / spb, bs = s0 - bin * spb;                     // (incrementally within the thread's own samples: no division by spb per sample)
+    float cur = bin < nb ? s_amp[bin] : 0.0f;
+    float prev = bin == 0 ? cur : (bin - 1 < nb ? s_amp[bin - 1] : 0.0f);
+#pragma unroll 4
+    for (int e = 0; e < kChunk; ++e) {
+        float x = 0.0f;
+        if (bin < nb) {
+            const float wgt = (float)bs / fspb;
+            const float a = (1.0f - wgt) * prev;
+            const float b = wgt * cur;
+            x = a + b;
+        }
+        s_x[kWarm + (int)threadIdx.x * kChunk + e] = x;
+        if (++bs == spb) { bs = 0; ++bin; prev = cur; cur = bin < nb ? s_amp[bin] : 0.0f; }
+    }
+    if ((int)threadIdx.x < kWarm) {
+        const int i = base - kWarm + (int)threadIdx.x;
+        s_x[threadIdx.x] = i >= 0 ? interp(i) : 0.0f;
+    }
+}
+// phase 2: the one-pole filter over this thread's kChunk samples behind a run-in of kWarm (0.75^96 ~ 1e-12); `my` = the thread's row
+// of kChunk outputs
+__device__ __forceinline__ void recon_filter(const int base, const float* s_x, float* my) {
+    const int s0 = base + (int)threadIdx.x * kChunk;
+    const int i0 = max(s0 - kWarm, 0);                           // global index of the first sample of the chain
+    const float* xs = s_x + (i0 - (base - kWarm));               // x[i0] in LDS
+    float y = 0.0f;
+    const int run = s0 - i0;                                     // kWarm, less at the very beginning of the IR
+    int e = 0;
+    if (i0 == 0) {                                               // Filtered[0] = IR[0] FSAC.cpp:371 (the first threads of the first block)
+        y = xs[0];
+        if (run == 0) my[0] = y;
+        e = 1;
+    }
+#pragma unroll 8
+    for (; e < run; ++e) { const float a = 0.25f * xs[e]; const float b = (1.0f - 0.25f) * y; y = a + b; }   // FSAC.cpp:374
+#pragma unroll 4
+    for (; e < run + kChunk; ++e) {
+        const float a = 0.25f * xs[e]; const float b = (1.0f - 0.25f) * y; y = a + b;
+        my[e - run] = y;
+    }
+}
+// the block's kBlock * kChunk consecutive samples from s_stage, 16 bytes per lane: the device array, and the channel row to the host slot
+__device__ __forceinline__ void recon_store(const int base, int num_samples, const float* s_stage, float* __restrict__ out, bool to_host,
+                                            float* host_out) {
+    for (int v = threadIdx.x; v < kBlock * kChunk / 4; v += kBlock) {
+        const int sidx = 4 * v;
+        if (base + sidx + 3 < num_samples) {
+            float4 o;
+            o.x = s_stage[sidx + sidx / kChunk]; o.y = s_stage[sidx + 1 + (sidx + 1) / kChunk];
+            o.z = s_stage[sidx + 2 + (sidx + 2) / kChunk]; o.w = s_stage[sidx + 3 + (sidx + 3) / kChunk];
+            if (out) *reinterpret_cast<float4*>(out + base + sidx) = o;
+            if (to_host) store_sys(host_out + base + sidx, o);
+        } else {
+            for (int e = 0; e < 4; ++e)
+                if (base + sidx + e < num_samples) {
+                    const float y1 = s_stage[sidx + e + (sidx + e) / kChunk];
+                    if (out) out[base + sidx + e] = y1;
+                    if (to_host) store_sys(host_out + base + sidx + e, y1);
+                }
+        }
+    }
+}
+
+__device__ __forceinline__ void reconstruct_body_fast(const int row, const int chunk_block, const float* __restrict__ energy, int B, int nb,
+                                                      int num_samples, int spb, float* __restrict__ ir_bands, float* __restrict__ ir_mono,
+                                                      float* s_amp, float* host_out, uint32_t* __restrict__ slot_mask = nullptr) {
+    float* s_x = s_amp + nb;
+    float* s_stage = s_x + kBlock * kChunk + kWarm;
+    if (ir_bands == nullptr && (row < B || host_out == nullptr)) return;   // (uniform) a superseded frame: only its channel row, for the host
+    recon_amplitudes(row, energy, B, nb, s_amp);
+    __syncthreads();
+    bool to_host = host_out != nullptr && row == B;         // (uniform for the workgroup)
+    float* out = ir_bands == nullptr ? nullptr : (row < B ? ir_bands + (size_t)row * num_samples : ir_mono);
+    const int base = chunk_block * kBlock * kChunk;          // the block's first sample
+    if (to_host) to_host = host_block_wanted(s_amp, nb, spb, base, chunk_block, slot_mask);
+    recon_interpolate(base, nb, spb, s_amp, s_x);
+    __syncthreads();
+    recon_filter(base, s_x, s_stage + threadIdx.x * (kChunk + 1));   // (+ 1: conflict-free rows)
+    __syncthreads();
+    recon_store(base, num_samples, s_stage, out, to_host, host_out);
+}
+
+// FS_FLAG_SPECTRAL_IR: the channel row (row B) as y[n] = (1/sqrt(B)) sum_b env_b[n] c_b[n] — env_b = band row b, bit for bit (the
+// phases above), c_b = the band's unit-power noise carrier ([B][carrier_stride(num_samples)] fp32, fs_fft.hip: launch_build_carriers).
+// The workgroup computes every band's envelope for its own block (no other workgroup's band row is read: the rows' workgroups are
+// not ordered, and a superseded frame has no band rows at all).  The products are summed over the bands in registers, the carrier
+// read as 16-byte loads of the thread's kChunk samples.  Zero blocks: a block is non-zero if ANY band's amplitude in its reach is
+// (one band above the 1e-6 cut can leave the band MEAN below it); where every envelope is zero the output is an exact zero.
+// Used by the fused frame kernel and by the reconstruct-only kernels alike: the same bits on every route.
+// LDS: reconstruct_body_fast's layout.
+__device__ __forceinline__ void reconstruct_spectral_row(const int chunk_block, const float* __restrict__ energy, int B, int nb,
+                                                         int num_samples, int spb, float* __restrict__ ir_bands, float* __restrict__ ir_mono,
+                                                         float* s_amp, float* host_out, uint32_t* __restrict__ slot_mask,
+                                                         const float* __restrict__ carrier) {
+    float* s_x = s_amp + nb;
+    float* s_stage = s_x + kBlock * kChunk + kWarm;
+    if (ir_bands == nullptr && host_out == nullptr) return;   // (uniform) nobody wants this row
+    float* out = ir_bands == nullptr ? nullptr : ir_mono;
+    const int base = chunk_block * kBlock * kChunk;
+    const int s0 = base + (int)threadIdx.x * kChunk;
+    const size_t ld = (size_t)carrier_stride(num_samples);
+    float* my = s_stage + threadIdx.x * (kChunk + 1);
+    float acc[kChunk];
+#pragma unroll
+    for (int e = 0; e < kChunk; ++e) acc[e] = 0.0f;
+    bool nz = false;
+    for (int band = 0; band < B; ++band) {
+        recon_amplitudes(band, energy, B, nb, s_amp);
+        __syncthreads();
+        nz = nz || block_reach_nonzero(s_amp, nb, spb, base);
+        recon_interpolate(base, nb, spb, s_amp, s_x);
+        __syncthreads();
+        recon_filter(base, s_x, my);                            // env_b of the thread's kChunk samples (its own row: no barrier)
+        if (s0 < num_samples) {
+            const float4* c = reinterpret_cast<const float4*>(carrier + (size_t)band * ld + s0);   // (ld and s0: multiples of kChunk: 16-byte aligned)
+#pragma unroll
+            for (int q = 0; q < kChunk / 4; ++q) {
+                const float4 cv = c[q];
+                acc[4 * q + 0] = acc[4 * q + 0] + my[4 * q + 0] * cv.x;
+                acc[4 * q + 1] = acc[4 * q + 1] + my[4 * q + 1] * cv.y;
+                acc[4 * q + 2] = acc[4 * q + 2] + my[4 * q + 2] * cv.z;
+                acc[4 * q + 3] = acc[4 * q + 3] + my[4 * q + 3] * cv.w;
+            }
+        }
+        __syncthreads();                                        // (the next band rewrites s_amp and s_x)
+    }
+    const float g = 1.0f / sqrtf((float)B);
+#pragma unroll
+    for (int e = 0; e < kChunk; ++e) my[e] = acc[e] * g;
+    bool to_host = host_out != nullptr;
+    if (to_host && slot_mask != nullptr) to_host = host_block_vote(nz, chunk_block, slot_mask);   // (its barriers order the rows above)
+    __syncthreads();
+    recon_store(base, num_samples, s_stage, out, to_host, host_out);
+}
+
+}  // namespace
+}  // namespace fs

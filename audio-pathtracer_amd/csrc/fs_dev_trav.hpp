@@ -1,0 +1,552 @@
+// fs_dev_trav.hpp — BVH traversal, one ray per lane (the resumable step, the bounded LDS stack with its deep store in
+// HBM), and the wave work sharing of closest-hit and any-hit queries.
+#pragma once
+#include "fs_dev_common.hpp"
+
+namespace fs {
+namespace {
+
+// ---------------------------------------------------------------------------------------------------
+// BVH traversal, one ray per lane, as a resumable single loop.  Every call of trav_step a busy lane
+// advances on BOTH fronts it has work on: it tests one triangle of its pending leaf AND visits its next
+// inner node (4 child boxes).  A wave executes both code paths in most iterations anyway (its lanes are
+// in different phases), so letting one lane use both halves the iterations a ray needs — per ray about
+// max(node visits, triangle tests) instead of their sum.  The closest hit does not depend on the order
+// of the tests, so results are unchanged.  A lane can be parked/resumed between any two steps.
+// `stack` is this lane's column of the workgroup's LDS stack (element i at stack[i * kBlock]).
+// ---------------------------------------------------------------------------------------------------
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+struct Trav {
+    int cur;        // next node: >= 0 inner index, < 0 leaf code (~cur = first*4 + count-1), kDone = none
+    int sp;         // stack top (entries live in [sb, sp))
+    int sb;         // stack bottom: 0 unless entries were given away from the bottom (wave work sharing)
+    int tri_i, tri_n;  // pending triangles [tri_i, tri_n) of the current leaf
+    float t;        // closest hit so far (init: tmax)
+    int leaf_index; // hit triangle (leaf order), -1 = none
+    uint32_t id;    // its input index (tie-break key)
+    uint32_t nv, nt;   // COUNT instantiations only (fs_set_profiling level 3): node records / triangle records this lane fetched
+    uint32_t ni, nl, nd;   // ... and (one lane per wave) node-request instructions, their active lanes, the distinct records among those
+};
+
+__device__ __forceinline__ void trav_init(Trav& T, float tmax, bool scene_nonempty) {
+    T.cur = scene_nonempty ? 0 : kDone;
+    T.sp = 0; T.sb = 0; T.tri_i = 0; T.tri_n = 0;
+    T.t = tmax; T.leaf_index = -1; T.id = 0xFFFFFFFFu;
+    T.nv = 0u; T.nt = 0u; T.ni = 0u; T.nl = 0u; T.nd = 0u;
+}
+__device__ __forceinline__ bool trav_busy(const Trav& T) { return T.tri_i < T.tri_n || T.cur != kDone; }
+
+// The step in pieces, ordered so that as little as possible lies between the arrival of a lane's records and the
+// request for its next ones (round 3: one extra L1-hit load per step costs the walk as much as 20 more vector
+// instructions — every instruction of a wave between `wait` and the next `issue` is on its serial critical path):
+//   trav_wait       the records have arrived
+//   trav_node_part  4 child boxes of the lane's node against the bound known so far, sort, pushes, next node
+//   trav_settle     a pending leaf becomes the triangle cursor and the next node is popped right away
+//   trav_issue      request the node and / or triangle record the lane needs NEXT (the triangle into the other register set)
+//   trav_tri_part   test the triangle that arrived with this step — in the shadow of the fetch just issued
+// The node test uses the bound from before this step's triangle test: a looser bound only admits more candidates,
+// and the (t, id) key decides among them, so the closest hit is unchanged bit for bit.
+// The loads are inline asm under the lanes' own exec mask, waited for once behind both groups: a lane without a
+// pending triangle (or node) requests nothing, both records of a lane are in flight together.  (Round 1 let every lane
+// fetch a dummy record 0 with plain loads instead, because inside `if (has_node)` / `if (has_tri)` blocks the compiler
+// sinks the first arithmetic on the loaded words into the block of the loads, i.e. waits for one record before it
+// requests the other: 448 lane-loads per wave iteration for 207 useful ones.)
+typedef float v4f __attribute__((ext_vector_type(4)));
+struct NodeRegs { v4f q0, q1, q2, q3; };
+struct TriRegs { v4f a, b, c; };
+
+// ---- bounded LDS stack with a deep store in HBM (DeviceScene.deep, fs_internal.hpp) ---------------------------
+// The logical stack of a lane is  deep[0, count)  followed by  LDS rows [sb, sp).  Entries move between the two in
+// chunks of kDeepChunk, oldest first out, newest first back, so pops keep their order.  All of it happens in ONE place,
+// trav_maintain, called at the top of a step for the lanes that need it; the pops and pushes of the step are the plain
+// LDS ones.  A lane with entries in the deep store carries T.sb = kDeepSb (-2; its real bottom is row 0 and it gives
+// nothing away to idle lanes meanwhile) and is kept at >= 2 LDS entries at the top of every step — a step pops at most
+// twice — so its pop test `sp > sb` never fails while the deep store still holds something.  One unsigned compare finds
+// both kinds of lane:  (unsigned)(sp + sb) >= limit - 4  (DeviceScene.stack_attn) is true for a lane close to its last rows (sb >= 0; two rows
+// early, or earlier for a lane that has given entries away — trav_maintain looks again) and for a flagged lane with
+// sp < 2 (sp - 2 wraps) or close to its last rows.  (Tests in the pops themselves cost 2 % of the walk, a deep count
+// read from LDS on every empty pop 7 %: profiles/r03_occupancy_ab.log.)
+constexpr int kDeepSb = -2;
+__device__ __forceinline__ int* trav_deep_count(const DeviceScene& sc, int* stack) { return stack + (size_t)sc.stack_limit * kBlock; }
+__device__ __forceinline__ void trav_deep_reset(const DeviceScene& sc, int* stack) {
+    if (sc.deep != nullptr) *trav_deep_count(sc, stack) = 0;
+}
+__device__ __forceinline__ bool trav_needs_maintenance(const DeviceScene& sc, const Trav& T) {
+    return (unsigned)(T.sp + T.sb) >= sc.stack_attn;   // stack_limit - 4 with a deep store, else never
+}
+// (rolled loops: these paths are as good as never taken, their code should stay small inside the traversal loop)
+__device__ __forceinline__ void trav_maintain(const DeviceScene& sc, Trav& T, int* stack) {
+    if (sc.deep == nullptr) return;   // (without a deep store stack_limit covers the tree's worst case)
+    int* cnt = trav_deep_count(sc, stack);
+    int32_t* col = sc.deep + (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (T.sb < 0) {
+        if (T.sp < 2) {   // the newest chunk comes back, below the entry that may be left
+            const int have = *cnt;
+            if (T.sp == 1) stack[kDeepChunk * kBlock] = stack[0];
+#pragma unroll 1
+            for (int i = 0; i < kDeepChunk; ++i) stack[i * kBlock] = col[(size_t)(have - kDeepChunk + i) * sc.deep_lanes];
+            T.sp += kDeepChunk;
+            *cnt = have - kDeepChunk;
+            if (have == kDeepChunk) T.sb = 0;
+            return;
+        }
+    } else if (T.sb > 0) {   // close the gap left by donated entries
+        const int n = T.sp - T.sb;
+#pragma unroll 1
+        for (int i = 0; i < n; ++i) stack[i * kBlock] = stack[(T.sb + i) * kBlock];
+        T.sb = 0; T.sp = n;
+    }
+    if (T.sp + 2 >= sc.stack_limit) {   // a node visit writes up to row sp + 2: the oldest chunk goes out
+        const int have = *cnt;
+#pragma unroll 1
+        for (int i = 0; i < kDeepChunk; ++i) col[(size_t)(have + i) * sc.deep_lanes] = stack[i * kBlock];
+#pragma unroll 1
+        for (int i = kDeepChunk; i < T.sp; ++i) stack[(i - kDeepChunk) * kBlock] = stack[i * kBlock];
+        T.sp -= kDeepChunk;
+        T.sb = kDeepSb;
+        *cnt = have + kDeepChunk;
+    }
+}
+// next pending entry into T.cur (kDone: none left)
+__device__ __forceinline__ void trav_pop(const DeviceScene& sc, Trav& T, int* stack) {
+    if (T.sp > T.sb) { --T.sp; T.cur = stack[T.sp * kBlock]; }
+    else T.cur = kDone;
+}
+
+__device__ __forceinline__ void trav_settle(const DeviceScene& sc, Trav& T, int* stack) {
+    if (T.tri_i >= T.tri_n && T.cur < 0 && T.cur != kDone) {
+        const int code = ~T.cur;
+        T.tri_i = code >> 2;
+        T.tri_n = T.tri_i + (code & 3) + 1;
+        trav_pop(sc, T, stack);
+    }
+}
+
+// The request.  ONE asm statement, executed by every lane that reaches it, with every destination register tied in and
+// out ("+v"): the lanes that want a record are selected by writing their ballot to EXEC inside the statement.  Both
+// matter.  (1) The compiler does not know that the destinations are still being written until the next trav_wait; with
+// conditionally executed "=v" outputs the old and the new value meet in a phi, and register allocation is free to
+// resolve that phi with copies placed right behind the request — reading registers whose data has not arrived (round 3
+// lost a day's first build to exactly that; tools/check_isa_hazards.py now proves the absence of such accesses on the
+// final ISA).  A tied operand chain issue -> wait -> use has no phi to resolve.  (2) Every wave executes the same
+// number of vector memory instructions per step whatever its lanes need, so counted waits stay possible.
+// (No cache-policy bits on these requests: measured, none helps — DESIGN.md section 5.)
+__device__ __forceinline__ void trav_issue(const DeviceScene& sc, const Trav& T, NodeRegs& N, TriRegs& X) {
+    const unsigned long long mn = __ballot(T.cur >= 0), mt = __ballot(T.tri_i < T.tri_n);   // subsets of EXEC
+    // (addresses of lanes that want nothing are never dereferenced)
+    const char* np = reinterpret_cast<const char*>(sc.nodes) + (size_t)(uint32_t)T.cur * sizeof(NodeQ4);
+    const Tri48* tp = sc.tris + (uint32_t)T.tri_i;
+    unsigned long long sv;
+    asm volatile("s_mov_b64 %[sv], exec\n\t"
+                 "s_mov_b64 exec, %[mn]\n\t"
+                 "global_load_dwordx4 %[q0], %[np], off\n\t"
+                 "global_load_dwordx4 %[q1], %[np], off offset:16\n\t"
+                 "global_load_dwordx4 %[q2], %[np], off offset:32\n\t"
+                 "global_load_dwordx4 %[q3], %[np], off offset:48\n\t"
+                 "s_mov_b64 exec, %[mt]\n\t"
+                 "s_cbranch_execz 1f\n\t"      // one wave step in four has no lane with a pending triangle
+                 "global_load_dwordx4 %[ta], %[tp], off\n\t"
+                 "global_load_dwordx4 %[tb], %[tp], off offset:16\n\t"
+                 "global_load_dwordx4 %[tc], %[tp], off offset:32\n"
+                 "1:\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [q0] "+&v"(N.q0), [q1] "+&v"(N.q1), [q2] "+&v"(N.q2), [q3] "+&v"(N.q3),
+                   [ta] "+&v"(X.a), [tb] "+&v"(X.b), [tc] "+&v"(X.c), [sv] "=&s"(sv)
+                 : [np] "v"(np), [tp] "v"(tp), [mn] "s"(mn), [mt] "s"(mt)
+                 : "memory");
+}
+
+__device__ __forceinline__ void trav_wait(NodeRegs& N, TriRegs& X) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(N.q0), "+v"(N.q1), "+v"(N.q2), "+v"(N.q3), "+v"(X.a), "+v"(X.b), "+v"(X.c));
+}
+
+// the triangle that arrived with this step (leaf-order index `tested`): Moeller-Trumbore, closest-hit update as selects
+template <bool ANY, bool IGN = false>
+__device__ __forceinline__ void trav_tri_part(const Ray& r, Trav& T, const TriRegs& X, const int tested,
+                                              uint32_t ignore_object = 0xFFFFFFFFu) {
+    const float4 a = make_float4(X.a.x, X.a.y, X.a.z, X.a.w), b = make_float4(X.b.x, X.b.y, X.b.z, X.b.w),
+                 c = make_float4(X.c.x, X.c.y, X.c.z, X.c.w);   // triangle: v0 | e1 | e2 (+ material, id, object)
+    float t = 0.0f;
+    // IGN: FCollisionQueryParams::AddIgnoredActor — triangles of one actor (object id in c.w) are skipped
+    bool hit = tri_hit(a, b, c, r, T.t, t);
+    if (IGN) hit = hit & (__float_as_uint(c.w) != ignore_object);
+    const uint32_t id = __float_as_uint(c.z);
+    if (ANY) {
+        if (hit) {
+            T.t = t; T.leaf_index = tested; T.id = id;
+            T.tri_i = 0; T.tri_n = 0; T.cur = kDone; T.sp = 0; T.sb = 0;  // first hit ends the query (records already requested are ignored)
+        }
+    } else {
+        // closest hit, ties to the lower input index — as selects, not branches.  (t, id) compares as ONE 64-bit
+        // key: t > 0, so its bits order like an integer, and a traversal without a hit yet carries id = ~0
+        // (equivalent to t < T.t | no hit yet | (t == T.t & id < T.id); one v_cmp_lt_u64 instead of five compares)
+        const unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | id;
+        const unsigned long long cur = ((unsigned long long)__float_as_uint(T.t) << 32) | T.id;
+        const bool better = hit & (key < cur);
+        T.t = better ? t : T.t;
+        T.leaf_index = better ? tested : T.leaf_index;
+        T.id = better ? id : T.id;
+    }
+}
+
+// the lane's inner node (T.cur >= 0): 4 child boxes, near-first order, far children to the stack, next node
+__device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray& r, Trav& T, int* stack, const NodeRegs& N) {
+    const float4 q0 = make_float4(N.q0.x, N.q0.y, N.q0.z, N.q0.w), q1 = make_float4(N.q1.x, N.q1.y, N.q1.z, N.q1.w),
+                 q2 = make_float4(N.q2.x, N.q2.y, N.q2.z, N.q2.w), q3 = make_float4(N.q3.x, N.q3.y, N.q3.z, N.q3.w);
+    // ---- 4-wide node, child boxes on the node's 8-bit grid: plane distance = fma(q, step*inv, (origin-o)*inv)
+    const float sx = q0.w * r.ix, sy = q2.z * r.iy, sz = q2.w * r.iz;   // grid step (a power of two) / direction
+    const float bx = fmaf(q0.x, r.ix, r.nox);
+    const float by = fmaf(q0.y, r.iy, r.noy);
+    const float bz = fmaf(q0.z, r.iz, r.noz);
+    const uint32_t lox = __float_as_uint(q1.x), loy = __float_as_uint(q1.y), loz = __float_as_uint(q1.z);
+    const uint32_t hix = __float_as_uint(q1.w), hiy = __float_as_uint(q2.x), hiz = __float_as_uint(q2.y);
+    // the ray's direction signs pick the entry / exit plane words once per node
+    const uint32_t nxw = r.ix < 0.0f ? hix : lox, fxw = r.ix < 0.0f ? lox : hix;
+    const uint32_t nyw = r.iy < 0.0f ? hiy : loy, fyw = r.iy < 0.0f ? loy : hiy;
+    const uint32_t nzw = r.iz < 0.0f ? hiz : loz, fzw = r.iz < 0.0f ? loz : hiz;
+    const v2f sx2 = {sx, sx}, sy2 = {sy, sy}, sz2 = {sz, sz}, bx2 = {bx, bx}, by2 = {by, by}, bz2 = {bz, bz};
+    uint32_t key[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        // (entry, exit) plane distances per axis as one packed fma each (v_pk_fma_f32)
+        const v2f qx = {(float)((nxw >> (8 * c)) & 0xFFu), (float)((fxw >> (8 * c)) & 0xFFu)};
+        const v2f qy = {(float)((nyw >> (8 * c)) & 0xFFu), (float)((fyw >> (8 * c)) & 0xFFu)};
+        const v2f qz = {(float)((nzw >> (8 * c)) & 0xFFu), (float)((fzw >> (8 * c)) & 0xFFu)};
+        const v2f tx = __builtin_elementwise_fma(qx, sx2, bx2);
+        const v2f ty = __builtin_elementwise_fma(qy, sy2, by2);
+        const v2f tz = __builtin_elementwise_fma(qz, sz2, bz2);
+        const float tnx = tx.x, tfx = tx.y, tny = ty.x, tfy = ty.y, tnz = tz.x, tfz = tz.y;
+        const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, 0.0f));
+        const float tf = fminf(fminf(tfx, tfy), fminf(tfz, T.t));
+        const bool h = tn <= tf;
+        // entry distance (>= 0, so its bits order like an integer) with the slot in the low 2 bits; a missed child
+        // sorts behind every hit one (kMissKey | slot)
+        key[c] = h ? ((__float_as_uint(tn) & ~3u) | (uint32_t)c) : (kMissKey | (uint32_t)c);
+    }
+    int ref0 = __float_as_int(q3.x), ref1 = __float_as_int(q3.y), ref2 = __float_as_int(q3.z),
+        ref3 = __float_as_int(q3.w);
+    // sort the 4 (key, child reference) pairs, nearest first: 5-comparator network, branch-free.  (Measured in
+    // round 2: choosing only the nearest child and pushing the rest in slot order — also no ordering at all for
+    // visibility rays — saves a dozen instructions per visit and costs as much in extra visits: walk 0.356 ->
+    // 0.361 ms, connect 0.075 -> 0.078 ms.)
+#define FS_CSWAP(a, b) { const bool sw_ = key[b] < key[a]; const uint32_t lo_ = min(key[a], key[b]); \
+                         const uint32_t hi_ = max(key[a], key[b]); key[a] = lo_; key[b] = hi_; \
+                         const int ra_ = sw_ ? ref##b : ref##a; const int rb_ = sw_ ? ref##a : ref##b; \
+                         ref##a = ra_; ref##b = rb_; }
+    FS_CSWAP(0, 1) FS_CSWAP(2, 3) FS_CSWAP(0, 2) FS_CSWAP(1, 3) FS_CSWAP(1, 2)
+#undef FS_CSWAP
+    // the number of children hit, read off the sorted keys: at least k + 1 <=> key[k] is a hit
+    const bool h1 = key[0] < kMissKey, h2 = key[1] < kMissKey, h3 = key[2] < kMissKey, h4 = key[3] < kMissKey;
+#ifdef FS_TRAV_STATS
+    atomicAdd(&g_trav_stats[5 + (h2 ? 2 : (h1 ? 1 : 0))], 1ull);   // [5] visits with no child hit, [6] one, [7] two or more
+#endif
+    // far children wait on the stack, farthest pushed first, at sp .. sp + hits - 2: with two hits all three stores
+    // land on sp and the last one (the second nearest) stays, with three hits the first two share sp — no store
+    // goes above the new top, so the stack needs exactly the tree's worst-case number of rows.  With fewer than two
+    // hits the three stores write (unused) words to the free row above the top: cheaper than branching around them,
+    // a wave nearly always has a lane that pushes.
+    const int p3 = T.sp;
+    const int p2 = p3 + (h4 ? 1 : 0);
+    const int p1 = p2 + (h3 ? 1 : 0);
+    stack[p3 * kBlock] = ref3;
+    stack[p2 * kBlock] = ref2;
+    stack[p1 * kBlock] = ref1;
+    T.sp = p1 + (h2 ? 1 : 0);
+    if (h1) T.cur = ref0;
+    else trav_pop(sc, T, stack);
+}
+
+// One whole step of a busy lane, in the pipelined order: node part, advance, request the next records (the
+// triangle into `nxt`), then the triangle part on `cur` while they are in flight.  Entry: the records of (T.cur,
+// T.tri_i) have arrived in (N, cur).
+template <bool ANY, bool IGN = false, bool COUNT = false>
+__device__ __forceinline__ void trav_advance(const DeviceScene& sc, const Ray& r, Trav& T, int* stack, NodeRegs& N,
+                                             TriRegs& cur, TriRegs& nxt, uint32_t ignore_object = 0xFFFFFFFFu) {
+    const bool has_tri = T.tri_i < T.tri_n;
+    const bool has_node = T.cur >= 0;
+    const int tested = T.tri_i;
+    if (COUNT) { T.nv += has_node ? 1u : 0u; T.nt += has_tri ? 1u : 0u; }
+#ifdef FS_TRAV_STATS   // diagnostic build only (tests/trav_stats.py): SIMD occupancy of the two step kinds
+    {
+        const unsigned long long mt = __ballot(has_tri), mn = __ballot(has_node);
+        unsigned long long* gs = g_trav_stats + (ANY ? 16 : 0);
+        if ((threadIdx.x & 63u) == (unsigned)(__ffsll((long long)__ballot(true)) - 1)) {
+            atomicAdd(&gs[0], 1ull);
+            if (mn) { atomicAdd(&gs[1], 1ull); atomicAdd(&gs[2], (unsigned long long)__popcll(mn)); }
+            if (mt) { atomicAdd(&gs[3], 1ull); atomicAdd(&gs[4], (unsigned long long)__popcll(mt)); }
+            atomicAdd(&gs[11], (unsigned long long)__popcll(mn & mt));
+        }
+    }
+#endif
+    // bounded LDS stack: a node visit writes up to row sp + 2.  Checked here, ahead of the node arithmetic and as one
+    // scalar branch for the wave, so that the node part stays a single basic block; lanes of trees without a deep store
+    // (stack_limit = worst case + 1) may pass the test near their worst case and return at once.
+#ifndef FS_DEEP_NO_CHECK   // compiled out in the wide flavour of the frame kernel (worst-case rows, fs_frame.hip)
+    if (__builtin_expect(__ballot(trav_needs_maintenance(sc, T)) != 0ull, 0)) {
+        if (trav_needs_maintenance(sc, T)) trav_maintain(sc, T, stack);
+    }
+#endif
+    if (has_node) trav_node_part(sc, r, T, stack, N);
+    if (has_tri) ++T.tri_i;
+    trav_settle(sc, T, stack);
+    if (COUNT) {   // counting instantiation only: how coherent is this wave's node request?  lanes that take part, distinct 64-B records among them
+        const unsigned long long mn = __ballot(T.cur >= 0);
+        if (mn != 0ull) {
+            unsigned distinct = 0;
+            for (unsigned long long rest = mn; rest != 0ull; rest &= rest - 1ull) {
+                const int l = __ffsll((long long)rest) - 1;
+                const int v = __builtin_amdgcn_readlane(T.cur, l);
+                const unsigned long long same = __ballot(T.cur == v) & mn;
+                distinct += (__ffsll((long long)same) - 1) == l ? 1u : 0u;
+            }
+            if ((threadIdx.x & 63u) == (unsigned)(__ffsll((long long)__ballot(true)) - 1)) {
+                T.ni += 1u; T.nl += (uint32_t)__popcll(mn); T.nd += distinct;
+            }
+        }
+    }
+    trav_issue(sc, T, N, nxt);
+    // the triangle test must stay BEHIND the requests: it is plain arithmetic on registers, which the compiler would
+    // otherwise move in front of the (to it unrelated) load instructions — and then fold the two register sets into one
+    asm volatile("" : "+v"(cur.a), "+v"(cur.b), "+v"(cur.c));
+    if (has_tri) trav_tri_part<ANY, IGN>(r, T, cur, tested, ignore_object);
+}
+
+// Before a traversal returns, every record it has requested must have landed: the compiler knows nothing of loads in
+// flight and would hand their destination registers to other values (an any-hit query ends with requests outstanding).
+__device__ __forceinline__ void trav_drain(NodeRegs& N, TriRegs& X, TriRegs& Y) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(N.q0), "+v"(N.q1), "+v"(N.q2), "+v"(N.q3), "+v"(X.a), "+v"(X.b), "+v"(X.c),
+                                        "+v"(Y.a), "+v"(Y.b), "+v"(Y.c));
+}
+
+// one ray per lane without work sharing (tests, tools, diagnostic builds); returns the number of steps taken
+template <bool ANY, bool IGN = false>
+__device__ __forceinline__ int trav_run(const DeviceScene& sc, const Ray& r, Trav& T, int* stack,
+                                        uint32_t ignore_object = 0xFFFFFFFFu) {
+    NodeRegs N;
+    TriRegs X, Y;
+    int steps = 0;
+    trav_settle(sc, T, stack);
+    trav_issue(sc, T, N, X);
+    // The loop is wave-uniform (lanes whose ray is finished idle along): a per-lane exit would make the compiler carry
+    // every lane's register sets out of the loop through copies — of registers that may still be in flight.
+    while (true) {
+        if (__ballot(trav_busy(T)) == 0ull) break;
+        trav_wait(N, X);
+        if (trav_busy(T)) { trav_advance<ANY, IGN>(sc, r, T, stack, N, X, Y, ignore_object); ++steps; }
+        if (__ballot(trav_busy(T)) == 0ull) break;
+        trav_wait(N, Y);
+        if (trav_busy(T)) { trav_advance<ANY, IGN>(sc, r, T, stack, N, Y, X, ignore_object); ++steps; }
+    }
+    trav_drain(N, X, Y);
+    return steps;
+}
+
+// ImpactNormal: the record's unit geometric normal, flipped to face the ray origin side; material of the hit
+__device__ __forceinline__ void hit_surface(const DeviceScene& sc, int leaf_index, const Ray& r, float& nx, float& ny,
+                                            float& nz, uint32_t& mat) {
+    const float4 c = sc.tris[leaf_index].c;
+    const float4 d = sc.tri_nrm[leaf_index];
+    float x = d.x, y = d.y, z = d.z;
+    float dn = fmaf(x, r.dx, fmaf(y, r.dy, z * r.dz));
+    if (dn > 0.0f) { x = -x; y = -y; z = -z; }
+    nx = x; ny = y; nz = z;
+    mat = __float_as_uint(c.y);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Wave work sharing for closest-hit AND any-hit queries (one implementation, three instantiations).
+//
+// The rays of a wave need very different numbers of traversal steps (median 19, p99 40) and the wave waits for
+// its slowest ray in every bounce.  A query parallelises: disjoint subtrees can be searched by different lanes.
+// So a lane that has finished its own ray takes the OLDEST pending subtree (bottom of the stack: the one its
+// owner would reach last) from a lane that still has pending entries, traverses it with that lane's ray and
+// reports into the owner's LDS mailbox.  All of it happens inside one wave (lock-step), without atomics on the stacks.
+//   closest hit (ANY = false): the partial answers merge by atomicMin on the 64-bit key (t bits << 32 | triangle
+//     id) — exactly the (t, id) order a single traversal applies, so the result does not depend on who searched
+//     what; a taken subtree starts from min(donor's bound, owner's mailbox).
+//   any hit (ANY = true): most connection rays are blocked and end at their first hit, the unobstructed ones must
+//     search every box along the segment; a hit anywhere settles the ray (flag in the owner's mailbox) and lanes
+//     still searching for a settled ray drop their work.
+//   IGN: FCollisionQueryParams::AddIgnoredActor per ray (legacy tracer).
+// LDS rows of kBlock words: rays (closest: origin, direction, reciprocals = 9 rows, the thief recomputes -o*inv;
+// any: origin, direction, tmax = 7 rows — the thief recomputes the reciprocals too, 40 B per lane keep two connect
+// workgroups on a CU next to the histogram) | [ignored actor] | mailbox (closest: u64 key + leaf; any: blocked flag) | donation boxes ref,
+// owner [, bound].  Every lane of the wave must call it (has_ray = false: nothing of its own, helps from the start).
+// ---------------------------------------------------------------------------------------------------
+template <bool ANY, bool IGN>
+struct ShareArea {
+    static constexpr int kRayRows = ANY ? 7 : 9;
+    static constexpr int kRows = kRayRows + (IGN ? 1 : 0) + (ANY ? 1 : 3) + 2 + (ANY ? 0 : 1);
+    static constexpr size_t kBytes = (size_t)kBlock * 4 * kRows;
+    float* rs; uint32_t* rign; unsigned long long* rkey; int* rleaf; int* blocked; int* dref; int* down; float* dbound;
+    __device__ __forceinline__ explicit ShareArea(int* base) {
+        rs = reinterpret_cast<float*>(base);
+        int* p = base + kRayRows * kBlock;
+        rign = reinterpret_cast<uint32_t*>(p); if (IGN) p += kBlock;
+        rkey = reinterpret_cast<unsigned long long*>(p); blocked = p; rleaf = p + 2 * kBlock;
+        p += (ANY ? 1 : 3) * kBlock;
+        dref = p; down = p + kBlock; dbound = reinterpret_cast<float*>(p + 2 * kBlock);
+    }
+};
+constexpr size_t kShareLdsBytes = ShareArea<false, false>::kBytes;      // 60 B per lane
+// The sharing round (ballots, donation boxes, the thieves' ray reload: ~50 VALU + ~35 SALU for the whole wave) runs only
+// once this many lanes have nothing to do: feeding the first few idle lanes costs every lane more than it returns.
+// Measured at cfg3 (profiles/r02_share_min_idle.log): 1 / 4 / 8 / 16 / 24 / 32 / 48 -> walk 0.304 / 0.303 / 0.298 /
+// 0.294 / 0.300 / 0.309 / 0.334 ms, connect 0.075 -> 0.072 ms at 16.  Sparse waves start above it.
+// (again on round 5's fused stream, profiles/r05_share_min_idle.log: 8 / 12 / 16 / 20 / 24 -> 971 / 981 / 988 / 981 / 975 M rays/s.)
+constexpr int kShareMinIdle = 16;
+constexpr size_t kShareAnyLdsBytes = ShareArea<true, false>::kBytes;    // 40 B per lane
+constexpr size_t kShareIgnLdsBytes = ShareArea<false, true>::kBytes;    // 64 B per lane
+
+// returns: ANY — the ray is blocked; closest — a hit was found (T.t, T.id, T.leaf_index describe it)
+template <bool ANY, bool IGN, bool COUNT = false>
+__device__ __forceinline__ bool trav_shared(const DeviceScene& sc, bool has_ray, const Ray& own, float tmax,
+                                            uint32_t ignore, Trav& T, int* stack, int* share) {
+    const ShareArea<ANY, IGN> A(share);
+    float* rs = A.rs;
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wbase = tid & ~63u;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    // publish this lane's ray and clear its mailbox
+    rs[0 * kBlock + tid] = own.ox;  rs[1 * kBlock + tid] = own.oy;  rs[2 * kBlock + tid] = own.oz;
+    rs[3 * kBlock + tid] = own.dx;  rs[4 * kBlock + tid] = own.dy;  rs[5 * kBlock + tid] = own.dz;
+    if (ANY) {
+        rs[6 * kBlock + tid] = tmax;
+        A.blocked[tid] = 0;
+    } else {
+        rs[6 * kBlock + tid] = own.ix;  rs[7 * kBlock + tid] = own.iy;  rs[8 * kBlock + tid] = own.iz;
+        A.rkey[tid] = ~0ull;
+        A.rleaf[tid] = -1;
+    }
+    if (IGN) A.rign[tid] = ignore;
+    unsigned owner = tid;   // block-local lane whose ray this lane is working on
+    uint32_t wign = ignore;
+    Ray wr = own;
+    trav_init(T, tmax, has_ray && sc.num_nodes > 0);
+    trav_deep_reset(sc, stack);
+    // The records of the NEXT step are requested as soon as this step has decided what they are: behind the node part
+    // of the step, before its triangle test (trav_advance) and before the work-sharing round below (ballots, donation
+    // boxes, mailboxes: half a dozen LDS round trips), which both run in the shadow of the fetch.  A wave in the thin
+    // tail of the frame runs alone on its SIMD and nothing else hides that latency.  Lanes that take work in the round
+    // request theirs at its end.  The triangle records alternate between two register sets (the loop body is
+    // instantiated twice): the one being tested is still needed while the next one is already arriving.
+    NodeRegs N;
+    TriRegs X, Y;
+    trav_settle(sc, T, stack);
+    trav_issue(sc, T, N, X);
+    // one step of the wave; cur = the triangle registers that arrive with this step, nxt = the ones requested for the
+    // next.  true = nothing is left anywhere in the wave.
+    auto step = [&](TriRegs& cur, TriRegs& nxt) -> bool {
+        trav_wait(N, cur);
+#ifdef FS_TRAV_STATS
+        {
+            const unsigned long long mb = __ballot(trav_busy(T)), mth = __ballot(trav_busy(T) && owner != tid);
+            if (lane == 0u) {
+                unsigned long long* gs = g_trav_stats + (ANY ? 16 : 0);
+                atomicAdd(&gs[8], (unsigned long long)__popcll(mb)); atomicAdd(&gs[9], (unsigned long long)__popcll(mth));
+                atomicAdd(&gs[10], 1ull);
+            }
+        }
+#endif
+        if (trav_busy(T)) {
+            trav_advance<ANY, IGN, COUNT>(sc, wr, T, stack, N, cur, nxt, wign);
+            if (ANY) {
+                if (T.leaf_index >= 0) { A.blocked[owner] = 1; T.leaf_index = -1; }   // first hit ends the query (T is idle now)
+                else if (A.blocked[owner]) { T.cur = kDone; T.sp = 0; T.sb = 0; T.tri_i = 0; T.tri_n = 0; }   // settled by another lane
+            } else if (!trav_busy(T) && T.leaf_index >= 0) {   // this (sub)traversal is over: report to the owner of the ray
+                const unsigned long long key = ((unsigned long long)__float_as_uint(T.t) << 32) | (unsigned long long)T.id;
+                atomicMin(&A.rkey[owner], key);
+                if (A.rkey[owner] == key) A.rleaf[owner] = T.leaf_index;
+            }
+        }
+        const bool idle = !trav_busy(T);
+        const unsigned long long busy_m = __ballot(!idle);
+        if (busy_m == 0ull) return true;                // nothing left anywhere in the wave
+        const unsigned long long idle_m = __ballot(idle);
+        if (__popcll(idle_m) < kShareMinIdle) return false;
+        const bool can_give = !idle && T.sp > T.sb && T.sb >= 0;   // (a lane with entries in the deep store keeps what it has)
+        const unsigned long long give_m = __ballot(can_give);
+        if (idle_m != 0ull && give_m != 0ull) {
+            const int n = min(__popcll(idle_m), __popcll(give_m));
+            if (can_give) {
+                const int r = __popcll(give_m & lt);
+                if (r < n) {
+                    A.dref[wbase + r] = stack[T.sb * kBlock];
+                    A.down[wbase + r] = (int)owner;
+                    if (!ANY) A.dbound[wbase + r] = T.t;
+                    ++T.sb;
+                    if (T.sb == T.sp) { T.sb = 0; T.sp = 0; }
+                }
+            }
+            if (idle) {
+                const int r = __popcll(idle_m & lt);
+                if (r < n) {
+                    const int e = A.dref[wbase + r];
+                    owner = (unsigned)A.down[wbase + r];
+                    float bound;
+                    if (ANY) {
+                        wr = make_ray(rs[0 * kBlock + owner], rs[1 * kBlock + owner], rs[2 * kBlock + owner],
+                                      rs[3 * kBlock + owner], rs[4 * kBlock + owner], rs[5 * kBlock + owner]);
+                        bound = rs[6 * kBlock + owner];
+                    } else {
+                        // the owner's mailbox may already hold a closer hit than the donor knew of
+                        bound = __uint_as_float(min(__float_as_uint(A.dbound[wbase + r]), (uint32_t)(A.rkey[owner] >> 32)));
+                        wr.ox = rs[0 * kBlock + owner];  wr.oy = rs[1 * kBlock + owner];  wr.oz = rs[2 * kBlock + owner];
+                        wr.dx = rs[3 * kBlock + owner];  wr.dy = rs[4 * kBlock + owner];  wr.dz = rs[5 * kBlock + owner];
+                        wr.ix = rs[6 * kBlock + owner];  wr.iy = rs[7 * kBlock + owner];  wr.iz = rs[8 * kBlock + owner];
+                        wr.nox = -(wr.ox * wr.ix); wr.noy = -(wr.oy * wr.iy); wr.noz = -(wr.oz * wr.iz);   // as make_ray
+                    }
+                    if (IGN) wign = A.rign[owner];
+                    T.cur = e; T.sp = 0; T.sb = 0; T.tri_i = 0; T.tri_n = 0;
+                    T.t = bound; T.leaf_index = -1; T.id = 0xFFFFFFFFu;
+                    trav_deep_reset(sc, stack);   // (an any-hit query that ended early may have left entries there)
+                    trav_settle(sc, T, stack);
+                    trav_issue(sc, T, N, nxt);
+                }
+            }
+        }
+        return false;
+    };
+    while (true) {
+        if (step(X, Y)) break;
+        if (step(Y, X)) break;
+    }
+    trav_drain(N, X, Y);
+    if (ANY) return A.blocked[tid] != 0;
+    // everything searched: the mailbox holds the closest hit of this lane's own ray
+    const unsigned long long key = A.rkey[tid];
+    if (key != ~0ull) {
+        T.t = __uint_as_float((uint32_t)(key >> 32));
+        T.id = (uint32_t)key;
+        T.leaf_index = A.rleaf[tid];
+        return true;
+    }
+    T.t = tmax;
+    T.leaf_index = -1;
+    T.id = 0xFFFFFFFFu;
+    return false;
+}
+// the three uses: BDPT walk, ConnectSubpaths' visibility ray, legacy tracer
+template <bool COUNT = false, bool IGN = false>
+__device__ __forceinline__ void trav_run_shared(const DeviceScene& sc, const Ray& own, Trav& T, int* stack, int* s_dyn,
+                                                float tmax, bool has_ray = true, uint32_t ignore = 0xFFFFFFFFu) {
+    trav_shared<false, IGN, COUNT>(sc, has_ray, own, tmax, ignore, T, stack, s_dyn + (size_t)sc.stack_rows * kBlock);
+}
+template <bool COUNT = false>
+__device__ __forceinline__ bool trav_any_shared(const DeviceScene& sc, bool has_ray, const Ray& own, float tmax,
+                                                int* stack, int* share, uint32_t* nv = nullptr, uint32_t* nt = nullptr) {
+    Trav T;
+    const bool blocked = trav_shared<true, false, COUNT>(sc, has_ray, own, tmax, 0xFFFFFFFFu, T, stack, share);
+    if (COUNT) { *nv += T.nv; *nt += T.nt; }
+    return blocked;
+}
+// COUNT instantiations: this lane's record fetches -> the frame scratch's work counters (one atomic per lane: the
+// counting frames are not timed)
+__device__ __forceinline__ void add_fetch_counts(unsigned* scratch, int first_counter, uint32_t nv, uint32_t nt) {
+    unsigned long long* counters = reinterpret_cast<unsigned long long*>(scratch + kCounterWord);
+    if (nv) atomicAdd(&counters[first_counter], (unsigned long long)nv);
+    if (nt) atomicAdd(&counters[first_counter + 1], (unsigned long long)nt);
+}
+
+}  // namespace
+}  // namespace fs

@@ -31,7 +31,11 @@
 #else
 #define FS_LAUNCH_FRAME launch_frame_narrow
 #endif
-#include "fs_device.hpp"
+#include "fs_dev_walk.hpp"
+#include "fs_dev_coop.hpp"
+#include "fs_dev_connect.hpp"
+#include "fs_dev_recon.hpp"
+#include "fs_launch.hpp"
 
 namespace fs {
 namespace {
@@ -211,7 +215,7 @@ bool FS_LAUNCH_FRAME(int B, const DeviceScene& sc, const FrameParts& f, hipStrea
         lds = std::max(lds, sizeof(float) * ((size_t)f.recon_nb + (size_t)kBlock * (kChunk + 1)));   // the amplitudes | the block's samples staged for 16-byte stores
         a.recon_carrier = f.recon_carrier;
         if (f.recon_carrier)   // reconstruct_spectral_row: reconstruct_body_fast's layout
-            lds = std::max(lds, sizeof(float) * ((size_t)f.recon_nb + (size_t)kBlock * kChunk + kWarm + (size_t)kBlock * (kChunk + 1)));
+            lds = std::max(lds, sizeof(float) * ((size_t)f.recon_nb + (size_t)kReconBlockSamples + kWarm + (size_t)kBlock * (kChunk + 1)));
     }
     if (blocks == 0) return false;
     if (blocks_only) { *blocks_only = blocks; return true; }

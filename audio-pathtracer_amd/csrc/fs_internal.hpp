@@ -53,7 +53,7 @@ struct alignas(16) Tri48 {
 };
 static_assert(sizeof(Tri48) == 48, "Tri48 must be 48 B");
 
-// What the cooperative traversal of small frames reads (fs_device.hpp: trav_coop): one 16-byte record per CHILD — a lane
+// What the cooperative traversal of small frames reads (fs_dev_coop.hpp: trav_coop): one 16-byte record per CHILD — a lane
 // tests one child box per step and fetches exactly its own record, with one ds_read_b128 (the first DeviceScene.lds_nodes
 // nodes of the breadth-first array are staged in LDS by every workgroup) or one global_load_dwordx4 — derived from the
 // NodeQ4 array after every commit and refit (fs_refit.hip: coop_nodes_kernel):
@@ -92,6 +92,11 @@ constexpr float kCoopMaxCoordinate = 16384.0f;   // largest |coordinate| (UE uni
 constexpr int kStackDepth = 64;   // largest worst-case stack need the builder accepts before it rebuilds shallower
 constexpr int kStackSlack = 1;
 constexpr int kBlock = 256;       // 4 waves of 64 lanes
+// Reconstruct (fs_dev_recon.hpp): a thread filters kChunk consecutive samples, a workgroup one block of kReconBlockSamples.
+// A zero-block mask word of a host ring slot has one bit per such block (host_block_vote; the host: slot_masks_usable).
+constexpr int kChunk = 16;
+constexpr int kReconBlockSamples = kBlock * kChunk;   // 4 096
+static_assert(64 % kChunk == 0, "carrier_stride (below) must hold whole chunks");
 // LDS-privatised part of the [bands][bins] energy histogram in the connect kernels.  With the reference's distance
 // scale (cm / 1000, ARTS.cpp:373) bin = path length in metres / 3.43: 256 bins cover 878 m, and a 262 144-ray frame
 // at cfg3 touches bins 0..60.  All 1000 bins cost 32 KB per workgroup at 8 bands — the 8 KB window keeps three
@@ -116,11 +121,11 @@ struct DeviceScene {
                               //   worst case + 1, nothing can overflow), else kStackRowsCap (more goes to `deep`)
     // Deep store (only for trees whose worst case exceeds kStackRowsCap rows): [deep_rows][deep_lanes] ints in HBM, column
     // blockIdx.x * kBlock + threadIdx.x.  A lane whose LDS rows are full moves its oldest entries there in chunks and
-    // takes them back when its LDS rows run low (fs_device.hpp: trav_maintain).  The worst case assumes
+    // takes them back when its LDS rows run low (fs_dev_trav.hpp: trav_maintain).  The worst case assumes
     // that a ray hits every child box at every level of the deepest path; rays that need more than kStackRowsCap rows
     // are rare enough that the trips to HBM do not show, and the bounded LDS stack lets four workgroups share a CU.
     uint32_t stack_attn;      // stack_limit - 4 with a deep store, else 0x7FFFFFFF: (unsigned)(sp + sb) >= stack_attn sends a
-                              //   lane to trav_maintain at the top of a step (fs_device.hpp)
+                              //   lane to trav_maintain at the top of a step (fs_dev_trav.hpp)
     int32_t stack_worst;      // rows of a stack that cannot overflow (worst case + 1) if a workgroup may have that much LDS, else
                               //   0: what the wide flavour of the frame kernel runs with (fs_frame.hip)
     const struct CoopInfo* coop_info;   // host bookkeeping: the cooperative traversal's node arrays (CoopView below); unused on the device
@@ -166,10 +171,7 @@ struct KParams {
                            // straight to the energy buffer with global atomics (kHistWindow, or all bins if fewer)
 };
 
-#ifndef FS_PLAN_COOP_MAX_UNCAPPED
-#define FS_PLAN_COOP_MAX_UNCAPPED (1u << 17)
-#endif
-constexpr uint32_t kPlanCoopMax = 32768, kPlanCoopMaxUncapped = FS_PLAN_COOP_MAX_UNCAPPED;   // KParams.plan_coop (fs_device.hpp: plan_coop_body)
+constexpr uint32_t kPlanCoopMax = 32768, kPlanCoopMaxUncapped = 1u << 17;   // KParams.plan_coop (fs_dev_walk.hpp: plan_coop_body)
 
 // legacy forward tracer (UpdateSound) constants and device-side accumulators
 struct SoundKParams {
@@ -323,7 +325,7 @@ struct FrameParts {
     const struct ReconItem* recon_tab = nullptr;
     int recon_B = 0, recon_nb = 0, recon_samples = 0;
     const float* recon_carrier = nullptr;   // the context's carriers if some item is spectral: the fused kernel's spectral instantiation
-    // the publish of those host slots (fs_device.hpp: publish_arrive): the ticket cell, the pinned host word, this launch's id (tickets == nullptr: by an event)
+    // the publish of those host slots (fs_dev_recon.hpp: publish_arrive): the ticket cell, the pinned host word, this launch's id (tickets == nullptr: by an event)
     PublishWord pub;
 };
 bool launch_frame(int B, const DeviceScene& sc, const FrameParts& f, hipStream_t s);
@@ -347,7 +349,7 @@ void launch_connect(int B, const DeviceScene& sc, const KParams& kp, const Subpa
 void launch_connect_all(int B, const DeviceScene& sc, const KParams& kp, const SubpathState& st, float* energy,
                         unsigned long long* fixed, unsigned* queue_head, hipStream_t s);
 void launch_fixed_to_energy(const unsigned long long* fixed, float* energy, int words, hipStream_t s);
-// carrier != nullptr (FS_FLAG_SPECTRAL_IR): row B is the spectral channel from the [B][carrier_stride] carrier set (fs_device.hpp:
+// carrier != nullptr (FS_FLAG_SPECTRAL_IR): row B is the spectral channel from the [B][carrier_stride] carrier set (fs_dev_recon.hpp:
 // reconstruct_spectral_row); the band rows are the same either way
 void launch_reconstruct(const float* energy, int B, int num_bins, int sample_rate, int num_samples, int spb,
                         float* ir_bands, float* ir_mono, hipStream_t s, const float* carrier = nullptr);

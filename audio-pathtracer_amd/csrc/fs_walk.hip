@@ -4,7 +4,9 @@
 //                      also FlushEnergyBuffer (:157-161).
 //   walk_kernel_*      _shared: one subpath per lane, length-sorted schedule, closest-hit queries shared within the wave
 //                      (default);  _sparse: the same on waves that own only a few subpaths (small frames).
-#include "fs_device.hpp"
+#include "fs_dev_walk.hpp"
+#include "fs_dev_coop.hpp"
+#include "fs_launch.hpp"
 
 namespace fs {
 namespace {
@@ -79,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void walk_kernel_coop(DeviceScene sc, CoopV
     walk_coop_body<LOBES, COUNT, EXT>(blockIdx.x, sc, cv, kp, st, scratch, perm, rays_per_wave, stage, lane);
 }
 // the default instantiation with eight waves per workgroup: one workgroup per CU keeps sixteen hundred more resident
-// records in its LDS than two workgroups of four waves could (fs_device.hpp: coop_lds_bytes)
+// records in its LDS than two workgroups of four waves could (fs_launch.hpp: coop_lds_bytes)
 constexpr int kCoopBigWaves = 8;
 __global__ __launch_bounds__(64 * kCoopBigWaves) void walk_kernel_coop_big(DeviceScene sc, CoopView cv, KParams kp, SubpathState st,
                                                                            const unsigned* __restrict__ scratch,

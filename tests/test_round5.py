@@ -1,5 +1,5 @@
 """Round 5: the streamed path publishes its impulse responses from the launch itself (ring slot writes by the reconstruct
-workgroups + a pinned host word, csrc/fs_device.hpp: publish_arrive) — the reference's contract is that the IR is in the
+workgroups + a pinned host word, csrc/fs_dev_recon.hpp: publish_arrive) — the reference's contract is that the IR is in the
 component's buffer when ReconstructImpulseResponse returns (FrequenSeeAudioComponent.cpp:377-378) and GetImpulseResponse
 reads that buffer (FrequenSeeAudioComponent.h:113).  Results must not depend on which of the three publish mechanisms
 (host word / tail-stream batch event / tail-stream copy + event) carried a frame."""
@@ -345,7 +345,7 @@ def test_small_frames_far_from_the_origin(pkg, oracle_mod, scene_factory):
 @pytest.mark.parametrize("path", ["waited", "streamed"])
 def test_zero_blocks_of_the_ring_slots_are_rewritten_when_they_must_be(pkg, scene_factory, path):
     """The reconstruct workgroups skip the host write of a 4 096-sample block whose samples are all exactly zero when the ring
-    slot's block is known to be zero already (csrc/fs_device.hpp: host_block_wanted; a room's IR ends after a quarter of the
+    slot's block is known to be zero already (csrc/fs_dev_recon.hpp: host_block_wanted; a room's IR ends after a quarter of the
     second).  The published IR must not depend on what the slot held eight publishes ago: energies with deposits in LATE bins
     (every block non-zero) and in early bins only alternate in runs longer and shorter than the ring, through the batch kernel
     (waited-for reconstructs), the fused launch (streamed frames with an installed energy buffer are not traced, so the streamed

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic (not a test, not the product build): SIMD occupancy of the traversal loop's two step kinds.
-Builds a -DFS_TRAV_STATS copy of libfrequensee.so into gpurun_out/ and runs one cfg3 frame through it.
+Builds a -DFS_TRAV_STATS copy of libfrequensee.so into tools/tmp/stats/ (tools/build_variant.sh: the one-unit
+fs_kernels_all.hip build) and runs one cfg3 frame through it.
 usage (GPU box): python tests/trav_stats.py"""
 import ctypes as C
 import json
@@ -10,14 +11,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-out = os.path.join(ROOT, "gpurun_out", "stats_build")
-os.makedirs(out, exist_ok=True)
-src = os.path.join(ROOT, "audio-pathtracer_amd", "csrc")
-subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-                "-munsafe-fp-atomics", "--offload-arch=gfx950", "-DFS_TRAV_STATS", "-shared", "-o",
-                os.path.join(out, "libfrequensee.so"), "-x", "hip", os.path.join(src, "fs_capi.cpp"),
-                os.path.join(src, "fs_bvh.cpp"), os.path.join(src, "fs_kernels.hip"), os.path.join(src, "fs_fft.hip"),
-                os.path.join(src, "fs_refit.hip"), os.path.join(src, "fs_build.hip")], check=True)
+subprocess.run(["bash", os.path.join("tools", "build_variant.sh"), "stats", "-DFS_TRAV_STATS"], cwd=ROOT, check=True)
+out = os.path.join(ROOT, "tools", "tmp", "stats")
 import __graft_entry__ as graft  # noqa: E402
 pkg = graft.load_package()
 pkg._capi.LIB_PATH = os.path.join(out, "libfrequensee.so")
