@@ -393,7 +393,7 @@ void launch_reconstruct(const float* energy, int B, int num_bins, int sample_rat
     (void)sample_rate;
     int chunks = (num_samples + kChunk - 1) / kChunk;
     dim3 grid((chunks + kBlock - 1) / kBlock, B + 1);
-    const size_t lds = sizeof(float) * ((size_t)num_bins + (size_t)kReconBlockSamples + kWarm + (size_t)kBlock * (kChunk + 1));
+    const size_t lds = recon_lds_bytes(num_bins);
     if (carrier) {
         allow_lds(reconstruct_kernel<true>, lds);
         hipLaunchKernelGGL(reconstruct_kernel<true>, grid, dim3(kBlock), lds, s, energy, B, num_bins, num_samples, spb, ir_bands, ir_mono, carrier);
@@ -407,7 +407,7 @@ void launch_reconstruct_batch(const ReconItem* table, int count, int B, int num_
                               const float* carrier) {
     if (count <= 0) return;
     const uint32_t chunks = (uint32_t)((num_samples + kChunk - 1) / kChunk), cb = (chunks + kBlock - 1) / kBlock;
-    const size_t lds = sizeof(float) * ((size_t)num_bins + (size_t)kReconBlockSamples + kWarm + (size_t)kBlock * (kChunk + 1));
+    const size_t lds = recon_lds_bytes(num_bins);
     bool spectral = false;   // (the table is pinned host memory the host has just written)
     for (int i = 0; i < count && carrier != nullptr; ++i) spectral = spectral || table[i].spectral != 0;
     const dim3 grid((uint32_t)count * (uint32_t)(B + 1) * cb);

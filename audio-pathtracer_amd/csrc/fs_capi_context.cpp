@@ -544,11 +544,16 @@ int fs_context_create(const fs_config* cfg, fs_context** out) {
     int lds = 0;
     if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, c.device) == hipSuccess && lds > 0)
         ctx->lds_limit = (size_t)lds;
-    // the reconstruct kernel stages one amplitude per bin in LDS; the traversal kernels' need depends on the tree and is
-    // checked at fs_scene_commit
-    if (sizeof(float) * (size_t)ctx->num_bins > ctx->lds_limit || ctx->num_bins < 1 || ctx->num_samples < 1)
+    // a reconstruct workgroup stages one amplitude per bin in LDS next to its block of samples (recon_lds_bytes); the traversal
+    // kernels' need depends on the tree and is checked at fs_scene_commit
+    if (ctx->num_bins < 1 || ctx->num_samples < 1)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "simulated_duration, bin_duration and sample_rate give " + std::to_string(ctx->num_bins) +
+                         " bins and " + std::to_string(ctx->num_samples) + " samples: at least one of each is needed");
+    if (ctx->num_bins > max_recon_bins(ctx->lds_limit))
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "simulated_duration / bin_duration give " + std::to_string(ctx->num_bins) +
-                         " bins: more than the reconstruct kernel can stage in the device's LDS");
+                         " bins: the reconstruct needs " + std::to_string(recon_lds_bytes(ctx->num_bins) + kReconStaticLdsReserve) +
+                         " B of LDS per workgroup, the device offers " + std::to_string(ctx->lds_limit) + " (at most " +
+                         std::to_string(max_recon_bins(ctx->lds_limit)) + " bins)");
 #ifdef FS_EXPERIMENTS
     if (const char* v = std::getenv("FS_WALK_VARIANT")) ctx->walk.variant = std::atoi(v) == 0 ? 0 : 2;
 #endif

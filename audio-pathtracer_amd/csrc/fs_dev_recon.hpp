@@ -8,8 +8,7 @@ namespace {
 
 // ReconstructImpulseResponse (FSAC.cpp:320-380) for one row (band, or row B = the band mean = the channel view) and one block
 // of kBlock chunks of kChunk samples; s_amp: [nb] floats of LDS.  Shared by reconstruct_kernel (tail stream) and the
-// reconstruct part of the fused frame kernel (fs_frame.hip).
-constexpr int kWarm = 96;
+// reconstruct part of the fused frame kernel (fs_frame.hip).  kWarm: fs_internal.hpp.
 // A publish without the host's help: the reconstruct workgroups of a launch write the channel views straight into the sources'
 // pinned host ring slots; every one of them, once its stores have been acknowledged, takes a ticket, and the workgroup that takes
 // the last one stores the launch's id into the context's pinned host word — fs_get_impulse_response* and the ring's back-pressure

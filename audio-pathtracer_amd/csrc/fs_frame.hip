@@ -212,10 +212,9 @@ bool FS_LAUNCH_FRAME(int B, const DeviceScene& sc, const FrameParts& f, hipStrea
         const uint32_t chunks = (uint32_t)((f.recon_samples + kChunk - 1) / kChunk);
         a.recon_cb = (chunks + kBlock - 1) / kBlock;
         blocks += (uint32_t)f.num_recon * (uint32_t)(f.recon_B + 1) * a.recon_cb;
-        lds = std::max(lds, sizeof(float) * ((size_t)f.recon_nb + (size_t)kBlock * (kChunk + 1)));   // the amplitudes | the block's samples staged for 16-byte stores
         a.recon_carrier = f.recon_carrier;
-        if (f.recon_carrier)   // reconstruct_spectral_row: reconstruct_body_fast's layout
-            lds = std::max(lds, sizeof(float) * ((size_t)f.recon_nb + (size_t)kReconBlockSamples + kWarm + (size_t)kBlock * (kChunk + 1)));
+        // reconstruct_body: the amplitudes | the block's samples staged for 16-byte stores; reconstruct_spectral_row: reconstruct_body_fast's layout
+        lds = std::max(lds, recon_lds_bytes(f.recon_nb, f.recon_carrier != nullptr));
     }
     if (blocks == 0) return false;
     if (blocks_only) { *blocks_only = blocks; return true; }

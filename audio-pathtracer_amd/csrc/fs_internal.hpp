@@ -96,11 +96,27 @@ constexpr int kBlock = 256;       // 4 waves of 64 lanes
 // A zero-block mask word of a host ring slot has one bit per such block (host_block_vote; the host: slot_masks_usable).
 constexpr int kChunk = 16;
 constexpr int kReconBlockSamples = kBlock * kChunk;   // 4 096
+constexpr int kWarm = 96;                             // samples of filter run-in before a thread's own chunk
+// LDS of one reconstruct workgroup: the row's amplitudes [num_bins] | the block's interpolated samples and their run-in
+// [kReconBlockSamples + kWarm] | the staged outputs [kBlock][kChunk + 1] (reconstruct_body_fast's layout, also that of the spectral
+// row).  fast = false: reconstruct_body's layout (the fused frame's plain rows), which has no interpolated samples.
+// fs_context_create refuses a shape whose reconstruct needs more than the device gives one workgroup.
+constexpr size_t recon_lds_bytes(int num_bins, bool fast = true) {
+    return sizeof(float) * ((size_t)num_bins + (fast ? (size_t)kReconBlockSamples + kWarm : 0) + (size_t)kBlock * (kChunk + 1));
+}
+// Room left next to it for the static LDS of the kernels that run a reconstruct (the fused frame kernels: 1 888 B on gfx950; the
+// batch kernel: 256 B for its workgroup vote).  A workgroup's static and dynamic LDS together must fit the device's limit.
+constexpr size_t kReconStaticLdsReserve = 4096;
+// the most bins whose reconstruct fits `lds` bytes per workgroup
+constexpr int max_recon_bins(size_t lds) {
+    return lds > recon_lds_bytes(0) + kReconStaticLdsReserve ? (int)((lds - recon_lds_bytes(0) - kReconStaticLdsReserve) / sizeof(float)) : 0;
+}
 static_assert(64 % kChunk == 0, "carrier_stride (below) must hold whole chunks");
 // LDS-privatised part of the [bands][bins] energy histogram in the connect kernels.  With the reference's distance
 // scale (cm / 1000, ARTS.cpp:373) bin = path length in metres / 3.43: 256 bins cover 878 m, and a 262 144-ray frame
 // at cfg3 touches bins 0..60.  All 1000 bins cost 32 KB per workgroup at 8 bands — the 8 KB window keeps three
-// connect workgroups on a CU instead of two.  FS_HIST_WINDOW overrides it (tests exercise the far path with 16).
+// connect workgroups on a CU instead of two.  FS_HIST_WINDOW overrides it (1 .. 4 096, read at fs_context_create;
+// tests/test_config_shapes.py: test_hist_window_override runs 1, 16 and 4 096 against the oracle).
 constexpr int kHistWindow = 256;
 constexpr int kUnboundedDepth = 1 << 24;   // the weights' depth cap when the walk has none: every strategy exists
 constexpr int kOverLevels = 448;            // second-tier walk steps of depth = 0 frames (64 + 448 = 512 steps)
