@@ -13,7 +13,6 @@
 //                        binary node; the survivors are compacted (prefix sum) and the round repeats until one cluster
 //                        is left (~30 rounds).  Bottom-up agglomeration by surface area gives a tree close to the host's
 //                        binned-SAH one — round 2's Karras radix tree (spatial-median splits) traced 1.6x slower.
-//                        (FS_BUILD_LBVH=1 still selects it, for comparison.)
 //   4. collapse_kernel   4-wide nodes level by level, breadth-first (ONE workgroup walks the levels: the tree has
 //                        ~N/4 wide nodes): a wide node opens the inner child of largest surface area until it has four;
 //                        subtrees of <= 2 triangles become leaves; every subtree owns a contiguous range of leaf-order
@@ -29,7 +28,6 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 
 #include "fs_internal.hpp"
 
@@ -65,47 +63,11 @@ __global__ __launch_bounds__(kBuildBlock) void morton_kernel(const float* __rest
 }
 
 // binary tree over the sorted triangles: internal nodes [0, N-1), leaves are sorted positions; child >= 0 internal,
-// ~leaf otherwise.  count = triangles below an internal node, area = surface area of its box (PLOC; 0 for the radix tree)
+// ~leaf otherwise.  count = triangles below an internal node, area = surface area of its box
 struct Bvh2 {
-    int* left; int* right; int* parent;   // (radix tree only) parent of internal node i: parent[i]; of leaf j: parent[(N-1) + j]
-    int* first; int* last;                // (radix tree only) key range of an internal node
+    int* left; int* right;
     int* count; float* area;
-    int root;
 };
-
-__device__ __forceinline__ int delta(const unsigned long long* __restrict__ k, int N, int i, int j) {
-    if (j < 0 || j >= N) return -1;
-    return __clzll((long long)(k[i] ^ k[j]));   // keys are unique: never 64
-}
-
-__global__ __launch_bounds__(kBuildBlock) void karras_kernel(const unsigned long long* __restrict__ keys, int N, Bvh2 b) {
-    const int i = blockIdx.x * kBuildBlock + threadIdx.x;
-    if (i >= N - 1) return;
-    const int d = delta(keys, N, i, i + 1) - delta(keys, N, i, i - 1) >= 0 ? 1 : -1;
-    const int dmin = delta(keys, N, i, i - d);
-    int lmax = 2;
-    while (delta(keys, N, i, i + lmax * d) > dmin) lmax *= 2;
-    int l = 0;
-    for (int t = lmax / 2; t >= 1; t /= 2)
-        if (delta(keys, N, i, i + (l + t) * d) > dmin) l += t;
-    const int j = i + l * d;
-    const int dnode = delta(keys, N, i, j);
-    int s = 0;
-    for (int t = (l + 1) / 2;; t = (t + 1) / 2) {
-        if (delta(keys, N, i, i + (s + t) * d) > dnode) s += t;
-        if (t == 1) break;
-    }
-    const int gamma = i + s * d + min(d, 0);
-    const int lo = min(i, j), hi = max(i, j);
-    const int lc = lo == gamma ? ~gamma : gamma;             // leaf if the split leaves one key on that side
-    const int rc = hi == gamma + 1 ? ~(gamma + 1) : gamma + 1;
-    b.left[i] = lc; b.right[i] = rc;
-    b.first[i] = lo; b.last[i] = hi;
-    b.count[i] = hi - lo + 1; b.area[i] = (float)(hi - lo + 1);   // no boxes here: "area" = size, the round-2 opening rule
-    b.parent[lc >= 0 ? lc : (N - 1) + ~lc] = i;
-    b.parent[rc >= 0 ? rc : (N - 1) + ~rc] = i;
-    if (i == 0) b.parent[0] = -1;
-}
 
 // ---- PLOC ------------------------------------------------------------------------------------------------------
 // Cluster c of a round is a node: id < N a triangle (sorted position id), else internal node id - N.  Boxes by node id.
@@ -259,7 +221,7 @@ __global__ __launch_bounds__(kCollapseBlock) void collapse_kernel(int N, Bvh2 b,
     __shared__ int s_begin, s_end, s_next, s_need, s_fail;
     if (threadIdx.x == 0) {
         s_begin = 0; s_end = 1; s_next = 1; s_need = 0; s_fail = 0;
-        wide_src[0] = N > 1 ? (root_ptr ? *root_ptr : b.root) : -1;     // a one-triangle scene: the root's only child is the leaf
+        wide_src[0] = N > 1 ? *root_ptr : -1;     // a one-triangle scene (no root_ptr): the root's only child is the leaf
         wide_start[0] = 0;
         need[0] = 0;
         info->level_begin[0] = 0;
@@ -383,7 +345,7 @@ size_t device_build_scratch_bytes(int T) {
     const size_t n = (size_t)std::max(T, 1);
     size_t bytes = 0;
     bytes += 2 * sizeof(unsigned long long) * n;            // keys, sorted keys
-    bytes += 6 * sizeof(int) * n + sizeof(int) * 2 * n;     // left, right, first, last, count, area (N) + parent (2N)
+    bytes += 4 * sizeof(int) * n;                           // left, right, count, area
     bytes += 4 * sizeof(int) * n;                           // wide_src, wide_start, need, pos_of
     bytes += 2 * sizeof(float4) * 2 * n;                    // PLOC node boxes
     bytes += 6 * sizeof(int) * n;                           // PLOC clusters (2), nn, valid, pos, merged
@@ -406,12 +368,8 @@ bool launch_device_build(const float* xyz, const uint16_t* mat, const uint32_t* 
     Bvh2 b{};
     b.left = reinterpret_cast<int*>(take(sizeof(int) * n));
     b.right = reinterpret_cast<int*>(take(sizeof(int) * n));
-    b.first = reinterpret_cast<int*>(take(sizeof(int) * n));
-    b.last = reinterpret_cast<int*>(take(sizeof(int) * n));
     b.count = reinterpret_cast<int*>(take(sizeof(int) * n));
     b.area = reinterpret_cast<float*>(take(sizeof(float) * n));
-    b.parent = reinterpret_cast<int*>(take(sizeof(int) * 2 * n));
-    b.root = 0;
     int* wide_src = reinterpret_cast<int*>(take(sizeof(int) * n));
     int* wide_start = reinterpret_cast<int*>(take(sizeof(int) * n));
     int* need = reinterpret_cast<int*>(take(sizeof(int) * n));
@@ -440,11 +398,8 @@ bool launch_device_build(const float* xyz, const uint16_t* mat, const uint32_t* 
     const unsigned blocks = (unsigned)((T + kBuildBlock - 1) / kBuildBlock);
     hipLaunchKernelGGL(morton_kernel, dim3(blocks), dim3(kBuildBlock), 0, s, xyz, T, l3, ie, keys);
     (void)hipcub::DeviceRadixSort::SortKeys(sort_buf, sort_tmp, keys, sorted, T, 0, 62, s);
-    static const bool lbvh = [] { const char* v = std::getenv("FS_BUILD_LBVH"); return v && std::atoi(v) != 0; }();
     const int* root_ptr = nullptr;
-    if (T > 1 && lbvh) {
-        hipLaunchKernelGGL(karras_kernel, dim3(blocks), dim3(kBuildBlock), 0, s, sorted, T, b);
-    } else if (T > 1) {
+    if (T > 1) {
         // PLOC rounds.  The cluster count lives on the device; the host only knows an upper bound (every round with more
         // than one cluster merges at least the globally closest pair) and reads the true count back every few rounds.
         hipLaunchKernelGGL(ploc_init_kernel, dim3(blocks), dim3(kBuildBlock), 0, s, xyz, sorted, T, P);

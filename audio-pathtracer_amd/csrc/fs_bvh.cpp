@@ -83,8 +83,7 @@ struct Builder {
 
     explicit Builder(BuildInput& i) : in(i), prims(i.prims) {}
 
-    static constexpr int kBinsMax = 256;
-    int kBins = std::getenv("FS_BVH_BINS") ? std::max(2, std::min(kBinsMax, std::atoi(std::getenv("FS_BVH_BINS")))) : 64;   // 32 -> 64 bins: -0.8 % node visits (tools/tree_cost.cpp), +0.6 % rays/s (profiles/r03_ab_tree.log)
+    static constexpr int kBins = 64;   // 32 -> 64 bins: -0.8 % node visits (tools/tree_cost.cpp), +0.6 % rays/s (profiles/r03_ab_tree.log)
     int kLeaf = 2;   // measured: a triangle test costs about as much as 2.5 child boxes, small leaves win
 
     int make(int first, int count, int depth) {
@@ -131,7 +130,7 @@ struct Builder {
         for (int ax = 0; ax < 3; ++ax) {
             float ext = cb.hi[ax] - cb.lo[ax];
             if (!(ext > 0.f)) continue;
-            Box bb[kBinsMax]; int bc[kBinsMax];
+            Box bb[kBins]; int bc[kBins];
             for (int b = 0; b < kBins; ++b) { bb[b].reset(); bc[b] = 0; }
             float scale = kBins / ext;
             for (int i = first; i < first + count; ++i) {
@@ -139,7 +138,7 @@ struct Builder {
                 int b = std::min(kBins - 1, std::max(0, (int)((p.cen[ax] - cb.lo[ax]) * scale)));
                 bb[b].grow(p.box); bc[b]++;
             }
-            float ra[kBinsMax]; int rc[kBinsMax];
+            float ra[kBins]; int rc[kBins];
             Box acc; acc.reset(); int c = 0;
             for (int b = kBins - 1; b >= 1; --b) {
                 acc.grow(bb[b]); c += bc[b];

@@ -17,6 +17,9 @@ void fs_sound_params_default(fs_sound_params* p) {
     p->listener_radius = 34.0f;    // ADefaultPawn collision sphere (engine default, build-owned)
 }
 
+// rays per wave of the tracer, the other lanes help (64 = no sharing; 2 vs 4: 0.259 vs 0.267 ms at 100 k triangles, 0.195 vs 0.212 at 5 k)
+constexpr int kSoundRaysPerWave = 2;
+
 int fs_update_sound(fs_context* ctx, fs_source h, const fs_sound_params* p, fs_sound_result* out) {
     if (!ctx || !out) return FS_ERR_INVALID_ARGUMENT;
     if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
@@ -43,7 +46,7 @@ int fs_update_sound(fs_context* ctx, fs_source h, const fs_sound_params* p, fs_s
     std::memcpy(sp.src, s->pos, sizeof(sp.src));
     std::memcpy(sp.lis, ctx->listener, sizeof(sp.lis));
     FS_HIP(ctx, hipMemsetAsync(ctx->d_sound, 0, sizeof(SoundAccum), ctx->stream));
-    launch_update_sound(ctx->scene, sp, ctx->d_sound, ctx->sound_rays_per_wave, ctx->stream);
+    launch_update_sound(ctx->scene, sp, ctx->d_sound, kSoundRaysPerWave, ctx->stream);
     FS_HIP(ctx, hipGetLastError());
     SoundAccum acc{};
     FS_HIP(ctx, hipMemcpyAsync(&acc, ctx->d_sound, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));

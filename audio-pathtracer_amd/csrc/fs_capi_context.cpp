@@ -404,7 +404,7 @@ int auto_rays_per_wave(unsigned long long lanes, int depth, unsigned long long w
 }
 
 // Pairs per wave of the connect kernel, same idea: a small frame's visibility queries are shared by sparse waves.
-// About 2048 waves (tools/connect_sparse_sweep.py): 8 192 pairs 0.065 -> 0.031 ms with 4 per wave, 32 768 pairs
+// About 2048 waves (round 3's sweep of pairs per wave): 8 192 pairs 0.065 -> 0.031 ms with 4 per wave, 32 768 pairs
 // 0.067 -> 0.043 ms with 16, dense waves from 131 072 pairs on.
 int auto_pairs_per_wave(unsigned long long pairs) {
     int ppw = 1;   // (round 3: 1 000 pairs, one per wave: 0.056 -> 0.044 ms; profiles/r03_ref_defaults_rpw.log)
@@ -526,16 +526,12 @@ int fs_context_create(const fs_config* cfg, fs_context** out) {
         // With three ordinary streams the rate of a pipelined stream of frames depended on how many streams the process
         // had created before (which hardware queues the compute and the tail stream were given): 965 – 970 M rays/s or
         // 880 M, 995 or 900 M at four frames per launch, by the count of earlier streams (profiles/r03_stream_queues.log;
-        // without publishes 990 / 1 015 M whatever the history).  FS_TAIL_STREAM_PRIORITY=0: ordinary streams again; 2: lowest.
+        // without publishes 990 / 1 015 M whatever the history).
         int prio_lo = 0, prio_hi = 0;   // (numerically lower = higher priority)
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        const int mode = std::getenv("FS_TAIL_STREAM_PRIORITY") ? std::atoi(std::getenv("FS_TAIL_STREAM_PRIORITY")) : 1;
-        const int prio = mode == 2 ? prio_lo : prio_hi;
-        if (mode != 0) e = hipStreamCreateWithPriority(&ctx->copy_stream, hipStreamNonBlocking, prio);
-        else e = hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking);
+        e = hipStreamCreateWithPriority(&ctx->copy_stream, hipStreamNonBlocking, prio_hi);
         if (e != hipSuccess) return ctx->fail(FS_ERR_NO_DEVICE, std::string("hipStreamCreate(copy): ") + hipGetErrorString(e));
-        if (mode != 0) e = hipStreamCreateWithPriority(&ctx->rev_stream, hipStreamNonBlocking, prio_hi);
-        else e = hipStreamCreateWithFlags(&ctx->rev_stream, hipStreamNonBlocking);
+        e = hipStreamCreateWithPriority(&ctx->rev_stream, hipStreamNonBlocking, prio_hi);
         if (e != hipSuccess) return ctx->fail(FS_ERR_NO_DEVICE, std::string("hipStreamCreate(reverb): ") + hipGetErrorString(e));
     }
     int cus = 0;
@@ -557,39 +553,18 @@ int fs_context_create(const fs_config* cfg, fs_context** out) {
 #ifdef FS_EXPERIMENTS
     if (const char* v = std::getenv("FS_WALK_VARIANT")) ctx->walk.variant = std::atoi(v) == 0 ? 0 : 2;
 #endif
-    if (const char* v = std::getenv("FS_WALK_PLAN")) ctx->walk.plan = std::atoi(v) ? 1 : 0;
     if (const char* v = std::getenv("FS_DEBUG_STALLS")) ctx->debug_stalls = std::atoi(v) != 0;
-    if (const char* v = std::getenv("FS_FLUSH_RECON_ON_COMPUTE")) ctx->flush_recon_on_compute = std::atoi(v) != 0;
     if (const char* v = std::getenv("FS_OVER_CAP")) ctx->over_cap_forced = std::max(1, std::atoi(v));
     if (const char* v = std::getenv("FS_WALK_COOP")) ctx->walk.coop = std::atoi(v) ? 1 : 0;
-    if (const char* v = std::getenv("FS_FUSED_RECON")) ctx->fused_recon = std::atoi(v) != 0;
-    if (const char* v = std::getenv("FS_FUSED_RECON_COMM")) ctx->fused_recon_comm = std::atoi(v) != 0;
-    if (const char* v = std::getenv("FS_FUSED_DRAIN")) ctx->fused_drain = std::atoi(v) != 0;
     ctx->hist_window = default_hist_window(ctx->cfg.num_bands);
     if (const char* v = std::getenv("FS_STACK_ROWS_CAP")) ctx->stack_rows_cap = std::max(kDeepChunk + 4, std::min(kStackDepth + 1, std::atoi(v)));
     if (const char* v = std::getenv("FS_HIST_WINDOW")) ctx->hist_window = std::max(1, std::min(4096, std::atoi(v)));
     if (const char* v = std::getenv("FS_WALK_RAYS_PER_WAVE")) ctx->walk_rays_per_wave = std::max(0, std::min(64, std::atoi(v)));
-    if (const char* v = std::getenv("FS_CONNECT_PAIRS_PER_WAVE")) ctx->connect_pairs_per_wave = std::max(0, std::min(64, std::atoi(v)));
     // staged depth = 0 walks (pipelined frames): the steps at which a walk moves on to the next launch.  12-step stages
     // (a launch carries one frame's worth of work, ~0.6 ms at 262 144 subpaths; a bounce of a wave on the full chip
     // takes ~35 us, so longer stages make their chain the launch's length), longer ones for the few hundred walks beyond
     // the main record tier (tools/stage_sweep.py, profiles/r03_stage_sweep.log)
     ctx->stage_bounds = {8, 18, 30, 46, 64, 96};   // best of the sets tried on 262 144-ray frames at roulette 0.9 (profiles/r03_stage_sweep.log)
-    if (const char* v = std::getenv("FS_STAGE_DENSE_FROM")) ctx->stage_dense_from = std::max(1, std::atoi(v));
-    if (const char* v = std::getenv("FS_WALK_STAGES")) {
-        std::vector<int> b;
-        for (const char* q = v; *q;) {
-            char* end = nullptr;
-            const long x = std::strtol(q, &end, 10);
-            if (end == q) break;
-            if (x > (b.empty() ? 0 : b.back()) && x < FS_MAX_DEPTH + kOverLevels && (int)b.size() < kMaxWalkParts - 1) b.push_back((int)x);
-            q = *end ? end + 1 : end;
-        }
-        ctx->stage_bounds = b;   // empty: depth = 0 frames are not held
-        ctx->stage_bounds_default = false;
-    }
-    if (const char* v = std::getenv("FS_SYNC_FIRST_RPW")) ctx->sync_first_rays_per_wave = std::max(0, std::min(64, std::atoi(v)));
-    if (const char* v = std::getenv("FS_SYNC_LATE_RPW")) ctx->sync_late_rays_per_wave = std::max(0, std::min(64, std::atoi(v)));
     ctx->sync_stage_bounds = {24};   // tools/sync_stage_sweep.py, profiles/r04_sync_stage_sweep*.jsonl
     if (const char* v = std::getenv("FS_SYNC_WALK_STAGES")) {
         std::vector<int> b;
@@ -611,16 +586,6 @@ int fs_context_create(const fs_config* cfg, fs_context** out) {
             ctx->sync_lane_end = end > 0 ? end : (1 << 30);
         }
     }
-    if (const char* v = std::getenv("FS_SYNC_STAGE_RPW")) {
-        for (const char* q = v; *q;) {
-            char* end = nullptr;
-            const long x = std::strtol(q, &end, 10);
-            if (end == q) break;
-            ctx->sync_stage_rpw.push_back((int)std::max(0l, std::min(64l, x)));
-            q = *end ? end + 1 : end;
-        }
-    }
-    if (const char* v = std::getenv("FS_SOUND_RAYS_PER_WAVE")) ctx->sound_rays_per_wave = std::max(1, std::min(64, std::atoi(v)));
     e = hipMalloc((void**)&ctx->walk.queue_head, sizeof(unsigned) * kScratchSets * kScratchAllocWords);   // each set with its counters
     if (e == hipSuccess) e = hipMemset(ctx->walk.queue_head, 0, sizeof(unsigned) * kScratchSets * kScratchAllocWords);
     if (e != hipSuccess) return ctx->fail(FS_ERR_NO_DEVICE, std::string("hipMalloc(queue): ") + hipGetErrorString(e));

@@ -385,9 +385,9 @@ int frame_launch(fs_context* ctx, Frame& f) {
     WalkLaunch wplan = ctx->walk;
     wplan.queue_head = scratch;
     wplan.perm = perm_buf;
-    if (f.unbounded || f.stages.size() > 1) wplan.plan = 1;   // the second record tier relies on the schedule: the longest walks own the lowest slots
     bool sort = false;
     const bool plan_runs = plan_shape(kp, wplan, nullptr, &sort);   // the plan pass (and the flush with it) runs for this frame
+    // (the second record tier relies on the schedule: the longest walks own the lowest slots)
     const uint32_t* perm = plan_runs && sort ? perm_buf : nullptr;
     if (!perm) st.slot_of = nullptr;   // no schedule: slot == subpath index
     const bool plan_held = f.pipe_ok && ctx->pipelining >= 2 && plan_runs;   // depth 2: the pass joins the fused launch below
@@ -407,7 +407,7 @@ int frame_launch(fs_context* ctx, Frame& f) {
     // (a staged walk's first stage is a frame of walks of at most stages[0].end steps)
     wl.rays_per_wave = ctx->walk_rays_per_wave > 0 ? ctx->walk_rays_per_wave
                                                    : auto_rays_per_wave(2ull * kp.num_local, std::min(kp.depth, f.stages[0].end));
-    const int ppw = ctx->connect_pairs_per_wave > 0 ? ctx->connect_pairs_per_wave : auto_pairs_per_wave(kp.num_local);
+    const int ppw = auto_pairs_per_wave(kp.num_local);
     if (f.pipe_ok) {   // (anything else has flushed the held frames before)
         fs_context::PipeFrame me;
         me.kp = kp; me.st = st; me.wl = wl; me.perm = perm; me.stages = f.stages; me.next_stage = 0; me.fixed = fixed; me.ppw = ppw;
@@ -481,10 +481,8 @@ int frame_launch(fs_context* ctx, Frame& f) {
                 // (profiles/r04_sync_stage_sweep4.jsonl: the first stage — everybody, at most `bound` steps — does best on waves of 16
                 // subpaths up to 64 000 of them and of 32 beyond: 0.80 / 0.94 ms per tick of 32 sources, 1.37 / 1.65 ms of 128,
                 // 1.19 / 1.49 ms per 262 144-ray frame; dense waves 0.89 / 1.18, 1.41 / 1.71, 1.20 / 1.64)
-                wk.rays_per_wave = k == 0 ? (ctx->sync_first_rays_per_wave > 0 ? ctx->sync_first_rays_per_wave : (2ull * kp.num_local >= 131072ull ? 32 : 16)) :
-                                   ctx->sync_late_rays_per_wave > 0 ? ctx->sync_late_rays_per_wave :
+                wk.rays_per_wave = k == 0 ? (2ull * kp.num_local >= 131072ull ? 32 : 16) :
                     auto_rays_per_wave(walk_stage_slots(kp, f.stages[k].begin), std::min(kp.depth, f.stages[k].end) - f.stages[k].begin, k > 0 ? 8192ull : 0ull);
-            if (ctx->walk_rays_per_wave <= 0 && k < ctx->sync_stage_rpw.size() && ctx->sync_stage_rpw[k] > 0) wk.rays_per_wave = ctx->sync_stage_rpw[k];
             return wk;
         };
         // The long-walk lane: the frame's time is its longest walk's chain of queries, and a query of a walk that shares a sparse

@@ -70,8 +70,8 @@ int finish_held_frame(fs_context* ctx, const fs_context::PipeFrame& q, bool may_
             // plain reconstruct: it rides in the next fused launch (fs_context::recon_owed) — on one GPU; with the library's
             // collective, in the launch after next, behind the all-reduce just enqueued on the tail stream
             const bool single = !ctx->comm && ctx->cfg.world_size == 1;
-            const bool summed = ctx->comm != nullptr && ctx->fused_recon_comm && s->reduced && s->red_recorded[it.cur];
-            if (may_defer_recon && ctx->fused_recon && (single || summed) && ctx->profiling < 2 &&
+            const bool summed = ctx->comm != nullptr && s->reduced && s->red_recorded[it.cur];
+            if (may_defer_recon && (single || summed) && ctx->profiling < 2 &&
                 !(it.recon.flags & FS_FLAG_FLUSH_BEFORE_RECONSTRUCT)) {
                 fs_context::ReconOwed o; o.s = s; o.cur = it.cur; o.fixed = q.fixed; o.p = it.recon; o.reduced = summed;
                 ctx->recon_owed.push_back(o);
@@ -98,6 +98,7 @@ void held_connect_part(const fs_context::PipeFrame& q, FrameParts& f) {
 }
 
 // rays per wave of a walk stage: by the number of walks it still has and the steps they have left at most
+constexpr uint32_t kStageDenseFrom = 4096;   // stages with at least this many (provisioned) walks use dense waves
 WalkLaunch stage_launch(const fs_context* ctx, const fs_context::PipeFrame& q, int stage) {
     WalkLaunch wl = q.wl;
     const WalkStage& sr = q.stages[(size_t)stage];
@@ -106,7 +107,7 @@ WalkLaunch stage_launch(const fs_context* ctx, const fs_context::PipeFrame& q, i
     // dependent bounces is what matters (profiles/r03_stage_sweep.log: the stand-alone frames' rule — ~4096 sparse waves
     // for mid-size frames — costs 0.87 instead of 0.63 ms per frame here; raising the late stages' wave priority: nothing)
     if (sr.begin > 0 && ctx->walk_rays_per_wave <= 0)
-        wl.rays_per_wave = walk_stage_slots(q.kp, sr.begin) >= (uint32_t)ctx->stage_dense_from ? 64 : 16;
+        wl.rays_per_wave = walk_stage_slots(q.kp, sr.begin) >= kStageDenseFrom ? 64 : 16;
     return wl;
 }
 
@@ -177,8 +178,7 @@ int flush_pending(fs_context* ctx) {
     if (dbg) t1 = clk::now();
     // (one GPU, or the pairs of a frame shared between ranks with the LIBRARY's collective: the sums over the ranks go onto the
     // tail stream as before, the reconstructs ride behind them in the drain's launches and publish through the host word)
-    const bool drainable = (!ctx->comm && ctx->cfg.world_size == 1) || (ctx->comm != nullptr && ctx->fused_recon_comm);
-    if (ctx->fused_drain && ctx->fused_recon && drainable && ctx->profiling < 2 &&
+    if ((ctx->comm != nullptr || ctx->cfg.world_size == 1) && ctx->profiling < 2 &&
         (!ctx->held.empty() || !ctx->recon_owed.empty())) {
         FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
         const int dr = drain_fused(ctx);

@@ -277,9 +277,9 @@ int run_owed_reconstructs(fs_context* ctx) {
 // COMPUTE stream as a batch of one — the kernel writes the published host slot itself, nothing crosses to the tail stream.
 // (Through the tail stream — a handoff event, a kernel and a copy on the priority queue while the compute queue is busy — one
 // flush in three took 6 ms longer than the others on the pool's boxes: tools/repeat_driver_bench.py, the driver's 20-step
-// region read 440 or 880 M rays/s.)  FS_FLUSH_RECON_ON_COMPUTE=0 restores the tail-stream path.
+// region read 440 or 880 M rays/s.)
 int flush_reconstruct(fs_context* ctx, Source* s, const fs_params* p) {
-    if (ctx->flush_recon_on_compute && !ctx->comm && ctx->cfg.world_size == 1) { Source* one = s; return reconstruct_batch(ctx, &one, 1, p, true); }
+    if (!ctx->comm && ctx->cfg.world_size == 1) { Source* one = s; return reconstruct_batch(ctx, &one, 1, p, true); }
     return reconstruct_now(ctx, s, p);
 }
 

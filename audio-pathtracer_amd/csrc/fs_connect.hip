@@ -262,8 +262,7 @@ void launch_connect_t(const DeviceScene& sc_in, const KParams& kp, const Subpath
     }
     // uncapped walks (the waited-for frames; the pipelined ones connect inside the fused launch): paths of up to a few hundred
     // segments, evaluated by ONE lane when the wave is dense — kConnectAhead records in flight (connect_body's AHEAD)
-    static const int ahead = std::getenv("FS_CONNECT_AHEAD") ? std::atoi(std::getenv("FS_CONNECT_AHEAD")) : 4;   // (0 / 1: one at a time)
-    if (st.over_levels != 0 && !kp.lobes && !kp.count && ahead > 1) {
+    if (st.over_levels != 0 && !kp.lobes && !kp.count) {
         if (batch) {
             allow_lds(connect_kernel<B, 0, true, false, false, kConnectAhead>, lds);
             hipLaunchKernelGGL((connect_kernel<B, 0, true, false, false, kConnectAhead>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed, queue_head,

@@ -289,9 +289,6 @@ struct fs_context {
     // frame, i.e. while the next one executes — a launch that waited for it would leave the GPU idle meanwhile
     struct ReconOwed { Source* s = nullptr; int cur = 0; bool fixed = false; fs_params p; bool reduced = false; int age = 0; };
     std::vector<ReconOwed> recon_owed;
-    bool fused_recon = true;                       // FS_FUSED_RECON=0: always the tail stream
-    bool fused_recon_comm = true;                  // FS_FUSED_RECON_COMM=0: with a communicator, always the tail stream
-    bool fused_drain = true;                       // FS_FUSED_DRAIN=0: a flush lets every held frame finish on kernels of its own (round 4's form)
     // Publishes of the compute stream (fused reconstruct parts, batches behind a tick or a flush): the launch writes the ring slots
     // and then its id into *h_pub_word (pinned, coherent) — see Source::pub_word.  pub_issued = id of the newest such launch.
     unsigned* d_pub_tickets = nullptr;             // device: the ticket cell of publish_arrive (re-armed by the launch that used it)
@@ -303,12 +300,9 @@ struct fs_context {
     uint64_t pub_issued = 0;
     int state_sets = 3;              // sets of the per-frame arrays (subpath state, records, schedules): frames in flight + 1
     bool state_cont = false;         // the sets include continuation records (staged walks)
-    std::vector<int> stage_bounds;   // staged depth = 0 walks: the steps at which a walk changes launch (FS_WALK_STAGES)
+    std::vector<int> stage_bounds;   // staged depth = 0 walks: the steps at which a walk changes launch (fs_set_walk_stages)
     bool stage_bounds_default = true; // not set by the host: grouped frames (two or more per launch) take kGroupedStageBounds
     std::vector<int> sync_stage_bounds;   // the same for depth = 0 frames that are waited for (stages back to back; FS_SYNC_WALK_STAGES)
-    int sync_first_rays_per_wave = 0;     // subpaths per wave of the first stage, 0 = by frame size (FS_SYNC_FIRST_RPW)
-    int sync_late_rays_per_wave = 0;      // subpaths per wave of the later stages, 0 = by the number of survivors (FS_SYNC_LATE_RPW)
-    std::vector<int> sync_stage_rpw;      // subpaths per wave of stage k of such a frame, overriding the two above where > 0 (FS_SYNC_STAGE_RPW: "32,64,0")
     // the long-walk lane of such a frame (WalkLane): walks of sync_lane_len steps or more take cooperative waves of their
     // own from step 0 on, steps [0, sync_lane_end) beside the first stage, the rest beside the second (FS_SYNC_LANE: "len,end"; len 0: off)
     // -1 (default): by the frame's size and the roulette — sync_lane_plan, fs_capi_frame.cpp; with it the ONE default bound moves too
@@ -317,7 +311,6 @@ struct fs_context {
     uint64_t syncs = 0;                   // fs_synchronize calls (a stand-alone reconstruct asks whether its producer waits for every frame: Source::recon_sync_mark)
     bool sync_stage_from_default = true;
     int sync_stage_from = 15000;          // ... of at least this many subpaths (smaller frames: every walk has a wave of its own anyway; with the long-walk lane an 8-source tick — 16 000 — gains 5 %, 14 000 lose: profiles/r05_stage_from.jsonl; 16 384 until then)
-    int stage_dense_from = 4096;     // stages with at least this many (provisioned) walks use dense waves (FS_STAGE_DENSE_FROM)
     std::shared_ptr<RefineJob> refine;   // fs_scene_commit_progressive: the background build whose tree replaces the device-built one
     std::vector<std::thread> refine_threads;   // every background build ever started (cancelled ones too): joined before the context goes
     bool moved_since_refine = false;     // fs_scene_update_triangles since the snapshot: re-apply the positions after the swap
@@ -340,7 +333,6 @@ struct fs_context {
     uint32_t over_cap = 0, over_cap_pos = 0;
     // FS_DEBUG_STALLS: where the producer waited (printed by fs_context_destroy): flushes of held frames, host waits for a publish
     // (count, microseconds), waits enqueued on the compute stream for another stream's event, owed reconstructs run on the tail stream
-    bool flush_recon_on_compute = true;   // FS_FLUSH_RECON_ON_COMPUTE (fs_capi_publish.cpp: flush_reconstruct)
     bool debug_stalls = false;
     struct { uint64_t flushes = 0, flushed_frames = 0, sync_publish = 0, sync_publish_us = 0, waits_enqueued = 0, waits_skipped = 0, owed_on_tail = 0, launches = 0,
              tail_ops = 0, pub_word = 0, pub_event = 0, lane_launches = 0; } dbg;   // fs_get_pipeline_counters
@@ -359,13 +351,11 @@ struct fs_context {
     unsigned batch_frame = 0;
     unsigned long long host_segments = 0;   // walk segments of frames without a plan pass (roulette off), since the last reset
 
-    // walk kernel launch shape (tunable through FS_WALK_VARIANT / FS_WALK_BLOCKS_PER_CU / FS_REFILL_THRESHOLD)
-    WalkLaunch walk{2, 256, nullptr, 1, nullptr};   // variant 2 = wave work sharing
+    // walk kernel launch shape (variant: FS_WALK_VARIANT in -DFS_EXPERIMENTS builds; coop: FS_WALK_COOP)
+    WalkLaunch walk{2, 256, nullptr, nullptr};   // variant 2 = wave work sharing
     int hist_window = kHistWindow; // FS_HIST_WINDOW
     size_t lds_limit = 64 * 1024;  // dynamic LDS a workgroup may ask for on this device (hipDeviceAttributeMaxSharedMemoryPerBlock)
     int walk_rays_per_wave = 0;    // BDPT walk: subpaths per wave, 0 = by frame size (FS_WALK_RAYS_PER_WAVE; 64 = dense waves)
-    int connect_pairs_per_wave = 0;   // connect kernel: pairs per wave, 0 = by frame size (FS_CONNECT_PAIRS_PER_WAVE; 64 = dense)
-    int sound_rays_per_wave = 2;   // legacy tracer: rays per wave, the other lanes help (FS_SOUND_RAYS_PER_WAVE; 64 = no sharing; 2 vs 4: 0.259 vs 0.267 ms at 100 k triangles, 0.195 vs 0.212 at 5 k)
 
     // measurement
     int profiling = 0;   // 0 off, 1 = HIP events around the dominant (walk) kernel only, 2 = every kernel

@@ -183,12 +183,13 @@ bool FS_LAUNCH_FRAME(int B, const DeviceScene& sc, const FrameParts& f, hipStrea
         // instead (they step through all the pairs): they finish while the long walks run and the tail is the
         // shortest walks (950 -> 965 M rays/s; 256: 962, 512: 946, 1 024: 921).  A launch whose walks fit the chip once
         // keeps the connect pass behind them: there every long walk has to start at t = 0 (858 -> 815 M with 384 first).
-        // FS_FRAME_CONNECT_FIRST = n > 0: always n first; < 0: never.  (cfg5's eight sources 894 -> 912 M, deterministic mode
-        // 835 -> 870 M, three frames per launch 818 -> 852 M; cfg4 and staged walks unchanged.)
-        static const int cap_env = std::getenv("FS_FRAME_CONNECT_FIRST") ? std::atoi(std::getenv("FS_FRAME_CONNECT_FIRST")) : 0;
-        // (walks of one length — Russian roulette off — leave no short walks for the tail: 660 -> 606 M with connect first)
-        const int cap_first = cap_env != 0 ? cap_env : (blocks >= 2048u && f.walk[0].kp.russian_roulette ? 384 : -1);
-        if (cap_first > 0 && f.num_walk > 0) { a.connect_blocks = std::min<uint32_t>(a.connect_blocks, (uint32_t)cap_first); a.connect_first = 1u; }
+        // (cfg5's eight sources 894 -> 912 M, deterministic mode 835 -> 870 M, three frames per launch 818 -> 852 M; cfg4 and
+        // staged walks unchanged.  Walks of one length — Russian roulette off — leave no short walks for the tail: 660 -> 606 M
+        // with connect first.)
+        if (blocks >= 2048u && f.num_walk > 0 && f.walk[0].kp.russian_roulette) {
+            a.connect_blocks = std::min<uint32_t>(a.connect_blocks, 384u);
+            a.connect_first = 1u;
+        }
         a.kpc = f.kpc; a.stc = f.stc; a.energy = f.energy; a.fixed = f.fixed; a.scratch_c = f.scratch_c; a.pairs_per_wave = f.ppw;
         a.energy_tab = f.energy_tab; a.fixed_tab = f.fixed_tab;
         blocks += a.connect_blocks;

@@ -289,8 +289,7 @@ struct WalkLaunch {
     int variant;         // 2 = wave work sharing (the only one in a default build); 0 = one subpath per lane (FS_EXPERIMENTS)
     int num_cus;         // compute units of the device
     unsigned* queue_head;  // frame scratch: [0] unused, then plan counts + cursors; zero at launch
-    int plan;            // 1 = sort subpaths by their (RNG-determined) length before walking
-    uint32_t* perm;      // [depth + 1][total] subpath indices bucketed by planned length
+    uint32_t* perm;      // [depth + 1][total] subpath indices bucketed by planned (RNG-determined) length: the plan pass's schedule
     int rays_per_wave = 64;   // < 64: sparse waves for small frames (variant 2): a wave owns this many subpaths, the other lanes help
     int coop = 1;             // 1: waves of 1, 2 or 4 subpaths search every ray with ALL the lanes of its group (walk_kernel_coop) instead of
                               //    lane-private descents that hand subtrees to idle lanes; 0: the sparse kernel for every rays_per_wave < 64

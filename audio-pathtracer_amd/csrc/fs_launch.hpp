@@ -1,7 +1,6 @@
 // fs_launch.hpp — host-side helpers of the kernel launchers: LDS sizes and limits, the deep store, the cooperative
 // traversal's node arrays.
 #pragma once
-#include <cstdlib>
 
 #include "fs_dev_coop.hpp"   // (the cooperative kernels' LDS layout: kCoopCap, kCoopWaveBytes)
 
@@ -75,12 +74,10 @@ inline bool coop_fits(const CoopView& cv, int R) {
     const int per = (1 << cv.wshift) - 1, kfull = std::max(1, (64 / R) >> cv.wshift);
     return cv.rec != nullptr && cv.nodes > 0 && (64 / R) >= (1 << cv.wshift) && cv.stack_need + 8 + per * kfull <= kCoopCap / R;
 }
-// the node array waves of R rays walk (FS_COOP_WIDE: bit r set = 16-wide nodes for 2^r rays per wave; default 1 and 2 rays)
+// the node array waves of R rays walk: 16-wide nodes for 1 and 2 rays per wave, 4-wide for 4 (the other one if it does not fit)
 inline const CoopView* coop_view(const DeviceScene& sc, int R) {
-    static const int wide_mask = std::getenv("FS_COOP_WIDE") ? std::atoi(std::getenv("FS_COOP_WIDE")) : 3;
     if (!sc.coop_info) return nullptr;
-    const int bit = R == 1 ? 1 : (R == 2 ? 2 : 4);
-    const CoopView* v = (wide_mask & bit) ? &sc.coop_info->wide16 : &sc.coop_info->wide4;
+    const CoopView* v = (R == 1 || R == 2) ? &sc.coop_info->wide16 : &sc.coop_info->wide4;
     if (!coop_fits(*v, R)) v = v == &sc.coop_info->wide16 ? &sc.coop_info->wide4 : &sc.coop_info->wide16;
     return coop_fits(*v, R) ? v : nullptr;
 }

@@ -56,7 +56,7 @@ for S in [int(x) for x in os.environ.get("LANE_SWEEP_TICKS", "32,128").split(","
     ctx.close()
 print(json.dumps(res))
 '''
-# a setting = environment assignments separated by blanks ("FS_SYNC_LANE=48,0 FS_COOP_BIG=0"); settings separated by ";"
+# a setting = environment assignments separated by blanks ("FS_SYNC_LANE=48,0 FS_SYNC_STAGE_FROM=1"); settings separated by ";"
 SETTINGS = sys.argv[2].split(";") if len(sys.argv) > 2 else ["FS_SYNC_LANE=0", "FS_SYNC_LANE=48,0", "FS_SYNC_LANE=56,0", "FS_SYNC_LANE=64,0", "FS_SYNC_LANE=48,78",
                                                               "FS_SYNC_LANE=40,78", "FS_SYNC_LANE=56,100", "FS_SYNC_LANE=40,60"]
 for setting in SETTINGS:

@@ -12,7 +12,4 @@ seed=$((13+off)); run FS_STRESS_PIPELINE=2
 seed=$((14+off)); run FS_STRESS_PIPELINE=2 FS_STRESS_FPL=2
 seed=$((15+off)); run FS_STRESS_PIPELINE=2 FS_STRESS_FPL=4
 seed=$((16+off)); run FS_STRESS_PIPELINE=2 FS_STRESS_FPL=3 FS_STACK_ROWS_CAP=12
-seed=$((17+off)); run FS_STRESS_PIPELINE=2 FS_STRESS_FPL=2 FS_FUSED_DRAIN=0
-seed=$((18+off)); run FS_STRESS_PIPELINE=2 FS_STRESS_FPL=2 FS_FUSED_RECON=0
-seed=$((19+off)); run FS_STRESS_PIPELINE=1 FS_STRESS_FPL=2 FS_FRAME_CONNECT_FIRST=64
 grep -c "^rc=0" $log; grep "^rc=\|^===" $log | paste - - | grep -v "rc=0" ; tail -2 $log
