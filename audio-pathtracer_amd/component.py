@@ -344,6 +344,11 @@ class Context:
     def reverb_release(self, src):
         self.check(self.lib.fs_reverb_release(self.h, src))
 
+    def reverb_set_crossfade(self, src, samples):
+        """crossfade the callback between successive IRs over `samples` output samples (0: off, the reference's abrupt
+        switch; include/frequensee.h fs_reverb_set_crossfade)"""
+        self.check(self.lib.fs_reverb_set_crossfade(self.h, src, int(samples)))
+
     def apply_material_fd(self, in_buffer, absorption, transmission, scattering):
         """UMaterialAcousticProcessor::ApplyMaterialFD (MAP.cpp:8-107) -> (specular, diffuse, transmitted)"""
         x = np.ascontiguousarray(in_buffer, dtype=np.float32).reshape(-1)
@@ -645,6 +650,10 @@ class FrequenSeeAudioReverbPlugin:
     def ProcessSourceAudio(self, component: FrequenSeeAudioComponent, AudioBuffer, literal_tail=False):
         return self.ctx.reverb_process(component._src, AudioBuffer, apply_reverb=component.bApplyReverb,
                                        literal_tail=literal_tail)
+
+    def SetCrossfade(self, component: FrequenSeeAudioComponent, samples):
+        """not in the reference: fade each new impulse response in over `samples` output samples (0: abrupt switch)"""
+        self.ctx.reverb_set_crossfade(component._src, samples)
 
 
 class MaterialAcousticProcessor:

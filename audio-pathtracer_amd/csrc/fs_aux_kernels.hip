@@ -320,10 +320,16 @@ __global__ void reverb_prepare_kernel(const float* __restrict__ in, float* __res
     cur[frame + i] = literal ? in[i] : in[2 * i + 1];
 }
 
+// FADE (fs_reverb_set_crossfade, its own instantiation: the plain one's arguments and code are today's): a second IR
+// `ir_to` over the same register window — the u loads are shared, the IR loads and FMAs double — and per output
+// y = (1 - g) (ir * u) + g (ir_to * u), g = (p + 1) / fade_len while p = fade_pos + s < fade_len, else 1.  g depends on
+// the output only, so each thread mixes its partial sums before the reduction (the sum is linear).
+template <bool FADE>
 __global__ __launch_bounds__(kBlock) void reverb_conv_kernel(const float* __restrict__ ir, int ir_size,
                                                              const float* __restrict__ ring, unsigned head,
                                                              const float* __restrict__ cur, int frame,
-                                                             float* __restrict__ out_interleaved) {
+                                                             float* __restrict__ out_interleaved,
+                                                             const float* __restrict__ ir_to, int fade_pos, int fade_len) {
     __shared__ float s_part[kRevOut][kBlock + 1];
     const int ch = blockIdx.y;
     const int s0 = blockIdx.x * kRevOut;
@@ -334,9 +340,9 @@ __global__ __launch_bounds__(kBlock) void reverb_conv_kernel(const float* __rest
     const int slice = ((ir_size + kBlock - 1) / kBlock + 15) & ~15;
     const int k0 = (int)threadIdx.x * slice;
     const int k1 = min(k0 + slice, ir_size);
-    float acc[kRevOut];
+    float acc[kRevOut], acc_to[kRevOut];
 #pragma unroll
-    for (int o = 0; o < kRevOut; ++o) acc[o] = 0.0f;
+    for (int o = 0; o < kRevOut; ++o) { acc[o] = 0.0f; acc_to[o] = 0.0f; }
     for (int kb = k0; kb < k1; kb += 16) {
         float w[31], h[16];
         const int j0 = tail + s0 - kb - 15;   // u index of w[0]
@@ -353,6 +359,23 @@ __global__ __launch_bounds__(kBlock) void reverb_conv_kernel(const float* __rest
         for (int i = 0; i < 16; ++i)
 #pragma unroll
             for (int o = 0; o < kRevOut; ++o) acc[o] = fmaf(h[i], w[15 - i + o], acc[o]);
+        if (FADE) {
+            float h2[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) h2[i] = (kb + i) < ir_size ? ir_to[kb + i] : 0.0f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+#pragma unroll
+                for (int o = 0; o < kRevOut; ++o) acc_to[o] = fmaf(h2[i], w[15 - i + o], acc_to[o]);
+        }
+    }
+    if (FADE) {
+#pragma unroll
+        for (int o = 0; o < kRevOut; ++o) {
+            const int p = fade_pos + s0 + o;
+            const float g = p < fade_len ? (float)(p + 1) / (float)fade_len : 1.0f;
+            acc[o] = (1.0f - g) * acc[o] + g * acc_to[o];
+        }
     }
 #pragma unroll
     for (int o = 0; o < kRevOut; ++o) s_part[o][threadIdx.x] = acc[o];
@@ -376,6 +399,16 @@ __global__ void reverb_push_kernel(const float* __restrict__ in, float* __restri
     if (i >= frame) return;
     ring[(head + (unsigned)i) & (unsigned)(kRevRing - 1)] = in[2 * i];
     ring[kRevRing + ((head + (unsigned)i) & (unsigned)(kRevRing - 1))] = in[2 * i + 1];
+}
+
+// A crossfade starts (fs_reverb_set_crossfade): h_from := (1 - a) h_from + a h_to — the IR heard at the last output sample of
+// a fade that is cut short (a = p0 / L; a = 0 leaves h_from as it is) — then h_to := the device-resident IR.
+__global__ void reverb_fade_start_kernel(float* __restrict__ h_from, float* __restrict__ h_to, const float* __restrict__ ir,
+                                         int n, float a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (a > 0.0f) h_from[i] = (1.0f - a) * h_from[i] + a * h_to[i];
+    h_to[i] = ir[i];
 }
 
 // AddEnergyAtDelay on the device-resident buffer (FSAC.h:87-91)
@@ -460,12 +493,22 @@ void launch_update_sound(const DeviceScene& sc_in, const SoundKParams& sp, Sound
 }
 
 void launch_reverb(const float* ir, int ir_size, float* ring, unsigned head, const float* in, float* cur, float* out,
-                   int frame, int literal_tail, hipStream_t s) {
+                   int frame, int literal_tail, hipStream_t s, const float* ir_to, int fade_pos, int fade_len) {
     const int tb = 256;
+    const dim3 grid((frame + kRevOut - 1) / kRevOut, 2);
     hipLaunchKernelGGL(reverb_prepare_kernel, dim3((frame + tb - 1) / tb), dim3(tb), 0, s, in, cur, frame, literal_tail);
-    hipLaunchKernelGGL(reverb_conv_kernel, dim3((frame + kRevOut - 1) / kRevOut, 2), dim3(kBlock), 0, s, ir, ir_size,
-                       ring, head, cur, frame, out);
+    if (ir_to)
+        hipLaunchKernelGGL(reverb_conv_kernel<true>, grid, dim3(kBlock), 0, s, ir, ir_size, ring, head, cur, frame, out,
+                           ir_to, fade_pos, fade_len);
+    else
+        hipLaunchKernelGGL(reverb_conv_kernel<false>, grid, dim3(kBlock), 0, s, ir, ir_size, ring, head, cur, frame, out,
+                           nullptr, 0, 0);
     hipLaunchKernelGGL(reverb_push_kernel, dim3((frame + tb - 1) / tb), dim3(tb), 0, s, in, ring, head, frame);
+}
+
+void launch_reverb_fade_start(float* h_from, float* h_to, const float* ir, int n, float a, hipStream_t s) {
+    const int tb = 256;
+    hipLaunchKernelGGL(reverb_fade_start_kernel, dim3((n + tb - 1) / tb), dim3(tb), 0, s, h_from, h_to, ir, n, a);
 }
 
 #ifdef FS_WAVE_TIMELINE

@@ -199,6 +199,8 @@ int fs_save_impulse_response(fs_context* ctx, fs_source h, int32_t channel, cons
 }
 
 // ---- f2: reverb convolution (RVB.cpp:74-213) ---------------------------------------------------------------------
+static int alloc_fade(fs_context* ctx, Source* s);
+
 int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
@@ -213,7 +215,8 @@ int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
     FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     FS_HIP(ctx, hipStreamSynchronize(ctx->rev_stream));
     if (s->d_ring) { (void)hipFree(s->d_ring); (void)hipFree(s->d_rev_in); (void)hipFree(s->d_rev_cur); (void)hipFree(s->d_rev_out); }
-    s->d_ring = s->d_rev_in = s->d_rev_cur = s->d_rev_out = nullptr;
+    if (s->d_fade_from) { (void)hipFree(s->d_fade_from); (void)hipFree(s->d_fade_to); }
+    s->d_ring = s->d_rev_in = s->d_rev_cur = s->d_rev_out = s->d_fade_from = s->d_fade_to = nullptr;
     FS_HIP(ctx, hipMalloc((void**)&s->d_ring, sizeof(float) * 2 * kReverbRing));
     FS_HIP(ctx, hipMalloc((void**)&s->d_rev_in, sizeof(float) * 2 * (size_t)frame_size));
     FS_HIP(ctx, hipMalloc((void**)&s->d_rev_cur, sizeof(float) * 2 * (size_t)frame_size));
@@ -221,6 +224,34 @@ int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
     FS_HIP(ctx, hipMemsetAsync(s->d_ring, 0, sizeof(float) * 2 * kReverbRing, ctx->rev_stream));   // SetNumZeroed
     s->rev_head = 0;
     s->rev_frame = frame_size;
+    s->fading = s->fade_primed = false;   // (the first callback takes the IR unfaded)
+    if (s->fade_len > 0) return alloc_fade(ctx, s);
+    return FS_OK;
+}
+
+// fs_reverb_set_crossfade: the callback's two IR copies, once the source has a reverb and a fade length
+static int alloc_fade(fs_context* ctx, Source* s) {
+    const size_t bytes = sizeof(float) * (size_t)ctx->num_samples;
+    if (!s->d_fade_from) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_from, bytes));
+    if (!s->d_fade_to) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_to, bytes));
+    return FS_OK;
+}
+
+int fs_reverb_set_crossfade(fs_context* ctx, fs_source h, int32_t samples) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (samples < 0 || (int64_t)samples > 4 * (int64_t)ctx->cfg.sample_rate)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "crossfade length out of range (0 = off, 1 .. 4 * sample_rate)");
+    if (samples > 0 && s->d_ring) {
+        FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+        const int rc = alloc_fade(ctx, s);
+        if (rc) return rc;
+    }
+    if (s->fade_len == 0) s->fade_primed = false;   // enabling: nothing to fade from
+    s->fading = false;                              // a running fade ends at its target IR
+    s->fade_len = samples;
     return FS_OK;
 }
 
@@ -235,22 +266,52 @@ int fs_reverb_process(fs_context* ctx, fs_source h, const float* in, float* out,
         std::memcpy(out, in, sizeof(float) * 2 * (size_t)frame);
         return FS_OK;
     }
+    if (s->fade_len > 0 && (!s->d_fade_from || !s->d_fade_to))   // (fs_reverb_init could not allocate them)
+        return ctx->fail(FS_ERR_OUT_OF_MEMORY, "the crossfade's impulse-response buffers are missing: call fs_reverb_init again");
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     // Audio thread.  The callback has its own stream: it is never queued behind a traced frame on the compute stream.
     // The device-resident IR is written by reconstructs on the tail stream: read it behind the newest one and make the
     // next one wait for this read — both through events, exchanged with the game thread under the source's ir_mu.
+    // With a crossfade (fs_reverb_set_crossfade) the callback convolves its own copies of the IR: it reads d_ir_mono only when a
+    // newer IR is there (ir_gen), once, into h_to — only then does it wait for the write and make the next one wait for it.
     hipStream_t rs = ctx->rev_stream;
+    const bool xfade = s->fade_len > 0;
+    const int literal = (flags & FS_REVERB_LITERAL_TAIL) ? 1 : 0;
     {
         std::lock_guard<std::mutex> g(s->ir_mu);
-        if (s->last_rec >= 0) FS_HIP(ctx, stream_waits_for_rec(ctx, rs, s, s->last_rec));
+        const bool take = xfade && (!s->fade_primed || s->ir_gen != s->fade_gen);
+        if ((!xfade || take) && s->last_rec >= 0) FS_HIP(ctx, stream_waits_for_rec(ctx, rs, s, s->last_rec));
+        if (take) {
+            float a = 0.0f;
+            if (s->fade_primed) {   // a fade from what is heard now: h_to alone, or the mix at the last output sample of a running fade
+                if (s->fading) a = (float)s->fade_pos / (float)s->fade_len;
+                else std::swap(s->d_fade_from, s->d_fade_to);
+                s->fading = true;
+                s->fade_pos = 0;
+            }
+            launch_reverb_fade_start(s->d_fade_from, s->d_fade_to, s->d_ir_mono, ctx->num_samples, a, rs);
+            FS_HIP(ctx, hipGetLastError());
+            FS_HIP(ctx, hipEventRecord(s->ev_rev, rs));
+            s->rev_recorded = true;
+            s->fade_primed = true;
+            s->fade_gen = s->ir_gen;
+        }
         FS_HIP(ctx, hipMemcpyAsync(s->d_rev_in, in, sizeof(float) * 2 * (size_t)frame, hipMemcpyHostToDevice, rs));
-        launch_reverb(s->d_ir_mono, ctx->num_samples, s->d_ring, s->rev_head, s->d_rev_in, s->d_rev_cur, s->d_rev_out, frame,
-                      (flags & FS_REVERB_LITERAL_TAIL) ? 1 : 0, rs);
+        if (!xfade)
+            launch_reverb(s->d_ir_mono, ctx->num_samples, s->d_ring, s->rev_head, s->d_rev_in, s->d_rev_cur, s->d_rev_out, frame, literal, rs);
+        else if (s->fading)
+            launch_reverb(s->d_fade_from, ctx->num_samples, s->d_ring, s->rev_head, s->d_rev_in, s->d_rev_cur, s->d_rev_out, frame, literal, rs,
+                          s->d_fade_to, s->fade_pos, s->fade_len);
+        else
+            launch_reverb(s->d_fade_to, ctx->num_samples, s->d_ring, s->rev_head, s->d_rev_in, s->d_rev_cur, s->d_rev_out, frame, literal, rs);
         FS_HIP(ctx, hipGetLastError());
-        FS_HIP(ctx, hipEventRecord(s->ev_rev, rs));
-        s->rev_recorded = true;
+        if (!xfade) {
+            FS_HIP(ctx, hipEventRecord(s->ev_rev, rs));
+            s->rev_recorded = true;
+        }
     }
     s->rev_head += (unsigned)frame;
+    if (s->fading && (s->fade_pos += frame) >= s->fade_len) s->fading = false;   // complete: h_from := h_to, one convolution again
     FS_HIP(ctx, hipMemcpyAsync(out, s->d_rev_out, sizeof(float) * 2 * (size_t)frame, hipMemcpyDeviceToHost, rs));
     FS_HIP(ctx, hipStreamSynchronize(rs));
     return FS_OK;
@@ -264,6 +325,7 @@ int fs_reverb_release(fs_context* ctx, fs_source h) {
         FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
         FS_HIP(ctx, hipMemsetAsync(s->d_ring, 0, sizeof(float) * 2 * kReverbRing, ctx->rev_stream));
         s->rev_head = 0;
+        s->fading = false;   // a running crossfade ends at its target IR
     }
     return FS_OK;
 }

@@ -164,6 +164,8 @@ void free_source(fs_context* ctx, Source* s) {
         if (s->d_rev_in) (void)hipFree(s->d_rev_in);
         if (s->d_rev_cur) (void)hipFree(s->d_rev_cur);
         if (s->d_rev_out) (void)hipFree(s->d_rev_out);
+        if (s->d_fade_from) (void)hipFree(s->d_fade_from);
+        if (s->d_fade_to) (void)hipFree(s->d_fade_to);
     }
     delete s;
 }

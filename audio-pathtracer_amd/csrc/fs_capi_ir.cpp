@@ -137,7 +137,7 @@ int fs_set_impulse_response(fs_context* ctx, fs_source h, const float* ir, int32
         const int cur = s->last_rec >= 0 ? s->last_rec : s->cur;
         FS_HIP(ctx, hipEventRecord(s->ev_rec[cur], tail));   // the reverb waits on this before reading d_ir_mono
         s->rec_recorded[cur] = true; s->rec_batch[cur] = 0; s->rec_on_compute[cur] = false;
-        s->last_rec = cur;
+        s->last_rec = cur; s->ir_gen++;
     }
     uint64_t seq = s->enqueued + 1;
     int slot = (int)(seq % kIrRing);

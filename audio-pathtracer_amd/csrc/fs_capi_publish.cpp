@@ -244,7 +244,7 @@ int owed_publish(fs_context* ctx, OwedLaunch& ol, bool launched_fused) {
         Source* s = o.s;
         s->rec_recorded[o.cur] = true; s->rec_on_compute[o.cur] = true; s->rec_batch[o.cur] = 0;
         if (ol.newest[i]) {   // (ir_mu is held)
-            s->last_rec = o.cur; s->cur_pub_seq = 0; s->dev_ir_word = ol.pub.id;
+            s->last_rec = o.cur; s->cur_pub_seq = 0; s->dev_ir_word = ol.pub.id; s->ir_gen++;
             if (s->d_ring) FS_HIP(ctx, hipEventRecord(s->ev_rec[o.cur], ctx->stream));   // fs_reverb_process reads d_ir_mono behind this
         }
         note_publish(ctx, s, ol.seq[i], (int)(ol.seq[i] % kIrRing), 0, ol.pub.id);
@@ -333,7 +333,7 @@ int reconstruct_now(fs_context* ctx, Source* s, const fs_params* p) {
         FS_HIP(ctx, hipGetLastError());
         FS_HIP(ctx, hipEventRecord(s->ev_rec[s->cur], tail));
         s->rec_recorded[s->cur] = true; s->rec_batch[s->cur] = 0; s->rec_on_compute[s->cur] = false;
-        s->last_rec = s->cur;
+        s->last_rec = s->cur; s->ir_gen++;
     }
     uint64_t seq = s->enqueued + 1;
     int slot = (int)(seq % kIrRing);
@@ -436,7 +436,7 @@ int reconstruct_batch(fs_context* ctx, Source* const* srcs, int count, const fs_
         for (int i = 0; i < n; ++i) {
             Source* s = g[i];
             s->rec_recorded[s->cur] = true; s->rec_batch[s->cur] = batch; s->rec_on_compute[s->cur] = on_compute;
-            s->last_rec = s->cur;
+            s->last_rec = s->cur; s->ir_gen++;
             const uint64_t seq = s->enqueued + 1;
             note_publish(ctx, s, seq, (int)(seq % kIrRing), batch, pub.id);
             if (on_compute) {

@@ -84,9 +84,10 @@ struct Source {
     hipEvent_t ev_rev = nullptr;       // reverb stream: the newest reverb callback has read d_ir_mono
     bool rev_recorded = false;
     // fs_reverb_process runs on the AUDIO thread while the game thread reconstructs: ir_mu guards what both touch —
-    // last_rec / rec_recorded / ev_rec (written by the reconstruct, read by the callback) and rev_recorded / ev_rev
+    // last_rec / rec_recorded / ev_rec / ir_gen (written by the reconstruct, read by the callback) and rev_recorded / ev_rev
     // (the other way round).  Held only while work is ENQUEUED (microseconds), never across a stream wait.
     std::mutex ir_mu;
+    uint64_t ir_gen = 0;               // bumped by every rewrite of the device IR (reconstructs, fs_set_impulse_response)
     float* energy() const { return d_energy[cur]; }
     // multi-GPU: the frame in the current buffer has been summed over the ranks (library collective), or handed to the
     // caller's collective (fs_energy_handoff); a world_size > 1 context refuses to reconstruct a frame that is neither
@@ -126,6 +127,14 @@ struct Source {
     // reverb (row f2): history rings [2][kReverbRing], staging buffers, write head
     float* d_ring = nullptr; float* d_rev_in = nullptr; float* d_rev_cur = nullptr; float* d_rev_out = nullptr;
     unsigned rev_head = 0; int rev_frame = 0;
+    // crossfade between successive IRs (fs_reverb_set_crossfade; the callback's own state, audio thread): fade_len L samples
+    // (0: off), the callback's copies of the IRs it fades between (h_to = the newest it took, generation fade_gen),
+    // fade_pos = samples output since the running fade began; fading == false: h_to alone is heard.
+    // fade_primed == false: h_to holds nothing yet (after fs_reverb_init or enabling) — the next callback takes the IR unfaded.
+    float* d_fade_from = nullptr; float* d_fade_to = nullptr;
+    int32_t fade_len = 0, fade_pos = 0;
+    bool fading = false, fade_primed = false;
+    uint64_t fade_gen = 0;
     float occlusion = 1.0f;            // OcclusionAttenuation FSAC.h:130 (1.f until the first UpdateSound)
 };
 

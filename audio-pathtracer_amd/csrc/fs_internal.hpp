@@ -384,8 +384,11 @@ void launch_trace_rays(const DeviceScene& sc, const float* o, const float* d, co
 // rays_per_wave < 64: sparse waves whose other lanes help with every closest-hit query; 64 = one ray per lane
 void launch_update_sound(const DeviceScene& sc, const SoundKParams& sp, SoundAccum* acc, int rays_per_wave, hipStream_t s);
 constexpr int kReverbRing = 65536;   // per-channel history ring (floats), matches kRevRing in the kernels
+// ir_to != nullptr: a crossfade from `ir` to `ir_to`, fade_pos samples into a fade of fade_len (fs_reverb_set_crossfade)
 void launch_reverb(const float* ir, int ir_size, float* ring, unsigned head, const float* in, float* cur, float* out,
-                   int frame, int literal_tail, hipStream_t s);
+                   int frame, int literal_tail, hipStream_t s, const float* ir_to = nullptr, int fade_pos = 0, int fade_len = 0);
+// a crossfade starts: h_from := (1 - a) h_from + a h_to (a > 0), then h_to := ir (n samples)
+void launch_reverb_fade_start(float* h_from, float* h_to, const float* ir, int n, float a, hipStream_t s);
 void launch_add_energy(float* energy_row, int num_bins, float delay_s, float e, hipStream_t s);
 // dynamic LDS the traversal kernels of a frame need for a tree with `stack_rows` stack rows: the larger of the walk
 // kernel (stack + work-sharing area) and the connect kernels (stack + [bands][bins] histogram + work-sharing area)

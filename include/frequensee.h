@@ -50,7 +50,7 @@
  *             fs_comm_enable_oneshot fs_comm_detach fs_comm_info fs_peers_init fs_peers_detach fs_gather_energy fs_gather_energy_async
  *             fs_copy_band_impulse_response fs_set_impulse_response fs_trace_rays
  *             fs_save_array_to_file fs_load_float_array fs_save_impulse_response
- *             fs_reverb_init fs_reverb_process fs_reverb_release fs_apply_material_fd
+ *             fs_reverb_init fs_reverb_process fs_reverb_release fs_reverb_set_crossfade fs_apply_material_fd
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
  * Environment variables (FS_*) are tuning and diagnostic knobs only; all of them are read ONCE — at fs_context_create, at a
@@ -526,7 +526,26 @@ int fs_reverb_init(fs_context* ctx, fs_source src, int32_t frame_size /* BufferL
  * reconstruct that wrote it (events, exchanged under a per-source mutex held only while work is enqueued) and waits for
  * its own stream only.  fs_reverb_init / fs_reverb_release of a source must not run concurrently with its callback. */
 int fs_reverb_process(fs_context* ctx, fs_source src, const float* in, float* out, int32_t apply_reverb, uint32_t flags);
-int fs_reverb_release(fs_context* ctx, fs_source src); /* OnReleaseSource: ClearBuffers */
+int fs_reverb_release(fs_context* ctx, fs_source src); /* OnReleaseSource: ClearBuffers; also ends a running crossfade */
+/* Crossfade between successive impulse responses (not in the reference, which switches abruptly; opt-in per source).
+ * samples == 0 (the default): every callback convolves with the IR on the device at that moment, the reference's switch.
+ * 1 <= samples <= 4 * sample_rate: the fade length L; anything else is FS_ERR_INVALID_ARGUMENT.  May be set before or after
+ * fs_reverb_init, under the same threading contract (never concurrently with the source's callback); every call ends a
+ * running fade at its target IR.  With L > 0 the callback keeps two IRs of its own on the device, h_from and h_to:
+ *  1. It sees the IR the default path would (the newest reconstruct's or fs_set_impulse_response's, waited for through the
+ *     same events).  When that IR is newer than h_to, a fade to it starts at this callback's first output sample; of several
+ *     rewrites between two callbacks only the newest counts.
+ *  2. With p = output samples since the fade began and g = (p + 1) / L while p < L:
+ *       y[s] = clamp((1 - g) (h_from * u)[s] + g (h_to * u)[s], -1, 1)
+ *     where u is the input the default path convolves (FS_REVERB_LITERAL_TAIL selects it as there).  At p = L the fade is
+ *     complete (h_from := h_to) and callbacks convolve one IR again.
+ *  3. A new IR p0 samples into a fade: h_from := (1 - p0 / L) h_from + (p0 / L) h_to (the IR heard at the last output sample),
+ *     then a fade from there to the new IR.  Exact (the convolution is linear in the IR): never more than two convolutions.
+ *  4. The first callback after fs_reverb_init or after enabling takes the current IR without a fade.  fs_reverb_release
+ *     clears the history and ends any fade; the bypass (apply_reverb == 0) touches no fade state.
+ *  5. The fade is linear, not equal-power: successive IRs of one source are strongly correlated (equal power would raise the
+ *     level by up to 3 dB mid-fade). */
+int fs_reverb_set_crossfade(fs_context* ctx, fs_source src, int32_t samples);
 
 /* ---- row f4: frequency-dependent material response of one audio block ------------------------------------
  *      UMaterialAcousticProcessor::ApplyMaterialFD (Private/MaterialAcousticProcessor.cpp:8-107, MAP.cpp):
