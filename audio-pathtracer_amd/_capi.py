@@ -52,8 +52,9 @@ EXPORTS = [
     "fs_apply_material_fd", "fs_energy_handoff", "fs_scene_update_triangles", "fs_scene_refit", "fs_set_impulse_response",
     "fs_scene_commit_fast", "fs_comm_unique_id", "fs_comm_init", "fs_comm_attach", "fs_comm_detach", "fs_comm_info", "fs_comm_enable_oneshot", "fs_shard_range",
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
-    "fs_set_band_edges",
+    "fs_set_band_edges", "fs_source_set_orientation", "fs_source_set_directivity",
 ]
+MAX_DIRECTIVITY_SAMPLES = 181   # FS_MAX_DIRECTIVITY_SAMPLES: 1 degree steps
 COMM_ID_BYTES = 128
 ERR_COMM = 8
 ERR_OVERFLOW = 9
@@ -224,6 +225,8 @@ def load():
         "fs_listener_set_position": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "fs_source_set_object": (C.c_int, [vp, i32, C.c_uint32]),
         "fs_listener_set_object": (C.c_int, [vp, C.c_uint32]),
+        "fs_source_set_orientation": (C.c_int, [vp, i32, C.POINTER(C.c_float)]),
+        "fs_source_set_directivity": (C.c_int, [vp, i32, f32p, i32, i32]),
         "fs_compute_energy_response": (C.c_int, [vp, i32, C.POINTER(Params), f32p]),
         "fs_compute_energy_response_async": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "fs_compute_energy_response_batch_async": (C.c_int, [vp, C.POINTER(C.c_int32), i32, C.POINTER(Params)]),

@@ -225,6 +225,21 @@ class Context:
     def set_listener_object(self, object_id=_capi.NO_OBJECT):
         self.check(self.lib.fs_listener_set_object(self.h, int(object_id)))
 
+    def set_source_orientation(self, src, forward):
+        """fs_source_set_orientation: the forward vector the source's directivity table is measured from (default (1, 0, 0))"""
+        self.check(self.lib.fs_source_set_orientation(self.h, int(src), _f3(forward)))
+
+    def set_source_directivity(self, src, gains=None):
+        """fs_source_set_directivity: gains [bands][samples] (sample k at k pi / (samples - 1) from the forward vector) or
+        None (omnidirectional again)"""
+        if gains is None:
+            self.check(self.lib.fs_source_set_directivity(self.h, int(src), None, 0, 0))
+            return
+        g = np.ascontiguousarray(gains, dtype=np.float32)
+        if g.ndim != 2:
+            raise ValueError("gains must be [bands][samples]")
+        self.check(self.lib.fs_source_set_directivity(self.h, int(src), g.ctypes.data, g.shape[0], g.shape[1]))
+
     def compute_energy_response_batch_async(self, sources, params):
         """several sources in one traced frame (UpdateSource over ActiveSources): same result per source as separate calls"""
         arr = (C.c_int32 * len(sources))(*[int(x) for x in sources])
@@ -427,6 +442,14 @@ class FrequenSeeAudioComponent:
         self._location = np.asarray(xyz, dtype=np.float32)
         if self._subsys is not None:
             self._ctx().set_source_position(self._src, self._location)
+
+    def SetForwardVector(self, forward):
+        """the owner's GetForwardVector(): what the directivity table is measured from"""
+        self._ctx().set_source_orientation(self._src, forward)
+
+    def SetDirectivity(self, gains=None):
+        """per-band gains [bands][samples] over 0 .. 180 degrees from the forward vector; None = omnidirectional"""
+        self._ctx().set_source_directivity(self._src, gains)
 
     @property
     def EnergyBuffer(self):

@@ -166,6 +166,7 @@ void free_source(fs_context* ctx, Source* s) {
         if (s->d_rev_out) (void)hipFree(s->d_rev_out);
         if (s->d_fade_from) (void)hipFree(s->d_fade_from);
         if (s->d_fade_to) (void)hipFree(s->d_fade_to);
+        if (s->d_dir) (void)hipFree(s->d_dir);   // (the callers have synchronised the compute stream)
     }
     delete s;
 }
@@ -655,6 +656,8 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->d_carrier) (void)hipFree(ctx->d_carrier);
         if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
         for (hipEvent_t e : ctx->ev_batch) if (e) (void)hipEventDestroy(e);
+        for (const fs_context::RetiredTable& r : ctx->retired_tables) { (void)hipFree(r.p); (void)hipEventDestroy(r.ev); }
+        ctx->retired_tables.clear();
     }
     for (hipEvent_t ev : ctx->tail_batch_ev) if (ev) (void)hipEventDestroy(ev);
     if (ctx->h_recon_tab) (void)hipHostFree(ctx->h_recon_tab);

@@ -36,6 +36,8 @@ struct Frame {
     KParams kp{};
     int B = 1, levels = 0;
     bool batch = false, unbounded = false, all_conn = false, mis = false, fixed = false, accumulate = false, pipe_ok = false;
+    bool dir = false;                   // some source of the frame has a directivity table: the directional connect kernels run
+    DirArgs dargs{};                    // ... with these descriptors (the orientations and tables in force at the frame's call)
     std::vector<WalkStage> stages;      // the walk in one piece, or the stages of a pipelined depth = 0 frame
     int lane_len = 0;                   // a waited-for staged frame: walks of this many steps or more take the long-walk lane (0: none)
     // frame_resources
@@ -131,14 +133,21 @@ void frame_describe(fs_context* ctx, Frame& f) {
     kp.mis = f.mis ? 1 : 0;
     f.fixed = (p->flags & FS_FLAG_DETERMINISTIC) != 0;
     f.accumulate = (p->flags & FS_FLAG_ACCUMULATE_ENERGY) != 0;
+    f.dir = false;
+    for (int i = 0; i < f.count; ++i) if (f.srcs[i]->d_dir) f.dir = true;
+    f.dargs.one = s->directivity();
+    f.dargs.tab = nullptr;
     // Pipelined frames: this frame's passes are held back (to be launched with the next frames') when the frame has the
     // default shape; any other frame first lets the held-back ones finish on their own.  A depth = 0 frame is held at
     // pipeline depth 2 only, as a STAGED walk: its longest walk is a chain of ~ log(subpaths) / log(1 / rr) dependent
     // bounces (118 at 262 144 subpaths) while 97 % of the walks end within 32 — launch s + 1 of the frame walks steps
     // [bound[s - 1], bound[s]) of the walks still alive, next to the other stages of the frames around it, so that every
     // launch carries one frame's worth of work and no chain longer than a stage.
-    const bool plain = !(p->flags & (FS_FLAG_MATERIAL_LOBES | FS_FLAG_MIS_BALANCE | FS_FLAG_ALL_CONNECTIONS | FS_FLAG_ACCUMULATE_ENERGY |
-                                     FS_FLAG_DOUBLE_POSITIONS));
+    const bool plain_walk = !(p->flags & (FS_FLAG_MATERIAL_LOBES | FS_FLAG_MIS_BALANCE | FS_FLAG_ALL_CONNECTIONS | FS_FLAG_ACCUMULATE_ENERGY |
+                                          FS_FLAG_DOUBLE_POSITIONS));
+    // (a directional source: its connect pass has no fused form — the frame runs on its own, like FS_FLAG_DOUBLE_POSITIONS
+    // frames; its walk is any other's, staged too when it is waited for)
+    const bool plain = plain_walk && !f.dir;
     // (a walk that ignores the actor it starts from — what the reference's GeneratePath always does, ARTS.cpp:322-327 — is held
     // like any other: the fused launch has a flavour whose walk parts carry the ignored actor, fs_frame_ext.hip)
     f.pipe_ok = ctx->pipelining > 0 && ctx->profiling < 2 && plain && !(p->listener_radius > 0.0f || p->source_radius > 0.0f) &&
@@ -158,7 +167,7 @@ void frame_describe(fs_context* ctx, Frame& f) {
         for (int bound : bounds) { WalkStage sr; sr.begin = begin; sr.end = bound; f.stages.push_back(sr); begin = bound; }
         WalkStage last; last.begin = begin; last.end = 1 << 30;
         f.stages.push_back(last);
-    } else if (!f.pipe_ok && f.unbounded && plain && ctx->profiling < 3 &&
+    } else if (!f.pipe_ok && f.unbounded && plain_walk && ctx->profiling < 3 &&
                // (an ignored actor or end-point spheres stage too: the stage kernels' EXT instantiations — tests/test_round5.py)
                !ctx->sync_stage_bounds.empty() && 2ull * kp.num_local >= (unsigned long long)ctx->sync_stage_from &&
                (2ull * kp.num_local >= (unsigned long long)kSyncStageFromWithoutLane || !ctx->sync_stage_from_default ||
@@ -264,8 +273,10 @@ int frame_resources(fs_context* ctx, Frame& f) {
     }
     if (f.batch) {
         // per-frame tables in one pinned staging block: energy pointers [count] | fixed-point buffer pointers [count] |
-        // source positions + actor ids [count][4].  The block is rewritten only after the previous frame's copy has left it.
-        const size_t bytes = 2 * (size_t)count * sizeof(void*) + (size_t)count * 4 * sizeof(float);
+        // source positions + actor ids [count][4] | (directional frames) directivity descriptors [count].  The block is rewritten
+        // only after the previous frame's copy has left it.
+        const size_t dir_off = 2 * (size_t)count * sizeof(void*) + (size_t)count * 4 * sizeof(float);   // (a multiple of 8)
+        const size_t bytes = dir_off + (f.dir ? (size_t)count * sizeof(Directivity) : 0);
         if (bytes > ctx->batch_cap) {
             FS_FLUSH(ctx);   // a held batched frame still carries pointers into the block that is about to be freed
             FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -296,6 +307,10 @@ int frame_resources(fs_context* ctx, Frame& f) {
                 t_fx[i] = f.fixed ? (void*)f.srcs[i]->d_fixed[f.cur_of[i]] : nullptr;
                 std::memcpy(t_pos + 4 * i, f.group ? f.group[i].pos : f.srcs[i]->pos, sizeof(float) * 3);
                 std::memcpy(t_pos + 4 * i + 3, &f.srcs[i]->object, sizeof(uint32_t));   // the source's actor (its walks ignore it)
+                if (f.dir) {
+                    const Directivity d = f.srcs[i]->directivity();
+                    std::memcpy(ctx->batch_build.data() + dir_off + (size_t)i * sizeof(Directivity), &d, sizeof(d));
+                }
             }
         }
         bool found = false;   // any slot that already holds exactly this table will do (it is only read)
@@ -332,6 +347,7 @@ int frame_resources(fs_context* ctx, Frame& f) {
         f.energy_tab = reinterpret_cast<float* const*>(db);
         f.fixed_tab = f.fixed ? reinterpret_cast<unsigned long long* const*>(db + (size_t)count * sizeof(void*)) : nullptr;
         kp.src_table = reinterpret_cast<const float*>(db + 2 * (size_t)count * sizeof(void*));
+        if (f.dir) f.dargs.tab = reinterpret_cast<const Directivity*>(db + dir_off);
     }
     return FS_OK;
 }
@@ -515,10 +531,11 @@ int frame_launch(fs_context* ctx, Frame& f) {
     }
     if (timed_frame) FS_HIP(ctx, hipEventRecord(tf.e[1], ctx->stream));
     if (f.all_conn)
-        launch_connect_all(B, ctx->scene, kp, st, s->energy(), fixed ? s->d_fixed[s->cur] : nullptr, scratch, ctx->stream);
+        launch_connect_all(B, ctx->scene, kp, st, s->energy(), fixed ? s->d_fixed[s->cur] : nullptr, scratch, ctx->stream,
+                           f.dir ? &f.dargs : nullptr);
     else
         launch_connect(B, ctx->scene, kp, st, s->energy(), fixed ? s->d_fixed[s->cur] : nullptr, scratch, ppw,
-                       energy_tab, fixed_tab, ctx->stream);
+                       energy_tab, fixed_tab, ctx->stream, f.dir ? &f.dargs : nullptr);
     if (fixed)
         for (int i = 0; i < count; ++i)
             launch_fixed_to_energy(srcs[i]->d_fixed[srcs[i]->cur], srcs[i]->energy(), B * ctx->num_bins, ctx->stream);
@@ -698,6 +715,67 @@ int fs_source_set_object(fs_context* ctx, fs_source h, uint32_t object_id) {
     return FS_OK;
 }
 
+int fs_source_set_orientation(fs_context* ctx, fs_source h, const float forward[3]) {
+    if (!ctx || !forward) return FS_ERR_INVALID_ARGUMENT;
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    const float x = forward[0], y = forward[1], z = forward[2];
+    const float l2 = x * x + y * y + z * z;
+    if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z) || !(l2 > 0.0f) || !std::isfinite(l2))
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_source_set_orientation: forward must be finite and non-zero");
+    const float len = sqrtf(l2);
+    // (no flush: a frame that waits in a group or the pipeline is omnidirectional, and a directional one has its copy)
+    s->fwd[0] = x / len; s->fwd[1] = y / len; s->fwd[2] = z / len;
+    return FS_OK;
+}
+
+int fs_source_set_directivity(fs_context* ctx, fs_source h, const float* gains, int32_t bands, int32_t samples) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (gains) {
+        if (bands != ctx->cfg.num_bands) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_source_set_directivity: bands != the context's band count");
+        if (samples < 2 || samples > FS_MAX_DIRECTIVITY_SAMPLES)
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_source_set_directivity: samples must be 2 .. FS_MAX_DIRECTIVITY_SAMPLES");
+        for (size_t i = 0; i < (size_t)bands * (size_t)samples; ++i)
+            if (!std::isfinite(gains[i]) || !(gains[i] >= 0.0f))
+                return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_source_set_directivity: gains must be finite and >= 0");
+    }
+    if (!gains && !s->d_dir) return FS_OK;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    FS_FLUSH(ctx);   // frames collected for a grouped launch were asked for with the old setting
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    // the tables of earlier set calls that no enqueued frame can read any more
+    for (size_t i = 0; i < ctx->retired_tables.size();) {
+        const fs_context::RetiredTable r = ctx->retired_tables[i];
+        if (hipEventQuery(r.ev) == hipSuccess) {
+            (void)hipFree(r.p); (void)hipEventDestroy(r.ev);
+            ctx->retired_tables[i] = ctx->retired_tables.back(); ctx->retired_tables.pop_back();
+        } else ++i;
+    }
+    float* fresh = nullptr;
+    if (gains) {   // a new allocation, filled before any frame can see it: an enqueued frame keeps reading the table of its call
+        const size_t bytes = sizeof(float) * (size_t)bands * (size_t)samples;
+        FS_HIP(ctx, hipMalloc((void**)&fresh, bytes));
+        const hipError_t e = hipMemcpy(fresh, gains, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(fresh); return ctx->hip_fail(e, "hipMemcpy(directivity)"); }
+    }
+    if (s->d_dir) {
+        fs_context::RetiredTable r{s->d_dir, nullptr};
+        hipError_t e = hipEventCreateWithFlags(&r.ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(r.ev, ctx->stream);
+        if (e != hipSuccess) {
+            if (r.ev) (void)hipEventDestroy(r.ev);
+            if (fresh) (void)hipFree(fresh);
+            return ctx->hip_fail(e, "hipEventRecord(directivity)");
+        }
+        ctx->retired_tables.push_back(r);
+    }
+    s->d_dir = fresh;
+    s->dir_samples = gains ? samples : 0;
+    return FS_OK;
+}
+
 int fs_listener_set_object(fs_context* ctx, uint32_t object_id) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     if (object_id != ctx->listener_object) FS_FLUSH(ctx);
@@ -723,7 +801,7 @@ int fs_compute_energy_response_async(fs_context* ctx, fs_source h, const fs_para
     fs_params def;
     const fs_params* q = p;
     if (!q) { fs_params_default(&def); q = &def; }
-    if (q->struct_size == sizeof(fs_params) && groupable(ctx, q)) {
+    if (q->struct_size == sizeof(fs_params) && groupable(ctx, q) && !s->d_dir) {   // (a directional source's frames are never held)
         if (!ctx->group.empty() && (!same_but_seed(ctx->group[0].p, *q) || std::memcmp(ctx->group[0].lis, ctx->listener, sizeof(ctx->listener)) != 0)) {
             const int gr = dispatch_group(ctx);   // (a batched frame has ONE listener position)
             if (gr) return gr;

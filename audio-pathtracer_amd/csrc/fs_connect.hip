@@ -14,6 +14,17 @@ __global__ __launch_bounds__(kBlock, AHEAD > 4 ? 2 : 4) void connect_kernel(Devi
                                                          unsigned long long* const* __restrict__ fixed_tab) {
     connect_body<B, LOBES, BATCH, COUNT, EXT, AHEAD>(blockIdx.x, gridDim.x, sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab);
 }
+// a directional source (fs_source_set_directivity): the same pass, every deposit weighted by D_b(w_e) — an entry of its own, so
+// that the kernels above keep their arguments
+template <int B, int LOBES, bool BATCH, bool COUNT, bool EXT = false, int AHEAD = 1>
+__global__ __launch_bounds__(kBlock, AHEAD > 4 ? 2 : 4) void connect_dir_kernel(DeviceScene sc, KParams kp, SubpathState st,
+                                                             float* __restrict__ energy,
+                                                             unsigned long long* __restrict__ fixed, unsigned* queue_head,
+                                                             int pairs_per_wave, float* const* __restrict__ energy_tab,
+                                                             unsigned long long* const* __restrict__ fixed_tab, DirArgs dir) {
+    connect_body<B, LOBES, BATCH, COUNT, EXT, AHEAD, true>(blockIdx.x, gridDim.x, sc, kp, st, energy, fixed, queue_head, pairs_per_wave,
+                                                          energy_tab, fixed_tab, dir);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // connect_all_kernel (row f3): the reference's unfinished "naive connections" (Is_NaiveConnections,
@@ -81,139 +92,12 @@ __device__ float mis_weight(const KParams& kp, const SubpathState& st, uint32_t 
     return (float)w;
 }
 
-template <int B>
-__global__ __launch_bounds__(kBlock) void connect_all_kernel(DeviceScene sc, KParams kp, SubpathState st,
-                                                             float* __restrict__ energy,
-                                                             unsigned long long* __restrict__ fixed,
-                                                             unsigned* queue_head) {
-    extern __shared__ __attribute__((aligned(16))) int s_dyn[];   // [stack_rows][kBlock] stack | [B][hist_window] histogram
-    int* s_stack = s_dyn;
-    float* s_hist = reinterpret_cast<float*>(s_dyn + (size_t)sc.stack_rows * kBlock);
-    const int nb = kp.num_bins, W = kp.hist_window, NB = band_count<B>(kp);
-    int* s_share = reinterpret_cast<int*>(s_hist + (size_t)NB * W);   // work-sharing area of trav_any_shared
-    __shared__ int s_lo, s_hi;
-    for (int i = threadIdx.x; i < NB * W; i += kBlock) s_hist[i] = 0.0f;
-    if (threadIdx.x == 0) { s_lo = nb; s_hi = -1; }
-    if (blockIdx.x == 0)
-        for (int i = threadIdx.x; i < 1 + 2 * kPlanBuckets; i += kBlock) queue_head[i] = 0u;
-    __syncthreads();
-
-    const uint32_t n = kp.num_local;
-    const uint32_t total = 2u * n;
-    const int lane = (int)(threadIdx.x & 63u);
-    const uint32_t wave = threadIdx.x >> 6, waves = kBlock / 64;
-    unsigned my_deposits = 0, my_tests = 0, my_segments = 0;
-    for (uint32_t li = blockIdx.x * waves + wave; li < n; li += gridDim.x * waves) {
-        const uint32_t sf = slot_of(st, li), sl = slot_of(st, n + li);
-        const uint2 Fm = st.end_misc[sf];
-        const uint2 Lm = st.end_misc[sl];
-        const int kf = (int)Fm.y, kl = (int)Lm.y;
-        if (lane == 0) my_segments += (unsigned)(kf + kl);   // fs_stats.segments: the steps the two walks took
-        // depth = 0 only: a walk that outlived the record store (overflow word raised, the frame is traced again)
-        if (st.over_levels && !(rec_fits(st, kf - 1, sf) && rec_fits(st, kl - 1, sl))) continue;
-        const int combos = (kf + 1) * (kl + 1);
-        for (int c0 = 0; c0 < combos; c0 += 64) {   // wave-uniform trip count: all lanes share the visibility queries
-            const bool active = c0 + lane < combos;
-            const int c = active ? c0 + lane : 0;
-            if (active) ++my_tests;
-            const int i = c / (kl + 1), j = c - i * (kl + 1);
-            // node Fi (position, material, probability) and node Bj (position)
-            float fx = kp.src[0], fy = kp.src[1], fz = kp.src[2];
-            if (i > 0) { const float4 q = load_pos(st, total, i - 1, sf); fx = q.x; fy = q.y; fz = q.z; }
-            float bx = kp.lis[0], by = kp.lis[1], bz = kp.lis[2];
-            if (j > 0) { const float4 q = load_pos(st, total, j - 1, sl); bx = q.x; by = q.y; bz = q.z; }
-            uint32_t fmat; float fprob;
-            if (i < kf) { fmat = load_mat(st, total, i, sf); fprob = load_np(st, total, i, sf).y; }
-            else { fmat = Fm.x; fprob = st.end_pos[sf].w; }
-            fmat &= 0xFFFFu;   // a connection vertex scatters diffusely whatever lobe the walk took there later (row f4)
-            float dx = bx - fx, dy = by - fy, dz = bz - fz;
-            float l2 = dx * dx + dy * dy + dz * dz;
-            float len = sqrtf(l2);
-            float inv = 1.0f / len;
-            float tmax = len - kp.connect_pullback;
-            bool has_ray = active && (l2 > 1e-8f) && (tmax > 0.0f);
-            Ray ray = make_ray(fx, fy, fz, dx * inv, dy * inv, dz * inv);
-            bool sphere_blocked = false;   // the end points' collision spheres: ConnectSubpaths ignores no actor
-            if (has_ray && (kp.listener_radius > 0.0f || kp.source_radius > 0.0f)) {
-                float ts;
-                sphere_blocked = (kp.listener_radius > 0.0f && sphere_hit(ray, kp.lis, kp.listener_radius, tmax, ts)) ||
-                                 (kp.source_radius > 0.0f && sphere_hit(ray, kp.src, kp.source_radius, tmax, ts));
-                if (sphere_blocked) has_ray = false;
-            }
-            const bool hit = trav_any_shared(sc, has_ray, ray, tmax, &s_stack[threadIdx.x], s_share);
-            if (!active || hit || sphere_blocked) continue;
-            ++my_deposits;
-            float E[Bands<B>::kMax];
-#pragma unroll
-            for (int b = 0; b < Bands<B>::kMax; ++b) E[b] = 1.0f;
-            float sd = 0.0f;
-            for (int a = 0; a < i; ++a) {                                 // F_a -> F_a+1
-                const float2 np = load_np(st, total, a, sf);
-                sd += np.x;
-                apply_segment<B>(E, np.x, load_mat(st, total, a, sf), np.y, kp, sc);
-            }
-            {                                                             // Fi -> Bj
-                float nd = sqrtf(l2) / kp.dist_divisor;
-                sd += nd;
-                apply_segment<B>(E, nd, fmat, fprob, kp, sc);
-            }
-            for (int a = j - 1; a >= 0; --a) {                            // B_a+1 -> B_a
-                const float2 np = load_np(st, total, a, sl);
-                sd += np.x;
-                uint32_t bmat = load_mat(st, total, a, sl);
-                if (a == j - 1) bmat &= 0xFFFFu;                          // Bj is the other connection vertex
-                apply_segment<B>(E, np.x, bmat, np.y, kp, sc);
-            }
-            const int t = i + j, D = kp.mis_depth;
-            const int lo_t = t - D > 0 ? t - D : 0, hi_t = t < D ? t : D;
-            float w = 1.0f / (float)(hi_t - lo_t + 1);
-            if (kp.mis) w = mis_weight(kp, st, total, sf, sl, i, j);
-            float delay = sd / kp.sound_speed;
-            float x = (delay * 1000.f) / 1.0f;
-            float fl = floorf(x);
-            int bin = !(fl > 0.0f) ? 0 : (fl >= (float)(nb - 1) ? nb - 1 : (int)fl);
-            const bool near = bin < W;
-            if (!fixed && near) {
-                atomicMin(&s_lo, bin);
-                atomicMax(&s_hi, bin);
-            }
-#pragma unroll
-            for (int b = 0; b < Bands<B>::kMax; ++b) {
-                if (B == 0 && b >= NB) break;
-                float e = E[b];
-                e = (e < kp.energy_clamp) ? e : kp.energy_clamp;
-                e *= kp.energy_gain;
-                e *= kp.norm;
-                e *= w;
-                if (fixed)
-                    atomicAdd(&fixed[b * nb + bin], (unsigned long long)__double2ll_rn((double)e * kFixedScale));
-                else if (near)
-                    atomicAdd(&s_hist[b * W + bin], e);   // ds_add_f32.  (Summing the equal-bin deposits of a wave first —
-                else                                      // ballot per distinct bin + butterfly per band — measured slower:
-                    atomicAdd(&energy[b * nb + bin], e);  // 2.12 -> 2.47 ms at cfg3; a pair's paths rarely share a bin.)
-            }
-        }
-    }
-    {   // work counters: one atomic per wave
-        unsigned long long* counters = reinterpret_cast<unsigned long long*>(queue_head + kCounterWord);
-        unsigned d = my_deposits, t = my_tests;
-        for (int o = 32; o > 0; o >>= 1) { d += __shfl_down(d, o); t += __shfl_down(t, o); }
-        if (lane == 0) {
-            if (my_segments) atomicAdd(&counters[0], (unsigned long long)my_segments);
-            if (d) atomicAdd(&counters[2], (unsigned long long)d);
-            if (t) atomicAdd(&counters[1], (unsigned long long)t);
-        }
-    }
-    __syncthreads();
-    const int lo = s_lo, hi = s_hi;
-    if (hi < lo) return;
-    const int span = hi - lo + 1;
-    for (int i = threadIdx.x; i < NB * span; i += kBlock) {
-        int b = i / span, bin = lo + (i - b * span);
-        float v = s_hist[b * W + bin];
-        if (v != 0.0f) atomicAdd(&energy[b * nb + bin], v);
-    }
-}
+#define FS_CONNECT_ALL_DIR 0
+#include "fs_connect_all.inc"
+#undef FS_CONNECT_ALL_DIR
+#define FS_CONNECT_ALL_DIR 1
+#include "fs_connect_all.inc"
+#undef FS_CONNECT_ALL_DIR
 
 // deterministic mode: fixed-point histogram -> the fp32 energy buffer (one rounding per bin, after all sums)
 __global__ __launch_bounds__(kBlock) void fixed_to_energy_kernel(const unsigned long long* __restrict__ fixed,
@@ -229,7 +113,7 @@ constexpr int kConnectAhead = 4;
 template <int B>
 void launch_connect_t(const DeviceScene& sc_in, const KParams& kp, const SubpathState& st, float* energy,
                       unsigned long long* fixed, unsigned* queue_head, int pairs_per_wave, float* const* energy_tab,
-                      unsigned long long* const* fixed_tab, hipStream_t s) {
+                      unsigned long long* const* fixed_tab, hipStream_t s, const DirArgs* dir) {
     if (kp.num_local == 0) return;
     DeviceScene sc = sc_in;
     if (pairs_per_wave < 1 || pairs_per_wave > 64) pairs_per_wave = 64;
@@ -246,9 +130,23 @@ void launch_connect_t(const DeviceScene& sc_in, const KParams& kp, const Subpath
         hipLaunchKernelGGL((connect_kernel<B, L, BT, CN>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy,   \
                            fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab);                                \
     } while (0)
+    // a directional source: the EXT pass's shape (run-time band count and lobes) through the directional entry
+    if (dir) {
+        if (B != 0) return launch_connect_t<0>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir);
+        if (batch) {
+            allow_lds(connect_dir_kernel<0, -1, true, false, true>, lds);
+            hipLaunchKernelGGL((connect_dir_kernel<0, -1, true, false, true>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed,
+                               queue_head, pairs_per_wave, energy_tab, fixed_tab, *dir);
+        } else {
+            allow_lds(connect_dir_kernel<0, -1, false, false, true>, lds);
+            hipLaunchKernelGGL((connect_dir_kernel<0, -1, false, false, true>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed,
+                               queue_head, pairs_per_wave, energy_tab, fixed_tab, *dir);
+        }
+        return;
+    }
     // FS_FLAG_DOUBLE_POSITIONS / end-point collision spheres: one instantiation pair with the run-time band count and run-time lobes
     if (kp.dpos || kp.listener_radius > 0.0f || kp.source_radius > 0.0f) {
-        if (B != 0) return launch_connect_t<0>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s);
+        if (B != 0) return launch_connect_t<0>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir);
         if (batch) {
             allow_lds(connect_kernel<0, -1, true, false, true>, lds);
             hipLaunchKernelGGL((connect_kernel<0, -1, true, false, true>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed,
@@ -284,13 +182,18 @@ void launch_connect_t(const DeviceScene& sc_in, const KParams& kp, const Subpath
 
 template <int B>
 void launch_connect_all_t(const DeviceScene& sc_in, const KParams& kp, const SubpathState& st, float* energy,
-                          unsigned long long* fixed, unsigned* queue_head, hipStream_t s) {
+                          unsigned long long* fixed, unsigned* queue_head, hipStream_t s, const DirArgs* dir) {
     if (kp.num_local == 0) return;
     DeviceScene sc = sc_in;
     uint32_t blocks = (kp.num_local + 3) / 4;   // one wave per pair, 4 waves per workgroup
     if (blocks > 4096) blocks = 4096;
     if (!attach_deep(sc, blocks)) return;
     size_t lds = stack_bytes(sc) + sizeof(float) * (size_t)kp.num_bands * (size_t)kp.hist_window + kShareAnyLdsBytes;
+    if (dir) {
+        allow_lds(connect_all_dir_kernel<B>, lds);
+        hipLaunchKernelGGL(connect_all_dir_kernel<B>, dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed, queue_head, *dir);
+        return;
+    }
     allow_lds(connect_all_kernel<B>, lds);
     hipLaunchKernelGGL(connect_all_kernel<B>, dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed, queue_head);
 }
@@ -299,24 +202,24 @@ void launch_connect_all_t(const DeviceScene& sc_in, const KParams& kp, const Sub
 
 void launch_connect(int B, const DeviceScene& sc, const KParams& kp, const SubpathState& st, float* energy,
                     unsigned long long* fixed, unsigned* queue_head, int pairs_per_wave, float* const* energy_tab,
-                    unsigned long long* const* fixed_tab, hipStream_t s) {
+                    unsigned long long* const* fixed_tab, hipStream_t s, const DirArgs* dir) {
     // instantiated for the band counts in use (the reference: 1; BASELINE.json's configurations: 4 and 8); B = 0 reads
     // kp.num_bands at run time
     switch (B) {
-        case 1: launch_connect_t<1>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s); break;
-        case 4: launch_connect_t<4>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s); break;
-        case 8: launch_connect_t<8>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s); break;
-        default: launch_connect_t<0>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s); break;
+        case 1: launch_connect_t<1>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir); break;
+        case 4: launch_connect_t<4>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir); break;
+        case 8: launch_connect_t<8>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir); break;
+        default: launch_connect_t<0>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir); break;
     }
 }
 
 void launch_connect_all(int B, const DeviceScene& sc, const KParams& kp, const SubpathState& st, float* energy,
-                        unsigned long long* fixed, unsigned* queue_head, hipStream_t s) {
+                        unsigned long long* fixed, unsigned* queue_head, hipStream_t s, const DirArgs* dir) {
     switch (B) {
-        case 1: launch_connect_all_t<1>(sc, kp, st, energy, fixed, queue_head, s); break;
-        case 4: launch_connect_all_t<4>(sc, kp, st, energy, fixed, queue_head, s); break;
-        case 8: launch_connect_all_t<8>(sc, kp, st, energy, fixed, queue_head, s); break;
-        default: launch_connect_all_t<0>(sc, kp, st, energy, fixed, queue_head, s); break;
+        case 1: launch_connect_all_t<1>(sc, kp, st, energy, fixed, queue_head, s, dir); break;
+        case 4: launch_connect_all_t<4>(sc, kp, st, energy, fixed, queue_head, s, dir); break;
+        case 8: launch_connect_all_t<8>(sc, kp, st, energy, fixed, queue_head, s, dir); break;
+        default: launch_connect_all_t<0>(sc, kp, st, energy, fixed, queue_head, s, dir); break;
     }
 }
 

@@ -73,6 +73,13 @@ struct Source {
     bool alive = false;
     float pos[3] = {0, 0, 0};
     uint32_t object = FS_NO_OBJECT;    // the actor this source belongs to: its own walks ignore it (fs_source_set_object)
+    // directivity (fs_source_set_orientation / fs_source_set_directivity): unit forward vector and the device table [B][dir_samples]
+    // (null: omnidirectional).  A new table is a new allocation: the one it replaces may still be read by an enqueued frame
+    // (fs_context::retired_tables)
+    float fwd[3] = {1.0f, 0.0f, 0.0f};
+    float* d_dir = nullptr;
+    int32_t dir_samples = 0;
+    fs::Directivity directivity() const { fs::Directivity d; std::memcpy(d.fwd, fwd, sizeof(d.fwd)); d.samples = dir_samples; d.table = d_dir; return d; }
     // Two energy buffers [B][bins], alternating per frame: while the tail stream still reduces /
     // reconstructs frame f from one of them, the compute stream already traces frame f+1 into the other.
     float* d_energy[kEnergyBufs] = {};
@@ -358,6 +365,10 @@ struct fs_context {
     size_t batch_bytes[kBatchSlots] = {};   // bytes of the table the slot's device copy holds (0: none) — same table again: no copy
     std::vector<char> batch_build;
     unsigned batch_frame = 0;
+    // directivity tables replaced or dropped (fs_source_set_directivity): freed once the compute stream has passed the event
+    // recorded at their retirement — every frame that may read one was enqueued on that stream before it
+    struct RetiredTable { float* p; hipEvent_t ev; };
+    std::vector<RetiredTable> retired_tables;
     unsigned long long host_segments = 0;   // walk segments of frames without a plan pass (roulette off), since the last reset
 
     // walk kernel launch shape (variant: FS_WALK_VARIANT in -DFS_EXPERIMENTS builds; coop: FS_WALK_COOP)

@@ -6,6 +6,55 @@ namespace fs {
 namespace {
 
 // ---------------------------------------------------------------------------------------------------
+// source directivity (fs_source_set_directivity, include/frequensee.h): one more factor per band on every deposit of a path,
+// D_b(theta) of the direction w_e the path left the source in.  The factor comes after the clamp of EvaluatePath
+// (e = min(E_b, clamp) * gain * norm [* MIS weight] * D_b): the reference's EvaluatePath stays as it is and the result is
+// linear in the table.  Nothing of the walk changes — no sample, no RNG word, no MIS weight (the pattern is part of the
+// contribution, not of the sampling density).
+// ---------------------------------------------------------------------------------------------------
+// The step with which the source's walk left the source: its first record with a length.  Until a ray hits, the walk stays
+// where it is and records a zero-length segment (walker_apply_hit: the duplicate node of ARTS.cpp:296).  -1: never left.
+__device__ __forceinline__ int emission_step(const SubpathState& st, uint32_t total, uint32_t sf, int records) {
+    for (int j = 0; j < records; ++j)
+        if (load_np(st, total, j, sf).x != 0.0f) return j;
+    return -1;
+}
+// ... and the ray it traced then: the sphere sample walker_next_ray drew for that step (source side, no normal yet), from the
+// same Philox words — the pair's global RNG index and the item's seed word, so the direction does not depend on sharding
+__device__ __forceinline__ void emission_ray(const KParams& kp, uint32_t li, int step, float& wx, float& wy, float& wz) {
+    const uint32_t sid = li / kp.pairs_per_source;
+    const uint32_t pair = kp.pair_begin + (li - sid * kp.pairs_per_source);
+    const uint32_t seed = kp.item_seeds > 0 ? item_seed_lo(kp, sid) : kp.seed_lo;
+    const uint32_t bs = (uint32_t)step << 1;
+    const uint4 r = philox(pair, bs, 0, seed, kp.seed_hi);
+    sample_sphere(pair, bs, r, seed, kp.seed_hi, wx, wy, wz);
+}
+// theta = atan2f(|w x f|, w . f) (well-conditioned near 0 and pi, unlike acosf of the dot); x = theta (K - 1) / pi,
+// k = min((int)x, K - 2), t = x - k.  (A zero-length connection of a walk that never left has no direction: theta = 0.)
+struct DirLookup { const float* row; int K, k; float t; };
+__device__ __forceinline__ DirLookup dir_lookup(const Directivity& d, float wx, float wy, float wz) {
+    DirLookup L;
+    L.row = d.table; L.K = d.samples; L.k = 0; L.t = 0.0f;
+    if (!d.table) return L;
+    const float fx = d.fwd[0], fy = d.fwd[1], fz = d.fwd[2];
+    const float cx = wy * fz - wz * fy, cy = wz * fx - wx * fz, cz = wx * fy - wy * fx;
+    const float sn = sqrtf(cx * cx + cy * cy + cz * cz), cs = wx * fx + wy * fy + wz * fz;
+    float x = atan2f(sn, cs) * (float)(d.samples - 1) / kPi;
+    if (!(x >= 0.0f)) x = 0.0f;
+    L.k = min((int)x, d.samples - 2);
+    L.t = x - (float)L.k;
+    return L;
+}
+// D_b = T[b][k] + t (T[b][k+1] - T[b][k]): a constant table gives that constant exactly.  Plain loads: at most 5.8 KB per
+// source, cache-resident (no LDS: the connect part's occupancy stays as it is)
+__device__ __forceinline__ float dir_gain(const DirLookup& L, int b) {
+    if (!L.row) return 1.0f;
+    const float* r = L.row + (size_t)b * (size_t)L.K + (size_t)L.k;
+    const float t0 = r[0], t1 = r[1];
+    return t0 + L.t * (t1 - t0);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // connect_kernel: ConnectSubpaths + EvaluatePath + clamp/gain + deposit
 // ---------------------------------------------------------------------------------------------------
 // pairs_per_wave < 64: sparse waves for small frames — a wave owns that many pairs (its first lanes), the other
@@ -19,12 +68,13 @@ namespace {
 // walk lie a whole level apart ([step][slot]): one at a time, every segment of a 100-segment path waited for its own miss.
 // (Also measured: the paths of 40 segments or more evaluated by the whole wave, as a sparse wave does for every path — no gain
 // on top of this: 88 -> 92 us at cfg3's size.  With the records ahead the longest path is no longer what the pass waits for.)
-template <int B, int LOBES, bool BATCH, bool COUNT, bool EXT = false, int AHEAD = 1>
+// DIR (connect_dir_kernel only): the source's directivity, `dir` — the pair's own lane weights its deposits by D_b(w_e).
+template <int B, int LOBES, bool BATCH, bool COUNT, bool EXT = false, int AHEAD = 1, bool DIR = false>
 __device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t nblocks, const DeviceScene& sc,
                                              const KParams& kp, const SubpathState& st, float* __restrict__ energy,
                                              unsigned long long* __restrict__ fixed, unsigned* queue_head,
                                              const int pairs_per_wave, float* const* __restrict__ energy_tab,
-                                             unsigned long long* const* __restrict__ fixed_tab) {
+                                             unsigned long long* const* __restrict__ fixed_tab, const DirArgs& dir = DirArgs()) {
     extern __shared__ __attribute__((aligned(16))) int s_dyn[];   // [stack_rows][kBlock] stack | [B][hist_window] histogram
     int* s_stack = s_dyn;
     float* s_hist = reinterpret_cast<float*>(s_dyn + (size_t)sc.stack_rows * kBlock);
@@ -223,6 +273,14 @@ __device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t 
         ++my_deposits;
         eval_alone();
         }
+        DirLookup dl;
+        if (DIR) {   // w_e: the ray the source's walk left by, else (it never left) the connection ray as computed above
+            const Directivity& d = dir.tab ? dir.tab[lc / kp.pairs_per_source] : dir.one;
+            float wx = ux, wy = uy, wz = uz;
+            const int ke = emission_step(st, total, sf, (int)Fm.y);
+            if (ke >= 0) emission_ray(kp, lc, ke, wx, wy, wz);
+            dl = dir_lookup(d, wx, wy, wz);
+        }
         float delay = sd / kp.sound_speed;                            // ARTS.cpp:419
         float x = (delay * 1000.f) / 1.0f;                            // FSAC.h:89, BinSizeMs = 1
         float fl = floorf(x);
@@ -239,6 +297,7 @@ __device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t 
             e = (e < kp.energy_clamp) ? e : kp.energy_clamp;          // FMath::Min ARTS.cpp:410
             e *= kp.energy_gain;                                      // ARTS.cpp:413
             e *= kp.norm;                                             // ARTS.cpp:164-170
+            if (DIR) e *= dir_gain(dl, b);                            // the source's directivity, last
             if (fixed_dst)   // deterministic mode: integer sum of 2^-40 quanta — exact, so order- and shard-independent
                 atomicAdd(&fixed_dst[b * nb + bin], (unsigned long long)__double2ll_rn((double)e * kFixedScale));
             else if (near)

@@ -189,6 +189,18 @@ struct KParams {
 
 constexpr uint32_t kPlanCoopMax = 32768, kPlanCoopMaxUncapped = 1u << 17;   // KParams.plan_coop (fs_dev_walk.hpp: plan_coop_body)
 
+// Source directivity (fs_source_set_directivity): a kernel argument of the directional connect kernels only — KParams,
+// ten times in the fused frame kernel's 4 KB of arguments, does not grow.  table == null: omnidirectional (factor 1).
+struct Directivity {
+    float fwd[3];            // unit forward vector
+    int32_t samples;         // K: samples per band
+    const float* table;      // device [bands][K], or null
+};
+struct DirArgs {
+    Directivity one;         // the frame's source
+    const Directivity* tab;  // batched frame: [sources] descriptors (device, in the batch table), indexed li / pairs_per_source; else null
+};
+
 // legacy forward tracer (UpdateSound) constants and device-side accumulators
 struct SoundKParams {
     uint32_t seed_lo, seed_hi;
@@ -359,10 +371,11 @@ uint32_t walk_stage_slots(const KParams& kp, int begin);
 // pointers), null for one source (`energy` / `fixed` are used)
 void launch_connect(int B, const DeviceScene& sc, const KParams& kp, const SubpathState& st, float* energy,
                     unsigned long long* fixed, unsigned* queue_head, int pairs_per_wave, float* const* energy_tab,
-                    unsigned long long* const* fixed_tab, hipStream_t s);
+                    unsigned long long* const* fixed_tab, hipStream_t s, const DirArgs* dir = nullptr);
 // row f3: every forward prefix x every backward prefix of each pair (one wave per pair), uniform MIS weights
+// dir != nullptr: a directional source (the directional entries, connect_dir_kernel / connect_all_dir_kernel)
 void launch_connect_all(int B, const DeviceScene& sc, const KParams& kp, const SubpathState& st, float* energy,
-                        unsigned long long* fixed, unsigned* queue_head, hipStream_t s);
+                        unsigned long long* fixed, unsigned* queue_head, hipStream_t s, const DirArgs* dir = nullptr);
 void launch_fixed_to_energy(const unsigned long long* fixed, float* energy, int words, hipStream_t s);
 // carrier != nullptr (FS_FLAG_SPECTRAL_IR): row B is the spectral channel from the [B][carrier_stride] carrier set (fs_dev_recon.hpp:
 // reconstruct_spectral_row); the band rows are the same either way

@@ -45,6 +45,10 @@ public:
 
     FVector GetComponentLocation() const { return Location_; }
     void SetComponentLocation(FVector L);
+    // source directivity: the owner's GetForwardVector() before a trace, and per-band gains [bands][samples] over
+    // 0 .. 180 degrees from it (empty: omnidirectional again) — fs_source_set_orientation / fs_source_set_directivity
+    void SetForwardVector(FVector F);
+    void SetDirectivity(const std::vector<float>& Gains, int Samples);
 
     int NumBins() const;      // FrequenSeeAudioComponent.h:137
     int NumSamples() const;   // :138
@@ -235,6 +239,14 @@ inline void FrequenSeeAudioComponent::OnUnregister() { if (SubSys_) SubSys_->UnR
 inline void FrequenSeeAudioComponent::SetComponentLocation(FVector L) {
     Location_ = L;
     if (SubSys_) SubSys_->Check(fs_source_set_position(SubSys_->Ctx_, Handle_, &L.X));
+}
+inline void FrequenSeeAudioComponent::SetForwardVector(FVector F) {
+    SubSys_->Check(fs_source_set_orientation(SubSys_->Ctx_, Handle_, &F.X));
+}
+inline void FrequenSeeAudioComponent::SetDirectivity(const std::vector<float>& Gains, int Samples) {
+    if (Gains.empty()) { SubSys_->Check(fs_source_set_directivity(SubSys_->Ctx_, Handle_, nullptr, 0, 0)); return; }
+    const int Bands = Samples > 0 ? (int)(Gains.size() / (size_t)Samples) : 0;
+    SubSys_->Check(fs_source_set_directivity(SubSys_->Ctx_, Handle_, Gains.data(), Bands, Samples));
 }
 inline int FrequenSeeAudioComponent::NumBins() const { return fs_num_bins(SubSys_->Ctx_); }
 inline int FrequenSeeAudioComponent::NumSamples() const { return fs_num_samples(SubSys_->Ctx_); }

@@ -52,6 +52,7 @@
  *             fs_save_array_to_file fs_load_float_array fs_save_impulse_response
  *             fs_reverb_init fs_reverb_process fs_reverb_release fs_reverb_set_crossfade fs_apply_material_fd
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
+ *             fs_source_set_orientation fs_source_set_directivity
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
  * Environment variables (FS_*) are tuning and diagnostic knobs only; all of them are read ONCE — at fs_context_create, at a
  * scene commit (builder knobs) or at the first launch of a kernel family — never per frame.
@@ -289,6 +290,33 @@ int fs_listener_set_position(fs_context* ctx, const float xyz[3]);
 #define FS_NO_OBJECT 0xFFFFFFFFu
 int fs_source_set_object(fs_context* ctx, fs_source src, uint32_t object_id);
 int fs_listener_set_object(fs_context* ctx, uint32_t object_id);
+
+/* ---- source directivity (EXTENDED): every path is weighted by the direction it left the source in ---------------------
+ * A source has an orientation f (default (1, 0, 0), UE's forward axis; any finite non-zero vector, normalised in fp32 as
+ * f / sqrtf(dot(f, f))) and an optional axisymmetric table T[b][k] of `samples` = K gains per band, sample k at the angle
+ * theta_k = k pi / (K - 1) from f (2 <= K <= FS_MAX_DIRECTIVITY_SAMPLES; bands = the context's band count; every gain
+ * finite and >= 0, absolute: not normalised).  No table (the default, and gains == NULL) = omnidirectional: today's
+ * kernels and results.
+ * The emission direction w_e of a connected path: the unit direction of the sphere sample with which the source's walk
+ * first HIT something (the exact ray it traced; until then a missed ray leaves the walk at the source); for a path whose
+ * walk never left the source, the connection ray's unit direction (from the double end points under
+ * FS_FLAG_DOUBLE_POSITIONS).  All-connections modes: per (i, j) the walk's ray if the prefix F_0..F_i has left the
+ * source, else the direction of the connection F_i -> B_j.
+ * theta = atan2f(|w_e x f|, w_e . f); x = theta (K - 1) / pi, k = min((int)x, K - 2), t = x - k;
+ * D_b = T[b][k] + t (T[b][k+1] - T[b][k]) (a constant table gives that constant exactly).  Every deposit of the path
+ * gets the factor last: e = min(E_b, energy_clamp) * energy_gain * norm [* MIS weight] * D_b (before the fixed-point
+ * conversion of FS_FLAG_DETERMINISTIC).  Applied after the reference's clamp, the weight leaves EvaluatePath untouched and
+ * the result is linear in the table.  Sampling, RNG use and MIS weights do not change (the pattern is part of the
+ * contribution, not of the sampling density); the result does not depend on sharding.
+ * A frame uses the orientation and table in force at its call (also an _async frame whose fs_synchronize comes after a
+ * later set call).  Frames of a source with a table are never held by fs_set_pipelining: held frames drain first and
+ * the frame runs on its own, like FS_FLAG_DOUBLE_POSITIONS frames.  A new source handle starts omnidirectional, facing
+ * (1, 0, 0).  Bad input: FS_ERR_INVALID_ARGUMENT, a bad handle: FS_ERR_BAD_HANDLE; a refused call changes nothing.
+ * Not applied by fs_update_sound or fs_trace_rays. */
+#define FS_MAX_DIRECTIVITY_SAMPLES 181   /* 1 degree steps */
+int fs_source_set_orientation(fs_context* ctx, fs_source src, const float forward[3]);
+int fs_source_set_directivity(fs_context* ctx, fs_source src, const float* gains /* [bands][samples] */, int32_t bands,
+                              int32_t samples);
 
 /* ---- the hot path ------------------------------------------------------------------------------- */
 /* ComputeEnergyResponse() == UpdateSource up to the deposit (ARTS.cpp:128-173): GenerateFullPaths
