@@ -34,6 +34,7 @@ FLAG_MATERIAL_LOBES = 64
 FLAG_ACCUMULATE_ENERGY = 128
 FLAG_DOUBLE_POSITIONS = 256
 FLAG_SPECTRAL_IR = 512   # reconstruct calls: the channel view as per-band noise carriers x band envelopes (include/frequensee.h)
+FLAG_ROOM_PARAMETERS = 1024   # reconstruct calls: also publish each band's room parameters (fs_get_room_parameters)
 NO_OBJECT = 0xFFFFFFFF
 
 # every symbol include/frequensee.h declares (tests check the library exports all of them)
@@ -52,7 +53,7 @@ EXPORTS = [
     "fs_apply_material_fd", "fs_energy_handoff", "fs_scene_update_triangles", "fs_scene_refit", "fs_set_impulse_response",
     "fs_scene_commit_fast", "fs_comm_unique_id", "fs_comm_init", "fs_comm_attach", "fs_comm_detach", "fs_comm_info", "fs_comm_enable_oneshot", "fs_shard_range",
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
-    "fs_set_band_edges", "fs_source_set_orientation", "fs_source_set_directivity",
+    "fs_set_band_edges", "fs_source_set_orientation", "fs_source_set_directivity", "fs_get_room_parameters",
 ]
 MAX_DIRECTIVITY_SAMPLES = 181   # FS_MAX_DIRECTIVITY_SAMPLES: 1 degree steps
 COMM_ID_BYTES = 128
@@ -184,6 +185,11 @@ class PipelineCounters(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
 
 
+class RoomParameters(C.Structure):
+    """fs_room_parameters (include/frequensee.h): one band's record, an array element (no struct_size)"""
+    _fields_ = [(k, C.c_float) for k in ("energy", "onset", "edt", "t20", "t30", "c50", "c80", "d50", "ts")]
+
+
 class FrequenSeeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"frequensee status {code}: {msg}")
@@ -243,6 +249,7 @@ def load():
         "fs_get_impulse_response": (C.c_int, [vp, i32, i32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(i32)]),
         "fs_copy_impulse_response": (C.c_int, [vp, i32, i32, f32p, i32]),
         "fs_get_impulse_response_sequence": (C.c_int, [vp, i32, C.POINTER(C.c_uint64)]),
+        "fs_get_room_parameters": (C.c_int, [vp, i32, C.POINTER(RoomParameters), i32, C.POINTER(C.c_uint64)]),
         "fs_copy_band_impulse_response": (C.c_int, [vp, i32, i32, f32p, i32]),
         "fs_get_energy_buffer": (C.c_int, [vp, i32, f32p, i32]),
         "fs_flush_energy_buffer": (C.c_int, [vp, i32]),

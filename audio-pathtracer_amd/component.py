@@ -299,6 +299,17 @@ class Context:
         self.check(self.lib.fs_get_impulse_response_sequence(self.h, src, C.byref(n)))
         return int(n.value)
 
+    ROOM_DTYPE = np.dtype([(k, np.float32) for k, _ in _capi.RoomParameters._fields_])
+
+    def room_parameters(self, src):
+        """FS_FLAG_ROOM_PARAMETERS (fs_get_room_parameters): (sequence, structured array [bands] of energy, onset, edt, t20, t30,
+        c50, c80, d50, ts) of the front publish; sequence 0 (and an array of NaN) when that publish carries no records"""
+        out = np.full(self.num_bands, np.nan, dtype=self.ROOM_DTYPE)
+        seq = C.c_uint64()
+        self.check(self.lib.fs_get_room_parameters(self.h, int(src), out.ctypes.data_as(C.POINTER(_capi.RoomParameters)),
+                                                   self.num_bands, C.byref(seq)))
+        return int(seq.value), out
+
     def band_impulse_response(self, src, band):
         out = np.empty(self.num_samples, dtype=np.float32)
         self.check(self.lib.fs_copy_band_impulse_response(self.h, src, band, out.ctypes.data, out.shape[0]))
@@ -490,6 +501,10 @@ class FrequenSeeAudioComponent:
 
     def GetBandImpulseResponse(self, band):
         return self._ctx().band_impulse_response(self._src, band)
+
+    def GetRoomParameters(self):
+        """the room parameters published with the front IR (a reconstruct with FS_FLAG_ROOM_PARAMETERS): (sequence, [bands])"""
+        return self._ctx().room_parameters(self._src)
 
     # legacy per-frame forward tracer (TickComponent -> UpdateSound, FSAC.cpp:103-109, 283-306)
     RaycastsPerTick = 1500      # FSAC.h:39

@@ -46,6 +46,36 @@ __global__ __launch_bounds__(kBlock) void reconstruct_batch_kernel(const ReconIt
         reconstruct_body_fast((int)(in_item / cb), (int)(in_item % cb), it.energy, B, nb, num_samples, it.spb, it.ir_bands, it.ir_mono, s_rb, it.host, it.mask);
     publish_arrive(pub.tickets, gridDim.x, pub.host_word, pub.id);
 }
+// FS_FLAG_ROOM_PARAMETERS (instantiations of their own, the overload with the `room` table: the ones above keep their code): behind
+// the count * (B + 1) * cb reconstruct workgroups, count * B more compute the records of (item, band) = the room-parameter
+// workgroup's index / B, % B, into room[item] + band * kRoomFields — before publish_arrive, so the launch's publish covers them.
+// (Placed first in the grid instead, they made the 32-source tick's kernel 95 instead of 75 us and the 128-source one no shorter.)
+template <bool SPECTRAL>
+__global__ __launch_bounds__(kBlock) void reconstruct_batch_kernel(const ReconItem* __restrict__ table, int B, int nb, int num_samples,
+                                                                   uint32_t cb, PublishWord pub, const float* __restrict__ carrier,
+                                                                   float* const* __restrict__ room, float bin_duration) {
+    extern __shared__ __attribute__((aligned(16))) float s_rb[];  // reconstruct_body_fast's layout (room_parameters_band: room_lds_bytes)
+    const uint32_t per_item = (uint32_t)(B + 1) * cb;
+    const uint32_t count = gridDim.x / (per_item + (uint32_t)B), recon_blocks = count * per_item;
+    if (blockIdx.x >= recon_blocks) {
+        const uint32_t r = blockIdx.x - recon_blocks, item = r / (uint32_t)B, band = r - item * (uint32_t)B;
+        room_parameters_band(table[item].energy + (size_t)band * nb, nb, bin_duration, room[item] + (size_t)band * kRoomFields, s_rb);
+    } else {
+        const uint32_t item = blockIdx.x / per_item, in_item = blockIdx.x - item * per_item;
+        const ReconItem it = table[item];
+        if (SPECTRAL && (int)(in_item / cb) == B && it.spectral)
+            reconstruct_spectral_row((int)(in_item % cb), it.energy, B, nb, num_samples, it.spb, it.ir_bands, it.ir_mono, s_rb, it.host, it.mask,
+                                     carrier);
+        else
+            reconstruct_body_fast((int)(in_item / cb), (int)(in_item % cb), it.energy, B, nb, num_samples, it.spb, it.ir_bands, it.ir_mono, s_rb, it.host, it.mask);
+    }
+    publish_arrive(pub.tickets, gridDim.x, pub.host_word, pub.id);
+}
+// ... and on its own (reconstruct_now, the tail stream): one workgroup per band
+__global__ __launch_bounds__(kBlock) void room_parameters_kernel(const float* __restrict__ energy, int nb, float bin_duration, float* out) {
+    extern __shared__ __attribute__((aligned(16))) float s_room[];   // room_lds_bytes
+    room_parameters_band(energy + (size_t)blockIdx.x * nb, nb, bin_duration, out + (size_t)blockIdx.x * kRoomFields, s_room);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // trace_rays_kernel: the engine line trace (tests / tools)
@@ -437,20 +467,36 @@ void launch_reconstruct(const float* energy, int B, int num_bins, int sample_rat
 }
 
 void launch_reconstruct_batch(const ReconItem* table, int count, int B, int num_bins, int num_samples, hipStream_t s, const PublishWord& pub,
-                              const float* carrier) {
+                              const float* carrier, float* const* room, float bin_duration) {
     if (count <= 0) return;
     const uint32_t chunks = (uint32_t)((num_samples + kChunk - 1) / kChunk), cb = (chunks + kBlock - 1) / kBlock;
     const size_t lds = recon_lds_bytes(num_bins);
     bool spectral = false;   // (the table is pinned host memory the host has just written)
     for (int i = 0; i < count && carrier != nullptr; ++i) spectral = spectral || table[i].spectral != 0;
+    if (room) {
+        typedef void (*RoomBatch)(const ReconItem*, int, int, int, uint32_t, PublishWord, const float*, float* const*, float);
+        const RoomBatch k = spectral ? RoomBatch(reconstruct_batch_kernel<true>) : RoomBatch(reconstruct_batch_kernel<false>);
+        const dim3 grid_r((uint32_t)count * ((uint32_t)(B + 1) * cb + (uint32_t)B));
+        allow_lds(k, lds);
+        hipLaunchKernelGGL(k, grid_r, dim3(kBlock), lds, s, table, B, num_bins, num_samples, cb, pub, spectral ? carrier : nullptr, room,
+                           bin_duration);
+        return;
+    }
+    typedef void (*PlainBatch)(const ReconItem*, int, int, int, uint32_t, PublishWord, const float*);   // (the overload without the table)
     const dim3 grid((uint32_t)count * (uint32_t)(B + 1) * cb);
     if (spectral) {
-        allow_lds(reconstruct_batch_kernel<true>, lds);
-        hipLaunchKernelGGL(reconstruct_batch_kernel<true>, grid, dim3(kBlock), lds, s, table, B, num_bins, num_samples, cb, pub, carrier);
+        allow_lds(PlainBatch(reconstruct_batch_kernel<true>), lds);
+        hipLaunchKernelGGL(PlainBatch(reconstruct_batch_kernel<true>), grid, dim3(kBlock), lds, s, table, B, num_bins, num_samples, cb, pub, carrier);
     } else {
-        allow_lds(reconstruct_batch_kernel<false>, lds);
-        hipLaunchKernelGGL(reconstruct_batch_kernel<false>, grid, dim3(kBlock), lds, s, table, B, num_bins, num_samples, cb, pub, nullptr);
+        allow_lds(PlainBatch(reconstruct_batch_kernel<false>), lds);
+        hipLaunchKernelGGL(PlainBatch(reconstruct_batch_kernel<false>), grid, dim3(kBlock), lds, s, table, B, num_bins, num_samples, cb, pub, nullptr);
     }
+}
+
+void launch_room_parameters(const float* energy, int B, int num_bins, float bin_duration, float* host_out, hipStream_t s) {
+    const size_t lds = room_lds_bytes(num_bins);
+    allow_lds(room_parameters_kernel, lds);
+    hipLaunchKernelGGL(room_parameters_kernel, dim3((uint32_t)B), dim3(kBlock), lds, s, energy, num_bins, bin_duration, host_out);
 }
 
 void launch_trace_rays(const DeviceScene& sc_in, const float* o, const float* d, const float* tmax, int N, int any_hit,

@@ -160,6 +160,7 @@ void free_source(fs_context* ctx, Source* s) {
             if (s->h_ir[i]) (void)hipHostFree(s->h_ir[i]);
             if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
         }
+        if (s->h_room.load()) (void)hipHostFree(s->h_room.load());
         if (s->d_ring) (void)hipFree(s->d_ring);
         if (s->d_rev_in) (void)hipFree(s->d_rev_in);
         if (s->d_rev_cur) (void)hipFree(s->d_rev_cur);
@@ -661,6 +662,7 @@ int fs_context_destroy(fs_context* ctx) {
     }
     for (hipEvent_t ev : ctx->tail_batch_ev) if (ev) (void)hipEventDestroy(ev);
     if (ctx->h_recon_tab) (void)hipHostFree(ctx->h_recon_tab);
+    if (ctx->h_room_tab) (void)hipHostFree(ctx->h_room_tab);
     if (ctx->h_pub_word) (void)hipHostFree(ctx->h_pub_word);
     if (ctx->d_pub_tickets) (void)hipFree(ctx->d_pub_tickets);   // (d_slot_masks lives in the same allocation)
     if (ctx->d_comm_stage) (void)hipFree(ctx->d_comm_stage);

@@ -145,6 +145,7 @@ int fs_set_impulse_response(fs_context* ctx, fs_source h, const float* ir, int32
     FS_HIP(ctx, slot_mask_all_dirty(ctx, s, slot, tail));
     FS_HIP(ctx, hipEventRecord(s->ev[slot], tail));
     ctx->dbg.tail_ops += 4 + (uint64_t)ctx->cfg.num_bands; ctx->dbg.pub_event++;
+    s->room_of[slot] = false;   // (an installed IR carries no room parameters)
     s->pub_word[slot] = 0; s->pub_batch[slot] = 0; s->seq_of[slot] = seq; s->enqueued = seq; s->cur_pub_seq = seq; s->dev_ir_word = 0;
     FS_HIP(ctx, hipStreamSynchronize(tail));   // `ir` is the caller's memory
     poll_published(ctx, s);
@@ -217,6 +218,39 @@ int fs_get_impulse_response_sequence(fs_context* ctx, fs_source h, uint64_t* com
     poll_published(ctx, s);   // also notices publishes that completed since the producer's last call
     *completed = s->front.load(std::memory_order_acquire);
     return FS_OK;
+}
+
+// FS_FLAG_ROOM_PARAMETERS: the records of the front publish.  Any thread, no lock, no runtime call beyond poll_published (what
+// fs_get_impulse_response_sequence makes).  The slot's records stay put for the next 7 publishes, like its IR: a copy during which
+// the front moved by 7 or more — or whose slot was taken by a later publish meanwhile — is made again from the new front.
+int fs_get_room_parameters(fs_context* ctx, fs_source h, fs_room_parameters* out, int32_t n, uint64_t* sequence) {
+    if (!ctx || !out || !sequence) return FS_ERR_INVALID_ARGUMENT;
+    Source* s = get_source(ctx, h);
+    if (!s) return FS_ERR_BAD_HANDLE;  // no err string write: may be called from the audio thread
+    if (n != ctx->cfg.num_bands) return FS_ERR_SIZE_MISMATCH;
+    poll_published(ctx, s);
+    uint64_t f = s->front.load(std::memory_order_acquire);
+    for (;;) {
+        const int slot = (int)(f % kIrRing);
+        if (f == 0) { *sequence = 0; return FS_OK; }
+        if (s->seq_of[slot].load(std::memory_order_acquire) == f) {   // (else the slot already belongs to a later publish: look again)
+            const fs_room_parameters* rec = s->h_room.load(std::memory_order_acquire);
+            if (rec == nullptr || !s->room_of[slot].load(std::memory_order_acquire)) { *sequence = 0; return FS_OK; }
+            fs_room_parameters copy[FS_MAX_BANDS];   // (out stays untouched unless this copy is whole)
+            std::memcpy(copy, rec + (size_t)slot * (size_t)n, sizeof(fs_room_parameters) * (size_t)n);
+            poll_published(ctx, s);
+            const uint64_t f2 = s->front.load(std::memory_order_acquire);
+            if (f2 - f < (uint64_t)(kIrRing - 1) && s->seq_of[slot].load(std::memory_order_acquire) == f) {
+                std::memcpy(out, copy, sizeof(fs_room_parameters) * (size_t)n);
+                *sequence = f;
+                return FS_OK;
+            }
+            f = f2;
+            continue;
+        }
+        poll_published(ctx, s);
+        f = s->front.load(std::memory_order_acquire);
+    }
 }
 
 int fs_copy_impulse_response(fs_context* ctx, fs_source h, int32_t channel, float* out, int32_t n) {

@@ -72,11 +72,12 @@ int finish_held_frame(fs_context* ctx, const fs_context::PipeFrame& q, bool may_
             const bool single = !ctx->comm && ctx->cfg.world_size == 1;
             const bool summed = ctx->comm != nullptr && s->reduced && s->red_recorded[it.cur];
             if (may_defer_recon && (single || summed) && ctx->profiling < 2 &&
-                !(it.recon.flags & FS_FLAG_FLUSH_BEFORE_RECONSTRUCT)) {
+                !(it.recon.flags & (FS_FLAG_FLUSH_BEFORE_RECONSTRUCT | FS_FLAG_ROOM_PARAMETERS))) {
                 fs_context::ReconOwed o; o.s = s; o.cur = it.cur; o.fixed = q.fixed; o.p = it.recon; o.reduced = summed;
                 ctx->recon_owed.push_back(o);
             } else {
-                // (what cannot ride in a fused launch: a literal second flush, per-kernel timing, a sharded frame without the library's
+                // (what cannot ride in a fused launch: a literal second flush, room parameters (FS_FLAG_ROOM_PARAMETERS: the fused
+                // kernel has no form that computes them), per-kernel timing, a sharded frame without the library's
                 // collective, more than a table slot's 256 reconstructs at once — on the tail stream beside the next launch, or, when
                 // nothing will be launched behind it, through flush_reconstruct.  Until round 5 a launch had four reconstruct parts and
                 // cfg5's eight sources per frame took this path in steady state.)

@@ -26,9 +26,30 @@ int ir_ring_backpressure(fs_context* ctx, Source* s, int more) {
 
 // publish number `seq` of the source has been enqueued: through the compute stream's host word (word != 0), a tail-stream
 // batch's event (batch != 0) or the slot's own event.  (Readers look at enqueued, then seq_of, then the kind: written in reverse.)
-static void note_publish(fs_context* ctx, Source* s, uint64_t seq, int slot, uint64_t batch = 0, uint64_t word = 0) {
+// room: the publish carries FS_FLAG_ROOM_PARAMETERS records (fs_get_room_parameters)
+static void note_publish(fs_context* ctx, Source* s, uint64_t seq, int slot, uint64_t batch = 0, uint64_t word = 0, bool room = false) {
     if (word) ctx->dbg.pub_word++; else ctx->dbg.pub_event++;
+    s->room_of[slot] = room;
     s->pub_word[slot] = word; s->pub_batch[slot] = batch; s->seq_of[slot] = seq; s->enqueued = seq;
+}
+
+// FS_FLAG_ROOM_PARAMETERS: the source's [kIrRing][B] records and the context's parallel batch table, at the first flagged reconstruct
+// (unflagged work allocates nothing)
+int ensure_room(fs_context* ctx, Source* s) {
+    if (!ctx->h_room_tab)
+        FS_HIP(ctx, hipHostMalloc((void**)&ctx->h_room_tab, sizeof(float*) * fs_context::kReconTabSlots * fs_context::kReconTabItems,
+                                  hipHostMallocDefault));
+    if (!s->h_room.load(std::memory_order_relaxed)) {
+        fs_room_parameters* r = nullptr;
+        const size_t bytes = sizeof(fs_room_parameters) * (size_t)kIrRing * (size_t)ctx->cfg.num_bands;
+        FS_HIP(ctx, hipHostMalloc((void**)&r, bytes, hipHostMallocCoherent));
+        std::memset(r, 0, bytes);
+        s->h_room.store(r, std::memory_order_release);
+    }
+    return FS_OK;
+}
+static float* room_slot(const fs_context* ctx, const Source* s, int slot) {
+    return reinterpret_cast<float*>(s->h_room.load(std::memory_order_relaxed) + (size_t)slot * (size_t)ctx->cfg.num_bands);
 }
 
 // before the COMPUTE stream writes the source's device IR set: whoever reads or writes it on the tail stream goes first
@@ -299,6 +320,8 @@ int reconstruct_now(fs_context* ctx, Source* s, const fs_params* p) {
                                      : (int)std::ceil(ctx->cfg.bin_duration * (float)ctx->cfg.sample_rate);  // FSAC.cpp:324
 
     { const int br = ir_ring_backpressure(ctx, s, 1); if (br) return br; }
+    const bool room = (p->flags & FS_FLAG_ROOM_PARAMETERS) != 0;
+    if (room) { const int rr = ensure_room(ctx, s); if (rr) return rr; }
     TimedFrame tf{};
     bool timed = ctx->profiling >= 2;
     if (timed) {
@@ -337,11 +360,15 @@ int reconstruct_now(fs_context* ctx, Source* s, const fs_params* p) {
     }
     uint64_t seq = s->enqueued + 1;
     int slot = (int)(seq % kIrRing);
+    if (room) {   // the records go into the slot before its event is recorded (the same histogram the reconstruct read)
+        launch_room_parameters(s->energy(), B, ctx->num_bins, ctx->cfg.bin_duration, room_slot(ctx, s, slot), tail);
+        FS_HIP(ctx, hipGetLastError());
+    }
     FS_HIP(ctx, hipMemcpyAsync(s->h_ir[slot], s->d_ir_mono, sizeof(float) * (size_t)ctx->num_samples,
                                hipMemcpyDeviceToHost, tail));
     FS_HIP(ctx, slot_mask_all_dirty(ctx, s, slot, tail));   // (a copy wrote every block: the kernels' zero-block bookkeeping starts over)
     FS_HIP(ctx, hipEventRecord(s->ev[slot], tail));
-    note_publish(ctx, s, seq, slot);
+    note_publish(ctx, s, seq, slot, 0, 0, room);
     s->cur_pub_seq = seq; s->dev_ir_word = 0;
     ctx->dbg.tail_ops += 4;   // the reconstruct kernel, its event, the copy, the publish event
     if (timed) {
@@ -386,10 +413,12 @@ int reconstruct_batch(fs_context* ctx, Source* const* srcs, int count, const fs_
     const int B = ctx->cfg.num_bands;
     const int spb = p->samples_per_bin > 0 ? p->samples_per_bin : (int)std::ceil(ctx->cfg.bin_duration * (float)ctx->cfg.sample_rate);  // FSAC.cpp:324
     hipStream_t tail = on_compute ? ctx->stream : ctx->copy_stream;
+    const bool room = (p->flags & FS_FLAG_ROOM_PARAMETERS) != 0;
     for (int first = 0; first < count; first += fs_context::kReconTabItems) {
         const int n = std::min(count - first, (int)fs_context::kReconTabItems);
         Source* const* g = srcs + first;
         for (int i = 0; i < n; ++i) { const int br = ir_ring_backpressure(ctx, g[i], 1); if (br) return br; }   // (before the mutexes: may wait for the GPU)
+        for (int i = 0; i < n && room; ++i) { const int rr = ensure_room(ctx, g[i]); if (rr) return rr; }
         // the tail stream takes over behind everything the compute stream has enqueued for these frames: one event pair
         bool ordered = true;   // (on_compute: the compute stream is behind its own kernels)
         for (int i = 0; i < n && !on_compute; ++i)
@@ -401,6 +430,7 @@ int reconstruct_batch(fs_context* ctx, Source* const* srcs, int count, const fs_
         unsigned slot_t = 0;
         { const int ar = acquire_recon_tab(ctx, &slot_t); if (ar) return ar; }
         ReconItem* tab = ctx->h_recon_tab + (size_t)slot_t * fs_context::kReconTabItems;
+        float** room_tab = room ? ctx->h_room_tab + (size_t)slot_t * fs_context::kReconTabItems : nullptr;   // (read by the same launch as tab)
         std::vector<Source*> order(g, g + n);
         std::sort(order.begin(), order.end());                 // one locking order for every thread
         std::vector<std::unique_lock<std::mutex>> locks;
@@ -421,8 +451,9 @@ int reconstruct_batch(fs_context* ctx, Source* const* srcs, int count, const fs_
             tab[i].energy = s->energy(); tab[i].ir_bands = s->d_ir_bands; tab[i].ir_mono = s->d_ir_mono; tab[i].host = s->h_ir[slot];
             tab[i].mask = slot_mask_ptr(ctx, s, slot);
             tab[i].spb = spb; tab[i].spectral = carrier != nullptr ? 1 : 0;
+            if (room_tab) room_tab[i] = room_slot(ctx, s, slot);
         }
-        launch_reconstruct_batch(tab, n, B, ctx->num_bins, ctx->num_samples, tail, pub, carrier);
+        launch_reconstruct_batch(tab, n, B, ctx->num_bins, ctx->num_samples, tail, pub, carrier, room_tab, ctx->cfg.bin_duration);
         FS_HIP(ctx, hipGetLastError());
         if (on_compute) {
             ctx->pub_issued = pub.id;
@@ -438,7 +469,7 @@ int reconstruct_batch(fs_context* ctx, Source* const* srcs, int count, const fs_
             s->rec_recorded[s->cur] = true; s->rec_batch[s->cur] = batch; s->rec_on_compute[s->cur] = on_compute;
             s->last_rec = s->cur; s->ir_gen++;
             const uint64_t seq = s->enqueued + 1;
-            note_publish(ctx, s, seq, (int)(seq % kIrRing), batch, pub.id);
+            note_publish(ctx, s, seq, (int)(seq % kIrRing), batch, pub.id, room);
             if (on_compute) {
                 s->cur_pub_seq = 0; s->dev_ir_word = pub.id;
                 if (s->d_ring) FS_HIP(ctx, hipEventRecord(s->ev_rec[s->cur], ctx->stream));   // fs_reverb_process reads d_ir_mono behind this

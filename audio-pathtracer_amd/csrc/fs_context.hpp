@@ -131,6 +131,10 @@ struct Source {
     std::atomic<uint64_t> seq_of[kIrRing] = {};   // (atomics: fs_get_impulse_response_sequence may look from another thread)
     std::atomic<uint64_t> enqueued{0};            // publishes enqueued so far
     std::atomic<uint64_t> front{0};    // newest COMPLETED publish (0 = none yet)
+    // FS_FLAG_ROOM_PARAMETERS: the records of ring slot k are h_room[k * B .. (k + 1) * B) (pinned, allocated at the source's first
+    // flagged reconstruct — ensure_room); room_of[k]: the publish in slot k carries them (noted with the slot's other notes)
+    std::atomic<fs_room_parameters*> h_room{nullptr};
+    std::atomic<bool> room_of[kIrRing] = {};
     // reverb (row f2): history rings [2][kReverbRing], staging buffers, write head
     float* d_ring = nullptr; float* d_rev_in = nullptr; float* d_rev_cur = nullptr; float* d_rev_out = nullptr;
     unsigned rev_head = 0; int rev_frame = 0;
@@ -256,6 +260,7 @@ struct fs_context {
     std::atomic<uint64_t> tail_batch_newest{0}, tail_batch_done{0};
     static constexpr int kReconTabSlots = 8, kReconTabItems = 256;
     ReconItem* h_recon_tab = nullptr;                  // pinned host: [kReconTabSlots][kReconTabItems], read by the batch kernel in place
+    float** h_room_tab = nullptr;                      // ... and the parallel table of FS_FLAG_ROOM_PARAMETERS launches (allocated at the first)
     uint64_t recon_tab_batch[kReconTabSlots] = {};     // the tail-stream batch that last read slot k, or ...
     uint64_t recon_tab_word[kReconTabSlots] = {};      // ... the compute-stream launch (publish word id) that did
     unsigned recon_tab_next = 0;
@@ -498,6 +503,7 @@ int reconstruct_batch(fs_context* ctx, Source* const* srcs, int count, const fs_
 int ir_ring_backpressure(fs_context* ctx, Source* s, int more);   // the IR ring's throttle before `more` publishes (may block; not under ir_mu)
 int ir_ring_backpressure_for(fs_context* ctx, Source* s);
 hipError_t tail_waits_for_compute_ir(fs_context* ctx, Source* s);   // before the tail stream writes the source's device IR set
+int ensure_room(fs_context* ctx, Source* s);   // FS_FLAG_ROOM_PARAMETERS: the source's record ring (and the context's batch table)
 
 // ---- fs_capi_comm.cpp ---------------------------------------------------------------------------------------------
 struct RcclApi {

@@ -337,5 +337,167 @@ __device__ __forceinline__ void reconstruct_spectral_row(const int chunk_block, 
     recon_store(base, num_samples, s_stage, out, to_host, host_out);
 }
 
+// FS_FLAG_ROOM_PARAMETERS: the room parameters of one band of a histogram, one workgroup (definitions: DESIGN.md section 8, "Room
+// parameters"; include/frequensee.h fs_room_parameters).  Everything in double, rounded to float once.  The row is read once into
+// LDS; thread t owns the contiguous bins [t per, (t + 1) per).  Every sum is a chunk sum in bin order followed by a fixed-order
+// tree over the threads (room_reduce), so the same row gives the same bits on every run and every route.  The Schroeder sum
+// S[k] = R_t + (the chunk's own suffix), R_t = the exclusive suffix scan of the chunk sums; each pass that needs L[k] walks its
+// chunk backwards and recomputes S[k] with the same operations (no [num_bins] doubles in LDS).
+// LDS: s_e [num_bins] floats | s_d [kRoomRows][kBlock] doubles + one broadcast slot (room_lds_bytes).  Thread 0 writes the record
+// `out` (kRoomFields floats of pinned host memory) with system-scope stores: the launch may publish right behind it.
+template <int NV, typename Op>
+__device__ __forceinline__ void room_reduce(double* s_d, Op op) {   // rows 0 .. NV-1 of s_d: after the call s_d[v * kBlock] = row v reduced
+    for (int stride = kBlock / 2; stride > 0; stride >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < stride)
+#pragma unroll
+            for (int v = 0; v < NV; ++v) s_d[v * kBlock + threadIdx.x] = op(s_d[v * kBlock + threadIdx.x], s_d[v * kBlock + threadIdx.x + stride]);
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ void room_parameters_band(const float* __restrict__ row, int nb, float bin_duration, float* out, float* s_lds) {
+    float* s_e = s_lds;
+    double* s_d = reinterpret_cast<double*>(s_lds + ((nb + 1) & ~1));
+    double* s_bc = s_d + kRoomRows * kBlock;                  // broadcast slot: S[k0]
+    const int t = (int)threadIdx.x;
+    for (int k = t; k < nb; k += kBlock) s_e[k] = row[k];
+    __syncthreads();
+    const int per = (nb + kBlock - 1) / kBlock;
+    const int k_lo = min(t * per, nb), k_hi = min(k_lo + per, nb);
+    // the energy, the peak, the validity
+    double csum = 0.0;
+    float cmax = 0.0f;
+    bool bad = false, pos = false;
+    for (int k = k_lo; k < k_hi; ++k) {
+        const float e = s_e[k];
+        bad = bad || !(e >= 0.0f) || e == INFINITY;              // negative, NaN or infinite
+        pos = pos || e > 0.0f;
+        cmax = fmaxf(cmax, e);
+        csum += (double)e;
+    }
+    s_d[t] = csum;
+    s_d[kBlock + t] = (double)cmax;
+    room_reduce<1>(s_d, [](double a, double b) { return a + b; });
+    const double energy = s_d[0];
+    __syncthreads();
+    room_reduce<1>(s_d + kBlock, [](double a, double b) { return a > b ? a : b; });
+    const double pk = s_d[kBlock];
+    const bool invalid = __syncthreads_or(bad ? 1 : 0) != 0 || __syncthreads_or(pos ? 1 : 0) == 0;
+    if (invalid) {   // (uniform)
+        if (t == 0) {
+            store_sys(out, (float)energy);
+            for (int f = 1; f < kRoomFields; ++f) store_sys(out + f, __int_as_float(0x7FC00000));
+        }
+        return;
+    }
+    // the onset: the first bin within 20 dB of the peak (a min-index reduction)
+    const double thr = pk / 100.0;
+    int first = nb;
+    for (int k = k_lo; k < k_hi && first == nb; ++k) if ((double)s_e[k] >= thr) first = k;
+    s_d[t] = (double)first;
+    room_reduce<1>(s_d, [](double a, double b) { return a < b ? a : b; });
+    const int k0 = (int)s_d[0];
+    __syncthreads();
+    // R_t: the exclusive suffix scan of the chunk sums (Hillis-Steele over two rows of s_d)
+    s_d[t] = csum;
+    double* src = s_d;
+    double* dst = s_d + kBlock;
+    for (int d = 1; d < kBlock; d <<= 1) {
+        __syncthreads();
+        dst[t] = t + d < kBlock ? src[t] + src[t + d] : src[t];
+        double* x = src; src = dst; dst = x;
+    }
+    __syncthreads();
+    const double R = t + 1 < kBlock ? src[t + 1] : 0.0;
+    __syncthreads();
+    // S[k0] (by the thread that owns k0)
+    if (k0 >= k_lo && k0 < k_hi) {
+        double inner = 0.0;
+        for (int k = k_hi - 1; k >= k0; --k) inner += (double)s_e[k];
+        *s_bc = R + inner;
+    }
+    __syncthreads();
+    const double S0 = *s_bc;
+    const double dt = (double)bin_duration;
+    const double lo[3] = {-10.0, -25.0, -35.0}, hi[3] = {0.0, -5.0, -5.0};   // edt, t20, t30
+    // pass A: fit points (count, sum t, sum L), "the decay leaves the range", early / late energy, sum t E
+    double n[3] = {0.0, 0.0, 0.0}, st[3] = {0.0, 0.0, 0.0}, sl[3] = {0.0, 0.0, 0.0};
+    bool below[3] = {false, false, false};
+    double e50 = 0.0, l50 = 0.0, e80 = 0.0, l80 = 0.0, te = 0.0;
+    {
+        double inner = 0.0;
+        for (int k = k_hi - 1; k >= k_lo && k >= k0; --k) {
+            const double e = (double)s_e[k];
+            inner += e;
+            const double S = R + inner;
+            const double L = S > 0.0 ? 10.0 * log10(S / S0) : -INFINITY;
+            const double tk = (double)(k - k0) * dt;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                if (L >= lo[r] && L <= hi[r]) { n[r] += 1.0; st[r] += tk; sl[r] += L; }
+                below[r] = below[r] || L < lo[r];
+            }
+            if (tk < 0.050) e50 += e; else l50 += e;
+            if (tk < 0.080) e80 += e; else l80 += e;
+            te += tk * e;
+        }
+    }
+    {
+        const double v[kRoomRows] = {n[0], n[1], n[2], st[0], st[1], st[2], sl[0], sl[1], sl[2], e50, l50, e80, l80, te};
+#pragma unroll
+        for (int i = 0; i < kRoomRows; ++i) s_d[i * kBlock + t] = v[i];
+    }
+    room_reduce<kRoomRows>(s_d, [](double a, double b) { return a + b; });
+    double sum[kRoomRows];
+#pragma unroll
+    for (int i = 0; i < kRoomRows; ++i) sum[i] = s_d[i * kBlock];
+    bool leaves[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) leaves[r] = __syncthreads_or(below[r] ? 1 : 0) != 0;   // (also the barrier before s_d is rewritten)
+    double tbar[3], lbar[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { tbar[r] = sum[3 + r] / sum[r]; lbar[r] = sum[6 + r] / sum[r]; }
+    // pass B: the centred sums of the three fits
+    double sxy[3] = {0.0, 0.0, 0.0}, sxx[3] = {0.0, 0.0, 0.0};
+    {
+        double inner = 0.0;
+        for (int k = k_hi - 1; k >= k_lo && k >= k0; --k) {
+            inner += (double)s_e[k];
+            const double S = R + inner;
+            const double L = S > 0.0 ? 10.0 * log10(S / S0) : -INFINITY;
+            const double tk = (double)(k - k0) * dt;
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                if (L >= lo[r] && L <= hi[r]) {
+                    const double a = tk - tbar[r], b = L - lbar[r];
+                    sxy[r] += a * b;
+                    sxx[r] += a * a;
+                }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { s_d[r * kBlock + t] = sxy[r]; s_d[(3 + r) * kBlock + t] = sxx[r]; }
+    room_reduce<6>(s_d, [](double a, double b) { return a + b; });
+    if (t == 0) {
+        const float qnan = __int_as_float(0x7FC00000);
+        float T[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double m = s_d[r * kBlock] / s_d[(3 + r) * kBlock];
+            T[r] = (sum[r] < 2.0 || !leaves[r] || !(m < 0.0)) ? qnan : (float)(-60.0 / m);
+        }
+        const double e50s = sum[9], l50s = sum[10], e80s = sum[11], l80s = sum[12];
+        store_sys(out + 0, (float)energy);
+        store_sys(out + 1, (float)((double)k0 * dt));
+        store_sys(out + 2, T[0]);
+        store_sys(out + 3, T[1]);
+        store_sys(out + 4, T[2]);
+        store_sys(out + 5, l50s > 0.0 ? (float)(10.0 * log10(e50s / l50s)) : INFINITY);
+        store_sys(out + 6, l80s > 0.0 ? (float)(10.0 * log10(e80s / l80s)) : INFINITY);
+        store_sys(out + 7, (float)(e50s / (e50s + l50s)));
+        store_sys(out + 8, (float)(sum[13] / (e50s + l50s)));
+    }
+}
+
 }  // namespace
 }  // namespace fs

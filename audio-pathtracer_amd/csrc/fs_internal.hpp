@@ -390,8 +390,22 @@ void launch_reconstruct(const float* energy, int B, int num_bins, int sample_rat
 struct ReconItem { const float* energy; float* ir_bands; float* ir_mono; float* host; uint32_t* mask; int32_t spb; int32_t spectral; };
 // pub.tickets != nullptr: the launch announces its own completion in the context's pinned host word (publish_arrive)
 // carrier: the context's carrier set (FS_FLAG_SPECTRAL_IR) for the items marked spectral (nullptr: none is)
+// room != nullptr (FS_FLAG_ROOM_PARAMETERS): room[i] = item i's [B] fs_room_parameters records in its pinned host ring slot, a table
+// parallel to `table` in pinned host memory; the launch gets count * B more workgroups that compute and write them before it publishes
 void launch_reconstruct_batch(const ReconItem* table, int count, int B, int num_bins, int num_samples, hipStream_t s, const PublishWord& pub = PublishWord(),
-                              const float* carrier = nullptr);
+                              const float* carrier = nullptr, float* const* room = nullptr, float bin_duration = 0.0f);
+// FS_FLAG_ROOM_PARAMETERS on its own (the tail stream's reconstruct_now): the [B] records of the [B][num_bins] histogram into host_out
+void launch_room_parameters(const float* energy, int B, int num_bins, float bin_duration, float* host_out, hipStream_t s);
+// one record: the fields of fs_room_parameters; LDS of a workgroup that computes one (fs_dev_recon.hpp: room_parameters_band):
+// the band row [num_bins] floats | kRoomRows rows of kBlock doubles + one — never more than recon_lds_bytes(num_bins)
+constexpr int kRoomFields = 9;
+static_assert(sizeof(fs_room_parameters) == sizeof(float) * kRoomFields, "fs_room_parameters: nine floats");
+constexpr int kRoomRows = 14;
+constexpr size_t room_lds_bytes(int num_bins) {
+    return sizeof(float) * (((size_t)num_bins + 1) & ~(size_t)1) + sizeof(double) * ((size_t)kRoomRows * kBlock + 1);
+}
+static_assert(room_lds_bytes(1) <= recon_lds_bytes(1) && room_lds_bytes(2) <= recon_lds_bytes(2),
+              "the room-parameter workgroups of a batch run with the reconstruct's LDS");
 void launch_trace_rays(const DeviceScene& sc, const float* o, const float* d, const float* tmax, int N, int any_hit,
                        int32_t* hit, float* t, int32_t* tri, float* normal, hipStream_t s);
 // rays_per_wave < 64: sparse waves whose other lanes help with every closest-hit query; 64 = one ray per lane

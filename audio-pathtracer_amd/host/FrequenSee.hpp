@@ -67,6 +67,9 @@ public:
     void SetImpulseResponse(const std::vector<float>& IR);
     // GenerateDummyImpulseResponse (.cpp:408-452) as it ends up: a delta at samples 0 and N-1
     std::vector<float> GenerateDummyImpulseResponse();
+    // the room parameters published with the front IR by a reconstruct with FS_FLAG_ROOM_PARAMETERS (one record per band; empty and
+    // *Sequence = 0 when that publish carries none) — fs_get_room_parameters, lock-free
+    std::vector<fs_room_parameters> GetRoomParameters(uint64_t* Sequence = nullptr) const;
 
     bool bApplyReverb = true;   // .h:60
 
@@ -294,6 +297,14 @@ inline std::vector<float> FrequenSeeAudioComponent::GenerateDummyImpulseResponse
     if (!IR.empty()) { IR.front() = 1.0f; IR.back() = 1.0f; }
     SetImpulseResponse(IR);
     return IR;
+}
+inline std::vector<fs_room_parameters> FrequenSeeAudioComponent::GetRoomParameters(uint64_t* Sequence) const {
+    std::vector<fs_room_parameters> v((size_t)SubSys_->NumBands());
+    uint64_t seq = 0;
+    SubSys_->Check(fs_get_room_parameters(SubSys_->Ctx_, Handle_, v.data(), (int32_t)v.size(), &seq));
+    if (Sequence) *Sequence = seq;
+    if (seq == 0) v.clear();
+    return v;
 }
 inline void FrequenSeeAudioComponent::SaveImpulseResponse(const std::string& Path, int Channel) const {
     SubSys_->Check(fs_save_impulse_response(SubSys_->Ctx_, Handle_, Channel, Path.c_str()));

@@ -52,7 +52,7 @@
  *             fs_save_array_to_file fs_load_float_array fs_save_impulse_response
  *             fs_reverb_init fs_reverb_process fs_reverb_release fs_reverb_set_crossfade fs_apply_material_fd
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
- *             fs_source_set_orientation fs_source_set_directivity
+ *             fs_source_set_orientation fs_source_set_directivity fs_get_room_parameters
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
  * Environment variables (FS_*) are tuning and diagnostic knobs only; all of them are read ONCE — at fs_context_create, at a
  * scene commit (builder knobs) or at the first launch of a kernel family — never per frame.
@@ -140,6 +140,11 @@ enum {
                                              * fs_set_band_edges, by default octaves centred at 125, 250, ... Hz (edges 125 * 2^(b - 0.5)).
                                              * Every consumer of the channel view (ring, reverb, export) gets it.  Rejected when the
                                              * edges do not fit under sample_rate / 2.  The carriers are built once per context. */
+#define FS_FLAG_ROOM_PARAMETERS 1024u      /* read by the RECONSTRUCT calls (fs_reconstruct_impulse_response[_async], _batch_async,
+                                             * fs_update_sources): the launch that reconstructs and publishes the IR also computes the
+                                             * room parameters of each band's histogram (fs_room_parameters) and publishes them under the
+                                             * same publish number — fs_get_room_parameters.  Such a reconstruct never rides in a fused
+                                             * launch of held frames (fs_set_pipelining): it runs on a kernel of its own. */
 #define FS_FLAG_DETERMINISTIC 8u            /* deposits are summed as 64-bit integers of 2^-40 energy quanta: the
                                              * histogram no longer depends on the order of the atomics, so it is bit-identical
                                              * from run to run and for every split of the pairs over GPUs (sum-reduce the u64
@@ -457,7 +462,8 @@ int fs_set_band_edges(fs_context* ctx, const float* edges_hz, int32_t count);
  * the batched reconstruct + fs_synchronize, with the reconstructs riding on the compute stream (nothing else to overlap
  * with when the caller waits); a depth = 0 frame whose records overflowed is traced again like fs_compute_energy_response
  * — the impulse responses (and sequence numbers) such a failed attempt published meanwhile are PROVISIONAL: the retry publishes
- * the complete ones behind them before the call returns (a concurrent reader may see one for a few hundred microseconds). */
+ * the complete ones behind them before the call returns (a concurrent reader may see one for a few hundred microseconds).  So are
+ * the FS_FLAG_ROOM_PARAMETERS records published with them (fs_get_room_parameters). */
 int fs_update_sources(fs_context* ctx, const fs_source* sources, int32_t count, const fs_params* params);
 
 /* GetImpulseResponse() (FSAC.h:113): pointer to the PUBLISHED [num_samples] channel buffer — a slot of the source's ring of 8
@@ -475,6 +481,22 @@ int fs_copy_impulse_response(fs_context* ctx, fs_source src, int32_t channel, fl
  * copying the buffer knows that the copy is whole (the pointer stays valid for 7 publishes), and the reverb callback can
  * keep the IR's spectrum while the number stands still instead of transforming the IR every callback (RVB.cpp:188). */
 int fs_get_impulse_response_sequence(fs_context* ctx, fs_source src, uint64_t* completed);
+/* FS_FLAG_ROOM_PARAMETERS: per band b, from the histogram E[k] the reconstruct read (fs_get_energy_buffer of that frame; N =
+ * fs_num_bins, dt = (double) bin_duration), in double, each field rounded to float once ("Room parameters"):
+ *   energy = sum_k E[k].  A band with a negative or non-finite bin, or no bin > 0, has every other field NaN.
+ *   onset  = k0 dt, k0 = the first k with E[k] >= max E / 100 (20 dB below the peak); t_k = (k - k0) dt for k >= k0.
+ *   edt, t20, t30: -60 / m, m = the least-squares slope (dB/s) of L[k] = 10 log10(S[k] / S[k0]), S[k] = sum_{j >= k} E[j], over the
+ *            k >= k0 with L[k] in [-10, 0], [-25, -5], [-35, -5] dB; NaN with fewer than 2 such points, when no L[k] falls below
+ *            the range (the histogram ends first) or when m >= 0.
+ *   c50, c80 = 10 log10(early / late) dB, early = sum of E[k >= k0] with t_k < 50 (80) ms, late = the rest from k0 on; +inf when
+ *            late is 0.  d50 = early / (early + late) at 50 ms.  ts = sum t_k E[k] / sum E[k] over k >= k0, in seconds.
+ * The last bin collects every later arrival and is taken as it is.  An array element: no struct_size. */
+typedef struct fs_room_parameters { float energy, onset, edt, t20, t30, c50, c80, d50, ts; } fs_room_parameters;   /* 36 bytes */
+/* The records of the FRONT publish (the one fs_get_impulse_response_sequence reports), n == num_bands of them: copied into out and
+ * *sequence = that publish's number.  A front publish without records (an unflagged reconstruct, fs_set_impulse_response, none
+ * yet) gives *sequence = 0 and leaves out untouched.  Any thread, no lock, no runtime call beyond what
+ * fs_get_impulse_response_sequence makes; the copy is whole (it is made again if the front moved by 7 or more meanwhile). */
+int fs_get_room_parameters(fs_context* ctx, fs_source src, fs_room_parameters* out, int32_t n, uint64_t* sequence);
 int fs_copy_band_impulse_response(fs_context* ctx, fs_source src, int32_t band, float* out, int32_t n);
 /* GetImpulseResponse() returns a MUTABLE reference in the reference (FSAC.h:113): consumers may install an IR of their
  * own (the authors' convolver checks used synthetic and downloaded IRs: GenerateDummyImpulseResponse FSAC.cpp:408-452,
