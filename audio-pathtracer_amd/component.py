@@ -367,6 +367,31 @@ class Context:
                                               _capi.REVERB_LITERAL_TAIL if literal_tail else 0))
         return out
 
+    def reverb_process_batch(self, sources, blocks, apply=None, literal_tail=False, want_out=True, want_mix=False):
+        """the callbacks of several sources as one set of launches (include/frequensee.h fs_reverb_process_batch):
+        blocks [count][frame_size * 2] -> out [count][frame_size * 2] (want_out), mix [frame_size * 2] (want_mix: the fp32 sum of
+        the outputs in list order), or the pair (out, mix) when both are asked for"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        count = int(srcs.shape[0])
+        a = np.ascontiguousarray(blocks, dtype=np.float32).reshape(count, -1) if count else np.zeros((0, 0), np.float32)
+        frames = getattr(self, "_rev_frame", {})
+        if count and int(srcs[0]) in frames and a.shape[1] != 2 * frames[int(srcs[0])]:
+            raise ValueError("every audio block must hold frame_size * 2 interleaved samples")
+        on = None
+        if apply is not None:
+            on = np.ascontiguousarray([1 if x else 0 for x in apply], dtype=np.int32)
+            if on.shape[0] != count:
+                raise ValueError("apply must have one entry per source")
+        out = np.empty_like(a) if want_out else None
+        mix = np.empty(a.shape[1], np.float32) if want_mix else None
+        self.check(self.lib.fs_reverb_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data,
+                                                    out.ctypes.data if want_out else None, on.ctypes.data if on is not None else None,
+                                                    _capi.REVERB_LITERAL_TAIL if literal_tail else 0,
+                                                    mix.ctypes.data if want_mix else None))
+        if want_out and want_mix:
+            return out, mix
+        return out if want_out else mix
+
     def reverb_release(self, src):
         self.check(self.lib.fs_reverb_release(self.h, src))
 
@@ -688,6 +713,12 @@ class FrequenSeeAudioReverbPlugin:
     def ProcessSourceAudio(self, component: FrequenSeeAudioComponent, AudioBuffer, literal_tail=False):
         return self.ctx.reverb_process(component._src, AudioBuffer, apply_reverb=component.bApplyReverb,
                                        literal_tail=literal_tail)
+
+    def ProcessSourcesAudio(self, components, buffers, literal_tail=False, want_out=True, want_mix=False):
+        """the mixer's loop over ProcessSourceAudio (RVB.cpp:118-170) as one call: buffers[i] is components[i]'s block; each
+        component's bApplyReverb is honoured.  Returns what Context.reverb_process_batch does."""
+        return self.ctx.reverb_process_batch([c._src for c in components], buffers, apply=[c.bApplyReverb for c in components],
+                                             literal_tail=literal_tail, want_out=want_out, want_mix=want_mix)
 
     def SetCrossfade(self, component: FrequenSeeAudioComponent, samples):
         """not in the reference: fade each new impulse response in over `samples` output samples (0: abrupt switch)"""

@@ -317,6 +317,168 @@ int fs_reverb_process(fs_context* ctx, fs_source h, const float* in, float* out,
     return FS_OK;
 }
 
+// fs_reverb_process_batch: the staging of one call (fs_context::h_rev_stage / d_rev_stage), every block 256-byte aligned
+extern "C++" {
+namespace {
+struct RevStageLayout {
+    size_t items, lists, in, up_bytes;      // host and device, the same offsets: what goes up in one copy
+    size_t h_out, h_mix, host_bytes;        // host: what comes back
+    size_t d_cur, d_out, d_mix, dev_bytes;  // device: out | mix adjacent, one copy back
+};
+size_t rev_align(size_t b) { return (b + 255) & ~(size_t)255; }
+RevStageLayout rev_stage_layout(int count, int frame) {
+    const size_t rows = sizeof(float) * 2 * (size_t)frame * (size_t)count, row = sizeof(float) * 2 * (size_t)frame;
+    RevStageLayout l;
+    l.items = 0;
+    l.lists = rev_align(sizeof(ReverbItem) * (size_t)count);
+    l.in = l.lists + rev_align(sizeof(int) * 3 * (size_t)count);
+    l.up_bytes = l.in + rows;
+    l.h_out = rev_align(l.up_bytes);
+    l.h_mix = l.h_out + rows;   // (adjacent to out: rows is a multiple of 8 bytes)
+    l.host_bytes = l.h_mix + row;
+    l.d_cur = rev_align(l.up_bytes);
+    l.d_out = l.d_cur + rev_align(rows);
+    l.d_mix = l.d_out + rows;
+    l.dev_bytes = l.d_mix + row;
+    return l;
+}
+}  // namespace
+}  // extern "C++"
+
+int fs_reverb_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in, float* out,
+                            const int32_t* apply_reverb, uint32_t flags, float* mix) {
+    if (!ctx || !sources || !in || (!out && !mix)) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    if (count < 1 || count > FS_MAX_REVERB_BATCH)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_REVERB_BATCH)");
+    // Everything is validated before the first state change or enqueue: a refused call changes nothing.
+    std::vector<Source*> srcs((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        Source* s = srcs[(size_t)i] = get_source(ctx, sources[i]);
+        if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+        if (!s->d_ring) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init has not been called for this source");
+        if (s->rev_frame != srcs[0]->rev_frame) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size");
+        if ((!apply_reverb || apply_reverb[i]) && s->fade_len > 0 && (!s->d_fade_from || !s->d_fade_to))
+            return ctx->fail(FS_ERR_OUT_OF_MEMORY, "the crossfade's impulse-response buffers are missing: call fs_reverb_init again");
+    }
+    std::vector<int32_t> order((size_t)count);   // rows by ascending Source*: the one locking order of every thread (fs_capi_publish.cpp)
+    for (int32_t i = 0; i < count; ++i) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return srcs[(size_t)a] < srcs[(size_t)b]; });
+    for (int32_t k = 1; k < count; ++k)
+        if (srcs[(size_t)order[(size_t)k]] == srcs[(size_t)order[(size_t)k - 1]])
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a source appears twice in the batch");
+    const int frame = srcs[0]->rev_frame;
+    const size_t row = 2 * (size_t)frame;   // floats
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    hipStream_t rs = ctx->rev_stream;
+    const RevStageLayout l = rev_stage_layout(count, frame);
+    if (l.host_bytes > ctx->rev_stage_host || l.dev_bytes > ctx->rev_stage_dev) {   // first call of this size (every call ends synchronised: nothing reads the old one)
+        if (ctx->h_rev_stage) (void)hipHostFree(ctx->h_rev_stage);
+        if (ctx->d_rev_stage) (void)hipFree(ctx->d_rev_stage);
+        ctx->h_rev_stage = ctx->d_rev_stage = nullptr; ctx->rev_stage_host = ctx->rev_stage_dev = 0;
+        FS_HIP(ctx, hipHostMalloc((void**)&ctx->h_rev_stage, l.host_bytes, hipHostMallocDefault));
+        ctx->rev_stage_host = l.host_bytes;
+        FS_HIP(ctx, hipMalloc((void**)&ctx->d_rev_stage, l.dev_bytes));
+        ctx->rev_stage_dev = l.dev_bytes;
+    }
+    char* hs = ctx->h_rev_stage; char* ds = ctx->d_rev_stage;
+    ReverbItem* items = (ReverbItem*)(hs + l.items);
+    int* plain = (int*)(hs + l.lists); int* fade = plain + count; int* take = fade + count;
+    int n_plain = 0, n_fade = 0, n_take = 0;
+    float* h_in = (float*)(hs + l.in);
+    for (int32_t i = 0; i < count; ++i)   // (a bypassed row goes up only for the mix)
+        if (mix || !apply_reverb || apply_reverb[i])
+            std::memcpy(h_in + (size_t)i * row, in + (size_t)i * row, sizeof(float) * row);
+    const int literal = (flags & FS_REVERB_LITERAL_TAIL) ? 1 : 0;
+    {
+        // Per source what fs_reverb_process does under ir_mu, in list order; the locks of all convolved sources are held while the
+        // work is enqueued (a reconstruct that found one free would not wait for a read this call has yet to record), not longer.
+        std::vector<std::unique_lock<std::mutex>> locks;
+        locks.reserve((size_t)count);
+        for (int32_t i : order)
+            if (!apply_reverb || apply_reverb[i]) locks.emplace_back(srcs[(size_t)i]->ir_mu);
+        for (int32_t i = 0; i < count; ++i) {
+            Source* s = srcs[(size_t)i];
+            ReverbItem& it = items[i];
+            std::memset(&it, 0, sizeof(it));
+            if (apply_reverb && !apply_reverb[i]) continue;   // the bypass touches no state
+            it.apply = 1;
+            const bool xfade = s->fade_len > 0;
+            const bool tk = xfade && (!s->fade_primed || s->ir_gen != s->fade_gen);
+            if ((!xfade || tk) && s->last_rec >= 0) {
+                const int buf = s->last_rec;
+                // (a finished reconstruct needs no barrier packet on the stream: S of them are most of a short batch)
+                bool done = false;
+                if (s->rec_recorded[buf] && !s->rec_batch[buf]) {
+                    done = hipEventQuery(s->ev_rec[buf]) == hipSuccess;
+                    if (!done) (void)hipGetLastError();   // hipErrorNotReady is not an error
+                }
+                if (!done) FS_HIP(ctx, stream_waits_for_rec(ctx, rs, s, buf));
+            }
+            if (tk) {
+                float a = 0.0f;
+                if (s->fade_primed) {   // a fade from what is heard now: h_to alone, or the mix at the last output sample of a running fade
+                    if (s->fading) a = (float)s->fade_pos / (float)s->fade_len;
+                    else std::swap(s->d_fade_from, s->d_fade_to);
+                    s->fading = true;
+                    s->fade_pos = 0;
+                }
+                it.take_from = s->d_fade_from; it.take_to = s->d_fade_to; it.take_ir = s->d_ir_mono; it.take_a = a;
+                take[n_take++] = i;
+                s->rev_recorded = true;   // (ev_rev is recorded behind the fade-start launch below, still under the lock)
+                s->fade_primed = true;
+                s->fade_gen = s->ir_gen;
+            }
+            it.ring = s->d_ring;
+            it.head = s->rev_head;
+            if (!xfade) { it.ir = s->d_ir_mono; plain[n_plain++] = i; s->rev_recorded = true; }
+            else if (s->fading) {
+                it.ir = s->d_fade_from; it.ir_to = s->d_fade_to; it.fade_pos = s->fade_pos; it.fade_len = s->fade_len;
+                fade[n_fade++] = i;
+            } else { it.ir = s->d_fade_to; plain[n_plain++] = i; }
+            s->rev_head += (unsigned)frame;
+            if (s->fading && (s->fade_pos += frame) >= s->fade_len) s->fading = false;   // complete: h_from := h_to, one convolution again
+        }
+        FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, rs));
+        const ReverbItem* d_items = (const ReverbItem*)(ds + l.items);
+        const int* d_plain = (const int*)(ds + l.lists);
+        if (n_take) {
+            launch_reverb_batch_fade_start(d_items, d_plain + 2 * count, n_take, ctx->num_samples, rs);
+            FS_HIP(ctx, hipGetLastError());
+            for (int k = 0; k < n_take; ++k) FS_HIP(ctx, hipEventRecord(srcs[(size_t)take[k]]->ev_rev, rs));
+        }
+        ReverbBatch b{};
+        b.items = d_items;
+        b.plain = d_plain; b.n_plain = n_plain;
+        b.fade = d_plain + count; b.n_fade = n_fade;
+        b.count = count; b.frame = frame; b.ir_size = ctx->num_samples; b.literal_tail = literal;
+        b.in = (const float*)(ds + l.in);
+        b.cur = (float*)(ds + l.d_cur);
+        b.out = (float*)(ds + l.d_out);
+        b.mix = mix ? (float*)(ds + l.d_mix) : nullptr;
+        launch_reverb_batch(b, rs);
+        FS_HIP(ctx, hipGetLastError());
+        for (int k = 0; k < n_plain; ++k) {   // without a crossfade the convolution itself reads d_ir_mono
+            Source* s = srcs[(size_t)plain[k]];
+            if (s->fade_len == 0) FS_HIP(ctx, hipEventRecord(s->ev_rev, rs));
+        }
+    }
+    if (out)   // out | mix are adjacent on both sides: one copy back
+        FS_HIP(ctx, hipMemcpyAsync(hs + l.h_out, ds + l.d_out, sizeof(float) * row * ((size_t)count + (mix ? 1 : 0)), hipMemcpyDeviceToHost, rs));
+    else
+        FS_HIP(ctx, hipMemcpyAsync(hs + l.h_mix, ds + l.d_mix, sizeof(float) * row, hipMemcpyDeviceToHost, rs));
+    FS_HIP(ctx, hipStreamSynchronize(rs));
+    if (out) {
+        const float* h_out = (const float*)(hs + l.h_out);
+        for (int32_t i = 0; i < count; ++i) {   // bApplyReverb == false: RVB.cpp:128-132
+            const float* from = (apply_reverb && !apply_reverb[i]) ? in + (size_t)i * row : h_out + (size_t)i * row;
+            if (from != out + (size_t)i * row) std::memcpy(out + (size_t)i * row, from, sizeof(float) * row);   // (in place: in == out)
+        }
+    }
+    if (mix) std::memcpy(mix, hs + l.h_mix, sizeof(float) * row);
+    return FS_OK;
+}
+
 int fs_reverb_release(fs_context* ctx, fs_source h) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     Source* s = get_source(ctx, h);

@@ -652,6 +652,8 @@ int fs_context_destroy(fs_context* ctx) {
             if (p) (void)hipFree(p);
         if (ctx->fft_graph) (void)hipGraphExecDestroy(ctx->fft_graph);
         if (ctx->h_fft_stage) (void)hipHostFree(ctx->h_fft_stage);
+        if (ctx->h_rev_stage) (void)hipHostFree(ctx->h_rev_stage);
+        if (ctx->d_rev_stage) (void)hipFree(ctx->d_rev_stage);
         if (ctx->d_batch) (void)hipFree(ctx->d_batch);
         if (ctx->d_build) (void)hipFree(ctx->d_build);
         if (ctx->d_carrier) (void)hipFree(ctx->d_carrier);

@@ -227,6 +227,11 @@ struct fs_context {
     size_t fft_stage_floats = 0;
     hipGraphExec_t fft_graph = nullptr;
     int fft_graph_n = -1, fft_graph_l = -1;
+    // fs_reverb_process_batch (audio thread): pinned host staging and its device mirror, grown at the first call that needs more
+    // (count x frame size), freed with the context.  Up: items [count] | plain, fade, take lists [3][count] | in [count][2 frame];
+    // down: out [count][2 frame] | mix [2 frame]; the device also holds the mono tails cur [count][2 frame].
+    char* h_rev_stage = nullptr; char* d_rev_stage = nullptr;
+    size_t rev_stage_host = 0, rev_stage_dev = 0;   // bytes
     // FS_FLAG_SPECTRAL_IR: the band edges (fs_set_band_edges: the B - 1 inner ones, ascending; empty = the defaults) and the
     // carriers built from them (fs_capi_publish.cpp: carrier_for — lazily, before the first spectral reconstruct)
     std::vector<double> band_edges;

@@ -416,6 +416,35 @@ void launch_reverb(const float* ir, int ir_size, float* ring, unsigned head, con
                    int frame, int literal_tail, hipStream_t s, const float* ir_to = nullptr, int fade_pos = 0, int fade_len = 0);
 // a crossfade starts: h_from := (1 - a) h_from + a h_to (a > 0), then h_to := ir (n samples)
 void launch_reverb_fade_start(float* h_from, float* h_to, const float* ir, int n, float a, hipStream_t s);
+// fs_reverb.hip (fs_reverb_process_batch): one descriptor per row of the call, in list order, read by every kernel of the batch.
+struct ReverbItem {
+    const float* ir;       // the convolution's IR (h_from while a crossfade runs) ...
+    const float* ir_to;    // ... and the IR it fades to (null: one convolution)
+    float* ring;           // history rings [2][kReverbRing]
+    float* take_from;      // a source that takes a newer IR in this callback (launch_reverb_batch_fade_start):
+    float* take_to;        //   h_from := (1 - take_a) h_from + take_a h_to (take_a > 0), then h_to := take_ir
+    const float* take_ir;
+    unsigned head;         // ring write head before this callback
+    int32_t fade_pos, fade_len;
+    float take_a;
+    int32_t apply;         // 0: the bypass (out row := in row, nothing else)
+    int32_t pad_;
+};
+static_assert(sizeof(ReverbItem) == 72, "ReverbItem: six pointers and six words, the host's staging layout");
+struct ReverbBatch {
+    const ReverbItem* items;        // [count]
+    const int* plain; int n_plain;  // rows convolved with one IR ...
+    const int* fade; int n_fade;    // ... and with two
+    int count, frame, ir_size, literal_tail;
+    const float* in;                // [count][2 * frame] interleaved
+    float* cur;                     // [count][2][frame] scratch
+    float* out;                     // [count][2 * frame] interleaved
+    float* mix;                     // [2 * frame], or null
+};
+// take: the rows whose crossfade starts in this callback (n_take >= 1), n = IR samples
+void launch_reverb_batch_fade_start(const ReverbItem* items, const int* take, int n_take, int n, hipStream_t s);
+// prepare + push, the convolutions of the two lists (each launched only when it has rows), the mix (when b.mix)
+void launch_reverb_batch(const ReverbBatch& b, hipStream_t s);
 void launch_add_energy(float* energy_row, int num_bins, float delay_s, float e, hipStream_t s);
 // dynamic LDS the traversal kernels of a frame need for a tree with `stack_rows` stack rows: the larger of the walk
 // kernel (stack + work-sharing area) and the connect kernels (stack + [bands][bins] histogram + work-sharing area)

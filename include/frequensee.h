@@ -50,7 +50,7 @@
  *             fs_comm_enable_oneshot fs_comm_detach fs_comm_info fs_peers_init fs_peers_detach fs_gather_energy fs_gather_energy_async
  *             fs_copy_band_impulse_response fs_set_impulse_response fs_trace_rays
  *             fs_save_array_to_file fs_load_float_array fs_save_impulse_response
- *             fs_reverb_init fs_reverb_process fs_reverb_release fs_reverb_set_crossfade fs_apply_material_fd
+ *             fs_reverb_init fs_reverb_process fs_reverb_process_batch fs_reverb_release fs_reverb_set_crossfade fs_apply_material_fd
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
  *             fs_source_set_orientation fs_source_set_directivity fs_get_room_parameters
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
@@ -576,6 +576,30 @@ int fs_reverb_init(fs_context* ctx, fs_source src, int32_t frame_size /* BufferL
  * reconstruct that wrote it (events, exchanged under a per-source mutex held only while work is enqueued) and waits for
  * its own stream only.  fs_reverb_init / fs_reverb_release of a source must not run concurrently with its callback. */
 int fs_reverb_process(fs_context* ctx, fs_source src, const float* in, float* out, int32_t apply_reverb, uint32_t flags);
+/* The callbacks of `count` sources as ONE set of launches (the mixer's loop over ProcessSourceAudio, RVB.cpp:118-170): the
+ * number of copies, kernel launches and stream synchronisations of a call does not grow with count.
+ *   in  [count][frame_size * 2]  interleaved stereo, host; row i belongs to sources[i]
+ *   out [count][frame_size * 2]  or NULL
+ *   apply_reverb [count]         or NULL = all on; flags (FS_REVERB_LITERAL_TAIL) hold for every source of the call
+ *   mix [frame_size * 2]         or NULL; out == NULL && mix == NULL is FS_ERR_INVALID_ARGUMENT
+ *  1. out[i] and the state of sources[i] afterwards (history, write head, crossfade state) are, to the bit, what
+ *     fs_reverb_process(ctx, sources[i], in[i], out[i], apply_reverb[i], flags) for i = 0 .. count - 1 in that order leaves, in
+ *     every state of that call (crossfades included; the bypass copies the row and touches no state).  Batch and single
+ *     calls may be mixed freely from one callback to the next.
+ *  2. mix[j] = ((out[0][j] + out[1][j]) + out[2][j]) + ... in fp32, in list order, over the values of rule 1 (each clamped; a
+ *     bypassed source contributes its input); the sum itself is not clamped.  It is computed on the device in that fixed
+ *     order (reproducible); with out == NULL only mix comes back from the device.
+ *  3. 1 <= count <= FS_MAX_REVERB_BATCH, every source has had fs_reverb_init, all share one frame size, no handle appears
+ *     twice: otherwise FS_ERR_INVALID_ARGUMENT (FS_ERR_BAD_HANDLE for a bad handle).  A refused call changes nothing.
+ *  4. The threading contract of fs_reverb_process, for every listed source: safe against the game thread's reconstructs and
+ *     fs_set_impulse_response, not concurrent with fs_reverb_init / _release / _set_crossfade or another callback of a
+ *     listed source.  The sources' mutexes are taken in the order the game thread takes them and held only while work is
+ *     enqueued.
+ *  5. Pinned staging owned by the context is grown at the FIRST call that needs more (count x frame_size); a call whose
+ *     count and frame size the context has already seen allocates no device or pinned memory. */
+#define FS_MAX_REVERB_BATCH 256
+int fs_reverb_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in, float* out,
+                            const int32_t* apply_reverb, uint32_t flags, float* mix);
 int fs_reverb_release(fs_context* ctx, fs_source src); /* OnReleaseSource: ClearBuffers; also ends a running crossfade */
 /* Crossfade between successive impulse responses (not in the reference, which switches abruptly; opt-in per source).
  * samples == 0 (the default): every callback convolves with the IR on the device at that moment, the reference's switch.
