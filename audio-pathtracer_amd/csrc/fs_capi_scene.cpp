@@ -478,6 +478,54 @@ int fs_scene_refit(fs_context* ctx) {
     return refresh_coop_nodes(ctx, false);
 }
 
+// Debug entry (not in include/frequensee.h; tests/tree_check.py reads the committed tree through it): one array of the
+// committed scene copied to host memory, sized for the scene — not for the capacity a fast commit keeps.  Read-only: held
+// frames are flushed and the compute stream drains as in the other scene calls, but a pending refit stays pending and
+// nothing is launched.  what: 0 header {nodes, triangles, levels, stack_need, bvh.pad, amax, coop16_nodes, coop_levels,
+// refit_pending, arrays of a fast commit, 0, 0} (12 x 4 B) | 1 NodeQ4[nodes] | 2 Tri64[T] | 3 Tri48[T] | 4 normals[T] |
+// 5 leaf_pos[T] | 6 level_begin[levels + 1] (host copy) | 7 CoopChild[4 nodes] | 8 CoopChild[16 coop16_nodes] |
+// 9 d_coop_levels [2][kMaxBuildLevels + 2] | 10 node_box[nodes][2].  cap too small: FS_ERR_SIZE_MISMATCH, *bytes = the size.
+__attribute__((visibility("default"))) int fs_debug_scene_snapshot(fs_context* ctx, int32_t what, void* out, size_t cap, size_t* bytes) {
+    if (!ctx || !bytes) return FS_ERR_INVALID_ARGUMENT;
+    *bytes = 0;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
+    if (!ctx->committed) return ctx->fail(FS_ERR_NOT_COMMITTED, "scene not committed");
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t nodes = ctx->bvh.nodes.size(), T = (size_t)ctx->T;
+    const size_t levels = ctx->bvh.level_begin.empty() ? 0 : ctx->bvh.level_begin.size() - 1;
+    uint32_t hdr[12] = {(uint32_t)nodes, (uint32_t)T, (uint32_t)levels, (uint32_t)ctx->bvh.stack_need, 0, 0,
+                        (uint32_t)ctx->coop16_nodes, (uint32_t)ctx->coop_levels, ctx->refit_pending ? 1u : 0u,
+                        ctx->fast_cap_tris > 0 ? 1u : 0u, 0, 0};
+    std::memcpy(&hdr[4], &ctx->bvh.pad, sizeof(float));
+    std::memcpy(&hdr[5], &ctx->amax, sizeof(float));
+    const void* src = nullptr;
+    bool on_device = true;
+    size_t need = 0;
+    switch (what) {
+        case 0: src = hdr; need = sizeof(hdr); on_device = false; break;
+        case 1: src = ctx->d_nodes; need = nodes * sizeof(NodeQ4); break;
+        case 2: src = ctx->d_tris; need = T * sizeof(Tri64); break;
+        case 3: src = ctx->d_tris48; need = T * sizeof(Tri48); break;
+        case 4: src = ctx->d_tri_nrm; need = T * sizeof(float4); break;
+        case 5: src = ctx->d_leaf_pos; need = T * sizeof(uint32_t); break;
+        case 6: src = ctx->bvh.level_begin.data(); need = ctx->bvh.level_begin.size() * sizeof(int32_t); on_device = false; break;
+        case 7: src = ctx->d_coop; need = 4 * nodes * sizeof(CoopChild); break;
+        case 8: src = ctx->d_coop16; need = 16 * (size_t)ctx->coop16_nodes * sizeof(CoopChild); break;
+        case 9: src = ctx->d_coop_levels; need = ctx->d_coop_levels ? 2 * (size_t)(kMaxBuildLevels + 2) * sizeof(int32_t) : 0; break;
+        case 10: src = ctx->d_node_box; need = 2 * nodes * sizeof(float4); break;
+        default: return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_debug_scene_snapshot: no such array");
+    }
+    *bytes = need;
+    if (need == 0) return FS_OK;
+    if (!src) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_debug_scene_snapshot: the scene holds no such array");
+    if (!out || cap < need) return ctx->fail(FS_ERR_SIZE_MISMATCH, "fs_debug_scene_snapshot: buffer too small");
+    if (on_device) FS_HIP(ctx, hipMemcpy(out, src, need, hipMemcpyDeviceToHost));
+    else std::memcpy(out, src, need);
+    return FS_OK;
+}
+
 int fs_scene_set_objects(fs_context* ctx, const uint32_t* object_id, int32_t T) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     if (object_id && T != ctx->T) return ctx->fail(FS_ERR_SIZE_MISMATCH, "object ids: T != number of triangles");

@@ -4,8 +4,9 @@
 // (AudioRayTracingSubsystem.cpp:333-336, FrequenSeeAudioComponent.cpp:229-232), so a moved prop is seen by
 // the next frame.  The host SAH build takes ~180 ms for 100 000 triangles; a moved subset is instead written
 // straight into the leaf-order triangle records and the 4-wide tree is refitted bottom-up on the device:
-// same topology, new boxes.  Results stay a function of ray and triangles only (boxes are conservative:
-// padded and quantised outwards exactly as in fs_bvh.cpp), so they equal a fresh build's bit for bit.
+// same topology, new boxes.  Results stay a function of ray and triangles only (boxes are conservative: padded and
+// quantised outwards by fs_bvh.cpp's rule, but around the records' v0 + e1, v0 + e2 where the host boxes the input
+// vertices: the bytes may differ from a host build's, tests/tree_check.py), so they equal a fresh build's bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -94,8 +95,8 @@ __global__ __launch_bounds__(kRefitBlock) void refit_level_kernel(NodeQ4* __rest
                 const float4 a = tris[t].a, b = tris[t].b;
                 const float e2z = tris[t].c.x;
                 box_point(cb[c], a.x, a.y, a.z);
-                box_point(cb[c], a.x + a.w, a.y + b.x, a.z + b.y);      // v0 + e1 (half an ulp off the input
-                box_point(cb[c], a.x + b.z, a.y + b.w, a.z + e2z);      // vertex at most; pad >= 0.01 cm)
+                box_point(cb[c], a.x + a.w, a.y + b.x, a.z + b.y);      // v0 + e1 (1.5 ulp of the largest coordinate off
+                box_point(cb[c], a.x + b.z, a.y + b.w, a.z + e2z);      // the input vertex at most; pad >= 32 such ulps)
             }
         }
         for (int k = 0; k < 3; ++k) { nb.lo[k] = fminf(nb.lo[k], cb[c].lo[k]); nb.hi[k] = fmaxf(nb.hi[k], cb[c].hi[k]); }
