@@ -1,6 +1,5 @@
 // fs_aux_kernels.hip — reconstruct_kernel (ReconstructImpulseResponse, FrequenSeeAudioComponent.cpp:320-380), the engine
-// line trace for tests / tools, the legacy forward tracer (UpdateSound, :132-306), the reverb plugin's per-callback
-// convolution (FrequenSeeAudioReverbPlugin.cpp:118-213), AddEnergyAtDelay on the device-resident buffer.
+// line trace for tests / tools, the legacy forward tracer (UpdateSound, :132-306), AddEnergyAtDelay on the device-resident buffer.
 #include "fs_dev_trav.hpp"
 #include "fs_dev_walk.hpp"
 #include "fs_dev_coop.hpp"
@@ -328,119 +327,6 @@ __global__ __launch_bounds__(kBlock) void update_sound_shared_kernel(DeviceScene
     if (traces) atomicAdd(&acc->traces, traces);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Row f2 — the reverb plugin's per-callback convolution (FFrequenSeeAudioReverbPlugin::ProcessSourceAudio,
-// FrequenSeeAudioReverbPlugin.cpp:118-170, ConvolveFFT :172-213).  The reference zero-pads the last
-// 47 999 + 1 024 samples and the 48 000-tap IR to 65 536 and multiplies three KissFFT spectra; only output
-// samples [47 999, 49 023) are kept, for which the circular product equals the plain convolution
-//   out[s] = sum_k IR[k] * u[47 999 + s - k].
-// On this chip 2 x 1024 x 48 000 MACs are a few microseconds of fp32 FMA, so the kernel evaluates that sum
-// directly (no FFT, no 65 536-point scratch, deterministic order): thread t owns a contiguous 192-tap slice
-// and slides a 31-sample register window over it (47 loads per 256 FMAs), partial sums meet in LDS.
-//   u[j] = j < tail ? ring[(head - tail + j) & mask] : cur[j - tail]
-// ---------------------------------------------------------------------------------------------------
-constexpr int kRevOut = 16;      // outputs per workgroup
-constexpr int kRevRing = 65536;  // history ring length per channel (power of two >= 47 999)
-
-__global__ void reverb_prepare_kernel(const float* __restrict__ in, float* __restrict__ cur, int frame, int literal) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= frame) return;
-    // RVB.cpp:147-148 copies the first `frame` floats of the INTERLEAVED buffer into both mono tails
-    cur[i] = literal ? in[i] : in[2 * i];
-    cur[frame + i] = literal ? in[i] : in[2 * i + 1];
-}
-
-// FADE (fs_reverb_set_crossfade, its own instantiation: the plain one's arguments and code are today's): a second IR
-// `ir_to` over the same register window — the u loads are shared, the IR loads and FMAs double — and per output
-// y = (1 - g) (ir * u) + g (ir_to * u), g = (p + 1) / fade_len while p = fade_pos + s < fade_len, else 1.  g depends on
-// the output only, so each thread mixes its partial sums before the reduction (the sum is linear).
-template <bool FADE>
-__global__ __launch_bounds__(kBlock) void reverb_conv_kernel(const float* __restrict__ ir, int ir_size,
-                                                             const float* __restrict__ ring, unsigned head,
-                                                             const float* __restrict__ cur, int frame,
-                                                             float* __restrict__ out_interleaved,
-                                                             const float* __restrict__ ir_to, int fade_pos, int fade_len) {
-    __shared__ float s_part[kRevOut][kBlock + 1];
-    const int ch = blockIdx.y;
-    const int s0 = blockIdx.x * kRevOut;
-    const int tail = ir_size - 1;
-    const float* rg = ring + (size_t)ch * kRevRing;
-    const float* cu = cur + (size_t)ch * frame;
-    const unsigned base = head - (unsigned)tail;   // ring index of u[0]
-    const int slice = ((ir_size + kBlock - 1) / kBlock + 15) & ~15;
-    const int k0 = (int)threadIdx.x * slice;
-    const int k1 = min(k0 + slice, ir_size);
-    float acc[kRevOut], acc_to[kRevOut];
-#pragma unroll
-    for (int o = 0; o < kRevOut; ++o) { acc[o] = 0.0f; acc_to[o] = 0.0f; }
-    for (int kb = k0; kb < k1; kb += 16) {
-        float w[31], h[16];
-        const int j0 = tail + s0 - kb - 15;   // u index of w[0]
-#pragma unroll
-        for (int i = 0; i < 31; ++i) {
-            const int j = j0 + i;
-            float v = 0.0f;
-            if (j >= 0 && j < tail + frame) v = j < tail ? rg[(base + (unsigned)j) & (unsigned)(kRevRing - 1)] : cu[j - tail];
-            w[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) h[i] = (kb + i) < ir_size ? ir[kb + i] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-#pragma unroll
-            for (int o = 0; o < kRevOut; ++o) acc[o] = fmaf(h[i], w[15 - i + o], acc[o]);
-        if (FADE) {
-            float h2[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) h2[i] = (kb + i) < ir_size ? ir_to[kb + i] : 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-#pragma unroll
-                for (int o = 0; o < kRevOut; ++o) acc_to[o] = fmaf(h2[i], w[15 - i + o], acc_to[o]);
-        }
-    }
-    if (FADE) {
-#pragma unroll
-        for (int o = 0; o < kRevOut; ++o) {
-            const int p = fade_pos + s0 + o;
-            const float g = p < fade_len ? (float)(p + 1) / (float)fade_len : 1.0f;
-            acc[o] = (1.0f - g) * acc[o] + g * acc_to[o];
-        }
-    }
-#pragma unroll
-    for (int o = 0; o < kRevOut; ++o) s_part[o][threadIdx.x] = acc[o];
-    __syncthreads();
-    for (int stride = kBlock / 2; stride > 0; stride >>= 1) {
-        if ((int)threadIdx.x < stride)
-#pragma unroll
-            for (int o = 0; o < kRevOut; ++o) s_part[o][threadIdx.x] += s_part[o][threadIdx.x + stride];
-        __syncthreads();
-    }
-    if (threadIdx.x < kRevOut && s0 + (int)threadIdx.x < frame) {
-        float v = s_part[threadIdx.x][0];
-        v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);                 // FMath::Clamp RVB.cpp:165-167, MixAlpha = 1
-        out_interleaved[2 * (s0 + (int)threadIdx.x) + ch] = v;
-    }
-}
-
-// AudioTailBuffer{Left,Right}.AddSamples(in, frame, ch, 2)  RVB.cpp:144-145
-__global__ void reverb_push_kernel(const float* __restrict__ in, float* __restrict__ ring, unsigned head, int frame) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= frame) return;
-    ring[(head + (unsigned)i) & (unsigned)(kRevRing - 1)] = in[2 * i];
-    ring[kRevRing + ((head + (unsigned)i) & (unsigned)(kRevRing - 1))] = in[2 * i + 1];
-}
-
-// A crossfade starts (fs_reverb_set_crossfade): h_from := (1 - a) h_from + a h_to — the IR heard at the last output sample of
-// a fade that is cut short (a = p0 / L; a = 0 leaves h_from as it is) — then h_to := the device-resident IR.
-__global__ void reverb_fade_start_kernel(float* __restrict__ h_from, float* __restrict__ h_to, const float* __restrict__ ir,
-                                         int n, float a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (a > 0.0f) h_from[i] = (1.0f - a) * h_from[i] + a * h_to[i];
-    h_to[i] = ir[i];
-}
-
 // AddEnergyAtDelay on the device-resident buffer (FSAC.h:87-91)
 __global__ void add_energy_kernel(float* row, int nb, float delay, float e) {
     float x = (delay * 1000.f) / 1.0f;
@@ -536,25 +422,6 @@ void launch_update_sound(const DeviceScene& sc_in, const SoundKParams& sp, Sound
     allow_lds(update_sound_shared_kernel, lds);
     hipLaunchKernelGGL(update_sound_shared_kernel, dim3((waves + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), lds, s, sc, sp,
                        acc, rays_per_wave);
-}
-
-void launch_reverb(const float* ir, int ir_size, float* ring, unsigned head, const float* in, float* cur, float* out,
-                   int frame, int literal_tail, hipStream_t s, const float* ir_to, int fade_pos, int fade_len) {
-    const int tb = 256;
-    const dim3 grid((frame + kRevOut - 1) / kRevOut, 2);
-    hipLaunchKernelGGL(reverb_prepare_kernel, dim3((frame + tb - 1) / tb), dim3(tb), 0, s, in, cur, frame, literal_tail);
-    if (ir_to)
-        hipLaunchKernelGGL(reverb_conv_kernel<true>, grid, dim3(kBlock), 0, s, ir, ir_size, ring, head, cur, frame, out,
-                           ir_to, fade_pos, fade_len);
-    else
-        hipLaunchKernelGGL(reverb_conv_kernel<false>, grid, dim3(kBlock), 0, s, ir, ir_size, ring, head, cur, frame, out,
-                           nullptr, 0, 0);
-    hipLaunchKernelGGL(reverb_push_kernel, dim3((frame + tb - 1) / tb), dim3(tb), 0, s, in, ring, head, frame);
-}
-
-void launch_reverb_fade_start(float* h_from, float* h_to, const float* ir, int n, float a, hipStream_t s) {
-    const int tb = 256;
-    hipLaunchKernelGGL(reverb_fade_start_kernel, dim3((n + tb - 1) / tb), dim3(tb), 0, s, h_from, h_to, ir, n, a);
 }
 
 #ifdef FS_WAVE_TIMELINE

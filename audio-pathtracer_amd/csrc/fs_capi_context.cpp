@@ -162,9 +162,6 @@ void free_source(fs_context* ctx, Source* s) {
         }
         if (s->h_room.load()) (void)hipHostFree(s->h_room.load());
         if (s->d_ring) (void)hipFree(s->d_ring);
-        if (s->d_rev_in) (void)hipFree(s->d_rev_in);
-        if (s->d_rev_cur) (void)hipFree(s->d_rev_cur);
-        if (s->d_rev_out) (void)hipFree(s->d_rev_out);
         if (s->d_fade_from) (void)hipFree(s->d_fade_from);
         if (s->d_fade_to) (void)hipFree(s->d_fade_to);
         if (s->d_dir) (void)hipFree(s->d_dir);   // (the callers have synchronised the compute stream)

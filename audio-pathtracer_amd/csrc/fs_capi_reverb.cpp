@@ -1,0 +1,268 @@
+// fs_capi_reverb.cpp — row f2, the reverb plugin's per-callback convolution (RVB.cpp:74-213) behind the C ABI: per-source set-up
+// (fs_reverb_init / _set_crossfade / _release) and the audio callback.  There is ONE callback path, reverb_rows: a list of rows
+// served by one set of launches (fs_reverb.hip); fs_reverb_process is that list with one row.
+#include "fs_context.hpp"
+
+namespace {
+
+// fs_reverb_set_crossfade: the callback's two IR copies, once the source has a reverb and a fade length
+int alloc_fade(fs_context* ctx, Source* s) {
+    const size_t bytes = sizeof(float) * (size_t)ctx->num_samples;
+    if (!s->d_fade_from) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_from, bytes));
+    if (!s->d_fade_to) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_to, bytes));
+    return FS_OK;
+}
+
+// The staging of one callback (fs_context::h_rev_stage / d_rev_stage), every block 256-byte aligned
+struct RevStageLayout {
+    size_t items, lists, in, up_bytes;      // host and device, the same offsets: what goes up in one copy
+    size_t h_out, h_mix, host_bytes;        // host: what comes back
+    size_t d_cur, d_out, d_mix, dev_bytes;  // device: out | mix adjacent, one copy back
+};
+size_t rev_align(size_t b) { return (b + 255) & ~(size_t)255; }
+RevStageLayout rev_stage_layout(int count, int frame) {
+    const size_t rows = sizeof(float) * 2 * (size_t)frame * (size_t)count, row = sizeof(float) * 2 * (size_t)frame;
+    RevStageLayout l;
+    l.items = 0;
+    l.lists = rev_align(sizeof(ReverbItem) * (size_t)count);
+    l.in = l.lists + rev_align(sizeof(int) * 3 * (size_t)count);
+    l.up_bytes = l.in + rows;
+    l.h_out = rev_align(l.up_bytes);
+    l.h_mix = l.h_out + rows;   // (adjacent to out: rows is a multiple of 8 bytes)
+    l.host_bytes = l.h_mix + row;
+    l.d_cur = rev_align(l.up_bytes);
+    l.d_out = l.d_cur + rev_align(rows);
+    l.d_mix = l.d_out + rows;
+    l.dev_bytes = l.d_mix + row;
+    return l;
+}
+
+const char* const kNoFadeBuffers = "the crossfade's impulse-response buffers are missing: call fs_reverb_init again";
+
+// One convolved source's step of a callback, under its ir_mu.  The callback has its own stream: it is never queued behind a traced
+// frame on the compute stream.  The device-resident IR is written by reconstructs on the tail stream: read it behind the newest one
+// and make the next one wait for this read — both through events, exchanged with the game thread under the source's ir_mu (the
+// caller records ev_rev behind the launch that reads d_ir_mono, still under the lock).  With a crossfade (fs_reverb_set_crossfade)
+// the callback convolves its own copies of the IR: it reads d_ir_mono only when a newer IR is there (ir_gen), once, into h_to —
+// only then does it wait for the write and make the next one wait for it.  *takes: this callback is such a one.
+int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbItem& it, bool* takes) {
+    it.apply = 1;
+    const bool xfade = s->fade_len > 0;
+    const bool tk = *takes = xfade && (!s->fade_primed || s->ir_gen != s->fade_gen);
+    if ((!xfade || tk) && s->last_rec >= 0) {
+        const int buf = s->last_rec;
+        // (a finished reconstruct needs no barrier packet on the stream: S of them are most of a short batch)
+        bool done = false;
+        if (s->rec_recorded[buf] && !s->rec_batch[buf]) {
+            done = hipEventQuery(s->ev_rec[buf]) == hipSuccess;
+            if (!done) (void)hipGetLastError();   // hipErrorNotReady is not an error
+        }
+        if (!done) FS_HIP(ctx, stream_waits_for_rec(ctx, rs, s, buf));
+    }
+    if (tk) {
+        float a = 0.0f;
+        if (s->fade_primed) {   // a fade from what is heard now: h_to alone, or the mix at the last output sample of a running fade
+            if (s->fading) a = (float)s->fade_pos / (float)s->fade_len;
+            else std::swap(s->d_fade_from, s->d_fade_to);
+            s->fading = true;
+            s->fade_pos = 0;
+        }
+        it.take_from = s->d_fade_from; it.take_to = s->d_fade_to; it.take_ir = s->d_ir_mono; it.take_a = a;
+        s->fade_primed = true;
+        s->fade_gen = s->ir_gen;
+    }
+    if (!xfade || tk) s->rev_recorded = true;
+    it.ring = s->d_ring;
+    it.head = s->rev_head;
+    if (!xfade) it.ir = s->d_ir_mono;
+    else if (s->fading) { it.ir = s->d_fade_from; it.ir_to = s->d_fade_to; it.fade_pos = s->fade_pos; it.fade_len = s->fade_len; }
+    else it.ir = s->d_fade_to;
+    s->rev_head += (unsigned)frame;
+    if (s->fading && (s->fade_pos += frame) >= s->fade_len) s->fading = false;   // complete: h_from := h_to, one convolution again
+    return FS_OK;
+}
+
+// The callback of `count` validated sources of one frame size (audio thread): one copy up, the launches, one copy back.
+int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float* in, float* out, const int32_t* apply_reverb,
+                uint32_t flags, float* mix) {
+    std::vector<int32_t> order((size_t)count);   // rows by ascending Source*: the one locking order of every thread (fs_capi_publish.cpp)
+    for (int32_t i = 0; i < count; ++i) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return srcs[a] < srcs[b]; });
+    for (int32_t k = 1; k < count; ++k)   // (still before the first state change or enqueue)
+        if (srcs[order[(size_t)k]] == srcs[order[(size_t)k - 1]])
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a source appears twice in the batch");
+    const int frame = srcs[0]->rev_frame;
+    const size_t row = 2 * (size_t)frame;   // floats
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    hipStream_t rs = ctx->rev_stream;
+    const RevStageLayout l = rev_stage_layout(count, frame);
+    if (l.host_bytes > ctx->rev_stage_host || l.dev_bytes > ctx->rev_stage_dev) {   // first call of this size (every call ends synchronised: nothing reads the old one)
+        if (ctx->h_rev_stage) (void)hipHostFree(ctx->h_rev_stage);
+        if (ctx->d_rev_stage) (void)hipFree(ctx->d_rev_stage);
+        ctx->h_rev_stage = ctx->d_rev_stage = nullptr; ctx->rev_stage_host = ctx->rev_stage_dev = 0;
+        FS_HIP(ctx, hipHostMalloc((void**)&ctx->h_rev_stage, l.host_bytes, hipHostMallocDefault));
+        ctx->rev_stage_host = l.host_bytes;
+        FS_HIP(ctx, hipMalloc((void**)&ctx->d_rev_stage, l.dev_bytes));
+        ctx->rev_stage_dev = l.dev_bytes;
+    }
+    char* hs = ctx->h_rev_stage; char* ds = ctx->d_rev_stage;
+    ReverbItem* items = (ReverbItem*)(hs + l.items);
+    int* plain = (int*)(hs + l.lists); int* fade = plain + count; int* take = fade + count;
+    int n_plain = 0, n_fade = 0, n_take = 0;
+    float* h_in = (float*)(hs + l.in);
+    for (int32_t i = 0; i < count; ++i)   // (a bypassed row goes up only for the mix)
+        if (mix || !apply_reverb || apply_reverb[i])
+            std::memcpy(h_in + (size_t)i * row, in + (size_t)i * row, sizeof(float) * row);
+    {
+        // The steps in list order; the locks of all convolved sources are held while the work is enqueued (a reconstruct that found
+        // one free would not wait for a read this call has yet to record), not longer.
+        std::vector<std::unique_lock<std::mutex>> locks;
+        locks.reserve((size_t)count);
+        for (int32_t i : order)
+            if (!apply_reverb || apply_reverb[i]) locks.emplace_back(srcs[i]->ir_mu);
+        for (int32_t i = 0; i < count; ++i) {
+            std::memset(&items[i], 0, sizeof(ReverbItem));
+            if (apply_reverb && !apply_reverb[i]) continue;   // the bypass touches no state
+            bool takes = false;
+            const int rc = reverb_step(ctx, srcs[i], rs, frame, items[i], &takes);
+            if (rc) return rc;
+            if (takes) take[n_take++] = i;
+            if (items[i].ir_to) fade[n_fade++] = i;
+            else plain[n_plain++] = i;
+        }
+        FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, rs));
+        const ReverbItem* d_items = (const ReverbItem*)(ds + l.items);
+        const int* d_plain = (const int*)(ds + l.lists);
+        if (n_take) {
+            launch_reverb_batch_fade_start(d_items, d_plain + 2 * count, n_take, ctx->num_samples, rs);
+            FS_HIP(ctx, hipGetLastError());
+            for (int k = 0; k < n_take; ++k) FS_HIP(ctx, hipEventRecord(srcs[take[k]]->ev_rev, rs));
+        }
+        ReverbBatch b{};
+        b.items = d_items;
+        b.plain = d_plain; b.n_plain = n_plain;
+        b.fade = d_plain + count; b.n_fade = n_fade;
+        b.count = count; b.frame = frame; b.ir_size = ctx->num_samples;
+        b.literal_tail = (flags & FS_REVERB_LITERAL_TAIL) ? 1 : 0;
+        b.in = (const float*)(ds + l.in);
+        b.cur = (float*)(ds + l.d_cur);
+        b.out = (float*)(ds + l.d_out);
+        b.mix = mix ? (float*)(ds + l.d_mix) : nullptr;
+        launch_reverb_batch(b, rs);
+        FS_HIP(ctx, hipGetLastError());
+        for (int k = 0; k < n_plain; ++k) {   // without a crossfade the convolution itself reads d_ir_mono
+            Source* s = srcs[plain[k]];
+            if (s->fade_len == 0) FS_HIP(ctx, hipEventRecord(s->ev_rev, rs));
+        }
+    }
+    if (out)   // out | mix are adjacent on both sides: one copy back
+        FS_HIP(ctx, hipMemcpyAsync(hs + l.h_out, ds + l.d_out, sizeof(float) * row * ((size_t)count + (mix ? 1 : 0)), hipMemcpyDeviceToHost, rs));
+    else
+        FS_HIP(ctx, hipMemcpyAsync(hs + l.h_mix, ds + l.d_mix, sizeof(float) * row, hipMemcpyDeviceToHost, rs));
+    FS_HIP(ctx, hipStreamSynchronize(rs));
+    if (out) {
+        const float* h_out = (const float*)(hs + l.h_out);
+        for (int32_t i = 0; i < count; ++i) {   // bApplyReverb == false: RVB.cpp:128-132
+            const float* from = (apply_reverb && !apply_reverb[i]) ? in + (size_t)i * row : h_out + (size_t)i * row;
+            if (from != out + (size_t)i * row) std::memcpy(out + (size_t)i * row, from, sizeof(float) * row);   // (in place: in == out)
+        }
+    }
+    if (mix) std::memcpy(mix, hs + l.h_mix, sizeof(float) * row);
+    return FS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (frame_size < 1 || frame_size > 16384 || ctx->num_samples - 1 > kReverbRing)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad reverb frame size / IR longer than the history ring");
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    // Reconstructs on the compute stream record an event for the callbacks only for a source that has a reverb: the ones
+    // already in flight finish before this source gets one.
+    FS_FLUSH(ctx);
+    FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    FS_HIP(ctx, hipStreamSynchronize(ctx->rev_stream));
+    if (s->d_ring) (void)hipFree(s->d_ring);
+    if (s->d_fade_from) { (void)hipFree(s->d_fade_from); (void)hipFree(s->d_fade_to); }
+    s->d_ring = s->d_fade_from = s->d_fade_to = nullptr;
+    FS_HIP(ctx, hipMalloc((void**)&s->d_ring, sizeof(float) * 2 * kReverbRing));
+    FS_HIP(ctx, hipMemsetAsync(s->d_ring, 0, sizeof(float) * 2 * kReverbRing, ctx->rev_stream));   // SetNumZeroed
+    s->rev_head = 0;
+    s->rev_frame = frame_size;
+    s->fading = s->fade_primed = false;   // (the first callback takes the IR unfaded)
+    if (s->fade_len > 0) return alloc_fade(ctx, s);
+    return FS_OK;
+}
+
+int fs_reverb_set_crossfade(fs_context* ctx, fs_source h, int32_t samples) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (samples < 0 || (int64_t)samples > 4 * (int64_t)ctx->cfg.sample_rate)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "crossfade length out of range (0 = off, 1 .. 4 * sample_rate)");
+    if (samples > 0 && s->d_ring) {
+        FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+        const int rc = alloc_fade(ctx, s);
+        if (rc) return rc;
+    }
+    if (s->fade_len == 0) s->fade_primed = false;   // enabling: nothing to fade from
+    s->fading = false;                              // a running fade ends at its target IR
+    s->fade_len = samples;
+    return FS_OK;
+}
+
+int fs_reverb_process(fs_context* ctx, fs_source h, const float* in, float* out, int32_t apply_reverb, uint32_t flags) {
+    if (!ctx || !in || !out) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (!s->d_ring) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init has not been called for this source");
+    if (!apply_reverb) {   // bApplyReverb == false: RVB.cpp:128-132 (neither the device nor any state; in == out is allowed)
+        if (out != in) std::memmove(out, in, sizeof(float) * 2 * (size_t)s->rev_frame);
+        return FS_OK;
+    }
+    if (s->fade_len > 0 && (!s->d_fade_from || !s->d_fade_to))   // (fs_reverb_init could not allocate them)
+        return ctx->fail(FS_ERR_OUT_OF_MEMORY, kNoFadeBuffers);
+    return reverb_rows(ctx, &s, 1, in, out, nullptr, flags, nullptr);
+}
+
+int fs_reverb_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in, float* out,
+                            const int32_t* apply_reverb, uint32_t flags, float* mix) {
+    if (!ctx || !sources || !in || (!out && !mix)) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    if (count < 1 || count > FS_MAX_REVERB_BATCH)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_REVERB_BATCH)");
+    // Everything is validated before the first state change or enqueue: a refused call changes nothing.
+    std::vector<Source*> srcs((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        Source* s = srcs[(size_t)i] = get_source(ctx, sources[i]);
+        if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+        if (!s->d_ring) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init has not been called for this source");
+        if (s->rev_frame != srcs[0]->rev_frame) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size");
+        if ((!apply_reverb || apply_reverb[i]) && s->fade_len > 0 && (!s->d_fade_from || !s->d_fade_to))
+            return ctx->fail(FS_ERR_OUT_OF_MEMORY, kNoFadeBuffers);
+    }
+    return reverb_rows(ctx, srcs.data(), count, in, out, apply_reverb, flags, mix);
+}
+
+int fs_reverb_release(fs_context* ctx, fs_source h) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (s->d_ring && ctx->device_ok) {
+        FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+        FS_HIP(ctx, hipMemsetAsync(s->d_ring, 0, sizeof(float) * 2 * kReverbRing, ctx->rev_stream));
+        s->rev_head = 0;
+        s->fading = false;   // a running crossfade ends at its target IR
+    }
+    return FS_OK;
+}
+
+}  // extern "C"

@@ -2,8 +2,8 @@
 // Internal: included by fs_capi_context.cpp (lifetime, helpers, stats), fs_capi_scene.cpp (geometry, commits, refit),
 // fs_capi_frame.cpp (sources, the traced frame: describe / resources / commit / launch), fs_capi_pipeline.cpp (held frames, the
 // drain), fs_capi_publish.cpp (reconstruct + publish: the IR ring, the host word, the fused launch's reconstruct parts),
-// fs_capi_ir.cpp (reconstruct / tick / IR / energy entry points), fs_capi_comm.cpp (RCCL behind the ABI) and fs_capi_aux.cpp
-// (legacy tracer, line trace, text interchange, reverb, material FD).
+// fs_capi_ir.cpp (reconstruct / tick / IR / energy entry points), fs_capi_comm.cpp (RCCL behind the ABI), fs_capi_reverb.cpp
+// (the reverb callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange, material FD).
 //
 // Mirrors the roles of UAudioRayTracingSubsystem (context lifetime, geometry/source registries,
 // per-source update: AudioRayTracingSubsystem.cpp:32-53, 128-195) and of UFrequenSeeAudioComponent's
@@ -135,8 +135,8 @@ struct Source {
     // flagged reconstruct — ensure_room); room_of[k]: the publish in slot k carries them (noted with the slot's other notes)
     std::atomic<fs_room_parameters*> h_room{nullptr};
     std::atomic<bool> room_of[kIrRing] = {};
-    // reverb (row f2): history rings [2][kReverbRing], staging buffers, write head
-    float* d_ring = nullptr; float* d_rev_in = nullptr; float* d_rev_cur = nullptr; float* d_rev_out = nullptr;
+    // reverb (row f2): history rings [2][kReverbRing], write head (a callback's rows are staged in fs_context::h_rev_stage / d_rev_stage)
+    float* d_ring = nullptr;
     unsigned rev_head = 0; int rev_frame = 0;
     // crossfade between successive IRs (fs_reverb_set_crossfade; the callback's own state, audio thread): fade_len L samples
     // (0: off), the callback's copies of the IRs it fades between (h_to = the newest it took, generation fade_gen),
@@ -227,7 +227,7 @@ struct fs_context {
     size_t fft_stage_floats = 0;
     hipGraphExec_t fft_graph = nullptr;
     int fft_graph_n = -1, fft_graph_l = -1;
-    // fs_reverb_process_batch (audio thread): pinned host staging and its device mirror, grown at the first call that needs more
+    // fs_reverb_process / fs_reverb_process_batch (audio thread): pinned host staging and its device mirror, grown at the first call that needs more
     // (count x frame size), freed with the context.  Up: items [count] | plain, fade, take lists [3][count] | in [count][2 frame];
     // down: out [count][2 frame] | mix [2 frame]; the device also holds the mono tails cur [count][2 frame].
     char* h_rev_stage = nullptr; char* d_rev_stage = nullptr;

@@ -411,12 +411,7 @@ void launch_trace_rays(const DeviceScene& sc, const float* o, const float* d, co
 // rays_per_wave < 64: sparse waves whose other lanes help with every closest-hit query; 64 = one ray per lane
 void launch_update_sound(const DeviceScene& sc, const SoundKParams& sp, SoundAccum* acc, int rays_per_wave, hipStream_t s);
 constexpr int kReverbRing = 65536;   // per-channel history ring (floats), matches kRevRing in the kernels
-// ir_to != nullptr: a crossfade from `ir` to `ir_to`, fade_pos samples into a fade of fade_len (fs_reverb_set_crossfade)
-void launch_reverb(const float* ir, int ir_size, float* ring, unsigned head, const float* in, float* cur, float* out,
-                   int frame, int literal_tail, hipStream_t s, const float* ir_to = nullptr, int fade_pos = 0, int fade_len = 0);
-// a crossfade starts: h_from := (1 - a) h_from + a h_to (a > 0), then h_to := ir (n samples)
-void launch_reverb_fade_start(float* h_from, float* h_to, const float* ir, int n, float a, hipStream_t s);
-// fs_reverb.hip (fs_reverb_process_batch): one descriptor per row of the call, in list order, read by every kernel of the batch.
+// fs_reverb.hip (the reverb callback): one descriptor per row of the call, in list order, read by every kernel of the callback.
 struct ReverbItem {
     const float* ir;       // the convolution's IR (h_from while a crossfade runs) ...
     const float* ir_to;    // ... and the IR it fades to (null: one convolution)
@@ -443,7 +438,8 @@ struct ReverbBatch {
 };
 // take: the rows whose crossfade starts in this callback (n_take >= 1), n = IR samples
 void launch_reverb_batch_fade_start(const ReverbItem* items, const int* take, int n_take, int n, hipStream_t s);
-// prepare + push, the convolutions of the two lists (each launched only when it has rows), the mix (when b.mix)
+// prepare (+ push, where the ring allows), the convolutions of the two lists (each launched only when it has rows), the push
+// (where it could not ride in front), the mix (when b.mix)
 void launch_reverb_batch(const ReverbBatch& b, hipStream_t s);
 void launch_add_energy(float* energy_row, int num_bins, float delay_s, float e, hipStream_t s);
 // dynamic LDS the traversal kernels of a frame need for a tree with `stack_rows` stack rows: the larger of the walk

@@ -1,19 +1,21 @@
-// fs_reverb.hip — the reverb callback of MANY sources as one set of launches (fs_reverb_process_batch, row f2).
+// fs_reverb.hip — row f2, the reverb plugin's per-callback convolution (FFrequenSeeAudioReverbPlugin::ProcessSourceAudio,
+// FrequenSeeAudioReverbPlugin.cpp:118-170, ConvolveFFT :172-213), for all rows of one audio callback as one set of launches
+// (fs_reverb_process_batch; fs_reverb_process is a callback of one row).
 //
-// fs_reverb_process (fs_aux_kernels.hip: reverb_prepare / reverb_conv / reverb_push) serves one source per call: three small
-// launches, 128 convolution workgroups on a chip of 256 CUs.  Here every kernel takes a table of per-source descriptors
-// (ReverbItem, fs_internal.hpp) and lays the sources side by side: the convolution is a grid of
-// (frame / 16 output tiles) x 2 channels x sources, a workgroup finds its source through blockIdx.z.
+// The reference zero-pads the last 47 999 + 1 024 samples and the 48 000-tap IR to 65 536 and multiplies three KissFFT spectra;
+// only output samples [47 999, 49 023) are kept, for which the circular product equals the plain convolution
+//   out[s] = sum_k IR[k] * u[47 999 + s - k].
+// On this chip 2 x 1024 x 48 000 MACs are a few microseconds of fp32 FMA, so the kernel evaluates that sum directly (no FFT, no
+// 65 536-point scratch, deterministic order): thread t owns a contiguous 192-tap slice and slides a 31-sample register window
+// over it (47 loads per 256 FMAs), partial sums meet in LDS.
 //
-// The results are the single call's TO THE BIT, so the arithmetic below is that kernel's restated, not shared (an inlined common
-// body changed a neighbouring kernel's schedule before: fs_connect_all.inc): the 16-aligned per-thread tap slices, the fmaf chain
-// over the 31-sample register window, the per-thread fade mix before the reduction, the LDS tree, the clamp.  The file is built
-// with the library's -ffp-contract=off: (1 - g) acc + g acc_to and (p + 1) / L round operation by operation, as there.
+// Every kernel takes a table of per-row descriptors (ReverbItem, fs_internal.hpp) and lays the rows side by side: the convolution
+// is a grid of (frame / 16 output tiles) x 2 channels x rows, a workgroup finds its row through blockIdx.z (one row alone is 128
+// workgroups on a chip of 256 CUs).  The file is built with the library's -ffp-contract=off: the fade mix (1 - g) acc + g acc_to
+// and (p + 1) / L round operation by operation.
 //
-// Sources that fade (two IRs, 16 more accumulators) and sources that do not are two launches over two index lists: one kernel
+// Rows that fade (two IRs, 16 more accumulators) and rows that do not are two launches over two index lists: one kernel
 // with a workgroup-uniform branch would give every workgroup the fading one's registers.
-// The ring positions a callback appends, [head, head + frame), are never among those its convolution reads, [head - tail, head)
-// (tail + frame <= 47 999 + 16 384 < 65 536), so the push rides in the prepare kernel in front of the convolution.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -27,7 +29,8 @@ constexpr int kRevOut = 16;      // outputs per workgroup
 constexpr int kRevRing = 65536;  // history ring length per channel (power of two >= 47 999)
 static_assert(kRevRing == kReverbRing, "the kernels' ring is the host's");
 
-// A crossfade starts for the sources of `take` (reverb_fade_start_kernel): h_from := (1 - a) h_from + a h_to (a > 0), h_to := ir
+// A crossfade starts for the rows of `take` (fs_reverb_set_crossfade): h_from := (1 - a) h_from + a h_to — the IR heard at the last
+// output sample of a fade that is cut short (a = p0 / L; a = 0 leaves h_from as it is) — then h_to := the device-resident IR.
 __global__ void reverb_batch_fade_start_kernel(const ReverbItem* __restrict__ items, const int* __restrict__ take, int n) {
     const ReverbItem it = items[take[blockIdx.y]];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -39,35 +42,46 @@ __global__ void reverb_batch_fade_start_kernel(const ReverbItem* __restrict__ it
     h_to[i] = it.take_ir[i];
 }
 
-// Row r of the call (blockIdx.y).  Bypassed (apply == 0): out row := in row (what the mix sums; the host copies the row itself).
-// Else reverb_prepare_kernel (the two mono tails of this callback) and reverb_push_kernel (the history ring) in one pass.
+// Row r of the call (blockIdx.y), the passes of `mode`.  kRevTails: a bypassed row (apply == 0) gets out row := in row (what the
+// mix sums; the host copies the row itself), a convolved one the two mono tails of this callback.  kRevPush: a convolved row's
+// samples enter its history ring.
+constexpr int kRevTails = 1, kRevPush = 2;
 __global__ void reverb_batch_prepare_kernel(const ReverbItem* __restrict__ items, const float* __restrict__ in_all,
-                                            float* __restrict__ cur_all, float* __restrict__ out_all, int frame, int literal) {
+                                            float* __restrict__ cur_all, float* __restrict__ out_all, int frame, int literal, int mode) {
     const int r = blockIdx.y;
     const ReverbItem it = items[r];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= frame) return;
     const float* in = in_all + (size_t)r * 2 * (size_t)frame;
     if (!it.apply) {
-        float* out = out_all + (size_t)r * 2 * (size_t)frame;
-        out[2 * i] = in[2 * i];
-        out[2 * i + 1] = in[2 * i + 1];
+        if (mode & kRevTails) {
+            float* out = out_all + (size_t)r * 2 * (size_t)frame;
+            out[2 * i] = in[2 * i];
+            out[2 * i + 1] = in[2 * i + 1];
+        }
         return;
     }
-    float* cur = cur_all + (size_t)r * 2 * (size_t)frame;
-    // RVB.cpp:147-148 copies the first `frame` floats of the INTERLEAVED buffer into both mono tails
-    cur[i] = literal ? in[i] : in[2 * i];
-    cur[frame + i] = literal ? in[i] : in[2 * i + 1];
-    // AudioTailBuffer{Left,Right}.AddSamples(in, frame, ch, 2)  RVB.cpp:144-145
-    float* ring = it.ring;
-    ring[(it.head + (unsigned)i) & (unsigned)(kRevRing - 1)] = in[2 * i];
-    ring[kRevRing + ((it.head + (unsigned)i) & (unsigned)(kRevRing - 1))] = in[2 * i + 1];
+    if (mode & kRevTails) {
+        float* cur = cur_all + (size_t)r * 2 * (size_t)frame;
+        // RVB.cpp:147-148 copies the first `frame` floats of the INTERLEAVED buffer into both mono tails
+        cur[i] = literal ? in[i] : in[2 * i];
+        cur[frame + i] = literal ? in[i] : in[2 * i + 1];
+    }
+    if (mode & kRevPush) {
+        // AudioTailBuffer{Left,Right}.AddSamples(in, frame, ch, 2)  RVB.cpp:144-145
+        float* ring = it.ring;
+        ring[(it.head + (unsigned)i) & (unsigned)(kRevRing - 1)] = in[2 * i];
+        ring[kRevRing + ((it.head + (unsigned)i) & (unsigned)(kRevRing - 1))] = in[2 * i + 1];
+    }
 }
 
-// reverb_conv_kernel<FADE> of source list[blockIdx.z]:  out[s] = sum_k IR[k] * u[tail + s - k],
+// The convolution of row list[blockIdx.z]:  out[s] = sum_k IR[k] * u[tail + s - k],
 //   u[j] = j < tail ? ring[(head - tail + j) & mask] : cur[j - tail]
 // thread t owns a contiguous 16-aligned tap slice and slides a 31-sample register window over it, partial sums meet in LDS.
-// FADE: y = (1 - g) (ir * u) + g (ir_to * u), g = (p + 1) / fade_len while p = fade_pos + s < fade_len, else 1.
+// FADE (fs_reverb_set_crossfade, its own instantiation): a second IR `ir_to` over the same register window — the u loads are
+// shared, the IR loads and FMAs double — and per output y = (1 - g) (ir * u) + g (ir_to * u), g = (p + 1) / fade_len while
+// p = fade_pos + s < fade_len, else 1.  g depends on the output only, so each thread mixes its partial sums before the reduction
+// (the sum is linear).
 template <bool FADE>
 __global__ __launch_bounds__(kBlock) void reverb_batch_conv_kernel(const ReverbItem* __restrict__ items, const int* __restrict__ list,
                                                                    int ir_size, const float* __restrict__ cur_all, int frame,
@@ -160,8 +174,14 @@ void launch_reverb_batch_fade_start(const ReverbItem* items, const int* take, in
 
 void launch_reverb_batch(const ReverbBatch& b, hipStream_t s) {
     const int tb = 256;
-    hipLaunchKernelGGL(reverb_batch_prepare_kernel, dim3((b.frame + tb - 1) / tb, b.count), dim3(tb), 0, s, b.items, b.in, b.cur, b.out,
-                       b.frame, b.literal_tail);
+    const dim3 rows((b.frame + tb - 1) / tb, b.count);
+    // A callback appends ring positions [head, head + frame) and its convolution reads [head - tail, head), tail = ir_size - 1,
+    // both modulo kRevRing: they are disjoint exactly while tail + frame <= kRevRing, and then the push rides in the prepare pass
+    // in front of the convolution (the default IR with any legal frame: 47 999 + 16 384 = 64 383 <= 65 536).  A longer IR's
+    // appended samples would land on the oldest history the convolution is about to read: there the push runs behind it.
+    const bool fused = (b.ir_size - 1) + b.frame <= kRevRing;
+    hipLaunchKernelGGL(reverb_batch_prepare_kernel, rows, dim3(tb), 0, s, b.items, b.in, b.cur, b.out, b.frame, b.literal_tail,
+                       fused ? kRevTails | kRevPush : kRevTails);
     const int tiles = (b.frame + kRevOut - 1) / kRevOut;
     if (b.n_plain > 0)
         hipLaunchKernelGGL(reverb_batch_conv_kernel<false>, dim3(tiles, 2, b.n_plain), dim3(kBlock), 0, s, b.items, b.plain, b.ir_size,
@@ -169,6 +189,8 @@ void launch_reverb_batch(const ReverbBatch& b, hipStream_t s) {
     if (b.n_fade > 0)
         hipLaunchKernelGGL(reverb_batch_conv_kernel<true>, dim3(tiles, 2, b.n_fade), dim3(kBlock), 0, s, b.items, b.fade, b.ir_size,
                            b.cur, b.frame, b.out);
+    if (!fused)
+        hipLaunchKernelGGL(reverb_batch_prepare_kernel, rows, dim3(tb), 0, s, b.items, b.in, b.cur, b.out, b.frame, b.literal_tail, kRevPush);
     if (b.mix)
         hipLaunchKernelGGL(reverb_batch_mix_kernel, dim3((2 * b.frame + tb - 1) / tb), dim3(tb), 0, s, b.out, b.count, 2 * b.frame, b.mix);
 }

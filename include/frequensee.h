@@ -571,10 +571,19 @@ int fs_save_impulse_response(fs_context* ctx, fs_source src, int32_t channel, co
  *      Private/FrequenSeeAudioReverbPlugin.cpp.  The source's most recent impulse response is used on the device. */
 #define FS_REVERB_LITERAL_TAIL 1u /* RVB.cpp:147-148 literally: the interleaved buffer's first `frame` floats feed both channels */
 int fs_reverb_init(fs_context* ctx, fs_source src, int32_t frame_size /* BufferLength, 1024 */);
-/* in/out: interleaved stereo [frame_size * 2]; apply_reverb == 0 is the bApplyReverb bypass (memcpy, RVB.cpp:128-132).
- * Audio-thread safe: runs on the context's reverb stream, reads the source's newest device-resident IR behind the
- * reconstruct that wrote it (events, exchanged under a per-source mutex held only while work is enqueued) and waits for
- * its own stream only.  fs_reverb_init / fs_reverb_release of a source must not run concurrently with its callback. */
+/* One source's callback.  in / out: interleaved stereo [frame_size * 2], host; they may be the same buffer.  Per source:
+ *  a. apply_reverb == 0 is the bApplyReverb bypass (RVB.cpp:128-132): out := in on the host; neither the device nor any state of
+ *     the source (history, write head, crossfade state) is touched.
+ *  b. Otherwise out = clamp(IR * u, -1, 1) per channel, u = the source's history followed by this block
+ *     (FS_REVERB_LITERAL_TAIL: the block as RVB.cpp:147-148 reads it), with the source's newest device-resident IR — or as
+ *     fs_reverb_set_crossfade states, where a fade length is set — and the block enters the history.
+ *  c. Audio-thread safe: runs on the context's reverb stream, reads the IR behind the reconstruct that wrote it (events,
+ *     exchanged under a per-source mutex held only while work is enqueued) and waits for its own stream only: safe against
+ *     the game thread's reconstructs and fs_set_impulse_response.  Not concurrent with fs_reverb_init / _release /
+ *     _set_crossfade of the source or another callback: ONE audio render thread runs the callbacks of a context, single and
+ *     batched — they share staging owned by the context (rule 5 below), not per-source buffers.
+ * fs_reverb_process is fs_reverb_process_batch with one row and no mix; its own checks come first, in this order: a null pointer
+ * is FS_ERR_INVALID_ARGUMENT, a bad handle FS_ERR_BAD_HANDLE, a source without fs_reverb_init FS_ERR_INVALID_ARGUMENT. */
 int fs_reverb_process(fs_context* ctx, fs_source src, const float* in, float* out, int32_t apply_reverb, uint32_t flags);
 /* The callbacks of `count` sources as ONE set of launches (the mixer's loop over ProcessSourceAudio, RVB.cpp:118-170): the
  * number of copies, kernel launches and stream synchronisations of a call does not grow with count.
@@ -582,19 +591,16 @@ int fs_reverb_process(fs_context* ctx, fs_source src, const float* in, float* ou
  *   out [count][frame_size * 2]  or NULL
  *   apply_reverb [count]         or NULL = all on; flags (FS_REVERB_LITERAL_TAIL) hold for every source of the call
  *   mix [frame_size * 2]         or NULL; out == NULL && mix == NULL is FS_ERR_INVALID_ARGUMENT
- *  1. out[i] and the state of sources[i] afterwards (history, write head, crossfade state) are, to the bit, what
- *     fs_reverb_process(ctx, sources[i], in[i], out[i], apply_reverb[i], flags) for i = 0 .. count - 1 in that order leaves, in
- *     every state of that call (crossfades included; the bypass copies the row and touches no state).  Batch and single
- *     calls may be mixed freely from one callback to the next.
+ *  1. Rules a - c above per row, in list order: out[i] and the state of sources[i] afterwards are those of rule a or b with
+ *     (sources[i], in[i], apply_reverb[i], flags), to the bit the same whether the sources are served by one call or by several
+ *     (crossfades included).  Batch and single calls may be mixed freely from one callback to the next.
  *  2. mix[j] = ((out[0][j] + out[1][j]) + out[2][j]) + ... in fp32, in list order, over the values of rule 1 (each clamped; a
  *     bypassed source contributes its input); the sum itself is not clamped.  It is computed on the device in that fixed
  *     order (reproducible); with out == NULL only mix comes back from the device.
  *  3. 1 <= count <= FS_MAX_REVERB_BATCH, every source has had fs_reverb_init, all share one frame size, no handle appears
  *     twice: otherwise FS_ERR_INVALID_ARGUMENT (FS_ERR_BAD_HANDLE for a bad handle).  A refused call changes nothing.
- *  4. The threading contract of fs_reverb_process, for every listed source: safe against the game thread's reconstructs and
- *     fs_set_impulse_response, not concurrent with fs_reverb_init / _release / _set_crossfade or another callback of a
- *     listed source.  The sources' mutexes are taken in the order the game thread takes them and held only while work is
- *     enqueued.
+ *  4. The threading contract of rule c for every listed source.  The sources' mutexes are taken in the order the game thread
+ *     takes them and held only while work is enqueued.
  *  5. Pinned staging owned by the context is grown at the FIRST call that needs more (count x frame_size); a call whose
  *     count and frame size the context has already seen allocates no device or pinned memory. */
 #define FS_MAX_REVERB_BATCH 256

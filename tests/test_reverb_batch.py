@@ -1,6 +1,8 @@
 """fs_reverb_process_batch: the reverb callbacks of many sources as one set of launches (include/frequensee.h beside
 fs_reverb_process).  The contract is the per-source loop's, to the bit: two contexts with the same sources and installed IRs,
 one driven by fs_reverb_process and one by the batch, must agree with np.array_equal in every state the single call has.
+(fs_reverb_process is a batch of one row: what these comparisons guard is the rows of one call against each other — the index
+lists, the per-row descriptors, the staging offsets.)
 Installed IRs are bit-equal in two contexts; traced ones are not (the histogram's atomics are unordered), so the traced test
 compares with a float64 restatement of the crossfade rules instead (CrossfadeModel, restated from test_reverb_crossfade.py)."""
 import ctypes as C
@@ -477,3 +479,70 @@ def test_audio_thread_against_game_thread(pkg, scene_factory, fade):
     assert not errors, errors
     assert counts == [CALLBACKS, TICKS] and 0.0 < peak[0] <= 1.0
     ctx.close()
+
+
+# ---- IR lengths that fill the history ring -------------------------------------------------------------------------------------
+# A callback appends ring positions [head, head + frame) and its convolution reads [head - tail, head), tail = ir_len - 1, both
+# modulo 65 536: once tail + frame > 65 536 the appended samples alias the oldest history u[0 ..], so the push must run behind
+# the convolution.  (tail + frame): 65 536, the last shape whose push may ride in front; 65 537, one past it; the tail is the
+# whole ring.  A clobbered u[0] meets the oldest tap, ir[-1] = 0.1: about 0.03 on 0.3-sigma input.
+RING_SHAPES = [(65057, 480), (65058, 480), (65537, 17)]
+
+
+def conv_f64(x, h, n):
+    """the first n samples of the linear convolution x * h in float64 (test_config_shapes.py)"""
+    L = 1
+    while L < len(x) + len(h):
+        L *= 2
+    return np.fft.irfft(np.fft.rfft(x, L) * np.fft.rfft(h, L), L)[:n]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ir_len,frame", RING_SHAPES)
+def test_ir_lengths_that_fill_the_ring(pkg, ir_len, frame):
+    """3 sources with their own IRs of ir_len samples (a 1 s context at ir_len Hz, as test_config_shapes.py::test_reverb_convolution;
+    source 1 with a crossfade enabled and a constant IR), six batch callbacks alternating the literal tail: every row is the
+    float64 convolution within that test's tolerance, and equals a second context driven by fs_reverb_process to the bit."""
+    S, calls = 3, 6
+    rng = np.random.default_rng(ir_len + frame)
+    n = np.arange(ir_len)
+    irs = []
+    for _ in range(S):
+        ir = (rng.normal(0, 1, ir_len) * np.exp(-n / (ir_len / 3.0)) * 0.004).astype(np.float32)
+        ir[0] = 0.25
+        ir[-1] = 0.1                                                    # the oldest tap reads the far end of the ring
+        irs.append(ir)
+    x = np.clip(rng.normal(0, 0.3, (calls, S, 2 * frame)), -1, 1).astype(np.float32)
+
+    def run(batch):
+        ctx = pkg.Context(num_bands=1, sample_rate=ir_len, simulated_duration=1.0)
+        assert ctx.num_samples == ir_len
+        srcs = [ctx.create_source((0.0, 0.0, 0.0)) for _ in range(S)]
+        for s, ir in zip(srcs, irs):
+            ctx.set_impulse_response(s, ir)
+            ctx.reverb_init(s, frame)
+        ctx.reverb_set_crossfade(srcs[1], 2 * frame + 1)
+        y = np.empty_like(x)
+        for c in range(calls):
+            if batch:
+                y[c] = ctx.reverb_process_batch(srcs, x[c], literal_tail=bool(c % 2))
+            else:
+                for i, s in enumerate(srcs):
+                    y[c, i] = ctx.reverb_process(s, x[c, i], literal_tail=bool(c % 2))
+        ctx.close()
+        return y
+
+    y = run(True)
+    for i in range(S):
+        h = irs[i].astype(np.float64)
+        for ch in range(2):
+            stream = x[:, i, ch::2].astype(np.float64).reshape(-1)
+            want = conv_f64(stream, h, stream.size).reshape(calls, frame)
+            for c in range(1, calls, 2):   # RVB.cpp:147-148: the current block is the interleaved buffer's first `frame` floats
+                d = x[c, i, :frame].astype(np.float64) - x[c, i, ch::2].astype(np.float64)
+                want[c] += conv_f64(d, h[:frame], frame)
+            want = np.clip(want, -1.0, 1.0)
+            err = np.abs(y[:, i, ch::2] - want)
+            print(f"ir_len {ir_len} frame {frame} source {i} channel {ch}: max error {err.max():.3e}, peak {np.abs(want).max():.3f}")
+            assert err.max() <= 5e-5 * max(1.0, np.abs(want).max()), (i, ch, np.unravel_index(np.argmax(err), err.shape))
+    assert np.array_equal(y, run(False))

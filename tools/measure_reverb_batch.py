@@ -1,22 +1,27 @@
 #!/usr/bin/env python3
 """Row f2 for many sources: host wall time of one audio callback that serves S sources, as the per-source loop of
-fs_reverb_process and as one fs_reverb_process_batch.
+fs_reverb_process and as one fs_reverb_process_batch — on this build and on a library built from the PARENT commit, whose
+numbers are the baselines and whose output bits this build must reproduce.
 
   * S in {1, 2, 8, 32, 128}, 1024 stereo frames, 48 000-tap installed IRs, three cases each: no crossfade; crossfade (2560
     samples) with constant IRs; crossfade with a new IR for every source before every callback (the installs are not timed);
-  * three series: the loop on a library built from the PARENT commit (--parent-lib, a second build tree: tools/build_variant.sh
-    in a checkout of the parent), the same loop on this build (the parent's code path: it must sit inside the parent's
-    spread) and the batch on this build.  Every series runs in a process of its own, the series alternate in rounds, and a
-    callback's time is the host clock around the call (which ends in the stream synchronise the audio thread waits for);
-  * per series the median and the 10th / 90th percentile over all timed callbacks (>= 500 after a warm-up), and the ratio of
-    the parent loop's median to the batch's.
+  * four series: the loop and the batch on a library built from the PARENT commit (--parent-lib, a second build tree:
+    tools/build_variant.sh in a checkout of the parent), the loop and the batch on this build.  Every series runs in a process
+    of its own, the series alternate in rounds, and a callback's time is the host clock around the call (which ends in the
+    stream synchronise the audio thread waits for);
+  * per series the median and the 10th / 90th percentile over all timed callbacks (>= 500 after a warm-up).  What must hold per
+    entry: this build's loop <= 1.07 x the parent's loop, this build's batch <= 1.07 x the parent's batch (medians; 7 % is the
+    spread already seen between sessions for the single call, 0.100 vs 0.107 ms);
+  * every series draws the same inputs and installs the same IRs (one seed), and returns a SHA-256 over all outputs of its
+    timed callbacks per size and case: this build's loop and batch must both equal the parent's loop (bits_equal_parent).
 
 Without a GPU the tool fails (the context cannot be created); nothing falls back.
 --profile-run: a short run of batch callbacks for S = 1 and S = 128 (plain, then fading with a new IR every callback), for
 `rocprofv3 --kernel-trace --stats -- python tools/measure_reverb_batch.py --profile-run` (launch counts and kernel times).
-usage: python tools/measure_reverb_batch.py --parent-lib PATH [--callbacks 500] [--rounds 2] [--out profiles/reverb_batch.json]"""
+usage: python tools/measure_reverb_batch.py --parent-lib PATH [--callbacks 500] [--rounds 2] [--out profiles/reverb_unified.json]"""
 import argparse
 import ctypes as C
+import hashlib
 import json
 import os
 import subprocess
@@ -33,7 +38,7 @@ FRAME = 1024
 FADE = 2560
 SIZES = (1, 2, 8, 32, 128)
 CASES = ("no_crossfade", "crossfade_constant_ir", "crossfade_new_ir_every_callback")
-SERIES = ("parent_loop", "this_loop", "this_batch")
+SERIES = ("parent_loop", "parent_batch", "this_loop", "this_batch")
 
 
 def noise_ir(rng, n):
@@ -86,7 +91,8 @@ class Lib:
 
 
 def series_times(lib, batch, callbacks, warmup, sizes=SIZES, cases=CASES):
-    """{S: {case: [seconds per callback]}}: sources are created once per case (3 x 128), the first S of them serve size S"""
+    """{S: {case: {"times": [seconds per callback], "sha256": of the timed callbacks' outputs}}}: sources are created once per
+    case (3 x 128), the first S of them serve size S; inputs and IRs come from one seed, whatever the series"""
     rng = np.random.default_rng(0)
     irs = [noise_ir(rng, lib.n) for _ in range(4)]
     res = {}
@@ -104,7 +110,7 @@ def series_times(lib, batch, callbacks, warmup, sizes=SIZES, cases=CASES):
         out = np.empty_like(blk)
         for case in cases:
             srcs = np.array(pools[case][:S], np.int32)
-            times = []
+            times, sha = [], hashlib.sha256()
             for i in range(warmup + callbacks):
                 if case == "crossfade_new_ir_every_callback":
                     for s in srcs:
@@ -123,7 +129,8 @@ def series_times(lib, batch, callbacks, warmup, sizes=SIZES, cases=CASES):
                     lib.ok(rcs)
                 if i >= warmup:
                     times.append(dt)
-            res.setdefault(str(S), {})[case] = times
+                    sha.update(out.tobytes())
+            res.setdefault(str(S), {})[case] = {"times": times, "sha256": sha.hexdigest()}
     return res
 
 
@@ -173,16 +180,19 @@ def main():
         sys.exit("--parent-lib: a libfrequensee.so built from the parent commit is the baseline of this measurement")
     per_round = (a.callbacks + a.rounds - 1) // a.rounds
     raw = {name: {} for name in SERIES}
+    bits = {name: {} for name in SERIES}   # [S][case]: the rounds' digests, in order
     for r in range(a.rounds):
-        for name, path, batch in (("parent_loop", a.parent_lib, False), ("this_loop", this_lib, False), ("this_batch", this_lib, True)):
+        for name, path, batch in (("parent_loop", a.parent_lib, False), ("parent_batch", a.parent_lib, True),
+                                  ("this_loop", this_lib, False), ("this_batch", this_lib, True)):
             cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--lib", path, "--callbacks", str(per_round), "--warmup", str(a.warmup)]
             p = subprocess.run(cmd + (["--batch"] if batch else []), capture_output=True, text=True, timeout=900)
             line = [x for x in p.stdout.splitlines() if x.startswith("RESULT ")]
             if p.returncode or not line:
                 sys.exit(f"{name} (round {r}) failed with status {p.returncode}:\n{p.stderr[-2000:]}")
             for S, cases in json.loads(line[0][7:]).items():
-                for case, ts in cases.items():
-                    raw[name].setdefault(S, {}).setdefault(case, []).extend(ts)
+                for case, got in cases.items():
+                    raw[name].setdefault(S, {}).setdefault(case, []).extend(got["times"])
+                    bits[name].setdefault(S, {}).setdefault(case, []).append(got["sha256"])
             print(f"round {r} {name} done", file=sys.stderr, flush=True)
     rec = {"callback": f"{FRAME} stereo frames, 48000-tap installed IRs, crossfade {FADE} samples", "rounds": a.rounds, "sizes": {}}
     holds = True
@@ -190,11 +200,14 @@ def main():
         row = {}
         for case in CASES:
             e = {name: stats(raw[name][str(S)][case]) for name in SERIES}
-            e["parent_loop_over_batch"] = e["parent_loop"]["median_ms"] / e["this_batch"]["median_ms"]
             e["this_loop_over_parent_loop"] = e["this_loop"]["median_ms"] / e["parent_loop"]["median_ms"]
-            # what must hold: faster than the parent's loop at S >= 2; at S = 1 within 7 % of the single call (the spread
-            # already seen between sessions for that call, 0.100 vs 0.107 ms)
-            e["holds"] = bool(e["parent_loop_over_batch"] > 1.0 if S >= 2 else e["this_batch"]["median_ms"] <= 1.07 * e["parent_loop"]["median_ms"])
+            e["this_batch_over_parent_batch"] = e["this_batch"]["median_ms"] / e["parent_batch"]["median_ms"]
+            want = bits["parent_loop"][str(S)][case]
+            e["sha256"] = want
+            e["bits_equal_parent"] = {name: bits[name][str(S)][case] == want for name in ("this_loop", "this_batch")}
+            # what must hold: each path within 7 % of the PARENT's same path, and the parent loop's bits from both
+            e["holds"] = bool(e["this_loop_over_parent_loop"] <= 1.07 and e["this_batch_over_parent_batch"] <= 1.07
+                              and all(e["bits_equal_parent"].values()))
             holds = holds and e["holds"]
             row[case] = e
         rec["sizes"][str(S)] = row
