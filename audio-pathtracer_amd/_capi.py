@@ -50,7 +50,7 @@ EXPORTS = [
     "fs_sound_params_default", "fs_scene_set_objects", "fs_update_sound", "fs_get_occlusion_attenuation",
     "fs_save_array_to_file", "fs_load_float_array", "fs_save_impulse_response",
     "fs_reverb_init", "fs_reverb_process", "fs_reverb_process_batch", "fs_reverb_release", "fs_reverb_set_crossfade",
-    "fs_apply_material_fd", "fs_energy_handoff", "fs_scene_update_triangles", "fs_scene_refit", "fs_set_impulse_response",
+    "fs_apply_material_fd", "fs_energy_handoff", "fs_scene_update_triangles", "fs_scene_refit", "fs_scene_set_object_transforms", "fs_set_impulse_response",
     "fs_scene_commit_fast", "fs_comm_unique_id", "fs_comm_init", "fs_comm_attach", "fs_comm_detach", "fs_comm_info", "fs_comm_enable_oneshot", "fs_shard_range",
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
     "fs_set_band_edges", "fs_source_set_orientation", "fs_source_set_directivity", "fs_get_room_parameters",
@@ -240,6 +240,7 @@ def load():
         "fs_energy_device_ptr": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "fs_scene_update_triangles": (C.c_int, [vp, i32, i32, f32p]),
         "fs_scene_refit": (C.c_int, [vp]),
+        "fs_scene_set_object_transforms": (C.c_int, [vp, C.c_void_p, f32p, i32]),
         "fs_set_impulse_response": (C.c_int, [vp, i32, f32p, i32]),
         "fs_energy_handoff": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]),
         "fs_reconstruct_impulse_response": (C.c_int, [vp, i32, C.POINTER(Params)]),

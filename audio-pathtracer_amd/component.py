@@ -192,6 +192,19 @@ class Context:
     def refit(self):
         self.check(self.lib.fs_scene_refit(self.h))
 
+    def set_object_transforms(self, ids, matrices):
+        """fs_scene_set_object_transforms: every listed actor (ids of set_scene's object_ids) placed at its row-major 3 x 4
+        matrix applied to its REST triangles; matrices [n][3][4] or [n][12].  Absolute, not cumulative; enqueues only"""
+        o = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1)
+        if m.shape[0] != 12 * o.shape[0]:
+            raise ValueError("matrices must hold 12 floats per id")
+        self.check(self.lib.fs_scene_set_object_transforms(self.h, o.ctypes.data if o.size else None,
+                                                           m.ctypes.data if m.size else None, o.shape[0]))
+
+    def set_object_transform(self, object_id, m):
+        self.set_object_transforms([int(object_id)], np.asarray(m, dtype=np.float32).reshape(1, 12))
+
     def set_listener(self, xyz):
         self.check(self.lib.fs_listener_set_position(self.h, _f3(xyz)))
 

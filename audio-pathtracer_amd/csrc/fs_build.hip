@@ -213,12 +213,16 @@ using BuildInfo = DeviceBuildInfo;   // build outputs the host reads back in one
 // One workgroup, breadth-first.  wide_src[w] = binary node the wide node w spans, wide_start[w] = first leaf-order
 // position of its triangles, need[w] = pending stack entries when a traversal arrives at w having hit every child on
 // the way (the bound the LDS stack is sized with).  pos_of[j] = leaf-order position of sorted triangle j.
+// The nodes of a level are numbered in the order of their parents and, under one parent, of its children (a block-wide
+// prefix sum over the parents' inner children): the same triangles give the same node array, byte for byte, every time.
 __global__ __launch_bounds__(kCollapseBlock) void collapse_kernel(int N, Bvh2 b, const int* __restrict__ root_ptr,
                                                                   NodeQ4* __restrict__ nodes, int* __restrict__ wide_src,
                                                                   int* __restrict__ wide_start, int* __restrict__ need,
                                                                   int* __restrict__ pos_of, BuildInfo* __restrict__ info,
                                                                   int max_nodes) {
     __shared__ int s_begin, s_end, s_next, s_need, s_fail;
+    typedef hipcub::BlockScan<int, kCollapseBlock> Scan;
+    __shared__ typename Scan::TempStorage s_scan;
     if (threadIdx.x == 0) {
         s_begin = 0; s_end = 1; s_next = 1; s_need = 0; s_fail = 0;
         wide_src[0] = N > 1 ? *root_ptr : -1;     // a one-triangle scene (no root_ptr): the root's only child is the leaf
@@ -231,11 +235,14 @@ __global__ __launch_bounds__(kCollapseBlock) void collapse_kernel(int N, Bvh2 b,
     int level = 0;
     while (true) {
         const int begin = s_begin, end = s_end;
-        for (int w = begin + (int)threadIdx.x; w < end; w += kCollapseBlock) {
+        for (int base = begin; base < end; base += kCollapseBlock) {
+            const int w = base + (int)threadIdx.x;
+            const bool live = w < end;
             int child[4];
             int n = 0;
-            const int src = wide_src[w];
-            if (src < 0) {
+            const int src = live ? wide_src[w] : -1;
+            if (!live) {
+            } else if (src < 0) {
                 child[n++] = ~0;                                   // leaf 0
             } else {
                 child[n++] = b.left[src];
@@ -256,12 +263,19 @@ __global__ __launch_bounds__(kCollapseBlock) void collapse_kernel(int N, Bvh2 b,
                     ++n;
                 }
             }
+            int inner = 0;                                         // children that become nodes of the next level
+            for (int i = 0; i < n; ++i) inner += child[i] >= 0 && b.count[child[i]] > 2;
+            int slot, total;
+            Scan(s_scan).ExclusiveSum(inner, slot, total);
+            slot += s_next;
+            __syncthreads();
+            if (threadIdx.x == 0) s_next += total;
             NodeQ4 q{};
-            const int my_need = need[w] + (n - 1);
-            atomicMax(&s_need, my_need);
+            const int my_need = live ? need[w] + (n - 1) : 0;
+            if (live) atomicMax(&s_need, my_need);
             uint32_t lo4 = 0, hi4 = 0;
-            int start = wide_start[w];
-            for (int c = 0; c < 4; ++c) {
+            int start = live ? wide_start[w] : 0;
+            for (int c = 0; live && c < 4; ++c) {
                 uint32_t ql = 255, qh = 0;                         // empty slot: lo > hi (refit keeps it empty)
                 q.child[c] = -1;
                 if (c < n) {
@@ -276,9 +290,9 @@ __global__ __launch_bounds__(kCollapseBlock) void collapse_kernel(int N, Bvh2 b,
                         pos_of[~b.left[cn]] = start;
                         pos_of[~b.right[cn]] = start + 1;
                     } else {
-                        const int slot = atomicAdd(&s_next, 1);
                         if (slot < max_nodes) { wide_src[slot] = cn; wide_start[slot] = start; need[slot] = my_need; q.child[c] = slot; }
                         else { s_fail = 1; q.child[c] = ~0; }
+                        ++slot;
                     }
                     start += cnt;
                 }
@@ -287,7 +301,8 @@ __global__ __launch_bounds__(kCollapseBlock) void collapse_kernel(int N, Bvh2 b,
             }
             q.lox = q.loy = q.loz = lo4;
             q.hix = q.hiy = q.hiz = hi4;
-            nodes[w] = q;
+            if (live) nodes[w] = q;
+            __syncthreads();                                       // s_next and the scan's storage, for the next chunk
         }
         __syncthreads();
         ++level;

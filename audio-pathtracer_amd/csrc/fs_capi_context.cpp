@@ -641,6 +641,7 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->d_gather) (void)hipFree(ctx->d_gather);
         for (hipEvent_t e : ctx->free_events) (void)hipEventDestroy(e);
         free_scene(ctx);
+        free_object_moves(ctx);
         free_state(ctx);
         if (ctx->walk.queue_head) (void)hipFree(ctx->walk.queue_head);
         if (ctx->d_sound) (void)hipFree(ctx->d_sound);

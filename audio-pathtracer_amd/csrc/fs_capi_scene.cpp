@@ -2,6 +2,8 @@
 // moving geometry (C ABI: include/frequensee.h; RegisterGeometry / UAcousticMaterial, ARTS.h:99-100, MAT.h:22-33).
 #include "fs_context.hpp"
 
+static int update_triangles(fs_context* ctx, int32_t first, int32_t count, const float* xyz, bool new_rest);
+
 namespace fsi {
 
 // A background build that is no longer wanted: the builder polls the flag and gives up; the thread itself is joined by
@@ -21,6 +23,72 @@ void join_refine_threads(fs_context* ctx) {
     ctx->refine_threads.clear();
 }
 
+// ---- fs_scene_set_object_transforms: the host side of the rest pose ---------------------------------------------------
+// one vertex by a row-major 3 x 4 matrix, every operation rounded (this file is built with -ffp-contract=off, as
+// transform_objects_kernel is): ((r0 x + r1 y) + r2 z) + t
+static inline void transform_vertex(const float* a, const float* r, float* w) {
+    const float x = r[0], y = r[1], z = r[2];
+    for (int k = 0; k < 3; ++k) w[k] = ((a[4 * k] * x + a[4 * k + 1] * y) + a[4 * k + 2] * z) + a[4 * k + 3];
+}
+
+// h_xyz = the world positions: the objects moved by transform since it was last brought up to date get their newest matrix
+// applied to their rest positions (what the device records already hold)
+void sync_world_positions(fs_context* ctx) {
+    ObjectMoves* mv = ctx->moves;
+    if (!mv || mv->stale_list.empty()) return;
+    for (uint32_t slot : mv->stale_list) {
+        const float* a = mv->m.data() + 12 * (size_t)slot;
+        for (uint32_t j = mv->off[slot]; j < mv->off[slot + 1]; ++j) {
+            const size_t t = mv->idx[j];
+            for (int v = 0; v < 3; ++v) transform_vertex(a, mv->rest.data() + 9 * t + 3 * v, ctx->h_xyz.data() + 9 * t + 3 * v);
+        }
+        mv->stale[slot] = 0;
+    }
+    mv->stale_list.clear();
+}
+
+// the largest |coordinate| transform_objects_kernel has written, folded into ctx->amax where the padding is computed or
+// reported: waits for the one 4-byte copy enqueued behind the newest kernel
+static hipError_t fold_moved_amax(fs_context* ctx) {
+    ObjectMoves* mv = ctx->moves;
+    if (!mv || !mv->amax_pending) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(mv->ev_amax);
+    if (e != hipSuccess) return e;
+    float v;
+    std::memcpy(&v, mv->h_amax, sizeof(float));
+    ctx->amax = std::max(ctx->amax, v);
+    mv->amax_pending = false;
+    return hipSuccess;
+}
+
+// every commit: the lists and the device copies describe the tree that has just been replaced (the rest pose stays)
+static void object_moves_after_commit(fs_context* ctx) {
+    ObjectMoves* mv = ctx->moves;
+    if (!mv) return;
+    mv->lists_valid = false;
+    mv->on_device = false;
+    mv->amax_pending = false;    // (the commit has drained the stream and taken amax from h_xyz)
+    mv->stale_list.clear();
+    if (mv->d_amax) (void)hipMemsetAsync(mv->d_amax, 0, sizeof(uint32_t), ctx->stream);
+}
+
+void free_object_moves(fs_context* ctx) {
+    ObjectMoves* mv = ctx->moves;
+    if (!mv) return;
+    if (mv->d_rest) (void)hipFree(mv->d_rest);
+    if (mv->d_idx) (void)hipFree(mv->d_idx);
+    if (mv->d_amax) (void)hipFree(mv->d_amax);
+    if (mv->h_amax) (void)hipHostFree(mv->h_amax);
+    if (mv->ev_amax) (void)hipEventDestroy(mv->ev_amax);
+    for (ObjectMoves::Set& st : mv->set) {
+        if (st.h) (void)hipHostFree(st.h);
+        if (st.d) (void)hipFree(st.d);
+        if (st.ev) (void)hipEventDestroy(st.ev);
+    }
+    delete mv;
+    ctx->moves = nullptr;
+}
+
 // fs_scene_commit_progressive: once the background build has finished, the next call that traces anything swaps its tree
 // in — held frames finish first (they were traced through the old tree's arrays), the stream drains, the records are
 // uploaded; triangles moved since the snapshot get their current positions and a refit.
@@ -36,9 +104,9 @@ int maybe_install_refined(fs_context* ctx) {
     const int rc = fs_scene_commit(ctx);
     ctx->prebuilt = nullptr;
     if (rc) return rc;
-    if (moved) {
+    if (moved) {   // (the commit has brought h_xyz up to the world positions; the rest pose is not touched)
         const std::vector<float> now = ctx->h_xyz;
-        return fs_scene_update_triangles(ctx, 0, ctx->T, now.data());
+        return update_triangles(ctx, 0, ctx->T, now.data(), false);
     }
     return FS_OK;
 }
@@ -55,6 +123,10 @@ int fs_scene_set_triangles(fs_context* ctx, const float* xyz, const uint16_t* ma
     for (size_t i = 0; i < 9 * (size_t)T; ++i)
         if (!std::isfinite(xyz[i])) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
     cancel_refine(ctx);   // a background build of the previous triangle set is of no use any more
+    if (ctx->moves) {     // a new rest pose: h_xyz itself until the next fs_scene_set_object_transforms
+        ctx->moves->rest.clear(); ctx->moves->rest_amax = 0.0;
+        ctx->moves->stale_list.clear(); ctx->moves->lists_valid = false;
+    }
     ctx->h_xyz.assign(xyz, xyz + 9 * (size_t)T);
     if (mat_id) ctx->h_mat.assign(mat_id, mat_id + T);
     else ctx->h_mat.assign((size_t)T, (uint16_t)FS_NO_MATERIAL);
@@ -182,6 +254,7 @@ static int refresh_coop_nodes(fs_context* ctx, bool topology_changed) {
 }
 
 static int finish_commit(fs_context* ctx, size_t scene_bytes) {
+    object_moves_after_commit(ctx);
     ctx->amax = 0.f;
     for (float v : ctx->h_xyz) ctx->amax = std::max(ctx->amax, std::fabs(v));
     ctx->scene.nodes = ctx->d_nodes;
@@ -229,6 +302,7 @@ int fs_scene_commit(fs_context* ctx) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
     FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
+    sync_world_positions(ctx);   // objects moved by transform: the tree is built over where they are now
     if (!ctx->prebuilt) cancel_refine(ctx);
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -325,6 +399,7 @@ int fs_scene_commit_fast(fs_context* ctx) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
     FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
+    sync_world_positions(ctx);   // objects moved by transform: the tree is built over where they are now
     cancel_refine(ctx);
     if (ctx->T < 1 || ctx->comm) return fs_scene_commit(ctx);   // empty scene / sharded run: the one build rank 0 broadcasts
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
@@ -433,7 +508,8 @@ int fs_scene_refine_wait(fs_context* ctx) {
 }
 
 // ---- moving geometry (row f4): ECC_WorldDynamic movers are seen by the next trace (ARTS.cpp:333-336) -------------
-int fs_scene_update_triangles(fs_context* ctx, int32_t first, int32_t count, const float* xyz) {
+// new_rest: the positions also become the triangles' rest positions (the public call; not the re-apply after a swap)
+static int update_triangles(fs_context* ctx, int32_t first, int32_t count, const float* xyz, bool new_rest) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
     FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
@@ -451,14 +527,163 @@ int fs_scene_update_triangles(fs_context* ctx, int32_t first, int32_t count, con
         FS_HIP(ctx, hipMalloc((void**)&ctx->d_move, sizeof(float) * 9 * (size_t)count));
         ctx->move_cap = (size_t)count;
     }
+    ObjectMoves* mv = new_rest ? ctx->moves : nullptr;
+    if (mv) sync_world_positions(ctx);   // an object's pending matrix must not be applied over these positions later
     std::memcpy(ctx->h_xyz.data() + 9 * (size_t)first, xyz, sizeof(float) * 9 * (size_t)count);   // a later commit stays consistent
+    if (mv && !mv->rest.empty()) {
+        std::memcpy(mv->rest.data() + 9 * (size_t)first, xyz, sizeof(float) * 9 * (size_t)count);
+        for (size_t i = 0; i < 9 * (size_t)count; ++i) mv->rest_amax = std::max(mv->rest_amax, (double)std::fabs(xyz[i]));
+    }
     if (ctx->refine) ctx->moved_since_refine = true;   // the background tree was built from the old positions
     for (size_t i = 0; i < 9 * (size_t)count; ++i) ctx->amax = std::max(ctx->amax, std::fabs(xyz[i]));
     // the staging buffer may still be read by the previous update's kernel: same stream, so ordered
     FS_HIP(ctx, hipMemcpyAsync(ctx->d_move, xyz, sizeof(float) * 9 * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
     launch_update_triangles(ctx->d_tris, ctx->d_tris48, ctx->d_tri_nrm, ctx->d_leaf_pos, first, count, ctx->d_move, ctx->stream);
     FS_HIP(ctx, hipGetLastError());
+    if (mv && mv->on_device)   // the device's copy of the rest pose follows
+        FS_HIP(ctx, hipMemcpyAsync(mv->d_rest + 9 * (size_t)first, ctx->d_move, sizeof(float) * 9 * (size_t)count, hipMemcpyDeviceToDevice, ctx->stream));
     FS_HIP(ctx, hipStreamSynchronize(ctx->stream));   // xyz is the caller's memory
+    ctx->refit_pending = true;
+    return FS_OK;
+}
+
+int fs_scene_update_triangles(fs_context* ctx, int32_t first, int32_t count, const float* xyz) {
+    return update_triangles(ctx, first, count, xyz, true);
+}
+
+// the objects' lists of input indices from h_obj, in order of first appearance (host only)
+static void build_object_lists(fs_context* ctx, ObjectMoves* mv) {
+    const size_t T = (size_t)ctx->T;
+    mv->slot_of.clear();
+    std::vector<uint32_t> slot((size_t)T), n;
+    for (size_t t = 0; t < T; ++t) {
+        const auto it = mv->slot_of.emplace(ctx->h_obj[t], (uint32_t)n.size());
+        if (it.second) n.push_back(0);
+        slot[t] = it.first->second;
+        ++n[slot[t]];
+    }
+    const size_t slots = n.size();
+    mv->off.assign(slots + 1, 0);
+    for (size_t k = 0; k < slots; ++k) mv->off[k + 1] = mv->off[k] + n[k];
+    mv->idx.resize(T);
+    std::vector<uint32_t> at(mv->off.begin(), mv->off.end() - 1);
+    for (size_t t = 0; t < T; ++t) mv->idx[at[slot[t]]++] = (uint32_t)t;
+    mv->m.assign(12 * slots, 0.f);
+    mv->stale.assign(slots, 0);
+    mv->seen.assign(slots, 0);
+    mv->stale_list.clear();
+    mv->stale_list.reserve(slots);
+    mv->lists_valid = true;
+}
+
+int fs_scene_set_object_transforms(fs_context* ctx, const uint32_t* object_ids, const float* m, int32_t count) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!object_ids || !m || count < 1) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_scene_set_object_transforms: null array or count < 1");
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    FS_FLUSH(ctx);   // pipelined frames: they were traced through the old positions
+    if (!ctx->committed) return ctx->fail(FS_ERR_NOT_COMMITTED, "scene not committed");
+    if (ctx->T < 1 || ctx->h_obj.size() != (size_t)ctx->T)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_scene_set_object_transforms: no object ids registered (fs_scene_set_objects)");
+    const size_t n = (size_t)count;
+    for (size_t i = 0; i < 12 * n; ++i)
+        if (!std::isfinite(m[i])) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_scene_set_object_transforms: non-finite matrix entry");
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    if (!ctx->moves) ctx->moves = new ObjectMoves();
+    ObjectMoves* mv = ctx->moves;
+    if (mv->rest.empty()) {   // the first call since fs_scene_set_triangles: nothing has been transformed yet, h_xyz is the rest pose
+        mv->rest = ctx->h_xyz;
+        float a = 0.f;
+        for (float v : mv->rest) a = std::max(a, std::fabs(v));
+        mv->rest_amax = (double)a;
+    }
+    if (!mv->lists_valid) build_object_lists(ctx, mv);
+    // ---- the refusals: nothing has changed up to here but caches
+    if (mv->call_slots.size() < n) mv->call_slots.resize(n);
+    ++mv->call;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const auto it = mv->slot_of.find(object_ids[i]);
+        if (it == mv->slot_of.end()) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_scene_set_object_transforms: an id owns no committed triangle");
+        const uint32_t slot = it->second;
+        if (mv->seen[slot] == mv->call) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_scene_set_object_transforms: an id appears twice");
+        mv->seen[slot] = mv->call;
+        mv->call_slots[i] = slot;
+        total += mv->off[slot + 1] - mv->off[slot];
+        for (int k = 0; k < 3; ++k) {   // could a transformed coordinate leave fp32?
+            const float* r = m + 12 * i + 4 * k;
+            const double reach = (std::fabs((double)r[0]) + std::fabs((double)r[1]) + std::fabs((double)r[2])) * mv->rest_amax + std::fabs((double)r[3]);
+            if (reach > 3e38) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_scene_set_object_transforms: a transformed coordinate could leave fp32");
+        }
+    }
+    // ---- resources: once per context, per commit, per larger count
+    if (!mv->d_amax) {
+        FS_HIP(ctx, hipMalloc((void**)&mv->d_amax, sizeof(uint32_t)));
+        FS_HIP(ctx, hipMemsetAsync(mv->d_amax, 0, sizeof(uint32_t), ctx->stream));
+        FS_HIP(ctx, hipHostMalloc((void**)&mv->h_amax, sizeof(uint32_t), hipHostMallocDefault));
+        *mv->h_amax = 0;
+        FS_HIP(ctx, hipEventCreateWithFlags(&mv->ev_amax, hipEventDisableTiming));
+        for (ObjectMoves::Set& st : mv->set) FS_HIP(ctx, hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    }
+    const size_t T = (size_t)ctx->T;
+    if (!mv->on_device) {
+        if (mv->dev_tris < T) {
+            FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (mv->d_rest) (void)hipFree(mv->d_rest);
+            if (mv->d_idx) (void)hipFree(mv->d_idx);
+            mv->d_rest = nullptr; mv->d_idx = nullptr; mv->dev_tris = 0;
+            FS_HIP(ctx, hipMalloc((void**)&mv->d_rest, sizeof(float) * 9 * T));
+            FS_HIP(ctx, hipMalloc((void**)&mv->d_idx, sizeof(uint32_t) * T));
+            mv->dev_tris = T;
+        }
+        FS_HIP(ctx, hipMemcpyAsync(mv->d_rest, mv->rest.data(), sizeof(float) * 9 * T, hipMemcpyHostToDevice, ctx->stream));
+        FS_HIP(ctx, hipMemcpyAsync(mv->d_idx, mv->idx.data(), sizeof(uint32_t) * T, hipMemcpyHostToDevice, ctx->stream));
+        FS_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (pageable sources; once per commit)
+        mv->on_device = true;
+    }
+    if (n > mv->cap) {
+        FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (ObjectMoves::Set& st : mv->set) {
+            if (st.h) (void)hipHostFree(st.h);
+            if (st.d) (void)hipFree(st.d);
+            st.h = nullptr; st.d = nullptr; st.used = false;
+        }
+        mv->cap = 0;
+        const size_t bytes = sizeof(uint32_t) * (14 * n + 1);
+        for (ObjectMoves::Set& st : mv->set) {
+            FS_HIP(ctx, hipHostMalloc((void**)&st.h, bytes, hipHostMallocDefault));
+            FS_HIP(ctx, hipMalloc((void**)&st.d, bytes));
+        }
+        mv->cap = n;
+    }
+    ObjectMoves::Set& st = mv->set[mv->next];
+    mv->next = (mv->next + 1) % ObjectMoves::kSets;
+    if (st.used && hipEventQuery(st.ev) != hipSuccess) FS_HIP(ctx, hipEventSynchronize(st.ev));   // the call before last has not run yet
+    // ---- the call: matrices | prefix | start into the pinned block, one copy, one launch, the 4-byte copy behind it
+    float* hm = reinterpret_cast<float*>(st.h);
+    uint32_t* hp = reinterpret_cast<uint32_t*>(st.h) + 12 * n;
+    uint32_t* hs = hp + (n + 1);
+    std::memcpy(hm, m, sizeof(float) * 12 * n);
+    hp[0] = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t slot = mv->call_slots[i];
+        hp[i + 1] = hp[i] + (mv->off[slot + 1] - mv->off[slot]);
+        hs[i] = mv->off[slot];
+        std::memcpy(mv->m.data() + 12 * (size_t)slot, m + 12 * i, sizeof(float) * 12);
+        if (!mv->stale[slot]) { mv->stale[slot] = 1; mv->stale_list.push_back(slot); }
+    }
+    if (ctx->refine) ctx->moved_since_refine = true;   // the background tree was built from the old positions
+    const size_t bytes = sizeof(uint32_t) * (14 * n + 1);
+    FS_HIP(ctx, hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    const float* dm = reinterpret_cast<const float*>(st.d);
+    const uint32_t* dp = reinterpret_cast<const uint32_t*>(st.d) + 12 * n;
+    launch_transform_objects(ctx->d_tris, ctx->d_tris48, ctx->d_tri_nrm, ctx->d_leaf_pos, mv->d_rest, mv->d_idx, dp, dp + (n + 1), dm,
+                             (int)n, (uint32_t)total, mv->d_amax, ctx->stream);
+    FS_HIP(ctx, hipGetLastError());
+    FS_HIP(ctx, hipEventRecord(st.ev, ctx->stream));
+    st.used = true;
+    FS_HIP(ctx, hipMemcpyAsync(mv->h_amax, mv->d_amax, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(ctx, hipEventRecord(mv->ev_amax, ctx->stream));
+    mv->amax_pending = true;
     ctx->refit_pending = true;
     return FS_OK;
 }
@@ -471,6 +696,7 @@ int fs_scene_refit(fs_context* ctx) {
     ctx->refit_pending = false;
     if (ctx->bvh.nodes.empty()) return FS_OK;
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    FS_HIP(ctx, fold_moved_amax(ctx));   // objects moved by transform: the device knows how far
     const float pad = std::max(std::max(0.01f, ctx->amax * 3.8146973e-06f), ctx->bvh.pad);   // as fs_bvh.cpp; never shrinks
     launch_refit(ctx->d_nodes, ctx->d_tris, ctx->d_node_box, ctx->bvh.level_begin.data(),
                  (int)ctx->bvh.level_begin.size() - 1, pad, ctx->stream);
@@ -493,6 +719,7 @@ __attribute__((visibility("default"))) int fs_debug_scene_snapshot(fs_context* c
     if (!ctx->committed) return ctx->fail(FS_ERR_NOT_COMMITTED, "scene not committed");
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    FS_HIP(ctx, fold_moved_amax(ctx));
     const size_t nodes = ctx->bvh.nodes.size(), T = (size_t)ctx->T;
     const size_t levels = ctx->bvh.level_begin.empty() ? 0 : ctx->bvh.level_begin.size() - 1;
     uint32_t hdr[12] = {(uint32_t)nodes, (uint32_t)T, (uint32_t)levels, (uint32_t)ctx->bvh.stack_need, 0, 0,

@@ -23,6 +23,8 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <unordered_map>
+#include <vector>
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and prototypes only: librccl is opened at run time (fs_comm_*), never linked
@@ -168,6 +170,40 @@ struct RefineJob {
     std::atomic<bool> cancel{false};   // a newer registration made this build useless: the builder gives up at its next check
 };
 
+// fs_scene_set_object_transforms (fs_capi_scene.cpp): everything the call keeps, allocated by the first call of a context.
+// The REST pose (the positions last given by fs_scene_set_triangles / fs_scene_update_triangles) lives beside
+// fs_context::h_xyz, which holds the WORLD positions; objects whose newest matrix h_xyz does not reflect yet are `stale`
+// and brought up to date by sync_world_positions when a commit, the swap of a progressive commit or
+// fs_scene_update_triangles needs them (the call itself does work proportional to the objects it lists).
+struct ObjectMoves {
+    static constexpr int kSets = 2;        // staging sets in rotation: a second call does not overwrite what the first one's kernel reads
+    std::vector<float> rest;               // [T][9], input order (empty until the first call after fs_scene_set_triangles)
+    double rest_amax = 0.0;                // largest |coordinate| the rest pose has held (grows only)
+    // the objects' lists of input indices (CSR over h_obj), built at the first call after a commit; a slot = one object id
+    bool lists_valid = false;
+    std::unordered_map<uint32_t, uint32_t> slot_of;
+    std::vector<uint32_t> off, idx;        // off [slots + 1] into idx [T]
+    std::vector<float> m;                  // [slots][12]: the newest matrix of every stale object
+    std::vector<uint8_t> stale;
+    std::vector<uint32_t> stale_list, call_slots;
+    std::vector<uint64_t> seen;            // the call that last listed the slot (an id twice in one call)
+    uint64_t call = 0;
+    // device copies of rest and idx, uploaded at the first call after a commit
+    bool on_device = false;
+    size_t dev_tris = 0;
+    float* d_rest = nullptr;
+    uint32_t* d_idx = nullptr;
+    // bit pattern of the largest |coordinate| the kernel has written since the commit, and its pinned host copy
+    uint32_t* d_amax = nullptr;
+    uint32_t* h_amax = nullptr;
+    hipEvent_t ev_amax = nullptr;
+    bool amax_pending = false;             // a copy into h_amax is enqueued that fs_context::amax has not seen
+    // per call: matrices [n][12] | prefix [n + 1] | start [n], pinned host block -> device block on the compute stream
+    struct Set { char* h = nullptr; char* d = nullptr; hipEvent_t ev = nullptr; bool used = false; } set[kSets];
+    size_t cap = 0;                        // objects per call the sets have room for
+    int next = 0;
+};
+
 struct fs_context {
     fs_config cfg{};
     int num_bins = 0, num_samples = 0;
@@ -215,6 +251,7 @@ struct fs_context {
     size_t build_cap = 0;
     size_t fast_cap_tris = 0;         // triangles the scene arrays of the last fast commit have room for (0: not reusable)
     bool refit_pending = false;
+    ObjectMoves* moves = nullptr;     // fs_scene_set_object_transforms: null until its first call
     DeviceScene scene{};
     // ApplyMaterialFD work buffers (row f4), sized for the largest block seen
     int fft_n = -1;              // log2 of the size the twiddle table was built for
@@ -441,6 +478,7 @@ hipError_t wait_energy_readers(fs_context* ctx, Source* s, int buf);   // ... or
 hipError_t handoff_energy(fs_context* ctx, Source* s);        // compute stream -> tail stream
 void free_source(fs_context* ctx, Source* s);
 void free_scene(fs_context* ctx);
+void free_object_moves(fs_context* ctx);   // fs_capi_scene.cpp (the caller has synchronised the compute stream)
 void free_state(fs_context* ctx);
 hipEvent_t take_event(fs_context* ctx);
 void resolve_timings(fs_context* ctx);

@@ -464,6 +464,12 @@ void launch_oneshot_reduce(const OneShotView& v, void* buffer, int words, bool u
 // first (node_box = scratch [num_nodes][2] float4 holding each node's fp32 bounds).
 void launch_update_triangles(Tri64* tris, Tri48* packed, float4* nrm, const uint32_t* leaf_pos, int first, int count,
                              const float* xyz, hipStream_t s);
+// fs_scene_set_object_transforms: every triangle of the n listed objects placed at its matrix applied to its rest position
+// (rest [T][9] input order; csr / start: the objects' lists of input indices; prefix [n + 1]: running triangle counts;
+// *amax_bits: bit pattern of the largest |coordinate| written, kept up by atomicMax)
+void launch_transform_objects(Tri64* tris, Tri48* packed, float4* nrm, const uint32_t* leaf_pos, const float* rest,
+                              const uint32_t* csr, const uint32_t* prefix, const uint32_t* start, const float* m, int n,
+                              uint32_t total, uint32_t* amax_bits, hipStream_t s);
 void launch_pack_triangles(const Tri64* tris, int count, Tri48* packed, float4* nrm, hipStream_t s);
 void launch_refit(NodeQ4* nodes, const Tri64* tris, float4* node_box, const int32_t* level_begin, int levels, float pad,
                   hipStream_t s);

@@ -18,16 +18,10 @@ namespace {
 
 constexpr int kRefitBlock = 256;
 
-// new vertex positions -> Tri64 {v0, e1, e2, unit normal}; material, input index and actor id are kept.
-// Same fp32 operation order as the host build (fs_bvh.cpp) — the normal is part of the hit-normal spec.
-__global__ __launch_bounds__(kRefitBlock) void update_tris_kernel(Tri64* __restrict__ tris, Tri48* __restrict__ packed,
-                                                                  float4* __restrict__ nrm,
-                                                                  const uint32_t* __restrict__ leaf_pos, int first,
-                                                                  int count, const float* __restrict__ xyz) {
-    const int i = blockIdx.x * kRefitBlock + threadIdx.x;
-    if (i >= count) return;
-    const float* p = xyz + 9 * (size_t)i;
-    const uint32_t pos = leaf_pos[first + i];
+// new vertex positions p[9] -> Tri64 {v0, e1, e2, unit normal} at leaf-order position pos; material, input index and
+// actor id are kept.  Same fp32 operation order as the host build (fs_bvh.cpp) — the normal is part of the hit-normal spec.
+__device__ __forceinline__ void write_record(Tri64* __restrict__ tris, Tri48* __restrict__ packed, float4* __restrict__ nrm,
+                                             uint32_t pos, const float* p) {
     Tri64& r = tris[pos];
     const float e1x = p[3] - p[0], e1y = p[4] - p[1], e1z = p[5] - p[2];
     const float e2x = p[6] - p[0], e2y = p[7] - p[1], e2z = p[8] - p[2];
@@ -42,6 +36,58 @@ __global__ __launch_bounds__(kRefitBlock) void update_tris_kernel(Tri64* __restr
     r.d = make_float4(nx * inv, ny * inv, nz * inv, 0.f);
     packed[pos] = Tri48{r.a, r.b, r.c};
     nrm[pos] = r.d;
+}
+
+__global__ __launch_bounds__(kRefitBlock) void update_tris_kernel(Tri64* __restrict__ tris, Tri48* __restrict__ packed,
+                                                                  float4* __restrict__ nrm,
+                                                                  const uint32_t* __restrict__ leaf_pos, int first,
+                                                                  int count, const float* __restrict__ xyz) {
+    const int i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= count) return;
+    const float* p = xyz + 9 * (size_t)i;
+    const uint32_t pos = leaf_pos[first + i];
+    write_record(tris, packed, nrm, pos, p);
+}
+
+// fs_scene_set_object_transforms: one thread per (listed object, triangle of it) pair, all objects of the call in one
+// launch.  prefix[n + 1] = running sum of the listed objects' triangle counts (the thread finds its object by binary
+// search), start[i] = where object i's input indices begin in the per-object lists `csr`, m[i] = its row-major 3 x 4
+// matrix.  A vertex is ((r0 x + r1 y) + r2 z) + t, every operation rounded (-ffp-contract=off): what numpy computes on
+// float32 arrays.  The largest |coordinate| written goes into *amax_bits (non-negative floats order as unsigned
+// integers): one atomic per wave.
+__global__ __launch_bounds__(kRefitBlock) void transform_objects_kernel(Tri64* __restrict__ tris, Tri48* __restrict__ packed,
+                                                                        float4* __restrict__ nrm,
+                                                                        const uint32_t* __restrict__ leaf_pos,
+                                                                        const float* __restrict__ rest,
+                                                                        const uint32_t* __restrict__ csr,
+                                                                        const uint32_t* __restrict__ prefix,
+                                                                        const uint32_t* __restrict__ start,
+                                                                        const float* __restrict__ m, int n, uint32_t total,
+                                                                        uint32_t* __restrict__ amax_bits) {
+    const uint32_t g = blockIdx.x * (uint32_t)kRefitBlock + threadIdx.x;
+    float mx = 0.f;
+    if (g < total) {
+        int lo = 0, hi = n;                        // the last i with prefix[i] <= g (prefix[0] = 0, prefix[n] = total > g)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (prefix[mid] <= g) lo = mid; else hi = mid;
+        }
+        const uint32_t tri = csr[start[lo] + (g - prefix[lo])];
+        const float* r = rest + 9 * (size_t)tri;
+        const float* a = m + 12 * (size_t)lo;
+        float p[9];
+        for (int v = 0; v < 3; ++v) {
+            const float x = r[3 * v], y = r[3 * v + 1], z = r[3 * v + 2];
+            for (int k = 0; k < 3; ++k) {
+                const float w = ((a[4 * k] * x + a[4 * k + 1] * y) + a[4 * k + 2] * z) + a[4 * k + 3];
+                p[3 * v + k] = w;
+                mx = fmaxf(mx, fabsf(w));
+            }
+        }
+        write_record(tris, packed, nrm, leaf_pos[tri], p);
+    }
+    for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
+    if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(amax_bits, __float_as_uint(mx));
 }
 
 // the kernels' view of the records (fs_internal.hpp: Tri48 + normals) from the authoring records
@@ -236,6 +282,14 @@ void launch_update_triangles(Tri64* tris, Tri48* packed, float4* nrm, const uint
     if (count <= 0) return;
     hipLaunchKernelGGL(update_tris_kernel, dim3((unsigned)((count + kRefitBlock - 1) / kRefitBlock)), dim3(kRefitBlock),
                        0, s, tris, packed, nrm, leaf_pos, first, count, xyz);
+}
+
+void launch_transform_objects(Tri64* tris, Tri48* packed, float4* nrm, const uint32_t* leaf_pos, const float* rest,
+                              const uint32_t* csr, const uint32_t* prefix, const uint32_t* start, const float* m, int n,
+                              uint32_t total, uint32_t* amax_bits, hipStream_t s) {
+    if (n <= 0 || total == 0) return;
+    hipLaunchKernelGGL(transform_objects_kernel, dim3((total + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, s,
+                       tris, packed, nrm, leaf_pos, rest, csr, prefix, start, m, n, total, amax_bits);
 }
 
 void launch_pack_triangles(const Tri64* tris, int count, Tri48* packed, float4* nrm, hipStream_t s) {

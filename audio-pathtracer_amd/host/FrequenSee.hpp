@@ -217,6 +217,14 @@ public:
         }
         throw std::runtime_error("FrequenSee: geometry component is not registered");
     }
+    // The same for a mover the engine describes by its component transform: M = row-major 3 x 4 {r00 r01 r02 tx, ...} applied
+    // to the triangles the component REGISTERED (`Comp->Triangles` stays the rest mesh and is not read here).  Absolute, not
+    // cumulative; 48 bytes, no upload of vertices and no wait.  The component's Actor id must be its own.
+    void GeometryMoved(const AcousticGeometryComponent* Comp, const float M[12]) {
+        Commit();
+        const uint32_t Id = Comp->Actor;
+        Check(fs_scene_set_object_transforms(Ctx_, &Id, M, 1));
+    }
     void Check(int rc) const { if (rc != FS_OK) throw std::runtime_error(std::string("FrequenSee: ") + fs_last_error(Ctx_)); }
 
     fs_params Params;                                   // the constants of AudioRayTracingSubsystem.cpp:282-284, 362-413

@@ -42,7 +42,7 @@
  * run-time scene changes, the rows SURVEY.md 8(f) ranks next (text interchange, reverb, material filter), measurement
  * and tools.  A host can ignore all of it and still be correct; it is there for throughput and for the tests —
  *   EXTENDED: fs_context_advice fs_scene_commit_fast fs_scene_commit_progressive fs_scene_refine_pending
- *             fs_scene_refine_wait fs_scene_update_triangles fs_scene_refit
+ *             fs_scene_refine_wait fs_scene_update_triangles fs_scene_refit fs_scene_set_object_transforms
  *             fs_compute_energy_response_async fs_compute_energy_response_batch_async
  *             fs_reconstruct_impulse_response_async fs_reconstruct_impulse_response_batch_async fs_synchronize fs_submit
  *             fs_set_pipelining fs_set_walk_stages fs_set_frames_per_launch fs_set_band_edges
@@ -280,6 +280,39 @@ int fs_scene_refine_wait(fs_context* ctx);
  * automatically by the next trace.  Results equal those of a fresh fs_scene_commit of the moved geometry. */
 int fs_scene_update_triangles(fs_context* ctx, int32_t first, int32_t count, const float* xyz /* [count][3][3] */);
 int fs_scene_refit(fs_context* ctx);
+/* Moving actors by transform (row f4).  m[i] is a row-major 3 x 4 affine matrix {r00 r01 r02 tx, r10 r11 r12 ty,
+ * r20 r21 r22 tz}: "actor object_ids[i] is now at this transform" — 48 bytes per actor instead of 36 per triangle, one
+ * launch for all movers of a tick, and no wait.
+ *   Rest pose.  The rest position of a triangle is the position last given for it by fs_scene_set_triangles or
+ * fs_scene_update_triangles (which places its triangles at the given world positions, as ever, and makes those their rest
+ * positions).  The call is absolute, not cumulative: every triangle whose id (fs_scene_set_objects) is object_ids[i] is
+ * placed at m[i] applied to its REST position, whatever transform the object had before.  Objects not listed stay where
+ * they are.
+ *   Arithmetic, in fp32, each operation rounded, no fused multiply-add: x' = ((r00 x + r01 y) + r02 z) + tx, likewise y'
+ * and z', for each of the three vertices; the record (v0, e1, e2, unit normal) is then derived from the three new vertices
+ * exactly as fs_scene_update_triangles derives it.  numpy on float32 arrays computes the same bits.  A mirroring or
+ * shearing matrix needs no special case.  The identity gives the rest positions back as numbers (a -0.0f coordinate may
+ * come back as +0.0f).
+ *   Equivalence.  After the call the committed scene is the scene that fs_scene_update_triangles calls carrying those
+ * transformed positions would have left, bit for bit, before the refit (records new, boxes old) and after it (box padding
+ * included).  The refit is pending and runs before the next trace; fs_scene_refit runs it now.
+ *   Later commits.  fs_scene_commit, fs_scene_commit_fast and fs_scene_commit_progressive without a new
+ * fs_scene_set_triangles (and the swap of a progressive commit) build over the CURRENT world positions and keep the rest
+ * pose: a later transform still maps the rest pose.  fs_scene_set_triangles defines a new rest pose.
+ *   Errors.  FS_ERR_INVALID_ARGUMENT: object_ids or m NULL, count < 1, a matrix entry not finite, an id twice in the call,
+ * an id that owns no committed triangle, no object ids registered (fs_scene_set_objects(NULL): "every triangle its own
+ * actor" has no ids to name), or a transformed coordinate that could leave fp32 — decided from the matrix and the largest
+ * rest coordinate c the scene has held, in double: (|r_i0| + |r_i1| + |r_i2|) c + |t_i| > 3e38 for some row i.
+ * FS_ERR_NOT_COMMITTED before a commit.  A refused call changes nothing.
+ *   Cost.  The caller's arrays are free when the call returns.  Host work is proportional to count, not to the number of
+ * triangles.  In the steady state — a count the context has seen before, at most one call between two traced frames — the
+ * call neither allocates nor waits for the device.  The first call after a commit uploads the rest positions and the
+ * per-object triangle lists once.  A context that never calls it allocates nothing.
+ *   Ordering.  Held frames (fs_set_pipelining) finish first, as for every scene call.  Sharded contexts: every rank makes
+ * the same call, as with fs_scene_update_triangles.
+ *   Not promised: tracing SPEED after large motion.  A refit keeps the tree's topology, so a door swung by 90 degrees sits
+ * in inflated boxes until the next fs_scene_commit_progressive.  Results never depend on it. */
+int fs_scene_set_object_transforms(fs_context* ctx, const uint32_t* object_ids, const float* m /* [count][12] */, int32_t count);
 
 /* ---- sources and listener: RegisterSource/UnRegisterSource (ARTS.h:103-104, ARTS.cpp:45-53),
  *      GetActorLocation of the source owner / the player pawn (ARTS.cpp:287) ------------------------- */
