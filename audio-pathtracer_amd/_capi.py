@@ -49,7 +49,7 @@ EXPORTS = [
     "fs_set_profiling", "fs_set_profiling_interval", "fs_get_stats", "fs_reset_stats", "fs_get_pipeline_counters", "fs_get_streams",
     "fs_sound_params_default", "fs_scene_set_objects", "fs_update_sound", "fs_get_occlusion_attenuation",
     "fs_save_array_to_file", "fs_load_float_array", "fs_save_impulse_response",
-    "fs_reverb_init", "fs_reverb_process", "fs_reverb_process_batch", "fs_reverb_release", "fs_reverb_set_crossfade",
+    "fs_reverb_init", "fs_reverb_process", "fs_reverb_process_batch", "fs_reverb_release", "fs_reverb_set_crossfade", "fs_reverb_set_engine",
     "fs_apply_material_fd", "fs_energy_handoff", "fs_scene_update_triangles", "fs_scene_refit", "fs_scene_set_object_transforms", "fs_set_impulse_response",
     "fs_scene_commit_fast", "fs_comm_unique_id", "fs_comm_init", "fs_comm_attach", "fs_comm_detach", "fs_comm_info", "fs_comm_enable_oneshot", "fs_shard_range",
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
@@ -61,6 +61,8 @@ ERR_COMM = 8
 ERR_OVERFLOW = 9
 REVERB_LITERAL_TAIL = 1
 MAX_REVERB_BATCH = 256
+REVERB_ENGINE_DIRECT = 0
+REVERB_ENGINE_PARTITIONED = 1
 
 
 class SoundParams(C.Structure):
@@ -278,6 +280,7 @@ def load():
         "fs_reverb_process_batch": (C.c_int, [vp, C.c_void_p, i32, f32p, f32p, C.c_void_p, C.c_uint32, f32p]),
         "fs_reverb_release": (C.c_int, [vp, i32]),
         "fs_reverb_set_crossfade": (C.c_int, [vp, i32, i32]),
+        "fs_reverb_set_engine": (C.c_int, [vp, i32, i32]),
         "fs_apply_material_fd": (C.c_int, [vp, f32p, i32, f32p, f32p, f32p, i32, f32p, f32p, f32p]),
         "fs_comm_unique_id": (C.c_int, [vp, C.c_size_t]),
         "fs_comm_init": (C.c_int, [vp, vp, C.c_size_t]),

@@ -413,6 +413,12 @@ class Context:
         switch; include/frequensee.h fs_reverb_set_crossfade)"""
         self.check(self.lib.fs_reverb_set_crossfade(self.h, src, int(samples)))
 
+    def reverb_set_engine(self, src, engine):
+        """the engine the source's next reverb_init gives it: _capi.REVERB_ENGINE_DIRECT (the default, tap by tap) or
+        _capi.REVERB_ENGINE_PARTITIONED (partitioned FFT convolution: no limit from the history ring, a cost that hardly
+        grows with the IR; include/frequensee.h fs_reverb_set_engine)"""
+        self.check(self.lib.fs_reverb_set_engine(self.h, src, int(engine)))
+
     def apply_material_fd(self, in_buffer, absorption, transmission, scattering):
         """UMaterialAcousticProcessor::ApplyMaterialFD (MAP.cpp:8-107) -> (specular, diffuse, transmitted)"""
         x = np.ascontiguousarray(in_buffer, dtype=np.float32).reshape(-1)
@@ -736,6 +742,10 @@ class FrequenSeeAudioReverbPlugin:
     def SetCrossfade(self, component: FrequenSeeAudioComponent, samples):
         """not in the reference: fade each new impulse response in over `samples` output samples (0: abrupt switch)"""
         self.ctx.reverb_set_crossfade(component._src, samples)
+
+    def SetEngine(self, component: FrequenSeeAudioComponent, engine):
+        """not in the reference: the convolution engine of the source's next OnInitSource (_capi.REVERB_ENGINE_*)"""
+        self.ctx.reverb_set_engine(component._src, engine)
 
 
 class MaterialAcousticProcessor:

@@ -1,21 +1,40 @@
 // fs_capi_reverb.cpp — row f2, the reverb plugin's per-callback convolution (RVB.cpp:74-213) behind the C ABI: per-source set-up
-// (fs_reverb_init / _set_crossfade / _release) and the audio callback.  There is ONE callback path, reverb_rows: a list of rows
-// served by one set of launches (fs_reverb.hip); fs_reverb_process is that list with one row.
+// (fs_reverb_init / _set_engine / _set_crossfade / _release) and the audio callback.  There is ONE callback path, reverb_rows: a
+// list of rows served by one set of launches (fs_reverb.hip, and fs_reverb_part.hip for the rows of the partitioned engine);
+// fs_reverb_process is that list with one row.
+#include <cmath>
+
 #include "fs_context.hpp"
 
 namespace {
 
-// fs_reverb_set_crossfade: the callback's two IR copies, once the source has a reverb and a fade length
-int alloc_fade(fs_context* ctx, Source* s) {
-    const size_t bytes = sizeof(float) * (size_t)ctx->num_samples;
-    if (!s->d_fade_from) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_from, bytes));
+bool partitioned(const Source* s) { return s->rev_engine == FS_REVERB_ENGINE_PARTITIONED; }
+
+// fs_reverb_set_crossfade: the callback's two IR copies, once the source has a reverb and a fade length — impulse responses for
+// the direct engine, partition spectra for the partitioned one, which needs the one it convolves (h_to) without a fade too
+// (both == false)
+int alloc_fade(fs_context* ctx, Source* s, bool both) {
+    const size_t bytes = partitioned(s) ? sizeof(float2) * ((size_t)s->part_K << s->part_n) : sizeof(float) * (size_t)ctx->num_samples;
+    if (both && !s->d_fade_from) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_from, bytes));
     if (!s->d_fade_to) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_to, bytes));
+    return FS_OK;
+}
+
+// the partitioned engine's twiddle table of N = 1 << n, in double on the host (as fs_apply_material_fd's); init time only
+int part_twiddles(fs_context* ctx, int n) {
+    if (ctx->d_rev_tw[n]) return FS_OK;
+    const size_t half = (size_t)1 << (n - 1);
+    std::vector<float2> w(half);
+    const double step = -2.0 * M_PI / (double)(half * 2);
+    for (size_t k = 0; k < half; ++k) w[k] = make_float2((float)std::cos(step * (double)k), (float)std::sin(step * (double)k));
+    FS_HIP(ctx, hipMalloc((void**)&ctx->d_rev_tw[n], sizeof(float2) * half));
+    FS_HIP(ctx, hipMemcpy(ctx->d_rev_tw[n], w.data(), sizeof(float2) * half, hipMemcpyHostToDevice));
     return FS_OK;
 }
 
 // The staging of one callback (fs_context::h_rev_stage / d_rev_stage), every block 256-byte aligned
 struct RevStageLayout {
-    size_t items, lists, in, up_bytes;      // host and device, the same offsets: what goes up in one copy
+    size_t items, pitems, lists, in, up_bytes;   // host and device, the same offsets: what goes up in one copy
     size_t h_out, h_mix, host_bytes;        // host: what comes back
     size_t d_cur, d_out, d_mix, dev_bytes;  // device: out | mix adjacent, one copy back
 };
@@ -24,8 +43,9 @@ RevStageLayout rev_stage_layout(int count, int frame) {
     const size_t rows = sizeof(float) * 2 * (size_t)frame * (size_t)count, row = sizeof(float) * 2 * (size_t)frame;
     RevStageLayout l;
     l.items = 0;
-    l.lists = rev_align(sizeof(ReverbItem) * (size_t)count);
-    l.in = l.lists + rev_align(sizeof(int) * 3 * (size_t)count);
+    l.pitems = rev_align(sizeof(ReverbItem) * (size_t)count);
+    l.lists = l.pitems + rev_align(sizeof(ReverbPartItem) * (size_t)count);
+    l.in = l.lists + rev_align(sizeof(int) * 6 * (size_t)count);
     l.up_bytes = l.in + rows;
     l.h_out = rev_align(l.up_bytes);
     l.h_mix = l.h_out + rows;   // (adjacent to out: rows is a multiple of 8 bytes)
@@ -37,6 +57,11 @@ RevStageLayout rev_stage_layout(int count, int frame) {
     return l;
 }
 
+// the bytes of Source::d_ring: the direct engine's two history rings, or the partitioned engine's state block
+size_t reverb_state_bytes(const Source* s) {
+    return partitioned(s) ? sizeof(float2) * part_state_elems(s->part_n, s->part_K) : sizeof(float) * 2 * kReverbRing;
+}
+
 const char* const kNoFadeBuffers = "the crossfade's impulse-response buffers are missing: call fs_reverb_init again";
 
 // One convolved source's step of a callback, under its ir_mu.  The callback has its own stream: it is never queued behind a traced
@@ -45,11 +70,16 @@ const char* const kNoFadeBuffers = "the crossfade's impulse-response buffers are
 // caller records ev_rev behind the launch that reads d_ir_mono, still under the lock).  With a crossfade (fs_reverb_set_crossfade)
 // the callback convolves its own copies of the IR: it reads d_ir_mono only when a newer IR is there (ir_gen), once, into h_to —
 // only then does it wait for the write and make the next one wait for it.  *takes: this callback is such a one.
-int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbItem& it, bool* takes) {
+// The partitioned engine (pit is the row's descriptor then, and `it` says only whose row it is) convolves spectra of its own with
+// or without a crossfade, so it takes in the same way in both cases: H_to from d_ir_mono, when a newer IR is there.
+int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbItem& it, ReverbPartItem& pit, bool* takes) {
     it.apply = 1;
+    it.engine = s->rev_engine;
+    const bool part = partitioned(s);
     const bool xfade = s->fade_len > 0;
-    const bool tk = *takes = xfade && (!s->fade_primed || s->ir_gen != s->fade_gen);
-    if ((!xfade || tk) && s->last_rec >= 0) {
+    const bool own = xfade || part;   // the callback convolves copies of its own
+    const bool tk = *takes = own && (!s->fade_primed || s->ir_gen != s->fade_gen);
+    if ((!own || tk) && s->last_rec >= 0) {
         const int buf = s->last_rec;
         // (a finished reconstruct needs no barrier packet on the stream: S of them are most of a short batch)
         bool done = false;
@@ -61,22 +91,33 @@ int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbIte
     }
     if (tk) {
         float a = 0.0f;
-        if (s->fade_primed) {   // a fade from what is heard now: h_to alone, or the mix at the last output sample of a running fade
+        if (xfade && s->fade_primed) {   // a fade from what is heard now: h_to alone, or the mix at the last output sample of a running fade
             if (s->fading) a = (float)s->fade_pos / (float)s->fade_len;
             else std::swap(s->d_fade_from, s->d_fade_to);
             s->fading = true;
             s->fade_pos = 0;
         }
-        it.take_from = s->d_fade_from; it.take_to = s->d_fade_to; it.take_ir = s->d_ir_mono; it.take_a = a;
+        if (part) { pit.take_from = (float2*)s->d_fade_from; pit.take_to = (float2*)s->d_fade_to; pit.take_ir = s->d_ir_mono; pit.take_a = a; }
+        else { it.take_from = s->d_fade_from; it.take_to = s->d_fade_to; it.take_ir = s->d_ir_mono; it.take_a = a; }
         s->fade_primed = true;
         s->fade_gen = s->ir_gen;
     }
-    if (!xfade || tk) s->rev_recorded = true;
-    it.ring = s->d_ring;
-    it.head = s->rev_head;
-    if (!xfade) it.ir = s->d_ir_mono;
-    else if (s->fading) { it.ir = s->d_fade_from; it.ir_to = s->d_fade_to; it.fade_pos = s->fade_pos; it.fade_len = s->fade_len; }
-    else it.ir = s->d_fade_to;
+    if (!own || tk) s->rev_recorded = true;
+    if (part) {
+        pit.active = 1;
+        pit.state = (float2*)s->d_ring;
+        pit.head = s->rev_head;
+        pit.slot = s->part_slot;
+        if (s->fading) { pit.h = (const float2*)s->d_fade_from; pit.h_to = (const float2*)s->d_fade_to; pit.fade_pos = s->fade_pos; pit.fade_len = s->fade_len; }
+        else pit.h = (const float2*)s->d_fade_to;
+        if (++s->part_slot == s->part_K) s->part_slot = 0;
+    } else {
+        it.ring = s->d_ring;
+        it.head = s->rev_head;
+        if (!xfade) it.ir = s->d_ir_mono;
+        else if (s->fading) { it.ir = s->d_fade_from; it.ir_to = s->d_fade_to; it.fade_pos = s->fade_pos; it.fade_len = s->fade_len; }
+        else it.ir = s->d_fade_to;
+    }
     s->rev_head += (unsigned)frame;
     if (s->fading && (s->fade_pos += frame) >= s->fade_len) s->fading = false;   // complete: h_from := h_to, one convolution again
     return FS_OK;
@@ -107,8 +148,11 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
     }
     char* hs = ctx->h_rev_stage; char* ds = ctx->d_rev_stage;
     ReverbItem* items = (ReverbItem*)(hs + l.items);
+    ReverbPartItem* pitems = (ReverbPartItem*)(hs + l.pitems);
     int* plain = (int*)(hs + l.lists); int* fade = plain + count; int* take = fade + count;
-    int n_plain = 0, n_fade = 0, n_take = 0;
+    int* pplain = take + count; int* pfade = pplain + count; int* ptake = pfade + count;   // the partitioned engine's three
+    int n_plain = 0, n_fade = 0, n_take = 0, n_pplain = 0, n_pfade = 0, n_ptake = 0, n_bypass = 0;
+    const Source* part_src = nullptr;
     float* h_in = (float*)(hs + l.in);
     for (int32_t i = 0; i < count; ++i)   // (a bypassed row goes up only for the mix)
         if (mix || !apply_reverb || apply_reverb[i])
@@ -122,13 +166,21 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
             if (!apply_reverb || apply_reverb[i]) locks.emplace_back(srcs[i]->ir_mu);
         for (int32_t i = 0; i < count; ++i) {
             std::memset(&items[i], 0, sizeof(ReverbItem));
-            if (apply_reverb && !apply_reverb[i]) continue;   // the bypass touches no state
+            std::memset(&pitems[i], 0, sizeof(ReverbPartItem));
+            if (apply_reverb && !apply_reverb[i]) { ++n_bypass; continue; }   // the bypass touches no state
             bool takes = false;
-            const int rc = reverb_step(ctx, srcs[i], rs, frame, items[i], &takes);
+            const int rc = reverb_step(ctx, srcs[i], rs, frame, items[i], pitems[i], &takes);
             if (rc) return rc;
-            if (takes) take[n_take++] = i;
-            if (items[i].ir_to) fade[n_fade++] = i;
-            else plain[n_plain++] = i;
+            if (pitems[i].active) {
+                part_src = srcs[i];
+                if (takes) ptake[n_ptake++] = i;
+                if (pitems[i].h_to) pfade[n_pfade++] = i;
+                else pplain[n_pplain++] = i;
+            } else {
+                if (takes) take[n_take++] = i;
+                if (items[i].ir_to) fade[n_fade++] = i;
+                else plain[n_plain++] = i;
+            }
         }
         FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, rs));
         const ReverbItem* d_items = (const ReverbItem*)(ds + l.items);
@@ -139,6 +191,19 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
             for (int k = 0; k < n_take; ++k) FS_HIP(ctx, hipEventRecord(srcs[take[k]]->ev_rev, rs));
         }
         ReverbBatch b{};
+        if (part_src) {   // (one frame size and one context: N and K are those of every partitioned row)
+            b.pitems = (const ReverbPartItem*)(ds + l.pitems);
+            b.part.plain = d_plain + 3 * count; b.part.n_plain = n_pplain;
+            b.part.fade = d_plain + 4 * count; b.part.n_fade = n_pfade;
+            b.part.n = part_src->part_n; b.part.K = part_src->part_K; b.part.frame = frame; b.part.ir_size = ctx->num_samples;
+            b.part.W = ctx->d_rev_tw[part_src->part_n];
+            if (n_ptake) {
+                launch_reverb_part_take(b.pitems, d_plain + 5 * count, n_ptake, b.part, rs);
+                FS_HIP(ctx, hipGetLastError());
+                for (int k = 0; k < n_ptake; ++k) FS_HIP(ctx, hipEventRecord(srcs[ptake[k]]->ev_rev, rs));
+            }
+        }
+        b.n_direct = n_plain + n_fade + n_bypass;
         b.items = d_items;
         b.plain = d_plain; b.n_plain = n_plain;
         b.fade = d_plain + count; b.n_fade = n_fade;
@@ -180,7 +245,11 @@ int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
     if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
     Source* s = get_source(ctx, h);
     if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-    if (frame_size < 1 || frame_size > 16384 || ctx->num_samples - 1 > kReverbRing)
+    const bool part = s->rev_engine_next == FS_REVERB_ENGINE_PARTITIONED;
+    if (part) {
+        if (frame_size < 16 || frame_size > 2048 || ctx->num_samples > 1048576)
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "partitioned reverb: frame size outside 16 .. 2048 / IR longer than 1 048 576 samples");
+    } else if (frame_size < 1 || frame_size > 16384 || ctx->num_samples - 1 > kReverbRing)
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad reverb frame size / IR longer than the history ring");
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     // Reconstructs on the compute stream record an event for the callbacks only for a source that has a reverb: the ones
@@ -189,14 +258,36 @@ int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
     FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     FS_HIP(ctx, hipStreamSynchronize(ctx->rev_stream));
     if (s->d_ring) (void)hipFree(s->d_ring);
-    if (s->d_fade_from) { (void)hipFree(s->d_fade_from); (void)hipFree(s->d_fade_to); }
+    if (s->d_fade_from) (void)hipFree(s->d_fade_from);
+    if (s->d_fade_to) (void)hipFree(s->d_fade_to);
     s->d_ring = s->d_fade_from = s->d_fade_to = nullptr;
-    FS_HIP(ctx, hipMalloc((void**)&s->d_ring, sizeof(float) * 2 * kReverbRing));
-    FS_HIP(ctx, hipMemsetAsync(s->d_ring, 0, sizeof(float) * 2 * kReverbRing, ctx->rev_stream));   // SetNumZeroed
+    s->rev_engine = s->rev_engine_next;
+    if (part) {   // N = the smallest power of two >= 2 F, K = ceil(num_samples / F)
+        s->part_n = 5;
+        while ((1 << s->part_n) < 2 * frame_size) ++s->part_n;
+        s->part_K = (ctx->num_samples + frame_size - 1) / frame_size;
+        const int rc = part_twiddles(ctx, s->part_n);
+        if (rc) return rc;
+    }
+    const size_t ring_bytes = reverb_state_bytes(s);
+    FS_HIP(ctx, hipMalloc((void**)&s->d_ring, ring_bytes));
+    FS_HIP(ctx, hipMemsetAsync(s->d_ring, 0, ring_bytes, ctx->rev_stream));   // SetNumZeroed
     s->rev_head = 0;
+    s->part_slot = 0;
     s->rev_frame = frame_size;
     s->fading = s->fade_primed = false;   // (the first callback takes the IR unfaded)
-    if (s->fade_len > 0) return alloc_fade(ctx, s);
+    if (s->fade_len > 0 || part) return alloc_fade(ctx, s, s->fade_len > 0);
+    return FS_OK;
+}
+
+int fs_reverb_set_engine(fs_context* ctx, fs_source h, int32_t engine) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (engine != FS_REVERB_ENGINE_DIRECT && engine != FS_REVERB_ENGINE_PARTITIONED)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "unknown reverb engine (FS_REVERB_ENGINE_DIRECT, FS_REVERB_ENGINE_PARTITIONED)");
+    s->rev_engine_next = engine;   // (the next fs_reverb_init's)
     return FS_OK;
 }
 
@@ -209,7 +300,7 @@ int fs_reverb_set_crossfade(fs_context* ctx, fs_source h, int32_t samples) {
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "crossfade length out of range (0 = off, 1 .. 4 * sample_rate)");
     if (samples > 0 && s->d_ring) {
         FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
-        const int rc = alloc_fade(ctx, s);
+        const int rc = alloc_fade(ctx, s, true);
         if (rc) return rc;
     }
     if (s->fade_len == 0) s->fade_primed = false;   // enabling: nothing to fade from
@@ -258,8 +349,9 @@ int fs_reverb_release(fs_context* ctx, fs_source h) {
     if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
     if (s->d_ring && ctx->device_ok) {
         FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
-        FS_HIP(ctx, hipMemsetAsync(s->d_ring, 0, sizeof(float) * 2 * kReverbRing, ctx->rev_stream));
+        FS_HIP(ctx, hipMemsetAsync(s->d_ring, 0, reverb_state_bytes(s), ctx->rev_stream));   // (partitioned: the window history and the spectrum ring)
         s->rev_head = 0;
+        s->part_slot = 0;
         s->fading = false;   // a running crossfade ends at its target IR
     }
     return FS_OK;

@@ -140,6 +140,13 @@ struct Source {
     // reverb (row f2): history rings [2][kReverbRing], write head (a callback's rows are staged in fs_context::h_rev_stage / d_rev_stage)
     float* d_ring = nullptr;
     unsigned rev_head = 0; int rev_frame = 0;
+    // fs_reverb_set_engine: the engine the next fs_reverb_init gives the source / the one it was initialised with.  PARTITIONED
+    // (fs_reverb_part.hip): d_ring is the engine's state block (ReverbPartItem: window history, products, delay line), float2
+    // [part_state_elems(part_n, part_K)]; N = 1 << part_n the transform, part_K partitions, part_slot the delay line's next slot;
+    // d_fade_to / d_fade_from below are partition spectra [part_K][N] float2, and d_fade_to exists without a fade length too:
+    // every callback convolves its own spectra, taken like a crossfade's h_to (fade_primed, fade_gen).
+    int32_t rev_engine_next = FS_REVERB_ENGINE_DIRECT, rev_engine = FS_REVERB_ENGINE_DIRECT;
+    int part_n = 0, part_K = 0, part_slot = 0;
     // crossfade between successive IRs (fs_reverb_set_crossfade; the callback's own state, audio thread): fade_len L samples
     // (0: off), the callback's copies of the IRs it fades between (h_to = the newest it took, generation fade_gen),
     // fade_pos = samples output since the running fade began; fading == false: h_to alone is heard.
@@ -265,10 +272,14 @@ struct fs_context {
     hipGraphExec_t fft_graph = nullptr;
     int fft_graph_n = -1, fft_graph_l = -1;
     // fs_reverb_process / fs_reverb_process_batch (audio thread): pinned host staging and its device mirror, grown at the first call that needs more
-    // (count x frame size), freed with the context.  Up: items [count] | plain, fade, take lists [3][count] | in [count][2 frame];
+    // (count x frame size), freed with the context.  Up: items [count] | the partitioned rows' items [count] | plain, fade, take lists
+    // of the two engines [6][count] | in [count][2 frame];
     // down: out [count][2 frame] | mix [2 frame]; the device also holds the mono tails cur [count][2 frame].
     char* h_rev_stage = nullptr; char* d_rev_stage = nullptr;
     size_t rev_stage_host = 0, rev_stage_dev = 0;   // bytes
+    // the partitioned engine's twiddles, W[k] = exp(-2 pi i k / N), k < N / 2, per n = log2 N <= 12: built by the first
+    // fs_reverb_init that needs the size, freed with the context
+    float2* d_rev_tw[13] = {};
     // FS_FLAG_SPECTRAL_IR: the band edges (fs_set_band_edges: the B - 1 inner ones, ascending; empty = the defaults) and the
     // carriers built from them (fs_capi_publish.cpp: carrier_for — lazily, before the first spectral reconstruct)
     std::vector<double> band_edges;

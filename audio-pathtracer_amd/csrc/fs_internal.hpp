@@ -423,9 +423,39 @@ struct ReverbItem {
     int32_t fade_pos, fade_len;
     float take_a;
     int32_t apply;         // 0: the bypass (out row := in row, nothing else)
-    int32_t pad_;
+    int32_t engine;        // FS_REVERB_ENGINE_*: a PARTITIONED row has its descriptor in the ReverbPartItem table; of this one
+                           // it fills apply and engine only, and the direct engine's kernels leave the row alone
 };
 static_assert(sizeof(ReverbItem) == 72, "ReverbItem: six pointers and six words, the host's staging layout");
+// fs_reverb_part.hip (FS_REVERB_ENGINE_PARTITIONED): the descriptor of row i of the call is pitems[i]; active == 0 for every row
+// that is not a convolved row of this engine.  A source's state is one block of float2 (Source::d_ring), all spectra in the
+// transforms' bit-reversed order:  hist [N] the window history ring (left + i right) | x_now [N] the literal-tail window's
+// spectrum | Y [2][N] the products (H, H_to) | xring [K][N] the delay line of window spectra;  N = 1 << n.
+struct ReverbPartItem {
+    const float2* h;       // partition spectra [K][N] (H_from while a crossfade runs) ...
+    const float2* h_to;    // ... and those it fades to (null: one product)
+    float2* state;
+    float2* take_from;     // a source that takes a newer IR in this callback (launch_reverb_part_take):
+    float2* take_to;       //   H_from := (1 - take_a) H_from + take_a H_to (take_a > 0), then H_to := the spectra of take_ir
+    const float* take_ir;
+    unsigned head;         // history write head before this callback
+    int32_t slot;          // delay-line slot this callback's spectrum enters
+    int32_t fade_pos, fade_len;
+    float take_a;
+    int32_t active;
+};
+static_assert(sizeof(ReverbPartItem) == 72, "ReverbPartItem: six pointers and six words, the host's staging layout");
+__host__ __device__ inline float2* part_hist(float2* state, int n) { return state; }
+__host__ __device__ inline float2* part_xnow(float2* state, int n) { return state + ((size_t)1 << n); }
+__host__ __device__ inline float2* part_y(float2* state, int n) { return state + ((size_t)2 << n); }
+__host__ __device__ inline float2* part_xring(float2* state, int n) { return state + ((size_t)4 << n); }
+constexpr size_t part_state_elems(int n, int K) { return ((size_t)4 + (size_t)K) << n; }
+struct ReverbPart {
+    const int* plain; int n_plain;  // rows with one product ...
+    const int* fade; int n_fade;    // ... and with two
+    const float2* W;                // twiddles of N = 1 << n
+    int n, K, frame, ir_size;
+};
 struct ReverbBatch {
     const ReverbItem* items;        // [count]
     const int* plain; int n_plain;  // rows convolved with one IR ...
@@ -435,12 +465,20 @@ struct ReverbBatch {
     float* cur;                     // [count][2][frame] scratch
     float* out;                     // [count][2 * frame] interleaved
     float* mix;                     // [2 * frame], or null
+    int n_direct;                   // convolved rows of the direct engine + bypassed rows: what the prepare pass serves
+    const ReverbPartItem* pitems;   // [count]: the rows of the partitioned engine (null: none in this call)
+    ReverbPart part;
 };
 // take: the rows whose crossfade starts in this callback (n_take >= 1), n = IR samples
 void launch_reverb_batch_fade_start(const ReverbItem* items, const int* take, int n_take, int n, hipStream_t s);
 // prepare (+ push, where the ring allows), the convolutions of the two lists (each launched only when it has rows), the push
-// (where it could not ride in front), the mix (when b.mix)
+// (where it could not ride in front), the partitioned engine's rows (launch_reverb_part, when b.pitems), the mix (when b.mix)
 void launch_reverb_batch(const ReverbBatch& b, hipStream_t s);
+// take: the partitioned rows that take a newer IR in this callback (n_take >= 1)
+void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, hipStream_t s);
+// the window transforms, the products of the two lists (each launched only when it has rows), the inverse and epilogue
+void launch_reverb_part(const ReverbPartItem* items, const ReverbPart& p, int count, int literal_tail, const float* in, float* out,
+                        hipStream_t s);
 void launch_add_energy(float* energy_row, int num_bins, float delay_s, float e, hipStream_t s);
 // dynamic LDS the traversal kernels of a frame need for a tree with `stack_rows` stack rows: the larger of the walk
 // kernel (stack + work-sharing area) and the connect kernels (stack + [bands][bins] histogram + work-sharing area)

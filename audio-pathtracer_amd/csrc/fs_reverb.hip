@@ -1,6 +1,7 @@
 // fs_reverb.hip — row f2, the reverb plugin's per-callback convolution (FFrequenSeeAudioReverbPlugin::ProcessSourceAudio,
 // FrequenSeeAudioReverbPlugin.cpp:118-170, ConvolveFFT :172-213), for all rows of one audio callback as one set of launches
-// (fs_reverb_process_batch; fs_reverb_process is a callback of one row).
+// (fs_reverb_process_batch; fs_reverb_process is a callback of one row).  This is the DIRECT engine, the default; a source may
+// choose the partitioned one of fs_reverb_part.hip instead (fs_reverb_set_engine), and a call may hold rows of both.
 //
 // The reference zero-pads the last 47 999 + 1 024 samples and the 48 000-tap IR to 65 536 and multiplies three KissFFT spectra;
 // only output samples [47 999, 49 023) are kept, for which the circular product equals the plain convolution
@@ -42,7 +43,8 @@ __global__ void reverb_batch_fade_start_kernel(const ReverbItem* __restrict__ it
     h_to[i] = it.take_ir[i];
 }
 
-// Row r of the call (blockIdx.y), the passes of `mode`.  kRevTails: a bypassed row (apply == 0) gets out row := in row (what the
+// Row r of the call (blockIdx.y), the passes of `mode` (a convolved row of the partitioned engine has neither tails nor a ring of
+// this kind: fs_reverb_part.hip serves it).  kRevTails: a bypassed row (apply == 0) gets out row := in row (what the
 // mix sums; the host copies the row itself), a convolved one the two mono tails of this callback.  kRevPush: a convolved row's
 // samples enter its history ring.
 constexpr int kRevTails = 1, kRevPush = 2;
@@ -61,6 +63,7 @@ __global__ void reverb_batch_prepare_kernel(const ReverbItem* __restrict__ items
         }
         return;
     }
+    if (it.engine != FS_REVERB_ENGINE_DIRECT) return;
     if (mode & kRevTails) {
         float* cur = cur_all + (size_t)r * 2 * (size_t)frame;
         // RVB.cpp:147-148 copies the first `frame` floats of the INTERLEAVED buffer into both mono tails
@@ -180,8 +183,9 @@ void launch_reverb_batch(const ReverbBatch& b, hipStream_t s) {
     // in front of the convolution (the default IR with any legal frame: 47 999 + 16 384 = 64 383 <= 65 536).  A longer IR's
     // appended samples would land on the oldest history the convolution is about to read: there the push runs behind it.
     const bool fused = (b.ir_size - 1) + b.frame <= kRevRing;
-    hipLaunchKernelGGL(reverb_batch_prepare_kernel, rows, dim3(tb), 0, s, b.items, b.in, b.cur, b.out, b.frame, b.literal_tail,
-                       fused ? kRevTails | kRevPush : kRevTails);
+    if (b.n_direct > 0)   // (a call of partitioned rows alone has nothing to prepare)
+        hipLaunchKernelGGL(reverb_batch_prepare_kernel, rows, dim3(tb), 0, s, b.items, b.in, b.cur, b.out, b.frame, b.literal_tail,
+                           fused ? kRevTails | kRevPush : kRevTails);
     const int tiles = (b.frame + kRevOut - 1) / kRevOut;
     if (b.n_plain > 0)
         hipLaunchKernelGGL(reverb_batch_conv_kernel<false>, dim3(tiles, 2, b.n_plain), dim3(kBlock), 0, s, b.items, b.plain, b.ir_size,
@@ -189,8 +193,9 @@ void launch_reverb_batch(const ReverbBatch& b, hipStream_t s) {
     if (b.n_fade > 0)
         hipLaunchKernelGGL(reverb_batch_conv_kernel<true>, dim3(tiles, 2, b.n_fade), dim3(kBlock), 0, s, b.items, b.fade, b.ir_size,
                            b.cur, b.frame, b.out);
-    if (!fused)
+    if (!fused && b.n_plain + b.n_fade > 0)
         hipLaunchKernelGGL(reverb_batch_prepare_kernel, rows, dim3(tb), 0, s, b.items, b.in, b.cur, b.out, b.frame, b.literal_tail, kRevPush);
+    if (b.pitems) launch_reverb_part(b.pitems, b.part, b.count, b.literal_tail, b.in, b.out, s);
     if (b.mix)
         hipLaunchKernelGGL(reverb_batch_mix_kernel, dim3((2 * b.frame + tb - 1) / tb), dim3(tb), 0, s, b.out, b.count, 2 * b.frame, b.mix);
 }

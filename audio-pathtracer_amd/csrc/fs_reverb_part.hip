@@ -1,0 +1,252 @@
+// fs_reverb_part.hip — row f2, the reverb callback's PARTITIONED engine (fs_reverb_set_engine): a uniformly partitioned
+// overlap-save convolution with a frequency-domain delay line, beside the direct form of fs_reverb.hip.
+//
+// With frame F, N = the smallest power of two >= 2F and K = ceil(ir_size / F):
+//   H_p = FFT_N(h[pF .. pF + F) zero-padded), p < K                      reverb_part_take_kernel (only when a newer IR is taken)
+//   X_t = FFT_N(w_L + i w_R), w = the last N samples ending in this block  reverb_part_forward_kernel -> a ring of K spectra
+//   Y   = sum_{p < K} H_p X_{t-p}                                         reverb_part_mac_kernel
+//   y   = IFFT_N(Y); out = the last F of y, real part left, imaginary part right   reverb_part_inverse_kernel
+// The IR is real and mono, so one complex transform carries both channels.  The cost of a callback is K N complex MACs and
+// three N-point transforms (0.1 M MACs at F = 1024 and 48 000 taps; the direct form needs 98 M), and the history is one window
+// whatever the IR length.
+//
+// The transforms are the radix-2 pair of fs_fft.hip, whole inside LDS (N <= 4096: 32 KB of float2, one workgroup each): forward =
+// decimation in frequency, natural order in, bit-reversed order out; inverse = decimation in time, bit-reversed in, natural
+// out.  H, X and Y all live in bit-reversed order and the product is pointwise, so no bit-reversal pass exists.  Twiddles come
+// from the host's double-precision table (W[k] = exp(-2 pi i k / N), k < N / 2, cached per N in the context).
+//
+// Every kernel finds its row through a table of ReverbPartItem (fs_internal.hpp), the rows of a call side by side in the grid;
+// nothing a row computes depends on the other rows, so a source gets the same bits alone or in any batch.  The file is built
+// with -ffp-contract=off: what is fused is written as fmaf.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "fs_internal.hpp"
+
+namespace fs {
+namespace {
+
+constexpr int kPartBlock = 256;
+constexpr int kMacBins = 64;                        // bins per multiply-accumulate workgroup: one wavefront wide
+constexpr int kMacWaves = kPartBlock / kMacBins;    // its wavefronts share the partitions: wave w takes p = w, w + 4, ...
+
+__device__ __forceinline__ float2 padd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 psub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ float2 pmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
+__device__ __forceinline__ float2 pmul_conj(float2 a, float2 w) { return make_float2(a.x * w.x + a.y * w.y, a.y * w.x - a.x * w.y); }
+// acc + h x, each component two fused steps in a fixed order
+__device__ __forceinline__ float2 pmac(float2 acc, float2 h, float2 x) {
+    return make_float2(fmaf(h.x, x.x, fmaf(-h.y, x.y, acc.x)), fmaf(h.x, x.y, fmaf(h.y, x.x, acc.y)));
+}
+
+// sh[0 .. 2^n): natural order -> the spectrum in bit-reversed order.  Every thread of the workgroup calls it; sh is complete
+// before (the caller's stores need no barrier of their own) and after.
+__device__ __forceinline__ void lds_fft_dif(float2* sh, const float2* __restrict__ W, int n) {
+    const uint32_t half = 1u << (n - 1);
+    for (int ls = n - 1; ls >= 0; --ls) {
+        __syncthreads();
+        const uint32_t s = 1u << ls;
+        for (uint32_t t = threadIdx.x; t < half; t += kPartBlock) {
+            const uint32_t j = t & (s - 1u);
+            const uint32_t i0 = ((t >> ls) << (ls + 1)) + j, i1 = i0 + s;
+            const float2 a = sh[i0], b = sh[i1];
+            sh[i0] = padd(a, b);
+            sh[i1] = pmul(psub(a, b), W[(size_t)j << (n - 1 - ls)]);
+        }
+    }
+    __syncthreads();
+}
+// sh[0 .. 2^n): a spectrum in bit-reversed order -> N times its inverse transform in natural order
+__device__ __forceinline__ void lds_fft_dit(float2* sh, const float2* __restrict__ W, int n) {
+    const uint32_t half = 1u << (n - 1);
+    for (int ls = 0; ls < n; ++ls) {
+        __syncthreads();
+        const uint32_t s = 1u << ls;
+        for (uint32_t t = threadIdx.x; t < half; t += kPartBlock) {
+            const uint32_t j = t & (s - 1u);
+            const uint32_t i0 = ((t >> ls) << (ls + 1)) + j, i1 = i0 + s;
+            const float2 a = sh[i0];
+            const float2 b = pmul_conj(sh[i1], W[(size_t)j << (n - 1 - ls)]);
+            sh[i0] = padd(a, b);
+            sh[i1] = psub(a, b);
+        }
+    }
+    __syncthreads();
+}
+
+// The rows of `take` get a newer IR: workgroup (p, k) owns partition p of row take[k].  First the fold of a fade that is cut
+// short, H_from[p] := (1 - a) H_from[p] + a H_to[p] (a = p0 / L > 0; exact on the spectra, the transform is linear), then
+// H_to[p] := FFT_N(ir[pF .. pF + F) zero-padded).
+__global__ __launch_bounds__(kPartBlock) void reverb_part_take_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ take,
+                                                                      const float2* __restrict__ W, int n, int frame, int ir_size) {
+    extern __shared__ __attribute__((aligned(16))) float2 sh[];
+    const ReverbPartItem it = items[take[blockIdx.y]];
+    const uint32_t N = 1u << n;
+    const uint32_t p = blockIdx.x;
+    float2* __restrict__ h_to = it.take_to + (size_t)p * N;
+    const float a = it.take_a;
+    if (a > 0.0f) {
+        float2* __restrict__ h_from = it.take_from + (size_t)p * N;
+        for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) {
+            const float2 f = h_from[i], t = h_to[i];
+            h_from[i] = make_float2((1.0f - a) * f.x + a * t.x, (1.0f - a) * f.y + a * t.y);
+        }
+    }
+    const float* __restrict__ ir = it.take_ir;
+    const uint32_t k0 = p * (uint32_t)frame;
+    for (uint32_t i = threadIdx.x; i < N; i += kPartBlock)
+        sh[i] = make_float2(i < (uint32_t)frame && k0 + i < (uint32_t)ir_size ? ir[k0 + i] : 0.0f, 0.0f);
+    lds_fft_dif(sh, W, n);
+    for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) h_to[i] = sh[i];
+}
+
+// Row r = blockIdx.x (left at once unless it is a convolved row of this engine): the transform of its window.  The window's
+// first N - F samples come from the history ring (N complex samples, left + i right, head = the sample this block starts at),
+// the last F are this block.  blockIdx.y == 0: the true block, which also enters the history; its transform enters the spectrum
+// ring at `slot`.  blockIdx.y == 1 (FS_REVERB_LITERAL_TAIL only): the block as RVB.cpp:147-148 reads it — the interleaved
+// buffer's first F floats in both channels — into the row's x_now, which this callback's product reads in place of the slot.
+// The history positions the first workgroup writes, [head, head + F), are not among those either reads, [head + F, head + N).
+__global__ __launch_bounds__(kPartBlock) void reverb_part_forward_kernel(const ReverbPartItem* __restrict__ items, const float* __restrict__ in_all,
+                                                                         const float2* __restrict__ W, int n, int frame) {
+    extern __shared__ __attribute__((aligned(16))) float2 sh[];
+    const int r = blockIdx.x;
+    const ReverbPartItem it = items[r];
+    if (!it.active) return;
+    const uint32_t N = 1u << n;
+    const bool literal = blockIdx.y != 0;
+    const float* __restrict__ in = in_all + (size_t)r * 2 * (size_t)frame;
+    float2* __restrict__ hist = part_hist(it.state, n);
+    const uint32_t old = N - (uint32_t)frame;
+    for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) {
+        float2 v;
+        if (j < old) {
+            v = hist[(it.head + (uint32_t)frame + j) & (N - 1u)];
+        } else {
+            const uint32_t i = j - old;
+            if (literal) {
+                v = make_float2(in[i], in[i]);
+            } else {
+                v = make_float2(in[2 * i], in[2 * i + 1]);
+                hist[(it.head + i) & (N - 1u)] = v;
+            }
+        }
+        sh[j] = v;
+    }
+    lds_fft_dif(sh, W, n);
+    float2* __restrict__ dst = literal ? part_xnow(it.state, n) : part_xring(it.state, n) + ((size_t)it.slot << n);
+    for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) dst[j] = sh[j];
+}
+
+// The product of row list[blockIdx.y] over the delay line: Y[b] = sum_p H_p[b] X_{t-p}[b], X_{t-p} = spectrum ring slot
+// (slot - p) mod K (p = 0: x_now in a literal-tail callback).  A workgroup owns 64 adjacent bins, so every load of a wavefront is
+// 512 contiguous bytes; its four wavefronts take p = w, w + 4, ... in ascending order and their sums meet in LDS as
+// ((s0 + s1) + s2) + s3 — an order fixed by K alone.  FADE: the same X against H_from and H_to, two sums (Y[0], Y[1]).
+template <bool FADE>
+__global__ __launch_bounds__(kPartBlock) void reverb_part_mac_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ list,
+                                                                     int n, int K, int literal) {
+    __shared__ float2 s_sum[FADE ? 2 : 1][kMacWaves][kMacBins];
+    const ReverbPartItem it = items[list[blockIdx.y]];
+    const uint32_t N = 1u << n;
+    const uint32_t lane = threadIdx.x & (kMacBins - 1), w = threadIdx.x / kMacBins;
+    const uint32_t b = blockIdx.x * kMacBins + lane;
+    const bool live = b < N;   // (N = 32: half a wavefront)
+    const float2* __restrict__ H = it.h;
+    const float2* __restrict__ H_to = it.h_to;
+    const float2* __restrict__ xring = part_xring(it.state, n);
+    const float2* __restrict__ xnow = part_xnow(it.state, n);
+    float2 acc = make_float2(0.0f, 0.0f), acc_to = make_float2(0.0f, 0.0f);
+    if (live) {
+#pragma unroll 4
+        for (int p = (int)w; p < K; p += kMacWaves) {
+            int sp = it.slot - p;
+            sp += sp < 0 ? K : 0;
+            const float2 x = (p == 0 && literal) ? xnow[b] : xring[((size_t)sp << n) + b];
+            acc = pmac(acc, H[((size_t)p << n) + b], x);
+            if (FADE) acc_to = pmac(acc_to, H_to[((size_t)p << n) + b], x);
+        }
+    }
+    s_sum[0][w][lane] = acc;
+    if (FADE) s_sum[FADE ? 1 : 0][w][lane] = acc_to;
+    __syncthreads();
+    if (w == 0 && live) {
+        float2* __restrict__ Y = part_y(it.state, n);
+        float2 v = s_sum[0][0][lane];
+#pragma unroll
+        for (int k = 1; k < kMacWaves; ++k) v = padd(v, s_sum[0][k][lane]);
+        Y[b] = v;
+        if (FADE) {
+            float2 u = s_sum[FADE ? 1 : 0][0][lane];
+#pragma unroll
+            for (int k = 1; k < kMacWaves; ++k) u = padd(u, s_sum[FADE ? 1 : 0][k][lane]);
+            Y[N + b] = u;
+        }
+    }
+}
+
+// Row r = blockIdx.x (as above): y = IFFT_N(Y) / N, the last F samples, real part left and imaginary part right, clamped
+// (FMath::Clamp RVB.cpp:165-167, MixAlpha = 1) into the interleaved out row.  A fading row (h_to) inverts both sums and mixes per
+// output sample, (1 - g) y_from + g y_to, g = (p + 1) / L while p = fade_pos + s < L, else 1 — the direct engine's expression.
+// LDS: the transform [N] and, for the fade, y_from's kept samples [F].
+__global__ __launch_bounds__(kPartBlock) void reverb_part_inverse_kernel(const ReverbPartItem* __restrict__ items, const float2* __restrict__ W,
+                                                                         int n, int frame, float* __restrict__ out_all) {
+    extern __shared__ __attribute__((aligned(16))) float2 sh[];
+    const int r = blockIdx.x;
+    const ReverbPartItem it = items[r];
+    if (!it.active) return;
+    const uint32_t N = 1u << n;
+    const float scale = 1.0f / (float)N;   // (a power of two: exact)
+    const float2* __restrict__ Y = part_y(it.state, n);
+    float2* keep = sh + N;
+    float* __restrict__ out = out_all + (size_t)r * 2 * (size_t)frame;
+    const uint32_t old = N - (uint32_t)frame;
+    for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) sh[j] = Y[j];
+    lds_fft_dit(sh, W, n);
+    const bool fade = it.h_to != nullptr;
+    if (fade) {
+        for (uint32_t s = threadIdx.x; s < (uint32_t)frame; s += kPartBlock) keep[s] = sh[old + s];
+        __syncthreads();
+        for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) sh[j] = Y[N + j];
+        lds_fft_dit(sh, W, n);
+    }
+    for (uint32_t s = threadIdx.x; s < (uint32_t)frame; s += kPartBlock) {
+        float2 v = sh[old + s];
+        v = make_float2(v.x * scale, v.y * scale);
+        if (fade) {
+            const float2 f = make_float2(keep[s].x * scale, keep[s].y * scale);
+            const int p = it.fade_pos + (int)s;
+            const float g = p < it.fade_len ? (float)(p + 1) / (float)it.fade_len : 1.0f;
+            v = make_float2((1.0f - g) * f.x + g * v.x, (1.0f - g) * f.y + g * v.y);
+        }
+        v.x = v.x < -1.0f ? -1.0f : (v.x > 1.0f ? 1.0f : v.x);
+        v.y = v.y < -1.0f ? -1.0f : (v.y > 1.0f ? 1.0f : v.y);
+        out[2 * s] = v.x;
+        out[2 * s + 1] = v.y;
+    }
+}
+
+}  // namespace
+
+void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, hipStream_t s) {
+    hipLaunchKernelGGL(reverb_part_take_kernel, dim3((unsigned)p.K, (unsigned)n_take), dim3(kPartBlock), sizeof(float2) << p.n, s, items,
+                       take, p.W, p.n, p.frame, p.ir_size);
+}
+
+void launch_reverb_part(const ReverbPartItem* items, const ReverbPart& p, int count, int literal_tail, const float* in, float* out,
+                        hipStream_t s) {
+    const size_t lds = sizeof(float2) << p.n;
+    const unsigned N = 1u << p.n;
+    hipLaunchKernelGGL(reverb_part_forward_kernel, dim3((unsigned)count, literal_tail ? 2u : 1u), dim3(kPartBlock), lds, s, items, in, p.W,
+                       p.n, p.frame);
+    const unsigned tiles = (N + kMacBins - 1) / kMacBins;
+    if (p.n_plain > 0)
+        hipLaunchKernelGGL(reverb_part_mac_kernel<false>, dim3(tiles, (unsigned)p.n_plain), dim3(kPartBlock), 0, s, items, p.plain, p.n, p.K,
+                           literal_tail);
+    if (p.n_fade > 0)
+        hipLaunchKernelGGL(reverb_part_mac_kernel<true>, dim3(tiles, (unsigned)p.n_fade), dim3(kPartBlock), 0, s, items, p.fade, p.n, p.K,
+                           literal_tail);
+    hipLaunchKernelGGL(reverb_part_inverse_kernel, dim3((unsigned)count), dim3(kPartBlock), lds + sizeof(float2) * (size_t)p.frame, s, items,
+                       p.W, p.n, p.frame, out);
+}
+
+}  // namespace fs

@@ -50,7 +50,7 @@
  *             fs_comm_enable_oneshot fs_comm_detach fs_comm_info fs_peers_init fs_peers_detach fs_gather_energy fs_gather_energy_async
  *             fs_copy_band_impulse_response fs_set_impulse_response fs_trace_rays
  *             fs_save_array_to_file fs_load_float_array fs_save_impulse_response
- *             fs_reverb_init fs_reverb_process fs_reverb_process_batch fs_reverb_release fs_reverb_set_crossfade fs_apply_material_fd
+ *             fs_reverb_init fs_reverb_process fs_reverb_process_batch fs_reverb_release fs_reverb_set_crossfade fs_reverb_set_engine fs_apply_material_fd
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
  *             fs_source_set_orientation fs_source_set_directivity fs_get_room_parameters
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
@@ -659,6 +659,33 @@ int fs_reverb_release(fs_context* ctx, fs_source src); /* OnReleaseSource: Clear
  *  5. The fade is linear, not equal-power: successive IRs of one source are strongly correlated (equal power would raise the
  *     level by up to 3 dB mid-fade). */
 int fs_reverb_set_crossfade(fs_context* ctx, fs_source src, int32_t samples);
+/* The engine that computes rule b's convolution, per source.  DIRECT (the default of a new source handle) evaluates the sum
+ * tap by tap: 2 * frame_size * num_samples MACs per callback and a history ring that bounds the IR (fs_reverb_init).
+ * PARTITIONED is a uniformly partitioned overlap-save convolution with a frequency-domain delay line: with F = frame_size,
+ * N = the smallest power of two >= 2 F and K = ceil(num_samples / F), the IR is kept as K spectra H_p = FFT_N(h[pF .. pF + F)),
+ * every callback transforms one window X_t = FFT_N(w_L + i w_R) of the last N samples into a ring of K spectra, and
+ * out = the last F samples of IFFT_N(sum_p H_p X_{t-p}), real part left, imaginary part right: K N complex MACs and three
+ * transforms, a history of one window whatever the IR length.
+ *  - The call only records the choice: it takes effect at the source's next fs_reverb_init, as the frame size does; until then
+ *    the source keeps the engine it was initialised with.  Threading contract of fs_reverb_set_crossfade.
+ *  - fs_reverb_init under PARTITIONED accepts 16 <= frame_size <= 2048 and any num_samples <= 1 048 576 (no ring limit), anything
+ *    else is FS_ERR_INVALID_ARGUMENT; it allocates all of the engine's per-source device memory (the second spectrum set of a
+ *    crossfade: there or in fs_reverb_set_crossfade), so batch rule 5 holds.  Under DIRECT its checks are unchanged.
+ *  - Every rule beside fs_reverb_process, fs_reverb_process_batch and fs_reverb_set_crossfade holds for a partitioned source, with
+ *    "to the bit" in batch rule 1 read as "to the bit between calls that serve the source with the same engine": a partitioned
+ *    source gives the same bits served by one call or several, alone or in any batch; the two engines agree with each other
+ *    within rounding (both within 2e-5 of the double-precision convolution, relative to the block's peak).  A batch may mix
+ *    sources of both engines at one frame size; its direct rows keep their bits.
+ *  - The spectra are built from the device-resident IR only by a callback that sees a newer IR than the one they hold (and by
+ *    the first after fs_reverb_init): only such a callback waits for a reconstruct.  Crossfade rule 3's fold is done on the
+ *    spectra (exact: the transform is linear); a fading source forms both products and mixes them per output sample.
+ *  - FS_REVERB_LITERAL_TAIL: the transform used in the callback is that of the window ending in the block as RVB.cpp:147-148
+ *    reads it; the transform of the true samples enters the ring (one more forward transform in such a callback).
+ * A null context is FS_ERR_INVALID_ARGUMENT, no device FS_ERR_NO_DEVICE, a bad handle FS_ERR_BAD_HANDLE, an engine other than
+ * these two FS_ERR_INVALID_ARGUMENT; a refused call changes nothing. */
+#define FS_REVERB_ENGINE_DIRECT      0   /* the tap-by-tap kernels, the default */
+#define FS_REVERB_ENGINE_PARTITIONED 1
+int fs_reverb_set_engine(fs_context* ctx, fs_source src, int32_t engine);
 
 /* ---- row f4: frequency-dependent material response of one audio block ------------------------------------
  *      UMaterialAcousticProcessor::ApplyMaterialFD (Private/MaterialAcousticProcessor.cpp:8-107, MAP.cpp):
