@@ -54,6 +54,7 @@ EXPORTS = [
     "fs_scene_commit_fast", "fs_comm_unique_id", "fs_comm_init", "fs_comm_attach", "fs_comm_detach", "fs_comm_info", "fs_comm_enable_oneshot", "fs_shard_range",
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
     "fs_set_band_edges", "fs_source_set_orientation", "fs_source_set_directivity", "fs_get_room_parameters",
+    "fs_direct_params_default", "fs_direct_sample_offsets", "fs_update_direct_paths",
 ]
 MAX_DIRECTIVITY_SAMPLES = 181   # FS_MAX_DIRECTIVITY_SAMPLES: 1 degree steps
 COMM_ID_BYTES = 128
@@ -63,6 +64,9 @@ REVERB_LITERAL_TAIL = 1
 MAX_REVERB_BATCH = 256
 REVERB_ENGINE_DIRECT = 0
 REVERB_ENGINE_PARTITIONED = 1
+MAX_DIRECT_BATCH = 256
+MAX_DIRECT_SAMPLES = 64
+DIRECT_MAX_QUERIES = 32
 
 
 class SoundParams(C.Structure):
@@ -193,6 +197,32 @@ class RoomParameters(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("energy", "onset", "edt", "t20", "t30", "c50", "c80", "d50", "ts")]
 
 
+class DirectParams(C.Structure):
+    """fs_direct_params (include/frequensee.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("samples", C.c_int32),
+        ("source_radius", C.c_float),
+        ("max_surfaces", C.c_int32),
+        ("step", C.c_float),
+        ("pullback", C.c_float),
+        ("dist_divisor", C.c_float),
+        ("sound_speed", C.c_float),
+    ]
+
+
+class DirectPath(C.Structure):
+    """fs_direct_path (include/frequensee.h): one source's row, an array element (no struct_size)"""
+    _fields_ = [
+        ("distance", C.c_float),
+        ("delay", C.c_float),
+        ("visibility", C.c_float),
+        ("surfaces", C.c_uint32),
+        ("samples_valid", C.c_uint32),
+        ("transmission", C.c_float * MAX_BANDS),
+    ]
+
+
 class FrequenSeeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"frequensee status {code}: {msg}")
@@ -299,6 +329,9 @@ def load():
         "fs_scene_commit_progressive": (C.c_int, [vp]),
         "fs_scene_refine_pending": (C.c_int, [vp, C.POINTER(i32)]),
         "fs_scene_refine_wait": (C.c_int, [vp]),
+        "fs_direct_params_default": (None, [C.POINTER(DirectParams)]),
+        "fs_direct_sample_offsets": (C.c_int, [i32, f32p]),
+        "fs_update_direct_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(DirectParams), C.c_void_p]),
         "fs_gather_energy": (C.c_int, [vp, i32, f32p, i32]),
         "fs_gather_energy_async": (C.c_int, [vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     }
@@ -321,6 +354,14 @@ def default_config(**kw) -> Config:
 def default_sound_params(**kw) -> SoundParams:
     p = SoundParams()
     load().fs_sound_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_direct_params(**kw) -> DirectParams:
+    p = DirectParams()
+    load().fs_direct_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -363,6 +363,31 @@ class Context:
         self.check(self.lib.fs_get_occlusion_attenuation(self.h, src, C.byref(v)))
         return float(v.value)
 
+    # ---- direct paths: the direct sound of every source of a tick in one launch ----
+    DIRECT_DTYPE = np.dtype([("distance", np.float32), ("delay", np.float32), ("visibility", np.float32), ("surfaces", np.uint32),
+                             ("samples_valid", np.uint32), ("transmission", np.float32, (_capi.MAX_BANDS,))])
+
+    @staticmethod
+    def direct_sample_offsets(n):
+        """fs_direct_sample_offsets: the [n][3] sample offsets (unit sphere, row 0 the centre) direct_paths uses for n samples"""
+        out = np.zeros((max(int(n), 0), 3), np.float32)
+        rc = _capi.load().fs_direct_sample_offsets(int(n), out.ctypes.data if out.size else None)
+        if rc != _capi.OK:
+            raise FrequenSeeError(rc, "fs_direct_sample_offsets: n must be 1 .. 64")
+        return out
+
+    def direct_paths(self, sources, out=None, **params):
+        """fs_update_direct_paths: one row per listed source — distance (cm), delay (s), visibility, surfaces the centre ray
+        crossed, samples_valid, transmission [8] (bands beyond num_bands: 0) — as a structured array; params = the fields of
+        fs_direct_params (samples, source_radius, max_surfaces, step, pullback, dist_divisor, sound_speed)"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        p = _capi.default_direct_params(**params)
+        if out is None:
+            out = np.zeros(srcs.shape[0], dtype=self.DIRECT_DTYPE)
+        self.check(self.lib.fs_update_direct_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
+                                                   out.ctypes.data if out.size else None))
+        return out
+
     # ---- row f2: reverb plugin convolution ----
     def reverb_init(self, src, frame_size=1024):
         self.check(self.lib.fs_reverb_init(self.h, src, frame_size))
@@ -550,6 +575,11 @@ class FrequenSeeAudioComponent:
         """the room parameters published with the front IR (a reconstruct with FS_FLAG_ROOM_PARAMETERS): (sequence, [bands])"""
         return self._ctx().room_parameters(self._src)
 
+    def GetDirectPath(self, **params):
+        """not in the reference (its occlusion plugin is a no-op): this source's direct sound — one row of Context.direct_paths"""
+        self._subsys._commit()
+        return self._ctx().direct_paths([self._src], **params)[0]
+
     # legacy per-frame forward tracer (TickComponent -> UpdateSound, FSAC.cpp:103-109, 283-306)
     RaycastsPerTick = 1500      # FSAC.h:39
     RaycastBounces = 10         # FSAC.h:42
@@ -673,6 +703,16 @@ class AudioRayTracingSubsystem:
             return
         self._commit()
         self.ctx.update_sources([s._src for s in srcs], self.params)
+
+    def UpdateDirectPaths(self, **params):
+        """the direct sound of all active sources in one launch: a structured array, row i for ActiveSources[i]
+        (Context.direct_paths; more than 256 sources take one launch per 256)"""
+        srcs = [s._src for s in self.ActiveSources]
+        if not srcs:
+            return np.zeros(0, dtype=Context.DIRECT_DTYPE)
+        self._commit()
+        step = _capi.MAX_DIRECT_BATCH
+        return np.concatenate([self.ctx.direct_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)])
 
     def SetPipelining(self, depth):
         """fs_set_pipelining: Tick then updates the sources one after the other like the reference's loop (ARTS.cpp:60-68),

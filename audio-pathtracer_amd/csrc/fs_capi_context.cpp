@@ -651,6 +651,9 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->fft_graph) (void)hipGraphExecDestroy(ctx->fft_graph);
         if (ctx->h_fft_stage) (void)hipHostFree(ctx->h_fft_stage);
         for (float2* w : ctx->d_rev_tw) if (w) (void)hipFree(w);
+        if (ctx->h_direct) (void)hipHostFree(ctx->h_direct);
+        if (ctx->d_direct) (void)hipFree(ctx->d_direct);
+        if (ctx->d_direct_off) (void)hipFree(ctx->d_direct_off);
         if (ctx->h_rev_stage) (void)hipHostFree(ctx->h_rev_stage);
         if (ctx->d_rev_stage) (void)hipFree(ctx->d_rev_stage);
         if (ctx->d_batch) (void)hipFree(ctx->d_batch);

@@ -3,7 +3,8 @@
 // fs_capi_frame.cpp (sources, the traced frame: describe / resources / commit / launch), fs_capi_pipeline.cpp (held frames, the
 // drain), fs_capi_publish.cpp (reconstruct + publish: the IR ring, the host word, the fused launch's reconstruct parts),
 // fs_capi_ir.cpp (reconstruct / tick / IR / energy entry points), fs_capi_comm.cpp (RCCL behind the ABI), fs_capi_reverb.cpp
-// (the reverb callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange, material FD).
+// (the reverb callback), fs_capi_direct.cpp (direct paths) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange,
+// material FD).
 //
 // Mirrors the roles of UAudioRayTracingSubsystem (context lifetime, geometry/source registries,
 // per-source update: AudioRayTracingSubsystem.cpp:32-53, 128-195) and of UFrequenSeeAudioComponent's
@@ -285,6 +286,13 @@ struct fs_context {
     std::vector<double> band_edges;
     float* d_carrier = nullptr;          // [B][carrier_stride(num_samples)] fp32
     float carrier_build_ms = 0.0f;       // device time of the last build (HIP events)
+    // fs_update_direct_paths (fs_capi_direct.cpp): pinned host staging — the rows' sources [direct_cap] float4 (read by the kernel
+    // in place) | the rows [direct_cap] fs_direct_path (the copy's target) — and the device rows, grown at the first call that needs
+    // more; the sample-offset tables [FS_MAX_DIRECT_SAMPLES][FS_MAX_DIRECT_SAMPLES][3] by n - 1, each uploaded at its first use
+    char* h_direct = nullptr; fs_direct_path* d_direct = nullptr;
+    int direct_cap = 0;
+    float* d_direct_off = nullptr;
+    uint64_t direct_off_have = 0;
     HostBVH bvh;
 
     float listener[3] = {0, 0, 0};

@@ -410,6 +410,19 @@ void launch_trace_rays(const DeviceScene& sc, const float* o, const float* d, co
                        int32_t* hit, float* t, int32_t* tri, float* normal, hipStream_t s);
 // rays_per_wave < 64: sparse waves whose other lanes help with every closest-hit query; 64 = one ray per lane
 void launch_update_sound(const DeviceScene& sc, const SoundKParams& sp, SoundAccum* acc, int rays_per_wave, hipStream_t s);
+// fs_direct.hip (fs_update_direct_paths): a wave per source row, lane k = sample k.  src = the rows' sources, xyz + the
+// source's actor id as bits, in pinned host memory (read in place); offsets = the [samples][3] table of the call's n (device);
+// out = the device staging the rows are written to.  samples is already 1 for a point source.
+struct DirectKParams {
+    const float4* src;
+    const float* offsets;
+    fs_direct_path* out;
+    float lis[3];
+    uint32_t lis_object;
+    int32_t count, samples, max_surfaces, num_bands;
+    float radius, step, pullback, dist_divisor, sound_speed;
+};
+void launch_direct_paths(const DeviceScene& sc, const DirectKParams& dp, hipStream_t s);
 constexpr int kReverbRing = 65536;   // per-channel history ring (floats), matches kRevRing in the kernels
 // fs_reverb.hip (the reverb callback): one descriptor per row of the call, in list order, read by every kernel of the callback.
 struct ReverbItem {

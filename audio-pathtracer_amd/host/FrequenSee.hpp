@@ -10,6 +10,7 @@
 // std::runtime_error carrying fs_last_error().
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -70,6 +71,9 @@ public:
     // the room parameters published with the front IR by a reconstruct with FS_FLAG_ROOM_PARAMETERS (one record per band; empty and
     // *Sequence = 0 when that publish carries none) — fs_get_room_parameters, lock-free
     std::vector<fs_room_parameters> GetRoomParameters(uint64_t* Sequence = nullptr) const;
+    // not in the reference (its occlusion plugin is a no-op): this source's direct sound — distance, arrival time, visibility and
+    // per-band transmission (fs_update_direct_paths with one row; Params = nullptr: the defaults)
+    fs_direct_path GetDirectPath(const fs_direct_params* Params = nullptr);
 
     bool bApplyReverb = true;   // .h:60
 
@@ -177,6 +181,18 @@ public:
             ForceUpdateSources();
         }
         ++Params.seed;
+    }
+    // the direct sound of every active source in one launch: row i for ActiveSources[i] (fs_update_direct_paths; more than
+    // FS_MAX_DIRECT_BATCH sources take one launch per FS_MAX_DIRECT_BATCH)
+    std::vector<fs_direct_path> UpdateDirectPaths(const fs_direct_params* P = nullptr) {
+        std::vector<fs_direct_path> Out(ActiveSources.size());
+        if (Out.empty()) return Out;
+        Commit();
+        std::vector<fs_source> H;
+        for (auto* s : ActiveSources) H.push_back(s->Handle_);
+        for (size_t i = 0; i < H.size(); i += FS_MAX_DIRECT_BATCH)
+            Check(fs_update_direct_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_DIRECT_BATCH), P, Out.data() + i));
+        return Out;
     }
     // fs_set_pipelining (0 off, 1, 2): Tick streams the sources instead of batching them
     void SetPipelining(int Depth) { Check(fs_set_pipelining(Ctx_, Depth)); Streamed_ = Depth != 0; }
@@ -313,6 +329,12 @@ inline std::vector<fs_room_parameters> FrequenSeeAudioComponent::GetRoomParamete
     if (Sequence) *Sequence = seq;
     if (seq == 0) v.clear();
     return v;
+}
+inline fs_direct_path FrequenSeeAudioComponent::GetDirectPath(const fs_direct_params* Params) {
+    SubSys_->Commit();
+    fs_direct_path r{};
+    SubSys_->Check(fs_update_direct_paths(SubSys_->Ctx_, &Handle_, 1, Params, &r));
+    return r;
 }
 inline void FrequenSeeAudioComponent::SaveImpulseResponse(const std::string& Path, int Channel) const {
     SubSys_->Check(fs_save_impulse_response(SubSys_->Ctx_, Handle_, Channel, Path.c_str()));

@@ -53,6 +53,7 @@
  *             fs_reverb_init fs_reverb_process fs_reverb_process_batch fs_reverb_release fs_reverb_set_crossfade fs_reverb_set_engine fs_apply_material_fd
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
  *             fs_source_set_orientation fs_source_set_directivity fs_get_room_parameters
+ *             fs_direct_params_default fs_direct_sample_offsets fs_update_direct_paths
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
  * Environment variables (FS_*) are tuning and diagnostic knobs only; all of them are read ONCE — at fs_context_create, at a
  * scene commit (builder knobs) or at the first launch of a kernel family — never per frame.
@@ -577,6 +578,74 @@ int fs_scene_set_objects(fs_context* ctx, const uint32_t* object_id, int32_t T);
 int fs_update_sound(fs_context* ctx, fs_source src, const fs_sound_params* p, fs_sound_result* out);
 /* GetOcclusionAttenuation() FSAC.h:112: value of the last fs_update_sound (1.0 before the first) */
 int fs_get_occlusion_attenuation(fs_context* ctx, fs_source src, float* out);
+
+/* ---- direct paths (EXTENDED): the direct sound of every source of a tick, in one launch -----------------------------------
+ * What a host needs to render the direct sound itself: the distance, the arrival time on the impulse response's time axis,
+ * how much of the source the listener sees, and how much gets through the surfaces in between, per band.  (In the default
+ * mode a traced pair is connected end to end, so the impulse response of a closed room holds almost no direct path; and
+ * fs_update_sound's occlusion_attenuation is one centre ray of one source that knows no transmission and no bands.)
+ * Deterministic — no random numbers — and specified to the bit: the library is built with -ffp-contract=off; below, every
+ * fp32 operation is rounded on its own, in the order written, and fmaf is a fused multiply-add.  numpy float32 scalars
+ * compute the same bits.
+ *   Sample offsets.  u_0 = (0, 0, 0); for k = 1 .. n-1 with j = k - 1, m = n - 1:  z = 1 - (2 j + 1) / m,
+ * rho = sqrt(1 - z z), phi = j pi (3 - sqrt(5)), u_k = (rho cos phi, rho sin phi, z) — computed on the host in double and
+ * rounded to float once.  fs_direct_sample_offsets returns exactly the table the kernel uses (FS_ERR_INVALID_ARGUMENT for
+ * n < 1, n > FS_MAX_DIRECT_SAMPLES or out == NULL).
+ *   chain(o, d, len) -> (reached, crossed, T[bands]).  T_b = 1, crossed = 0, rem = len; for q = 0, 1, ...:
+ *     1. !(rem > 0): reached.
+ *     2. the closest hit of the ray (o, d) within tmax = rem — the answer fs_trace_rays gives, ignoring nothing;
+ *     3. no hit: reached.
+ *     4. the hit triangle's object id (fs_scene_set_objects) equals the source's fs_source_set_object id or the listener's
+ *        fs_listener_set_object id, and that id is not FS_NO_OBJECT: the ray passes — nothing is counted or multiplied;
+ *     5. else crossed += 1; crossed > max_surfaces: blocked, T := 0, end; else T_b = T_b * tau_b with tau_b the transmitted
+ *        gain of the hit material (the transmission of fs_scene_set_materials clamped to the absorption and to >= 0;
+ *        FS_NO_MATERIAL, an id >= num_materials or no transmission array: 0); every T_b == 0: blocked, end.
+ *     6. (4 and 5) adv = t + step; o = (fmaf(adv, d.x, o.x), fmaf(adv, d.y, o.y), fmaf(adv, d.z, o.z)); rem = rem - adv;
+ *        q + 1 == FS_DIRECT_MAX_QUERIES: blocked, T := 0, end.
+ *   Per source at S, listener at L:  dx = L.x - S.x (dy, dz alike); distance = sqrtf((dx dx + dy dy) + dz dz);
+ * delay = (distance / dist_divisor) / sound_speed (EvaluatePath's rule: the direct sound lines up with the impulse response).
+ * source_radius == 0: only sample 0 exists (n := 1).  Sample k is VALID when k == 0 or chain(S, u_k, r).crossed == 0 (a
+ * sample point behind a wall the source stands close to does not count).  p_k = S + r u_k per component, e = L - p_k,
+ * len = sqrtf((e.x e.x + e.y e.y) + e.z e.z); len == 0: the sample is free with T = 1; else inv = 1.0f / len, d = e inv,
+ * (reached, crossed, T) = chain(p_k, d, len - pullback).  A sample is FREE when it reached with crossed == 0.
+ * samples_valid = V; visibility = (float)free / (float)V; transmission[b] = (float)(sum / (double)V), sum = the double sum
+ * of (double)T_k[b] over the valid k in ascending k; surfaces = crossed of sample 0.  An empty committed scene gives free
+ * lines.  Nothing depends on which builder made the tree.
+ *   Errors.  FS_ERR_INVALID_ARGUMENT: ctx, sources or out NULL, count < 1 or > FS_MAX_DIRECT_BATCH, a struct_size other than
+ * sizeof(fs_direct_params), a field outside its range or not finite.  FS_ERR_NO_DEVICE, FS_ERR_BAD_HANDLE,
+ * FS_ERR_NOT_COMMITTED as elsewhere.  A handle may appear twice: the rows are independent.  A refused call writes nothing.
+ *   Ordering and cost.  Like fs_update_sound: a finished progressive build is installed and a pending refit (also one left
+ * by fs_scene_set_object_transforms) runs first; then ONE launch on the compute stream, one copy back and one wait, whatever
+ * count is.  Held frames are not flushed; no state of the sources changes (energy, impulse response, occlusion scalar).
+ * Staging grows at the first call that needs more: a call with a count and samples the context has seen allocates nothing,
+ * and the offset table of a given n is uploaded once per context.  Sharded contexts: any rank may call it, no collective. */
+#define FS_MAX_DIRECT_BATCH 256
+#define FS_MAX_DIRECT_SAMPLES 64 /* one wave */
+#define FS_DIRECT_MAX_QUERIES 32 /* closest-hit queries one ray may chain */
+typedef struct fs_direct_params {
+    uint32_t struct_size;  /* = sizeof(fs_direct_params) */
+    int32_t samples;       /* n, 1 .. FS_MAX_DIRECT_SAMPLES; default 16 */
+    float source_radius;   /* r in cm, >= 0, finite; default 0: a point source, only the centre ray */
+    int32_t max_surfaces;  /* 1 .. 31; default 8: a ray that would cross more is blocked */
+    float step;            /* cm a ray advances past a crossed surface, >= 0; default 0.1 (FSAC.cpp:232) */
+    float pullback;        /* cm the ray stops short of the listener, >= 0; default 0.1 (ARTS.cpp:253) */
+    float dist_divisor;    /* 1000, as fs_params */
+    float sound_speed;     /* 343, as fs_params */
+} fs_direct_params;
+
+typedef struct fs_direct_path {
+    float distance;        /* cm */
+    float delay;           /* s, on the impulse response's time axis */
+    float visibility;      /* share of the valid samples with a free line */
+    uint32_t surfaces;     /* surfaces the centre ray crossed (counted ones) */
+    uint32_t samples_valid;
+    float transmission[FS_MAX_BANDS]; /* bands beyond num_bands: 0 */
+} fs_direct_path;          /* an array element: no struct_size */
+
+void fs_direct_params_default(fs_direct_params* p);
+int fs_direct_sample_offsets(int32_t n, float* out /* [n][3] */); /* host only, needs no context */
+int fs_update_direct_paths(fs_context* ctx, const fs_source* sources, int32_t count,
+                           const fs_direct_params* params /* NULL = defaults */, fs_direct_path* out /* [count] */);
 
 /* ---- engine line trace the BVH kernel replaces (UWorld::LineTraceSingleByObjectType; call sites
  *      ARTS.cpp:252-254 any-hit, :340-342 closest-hit). Batch query, host arrays. ------------------- */
