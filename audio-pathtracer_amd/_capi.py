@@ -55,6 +55,7 @@ EXPORTS = [
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
     "fs_set_band_edges", "fs_source_set_orientation", "fs_source_set_directivity", "fs_get_room_parameters",
     "fs_direct_params_default", "fs_direct_sample_offsets", "fs_update_direct_paths",
+    "fs_direct_band_kernels", "fs_direct_render_init", "fs_direct_render_release", "fs_direct_render_process_batch",
 ]
 MAX_DIRECTIVITY_SAMPLES = 181   # FS_MAX_DIRECTIVITY_SAMPLES: 1 degree steps
 COMM_ID_BYTES = 128
@@ -67,6 +68,8 @@ REVERB_ENGINE_PARTITIONED = 1
 MAX_DIRECT_BATCH = 256
 MAX_DIRECT_SAMPLES = 64
 DIRECT_MAX_QUERIES = 32
+MAX_DIRECT_RENDER_BATCH = 256
+DIRECT_RENDER_MAX_TAPS = 2047
 
 
 class SoundParams(C.Structure):
@@ -223,6 +226,14 @@ class DirectPath(C.Structure):
     ]
 
 
+class DirectRenderTarget(C.Structure):
+    """fs_direct_render_target (include/frequensee.h): one source's target of a callback, an array element (no struct_size)"""
+    _fields_ = [
+        ("delay", C.c_float),
+        ("band_gain", C.c_float * MAX_BANDS),
+    ]
+
+
 class FrequenSeeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"frequensee status {code}: {msg}")
@@ -332,6 +343,10 @@ def load():
         "fs_direct_params_default": (None, [C.POINTER(DirectParams)]),
         "fs_direct_sample_offsets": (C.c_int, [i32, f32p]),
         "fs_update_direct_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(DirectParams), C.c_void_p]),
+        "fs_direct_band_kernels": (C.c_int, [i32, f32p, i32, i32, f32p]),
+        "fs_direct_render_init": (C.c_int, [vp, i32, i32, i32, C.c_float]),
+        "fs_direct_render_release": (C.c_int, [vp, i32]),
+        "fs_direct_render_process_batch": (C.c_int, [vp, C.c_void_p, i32, f32p, C.c_void_p, f32p, f32p]),
         "fs_gather_energy": (C.c_int, [vp, i32, f32p, i32]),
         "fs_gather_energy_async": (C.c_int, [vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     }

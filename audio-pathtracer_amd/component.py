@@ -388,6 +388,59 @@ class Context:
                                                    out.ctypes.data if out.size else None))
         return out
 
+    # ---- direct sound on the audio thread: fractional delay + band FIR for all sources of a callback ----
+    RENDER_TARGET_DTYPE = np.dtype([("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,))])
+
+    @staticmethod
+    def direct_band_kernels(sample_rate, bands, taps, edges=None):
+        """fs_direct_band_kernels: the [bands][taps] band kernels (edges: the bands - 1 inner edges in Hz, None = the default
+        octave edges); with the context's sample rate, band count and edges it is the table direct_render_init uploads"""
+        e = None if edges is None else np.ascontiguousarray(edges, dtype=np.float32).reshape(-1)
+        if e is not None and e.shape[0] != max(int(bands) - 1, 0):
+            raise ValueError("edges must hold bands - 1 values")
+        out = np.zeros((max(int(bands), 0), max(int(taps), 0)), np.float32)
+        rc = _capi.load().fs_direct_band_kernels(int(sample_rate), e.ctypes.data if e is not None and e.size else None, int(bands),
+                                                 int(taps), out.ctypes.data if out.size else None)
+        if rc != _capi.OK:
+            raise FrequenSeeError(rc, "fs_direct_band_kernels: bands 1 .. 8, taps odd 1 .. 2047, edges ascending inside (0, sample_rate / 2)")
+        return out
+
+    def direct_render_init(self, src, frame_size=1024, taps=255, max_delay_seconds=1.0):
+        self.check(self.lib.fs_direct_render_init(self.h, src, int(frame_size), int(taps), float(max_delay_seconds)))
+        self._dr_shape = getattr(self, "_dr_shape", {})
+        self._dr_shape[src] = (int(frame_size), int(taps))
+
+    def direct_render_release(self, src):
+        self.check(self.lib.fs_direct_render_release(self.h, src))
+
+    def direct_render_process_batch(self, sources, blocks, targets, want_out=True, want_mix=False):
+        """the direct sound of several sources as one set of launches (include/frequensee.h fs_direct_render_process_batch):
+        blocks [count][frame_size * 2], targets a RENDER_TARGET_DTYPE array or (delay, band_gain) pairs -> out
+        [count][frame_size * 2] (want_out), mix [frame_size * 2] (want_mix), or the pair (out, mix)"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        count = int(srcs.shape[0])
+        a = np.ascontiguousarray(blocks, dtype=np.float32).reshape(count, -1) if count else np.zeros((0, 0), np.float32)
+        shapes = getattr(self, "_dr_shape", {})
+        if count and int(srcs[0]) in shapes and a.shape[1] != 2 * shapes[int(srcs[0])][0]:
+            raise ValueError("every audio block must hold frame_size * 2 interleaved samples")
+        if isinstance(targets, np.ndarray) and targets.dtype == self.RENDER_TARGET_DTYPE:
+            t = np.ascontiguousarray(targets).reshape(-1)
+        else:
+            t = np.zeros(len(targets), dtype=self.RENDER_TARGET_DTYPE)
+            for i, (delay, gains) in enumerate(targets):
+                g = np.asarray(gains, np.float32).reshape(-1)
+                t[i]["delay"] = delay
+                t[i]["band_gain"][:g.shape[0]] = g
+        if t.shape[0] != count:
+            raise ValueError("targets must have one entry per source")
+        out = np.empty_like(a) if want_out else None
+        mix = np.empty(a.shape[1], np.float32) if want_mix else None
+        self.check(self.lib.fs_direct_render_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data, t.ctypes.data,
+                                                           out.ctypes.data if want_out else None, mix.ctypes.data if want_mix else None))
+        if want_out and want_mix:
+            return out, mix
+        return out if want_out else mix
+
     # ---- row f2: reverb plugin convolution ----
     def reverb_init(self, src, frame_size=1024):
         self.check(self.lib.fs_reverb_init(self.h, src, frame_size))
@@ -786,6 +839,43 @@ class FrequenSeeAudioReverbPlugin:
     def SetEngine(self, component: FrequenSeeAudioComponent, engine):
         """not in the reference: the convolution engine of the source's next OnInitSource (_capi.REVERB_ENGINE_*)"""
         self.ctx.reverb_set_engine(component._src, engine)
+
+
+class FrequenSeeAudioOcclusionPlugin:
+    """FFrequenSeeAudioOcclusionPlugin (Private/FrequenSeeAudioOcclusionPlugin.cpp:33-50), with the multiply the reference
+    leaves commented out done: per audio callback every source's block is delayed by its direct path's arrival time and
+    filtered by its per-band transmission.  Distance attenuation stays the host's."""
+
+    def __init__(self, subsystem: AudioRayTracingSubsystem):
+        self.ctx = subsystem.ctx
+        self.FrameSize = 1024
+        self.Taps = 255
+        self.MaxDelaySeconds = 1.0
+
+    def Initialize(self, BufferLength=1024, Taps=255, MaxDelaySeconds=1.0):
+        self.FrameSize, self.Taps, self.MaxDelaySeconds = int(BufferLength), int(Taps), float(MaxDelaySeconds)
+
+    def OnInitSource(self, component: FrequenSeeAudioComponent):
+        self.ctx.direct_render_init(component._src, self.FrameSize, self.Taps, self.MaxDelaySeconds)
+
+    def OnReleaseSource(self, component: FrequenSeeAudioComponent):
+        self.ctx.direct_render_release(component._src)
+
+    def Targets(self, paths):
+        """the callback's targets from UpdateDirectPaths rows: band_gain = transmission, delay = the path's arrival time less
+        the filter's own latency of (Taps - 1) / 2 samples, not below 0"""
+        t = np.zeros(len(paths), dtype=Context.RENDER_TARGET_DTYPE)
+        latency = ((self.Taps - 1) // 2) / float(self.ctx.cfg.sample_rate)
+        for i, p in enumerate(paths):
+            t[i]["delay"] = max(float(p["delay"]) - latency, 0.0)
+            t[i]["band_gain"] = p["transmission"]
+        return t
+
+    def ProcessAudio(self, components, buffers, paths, want_out=True, want_mix=False):
+        """buffers[i] is components[i]'s block, paths[i] its row of UpdateDirectPaths.  Returns what
+        Context.direct_render_process_batch does."""
+        return self.ctx.direct_render_process_batch([c._src for c in components], buffers, self.Targets(paths),
+                                                    want_out=want_out, want_mix=want_mix)
 
 
 class MaterialAcousticProcessor:

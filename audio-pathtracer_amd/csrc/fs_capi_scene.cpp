@@ -387,6 +387,9 @@ int fs_scene_commit(fs_context* ctx) {
         }
         FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         FS_HIP(ctx, hipMalloc((void**)&ctx->d_node_box, sizeof(float4) * 2 * std::max<size_t>(n_nodes, 1)));
+        // (scratch of the refit, but fs_debug_scene_snapshot hands it out: defined — zero — until the first refit writes it,
+        // not whatever the allocation held before)
+        FS_HIP(ctx, hipMemsetAsync(ctx->d_node_box, 0, sizeof(float4) * 2 * std::max<size_t>(n_nodes, 1), ctx->stream));
     }
     if (tb) { const int pr = pack_scene(ctx, n_tris, n_tris); if (pr) return pr; }
     return finish_commit(ctx, nb + n_tris * (sizeof(Tri48) + sizeof(float4)) + mb);

@@ -3,7 +3,7 @@
 // fs_capi_frame.cpp (sources, the traced frame: describe / resources / commit / launch), fs_capi_pipeline.cpp (held frames, the
 // drain), fs_capi_publish.cpp (reconstruct + publish: the IR ring, the host word, the fused launch's reconstruct parts),
 // fs_capi_ir.cpp (reconstruct / tick / IR / energy entry points), fs_capi_comm.cpp (RCCL behind the ABI), fs_capi_reverb.cpp
-// (the reverb callback), fs_capi_direct.cpp (direct paths) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange,
+// (the reverb callback), fs_capi_direct.cpp (direct paths), fs_capi_direct_render.cpp (the direct-sound callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange,
 // material FD).
 //
 // Mirrors the roles of UAudioRayTracingSubsystem (context lifetime, geometry/source registries,
@@ -156,6 +156,13 @@ struct Source {
     int32_t fade_len = 0, fade_pos = 0;
     bool fading = false, fade_primed = false;
     uint64_t fade_gen = 0;
+    // direct sound (fs_direct_render_init; the audio thread's, like the reverb fields): the state block — DirectRenderState, then
+    // at kDirectRenderHeader the history rings [2][dr_ring] — and what the source was initialised with; dr_table is one of
+    // fs_context::dr_tables' (owned by the context); dr_max_delay = D, the largest delay in samples
+    char* d_dr = nullptr;
+    int dr_frame = 0, dr_taps = 0, dr_max_delay = 0;
+    unsigned dr_ring = 0;
+    const float* dr_table = nullptr;
     float occlusion = 1.0f;            // OcclusionAttenuation FSAC.h:130 (1.f until the first UpdateSound)
 };
 
@@ -293,6 +300,14 @@ struct fs_context {
     int direct_cap = 0;
     float* d_direct_off = nullptr;
     uint64_t direct_off_have = 0;
+    // fs_direct_render_process_batch (audio thread): staging of its own — a reverb and a direct callback of different counts may
+    // follow each other in one audio callback, and h_direct / d_direct are the game thread's.  Up: items [count] | in [count][2 frame];
+    // the device also holds the plans [count]; down: out [count][2 frame] | mix [2 frame].  Grown at the first call that needs more.
+    char* h_dr_stage = nullptr; char* d_dr_stage = nullptr;
+    size_t dr_stage_host = 0, dr_stage_dev = 0;   // bytes
+    // the band-kernel tables fs_direct_render_init has built, one per (taps, edges in force); freed with the context
+    struct DirectRenderTable { int taps; std::vector<double> edges; float* d; };
+    std::vector<DirectRenderTable> dr_tables;
     HostBVH bvh;
 
     float listener[3] = {0, 0, 0};

@@ -492,6 +492,45 @@ void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n
 // the window transforms, the products of the two lists (each launched only when it has rows), the inverse and epilogue
 void launch_reverb_part(const ReverbPartItem* items, const ReverbPart& p, int count, int literal_tail, const float* in, float* out,
                         hipStream_t s);
+// fs_direct_render.hip (the direct-sound callback).  A source's state is one device block (Source::d_dr): this header, then at
+// kDirectRenderHeader bytes the two history rings [2][ring] (ring a power of two); zeroed = not primed, nothing heard yet.
+struct DirectRenderState {
+    unsigned n0;           // absolute index of the next block's first sample (wraps; the ring index is n & mask)
+    float d0;              // the delay the last output sample used, in samples
+    int32_t primed;        // 0: the next callback takes its target without a ramp
+    int32_t pad;
+    float g0[FS_MAX_BANDS];   // the gains the last output sample used
+};
+constexpr size_t kDirectRenderHeader = 64;
+static_assert(sizeof(DirectRenderState) == 48 && sizeof(DirectRenderState) <= kDirectRenderHeader, "DirectRenderState: twelve words in front of the rings");
+// one descriptor per row of the call, in list order: the host's staging layout
+struct DirectRenderItem {
+    DirectRenderState* state;
+    float* ring;           // [2][mask + 1]
+    const float* table;    // the band kernels [bands][taps] the source was initialised with
+    unsigned mask;
+    float d1;              // the row's target: delay in samples, gains
+    float g1[FS_MAX_BANDS];
+};
+static_assert(sizeof(DirectRenderItem) == 64, "DirectRenderItem: three pointers and ten words, the host's staging layout");
+// what the plan pass fixes for a row: the state before this callback (its target where the source was not primed) and the
+// slew-limited change of the delay over the block
+struct DirectRenderPlan {
+    unsigned n0;
+    float d0, e;
+    int32_t pad;
+    float g0[FS_MAX_BANDS];
+};
+struct DirectRenderBatch {
+    const DirectRenderItem* items;  // [count]
+    DirectRenderPlan* plans;        // [count] scratch
+    int count, frame, taps, bands;
+    const float* in;                // [count][2 * frame] interleaved
+    float* out;                     // [count][2 * frame] interleaved
+    float* mix;                     // [2 * frame], or null
+};
+// the plan pass, the render pass (which also appends the blocks to the rings), the mix (when b.mix)
+void launch_direct_render(const DirectRenderBatch& b, hipStream_t s);
 void launch_add_energy(float* energy_row, int num_bins, float delay_s, float e, hipStream_t s);
 // dynamic LDS the traversal kernels of a frame need for a tree with `stack_rows` stack rows: the larger of the walk
 // kernel (stack + work-sharing area) and the connect kernels (stack + [bands][bins] histogram + work-sharing area)

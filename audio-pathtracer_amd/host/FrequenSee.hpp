@@ -79,6 +79,7 @@ public:
 
 private:
     friend class AudioRayTracingSubsystem;
+    friend class FrequenSeeAudioOcclusionPlugin;
     FVector Location_;
     AudioRayTracingSubsystem* SubSys_ = nullptr;
     fs_source Handle_ = -1;
@@ -258,6 +259,7 @@ private:
     bool Streamed_ = false;
     friend class FrequenSeeAudioComponent;
     friend class MaterialAcousticProcessor;
+    friend class FrequenSeeAudioOcclusionPlugin;
 };
 
 inline FrequenSeeAudioComponent::~FrequenSeeAudioComponent() { OnUnregister(); }
@@ -365,6 +367,51 @@ public:
                                             Out.Transmitted.data()));
         return Out;
     }
+
+private:
+    AudioRayTracingSubsystem* SubSys_;
+};
+
+// FFrequenSeeAudioOcclusionPlugin (Private/FrequenSeeAudioOcclusionPlugin.cpp:33-50) with the multiply the reference leaves
+// commented out done: per audio callback every source's block is delayed by its direct path's arrival time (a fractional,
+// slew-limited delay: the Doppler shift) and filtered by its per-band transmission — fs_direct_render_process_batch, one call
+// for all sources.  Distance attenuation stays the host's.
+class FrequenSeeAudioOcclusionPlugin {
+public:
+    explicit FrequenSeeAudioOcclusionPlugin(AudioRayTracingSubsystem& SubSys) : SubSys_(&SubSys) {}
+    void Initialize(int BufferLength = 1024, int TapCount = 255, float MaxDelay = 1.0f) {
+        FrameSize = BufferLength; Taps = TapCount; MaxDelaySeconds = MaxDelay;
+    }
+    void OnInitSource(const FrequenSeeAudioComponent& C) {
+        SubSys_->Check(fs_direct_render_init(SubSys_->Ctx_, C.Handle_, FrameSize, Taps, MaxDelaySeconds));
+    }
+    void OnReleaseSource(const FrequenSeeAudioComponent& C) { SubSys_->Check(fs_direct_render_release(SubSys_->Ctx_, C.Handle_)); }
+    // the callback's targets from UpdateDirectPaths rows: band_gain = transmission, delay = the path's arrival time less the
+    // filter's own latency of (Taps - 1) / 2 samples, not below 0
+    std::vector<fs_direct_render_target> Targets(const std::vector<fs_direct_path>& Paths) const {
+        std::vector<fs_direct_render_target> T(Paths.size());
+        const double Latency = (double)((Taps - 1) / 2) / (double)SampleRate;
+        for (size_t i = 0; i < Paths.size(); ++i) {
+            T[i].delay = (float)std::max((double)Paths[i].delay - Latency, 0.0);
+            for (int b = 0; b < FS_MAX_BANDS; ++b) T[i].band_gain[b] = Paths[i].transmission[b];
+        }
+        return T;
+    }
+    // In [count][FrameSize * 2] interleaved stereo, row i for Sources[i] and Paths[i]; Out [count][FrameSize * 2] or nullptr,
+    // Mix [FrameSize * 2] (the fp32 sum of the rows in list order) or nullptr
+    void ProcessAudio(const std::vector<FrequenSeeAudioComponent*>& Sources, const float* In, const std::vector<fs_direct_path>& Paths,
+                      float* Out, float* Mix = nullptr) {
+        std::vector<fs_source> H;
+        for (const auto* s : Sources) H.push_back(s->Handle_);
+        const std::vector<fs_direct_render_target> T = Targets(Paths);
+        if (T.size() != H.size()) throw std::runtime_error("FrequenSee: one direct path per source");
+        SubSys_->Check(fs_direct_render_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, T.data(), Out, Mix));
+    }
+
+    int FrameSize = 1024;   // AudioCallbackBufferFrameSize, Config/DefaultEngine.ini:13
+    int Taps = 255;
+    float MaxDelaySeconds = 1.0f;
+    int SampleRate = 48000;   // fs_config_default's, FSAC.h:133
 
 private:
     AudioRayTracingSubsystem* SubSys_;

@@ -54,6 +54,7 @@
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
  *             fs_source_set_orientation fs_source_set_directivity fs_get_room_parameters
  *             fs_direct_params_default fs_direct_sample_offsets fs_update_direct_paths
+ *             fs_direct_band_kernels fs_direct_render_init fs_direct_render_release fs_direct_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
  * Environment variables (FS_*) are tuning and diagnostic knobs only; all of them are read ONCE — at fs_context_create, at a
  * scene commit (builder knobs) or at the first launch of a kernel family — never per frame.
@@ -755,6 +756,77 @@ int fs_reverb_set_crossfade(fs_context* ctx, fs_source src, int32_t samples);
 #define FS_REVERB_ENGINE_DIRECT      0   /* the tap-by-tap kernels, the default */
 #define FS_REVERB_ENGINE_PARTITIONED 1
 int fs_reverb_set_engine(fs_context* ctx, fs_source src, int32_t engine);
+
+/* ---- direct sound on the audio thread (EXTENDED): what fs_update_direct_paths' rows are rendered with ---------------------
+ *      The reference's slot is FFrequenSeeAudioOcclusionPlugin::ProcessAudio (Private/FrequenSeeAudioOcclusionPlugin.cpp:33-50),
+ *      which fetches the occlusion scalar and leaves the multiply commented out; its DopplerActor fakes the pitch shift with a
+ *      SetPitchMultiplier.  Here both are one block per source, for all sources of a callback in one set of launches: a
+ *      time-varying fractional delay (which IS the Doppler shift) and a short linear-phase FIR whose taps are
+ *      sum_b band_gain[b] * k_b, k_b a fixed band kernel.  No panning, no distance attenuation: those stay the host's.
+ *   Band kernels.  T = taps, odd, 1 .. FS_DIRECT_RENDER_MAX_TAPS; c = (T - 1) / 2; m = t - c.
+ *     w[m] = 0.5 + 0.5 cos(pi m / (c + 1));  L_f[m] = sin(2 pi f m / fs) / (pi m) for m != 0, L_f[0] = 2 f / fs.
+ *     Edges e_0 = 0 (L := 0); e_1 .. e_{B-1} the inner edges — the floats given, or 125 * 2^(b - 0.5) when edges_hz is NULL;
+ *     e_B = Nyquist with L := the unit impulse at m = 0, taken exactly, so that the bands telescope to a delta.
+ *     k_b[t] = w[m] (L_{e_{b+1}}[m] - L_{e_b}[m]), computed on the host in double and rounded to float once.
+ *   fs_direct_band_kernels writes that table [bands][taps]; host only, no context, no device.  FS_ERR_INVALID_ARGUMENT: out
+ *   NULL, bands outside 1 .. FS_MAX_BANDS, taps even or out of range, sample_rate < 1, edges that are not finite, not strictly
+ *   ascending or not inside (0, sample_rate / 2).  fs_direct_render_init builds exactly this table from the context's sample
+ *   rate, band count and the edges in force (fs_set_band_edges, else the defaults) and uploads it once per (context, T, edges).
+ *   What the formula gives (measured on the CPU): with unit gains the taps are a delta within 1.3e-8; T = 255 separates the
+ *   octave bands from 500 Hz up and blends 125 and 250 Hz, T = 1023 separates all eight; the output is late by c samples —
+ *   2.6 ms at the suggested default T = 255 and 48 kHz — which the host may subtract from `delay`.
+ *   State per source, all device-resident, all allocated by fs_direct_render_init: a zeroed history ring per channel, an
+ *   absolute sample counter n0, the last delay d0 (samples), the last gains g0, a primed flag.  D = ceil(max_delay_seconds fs);
+ *   the ring is the smallest power of two >= D + T + 1 + F floats, and D + T + 1 + F <= 2^20; 16 <= F = frame_size <= 16384:
+ *   otherwise FS_ERR_INVALID_ARGUMENT (also for even T, and for edges in force that do not lie in (0, fs / 2)).  Calling it again
+ *   re-initialises the source with the new F, T and D.  fs_direct_render_release: history := 0, and the next callback takes
+ *   its target without a ramp (a source without fs_direct_render_init: nothing to do, FS_OK).
+ *   One callback, per row.  fp32 throughout; every operation is rounded on its own, in the order written (the library is built
+ *   with -ffp-contract=off); numpy float32 computes the same bits.
+ *     Target.  d1 = delay * (float)fs; g1 = band_gain.  A delay that is negative, not finite or with d1 > D, or a gain (of a
+ *       band < num_bands) that is negative or not finite, refuses the WHOLE call: nothing changes, nothing is enqueued.
+ *     First callback (not primed): d0 := d1, g0 := g1.
+ *     Slew limit.  e = clamp(d1 - d0, -F/2, +F/2): a teleport glides at half a sample per sample instead of clicking.  The
+ *       state after the call is d0 + e — what the last output sample used — and g1.
+ *     Taps.  cA[t] = sum over b ascending of (c = c + gA[b] * k_b[t], from 0), A = 0, 1;  dc[t] = c1[t] - c0[t].
+ *     Output s (0 .. F-1) of channel ch, x(n) the channel's sample at absolute index n (zero before the stream began):
+ *       a = (float)(s + 1) / (float)F;  d = d0 + a * e;  i = floorf(d), f = d - (float)i;  c = c0[t] + a * dc[t];
+ *       p = n0 + s - t - i;  v = x(p) + f * (x(p - 1) - x(p));
+ *       four accumulators: acc_j takes the taps t = j (mod 4) in ascending t, acc_j = acc_j + c * v;
+ *       y = (acc_0 + acc_1) + (acc_2 + acc_3).  Not clamped (the reference's multiply has no clamp).
+ *     The accumulator order is part of the contract: a source gives the same bits served alone or in any batch.
+ *     Afterwards the block enters the history and n0 += F.
+ *   fs_direct_render_process_batch.
+ *     in  [count][frame_size * 2]  interleaved stereo, host; row i belongs to sources[i] and targets[i]
+ *     out [count][frame_size * 2]  or NULL
+ *     mix [frame_size * 2]         or NULL; out == NULL && mix == NULL is FS_ERR_INVALID_ARGUMENT
+ *    1. Per row, in list order, the rule above: out[i] and the state of sources[i] afterwards are, to the bit, the same whether
+ *       the sources are served by one call or by several.
+ *    2. mix[j] = ((out[0][j] + out[1][j]) + out[2][j]) + ... in fp32, in list order; computed on the device in that fixed
+ *       order (reproducible); with out == NULL only mix comes back from the device.
+ *    3. 1 <= count <= FS_MAX_DIRECT_RENDER_BATCH, every source has had fs_direct_render_init, all share one frame size and one
+ *       T, no handle appears twice, every target is legal: otherwise FS_ERR_INVALID_ARGUMENT (FS_ERR_BAD_HANDLE for a bad
+ *       handle; a null pointer FS_ERR_INVALID_ARGUMENT, no device FS_ERR_NO_DEVICE).  A refused call changes nothing.
+ *    4. Audio-thread safe: runs on the context's reverb stream and waits for that stream only.  It reads no impulse response
+ *       and takes no source mutex.  Not concurrent with fs_direct_render_init / _release of a listed source or another
+ *       callback (reverb or direct): ONE audio render thread runs the callbacks of a context.
+ *    5. Staging of its own, owned by the context (pinned host + device; not the reverb callback's and not
+ *       fs_update_direct_paths'), grown at the FIRST call that needs more (count x frame_size); a call whose count and frame
+ *       size the context has already seen allocates no device or pinned memory.  One copy up, a number of launches that does
+ *       not grow with count, one copy back, one wait.
+ *   fs_source_destroy and fs_context_destroy free everything. */
+#define FS_MAX_DIRECT_RENDER_BATCH 256
+#define FS_DIRECT_RENDER_MAX_TAPS  2047
+typedef struct fs_direct_render_target {
+    float delay;                   /* s, >= 0: fs_direct_path.delay, less whatever latency the host compensates */
+    float band_gain[FS_MAX_BANDS]; /* finite, >= 0; entries beyond num_bands ignored */
+} fs_direct_render_target;         /* an array element: no struct_size; 36 bytes */
+int fs_direct_band_kernels(int32_t sample_rate, const float* edges_hz /* [bands - 1], or NULL = the default octave edges */,
+                           int32_t bands, int32_t taps, float* out /* [bands][taps] */);
+int fs_direct_render_init(fs_context* ctx, fs_source src, int32_t frame_size, int32_t taps, float max_delay_seconds);
+int fs_direct_render_release(fs_context* ctx, fs_source src);
+int fs_direct_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in,
+                                   const fs_direct_render_target* targets /* [count] */, float* out, float* mix);
 
 /* ---- row f4: frequency-dependent material response of one audio block ------------------------------------
  *      UMaterialAcousticProcessor::ApplyMaterialFD (Private/MaterialAcousticProcessor.cpp:8-107, MAP.cpp):
