@@ -55,6 +55,7 @@ EXPORTS = [
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
     "fs_set_band_edges", "fs_source_set_orientation", "fs_source_set_directivity", "fs_get_room_parameters",
     "fs_direct_params_default", "fs_direct_sample_offsets", "fs_update_direct_paths",
+    "fs_reflection_params_default", "fs_update_reflection_paths",
     "fs_direct_band_kernels", "fs_direct_render_init", "fs_direct_render_release", "fs_direct_render_process_batch",
 ]
 MAX_DIRECTIVITY_SAMPLES = 181   # FS_MAX_DIRECTIVITY_SAMPLES: 1 degree steps
@@ -69,6 +70,10 @@ MAX_DIRECT_BATCH = 256
 MAX_DIRECT_SAMPLES = 64
 DIRECT_MAX_QUERIES = 32
 MAX_DIRECT_RENDER_BATCH = 256
+MAX_REFLECTIONS = 16
+MAX_REFLECTION_CANDIDATES = 256
+MAX_REFLECTION_BATCH = 256
+REFLECTION_OVERFLOW = 1
 DIRECT_RENDER_MAX_TAPS = 2047
 
 
@@ -226,6 +231,39 @@ class DirectPath(C.Structure):
     ]
 
 
+class ReflectionParams(C.Structure):
+    """fs_reflection_params (include/frequensee.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("max_paths", C.c_int32),
+        ("max_candidates", C.c_int32),
+        ("margin", C.c_float),
+        ("step", C.c_float),
+        ("offset", C.c_float),
+        ("pullback", C.c_float),
+        ("dist_divisor", C.c_float),
+        ("sound_speed", C.c_float),
+    ]
+
+
+class ReflectionPath(C.Structure):
+    """fs_reflection_path (include/frequensee.h): one reflection of one source, an array element (no struct_size)"""
+    _fields_ = [
+        ("length", C.c_float),
+        ("delay", C.c_float),
+        ("point", C.c_float * 3),
+        ("direction", C.c_float * 3),
+        ("triangle", C.c_uint32),
+        ("material", C.c_uint32),
+        ("reflectance", C.c_float * MAX_BANDS),
+    ]
+
+
+class ReflectionRow(C.Structure):
+    """fs_reflection_row (include/frequensee.h): one source's counts, an array element (no struct_size)"""
+    _fields_ = [(k, C.c_uint32) for k in ("candidates", "found", "returned", "flags")]
+
+
 class DirectRenderTarget(C.Structure):
     """fs_direct_render_target (include/frequensee.h): one source's target of a callback, an array element (no struct_size)"""
     _fields_ = [
@@ -343,6 +381,8 @@ def load():
         "fs_direct_params_default": (None, [C.POINTER(DirectParams)]),
         "fs_direct_sample_offsets": (C.c_int, [i32, f32p]),
         "fs_update_direct_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(DirectParams), C.c_void_p]),
+        "fs_reflection_params_default": (None, [C.POINTER(ReflectionParams)]),
+        "fs_update_reflection_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(ReflectionParams), C.c_void_p, C.c_void_p]),
         "fs_direct_band_kernels": (C.c_int, [i32, f32p, i32, i32, f32p]),
         "fs_direct_render_init": (C.c_int, [vp, i32, i32, i32, C.c_float]),
         "fs_direct_render_release": (C.c_int, [vp, i32]),
@@ -377,6 +417,14 @@ def default_sound_params(**kw) -> SoundParams:
 def default_direct_params(**kw) -> DirectParams:
     p = DirectParams()
     load().fs_direct_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_reflection_params(**kw) -> ReflectionParams:
+    p = ReflectionParams()
+    load().fs_reflection_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -388,6 +388,24 @@ class Context:
                                                    out.ctypes.data if out.size else None))
         return out
 
+    # ---- reflection paths: the first-order specular reflections of every source of a tick ----
+    REFLECTION_ROW_DTYPE = np.dtype([("candidates", np.uint32), ("found", np.uint32), ("returned", np.uint32), ("flags", np.uint32)])
+    REFLECTION_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("point", np.float32, (3,)), ("direction", np.float32, (3,)),
+                                 ("triangle", np.uint32), ("material", np.uint32), ("reflectance", np.float32, (_capi.MAX_BANDS,))])
+
+    def reflection_paths(self, sources, **params):
+        """fs_update_reflection_paths: (rows [count], paths [count][max_paths]) as structured arrays — per listed source the counts
+        (candidates, found, returned, flags) and its `returned` shortest reflections (length cm, delay s, point, direction from the
+        listener, triangle, material, reflectance [8]; entries beyond `returned` are zero); params = the fields of
+        fs_reflection_params (max_paths, max_candidates, margin, step, offset, pullback, dist_divisor, sound_speed)"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        p = _capi.default_reflection_params(**params)
+        rows = np.zeros(srcs.shape[0], dtype=self.REFLECTION_ROW_DTYPE)
+        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=self.REFLECTION_DTYPE)
+        self.check(self.lib.fs_update_reflection_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
+                                                       rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
+        return rows, paths
+
     # ---- direct sound on the audio thread: fractional delay + band FIR for all sources of a callback ----
     RENDER_TARGET_DTYPE = np.dtype([("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,))])
 
@@ -766,6 +784,17 @@ class AudioRayTracingSubsystem:
         self._commit()
         step = _capi.MAX_DIRECT_BATCH
         return np.concatenate([self.ctx.direct_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)])
+
+    def UpdateReflectionPaths(self, **params):
+        """the first-order specular reflections of all active sources: (rows, paths), row i and paths[i] for ActiveSources[i]
+        (Context.reflection_paths; more than 256 sources take one call per 256)"""
+        srcs = [s._src for s in self.ActiveSources]
+        if not srcs:
+            return np.zeros(0, dtype=Context.REFLECTION_ROW_DTYPE), np.zeros((0, 0), dtype=Context.REFLECTION_DTYPE)
+        self._commit()
+        step = _capi.MAX_REFLECTION_BATCH
+        parts = [self.ctx.reflection_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
+        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
 
     def SetPipelining(self, depth):
         """fs_set_pipelining: Tick then updates the sources one after the other like the reference's loop (ARTS.cpp:60-68),

@@ -655,6 +655,8 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->h_direct) (void)hipHostFree(ctx->h_direct);
         if (ctx->d_direct) (void)hipFree(ctx->d_direct);
         if (ctx->d_direct_off) (void)hipFree(ctx->d_direct_off);
+        if (ctx->h_reflect) (void)hipHostFree(ctx->h_reflect);
+        if (ctx->d_reflect) (void)hipFree(ctx->d_reflect);
         if (ctx->h_rev_stage) (void)hipHostFree(ctx->h_rev_stage);
         if (ctx->d_rev_stage) (void)hipFree(ctx->d_rev_stage);
         if (ctx->h_dr_stage) (void)hipHostFree(ctx->h_dr_stage);

@@ -3,7 +3,7 @@
 // fs_capi_frame.cpp (sources, the traced frame: describe / resources / commit / launch), fs_capi_pipeline.cpp (held frames, the
 // drain), fs_capi_publish.cpp (reconstruct + publish: the IR ring, the host word, the fused launch's reconstruct parts),
 // fs_capi_ir.cpp (reconstruct / tick / IR / energy entry points), fs_capi_comm.cpp (RCCL behind the ABI), fs_capi_reverb.cpp
-// (the reverb callback), fs_capi_direct.cpp (direct paths), fs_capi_direct_render.cpp (the direct-sound callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange,
+// (the reverb callback), fs_capi_direct.cpp (direct paths), fs_capi_reflect.cpp (reflection paths), fs_capi_direct_render.cpp (the direct-sound callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange,
 // material FD).
 //
 // Mirrors the roles of UAudioRayTracingSubsystem (context lifetime, geometry/source registries,
@@ -300,6 +300,11 @@ struct fs_context {
     int direct_cap = 0;
     float* d_direct_off = nullptr;
     uint64_t direct_off_have = 0;
+    // fs_update_reflection_paths (fs_capi_reflect.cpp): staging of its own, sized for the largest max_paths and max_candidates so that
+    // only a larger count grows it.  Pinned: sources [reflect_cap] float4 | the copy's target, rows [count] then paths [count][max_paths].
+    // Device: sources [reflect_cap] float4 | counters [reflect_cap] | candidates [reflect_cap][FS_MAX_REFLECTION_CANDIDATES] | rows and paths.
+    char* h_reflect = nullptr; char* d_reflect = nullptr;
+    int reflect_cap = 0;
     // fs_direct_render_process_batch (audio thread): staging of its own — a reverb and a direct callback of different counts may
     // follow each other in one audio callback, and h_direct / d_direct are the game thread's.  Up: items [count] | in [count][2 frame];
     // the device also holds the plans [count]; down: out [count][2 frame] | mix [2 frame].  Grown at the first call that needs more.

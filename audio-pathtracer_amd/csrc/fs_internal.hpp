@@ -423,6 +423,23 @@ struct DirectKParams {
     float radius, step, pullback, dist_divisor, sound_speed;
 };
 void launch_direct_paths(const DeviceScene& sc, const DirectKParams& dp, hipStream_t s);
+// fs_reflect.hip (fs_update_reflection_paths): reflect_scan_kernel, a thread per triangle record against every row of the call,
+// appends the filter's survivors to the rows' candidate lists; reflect_confirm_kernel, a wave per row, runs the two legs of every
+// candidate and writes the row and its paths.  src = the rows' sources, xyz + the source's actor id as bits (device); counters
+// [count] zeroed ahead of the scan; cand [count][max_candidates] leaf positions; rows [count] and paths [count][max_paths] = the
+// device staging the copy back reads.
+struct ReflectKParams {
+    const float4* src;
+    uint32_t* counters;
+    uint32_t* cand;
+    fs_reflection_row* rows;
+    fs_reflection_path* paths;
+    float lis[3];
+    uint32_t lis_object;
+    int32_t count, max_paths, max_candidates, num_bands;
+    float margin, step, offset, pullback, dist_divisor, sound_speed;
+};
+void launch_reflection_paths(const DeviceScene& sc, const ReflectKParams& rp, hipStream_t s);
 constexpr int kReverbRing = 65536;   // per-channel history ring (floats), matches kRevRing in the kernels
 // fs_reverb.hip (the reverb callback): one descriptor per row of the call, in list order, read by every kernel of the callback.
 struct ReverbItem {

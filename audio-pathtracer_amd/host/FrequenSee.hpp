@@ -195,6 +195,25 @@ public:
             Check(fs_update_direct_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_DIRECT_BATCH), P, Out.data() + i));
         return Out;
     }
+    // the first-order specular reflections of every active source: Rows[i] and Paths[i * MaxPaths .. ) for ActiveSources[i]
+    // (fs_update_reflection_paths; MaxPaths = P->max_paths, the default's without P; one call per FS_MAX_REFLECTION_BATCH sources)
+    struct ReflectionPaths { int32_t MaxPaths = 0; std::vector<fs_reflection_row> Rows; std::vector<fs_reflection_path> Paths; };
+    ReflectionPaths UpdateReflectionPaths(const fs_reflection_params* P = nullptr) {
+        fs_reflection_params Def;
+        fs_reflection_params_default(&Def);
+        ReflectionPaths Out;
+        Out.MaxPaths = P ? P->max_paths : Def.max_paths;
+        if (ActiveSources.empty()) return Out;
+        Out.Rows.resize(ActiveSources.size());
+        Out.Paths.resize(ActiveSources.size() * (size_t)std::min(std::max(Out.MaxPaths, 1), FS_MAX_REFLECTIONS));   // (a bad max_paths is refused below)
+        Commit();
+        std::vector<fs_source> H;
+        for (auto* s : ActiveSources) H.push_back(s->Handle_);
+        for (size_t i = 0; i < H.size(); i += FS_MAX_REFLECTION_BATCH)
+            Check(fs_update_reflection_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_REFLECTION_BATCH), P,
+                                             Out.Rows.data() + i, Out.Paths.data() + i * (size_t)Out.MaxPaths));
+        return Out;
+    }
     // fs_set_pipelining (0 off, 1, 2): Tick streams the sources instead of batching them
     void SetPipelining(int Depth) { Check(fs_set_pipelining(Ctx_, Depth)); Streamed_ = Depth != 0; }
     // fs_set_frames_per_launch (1 .. 4): consecutive streamed frames share a launch (each keeps its seed, buffer and IR)

@@ -54,6 +54,7 @@
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
  *             fs_source_set_orientation fs_source_set_directivity fs_get_room_parameters
  *             fs_direct_params_default fs_direct_sample_offsets fs_update_direct_paths
+ *             fs_reflection_params_default fs_update_reflection_paths
  *             fs_direct_band_kernels fs_direct_render_init fs_direct_render_release fs_direct_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
  * Environment variables (FS_*) are tuning and diagnostic knobs only; all of them are read ONCE — at fs_context_create, at a
@@ -647,6 +648,87 @@ void fs_direct_params_default(fs_direct_params* p);
 int fs_direct_sample_offsets(int32_t n, float* out /* [n][3] */); /* host only, needs no context */
 int fs_update_direct_paths(fs_context* ctx, const fs_source* sources, int32_t count,
                            const fs_direct_params* params /* NULL = defaults */, fs_direct_path* out /* [count] */);
+
+/* ---- reflection paths (EXTENDED): the first-order specular reflections of every source of a tick -------------------------
+ * What a host places between the direct sound (fs_update_direct_paths) and the late field (the traced impulse response, fs_reverb_*):
+ * per source the discrete early reflections off single triangles — length, arrival time on the impulse response's time axis,
+ * reflection point, the direction the listener hears it from, the reflector and its specular gain per band.  (In the traced impulse
+ * response such a reflection is a 1 ms energy bin: no arrival time finer than the bin, no direction, no identity from tick to tick.)
+ * The reflectors are found by an exhaustive scan of the triangles, not by sampling: no noise, no seed.  Specified to the bit, like
+ * direct paths: the library is built with -ffp-contract=off; below, every fp32 operation is rounded on its own, in the order written,
+ * fmaf is a fused multiply-add, a dot product or squared length a.b is (a.x b.x + a.y b.y) + a.z b.z, and cross(a, b) has the
+ * components (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x): product, product, subtract.  numpy float32 scalars compute the
+ * same bits.  Every discrete decision that could be marginal beyond the filter — which triangle a reflection point lies in, whether a
+ * leg is blocked — is taken by the closest-hit query fs_trace_rays answers.
+ *   Records.  Triangle i (input order, vertices v0 v1 v2 in force) is known by v0, e1 = v1 - v0, e2 = v2 - v0: one fp32 subtraction
+ * per component.  That is exactly what the host build, the device build, fs_scene_update_triangles and the transform kernel of
+ * fs_scene_set_object_transforms write into a triangle's record (the last from the vertices it has just computed).
+ *   Per source at S with fs_source_set_object id so, listener at L with fs_listener_set_object id lo, for every triangle i:
+ *   1. Filter (part of the definition).  n = cross(e1, e2); nn = n.n; nn == 0: rejected.  hS = (S - v0).n, hL = (L - v0).n; kept only
+ *      if (hS > 0 && hL > 0) || (hS < 0 && hL < 0).  k = (2 hS) / nn; S' = S - k n per component (the mirror image); D = S' - L.
+ *      Moeller-Trumbore on the segment L + s D:  p = cross(D, e2); det = e1.p; det == 0: rejected; inv = 1.0f / det; tv = L - v0;
+ *      u = (tv.p) inv; q = cross(tv, e1); v = (D.q) inv; s = (e2.q) inv.  Passed iff u >= -m && v >= -m && u + v <= 1 + m && s > 0 &&
+ *      s < 1 with m = margin.  A triangle whose object id equals so or lo, that id not FS_NO_OBJECT, is never a candidate.
+ *      candidates = the number of triangles that pass.  candidates > max_candidates: flags = FS_REFLECTION_OVERFLOW, found =
+ *      returned = 0 and nothing else of the row is computed (the count is exact even where the list is capped).
+ *   2. Leg 1, per candidate.  len1 = sqrtf(D.D); d = D (1.0f / len1); o = L; rem = len1; acc = 0.  For q = 0 ..
+ *      FS_DIRECT_MAX_QUERIES - 1: the closest hit of (o, d) within tmax = rem (fs_trace_rays' answer, ignoring nothing) at distance t.
+ *      No hit: rejected.  The hit triangle belongs to an own actor (its id equals so or lo, not FS_NO_OBJECT): adv = t + step;
+ *      o = fmaf(adv, d, o) per component; rem = rem - adv; acc = acc + adv; next query.  The hit triangle is i: t1 = acc + t,
+ *      P = fmaf(t, d, o) per component, accepted.  Any other triangle: rejected.  Out of queries: rejected.
+ *   3. Leg 2.  e = S - P; len2 = sqrtf(e.e); len2 == 0: rejected.  d2 = e (1.0f / len2); o2 = fmaf(offset, d2, P) per component;
+ *      chain(o2, d2, (len2 - offset) - pullback) of "direct paths" with max_surfaces = 0 and this call's step.  The candidate is
+ *      CONFIRMED iff the chain reached with crossed == 0.  No transmission is applied on reflection legs: a leg either passes own
+ *      actors only, or the reflection does not exist.
+ *   4. Row.  length = t1 + len2; delay = (length / dist_divisor) / sound_speed; point = P; direction = d; triangle = i; material = the
+ *      triangle's material id; reflectance[b] = the specular gain of that material, the value the specular lobe of
+ *      FS_FLAG_MATERIAL_LOBES multiplies in, for b < num_bands and 0 beyond; a triangle with FS_NO_MATERIAL, an id >= num_materials or
+ *      a scene without a material table has reflectance 1 in every band (such a surface applies no material factor in the trace
+ *      either).  found = the number confirmed.  The confirmed paths are ordered by (length as fp32 ascending, triangle ascending); the
+ *      first returned = min(found, max_paths) are written to the source's max_paths entries of `paths`, the entries beyond
+ *      `returned` (all of them for an overflowed row) as all-zero bytes.  Nothing depends on which builder made the tree, on the order
+ *      in which candidates were collected, or on count.  An empty committed scene gives rows of zeros.
+ *   Errors.  FS_ERR_INVALID_ARGUMENT: ctx, sources, rows or paths NULL, count < 1 or > FS_MAX_REFLECTION_BATCH, a struct_size other
+ * than sizeof(fs_reflection_params), a field outside its range or not finite.  FS_ERR_NO_DEVICE, FS_ERR_BAD_HANDLE,
+ * FS_ERR_NOT_COMMITTED as elsewhere.  A handle may appear twice: the rows are independent.  A refused call writes nothing.
+ *   Ordering and cost.  Like fs_update_direct_paths: a finished progressive build is installed and a pending refit (also one left
+ * by fs_scene_set_object_transforms) runs first; then the source table's upload, one clear, TWO launches on the compute stream — the
+ * scan of all triangles against all rows, the confirmation of the candidates, a wave per row — one copy back and one wait, whatever
+ * count is.  Held frames are not flushed; no state of the sources changes (energy, impulse response, occlusion scalar).  Staging of
+ * its own (not that of fs_update_direct_paths) grows at the first call that needs more: a call with a count the context has seen
+ * allocates nothing.  Sharded contexts: any rank may call it, no collective. */
+#define FS_MAX_REFLECTIONS            16
+#define FS_MAX_REFLECTION_CANDIDATES 256
+#define FS_MAX_REFLECTION_BATCH      256
+#define FS_REFLECTION_OVERFLOW        1u   /* fs_reflection_row.flags */
+typedef struct fs_reflection_params {
+    uint32_t struct_size;     /* = sizeof(fs_reflection_params) */
+    int32_t  max_paths;       /* 1 .. FS_MAX_REFLECTIONS, default 8: rows of `paths` per source */
+    int32_t  max_candidates;  /* 1 .. FS_MAX_REFLECTION_CANDIDATES, default 256 */
+    float    margin;          /* barycentric slack of the filter, >= 0, finite; default 1e-3 */
+    float    step;            /* cm a leg advances past a passed own-actor surface, >= 0; default 0.1 */
+    float    offset;          /* cm the second leg starts off the reflector, >= 0; default 0.1 */
+    float    pullback;        /* cm the second leg stops short of the source, >= 0; default 0.1 */
+    float    dist_divisor;    /* 1000, as fs_params */
+    float    sound_speed;     /* 343, as fs_params */
+} fs_reflection_params;
+
+typedef struct fs_reflection_path {
+    float    length;          /* cm, listener -> reflection point -> source */
+    float    delay;           /* s, on the impulse response's time axis: (length / dist_divisor) / sound_speed */
+    float    point[3];        /* the reflection point P */
+    float    direction[3];    /* unit, from the listener towards P: what a host pans by */
+    uint32_t triangle;        /* input index of the reflector */
+    uint32_t material;        /* its material id (FS_NO_MATERIAL possible) */
+    float    reflectance[FS_MAX_BANDS]; /* bands beyond num_bands: 0 */
+} fs_reflection_path;         /* an array element: no struct_size; 72 bytes */
+
+typedef struct fs_reflection_row { uint32_t candidates, found, returned, flags; } fs_reflection_row;
+
+void fs_reflection_params_default(fs_reflection_params* p);
+int fs_update_reflection_paths(fs_context* ctx, const fs_source* sources, int32_t count,
+                               const fs_reflection_params* params /* NULL = defaults */,
+                               fs_reflection_row* rows /* [count] */, fs_reflection_path* paths /* [count][max_paths] */);
 
 /* ---- engine line trace the BVH kernel replaces (UWorld::LineTraceSingleByObjectType; call sites
  *      ARTS.cpp:252-254 any-hit, :340-342 closest-hit). Batch query, host arrays. ------------------- */
