@@ -108,7 +108,11 @@ enum {
                                              * deposits into the buffer the previous frame of this source used, without clearing it
                                              * (single-GPU contexts only; with FS_FLAG_DETERMINISTIC the fixed-point histogram
                                              * accumulates — keep one mode for the whole accumulation) */
-#define FS_FLAG_COSINE_SAMPLING 4u          /* cosine-weighted bounce instead of VRandCone(n, 90 deg) */
+#define FS_FLAG_COSINE_SAMPLING 4u          /* cosine-weighted bounce instead of VRandCone(n, 90 deg).  Both maps build the direction in the
+                                             * tangent frame of Duff et al. 2017, which reads copysign(1, n.z) — the sign of a ZERO too: off
+                                             * a wall with n.z = 0 the bounce depends on whether the hit normal's zero is +0 (the triangle's
+                                             * winding normal e1 x e2) or -0 (that normal negated, zeros included, because it faced along
+                                             * the ray).  DESIGN.md section 4 has the formulas. */
 #define FS_FLAG_ALL_CONNECTIONS 16u         /* row f3, the reference's unfinished draft (Is_NaiveConnections, ARTS.cpp:518-546): connect every
                                              * forward prefix F0..Fi with every backward prefix B0..Bj of a pair (visibility test and
                                              * EvaluatePath as for the end-to-end connection) and combine the (i, j) that give the same
