@@ -57,6 +57,7 @@ EXPORTS = [
     "fs_direct_params_default", "fs_direct_sample_offsets", "fs_update_direct_paths",
     "fs_reflection_params_default", "fs_update_reflection_paths",
     "fs_direct_band_kernels", "fs_direct_render_init", "fs_direct_render_release", "fs_direct_render_process_batch",
+    "fs_reflection_render_init", "fs_reflection_render_release", "fs_reflection_render_process_batch",
 ]
 MAX_DIRECTIVITY_SAMPLES = 181   # FS_MAX_DIRECTIVITY_SAMPLES: 1 degree steps
 COMM_ID_BYTES = 128
@@ -75,6 +76,8 @@ MAX_REFLECTION_CANDIDATES = 256
 MAX_REFLECTION_BATCH = 256
 REFLECTION_OVERFLOW = 1
 DIRECT_RENDER_MAX_TAPS = 2047
+MAX_REFLECTION_VOICES = 32
+MAX_REFLECTION_RENDER_BATCH = 256
 
 
 class SoundParams(C.Structure):
@@ -272,6 +275,21 @@ class DirectRenderTarget(C.Structure):
     ]
 
 
+class ReflectionVoice(C.Structure):
+    """fs_reflection_voice (include/frequensee.h): one entry of a source's voice list, an array element (no struct_size)"""
+    _fields_ = [
+        ("key", C.c_uint32),
+        ("delay", C.c_float),
+        ("band_gain", C.c_float * MAX_BANDS),
+        ("channel_gain", C.c_float * 2),
+    ]
+
+
+class ReflectionRenderRow(C.Structure):
+    """fs_reflection_render_row (include/frequensee.h): one source's counts of a callback, an array element (no struct_size)"""
+    _fields_ = [(k, C.c_uint32) for k in ("sounding", "started", "ended", "dropped")]
+
+
 class FrequenSeeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"frequensee status {code}: {msg}")
@@ -387,6 +405,9 @@ def load():
         "fs_direct_render_init": (C.c_int, [vp, i32, i32, i32, C.c_float]),
         "fs_direct_render_release": (C.c_int, [vp, i32]),
         "fs_direct_render_process_batch": (C.c_int, [vp, C.c_void_p, i32, f32p, C.c_void_p, f32p, f32p]),
+        "fs_reflection_render_init": (C.c_int, [vp, i32, i32, i32, i32, C.c_float]),
+        "fs_reflection_render_release": (C.c_int, [vp, i32]),
+        "fs_reflection_render_process_batch": (C.c_int, [vp, C.c_void_p, i32, f32p, C.c_void_p, C.c_void_p, i32, f32p, f32p, C.c_void_p]),
         "fs_gather_energy": (C.c_int, [vp, i32, f32p, i32]),
         "fs_gather_energy_async": (C.c_int, [vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     }

@@ -459,6 +459,59 @@ class Context:
             return out, mix
         return out if want_out else mix
 
+    # ---- early reflections on the audio thread: a bank of delayed, filtered, panned voices per source ----
+    REFLECTION_VOICE_DTYPE = np.dtype([("key", np.uint32), ("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,)),
+                                       ("channel_gain", np.float32, (2,))])
+    REFLECTION_RENDER_ROW_DTYPE = np.dtype([("sounding", np.uint32), ("started", np.uint32), ("ended", np.uint32), ("dropped", np.uint32)])
+
+    def reflection_render_init(self, src, frame_size=1024, taps=255, voices=32, max_delay_seconds=1.0):
+        self.check(self.lib.fs_reflection_render_init(self.h, src, int(frame_size), int(taps), int(voices), float(max_delay_seconds)))
+        self._rr_shape = getattr(self, "_rr_shape", {})
+        self._rr_shape[src] = (int(frame_size), int(taps))
+
+    def reflection_render_release(self, src):
+        self.check(self.lib.fs_reflection_render_release(self.h, src))
+
+    def reflection_render_process_batch(self, sources, blocks, voices, stride=None, want_out=True, want_mix=False):
+        """the early reflections of several sources as one set of launches (include/frequensee.h
+        fs_reflection_render_process_batch): blocks [count][frame_size * 2]; voices one list per source, each a
+        REFLECTION_VOICE_DTYPE array or (key, delay, band_gain, channel_gain) tuples; stride = the row length handed to the library
+        (default: the longest list, at least 1) -> (out [count][frame_size * 2] (want_out), mix [frame_size * 2] (want_mix), rows
+        [count] REFLECTION_RENDER_ROW_DTYPE); what was not asked for is left out of the tuple"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        count = int(srcs.shape[0])
+        a = np.ascontiguousarray(blocks, dtype=np.float32).reshape(count, -1) if count else np.zeros((0, 0), np.float32)
+        shapes = getattr(self, "_rr_shape", {})
+        if count and int(srcs[0]) in shapes and a.shape[1] != 2 * shapes[int(srcs[0])][0]:
+            raise ValueError("every audio block must hold frame_size * 2 interleaved samples")
+        if len(voices) != count:
+            raise ValueError("voices must have one list per source")
+        if stride is None:
+            stride = max([len(v) for v in voices] + [1])
+        stride = int(stride)
+        if any(len(v) > stride for v in voices):
+            raise ValueError("a voice list is longer than stride")
+        table = np.zeros((count, max(stride, 1)), dtype=self.REFLECTION_VOICE_DTYPE)
+        counts = np.zeros(count, np.int32)
+        for i, lst in enumerate(voices):
+            counts[i] = len(lst)
+            if isinstance(lst, np.ndarray) and lst.dtype == self.REFLECTION_VOICE_DTYPE:
+                table[i, :len(lst)] = lst
+                continue
+            for e, (key, delay, gains, chan) in enumerate(lst):
+                g = np.asarray(gains, np.float32).reshape(-1)
+                table[i, e]["key"] = key
+                table[i, e]["delay"] = delay
+                table[i, e]["band_gain"][:g.shape[0]] = g
+                table[i, e]["channel_gain"] = chan
+        out = np.empty_like(a) if want_out else None
+        mix = np.empty(a.shape[1], np.float32) if want_mix else None
+        rows = np.zeros(count, dtype=self.REFLECTION_RENDER_ROW_DTYPE)
+        self.check(self.lib.fs_reflection_render_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data, table.ctypes.data,
+                                                               counts.ctypes.data, stride, out.ctypes.data if want_out else None,
+                                                               mix.ctypes.data if want_mix else None, rows.ctypes.data))
+        return tuple(x for x, want in ((out, want_out), (mix, want_mix), (rows, True)) if want)
+
     # ---- row f2: reverb plugin convolution ----
     def reverb_init(self, src, frame_size=1024):
         self.check(self.lib.fs_reverb_init(self.h, src, frame_size))
@@ -905,6 +958,61 @@ class FrequenSeeAudioOcclusionPlugin:
         Context.direct_render_process_batch does."""
         return self.ctx.direct_render_process_batch([c._src for c in components], buffers, self.Targets(paths),
                                                     want_out=want_out, want_mix=want_mix)
+
+
+class FrequenSeeAudioReflectionPlugin:
+    """Not in the reference: per audio callback every source's block is rendered once per first-order reflection of
+    UpdateReflectionPaths — delayed by the path's arrival time (fractional and slew-limited: each reflection has a Doppler shift of
+    its own), filtered by its per-band reflectance, weighted by a per-channel gain and summed (fs_reflection_render_process_batch).
+    A reflection is recognised from callback to callback by its triangle; one that appears or vanishes fades over one block.
+    Panning and the distance law are this plugin's (Voices), not the library's."""
+
+    def __init__(self, subsystem: AudioRayTracingSubsystem):
+        self.ctx = subsystem.ctx
+        self.FrameSize = 1024
+        self.Taps = 255
+        self.VoiceCount = 32
+        self.MaxDelaySeconds = 1.0
+
+    def Initialize(self, BufferLength=1024, Taps=255, Voices=32, MaxDelaySeconds=1.0):
+        self.FrameSize, self.Taps, self.VoiceCount, self.MaxDelaySeconds = int(BufferLength), int(Taps), int(Voices), float(MaxDelaySeconds)
+
+    def OnInitSource(self, component: FrequenSeeAudioComponent):
+        self.ctx.reflection_render_init(component._src, self.FrameSize, self.Taps, self.VoiceCount, self.MaxDelaySeconds)
+
+    def OnReleaseSource(self, component: FrequenSeeAudioComponent):
+        self.ctx.reflection_render_release(component._src)
+
+    def Voices(self, row, paths, right=None, reference_length=None):
+        """one source's entries from its UpdateReflectionPaths result (row: its counts, paths: its path array), over the first
+        row["returned"] paths: key = triangle, band_gain = reflectance, delay = the path's arrival time less the filter's own
+        latency of (Taps - 1) / 2 samples, not below 0.  channel_gain = (1, 1); with `right` (the listener's unit right vector) the
+        constant-power pan (cos t, sin t), t = (dot(direction, right) + 1) pi / 4; with reference_length (cm) scaled by
+        min(1, reference_length / length)"""
+        n = int(row["returned"])
+        v = np.zeros(n, dtype=Context.REFLECTION_VOICE_DTYPE)
+        latency = ((self.Taps - 1) // 2) / float(self.ctx.cfg.sample_rate)
+        r = None if right is None else np.asarray(right, np.float64).reshape(3)
+        for i in range(n):
+            p = paths[i]
+            v[i]["key"] = p["triangle"]
+            v[i]["delay"] = max(float(p["delay"]) - latency, 0.0)
+            v[i]["band_gain"] = p["reflectance"]
+            left_right = np.ones(2, np.float64)
+            if r is not None:
+                t = (float(np.dot(np.asarray(p["direction"], np.float64), r)) + 1.0) * np.pi / 4.0
+                left_right = np.array([np.cos(t), np.sin(t)])
+            if reference_length is not None:
+                left_right = left_right * min(1.0, float(reference_length) / float(p["length"]))
+            v[i]["channel_gain"] = left_right
+        return v
+
+    def ProcessAudio(self, components, buffers, rows, paths, right=None, reference_length=None, want_out=True, want_mix=False):
+        """buffers[i] is components[i]'s block, rows[i] / paths[i] its results of UpdateReflectionPaths.  Returns what
+        Context.reflection_render_process_batch does."""
+        voices = [self.Voices(rows[i], paths[i], right, reference_length) for i in range(len(components))]
+        return self.ctx.reflection_render_process_batch([c._src for c in components], buffers, voices,
+                                                        want_out=want_out, want_mix=want_mix)
 
 
 class MaterialAcousticProcessor:

@@ -165,6 +165,7 @@ void free_source(fs_context* ctx, Source* s) {
         if (s->d_fade_from) (void)hipFree(s->d_fade_from);
         if (s->d_fade_to) (void)hipFree(s->d_fade_to);
         if (s->d_dr) (void)hipFree(s->d_dr);
+        if (s->d_rr) (void)hipFree(s->d_rr);
         if (s->d_dir) (void)hipFree(s->d_dir);   // (the callers have synchronised the compute stream)
     }
     delete s;
@@ -661,6 +662,8 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->d_rev_stage) (void)hipFree(ctx->d_rev_stage);
         if (ctx->h_dr_stage) (void)hipHostFree(ctx->h_dr_stage);
         if (ctx->d_dr_stage) (void)hipFree(ctx->d_dr_stage);
+        if (ctx->h_rr_stage) (void)hipHostFree(ctx->h_rr_stage);
+        if (ctx->d_rr_stage) (void)hipFree(ctx->d_rr_stage);
         for (const auto& t : ctx->dr_tables) if (t.d) (void)hipFree(t.d);
         if (ctx->d_batch) (void)hipFree(ctx->d_batch);
         if (ctx->d_build) (void)hipFree(ctx->d_build);

@@ -43,7 +43,7 @@ void band_kernels(int sample_rate, const std::vector<double>& e, int B, int T, f
         }
 }
 
-bool taps_ok(int32_t taps) { return taps >= 1 && taps <= FS_DIRECT_RENDER_MAX_TAPS && (taps & 1) == 1; }
+bool taps_ok(int32_t taps) { return direct_render_taps_ok(taps); }
 
 // The staging of one callback (fs_context::h_dr_stage / d_dr_stage), every block 256-byte aligned
 struct DrStageLayout {
@@ -70,8 +70,13 @@ DrStageLayout dr_stage_layout(int count, int frame) {
 
 size_t dr_state_bytes(const Source* s) { return kDirectRenderHeader + sizeof(float) * 2 * (size_t)s->dr_ring; }
 
-// the table of (taps, edges in force), built and uploaded at its first use
-int table_for(fs_context* ctx, int taps, const float** out) {
+}  // namespace
+
+namespace fsi {
+
+bool direct_render_taps_ok(int32_t taps) { return taps >= 1 && taps <= FS_DIRECT_RENDER_MAX_TAPS && (taps & 1) == 1; }
+
+int direct_render_table_for(fs_context* ctx, int taps, const float** out) {
     const int B = ctx->cfg.num_bands;
     const std::vector<double> e = inner_edges(ctx->band_edges, B);
     for (const auto& t : ctx->dr_tables)
@@ -89,7 +94,7 @@ int table_for(fs_context* ctx, int taps, const float** out) {
     return FS_OK;
 }
 
-}  // namespace
+}  // namespace fsi
 
 extern "C" {
 
@@ -119,7 +124,7 @@ int fs_direct_render_init(fs_context* ctx, fs_source h, int32_t frame_size, int3
     while ((double)ring < need) ring <<= 1;
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const float* table = nullptr;
-    const int rc = table_for(ctx, taps, &table);
+    const int rc = direct_render_table_for(ctx, taps, &table);
     if (rc) return rc;
     FS_HIP(ctx, hipStreamSynchronize(ctx->rev_stream));
     if (s->d_dr) (void)hipFree(s->d_dr);

@@ -3,7 +3,7 @@
 // fs_capi_frame.cpp (sources, the traced frame: describe / resources / commit / launch), fs_capi_pipeline.cpp (held frames, the
 // drain), fs_capi_publish.cpp (reconstruct + publish: the IR ring, the host word, the fused launch's reconstruct parts),
 // fs_capi_ir.cpp (reconstruct / tick / IR / energy entry points), fs_capi_comm.cpp (RCCL behind the ABI), fs_capi_reverb.cpp
-// (the reverb callback), fs_capi_direct.cpp (direct paths), fs_capi_reflect.cpp (reflection paths), fs_capi_direct_render.cpp (the direct-sound callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange,
+// (the reverb callback), fs_capi_direct.cpp (direct paths), fs_capi_reflect.cpp (reflection paths), fs_capi_direct_render.cpp (the direct-sound callback), fs_capi_reflect_render.cpp (the early-reflection callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange,
 // material FD).
 //
 // Mirrors the roles of UAudioRayTracingSubsystem (context lifetime, geometry/source registries,
@@ -163,6 +163,15 @@ struct Source {
     int dr_frame = 0, dr_taps = 0, dr_max_delay = 0;
     unsigned dr_ring = 0;
     const float* dr_table = nullptr;
+    // early reflections (fs_reflection_render_init; the audio thread's): the state block — ReflectRenderState, then at
+    // kReflectRenderHeader the history rings [2][rr_ring] shared by the rr_voices slots — and what the source was initialised with
+    // (rr_table: one of fs_context::dr_tables'); rr_held / rr_key: the slot table the callback matches against, the host's copy
+    char* d_rr = nullptr;
+    int rr_frame = 0, rr_taps = 0, rr_voices = 0, rr_max_delay = 0;
+    unsigned rr_ring = 0;
+    const float* rr_table = nullptr;
+    bool rr_held[FS_MAX_REFLECTION_VOICES] = {};
+    uint32_t rr_key[FS_MAX_REFLECTION_VOICES] = {};
     float occlusion = 1.0f;            // OcclusionAttenuation FSAC.h:130 (1.f until the first UpdateSound)
 };
 
@@ -313,6 +322,11 @@ struct fs_context {
     // the band-kernel tables fs_direct_render_init has built, one per (taps, edges in force); freed with the context
     struct DirectRenderTable { int taps; std::vector<double> edges; float* d; };
     std::vector<DirectRenderTable> dr_tables;
+    // fs_reflection_render_process_batch (audio thread): staging of its own, beside the reverb's and the direct sound's.  Up: items
+    // [count] | voices [count][stride] | in [count][2 frame]; the device also holds the counters [count] and the plans
+    // [count][FS_MAX_REFLECTION_VOICES]; down: out [count][2 frame] | mix [2 frame].  Grown at the first call that needs more.
+    char* h_rr_stage = nullptr; char* d_rr_stage = nullptr;
+    size_t rr_stage_host = 0, rr_stage_dev = 0;   // bytes
     HostBVH bvh;
 
     float listener[3] = {0, 0, 0};
@@ -509,6 +523,10 @@ constexpr float kMaxUnboundedRr = 0.95f;   // depth = 0 (uncapped walks): the st
 
 namespace fsi {
 
+// ---- fs_capi_direct_render.cpp: what the reflection renderer shares with the direct one
+bool direct_render_taps_ok(int32_t taps);
+// the device table of (taps, edges in force), built and uploaded at its first use; owned by the context
+int direct_render_table_for(fs_context* ctx, int taps, const float** out);
 // ---- fs_capi_context.cpp ------------------------------------------------------------------------------------------
 Source* get_source(fs_context* ctx, fs_source h);
 hipError_t wait_energy_readers(fs_context* ctx, Source* s);            // before the compute stream writes the current energy buffer

@@ -548,6 +548,60 @@ struct DirectRenderBatch {
 };
 // the plan pass, the render pass (which also appends the blocks to the rings), the mix (when b.mix)
 void launch_direct_render(const DirectRenderBatch& b, hipStream_t s);
+// fs_reflect_render.hip (the early-reflection callback).  A source's state is one device block (Source::d_rr): this header, then at
+// kReflectRenderHeader bytes the two history rings [2][ring], shared by the source's slots; zeroed = every slot free, nothing heard.
+struct ReflectRenderSlot {
+    int32_t held;          // the device's record of the slot table; the matching itself runs on the host's copy (Source::rr_held / rr_key)
+    uint32_t key;
+    float d0;              // the delay the slot's last output sample used, in samples
+    float g0[FS_MAX_BANDS];   // ... its band gains
+    float w0[2];           // ... its channel gains
+    int32_t pad[3];
+};
+static_assert(sizeof(ReflectRenderSlot) == 64, "ReflectRenderSlot: sixteen words");
+struct ReflectRenderState {
+    unsigned n0;           // absolute index of the next block's first sample (wraps; the ring index is n & mask)
+    int32_t pad[15];
+    ReflectRenderSlot slot[FS_MAX_REFLECTION_VOICES];
+};
+constexpr size_t kReflectRenderHeader = 2304;
+static_assert(sizeof(ReflectRenderState) == 2112 && sizeof(ReflectRenderState) <= kReflectRenderHeader && kReflectRenderHeader % 256 == 0,
+              "ReflectRenderState: the counter's line and the slots in front of the rings");
+// what the host's matching decided for a slot in this callback (ReflectRenderItem::op): idle, ending, or continuing / starting
+// with entry e of the row as kReflectContinue + e / kReflectStart + e
+constexpr int kReflectIdle = -1, kReflectEnd = -2, kReflectContinue = 0, kReflectStart = FS_MAX_REFLECTION_VOICES;
+// one descriptor per row of the call, in list order: the host's staging layout
+struct ReflectRenderItem {
+    ReflectRenderState* state;
+    float* ring;           // [2][mask + 1]
+    const float* table;    // the band kernels [bands][taps] the source was initialised with
+    unsigned mask;
+    int32_t slots;         // V
+    int8_t op[FS_MAX_REFLECTION_VOICES];
+};
+static_assert(sizeof(ReflectRenderItem) == 64, "ReflectRenderItem: three pointers, two words and a byte per slot, the host's staging layout");
+// what the plan pass fixes for a sounding slot: where this callback ramps from, the slew-limited change of the delay, the gains
+// it ramps between and the channel gains' start and change
+struct ReflectRenderPlan {
+    float d0, e;
+    float g0[FS_MAX_BANDS], g1[FS_MAX_BANDS];
+    float w0[2], dw[2];
+    int32_t pad[2];
+};
+static_assert(sizeof(ReflectRenderPlan) == 96, "ReflectRenderPlan: twenty-four words");
+struct ReflectRenderBatch {
+    const ReflectRenderItem* items;     // [count]
+    const fs_reflection_voice* voices;  // [count][stride]
+    ReflectRenderPlan* plans;           // [count][FS_MAX_REFLECTION_VOICES] scratch
+    unsigned* n0;                       // [count] scratch: every row's counter before this callback
+    int count, stride, frame, taps, bands;
+    float fs;                           // the sample rate: an entry's d1 = delay * fs
+    const float* in;                    // [count][2 * frame] interleaved
+    float* out;                         // [count][2 * frame] interleaved
+    float* mix;                         // [2 * frame], or null
+};
+// the plan pass, the render pass (which also appends the blocks to the rings), the mix (when b.mix)
+void launch_reflect_render(const ReflectRenderBatch& b, hipStream_t s);
 void launch_add_energy(float* energy_row, int num_bins, float delay_s, float e, hipStream_t s);
 // dynamic LDS the traversal kernels of a frame need for a tree with `stack_rows` stack rows: the larger of the walk
 // kernel (stack + work-sharing area) and the connect kernels (stack + [bands][bins] histogram + work-sharing area)

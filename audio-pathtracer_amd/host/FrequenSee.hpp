@@ -11,6 +11,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -80,6 +81,7 @@ public:
 private:
     friend class AudioRayTracingSubsystem;
     friend class FrequenSeeAudioOcclusionPlugin;
+    friend class FrequenSeeAudioReflectionPlugin;
     FVector Location_;
     AudioRayTracingSubsystem* SubSys_ = nullptr;
     fs_source Handle_ = -1;
@@ -279,6 +281,7 @@ private:
     friend class FrequenSeeAudioComponent;
     friend class MaterialAcousticProcessor;
     friend class FrequenSeeAudioOcclusionPlugin;
+    friend class FrequenSeeAudioReflectionPlugin;
 };
 
 inline FrequenSeeAudioComponent::~FrequenSeeAudioComponent() { OnUnregister(); }
@@ -429,6 +432,81 @@ public:
 
     int FrameSize = 1024;   // AudioCallbackBufferFrameSize, Config/DefaultEngine.ini:13
     int Taps = 255;
+    float MaxDelaySeconds = 1.0f;
+    int SampleRate = 48000;   // fs_config_default's, FSAC.h:133
+
+private:
+    AudioRayTracingSubsystem* SubSys_;
+};
+
+// Not in the reference: per audio callback every source's block is rendered once per first-order reflection of
+// fs_update_reflection_paths — delayed by the path's arrival time (fractional and slew-limited: each reflection has a Doppler shift
+// of its own), filtered by its per-band reflectance, weighted by a per-channel gain and summed — fs_reflection_render_process_batch,
+// one call for all sources.  A reflection is recognised from callback to callback by its triangle; one that appears or vanishes
+// fades over one block.  Panning and the distance law are this plugin's (Voices), not the library's.
+class FrequenSeeAudioReflectionPlugin {
+public:
+    explicit FrequenSeeAudioReflectionPlugin(AudioRayTracingSubsystem& SubSys) : SubSys_(&SubSys) {}
+    void Initialize(int BufferLength = 1024, int TapCount = 255, int Voices = FS_MAX_REFLECTION_VOICES, float MaxDelay = 1.0f) {
+        FrameSize = BufferLength; Taps = TapCount; VoiceCount = Voices; MaxDelaySeconds = MaxDelay;
+    }
+    void OnInitSource(const FrequenSeeAudioComponent& C) {
+        SubSys_->Check(fs_reflection_render_init(SubSys_->Ctx_, C.Handle_, FrameSize, Taps, VoiceCount, MaxDelaySeconds));
+    }
+    void OnReleaseSource(const FrequenSeeAudioComponent& C) { SubSys_->Check(fs_reflection_render_release(SubSys_->Ctx_, C.Handle_)); }
+    // one source's entries from its row and paths of fs_update_reflection_paths, over the first Row.returned paths: key = triangle,
+    // band_gain = reflectance, delay = the path's arrival time less the filter's own latency of (Taps - 1) / 2 samples, not below 0.
+    // channel_gain = (1, 1); with Right (the listener's unit right vector) the constant-power pan (cos t, sin t),
+    // t = (dot(direction, Right) + 1) pi / 4; with ReferenceLength > 0 (cm) scaled by min(1, ReferenceLength / length)
+    std::vector<fs_reflection_voice> Voices(const fs_reflection_row& Row, const fs_reflection_path* Paths, const FVector* Right = nullptr,
+                                            float ReferenceLength = 0.0f) const {
+        std::vector<fs_reflection_voice> V((size_t)Row.returned);
+        const double Latency = (double)((Taps - 1) / 2) / (double)SampleRate;
+        for (size_t i = 0; i < V.size(); ++i) {
+            const fs_reflection_path& P = Paths[i];
+            V[i].key = P.triangle;
+            V[i].delay = (float)std::max((double)P.delay - Latency, 0.0);
+            for (int b = 0; b < FS_MAX_BANDS; ++b) V[i].band_gain[b] = P.reflectance[b];
+            double L = 1.0, R = 1.0;
+            if (Right) {
+                const double Dot = (double)P.direction[0] * Right->X + (double)P.direction[1] * Right->Y + (double)P.direction[2] * Right->Z;
+                const double T = (Dot + 1.0) * 3.14159265358979323846 / 4.0;
+                L = std::cos(T); R = std::sin(T);
+            }
+            if (ReferenceLength > 0.0f) {
+                const double G = std::min(1.0, (double)ReferenceLength / (double)P.length);
+                L *= G; R *= G;
+            }
+            V[i].channel_gain[0] = (float)L;
+            V[i].channel_gain[1] = (float)R;
+        }
+        return V;
+    }
+    // In [count][FrameSize * 2] interleaved stereo, row i for Sources[i], Rows[i] and Paths[i * MaxPaths ..] (the arrays
+    // fs_update_reflection_paths filled with max_paths = MaxPaths); Out [count][FrameSize * 2] or nullptr, Mix [FrameSize * 2] (the
+    // fp32 sum of the rows in list order) or nullptr, Counts [count] or nullptr
+    void ProcessAudio(const std::vector<FrequenSeeAudioComponent*>& Sources, const float* In, const std::vector<fs_reflection_row>& Rows,
+                      const std::vector<fs_reflection_path>& Paths, int MaxPaths, float* Out, float* Mix = nullptr,
+                      const FVector* Right = nullptr, float ReferenceLength = 0.0f, fs_reflection_render_row* Counts = nullptr) {
+        if (Rows.size() != Sources.size() || Paths.size() != Sources.size() * (size_t)MaxPaths || MaxPaths < 1 ||
+            MaxPaths > FS_MAX_REFLECTION_VOICES)
+            throw std::runtime_error("FrequenSee: one reflection row and MaxPaths paths per source");
+        std::vector<fs_source> H;
+        std::vector<fs_reflection_voice> All(Sources.size() * (size_t)MaxPaths);
+        std::vector<int32_t> N;
+        for (size_t i = 0; i < Sources.size(); ++i) {
+            H.push_back(Sources[i]->Handle_);
+            const std::vector<fs_reflection_voice> V = Voices(Rows[i], Paths.data() + i * (size_t)MaxPaths, Right, ReferenceLength);
+            std::copy(V.begin(), V.end(), All.begin() + (std::ptrdiff_t)(i * (size_t)MaxPaths));
+            N.push_back((int32_t)V.size());
+        }
+        SubSys_->Check(fs_reflection_render_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, All.data(), N.data(), MaxPaths, Out,
+                                                          Mix, Counts));
+    }
+
+    int FrameSize = 1024;   // AudioCallbackBufferFrameSize, Config/DefaultEngine.ini:13
+    int Taps = 255;
+    int VoiceCount = FS_MAX_REFLECTION_VOICES;
     float MaxDelaySeconds = 1.0f;
     int SampleRate = 48000;   // fs_config_default's, FSAC.h:133
 

@@ -56,6 +56,7 @@
  *             fs_direct_params_default fs_direct_sample_offsets fs_update_direct_paths
  *             fs_reflection_params_default fs_update_reflection_paths
  *             fs_direct_band_kernels fs_direct_render_init fs_direct_render_release fs_direct_render_process_batch
+ *             fs_reflection_render_init fs_reflection_render_release fs_reflection_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
  * Environment variables (FS_*) are tuning and diagnostic knobs only; all of them are read ONCE — at fs_context_create, at a
  * scene commit (builder knobs) or at the first launch of a kernel family — never per frame.
@@ -913,6 +914,81 @@ int fs_direct_render_init(fs_context* ctx, fs_source src, int32_t frame_size, in
 int fs_direct_render_release(fs_context* ctx, fs_source src);
 int fs_direct_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in,
                                    const fs_direct_render_target* targets /* [count] */, float* out, float* mix);
+
+/* ---- early reflections on the audio thread (EXTENDED): what fs_update_reflection_paths' paths are rendered with -----------
+ *      Not in the reference.  Per source a VOICE BANK: up to `voices` slots, each one exactly the direct renderer's block above (a
+ *      fractional, slew-limited delay — the Doppler shift — and the band FIR) reading ONE history ring shared by all slots of the
+ *      source, weighted by a per-channel gain (where the host's pan and distance law go) and summed.  Voices are matched from
+ *      callback to callback by a key (the reflector's triangle); a voice whose key appears fades in over one block, one whose key
+ *      disappears fades out over one block: a reflection that switches on or off at a block boundary does not click.  All sources
+ *      of a callback share one set of launches.  The library applies only the gains it is given.
+ *   Band kernels.  The table of fs_direct_band_kernels for the context's sample rate, band count and edges in force: the very
+ *   upload fs_direct_render_init uses for the same (context, T, edges).
+ *   fs_reflection_render_init.  F = frame_size, T = taps, D = ceil(max_delay_seconds fs) under fs_direct_render_init's limits
+ *   (16 <= F <= 16384; T odd, 1 .. FS_DIRECT_RENDER_MAX_TAPS; the ring is the smallest power of two >= D + T + 1 + F floats and
+ *   D + T + 1 + F <= 2^20; edges in force inside (0, fs / 2)), and 1 <= V = voices <= FS_MAX_REFLECTION_VOICES: otherwise
+ *   FS_ERR_INVALID_ARGUMENT.  State per source, device-resident, all allocated here: a zeroed history ring per channel shared by
+ *   the slots, the absolute sample counter n0, and V slots {held, key, d0, g0[bands], w0[2]}, all free.  The matching below
+ *   depends only on the keys and on which slots are held, so the library does it on a host-side copy of (held, key) per slot;
+ *   the audio thread is its only writer.  Calling init again re-initialises the source with the new F, T, V and D.
+ *   fs_reflection_render_release: history := 0 and every slot free — the next callback's voices fade in from silence (a source
+ *   without fs_reflection_render_init: nothing to do, FS_OK).
+ *   One callback, per row i with its voice_counts[i] entries voices[i * stride ..].  fp32 throughout; every operation is rounded
+ *   on its own, in the order written (the library is built with -ffp-contract=off); numpy float32 computes the same bits.
+ *     1. Match, against the slots as the previous callback left them; for an entry d1 = delay * (float)fs, g1 = band_gain,
+ *        w1 = channel_gain.
+ *        - A held slot whose key is among the row's entries CONTINUES: it ramps from its state (d0, g0, w0) to (d1, g1, w1).
+ *        - A held slot whose key is not ENDS: d1 := d0 (the delay freezes), g1 := g0, w1 := 0.  It is free after this callback,
+ *          not during it.
+ *        - The entries whose key no held slot has, in list order: each STARTS on the lowest-numbered slot that was free when the
+ *          callback began and has not been taken in this callback, with d0 := d1, g0 := g1, w0 := 0.  When no such slot is left
+ *          the entry is DROPPED for this callback: not rendered, counted, and started by a later callback if the host still
+ *          lists it and a slot is free.  A host that wants no drops gives voices = 2 x the largest number of entries it lists.
+ *     2. Voice output.  For every sounding slot j (continuing, ending or starting) y_j(s, ch) is "Output s" of the direct
+ *        renderer above, verbatim, with this slot's (d0, e, g0, g1): e = clamp(d1 - d0, -F/2, +F/2); cA[t] band by band
+ *        ascending; a = (float)(s + 1) / (float)F; the four accumulators over t = j (mod 4) combined as
+ *        (acc_0 + acc_1) + (acc_2 + acc_3); x(n) the source's shared history followed by this block.
+ *     3. Sum, over the sounding slots in ascending slot number, from acc = 0: dw = w1[ch] - w0[ch]; w = w0[ch] + a * dw;
+ *        acc = acc + w * y_j.  out(s, ch) = acc, not clamped.  A row without a sounding slot gives zeros.
+ *     4. Afterwards a continuing or started slot holds d0 + e, g1 (0 beyond num_bands) and w1; an ended slot is free; the block
+ *        enters the history; n0 += F.  rows[i] = the counts of this callback: sounding = slots rendered, started, ended, dropped.
+ *   fs_reflection_render_process_batch.
+ *     in  [count][frame_size * 2]  interleaved stereo, host; row i belongs to sources[i]
+ *     voices [count][stride], voice_counts [count]: row i lists voice_counts[i] entries, 0 .. stride
+ *     out [count][frame_size * 2]  or NULL
+ *     mix [frame_size * 2]         or NULL; out == NULL && mix == NULL is FS_ERR_INVALID_ARGUMENT
+ *     rows [count]                 or NULL
+ *    Refusals.  Each refuses the WHOLE call before any state change or enqueue — nothing changes, out, mix and rows are not
+ *    written: FS_ERR_INVALID_ARGUMENT for a NULL sources, in, voices or voice_counts; count outside
+ *    1 .. FS_MAX_REFLECTION_RENDER_BATCH; stride outside 1 .. FS_MAX_REFLECTION_VOICES; a voice_counts[i] outside 0 .. stride; a
+ *    key that appears twice in one row; a delay that is negative, not finite or with d1 > D; a band gain (band < num_bands) that
+ *    is negative or not finite; a channel gain that is not finite; a handle that appears twice; a source without
+ *    fs_reflection_render_init; sources that do not share F and T (V may differ).  FS_ERR_BAD_HANDLE for a bad handle,
+ *    FS_ERR_NO_DEVICE without a device.
+ *    Batch rules: 1, 2, 4 and 5 of fs_direct_render_process_batch, read for this call.  A source gives the same bits and the
+ *    same state served alone, in any batch or in a permuted batch; mix is the fp32 sum in list order, computed on the device;
+ *    the call runs on the reverb stream, waits for that stream only, takes no source mutex and reads no impulse response; ONE
+ *    audio render thread runs all callbacks of a context (reverb, direct and reflections); staging of its own (pinned + device)
+ *    grows at the first call that needs more (count x frame_size, count x stride) and a call of a shape the context has seen
+ *    allocates nothing; one copy up, a number of launches that does not grow with count, one copy back, one wait.
+ *   fs_source_destroy and fs_context_destroy free everything. */
+#define FS_MAX_REFLECTION_VOICES        32   /* slots per source */
+#define FS_MAX_REFLECTION_RENDER_BATCH 256
+typedef struct fs_reflection_voice {
+    uint32_t key;                     /* identity from callback to callback: fs_reflection_path.triangle */
+    float    delay;                   /* s, >= 0: fs_reflection_path.delay, less whatever latency the host compensates */
+    float    band_gain[FS_MAX_BANDS]; /* finite, >= 0: fs_reflection_path.reflectance; entries beyond num_bands ignored */
+    float    channel_gain[2];         /* finite, any sign: the host's pan and distance law, left / right */
+} fs_reflection_voice;                /* an array element: no struct_size; 48 bytes */
+typedef struct fs_reflection_render_row {
+    uint32_t sounding, started, ended, dropped;
+} fs_reflection_render_row;           /* 16 bytes */
+int fs_reflection_render_init(fs_context* ctx, fs_source src, int32_t frame_size, int32_t taps, int32_t voices, float max_delay_seconds);
+int fs_reflection_render_release(fs_context* ctx, fs_source src);
+int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in /* [count][F * 2] */,
+                                       const fs_reflection_voice* voices /* [count][stride] */, const int32_t* voice_counts /* [count] */,
+                                       int32_t stride, float* out /* [count][F * 2] or NULL */, float* mix /* [F * 2] or NULL */,
+                                       fs_reflection_render_row* rows /* [count] or NULL */);
 
 /* ---- row f4: frequency-dependent material response of one audio block ------------------------------------
  *      UMaterialAcousticProcessor::ApplyMaterialFD (Private/MaterialAcousticProcessor.cpp:8-107, MAP.cpp):
