@@ -56,6 +56,7 @@ EXPORTS = [
     "fs_set_band_edges", "fs_source_set_orientation", "fs_source_set_directivity", "fs_get_room_parameters",
     "fs_direct_params_default", "fs_direct_sample_offsets", "fs_update_direct_paths",
     "fs_reflection_params_default", "fs_update_reflection_paths",
+    "fs_diffraction_params_default", "fs_update_diffraction_paths",
     "fs_direct_band_kernels", "fs_direct_render_init", "fs_direct_render_release", "fs_direct_render_process_batch",
     "fs_reflection_render_init", "fs_reflection_render_release", "fs_reflection_render_process_batch",
 ]
@@ -75,6 +76,11 @@ MAX_REFLECTIONS = 16
 MAX_REFLECTION_CANDIDATES = 256
 MAX_REFLECTION_BATCH = 256
 REFLECTION_OVERFLOW = 1
+MAX_DIFFRACTIONS = 16
+MAX_DIFFRACTION_CANDIDATES = 2048
+MAX_DIFFRACTION_BATCH = 256
+DIFFRACTION_OVERFLOW = 1
+DIFFRACTION_VOICE_TAG = 0x80000000   # the top bit of a diffraction voice's key: 0x80000000 | (4 triangle + edge)
 DIRECT_RENDER_MAX_TAPS = 2047
 MAX_REFLECTION_VOICES = 32
 MAX_REFLECTION_RENDER_BATCH = 256
@@ -267,6 +273,44 @@ class ReflectionRow(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("candidates", "found", "returned", "flags")]
 
 
+class DiffractionParams(C.Structure):
+    """fs_diffraction_params (include/frequensee.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("max_paths", C.c_int32),
+        ("max_candidates", C.c_int32),
+        ("margin", C.c_float),
+        ("max_detour", C.c_float),
+        ("offset", C.c_float),
+        ("merge", C.c_float),
+        ("step", C.c_float),
+        ("pullback", C.c_float),
+        ("dist_divisor", C.c_float),
+        ("sound_speed", C.c_float),
+    ]
+
+
+class DiffractionPath(C.Structure):
+    """fs_diffraction_path (include/frequensee.h): one diffraction path of one source, an array element (no struct_size)"""
+    _fields_ = [
+        ("length", C.c_float),
+        ("delay", C.c_float),
+        ("detour", C.c_float),
+        ("cos_bend", C.c_float),
+        ("apex", C.c_float * 3),
+        ("direction", C.c_float * 3),
+        ("triangle", C.c_uint32),
+        ("edge", C.c_uint32),
+        ("material", C.c_uint32),
+        ("gain", C.c_float * MAX_BANDS),
+    ]
+
+
+class DiffractionRow(C.Structure):
+    """fs_diffraction_row (include/frequensee.h): one source's counts, an array element (no struct_size)"""
+    _fields_ = [(k, C.c_uint32) for k in ("candidates", "confirmed", "found", "returned", "flags")]
+
+
 class DirectRenderTarget(C.Structure):
     """fs_direct_render_target (include/frequensee.h): one source's target of a callback, an array element (no struct_size)"""
     _fields_ = [
@@ -401,6 +445,8 @@ def load():
         "fs_update_direct_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(DirectParams), C.c_void_p]),
         "fs_reflection_params_default": (None, [C.POINTER(ReflectionParams)]),
         "fs_update_reflection_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(ReflectionParams), C.c_void_p, C.c_void_p]),
+        "fs_diffraction_params_default": (None, [C.POINTER(DiffractionParams)]),
+        "fs_update_diffraction_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(DiffractionParams), C.c_void_p, C.c_void_p]),
         "fs_direct_band_kernels": (C.c_int, [i32, f32p, i32, i32, f32p]),
         "fs_direct_render_init": (C.c_int, [vp, i32, i32, i32, C.c_float]),
         "fs_direct_render_release": (C.c_int, [vp, i32]),
@@ -446,6 +492,14 @@ def default_direct_params(**kw) -> DirectParams:
 def default_reflection_params(**kw) -> ReflectionParams:
     p = ReflectionParams()
     load().fs_reflection_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_diffraction_params(**kw) -> DiffractionParams:
+    p = DiffractionParams()
+    load().fs_diffraction_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -406,6 +406,27 @@ class Context:
                                                        rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
         return rows, paths
 
+    # ---- diffraction paths: the first-order edge diffraction of every source of a tick ----
+    DIFFRACTION_ROW_DTYPE = np.dtype([("candidates", np.uint32), ("confirmed", np.uint32), ("found", np.uint32), ("returned", np.uint32),
+                                      ("flags", np.uint32)])
+    DIFFRACTION_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("detour", np.float32), ("cos_bend", np.float32),
+                                  ("apex", np.float32, (3,)), ("direction", np.float32, (3,)), ("triangle", np.uint32), ("edge", np.uint32),
+                                  ("material", np.uint32), ("gain", np.float32, (_capi.MAX_BANDS,))])
+
+    def diffraction_paths(self, sources, **params):
+        """fs_update_diffraction_paths: (rows [count], paths [count][max_paths]) as structured arrays — per listed source the counts
+        (candidates, confirmed, found, returned, flags) and its `returned` shortest paths round one edge (length cm, delay s, detour
+        cm, cos_bend, apex, direction from the listener, triangle, edge, material, gain [8]; entries beyond `returned` are zero);
+        params = the fields of fs_diffraction_params (max_paths, max_candidates, margin, max_detour, offset, merge, step, pullback,
+        dist_divisor, sound_speed)"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        p = _capi.default_diffraction_params(**params)
+        rows = np.zeros(srcs.shape[0], dtype=self.DIFFRACTION_ROW_DTYPE)
+        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=self.DIFFRACTION_DTYPE)
+        self.check(self.lib.fs_update_diffraction_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
+                                                        rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
+        return rows, paths
+
     # ---- direct sound on the audio thread: fractional delay + band FIR for all sources of a callback ----
     RENDER_TARGET_DTYPE = np.dtype([("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,))])
 
@@ -849,6 +870,17 @@ class AudioRayTracingSubsystem:
         parts = [self.ctx.reflection_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
         return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
 
+    def UpdateDiffractionPaths(self, **params):
+        """the first-order edge diffraction of all active sources: (rows, paths), row i and paths[i] for ActiveSources[i]
+        (Context.diffraction_paths; more than 256 sources take one call per 256)"""
+        srcs = [s._src for s in self.ActiveSources]
+        if not srcs:
+            return np.zeros(0, dtype=Context.DIFFRACTION_ROW_DTYPE), np.zeros((0, 0), dtype=Context.DIFFRACTION_DTYPE)
+        self._commit()
+        step = _capi.MAX_DIFFRACTION_BATCH
+        parts = [self.ctx.diffraction_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
+        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
+
     def SetPipelining(self, depth):
         """fs_set_pipelining: Tick then updates the sources one after the other like the reference's loop (ARTS.cpp:60-68),
         streamed — every call launches one kernel that plans this source's frame, walks the previous source's and
@@ -983,21 +1015,26 @@ class FrequenSeeAudioReflectionPlugin:
     def OnReleaseSource(self, component: FrequenSeeAudioComponent):
         self.ctx.reflection_render_release(component._src)
 
-    def Voices(self, row, paths, right=None, reference_length=None):
+    def Voices(self, row, paths, right=None, reference_length=None, diffraction=None):
         """one source's entries from its UpdateReflectionPaths result (row: its counts, paths: its path array), over the first
         row["returned"] paths: key = triangle, band_gain = reflectance, delay = the path's arrival time less the filter's own
         latency of (Taps - 1) / 2 samples, not below 0.  channel_gain = (1, 1); with `right` (the listener's unit right vector) the
         constant-power pan (cos t, sin t), t = (dot(direction, right) + 1) pi / 4; with reference_length (cm) scaled by
-        min(1, reference_length / length)"""
+        min(1, reference_length / length).  diffraction = (row, paths) of the same source from UpdateDiffractionPaths appends one
+        voice per returned diffraction path — band_gain = gain, delay, pan and distance law as above, key = 0x80000000 |
+        (4 triangle + edge): no reflection's key while the scene has fewer than 2^29 triangles, which is checked"""
         n = int(row["returned"])
-        v = np.zeros(n, dtype=Context.REFLECTION_VOICE_DTYPE)
+        m = 0 if diffraction is None else int(diffraction[0]["returned"])
+        v = np.zeros(n + m, dtype=Context.REFLECTION_VOICE_DTYPE)
         latency = ((self.Taps - 1) // 2) / float(self.ctx.cfg.sample_rate)
         r = None if right is None else np.asarray(right, np.float64).reshape(3)
-        for i in range(n):
-            p = paths[i]
-            v[i]["key"] = p["triangle"]
+        for i in range(n + m):
+            p = paths[i] if i < n else diffraction[1][i - n]
+            if diffraction is not None and int(p["triangle"]) >= _capi.DIFFRACTION_VOICE_TAG >> 2:
+                raise ValueError("Voices: triangle index 2^29 or above: reflection and diffraction keys would collide")
+            v[i]["key"] = p["triangle"] if i < n else _capi.DIFFRACTION_VOICE_TAG | (int(p["triangle"]) * 4 + int(p["edge"]))
             v[i]["delay"] = max(float(p["delay"]) - latency, 0.0)
-            v[i]["band_gain"] = p["reflectance"]
+            v[i]["band_gain"] = p["reflectance"] if i < n else p["gain"]
             left_right = np.ones(2, np.float64)
             if r is not None:
                 t = (float(np.dot(np.asarray(p["direction"], np.float64), r)) + 1.0) * np.pi / 4.0
@@ -1007,10 +1044,12 @@ class FrequenSeeAudioReflectionPlugin:
             v[i]["channel_gain"] = left_right
         return v
 
-    def ProcessAudio(self, components, buffers, rows, paths, right=None, reference_length=None, want_out=True, want_mix=False):
-        """buffers[i] is components[i]'s block, rows[i] / paths[i] its results of UpdateReflectionPaths.  Returns what
-        Context.reflection_render_process_batch does."""
-        voices = [self.Voices(rows[i], paths[i], right, reference_length) for i in range(len(components))]
+    def ProcessAudio(self, components, buffers, rows, paths, right=None, reference_length=None, want_out=True, want_mix=False,
+                     diffraction=None):
+        """buffers[i] is components[i]'s block, rows[i] / paths[i] its results of UpdateReflectionPaths; diffraction = the (rows,
+        paths) of UpdateDiffractionPaths, or None.  Returns what Context.reflection_render_process_batch does."""
+        voices = [self.Voices(rows[i], paths[i], right, reference_length,
+                              None if diffraction is None else (diffraction[0][i], diffraction[1][i])) for i in range(len(components))]
         return self.ctx.reflection_render_process_batch([c._src for c in components], buffers, voices,
                                                         want_out=want_out, want_mix=want_mix)
 

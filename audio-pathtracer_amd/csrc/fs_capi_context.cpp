@@ -658,6 +658,8 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->d_direct_off) (void)hipFree(ctx->d_direct_off);
         if (ctx->h_reflect) (void)hipHostFree(ctx->h_reflect);
         if (ctx->d_reflect) (void)hipFree(ctx->d_reflect);
+        if (ctx->h_diffract) (void)hipHostFree(ctx->h_diffract);
+        if (ctx->d_diffract) (void)hipFree(ctx->d_diffract);
         if (ctx->h_rev_stage) (void)hipHostFree(ctx->h_rev_stage);
         if (ctx->d_rev_stage) (void)hipFree(ctx->d_rev_stage);
         if (ctx->h_dr_stage) (void)hipHostFree(ctx->h_dr_stage);

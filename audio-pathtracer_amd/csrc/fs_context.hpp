@@ -314,6 +314,16 @@ struct fs_context {
     // Device: sources [reflect_cap] float4 | counters [reflect_cap] | candidates [reflect_cap][FS_MAX_REFLECTION_CANDIDATES] | rows and paths.
     char* h_reflect = nullptr; char* d_reflect = nullptr;
     int reflect_cap = 0;
+    // fs_update_diffraction_paths (fs_capi_diffract.cpp): staging of its own, likewise sized for the largest max_paths and max_candidates.
+    // Pinned: sources [diffract_cap] float4 | the copy's target, rows [count] then paths [count][max_paths].  Device: sources
+    // [diffract_cap] float4 | confirmed records [diffract_cap][FS_MAX_DIFFRACTION_CANDIDATES] | counters [diffract_cap] | candidates
+    // [diffract_cap][FS_MAX_DIFFRACTION_CANDIDATES] | rows and paths.  diffract_f: the band centres f_b of the edges in force
+    // (diffract_f_edges, diffract_f_bands: what they were built from; rebuilt when fs_set_band_edges has changed them).
+    char* h_diffract = nullptr; char* d_diffract = nullptr;
+    int diffract_cap = 0;
+    double diffract_f[FS_MAX_BANDS] = {};
+    std::vector<double> diffract_f_edges;
+    int diffract_f_bands = 0;
     // fs_direct_render_process_batch (audio thread): staging of its own — a reverb and a direct callback of different counts may
     // follow each other in one audio callback, and h_direct / d_direct are the game thread's.  Up: items [count] | in [count][2 frame];
     // the device also holds the plans [count]; down: out [count][2 frame] | mix [2 frame].  Grown at the first call that needs more.

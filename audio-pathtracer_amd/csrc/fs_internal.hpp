@@ -440,6 +440,31 @@ struct ReflectKParams {
     float margin, step, offset, pullback, dist_divisor, sound_speed;
 };
 void launch_reflection_paths(const DeviceScene& sc, const ReflectKParams& rp, hipStream_t s);
+// fs_diffract.hip (fs_update_diffraction_paths): diffract_scan_kernel, a thread per triangle record against every row of the call,
+// appends the filter's surviving (leaf position * 4 + edge) to the rows' candidate lists; diffract_confirm_kernel, a wave per row,
+// runs the three legs of every candidate, compacts the confirmed ones into `conf`, merges, ranks and writes the row and its paths.
+// src, counters, cand, rows, paths as ReflectKParams; conf [count][max_candidates] records, written and read by the row's wave only.
+struct DiffractRecord {
+    uint32_t length_bits, key;   // key = input index * 4 + edge
+    float apex[3], direction[3];
+    float detour, cos_bend;
+    uint32_t material, pad;
+};
+static_assert(sizeof(DiffractRecord) == 48, "DiffractRecord: twelve words");
+struct DiffractKParams {
+    const float4* src;
+    uint32_t* counters;
+    uint32_t* cand;
+    DiffractRecord* conf;
+    fs_diffraction_row* rows;
+    fs_diffraction_path* paths;
+    float lis[3];
+    uint32_t lis_object;
+    int32_t count, max_paths, max_candidates, num_bands;
+    float margin, max_detour, offset, merge, step, pullback, dist_divisor, sound_speed;
+    float k[FS_MAX_BANDS];   // k_b = 40 f_b / (sound_speed dist_divisor)
+};
+void launch_diffraction_paths(const DeviceScene& sc, const DiffractKParams& dp, hipStream_t s);
 constexpr int kReverbRing = 65536;   // per-channel history ring (floats), matches kRevRing in the kernels
 // fs_reverb.hip (the reverb callback): one descriptor per row of the call, in list order, read by every kernel of the callback.
 struct ReverbItem {

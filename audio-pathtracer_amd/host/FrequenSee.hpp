@@ -216,6 +216,25 @@ public:
                                              Out.Rows.data() + i, Out.Paths.data() + i * (size_t)Out.MaxPaths));
         return Out;
     }
+    // the first-order edge diffraction of every active source: Rows[i] and Paths[i * MaxPaths .. ) for ActiveSources[i]
+    // (fs_update_diffraction_paths; MaxPaths = P->max_paths, the default's without P; one call per FS_MAX_DIFFRACTION_BATCH sources)
+    struct DiffractionPaths { int32_t MaxPaths = 0; std::vector<fs_diffraction_row> Rows; std::vector<fs_diffraction_path> Paths; };
+    DiffractionPaths UpdateDiffractionPaths(const fs_diffraction_params* P = nullptr) {
+        fs_diffraction_params Def;
+        fs_diffraction_params_default(&Def);
+        DiffractionPaths Out;
+        Out.MaxPaths = P ? P->max_paths : Def.max_paths;
+        if (ActiveSources.empty()) return Out;
+        Out.Rows.resize(ActiveSources.size());
+        Out.Paths.resize(ActiveSources.size() * (size_t)std::min(std::max(Out.MaxPaths, 1), FS_MAX_DIFFRACTIONS));   // (a bad max_paths is refused below)
+        Commit();
+        std::vector<fs_source> H;
+        for (auto* s : ActiveSources) H.push_back(s->Handle_);
+        for (size_t i = 0; i < H.size(); i += FS_MAX_DIFFRACTION_BATCH)
+            Check(fs_update_diffraction_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_DIFFRACTION_BATCH), P,
+                                              Out.Rows.data() + i, Out.Paths.data() + i * (size_t)Out.MaxPaths));
+        return Out;
+    }
     // fs_set_pipelining (0 off, 1, 2): Tick streams the sources instead of batching them
     void SetPipelining(int Depth) { Check(fs_set_pipelining(Ctx_, Depth)); Streamed_ = Depth != 0; }
     // fs_set_frames_per_launch (1 .. 4): consecutive streamed frames share a launch (each keeps its seed, buffer and IR)
@@ -457,24 +476,35 @@ public:
     // one source's entries from its row and paths of fs_update_reflection_paths, over the first Row.returned paths: key = triangle,
     // band_gain = reflectance, delay = the path's arrival time less the filter's own latency of (Taps - 1) / 2 samples, not below 0.
     // channel_gain = (1, 1); with Right (the listener's unit right vector) the constant-power pan (cos t, sin t),
-    // t = (dot(direction, Right) + 1) pi / 4; with ReferenceLength > 0 (cm) scaled by min(1, ReferenceLength / length)
+    // t = (dot(direction, Right) + 1) pi / 4; with ReferenceLength > 0 (cm) scaled by min(1, ReferenceLength / length).
+    // DRow / DPaths (the same source's row and paths of fs_update_diffraction_paths) append one voice per returned diffraction path:
+    // band_gain = gain, delay, pan and distance law as above, key = 0x80000000 | (4 triangle + edge) — no reflection's key while the
+    // scene has fewer than 2^29 triangles; an index beyond that is refused
     std::vector<fs_reflection_voice> Voices(const fs_reflection_row& Row, const fs_reflection_path* Paths, const FVector* Right = nullptr,
-                                            float ReferenceLength = 0.0f) const {
-        std::vector<fs_reflection_voice> V((size_t)Row.returned);
+                                            float ReferenceLength = 0.0f, const fs_diffraction_row* DRow = nullptr,
+                                            const fs_diffraction_path* DPaths = nullptr) const {
+        const size_t NR = (size_t)Row.returned, ND = DRow && DPaths ? (size_t)DRow->returned : 0;
+        std::vector<fs_reflection_voice> V(NR + ND);
         const double Latency = (double)((Taps - 1) / 2) / (double)SampleRate;
         for (size_t i = 0; i < V.size(); ++i) {
-            const fs_reflection_path& P = Paths[i];
-            V[i].key = P.triangle;
-            V[i].delay = (float)std::max((double)P.delay - Latency, 0.0);
-            for (int b = 0; b < FS_MAX_BANDS; ++b) V[i].band_gain[b] = P.reflectance[b];
+            const bool Refl = i < NR;
+            const uint32_t Tri = Refl ? Paths[i].triangle : DPaths[i - NR].triangle;
+            if (ND && Tri >= (0x80000000u >> 2))
+                throw std::runtime_error("FrequenSee: triangle index 2^29 or above: reflection and diffraction keys would collide");
+            const float* Dir = Refl ? Paths[i].direction : DPaths[i - NR].direction;
+            const float* Gain = Refl ? Paths[i].reflectance : DPaths[i - NR].gain;
+            const float Delay = Refl ? Paths[i].delay : DPaths[i - NR].delay, Length = Refl ? Paths[i].length : DPaths[i - NR].length;
+            V[i].key = Refl ? Tri : (0x80000000u | (Tri * 4u + DPaths[i - NR].edge));
+            V[i].delay = (float)std::max((double)Delay - Latency, 0.0);
+            for (int b = 0; b < FS_MAX_BANDS; ++b) V[i].band_gain[b] = Gain[b];
             double L = 1.0, R = 1.0;
             if (Right) {
-                const double Dot = (double)P.direction[0] * Right->X + (double)P.direction[1] * Right->Y + (double)P.direction[2] * Right->Z;
+                const double Dot = (double)Dir[0] * Right->X + (double)Dir[1] * Right->Y + (double)Dir[2] * Right->Z;
                 const double T = (Dot + 1.0) * 3.14159265358979323846 / 4.0;
                 L = std::cos(T); R = std::sin(T);
             }
             if (ReferenceLength > 0.0f) {
-                const double G = std::min(1.0, (double)ReferenceLength / (double)P.length);
+                const double G = std::min(1.0, (double)ReferenceLength / (double)Length);
                 L *= G; R *= G;
             }
             V[i].channel_gain[0] = (float)L;
@@ -484,23 +514,29 @@ public:
     }
     // In [count][FrameSize * 2] interleaved stereo, row i for Sources[i], Rows[i] and Paths[i * MaxPaths ..] (the arrays
     // fs_update_reflection_paths filled with max_paths = MaxPaths); Out [count][FrameSize * 2] or nullptr, Mix [FrameSize * 2] (the
-    // fp32 sum of the rows in list order) or nullptr, Counts [count] or nullptr
+    // fp32 sum of the rows in list order) or nullptr, Counts [count] or nullptr; Diffraction = UpdateDiffractionPaths' result for the
+    // same sources (its voices follow each source's reflections) or nullptr
     void ProcessAudio(const std::vector<FrequenSeeAudioComponent*>& Sources, const float* In, const std::vector<fs_reflection_row>& Rows,
                       const std::vector<fs_reflection_path>& Paths, int MaxPaths, float* Out, float* Mix = nullptr,
-                      const FVector* Right = nullptr, float ReferenceLength = 0.0f, fs_reflection_render_row* Counts = nullptr) {
-        if (Rows.size() != Sources.size() || Paths.size() != Sources.size() * (size_t)MaxPaths || MaxPaths < 1 ||
-            MaxPaths > FS_MAX_REFLECTION_VOICES)
-            throw std::runtime_error("FrequenSee: one reflection row and MaxPaths paths per source");
+                      const FVector* Right = nullptr, float ReferenceLength = 0.0f, fs_reflection_render_row* Counts = nullptr,
+                      const AudioRayTracingSubsystem::DiffractionPaths* Diffraction = nullptr) {
+        const int DMax = Diffraction ? Diffraction->MaxPaths : 0, Stride = MaxPaths + DMax;
+        if (Rows.size() != Sources.size() || Paths.size() != Sources.size() * (size_t)MaxPaths || MaxPaths < 1 || DMax < 0 ||
+            Stride > FS_MAX_REFLECTION_VOICES ||
+            (Diffraction && (Diffraction->Rows.size() != Sources.size() || Diffraction->Paths.size() != Sources.size() * (size_t)DMax)))
+            throw std::runtime_error("FrequenSee: one row and MaxPaths paths per source");
         std::vector<fs_source> H;
-        std::vector<fs_reflection_voice> All(Sources.size() * (size_t)MaxPaths);
+        std::vector<fs_reflection_voice> All(Sources.size() * (size_t)Stride);
         std::vector<int32_t> N;
         for (size_t i = 0; i < Sources.size(); ++i) {
             H.push_back(Sources[i]->Handle_);
-            const std::vector<fs_reflection_voice> V = Voices(Rows[i], Paths.data() + i * (size_t)MaxPaths, Right, ReferenceLength);
-            std::copy(V.begin(), V.end(), All.begin() + (std::ptrdiff_t)(i * (size_t)MaxPaths));
+            const std::vector<fs_reflection_voice> V = Voices(Rows[i], Paths.data() + i * (size_t)MaxPaths, Right, ReferenceLength,
+                                                              Diffraction ? &Diffraction->Rows[i] : nullptr,
+                                                              Diffraction ? Diffraction->Paths.data() + i * (size_t)DMax : nullptr);
+            std::copy(V.begin(), V.end(), All.begin() + (std::ptrdiff_t)(i * (size_t)Stride));
             N.push_back((int32_t)V.size());
         }
-        SubSys_->Check(fs_reflection_render_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, All.data(), N.data(), MaxPaths, Out,
+        SubSys_->Check(fs_reflection_render_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, All.data(), N.data(), Stride, Out,
                                                           Mix, Counts));
     }
 

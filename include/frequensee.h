@@ -55,6 +55,7 @@
  *             fs_source_set_orientation fs_source_set_directivity fs_get_room_parameters
  *             fs_direct_params_default fs_direct_sample_offsets fs_update_direct_paths
  *             fs_reflection_params_default fs_update_reflection_paths
+ *             fs_diffraction_params_default fs_update_diffraction_paths
  *             fs_direct_band_kernels fs_direct_render_init fs_direct_render_release fs_direct_render_process_batch
  *             fs_reflection_render_init fs_reflection_render_release fs_reflection_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
@@ -734,6 +735,94 @@ void fs_reflection_params_default(fs_reflection_params* p);
 int fs_update_reflection_paths(fs_context* ctx, const fs_source* sources, int32_t count,
                                const fs_reflection_params* params /* NULL = defaults */,
                                fs_reflection_row* rows /* [count] */, fs_reflection_path* paths /* [count][max_paths] */);
+
+/* ---- diffraction paths (EXTENDED): the first-order edge diffraction of every source of a tick -----------------------------
+ * What is left of a source that has walked behind a corner or a partition: the sound that bends round ONE free edge of the
+ * obstacle — listener -> apex E0 on a triangle edge -> source — late by the detour, from the direction of the edge, the high bands
+ * rolled off.  Found like the reflections, by an exhaustive scan of every (triangle, edge): no sampling, no seed, and no edge
+ * adjacency — a triangle's record (v0, e1, e2, input index, material, object id) is all the scan reads.  Specified to the bit with
+ * the conventions of "reflection paths" (-ffp-contract=off, every fp32 operation rounded on its own in the order written, fmaf
+ * fused, a.b = (a.x b.x + a.y b.y) + a.z b.z, cross = product, product, subtract; divide and sqrtf correctly rounded).  Every
+ * marginal decision beyond the filter is taken by the closest-hit query fs_trace_rays answers.
+ *   Per source at S (actor id so), listener at L (actor id lo), triangle i, edge j = 0, 1, 2 with start a and vector w:
+ *   j = 0: a = v0, w = e1;  j = 1: a = v0 + e1, w = e2 - e1;  j = 2: a = v0 + e2, w = -e2 (per component).
+ *   1. Filter (part of the definition).  A triangle whose object id equals so or lo, that id not FS_NO_OBJECT, is never a
+ *      candidate.  n = cross(e1, e2); nn = n.n; nn == 0: rejected.  hS = (S - v0).n, hL = (L - v0).n; kept only if
+ *      (hS > 0 && hL < 0) || (hS < 0 && hL > 0): strictly on opposite sides.  ww = w.w; o = cross(w, n) (in the plane, away from
+ *      the triangle's interior); oo = o.o; ww == 0 or oo == 0: rejected.  rS = S - a, rL = L - a; tS = (rS.w) / ww, tL = (rL.w) / ww;
+ *      cS = cross(rS, w), cL = cross(rL, w); dS = sqrtf((cS.cS) / ww), dL = sqrtf((cL.cL) / ww); sum = dS + dL; sum == 0:
+ *      rejected.  t = tS + ((tL - tS) dS) / sum; kept iff t >= -margin && t <= 1.0f + margin.  E0 = fmaf(t, w, a) per component (not
+ *      clamped).  u = S - E0, v = E0 - L; lS = sqrtf(u.u), lL = sqrtf(v.v); lS == 0 or lL == 0: rejected.  length = lS + lL;
+ *      g = S - L; distance = sqrtf(g.g); detour = length - distance; kept iff detour <= max_detour.  Shadow zone: s = hS / (hS - hL);
+ *      X = fmaf(s, L - S, S) per component (where the segment S -> L meets the plane); kept iff (X - E0).o <= 0 — a lit listener has
+ *      no path, and detour -> 0 at the shadow boundary.  candidates = the number of (i, j) that pass.  candidates > max_candidates:
+ *      flags = FS_DIFFRACTION_OVERFLOW, confirmed = found = returned = 0 and nothing else of the row is computed.
+ *   2. Confirmation, per candidate: three legs, each chain(..) of "direct paths" with max_surfaces = 0 and this call's step (own
+ *      actors are passed, anything else blocks).  io = 1.0f / sqrtf(oo), oh = o io; in = 1.0f / sqrtf(nn), nh = n in if hS > 0 else
+ *      n (-in): the unit normal towards S.  Eo = fmaf(offset, oh, E0); ES = fmaf(offset, nh, Eo); EL = fmaf(-offset, nh, Eo).
+ *      Leg A: e = ES - S, len = sqrtf(e.e); len == 0: reached; else chain(S, e (1.0f / len), len).
+ *      Leg B: chain(ES, -nh, 2.0f offset).
+ *      Leg C: e = L - EL, len = sqrtf(e.e); len == 0: reached; else chain(EL, e (1.0f / len), len - pullback).
+ *      CONFIRMED iff all three reached with crossed == 0 (the verdicts are independent: their order is free).  Leg B rejects the
+ *      interior edges of a tessellated wall — Eo lies on the neighbouring triangle — and edges that run into a floor or another
+ *      surface; a free rim or a convex corner passes.  confirmed = the number confirmed.
+ *   3. Merge.  A convex corner is found once from each face, a vertex shared by two rim edges twice.  key = (length as fp32 bits,
+ *      4 i + j), compared as a pair.  A confirmed entry is DROPPED iff some confirmed entry of the row with a smaller key — dropped
+ *      itself or not — has q = E0 - E0', q.q < merge merge.  found = the number kept.
+ *   4. Row.  The kept entries are ordered by key ascending; the first returned = min(found, max_paths) are written, the entries
+ *      beyond `returned` (all of them for an overflowed row) as all-zero bytes.  delay = (length / dist_divisor) / sound_speed;
+ *      cos_bend = (u.v) / (lS lL), the cosine between E0 - S and L - E0 (1 = no bend); apex = E0; direction = v (1.0f / lL), from the
+ *      listener towards E0; triangle = i, edge = j, material = the triangle's material id;
+ *      gain[b] = 1.0f / sqrtf(3.0f + k_b detour) for b < num_bands and 0 beyond: Maekawa's barrier attenuation 10 log10(3 + 20 N)
+ *      as an amplitude, with the Fresnel number N = 2 delta f_b / c, i.e. k_b = 40 f_b / (sound_speed dist_divisor), computed by the
+ *      host in double and rounded to float once.  f_b = sqrt(lo_b hi_b) of the band's edges in force (fs_set_band_edges, else the
+ *      default octave edges); the lowest band's lo is half its hi, the highest band's hi twice its lo (the defaults give 125, 250,
+ *      ... Hz), and a single band has f_0 = 1000 Hz.  The gain is an estimate a host is free to ignore: a barrier formula, not
+ *      the uniform theory of diffraction, and it contains no distance law.  First order only: a thick obstacle, which needs two
+ *      edges, yields nothing.  Nothing depends on which builder made the tree, on the order in which candidates were collected, or
+ *      on count.  An empty committed scene gives rows of zeros.
+ *   The key a host gives the voice of a path (fs_reflection_render_process_batch) is 0x80000000 | (4 triangle + edge): no
+ *   reflection's key (its triangle) has the top bit set in a scene of fewer than 2^29 triangles.
+ *   Errors, ordering and cost: as fs_update_reflection_paths, with FS_MAX_DIFFRACTION_BATCH — the source table's upload, one clear,
+ *   TWO launches (the scan of all triangles against all rows; the confirmation, a wave per row), one copy back and one wait, whatever
+ *   count is; staging of its own, grown only at the first call with a larger count.  max_detour must be finite and > 0. */
+#define FS_MAX_DIFFRACTIONS            16
+#define FS_MAX_DIFFRACTION_CANDIDATES 2048
+#define FS_MAX_DIFFRACTION_BATCH      256
+#define FS_DIFFRACTION_OVERFLOW        1u   /* fs_diffraction_row.flags */
+typedef struct fs_diffraction_params {
+    uint32_t struct_size;     /* = sizeof(fs_diffraction_params) */
+    int32_t  max_paths;       /* 1 .. FS_MAX_DIFFRACTIONS, default 4: rows of `paths` per source */
+    int32_t  max_candidates;  /* 1 .. FS_MAX_DIFFRACTION_CANDIDATES, default 1024 */
+    float    margin;          /* slack of the apex's edge parameter, >= 0, finite; default 1e-3 */
+    float    max_detour;      /* cm, > 0, finite; default 1000: longer detours are inaudible */
+    float    offset;          /* cm the legs' ends stand off the edge, >= 0; default 0.1 */
+    float    merge;           /* cm within which two apexes are one path, >= 0; default 1.0 */
+    float    step;            /* cm a leg advances past a passed own-actor surface, >= 0; default 0.1 */
+    float    pullback;        /* cm the last leg stops short of the listener, >= 0; default 0.1 */
+    float    dist_divisor;    /* 1000, as fs_params */
+    float    sound_speed;     /* 343, as fs_params */
+} fs_diffraction_params;
+
+typedef struct fs_diffraction_path {
+    float    length;          /* cm, listener -> apex -> source */
+    float    delay;           /* s, on the impulse response's time axis: (length / dist_divisor) / sound_speed */
+    float    detour;          /* cm, length - |S - L| */
+    float    cos_bend;        /* cosine of the angle the path turns by at the apex; 1 = straight on */
+    float    apex[3];         /* E0 */
+    float    direction[3];    /* unit, from the listener towards E0: what a host pans by */
+    uint32_t triangle;        /* input index of the triangle the edge belongs to */
+    uint32_t edge;            /* 0: v0 -> v1, 1: v1 -> v2, 2: v2 -> v0 */
+    uint32_t material;        /* the triangle's material id (FS_NO_MATERIAL possible) */
+    float    gain[FS_MAX_BANDS]; /* the barrier estimate; bands beyond num_bands: 0 */
+} fs_diffraction_path;        /* an array element: no struct_size; 84 bytes */
+
+typedef struct fs_diffraction_row { uint32_t candidates, confirmed, found, returned, flags; } fs_diffraction_row;
+
+void fs_diffraction_params_default(fs_diffraction_params* p);
+int fs_update_diffraction_paths(fs_context* ctx, const fs_source* sources, int32_t count,
+                                const fs_diffraction_params* params /* NULL = defaults */,
+                                fs_diffraction_row* rows /* [count] */, fs_diffraction_path* paths /* [count][max_paths] */);
 
 /* ---- engine line trace the BVH kernel replaces (UWorld::LineTraceSingleByObjectType; call sites
  *      ARTS.cpp:252-254 any-hit, :340-342 closest-hit). Batch query, host arrays. ------------------- */
