@@ -653,13 +653,8 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->fft_graph) (void)hipGraphExecDestroy(ctx->fft_graph);
         if (ctx->h_fft_stage) (void)hipHostFree(ctx->h_fft_stage);
         for (float2* w : ctx->d_rev_tw) if (w) (void)hipFree(w);
-        if (ctx->h_direct) (void)hipHostFree(ctx->h_direct);
-        if (ctx->d_direct) (void)hipFree(ctx->d_direct);
+        for (PathStaging* st : {&ctx->direct_stage, &ctx->reflect_stage, &ctx->diffract_stage}) st->release();
         if (ctx->d_direct_off) (void)hipFree(ctx->d_direct_off);
-        if (ctx->h_reflect) (void)hipHostFree(ctx->h_reflect);
-        if (ctx->d_reflect) (void)hipFree(ctx->d_reflect);
-        if (ctx->h_diffract) (void)hipHostFree(ctx->h_diffract);
-        if (ctx->d_diffract) (void)hipFree(ctx->d_diffract);
         if (ctx->h_rev_stage) (void)hipHostFree(ctx->h_rev_stage);
         if (ctx->d_rev_stage) (void)hipFree(ctx->d_rev_stage);
         if (ctx->h_dr_stage) (void)hipHostFree(ctx->h_dr_stage);

@@ -3,7 +3,7 @@
 // fs_capi_frame.cpp (sources, the traced frame: describe / resources / commit / launch), fs_capi_pipeline.cpp (held frames, the
 // drain), fs_capi_publish.cpp (reconstruct + publish: the IR ring, the host word, the fused launch's reconstruct parts),
 // fs_capi_ir.cpp (reconstruct / tick / IR / energy entry points), fs_capi_comm.cpp (RCCL behind the ABI), fs_capi_reverb.cpp
-// (the reverb callback), fs_capi_direct.cpp (direct paths), fs_capi_reflect.cpp (reflection paths), fs_capi_direct_render.cpp (the direct-sound callback), fs_capi_reflect_render.cpp (the early-reflection callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange,
+// (the reverb callback), fs_capi_paths.cpp (direct, reflection and diffraction paths), fs_capi_direct_render.cpp (the direct-sound callback), fs_capi_reflect_render.cpp (the early-reflection callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange,
 // material FD).
 //
 // Mirrors the roles of UAudioRayTracingSubsystem (context lifetime, geometry/source registries,
@@ -228,6 +228,17 @@ struct ObjectMoves {
     int next = 0;
 };
 
+// A path query's staging pair (fs_capi_paths.cpp): pinned host memory and its device counterpart, both with room for `cap` rows.
+// Plain pointers: grow replaces the pair, release frees it (fs_context_destroy).
+struct PathStaging {
+    char* h = nullptr;
+    char* d = nullptr;
+    int cap = 0;
+    // room for `count` rows: a pair too small is replaced by one of twice the rows (32 at least) until it fits.  FS_OK or the failure reported.
+    int grow(fs_context* ctx, int count, size_t pinned_bytes_per_row, size_t device_bytes_per_row);
+    void release();
+};
+
 struct fs_context {
     fs_config cfg{};
     int num_bins = 0, num_samples = 0;
@@ -302,30 +313,24 @@ struct fs_context {
     std::vector<double> band_edges;
     float* d_carrier = nullptr;          // [B][carrier_stride(num_samples)] fp32
     float carrier_build_ms = 0.0f;       // device time of the last build (HIP events)
-    // fs_update_direct_paths (fs_capi_direct.cpp): pinned host staging — the rows' sources [direct_cap] float4 (read by the kernel
-    // in place) | the rows [direct_cap] fs_direct_path (the copy's target) — and the device rows, grown at the first call that needs
-    // more; the sample-offset tables [FS_MAX_DIRECT_SAMPLES][FS_MAX_DIRECT_SAMPLES][3] by n - 1, each uploaded at its first use
-    char* h_direct = nullptr; fs_direct_path* d_direct = nullptr;
-    int direct_cap = 0;
+    // The path queries' staging (fs_capi_paths.cpp), one per query: the queries share no buffer.  Each is sized for its query's
+    // largest max_paths and max_candidates, so that only a larger count grows it.
+    // direct_stage — pinned: the rows' sources [cap] float4 (read by the kernel in place) | the rows [cap] fs_direct_path (the copy's
+    // target); device: the rows.  d_direct_off: the sample-offset tables [FS_MAX_DIRECT_SAMPLES][FS_MAX_DIRECT_SAMPLES][3] by n - 1,
+    // each uploaded at its first use.
+    // reflect_stage — pinned: sources [cap] float4 | the copy's target, rows [count] then paths [count][max_paths]; device: sources
+    // [cap] float4 | counters [cap] | candidates [cap][FS_MAX_REFLECTION_CANDIDATES] | rows and paths.
+    // diffract_stage — pinned: as reflect_stage; device: sources [cap] float4 | confirmed records [cap][FS_MAX_DIFFRACTION_CANDIDATES]
+    // | counters [cap] | candidates [cap][FS_MAX_DIFFRACTION_CANDIDATES] | rows and paths.  diffract_f: the band centres f_b of the
+    // edges in force (diffract_f_edges, diffract_f_bands: what they were built from; rebuilt when fs_set_band_edges has changed them).
+    PathStaging direct_stage, reflect_stage, diffract_stage;
     float* d_direct_off = nullptr;
     uint64_t direct_off_have = 0;
-    // fs_update_reflection_paths (fs_capi_reflect.cpp): staging of its own, sized for the largest max_paths and max_candidates so that
-    // only a larger count grows it.  Pinned: sources [reflect_cap] float4 | the copy's target, rows [count] then paths [count][max_paths].
-    // Device: sources [reflect_cap] float4 | counters [reflect_cap] | candidates [reflect_cap][FS_MAX_REFLECTION_CANDIDATES] | rows and paths.
-    char* h_reflect = nullptr; char* d_reflect = nullptr;
-    int reflect_cap = 0;
-    // fs_update_diffraction_paths (fs_capi_diffract.cpp): staging of its own, likewise sized for the largest max_paths and max_candidates.
-    // Pinned: sources [diffract_cap] float4 | the copy's target, rows [count] then paths [count][max_paths].  Device: sources
-    // [diffract_cap] float4 | confirmed records [diffract_cap][FS_MAX_DIFFRACTION_CANDIDATES] | counters [diffract_cap] | candidates
-    // [diffract_cap][FS_MAX_DIFFRACTION_CANDIDATES] | rows and paths.  diffract_f: the band centres f_b of the edges in force
-    // (diffract_f_edges, diffract_f_bands: what they were built from; rebuilt when fs_set_band_edges has changed them).
-    char* h_diffract = nullptr; char* d_diffract = nullptr;
-    int diffract_cap = 0;
     double diffract_f[FS_MAX_BANDS] = {};
     std::vector<double> diffract_f_edges;
     int diffract_f_bands = 0;
     // fs_direct_render_process_batch (audio thread): staging of its own — a reverb and a direct callback of different counts may
-    // follow each other in one audio callback, and h_direct / d_direct are the game thread's.  Up: items [count] | in [count][2 frame];
+    // follow each other in one audio callback, and direct_stage is the game thread's.  Up: items [count] | in [count][2 frame];
     // the device also holds the plans [count]; down: out [count][2 frame] | mix [2 frame].  Grown at the first call that needs more.
     char* h_dr_stage = nullptr; char* d_dr_stage = nullptr;
     size_t dr_stage_host = 0, dr_stage_dev = 0;   // bytes

@@ -1,25 +1,21 @@
 // fs_diffract.hip — fs_update_diffraction_paths: the first-order edge diffraction of every source of a tick.  The definitions
 // (filter, the three legs, the merge, the row) are those of include/frequensee.h, operation by operation; this file is their mapping
-// onto the device, in two kernels — the construction of fs_reflect.hip with another filter and three legs instead of two.
-//   diffract_scan_kernel: one thread per triangle record, loaded once; the call's source rows are staged in LDS (a broadcast), the
-// listener is a kernel argument.  The three edges are filtered in registers for each row (what they share — normal, plane distances —
-// is computed once); a survivor takes a place in the row's candidate list by atomicAdd on the row's counter and stores leaf position
-// * 4 + edge.  The counter keeps counting past the cap: `candidates` is exact, an overflowed row is recognised in any order.
+// onto the device, in two kernels — the construction of fs_reflect.hip with another filter and three legs instead of two; what the two
+// files have in common is in fs_dev_paths.hpp.
+//   diffract_scan_kernel: the scan scaffold (scan_records) with this file's filter.  The three edges of a record are filtered in
+// registers for each row (what they share — normal, plane distances — is unpacked once); a survivor's code is leaf position * 4 + edge.
 //   diffract_confirm_kernel: one wave per source row, kBlock / 64 rows per workgroup; the lanes stride over the row's candidates
 // (at most FS_MAX_DIFFRACTION_CANDIDATES / 64 = 32 rounds).  A lane recomputes its candidate's values with the filter's own code —
-// the same bits — and runs the legs, the short one first, as wave-convergent loops round the lane-private trav_run<false>; a lane
+// the same bits — and runs the legs, the short one first, as chains (path_chain) round one copy of the traversal; a lane
 // whose candidate has already failed idles along with an empty cursor, a round in which no lane is left skips the remaining legs.
 // Nothing is kept per candidate: a confirmed one takes the next place of the row's list in the call's device staging (ballot and
 // prefix count, no atomics), written and read by the row's own wave only.  The merge and the ranks are counted over that list — a
 // handful of entries — in two passes: dropped or not, then the rank among the kept.  Plain vector stores, no sort network.
 //   Dynamic LDS of the confirm kernel: the stack rows [stack_rows][kBlock], nothing else.
-#include "fs_dev_trav.hpp"
-#include "fs_launch.hpp"
+#include "fs_dev_paths.hpp"
 
 namespace fs {
 namespace {
-
-constexpr uint32_t kDiffNoObject = FS_NO_OBJECT;
 
 // what step 1 hands on to the legs and the row
 struct DiffCandidate {
@@ -28,23 +24,27 @@ struct DiffCandidate {
     float vx, vy, vz, lL;  // v = E0 - L
     float length, detour;
     float ox, oy, oz, oo;  // o = cross(w, n)
-    float nx, ny, nz, nn, hS;
 };
 
-// Step 1 of the rule for one (triangle record, edge, source row)
-__device__ __forceinline__ bool diffract_filter(const float4 a, const float4 b, const float4 c, int edge, float Sx, float Sy, float Sz, uint32_t so,
-                                                const float (&L)[3], uint32_t lo, float m, float max_detour, DiffCandidate& f) {
-    const float v0x = a.x, v0y = a.y, v0z = a.z;
-    const float e1x = a.w, e1y = b.x, e1z = b.y;
-    const float e2x = b.z, e2y = b.w, e2z = c.x;
-    const uint32_t object = __float_as_uint(c.w);
-    const bool own = object != kDiffNoObject && (object == so || object == lo);
-    const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-    const float nn = (nx * nx + ny * ny) + nz * nz;
-    const float tx = L[0] - v0x, ty = L[1] - v0y, tz = L[2] - v0z;
-    const float hL = (tx * nx + ty * ny) + tz * nz;
-    const float sx = Sx - v0x, sy = Sy - v0y, sz = Sz - v0z;
-    const float hS = (sx * nx + sy * ny) + sz * nz;
+// the part of step 1 that the three edges of a record share beyond g: |S - L| and X, where the line S -> L meets the record's plane
+struct DiffPlane {
+    float distance, Xx, Xy, Xz;
+};
+__device__ __forceinline__ DiffPlane diffract_plane(const TriEnds g, const float4 s4, const float (&L)[3]) {
+    DiffPlane p;
+    const float gx = s4.x - L[0], gy = s4.y - L[1], gz = s4.z - L[2];
+    p.distance = sqrtf((gx * gx + gy * gy) + gz * gz);
+    const float s = g.hS / (g.hS - g.hL);
+    p.Xx = fmaf(s, L[0] - s4.x, s4.x); p.Xy = fmaf(s, L[1] - s4.y, s4.y); p.Xz = fmaf(s, L[2] - s4.z, s4.z);
+    return p;
+}
+
+// Step 1 of the rule for one (triangle record, edge, source row); g and p = what the record's three edges share
+__device__ __forceinline__ bool diffract_filter(const TriEnds g, const DiffPlane p, int edge, const float4 s4, const float (&L)[3], float m,
+                                                float max_detour, DiffCandidate& f) {
+    const float v0x = g.v0x, v0y = g.v0y, v0z = g.v0z, e1x = g.e1x, e1y = g.e1y, e1z = g.e1z, e2x = g.e2x, e2y = g.e2y, e2z = g.e2z;
+    const float nx = g.nx, ny = g.ny, nz = g.nz, nn = g.nn, hS = g.hS, hL = g.hL;
+    const float Sx = s4.x, Sy = s4.y, Sz = s4.z;
     const bool opposite = (hS > 0.0f && hL < 0.0f) || (hS < 0.0f && hL > 0.0f);
     const float ax = edge == 0 ? v0x : (edge == 1 ? v0x + e1x : v0x + e2x);
     const float ay = edge == 0 ? v0y : (edge == 1 ? v0y + e1y : v0y + e2y);
@@ -71,100 +71,50 @@ __device__ __forceinline__ bool diffract_filter(const float4 a, const float4 b, 
     const float lS = sqrtf((ux * ux + uy * uy) + uz * uz);
     const float lL = sqrtf((vx * vx + vy * vy) + vz * vz);
     const float length = lS + lL;
-    const float gx = Sx - L[0], gy = Sy - L[1], gz = Sz - L[2];
-    const float distance = sqrtf((gx * gx + gy * gy) + gz * gz);
-    const float detour = length - distance;
-    const float s = hS / (hS - hL);
-    const float Xx = fmaf(s, L[0] - Sx, Sx), Xy = fmaf(s, L[1] - Sy, Sy), Xz = fmaf(s, L[2] - Sz, Sz);
-    const float qx = Xx - E0x, qy = Xy - E0y, qz = Xz - E0z;
+    const float detour = length - p.distance;
+    const float qx = p.Xx - E0x, qy = p.Xy - E0y, qz = p.Xz - E0z;
     const float shadow = (qx * ox + qy * oy) + qz * oz;
     f.E0x = E0x; f.E0y = E0y; f.E0z = E0z;
     f.ux = ux; f.uy = uy; f.uz = uz; f.lS = lS;
     f.vx = vx; f.vy = vy; f.vz = vz; f.lL = lL;
     f.length = length; f.detour = detour;
     f.ox = ox; f.oy = oy; f.oz = oz; f.oo = oo;
-    f.nx = nx; f.ny = ny; f.nz = nz; f.nn = nn; f.hS = hS;
-    return !own && nn != 0.0f && opposite && ww != 0.0f && oo != 0.0f && sum != 0.0f && t >= -m && t <= 1.0f + m && lS != 0.0f && lL != 0.0f &&
+    return !g.own && nn != 0.0f && opposite && ww != 0.0f && oo != 0.0f && sum != 0.0f && t >= -m && t <= 1.0f + m && lS != 0.0f && lL != 0.0f &&
            detour <= max_detour && shadow <= 0.0f;
 }
 
 __global__ __launch_bounds__(kBlock) void diffract_scan_kernel(DeviceScene sc, DiffractKParams dp) {
-    __shared__ float4 s_src[FS_MAX_DIFFRACTION_BATCH];
-    for (int r = (int)threadIdx.x; r < dp.count; r += kBlock) s_src[r] = dp.src[r];
-    __syncthreads();
-    const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
-    if (i >= sc.num_tris) return;
-    const Tri48 rec = sc.tris[i];
-#pragma unroll 1
-    for (int r = 0; r < dp.count; ++r) {
-        const float4 s4 = s_src[r];
+    scan_records(sc, dp.h, dp.counters, dp.cand, dp.max_candidates, [&](uint32_t leaf, const TriEnds g, const float4 s4, auto&& emit) {
+        const DiffPlane p = diffract_plane(g, s4, dp.h.lis);
 #pragma unroll
         for (int edge = 0; edge < 3; ++edge) {
             DiffCandidate f;
-            if (diffract_filter(rec.a, rec.b, rec.c, edge, s4.x, s4.y, s4.z, __float_as_uint(s4.w), dp.lis, dp.lis_object, dp.margin, dp.max_detour, f)) {
-                const uint32_t k = atomicAdd(&dp.counters[r], 1u);
-                if (k < (uint32_t)dp.max_candidates) dp.cand[(size_t)r * dp.max_candidates + k] = (uint32_t)i * 4u + (uint32_t)edge;
-            }
+            if (diffract_filter(g, p, edge, s4, dp.h.lis, dp.margin, dp.max_detour, f)) emit(leaf * 4u + (uint32_t)edge);
         }
-    }
-}
-
-// One leg for every lane of the wave at once: chain(o, d, len) of "direct paths" with max_surfaces = 0; `active` = this lane has a
-// leg to run.  true = reached with crossed == 0: nothing but triangles of the own actors within len (passed with adv = t + step,
-// chain's rule 6).  (!(rem > 0) ends a leg as reached before its query: a query with such a tmax has no hit.)
-__device__ __forceinline__ bool diffract_leg(const DeviceScene& sc, const DiffractKParams& dp, uint32_t src_object, bool active,
-                                             float ox, float oy, float oz, float dx, float dy, float dz, float len, int* stack) {
-    bool reached = false, live = active;
-    float rem = len;
-#pragma unroll 1
-    for (int q = 0; q < FS_DIRECT_MAX_QUERIES; ++q) {
-        if (live && !(rem > 0.0f)) { reached = true; live = false; }
-        if (__ballot(live) == 0ull) break;
-        const Ray r = make_ray(ox, oy, oz, dx, dy, dz);
-        Trav tv;
-        trav_init(tv, rem, live && sc.num_nodes > 0);
-        trav_deep_reset(sc, stack);
-        trav_run<false>(sc, r, tv, stack);
-        if (!live) continue;
-        if (tv.leaf_index < 0) { reached = true; live = false; continue; }
-        const uint32_t object = __float_as_uint(sc.tris[tv.leaf_index].c.w);
-        const bool own = object != kDiffNoObject && (object == src_object || object == dp.lis_object);
-        if (!own) { live = false; continue; }
-        const float adv = tv.t + dp.step;
-        ox = fmaf(adv, dx, ox); oy = fmaf(adv, dy, oy); oz = fmaf(adv, dz, oz);
-        rem = rem - adv;
-        if (q + 1 == FS_DIRECT_MAX_QUERIES) live = false;   // out of queries: blocked
-    }
-    return reached;
+    });
 }
 
 __global__ __launch_bounds__(kBlock) void diffract_confirm_kernel(DeviceScene sc, DiffractKParams dp) {
     extern __shared__ __attribute__((aligned(16))) int s_dyn[];   // [stack_rows][kBlock]
     int* stack = &s_dyn[threadIdx.x];
-    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
-    const int maxc = dp.max_candidates, B = dp.num_bands;
-    const int row = (int)(blockIdx.x * (kBlock / 64)) + wave;
-    const bool row_ok = row < dp.count;
-    const float4 s4 = dp.src[row_ok ? row : 0];
-    const uint32_t src_object = __float_as_uint(s4.w);
-    const uint32_t cands = row_ok ? dp.counters[row] : 0u;
-    const bool overflow = cands > (uint32_t)maxc;
-    const int n = overflow ? 0 : (int)cands;
-    const uint32_t* list = dp.cand + (size_t)(row_ok ? row : 0) * maxc;
-    DiffractRecord* conf = dp.conf + (size_t)(row_ok ? row : 0) * maxc;
+    const ConfirmRow cr = confirm_row(dp.h, dp.counters, dp.cand, dp.max_candidates);
+    const int lane = cr.lane, n = cr.n, row = cr.row, B = dp.h.num_bands;
+    const float4 s4 = cr.s4;
+    DiffractRecord* conf = dp.conf + (size_t)cr.slot * dp.max_candidates;
     uint32_t confirmed = 0u;
 #pragma unroll 1
     for (int base = 0; base < n; base += 64) {   // (wave-uniform)
         const int c = base + lane;
         const bool mine = c < n;
-        const uint32_t code = mine ? list[c] : 0u;
+        const uint32_t code = mine ? cr.list[c] : 0u;
         const Tri48 rec = sc.tris[code >> 2];
+        const TriEnds g = tri_ends(rec, s4, dp.h);
         DiffCandidate f;
-        (void)diffract_filter(rec.a, rec.b, rec.c, (int)(code & 3u), s4.x, s4.y, s4.z, src_object, dp.lis, dp.lis_object, dp.margin, dp.max_detour, f);
+        (void)diffract_filter(g, diffract_plane(g, s4, dp.h.lis), (int)(code & 3u), s4, dp.h.lis, dp.margin, dp.max_detour, f);
         const float io = 1.0f / sqrtf(f.oo);
-        const float in = 1.0f / sqrtf(f.nn);
-        const float sg = f.hS > 0.0f ? in : -in;
-        const float nhx = f.nx * sg, nhy = f.ny * sg, nhz = f.nz * sg;
+        const float in = 1.0f / sqrtf(g.nn);
+        const float sg = g.hS > 0.0f ? in : -in;
+        const float nhx = g.nx * sg, nhy = g.ny * sg, nhz = g.nz * sg;
         const float Eox = fmaf(dp.offset, f.ox * io, f.E0x), Eoy = fmaf(dp.offset, f.oy * io, f.E0y), Eoz = fmaf(dp.offset, f.oz * io, f.E0z);
         const float ESx = fmaf(dp.offset, nhx, Eox), ESy = fmaf(dp.offset, nhy, Eoy), ESz = fmaf(dp.offset, nhz, Eoz);
         const float ELx = fmaf(-dp.offset, nhx, Eox), ELy = fmaf(-dp.offset, nhy, Eoy), ELz = fmaf(-dp.offset, nhz, Eoz);
@@ -173,12 +123,13 @@ __global__ __launch_bounds__(kBlock) void diffract_confirm_kernel(DeviceScene sc
         for (int leg = 0; leg < 3; ++leg) {   // B, A, C: one copy of the traversal; the verdicts are independent
             if (__ballot(ok) == 0ull) break;
             const float fx = leg == 0 ? ESx : (leg == 1 ? s4.x : ELx), fy = leg == 0 ? ESy : (leg == 1 ? s4.y : ELy), fz = leg == 0 ? ESz : (leg == 1 ? s4.z : ELz);
-            const float ex = (leg == 1 ? ESx : dp.lis[0]) - fx, ey = (leg == 1 ? ESy : dp.lis[1]) - fy, ez = (leg == 1 ? ESz : dp.lis[2]) - fz;
+            const float ex = (leg == 1 ? ESx : dp.h.lis[0]) - fx, ey = (leg == 1 ? ESy : dp.h.lis[1]) - fy, ez = (leg == 1 ? ESz : dp.h.lis[2]) - fz;
             const float len = sqrtf((ex * ex + ey * ey) + ez * ez);
             const float inv = 1.0f / len;
             const float dx = leg == 0 ? -nhx : ex * inv, dy = leg == 0 ? -nhy : ey * inv, dz = leg == 0 ? -nhz : ez * inv;
-            const float reach = leg == 0 ? 2.0f * dp.offset : (leg == 1 ? len : len - dp.pullback);
-            ok = diffract_leg(sc, dp, src_object, ok, fx, fy, fz, dx, dy, dz, reach, stack) && ok;
+            const float reach = leg == 0 ? 2.0f * dp.offset : (leg == 1 ? len : len - dp.h.pullback);
+            // chain(o, d, len) with max_surfaces = 0: confirmed while reached (with crossed == 0)
+            ok = path_chain(sc, dp.h, cr.src_object, ok, fx, fy, fz, dx, dy, dz, reach, stack, StopAtHit()) == kChainReached && ok;
         }
         const unsigned long long votes = __ballot(ok);
         if (ok) {
@@ -204,19 +155,19 @@ __global__ __launch_bounds__(kBlock) void diffract_confirm_kernel(DeviceScene sc
         bool kept = e < confirmed;
         if (kept) {
             const DiffractRecord me = conf[e];
-            const unsigned long long key = ((unsigned long long)me.length_bits << 32) | me.key;
+            const unsigned long long key = path_key(me.length_bits, me.key);
             for (uint32_t j = 0u; j < confirmed; ++j) {
                 const DiffractRecord* x = conf + j;
                 const float qx = me.apex[0] - x->apex[0], qy = me.apex[1] - x->apex[1], qz = me.apex[2] - x->apex[2];
                 const float qq = (qx * qx + qy * qy) + qz * qz;
-                if ((((unsigned long long)x->length_bits << 32) | x->key) < key && qq < mm) kept = false;
+                if (path_key(x->length_bits, x->key) < key && qq < mm) kept = false;
             }
             conf[e].pad = kept ? 1u : 0u;
         }
         found += (uint32_t)__popcll(__ballot(kept));
     }
     __syncthreads();
-    if (!row_ok) return;
+    if (!cr.row_ok) return;
     const uint32_t returned = min(found, (uint32_t)dp.max_paths);
     fs_diffraction_path* out = dp.paths + (size_t)row * dp.max_paths;
 #pragma unroll 1
@@ -225,17 +176,15 @@ __global__ __launch_bounds__(kBlock) void diffract_confirm_kernel(DeviceScene sc
         if (e >= confirmed) continue;
         const DiffractRecord me = conf[e];
         if (me.pad == 0u) continue;
-        const unsigned long long key = ((unsigned long long)me.length_bits << 32) | me.key;
-        uint32_t rank = 0u;
-        for (uint32_t j = 0u; j < confirmed; ++j) {
+        const uint32_t rank = rank_among(confirmed, path_key(me.length_bits, me.key), [&](uint32_t j) {
             const DiffractRecord* x = conf + j;
-            rank += (x->pad != 0u && (((unsigned long long)x->length_bits << 32) | x->key) < key) ? 1u : 0u;
-        }
+            return x->pad != 0u ? path_key(x->length_bits, x->key) : kNoPathKey;
+        });
         if (rank >= (uint32_t)dp.max_paths) continue;
         fs_diffraction_path* o = out + rank;
         const float length = __uint_as_float(me.length_bits);
         o->length = length;
-        o->delay = (length / dp.dist_divisor) / dp.sound_speed;
+        o->delay = path_delay(dp.h, length);
         o->detour = me.detour;
         o->cos_bend = me.cos_bend;
         o->apex[0] = me.apex[0]; o->apex[1] = me.apex[1]; o->apex[2] = me.apex[2];
@@ -246,33 +195,21 @@ __global__ __launch_bounds__(kBlock) void diffract_confirm_kernel(DeviceScene sc
 #pragma unroll
         for (int b = 0; b < FS_MAX_BANDS; ++b) o->gain[b] = b < B ? 1.0f / sqrtf(3.0f + dp.k[b] * me.detour) : 0.0f;
     }
-    if ((uint32_t)lane >= returned && lane < dp.max_paths) {   // the entries beyond `returned`: zero bytes
-        uint32_t* z = reinterpret_cast<uint32_t*>(out + lane);
-#pragma unroll
-        for (int k = 0; k < (int)(sizeof(fs_diffraction_path) / sizeof(uint32_t)); ++k) z[k] = 0u;
-    }
+    zero_tail(out, lane, returned, dp.max_paths);
     if (lane == 0) {
         fs_diffraction_row* r = dp.rows + row;
-        r->candidates = cands;
+        r->candidates = cr.cands;
         r->confirmed = confirmed;
         r->found = found;
         r->returned = returned;
-        r->flags = overflow ? FS_DIFFRACTION_OVERFLOW : 0u;
+        r->flags = cr.overflow ? FS_DIFFRACTION_OVERFLOW : 0u;
     }
 }
 
 }  // namespace
 
-void launch_diffraction_paths(const DeviceScene& sc_in, const DiffractKParams& dp, hipStream_t s) {
-    if (dp.count <= 0) return;
-    const uint32_t blocks = (uint32_t)((dp.count + kBlock / 64 - 1) / (kBlock / 64));
-    DeviceScene sc = sc_in;
-    if (!attach_deep(sc, blocks)) return;
-    if (sc.num_tris > 0)
-        hipLaunchKernelGGL(diffract_scan_kernel, dim3((uint32_t)((sc.num_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, sc, dp);
-    const size_t lds = stack_bytes(sc);
-    allow_lds(diffract_confirm_kernel, lds);
-    hipLaunchKernelGGL(diffract_confirm_kernel, dim3(blocks), dim3(kBlock), lds, s, sc, dp);
+void launch_diffraction_paths(const DeviceScene& sc, const DiffractKParams& dp, hipStream_t s) {
+    launch_scan_confirm(diffract_scan_kernel, diffract_confirm_kernel, sc, dp, 0, s);
 }
 
 }  // namespace fs

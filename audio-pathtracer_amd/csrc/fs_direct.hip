@@ -2,77 +2,50 @@
 // every source of a tick, in one launch.  The definitions (sample offsets, chain, the per-source rule) are those of
 // include/frequensee.h, operation by operation; this file is their mapping onto the device.
 //   One wave per source row, lane k = sample k; a workgroup of kBlock threads serves kBlock / 64 rows.  Each lane runs its
-// two chains — the validity chain from the source's centre to its sample point, then the chain towards the listener — as
-// a loop of dependent closest-hit queries in which the whole wave meets at every query: the lane-private traversal
-// (trav_run<false>, the one trace_rays_kernel runs and tests/test_gpu_parity.py holds to the oracle's scan bit for bit)
-// is a wave-uniform loop, a lane whose chain has ended or whose sample does not exist idles along with an empty cursor.
+// two chains — the validity chain from the source's centre to its sample point, then the chain towards the listener — with
+// path_chain (fs_dev_paths.hpp), the loop the reflection and diffraction legs run too: the whole wave meets at every query, a lane
+// whose chain has ended or whose sample does not exist idles along with an empty cursor.
 //   Dynamic LDS: the stack rows [stack_rows][kBlock] | T [kBlock][FS_MAX_BANDS] | flags [kBlock].  The reduction has a
 // fixed order: lane b of the row's wave adds the valid samples' T_k[b] serially in double, ascending k.
-#include "fs_dev_trav.hpp"
-#include "fs_launch.hpp"
+#include "fs_dev_paths.hpp"
 
 namespace fs {
 namespace {
 
-constexpr uint32_t kDirectNoObject = FS_NO_OBJECT;
 constexpr uint32_t kDirectValid = 1u, kDirectFree = 2u;
 constexpr size_t kDirectLdsBytes = (size_t)kBlock * (sizeof(float) * FS_MAX_BANDS + sizeof(uint32_t));
 
-// chain(o, d, len) for every lane of the wave at once (include/frequensee.h); `active` = this lane has a chain to run.
+// chain(o, d, len) with the header's counting rule (path_chain, fs_dev_paths.hpp); `active` = this lane has a chain to run.
 // T of a lane without one stays 1, crossed 0, reached false.
 __device__ __forceinline__ void direct_chain(const DeviceScene& sc, const DirectKParams& dp, int max_surfaces, uint32_t src_object,
                                              bool active, float ox, float oy, float oz, float dx, float dy, float dz, float len,
                                              int* stack, bool& reached, uint32_t& crossed, float (&T)[FS_MAX_BANDS]) {
-    const int B = dp.num_bands;
+    const int B = dp.h.num_bands;
 #pragma unroll
     for (int b = 0; b < FS_MAX_BANDS; ++b) T[b] = 1.0f;
     crossed = 0u;
-    reached = false;
-    float rem = len;
-    bool live = active;
-#pragma unroll 1
-    for (int q = 0; q < FS_DIRECT_MAX_QUERIES; ++q) {
-        if (live && !(rem > 0.0f)) { reached = true; live = false; }
-        if (__ballot(live) == 0ull) break;
-        const Ray r = make_ray(ox, oy, oz, dx, dy, dz);
-        Trav tv;
-        trav_init(tv, rem, live && sc.num_nodes > 0);
-        trav_deep_reset(sc, stack);
-        trav_run<false>(sc, r, tv, stack);
-        if (!live) continue;
-        if (tv.leaf_index < 0) { reached = true; live = false; continue; }
-        const float4 c = sc.tris[tv.leaf_index].c;
-        const uint32_t mat = __float_as_uint(c.y), object = __float_as_uint(c.w);
-        const bool own = object != kDirectNoObject && (object == src_object || object == dp.lis_object);
-        if (!own) {
-            crossed += 1u;
-            bool through = false;
-            if (crossed <= (uint32_t)max_surfaces) {
-                const float* tau = sc.lobe_gain != nullptr && mat < (uint32_t)sc.num_materials
-                                       ? sc.lobe_gain + ((size_t)mat * 3 + kLobeTransmit) * B : nullptr;
+    const int end = path_chain(sc, dp.h, src_object, active, ox, oy, oz, dx, dy, dz, len, stack,
+                               [&](int leaf, float, float, float, float, float, float, float, float) {
+        const uint32_t mat = __float_as_uint(sc.tris[leaf].c.y);
+        crossed += 1u;
+        bool through = false;
+        if (crossed <= (uint32_t)max_surfaces) {
+            const float* tau = sc.lobe_gain != nullptr && mat < (uint32_t)sc.num_materials
+                                   ? sc.lobe_gain + ((size_t)mat * 3 + kLobeTransmit) * B : nullptr;
 #pragma unroll
-                for (int b = 0; b < FS_MAX_BANDS; ++b) {
-                    if (b < B) {
-                        T[b] = T[b] * (tau != nullptr ? tau[b] : 0.0f);
-                        through = through || T[b] != 0.0f;
-                    }
+            for (int b = 0; b < FS_MAX_BANDS; ++b) {
+                if (b < B) {
+                    T[b] = T[b] * (tau != nullptr ? tau[b] : 0.0f);
+                    through = through || T[b] != 0.0f;
                 }
             }
-            if (!through) {   // more surfaces than allowed, or nothing left in any band: blocked
-#pragma unroll
-                for (int b = 0; b < FS_MAX_BANDS; ++b) T[b] = 0.0f;
-                live = false;
-                continue;
-            }
         }
-        const float adv = tv.t + dp.step;
-        ox = fmaf(adv, dx, ox); oy = fmaf(adv, dy, oy); oz = fmaf(adv, dz, oz);
-        rem = rem - adv;
-        if (q + 1 == FS_DIRECT_MAX_QUERIES) {
+        return through;   // false: more surfaces than allowed, or nothing left in any band
+    });
+    reached = end == kChainReached;
+    if (end == kChainStopped || end == kChainSpent) {   // blocked
 #pragma unroll
-            for (int b = 0; b < FS_MAX_BANDS; ++b) T[b] = 0.0f;
-            live = false;
-        }
+        for (int b = 0; b < FS_MAX_BANDS; ++b) T[b] = 0.0f;
     }
 }
 
@@ -82,11 +55,11 @@ __global__ __launch_bounds__(kBlock) void direct_paths_kernel(DeviceScene sc, Di
     float* s_t = reinterpret_cast<float*>(s_dyn + (size_t)sc.stack_rows * kBlock);
     uint32_t* s_flags = reinterpret_cast<uint32_t*>(s_t + (size_t)kBlock * FS_MAX_BANDS);
     const int lane = (int)(threadIdx.x & 63u), wbase = (int)(threadIdx.x & ~63u);
-    const int row = (int)(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
-    const bool row_ok = row < dp.count;
-    const int n = dp.samples, B = dp.num_bands;
+    const int row = (int)(blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6));
+    const bool row_ok = row < dp.h.count;
+    const int n = dp.samples, B = dp.h.num_bands;
     const bool mine = row_ok && lane < n;
-    const float4 s4 = dp.src[row_ok ? row : 0];
+    const float4 s4 = dp.h.src[row_ok ? row : 0];
     const uint32_t src_object = __float_as_uint(s4.w);
     const int k = mine ? lane : 0;
     const float ux = dp.offsets[3 * k], uy = dp.offsets[3 * k + 1], uz = dp.offsets[3 * k + 2];
@@ -101,11 +74,11 @@ __global__ __launch_bounds__(kBlock) void direct_paths_kernel(DeviceScene sc, Di
     const bool valid = mine && (lane == 0 || crossed == 0u);
 
     const float px = s4.x + rad * ux, py = s4.y + rad * uy, pz = s4.z + rad * uz;
-    const float ex = dp.lis[0] - px, ey = dp.lis[1] - py, ez = dp.lis[2] - pz;
+    const float ex = dp.h.lis[0] - px, ey = dp.h.lis[1] - py, ez = dp.h.lis[2] - pz;
     const float len = sqrtf((ex * ex + ey * ey) + ez * ez);
     const bool trace = valid && len != 0.0f;
     const float inv = 1.0f / (trace ? len : 1.0f);
-    direct_chain(sc, dp, dp.max_surfaces, src_object, trace, px, py, pz, ex * inv, ey * inv, ez * inv, len - dp.pullback, stack,
+    direct_chain(sc, dp, dp.max_surfaces, src_object, trace, px, py, pz, ex * inv, ey * inv, ez * inv, len - dp.h.pullback, stack,
                  reached, crossed, T);
     const bool is_free = valid && (!trace || (reached && crossed == 0u));   // (len == 0: free with T = 1, what an idle chain leaves)
 
@@ -127,10 +100,10 @@ __global__ __launch_bounds__(kBlock) void direct_paths_kernel(DeviceScene sc, Di
     fs_direct_path* o = dp.out + row;
     o->transmission[lane] = lane < B ? (float)(sum / (double)V) : 0.0f;
     if (lane == 0) {
-        const float dx = dp.lis[0] - s4.x, dy = dp.lis[1] - s4.y, dz = dp.lis[2] - s4.z;
+        const float dx = dp.h.lis[0] - s4.x, dy = dp.h.lis[1] - s4.y, dz = dp.h.lis[2] - s4.z;
         const float distance = sqrtf((dx * dx + dy * dy) + dz * dz);
         o->distance = distance;
-        o->delay = (distance / dp.dist_divisor) / dp.sound_speed;
+        o->delay = path_delay(dp.h, distance);
         o->visibility = (float)nfree / (float)V;
         o->surfaces = crossed;
         o->samples_valid = V;
@@ -140,8 +113,8 @@ __global__ __launch_bounds__(kBlock) void direct_paths_kernel(DeviceScene sc, Di
 }  // namespace
 
 void launch_direct_paths(const DeviceScene& sc_in, const DirectKParams& dp, hipStream_t s) {
-    if (dp.count <= 0) return;
-    const uint32_t blocks = (uint32_t)((dp.count + kBlock / 64 - 1) / (kBlock / 64));
+    if (dp.h.count <= 0) return;
+    const uint32_t blocks = row_blocks(dp.h.count);
     DeviceScene sc = sc_in;
     if (!attach_deep(sc, blocks)) return;
     const size_t lds = stack_bytes(sc) + kDirectLdsBytes;

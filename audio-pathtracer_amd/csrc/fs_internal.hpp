@@ -410,40 +410,44 @@ void launch_trace_rays(const DeviceScene& sc, const float* o, const float* d, co
                        int32_t* hit, float* t, int32_t* tri, float* normal, hipStream_t s);
 // rays_per_wave < 64: sparse waves whose other lanes help with every closest-hit query; 64 = one ray per lane
 void launch_update_sound(const DeviceScene& sc, const SoundKParams& sp, SoundAccum* acc, int rays_per_wave, hipStream_t s);
-// fs_direct.hip (fs_update_direct_paths): a wave per source row, lane k = sample k.  src = the rows' sources, xyz + the
-// source's actor id as bits, in pinned host memory (read in place); offsets = the [samples][3] table of the call's n (device);
-// out = the device staging the rows are written to.  samples is already 1 for a point source.
-struct DirectKParams {
+// The common head of the three path queries' kernel arguments (fs_dev_paths.hpp reads nothing else of them): src = the rows' sources,
+// xyz + the source's actor id as bits; lis, lis_object = the listener and its actor; count rows.
+struct PathKHead {
     const float4* src;
-    const float* offsets;
-    fs_direct_path* out;
     float lis[3];
     uint32_t lis_object;
-    int32_t count, samples, max_surfaces, num_bands;
-    float radius, step, pullback, dist_divisor, sound_speed;
+    int32_t count, num_bands;
+    float step, pullback, dist_divisor, sound_speed;
+};
+// fs_direct.hip (fs_update_direct_paths): a wave per source row, lane k = sample k.  h.src lies in pinned host memory (read in
+// place); offsets = the [samples][3] table of the call's n (device); out = the device staging the rows are written to.  samples is
+// already 1 for a point source.
+struct DirectKParams {
+    PathKHead h;
+    const float* offsets;
+    fs_direct_path* out;
+    int32_t samples, max_surfaces;
+    float radius;
 };
 void launch_direct_paths(const DeviceScene& sc, const DirectKParams& dp, hipStream_t s);
 // fs_reflect.hip (fs_update_reflection_paths): reflect_scan_kernel, a thread per triangle record against every row of the call,
 // appends the filter's survivors to the rows' candidate lists; reflect_confirm_kernel, a wave per row, runs the two legs of every
-// candidate and writes the row and its paths.  src = the rows' sources, xyz + the source's actor id as bits (device); counters
-// [count] zeroed ahead of the scan; cand [count][max_candidates] leaf positions; rows [count] and paths [count][max_paths] = the
-// device staging the copy back reads.
+// candidate and writes the row and its paths.  h.src on the device; counters [count] zeroed ahead of the scan; cand
+// [count][max_candidates] leaf positions; rows [count] and paths [count][max_paths] = the device staging the copy back reads.
 struct ReflectKParams {
-    const float4* src;
+    PathKHead h;
     uint32_t* counters;
     uint32_t* cand;
     fs_reflection_row* rows;
     fs_reflection_path* paths;
-    float lis[3];
-    uint32_t lis_object;
-    int32_t count, max_paths, max_candidates, num_bands;
-    float margin, step, offset, pullback, dist_divisor, sound_speed;
+    int32_t max_paths, max_candidates;
+    float margin, offset;
 };
 void launch_reflection_paths(const DeviceScene& sc, const ReflectKParams& rp, hipStream_t s);
 // fs_diffract.hip (fs_update_diffraction_paths): diffract_scan_kernel, a thread per triangle record against every row of the call,
 // appends the filter's surviving (leaf position * 4 + edge) to the rows' candidate lists; diffract_confirm_kernel, a wave per row,
 // runs the three legs of every candidate, compacts the confirmed ones into `conf`, merges, ranks and writes the row and its paths.
-// src, counters, cand, rows, paths as ReflectKParams; conf [count][max_candidates] records, written and read by the row's wave only.
+// h.src, counters, cand, rows, paths as ReflectKParams; conf [count][max_candidates] records, written and read by the row's wave only.
 struct DiffractRecord {
     uint32_t length_bits, key;   // key = input index * 4 + edge
     float apex[3], direction[3];
@@ -452,16 +456,14 @@ struct DiffractRecord {
 };
 static_assert(sizeof(DiffractRecord) == 48, "DiffractRecord: twelve words");
 struct DiffractKParams {
-    const float4* src;
+    PathKHead h;
     uint32_t* counters;
     uint32_t* cand;
     DiffractRecord* conf;
     fs_diffraction_row* rows;
     fs_diffraction_path* paths;
-    float lis[3];
-    uint32_t lis_object;
-    int32_t count, max_paths, max_candidates, num_bands;
-    float margin, max_detour, offset, merge, step, pullback, dist_divisor, sound_speed;
+    int32_t max_paths, max_candidates;
+    float margin, max_detour, offset, merge;
     float k[FS_MAX_BANDS];   // k_b = 40 f_b / (sound_speed dist_divisor)
 };
 void launch_diffraction_paths(const DeviceScene& sc, const DiffractKParams& dp, hipStream_t s);

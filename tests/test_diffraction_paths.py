@@ -616,6 +616,51 @@ def test_steady_state_allocates_nothing(pkg):
     ctx.close()
 
 
+def interleaved_positions():
+    """33 seeded positions, the even ones on SRC's side of the partition and the odd ones on the listener's"""
+    pos = np.random.default_rng(0x1A7E).uniform([50.0, 50.0, 40.0], [450.0, 750.0, 260.0], (33, 3)).astype(np.float32)
+    pos[1::2, 0] += np.float32(500.0)
+    return pos
+
+
+@pytest.mark.gpu
+def test_queries_interleaved_on_one_context(pkg):
+    """the three queries share their chain, scan and staging code but no buffer: on one context, in an order in which every staging is
+    used (count 5: a confirm workgroup with three idle waves; count 1), then grown past its first capacity of 32 (count 33), then used
+    again with fewer rows, each call returns the bytes it returns as the first call of a fresh context"""
+    w = sheet_world(4)
+    assert len(w.tri) == 224
+    pos = interleaved_positions()
+    assert np.any(pos[:, 0] < 500.0) and np.any(pos[:, 0] > 500.0)
+
+    def fresh():
+        ctx = w.context(pkg)
+        ctx.set_listener(LIS)
+        return ctx, place(ctx, pos)
+
+    def run(ctx, h, query, count):
+        if query == "direct":
+            return (ctx.direct_paths(h[:count], samples=16, source_radius=30.0),)
+        return getattr(ctx, query + "_paths")(h[:count])
+
+    calls = [("diffraction", 5), ("direct", 33), ("reflection", 1), ("diffraction", 33), ("reflection", 33), ("direct", 5), ("reflection", 5),
+             ("diffraction", 1)]
+    ctx, h = fresh()
+    got = [run(ctx, h, query, count) for query, count in calls]
+    ctx.close()
+    for i, ((query, count), g) in enumerate(zip(calls, got)):
+        one, h1 = fresh()
+        want = run(one, h1, query, count)
+        one.close()
+        assert len(g) == len(want) and all(len(a) == count for a in g)
+        for a, b in zip(g, want):
+            assert a.tobytes() == b.tobytes(), f"call {i} ({query}, count {count}) differs from the same call on a fresh context"
+    # the comparison is not of zeros
+    direct, diffraction, reflection = got[1][0], got[3], got[4]
+    assert np.any(direct["visibility"] < 1.0) and np.any(direct["visibility"] == 1.0)
+    assert np.any(reflection[0]["returned"] > 0) and np.any(diffraction[0]["returned"] > 0)
+
+
 @pytest.mark.gpu
 def test_component_layer(pkg, oracle_mod):
     """a source walks behind the partition: UpdateDiffractionPaths is Context.diffraction_paths over the active sources, Voices()
