@@ -427,6 +427,26 @@ class Context:
                                                         rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
         return rows, paths
 
+    # ---- second-order reflection paths: the specular reflections off two triangles of every source of a tick ----
+    REFLECTION2_ROW_DTYPE = np.dtype([("near", np.uint32), ("candidates", np.uint32), ("found", np.uint32), ("returned", np.uint32),
+                                      ("flags", np.uint32)])
+    REFLECTION2_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("point", np.float32, (2, 3)), ("direction", np.float32, (3,)),
+                                  ("triangle", np.uint32, (2,)), ("material", np.uint32, (2,)), ("reflectance", np.float32, (_capi.MAX_BANDS,))])
+
+    def reflection2_paths(self, sources, **params):
+        """fs_update_reflection2_paths: (rows [count], paths [count][max_paths]) as structured arrays — per listed source the counts
+        (near, candidates, found, returned, flags) and its `returned` shortest paths listener -> PA on triangle a -> PB on triangle b
+        -> source (length cm, delay s, point [PA, PB], direction from the listener, triangle [a, b], material [2], reflectance [8];
+        entries beyond `returned` are zero); params = the fields of fs_reflection2_params (max_paths, max_near, max_candidates,
+        max_length, margin, step, offset, pullback, dist_divisor, sound_speed)"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        p = _capi.default_reflection2_params(**params)
+        rows = np.zeros(srcs.shape[0], dtype=self.REFLECTION2_ROW_DTYPE)
+        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=self.REFLECTION2_DTYPE)
+        self.check(self.lib.fs_update_reflection2_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
+                                                        rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
+        return rows, paths
+
     # ---- direct sound on the audio thread: fractional delay + band FIR for all sources of a callback ----
     RENDER_TARGET_DTYPE = np.dtype([("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,))])
 
@@ -881,6 +901,17 @@ class AudioRayTracingSubsystem:
         parts = [self.ctx.diffraction_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
         return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
 
+    def UpdateReflection2Paths(self, **params):
+        """the second-order specular reflections of all active sources: (rows, paths), row i and paths[i] for ActiveSources[i]
+        (Context.reflection2_paths; more than 256 sources take one call per 256)"""
+        srcs = [s._src for s in self.ActiveSources]
+        if not srcs:
+            return np.zeros(0, dtype=Context.REFLECTION2_ROW_DTYPE), np.zeros((0, 0), dtype=Context.REFLECTION2_DTYPE)
+        self._commit()
+        step = _capi.MAX_REFLECTION2_BATCH
+        parts = [self.ctx.reflection2_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
+        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
+
     def SetPipelining(self, depth):
         """fs_set_pipelining: Tick then updates the sources one after the other like the reference's loop (ARTS.cpp:60-68),
         streamed — every call launches one kernel that plans this source's frame, walks the previous source's and
@@ -1015,41 +1046,65 @@ class FrequenSeeAudioReflectionPlugin:
     def OnReleaseSource(self, component: FrequenSeeAudioComponent):
         self.ctx.reflection_render_release(component._src)
 
-    def Voices(self, row, paths, right=None, reference_length=None, diffraction=None):
+    @staticmethod
+    def SecondOrderKey(a, b):
+        """the key of the voice of a second-order path off the triangles a and b: 0x40000000 | (h >> 2) with
+        h = (a * 2654435761 + b) mod 2^32 — no first-order key (a triangle below 2^29), no diffraction key (0x80000000 | ...)"""
+        return _capi.REFLECTION2_VOICE_TAG | (((int(a) * 2654435761 + int(b)) & 0xFFFFFFFF) >> 2)
+
+    def Voices(self, row, paths, right=None, reference_length=None, diffraction=None, second=None):
         """one source's entries from its UpdateReflectionPaths result (row: its counts, paths: its path array), over the first
         row["returned"] paths: key = triangle, band_gain = reflectance, delay = the path's arrival time less the filter's own
         latency of (Taps - 1) / 2 samples, not below 0.  channel_gain = (1, 1); with `right` (the listener's unit right vector) the
         constant-power pan (cos t, sin t), t = (dot(direction, right) + 1) pi / 4; with reference_length (cm) scaled by
         min(1, reference_length / length).  diffraction = (row, paths) of the same source from UpdateDiffractionPaths appends one
         voice per returned diffraction path — band_gain = gain, delay, pan and distance law as above, key = 0x80000000 |
-        (4 triangle + edge): no reflection's key while the scene has fewer than 2^29 triangles, which is checked"""
+        (4 triangle + edge): no reflection's key while the scene has fewer than 2^29 triangles, which is checked.  second = (row,
+        paths) of the same source from UpdateReflection2Paths appends one voice per returned second-order path — band_gain =
+        reflectance, delay, pan and distance law as above, key = SecondOrderKey(triangle[0], triangle[1]).  Two second-order paths
+        of the row whose keys collide: the earlier in the row — the shorter, ties by (a, b) — is kept and the other dropped (the
+        renderer refuses duplicate keys)."""
         n = int(row["returned"])
         m = 0 if diffraction is None else int(diffraction[0]["returned"])
-        v = np.zeros(n + m, dtype=Context.REFLECTION_VOICE_DTYPE)
+        k = 0 if second is None else int(second[0]["returned"])
+        tagged = diffraction is not None or second is not None
+        v = np.zeros(n + m + k, dtype=Context.REFLECTION_VOICE_DTYPE)
         latency = ((self.Taps - 1) // 2) / float(self.ctx.cfg.sample_rate)
         r = None if right is None else np.asarray(right, np.float64).reshape(3)
-        for i in range(n + m):
-            p = paths[i] if i < n else diffraction[1][i - n]
-            if diffraction is not None and int(p["triangle"]) >= _capi.DIFFRACTION_VOICE_TAG >> 2:
-                raise ValueError("Voices: triangle index 2^29 or above: reflection and diffraction keys would collide")
-            v[i]["key"] = p["triangle"] if i < n else _capi.DIFFRACTION_VOICE_TAG | (int(p["triangle"]) * 4 + int(p["edge"]))
-            v[i]["delay"] = max(float(p["delay"]) - latency, 0.0)
-            v[i]["band_gain"] = p["reflectance"] if i < n else p["gain"]
+        seen, kept = set(), 0
+        for i in range(n + m + k):
+            p = paths[i] if i < n else (diffraction[1][i - n] if i < n + m else second[1][i - n - m])
+            if i < n + m:
+                if tagged and int(p["triangle"]) >= _capi.REFLECTION2_VOICE_TAG >> 1:
+                    raise ValueError("Voices: triangle index 2^29 or above: the keys of the path kinds would collide")
+                key = int(p["triangle"]) if i < n else _capi.DIFFRACTION_VOICE_TAG | (int(p["triangle"]) * 4 + int(p["edge"]))
+            else:
+                key = self.SecondOrderKey(p["triangle"][0], p["triangle"][1])
+                if key in seen:
+                    continue
+                seen.add(key)
+            o = v[kept]
+            kept += 1
+            o["key"] = key
+            o["delay"] = max(float(p["delay"]) - latency, 0.0)
+            o["band_gain"] = p["gain"] if n <= i < n + m else p["reflectance"]
             left_right = np.ones(2, np.float64)
             if r is not None:
                 t = (float(np.dot(np.asarray(p["direction"], np.float64), r)) + 1.0) * np.pi / 4.0
                 left_right = np.array([np.cos(t), np.sin(t)])
             if reference_length is not None:
                 left_right = left_right * min(1.0, float(reference_length) / float(p["length"]))
-            v[i]["channel_gain"] = left_right
-        return v
+            o["channel_gain"] = left_right
+        return v[:kept]
 
     def ProcessAudio(self, components, buffers, rows, paths, right=None, reference_length=None, want_out=True, want_mix=False,
-                     diffraction=None):
+                     diffraction=None, second=None):
         """buffers[i] is components[i]'s block, rows[i] / paths[i] its results of UpdateReflectionPaths; diffraction = the (rows,
-        paths) of UpdateDiffractionPaths, or None.  Returns what Context.reflection_render_process_batch does."""
+        paths) of UpdateDiffractionPaths, second = the (rows, paths) of UpdateReflection2Paths, or None.  Returns what
+        Context.reflection_render_process_batch does."""
         voices = [self.Voices(rows[i], paths[i], right, reference_length,
-                              None if diffraction is None else (diffraction[0][i], diffraction[1][i])) for i in range(len(components))]
+                              None if diffraction is None else (diffraction[0][i], diffraction[1][i]),
+                              None if second is None else (second[0][i], second[1][i])) for i in range(len(components))]
         return self.ctx.reflection_render_process_batch([c._src for c in components], buffers, voices,
                                                         want_out=want_out, want_mix=want_mix)
 

@@ -1,6 +1,7 @@
 // fs_capi_paths.cpp — the path queries of a tick, each one call for all its sources: fs_update_direct_paths (fs_direct.hip) with the
-// sample offsets it uses, fs_update_reflection_paths (fs_reflect.hip) and fs_update_diffraction_paths (fs_diffract.hip), their
-// defaults, and what the three share on the host: the prologue, the staging, the packing of the sources and the copy back.
+// sample offsets it uses, fs_update_reflection_paths (fs_reflect.hip), fs_update_diffraction_paths (fs_diffract.hip) and
+// fs_update_reflection2_paths (fs_reflect2.hip), their defaults, and what the four share on the host: the prologue, the staging, the
+// packing of the sources and the copy back.
 #include "fs_context.hpp"
 
 static_assert(sizeof(fs_direct_params) == 32, "fs_direct_params: eight words");
@@ -11,6 +12,9 @@ static_assert(sizeof(fs_reflection_row) == 16, "fs_reflection_row: four words");
 static_assert(sizeof(fs_diffraction_params) == 44, "fs_diffraction_params: eleven words");
 static_assert(sizeof(fs_diffraction_path) == 84, "fs_diffraction_path: thirteen words and the bands");
 static_assert(sizeof(fs_diffraction_row) == 20, "fs_diffraction_row: five words");
+static_assert(sizeof(fs_reflection2_params) == 44, "fs_reflection2_params: eleven words");
+static_assert(sizeof(fs_reflection2_path) == 92, "fs_reflection2_path: fifteen words and the bands");
+static_assert(sizeof(fs_reflection2_row) == 20, "fs_reflection2_row: five words");
 
 int PathStaging::grow(fs_context* ctx, int count, size_t pinned_bytes_per_row, size_t device_bytes_per_row) {
     if (count <= cap) return FS_OK;
@@ -297,6 +301,75 @@ int fs_update_diffraction_paths(fs_context* ctx, const fs_source* sources, int32
     launch_diffraction_paths(ctx->scene, dp, ctx->stream);
     FS_HIP(ctx, hipGetLastError());
     return copy_back_rows_paths(ctx, h_out, d_out, rows_bytes, sizeof(fs_diffraction_path) * (size_t)count * (size_t)p->max_paths, rows, paths);
+}
+
+// ---- second-order reflection paths ------------------------------------------------------------------------------------------
+void fs_reflection2_params_default(fs_reflection2_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = sizeof(fs_reflection2_params);
+    p->max_paths = 16;
+    p->max_near = 16384;
+    p->max_candidates = 256;
+    p->max_length = 1500.f;   // (2000 leaves most old_mine rows beyond max_near: DESIGN.md "Second-order reflection paths")
+    p->margin = 1e-3f;
+    p->step = 0.1f;
+    p->offset = 0.1f;
+    p->pullback = 0.1f;
+    p->dist_divisor = 1000.f;
+    p->sound_speed = 343.f;
+}
+
+int fs_update_reflection2_paths(fs_context* ctx, const fs_source* sources, int32_t count, const fs_reflection2_params* p,
+                                fs_reflection2_row* rows, fs_reflection2_path* paths) {
+    if (!ctx || !sources || !rows || !paths) return FS_ERR_INVALID_ARGUMENT;
+    if (count < 1 || count > FS_MAX_REFLECTION2_BATCH) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_REFLECTION2_BATCH)");
+    fs_reflection2_params def;
+    if (!p) { fs_reflection2_params_default(&def); p = &def; }
+    if (p->struct_size != sizeof(fs_reflection2_params)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reflection2_params.struct_size mismatch");
+    if (p->max_paths < 1 || p->max_paths > FS_MAX_REFLECTION2_PATHS || p->max_near < 1 || p->max_near > FS_MAX_REFLECTION2_NEAR ||
+        p->max_candidates < 1 || p->max_candidates > FS_MAX_REFLECTION2_CANDIDATES || !finite_above_zero(p->max_length) ||
+        !finite_at_least_zero(p->margin) || !finite_at_least_zero(p->step) || !finite_at_least_zero(p->offset) ||
+        !finite_at_least_zero(p->pullback) || !finite_above_zero(p->dist_divisor) || !finite_above_zero(p->sound_speed))
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad second-order reflection-path params");
+    { int pr = paths_prologue(ctx, sources, count); if (pr) return pr; }
+    constexpr size_t kNear = FS_MAX_REFLECTION2_NEAR, kCand = FS_MAX_REFLECTION2_CANDIDATES;
+    constexpr size_t kOutPerRow = sizeof(fs_reflection2_row) + FS_MAX_REFLECTION2_PATHS * sizeof(fs_reflection2_path);
+    PathStaging& st = ctx->reflect2_stage;
+    { int gr = st.grow(ctx, count, sizeof(float4) + kOutPerRow,
+                       sizeof(float4) + sizeof(uint32_t) * (2 + kNear + kCand) + sizeof(Reflect2Record) * kCand + kOutPerRow); if (gr) return gr; }
+    const size_t cap = (size_t)st.cap;
+    float4* h_src = reinterpret_cast<float4*>(st.h);
+    char* h_out = st.h + cap * sizeof(float4);
+    float4* d_src = reinterpret_cast<float4*>(st.d);
+    uint32_t* d_near_counters = reinterpret_cast<uint32_t*>(st.d + cap * sizeof(float4));
+    uint32_t* d_counters = d_near_counters + cap;
+    uint32_t* d_near = d_counters + cap;
+    uint32_t* d_cand = d_near + cap * kNear;
+    Reflect2Record* d_conf = reinterpret_cast<Reflect2Record*>(d_cand + cap * kCand);
+    char* d_out = reinterpret_cast<char*>(d_conf + cap * kCand);
+    const size_t rows_bytes = sizeof(fs_reflection2_row) * (size_t)count;
+    pack_sources(ctx, sources, count, h_src);
+    Reflect2KParams rp{};
+    rp.h = path_head(ctx, d_src, count, p->step, p->pullback, p->dist_divisor, p->sound_speed);
+    rp.near_counters = d_near_counters;
+    rp.counters = d_counters;
+    rp.near = d_near;
+    rp.cand = d_cand;
+    rp.conf = d_conf;
+    rp.rows = reinterpret_cast<fs_reflection2_row*>(d_out);
+    rp.paths = reinterpret_cast<fs_reflection2_path*>(d_out + rows_bytes);
+    rp.max_paths = p->max_paths;
+    rp.max_near = p->max_near;
+    rp.max_candidates = p->max_candidates;
+    rp.max_length = p->max_length;
+    rp.margin = p->margin;
+    rp.offset = p->offset;
+    FS_HIP(ctx, hipMemcpyAsync(d_src, h_src, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(ctx, hipMemsetAsync(d_near_counters, 0, sizeof(uint32_t) * 2 * cap, ctx->stream));   // both counter arrays: they lie side by side
+    launch_reflection2_paths(ctx->scene, rp, ctx->stream);
+    FS_HIP(ctx, hipGetLastError());
+    return copy_back_rows_paths(ctx, h_out, d_out, rows_bytes, sizeof(fs_reflection2_path) * (size_t)count * (size_t)p->max_paths, rows, paths);
 }
 
 }  // extern "C"

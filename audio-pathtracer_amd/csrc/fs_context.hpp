@@ -323,7 +323,10 @@ struct fs_context {
     // diffract_stage — pinned: as reflect_stage; device: sources [cap] float4 | confirmed records [cap][FS_MAX_DIFFRACTION_CANDIDATES]
     // | counters [cap] | candidates [cap][FS_MAX_DIFFRACTION_CANDIDATES] | rows and paths.  diffract_f: the band centres f_b of the
     // edges in force (diffract_f_edges, diffract_f_bands: what they were built from; rebuilt when fs_set_band_edges has changed them).
-    PathStaging direct_stage, reflect_stage, diffract_stage;
+    // reflect2_stage — pinned: as reflect_stage; device: sources [cap] float4 | near counters [cap] | candidate counters [cap] | near
+    // lists [cap][FS_MAX_REFLECTION2_NEAR] | candidates [cap][FS_MAX_REFLECTION2_CANDIDATES] | confirmed records
+    // [cap][FS_MAX_REFLECTION2_CANDIDATES] | rows and paths.
+    PathStaging direct_stage, reflect_stage, diffract_stage, reflect2_stage;
     float* d_direct_off = nullptr;
     uint64_t direct_off_have = 0;
     double diffract_f[FS_MAX_BANDS] = {};

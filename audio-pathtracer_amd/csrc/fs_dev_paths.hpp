@@ -1,4 +1,4 @@
-// fs_dev_paths.hpp — what the three path queries (fs_direct.hip, fs_reflect.hip, fs_diffract.hip) share on the device: the own-actor
+// fs_dev_paths.hpp — what the four path queries (fs_direct.hip, fs_reflect.hip, fs_diffract.hip, fs_reflect2.hip) share on the device: the own-actor
 // test, chain(o, d, len) of include/frequensee.h as one wave-convergent loop, the unpacking of a triangle record against a source
 // and the listener, the scan kernels' scaffold and the confirm kernels' common pieces.  Nothing here knows which query calls it: what
 // differs between them arrives as a callable.  Every fp32 operation stands where the header's rules put it (the files are built
@@ -11,7 +11,8 @@
 namespace fs {
 namespace {
 
-static_assert(FS_MAX_REFLECTION_BATCH == FS_MAX_DIFFRACTION_BATCH, "the scan kernels stage a call's rows in one LDS array size");
+static_assert(FS_MAX_REFLECTION_BATCH == FS_MAX_DIFFRACTION_BATCH && FS_MAX_REFLECTION_BATCH == FS_MAX_REFLECTION2_BATCH,
+              "the scan kernels stage a call's rows in one LDS array size");
 constexpr int kPathBatch = FS_MAX_REFLECTION_BATCH;
 constexpr int kRowsPerBlock = kBlock / 64;   // the wave-per-row kernels: a workgroup serves kBlock / 64 rows
 
@@ -156,9 +157,16 @@ __device__ __forceinline__ ConfirmRow confirm_row(const PathKHead& h, const uint
 __device__ __forceinline__ unsigned long long path_key(uint32_t length_bits, uint32_t index) { return ((unsigned long long)length_bits << 32) | index; }
 constexpr unsigned long long kNoPathKey = ~0ull;   // the key of an entry that is not ranked: smaller than no path's (a length's bits are never all ones)
 
+// the order of a path off two triangles: (length bits, a), then b — a 96-bit key
+struct PathKey96 {
+    unsigned long long hi;
+    uint32_t lo;
+};
+__device__ __forceinline__ bool operator<(const PathKey96& x, const PathKey96& y) { return x.hi < y.hi || (x.hi == y.hi && x.lo < y.lo); }
+
 // a path's rank: how many of the row's n keys are smaller.  No sort network, no atomics.
-template <typename KeyAt>
-__device__ __forceinline__ uint32_t rank_among(uint32_t n, unsigned long long key, KeyAt&& key_at) {
+template <typename Key, typename KeyAt>
+__device__ __forceinline__ uint32_t rank_among(uint32_t n, Key key, KeyAt&& key_at) {
     uint32_t rank = 0u;
     for (uint32_t j = 0u; j < n; ++j) rank += key_at(j) < key ? 1u : 0u;
     return rank;

@@ -467,6 +467,33 @@ struct DiffractKParams {
     float k[FS_MAX_BANDS];   // k_b = 40 f_b / (sound_speed dist_divisor)
 };
 void launch_diffraction_paths(const DeviceScene& sc, const DiffractKParams& dp, hipStream_t s);
+// fs_reflect2.hip (fs_update_reflection2_paths): reflect2_near_kernel, a thread per triangle record against every row of the call,
+// appends the leaf positions of the near triangles to the rows' near lists; reflect2_pair_kernel tests every ordered pair of a row's
+// near list and appends the survivors, as two near-list slots packed 15 + 15 bits, to the rows' candidate lists;
+// reflect2_confirm_kernel, a wave per row, runs the three legs of every candidate, compacts the confirmed ones into `conf`, ranks and
+// writes the row and its paths.  h.src, rows, paths as ReflectKParams; near_counters [count] and counters [count] lie side by side
+// (one clear); near [count][max_near]; cand [count][max_candidates]; conf [count][max_candidates] records, written and read by the
+// row's wave only.
+struct Reflect2Record {
+    uint32_t length_bits, a, b;   // a, b = input indices
+    float pa[3], pb[3], direction[3];
+    uint32_t material[2];
+};
+static_assert(sizeof(Reflect2Record) == 56, "Reflect2Record: fourteen words");
+static_assert(FS_MAX_REFLECTION2_NEAR <= 1 << 15, "a candidate is two near-list slots of 15 bits");
+struct Reflect2KParams {
+    PathKHead h;
+    uint32_t* near_counters;
+    uint32_t* counters;
+    uint32_t* near;
+    uint32_t* cand;
+    Reflect2Record* conf;
+    fs_reflection2_row* rows;
+    fs_reflection2_path* paths;
+    int32_t max_paths, max_near, max_candidates;
+    float max_length, margin, offset;
+};
+void launch_reflection2_paths(const DeviceScene& sc, const Reflect2KParams& rp, hipStream_t s);
 constexpr int kReverbRing = 65536;   // per-channel history ring (floats), matches kRevRing in the kernels
 // fs_reverb.hip (the reverb callback): one descriptor per row of the call, in list order, read by every kernel of the callback.
 struct ReverbItem {

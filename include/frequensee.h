@@ -56,6 +56,7 @@
  *             fs_direct_params_default fs_direct_sample_offsets fs_update_direct_paths
  *             fs_reflection_params_default fs_update_reflection_paths
  *             fs_diffraction_params_default fs_update_diffraction_paths
+ *             fs_reflection2_params_default fs_update_reflection2_paths
  *             fs_direct_band_kernels fs_direct_render_init fs_direct_render_release fs_direct_render_process_batch
  *             fs_reflection_render_init fs_reflection_render_release fs_reflection_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
@@ -823,6 +824,94 @@ void fs_diffraction_params_default(fs_diffraction_params* p);
 int fs_update_diffraction_paths(fs_context* ctx, const fs_source* sources, int32_t count,
                                 const fs_diffraction_params* params /* NULL = defaults */,
                                 fs_diffraction_row* rows /* [count] */, fs_diffraction_path* paths /* [count][max_paths] */);
+
+/* ---- second-order reflection paths (EXTENDED): the specular reflections off two triangles of every source of a tick -------
+ * What fills the gap between the few first-order reflections and the traced late field: listener -> PA on triangle a -> PB on
+ * triangle b -> source.  a is the reflector at the listener's end, b the one at the source's end.  Found by an exhaustive scan of the
+ * ordered pairs of the triangles near enough to lie on a path within the length cap: no sampling, no seed.  Specified to the bit with
+ * the conventions of "reflection paths" (-ffp-contract=off, every fp32 operation rounded on its own in the order written, fmaf
+ * fused, a.b = (a.x b.x + a.y b.y) + a.z b.z, cross = product, product, subtract; divide and sqrtf correctly rounded; the records
+ * v0, e1, e2; own actors by the ids so / lo).  Every marginal decision beyond the filters is taken by the closest-hit query
+ * fs_trace_rays answers.
+ *   MT(o, D, k), the Moeller-Trumbore block of the first-order rule's step 1 read for the segment o + s D and triangle k:
+ * p = cross(D, e2); det = e1.p; det == 0: rejected; inv = 1.0f / det; tv = o - v0; u = (tv.p) inv; q = cross(tv, e1); v = (D.q) inv;
+ * s = (e2.q) inv.  It passes iff u >= -m && v >= -m && u + v <= 1 + m && s > 0 && s < 1 with m = margin.
+ *   n_k = cross(e1, e2) and nn_k = n_k.n_k of triangle k.  Per source at S, listener at L:
+ *   0. Near set (part of the definition, not an optimisation that may differ).  Triangle k is NEAR iff nn_k != 0, it is not an own
+ *      actor's (its object id equals so or lo, that id not FS_NO_OBJECT) and
+ *      ((sqrtf(a.a) + sqrtf(b.b)) - (reach + reach)) <= max_length with a = S - v0, b = L - v0 and
+ *      reach = fmaxf(sqrtf(e1.e1), sqrtf(e2.e2)): every point of a triangle lies within reach of v0, so a triangle outside this
+ *      bound carries no path of at most max_length.  near = their number.  near > max_near: flags = FS_REFLECTION2_NEAR_OVERFLOW,
+ *      every other count is 0 and nothing else of the row is computed.
+ *   1. Pair filter, for every ordered pair (b, a) of near triangles with a != b.  hS = (S - v0_b).n_b; hS == 0: rejected.
+ *      k1 = (2 hS) / nn_b; S1 = S - k1 n_b per component (the image in b).  h1 = (S1 - v0_a).n_a; hL = (L - v0_a).n_a; kept only if
+ *      (h1 > 0 && hL > 0) || (h1 < 0 && hL < 0).  k2 = (2 h1) / nn_a; S2 = S1 - k2 n_a (the image of the image); D = S2 - L.
+ *      MT(L, D, a) passes and gives s; sqrtf(D.D) <= max_length.  Q = fmaf(s, D, L) per component; hQ = (Q - v0_b).n_b; kept only if
+ *      (hQ > 0 && hS > 0) || (hQ < 0 && hS < 0).  D2 = S1 - Q; MT(Q, D2, b) passes.  candidates = the number of ordered pairs that
+ *      pass.  candidates > max_candidates: flags = FS_REFLECTION2_OVERFLOW, found = returned = 0 (the count is exact even where
+ *      the list is capped).
+ *   2. Leg 1, per candidate: the first-order rule's leg 1 from L along D with target a (len1 = sqrtf(D.D); d = D (1.0f / len1);
+ *      own actors are passed by adv = t + step; the first other triangle hit must be a).  It yields t1 = acc + t, PA = fmaf(t, d, o)
+ *      and the unit direction d.
+ *   3. Leg 2.  E = S1 - PA; len2 = sqrtf(E.E); len2 == 0: rejected.  d2 = E (1.0f / len2); o = fmaf(offset, d2, PA) per component;
+ *      rem = len2 - offset; acc = 0.  The queries are those of leg 1 (!(rem > 0) before a query or a query without a hit: rejected);
+ *      the first triangle hit that is not an own actor's must be b: t2 = offset + (acc + t), PB = fmaf(t, d2, o).  Any other
+ *      triangle or running out of queries: rejected.
+ *   4. Leg 3, the first-order rule's leg 2 from PB to S.  e = S - PB; len3 = sqrtf(e.e); len3 == 0: rejected.  d3 = e (1.0f / len3);
+ *      chain(fmaf(offset, d3, PB), d3, (len3 - offset) - pullback) of "direct paths" with max_surfaces = 0 and this call's step.  The
+ *      pair is CONFIRMED iff the chain reached with crossed == 0.
+ *   5. Row.  length = (t1 + t2) + len3; delay = (length / dist_divisor) / sound_speed; point[0] = PA, point[1] = PB; direction = d;
+ *      triangle[0] = a, triangle[1] = b (input indices); material[0], material[1] their material ids; reflectance[band] =
+ *      gA[band] * gB[band], one fp32 multiply of the two specular gains of "reflection paths" (1 for a surface without a material),
+ *      0 beyond num_bands.  found = the number confirmed.  The confirmed paths are ordered by (length as fp32 bits, a, b) ascending;
+ *      the first returned = min(found, max_paths) are written, the entries beyond `returned` (all of them for an overflowed row) as
+ *      all-zero bytes.  Nothing depends on which builder made the tree, on the order of collection or on count.  An empty
+ *      committed scene gives rows of zeros.
+ *   The key a host gives the voice of such a path (fs_reflection_render_process_batch) is 0x40000000 | (h >> 2) with
+ *   h = (a * 2654435761 + b) mod 2^32: disjoint from the first-order keys (a triangle below 2^29) and from the diffraction keys
+ *   (0x80000000 | ...).  Two paths of one row may share a key: a host keeps the shorter (the earlier in the row) and drops the other.
+ *   Errors, ordering, refusals and staging: as fs_update_reflection_paths, with FS_MAX_REFLECTION2_BATCH — the source table's
+ *   upload, one clear (of both counter arrays), THREE launches on the compute stream (the near scan of all triangles against all rows;
+ *   the pair filter over every row's near list; the confirmation, a wave per row), one copy back and one wait, whatever count is;
+ *   staging of its own, grown only at the first call with a larger count.  max_length must be finite and > 0.
+ *   Cost: near^2 pair tests per row.  The default max_length keeps near below the default max_near around a listener in a mine of
+ *   100 000 triangles (at most 14 728 of 16 384 for sources within 600 cm; at 2000 cm most such rows overflow). */
+#define FS_MAX_REFLECTION2_PATHS         32
+#define FS_MAX_REFLECTION2_NEAR       32768
+#define FS_MAX_REFLECTION2_CANDIDATES  1024
+#define FS_MAX_REFLECTION2_BATCH        256
+#define FS_REFLECTION2_OVERFLOW          1u   /* fs_reflection2_row.flags: more candidates than max_candidates */
+#define FS_REFLECTION2_NEAR_OVERFLOW     2u   /* fs_reflection2_row.flags: more near triangles than max_near */
+typedef struct fs_reflection2_params {
+    uint32_t struct_size;     /* = sizeof(fs_reflection2_params) */
+    int32_t  max_paths;       /* 1 .. FS_MAX_REFLECTION2_PATHS, default 16: rows of `paths` per source */
+    int32_t  max_near;        /* 1 .. FS_MAX_REFLECTION2_NEAR, default 16384 */
+    int32_t  max_candidates;  /* 1 .. FS_MAX_REFLECTION2_CANDIDATES, default 256 */
+    float    max_length;      /* cm, > 0, finite; default 1500: the longest path looked for */
+    float    margin;          /* as fs_reflection_params, default 1e-3 */
+    float    step;            /* as fs_reflection_params, default 0.1 */
+    float    offset;          /* cm legs 2 and 3 start off their reflector, >= 0; default 0.1 */
+    float    pullback;        /* cm leg 3 stops short of the source, >= 0; default 0.1 */
+    float    dist_divisor;    /* 1000, as fs_params */
+    float    sound_speed;     /* 343, as fs_params */
+} fs_reflection2_params;
+
+typedef struct fs_reflection2_path {
+    float    length;          /* cm, listener -> PA -> PB -> source */
+    float    delay;           /* s, on the impulse response's time axis: (length / dist_divisor) / sound_speed */
+    float    point[2][3];     /* PA, PB */
+    float    direction[3];    /* unit, from the listener towards PA: what a host pans by */
+    uint32_t triangle[2];     /* input indices of a and b */
+    uint32_t material[2];     /* their material ids (FS_NO_MATERIAL possible) */
+    float    reflectance[FS_MAX_BANDS]; /* gA gB; bands beyond num_bands: 0 */
+} fs_reflection2_path;        /* an array element: no struct_size; 92 bytes */
+
+typedef struct fs_reflection2_row { uint32_t near, candidates, found, returned, flags; } fs_reflection2_row;
+
+void fs_reflection2_params_default(fs_reflection2_params* p);
+int fs_update_reflection2_paths(fs_context* ctx, const fs_source* sources, int32_t count,
+                                const fs_reflection2_params* params /* NULL = defaults */,
+                                fs_reflection2_row* rows /* [count] */, fs_reflection2_path* paths /* [count][max_paths] */);
 
 /* ---- engine line trace the BVH kernel replaces (UWorld::LineTraceSingleByObjectType; call sites
  *      ARTS.cpp:252-254 any-hit, :340-342 closest-hit). Batch query, host arrays. ------------------- */
