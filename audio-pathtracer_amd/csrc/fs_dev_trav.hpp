@@ -36,6 +36,15 @@ __device__ __forceinline__ void trav_init(Trav& T, float tmax, bool scene_nonemp
     T.nv = 0u; T.nt = 0u; T.ni = 0u; T.nl = 0u; T.nd = 0u;
 }
 __device__ __forceinline__ bool trav_busy(const Trav& T) { return T.tri_i < T.tri_n || T.cur != kDone; }
+// The lanes of the wave for which `p` holds, for the masks of every step.  `p` should be ONE compare on registers: then
+// the mask is the compare's own scalar result.  __ballot(int), the ballot of `a || b` and the ballot of a condition the
+// compiler has traced back through branches all turn the lane mask they start from into a 0 / 1 per lane and compare
+// that again (v_cndmask 0, 1 + v_cmp_ne: two vector instructions per mask).
+__device__ __forceinline__ unsigned long long lane_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// the number of lanes of `m` below this one (v_mbcnt: no per-lane mask of the lower lanes has to live in registers)
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
 
 // The step in pieces, ordered so that as little as possible lies between the arrival of a lane's records and the
 // request for its next ones (round 3: one extra L1-hit load per step costs the walk as much as 20 more vector
@@ -67,6 +76,11 @@ struct TriRegs { v4f a, b, c; };
 // early, or earlier for a lane that has given entries away — trav_maintain looks again) and for a flagged lane with
 // sp < 2 (sp - 2 wraps) or close to its last rows.  (Tests in the pops themselves cost 2 % of the walk, a deep count
 // read from LDS on every empty pop 7 %: profiles/r03_occupancy_ab.log.)
+// The pops read LDS and wait for it (up to two round trips per step, on the wave's serial chain between its node
+// arithmetic and its request).  Keeping the top row(s) in registers instead was built three ways and measured — a reload
+// inside the pop, one row or two rows read again behind every step's request (the last leaves no LDS read and no LDS
+// wait on the chain at all): SQ_WAIT_ANY - 3 %, SQ_WAIT_INST_ANY + 2 %, the frame 1.2 - 1.9 % SLOWER each time.  Not
+// kept: DESIGN.md section 5 "The stack top in a register", profiles/stack_top_*.
 constexpr int kDeepSb = -2;
 __device__ __forceinline__ int* trav_deep_count(const DeviceScene& sc, int* stack) { return stack + (size_t)sc.stack_limit * kBlock; }
 __device__ __forceinline__ void trav_deep_reset(const DeviceScene& sc, int* stack) {
@@ -133,7 +147,11 @@ __device__ __forceinline__ void trav_settle(const DeviceScene& sc, Trav& T, int*
 // number of vector memory instructions per step whatever its lanes need, so counted waits stay possible.
 // (No cache-policy bits on these requests: measured, none helps — DESIGN.md section 5.)
 __device__ __forceinline__ void trav_issue(const DeviceScene& sc, const Trav& T, NodeRegs& N, TriRegs& X) {
-    const unsigned long long mn = __ballot(T.cur >= 0), mt = __ballot(T.tri_i < T.tri_n);   // subsets of EXEC
+    // (the compare is made on the register: what the compiler knows of tri_i < tri_n from the branches behind it is a
+    // lane mask spread over several scalar registers, which it would turn into 0 / 1 per lane and compare again)
+    int ti = T.tri_i;
+    asm volatile("" : "+v"(ti));
+    const unsigned long long mn = lane_mask(T.cur >= 0), mt = lane_mask(ti < T.tri_n);   // subsets of EXEC
     // (addresses of lanes that want nothing are never dereferenced)
     const char* np = reinterpret_cast<const char*>(sc.nodes) + (size_t)(uint32_t)T.cur * sizeof(NodeQ4);
     const Tri48* tp = sc.tris + (uint32_t)T.tri_i;
@@ -283,7 +301,7 @@ __device__ __forceinline__ void trav_advance(const DeviceScene& sc, const Ray& r
     // scalar branch for the wave, so that the node part stays a single basic block; lanes of trees without a deep store
     // (stack_limit = worst case + 1) may pass the test near their worst case and return at once.
 #ifndef FS_DEEP_NO_CHECK   // compiled out in the wide flavour of the frame kernel (worst-case rows, fs_frame.hip)
-    if (__builtin_expect(__ballot(trav_needs_maintenance(sc, T)) != 0ull, 0)) {
+    if (__builtin_expect(lane_mask(trav_needs_maintenance(sc, T)) != 0ull, 0)) {
         if (trav_needs_maintenance(sc, T)) trav_maintain(sc, T, stack);
     }
 #endif
@@ -405,8 +423,7 @@ __device__ __forceinline__ bool trav_shared(const DeviceScene& sc, bool has_ray,
                                             uint32_t ignore, Trav& T, int* stack, int* share) {
     const ShareArea<ANY, IGN> A(share);
     float* rs = A.rs;
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wbase = tid & ~63u;
-    const unsigned long long lt = (1ull << lane) - 1ull;
+    const unsigned tid = threadIdx.x, wbase = tid & ~63u;
     // publish this lane's ray and clear its mailbox
     rs[0 * kBlock + tid] = own.ox;  rs[1 * kBlock + tid] = own.oy;  rs[2 * kBlock + tid] = own.oz;
     rs[3 * kBlock + tid] = own.dx;  rs[4 * kBlock + tid] = own.dy;  rs[5 * kBlock + tid] = own.dz;
@@ -441,7 +458,7 @@ __device__ __forceinline__ bool trav_shared(const DeviceScene& sc, bool has_ray,
 #ifdef FS_TRAV_STATS
         {
             const unsigned long long mb = __ballot(trav_busy(T)), mth = __ballot(trav_busy(T) && owner != tid);
-            if (lane == 0u) {
+            if ((tid & 63u) == 0u) {
                 unsigned long long* gs = g_trav_stats + (ANY ? 16 : 0);
                 atomicAdd(&gs[8], (unsigned long long)__popcll(mb)); atomicAdd(&gs[9], (unsigned long long)__popcll(mth));
                 atomicAdd(&gs[10], 1ull);
@@ -460,16 +477,17 @@ __device__ __forceinline__ bool trav_shared(const DeviceScene& sc, bool has_ray,
             }
         }
         const bool idle = !trav_busy(T);
-        const unsigned long long busy_m = __ballot(!idle);
+        // (one ballot per compare, joined as scalars)
+        const unsigned long long busy_m = lane_mask(T.tri_i < T.tri_n) | lane_mask(T.cur != kDone);
         if (busy_m == 0ull) return true;                // nothing left anywhere in the wave
-        const unsigned long long idle_m = __ballot(idle);
+        const unsigned long long idle_m = lane_mask(true) & ~busy_m;   // (the lanes here that are not busy: no second ballot)
         if (__popcll(idle_m) < kShareMinIdle) return false;
         const bool can_give = !idle && T.sp > T.sb && T.sb >= 0;   // (a lane with entries in the deep store keeps what it has)
-        const unsigned long long give_m = __ballot(can_give);
+        const unsigned long long give_m = lane_mask(can_give);
         if (idle_m != 0ull && give_m != 0ull) {
             const int n = min(__popcll(idle_m), __popcll(give_m));
             if (can_give) {
-                const int r = __popcll(give_m & lt);
+                const int r = lanes_below(give_m);
                 if (r < n) {
                     A.dref[wbase + r] = stack[T.sb * kBlock];
                     A.down[wbase + r] = (int)owner;
@@ -479,7 +497,7 @@ __device__ __forceinline__ bool trav_shared(const DeviceScene& sc, bool has_ray,
                 }
             }
             if (idle) {
-                const int r = __popcll(idle_m & lt);
+                const int r = lanes_below(idle_m);
                 if (r < n) {
                     const int e = A.dref[wbase + r];
                     owner = (unsigned)A.down[wbase + r];
