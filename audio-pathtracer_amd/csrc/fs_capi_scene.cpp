@@ -254,6 +254,9 @@ static int refresh_coop_nodes(fs_context* ctx, bool topology_changed) {
 }
 
 static int finish_commit(fs_context* ctx, size_t scene_bytes) {
+    // the traversal's requests carry 32-bit byte offsets into the node and triangle records (DeviceScene, fs_internal.hpp)
+    if ((uint64_t)ctx->bvh.nodes.size() * sizeof(NodeQ4) > 0xFFFFFFFFull || (uint64_t)ctx->T * sizeof(Tri48) > 0xFFFFFFFFull)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "scene too large: node or triangle records exceed 4 GiB");
     object_moves_after_commit(ctx);
     ctx->amax = 0.f;
     for (float v : ctx->h_xyz) ctx->amax = std::max(ctx->amax, std::fabs(v));

@@ -15,7 +15,6 @@ namespace {
 // of the tests, so results are unchanged.  A lane can be parked/resumed between any two steps.
 // `stack` is this lane's column of the workgroup's LDS stack (element i at stack[i * kBlock]).
 // ---------------------------------------------------------------------------------------------------
-typedef float v2f __attribute__((ext_vector_type(2)));
 
 struct Trav {
     int cur;        // next node: >= 0 inner index, < 0 leaf code (~cur = first*4 + count-1), kDone = none
@@ -29,10 +28,13 @@ struct Trav {
     uint32_t ni, nl, nd;   // ... and (one lane per wave) node-request instructions, their active lanes, the distinct records among those
 };
 
+// The bound T.t is canonical (no signalling NaN) from the start: it enters here and with a taken subtree, and every
+// later value is the result of a division.  The node part's min with it then needs no canonicalising v_max per visit.
+__device__ __forceinline__ float canonical_bound(float t) { return __builtin_canonicalizef(t); }
 __device__ __forceinline__ void trav_init(Trav& T, float tmax, bool scene_nonempty) {
     T.cur = scene_nonempty ? 0 : kDone;
     T.sp = 0; T.sb = 0; T.tri_i = 0; T.tri_n = 0;
-    T.t = tmax; T.leaf_index = -1; T.id = 0xFFFFFFFFu;
+    T.t = canonical_bound(tmax); T.leaf_index = -1; T.id = 0xFFFFFFFFu;
     T.nv = 0u; T.nt = 0u; T.ni = 0u; T.nl = 0u; T.nd = 0u;
 }
 __device__ __forceinline__ bool trav_busy(const Trav& T) { return T.tri_i < T.tri_n || T.cur != kDone; }
@@ -145,33 +147,42 @@ __device__ __forceinline__ void trav_settle(const DeviceScene& sc, Trav& T, int*
 // lost a day's first build to exactly that; tools/check_isa_hazards.py now proves the absence of such accesses on the
 // final ISA).  A tied operand chain issue -> wait -> use has no phi to resolve.  (2) Every wave executes the same
 // number of vector memory instructions per step whatever its lanes need, so counted waits stay possible.
+// Addresses: the record arrays' bases are wave-uniform and stay in scalar registers; a lane supplies only its 32-bit
+// byte offset (node index << 6, triangle index * 48 as a shift-add and a shift) and the 16-byte quarters are the
+// instruction's own offset — `global_load_dwordx4 vdst, voff, s[base:base+1] offset:n`.  No 64-bit vector arithmetic
+// and no address pairs in a kernel held to 128 registers; fs_scene_commit refuses a scene whose record arrays exceed
+// 4 GiB (DeviceScene, fs_internal.hpp).
 // (No cache-policy bits on these requests: measured, none helps — DESIGN.md section 5.)
-__device__ __forceinline__ void trav_issue(const DeviceScene& sc, const Trav& T, NodeRegs& N, TriRegs& X) {
+__device__ __forceinline__ void trav_issue(const DeviceScene& sc, Trav& T, NodeRegs& N, TriRegs& X) {
     // (the compare is made on the register: what the compiler knows of tri_i < tri_n from the branches behind it is a
     // lane mask spread over several scalar registers, which it would turn into 0 / 1 per lane and compare again)
-    int ti = T.tri_i;
-    asm volatile("" : "+v"(ti));
+    // (made opaque in place: a copy of tri_i for the compare would be a v_mov on the way to the request)
+    asm volatile("" : "+v"(T.tri_i));
+    const int ti = T.tri_i;
     const unsigned long long mn = lane_mask(T.cur >= 0), mt = lane_mask(ti < T.tri_n);   // subsets of EXEC
-    // (addresses of lanes that want nothing are never dereferenced)
-    const char* np = reinterpret_cast<const char*>(sc.nodes) + (size_t)(uint32_t)T.cur * sizeof(NodeQ4);
-    const Tri48* tp = sc.tris + (uint32_t)T.tri_i;
+    // (offsets of lanes that want nothing are never dereferenced)
+    static_assert(sizeof(NodeQ4) == 64 && sizeof(Tri48) == 48, "the request's byte offsets");
+    const uint32_t no = (uint32_t)T.cur << 6;
+    uint32_t to = ((uint32_t)ti << 1) + (uint32_t)ti;   // * 48 as a shift-add and a shift (left alone the compiler
+    asm("" : "+v"(to));                                 //   makes it one quarter-rate v_mul_lo_u32)
+    to <<= 4;
     unsigned long long sv;
     asm volatile("s_mov_b64 %[sv], exec\n\t"
                  "s_mov_b64 exec, %[mn]\n\t"
-                 "global_load_dwordx4 %[q0], %[np], off\n\t"
-                 "global_load_dwordx4 %[q1], %[np], off offset:16\n\t"
-                 "global_load_dwordx4 %[q2], %[np], off offset:32\n\t"
-                 "global_load_dwordx4 %[q3], %[np], off offset:48\n\t"
+                 "global_load_dwordx4 %[q0], %[no], %[nb]\n\t"
+                 "global_load_dwordx4 %[q1], %[no], %[nb] offset:16\n\t"
+                 "global_load_dwordx4 %[q2], %[no], %[nb] offset:32\n\t"
+                 "global_load_dwordx4 %[q3], %[no], %[nb] offset:48\n\t"
                  "s_mov_b64 exec, %[mt]\n\t"
                  "s_cbranch_execz 1f\n\t"      // one wave step in four has no lane with a pending triangle
-                 "global_load_dwordx4 %[ta], %[tp], off\n\t"
-                 "global_load_dwordx4 %[tb], %[tp], off offset:16\n\t"
-                 "global_load_dwordx4 %[tc], %[tp], off offset:32\n"
+                 "global_load_dwordx4 %[ta], %[to], %[tb_]\n\t"
+                 "global_load_dwordx4 %[tb], %[to], %[tb_] offset:16\n\t"
+                 "global_load_dwordx4 %[tc], %[to], %[tb_] offset:32\n"
                  "1:\n\t"
                  "s_mov_b64 exec, %[sv]"
                  : [q0] "+&v"(N.q0), [q1] "+&v"(N.q1), [q2] "+&v"(N.q2), [q3] "+&v"(N.q3),
                    [ta] "+&v"(X.a), [tb] "+&v"(X.b), [tc] "+&v"(X.c), [sv] "=&s"(sv)
-                 : [np] "v"(np), [tp] "v"(tp), [mn] "s"(mn), [mt] "s"(mt)
+                 : [no] "v"(no), [to] "v"(to), [nb] "s"(sc.nodes), [tb_] "s"(sc.tris), [mn] "s"(mn), [mt] "s"(mt)
                  : "memory");
 }
 
@@ -208,8 +219,33 @@ __device__ __forceinline__ void trav_tri_part(const Ray& r, Trav& T, const TriRe
     }
 }
 
+// The signs of a ray's direction (of its reciprocals: `inv < 0.0f`, so -0.0 and NaN count as positive) as three lane
+// masks of the wave, in scalar registers.  They pick the entry / exit plane words of every node visit; a lane's ray
+// changes only when it takes another lane's ray in the sharing round, so the three compares are made where a traversal
+// starts and again in a round in which lanes have taken rays (for the whole wave), not once per visit.  Only lanes
+// that were active at ray_signs() may use the masks.
+struct RaySigns { unsigned long long x, y, z; };
+__device__ __forceinline__ RaySigns ray_signs(const Ray& r) {
+    return RaySigns{lane_mask(r.ix < 0.0f), lane_mask(r.iy < 0.0f), lane_mask(r.iz < 0.0f)};
+}
+// m's bit of this lane ? if_set : if_clear, the mask as the select's scalar condition
+__device__ __forceinline__ uint32_t lane_select(unsigned long long m, uint32_t if_set, uint32_t if_clear) {
+    uint32_t out;
+    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(out) : "v"(if_clear), "v"(if_set), "s"(m));
+    return out;
+}
+
+// fminf of two canonical values as the bare instruction (the compiler cannot see that the loop-carried bound is
+// canonical — trav_init — and would put v_max_f32 t, t in front of every visit's mins)
+__device__ __forceinline__ float min_canonical(float a, float b) {
+    float out;
+    asm("v_min_f32 %0, %1, %2" : "=v"(out) : "v"(a), "v"(b));
+    return out;
+}
+
 // the lane's inner node (T.cur >= 0): 4 child boxes, near-first order, far children to the stack, next node
-__device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray& r, Trav& T, int* stack, const NodeRegs& N) {
+__device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray& r, const RaySigns& sg, Trav& T, int* stack,
+                                               const NodeRegs& N) {
     const float4 q0 = make_float4(N.q0.x, N.q0.y, N.q0.z, N.q0.w), q1 = make_float4(N.q1.x, N.q1.y, N.q1.z, N.q1.w),
                  q2 = make_float4(N.q2.x, N.q2.y, N.q2.z, N.q2.w), q3 = make_float4(N.q3.x, N.q3.y, N.q3.z, N.q3.w);
     // ---- 4-wide node, child boxes on the node's 8-bit grid: plane distance = fma(q, step*inv, (origin-o)*inv)
@@ -220,23 +256,20 @@ __device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray&
     const uint32_t lox = __float_as_uint(q1.x), loy = __float_as_uint(q1.y), loz = __float_as_uint(q1.z);
     const uint32_t hix = __float_as_uint(q1.w), hiy = __float_as_uint(q2.x), hiz = __float_as_uint(q2.y);
     // the ray's direction signs pick the entry / exit plane words once per node
-    const uint32_t nxw = r.ix < 0.0f ? hix : lox, fxw = r.ix < 0.0f ? lox : hix;
-    const uint32_t nyw = r.iy < 0.0f ? hiy : loy, fyw = r.iy < 0.0f ? loy : hiy;
-    const uint32_t nzw = r.iz < 0.0f ? hiz : loz, fzw = r.iz < 0.0f ? loz : hiz;
-    const v2f sx2 = {sx, sx}, sy2 = {sy, sy}, sz2 = {sz, sz}, bx2 = {bx, bx}, by2 = {by, by}, bz2 = {bz, bz};
+    const uint32_t nxw = lane_select(sg.x, hix, lox), fxw = lane_select(sg.x, lox, hix);
+    const uint32_t nyw = lane_select(sg.y, hiy, loy), fyw = lane_select(sg.y, loy, hiy);
+    const uint32_t nzw = lane_select(sg.z, hiz, loz), fzw = lane_select(sg.z, loz, hiz);
     uint32_t key[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        // (entry, exit) plane distances per axis as one packed fma each (v_pk_fma_f32)
-        const v2f qx = {(float)((nxw >> (8 * c)) & 0xFFu), (float)((fxw >> (8 * c)) & 0xFFu)};
-        const v2f qy = {(float)((nyw >> (8 * c)) & 0xFFu), (float)((fyw >> (8 * c)) & 0xFFu)};
-        const v2f qz = {(float)((nzw >> (8 * c)) & 0xFFu), (float)((fzw >> (8 * c)) & 0xFFu)};
-        const v2f tx = __builtin_elementwise_fma(qx, sx2, bx2);
-        const v2f ty = __builtin_elementwise_fma(qy, sy2, by2);
-        const v2f tz = __builtin_elementwise_fma(qz, sz2, bz2);
-        const float tnx = tx.x, tfx = tx.y, tny = ty.x, tfy = ty.y, tnz = tz.x, tfz = tz.y;
+        // entry and exit plane distances per axis: six plain fmas.  (As three v_pk_fma_f32 — twelve instructions fewer
+        // per visit — the frame is 1.4 % slower: a packed f32 operation costs more than the two it replaces and wants
+        // its operands in aligned register pairs.  DESIGN.md section 5.)
+        const float tnx = fmaf((float)((nxw >> (8 * c)) & 0xFFu), sx, bx), tfx = fmaf((float)((fxw >> (8 * c)) & 0xFFu), sx, bx);
+        const float tny = fmaf((float)((nyw >> (8 * c)) & 0xFFu), sy, by), tfy = fmaf((float)((fyw >> (8 * c)) & 0xFFu), sy, by);
+        const float tnz = fmaf((float)((nzw >> (8 * c)) & 0xFFu), sz, bz), tfz = fmaf((float)((fzw >> (8 * c)) & 0xFFu), sz, bz);
         const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, 0.0f));
-        const float tf = fminf(fminf(tfx, tfy), fminf(tfz, T.t));
+        const float tf = fminf(fminf(tfx, tfy), min_canonical(tfz, T.t));
         const bool h = tn <= tf;
         // entry distance (>= 0, so its bits order like an integer) with the slot in the low 2 bits; a missed child
         // sorts behind every hit one (kMissKey | slot)
@@ -279,7 +312,7 @@ __device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray&
 // triangle into `nxt`), then the triangle part on `cur` while they are in flight.  Entry: the records of (T.cur,
 // T.tri_i) have arrived in (N, cur).
 template <bool ANY, bool IGN = false, bool COUNT = false>
-__device__ __forceinline__ void trav_advance(const DeviceScene& sc, const Ray& r, Trav& T, int* stack, NodeRegs& N,
+__device__ __forceinline__ void trav_advance(const DeviceScene& sc, const Ray& r, const RaySigns& sg, Trav& T, int* stack, NodeRegs& N,
                                              TriRegs& cur, TriRegs& nxt, uint32_t ignore_object = 0xFFFFFFFFu) {
     const bool has_tri = T.tri_i < T.tri_n;
     const bool has_node = T.cur >= 0;
@@ -305,7 +338,7 @@ __device__ __forceinline__ void trav_advance(const DeviceScene& sc, const Ray& r
         if (trav_needs_maintenance(sc, T)) trav_maintain(sc, T, stack);
     }
 #endif
-    if (has_node) trav_node_part(sc, r, T, stack, N);
+    if (has_node) trav_node_part(sc, r, sg, T, stack, N);
     if (has_tri) ++T.tri_i;
     trav_settle(sc, T, stack);
     if (COUNT) {   // counting instantiation only: how coherent is this wave's node request?  lanes that take part, distinct 64-B records among them
@@ -344,6 +377,7 @@ __device__ __forceinline__ int trav_run(const DeviceScene& sc, const Ray& r, Tra
     NodeRegs N;
     TriRegs X, Y;
     int steps = 0;
+    const RaySigns sg = ray_signs(r);
     trav_settle(sc, T, stack);
     trav_issue(sc, T, N, X);
     // The loop is wave-uniform (lanes whose ray is finished idle along): a per-lane exit would make the compiler carry
@@ -351,10 +385,10 @@ __device__ __forceinline__ int trav_run(const DeviceScene& sc, const Ray& r, Tra
     while (true) {
         if (__ballot(trav_busy(T)) == 0ull) break;
         trav_wait(N, X);
-        if (trav_busy(T)) { trav_advance<ANY, IGN>(sc, r, T, stack, N, X, Y, ignore_object); ++steps; }
+        if (trav_busy(T)) { trav_advance<ANY, IGN>(sc, r, sg, T, stack, N, X, Y, ignore_object); ++steps; }
         if (__ballot(trav_busy(T)) == 0ull) break;
         trav_wait(N, Y);
-        if (trav_busy(T)) { trav_advance<ANY, IGN>(sc, r, T, stack, N, Y, X, ignore_object); ++steps; }
+        if (trav_busy(T)) { trav_advance<ANY, IGN>(sc, r, sg, T, stack, N, Y, X, ignore_object); ++steps; }
     }
     trav_drain(N, X, Y);
     return steps;
@@ -439,6 +473,7 @@ __device__ __forceinline__ bool trav_shared(const DeviceScene& sc, bool has_ray,
     unsigned owner = tid;   // block-local lane whose ray this lane is working on
     uint32_t wign = ignore;
     Ray wr = own;
+    RaySigns sg = ray_signs(wr);   // of the rays the lanes work on: made again below when lanes have taken others
     trav_init(T, tmax, has_ray && sc.num_nodes > 0);
     trav_deep_reset(sc, stack);
     // The records of the NEXT step are requested as soon as this step has decided what they are: behind the node part
@@ -466,7 +501,7 @@ __device__ __forceinline__ bool trav_shared(const DeviceScene& sc, bool has_ray,
         }
 #endif
         if (trav_busy(T)) {
-            trav_advance<ANY, IGN, COUNT>(sc, wr, T, stack, N, cur, nxt, wign);
+            trav_advance<ANY, IGN, COUNT>(sc, wr, sg, T, stack, N, cur, nxt, wign);
             if (ANY) {
                 if (T.leaf_index >= 0) { A.blocked[owner] = 1; T.leaf_index = -1; }   // first hit ends the query (T is idle now)
                 else if (A.blocked[owner]) { T.cur = kDone; T.sp = 0; T.sb = 0; T.tri_i = 0; T.tri_n = 0; }   // settled by another lane
@@ -516,12 +551,13 @@ __device__ __forceinline__ bool trav_shared(const DeviceScene& sc, bool has_ray,
                     }
                     if (IGN) wign = A.rign[owner];
                     T.cur = e; T.sp = 0; T.sb = 0; T.tri_i = 0; T.tri_n = 0;
-                    T.t = bound; T.leaf_index = -1; T.id = 0xFFFFFFFFu;
+                    T.t = canonical_bound(bound); T.leaf_index = -1; T.id = 0xFFFFFFFFu;
                     trav_deep_reset(sc, stack);   // (an any-hit query that ended early may have left entries there)
                     trav_settle(sc, T, stack);
                     trav_issue(sc, T, N, nxt);
                 }
             }
+            sg = ray_signs(wr);   // (n >= 1 here: some lane has taken a ray; every lane of the wave is back at this point)
         }
         return false;
     };

@@ -121,6 +121,9 @@ constexpr int kHistWindow = 256;
 constexpr int kUnboundedDepth = 1 << 24;   // the weights' depth cap when the walk has none: every strategy exists
 constexpr int kOverLevels = 448;            // second-tier walk steps of depth = 0 frames (64 + 448 = 512 steps)
 
+// The traversal addresses `nodes` and `tris` by a scalar base and a 32-bit byte offset per lane (fs_dev_trav.hpp:
+// trav_issue): num_nodes * sizeof(NodeQ4) and num_tris * sizeof(Tri48) fit 32 bits in every view — a larger scene is
+// refused at commit (fs_capi_scene.cpp: finish_commit).
 struct DeviceScene {
     const NodeQ4* nodes;
     const Tri48* tris;        // traversal records, leaf order
