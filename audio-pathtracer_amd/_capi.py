@@ -58,6 +58,7 @@ EXPORTS = [
     "fs_reflection_params_default", "fs_update_reflection_paths",
     "fs_diffraction_params_default", "fs_update_diffraction_paths",
     "fs_reflection2_params_default", "fs_update_reflection2_paths",
+    "fs_diffraction2_params_default", "fs_update_diffraction2_paths",
     "fs_direct_band_kernels", "fs_direct_render_init", "fs_direct_render_release", "fs_direct_render_process_batch",
     "fs_reflection_render_init", "fs_reflection_render_release", "fs_reflection_render_process_batch",
 ]
@@ -89,6 +90,13 @@ MAX_REFLECTION2_BATCH = 256
 REFLECTION2_OVERFLOW = 1
 REFLECTION2_NEAR_OVERFLOW = 2
 REFLECTION2_VOICE_TAG = 0x40000000   # a second-order voice's key: 0x40000000 | (((a * 2654435761 + b) mod 2^32) >> 2)
+MAX_DIFFRACTION2_PATHS = 16
+MAX_DIFFRACTION2_NEAR = 32768
+MAX_DIFFRACTION2_CANDIDATES = 2048
+MAX_DIFFRACTION2_BATCH = 256
+DIFFRACTION2_OVERFLOW = 1
+DIFFRACTION2_NEAR_OVERFLOW = 2
+DIFFRACTION2_VOICE_TAG = 0x20000000   # a second-order diffraction voice's key: 0x20000000 | (((kp * 2654435761 + kq) mod 2^32) >> 3), k = 4 triangle + edge
 DIRECT_RENDER_MAX_TAPS = 2047
 MAX_REFLECTION_VOICES = 32
 MAX_REFLECTION_RENDER_BATCH = 256
@@ -354,6 +362,47 @@ class Reflection2Row(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("near", "candidates", "found", "returned", "flags")]
 
 
+class Diffraction2Params(C.Structure):
+    """fs_diffraction2_params (include/frequensee.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("max_paths", C.c_int32),
+        ("max_near", C.c_int32),
+        ("max_candidates", C.c_int32),
+        ("margin", C.c_float),
+        ("max_detour", C.c_float),
+        ("min_parallel", C.c_float),
+        ("offset", C.c_float),
+        ("merge", C.c_float),
+        ("step", C.c_float),
+        ("pullback", C.c_float),
+        ("dist_divisor", C.c_float),
+        ("sound_speed", C.c_float),
+    ]
+
+
+class Diffraction2Path(C.Structure):
+    """fs_diffraction2_path (include/frequensee.h): one path round two edges of one source, an array element (no struct_size)"""
+    _fields_ = [
+        ("length", C.c_float),
+        ("delay", C.c_float),
+        ("detour", C.c_float),
+        ("gap", C.c_float),
+        ("cos_bend", C.c_float * 2),
+        ("apex", (C.c_float * 3) * 2),
+        ("direction", C.c_float * 3),
+        ("triangle", C.c_uint32 * 2),
+        ("edge", C.c_uint32 * 2),
+        ("material", C.c_uint32 * 2),
+        ("gain", C.c_float * MAX_BANDS),
+    ]
+
+
+class Diffraction2Row(C.Structure):
+    """fs_diffraction2_row (include/frequensee.h): one source's counts, an array element (no struct_size)"""
+    _fields_ = [(k, C.c_uint32) for k in ("near", "candidates", "confirmed", "found", "returned", "flags")]
+
+
 class DirectRenderTarget(C.Structure):
     """fs_direct_render_target (include/frequensee.h): one source's target of a callback, an array element (no struct_size)"""
     _fields_ = [
@@ -492,6 +541,8 @@ def load():
         "fs_update_diffraction_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(DiffractionParams), C.c_void_p, C.c_void_p]),
         "fs_reflection2_params_default": (None, [C.POINTER(Reflection2Params)]),
         "fs_update_reflection2_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(Reflection2Params), C.c_void_p, C.c_void_p]),
+        "fs_diffraction2_params_default": (None, [C.POINTER(Diffraction2Params)]),
+        "fs_update_diffraction2_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(Diffraction2Params), C.c_void_p, C.c_void_p]),
         "fs_direct_band_kernels": (C.c_int, [i32, f32p, i32, i32, f32p]),
         "fs_direct_render_init": (C.c_int, [vp, i32, i32, i32, C.c_float]),
         "fs_direct_render_release": (C.c_int, [vp, i32]),
@@ -553,6 +604,14 @@ def default_diffraction_params(**kw) -> DiffractionParams:
 def default_reflection2_params(**kw) -> Reflection2Params:
     p = Reflection2Params()
     load().fs_reflection2_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_diffraction2_params(**kw) -> Diffraction2Params:
+    p = Diffraction2Params()
+    load().fs_diffraction2_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -447,6 +447,29 @@ class Context:
                                                         rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
         return rows, paths
 
+    # ---- second-order diffraction paths: the diffraction round thick obstacles of every source of a tick ----
+    DIFFRACTION2_ROW_DTYPE = np.dtype([("near", np.uint32), ("candidates", np.uint32), ("confirmed", np.uint32), ("found", np.uint32),
+                                       ("returned", np.uint32), ("flags", np.uint32)])
+    DIFFRACTION2_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("detour", np.float32), ("gap", np.float32),
+                                   ("cos_bend", np.float32, (2,)), ("apex", np.float32, (2, 3)), ("direction", np.float32, (3,)),
+                                   ("triangle", np.uint32, (2,)), ("edge", np.uint32, (2,)), ("material", np.uint32, (2,)),
+                                   ("gain", np.float32, (_capi.MAX_BANDS,))])
+
+    def diffraction2_paths(self, sources, **params):
+        """fs_update_diffraction2_paths: (rows [count], paths [count][max_paths]) as structured arrays — per listed source the counts
+        (near, candidates, confirmed, found, returned, flags) and its `returned` shortest paths listener -> E0 -> E1 -> source round
+        two parallel edges (length cm, delay s, detour cm, gap cm, cos_bend [2], apex [E0, E1], direction from the listener,
+        triangle [2], edge [2], material [2], gain [8]; index 0 is the listener's end; entries beyond `returned` are zero);
+        params = the fields of fs_diffraction2_params (max_paths, max_near, max_candidates, margin, max_detour, min_parallel, offset,
+        merge, step, pullback, dist_divisor, sound_speed)"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        p = _capi.default_diffraction2_params(**params)
+        rows = np.zeros(srcs.shape[0], dtype=self.DIFFRACTION2_ROW_DTYPE)
+        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=self.DIFFRACTION2_DTYPE)
+        self.check(self.lib.fs_update_diffraction2_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
+                                                         rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
+        return rows, paths
+
     # ---- direct sound on the audio thread: fractional delay + band FIR for all sources of a callback ----
     RENDER_TARGET_DTYPE = np.dtype([("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,))])
 
@@ -912,6 +935,17 @@ class AudioRayTracingSubsystem:
         parts = [self.ctx.reflection2_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
         return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
 
+    def UpdateDiffraction2Paths(self, **params):
+        """the diffraction round thick obstacles of all active sources: (rows, paths), row i and paths[i] for ActiveSources[i]
+        (Context.diffraction2_paths; more than 256 sources take one call per 256)"""
+        srcs = [s._src for s in self.ActiveSources]
+        if not srcs:
+            return np.zeros(0, dtype=Context.DIFFRACTION2_ROW_DTYPE), np.zeros((0, 0), dtype=Context.DIFFRACTION2_DTYPE)
+        self._commit()
+        step = _capi.MAX_DIFFRACTION2_BATCH
+        parts = [self.ctx.diffraction2_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
+        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
+
     def SetPipelining(self, depth):
         """fs_set_pipelining: Tick then updates the sources one after the other like the reference's loop (ARTS.cpp:60-68),
         streamed — every call launches one kernel that plans this source's frame, walks the previous source's and
@@ -1052,7 +1086,14 @@ class FrequenSeeAudioReflectionPlugin:
         h = (a * 2654435761 + b) mod 2^32 — no first-order key (a triangle below 2^29), no diffraction key (0x80000000 | ...)"""
         return _capi.REFLECTION2_VOICE_TAG | (((int(a) * 2654435761 + int(b)) & 0xFFFFFFFF) >> 2)
 
-    def Voices(self, row, paths, right=None, reference_length=None, diffraction=None, second=None):
+    @staticmethod
+    def Diffraction2Key(triangle, edge):
+        """the key of the voice of a path round the edge records (triangle[0], edge[0]) and (triangle[1], edge[1]):
+        0x20000000 | (h >> 3) with h = ((4 i_p + j_p) * 2654435761 + (4 i_q + j_q)) mod 2^32 — the one range no other kind uses"""
+        kp, kq = 4 * int(triangle[0]) + int(edge[0]), 4 * int(triangle[1]) + int(edge[1])
+        return _capi.DIFFRACTION2_VOICE_TAG | (((kp * 2654435761 + kq) & 0xFFFFFFFF) >> 3)
+
+    def Voices(self, row, paths, right=None, reference_length=None, diffraction=None, second=None, diffraction2=None):
         """one source's entries from its UpdateReflectionPaths result (row: its counts, paths: its path array), over the first
         row["returned"] paths: key = triangle, band_gain = reflectance, delay = the path's arrival time less the filter's own
         latency of (Taps - 1) / 2 samples, not below 0.  channel_gain = (1, 1); with `right` (the listener's unit right vector) the
@@ -1063,23 +1104,27 @@ class FrequenSeeAudioReflectionPlugin:
         paths) of the same source from UpdateReflection2Paths appends one voice per returned second-order path — band_gain =
         reflectance, delay, pan and distance law as above, key = SecondOrderKey(triangle[0], triangle[1]).  Two second-order paths
         of the row whose keys collide: the earlier in the row — the shorter, ties by (a, b) — is kept and the other dropped (the
-        renderer refuses duplicate keys)."""
+        renderer refuses duplicate keys).  diffraction2 = (row, paths) of the same source from UpdateDiffraction2Paths appends, last,
+        one voice per returned path round two edges — band_gain = gain, key = Diffraction2Key(triangle, edge); on colliding keys
+        the earlier in the row is kept likewise."""
         n = int(row["returned"])
         m = 0 if diffraction is None else int(diffraction[0]["returned"])
         k = 0 if second is None else int(second[0]["returned"])
-        tagged = diffraction is not None or second is not None
-        v = np.zeros(n + m + k, dtype=Context.REFLECTION_VOICE_DTYPE)
+        k2 = 0 if diffraction2 is None else int(diffraction2[0]["returned"])
+        tagged = diffraction is not None or second is not None or diffraction2 is not None
+        v = np.zeros(n + m + k + k2, dtype=Context.REFLECTION_VOICE_DTYPE)
         latency = ((self.Taps - 1) // 2) / float(self.ctx.cfg.sample_rate)
         r = None if right is None else np.asarray(right, np.float64).reshape(3)
         seen, kept = set(), 0
-        for i in range(n + m + k):
-            p = paths[i] if i < n else (diffraction[1][i - n] if i < n + m else second[1][i - n - m])
+        for i in range(n + m + k + k2):
+            p = paths[i] if i < n else (diffraction[1][i - n] if i < n + m else (second[1][i - n - m] if i < n + m + k else
+                                                                                 diffraction2[1][i - n - m - k]))
             if i < n + m:
                 if tagged and int(p["triangle"]) >= _capi.REFLECTION2_VOICE_TAG >> 1:
                     raise ValueError("Voices: triangle index 2^29 or above: the keys of the path kinds would collide")
                 key = int(p["triangle"]) if i < n else _capi.DIFFRACTION_VOICE_TAG | (int(p["triangle"]) * 4 + int(p["edge"]))
             else:
-                key = self.SecondOrderKey(p["triangle"][0], p["triangle"][1])
+                key = self.SecondOrderKey(p["triangle"][0], p["triangle"][1]) if i < n + m + k else self.Diffraction2Key(p["triangle"], p["edge"])
                 if key in seen:
                     continue
                 seen.add(key)
@@ -1087,7 +1132,7 @@ class FrequenSeeAudioReflectionPlugin:
             kept += 1
             o["key"] = key
             o["delay"] = max(float(p["delay"]) - latency, 0.0)
-            o["band_gain"] = p["gain"] if n <= i < n + m else p["reflectance"]
+            o["band_gain"] = p["gain"] if n <= i < n + m or i >= n + m + k else p["reflectance"]
             left_right = np.ones(2, np.float64)
             if r is not None:
                 t = (float(np.dot(np.asarray(p["direction"], np.float64), r)) + 1.0) * np.pi / 4.0
@@ -1098,13 +1143,15 @@ class FrequenSeeAudioReflectionPlugin:
         return v[:kept]
 
     def ProcessAudio(self, components, buffers, rows, paths, right=None, reference_length=None, want_out=True, want_mix=False,
-                     diffraction=None, second=None):
+                     diffraction=None, second=None, diffraction2=None):
         """buffers[i] is components[i]'s block, rows[i] / paths[i] its results of UpdateReflectionPaths; diffraction = the (rows,
-        paths) of UpdateDiffractionPaths, second = the (rows, paths) of UpdateReflection2Paths, or None.  Returns what
+        paths) of UpdateDiffractionPaths, second = the (rows, paths) of UpdateReflection2Paths, diffraction2 = the (rows, paths) of
+        UpdateDiffraction2Paths, or None.  Returns what
         Context.reflection_render_process_batch does."""
         voices = [self.Voices(rows[i], paths[i], right, reference_length,
                               None if diffraction is None else (diffraction[0][i], diffraction[1][i]),
-                              None if second is None else (second[0][i], second[1][i])) for i in range(len(components))]
+                              None if second is None else (second[0][i], second[1][i]),
+                              None if diffraction2 is None else (diffraction2[0][i], diffraction2[1][i])) for i in range(len(components))]
         return self.ctx.reflection_render_process_batch([c._src for c in components], buffers, voices,
                                                         want_out=want_out, want_mix=want_mix)
 

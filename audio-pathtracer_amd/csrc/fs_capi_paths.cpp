@@ -1,7 +1,7 @@
 // fs_capi_paths.cpp — the path queries of a tick, each one call for all its sources: fs_update_direct_paths (fs_direct.hip) with the
-// sample offsets it uses, fs_update_reflection_paths (fs_reflect.hip), fs_update_diffraction_paths (fs_diffract.hip) and
-// fs_update_reflection2_paths (fs_reflect2.hip), their defaults, and what the four share on the host: the prologue, the staging, the
-// packing of the sources and the copy back.
+// sample offsets it uses, fs_update_reflection_paths (fs_reflect.hip), fs_update_diffraction_paths (fs_diffract.hip),
+// fs_update_reflection2_paths (fs_reflect2.hip) and fs_update_diffraction2_paths (fs_diffract2.hip), their defaults, and what the
+// five share on the host: the prologue, the staging, the packing of the sources and the copy back.
 #include "fs_context.hpp"
 
 static_assert(sizeof(fs_direct_params) == 32, "fs_direct_params: eight words");
@@ -15,6 +15,14 @@ static_assert(sizeof(fs_diffraction_row) == 20, "fs_diffraction_row: five words"
 static_assert(sizeof(fs_reflection2_params) == 44, "fs_reflection2_params: eleven words");
 static_assert(sizeof(fs_reflection2_path) == 92, "fs_reflection2_path: fifteen words and the bands");
 static_assert(sizeof(fs_reflection2_row) == 20, "fs_reflection2_row: five words");
+static_assert(sizeof(fs_diffraction2_params) == 52, "fs_diffraction2_params: thirteen words");
+static_assert(sizeof(fs_diffraction2_path) == 116, "fs_diffraction2_path: twenty-one words and the bands");
+static_assert(offsetof(fs_diffraction2_path, detour) == 8 && offsetof(fs_diffraction2_path, gap) == 12 && offsetof(fs_diffraction2_path, cos_bend) == 16 &&
+                  offsetof(fs_diffraction2_path, apex) == 24 && offsetof(fs_diffraction2_path, direction) == 48 &&
+                  offsetof(fs_diffraction2_path, triangle) == 60 && offsetof(fs_diffraction2_path, edge) == 68 &&
+                  offsetof(fs_diffraction2_path, material) == 76 && offsetof(fs_diffraction2_path, gain) == 84,
+              "fs_diffraction2_path: the offsets of include/frequensee.h");
+static_assert(sizeof(fs_diffraction2_row) == 24, "fs_diffraction2_row: six words");
 
 int PathStaging::grow(fs_context* ctx, int count, size_t pinned_bytes_per_row, size_t device_bytes_per_row) {
     if (count <= cap) return FS_OK;
@@ -95,6 +103,14 @@ void band_centres(const std::vector<double>& given, int B, double* f) {
         const double lo = b == 0 ? e[0] / 2.0 : e[(size_t)b - 1], hi = b == B - 1 ? e[(size_t)B - 2] * 2.0 : e[(size_t)b];
         f[b] = std::sqrt(lo * hi);
     }
+}
+
+// ctx->diffract_f = the band centres of the edges in force: once per (context, edges in force)
+void refresh_band_centres(fs_context* ctx) {
+    if (ctx->diffract_f_edges == ctx->band_edges && ctx->diffract_f_bands == ctx->cfg.num_bands) return;
+    band_centres(ctx->band_edges, ctx->cfg.num_bands, ctx->diffract_f);
+    ctx->diffract_f_edges = ctx->band_edges;
+    ctx->diffract_f_bands = ctx->cfg.num_bands;
 }
 
 }  // namespace
@@ -266,11 +282,7 @@ int fs_update_diffraction_paths(fs_context* ctx, const fs_source* sources, int32
     PathStaging& st = ctx->diffract_stage;
     { int gr = st.grow(ctx, count, sizeof(float4) + kOutPerRow,
                        sizeof(float4) + sizeof(DiffractRecord) * kCand + sizeof(uint32_t) * (1 + kCand) + kOutPerRow); if (gr) return gr; }
-    if (ctx->diffract_f_edges != ctx->band_edges || ctx->diffract_f_bands != ctx->cfg.num_bands) {   // once per (context, edges in force)
-        band_centres(ctx->band_edges, ctx->cfg.num_bands, ctx->diffract_f);
-        ctx->diffract_f_edges = ctx->band_edges;
-        ctx->diffract_f_bands = ctx->cfg.num_bands;
-    }
+    refresh_band_centres(ctx);
     const size_t cap = (size_t)st.cap;
     float4* h_src = reinterpret_cast<float4*>(st.h);
     char* h_out = st.h + cap * sizeof(float4);
@@ -370,6 +382,86 @@ int fs_update_reflection2_paths(fs_context* ctx, const fs_source* sources, int32
     launch_reflection2_paths(ctx->scene, rp, ctx->stream);
     FS_HIP(ctx, hipGetLastError());
     return copy_back_rows_paths(ctx, h_out, d_out, rows_bytes, sizeof(fs_reflection2_path) * (size_t)count * (size_t)p->max_paths, rows, paths);
+}
+
+// ---- second-order diffraction paths -----------------------------------------------------------------------------------------
+void fs_diffraction2_params_default(fs_diffraction2_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = sizeof(fs_diffraction2_params);
+    p->max_paths = 4;
+    p->max_near = 16384;
+    p->max_candidates = 1024;
+    p->margin = 1e-3f;
+    p->max_detour = 250.f;    // (at the first-order call's 1000 every old_mine row overflows max_near: DESIGN.md "Second-order diffraction paths")
+    p->min_parallel = 0.999f;
+    p->offset = 0.1f;
+    p->merge = 1.0f;
+    p->step = 0.1f;
+    p->pullback = 0.1f;
+    p->dist_divisor = 1000.f;
+    p->sound_speed = 343.f;
+}
+
+int fs_update_diffraction2_paths(fs_context* ctx, const fs_source* sources, int32_t count, const fs_diffraction2_params* p,
+                                 fs_diffraction2_row* rows, fs_diffraction2_path* paths) {
+    if (!ctx || !sources || !rows || !paths) return FS_ERR_INVALID_ARGUMENT;
+    if (count < 1 || count > FS_MAX_DIFFRACTION2_BATCH) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_DIFFRACTION2_BATCH)");
+    fs_diffraction2_params def;
+    if (!p) { fs_diffraction2_params_default(&def); p = &def; }
+    if (p->struct_size != sizeof(fs_diffraction2_params)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_diffraction2_params.struct_size mismatch");
+    if (p->max_paths < 1 || p->max_paths > FS_MAX_DIFFRACTION2_PATHS || p->max_near < 1 || p->max_near > FS_MAX_DIFFRACTION2_NEAR ||
+        p->max_candidates < 1 || p->max_candidates > FS_MAX_DIFFRACTION2_CANDIDATES || !finite_at_least_zero(p->margin) ||
+        !finite_above_zero(p->max_detour) || !finite_above_zero(p->min_parallel) || p->min_parallel > 1.0f || !finite_at_least_zero(p->offset) ||
+        !finite_at_least_zero(p->merge) || !finite_at_least_zero(p->step) || !finite_at_least_zero(p->pullback) ||
+        !finite_above_zero(p->dist_divisor) || !finite_above_zero(p->sound_speed))
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad second-order diffraction-path params");
+    { int pr = paths_prologue(ctx, sources, count); if (pr) return pr; }
+    constexpr size_t kNear = FS_MAX_DIFFRACTION2_NEAR, kCand = FS_MAX_DIFFRACTION2_CANDIDATES;
+    constexpr size_t kOutPerRow = sizeof(fs_diffraction2_row) + FS_MAX_DIFFRACTION2_PATHS * sizeof(fs_diffraction2_path);
+    PathStaging& st = ctx->diffract2_stage;
+    { int gr = st.grow(ctx, count, sizeof(float4) + kOutPerRow,
+                       sizeof(float4) + sizeof(uint32_t) * (2 + kNear + kCand) + sizeof(Diffract2Record) * kCand + kOutPerRow); if (gr) return gr; }
+    refresh_band_centres(ctx);
+    const size_t cap = (size_t)st.cap;
+    float4* h_src = reinterpret_cast<float4*>(st.h);
+    char* h_out = st.h + cap * sizeof(float4);
+    float4* d_src = reinterpret_cast<float4*>(st.d);
+    uint32_t* d_near_counters = reinterpret_cast<uint32_t*>(st.d + cap * sizeof(float4));
+    uint32_t* d_counters = d_near_counters + cap;
+    uint32_t* d_near = d_counters + cap;
+    uint32_t* d_cand = d_near + cap * kNear;
+    Diffract2Record* d_conf = reinterpret_cast<Diffract2Record*>(d_cand + cap * kCand);
+    char* d_out = reinterpret_cast<char*>(d_conf + cap * kCand);
+    const size_t rows_bytes = sizeof(fs_diffraction2_row) * (size_t)count;
+    pack_sources(ctx, sources, count, h_src);
+    Diffract2KParams dp{};
+    dp.h = path_head(ctx, d_src, count, p->step, p->pullback, p->dist_divisor, p->sound_speed);
+    dp.near_counters = d_near_counters;
+    dp.counters = d_counters;
+    dp.near = d_near;
+    dp.cand = d_cand;
+    dp.conf = d_conf;
+    dp.rows = reinterpret_cast<fs_diffraction2_row*>(d_out);
+    dp.paths = reinterpret_cast<fs_diffraction2_path*>(d_out + rows_bytes);
+    dp.max_paths = p->max_paths;
+    dp.max_near = p->max_near;
+    dp.max_candidates = p->max_candidates;
+    dp.margin = p->margin;
+    dp.max_detour = p->max_detour;
+    dp.min_parallel = p->min_parallel;
+    dp.offset = p->offset;
+    dp.merge = p->merge;
+    // k_b and lam5_b travel with the launch's arguments: sixteen words, no table on the device
+    for (int b = 0; b < ctx->cfg.num_bands; ++b) {
+        dp.k[b] = (float)(40.0 * ctx->diffract_f[b] / ((double)p->sound_speed * (double)p->dist_divisor));
+        dp.lam5[b] = (float)(5.0 * (double)p->sound_speed * (double)p->dist_divisor / ctx->diffract_f[b]);
+    }
+    FS_HIP(ctx, hipMemcpyAsync(d_src, h_src, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(ctx, hipMemsetAsync(d_near_counters, 0, sizeof(uint32_t) * 2 * cap, ctx->stream));   // both counter arrays: they lie side by side
+    launch_diffraction2_paths(ctx->scene, dp, ctx->stream);
+    FS_HIP(ctx, hipGetLastError());
+    return copy_back_rows_paths(ctx, h_out, d_out, rows_bytes, sizeof(fs_diffraction2_path) * (size_t)count * (size_t)p->max_paths, rows, paths);
 }
 
 }  // extern "C"

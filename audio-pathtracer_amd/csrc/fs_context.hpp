@@ -326,7 +326,8 @@ struct fs_context {
     // reflect2_stage — pinned: as reflect_stage; device: sources [cap] float4 | near counters [cap] | candidate counters [cap] | near
     // lists [cap][FS_MAX_REFLECTION2_NEAR] | candidates [cap][FS_MAX_REFLECTION2_CANDIDATES] | confirmed records
     // [cap][FS_MAX_REFLECTION2_CANDIDATES] | rows and paths.
-    PathStaging direct_stage, reflect_stage, diffract_stage, reflect2_stage;
+    // diffract2_stage — as reflect2_stage with the FS_MAX_DIFFRACTION2_* sizes; it shares diffract_f.
+    PathStaging direct_stage, reflect_stage, diffract_stage, reflect2_stage, diffract2_stage;
     float* d_direct_off = nullptr;
     uint64_t direct_off_have = 0;
     double diffract_f[FS_MAX_BANDS] = {};

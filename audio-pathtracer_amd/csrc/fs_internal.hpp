@@ -497,6 +497,35 @@ struct Reflect2KParams {
     float max_length, margin, offset;
 };
 void launch_reflection2_paths(const DeviceScene& sc, const Reflect2KParams& rp, hipStream_t s);
+// fs_diffract2.hip (fs_update_diffraction2_paths): diffract2_near_kernel, a thread per triangle record against every row of the call,
+// appends (leaf position * 4 + edge) of the near edge records to the rows' near lists; diffract2_pair_kernel tests every ordered
+// pair (q, p) of a row's near list and appends the survivors, as two near-list slots packed 15 + 15 bits (q high), to the rows'
+// candidate lists; diffract2_confirm_kernel, a wave per row, runs the five legs of every candidate, compacts the confirmed ones into
+// `conf`, merges, ranks and writes the row and its paths.  The arrays as Reflect2KParams.
+struct Diffract2Record {
+    uint32_t length_bits, kp, kq;   // kp, kq = input index * 4 + edge of the listener's and the source's edge record
+    float apex[2][3], direction[3];
+    float detour, gap, cos_bend[2];
+    uint32_t material[2];
+    uint32_t kept;
+};
+static_assert(sizeof(Diffract2Record) == 76, "Diffract2Record: nineteen words");
+static_assert(FS_MAX_DIFFRACTION2_NEAR <= 1 << 15, "a candidate is two near-list slots of 15 bits");
+struct Diffract2KParams {
+    PathKHead h;
+    uint32_t* near_counters;
+    uint32_t* counters;
+    uint32_t* near;
+    uint32_t* cand;
+    Diffract2Record* conf;
+    fs_diffraction2_row* rows;
+    fs_diffraction2_path* paths;
+    int32_t max_paths, max_near, max_candidates;
+    float margin, max_detour, min_parallel, offset, merge;
+    float k[FS_MAX_BANDS];      // k_b = 40 f_b / (sound_speed dist_divisor)
+    float lam5[FS_MAX_BANDS];   // lam5_b = 5 sound_speed dist_divisor / f_b
+};
+void launch_diffraction2_paths(const DeviceScene& sc, const Diffract2KParams& dp, hipStream_t s);
 constexpr int kReverbRing = 65536;   // per-channel history ring (floats), matches kRevRing in the kernels
 // fs_reverb.hip (the reverb callback): one descriptor per row of the call, in list order, read by every kernel of the callback.
 struct ReverbItem {

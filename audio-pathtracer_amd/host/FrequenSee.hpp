@@ -254,6 +254,25 @@ public:
                                               Out.Rows.data() + i, Out.Paths.data() + i * (size_t)Out.MaxPaths));
         return Out;
     }
+    // the diffraction round thick obstacles of every active source: Rows[i] and Paths[i * MaxPaths .. ) for ActiveSources[i]
+    // (fs_update_diffraction2_paths; MaxPaths = P->max_paths, the default's without P; one call per FS_MAX_DIFFRACTION2_BATCH sources)
+    struct Diffraction2Paths { int32_t MaxPaths = 0; std::vector<fs_diffraction2_row> Rows; std::vector<fs_diffraction2_path> Paths; };
+    Diffraction2Paths UpdateDiffraction2Paths(const fs_diffraction2_params* P = nullptr) {
+        fs_diffraction2_params Def;
+        fs_diffraction2_params_default(&Def);
+        Diffraction2Paths Out;
+        Out.MaxPaths = P ? P->max_paths : Def.max_paths;
+        if (ActiveSources.empty()) return Out;
+        Out.Rows.resize(ActiveSources.size());
+        Out.Paths.resize(ActiveSources.size() * (size_t)std::min(std::max(Out.MaxPaths, 1), FS_MAX_DIFFRACTION2_PATHS));   // (a bad max_paths is refused below)
+        Commit();
+        std::vector<fs_source> H;
+        for (auto* s : ActiveSources) H.push_back(s->Handle_);
+        for (size_t i = 0; i < H.size(); i += FS_MAX_DIFFRACTION2_BATCH)
+            Check(fs_update_diffraction2_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_DIFFRACTION2_BATCH), P,
+                                               Out.Rows.data() + i, Out.Paths.data() + i * (size_t)Out.MaxPaths));
+        return Out;
+    }
     // fs_set_pipelining (0 off, 1, 2): Tick streams the sources instead of batching them
     void SetPipelining(int Depth) { Check(fs_set_pipelining(Ctx_, Depth)); Streamed_ = Depth != 0; }
     // fs_set_frames_per_launch (1 .. 4): consecutive streamed frames share a launch (each keeps its seed, buffer and IR)
@@ -501,28 +520,37 @@ public:
     // scene has fewer than 2^29 triangles; an index beyond that is refused.  SRow / SPaths (the same source's row and paths of
     // fs_update_reflection2_paths) append one voice per returned second-order path: band_gain = reflectance, delay, pan and distance
     // law as above, key = SecondOrderKey(a, b).  Two second-order paths of the row whose keys collide: the earlier in the row — the
-    // shorter, ties by (a, b) — is kept and the other dropped (the renderer refuses duplicate keys)
+    // shorter, ties by (a, b) — is kept and the other dropped (the renderer refuses duplicate keys).  TRow / TPaths (the same
+    // source's row and paths of fs_update_diffraction2_paths) append, last, one voice per returned path round two edges: band_gain =
+    // gain, key = Diffraction2Key(triangle, edge); on colliding keys the earlier in the row is kept likewise
     static uint32_t SecondOrderKey(uint32_t A, uint32_t B) { return 0x40000000u | ((A * 2654435761u + B) >> 2); }
+    static uint32_t Diffraction2Key(const uint32_t (&Triangle)[2], const uint32_t (&Edge)[2]) {
+        return 0x20000000u | (((4u * Triangle[0] + Edge[0]) * 2654435761u + (4u * Triangle[1] + Edge[1])) >> 3);
+    }
     std::vector<fs_reflection_voice> Voices(const fs_reflection_row& Row, const fs_reflection_path* Paths, const FVector* Right = nullptr,
                                             float ReferenceLength = 0.0f, const fs_diffraction_row* DRow = nullptr,
                                             const fs_diffraction_path* DPaths = nullptr, const fs_reflection2_row* SRow = nullptr,
-                                            const fs_reflection2_path* SPaths = nullptr) const {
+                                            const fs_reflection2_path* SPaths = nullptr, const fs_diffraction2_row* TRow = nullptr,
+                                            const fs_diffraction2_path* TPaths = nullptr) const {
         const size_t NR = (size_t)Row.returned, ND = DRow && DPaths ? (size_t)DRow->returned : 0, NS = SRow && SPaths ? (size_t)SRow->returned : 0;
+        const size_t NT = TRow && TPaths ? (size_t)TRow->returned : 0;
         std::vector<fs_reflection_voice> V;
-        V.reserve(NR + ND + NS);
+        V.reserve(NR + ND + NS + NT);
         const double Latency = (double)((Taps - 1) / 2) / (double)SampleRate;
-        for (size_t i = 0; i < NR + ND + NS; ++i) {
-            const bool Refl = i < NR, Second = i >= NR + ND;
+        for (size_t i = 0; i < NR + ND + NS + NT; ++i) {
+            const bool Refl = i < NR, Second = i >= NR + ND && i < NR + ND + NS, Thick = i >= NR + ND + NS;
             const fs_reflection2_path* S = Second ? SPaths + (i - NR - ND) : nullptr;
-            const uint32_t Tri = Refl ? Paths[i].triangle : (Second ? 0u : DPaths[i - NR].triangle);
-            if ((ND || (SRow && SPaths)) && Tri >= (0x80000000u >> 2))
+            const fs_diffraction2_path* T = Thick ? TPaths + (i - NR - ND - NS) : nullptr;
+            const uint32_t Tri = Refl ? Paths[i].triangle : (Second || Thick ? 0u : DPaths[i - NR].triangle);
+            if ((ND || (SRow && SPaths) || (TRow && TPaths)) && Tri >= (0x80000000u >> 2))
                 throw std::runtime_error("FrequenSee: triangle index 2^29 or above: the keys of the path kinds would collide");
-            const float* Dir = Refl ? Paths[i].direction : (Second ? S->direction : DPaths[i - NR].direction);
-            const float* Gain = Refl ? Paths[i].reflectance : (Second ? S->reflectance : DPaths[i - NR].gain);
-            const float Delay = Refl ? Paths[i].delay : (Second ? S->delay : DPaths[i - NR].delay);
-            const float Length = Refl ? Paths[i].length : (Second ? S->length : DPaths[i - NR].length);
-            const uint32_t Key = Refl ? Tri : (Second ? SecondOrderKey(S->triangle[0], S->triangle[1]) : (0x80000000u | (Tri * 4u + DPaths[i - NR].edge)));
-            if (Second && std::any_of(V.begin() + (std::ptrdiff_t)(NR + ND), V.end(), [&](const fs_reflection_voice& X) { return X.key == Key; })) continue;
+            const float* Dir = Refl ? Paths[i].direction : (Second ? S->direction : (Thick ? T->direction : DPaths[i - NR].direction));
+            const float* Gain = Refl ? Paths[i].reflectance : (Second ? S->reflectance : (Thick ? T->gain : DPaths[i - NR].gain));
+            const float Delay = Refl ? Paths[i].delay : (Second ? S->delay : (Thick ? T->delay : DPaths[i - NR].delay));
+            const float Length = Refl ? Paths[i].length : (Second ? S->length : (Thick ? T->length : DPaths[i - NR].length));
+            const uint32_t Key = Refl ? Tri : (Second ? SecondOrderKey(S->triangle[0], S->triangle[1])
+                                                      : (Thick ? Diffraction2Key(T->triangle, T->edge) : (0x80000000u | (Tri * 4u + DPaths[i - NR].edge))));
+            if ((Second || Thick) && std::any_of(V.begin() + (std::ptrdiff_t)(NR + ND), V.end(), [&](const fs_reflection_voice& X) { return X.key == Key; })) continue;
             V.emplace_back();
             const size_t Slot = V.size() - 1;
             V[Slot].key = Key;
@@ -547,20 +575,24 @@ public:
     // fs_update_reflection_paths filled with max_paths = MaxPaths); Out [count][FrameSize * 2] or nullptr, Mix [FrameSize * 2] (the
     // fp32 sum of the rows in list order) or nullptr, Counts [count] or nullptr; Diffraction = UpdateDiffractionPaths' result for the
     // same sources (its voices follow each source's reflections) or nullptr; Second = UpdateReflection2Paths' result for the same
-    // sources (its voices come last) or nullptr.  A source's table has MaxPaths + Diffraction->MaxPaths + Second->MaxPaths entries,
-    // FS_MAX_REFLECTION_VOICES (32) at most: the three defaults of 8, 4 and 16 fit, 16 + 16 + 16 is refused
+    // sources (its voices follow those) or nullptr; Thick = UpdateDiffraction2Paths' result for the same sources (its voices come
+    // last) or nullptr.  A source's table has MaxPaths + Diffraction->MaxPaths + Second->MaxPaths + Thick->MaxPaths entries,
+    // FS_MAX_REFLECTION_VOICES (32) at most: the four defaults of 8, 4, 16 and 4 fit, 16 + 16 + 16 is refused
     void ProcessAudio(const std::vector<FrequenSeeAudioComponent*>& Sources, const float* In, const std::vector<fs_reflection_row>& Rows,
                       const std::vector<fs_reflection_path>& Paths, int MaxPaths, float* Out, float* Mix = nullptr,
                       const FVector* Right = nullptr, float ReferenceLength = 0.0f, fs_reflection_render_row* Counts = nullptr,
                       const AudioRayTracingSubsystem::DiffractionPaths* Diffraction = nullptr,
-                      const AudioRayTracingSubsystem::Reflection2Paths* Second = nullptr) {
-        const int DMax = Diffraction ? Diffraction->MaxPaths : 0, SMax = Second ? Second->MaxPaths : 0, Stride = MaxPaths + DMax + SMax;
+                      const AudioRayTracingSubsystem::Reflection2Paths* Second = nullptr,
+                      const AudioRayTracingSubsystem::Diffraction2Paths* Thick = nullptr) {
+        const int DMax = Diffraction ? Diffraction->MaxPaths : 0, SMax = Second ? Second->MaxPaths : 0, TMax = Thick ? Thick->MaxPaths : 0;
+        const int Stride = MaxPaths + DMax + SMax + TMax;
         if (Stride > FS_MAX_REFLECTION_VOICES)
-            throw std::runtime_error("FrequenSee: max_paths of the reflections, the diffraction paths and the second-order reflections add up to " +
+            throw std::runtime_error("FrequenSee: max_paths of the reflections, the diffraction paths and the second-order paths add up to " +
                                      std::to_string(Stride) + " voices per source, more than FS_MAX_REFLECTION_VOICES");
-        if (Rows.size() != Sources.size() || Paths.size() != Sources.size() * (size_t)MaxPaths || MaxPaths < 1 || DMax < 0 || SMax < 0 ||
+        if (Rows.size() != Sources.size() || Paths.size() != Sources.size() * (size_t)MaxPaths || MaxPaths < 1 || DMax < 0 || SMax < 0 || TMax < 0 ||
             (Diffraction && (Diffraction->Rows.size() != Sources.size() || Diffraction->Paths.size() != Sources.size() * (size_t)DMax)) ||
-            (Second && (Second->Rows.size() != Sources.size() || Second->Paths.size() != Sources.size() * (size_t)SMax)))
+            (Second && (Second->Rows.size() != Sources.size() || Second->Paths.size() != Sources.size() * (size_t)SMax)) ||
+            (Thick && (Thick->Rows.size() != Sources.size() || Thick->Paths.size() != Sources.size() * (size_t)TMax)))
             throw std::runtime_error("FrequenSee: one row and MaxPaths paths per source");
         std::vector<fs_source> H;
         std::vector<fs_reflection_voice> All(Sources.size() * (size_t)Stride);
@@ -571,7 +603,9 @@ public:
                                                               Diffraction ? &Diffraction->Rows[i] : nullptr,
                                                               Diffraction ? Diffraction->Paths.data() + i * (size_t)DMax : nullptr,
                                                               Second ? &Second->Rows[i] : nullptr,
-                                                              Second ? Second->Paths.data() + i * (size_t)SMax : nullptr);
+                                                              Second ? Second->Paths.data() + i * (size_t)SMax : nullptr,
+                                                              Thick ? &Thick->Rows[i] : nullptr,
+                                                              Thick ? Thick->Paths.data() + i * (size_t)TMax : nullptr);
             std::copy(V.begin(), V.end(), All.begin() + (std::ptrdiff_t)(i * (size_t)Stride));
             N.push_back((int32_t)V.size());
         }

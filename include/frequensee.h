@@ -57,6 +57,7 @@
  *             fs_reflection_params_default fs_update_reflection_paths
  *             fs_diffraction_params_default fs_update_diffraction_paths
  *             fs_reflection2_params_default fs_update_reflection2_paths
+ *             fs_diffraction2_params_default fs_update_diffraction2_paths
  *             fs_direct_band_kernels fs_direct_render_init fs_direct_render_release fs_direct_render_process_batch
  *             fs_reflection_render_init fs_reflection_render_release fs_reflection_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
@@ -780,7 +781,7 @@ int fs_update_reflection_paths(fs_context* ctx, const fs_source* sources, int32_
  *      default octave edges); the lowest band's lo is half its hi, the highest band's hi twice its lo (the defaults give 125, 250,
  *      ... Hz), and a single band has f_0 = 1000 Hz.  The gain is an estimate a host is free to ignore: a barrier formula, not
  *      the uniform theory of diffraction, and it contains no distance law.  First order only: a thick obstacle, which needs two
- *      edges, yields nothing.  Nothing depends on which builder made the tree, on the order in which candidates were collected, or
+ *      edges, is fs_update_diffraction2_paths' business.  Nothing depends on which builder made the tree, on the order in which candidates were collected, or
  *      on count.  An empty committed scene gives rows of zeros.
  *   The key a host gives the voice of a path (fs_reflection_render_process_batch) is 0x80000000 | (4 triangle + edge): no
  *   reflection's key (its triangle) has the top bit set in a scene of fewer than 2^29 triangles.
@@ -912,6 +913,127 @@ void fs_reflection2_params_default(fs_reflection2_params* p);
 int fs_update_reflection2_paths(fs_context* ctx, const fs_source* sources, int32_t count,
                                 const fs_reflection2_params* params /* NULL = defaults */,
                                 fs_reflection2_row* rows /* [count] */, fs_reflection2_path* paths /* [count][max_paths] */);
+
+/* ---- second-order diffraction paths (EXTENDED): the diffraction round thick obstacles of every source of a tick -------------
+ * What is left of a source behind a wall, a pillar or a crate with thickness: no edge is seen by the source and the listener both,
+ * and the shortest sound path bends at TWO edges — source -> apex E1 on the rim of the face towards the source -> apex E0 on the
+ * rim of the face towards the listener -> listener.  Index 0 is the listener's end and index 1 the source's, as in
+ * fs_reflection2_path.  Found by an exhaustive scan of the ordered pairs of the edge records near enough to lie on a path within the
+ * detour cap: no sampling, no seed, no edge adjacency.  Specified to the bit with the conventions of "diffraction paths"
+ * (-ffp-contract=off, every fp32 operation rounded on its own in the order written, fmaf fused, a.b = (a.x b.x + a.y b.y) + a.z b.z,
+ * cross = product, product, subtract; divide and sqrtf correctly rounded; the records v0, e1, e2; own actors by the ids so / lo).
+ * Every marginal decision beyond the filters is taken by the closest-hit query fs_trace_rays answers.
+ *   An EDGE RECORD r = (triangle i, edge j) has the start a and the vector w of the first-order rule (j = 0: a = v0, w = e1; j = 1:
+ * a = v0 + e1, w = e2 - e1; j = 2: a = v0 + e2, w = -e2), ww = w.w, the triangle's n = cross(e1, e2), nn = n.n and v0,
+ * o = cross(w, n), oo = o.o, and the code k_r = 4 i + j (i the input index).  The path is S -> E1 on record q -> E0 on record p -> L.
+ * Per source at S, listener at L; g = S - L, distance = sqrtf(g.g):
+ *   0. Near set (part of the definition).  Record r is NEAR iff nn != 0, ww != 0, oo != 0, its triangle is not an own actor's, and
+ *      ((sqrtf(rS.rS) + sqrtf(rL.rL)) - (reach + reach)) <= distance + max_detour with rS = S - a, rL = L - a, reach = sqrtf(ww):
+ *      every point of the edge lies within reach of a, so an edge outside this bound carries no path within the detour cap.
+ *      near = their number.  near > max_near: flags = FS_DIFFRACTION2_NEAR_OVERFLOW, every other count is 0 and nothing else of
+ *      the row is computed.
+ *   1. Pair filter, for every ordered pair (q, p) of near records with q != p; a pair is rejected at the first test it fails.
+ *      Parallel: c = w_q.w_p; kept iff c c >= min_parallel (ww_q ww_p).  The two rims of a slab are parallel; skew pairs — over the
+ *      top, then round a side — are out of scope.
+ *      Gap: r = a_p - a_q; cg = cross(r, w_q); gg = cg.cg; kept iff gg > (merge merge) ww_q — the distance of a_p from q's line
+ *      exceeds merge, tested without the divide and the root.  Two records of one geometric edge (a rim found from both its faces)
+ *      are the first-order query's business.  g = sqrtf(gg / ww_q).
+ *      Apexes, all parameters on q's line: rS = S - a_q, rL = L - a_q; tS = (rS.w_q) / ww_q, tL = (rL.w_q) / ww_q;
+ *      cS = cross(rS, w_q), dS = sqrtf((cS.cS) / ww_q); r' = L - a_p, cL = cross(r', w_p), dL = sqrtf((cL.cL) / ww_p);
+ *      dt = tL - tS; dSg = dS + g; sum = dSg + dL; sum == 0: rejected.  t1 = tS + (dt dS) / sum; kept iff t1 >= -margin &&
+ *      t1 <= 1.0f + margin.  tm = tS + (dt dSg) / sum.  E1 = fmaf(t1, w_q, a_q), P = fmaf(tm, w_q, a_q) per component;
+ *      t0 = ((P - a_p).w_p) / ww_p; kept iff t0 >= -margin && t0 <= 1.0f + margin; E0 = fmaf(t0, w_p, a_p).  Nothing is clamped.
+ *      This is the closed form of unfolding three half-planes about two parallel lines: for exactly parallel edges the shortest
+ *      path, within min_parallel a path whose length is computed from its own points.
+ *      Sides: hS = (S - v0_q).n_q, h0 = (E0 - v0_q).n_q; kept iff (hS > 0 && h0 < 0) || (hS < 0 && h0 > 0).  hL = (L - v0_p).n_p,
+ *      h1 = (E1 - v0_p).n_p; kept iff strictly opposite likewise.  A slab's rims are found from the faces that look at S and at L;
+ *      the face between them is rejected, the other apex lying in its plane.
+ *      Shadow zones, the first-order rule's test twice with the other apex as the far end: s1 = hS / (hS - h0);
+ *      X1 = fmaf(s1, E0 - S, S); kept iff (X1 - E1).o_q <= 0.  s0 = h1 / (h1 - hL); X0 = fmaf(s0, L - E1, E1); kept iff
+ *      (X0 - E0).o_p <= 0.  A pair whose far apex is lit from the near end has no second-order path.
+ *      Length: u = S - E1, m = E1 - E0, v = E0 - L; l1 = sqrtf(u.u), lm = sqrtf(m.m), l0 = sqrtf(v.v); any of them 0: rejected.
+ *      length = (l1 + lm) + l0; detour = length - distance; kept iff detour <= max_detour.
+ *      candidates = the number of pairs that pass (exact even where the list is capped).  candidates > max_candidates:
+ *      flags = FS_DIFFRACTION2_OVERFLOW, confirmed = found = returned = 0.
+ *   2. Confirmation, per candidate: five legs, each chain(..) of "direct paths" with max_surfaces = 0 and this call's step.  With
+ *      the first-order rule's construction at each edge — io = 1.0f / sqrtf(oo), oh = o io; in = 1.0f / sqrtf(nn); nh_q = n_q in if
+ *      hS > 0 else n_q (-in), the unit normal of q towards S; nh_p = n_p in if hL > 0 else n_p (-in), that of p towards L:
+ *      Eo1 = fmaf(offset, oh_q, E1); ES = fmaf(offset, nh_q, Eo1); EM1 = fmaf(-offset, nh_q, Eo1);
+ *      Eo0 = fmaf(offset, oh_p, E0); EL = fmaf(offset, nh_p, Eo0); EM0 = fmaf(-offset, nh_p, Eo0).
+ *      Leg 1: e = ES - S, len = sqrtf(e.e); len == 0: reached; else chain(S, e (1.0f / len), len).
+ *      Leg 2: chain(ES, -nh_q, 2.0f offset).
+ *      Leg 3: e = EM0 - EM1, len likewise; chain(EM1, e (1.0f / len), len): it runs `offset` above the face between the rims.
+ *      Leg 4: chain(EM0, nh_p, 2.0f offset); it ends at EL.
+ *      Leg 5: e = L - EL, len likewise; chain(EL, e (1.0f / len), len - pullback).
+ *      CONFIRMED iff all five reached with crossed == 0 (the verdicts are independent: their order is free).  The short legs 2 and
+ *      4 reject the interior edges of tessellated faces and edges that run into another surface, as leg B of the first-order rule.
+ *   3. Merge.  key = (length as fp32 bits, k_p, k_q), compared as a triple.  A confirmed entry is DROPPED iff some confirmed entry
+ *      of the row with a smaller key — dropped itself or not — has BOTH q0 = E0 - E0', q0.q0 < merge merge and q1 = E1 - E1',
+ *      q1.q1 < merge merge.  found = the number kept.
+ *   4. Row.  The kept entries are ordered by key ascending; the first returned = min(found, max_paths) are written, the entries
+ *      beyond `returned` (all of them for an overflowed row) as all-zero bytes.  delay = (length / dist_divisor) / sound_speed;
+ *      gap = g; cos_bend[0] = (m.v) / (lm l0), cos_bend[1] = (u.m) / (l1 lm) (1 = no bend); apex[0] = E0, apex[1] = E1;
+ *      direction = v (1.0f / l0), from the listener towards E0; triangle, edge, material [0] of p and [1] of q.
+ *      gain[b] = 1.0f / sqrtf(3.0f + (k_b C3) detour) for b < num_bands and 0 beyond, with r = lam5_b / gap; rr = r r;
+ *      C3 = (1.0f + rr) / ((1.0f / 3.0f) + rr): ISO 9613-2's double-diffraction term on the first-order barrier formula.  k_b as in
+ *      "diffraction paths"; lam5_b = 5 sound_speed dist_divisor / f_b, computed by the host in double and rounded to float once.
+ *      C3 goes to 1 as the gap closes — the first-order gain — and to 3 for a wide slab.  Like the first-order gain it is an
+ *      estimate a host is free to ignore, and it contains no distance law.  Nothing depends on which builder made the tree, on
+ *      the order of collection or on count.  An empty committed scene gives rows of zeros.
+ *   The key a host gives the voice of such a path (fs_reflection_render_process_batch) is 0x20000000 | (h >> 3) with
+ *   h = (k_p * 2654435761 + k_q) mod 2^32: the one range no other kind uses (first-order reflections below 2^29, second-order
+ *   reflections 0x40000000 | ..., first-order diffraction 0x80000000 | ...).  Two paths of one row may share a key: a host keeps the
+ *   earlier in the row and drops the other.
+ *   Errors, ordering, refusals and staging: as fs_update_diffraction_paths, with FS_MAX_DIFFRACTION2_BATCH — the source table's
+ *   upload, one clear (of both counter arrays), THREE launches on the compute stream (the near scan of all edge records against
+ *   all rows; the pair filter over every row's near list; the confirmation, a wave per row), one copy back and one wait, whatever
+ *   count is; staging of its own, grown only at the first call with a larger count.  max_detour must be finite and > 0,
+ *   min_parallel finite, > 0 and <= 1.
+ *   Cost: near^2 pair tests per row, near counted in edge records — three per triangle.  The default max_detour keeps near below
+ *   the default max_near around a listener in a mine of 100 000 triangles (at most 12 427 of 16 384 for sources within 600 cm; at
+ *   500 cm half of such rows overflow, at the first-order call's 1000 cm all of them). */
+#define FS_MAX_DIFFRACTION2_PATHS         16
+#define FS_MAX_DIFFRACTION2_NEAR       32768
+#define FS_MAX_DIFFRACTION2_CANDIDATES  2048
+#define FS_MAX_DIFFRACTION2_BATCH        256
+#define FS_DIFFRACTION2_OVERFLOW          1u   /* fs_diffraction2_row.flags: more candidates than max_candidates */
+#define FS_DIFFRACTION2_NEAR_OVERFLOW     2u   /* fs_diffraction2_row.flags: more near edge records than max_near */
+typedef struct fs_diffraction2_params {
+    uint32_t struct_size;     /* = sizeof(fs_diffraction2_params) */
+    int32_t  max_paths;       /* 1 .. FS_MAX_DIFFRACTION2_PATHS, default 4: rows of `paths` per source */
+    int32_t  max_near;        /* 1 .. FS_MAX_DIFFRACTION2_NEAR, default 16384 */
+    int32_t  max_candidates;  /* 1 .. FS_MAX_DIFFRACTION2_CANDIDATES, default 1024 */
+    float    margin;          /* slack of the apexes' edge parameters, >= 0, finite; default 1e-3 */
+    float    max_detour;      /* cm, > 0, finite; default 250: it bounds near, and with it the cost */
+    float    min_parallel;    /* squared cosine two edges must reach to count as parallel, in (0, 1]; default 0.999 */
+    float    offset;          /* as fs_diffraction_params, default 0.1 */
+    float    merge;           /* cm: the least gap, and the distance within which two paths' apexes are one; >= 0; default 1.0 */
+    float    step;            /* as fs_diffraction_params, default 0.1 */
+    float    pullback;        /* cm leg 5 stops short of the listener, >= 0; default 0.1 */
+    float    dist_divisor;    /* 1000, as fs_params */
+    float    sound_speed;     /* 343, as fs_params */
+} fs_diffraction2_params;
+
+typedef struct fs_diffraction2_path {
+    float    length;          /* cm, listener -> E0 -> E1 -> source */
+    float    delay;           /* s, on the impulse response's time axis: (length / dist_divisor) / sound_speed */
+    float    detour;          /* cm, length - |S - L| */
+    float    gap;             /* cm, g: the distance between the two edges' lines, the obstacle's thickness (ISO 9613-2's e) */
+    float    cos_bend[2];     /* cosine of the angle the path turns by at E0 and at E1; 1 = straight on */
+    float    apex[2][3];      /* E0, E1 */
+    float    direction[3];    /* unit, from the listener towards E0: what a host pans by */
+    uint32_t triangle[2];     /* input indices of the triangles of p and q */
+    uint32_t edge[2];         /* their edges: 0: v0 -> v1, 1: v1 -> v2, 2: v2 -> v0 */
+    uint32_t material[2];     /* their material ids (FS_NO_MATERIAL possible) */
+    float    gain[FS_MAX_BANDS]; /* the barrier estimate; bands beyond num_bands: 0 */
+} fs_diffraction2_path;       /* an array element: no struct_size; 116 bytes */
+
+typedef struct fs_diffraction2_row { uint32_t near, candidates, confirmed, found, returned, flags; } fs_diffraction2_row;
+
+void fs_diffraction2_params_default(fs_diffraction2_params* p);
+int fs_update_diffraction2_paths(fs_context* ctx, const fs_source* sources, int32_t count,
+                                 const fs_diffraction2_params* params /* NULL = defaults */,
+                                 fs_diffraction2_row* rows /* [count] */, fs_diffraction2_path* paths /* [count][max_paths] */);
 
 /* ---- engine line trace the BVH kernel replaces (UWorld::LineTraceSingleByObjectType; call sites
  *      ARTS.cpp:252-254 any-hit, :340-342 closest-hit). Batch query, host arrays. ------------------- */
