@@ -561,71 +561,49 @@ def load():
     return lib
 
 
-def default_config(**kw) -> Config:
-    c = Config()
-    load().fs_config_default(C.byref(c))
+def _defaults(struct, fill, kw):
+    """a struct as the library's fs_*_default call fills it, then the caller's fields"""
+    p = struct()
+    getattr(load(), fill)(C.byref(p))
     for k, v in kw.items():
-        setattr(c, k, v)
-    return c
+        setattr(p, k, v)
+    return p
+
+
+def default_config(**kw) -> Config:
+    return _defaults(Config, "fs_config_default", kw)
 
 
 def default_sound_params(**kw) -> SoundParams:
-    p = SoundParams()
-    load().fs_sound_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(SoundParams, "fs_sound_params_default", kw)
 
 
 def default_direct_params(**kw) -> DirectParams:
-    p = DirectParams()
-    load().fs_direct_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(DirectParams, "fs_direct_params_default", kw)
 
 
 def default_reflection_params(**kw) -> ReflectionParams:
-    p = ReflectionParams()
-    load().fs_reflection_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(ReflectionParams, "fs_reflection_params_default", kw)
 
 
 def default_diffraction_params(**kw) -> DiffractionParams:
-    p = DiffractionParams()
-    load().fs_diffraction_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(DiffractionParams, "fs_diffraction_params_default", kw)
 
 
 def default_reflection2_params(**kw) -> Reflection2Params:
-    p = Reflection2Params()
-    load().fs_reflection2_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(Reflection2Params, "fs_reflection2_params_default", kw)
 
 
 def default_diffraction2_params(**kw) -> Diffraction2Params:
-    p = Diffraction2Params()
-    load().fs_diffraction2_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(Diffraction2Params, "fs_diffraction2_params_default", kw)
 
 
 def default_params(**kw) -> Params:
-    p = Params()
-    load().fs_params_default(C.byref(p))
-    for k, v in kw.items():
-        if k == "air_absorption":
-            for i, x in enumerate(v):
-                p.air_absorption[i] = float(x)
-        else:
-            setattr(p, k, v)
+    air = kw.pop("air_absorption", None)
+    p = _defaults(Params, "fs_params_default", kw)
+    if air is not None:
+        for i, x in enumerate(air):
+            p.air_absorption[i] = float(x)
     return p
 
 

@@ -388,6 +388,16 @@ class Context:
                                                    out.ctypes.data if out.size else None))
         return out
 
+    def _rows_and_paths(self, update, p, row_dtype, path_dtype, sources):
+        """the body of the four rows-and-paths queries: `update` (fs_update_*_paths) with the params p into fresh
+        (rows [count], paths [count][max_paths]) of the two dtypes"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        rows = np.zeros(srcs.shape[0], dtype=row_dtype)
+        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=path_dtype)
+        self.check(update(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
+                          rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
+        return rows, paths
+
     # ---- reflection paths: the first-order specular reflections of every source of a tick ----
     REFLECTION_ROW_DTYPE = np.dtype([("candidates", np.uint32), ("found", np.uint32), ("returned", np.uint32), ("flags", np.uint32)])
     REFLECTION_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("point", np.float32, (3,)), ("direction", np.float32, (3,)),
@@ -398,13 +408,8 @@ class Context:
         (candidates, found, returned, flags) and its `returned` shortest reflections (length cm, delay s, point, direction from the
         listener, triangle, material, reflectance [8]; entries beyond `returned` are zero); params = the fields of
         fs_reflection_params (max_paths, max_candidates, margin, step, offset, pullback, dist_divisor, sound_speed)"""
-        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
-        p = _capi.default_reflection_params(**params)
-        rows = np.zeros(srcs.shape[0], dtype=self.REFLECTION_ROW_DTYPE)
-        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=self.REFLECTION_DTYPE)
-        self.check(self.lib.fs_update_reflection_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
-                                                       rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
-        return rows, paths
+        return self._rows_and_paths(self.lib.fs_update_reflection_paths, _capi.default_reflection_params(**params), self.REFLECTION_ROW_DTYPE,
+                                    self.REFLECTION_DTYPE, sources)
 
     # ---- diffraction paths: the first-order edge diffraction of every source of a tick ----
     DIFFRACTION_ROW_DTYPE = np.dtype([("candidates", np.uint32), ("confirmed", np.uint32), ("found", np.uint32), ("returned", np.uint32),
@@ -419,13 +424,8 @@ class Context:
         cm, cos_bend, apex, direction from the listener, triangle, edge, material, gain [8]; entries beyond `returned` are zero);
         params = the fields of fs_diffraction_params (max_paths, max_candidates, margin, max_detour, offset, merge, step, pullback,
         dist_divisor, sound_speed)"""
-        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
-        p = _capi.default_diffraction_params(**params)
-        rows = np.zeros(srcs.shape[0], dtype=self.DIFFRACTION_ROW_DTYPE)
-        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=self.DIFFRACTION_DTYPE)
-        self.check(self.lib.fs_update_diffraction_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
-                                                        rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
-        return rows, paths
+        return self._rows_and_paths(self.lib.fs_update_diffraction_paths, _capi.default_diffraction_params(**params), self.DIFFRACTION_ROW_DTYPE,
+                                    self.DIFFRACTION_DTYPE, sources)
 
     # ---- second-order reflection paths: the specular reflections off two triangles of every source of a tick ----
     REFLECTION2_ROW_DTYPE = np.dtype([("near", np.uint32), ("candidates", np.uint32), ("found", np.uint32), ("returned", np.uint32),
@@ -439,13 +439,8 @@ class Context:
         -> source (length cm, delay s, point [PA, PB], direction from the listener, triangle [a, b], material [2], reflectance [8];
         entries beyond `returned` are zero); params = the fields of fs_reflection2_params (max_paths, max_near, max_candidates,
         max_length, margin, step, offset, pullback, dist_divisor, sound_speed)"""
-        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
-        p = _capi.default_reflection2_params(**params)
-        rows = np.zeros(srcs.shape[0], dtype=self.REFLECTION2_ROW_DTYPE)
-        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=self.REFLECTION2_DTYPE)
-        self.check(self.lib.fs_update_reflection2_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
-                                                        rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
-        return rows, paths
+        return self._rows_and_paths(self.lib.fs_update_reflection2_paths, _capi.default_reflection2_params(**params), self.REFLECTION2_ROW_DTYPE,
+                                    self.REFLECTION2_DTYPE, sources)
 
     # ---- second-order diffraction paths: the diffraction round thick obstacles of every source of a tick ----
     DIFFRACTION2_ROW_DTYPE = np.dtype([("near", np.uint32), ("candidates", np.uint32), ("confirmed", np.uint32), ("found", np.uint32),
@@ -462,13 +457,8 @@ class Context:
         triangle [2], edge [2], material [2], gain [8]; index 0 is the listener's end; entries beyond `returned` are zero);
         params = the fields of fs_diffraction2_params (max_paths, max_near, max_candidates, margin, max_detour, min_parallel, offset,
         merge, step, pullback, dist_divisor, sound_speed)"""
-        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
-        p = _capi.default_diffraction2_params(**params)
-        rows = np.zeros(srcs.shape[0], dtype=self.DIFFRACTION2_ROW_DTYPE)
-        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=self.DIFFRACTION2_DTYPE)
-        self.check(self.lib.fs_update_diffraction2_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
-                                                         rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
-        return rows, paths
+        return self._rows_and_paths(self.lib.fs_update_diffraction2_paths, _capi.default_diffraction2_params(**params), self.DIFFRACTION2_ROW_DTYPE,
+                                    self.DIFFRACTION2_DTYPE, sources)
 
     # ---- direct sound on the audio thread: fractional delay + band FIR for all sources of a callback ----
     RENDER_TARGET_DTYPE = np.dtype([("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,))])

@@ -1,7 +1,8 @@
 // fs_capi_paths.cpp — the path queries of a tick, each one call for all its sources: fs_update_direct_paths (fs_direct.hip) with the
 // sample offsets it uses, fs_update_reflection_paths (fs_reflect.hip), fs_update_diffraction_paths (fs_diffract.hip),
 // fs_update_reflection2_paths (fs_reflect2.hip) and fs_update_diffraction2_paths (fs_diffract2.hip), their defaults, and what the
-// five share on the host: the prologue, the staging, the packing of the sources and the copy back.
+// five share on the host: the prologue, the staging and its layout, the packing of the sources and, for the four that return rows
+// and paths, one driver from the argument checks to the copy back (update_rows_paths).
 #include "fs_context.hpp"
 
 static_assert(sizeof(fs_direct_params) == 32, "fs_direct_params: eight words");
@@ -24,14 +25,16 @@ static_assert(offsetof(fs_diffraction2_path, detour) == 8 && offsetof(fs_diffrac
               "fs_diffraction2_path: the offsets of include/frequensee.h");
 static_assert(sizeof(fs_diffraction2_row) == 24, "fs_diffraction2_row: six words");
 
-int PathStaging::grow(fs_context* ctx, int count, size_t pinned_bytes_per_row, size_t device_bytes_per_row) {
+int PathStaging::grow(fs_context* ctx, int count, const PathLayout& pinned_layout, const PathLayout& device_layout) {
+    pinned = pinned_layout;
+    device = device_layout;
     if (count <= cap) return FS_OK;
     // (every earlier call has been waited for: nothing in the stream reads the old staging)
     int rows = std::max(cap, 32);
     while (rows < count) rows *= 2;
     release();
-    FS_HIP(ctx, hipHostMalloc((void**)&h, (size_t)rows * pinned_bytes_per_row, hipHostMallocDefault));
-    FS_HIP(ctx, hipMalloc((void**)&d, (size_t)rows * device_bytes_per_row));
+    FS_HIP(ctx, hipHostMalloc((void**)&h, (size_t)rows * pinned.before(kPathSegments), hipHostMallocDefault));
+    FS_HIP(ctx, hipMalloc((void**)&d, (size_t)rows * device.before(kPathSegments)));
     cap = rows;
     return FS_OK;
 }
@@ -83,16 +86,6 @@ PathKHead path_head(const fs_context* ctx, const float4* src, int32_t count, flo
     return h;
 }
 
-// A scan-and-confirm query's device results — rows [count], then paths [count][max_paths] — through the pinned staging into the
-// caller's two arrays; waits for the call's kernels.
-int copy_back_rows_paths(fs_context* ctx, char* h_out, const char* d_out, size_t rows_bytes, size_t paths_bytes, void* rows, void* paths) {
-    FS_HIP(ctx, hipMemcpyAsync(h_out, d_out, rows_bytes + paths_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(rows, h_out, rows_bytes);
-    std::memcpy(paths, h_out + rows_bytes, paths_bytes);
-    return FS_OK;
-}
-
 // f_b of the header: the geometric mean of each band's edges, the outer bands with an octave-wide virtual edge
 void band_centres(const std::vector<double>& given, int B, double* f) {
     std::vector<double> e = given;
@@ -111,6 +104,80 @@ void refresh_band_centres(fs_context* ctx) {
     band_centres(ctx->band_edges, ctx->cfg.num_bands, ctx->diffract_f);
     ctx->diffract_f_edges = ctx->band_edges;
     ctx->diffract_f_bands = ctx->cfg.num_bands;
+}
+
+// k_b = 40 f_b / (sound_speed dist_divisor) and, where asked for, lam5_b = 5 sound_speed dist_divisor / f_b of the bands in force:
+// they travel with the launch's arguments, no table on the device
+void band_factors(fs_context* ctx, float sound_speed, float dist_divisor, float* k, float* lam5) {
+    refresh_band_centres(ctx);
+    for (int b = 0; b < ctx->cfg.num_bands; ++b) {
+        k[b] = (float)(40.0 * ctx->diffract_f[b] / ((double)sound_speed * (double)dist_divisor));
+        if (lam5) lam5[b] = (float)(5.0 * (double)sound_speed * (double)dist_divisor / ctx->diffract_f[b]);
+    }
+}
+
+// p, or the query's defaults where the caller passed none; false = a struct_size that is not this library's
+template <typename Params>
+bool params_or_default(const Params*& p, Params& def, void (*defaults)(Params*)) {
+    if (!p) { defaults(&def); p = &def; }
+    return p->struct_size == sizeof(Params);
+}
+
+// What one of the four rows-and-paths queries is, beyond its kernels: its messages, its staging and the sizes the staging is laid
+// out for (per row: counter arrays, near-list and candidate entries, bytes of a confirmed record, paths).
+template <typename Params, typename KP>
+struct RowsPathsQuery {
+    int32_t max_batch;
+    const char *bad_count, *bad_size, *bad_params;
+    void (*defaults)(Params*);
+    PathStaging fs_context::*stage;
+    size_t counter_arrays, max_near, max_candidates, record_bytes, max_paths;
+    void (*launch)(const DeviceScene&, const KP&, hipStream_t);
+};
+
+// A rows-and-paths query from its arguments to the caller's two arrays, every check in the order the header gives.  valid(p) is the
+// query's own test of its params; fill(kp, p, st) sets what the kernels read beyond h, rows and paths: the lists of st and the params.
+template <typename Params, typename KP, typename Row, typename Path, typename Valid, typename Fill>
+int update_rows_paths(const RowsPathsQuery<Params, KP>& q, fs_context* ctx, const fs_source* sources, int32_t count, const Params* p, Row* rows,
+                      Path* paths, Valid&& valid, Fill&& fill) {
+    if (!ctx || !sources || !rows || !paths) return FS_ERR_INVALID_ARGUMENT;
+    if (count < 1 || count > q.max_batch) return ctx->fail(FS_ERR_INVALID_ARGUMENT, q.bad_count);
+    Params def;
+    if (!params_or_default(p, def, q.defaults)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, q.bad_size);
+    if (!valid(*p)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, q.bad_params);
+    { int pr = paths_prologue(ctx, sources, count); if (pr) return pr; }
+    const size_t out_per_row = sizeof(Row) + q.max_paths * sizeof(Path);
+    PathStaging& st = ctx->*q.stage;
+    { int gr = st.grow(ctx, count, PathLayout{{sizeof(float4), 0, 0, 0, 0, out_per_row}},
+                       PathLayout{{sizeof(float4), sizeof(uint32_t) * q.counter_arrays, sizeof(uint32_t) * q.max_near, sizeof(uint32_t) * q.max_candidates,
+                                   q.record_bytes * q.max_candidates, out_per_row}}); if (gr) return gr; }
+    float4* h_src = reinterpret_cast<float4*>(st.host(kSegSources));
+    float4* d_src = reinterpret_cast<float4*>(st.dev(kSegSources));
+    char *h_out = st.host(kSegOut), *d_out = st.dev(kSegOut);
+    const size_t rows_bytes = sizeof(Row) * (size_t)count, paths_bytes = sizeof(Path) * (size_t)count * (size_t)p->max_paths;
+    pack_sources(ctx, sources, count, h_src);
+    KP kp{};
+    kp.h = path_head(ctx, d_src, count, p->step, p->pullback, p->dist_divisor, p->sound_speed);
+    kp.rows = reinterpret_cast<Row*>(d_out);
+    kp.paths = reinterpret_cast<Path*>(d_out + rows_bytes);
+    kp.max_paths = p->max_paths;
+    fill(kp, *p, st);
+    FS_HIP(ctx, hipMemcpyAsync(d_src, h_src, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(ctx, hipMemsetAsync(st.dev(kSegCounters), 0, st.dev_bytes(kSegCounters), ctx->stream));   // every counter array of the call: one clear
+    q.launch(ctx->scene, kp, ctx->stream);
+    FS_HIP(ctx, hipGetLastError());
+    FS_HIP(ctx, hipMemcpyAsync(h_out, d_out, rows_bytes + paths_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(ctx, hipStreamSynchronize(ctx->stream));   // waits for the call's kernels
+    std::memcpy(rows, h_out, rows_bytes);
+    std::memcpy(paths, h_out + rows_bytes, paths_bytes);
+    return FS_OK;
+}
+
+// the lists of a first-order query's staging, and of a second-order one's
+uint32_t* staged_words(const PathStaging& st, int seg) { return reinterpret_cast<uint32_t*>(st.dev(seg)); }
+NearPairLists staged_pair_lists(const PathStaging& st, int32_t max_near, int32_t max_candidates) {
+    return NearPairLists{staged_words(st, kSegCounters), staged_words(st, kSegCounters) + st.cap, staged_words(st, kSegNear), staged_words(st, kSegCand),
+                         max_near, max_candidates};
 }
 
 }  // namespace
@@ -152,15 +219,15 @@ int fs_update_direct_paths(fs_context* ctx, const fs_source* sources, int32_t co
     if (!ctx || !sources || !out) return FS_ERR_INVALID_ARGUMENT;
     if (count < 1 || count > FS_MAX_DIRECT_BATCH) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_DIRECT_BATCH)");
     fs_direct_params def;
-    if (!p) { fs_direct_params_default(&def); p = &def; }
-    if (p->struct_size != sizeof(fs_direct_params)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_direct_params.struct_size mismatch");
+    if (!params_or_default(p, def, fs_direct_params_default)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_direct_params.struct_size mismatch");
     if (p->samples < 1 || p->samples > FS_MAX_DIRECT_SAMPLES || p->max_surfaces < 1 || p->max_surfaces > FS_DIRECT_MAX_QUERIES - 1 ||
         !finite_at_least_zero(p->source_radius) || !finite_at_least_zero(p->step) || !finite_at_least_zero(p->pullback) ||
         !finite_above_zero(p->dist_divisor) || !finite_above_zero(p->sound_speed))
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad direct-path params");
     { int pr = paths_prologue(ctx, sources, count); if (pr) return pr; }
     PathStaging& st = ctx->direct_stage;
-    { int gr = st.grow(ctx, count, sizeof(float4) + sizeof(fs_direct_path), sizeof(fs_direct_path)); if (gr) return gr; }
+    { int gr = st.grow(ctx, count, PathLayout{{sizeof(float4), 0, 0, 0, 0, sizeof(fs_direct_path)}}, PathLayout{{0, 0, 0, 0, 0, sizeof(fs_direct_path)}});
+      if (gr) return gr; }
     const int n = p->source_radius == 0.0f ? 1 : p->samples;
     constexpr size_t kTable = (size_t)FS_MAX_DIRECT_SAMPLES * 3;
     if (!ctx->d_direct_off) FS_HIP(ctx, hipMalloc((void**)&ctx->d_direct_off, sizeof(float) * kTable * FS_MAX_DIRECT_SAMPLES));
@@ -171,9 +238,9 @@ int fs_update_direct_paths(fs_context* ctx, const fs_source* sources, int32_t co
         FS_HIP(ctx, hipMemcpy(d_off, tab, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
         ctx->direct_off_have |= 1ull << (n - 1);
     }
-    float4* h_src = reinterpret_cast<float4*>(st.h);
-    fs_direct_path* h_out = reinterpret_cast<fs_direct_path*>(st.h + (size_t)st.cap * sizeof(float4));
-    fs_direct_path* d_out = reinterpret_cast<fs_direct_path*>(st.d);
+    float4* h_src = reinterpret_cast<float4*>(st.host(kSegSources));
+    fs_direct_path* h_out = reinterpret_cast<fs_direct_path*>(st.host(kSegOut));
+    fs_direct_path* d_out = reinterpret_cast<fs_direct_path*>(st.dev(kSegOut));
     pack_sources(ctx, sources, count, h_src);
     DirectKParams dp{};
     dp.h = path_head(ctx, h_src, count, p->step, p->pullback, p->dist_divisor, p->sound_speed);
@@ -207,44 +274,21 @@ void fs_reflection_params_default(fs_reflection_params* p) {
 
 int fs_update_reflection_paths(fs_context* ctx, const fs_source* sources, int32_t count, const fs_reflection_params* p,
                                fs_reflection_row* rows, fs_reflection_path* paths) {
-    if (!ctx || !sources || !rows || !paths) return FS_ERR_INVALID_ARGUMENT;
-    if (count < 1 || count > FS_MAX_REFLECTION_BATCH) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_REFLECTION_BATCH)");
-    fs_reflection_params def;
-    if (!p) { fs_reflection_params_default(&def); p = &def; }
-    if (p->struct_size != sizeof(fs_reflection_params)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reflection_params.struct_size mismatch");
-    if (p->max_paths < 1 || p->max_paths > FS_MAX_REFLECTIONS || p->max_candidates < 1 || p->max_candidates > FS_MAX_REFLECTION_CANDIDATES ||
-        !finite_at_least_zero(p->margin) || !finite_at_least_zero(p->step) || !finite_at_least_zero(p->offset) ||
-        !finite_at_least_zero(p->pullback) || !finite_above_zero(p->dist_divisor) || !finite_above_zero(p->sound_speed))
-        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad reflection-path params");
-    { int pr = paths_prologue(ctx, sources, count); if (pr) return pr; }
-    constexpr size_t kCand = FS_MAX_REFLECTION_CANDIDATES;
-    constexpr size_t kOutPerRow = sizeof(fs_reflection_row) + FS_MAX_REFLECTIONS * sizeof(fs_reflection_path);
-    PathStaging& st = ctx->reflect_stage;
-    { int gr = st.grow(ctx, count, sizeof(float4) + kOutPerRow, sizeof(float4) + sizeof(uint32_t) * (1 + kCand) + kOutPerRow); if (gr) return gr; }
-    const size_t cap = (size_t)st.cap;
-    float4* h_src = reinterpret_cast<float4*>(st.h);
-    char* h_out = st.h + cap * sizeof(float4);
-    float4* d_src = reinterpret_cast<float4*>(st.d);
-    uint32_t* d_counters = reinterpret_cast<uint32_t*>(st.d + cap * sizeof(float4));
-    uint32_t* d_cand = d_counters + cap;
-    char* d_out = reinterpret_cast<char*>(d_cand + cap * kCand);
-    const size_t rows_bytes = sizeof(fs_reflection_row) * (size_t)count;
-    pack_sources(ctx, sources, count, h_src);
-    ReflectKParams rp{};
-    rp.h = path_head(ctx, d_src, count, p->step, p->pullback, p->dist_divisor, p->sound_speed);
-    rp.counters = d_counters;
-    rp.cand = d_cand;
-    rp.rows = reinterpret_cast<fs_reflection_row*>(d_out);
-    rp.paths = reinterpret_cast<fs_reflection_path*>(d_out + rows_bytes);
-    rp.max_paths = p->max_paths;
-    rp.max_candidates = p->max_candidates;
-    rp.margin = p->margin;
-    rp.offset = p->offset;
-    FS_HIP(ctx, hipMemcpyAsync(d_src, h_src, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(ctx, hipMemsetAsync(d_counters, 0, sizeof(uint32_t) * (size_t)count, ctx->stream));
-    launch_reflection_paths(ctx->scene, rp, ctx->stream);
-    FS_HIP(ctx, hipGetLastError());
-    return copy_back_rows_paths(ctx, h_out, d_out, rows_bytes, sizeof(fs_reflection_path) * (size_t)count * (size_t)p->max_paths, rows, paths);
+    static const RowsPathsQuery<fs_reflection_params, ReflectKParams> q = {
+        FS_MAX_REFLECTION_BATCH, "count out of range (1 .. FS_MAX_REFLECTION_BATCH)", "fs_reflection_params.struct_size mismatch",
+        "bad reflection-path params", fs_reflection_params_default, &fs_context::reflect_stage,
+        1, 0, FS_MAX_REFLECTION_CANDIDATES, 0, FS_MAX_REFLECTIONS, launch_reflection_paths};
+    return update_rows_paths(q, ctx, sources, count, p, rows, paths, [](const fs_reflection_params& p) {
+        return p.max_paths >= 1 && p.max_paths <= FS_MAX_REFLECTIONS && p.max_candidates >= 1 && p.max_candidates <= FS_MAX_REFLECTION_CANDIDATES &&
+               finite_at_least_zero(p.margin) && finite_at_least_zero(p.step) && finite_at_least_zero(p.offset) && finite_at_least_zero(p.pullback) &&
+               finite_above_zero(p.dist_divisor) && finite_above_zero(p.sound_speed);
+    }, [](ReflectKParams& rp, const fs_reflection_params& p, const PathStaging& st) {
+        rp.counters = staged_words(st, kSegCounters);
+        rp.cand = staged_words(st, kSegCand);
+        rp.max_candidates = p.max_candidates;
+        rp.margin = p.margin;
+        rp.offset = p.offset;
+    });
 }
 
 // ---- diffraction paths ------------------------------------------------------------------------------------------------------
@@ -266,53 +310,25 @@ void fs_diffraction_params_default(fs_diffraction_params* p) {
 
 int fs_update_diffraction_paths(fs_context* ctx, const fs_source* sources, int32_t count, const fs_diffraction_params* p,
                                 fs_diffraction_row* rows, fs_diffraction_path* paths) {
-    if (!ctx || !sources || !rows || !paths) return FS_ERR_INVALID_ARGUMENT;
-    if (count < 1 || count > FS_MAX_DIFFRACTION_BATCH) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_DIFFRACTION_BATCH)");
-    fs_diffraction_params def;
-    if (!p) { fs_diffraction_params_default(&def); p = &def; }
-    if (p->struct_size != sizeof(fs_diffraction_params)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_diffraction_params.struct_size mismatch");
-    if (p->max_paths < 1 || p->max_paths > FS_MAX_DIFFRACTIONS || p->max_candidates < 1 || p->max_candidates > FS_MAX_DIFFRACTION_CANDIDATES ||
-        !finite_at_least_zero(p->margin) || !finite_above_zero(p->max_detour) || !finite_at_least_zero(p->offset) ||
-        !finite_at_least_zero(p->merge) || !finite_at_least_zero(p->step) || !finite_at_least_zero(p->pullback) ||
-        !finite_above_zero(p->dist_divisor) || !finite_above_zero(p->sound_speed))
-        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad diffraction-path params");
-    { int pr = paths_prologue(ctx, sources, count); if (pr) return pr; }
-    constexpr size_t kCand = FS_MAX_DIFFRACTION_CANDIDATES;
-    constexpr size_t kOutPerRow = sizeof(fs_diffraction_row) + FS_MAX_DIFFRACTIONS * sizeof(fs_diffraction_path);
-    PathStaging& st = ctx->diffract_stage;
-    { int gr = st.grow(ctx, count, sizeof(float4) + kOutPerRow,
-                       sizeof(float4) + sizeof(DiffractRecord) * kCand + sizeof(uint32_t) * (1 + kCand) + kOutPerRow); if (gr) return gr; }
-    refresh_band_centres(ctx);
-    const size_t cap = (size_t)st.cap;
-    float4* h_src = reinterpret_cast<float4*>(st.h);
-    char* h_out = st.h + cap * sizeof(float4);
-    float4* d_src = reinterpret_cast<float4*>(st.d);
-    DiffractRecord* d_conf = reinterpret_cast<DiffractRecord*>(st.d + cap * sizeof(float4));
-    uint32_t* d_counters = reinterpret_cast<uint32_t*>(d_conf + cap * kCand);
-    uint32_t* d_cand = d_counters + cap;
-    char* d_out = reinterpret_cast<char*>(d_cand + cap * kCand);
-    const size_t rows_bytes = sizeof(fs_diffraction_row) * (size_t)count;
-    pack_sources(ctx, sources, count, h_src);
-    DiffractKParams dp{};
-    dp.h = path_head(ctx, d_src, count, p->step, p->pullback, p->dist_divisor, p->sound_speed);
-    dp.counters = d_counters;
-    dp.cand = d_cand;
-    dp.conf = d_conf;
-    dp.rows = reinterpret_cast<fs_diffraction_row*>(d_out);
-    dp.paths = reinterpret_cast<fs_diffraction_path*>(d_out + rows_bytes);
-    dp.max_paths = p->max_paths;
-    dp.max_candidates = p->max_candidates;
-    dp.margin = p->margin;
-    dp.max_detour = p->max_detour;
-    dp.offset = p->offset;
-    dp.merge = p->merge;
-    // k_b travels with the launch's arguments: eight words, no table on the device
-    for (int b = 0; b < ctx->cfg.num_bands; ++b) dp.k[b] = (float)(40.0 * ctx->diffract_f[b] / ((double)p->sound_speed * (double)p->dist_divisor));
-    FS_HIP(ctx, hipMemcpyAsync(d_src, h_src, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(ctx, hipMemsetAsync(d_counters, 0, sizeof(uint32_t) * (size_t)count, ctx->stream));
-    launch_diffraction_paths(ctx->scene, dp, ctx->stream);
-    FS_HIP(ctx, hipGetLastError());
-    return copy_back_rows_paths(ctx, h_out, d_out, rows_bytes, sizeof(fs_diffraction_path) * (size_t)count * (size_t)p->max_paths, rows, paths);
+    static const RowsPathsQuery<fs_diffraction_params, DiffractKParams> q = {
+        FS_MAX_DIFFRACTION_BATCH, "count out of range (1 .. FS_MAX_DIFFRACTION_BATCH)", "fs_diffraction_params.struct_size mismatch",
+        "bad diffraction-path params", fs_diffraction_params_default, &fs_context::diffract_stage,
+        1, 0, FS_MAX_DIFFRACTION_CANDIDATES, sizeof(DiffractRecord), FS_MAX_DIFFRACTIONS, launch_diffraction_paths};
+    return update_rows_paths(q, ctx, sources, count, p, rows, paths, [](const fs_diffraction_params& p) {
+        return p.max_paths >= 1 && p.max_paths <= FS_MAX_DIFFRACTIONS && p.max_candidates >= 1 && p.max_candidates <= FS_MAX_DIFFRACTION_CANDIDATES &&
+               finite_at_least_zero(p.margin) && finite_above_zero(p.max_detour) && finite_at_least_zero(p.offset) && finite_at_least_zero(p.merge) &&
+               finite_at_least_zero(p.step) && finite_at_least_zero(p.pullback) && finite_above_zero(p.dist_divisor) && finite_above_zero(p.sound_speed);
+    }, [ctx](DiffractKParams& dp, const fs_diffraction_params& p, const PathStaging& st) {
+        dp.counters = staged_words(st, kSegCounters);
+        dp.cand = staged_words(st, kSegCand);
+        dp.conf = reinterpret_cast<DiffractRecord*>(st.dev(kSegConf));
+        dp.max_candidates = p.max_candidates;
+        dp.margin = p.margin;
+        dp.max_detour = p.max_detour;
+        dp.offset = p.offset;
+        dp.merge = p.merge;
+        band_factors(ctx, p.sound_speed, p.dist_divisor, dp.k, nullptr);
+    });
 }
 
 // ---- second-order reflection paths ------------------------------------------------------------------------------------------
@@ -334,54 +350,22 @@ void fs_reflection2_params_default(fs_reflection2_params* p) {
 
 int fs_update_reflection2_paths(fs_context* ctx, const fs_source* sources, int32_t count, const fs_reflection2_params* p,
                                 fs_reflection2_row* rows, fs_reflection2_path* paths) {
-    if (!ctx || !sources || !rows || !paths) return FS_ERR_INVALID_ARGUMENT;
-    if (count < 1 || count > FS_MAX_REFLECTION2_BATCH) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_REFLECTION2_BATCH)");
-    fs_reflection2_params def;
-    if (!p) { fs_reflection2_params_default(&def); p = &def; }
-    if (p->struct_size != sizeof(fs_reflection2_params)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reflection2_params.struct_size mismatch");
-    if (p->max_paths < 1 || p->max_paths > FS_MAX_REFLECTION2_PATHS || p->max_near < 1 || p->max_near > FS_MAX_REFLECTION2_NEAR ||
-        p->max_candidates < 1 || p->max_candidates > FS_MAX_REFLECTION2_CANDIDATES || !finite_above_zero(p->max_length) ||
-        !finite_at_least_zero(p->margin) || !finite_at_least_zero(p->step) || !finite_at_least_zero(p->offset) ||
-        !finite_at_least_zero(p->pullback) || !finite_above_zero(p->dist_divisor) || !finite_above_zero(p->sound_speed))
-        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad second-order reflection-path params");
-    { int pr = paths_prologue(ctx, sources, count); if (pr) return pr; }
-    constexpr size_t kNear = FS_MAX_REFLECTION2_NEAR, kCand = FS_MAX_REFLECTION2_CANDIDATES;
-    constexpr size_t kOutPerRow = sizeof(fs_reflection2_row) + FS_MAX_REFLECTION2_PATHS * sizeof(fs_reflection2_path);
-    PathStaging& st = ctx->reflect2_stage;
-    { int gr = st.grow(ctx, count, sizeof(float4) + kOutPerRow,
-                       sizeof(float4) + sizeof(uint32_t) * (2 + kNear + kCand) + sizeof(Reflect2Record) * kCand + kOutPerRow); if (gr) return gr; }
-    const size_t cap = (size_t)st.cap;
-    float4* h_src = reinterpret_cast<float4*>(st.h);
-    char* h_out = st.h + cap * sizeof(float4);
-    float4* d_src = reinterpret_cast<float4*>(st.d);
-    uint32_t* d_near_counters = reinterpret_cast<uint32_t*>(st.d + cap * sizeof(float4));
-    uint32_t* d_counters = d_near_counters + cap;
-    uint32_t* d_near = d_counters + cap;
-    uint32_t* d_cand = d_near + cap * kNear;
-    Reflect2Record* d_conf = reinterpret_cast<Reflect2Record*>(d_cand + cap * kCand);
-    char* d_out = reinterpret_cast<char*>(d_conf + cap * kCand);
-    const size_t rows_bytes = sizeof(fs_reflection2_row) * (size_t)count;
-    pack_sources(ctx, sources, count, h_src);
-    Reflect2KParams rp{};
-    rp.h = path_head(ctx, d_src, count, p->step, p->pullback, p->dist_divisor, p->sound_speed);
-    rp.near_counters = d_near_counters;
-    rp.counters = d_counters;
-    rp.near = d_near;
-    rp.cand = d_cand;
-    rp.conf = d_conf;
-    rp.rows = reinterpret_cast<fs_reflection2_row*>(d_out);
-    rp.paths = reinterpret_cast<fs_reflection2_path*>(d_out + rows_bytes);
-    rp.max_paths = p->max_paths;
-    rp.max_near = p->max_near;
-    rp.max_candidates = p->max_candidates;
-    rp.max_length = p->max_length;
-    rp.margin = p->margin;
-    rp.offset = p->offset;
-    FS_HIP(ctx, hipMemcpyAsync(d_src, h_src, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(ctx, hipMemsetAsync(d_near_counters, 0, sizeof(uint32_t) * 2 * cap, ctx->stream));   // both counter arrays: they lie side by side
-    launch_reflection2_paths(ctx->scene, rp, ctx->stream);
-    FS_HIP(ctx, hipGetLastError());
-    return copy_back_rows_paths(ctx, h_out, d_out, rows_bytes, sizeof(fs_reflection2_path) * (size_t)count * (size_t)p->max_paths, rows, paths);
+    static const RowsPathsQuery<fs_reflection2_params, Reflect2KParams> q = {
+        FS_MAX_REFLECTION2_BATCH, "count out of range (1 .. FS_MAX_REFLECTION2_BATCH)", "fs_reflection2_params.struct_size mismatch",
+        "bad second-order reflection-path params", fs_reflection2_params_default, &fs_context::reflect2_stage,
+        2, FS_MAX_REFLECTION2_NEAR, FS_MAX_REFLECTION2_CANDIDATES, sizeof(Reflect2Record), FS_MAX_REFLECTION2_PATHS, launch_reflection2_paths};
+    return update_rows_paths(q, ctx, sources, count, p, rows, paths, [](const fs_reflection2_params& p) {
+        return p.max_paths >= 1 && p.max_paths <= FS_MAX_REFLECTION2_PATHS && p.max_near >= 1 && p.max_near <= FS_MAX_REFLECTION2_NEAR &&
+               p.max_candidates >= 1 && p.max_candidates <= FS_MAX_REFLECTION2_CANDIDATES && finite_above_zero(p.max_length) &&
+               finite_at_least_zero(p.margin) && finite_at_least_zero(p.step) && finite_at_least_zero(p.offset) && finite_at_least_zero(p.pullback) &&
+               finite_above_zero(p.dist_divisor) && finite_above_zero(p.sound_speed);
+    }, [](Reflect2KParams& rp, const fs_reflection2_params& p, const PathStaging& st) {
+        rp.l = staged_pair_lists(st, p.max_near, p.max_candidates);
+        rp.conf = reinterpret_cast<Reflect2Record*>(st.dev(kSegConf));
+        rp.max_length = p.max_length;
+        rp.margin = p.margin;
+        rp.offset = p.offset;
+    });
 }
 
 // ---- second-order diffraction paths -----------------------------------------------------------------------------------------
@@ -405,63 +389,26 @@ void fs_diffraction2_params_default(fs_diffraction2_params* p) {
 
 int fs_update_diffraction2_paths(fs_context* ctx, const fs_source* sources, int32_t count, const fs_diffraction2_params* p,
                                  fs_diffraction2_row* rows, fs_diffraction2_path* paths) {
-    if (!ctx || !sources || !rows || !paths) return FS_ERR_INVALID_ARGUMENT;
-    if (count < 1 || count > FS_MAX_DIFFRACTION2_BATCH) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_DIFFRACTION2_BATCH)");
-    fs_diffraction2_params def;
-    if (!p) { fs_diffraction2_params_default(&def); p = &def; }
-    if (p->struct_size != sizeof(fs_diffraction2_params)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_diffraction2_params.struct_size mismatch");
-    if (p->max_paths < 1 || p->max_paths > FS_MAX_DIFFRACTION2_PATHS || p->max_near < 1 || p->max_near > FS_MAX_DIFFRACTION2_NEAR ||
-        p->max_candidates < 1 || p->max_candidates > FS_MAX_DIFFRACTION2_CANDIDATES || !finite_at_least_zero(p->margin) ||
-        !finite_above_zero(p->max_detour) || !finite_above_zero(p->min_parallel) || p->min_parallel > 1.0f || !finite_at_least_zero(p->offset) ||
-        !finite_at_least_zero(p->merge) || !finite_at_least_zero(p->step) || !finite_at_least_zero(p->pullback) ||
-        !finite_above_zero(p->dist_divisor) || !finite_above_zero(p->sound_speed))
-        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad second-order diffraction-path params");
-    { int pr = paths_prologue(ctx, sources, count); if (pr) return pr; }
-    constexpr size_t kNear = FS_MAX_DIFFRACTION2_NEAR, kCand = FS_MAX_DIFFRACTION2_CANDIDATES;
-    constexpr size_t kOutPerRow = sizeof(fs_diffraction2_row) + FS_MAX_DIFFRACTION2_PATHS * sizeof(fs_diffraction2_path);
-    PathStaging& st = ctx->diffract2_stage;
-    { int gr = st.grow(ctx, count, sizeof(float4) + kOutPerRow,
-                       sizeof(float4) + sizeof(uint32_t) * (2 + kNear + kCand) + sizeof(Diffract2Record) * kCand + kOutPerRow); if (gr) return gr; }
-    refresh_band_centres(ctx);
-    const size_t cap = (size_t)st.cap;
-    float4* h_src = reinterpret_cast<float4*>(st.h);
-    char* h_out = st.h + cap * sizeof(float4);
-    float4* d_src = reinterpret_cast<float4*>(st.d);
-    uint32_t* d_near_counters = reinterpret_cast<uint32_t*>(st.d + cap * sizeof(float4));
-    uint32_t* d_counters = d_near_counters + cap;
-    uint32_t* d_near = d_counters + cap;
-    uint32_t* d_cand = d_near + cap * kNear;
-    Diffract2Record* d_conf = reinterpret_cast<Diffract2Record*>(d_cand + cap * kCand);
-    char* d_out = reinterpret_cast<char*>(d_conf + cap * kCand);
-    const size_t rows_bytes = sizeof(fs_diffraction2_row) * (size_t)count;
-    pack_sources(ctx, sources, count, h_src);
-    Diffract2KParams dp{};
-    dp.h = path_head(ctx, d_src, count, p->step, p->pullback, p->dist_divisor, p->sound_speed);
-    dp.near_counters = d_near_counters;
-    dp.counters = d_counters;
-    dp.near = d_near;
-    dp.cand = d_cand;
-    dp.conf = d_conf;
-    dp.rows = reinterpret_cast<fs_diffraction2_row*>(d_out);
-    dp.paths = reinterpret_cast<fs_diffraction2_path*>(d_out + rows_bytes);
-    dp.max_paths = p->max_paths;
-    dp.max_near = p->max_near;
-    dp.max_candidates = p->max_candidates;
-    dp.margin = p->margin;
-    dp.max_detour = p->max_detour;
-    dp.min_parallel = p->min_parallel;
-    dp.offset = p->offset;
-    dp.merge = p->merge;
-    // k_b and lam5_b travel with the launch's arguments: sixteen words, no table on the device
-    for (int b = 0; b < ctx->cfg.num_bands; ++b) {
-        dp.k[b] = (float)(40.0 * ctx->diffract_f[b] / ((double)p->sound_speed * (double)p->dist_divisor));
-        dp.lam5[b] = (float)(5.0 * (double)p->sound_speed * (double)p->dist_divisor / ctx->diffract_f[b]);
-    }
-    FS_HIP(ctx, hipMemcpyAsync(d_src, h_src, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(ctx, hipMemsetAsync(d_near_counters, 0, sizeof(uint32_t) * 2 * cap, ctx->stream));   // both counter arrays: they lie side by side
-    launch_diffraction2_paths(ctx->scene, dp, ctx->stream);
-    FS_HIP(ctx, hipGetLastError());
-    return copy_back_rows_paths(ctx, h_out, d_out, rows_bytes, sizeof(fs_diffraction2_path) * (size_t)count * (size_t)p->max_paths, rows, paths);
+    static const RowsPathsQuery<fs_diffraction2_params, Diffract2KParams> q = {
+        FS_MAX_DIFFRACTION2_BATCH, "count out of range (1 .. FS_MAX_DIFFRACTION2_BATCH)", "fs_diffraction2_params.struct_size mismatch",
+        "bad second-order diffraction-path params", fs_diffraction2_params_default, &fs_context::diffract2_stage,
+        2, FS_MAX_DIFFRACTION2_NEAR, FS_MAX_DIFFRACTION2_CANDIDATES, sizeof(Diffract2Record), FS_MAX_DIFFRACTION2_PATHS, launch_diffraction2_paths};
+    return update_rows_paths(q, ctx, sources, count, p, rows, paths, [](const fs_diffraction2_params& p) {
+        return p.max_paths >= 1 && p.max_paths <= FS_MAX_DIFFRACTION2_PATHS && p.max_near >= 1 && p.max_near <= FS_MAX_DIFFRACTION2_NEAR &&
+               p.max_candidates >= 1 && p.max_candidates <= FS_MAX_DIFFRACTION2_CANDIDATES && finite_at_least_zero(p.margin) &&
+               finite_above_zero(p.max_detour) && finite_above_zero(p.min_parallel) && p.min_parallel <= 1.0f && finite_at_least_zero(p.offset) &&
+               finite_at_least_zero(p.merge) && finite_at_least_zero(p.step) && finite_at_least_zero(p.pullback) &&
+               finite_above_zero(p.dist_divisor) && finite_above_zero(p.sound_speed);
+    }, [ctx](Diffract2KParams& dp, const fs_diffraction2_params& p, const PathStaging& st) {
+        dp.l = staged_pair_lists(st, p.max_near, p.max_candidates);
+        dp.conf = reinterpret_cast<Diffract2Record*>(st.dev(kSegConf));
+        dp.margin = p.margin;
+        dp.max_detour = p.max_detour;
+        dp.min_parallel = p.min_parallel;
+        dp.offset = p.offset;
+        dp.merge = p.merge;
+        band_factors(ctx, p.sound_speed, p.dist_divisor, dp.k, dp.lam5);
+    });
 }
 
 }  // extern "C"

@@ -229,13 +229,30 @@ struct ObjectMoves {
 };
 
 // A path query's staging pair (fs_capi_paths.cpp): pinned host memory and its device counterpart, both with room for `cap` rows.
+// A buffer is a row of segments in the order of PathSegment, each [cap] times its bytes per row (0: the query has no such segment):
+// the rows' sources as float4 | the counters a call clears, [cap] words each and side by side (a second-order query has two: near
+// counters, then candidate counters) | near lists | candidate lists | confirmed records | what the copy back reads, rows [count]
+// then paths [count][max_paths].  grow sizes the buffers and host / dev find a segment from the one PathLayout.
 // Plain pointers: grow replaces the pair, release frees it (fs_context_destroy).
+enum PathSegment { kSegSources, kSegCounters, kSegNear, kSegCand, kSegConf, kSegOut, kPathSegments };
+struct PathLayout {
+    size_t bytes_per_row[kPathSegments];
+    size_t before(int seg) const {   // the bytes per row of the segments ahead of seg (kPathSegments: of them all)
+        size_t sum = 0;
+        for (int i = 0; i < seg; ++i) sum += bytes_per_row[i];
+        return sum;
+    }
+};
 struct PathStaging {
     char* h = nullptr;
     char* d = nullptr;
     int cap = 0;
+    PathLayout pinned{}, device{};   // what grow was called with
     // room for `count` rows: a pair too small is replaced by one of twice the rows (32 at least) until it fits.  FS_OK or the failure reported.
-    int grow(fs_context* ctx, int count, size_t pinned_bytes_per_row, size_t device_bytes_per_row);
+    int grow(fs_context* ctx, int count, const PathLayout& pinned_layout, const PathLayout& device_layout);
+    char* host(int seg) const { return h + (size_t)cap * pinned.before(seg); }
+    char* dev(int seg) const { return d + (size_t)cap * device.before(seg); }
+    size_t dev_bytes(int seg) const { return (size_t)cap * device.bytes_per_row[seg]; }
     void release();
 };
 
@@ -314,19 +331,11 @@ struct fs_context {
     float* d_carrier = nullptr;          // [B][carrier_stride(num_samples)] fp32
     float carrier_build_ms = 0.0f;       // device time of the last build (HIP events)
     // The path queries' staging (fs_capi_paths.cpp), one per query: the queries share no buffer.  Each is sized for its query's
-    // largest max_paths and max_candidates, so that only a larger count grows it.
-    // direct_stage — pinned: the rows' sources [cap] float4 (read by the kernel in place) | the rows [cap] fs_direct_path (the copy's
-    // target); device: the rows.  d_direct_off: the sample-offset tables [FS_MAX_DIRECT_SAMPLES][FS_MAX_DIRECT_SAMPLES][3] by n - 1,
-    // each uploaded at its first use.
-    // reflect_stage — pinned: sources [cap] float4 | the copy's target, rows [count] then paths [count][max_paths]; device: sources
-    // [cap] float4 | counters [cap] | candidates [cap][FS_MAX_REFLECTION_CANDIDATES] | rows and paths.
-    // diffract_stage — pinned: as reflect_stage; device: sources [cap] float4 | confirmed records [cap][FS_MAX_DIFFRACTION_CANDIDATES]
-    // | counters [cap] | candidates [cap][FS_MAX_DIFFRACTION_CANDIDATES] | rows and paths.  diffract_f: the band centres f_b of the
-    // edges in force (diffract_f_edges, diffract_f_bands: what they were built from; rebuilt when fs_set_band_edges has changed them).
-    // reflect2_stage — pinned: as reflect_stage; device: sources [cap] float4 | near counters [cap] | candidate counters [cap] | near
-    // lists [cap][FS_MAX_REFLECTION2_NEAR] | candidates [cap][FS_MAX_REFLECTION2_CANDIDATES] | confirmed records
-    // [cap][FS_MAX_REFLECTION2_CANDIDATES] | rows and paths.
-    // diffract2_stage — as reflect2_stage with the FS_MAX_DIFFRACTION2_* sizes; it shares diffract_f.
+    // largest max_paths, max_near and max_candidates, so that only a larger count grows it; its segments are the query's PathLayout.
+    // direct_stage: the kernel reads the pinned sources in place.  d_direct_off: the sample-offset tables
+    // [FS_MAX_DIRECT_SAMPLES][FS_MAX_DIRECT_SAMPLES][3] by n - 1, each uploaded at its first use.
+    // diffract_f: the band centres f_b of the edges in force (diffract_f_edges, diffract_f_bands: what they were built from; rebuilt
+    // when fs_set_band_edges has changed them), shared by the two diffraction queries.
     PathStaging direct_stage, reflect_stage, diffract_stage, reflect2_stage, diffract2_stage;
     float* d_direct_off = nullptr;
     uint64_t direct_off_have = 0;

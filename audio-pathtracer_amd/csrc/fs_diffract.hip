@@ -1,16 +1,15 @@
 // fs_diffract.hip — fs_update_diffraction_paths: the first-order edge diffraction of every source of a tick.  The definitions
 // (filter, the three legs, the merge, the row) are those of include/frequensee.h, operation by operation; this file is their mapping
-// onto the device, in two kernels — the construction of fs_reflect.hip with another filter and three legs instead of two; what the two
-// files have in common is in fs_dev_paths.hpp.
+// onto the device, in two kernels on the scaffolds of fs_dev_paths.hpp.
 //   diffract_scan_kernel: the scan scaffold (scan_records) with this file's filter.  The three edges of a record are filtered in
 // registers for each row (what they share — normal, plane distances — is unpacked once); a survivor's code is leaf position * 4 + edge.
 //   diffract_confirm_kernel: one wave per source row, kBlock / 64 rows per workgroup; the lanes stride over the row's candidates
 // (at most FS_MAX_DIFFRACTION_CANDIDATES / 64 = 32 rounds).  A lane recomputes its candidate's values with the filter's own code —
 // the same bits — and runs the legs, the short one first, as chains (path_chain) round one copy of the traversal; a lane
 // whose candidate has already failed idles along with an empty cursor, a round in which no lane is left skips the remaining legs.
-// Nothing is kept per candidate: a confirmed one takes the next place of the row's list in the call's device staging (ballot and
-// prefix count, no atomics), written and read by the row's own wave only.  The merge and the ranks are counted over that list — a
-// handful of entries — in two passes: dropped or not, then the rank among the kept.  Plain vector stores, no sort network.
+// Nothing is kept per candidate: a confirmed one takes the next place of the row's list in the call's device staging (compact_slot,
+// no atomics), written and read by the row's own wave only.  The merge and the ranks are counted over that list — a handful of
+// entries — in two passes: dropped or not (mark_kept), then the rank among the kept.  Plain vector stores, no sort network.
 //   Dynamic LDS of the confirm kernel: the stack rows [stack_rows][kBlock], nothing else.
 #include "fs_dev_paths.hpp"
 
@@ -32,8 +31,7 @@ struct DiffPlane {
 };
 __device__ __forceinline__ DiffPlane diffract_plane(const TriEnds g, const float4 s4, const float (&L)[3]) {
     DiffPlane p;
-    const float gx = s4.x - L[0], gy = s4.y - L[1], gz = s4.z - L[2];
-    p.distance = sqrtf((gx * gx + gy * gy) + gz * gz);
+    p.distance = row_distance(s4, L);
     const float s = g.hS / (g.hS - g.hL);
     p.Xx = fmaf(s, L[0] - s4.x, s4.x); p.Xy = fmaf(s, L[1] - s4.y, s4.y); p.Xz = fmaf(s, L[2] - s4.z, s4.z);
     return p;
@@ -42,19 +40,11 @@ __device__ __forceinline__ DiffPlane diffract_plane(const TriEnds g, const float
 // Step 1 of the rule for one (triangle record, edge, source row); g and p = what the record's three edges share
 __device__ __forceinline__ bool diffract_filter(const TriEnds g, const DiffPlane p, int edge, const float4 s4, const float (&L)[3], float m,
                                                 float max_detour, DiffCandidate& f) {
-    const float v0x = g.v0x, v0y = g.v0y, v0z = g.v0z, e1x = g.e1x, e1y = g.e1y, e1z = g.e1z, e2x = g.e2x, e2y = g.e2y, e2z = g.e2z;
-    const float nx = g.nx, ny = g.ny, nz = g.nz, nn = g.nn, hS = g.hS, hL = g.hL;
+    const float nn = g.nn, hS = g.hS, hL = g.hL;
     const float Sx = s4.x, Sy = s4.y, Sz = s4.z;
     const bool opposite = (hS > 0.0f && hL < 0.0f) || (hS < 0.0f && hL > 0.0f);
-    const float ax = edge == 0 ? v0x : (edge == 1 ? v0x + e1x : v0x + e2x);
-    const float ay = edge == 0 ? v0y : (edge == 1 ? v0y + e1y : v0y + e2y);
-    const float az = edge == 0 ? v0z : (edge == 1 ? v0z + e1z : v0z + e2z);
-    const float wx = edge == 0 ? e1x : (edge == 1 ? e2x - e1x : -e2x);
-    const float wy = edge == 0 ? e1y : (edge == 1 ? e2y - e1y : -e2y);
-    const float wz = edge == 0 ? e1z : (edge == 1 ? e2z - e1z : -e2z);
-    const float ww = (wx * wx + wy * wy) + wz * wz;
-    const float ox = wy * nz - wz * ny, oy = wz * nx - wx * nz, oz = wx * ny - wy * nx;
-    const float oo = (ox * ox + oy * oy) + oz * oz;
+    const EdgeRec e = edge_rec(g, edge);
+    const float ax = e.ax, ay = e.ay, az = e.az, wx = e.wx, wy = e.wy, wz = e.wz, ww = e.ww, ox = e.ox, oy = e.oy, oz = e.oz, oo = e.oo;
     const float rSx = Sx - ax, rSy = Sy - ay, rSz = Sz - az;
     const float rLx = L[0] - ax, rLy = L[1] - ay, rLz = L[2] - az;
     const float tS = ((rSx * wx + rSy * wy) + rSz * wz) / ww;
@@ -111,13 +101,8 @@ __global__ __launch_bounds__(kBlock) void diffract_confirm_kernel(DeviceScene sc
         const TriEnds g = tri_ends(rec, s4, dp.h);
         DiffCandidate f;
         (void)diffract_filter(g, diffract_plane(g, s4, dp.h.lis), (int)(code & 3u), s4, dp.h.lis, dp.margin, dp.max_detour, f);
-        const float io = 1.0f / sqrtf(f.oo);
-        const float in = 1.0f / sqrtf(g.nn);
-        const float sg = g.hS > 0.0f ? in : -in;
-        const float nhx = g.nx * sg, nhy = g.ny * sg, nhz = g.nz * sg;
-        const float Eox = fmaf(dp.offset, f.ox * io, f.E0x), Eoy = fmaf(dp.offset, f.oy * io, f.E0y), Eoz = fmaf(dp.offset, f.oz * io, f.E0z);
-        const float ESx = fmaf(dp.offset, nhx, Eox), ESy = fmaf(dp.offset, nhy, Eoy), ESz = fmaf(dp.offset, nhz, Eoz);
-        const float ELx = fmaf(-dp.offset, nhx, Eox), ELy = fmaf(-dp.offset, nhy, Eoy), ELz = fmaf(-dp.offset, nhz, Eoz);
+        const ApexOffsets ao = apex_offsets(f.E0x, f.E0y, f.E0z, f.ox, f.oy, f.oz, f.oo, g.nx, g.ny, g.nz, g.nn, g.hS, dp.offset);   // towards S
+        const float nhx = ao.nhx, nhy = ao.nhy, nhz = ao.nhz, ESx = ao.upx, ESy = ao.upy, ESz = ao.upz, ELx = ao.downx, ELy = ao.downy, ELz = ao.downz;
         bool ok = mine;
 #pragma unroll 1
         for (int leg = 0; leg < 3; ++leg) {   // B, A, C: one copy of the traversal; the verdicts are independent
@@ -133,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void diffract_confirm_kernel(DeviceScene sc
         }
         const unsigned long long votes = __ballot(ok);
         if (ok) {
-            DiffractRecord* o = conf + confirmed + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
+            DiffractRecord* o = conf + confirmed + compact_slot(votes, lane);
             const float il = 1.0f / f.lL;
             o->length_bits = __float_as_uint(f.length);
             o->key = __float_as_uint(rec.c.z) * 4u + (code & 3u);
@@ -142,30 +127,17 @@ __global__ __launch_bounds__(kBlock) void diffract_confirm_kernel(DeviceScene sc
             o->detour = f.detour;
             o->cos_bend = ((f.ux * f.vx + f.uy * f.vy) + f.uz * f.vz) / (f.lS * f.lL);
             o->material = __float_as_uint(rec.c.y);
-            o->pad = 0u;
+            o->kept = 0u;
         }
         confirmed += (uint32_t)__popcll(votes);
     }
     __syncthreads();   // the list is in memory for every lane of the wave that wrote it
     const float mm = dp.merge * dp.merge;
-    uint32_t found = 0u;
-#pragma unroll 1
-    for (uint32_t base = 0u; base < confirmed; base += 64u) {   // dropped or kept
-        const uint32_t e = base + (uint32_t)lane;
-        bool kept = e < confirmed;
-        if (kept) {
-            const DiffractRecord me = conf[e];
-            const unsigned long long key = path_key(me.length_bits, me.key);
-            for (uint32_t j = 0u; j < confirmed; ++j) {
-                const DiffractRecord* x = conf + j;
-                const float qx = me.apex[0] - x->apex[0], qy = me.apex[1] - x->apex[1], qz = me.apex[2] - x->apex[2];
-                const float qq = (qx * qx + qy * qy) + qz * qz;
-                if (path_key(x->length_bits, x->key) < key && qq < mm) kept = false;
-            }
-            conf[e].pad = kept ? 1u : 0u;
-        }
-        found += (uint32_t)__popcll(__ballot(kept));
-    }
+    const uint32_t found = mark_kept(conf, confirmed, lane, [](const DiffractRecord* x) { return path_key(x->length_bits, x->key); },
+                                     [&](const DiffractRecord& me, const DiffractRecord* x) {
+        const float qx = me.apex[0] - x->apex[0], qy = me.apex[1] - x->apex[1], qz = me.apex[2] - x->apex[2];
+        return ((qx * qx + qy * qy) + qz * qz) < mm;
+    });
     __syncthreads();
     if (!cr.row_ok) return;
     const uint32_t returned = min(found, (uint32_t)dp.max_paths);
@@ -175,10 +147,10 @@ __global__ __launch_bounds__(kBlock) void diffract_confirm_kernel(DeviceScene sc
         const uint32_t e = base + (uint32_t)lane;
         if (e >= confirmed) continue;
         const DiffractRecord me = conf[e];
-        if (me.pad == 0u) continue;
+        if (me.kept == 0u) continue;
         const uint32_t rank = rank_among(confirmed, path_key(me.length_bits, me.key), [&](uint32_t j) {
             const DiffractRecord* x = conf + j;
-            return x->pad != 0u ? path_key(x->length_bits, x->key) : kNoPathKey;
+            return x->kept != 0u ? path_key(x->length_bits, x->key) : kNoPathKey;
         });
         if (rank >= (uint32_t)dp.max_paths) continue;
         fs_diffraction_path* o = out + rank;

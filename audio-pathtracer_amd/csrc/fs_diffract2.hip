@@ -1,60 +1,25 @@
 // fs_diffract2.hip — fs_update_diffraction2_paths: the second-order edge diffraction of every source of a tick, the sound that bends
 // round the two parallel rims of a thick obstacle.  The definitions (near set, pair filter, the five legs, the merge, the row) are
-// those of include/frequensee.h, operation by operation; this file is their mapping onto the device, in three kernels — the
-// construction of fs_reflect2.hip with edge records in place of triangles and the legs and the merge of fs_diffract.hip.
-//   diffract2_near_kernel: the scan scaffold of fs_dev_paths.hpp (scan_records) with step 0 as its filter over the three edges of a
-// record; a near edge record's code is leaf position * 4 + edge, the row's near list the "candidate list" of the scaffold.
-//   diffract2_pair_kernel: the hot one — near^2 pair tests per row.  A thread holds one near edge record in the role of q (the
-// source's end) in registers, with what depends on q and the row alone — tS, tL - tS, dS, their product, hS, o_q — precomputed; the
-// row's near list in the role of p (the listener's end) streams through LDS in tiles of kPairTile entries.  Each of the tile's threads
-// unpacks one p once — a, w, ww, dL, v0, hL, n: 15 words — and the inner loop reads entry after entry at one address for the whole
-// wave (an LDS broadcast).  The parallel test (six multiplies) and the gap test stand before any divide or square root: they leave
-// the pairs of parallel edges that are not one line; the apex ranges and the strict-side tests end the rest but for a handful.  A
-// survivor takes a place in the row's candidate list by atomicAdd (the counter keeps counting past the cap) as its two near-list
-// slots, 15 + 15 bits.
-//   The grid is (tile of q, share of the p tiles, row), as reflect2_pair_kernel's: a call for one source fills the chip.
-//   diffract2_confirm_kernel: the shape of diffract_confirm_kernel — one wave per source row, kBlock / 64 rows per workgroup, the
-// lanes stride over the row's candidates (at most FS_MAX_DIFFRACTION2_CANDIDATES / 64 = 32 rounds).  A lane recomputes its pair's
-// values with the pair filter's own code — the same bits — and runs the five legs, the two short ones first, as chains (path_chain)
-// round one copy of the traversal; a lane whose candidate has already failed idles along.  A confirmed one takes the next place of
-// the row's list in the call's device staging (ballot and prefix count), written and read by the row's own wave only; merge and
-// rank are counted over that list by the 96-bit key (length bits, p, q).  Plain vector stores, no sort network.
+// those of include/frequensee.h, operation by operation; this file is their mapping onto the device, in three kernels on the
+// scaffolds of fs_dev_paths.hpp.
+//   diffract2_near_kernel: the scan scaffold (scan_records) with step 0 as its filter over the three edges of a record; a near edge
+// record's code is leaf position * 4 + edge, the row's near list the "candidate list" of the scaffold.
+//   diffract2_pair_kernel: the hot one — the pair scaffold (pair_records).  The held entry is a near edge record in the role of q (the
+// source's end), with what depends on q and the row alone — tS, tL - tS, dS, their product, hS, o_q — precomputed; the streamed one a
+// near edge record in the role of p (the listener's end): a, w, ww, dL, v0, hL, n, 15 words.  The parallel test (six multiplies)
+// and the gap test stand before any divide or square root: they leave the pairs of parallel edges that are not one line; the apex
+// ranges and the strict-side tests end the rest but for a handful.
+//   diffract2_confirm_kernel: one wave per source row (confirm_row), the lanes stride over the row's candidates (at most
+// FS_MAX_DIFFRACTION2_CANDIDATES / 64 = 32 rounds).  A lane recomputes its pair's values with the pair filter's own code — the same
+// bits — and runs the five legs, the two short ones first, as chains (path_chain) round one copy of the traversal; a lane whose
+// candidate has already failed idles along.  A confirmed one takes the next place of the row's list in the call's device staging
+// (compact_slot), written and read by the row's own wave only; merge (mark_kept) and rank are counted over that list by the 96-bit
+// key (length bits, p, q).  Plain vector stores, no sort network.
 //   Dynamic LDS of the confirm kernel: the stack rows [stack_rows][kBlock], nothing else.
 #include "fs_dev_paths.hpp"
 
 namespace fs {
 namespace {
-
-static_assert(FS_MAX_DIFFRACTION2_BATCH == FS_MAX_REFLECTION_BATCH, "the scan kernels stage a call's rows in one LDS array size");
-
-constexpr int kPairTile = kBlock;   // entries of p per LDS tile: one per thread
-constexpr int kPairSplit = 16;      // the p tiles of a row are shared among at most this many workgroups per tile of q
-constexpr int kSlotBits = 15;       // a candidate = slot of q << 15 | slot of p
-
-// edge j of a record: start a, vector w, ww = w.w, o = cross(w, n), oo = o.o — the first-order rule's, operation by operation
-struct EdgeRec {
-    float ax, ay, az, wx, wy, wz, ww;
-    float ox, oy, oz, oo;
-};
-__device__ __forceinline__ EdgeRec edge_rec(const TriEnds g, int edge) {
-    EdgeRec e;
-    e.ax = edge == 0 ? g.v0x : (edge == 1 ? g.v0x + g.e1x : g.v0x + g.e2x);
-    e.ay = edge == 0 ? g.v0y : (edge == 1 ? g.v0y + g.e1y : g.v0y + g.e2y);
-    e.az = edge == 0 ? g.v0z : (edge == 1 ? g.v0z + g.e1z : g.v0z + g.e2z);
-    e.wx = edge == 0 ? g.e1x : (edge == 1 ? g.e2x - g.e1x : -g.e2x);
-    e.wy = edge == 0 ? g.e1y : (edge == 1 ? g.e2y - g.e1y : -g.e2y);
-    e.wz = edge == 0 ? g.e1z : (edge == 1 ? g.e2z - g.e1z : -g.e2z);
-    e.ww = (e.wx * e.wx + e.wy * e.wy) + e.wz * e.wz;
-    e.ox = e.wy * g.nz - e.wz * g.ny; e.oy = e.wz * g.nx - e.wx * g.nz; e.oz = e.wx * g.ny - e.wy * g.nx;
-    e.oo = (e.ox * e.ox + e.oy * e.oy) + e.oz * e.oz;
-    return e;
-}
-
-// |S - L| of a row
-__device__ __forceinline__ float row_distance(const float4 s4, const float (&L)[3]) {
-    const float gx = s4.x - L[0], gy = s4.y - L[1], gz = s4.z - L[2];
-    return sqrtf((gx * gx + gy * gy) + gz * gz);
-}
 
 // Step 0 of the rule for one (edge record, source row); bound = |S - L| + max_detour
 __device__ __forceinline__ bool diffract2_near(const TriEnds g, const EdgeRec e, const float4 s4, const float (&L)[3], float bound) {
@@ -72,6 +37,7 @@ struct PairQ {
     float nx, ny, nz, v0x, v0y, v0z, hS;
     float ox, oy, oz;
     float tS, dt, dS, dtdS;   // tS, tL - tS, dS, (tL - tS) dS: S and L against q's line
+    float distance;           // |S - L|: the row's, the same in every lane — it travels with q to the detour test
 };
 __device__ __forceinline__ PairQ pair_q(const TriEnds g, const EdgeRec e, const float4 s4, const float (&L)[3]) {
     PairQ q;
@@ -86,6 +52,7 @@ __device__ __forceinline__ PairQ pair_q(const TriEnds g, const EdgeRec e, const 
     q.dS = sqrtf(((cx * cx + cy * cy) + cz * cz) / e.ww);
     q.dt = tL - q.tS;
     q.dtdS = q.dt * q.dS;
+    q.distance = row_distance(s4, L);
     return q;
 }
 
@@ -120,7 +87,7 @@ __device__ __forceinline__ bool strictly_opposite(float a, float b) { return (a 
 
 // Step 1 of the rule for one ordered pair (q, p) of near edge records.  The early returns change no bit: every operation is rounded
 // on its own wherever it stands.
-__device__ __forceinline__ bool pair2_filter(const PairQ& q, const PairP& p, const float4 s4, const float (&L)[3], float distance, float m,
+__device__ __forceinline__ bool pair2_filter(const PairQ& q, const PairP& p, const float4 s4, const float (&L)[3], float m,
                                              float min_parallel, float mm, float max_detour, Pair2& f) {
     const float c = (q.wx * p.wx + q.wy * p.wy) + q.wz * p.wz;
     if (!(c * c >= min_parallel * (q.ww * p.ww))) return false;
@@ -165,7 +132,7 @@ __device__ __forceinline__ bool pair2_filter(const PairQ& q, const PairP& p, con
     const float lm = sqrtf((mx * mx + my * my) + mz * mz);
     const float l0 = sqrtf((vx * vx + vy * vy) + vz * vz);
     const float length = (l1 + lm) + l0;
-    const float detour = length - distance;
+    const float detour = length - q.distance;
     f.E0x = E0x; f.E0y = E0y; f.E0z = E0z; f.E1x = E1x; f.E1y = E1y; f.E1z = E1z;
     f.ux = ux; f.uy = uy; f.uz = uz; f.l1 = l1;
     f.mx = mx; f.my = my; f.mz = mz; f.lm = lm;
@@ -176,7 +143,7 @@ __device__ __forceinline__ bool pair2_filter(const PairQ& q, const PairP& p, con
 }
 
 __global__ __launch_bounds__(kBlock) void diffract2_near_kernel(DeviceScene sc, Diffract2KParams dp) {
-    scan_records(sc, dp.h, dp.near_counters, dp.near, dp.max_near, [&](uint32_t leaf, const TriEnds g, const float4 s4, auto&& emit) {
+    scan_records(sc, dp.h, dp.l.near_counters, dp.l.near, dp.l.max_near, [&](uint32_t leaf, const TriEnds g, const float4 s4, auto&& emit) {
         const float bound = row_distance(s4, dp.h.lis) + dp.max_detour;
 #pragma unroll
         for (int edge = 0; edge < 3; ++edge)
@@ -185,48 +152,24 @@ __global__ __launch_bounds__(kBlock) void diffract2_near_kernel(DeviceScene sc, 
 }
 
 __global__ __launch_bounds__(kBlock) void diffract2_pair_kernel(DeviceScene sc, Diffract2KParams dp) {
-    __shared__ float4 s_p[4][kPairTile];
-    const int row = (int)blockIdx.z;
-    const uint32_t counted = dp.near_counters[row];
-    if (counted > (uint32_t)dp.max_near || blockIdx.x * (uint32_t)kBlock >= counted) return;   // (the same for the whole workgroup)
-    const int near = (int)counted;
-    const uint32_t* list = dp.near + (size_t)row * dp.max_near;
-    const float4 s4 = dp.h.src[row];
-    const float distance = row_distance(s4, dp.h.lis);
     const float mm = dp.merge * dp.merge;
-    const int q_slot = (int)(blockIdx.x * kBlock + threadIdx.x);
-    const bool have_q = q_slot < near;
-    const uint32_t q_code = list[have_q ? q_slot : 0];
-    const TriEnds gq = tri_ends(sc.tris[q_code >> 2], s4, dp.h);
-    const PairQ q = pair_q(gq, edge_rec(gq, (int)(q_code & 3u)), s4, dp.h.lis);
-    const int tiles = (near + kPairTile - 1) / kPairTile;
-#pragma unroll 1
-    for (int t = (int)blockIdx.y; t < tiles; t += (int)gridDim.y) {
-        const int first = t * kPairTile;
-        __syncthreads();   // the tile before has been read
-        if (first + (int)threadIdx.x < near) {
-            const uint32_t p_code = list[first + (int)threadIdx.x];
-            const TriEnds gp = tri_ends(sc.tris[p_code >> 2], s4, dp.h);
-            const PairP p = pair_p(gp, edge_rec(gp, (int)(p_code & 3u)), dp.h.lis);
-            s_p[0][threadIdx.x] = make_float4(p.ax, p.ay, p.az, p.ww);
-            s_p[1][threadIdx.x] = make_float4(p.wx, p.wy, p.wz, p.dL);
-            s_p[2][threadIdx.x] = make_float4(p.v0x, p.v0y, p.v0z, p.hL);
-            s_p[3][threadIdx.x] = make_float4(p.nx, p.ny, p.nz, 0.0f);
-        }
-        __syncthreads();
-        const int np = min(kPairTile, near - first);
-        if (!have_q) continue;
-#pragma unroll 1
-        for (int j = 0; j < np; ++j) {   // (j is the same in every lane: each read below is one address per wave)
-            const float4 p0 = s_p[0][j], p1 = s_p[1][j], p2 = s_p[2][j], p3 = s_p[3][j];
-            const PairP p = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w, p2.x, p2.y, p2.z, p2.w, p3.x, p3.y, p3.z};
+    pair_records(
+        dp.h, dp.l,
+        [&](uint32_t code, const float4 s4) {
+            const TriEnds g = tri_ends(sc.tris[code >> 2], s4, dp.h);
+            return pair_q(g, edge_rec(g, (int)(code & 3u)), s4, dp.h.lis);
+        },
+        [&](uint32_t code, const float4 s4) {
+            const TriEnds g = tri_ends(sc.tris[code >> 2], s4, dp.h);
+            const PairP p = pair_p(g, edge_rec(g, (int)(code & 3u)), dp.h.lis);
+            return PairRow{make_float4(p.ax, p.ay, p.az, p.ww), make_float4(p.wx, p.wy, p.wz, p.dL), make_float4(p.v0x, p.v0y, p.v0z, p.hL),
+                           make_float4(p.nx, p.ny, p.nz, 0.0f)};
+        },
+        [&](const PairQ& q, const PairRow r, const float4 s4) {
+            const PairP p = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w, r.d.x, r.d.y, r.d.z};
             Pair2 f;
-            if (first + j != q_slot && pair2_filter(q, p, s4, dp.h.lis, distance, dp.margin, dp.min_parallel, mm, dp.max_detour, f)) {
-                const uint32_t k = atomicAdd(&dp.counters[row], 1u);
-                if (k < (uint32_t)dp.max_candidates) dp.cand[(size_t)row * dp.max_candidates + k] = ((uint32_t)q_slot << kSlotBits) | (uint32_t)(first + j);
-            }
-        }
-    }
+            return pair2_filter(q, p, s4, dp.h.lis, dp.margin, dp.min_parallel, mm, dp.max_detour, f);
+        });
 }
 
 __device__ __forceinline__ PathKey96 record_key(const Diffract2Record* x) { return PathKey96{path_key(x->length_bits, x->kp), x->kq}; }
@@ -234,13 +177,12 @@ __device__ __forceinline__ PathKey96 record_key(const Diffract2Record* x) { retu
 __global__ __launch_bounds__(kBlock) void diffract2_confirm_kernel(DeviceScene sc, Diffract2KParams dp) {
     extern __shared__ __attribute__((aligned(16))) int s_dyn[];   // [stack_rows][kBlock]
     int* stack = &s_dyn[threadIdx.x];
-    const ConfirmRow cr = confirm_row(dp.h, dp.counters, dp.cand, dp.max_candidates);
+    const ConfirmRow cr = confirm_row(dp.h, dp.l);
     const int lane = cr.lane, n = cr.n, row = cr.row, B = dp.h.num_bands;
     const float4 s4 = cr.s4;
-    const uint32_t near = cr.row_ok ? dp.near_counters[row] : 0u;
-    const uint32_t* list = dp.near + (size_t)cr.slot * dp.max_near;
-    Diffract2Record* conf = dp.conf + (size_t)cr.slot * dp.max_candidates;
-    const float distance = row_distance(s4, dp.h.lis);
+    const uint32_t near = near_count(cr, dp.l);
+    const uint32_t* list = dp.l.near + (size_t)cr.slot * dp.l.max_near;
+    Diffract2Record* conf = dp.conf + (size_t)cr.slot * dp.l.max_candidates;
     const float mm = dp.merge * dp.merge;
     uint32_t confirmed = 0u;
 #pragma unroll 1
@@ -248,24 +190,18 @@ __global__ __launch_bounds__(kBlock) void diffract2_confirm_kernel(DeviceScene s
         const int c = base + lane;
         const bool mine = c < n;
         const uint32_t code = mine ? cr.list[c] : 0u;
-        const uint32_t q_code = list[code >> kSlotBits], p_code = list[code & ((1u << kSlotBits) - 1u)];
+        const uint32_t q_code = pair_held(list, code), p_code = pair_streamed(list, code);
         const Tri48 recQ = sc.tris[q_code >> 2], recP = sc.tris[p_code >> 2];
         const TriEnds gq = tri_ends(recQ, s4, dp.h), gp = tri_ends(recP, s4, dp.h);
         const EdgeRec eq = edge_rec(gq, (int)(q_code & 3u)), ep = edge_rec(gp, (int)(p_code & 3u));
         Pair2 f = {};
-        (void)pair2_filter(pair_q(gq, eq, s4, dp.h.lis), pair_p(gp, ep, dp.h.lis), s4, dp.h.lis, distance, dp.margin, dp.min_parallel, mm,
+        (void)pair2_filter(pair_q(gq, eq, s4, dp.h.lis), pair_p(gp, ep, dp.h.lis), s4, dp.h.lis, dp.margin, dp.min_parallel, mm,
                            dp.max_detour, f);
         // the first-order rule's construction at each edge: the unit normal of q towards S, of p towards L
-        const float ioq = 1.0f / sqrtf(eq.oo), inq = 1.0f / sqrtf(gq.nn), sq = gq.hS > 0.0f ? inq : -inq;
-        const float nqx = gq.nx * sq, nqy = gq.ny * sq, nqz = gq.nz * sq;
-        const float Eo1x = fmaf(dp.offset, eq.ox * ioq, f.E1x), Eo1y = fmaf(dp.offset, eq.oy * ioq, f.E1y), Eo1z = fmaf(dp.offset, eq.oz * ioq, f.E1z);
-        const float ESx = fmaf(dp.offset, nqx, Eo1x), ESy = fmaf(dp.offset, nqy, Eo1y), ESz = fmaf(dp.offset, nqz, Eo1z);
-        const float M1x = fmaf(-dp.offset, nqx, Eo1x), M1y = fmaf(-dp.offset, nqy, Eo1y), M1z = fmaf(-dp.offset, nqz, Eo1z);
-        const float iop = 1.0f / sqrtf(ep.oo), inp = 1.0f / sqrtf(gp.nn), sp = gp.hL > 0.0f ? inp : -inp;
-        const float npx = gp.nx * sp, npy = gp.ny * sp, npz = gp.nz * sp;
-        const float Eo0x = fmaf(dp.offset, f.opx * iop, f.E0x), Eo0y = fmaf(dp.offset, f.opy * iop, f.E0y), Eo0z = fmaf(dp.offset, f.opz * iop, f.E0z);
-        const float ELx = fmaf(dp.offset, npx, Eo0x), ELy = fmaf(dp.offset, npy, Eo0y), ELz = fmaf(dp.offset, npz, Eo0z);
-        const float M0x = fmaf(-dp.offset, npx, Eo0x), M0y = fmaf(-dp.offset, npy, Eo0y), M0z = fmaf(-dp.offset, npz, Eo0z);
+        const ApexOffsets aq = apex_offsets(f.E1x, f.E1y, f.E1z, eq.ox, eq.oy, eq.oz, eq.oo, gq.nx, gq.ny, gq.nz, gq.nn, gq.hS, dp.offset);
+        const ApexOffsets ap = apex_offsets(f.E0x, f.E0y, f.E0z, f.opx, f.opy, f.opz, ep.oo, gp.nx, gp.ny, gp.nz, gp.nn, gp.hL, dp.offset);
+        const float nqx = aq.nhx, nqy = aq.nhy, nqz = aq.nhz, ESx = aq.upx, ESy = aq.upy, ESz = aq.upz, M1x = aq.downx, M1y = aq.downy, M1z = aq.downz;
+        const float npx = ap.nhx, npy = ap.nhy, npz = ap.nhz, ELx = ap.upx, ELy = ap.upy, ELz = ap.upz, M0x = ap.downx, M0y = ap.downy, M0z = ap.downz;
         bool ok = mine;
 #pragma unroll 1
         for (int leg = 0; leg < 5; ++leg) {   // legs 2, 4, 3, 1, 5 of the rule: one copy of the traversal; the verdicts are independent
@@ -287,7 +223,7 @@ __global__ __launch_bounds__(kBlock) void diffract2_confirm_kernel(DeviceScene s
         }
         const unsigned long long votes = __ballot(ok);
         if (ok) {
-            Diffract2Record* o = conf + confirmed + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
+            Diffract2Record* o = conf + confirmed + compact_slot(votes, lane);
             const float il = 1.0f / f.l0;
             o->length_bits = __float_as_uint(f.length);
             o->kp = __float_as_uint(recP.c.z) * 4u + (p_code & 3u);
@@ -305,25 +241,12 @@ __global__ __launch_bounds__(kBlock) void diffract2_confirm_kernel(DeviceScene s
         confirmed += (uint32_t)__popcll(votes);
     }
     __syncthreads();   // the list is in memory for every lane of the wave that wrote it
-    uint32_t found = 0u;
-#pragma unroll 1
-    for (uint32_t base = 0u; base < confirmed; base += 64u) {   // dropped or kept
-        const uint32_t e = base + (uint32_t)lane;
-        bool kept = e < confirmed;
-        if (kept) {
-            const Diffract2Record me = conf[e];
-            const PathKey96 key = record_key(&me);
-            for (uint32_t j = 0u; j < confirmed; ++j) {
-                const Diffract2Record* x = conf + j;
-                const float ax = me.apex[0][0] - x->apex[0][0], ay = me.apex[0][1] - x->apex[0][1], az = me.apex[0][2] - x->apex[0][2];
-                const float bx = me.apex[1][0] - x->apex[1][0], by = me.apex[1][1] - x->apex[1][1], bz = me.apex[1][2] - x->apex[1][2];
-                const float aa = (ax * ax + ay * ay) + az * az, bb = (bx * bx + by * by) + bz * bz;
-                if (record_key(x) < key && aa < mm && bb < mm) kept = false;
-            }
-            conf[e].kept = kept ? 1u : 0u;
-        }
-        found += (uint32_t)__popcll(__ballot(kept));
-    }
+    const uint32_t found = mark_kept(conf, confirmed, lane, [](const Diffract2Record* x) { return record_key(x); },
+                                     [&](const Diffract2Record& me, const Diffract2Record* x) {
+        const float ax = me.apex[0][0] - x->apex[0][0], ay = me.apex[0][1] - x->apex[0][1], az = me.apex[0][2] - x->apex[0][2];
+        const float bx = me.apex[1][0] - x->apex[1][0], by = me.apex[1][1] - x->apex[1][1], bz = me.apex[1][2] - x->apex[1][2];
+        return ((ax * ax + ay * ay) + az * az) < mm && ((bx * bx + by * by) + bz * bz) < mm;
+    });
     __syncthreads();
     if (!cr.row_ok) return;
     const uint32_t returned = min(found, (uint32_t)dp.max_paths);
@@ -361,33 +284,20 @@ __global__ __launch_bounds__(kBlock) void diffract2_confirm_kernel(DeviceScene s
     }
     zero_tail(out, lane, returned, dp.max_paths);
     if (lane == 0) {
-        const bool near_overflow = near > (uint32_t)dp.max_near;
         fs_diffraction2_row* r = dp.rows + row;
         r->near = near;
         r->candidates = cr.cands;
         r->confirmed = confirmed;
         r->found = found;
         r->returned = returned;
-        r->flags = near_overflow ? FS_DIFFRACTION2_NEAR_OVERFLOW : (cr.overflow ? FS_DIFFRACTION2_OVERFLOW : 0u);
+        r->flags = pair_row_flags(cr, dp.l, near, FS_DIFFRACTION2_NEAR_OVERFLOW, FS_DIFFRACTION2_OVERFLOW);
     }
 }
 
 }  // namespace
 
-void launch_diffraction2_paths(const DeviceScene& sc_in, const Diffract2KParams& dp, hipStream_t s) {
-    if (dp.h.count <= 0) return;
-    const uint32_t blocks = row_blocks(dp.h.count);
-    DeviceScene sc = sc_in;
-    if (!attach_deep(sc, blocks)) return;
-    if (sc.num_tris > 0) {
-        hipLaunchKernelGGL(diffract2_near_kernel, dim3((uint32_t)((sc.num_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, sc, dp);
-        const long long records = 3ll * (long long)sc.num_tris;
-        const uint32_t q_tiles = (uint32_t)((std::min(records, (long long)dp.max_near) + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(diffract2_pair_kernel, dim3(q_tiles, std::min(q_tiles, (uint32_t)kPairSplit), (uint32_t)dp.h.count), dim3(kBlock), 0, s, sc, dp);
-    }
-    const size_t lds = stack_bytes(sc);
-    allow_lds(diffract2_confirm_kernel, lds);
-    hipLaunchKernelGGL(diffract2_confirm_kernel, dim3(blocks), dim3(kBlock), lds, s, sc, dp);
+void launch_diffraction2_paths(const DeviceScene& sc, const Diffract2KParams& dp, hipStream_t s) {
+    launch_near_pair_confirm(diffract2_near_kernel, diffract2_pair_kernel, diffract2_confirm_kernel, sc, dp, 3, dp.l.max_near, 0, s);   // a triangle: three edge records
 }
 
 }  // namespace fs

@@ -413,8 +413,10 @@ void launch_trace_rays(const DeviceScene& sc, const float* o, const float* d, co
                        int32_t* hit, float* t, int32_t* tri, float* normal, hipStream_t s);
 // rays_per_wave < 64: sparse waves whose other lanes help with every closest-hit query; 64 = one ray per lane
 void launch_update_sound(const DeviceScene& sc, const SoundKParams& sp, SoundAccum* acc, int rays_per_wave, hipStream_t s);
-// The common head of the three path queries' kernel arguments (fs_dev_paths.hpp reads nothing else of them): src = the rows' sources,
-// xyz + the source's actor id as bits; lis, lis_object = the listener and its actor; count rows.
+// The path queries' kernel arguments.  What the queries share on the device — the chain, the scan, pair and confirm scaffolds, the
+// launches — is described in fs_dev_paths.hpp, each query's own kernels in its .hip file; here is what the host fills in.
+// The common head (fs_dev_paths.hpp reads nothing else of a first-order query): src = the rows' sources, xyz + the source's actor id as
+// bits; lis, lis_object = the listener and its actor; count rows.
 struct PathKHead {
     const float4* src;
     float lis[3];
@@ -433,9 +435,7 @@ struct DirectKParams {
     float radius;
 };
 void launch_direct_paths(const DeviceScene& sc, const DirectKParams& dp, hipStream_t s);
-// fs_reflect.hip (fs_update_reflection_paths): reflect_scan_kernel, a thread per triangle record against every row of the call,
-// appends the filter's survivors to the rows' candidate lists; reflect_confirm_kernel, a wave per row, runs the two legs of every
-// candidate and writes the row and its paths.  h.src on the device; counters [count] zeroed ahead of the scan; cand
+// fs_reflect.hip (fs_update_reflection_paths): scan and confirm.  h.src on the device; counters [count] zeroed ahead of the scan; cand
 // [count][max_candidates] leaf positions; rows [count] and paths [count][max_paths] = the device staging the copy back reads.
 struct ReflectKParams {
     PathKHead h;
@@ -447,15 +447,13 @@ struct ReflectKParams {
     float margin, offset;
 };
 void launch_reflection_paths(const DeviceScene& sc, const ReflectKParams& rp, hipStream_t s);
-// fs_diffract.hip (fs_update_diffraction_paths): diffract_scan_kernel, a thread per triangle record against every row of the call,
-// appends the filter's surviving (leaf position * 4 + edge) to the rows' candidate lists; diffract_confirm_kernel, a wave per row,
-// runs the three legs of every candidate, compacts the confirmed ones into `conf`, merges, ranks and writes the row and its paths.
-// h.src, counters, cand, rows, paths as ReflectKParams; conf [count][max_candidates] records, written and read by the row's wave only.
+// fs_diffract.hip (fs_update_diffraction_paths): scan and confirm; a candidate is leaf position * 4 + edge.  The arrays as
+// ReflectKParams; conf [count][max_candidates] = the confirmed records, written and read by the row's wave only.
 struct DiffractRecord {
     uint32_t length_bits, key;   // key = input index * 4 + edge
     float apex[3], direction[3];
     float detour, cos_bend;
-    uint32_t material, pad;
+    uint32_t material, kept;
 };
 static_assert(sizeof(DiffractRecord) == 48, "DiffractRecord: twelve words");
 struct DiffractKParams {
@@ -470,38 +468,36 @@ struct DiffractKParams {
     float k[FS_MAX_BANDS];   // k_b = 40 f_b / (sound_speed dist_divisor)
 };
 void launch_diffraction_paths(const DeviceScene& sc, const DiffractKParams& dp, hipStream_t s);
-// fs_reflect2.hip (fs_update_reflection2_paths): reflect2_near_kernel, a thread per triangle record against every row of the call,
-// appends the leaf positions of the near triangles to the rows' near lists; reflect2_pair_kernel tests every ordered pair of a row's
-// near list and appends the survivors, as two near-list slots packed 15 + 15 bits, to the rows' candidate lists;
-// reflect2_confirm_kernel, a wave per row, runs the three legs of every candidate, compacts the confirmed ones into `conf`, ranks and
-// writes the row and its paths.  h.src, rows, paths as ReflectKParams; near_counters [count] and counters [count] lie side by side
-// (one clear); near [count][max_near]; cand [count][max_candidates]; conf [count][max_candidates] records, written and read by the
-// row's wave only.
+// What the pair scaffold reads of a second-order query: near_counters [count] and counters [count], zeroed ahead of the scan; near
+// [count][max_near] = the rows' near lists (the scan's codes); cand [count][max_candidates] = the surviving pairs, two near-list slots
+// packed 15 + 15 bits.
+struct NearPairLists {
+    uint32_t* near_counters;
+    uint32_t* counters;
+    uint32_t* near;
+    uint32_t* cand;
+    int32_t max_near, max_candidates;
+};
+// fs_reflect2.hip (fs_update_reflection2_paths): near scan, pair tests and confirm; a near code is a leaf position.  h.src, rows, paths
+// as ReflectKParams; conf as DiffractKParams.
 struct Reflect2Record {
     uint32_t length_bits, a, b;   // a, b = input indices
     float pa[3], pb[3], direction[3];
     uint32_t material[2];
 };
 static_assert(sizeof(Reflect2Record) == 56, "Reflect2Record: fourteen words");
-static_assert(FS_MAX_REFLECTION2_NEAR <= 1 << 15, "a candidate is two near-list slots of 15 bits");
 struct Reflect2KParams {
     PathKHead h;
-    uint32_t* near_counters;
-    uint32_t* counters;
-    uint32_t* near;
-    uint32_t* cand;
     Reflect2Record* conf;
     fs_reflection2_row* rows;
     fs_reflection2_path* paths;
-    int32_t max_paths, max_near, max_candidates;
+    int32_t max_paths;
+    NearPairLists l;
     float max_length, margin, offset;
 };
 void launch_reflection2_paths(const DeviceScene& sc, const Reflect2KParams& rp, hipStream_t s);
-// fs_diffract2.hip (fs_update_diffraction2_paths): diffract2_near_kernel, a thread per triangle record against every row of the call,
-// appends (leaf position * 4 + edge) of the near edge records to the rows' near lists; diffract2_pair_kernel tests every ordered
-// pair (q, p) of a row's near list and appends the survivors, as two near-list slots packed 15 + 15 bits (q high), to the rows'
-// candidate lists; diffract2_confirm_kernel, a wave per row, runs the five legs of every candidate, compacts the confirmed ones into
-// `conf`, merges, ranks and writes the row and its paths.  The arrays as Reflect2KParams.
+// fs_diffract2.hip (fs_update_diffraction2_paths): near scan, pair tests (q, p; q high) and confirm; a near code is leaf position * 4
+// + edge.  The arrays as Reflect2KParams.
 struct Diffract2Record {
     uint32_t length_bits, kp, kq;   // kp, kq = input index * 4 + edge of the listener's and the source's edge record
     float apex[2][3], direction[3];
@@ -510,17 +506,13 @@ struct Diffract2Record {
     uint32_t kept;
 };
 static_assert(sizeof(Diffract2Record) == 76, "Diffract2Record: nineteen words");
-static_assert(FS_MAX_DIFFRACTION2_NEAR <= 1 << 15, "a candidate is two near-list slots of 15 bits");
 struct Diffract2KParams {
     PathKHead h;
-    uint32_t* near_counters;
-    uint32_t* counters;
-    uint32_t* near;
-    uint32_t* cand;
     Diffract2Record* conf;
     fs_diffraction2_row* rows;
     fs_diffraction2_path* paths;
-    int32_t max_paths, max_near, max_candidates;
+    int32_t max_paths;
+    NearPairLists l;
     float margin, max_detour, min_parallel, offset, merge;
     float k[FS_MAX_BANDS];      // k_b = 40 f_b / (sound_speed dist_divisor)
     float lam5[FS_MAX_BANDS];   // lam5_b = 5 sound_speed dist_divisor / f_b

@@ -59,28 +59,20 @@ __global__ __launch_bounds__(kBlock) void reflect_confirm_kernel(DeviceScene sc,
         const float len1 = sqrtf((Dx * Dx + Dy * Dy) + Dz * Dz);
         const float inv1 = 1.0f / len1;
         const float dx = Dx * inv1, dy = Dy * inv1, dz = Dz * inv1;
-        // leg 1 ends at the first triangle that is not an own actor's, and asks that it be the candidate's record: t1 = the distance
+        // leg 1 ends at the first triangle that is not an own actor's, and asks that it be the candidate's record: t = the distance
         // from the leg's start, P = the hit point
-        float t1 = 0.0f, Px = 0.0f, Py = 0.0f, Pz = 0.0f;
-        bool hit = false;
-        (void)path_chain(sc, rp.h, cr.src_object, mine, rp.h.lis[0], rp.h.lis[1], rp.h.lis[2], dx, dy, dz, len1, stack,
-                         [&](int at, float t, float acc, float ox, float oy, float oz, float qx, float qy, float qz) {
-            if (at == leaf) {
-                hit = true;
-                t1 = acc + t;
-                Px = fmaf(t, qx, ox); Py = fmaf(t, qy, oy); Pz = fmaf(t, qz, oz);
-            }
-            return false;
-        });
+        AskLeaf l1{leaf};
+        (void)path_chain(sc, rp.h, cr.src_object, mine, rp.h.lis[0], rp.h.lis[1], rp.h.lis[2], dx, dy, dz, len1, stack, l1);
+        const float Px = l1.Px, Py = l1.Py, Pz = l1.Pz;
         const float ex = s4.x - Px, ey = s4.y - Py, ez = s4.z - Pz;
         const float len2 = sqrtf((ex * ex + ey * ey) + ez * ez);
-        const bool second = mine && hit && len2 != 0.0f;
+        const bool second = mine && l1.hit && len2 != 0.0f;
         const float inv2 = 1.0f / (second ? len2 : 1.0f);
         const float d2x = ex * inv2, d2y = ey * inv2, d2z = ez * inv2;
         // leg 2 is chain(o, d, len) with max_surfaces = 0 and asks for reached (with crossed == 0)
         const bool ok = path_chain(sc, rp.h, cr.src_object, second, fmaf(rp.offset, d2x, Px), fmaf(rp.offset, d2y, Py), fmaf(rp.offset, d2z, Pz),
                                    d2x, d2y, d2z, (len2 - rp.offset) - rp.h.pullback, stack, StopAtHit()) == kChainReached;
-        const float length = t1 + len2;
+        const float length = l1.t + len2;
         if (mine) {
             w[0 * maxc + c] = ok ? __float_as_uint(length) : 0xFFFFFFFFu;
             w[1 * maxc + c] = ok ? __float_as_uint(rec.c.z) : 0xFFFFFFFFu;
@@ -109,8 +101,7 @@ __global__ __launch_bounds__(kBlock) void reflect_confirm_kernel(DeviceScene sc,
         o->direction[0] = __uint_as_float(w[6 * maxc + c]); o->direction[1] = __uint_as_float(w[7 * maxc + c]); o->direction[2] = __uint_as_float(w[8 * maxc + c]);
         o->triangle = w[maxc + c];
         o->material = mat;
-        // the specular gain of the lobe table; a surface without a material applies no factor (apply_segment)
-        const float* g = sc.lobe_gain != nullptr && mat < (uint32_t)sc.num_materials ? sc.lobe_gain + ((size_t)mat * 3 + kLobeSpecular) * B : nullptr;
+        const float* g = specular_gain(sc, mat, B);
 #pragma unroll
         for (int b = 0; b < FS_MAX_BANDS; ++b) o->reflectance[b] = b < B ? (g != nullptr ? g[b] : 1.0f) : 0.0f;
     }

@@ -3,32 +3,20 @@
 // mapping onto the device, in three kernels.
 //   reflect2_near_kernel: the scan scaffold of fs_dev_paths.hpp (scan_records) with step 0 as its filter; a near triangle's code is
 // its leaf position, the row's near list the "candidate list" of the scaffold.
-//   reflect2_pair_kernel: the hot one — near^2 pair tests per row.  A thread holds one near triangle in the role of a in registers
-// (what MT(L, D, a) needs of it that does not depend on b — tv, q, e2.q — included); the row's near list in the role of b streams
-// through LDS in tiles of kPairTile entries.  Each of the tile's threads unpacks one b once — hS, S1, n_b and the record, 16 words —
-// and the inner loop reads entry after entry at one address for the whole wave (an LDS broadcast).  The strict-side test (h1
-// against hL) comes before any divide — it rejects a sixth of the pairs in a closed shoebox — and the rest ends at MT(L, D, a) but
-// for a handful.  A survivor takes a place in the row's candidate list by atomicAdd (the counter keeps counting past the cap) as
-// its two near-list slots, 15 + 15 bits.
-//   The grid is (tile of a, share of the b tiles, row): blockIdx.y strides over the b tiles, kPairSplit ways at most.  With (tile
-// of a, row) alone a call for one source in a 5 000-triangle room is 20 workgroups on a chip of 256 compute units; split 16 ways
-// it is 320.  The near count is known on the device only, so the grid is sized for min(max_near, triangles) and a workgroup
-// beyond the row's near list leaves at once.
-//   reflect2_confirm_kernel: the shape of diffract_confirm_kernel — one wave per source row, kBlock / 64 rows per workgroup, the
-// lanes stride over the row's candidates (at most FS_MAX_REFLECTION2_CANDIDATES / 64 = 16 rounds).  A lane recomputes S1 and D with
-// the pair filter's own code — the same bits — and runs the three legs as chains (path_chain) one after the other; a lane whose
-// candidate has already failed idles along.  A confirmed one takes the next place of the row's list in the call's device staging
-// (ballot and prefix count), written and read by the row's own wave only; the rank is counted over that list by the 96-bit key
-// (length bits, a, b).  Plain vector stores, no sort network.
+//   reflect2_pair_kernel: the hot one — the pair scaffold (pair_records).  The held entry is a near triangle in the role of a (what
+// MT(L, D, a) needs of it that does not depend on b — tv, q, e2.q — included), the streamed one a near triangle in the role of b:
+// hS, S1, n_b and the record, 16 words.  The strict-side test (h1 against hL) comes before any divide — it rejects a sixth of the
+// pairs in a closed shoebox — and the rest ends at MT(L, D, a) but for a handful.
+//   reflect2_confirm_kernel: one wave per source row (confirm_row), the lanes stride over the row's candidates (at most
+// FS_MAX_REFLECTION2_CANDIDATES / 64 = 16 rounds).  A lane recomputes S1 and D with the pair filter's own code — the same bits — and
+// runs the three legs as chains (path_chain) one after the other; a lane whose candidate has already failed idles along.  A
+// confirmed one takes the next place of the row's list in the call's device staging (compact_slot), written and read by the row's
+// own wave only; the rank is counted over that list by the 96-bit key (length bits, a, b).  Plain vector stores, no sort network.
 //   Dynamic LDS of the confirm kernel: the stack rows [stack_rows][kBlock], nothing else.
 #include "fs_dev_paths.hpp"
 
 namespace fs {
 namespace {
-
-constexpr int kPairTile = kBlock;   // entries of b per LDS tile: one per thread
-constexpr int kPairSplit = 16;      // the b tiles of a row are shared among at most this many workgroups per tile of a
-constexpr int kSlotBits = 15;       // a candidate = slot of a << 15 | slot of b
 
 // what the pair filter reads of triangle a: nothing of it depends on b or on S
 struct PairA {
@@ -108,66 +96,42 @@ __device__ __forceinline__ bool pair_filter(const PairA& a, const PairB& b, cons
 }
 
 __global__ __launch_bounds__(kBlock) void reflect2_near_kernel(DeviceScene sc, Reflect2KParams rp) {
-    scan_records(sc, rp.h, rp.near_counters, rp.near, rp.max_near, [&](uint32_t leaf, const TriEnds g, const float4 s4, auto&& emit) {
+    scan_records(sc, rp.h, rp.l.near_counters, rp.l.near, rp.l.max_near, [&](uint32_t leaf, const TriEnds g, const float4 s4, auto&& emit) {
         if (reflect2_near(g, s4, rp.max_length)) emit(leaf);
     });
 }
 
 __global__ __launch_bounds__(kBlock) void reflect2_pair_kernel(DeviceScene sc, Reflect2KParams rp) {
-    __shared__ float4 s_b[4][kPairTile];
-    const int row = (int)blockIdx.z;
-    const uint32_t counted = rp.near_counters[row];
-    if (counted > (uint32_t)rp.max_near || blockIdx.x * (uint32_t)kBlock >= counted) return;   // (the same for the whole workgroup)
-    const int near = (int)counted;
-    const uint32_t* list = rp.near + (size_t)row * rp.max_near;
-    const float4 s4 = rp.h.src[row];
-    const int a_slot = (int)(blockIdx.x * kBlock + threadIdx.x);
-    const bool have_a = a_slot < near;
-    const PairA a = pair_a(tri_ends(sc.tris[list[have_a ? a_slot : 0]], s4, rp.h));
-    const int tiles = (near + kPairTile - 1) / kPairTile;
-#pragma unroll 1
-    for (int t = (int)blockIdx.y; t < tiles; t += (int)gridDim.y) {
-        const int first = t * kPairTile;
-        __syncthreads();   // the tile before has been read
-        if (first + (int)threadIdx.x < near) {
-            const PairB b = pair_b(tri_ends(sc.tris[list[first + (int)threadIdx.x]], s4, rp.h), s4);
-            s_b[0][threadIdx.x] = make_float4(b.S1x, b.S1y, b.S1z, b.hS);
-            s_b[1][threadIdx.x] = make_float4(b.nx, b.ny, b.nz, b.v0x);
-            s_b[2][threadIdx.x] = make_float4(b.v0y, b.v0z, b.e1x, b.e1y);
-            s_b[3][threadIdx.x] = make_float4(b.e1z, b.e2x, b.e2y, b.e2z);
-        }
-        __syncthreads();
-        const int nb = min(kPairTile, near - first);
-        if (!have_a) continue;
-#pragma unroll 1
-        for (int j = 0; j < nb; ++j) {   // (j is the same in every lane: each read below is one address per wave)
-            const float4 b0 = s_b[0][j], b1 = s_b[1][j], b2 = s_b[2][j], b3 = s_b[3][j];
-            const PairB b = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
+    pair_records(
+        rp.h, rp.l, [&](uint32_t leaf, const float4 s4) { return pair_a(tri_ends(sc.tris[leaf], s4, rp.h)); },
+        [&](uint32_t leaf, const float4 s4) {
+            const PairB b = pair_b(tri_ends(sc.tris[leaf], s4, rp.h), s4);
+            return PairRow{make_float4(b.S1x, b.S1y, b.S1z, b.hS), make_float4(b.nx, b.ny, b.nz, b.v0x), make_float4(b.v0y, b.v0z, b.e1x, b.e1y),
+                           make_float4(b.e1z, b.e2x, b.e2y, b.e2z)};
+        },
+        [&](const PairA& a, const PairRow r, const float4) {
+            const PairB b = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w, r.d.x, r.d.y, r.d.z, r.d.w};
             float Dx, Dy, Dz;
-            if (first + j != a_slot && pair_filter(a, b, rp.h.lis, rp.margin, rp.max_length, Dx, Dy, Dz)) {
-                const uint32_t k = atomicAdd(&rp.counters[row], 1u);
-                if (k < (uint32_t)rp.max_candidates) rp.cand[(size_t)row * rp.max_candidates + k] = ((uint32_t)a_slot << kSlotBits) | (uint32_t)(first + j);
-            }
-        }
-    }
+            return pair_filter(a, b, rp.h.lis, rp.margin, rp.max_length, Dx, Dy, Dz);
+        });
 }
 
 __global__ __launch_bounds__(kBlock) void reflect2_confirm_kernel(DeviceScene sc, Reflect2KParams rp) {
     extern __shared__ __attribute__((aligned(16))) int s_dyn[];   // [stack_rows][kBlock]
     int* stack = &s_dyn[threadIdx.x];
-    const ConfirmRow cr = confirm_row(rp.h, rp.counters, rp.cand, rp.max_candidates);
+    const ConfirmRow cr = confirm_row(rp.h, rp.l);
     const int lane = cr.lane, n = cr.n, row = cr.row, B = rp.h.num_bands;
     const float4 s4 = cr.s4;
-    const uint32_t near = cr.row_ok ? rp.near_counters[row] : 0u;
-    const uint32_t* list = rp.near + (size_t)cr.slot * rp.max_near;
-    Reflect2Record* conf = rp.conf + (size_t)cr.slot * rp.max_candidates;
+    const uint32_t near = near_count(cr, rp.l);
+    const uint32_t* list = rp.l.near + (size_t)cr.slot * rp.l.max_near;
+    Reflect2Record* conf = rp.conf + (size_t)cr.slot * rp.l.max_candidates;
     uint32_t found = 0u;
 #pragma unroll 1
     for (int base = 0; base < n; base += 64) {   // (wave-uniform; n > 0 only where the near list is whole and has two entries at least)
         const int c = base + lane;
         const bool mine = c < n;
         const uint32_t code = mine ? cr.list[c] : 0u;
-        const int leafA = (int)list[code >> kSlotBits], leafB = (int)list[code & ((1u << kSlotBits) - 1u)];
+        const int leafA = (int)pair_held(list, code), leafB = (int)pair_streamed(list, code);
         const Tri48 recA = sc.tris[leafA], recB = sc.tris[leafB];
         const PairB pb = pair_b(tri_ends(recB, s4, rp.h), s4);
         float Dx = 1.0f, Dy = 0.0f, Dz = 0.0f;
@@ -176,49 +140,32 @@ __global__ __launch_bounds__(kBlock) void reflect2_confirm_kernel(DeviceScene sc
         const float inv1 = 1.0f / len1;
         const float dx = Dx * inv1, dy = Dy * inv1, dz = Dz * inv1;
         // leg 1 ends at the first triangle that is not an own actor's, and asks that it be a
-        float t1 = 0.0f, PAx = 0.0f, PAy = 0.0f, PAz = 0.0f;
-        bool hit = false;
-        (void)path_chain(sc, rp.h, cr.src_object, mine, rp.h.lis[0], rp.h.lis[1], rp.h.lis[2], dx, dy, dz, len1, stack,
-                         [&](int at, float t, float acc, float ox, float oy, float oz, float qx, float qy, float qz) {
-            if (at == leafA) {
-                hit = true;
-                t1 = acc + t;
-                PAx = fmaf(t, qx, ox); PAy = fmaf(t, qy, oy); PAz = fmaf(t, qz, oz);
-            }
-            return false;
-        });
+        AskLeaf la{leafA};
+        (void)path_chain(sc, rp.h, cr.src_object, mine, rp.h.lis[0], rp.h.lis[1], rp.h.lis[2], dx, dy, dz, len1, stack, la);
         // leg 2, from PA towards the image S1, asks for b
-        const float Ex = pb.S1x - PAx, Ey = pb.S1y - PAy, Ez = pb.S1z - PAz;
+        const float Ex = pb.S1x - la.Px, Ey = pb.S1y - la.Py, Ez = pb.S1z - la.Pz;
         const float len2 = sqrtf((Ex * Ex + Ey * Ey) + Ez * Ez);
-        const bool second = mine && hit && len2 != 0.0f;
+        const bool second = mine && la.hit && len2 != 0.0f;
         const float inv2 = 1.0f / (second ? len2 : 1.0f);
         const float d2x = Ex * inv2, d2y = Ey * inv2, d2z = Ez * inv2;
-        float t2 = 0.0f, PBx = 0.0f, PBy = 0.0f, PBz = 0.0f;
-        hit = false;
-        (void)path_chain(sc, rp.h, cr.src_object, second, fmaf(rp.offset, d2x, PAx), fmaf(rp.offset, d2y, PAy), fmaf(rp.offset, d2z, PAz), d2x, d2y,
-                         d2z, len2 - rp.offset, stack, [&](int at, float t, float acc, float ox, float oy, float oz, float qx, float qy, float qz) {
-            if (at == leafB) {
-                hit = true;
-                t2 = rp.offset + (acc + t);
-                PBx = fmaf(t, qx, ox); PBy = fmaf(t, qy, oy); PBz = fmaf(t, qz, oz);
-            }
-            return false;
-        });
+        AskLeaf lb{leafB};
+        (void)path_chain(sc, rp.h, cr.src_object, second, fmaf(rp.offset, d2x, la.Px), fmaf(rp.offset, d2y, la.Py), fmaf(rp.offset, d2z, la.Pz), d2x,
+                         d2y, d2z, len2 - rp.offset, stack, lb);
         // leg 3 is chain(o, d, len) with max_surfaces = 0 and asks for reached (with crossed == 0)
-        const float ex = s4.x - PBx, ey = s4.y - PBy, ez = s4.z - PBz;
+        const float ex = s4.x - lb.Px, ey = s4.y - lb.Py, ez = s4.z - lb.Pz;
         const float len3 = sqrtf((ex * ex + ey * ey) + ez * ez);
-        const bool third = second && hit && len3 != 0.0f;
+        const bool third = second && lb.hit && len3 != 0.0f;
         const float inv3 = 1.0f / (third ? len3 : 1.0f);
         const float d3x = ex * inv3, d3y = ey * inv3, d3z = ez * inv3;
-        const bool ok = path_chain(sc, rp.h, cr.src_object, third, fmaf(rp.offset, d3x, PBx), fmaf(rp.offset, d3y, PBy), fmaf(rp.offset, d3z, PBz),
+        const bool ok = path_chain(sc, rp.h, cr.src_object, third, fmaf(rp.offset, d3x, lb.Px), fmaf(rp.offset, d3y, lb.Py), fmaf(rp.offset, d3z, lb.Pz),
                                    d3x, d3y, d3z, (len3 - rp.offset) - rp.h.pullback, stack, StopAtHit()) == kChainReached;
         const unsigned long long votes = __ballot(ok);
         if (ok) {
-            Reflect2Record* o = conf + found + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
-            o->length_bits = __float_as_uint((t1 + t2) + len3);
+            Reflect2Record* o = conf + found + compact_slot(votes, lane);
+            o->length_bits = __float_as_uint((la.t + (rp.offset + lb.t)) + len3);
             o->a = __float_as_uint(recA.c.z); o->b = __float_as_uint(recB.c.z);
-            o->pa[0] = PAx; o->pa[1] = PAy; o->pa[2] = PAz;
-            o->pb[0] = PBx; o->pb[1] = PBy; o->pb[2] = PBz;
+            o->pa[0] = la.Px; o->pa[1] = la.Py; o->pa[2] = la.Pz;
+            o->pb[0] = lb.Px; o->pb[1] = lb.Py; o->pb[2] = lb.Pz;
             o->direction[0] = dx; o->direction[1] = dy; o->direction[2] = dz;
             o->material[0] = __float_as_uint(recA.c.y); o->material[1] = __float_as_uint(recB.c.y);
         }
@@ -247,40 +194,25 @@ __global__ __launch_bounds__(kBlock) void reflect2_confirm_kernel(DeviceScene sc
         o->direction[0] = me.direction[0]; o->direction[1] = me.direction[1]; o->direction[2] = me.direction[2];
         o->triangle[0] = me.a; o->triangle[1] = me.b;
         o->material[0] = me.material[0]; o->material[1] = me.material[1];
-        // the two specular gains of the lobe table; a surface without a material applies no factor (apply_segment)
-        const bool lobes = sc.lobe_gain != nullptr;
-        const float* gA = lobes && me.material[0] < (uint32_t)sc.num_materials ? sc.lobe_gain + ((size_t)me.material[0] * 3 + kLobeSpecular) * B : nullptr;
-        const float* gB = lobes && me.material[1] < (uint32_t)sc.num_materials ? sc.lobe_gain + ((size_t)me.material[1] * 3 + kLobeSpecular) * B : nullptr;
+        const float *gA = specular_gain(sc, me.material[0], B), *gB = specular_gain(sc, me.material[1], B);
 #pragma unroll
         for (int b = 0; b < FS_MAX_BANDS; ++b) o->reflectance[b] = b < B ? (gA != nullptr ? gA[b] : 1.0f) * (gB != nullptr ? gB[b] : 1.0f) : 0.0f;
     }
     zero_tail(out, lane, returned, rp.max_paths);
     if (lane == 0) {
-        const bool near_overflow = near > (uint32_t)rp.max_near;
         fs_reflection2_row* r = rp.rows + row;
         r->near = near;
         r->candidates = cr.cands;
         r->found = found;
         r->returned = returned;
-        r->flags = near_overflow ? FS_REFLECTION2_NEAR_OVERFLOW : (cr.overflow ? FS_REFLECTION2_OVERFLOW : 0u);
+        r->flags = pair_row_flags(cr, rp.l, near, FS_REFLECTION2_NEAR_OVERFLOW, FS_REFLECTION2_OVERFLOW);
     }
 }
 
 }  // namespace
 
-void launch_reflection2_paths(const DeviceScene& sc_in, const Reflect2KParams& rp, hipStream_t s) {
-    if (rp.h.count <= 0) return;
-    const uint32_t blocks = row_blocks(rp.h.count);
-    DeviceScene sc = sc_in;
-    if (!attach_deep(sc, blocks)) return;
-    if (sc.num_tris > 0) {
-        hipLaunchKernelGGL(reflect2_near_kernel, dim3((uint32_t)((sc.num_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, sc, rp);
-        const uint32_t a_tiles = (uint32_t)((std::min(sc.num_tris, rp.max_near) + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(reflect2_pair_kernel, dim3(a_tiles, std::min(a_tiles, (uint32_t)kPairSplit), (uint32_t)rp.h.count), dim3(kBlock), 0, s, sc, rp);
-    }
-    const size_t lds = stack_bytes(sc);
-    allow_lds(reflect2_confirm_kernel, lds);
-    hipLaunchKernelGGL(reflect2_confirm_kernel, dim3(blocks), dim3(kBlock), lds, s, sc, rp);
+void launch_reflection2_paths(const DeviceScene& sc, const Reflect2KParams& rp, hipStream_t s) {
+    launch_near_pair_confirm(reflect2_near_kernel, reflect2_pair_kernel, reflect2_confirm_kernel, sc, rp, 1, rp.l.max_near, 0, s);   // a triangle: one near entry
 }
 
 }  // namespace fs

@@ -197,82 +197,49 @@ public:
             Check(fs_update_direct_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_DIRECT_BATCH), P, Out.data() + i));
         return Out;
     }
-    // the first-order specular reflections of every active source: Rows[i] and Paths[i * MaxPaths .. ) for ActiveSources[i]
-    // (fs_update_reflection_paths; MaxPaths = P->max_paths, the default's without P; one call per FS_MAX_REFLECTION_BATCH sources)
+    // The four rows-and-paths queries of every active source: Rows[i] and Paths[i * MaxPaths .. ) for ActiveSources[i]; MaxPaths =
+    // P->max_paths, the default's without P; one call per FS_MAX_*_BATCH sources.
+    // the first-order specular reflections (fs_update_reflection_paths)
     struct ReflectionPaths { int32_t MaxPaths = 0; std::vector<fs_reflection_row> Rows; std::vector<fs_reflection_path> Paths; };
     ReflectionPaths UpdateReflectionPaths(const fs_reflection_params* P = nullptr) {
-        fs_reflection_params Def;
-        fs_reflection_params_default(&Def);
-        ReflectionPaths Out;
-        Out.MaxPaths = P ? P->max_paths : Def.max_paths;
-        if (ActiveSources.empty()) return Out;
-        Out.Rows.resize(ActiveSources.size());
-        Out.Paths.resize(ActiveSources.size() * (size_t)std::min(std::max(Out.MaxPaths, 1), FS_MAX_REFLECTIONS));   // (a bad max_paths is refused below)
-        Commit();
-        std::vector<fs_source> H;
-        for (auto* s : ActiveSources) H.push_back(s->Handle_);
-        for (size_t i = 0; i < H.size(); i += FS_MAX_REFLECTION_BATCH)
-            Check(fs_update_reflection_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_REFLECTION_BATCH), P,
-                                             Out.Rows.data() + i, Out.Paths.data() + i * (size_t)Out.MaxPaths));
-        return Out;
+        return UpdateRowsPaths<ReflectionPaths>(P, fs_reflection_params_default, fs_update_reflection_paths, FS_MAX_REFLECTIONS, FS_MAX_REFLECTION_BATCH);
     }
-    // the first-order edge diffraction of every active source: Rows[i] and Paths[i * MaxPaths .. ) for ActiveSources[i]
-    // (fs_update_diffraction_paths; MaxPaths = P->max_paths, the default's without P; one call per FS_MAX_DIFFRACTION_BATCH sources)
+    // the first-order edge diffraction (fs_update_diffraction_paths)
     struct DiffractionPaths { int32_t MaxPaths = 0; std::vector<fs_diffraction_row> Rows; std::vector<fs_diffraction_path> Paths; };
     DiffractionPaths UpdateDiffractionPaths(const fs_diffraction_params* P = nullptr) {
-        fs_diffraction_params Def;
-        fs_diffraction_params_default(&Def);
-        DiffractionPaths Out;
-        Out.MaxPaths = P ? P->max_paths : Def.max_paths;
-        if (ActiveSources.empty()) return Out;
-        Out.Rows.resize(ActiveSources.size());
-        Out.Paths.resize(ActiveSources.size() * (size_t)std::min(std::max(Out.MaxPaths, 1), FS_MAX_DIFFRACTIONS));   // (a bad max_paths is refused below)
-        Commit();
-        std::vector<fs_source> H;
-        for (auto* s : ActiveSources) H.push_back(s->Handle_);
-        for (size_t i = 0; i < H.size(); i += FS_MAX_DIFFRACTION_BATCH)
-            Check(fs_update_diffraction_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_DIFFRACTION_BATCH), P,
-                                              Out.Rows.data() + i, Out.Paths.data() + i * (size_t)Out.MaxPaths));
-        return Out;
+        return UpdateRowsPaths<DiffractionPaths>(P, fs_diffraction_params_default, fs_update_diffraction_paths, FS_MAX_DIFFRACTIONS, FS_MAX_DIFFRACTION_BATCH);
     }
-    // the second-order specular reflections of every active source: Rows[i] and Paths[i * MaxPaths .. ) for ActiveSources[i]
-    // (fs_update_reflection2_paths; MaxPaths = P->max_paths, the default's without P; one call per FS_MAX_REFLECTION2_BATCH sources)
+    // the second-order specular reflections (fs_update_reflection2_paths)
     struct Reflection2Paths { int32_t MaxPaths = 0; std::vector<fs_reflection2_row> Rows; std::vector<fs_reflection2_path> Paths; };
     Reflection2Paths UpdateReflection2Paths(const fs_reflection2_params* P = nullptr) {
-        fs_reflection2_params Def;
-        fs_reflection2_params_default(&Def);
-        Reflection2Paths Out;
-        Out.MaxPaths = P ? P->max_paths : Def.max_paths;
-        if (ActiveSources.empty()) return Out;
-        Out.Rows.resize(ActiveSources.size());
-        Out.Paths.resize(ActiveSources.size() * (size_t)std::min(std::max(Out.MaxPaths, 1), FS_MAX_REFLECTION2_PATHS));   // (a bad max_paths is refused below)
-        Commit();
-        std::vector<fs_source> H;
-        for (auto* s : ActiveSources) H.push_back(s->Handle_);
-        for (size_t i = 0; i < H.size(); i += FS_MAX_REFLECTION2_BATCH)
-            Check(fs_update_reflection2_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_REFLECTION2_BATCH), P,
-                                              Out.Rows.data() + i, Out.Paths.data() + i * (size_t)Out.MaxPaths));
-        return Out;
+        return UpdateRowsPaths<Reflection2Paths>(P, fs_reflection2_params_default, fs_update_reflection2_paths, FS_MAX_REFLECTION2_PATHS,
+                                                 FS_MAX_REFLECTION2_BATCH);
     }
-    // the diffraction round thick obstacles of every active source: Rows[i] and Paths[i * MaxPaths .. ) for ActiveSources[i]
-    // (fs_update_diffraction2_paths; MaxPaths = P->max_paths, the default's without P; one call per FS_MAX_DIFFRACTION2_BATCH sources)
+    // the diffraction round thick obstacles (fs_update_diffraction2_paths)
     struct Diffraction2Paths { int32_t MaxPaths = 0; std::vector<fs_diffraction2_row> Rows; std::vector<fs_diffraction2_path> Paths; };
     Diffraction2Paths UpdateDiffraction2Paths(const fs_diffraction2_params* P = nullptr) {
-        fs_diffraction2_params Def;
-        fs_diffraction2_params_default(&Def);
-        Diffraction2Paths Out;
+        return UpdateRowsPaths<Diffraction2Paths>(P, fs_diffraction2_params_default, fs_update_diffraction2_paths, FS_MAX_DIFFRACTION2_PATHS,
+                                                  FS_MAX_DIFFRACTION2_BATCH);
+    }
+private:
+    template <typename Result, typename Params, typename Row, typename Path>
+    Result UpdateRowsPaths(const Params* P, void (*Defaults)(Params*), int (*Update)(fs_context*, const fs_source*, int32_t, const Params*, Row*, Path*),
+                           int MaxPathsCap, size_t Batch) {
+        Params Def;
+        Defaults(&Def);
+        Result Out;
         Out.MaxPaths = P ? P->max_paths : Def.max_paths;
         if (ActiveSources.empty()) return Out;
         Out.Rows.resize(ActiveSources.size());
-        Out.Paths.resize(ActiveSources.size() * (size_t)std::min(std::max(Out.MaxPaths, 1), FS_MAX_DIFFRACTION2_PATHS));   // (a bad max_paths is refused below)
+        Out.Paths.resize(ActiveSources.size() * (size_t)std::min(std::max(Out.MaxPaths, 1), MaxPathsCap));   // (a bad max_paths is refused below)
         Commit();
         std::vector<fs_source> H;
         for (auto* s : ActiveSources) H.push_back(s->Handle_);
-        for (size_t i = 0; i < H.size(); i += FS_MAX_DIFFRACTION2_BATCH)
-            Check(fs_update_diffraction2_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_DIFFRACTION2_BATCH), P,
-                                               Out.Rows.data() + i, Out.Paths.data() + i * (size_t)Out.MaxPaths));
+        for (size_t i = 0; i < H.size(); i += Batch)
+            Check(Update(Ctx_, H.data() + i, (int32_t)std::min(H.size() - i, Batch), P, Out.Rows.data() + i, Out.Paths.data() + i * (size_t)Out.MaxPaths));
         return Out;
     }
+public:
     // fs_set_pipelining (0 off, 1, 2): Tick streams the sources instead of batching them
     void SetPipelining(int Depth) { Check(fs_set_pipelining(Ctx_, Depth)); Streamed_ = Depth != 0; }
     // fs_set_frames_per_launch (1 .. 4): consecutive streamed frames share a launch (each keeps its seed, buffer and IR)

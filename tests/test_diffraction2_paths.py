@@ -511,6 +511,61 @@ def test_thick_box(pkg, oracle_mod, n):
     ctx.close()
 
 
+# ---- near lists that end at the edges of the pair kernel's tiles ---------------------------------------------------------
+# The pair kernel streams a row's near list through LDS in tiles of 256 entries, shared among at most 16 workgroups per tile of q:
+# a list of 255, 256 and 257 entries ends one entry either side of a tile's edge, one of 4100 has 17 tiles (one workgroup takes two).
+TILE_EDGE_NEAR = (255, 256, 257, 4100)
+_tile_edges = {}
+
+
+def sparse_field(count):
+    """count triangles of 1 cm, 11 cm apart above the thick box, each turned a little further about z: their edges are parallel to
+    no rim, so the paths stay the thick box's"""
+    k = np.arange(count)
+    v0 = np.stack([250.0 + 11.0 * (k % 48), 20.0 + 11.0 * (k // 48), np.full(count, 260.0)], axis=1)
+    a = 0.3 + 0.9 * k / max(count, 1)
+    e1 = np.stack([np.cos(a), np.sin(a), np.zeros(count)], axis=1)
+    e2 = np.stack([-np.sin(a), np.cos(a), np.zeros(count)], axis=1)
+    return np.stack([v0, v0 + e1, v0 + e2], axis=1).astype(np.float32)
+
+
+def tile_edge_case(pkg, oracle_mod, near):
+    """(world, max_detour, the call's two arrays by the restatement): the thick box with a sparse field of more edge records than
+    asked for, and the max_detour that lies between the near bounds of record number `near` and the next — computed once"""
+    if near not in _tile_edges:
+        w = box_world(extra=[(sparse_field(near // 3 + 24), OPAQUE, 3)])
+        y = Diffraction2(oracle_mod, w)
+        S32, L32 = np.asarray(SRC, np.float32), np.asarray(LIS, np.float32)
+        with np.errstate(all="ignore"):
+            rS, rL, reach, g = S32[None, :] - y.ra, L32[None, :] - y.ra, np.sqrt(y.rww), S32 - L32
+            need = np.sort(((np.sqrt(dot(rS, rS)) + np.sqrt(dot(rL, rL))) - (reach + reach)) - np.sqrt(dot(g, g)))
+        assert need.dtype == np.float32 and len(need) > near and need[near] - need[near - 1] > 1e-2, "no max_detour cuts the list there"
+        detour = float(need[near - 1]) + 0.5 * float(need[near] - need[near - 1])
+        assert detour > TOP["detour"] + 1.0
+        _tile_edges[near] = w, detour, y.expect(pkg, [SRC], LIS, max_detour=detour)
+    return _tile_edges[near]
+
+
+@pytest.mark.parametrize("near", TILE_EDGE_NEAR)
+def test_tile_edge_preconditions(pkg, oracle_mod, near):
+    """the restatement alone: the near list has the length asked for, the candidates stay a handful and paths are found"""
+    rows, paths = tile_edge_case(pkg, oracle_mod, near)[2]
+    assert rows[0]["near"] == near and 0 < rows[0]["candidates"] <= 64 and rows[0]["returned"] > 0 and rows[0]["flags"] == 0
+    assert np.all(paths[0]["length"][:rows[0]["returned"]] > 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("near", TILE_EDGE_NEAR)
+def test_near_list_at_tile_edges(pkg, oracle_mod, near):
+    w, detour, want = tile_edge_case(pkg, oracle_mod, near)
+    ctx = w.context(pkg)
+    ctx.set_listener(LIS)
+    got = ctx.diffraction2_paths(place(ctx, [SRC]), max_detour=detour)
+    assert_equal(got, want, f"near list of {near}")
+    assert got[0][0]["near"] == near and got[0][0]["returned"] > 0
+    ctx.close()
+
+
 BLOCKERS = {   # a small quad across each leg of the path over the top (apexes at y = 222 and 235, z = 200)
     "leg 1": quad_grid((400.0, 150.0, 150.0), (0.0, 150.0, 0.0), (0.0, 0.0, 60.0), 1),       # between S and the near rim, across x = 400
     "leg 2": quad_grid((449.95, 210.0, 200.05), (0.0, 30.0, 0.0), (0.0, 0.0, 10.0), 1),       # a lip standing on the near rim, off the face

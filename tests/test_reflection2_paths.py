@@ -359,6 +359,48 @@ def test_shoebox(pkg, oracle_mod, n):
     ctx.close()
 
 
+# ---- near lists that end at the edges of the pair kernel's tiles ---------------------------------------------------------
+# The pair kernel streams a row's near list through LDS in tiles of 256 entries, shared among at most 16 workgroups per tile of a:
+# a list of 255, 256 and 257 entries ends one entry either side of a tile's edge, one of 4100 has 17 tiles (one workgroup takes two).
+TILE_EDGE_NEAR = (255, 256, 257, 4100)
+_tile_edges = {}
+
+
+def sparse_field(count):
+    """count triangles of 1 cm, 12 cm apart under the ceiling: every one is near (max_length = FAR), the reflectors stay the walls"""
+    k = np.arange(count)
+    v0 = np.stack([60.0 + 12.0 * (k % 72), 40.0 + 12.0 * (k // 72), np.full(count, 285.0)], axis=1)
+    return np.stack([v0, v0 + [1.0, 0.0, 0.0], v0 + [0.0, 1.0, 0.0]], axis=1).astype(np.float32)
+
+
+def tile_edge_case(pkg, oracle_mod, near):
+    """(world, the call's two arrays by the restatement) of the shoebox with near - 12 triangles of the sparse field — computed once"""
+    if near not in _tile_edges:
+        w = shoebox_world([(sparse_field(near - 12), OPAQUE, 3)])
+        _tile_edges[near] = w, Reflection2(oracle_mod, w).expect(pkg, [SRC2], LIS2, max_paths=32, max_length=FAR)
+    return _tile_edges[near]
+
+
+@pytest.mark.parametrize("near", TILE_EDGE_NEAR)
+def test_tile_edge_preconditions(pkg, oracle_mod, near):
+    """the restatement alone: the near list has the length asked for, the candidates stay a handful and paths are found"""
+    rows, paths = tile_edge_case(pkg, oracle_mod, near)[1]
+    assert rows[0]["near"] == near and 0 < rows[0]["candidates"] <= 64 and rows[0]["returned"] > 0 and rows[0]["flags"] == 0
+    assert np.all(paths[0]["length"][:rows[0]["returned"]] > 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("near", TILE_EDGE_NEAR)
+def test_near_list_at_tile_edges(pkg, oracle_mod, near):
+    w, want = tile_edge_case(pkg, oracle_mod, near)
+    ctx = w.context(pkg)
+    ctx.set_listener(LIS2)
+    got = ctx.reflection2_paths(place(ctx, [SRC2]), max_paths=32, max_length=FAR)
+    assert_equal(got, want, f"near list of {near}")
+    assert got[0][0]["near"] == near and got[0][0]["returned"] > 0
+    ctx.close()
+
+
 @pytest.mark.gpu
 def test_room_centre_equal_lengths(pkg, oracle_mod):
     """source and listener at the centre: the paths come in groups of one length, the rank within them is decided by (a, b)"""
