@@ -460,6 +460,23 @@ class Context:
         return self._rows_and_paths(self.lib.fs_update_diffraction2_paths, _capi.default_diffraction2_params(**params), self.DIFFRACTION2_ROW_DTYPE,
                                     self.DIFFRACTION2_DTYPE, sources)
 
+    # ---- the audio callbacks: what the three *_process_batch mirrors share ----
+    def _callback_open(self, sources, blocks, frames, want_out, want_mix):
+        """the opening of a callback: (handles, count, blocks [count][frame_size * 2], out or None, mix or None); frames = the
+        frame size each initialised source was given"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        count = int(srcs.shape[0])
+        a = np.ascontiguousarray(blocks, dtype=np.float32).reshape(count, -1) if count else np.zeros((0, 0), np.float32)
+        if count and int(srcs[0]) in frames and a.shape[1] != 2 * frames[int(srcs[0])]:
+            raise ValueError("every audio block must hold frame_size * 2 interleaved samples")
+        return srcs, count, a, np.empty_like(a) if want_out else None, np.empty(a.shape[1], np.float32) if want_mix else None
+
+    @staticmethod
+    def _callback_close(*results):
+        """the close: what was asked for (not None) — alone, or as a tuple when there is more than one"""
+        got = tuple(x for x in results if x is not None)
+        return got if len(got) > 1 else got[0]
+
     # ---- direct sound on the audio thread: fractional delay + band FIR for all sources of a callback ----
     RENDER_TARGET_DTYPE = np.dtype([("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,))])
 
@@ -479,8 +496,8 @@ class Context:
 
     def direct_render_init(self, src, frame_size=1024, taps=255, max_delay_seconds=1.0):
         self.check(self.lib.fs_direct_render_init(self.h, src, int(frame_size), int(taps), float(max_delay_seconds)))
-        self._dr_shape = getattr(self, "_dr_shape", {})
-        self._dr_shape[src] = (int(frame_size), int(taps))
+        self._dr_frame = getattr(self, "_dr_frame", {})
+        self._dr_frame[src] = int(frame_size)
 
     def direct_render_release(self, src):
         self.check(self.lib.fs_direct_render_release(self.h, src))
@@ -489,12 +506,7 @@ class Context:
         """the direct sound of several sources as one set of launches (include/frequensee.h fs_direct_render_process_batch):
         blocks [count][frame_size * 2], targets a RENDER_TARGET_DTYPE array or (delay, band_gain) pairs -> out
         [count][frame_size * 2] (want_out), mix [frame_size * 2] (want_mix), or the pair (out, mix)"""
-        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
-        count = int(srcs.shape[0])
-        a = np.ascontiguousarray(blocks, dtype=np.float32).reshape(count, -1) if count else np.zeros((0, 0), np.float32)
-        shapes = getattr(self, "_dr_shape", {})
-        if count and int(srcs[0]) in shapes and a.shape[1] != 2 * shapes[int(srcs[0])][0]:
-            raise ValueError("every audio block must hold frame_size * 2 interleaved samples")
+        srcs, count, a, out, mix = self._callback_open(sources, blocks, getattr(self, "_dr_frame", {}), want_out, want_mix)
         if isinstance(targets, np.ndarray) and targets.dtype == self.RENDER_TARGET_DTYPE:
             t = np.ascontiguousarray(targets).reshape(-1)
         else:
@@ -505,13 +517,9 @@ class Context:
                 t[i]["band_gain"][:g.shape[0]] = g
         if t.shape[0] != count:
             raise ValueError("targets must have one entry per source")
-        out = np.empty_like(a) if want_out else None
-        mix = np.empty(a.shape[1], np.float32) if want_mix else None
         self.check(self.lib.fs_direct_render_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data, t.ctypes.data,
                                                            out.ctypes.data if want_out else None, mix.ctypes.data if want_mix else None))
-        if want_out and want_mix:
-            return out, mix
-        return out if want_out else mix
+        return self._callback_close(out, mix)
 
     # ---- early reflections on the audio thread: a bank of delayed, filtered, panned voices per source ----
     REFLECTION_VOICE_DTYPE = np.dtype([("key", np.uint32), ("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,)),
@@ -520,8 +528,8 @@ class Context:
 
     def reflection_render_init(self, src, frame_size=1024, taps=255, voices=32, max_delay_seconds=1.0):
         self.check(self.lib.fs_reflection_render_init(self.h, src, int(frame_size), int(taps), int(voices), float(max_delay_seconds)))
-        self._rr_shape = getattr(self, "_rr_shape", {})
-        self._rr_shape[src] = (int(frame_size), int(taps))
+        self._rr_frame = getattr(self, "_rr_frame", {})
+        self._rr_frame[src] = int(frame_size)
 
     def reflection_render_release(self, src):
         self.check(self.lib.fs_reflection_render_release(self.h, src))
@@ -532,12 +540,7 @@ class Context:
         REFLECTION_VOICE_DTYPE array or (key, delay, band_gain, channel_gain) tuples; stride = the row length handed to the library
         (default: the longest list, at least 1) -> (out [count][frame_size * 2] (want_out), mix [frame_size * 2] (want_mix), rows
         [count] REFLECTION_RENDER_ROW_DTYPE); what was not asked for is left out of the tuple"""
-        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
-        count = int(srcs.shape[0])
-        a = np.ascontiguousarray(blocks, dtype=np.float32).reshape(count, -1) if count else np.zeros((0, 0), np.float32)
-        shapes = getattr(self, "_rr_shape", {})
-        if count and int(srcs[0]) in shapes and a.shape[1] != 2 * shapes[int(srcs[0])][0]:
-            raise ValueError("every audio block must hold frame_size * 2 interleaved samples")
+        srcs, count, a, out, mix = self._callback_open(sources, blocks, getattr(self, "_rr_frame", {}), want_out, want_mix)
         if len(voices) != count:
             raise ValueError("voices must have one list per source")
         if stride is None:
@@ -558,13 +561,11 @@ class Context:
                 table[i, e]["delay"] = delay
                 table[i, e]["band_gain"][:g.shape[0]] = g
                 table[i, e]["channel_gain"] = chan
-        out = np.empty_like(a) if want_out else None
-        mix = np.empty(a.shape[1], np.float32) if want_mix else None
         rows = np.zeros(count, dtype=self.REFLECTION_RENDER_ROW_DTYPE)
         self.check(self.lib.fs_reflection_render_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data, table.ctypes.data,
                                                                counts.ctypes.data, stride, out.ctypes.data if want_out else None,
                                                                mix.ctypes.data if want_mix else None, rows.ctypes.data))
-        return tuple(x for x, want in ((out, want_out), (mix, want_mix), (rows, True)) if want)
+        return self._callback_close(out, mix, rows)
 
     # ---- row f2: reverb plugin convolution ----
     def reverb_init(self, src, frame_size=1024):
@@ -587,26 +588,17 @@ class Context:
         """the callbacks of several sources as one set of launches (include/frequensee.h fs_reverb_process_batch):
         blocks [count][frame_size * 2] -> out [count][frame_size * 2] (want_out), mix [frame_size * 2] (want_mix: the fp32 sum of
         the outputs in list order), or the pair (out, mix) when both are asked for"""
-        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
-        count = int(srcs.shape[0])
-        a = np.ascontiguousarray(blocks, dtype=np.float32).reshape(count, -1) if count else np.zeros((0, 0), np.float32)
-        frames = getattr(self, "_rev_frame", {})
-        if count and int(srcs[0]) in frames and a.shape[1] != 2 * frames[int(srcs[0])]:
-            raise ValueError("every audio block must hold frame_size * 2 interleaved samples")
+        srcs, count, a, out, mix = self._callback_open(sources, blocks, getattr(self, "_rev_frame", {}), want_out, want_mix)
         on = None
         if apply is not None:
             on = np.ascontiguousarray([1 if x else 0 for x in apply], dtype=np.int32)
             if on.shape[0] != count:
                 raise ValueError("apply must have one entry per source")
-        out = np.empty_like(a) if want_out else None
-        mix = np.empty(a.shape[1], np.float32) if want_mix else None
         self.check(self.lib.fs_reverb_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data,
                                                     out.ctypes.data if want_out else None, on.ctypes.data if on is not None else None,
                                                     _capi.REVERB_LITERAL_TAIL if literal_tail else 0,
                                                     mix.ctypes.data if want_mix else None))
-        if want_out and want_mix:
-            return out, mix
-        return out if want_out else mix
+        return self._callback_close(out, mix)
 
     def reverb_release(self, src):
         self.check(self.lib.fs_reverb_release(self.h, src))

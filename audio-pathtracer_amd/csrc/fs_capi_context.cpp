@@ -164,8 +164,7 @@ void free_source(fs_context* ctx, Source* s) {
         if (s->d_ring) (void)hipFree(s->d_ring);
         if (s->d_fade_from) (void)hipFree(s->d_fade_from);
         if (s->d_fade_to) (void)hipFree(s->d_fade_to);
-        if (s->d_dr) (void)hipFree(s->d_dr);
-        if (s->d_rr) (void)hipFree(s->d_rr);
+        for (RenderSetup* r : {&s->dr, &s->rr}) if (r->d) (void)hipFree(r->d);
         if (s->d_dir) (void)hipFree(s->d_dir);   // (the callers have synchronised the compute stream)
     }
     delete s;
@@ -655,12 +654,7 @@ int fs_context_destroy(fs_context* ctx) {
         for (float2* w : ctx->d_rev_tw) if (w) (void)hipFree(w);
         for (PathStaging* st : {&ctx->direct_stage, &ctx->reflect_stage, &ctx->diffract_stage, &ctx->reflect2_stage, &ctx->diffract2_stage}) st->release();
         if (ctx->d_direct_off) (void)hipFree(ctx->d_direct_off);
-        if (ctx->h_rev_stage) (void)hipHostFree(ctx->h_rev_stage);
-        if (ctx->d_rev_stage) (void)hipFree(ctx->d_rev_stage);
-        if (ctx->h_dr_stage) (void)hipHostFree(ctx->h_dr_stage);
-        if (ctx->d_dr_stage) (void)hipFree(ctx->d_dr_stage);
-        if (ctx->h_rr_stage) (void)hipHostFree(ctx->h_rr_stage);
-        if (ctx->d_rr_stage) (void)hipFree(ctx->d_rr_stage);
+        for (CallbackStage* st : {&ctx->rev_stage, &ctx->dr_stage, &ctx->rr_stage}) st->release();
         for (const auto& t : ctx->dr_tables) if (t.d) (void)hipFree(t.d);
         if (ctx->d_batch) (void)hipFree(ctx->d_batch);
         if (ctx->d_build) (void)hipFree(ctx->d_build);

@@ -45,31 +45,6 @@ void band_kernels(int sample_rate, const std::vector<double>& e, int B, int T, f
 
 bool taps_ok(int32_t taps) { return direct_render_taps_ok(taps); }
 
-// The staging of one callback (fs_context::h_dr_stage / d_dr_stage), every block 256-byte aligned
-struct DrStageLayout {
-    size_t items, in, up_bytes;              // host and device, the same offsets: what goes up in one copy
-    size_t h_out, h_mix, host_bytes;         // host: what comes back
-    size_t d_plans, d_out, d_mix, dev_bytes; // device: out | mix adjacent, one copy back
-};
-size_t dr_align(size_t b) { return (b + 255) & ~(size_t)255; }
-DrStageLayout dr_stage_layout(int count, int frame) {
-    const size_t rows = sizeof(float) * 2 * (size_t)frame * (size_t)count, row = sizeof(float) * 2 * (size_t)frame;
-    DrStageLayout l;
-    l.items = 0;
-    l.in = dr_align(sizeof(DirectRenderItem) * (size_t)count);
-    l.up_bytes = l.in + rows;
-    l.h_out = dr_align(l.up_bytes);
-    l.h_mix = l.h_out + rows;   // (adjacent to out)
-    l.host_bytes = l.h_mix + row;
-    l.d_plans = dr_align(l.up_bytes);
-    l.d_out = l.d_plans + dr_align(sizeof(DirectRenderPlan) * (size_t)count);
-    l.d_mix = l.d_out + rows;
-    l.dev_bytes = l.d_mix + row;
-    return l;
-}
-
-size_t dr_state_bytes(const Source* s) { return kDirectRenderHeader + sizeof(float) * 2 * (size_t)s->dr_ring; }
-
 }  // namespace
 
 namespace fsi {
@@ -91,6 +66,57 @@ int direct_render_table_for(fs_context* ctx, int taps, const float** out) {
     if (err != hipSuccess) { (void)hipFree(d); return ctx->hip_fail(err, "hipMemcpy (band kernels)"); }
     ctx->dr_tables.push_back({taps, e, d});
     *out = d;
+    return FS_OK;
+}
+
+int render_setup(fs_context* ctx, RenderSetup& r, size_t header, int frame, int taps, double d_max, double need) {
+    unsigned ring = 1;
+    while ((double)ring < need) ring <<= 1;
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    const float* table = nullptr;
+    const int rc = direct_render_table_for(ctx, taps, &table);
+    if (rc) return rc;
+    FS_HIP(ctx, hipStreamSynchronize(ctx->rev_stream));
+    if (r.d) (void)hipFree(r.d);
+    r = RenderSetup{nullptr, frame, taps, (int)d_max, ring, table};
+    const size_t bytes = header + sizeof(float) * 2 * (size_t)ring;
+    FS_HIP(ctx, hipMalloc((void**)&r.d, bytes));
+    FS_HIP(ctx, hipMemsetAsync(r.d, 0, bytes, ctx->rev_stream));
+    return FS_OK;
+}
+
+int render_clear(fs_context* ctx, const RenderSetup& r, size_t header) {
+    if (r.d && ctx->device_ok) {
+        FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+        FS_HIP(ctx, hipMemsetAsync(r.d, 0, header + sizeof(float) * 2 * (size_t)r.ring, ctx->rev_stream));
+    }
+    return FS_OK;
+}
+
+Source* render_row(fs_context* ctx, fs_source h, RenderSetup Source::*which, const char* no_setup, const Source* first, int* rc) {
+    Source* s = get_source(ctx, h);
+    if (!s) *rc = ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    else if (!(s->*which).d) *rc = ctx->fail(FS_ERR_INVALID_ARGUMENT, no_setup);
+    else if (first && ((s->*which).frame != (first->*which).frame || (s->*which).taps != (first->*which).taps))
+        *rc = ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size and one tap count");
+    else *rc = FS_OK;
+    return *rc ? nullptr : s;
+}
+
+int render_aim_check(fs_context* ctx, const char* whose, float delay, const float* band_gain, const RenderSetup& r) {
+    if (!std::isfinite(delay) || !(delay >= 0.0f) || delay * (float)ctx->cfg.sample_rate > (float)r.max_delay)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, std::string("a ") + whose + "'s delay is negative, not finite or beyond the source's max delay");
+    for (int b = 0; b < ctx->cfg.num_bands; ++b)
+        if (!std::isfinite(band_gain[b]) || !(band_gain[b] >= 0.0f))
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, std::string("a ") + whose + "'s band gain is negative or not finite");
+    return FS_OK;
+}
+
+int render_no_duplicates(fs_context* ctx, const std::vector<Source*>& srcs) {
+    std::vector<Source*> sorted(srcs);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a source appears twice in the batch");
     return FS_OK;
 }
 
@@ -120,34 +146,14 @@ int fs_direct_render_init(fs_context* ctx, fs_source h, int32_t frame_size, int3
     const double need = d_max + (double)taps + 1.0 + (double)frame_size;
     if (need > 1048576.0)
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_direct_render_init: max delay + taps + 1 + frame size exceed 1 048 576 samples");
-    unsigned ring = 1;
-    while ((double)ring < need) ring <<= 1;
-    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    const float* table = nullptr;
-    const int rc = direct_render_table_for(ctx, taps, &table);
-    if (rc) return rc;
-    FS_HIP(ctx, hipStreamSynchronize(ctx->rev_stream));
-    if (s->d_dr) (void)hipFree(s->d_dr);
-    s->d_dr = nullptr;
-    s->dr_frame = frame_size;
-    s->dr_taps = taps;
-    s->dr_max_delay = (int)d_max;
-    s->dr_ring = ring;
-    s->dr_table = table;
-    FS_HIP(ctx, hipMalloc((void**)&s->d_dr, dr_state_bytes(s)));
-    FS_HIP(ctx, hipMemsetAsync(s->d_dr, 0, dr_state_bytes(s), ctx->rev_stream));
-    return FS_OK;
+    return render_setup(ctx, s->dr, kDirectRenderHeader, frame_size, taps, d_max, need);
 }
 
 int fs_direct_render_release(fs_context* ctx, fs_source h) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     Source* s = get_source(ctx, h);
     if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-    if (s->d_dr && ctx->device_ok) {   // history := 0, not primed
-        FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
-        FS_HIP(ctx, hipMemsetAsync(s->d_dr, 0, dr_state_bytes(s), ctx->rev_stream));
-    }
-    return FS_OK;
+    return render_clear(ctx, s->dr, kDirectRenderHeader);   // history := 0, not primed
 }
 
 int fs_direct_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in,
@@ -161,69 +167,42 @@ int fs_direct_render_process_batch(fs_context* ctx, const fs_source* sources, in
     const float fs_f = (float)ctx->cfg.sample_rate;
     std::vector<Source*> srcs((size_t)count);
     for (int32_t i = 0; i < count; ++i) {
-        Source* s = srcs[(size_t)i] = get_source(ctx, sources[i]);
-        if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-        if (!s->d_dr) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_direct_render_init has not been called for this source");
-        if (s->dr_frame != srcs[0]->dr_frame || s->dr_taps != srcs[0]->dr_taps)
-            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size and one tap count");
-        const fs_direct_render_target& t = targets[i];
-        if (!std::isfinite(t.delay) || !(t.delay >= 0.0f) || t.delay * fs_f > (float)s->dr_max_delay)
-            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a target's delay is negative, not finite or beyond the source's max delay");
-        for (int b = 0; b < B; ++b)
-            if (!std::isfinite(t.band_gain[b]) || !(t.band_gain[b] >= 0.0f))
-                return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a target's band gain is negative or not finite");
+        int rc;
+        srcs[(size_t)i] = render_row(ctx, sources[i], &Source::dr, "fs_direct_render_init has not been called for this source", i ? srcs[0] : nullptr, &rc);
+        if (!rc) rc = render_aim_check(ctx, "target", targets[i].delay, targets[i].band_gain, srcs[(size_t)i]->dr);
+        if (rc) return rc;
     }
-    {
-        std::vector<Source*> sorted(srcs);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a source appears twice in the batch");
-    }
-    const int frame = srcs[0]->dr_frame;
-    const size_t row = 2 * (size_t)frame;   // floats
+    { const int rc = render_no_duplicates(ctx, srcs); if (rc) return rc; }
+    const int frame = srcs[0]->dr.frame;
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    hipStream_t rs = ctx->rev_stream;
-    const DrStageLayout l = dr_stage_layout(count, frame);
-    if (l.host_bytes > ctx->dr_stage_host || l.dev_bytes > ctx->dr_stage_dev) {   // first call of this size (every call ends synchronised: nothing reads the old one)
-        if (ctx->h_dr_stage) (void)hipHostFree(ctx->h_dr_stage);
-        if (ctx->d_dr_stage) (void)hipFree(ctx->d_dr_stage);
-        ctx->h_dr_stage = ctx->d_dr_stage = nullptr; ctx->dr_stage_host = ctx->dr_stage_dev = 0;
-        FS_HIP(ctx, hipHostMalloc((void**)&ctx->h_dr_stage, l.host_bytes, hipHostMallocDefault));
-        ctx->dr_stage_host = l.host_bytes;
-        FS_HIP(ctx, hipMalloc((void**)&ctx->d_dr_stage, l.dev_bytes));
-        ctx->dr_stage_dev = l.dev_bytes;
-    }
-    char* hs = ctx->h_dr_stage; char* ds = ctx->d_dr_stage;
-    DirectRenderItem* items = (DirectRenderItem*)(hs + l.items);
+    const CallbackLayout l = callback_layout(count, frame, {sizeof(DirectRenderItem) * (size_t)count}, {sizeof(DirectRenderPlan) * (size_t)count});
+    { const int rc = ctx->dr_stage.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
+    char* hs = ctx->dr_stage.h; char* ds = ctx->dr_stage.d;
+    DirectRenderItem* items = (DirectRenderItem*)(hs + l.up[0]);
     for (int32_t i = 0; i < count; ++i) {
-        const Source* s = srcs[(size_t)i];
+        const RenderSetup& r = srcs[(size_t)i]->dr;
         DirectRenderItem& it = items[i];
         std::memset(&it, 0, sizeof(it));
-        it.state = (DirectRenderState*)s->d_dr;
-        it.ring = (float*)(s->d_dr + kDirectRenderHeader);
-        it.table = s->dr_table;
-        it.mask = s->dr_ring - 1u;
+        it.state = (DirectRenderState*)r.d;
+        it.ring = (float*)(r.d + kDirectRenderHeader);
+        it.table = r.table;
+        it.mask = r.ring - 1u;
         it.d1 = targets[i].delay * fs_f;
         for (int b = 0; b < B; ++b) it.g1[b] = targets[i].band_gain[b];
     }
-    std::memcpy(hs + l.in, in, sizeof(float) * row * (size_t)count);
-    FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, rs));
+    std::memcpy(hs + l.in, in, l.rows);
+    FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, ctx->rev_stream));
     DirectRenderBatch b{};
-    b.items = (const DirectRenderItem*)(ds + l.items);
-    b.plans = (DirectRenderPlan*)(ds + l.d_plans);
-    b.count = count; b.frame = frame; b.taps = srcs[0]->dr_taps; b.bands = B;
+    b.items = (const DirectRenderItem*)(ds + l.up[0]);
+    b.plans = (DirectRenderPlan*)(ds + l.scratch[0]);
+    b.count = count; b.frame = frame; b.taps = srcs[0]->dr.taps; b.bands = B;
     b.in = (const float*)(ds + l.in);
     b.out = (float*)(ds + l.d_out);
     b.mix = mix ? (float*)(ds + l.d_mix) : nullptr;
-    launch_direct_render(b, rs);
+    launch_direct_render(b, ctx->rev_stream);
     FS_HIP(ctx, hipGetLastError());
-    if (out)   // out | mix are adjacent on both sides: one copy back
-        FS_HIP(ctx, hipMemcpyAsync(hs + l.h_out, ds + l.d_out, sizeof(float) * row * ((size_t)count + (mix ? 1 : 0)), hipMemcpyDeviceToHost, rs));
-    else
-        FS_HIP(ctx, hipMemcpyAsync(hs + l.h_mix, ds + l.d_mix, sizeof(float) * row, hipMemcpyDeviceToHost, rs));
-    FS_HIP(ctx, hipStreamSynchronize(rs));
-    if (out) std::memcpy(out, hs + l.h_out, sizeof(float) * row * (size_t)count);
-    if (mix) std::memcpy(mix, hs + l.h_mix, sizeof(float) * row);
+    { const int rc = callback_finish(ctx, ctx->dr_stage, l, out != nullptr, mix); if (rc) return rc; }
+    if (out) std::memcpy(out, hs + l.h_out, l.rows);
     return FS_OK;
 }
 

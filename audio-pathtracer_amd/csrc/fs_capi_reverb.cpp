@@ -32,30 +32,8 @@ int part_twiddles(fs_context* ctx, int n) {
     return FS_OK;
 }
 
-// The staging of one callback (fs_context::h_rev_stage / d_rev_stage), every block 256-byte aligned
-struct RevStageLayout {
-    size_t items, pitems, lists, in, up_bytes;   // host and device, the same offsets: what goes up in one copy
-    size_t h_out, h_mix, host_bytes;        // host: what comes back
-    size_t d_cur, d_out, d_mix, dev_bytes;  // device: out | mix adjacent, one copy back
-};
-size_t rev_align(size_t b) { return (b + 255) & ~(size_t)255; }
-RevStageLayout rev_stage_layout(int count, int frame) {
-    const size_t rows = sizeof(float) * 2 * (size_t)frame * (size_t)count, row = sizeof(float) * 2 * (size_t)frame;
-    RevStageLayout l;
-    l.items = 0;
-    l.pitems = rev_align(sizeof(ReverbItem) * (size_t)count);
-    l.lists = l.pitems + rev_align(sizeof(ReverbPartItem) * (size_t)count);
-    l.in = l.lists + rev_align(sizeof(int) * 6 * (size_t)count);
-    l.up_bytes = l.in + rows;
-    l.h_out = rev_align(l.up_bytes);
-    l.h_mix = l.h_out + rows;   // (adjacent to out: rows is a multiple of 8 bytes)
-    l.host_bytes = l.h_mix + row;
-    l.d_cur = rev_align(l.up_bytes);
-    l.d_out = l.d_cur + rev_align(rows);
-    l.d_mix = l.d_out + rows;
-    l.dev_bytes = l.d_mix + row;
-    return l;
-}
+// the reverb callback's own blocks in its staging (fs_context::rev_stage): CallbackLayout::up; scratch[0] = the mono tails cur
+enum { kRevItems, kRevPartItems, kRevLists };
 
 // the bytes of Source::d_ring: the direct engine's two history rings, or the partitioned engine's state block
 size_t reverb_state_bytes(const Source* s) {
@@ -136,20 +114,13 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
     const size_t row = 2 * (size_t)frame;   // floats
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     hipStream_t rs = ctx->rev_stream;
-    const RevStageLayout l = rev_stage_layout(count, frame);
-    if (l.host_bytes > ctx->rev_stage_host || l.dev_bytes > ctx->rev_stage_dev) {   // first call of this size (every call ends synchronised: nothing reads the old one)
-        if (ctx->h_rev_stage) (void)hipHostFree(ctx->h_rev_stage);
-        if (ctx->d_rev_stage) (void)hipFree(ctx->d_rev_stage);
-        ctx->h_rev_stage = ctx->d_rev_stage = nullptr; ctx->rev_stage_host = ctx->rev_stage_dev = 0;
-        FS_HIP(ctx, hipHostMalloc((void**)&ctx->h_rev_stage, l.host_bytes, hipHostMallocDefault));
-        ctx->rev_stage_host = l.host_bytes;
-        FS_HIP(ctx, hipMalloc((void**)&ctx->d_rev_stage, l.dev_bytes));
-        ctx->rev_stage_dev = l.dev_bytes;
-    }
-    char* hs = ctx->h_rev_stage; char* ds = ctx->d_rev_stage;
-    ReverbItem* items = (ReverbItem*)(hs + l.items);
-    ReverbPartItem* pitems = (ReverbPartItem*)(hs + l.pitems);
-    int* plain = (int*)(hs + l.lists); int* fade = plain + count; int* take = fade + count;
+    const CallbackLayout l = callback_layout(count, frame, {sizeof(ReverbItem) * (size_t)count, sizeof(ReverbPartItem) * (size_t)count, sizeof(int) * 6 * (size_t)count},
+                                             {sizeof(float) * row * (size_t)count});
+    { const int rc = ctx->rev_stage.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
+    char* hs = ctx->rev_stage.h; char* ds = ctx->rev_stage.d;
+    ReverbItem* items = (ReverbItem*)(hs + l.up[kRevItems]);
+    ReverbPartItem* pitems = (ReverbPartItem*)(hs + l.up[kRevPartItems]);
+    int* plain = (int*)(hs + l.up[kRevLists]); int* fade = plain + count; int* take = fade + count;
     int* pplain = take + count; int* pfade = pplain + count; int* ptake = pfade + count;   // the partitioned engine's three
     int n_plain = 0, n_fade = 0, n_take = 0, n_pplain = 0, n_pfade = 0, n_ptake = 0, n_bypass = 0;
     const Source* part_src = nullptr;
@@ -183,8 +154,8 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
             }
         }
         FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, rs));
-        const ReverbItem* d_items = (const ReverbItem*)(ds + l.items);
-        const int* d_plain = (const int*)(ds + l.lists);
+        const ReverbItem* d_items = (const ReverbItem*)(ds + l.up[kRevItems]);
+        const int* d_plain = (const int*)(ds + l.up[kRevLists]);
         if (n_take) {
             launch_reverb_batch_fade_start(d_items, d_plain + 2 * count, n_take, ctx->num_samples, rs);
             FS_HIP(ctx, hipGetLastError());
@@ -192,7 +163,7 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
         }
         ReverbBatch b{};
         if (part_src) {   // (one frame size and one context: N and K are those of every partitioned row)
-            b.pitems = (const ReverbPartItem*)(ds + l.pitems);
+            b.pitems = (const ReverbPartItem*)(ds + l.up[kRevPartItems]);
             b.part.plain = d_plain + 3 * count; b.part.n_plain = n_pplain;
             b.part.fade = d_plain + 4 * count; b.part.n_fade = n_pfade;
             b.part.n = part_src->part_n; b.part.K = part_src->part_K; b.part.frame = frame; b.part.ir_size = ctx->num_samples;
@@ -210,7 +181,7 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
         b.count = count; b.frame = frame; b.ir_size = ctx->num_samples;
         b.literal_tail = (flags & FS_REVERB_LITERAL_TAIL) ? 1 : 0;
         b.in = (const float*)(ds + l.in);
-        b.cur = (float*)(ds + l.d_cur);
+        b.cur = (float*)(ds + l.scratch[0]);
         b.out = (float*)(ds + l.d_out);
         b.mix = mix ? (float*)(ds + l.d_mix) : nullptr;
         launch_reverb_batch(b, rs);
@@ -220,23 +191,70 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
             if (s->fade_len == 0) FS_HIP(ctx, hipEventRecord(s->ev_rev, rs));
         }
     }
-    if (out)   // out | mix are adjacent on both sides: one copy back
-        FS_HIP(ctx, hipMemcpyAsync(hs + l.h_out, ds + l.d_out, sizeof(float) * row * ((size_t)count + (mix ? 1 : 0)), hipMemcpyDeviceToHost, rs));
-    else
-        FS_HIP(ctx, hipMemcpyAsync(hs + l.h_mix, ds + l.d_mix, sizeof(float) * row, hipMemcpyDeviceToHost, rs));
-    FS_HIP(ctx, hipStreamSynchronize(rs));
-    if (out) {
+    { const int rc = callback_finish(ctx, ctx->rev_stage, l, out != nullptr, mix); if (rc) return rc; }
+    if (out) {   // row by row: a bypassed row comes from in, and the call may be in place
         const float* h_out = (const float*)(hs + l.h_out);
         for (int32_t i = 0; i < count; ++i) {   // bApplyReverb == false: RVB.cpp:128-132
             const float* from = (apply_reverb && !apply_reverb[i]) ? in + (size_t)i * row : h_out + (size_t)i * row;
             if (from != out + (size_t)i * row) std::memcpy(out + (size_t)i * row, from, sizeof(float) * row);   // (in place: in == out)
         }
     }
-    if (mix) std::memcpy(mix, hs + l.h_mix, sizeof(float) * row);
     return FS_OK;
 }
 
 }  // namespace
+
+int CallbackStage::fit(fs_context* ctx, size_t host_bytes, size_t dev_bytes) {
+    if (host_bytes <= host_cap && dev_bytes <= dev_cap) return FS_OK;
+    // first call of this size (every call ends synchronised: nothing reads the old pair)
+    const size_t hb = std::max(host_bytes, host_cap), db = std::max(dev_bytes, dev_cap);
+    release();
+    FS_HIP(ctx, hipHostMalloc((void**)&h, hb, hipHostMallocDefault));
+    host_cap = hb;
+    FS_HIP(ctx, hipMalloc((void**)&d, db));
+    dev_cap = db;
+    return FS_OK;
+}
+
+void CallbackStage::release() {
+    if (h) (void)hipHostFree(h);
+    if (d) (void)hipFree(d);
+    h = d = nullptr; host_cap = dev_cap = 0;
+}
+
+namespace fsi {
+
+CallbackLayout callback_layout(int count, int frame, std::initializer_list<size_t> up_blocks, std::initializer_list<size_t> scratch_blocks) {
+    auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    CallbackLayout l;
+    l.row = sizeof(float) * 2 * (size_t)frame;
+    l.rows = l.row * (size_t)count;
+    int k = 0;
+    for (size_t bytes : up_blocks) { l.up[k++] = l.in; l.in += align(bytes); }
+    l.up_bytes = l.in + l.rows;
+    l.h_out = align(l.up_bytes);
+    l.h_mix = l.h_out + l.rows;   // (adjacent to out: rows is a multiple of 8 bytes)
+    l.host_bytes = l.h_mix + l.row;
+    l.d_out = align(l.up_bytes);
+    k = 0;
+    for (size_t bytes : scratch_blocks) { l.scratch[k++] = l.d_out; l.d_out += align(bytes); }
+    l.d_mix = l.d_out + l.rows;
+    l.dev_bytes = l.d_mix + l.row;
+    return l;
+}
+
+int callback_finish(fs_context* ctx, const CallbackStage& st, const CallbackLayout& l, bool want_out, float* mix) {
+    hipStream_t rs = ctx->rev_stream;
+    if (want_out)   // out | mix are adjacent on both sides: one copy back
+        FS_HIP(ctx, hipMemcpyAsync(st.h + l.h_out, st.d + l.d_out, l.rows + (mix ? l.row : 0), hipMemcpyDeviceToHost, rs));
+    else
+        FS_HIP(ctx, hipMemcpyAsync(st.h + l.h_mix, st.d + l.d_mix, l.row, hipMemcpyDeviceToHost, rs));
+    FS_HIP(ctx, hipStreamSynchronize(rs));
+    if (mix) std::memcpy(mix, st.h + l.h_mix, l.row);
+    return FS_OK;
+}
+
+}  // namespace fsi
 
 extern "C" {
 

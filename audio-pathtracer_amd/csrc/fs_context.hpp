@@ -3,8 +3,9 @@
 // fs_capi_frame.cpp (sources, the traced frame: describe / resources / commit / launch), fs_capi_pipeline.cpp (held frames, the
 // drain), fs_capi_publish.cpp (reconstruct + publish: the IR ring, the host word, the fused launch's reconstruct parts),
 // fs_capi_ir.cpp (reconstruct / tick / IR / energy entry points), fs_capi_comm.cpp (RCCL behind the ABI), fs_capi_reverb.cpp
-// (the reverb callback), fs_capi_paths.cpp (direct, reflection and diffraction paths), fs_capi_direct_render.cpp (the direct-sound callback), fs_capi_reflect_render.cpp (the early-reflection callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange,
-// material FD).
+// (the reverb callback, and the staging, layout and tail of all three audio callbacks), fs_capi_paths.cpp (the five path queries),
+// fs_capi_direct_render.cpp (the direct-sound callback, and what the two renderers share on the host), fs_capi_reflect_render.cpp
+// (the early-reflection callback) and fs_capi_aux.cpp (legacy tracer, line trace, text interchange, material FD).
 //
 // Mirrors the roles of UAudioRayTracingSubsystem (context lifetime, geometry/source registries,
 // per-source update: AudioRayTracingSubsystem.cpp:32-53, 128-195) and of UFrequenSeeAudioComponent's
@@ -72,6 +73,16 @@ static_assert(kEnergyBufs >= 4 * (kMaxWalkParts + 3), "four frames of one source
 // before it reads host memory (the publishes' ev[slot], tail_batch_ev) keep the system scope.
 constexpr unsigned kDeviceEventFlags = hipEventDisableTiming | hipEventReleaseToDevice;
 
+// What fs_direct_render_init / fs_reflection_render_init gave a source (the audio thread's, like the reverb fields): the state
+// block on the device — the renderer's header, then the history rings [2][ring] — and what the source was initialised with;
+// table is one of fs_context::dr_tables' (owned by the context); max_delay = D, the largest delay in samples
+struct RenderSetup {
+    char* d = nullptr;
+    int frame = 0, taps = 0, max_delay = 0;
+    unsigned ring = 0;
+    const float* table = nullptr;
+};
+
 struct Source {
     bool alive = false;
     float pos[3] = {0, 0, 0};
@@ -138,7 +149,7 @@ struct Source {
     // flagged reconstruct — ensure_room); room_of[k]: the publish in slot k carries them (noted with the slot's other notes)
     std::atomic<fs_room_parameters*> h_room{nullptr};
     std::atomic<bool> room_of[kIrRing] = {};
-    // reverb (row f2): history rings [2][kReverbRing], write head (a callback's rows are staged in fs_context::h_rev_stage / d_rev_stage)
+    // reverb (row f2): history rings [2][kReverbRing], write head (a callback's rows are staged in fs_context::rev_stage)
     float* d_ring = nullptr;
     unsigned rev_head = 0; int rev_frame = 0;
     // fs_reverb_set_engine: the engine the next fs_reverb_init gives the source / the one it was initialised with.  PARTITIONED
@@ -156,20 +167,11 @@ struct Source {
     int32_t fade_len = 0, fade_pos = 0;
     bool fading = false, fade_primed = false;
     uint64_t fade_gen = 0;
-    // direct sound (fs_direct_render_init; the audio thread's, like the reverb fields): the state block — DirectRenderState, then
-    // at kDirectRenderHeader the history rings [2][dr_ring] — and what the source was initialised with; dr_table is one of
-    // fs_context::dr_tables' (owned by the context); dr_max_delay = D, the largest delay in samples
-    char* d_dr = nullptr;
-    int dr_frame = 0, dr_taps = 0, dr_max_delay = 0;
-    unsigned dr_ring = 0;
-    const float* dr_table = nullptr;
-    // early reflections (fs_reflection_render_init; the audio thread's): the state block — ReflectRenderState, then at
-    // kReflectRenderHeader the history rings [2][rr_ring] shared by the rr_voices slots — and what the source was initialised with
-    // (rr_table: one of fs_context::dr_tables'); rr_held / rr_key: the slot table the callback matches against, the host's copy
-    char* d_rr = nullptr;
-    int rr_frame = 0, rr_taps = 0, rr_voices = 0, rr_max_delay = 0;
-    unsigned rr_ring = 0;
-    const float* rr_table = nullptr;
+    // direct sound (header: DirectRenderState, kDirectRenderHeader bytes) and early reflections (header: ReflectRenderState,
+    // kReflectRenderHeader bytes; the rings are shared by the rr_voices slots); rr_held / rr_key: the slot table the reflection
+    // callback matches against, the host's copy
+    RenderSetup dr, rr;
+    int rr_voices = 0;
     bool rr_held[FS_MAX_REFLECTION_VOICES] = {};
     uint32_t rr_key[FS_MAX_REFLECTION_VOICES] = {};
     float occlusion = 1.0f;            // OcclusionAttenuation FSAC.h:130 (1.f until the first UpdateSound)
@@ -256,6 +258,28 @@ struct PathStaging {
     void release();
 };
 
+// An audio callback's staging pair (fs_capi_reverb.cpp): pinned host memory and its device counterpart, in bytes.  What lies
+// where is the call's CallbackLayout.  fit grows the pair: each side to the larger of what it has and what is asked, never
+// smaller — the two sides do not grow in step when the count and the frame size vary apart, and a side that shrank would be
+// reallocated by the next call of the old shape.  Plain pointers: fit replaces the pair, release frees it (fs_context_destroy).
+struct CallbackStage {
+    char* h = nullptr;
+    char* d = nullptr;
+    size_t host_cap = 0, dev_cap = 0;
+    int fit(fs_context* ctx, size_t host_bytes, size_t dev_bytes);   // FS_OK or the failure reported
+    void release();
+};
+// Where a callback of `count` rows of `frame` samples keeps what in its staging pair, every block 256-byte aligned.  What goes up in
+// one copy has the same offsets on both sides: the call's own blocks (up[k], in the order given), then in [count][2 frame].  Behind
+// it the host holds what comes back, out [count][2 frame] | mix [2 frame]; the device holds the call's scratch blocks (scratch[k]),
+// then out | mix, adjacent as on the host: one copy back.
+struct CallbackLayout {
+    size_t up[3] = {}, in = 0, up_bytes = 0;
+    size_t h_out = 0, h_mix = 0, host_bytes = 0;
+    size_t scratch[2] = {}, d_out = 0, d_mix = 0, dev_bytes = 0;
+    size_t rows = 0, row = 0;   // the bytes of in and of out, and of mix
+};
+
 struct fs_context {
     fs_config cfg{};
     int num_bins = 0, num_samples = 0;
@@ -316,12 +340,15 @@ struct fs_context {
     size_t fft_stage_floats = 0;
     hipGraphExec_t fft_graph = nullptr;
     int fft_graph_n = -1, fft_graph_l = -1;
-    // fs_reverb_process / fs_reverb_process_batch (audio thread): pinned host staging and its device mirror, grown at the first call that needs more
-    // (count x frame size), freed with the context.  Up: items [count] | the partitioned rows' items [count] | plain, fade, take lists
-    // of the two engines [6][count] | in [count][2 frame];
-    // down: out [count][2 frame] | mix [2 frame]; the device also holds the mono tails cur [count][2 frame].
-    char* h_rev_stage = nullptr; char* d_rev_stage = nullptr;
-    size_t rev_stage_host = 0, rev_stage_dev = 0;   // bytes
+    // The audio callbacks' staging, one pair each, grown at the first call that needs more and freed with the context: a reverb, a
+    // direct and a reflection callback of different counts may follow each other in one audio callback (and direct_stage below is
+    // the game thread's).  Beside in, out and mix (CallbackLayout) they hold
+    // rev_stage (fs_reverb_process / _batch): up, items [count] | the partitioned rows' items [count] | plain, fade, take lists of
+    //   the two engines [6][count]; scratch, the mono tails cur [count][2 frame]
+    // dr_stage (fs_direct_render_process_batch): up, items [count]; scratch, the plans [count]
+    // rr_stage (fs_reflection_render_process_batch): up, items [count] | voices [count][stride]; scratch, the counters [count] |
+    //   the plans [count][FS_MAX_REFLECTION_VOICES]
+    CallbackStage rev_stage, dr_stage, rr_stage;
     // the partitioned engine's twiddles, W[k] = exp(-2 pi i k / N), k < N / 2, per n = log2 N <= 12: built by the first
     // fs_reverb_init that needs the size, freed with the context
     float2* d_rev_tw[13] = {};
@@ -342,19 +369,9 @@ struct fs_context {
     double diffract_f[FS_MAX_BANDS] = {};
     std::vector<double> diffract_f_edges;
     int diffract_f_bands = 0;
-    // fs_direct_render_process_batch (audio thread): staging of its own — a reverb and a direct callback of different counts may
-    // follow each other in one audio callback, and direct_stage is the game thread's.  Up: items [count] | in [count][2 frame];
-    // the device also holds the plans [count]; down: out [count][2 frame] | mix [2 frame].  Grown at the first call that needs more.
-    char* h_dr_stage = nullptr; char* d_dr_stage = nullptr;
-    size_t dr_stage_host = 0, dr_stage_dev = 0;   // bytes
     // the band-kernel tables fs_direct_render_init has built, one per (taps, edges in force); freed with the context
     struct DirectRenderTable { int taps; std::vector<double> edges; float* d; };
     std::vector<DirectRenderTable> dr_tables;
-    // fs_reflection_render_process_batch (audio thread): staging of its own, beside the reverb's and the direct sound's.  Up: items
-    // [count] | voices [count][stride] | in [count][2 frame]; the device also holds the counters [count] and the plans
-    // [count][FS_MAX_REFLECTION_VOICES]; down: out [count][2 frame] | mix [2 frame].  Grown at the first call that needs more.
-    char* h_rr_stage = nullptr; char* d_rr_stage = nullptr;
-    size_t rr_stage_host = 0, rr_stage_dev = 0;   // bytes
     HostBVH bvh;
 
     float listener[3] = {0, 0, 0};
@@ -551,10 +568,25 @@ constexpr float kMaxUnboundedRr = 0.95f;   // depth = 0 (uncapped walks): the st
 
 namespace fsi {
 
-// ---- fs_capi_direct_render.cpp: what the reflection renderer shares with the direct one
+// ---- fs_capi_reverb.cpp: what the three audio callbacks share ------------------------------------------------------
+// the layout of a call: up_blocks / scratch_blocks = the bytes of its own blocks (CallbackLayout::up / scratch), in order
+CallbackLayout callback_layout(int count, int frame, std::initializer_list<size_t> up_blocks, std::initializer_list<size_t> scratch_blocks);
+// The tail of a callback whose launches are enqueued on the reverb stream: the copy back (out | mix in one when both are wanted,
+// else mix alone), the wait, mix copied out.  The rows of out are then in st.h + l.h_out: the caller's to copy.
+int callback_finish(fs_context* ctx, const CallbackStage& st, const CallbackLayout& l, bool want_out, float* mix);
+// ---- fs_capi_direct_render.cpp: what the reflection renderer shares with the direct one -----------------------------
 bool direct_render_taps_ok(int32_t taps);
-// the device table of (taps, edges in force), built and uploaded at its first use; owned by the context
-int direct_render_table_for(fs_context* ctx, int taps, const float** out);
+// What both inits do once the arguments are found good (need = d_max + taps + 1 + frame samples, the ring's least size): the
+// table of (taps, edges in force), the wait for the callbacks' stream, the old state block freed, a zeroed new one of
+// header bytes + the rings.  A failure before the wait changes nothing; one after it leaves the source without a set-up.
+int render_setup(fs_context* ctx, RenderSetup& r, size_t header, int frame, int taps, double d_max, double need);
+int render_clear(fs_context* ctx, const RenderSetup& r, size_t header);   // the releases: history := 0 (enqueued), where there is a set-up
+// a row's first checks, in this order: the handle, the set-up (`which` of the source's two; no_setup: the message), the batch's
+// one shape (first: row 0's source, nullptr in row 0).  *rc = FS_OK and the source, or the failure reported and nullptr.
+Source* render_row(fs_context* ctx, fs_source h, RenderSetup Source::*which, const char* no_setup, const Source* first, int* rc);
+// a target's or a voice's (`whose`) delay and band gains against the source's set-up
+int render_aim_check(fs_context* ctx, const char* whose, float delay, const float* band_gain, const RenderSetup& r);
+int render_no_duplicates(fs_context* ctx, const std::vector<Source*>& srcs);   // "a source appears twice in the batch"
 // ---- fs_capi_context.cpp ------------------------------------------------------------------------------------------
 Source* get_source(fs_context* ctx, fs_source h);
 hipError_t wait_energy_readers(fs_context* ctx, Source* s);            // before the compute stream writes the current energy buffer

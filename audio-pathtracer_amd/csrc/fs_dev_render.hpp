@@ -1,0 +1,138 @@
+// fs_dev_render.hpp — what the two render kernels of the audio thread (fs_direct_render.hip, fs_reflect_render.hip) share on the
+// device: one voice's block — a time-varying fractional delay and a linear-phase FIR whose taps ramp from sum_b g0_b k_b to
+// sum_b g1_b k_b — as pieces a kernel puts together: the delay of an output sample and its slew clamp, the tap table and the
+// tile's read window in LDS, the tap loop of one output sample, the output store with the ring append.  The rule is
+// include/frequensee.h's, to the bit: every fp32 operation stands where the header puts it (the files are built with
+// -ffp-contract=off and the tests compare bits).  No piece holds a barrier or a return: each says which barrier its caller owes.
+// The LDS arrays travel as references to arrays, so that after inlining the tap loop still reads them with LDS instructions.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "fs_internal.hpp"
+
+namespace fs {
+namespace {
+
+constexpr int kRenderTile = 256;                               // outputs per workgroup = threads per workgroup
+constexpr int kRenderMaxTaps = FS_DIRECT_RENDER_MAX_TAPS;
+// the window of a tile: its outputs, the taps, x(p - 1), and the delay's travel across the tile — the slew limit bounds that
+// to half a sample per sample, plus one for the floor
+constexpr int kRenderWindow = kRenderTile + kRenderTile / 2 + kRenderMaxTaps + 8;
+using RenderTaps = float2[kRenderMaxTaps + 1];   // {c0[t], dc[t]}
+using RenderWindow = float[kRenderWindow];
+
+// the delay of output sample s: a = (s + 1) / F, d = d0 + a e
+__device__ __forceinline__ float render_delay(float d0, float e, int s, float frame_f, float* a_out) {
+    const float a = (float)(s + 1) / frame_f;
+    *a_out = a;
+    return d0 + a * e;
+}
+
+// the slew limit of a callback's change of delay: half a sample per sample
+__device__ __forceinline__ float render_slew(float e, int frame) {
+    const float half = 0.5f * (float)frame;
+    if (e < -half) e = -half;
+    if (e > half) e = half;
+    return e;
+}
+
+// {c0[t], c1[t] - c0[t]}, c = sum_b g_b k_b, into s_cd.  The caller owes a barrier between this and the first render_sample, and
+// one between the last render_sample and the next build.
+__device__ __forceinline__ void render_build_taps(RenderTaps& s_cd, const float* __restrict__ table, const float* __restrict__ g0,
+                                                  const float* __restrict__ g1, int taps, int bands, int tid) {
+    for (int t = tid; t < taps; t += kRenderTile) {
+        float c0 = 0.0f, c1 = 0.0f;
+        for (int b = 0; b < bands; ++b) {
+            const float k = table[(size_t)b * (size_t)taps + t];
+            c0 = c0 + g0[b] * k;
+            c1 = c1 + g1[b] * k;
+        }
+        s_cd[t] = make_float2(c0, c1 - c0);
+    }
+}
+
+// The read window of the tile's outputs [s_a, s_b] of channel ch into s_win, from the ring (samples before n0) and the
+// block (from n0 on; past the block's end: 0).  Returns i_hi, the largest whole delay of the tile, which places a sample's taps
+// in the window (render_sample).  The same barriers as render_build_taps.
+__device__ __forceinline__ int render_stage_window(RenderWindow& s_win, const float* __restrict__ ring, unsigned mask,
+                                                   const float* __restrict__ in, int ch, unsigned n0, float d0, float e, int s_a, int s_b, int frame,
+                                                   float frame_f, int taps, int tid) {
+    // d is monotone in s (every rounding is), so the tile's whole delays lie between those of its first and last output
+    float a_unused;
+    const int i_a = (int)floorf(render_delay(d0, e, s_a, frame_f, &a_unused));
+    const int i_b = (int)floorf(render_delay(d0, e, s_b, frame_f, &a_unused));
+    const int i_lo = min(i_a, i_b), i_hi = max(i_a, i_b);
+    const unsigned p_lo = n0 + (unsigned)s_a - (unsigned)(taps - 1) - (unsigned)i_hi - 1u;   // absolute index of s_win[0]
+    const int wlen = min((s_b - s_a) + (i_hi - i_lo) + taps + 1, kRenderWindow);
+    for (int j = tid; j < wlen; j += kRenderTile) {
+        const unsigned p = p_lo + (unsigned)j;
+        const int rel = (int)(p - n0);   // >= 0: a sample of this block
+        float v = 0.0f;
+        if (rel < 0) v = ring[p & mask];
+        else if (rel < frame) v = in[2 * rel + ch];
+        s_win[j] = v;
+    }
+    return i_hi;
+}
+
+// Output sample s < frame of the voice whose taps and window the LDS holds: the four-accumulator tap loop, (acc0 + acc1) +
+// (acc2 + acc3); *a_out = the sample's ramp position.  c0 / dc are wave-uniform broadcasts, neighbouring lanes read neighbouring
+// samples, x(p - 1) of tap t is x(p) of tap t + 1 (one sample read per tap).  Behind the barrier that follows the build and the
+// staging.
+__device__ __forceinline__ float render_sample(const RenderTaps& s_cd, const RenderWindow& s_win, float d0, float e, int s, int s_a,
+                                               int i_hi, float frame_f, int taps, float* a_out) {
+    float a;
+    const float d = render_delay(d0, e, s, frame_f, &a);
+    *a_out = a;
+    const float fl = floorf(d);
+    const int i = (int)fl;
+    const float f = d - fl;
+    // tap t reads x(p) = s_win[base - t] and x(p - 1) = s_win[base - t - 1], p = n0 + s - t - i
+    const int base = min((s - s_a) + (i_hi - i) + taps, kRenderWindow - 1);
+    float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f, acc3 = 0.0f;
+    float xp = s_win[base];
+    int t = 0;
+    for (; t + 4 <= taps; t += 4) {
+        const float2 k0 = s_cd[t], k1 = s_cd[t + 1], k2 = s_cd[t + 2], k3 = s_cd[t + 3];
+        const float x1 = s_win[base - t - 1], x2 = s_win[base - t - 2], x3 = s_win[base - t - 3], x4 = s_win[base - t - 4];
+        acc0 = acc0 + (k0.x + a * k0.y) * (xp + f * (x1 - xp));
+        acc1 = acc1 + (k1.x + a * k1.y) * (x1 + f * (x2 - x1));
+        acc2 = acc2 + (k2.x + a * k2.y) * (x2 + f * (x3 - x2));
+        acc3 = acc3 + (k3.x + a * k3.y) * (x3 + f * (x4 - x3));
+        xp = x4;
+    }
+    if (t < taps) {
+        const float2 k0 = s_cd[t];
+        const float x1 = s_win[base - t - 1];
+        acc0 = acc0 + (k0.x + a * k0.y) * (xp + f * (x1 - xp));
+        xp = x1;
+        ++t;
+    }
+    if (t < taps) {
+        const float2 k1 = s_cd[t];
+        const float x2 = s_win[base - t - 1];
+        acc1 = acc1 + (k1.x + a * k1.y) * (xp + f * (x2 - xp));
+        xp = x2;
+        ++t;
+    }
+    if (t < taps) {
+        const float2 k2 = s_cd[t];
+        const float x3 = s_win[base - t - 1];
+        acc2 = acc2 + (k2.x + a * k2.y) * (xp + f * (x3 - xp));
+    }
+    return (acc0 + acc1) + (acc2 + acc3);
+}
+
+// Output sample s < frame of row r: y into out, the input sample into the ring.  A callback reads ring positions [n0 - D - T, n0)
+// and writes [n0, n0 + F), disjoint modulo the ring because it holds D + T + 1 + F or more: no barrier.
+__device__ __forceinline__ void render_store(float* __restrict__ out_all, float* __restrict__ ring, unsigned mask,
+                                             const float* __restrict__ in, int r, int ch, unsigned n0, int s, int frame, float y) {
+    out_all[(size_t)r * 2 * (size_t)frame + 2 * (size_t)s + ch] = y;
+    ring[(n0 + (unsigned)s) & mask] = in[2 * s + ch];
+}
+
+}  // namespace
+}  // namespace fs

@@ -582,12 +582,15 @@ void launch_reverb_batch_fade_start(const ReverbItem* items, const int* take, in
 // prepare (+ push, where the ring allows), the convolutions of the two lists (each launched only when it has rows), the push
 // (where it could not ride in front), the partitioned engine's rows (launch_reverb_part, when b.pitems), the mix (when b.mix)
 void launch_reverb_batch(const ReverbBatch& b, hipStream_t s);
+// the mix of the three audio callbacks (the reverb's, the direct sound's, the early reflections'): mix [2 * frame] = the fp32 sum
+// of out [count][2 * frame] over the rows, in list order
+void launch_callback_mix(const float* out, int count, int frame, float* mix, hipStream_t s);
 // take: the partitioned rows that take a newer IR in this callback (n_take >= 1)
 void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, hipStream_t s);
 // the window transforms, the products of the two lists (each launched only when it has rows), the inverse and epilogue
 void launch_reverb_part(const ReverbPartItem* items, const ReverbPart& p, int count, int literal_tail, const float* in, float* out,
                         hipStream_t s);
-// fs_direct_render.hip (the direct-sound callback).  A source's state is one device block (Source::d_dr): this header, then at
+// fs_direct_render.hip (the direct-sound callback).  A source's state is one device block (Source::dr.d): this header, then at
 // kDirectRenderHeader bytes the two history rings [2][ring] (ring a power of two); zeroed = not primed, nothing heard yet.
 struct DirectRenderState {
     unsigned n0;           // absolute index of the next block's first sample (wraps; the ring index is n & mask)
@@ -626,7 +629,7 @@ struct DirectRenderBatch {
 };
 // the plan pass, the render pass (which also appends the blocks to the rings), the mix (when b.mix)
 void launch_direct_render(const DirectRenderBatch& b, hipStream_t s);
-// fs_reflect_render.hip (the early-reflection callback).  A source's state is one device block (Source::d_rr): this header, then at
+// fs_reflect_render.hip (the early-reflection callback).  A source's state is one device block (Source::rr.d): this header, then at
 // kReflectRenderHeader bytes the two history rings [2][ring], shared by the source's slots; zeroed = every slot free, nothing heard.
 struct ReflectRenderSlot {
     int32_t held;          // the device's record of the slot table; the matching itself runs on the host's copy (Source::rr_held / rr_key)

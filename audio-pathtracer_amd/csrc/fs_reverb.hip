@@ -160,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void reverb_batch_conv_kernel(const ReverbI
 }
 
 // mix[j] = ((out[0][j] + out[1][j]) + out[2][j]) + ... in list order, fp32, not clamped: one thread per sample, so the order is fixed
-__global__ void reverb_batch_mix_kernel(const float* __restrict__ out_all, int count, int n2, float* __restrict__ mix) {
+__global__ void callback_mix_kernel(const float* __restrict__ out_all, int count, int n2, float* __restrict__ mix) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n2) return;
     float v = out_all[j];
@@ -169,6 +169,11 @@ __global__ void reverb_batch_mix_kernel(const float* __restrict__ out_all, int c
 }
 
 }  // namespace
+
+void launch_callback_mix(const float* out, int count, int frame, float* mix, hipStream_t s) {
+    const int tb = 256;
+    hipLaunchKernelGGL(callback_mix_kernel, dim3((2 * frame + tb - 1) / tb), dim3(tb), 0, s, out, count, 2 * frame, mix);
+}
 
 void launch_reverb_batch_fade_start(const ReverbItem* items, const int* take, int n_take, int n, hipStream_t s) {
     const int tb = 256;
@@ -196,8 +201,7 @@ void launch_reverb_batch(const ReverbBatch& b, hipStream_t s) {
     if (!fused && b.n_plain + b.n_fade > 0)
         hipLaunchKernelGGL(reverb_batch_prepare_kernel, rows, dim3(tb), 0, s, b.items, b.in, b.cur, b.out, b.frame, b.literal_tail, kRevPush);
     if (b.pitems) launch_reverb_part(b.pitems, b.part, b.count, b.literal_tail, b.in, b.out, s);
-    if (b.mix)
-        hipLaunchKernelGGL(reverb_batch_mix_kernel, dim3((2 * b.frame + tb - 1) / tb), dim3(tb), 0, s, b.out, b.count, 2 * b.frame, b.mix);
+    if (b.mix) launch_callback_mix(b.out, b.count, b.frame, b.mix, s);
 }
 
 }  // namespace fs

@@ -418,13 +418,28 @@ private:
     AudioRayTracingSubsystem* SubSys_;
 };
 
+// What the two render plugins below share: the shape of their callback and a path's arrival time as the delay of a target or a voice
+class FrequenSeeRenderPlugin {
+public:
+    int FrameSize = 1024;   // AudioCallbackBufferFrameSize, Config/DefaultEngine.ini:13
+    int Taps = 255;
+    float MaxDelaySeconds = 1.0f;
+    int SampleRate = 48000;   // fs_config_default's, FSAC.h:133
+
+protected:
+    explicit FrequenSeeRenderPlugin(AudioRayTracingSubsystem& SubSys) : SubSys_(&SubSys) {}
+    // the arrival time less the filter's own latency of (Taps - 1) / 2 samples, not below 0
+    float TargetDelay(float Arrival) const { return (float)std::max((double)Arrival - (double)((Taps - 1) / 2) / (double)SampleRate, 0.0); }
+    AudioRayTracingSubsystem* SubSys_;
+};
+
 // FFrequenSeeAudioOcclusionPlugin (Private/FrequenSeeAudioOcclusionPlugin.cpp:33-50) with the multiply the reference leaves
 // commented out done: per audio callback every source's block is delayed by its direct path's arrival time (a fractional,
 // slew-limited delay: the Doppler shift) and filtered by its per-band transmission — fs_direct_render_process_batch, one call
 // for all sources.  Distance attenuation stays the host's.
-class FrequenSeeAudioOcclusionPlugin {
+class FrequenSeeAudioOcclusionPlugin : public FrequenSeeRenderPlugin {
 public:
-    explicit FrequenSeeAudioOcclusionPlugin(AudioRayTracingSubsystem& SubSys) : SubSys_(&SubSys) {}
+    explicit FrequenSeeAudioOcclusionPlugin(AudioRayTracingSubsystem& SubSys) : FrequenSeeRenderPlugin(SubSys) {}
     void Initialize(int BufferLength = 1024, int TapCount = 255, float MaxDelay = 1.0f) {
         FrameSize = BufferLength; Taps = TapCount; MaxDelaySeconds = MaxDelay;
     }
@@ -432,13 +447,11 @@ public:
         SubSys_->Check(fs_direct_render_init(SubSys_->Ctx_, C.Handle_, FrameSize, Taps, MaxDelaySeconds));
     }
     void OnReleaseSource(const FrequenSeeAudioComponent& C) { SubSys_->Check(fs_direct_render_release(SubSys_->Ctx_, C.Handle_)); }
-    // the callback's targets from UpdateDirectPaths rows: band_gain = transmission, delay = the path's arrival time less the
-    // filter's own latency of (Taps - 1) / 2 samples, not below 0
+    // the callback's targets from UpdateDirectPaths rows: band_gain = transmission, delay = TargetDelay of the path's arrival time
     std::vector<fs_direct_render_target> Targets(const std::vector<fs_direct_path>& Paths) const {
         std::vector<fs_direct_render_target> T(Paths.size());
-        const double Latency = (double)((Taps - 1) / 2) / (double)SampleRate;
         for (size_t i = 0; i < Paths.size(); ++i) {
-            T[i].delay = (float)std::max((double)Paths[i].delay - Latency, 0.0);
+            T[i].delay = TargetDelay(Paths[i].delay);
             for (int b = 0; b < FS_MAX_BANDS; ++b) T[i].band_gain[b] = Paths[i].transmission[b];
         }
         return T;
@@ -453,14 +466,6 @@ public:
         if (T.size() != H.size()) throw std::runtime_error("FrequenSee: one direct path per source");
         SubSys_->Check(fs_direct_render_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, T.data(), Out, Mix));
     }
-
-    int FrameSize = 1024;   // AudioCallbackBufferFrameSize, Config/DefaultEngine.ini:13
-    int Taps = 255;
-    float MaxDelaySeconds = 1.0f;
-    int SampleRate = 48000;   // fs_config_default's, FSAC.h:133
-
-private:
-    AudioRayTracingSubsystem* SubSys_;
 };
 
 // Not in the reference: per audio callback every source's block is rendered once per first-order reflection of
@@ -468,9 +473,9 @@ private:
 // of its own), filtered by its per-band reflectance, weighted by a per-channel gain and summed — fs_reflection_render_process_batch,
 // one call for all sources.  A reflection is recognised from callback to callback by its triangle; one that appears or vanishes
 // fades over one block.  Panning and the distance law are this plugin's (Voices), not the library's.
-class FrequenSeeAudioReflectionPlugin {
+class FrequenSeeAudioReflectionPlugin : public FrequenSeeRenderPlugin {
 public:
-    explicit FrequenSeeAudioReflectionPlugin(AudioRayTracingSubsystem& SubSys) : SubSys_(&SubSys) {}
+    explicit FrequenSeeAudioReflectionPlugin(AudioRayTracingSubsystem& SubSys) : FrequenSeeRenderPlugin(SubSys) {}
     void Initialize(int BufferLength = 1024, int TapCount = 255, int Voices = FS_MAX_REFLECTION_VOICES, float MaxDelay = 1.0f) {
         FrameSize = BufferLength; Taps = TapCount; VoiceCount = Voices; MaxDelaySeconds = MaxDelay;
     }
@@ -479,7 +484,7 @@ public:
     }
     void OnReleaseSource(const FrequenSeeAudioComponent& C) { SubSys_->Check(fs_reflection_render_release(SubSys_->Ctx_, C.Handle_)); }
     // one source's entries from its row and paths of fs_update_reflection_paths, over the first Row.returned paths: key = triangle,
-    // band_gain = reflectance, delay = the path's arrival time less the filter's own latency of (Taps - 1) / 2 samples, not below 0.
+    // band_gain = reflectance, delay = TargetDelay of the path's arrival time.
     // channel_gain = (1, 1); with Right (the listener's unit right vector) the constant-power pan (cos t, sin t),
     // t = (dot(direction, Right) + 1) pi / 4; with ReferenceLength > 0 (cm) scaled by min(1, ReferenceLength / length).
     // DRow / DPaths (the same source's row and paths of fs_update_diffraction_paths) append one voice per returned diffraction path:
@@ -503,7 +508,6 @@ public:
         const size_t NT = TRow && TPaths ? (size_t)TRow->returned : 0;
         std::vector<fs_reflection_voice> V;
         V.reserve(NR + ND + NS + NT);
-        const double Latency = (double)((Taps - 1) / 2) / (double)SampleRate;
         for (size_t i = 0; i < NR + ND + NS + NT; ++i) {
             const bool Refl = i < NR, Second = i >= NR + ND && i < NR + ND + NS, Thick = i >= NR + ND + NS;
             const fs_reflection2_path* S = Second ? SPaths + (i - NR - ND) : nullptr;
@@ -521,7 +525,7 @@ public:
             V.emplace_back();
             const size_t Slot = V.size() - 1;
             V[Slot].key = Key;
-            V[Slot].delay = (float)std::max((double)Delay - Latency, 0.0);
+            V[Slot].delay = TargetDelay(Delay);
             for (int b = 0; b < FS_MAX_BANDS; ++b) V[Slot].band_gain[b] = Gain[b];
             double L = 1.0, R = 1.0;
             if (Right) {
@@ -580,14 +584,7 @@ public:
                                                           Mix, Counts));
     }
 
-    int FrameSize = 1024;   // AudioCallbackBufferFrameSize, Config/DefaultEngine.ini:13
-    int Taps = 255;
     int VoiceCount = FS_MAX_REFLECTION_VOICES;
-    float MaxDelaySeconds = 1.0f;
-    int SampleRate = 48000;   // fs_config_default's, FSAC.h:133
-
-private:
-    AudioRayTracingSubsystem* SubSys_;
 };
 
 }  // namespace frequensee

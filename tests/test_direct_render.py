@@ -277,7 +277,9 @@ def one(ctx, src, block, delay, gains):
     return ctx.direct_render_process_batch([src], block[None], [(delay, gains)])[0]
 
 
-SHAPES = [(64, 1), (64, 15), (64, 255), (320, 1), (320, 15), (320, 255)]
+# F = 64: a partial tile; 256: exactly one tile; 320: a full tile and a partial one.  T = 5, 9: one tail step behind one and two full
+# groups of four (T = 1 never enters the four-wide loop, the other lengths are 3 mod 4)
+SHAPES = [(64, 1), (64, 15), (64, 255), (320, 1), (320, 15), (320, 255), (64, 5), (320, 9), (256, 5)]
 
 
 @pytest.mark.gpu
@@ -582,6 +584,40 @@ def test_staging_is_not_the_reverbs(pkg):
     both, rev, drc = run(True, True), run(True, False), run(False, True)
     assert both[0::2] == rev, "the reverb rows changed beside a direct batch"
     assert both[1::2] == drc, "the direct rows changed beside a reverb batch"
+
+
+@pytest.mark.gpu
+def test_staging_grows_on_one_side_only(pkg):
+    """shape X = 256 sources at frame 16, then shape Y = 8 other sources at frame 640, then X, then Y, in one context: every call's
+    output equals that of the same callbacks run alone in a fresh context.  The staging of a call of `count` rows of frame F is
+    (blocks 256-byte aligned; an item is 64 bytes, a plan 48, a row 8 F)
+      pinned  items [count] | in [count] rows | out [count] rows | mix, one row
+      device  items [count] | in [count] rows | plans [count] | out [count] rows | mix, one row
+    X: 16 384 + 32 768 + 32 768 + 128 = 82 048 pinned, 16 384 + 32 768 + 12 288 + 32 768 + 128 = 94 336 device;
+    Y: 512 + 40 960 + 40 960 + 5 120 = 87 552 pinned, 512 + 40 960 + 512 + 40 960 + 5 120 = 88 064 device.
+    From X to Y the pinned side has to grow while the device side must keep its 94 336 bytes: a pair reallocated to what Y asks
+    for, its capacities then taken for X's, would let the next X overrun the device block."""
+    taps, gains = 15, np.ones(8, np.float32)
+    shapes = {"X": (256, 16), "Y": (8, 640)}
+    rng = np.random.default_rng(0x51DE)
+    calls = [(name, noise(rng, *shapes[name])) for name in "XYXY"]
+
+    def run(names):
+        ctx = pkg.Context(num_bands=1)
+        srcs = {}
+        for name in names:
+            count, frame = shapes[name]
+            srcs[name] = [ctx.create_source() for _ in range(count)]
+            for s in srcs[name]:
+                ctx.direct_render_init(s, frame, taps, 0.01)
+        outs = [ctx.direct_render_process_batch(srcs[name], blk, [(0.002, gains)] * len(srcs[name]), want_mix=True)
+                for name, blk in calls if name in names]
+        ctx.close()
+        return [out.tobytes() + mix.tobytes() for out, mix in outs]
+
+    both, x, y = run("XY"), run("X"), run("Y")
+    assert both[0::2] == x, "the rows of shape X changed beside calls of shape Y"
+    assert both[1::2] == y, "the rows of shape Y changed beside calls of shape X"
 
 
 @pytest.mark.gpu

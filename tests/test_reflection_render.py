@@ -299,7 +299,9 @@ def bank_schedule(rng):
     ]
 
 
-SHAPES = [(64, 1), (64, 15), (64, 255), (320, 15), (320, 255)]   # F = 64: a partial tile; 320: a full tile and a partial one
+# F = 64: a partial tile; 256: exactly one tile; 320: a full tile and a partial one.  T = 5, 9: one tail step behind one and two full
+# groups of four (T = 1 never enters the four-wide loop, the other lengths are 3 mod 4)
+SHAPES = [(64, 1), (64, 15), (64, 255), (320, 15), (320, 255), (64, 5), (320, 9), (256, 5)]
 
 
 @pytest.mark.gpu
