@@ -26,12 +26,40 @@ is FRAGILE: whether a plane cuts the ray's range at all is decided by the distan
 plane, wrong by e (across the wall a node sits on: by rounding only, the node is coord +- offset there); whether the
 crossing lies inside the rectangle by the in-plane margin, wrong by (e + t 3e-7) / |d . n|.  A pair with a fragile decision
 is flagged and the tests leave it out (they bound how many there may be).
+
+Three modes have no line of the reference behind them: the build owns them, and their definition is the prose of
+include/frequensee.h (the comments of FS_FLAG_ALL_CONNECTIONS, FS_FLAG_MIS_BALANCE, FS_FLAG_MATERIAL_LOBES) and of DESIGN.md
+section 8 (rows "f3" and "f4 (lobes in the walk)").  The model's part for them is written from that prose, again not from
+oracle/fs_oracle.c or the kernels, and shares with the build exactly this and nothing else:
+
+  lobes in the walk   the table made at commit from the float32 arrays (Refl = 1 - alpha, tau clamped to Refl + tau <= 1, gains
+                      diffuse Refl sigma, specular Refl (1 - sigma), transmitted tau; probability = band mean of a gain / the sum
+                      of the three means, diffuse 1 when that sum is 0); word 3 of the bounce's block 0 picks the lobe at a
+                      vertex reached by a hit on a material, intervals in the order diffuse, specular, transmitted; specular = the
+                      arriving direction mirrored at the stored normal, transmitted = the arriving direction continued from
+                      pos - 2 offset n; probability x lobe probability (specular, transmitted: roulette x lobe probability);
+                      EvaluatePath takes the gain of the lobe a vertex was LEFT by (diffuse over pi), the diffuse gain over pi at
+                      both connection vertices
+  all prefixes        every (i, j) of a pair is the candidate path F0..Fi, Bj..B0 with the weight 1 / N(i + j),
+                      N(t) = #{(i', j') in [0, D]^2, i' + j' = t}, D = depth (infinite for depth 0), applied to the clamped gain
+  balance heuristic   w = p_i / sum_s p_s over s in [max(0, t - D), min(t, D)] with the densities of DESIGN.md section 8, strategy
+                      by strategy; the uniform weight instead when a segment has l^2 <= 1e-8 or the ratio is not positive
+                      and finite
+
+A contribution (i, j) is flagged iff a decision of turns 0..i-1 of the forward walk, of turns 0..j-1 of the backward walk, its
+own connection, a MinSeg or bin-edge test of its path or a weight fallback is fragile: walk() reports fragility per turn.
+Whether a deposit of next to no energy is there at all (float32's range ends at 1.2e-38) is one more such decision
+(evaluate_candidate).  The frames of these modes carry the bound PER AXIS (Params.axis_bounds, Scene._candidates_by_axis): the
+scalar rule above multiplies by 1 / cos at every hit and passes the room's size after 10 ... 14 turns, the per-axis rule follows
+the float32 walk's real drift (1e-3 cm after 30 turns) closely enough for walks of 30 ... 40 turns.  The default mode keeps the
+scalar rule, and with it its results bit for bit.
 """
 import math
 import struct
 
 MASK = 0xFFFFFFFF
 NO_MATERIAL = None
+LOBE_DIFFUSE, LOBE_SPECULAR, LOBE_TRANSMIT = 0, 1, 2
 
 
 def f32(x):
@@ -78,6 +106,8 @@ class Params:
         self.sound_speed = 343.0             # :362
         self.air_absorption = [f32(0.05)] * bands   # :395
         self.cosine = False                  # the build's cosine-weighted map instead of VRandCone(n, 90 deg)
+        self.lobes = False                   # FS_FLAG_MATERIAL_LOBES: Scene.set_lobes gives the table
+        self.axis_bounds = False             # the walk's bound per axis (Scene._candidates_by_axis) instead of the scalar one
         self.bin_size_ms = 1
         self.num_bins = 1000                 # FSAC.h:137
         for k, v in kw.items():
@@ -109,6 +139,35 @@ class Scene:
         self.rects = list(rects)
         self.absorption = [list(map(float, row)) for row in absorption]   # [materials][bands]: Absorption[b].Value
         self.bands = len(self.absorption[0])
+        self.lobe_gain = self.lobe_prob = None
+
+    def set_lobes(self, transmission, scattering):
+        """the lobe table of FS_FLAG_MATERIAL_LOBES from the FLOAT32 values of Absorption / Transmission / Scattering
+        [materials][bands]: lobe_gain[m][lobe][b], lobe_prob[m][lobe], lobes in the order diffuse, specular, transmitted"""
+        self.lobe_gain, self.lobe_prob = [], []
+        for a_row, t_row, s_row in zip(self.absorption, transmission, scattering):
+            gains = [[], [], []]
+            for a, tau, sigma in zip(a_row, t_row, s_row):
+                refl = 1.0 - f32(a)
+                tau = min(f32(tau), 1.0 - refl)                          # Refl + tau <= 1
+                gains[LOBE_DIFFUSE].append(refl * f32(sigma))
+                gains[LOBE_SPECULAR].append(refl * (1.0 - f32(sigma)))
+                gains[LOBE_TRANSMIT].append(tau)
+            means = [sum(g) / len(g) for g in gains]
+            total = sum(means)
+            self.lobe_gain.append(gains)
+            self.lobe_prob.append([m / total for m in means] if total > 0.0 else [1.0, 0.0, 0.0])
+
+    def pick_lobe(self, material, u):
+        """the lobe of the uniform u: [0, P_d) diffuse, [P_d, P_d + P_s) specular, the rest transmitted -> (lobe, its
+        probability, fragile: u within 1e-6 of a threshold)"""
+        pd, ps, pt = self.lobe_prob[material]
+        fragile = abs(u - pd) < 1e-6 or abs(u - (pd + ps)) < 1e-6
+        if u < pd:
+            return LOBE_DIFFUSE, pd, fragile
+        if u < pd + ps:
+            return LOBE_SPECULAR, ps, fragile
+        return LOBE_TRANSMIT, pt, fragile
 
     def triangles(self, n=1):
         """every rectangle as n x n cells of two triangles (v0, v0 + e1, v0 + e2) -> ([T][3][3] coordinates, [T] material ids
@@ -135,6 +194,8 @@ class Scene:
         bound at the hit).  e: the bound of the node at o, own: the axis of that node's normal (ACROSS its own wall a node is
         coord +- offset, wrong by float32 rounding only, at most 1e-3 cm at these sizes: the bound is an in-plane matter);
         e_far, far_own: the same for the node the segment ends at (a connection), None for a ray that just ends at tmax"""
+        if isinstance(e, tuple):
+            return self._candidates_by_axis(o, d, tmax, e, e_far)
         out = []
         e_all = e + (e_far or 0.0)
         for r in self.rects:
@@ -157,6 +218,43 @@ class Scene:
             thr = 4.0 * (e_hit - 2e-4) + 1e-3
             out.append((t, r, m >= 0.0 and 0.0 < t <= tmax, clear and s0 * s1 < 0.0 and m > thr,
                         (clear and s0 * s1 > 0.0) or m < -thr, thr, e_hit))
+        return out
+
+    def _candidates_by_axis(self, o, d, tmax, E, E_far):
+        """_candidates with a bound PER AXIS, E = (Ex, Ey, Ez) (Params.axis_bounds).  The scalar rule divides the whole bound by
+        |d . n| at every hit, the worst case of every bounce at once, and so passes the room's size after 10 ... 14 turns while
+        the float32 walk is still within 1e-3 cm of this one.  To first order a node displaced by delta, its ray's direction
+        unchanged (the cone sample depends on the axis-aligned normal alone, the mirrored and the continued direction on the
+        arriving one), crosses the plane x[a] = coord displaced by delta_w - (d_w / d_a) delta_a along the in-plane axis w:
+
+            E'_w = E_w + |d_w / d_a| E_a + t 3e-7 / |d_a| + 2e-4,    E'_a = 1e-3
+
+        (3e-7, 2e-4, 1e-3: the direction's error, a coordinate's rounding, the rounding across the node's own wall, as in the
+        scalar rule).  Across its own wall a node HAS E_a = 1e-3, so the own-axis exception needs no case of its own.  For a
+        connection both ends move: the crossing by at most the sum of what each end alone would move it."""
+        out = []
+        Ea = tuple(E[i] + E_far[i] for i in range(3)) if E_far is not None else E
+        for r in self.rects:
+            a, u, v = r.axis, r.u, r.v
+            da = d[a]
+            if da == 0.0:
+                continue
+            t = (r.coord - o[a]) / da
+            pu, pv = o[u] + t * d[u], o[v] + t * d[v]
+            mu, mv = min(pu - r.ulo, r.uhi - pu), min(pv - r.vlo, r.vhi - pv)
+            s0 = o[a] - r.coord
+            s1 = s0 + tmax * da
+            e1 = E[a] if E_far is None else E_far[a]
+            clear = abs(s0) > 4.0 * E[a] + 1e-3 and abs(s1) > 4.0 * (e1 + tmax * 3e-7) + 1e-3
+            along = abs(t) * 3e-7 / abs(da)
+            eu = Ea[u] + abs(d[u] / da) * Ea[a] + along
+            ev = Ea[v] + abs(d[v] / da) * Ea[a] + along
+            tu, tv = 4.0 * eu + 1e-3, 4.0 * ev + 1e-3
+            thr = max(tu, tv, 4.0 * (Ea[a] / abs(da) + along) + 1e-3)      # (of t: where along the ray the plane is met)
+            bound = [0.0, 0.0, 0.0]
+            bound[a], bound[u], bound[v] = 1e-3, eu + 2e-4, ev + 2e-4
+            out.append((t, r, min(mu, mv) >= 0.0 and 0.0 < t <= tmax, clear and s0 * s1 < 0.0 and mu > tu and mv > tv,
+                        (clear and s0 * s1 > 0.0) or mu < -tu or mv < -tv, thr, tuple(bound)))
         return out
 
     def closest(self, o, d, tmax, e=0.0, own=None):
@@ -235,10 +333,18 @@ def sample_cone(n, U, V, cosine):
 
 # ---- GeneratePath ----------------------------------------------------------------------------------------------------------------------
 class Node:
-    __slots__ = ("pos", "normal", "material", "prob", "bound")
+    """arrive: the direction of the ray whose HIT made the node (None for an end point and for the duplicate node a miss
+    pushes); lobe: the lobe the walk left the node by, picked: whether it picked one (lobe mode)"""
+    __slots__ = ("pos", "normal", "material", "prob", "bound", "arrive", "lobe", "picked")
 
-    def __init__(self, pos, normal, material, prob, bound=0.0):
+    def __init__(self, pos, normal, material, prob, bound=0.0, arrive=None):
         self.pos, self.normal, self.material, self.prob, self.bound = pos, normal, material, prob, bound
+        self.arrive, self.lobe, self.picked = arrive, LOBE_DIFFUSE, False
+
+
+def scalar_bound(bound):
+    """a node's bound as one number: itself, or the sum of the per-axis bounds (no less than their norm)"""
+    return bound[0] + bound[1] + bound[2] if isinstance(bound, tuple) else bound
 
 
 def own_axis(node):
@@ -252,6 +358,8 @@ def step(scene, prm, pair, side, k, node):
     words = draw(prm.seed, pair, side, k, 0)
     if prm.russian_roulette and not (u01(words[0]) < prm.rr_prob):       # :301-302, :349-353
         return None
+    if prm.lobes and node.arrive is not None and node.material is not NO_MATERIAL:
+        return _lobe_step(scene, prm, words, node)       # (an end point, a vertex without material and the duplicate node do not pick)
     if node.normal is None:                                              # CurrentNormal.IsNearlyZero() :306
         d, fragile = sample_sphere(prm.seed, pair, side, k, words)
         prob = prm.rr_prob / (4.0 * math.pi)                             # :309-310
@@ -259,19 +367,48 @@ def step(scene, prm, pair, side, k, node):
         d, cos_theta = sample_cone(node.normal, u01(words[1]), u01(words[2]), prm.cosine)
         fragile = False
         prob = prm.rr_prob * cos_theta / math.pi                         # :316-317
-    rect, t, fr, bound = scene.closest(node.pos, d, prm.max_trace_dist, node.bound, own_axis(node))   # :340-342
+    return _trace(scene, prm, node, node.pos, d, prob, fragile)
+
+
+def _trace(scene, prm, node, origin, d, prob, fragile):
+    rect, t, fr, bound = scene.closest(origin, d, prm.max_trace_dist, node.bound, own_axis(node))   # :340-342
     fragile = fragile or fr
     if rect is None:
         return Node(node.pos, node.normal, node.material, prob, node.bound), fragile, False
     n = FLIPPED[rect.axis] if d[rect.axis] > 0.0 else WINDING[rect.axis]  # ImpactNormal faces the side the ray came from
-    pos = tuple(node.pos[i] + t * d[i] + prm.surface_offset * n[i] for i in range(3))   # :345
-    return Node(pos, n, rect.material, prob, bound), fragile, True        # :346-347
+    pos = tuple(origin[i] + t * d[i] + prm.surface_offset * n[i] for i in range(3))   # :345
+    return Node(pos, n, rect.material, prob, bound, arrive=d), fragile, True   # :346-347
 
 
-def walk(scene, prm, pair, side, start):
+def _lobe_step(scene, prm, words, node):
+    """the turn behind a vertex that a hit on a material made, in lobe mode: word 3 (the cone sample leaves it unused) picks
+    the lobe the walk leaves `node` by, and the node keeps it for EvaluatePath"""
+    node.lobe, lobe_prob, fragile = scene.pick_lobe(node.material, u01(words[3]))
+    node.picked = True
+    n, a, origin = node.normal, node.arrive, node.pos
+    if node.lobe == LOBE_DIFFUSE:
+        d, cos_theta = sample_cone(n, u01(words[1]), u01(words[2]), prm.cosine)
+        prob = prm.rr_prob * cos_theta / math.pi * lobe_prob
+    else:
+        prob = prm.rr_prob * lobe_prob
+        if node.lobe == LOBE_SPECULAR:
+            dn = a[0] * n[0] + a[1] * n[1] + a[2] * n[2]
+            d = tuple(a[i] - 2.0 * dn * n[i] for i in range(3))
+        else:
+            # the far side of the surface, 0.1 cm BEYOND the node's own wall.  The own-axis rule of Scene._candidates holds as it
+            # stands: across that wall the origin is coord - offset where the node was coord + offset, still the wall's
+            # coordinate and a constant, wrong by float32 rounding only, and 0.1 cm clears the 5e-3 cm the rule asks for; in the
+            # wall's plane the origin is the node, with the node's bound
+            d = a
+            origin = tuple(node.pos[i] - 2.0 * prm.surface_offset * n[i] for i in range(3))
+    return _trace(scene, prm, node, origin, d, prob, fragile)
+
+
+def walk(scene, prm, pair, side, start, turns=None):
     """ARTS.cpp:279-355 -> (nodes, fragile).  Node k is pushed with the probability the PREVIOUS turn computed (:297), before
-    the cap and the roulette; a turn that misses pushes the same place again."""
-    node = Node(tuple(float(x) for x in start), None, NO_MATERIAL, 1.0)  # :287-291
+    the cap and the roulette; a turn that misses pushes the same place again.  turns: a list that receives, per turn k (the
+    one that makes node k + 1), whether a decision of it was fragile."""
+    node = Node(tuple(float(x) for x in start), None, NO_MATERIAL, 1.0, (0.0, 0.0, 0.0) if prm.axis_bounds else 0.0)  # :287-291
     nodes, fragile, k = [], False, 0
     cap = prm.depth if prm.depth > 0 else (None if prm.russian_roulette and prm.rr_prob < 1.0 else 64)
     while True:
@@ -283,6 +420,8 @@ def walk(scene, prm, pair, side, start):
             break
         node, fr, _ = nxt
         fragile = fragile or fr
+        if turns is not None:
+            turns.append(fr)
         k += 1
     return nodes, fragile
 
@@ -297,16 +436,17 @@ def connect(scene, prm, f, b):
     length = math.sqrt(l2)
     tmax = length - prm.connect_pullback
     if not tmax > 0.0:
-        return True, abs(tmax) < 1e-3 + 4.0 * (f.bound + b.bound)
+        return True, abs(tmax) < 1e-3 + 4.0 * (scalar_bound(f.bound) + scalar_bound(b.bound))
     d = (diff[0] / length, diff[1] / length, diff[2] / length)
     hit, fragile = scene.any_hit(f.pos, d, tmax, f.bound, own_axis(f), b.bound, own_axis(b))
     return not hit, fragile
 
 
 # ---- EvaluatePath, the bin rule ----------------------------------------------------------------------------------------------------------
-def evaluate_path_bands_f64(positions, reflectivity, has_material, probability, prm=None):
+def evaluate_path_bands_f64(positions, reflectivity, has_material, probability, prm=None, over_pi=None):
     """ARTS.cpp:358-420 for one path and B bands: positions [n][3] (cm), per node its Absorption[b].Value row [B], whether it
-    has a geometry component with a material, and its Probability -> (DelaySeconds, [Gain per band], a segment within 1e-5 of MinSeg)"""
+    has a geometry component with a material, and its Probability -> (DelaySeconds, [Gain per band], a segment within 1e-5 of MinSeg).
+    over_pi (lobe mode): per node whether its row is divided by pi (a diffuse gain) or taken as it is (specular, transmitted)"""
     prm = prm or Params(bands=len(reflectivity[0]))
     B = len(prm.air_absorption)
     energy, scaled, near = [1.0] * B, 0.0, False
@@ -320,6 +460,8 @@ def evaluate_path_bands_f64(positions, reflectivity, has_material, probability, 
         pw = probability[i] ** prm.prob_exponent                                        # :398
         for b in range(B):
             bsdf = reflectivity[i][b] / math.pi if has_material[i] else 1.0             # :382-386
+            if over_pi is not None and has_material[i] and not over_pi[i]:
+                bsdf = reflectivity[i][b]
             e = energy[b]
             e *= bsdf                                                                   # :392
             e *= geometry                                                               # :393
@@ -340,6 +482,192 @@ def near_bin_edge(delay_seconds, bin_size_ms=1, rel=2e-5):
     return abs(x - round(x)) < rel * max(abs(x), 1.0)
 
 
+# ---- the build-owned modes: lobe gains along a path, all prefixes, their weights -------------------------------------------------------------
+def evaluate_candidate(scene, prm, fwd, bwd):
+    """EvaluatePath of the candidate path fwd[0] .. fwd[-1], bwd[-1] .. bwd[0] -> (DelaySeconds, [Gain per band], near MinSeg).
+    In lobe mode a vertex contributes the gain of the lobe the walk left it by, the two connection vertices fwd[-1] and bwd[-1]
+    the diffuse gain (they were not left along the path: a delta lobe cannot be connected)."""
+    path = list(fwd) + list(bwd)[::-1]
+    ci = len(fwd) - 1
+    refl, over_pi = [], []
+    for idx, n in enumerate(path):
+        if n.material is NO_MATERIAL:
+            refl.append(None)
+            over_pi.append(True)
+        elif prm.lobes:
+            lobe = LOBE_DIFFUSE if idx in (ci, ci + 1) else n.lobe
+            refl.append(scene.lobe_gain[n.material][lobe])
+            over_pi.append(lobe == LOBE_DIFFUSE)
+        else:
+            refl.append(scene.absorption[n.material])
+            over_pi.append(True)
+    delay, gains, near = evaluate_path_bands_f64([n.pos for n in path], refl, [x is not None for x in refl], [n.prob for n in path], prm,
+                                                 over_pi)
+    # whether a deposit is there at all is a discrete decision too: the build multiplies the factors in float32, whose normal
+    # range ends at 1.2e-38, so the energy of a path of some 40 segments is inexact or zero there.  1e-36 leaves a factor of 100
+    # for the division by Probability^0.1 (at most some 2 per segment) that follows a segment's smallest intermediate product
+    tiny = any(0.0 < g < 1e-36 * prm.energy_gain for g in gains)
+    return delay, gains, near or tiny
+
+
+def strategy_range(t, depth):
+    """the strategies s = i of a path with t = i + j surface vertices that a depth cap D leaves: [max(0, t - D), min(t, D)];
+    D is infinite for depth 0"""
+    return (0, t) if depth <= 0 else (max(0, t - depth), min(t, depth))
+
+
+def strategies(t, depth):
+    """N(t) = #{(i', j') in [0, D]^2, i' + j' = t}"""
+    lo, hi = strategy_range(t, depth)
+    return hi - lo + 1
+
+
+COSINE_FLOOR = 1e-6      # an own cosine below it makes the strategy's density next to nothing: next to the `ratio` fallback
+
+
+def balance_weight(path, s, depth):
+    """The balance heuristic of DESIGN.md section 8 for the connected path y_0 (source), y_1 .. y_t (surface vertices with their
+    stored normals), y_{t+1} (listener), produced by strategy s (y_1 .. y_s from the source, the rest from the listener), written
+    out strategy by strategy -> (weight, fallback, fragile); fallback: None, "segment" (a segment with l^2 <= 1e-8) or "ratio" (the
+    ratio not positive or not finite): the uniform weight 1 / N(t) then.
+
+      d_k = unit(y_{k+1} - y_k), L_k = |y_{k+1} - y_k|
+      pf_k = Pf(k) |n_{k+1} . d_k| / L_k^2,  Pf(0) = 1 / 4 pi,     Pf(k) = max(0, n_k . d_k) / pi
+      pb_k = Pb(k + 1) |n_k . d_k| / L_k^2,  Pb(t + 1) = 1 / 4 pi, Pb(k) = max(0, -n_k . d_{k-1}) / pi
+      p_s = prod_{k < s} pf_k  prod_{k > s} pb_k,    w = p_i / sum_{s in [lo, hi]} p_s
+
+    Fragile: a segment that is not exactly of length 0 (the duplicate node is a copy) but shorter than 1e-3 cm + 4 x its nodes'
+    bounds, an own density (p_s of the strategy s itself) that a cosine of |c| < COSINE_FLOOR makes next to nothing, or one below
+    1e-280 (see there).  A cosine of 0 in ANOTHER strategy's density (a connection along a wall: both nodes have the wall's
+    coordinate +- offset) is no decision: max(0, c) is continuous, that strategy just has no density."""
+    t = len(path) - 2
+    lo, hi = strategy_range(t, depth)
+    uniform = 1.0 / (hi - lo + 1)
+    seg, fragile = [], False
+    for k in range(t + 1):
+        diff = [path[k + 1].pos[i] - path[k].pos[i] for i in range(3)]
+        l2 = diff[0] * diff[0] + diff[1] * diff[1] + diff[2] * diff[2]
+        if l2 != 0.0 and math.sqrt(l2) < 1e-3 + 4.0 * (scalar_bound(path[k].bound) + scalar_bound(path[k + 1].bound)):
+            fragile = True
+        if not l2 > 1e-8:
+            return uniform, "segment", fragile
+        length = math.sqrt(l2)
+        seg.append(((diff[0] / length, diff[1] / length, diff[2] / length), l2))
+
+    def cos(k, j):      # n_k . d_j, 0 for an end point (never asked for in a product that is used)
+        n = path[k].normal
+        return 0.0 if n is None else n[0] * seg[j][0][0] + n[1] * seg[j][0][1] + n[2] * seg[j][0][2]
+
+    def pf(k):
+        P = 1.0 / (4.0 * math.pi) if k == 0 else max(0.0, cos(k, k)) / math.pi
+        return P * abs(cos(k + 1, k)) / seg[k][1]
+
+    def pb(k):
+        P = 1.0 / (4.0 * math.pi) if k == t else max(0.0, -cos(k + 1, k)) / math.pi
+        return P * abs(cos(k, k)) / seg[k][1]
+
+    def p(sp):
+        v = 1.0
+        for k in range(sp):
+            v *= pf(k)
+        for k in range(sp + 1, t + 1):
+            v *= pb(k)
+        return v
+
+    own = [cos(k, k) for k in range(1, s)] + [cos(k + 1, k) for k in range(s)] + \
+          [cos(k + 1, k) for k in range(s + 1, t)] + [cos(k, k) for k in range(s + 1, t + 1)]
+    fragile = fragile or any(abs(c) < COSINE_FLOOR for c in own)
+    total = sum(p(sp) for sp in range(lo, hi + 1))
+    # a product of more than some 40 densities (1e-7 each at these sizes) leaves the range of a double, and WHERE it does depends
+    # on the order of the multiplications, which the definition shares with no one-pass evaluation: next to the range's end it
+    # is a discrete decision with an unknown threshold
+    fragile = fragile or not p(s) > 1e-280
+    ratio = p(s) / total if total > 0.0 else math.nan
+    if not (ratio > 0.0 and math.isfinite(ratio)):
+        return uniform, "ratio", fragile
+    return ratio, None, fragile
+
+
+class Contribution:
+    __slots__ = ("i", "j", "visible", "fragile", "bin", "energy", "fallback")
+
+
+class PrefixPair:
+    __slots__ = ("fwd", "bwd", "steps", "connections", "contributions", "flagged")
+
+
+def prefix_pair(scene, prm, idx, src, lis, num_pairs, balance=False):
+    """a pair of the all-prefix mode: every (i, j) is the candidate path F0..Fi, Bj..B0 — connect and evaluate as for the end-to-end
+    connection, energy = Gain x weight / pairs.  Contribution (i, j) is flagged iff a turn below i of the forward walk, a turn below
+    j of the backward walk, its connection, a MinSeg or bin-edge test of its path or a weight fallback is fragile."""
+    r = PrefixPair()
+    tf, tb = [], []
+    r.fwd, _ = walk(scene, prm, idx, 0, src, tf)
+    r.bwd, _ = walk(scene, prm, idx, 1, lis, tb)
+    r.steps = len(r.fwd) + len(r.bwd) - 2
+    r.connections = len(r.fwd) * len(r.bwd)
+    r.contributions, r.flagged = [], 0
+    ff = [any(tf[:i]) for i in range(len(r.fwd))]
+    fb = [any(tb[:j]) for j in range(len(r.bwd))]
+    for i in range(len(r.fwd)):
+        for j in range(len(r.bwd)):
+            c = Contribution()
+            c.i, c.j, c.bin, c.energy, c.fallback = i, j, None, None, None
+            c.visible, fc = connect(scene, prm, r.fwd[i], r.bwd[j])
+            c.fragile = ff[i] or fb[j] or fc
+            if c.visible:
+                delay, gains, near = evaluate_candidate(scene, prm, r.fwd[:i + 1], r.bwd[:j + 1])
+                if balance:
+                    w, c.fallback, fw = balance_weight(r.fwd[:i + 1] + r.bwd[j::-1], i, prm.depth)
+                else:
+                    w, fw = 1.0 / strategies(i + j, prm.depth), False
+                c.bin = bin_of(delay, prm.bin_size_ms, prm.num_bins)
+                c.energy = [g * w / num_pairs for g in gains]
+                c.fragile = c.fragile or near or near_bin_edge(delay, prm.bin_size_ms) or fw
+            r.flagged += c.fragile
+            r.contributions.append(c)
+    return r
+
+
+class PrefixFrame:
+    """what an all-prefix frame deposits, by the model: H [B][bins] summed over the contributions that are not flagged, count =
+    their number per bin, flagged = the number of flagged contributions, deposits = the visible ones among the others,
+    connections = sum over the pairs of (kf + 1)(km + 1) and steps = the rays of all walks (both exact); what the frame
+    exercised: fallbacks by kind, lobes picked by kind, the largest number of prefix combinations of a pair"""
+
+    def __init__(self, scene, prm, src, lis, num_pairs, balance=False, keep_pairs=False):
+        self.H = [[0.0] * prm.num_bins for _ in range(scene.bands)]
+        self.count = [0] * prm.num_bins
+        self.flagged, self.deposits, self.steps, self.connections, self.pairs = 0, 0, 0, 0, []
+        self.fallbacks = {"segment": 0, "ratio": 0}
+        self.lobes = [0, 0, 0]
+        self.most_combinations = self.pairs_over_64 = 0
+        for i in range(num_pairs):
+            r = prefix_pair(scene, prm, i, src, lis, num_pairs, balance)
+            self.steps += r.steps
+            self.connections += r.connections
+            self.flagged += r.flagged
+            self.most_combinations = max(self.most_combinations, r.connections)
+            self.pairs_over_64 += r.connections > 64
+            count_lobes(self.lobes, r.fwd + r.bwd)
+            if keep_pairs:
+                self.pairs.append(r)
+            for c in r.contributions:
+                if c.fallback:
+                    self.fallbacks[c.fallback] += 1
+                if c.visible and not c.fragile:
+                    self.deposits += 1
+                    self.count[c.bin] += 1
+                    for b in range(scene.bands):
+                        self.H[b][c.bin] += c.energy[b]
+
+
+def count_lobes(counts, nodes):
+    for n in nodes:
+        if n.picked:
+            counts[n.lobe] += 1
+
+
 # ---- one pair, one frame -----------------------------------------------------------------------------------------------------------------
 class Pair:
     __slots__ = ("fwd", "bwd", "steps", "visible", "fragile", "delay", "bin", "energy")
@@ -357,9 +685,12 @@ def pair(scene, prm, i, src, lis, num_pairs):
     r.delay, r.bin, r.energy = None, None, None
     if r.visible:
         path = r.fwd + r.bwd[::-1]                                                      # :262-267
-        refl = [scene.absorption[n.material] if n.material is not NO_MATERIAL else None for n in path]
-        r.delay, gains, near = evaluate_path_bands_f64([n.pos for n in path], refl, [x is not None for x in refl],
-                                                       [n.prob for n in path], prm)
+        if prm.lobes:
+            r.delay, gains, near = evaluate_candidate(scene, prm, r.fwd, r.bwd)
+        else:
+            refl = [scene.absorption[n.material] if n.material is not NO_MATERIAL else None for n in path]
+            r.delay, gains, near = evaluate_path_bands_f64([n.pos for n in path], refl, [x is not None for x in refl],
+                                                           [n.prob for n in path], prm)
         r.bin = bin_of(r.delay, prm.bin_size_ms, prm.num_bins)
         r.energy = [g / num_pairs for g in gains]                                       # :164, :170
         r.fragile = r.fragile or near or near_bin_edge(r.delay, prm.bin_size_ms)
@@ -375,9 +706,11 @@ class Frame:
         self.H = [[0.0] * prm.num_bins for _ in range(scene.bands)]
         self.count = [0] * prm.num_bins                     # deposits per bin behind H
         self.flagged, self.deposits, self.steps, self.pairs = [], 0, 0, []
+        self.connections, self.lobes = num_pairs, [0, 0, 0]      # (lobe mode: the lobes picked, by kind)
         for i in range(num_pairs):
             r = pair(scene, prm, i, src, lis, num_pairs)
             self.steps += r.steps
+            count_lobes(self.lobes, r.fwd + r.bwd)
             if keep_pairs:
                 self.pairs.append(r)
             if r.fragile:

@@ -24,12 +24,25 @@ relative difference in a good entry is 3e-7 ... 9e-7 (1.2e-6 in deterministic mo
 (0.09 %), 7 more deposits than the model's unflagged ones, 5 bad bins, and 3.3e-5 as its largest difference (ENERGY_RTOL = 4e-5:
 the oracle differs from the model by the same 3.3e-5 there.  It is no evaluation error but the float32 walk's drift: after a
 grazing bounce one path's last node lies 0.056 cm from the model's, which changes 1 / d^2 of its 29.6 m segment by 3.8e-5).
+
+The build-owned modes (FS_FLAG_ALL_CONNECTIONS, FS_FLAG_MIS_BALANCE, FS_FLAG_MATERIAL_LOBES) are frames of MANY contributions
+per pair: Fr is then the set of flagged contributions (i, j), C = the sum over the pairs of (kf + 1)(km + 1) replaces P in
+connections_tested == C, D counts the unflagged contributions that deposit, and the tolerance is the mode's (MODES in
+tests/test_independent_restatement.py: 4 x what oracle and model differ by on the CPU).  A flagged contribution can still only add
+one deposit of at most energy_gain energy_clamp / P, its weight being at most 1.
+Measured on an MI355X, 1024 pairs: uniform and balance-heuristic weights at depth 4: 3 flagged of 16 919, 7 866 deposits against
+the model's 7 863 unflagged, no bad bin; at depth 8: 24 flagged of 37 339, 21 664 against 21 643, one bad bin; lobes at depth 4 / 8:
+1 / 3 flagged pairs, deposits equal, no bad bin, largest difference of a good entry 6e-7 / 6e-6; lobes with all prefixes: 30
+flagged, 4 more deposits, one bad bin.  In the all-prefix frames the largest difference of an entry that is not bad is 6e-5 ...
+1.9e-4: the deposit of a flagged contribution that stays below the tolerance of an occupied bin (the oracle's frame differs
+from H by the same 1.92e-4 in the same bin); deposits and counters equal the oracle's in every frame.
 """
 import numpy as np
 import pytest
 
 import restate_walk as rw
-from test_independent_restatement import ENERGY_RTOL, model_frame
+from test_independent_restatement import (ENERGY_RTOL, LOBE_SIGMA, LOBE_TAU, LOBES, MODES, flagged_contributions, mode_frame, mode_rtol,
+                                          model_frame)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,14 +53,17 @@ GAIN = 10.0                        # energy_gain of the model's frames (the refe
 _ctx = {}
 
 
-def context(pkg, cut, fast=False, bands=4, pipelining=0, tag=""):
-    """a context with the test scene's rectangles cut into cut x cut cells, kept for the other tests of the module"""
-    key = (cut, fast, bands, pipelining, tag)
+def context(pkg, cut, fast=False, bands=4, pipelining=0, tag="", lobes=False):
+    """a context with the test scene's rectangles cut into cut x cut cells, kept for the other tests of the module; lobes: with
+    the Transmission / Scattering arrays of tests/test_independent_restatement.py"""
+    key = (cut, fast, bands, pipelining, tag, lobes)
     if key not in _ctx:
         sc = rw.make_test_scene()
         tri, mat = sc.triangles(cut)
         ctx = pkg.Context(num_bands=bands)
-        ctx.set_scene(np.asarray(tri, np.float32), np.asarray(mat, np.uint16), np.asarray(sc.absorption, np.float32)[:, :bands], fast=fast)
+        arrays = [np.asarray(a, np.float32)[:, :bands] for a in (LOBE_TAU, LOBE_SIGMA)] if lobes else [None, None]
+        ctx.set_scene(np.asarray(tri, np.float32), np.asarray(mat, np.uint16), np.asarray(sc.absorption, np.float32)[:, :bands],
+                      transmission=arrays[0], scattering=arrays[1], fast=fast)
         ctx.set_listener(rw.LISTENER)
         if pipelining:
             ctx.set_pipelining(pipelining)
@@ -62,17 +78,20 @@ def expected(depth, roulette=True, cosine=False, pairs=1024):
     return fr
 
 
-def check_frame(pkg, ctx, src, fr, pairs, depth, roulette=True, flags=0, gain=GAIN, bands=4):
+def check_frame(pkg, ctx, src, fr, pairs, depth, roulette=True, flags=0, gain=GAIN, bands=4, rtol=ENERGY_RTOL):
+    """fr: a frame of the model, of one contribution per pair (rw.Frame: C = pairs) or of many (rw.PrefixFrame: C = the sum of
+    (kf + 1)(km + 1)); nfr = its flagged contributions, each of which can only ADD one deposit of at most gain clamp / pairs (a
+    weight is at most 1) somewhere"""
     p = pkg.default_params(num_rays=2 * pairs, depth=depth, seed=SEED, russian_roulette=int(roulette), flags=flags, energy_gain=gain)
     ctx.reset_stats()
     G = ctx.compute_energy_response(src, p).astype(np.float64)
     st = ctx.stats()
-    nfr = len(fr.flagged)
+    nfr = flagged_contributions(fr)
     assert st["segments"] == st["planned_segments"] == fr.steps
-    assert st["connections_tested"] == pairs
+    assert st["connections_tested"] == fr.connections
     assert abs(st["deposits"] - fr.deposits) <= nfr, (st["deposits"], fr.deposits, nfr)
     H = np.asarray(fr.H, np.float64)[:bands] * (gain / GAIN)           # (the gain is the last factor of a deposit: H is linear in it)
-    allow = ENERGY_RTOL * H + 1e-30
+    allow = rtol * H + 1e-30
     if flags & DET:   # every deposit is rounded to the nearest multiple of 2^-40 (include/frequensee.h): half a quantum each
         allow = allow + np.asarray(fr.count, np.float64)[None, :] * 2.0 ** -41
     R = G - H
@@ -136,3 +155,53 @@ def test_dense_waves(pkg, monkeypatch, pipelining):
         for cut in (1, 8):
             ctx, src = context(pkg, cut, pipelining=pipelining, tag="dense")
             check_frame(pkg, ctx, src, fr, 1024, depth, roulette)
+
+
+# ---- the build-owned modes: all prefixes (connect_all_kernel), balance-heuristic weights, lobes in the walk ---------------------------------
+def mode_expected(mode, depth, bands=4):
+    fr = mode_frame(mode, depth, True, SEED, 1024, gain=GAIN, bands=bands)
+    assert flagged_contributions(fr) <= 0.02 * fr.connections      # a condition on the inputs, checked before the GPU is used
+    assert fr.deposits > 1024 // 10
+    return fr
+
+
+def check_mode_frame(pkg, ctx, src, fr, mode, depth, flags=0, **kw):
+    check_frame(pkg, ctx, src, fr, 1024, depth, flags=MODES[mode][0] | flags, rtol=mode_rtol(mode), **kw)
+
+
+@pytest.mark.parametrize("mode,depth", [("uniform", 4), ("uniform", 8), ("balance", 4), ("balance", 8), ("lobes", 4), ("lobes", 8), ("lobes_all", 4)])
+def test_mode_frames(pkg, mode, depth):
+    """1024 pairs in the modes whose only definition is DESIGN.md section 8, against the model's restatement of it.  Uniform weights
+    at depth 4: 25 prefix combinations per pair at most, one round of connect_all_kernel's wave; at depth 8 up to 81, a second,
+    partly filled round (the model counts the pairs beyond 64 and the CPU test asserts there are some)"""
+    fr = mode_expected(mode, depth)
+    if depth == 8 and mode != "lobes":
+        assert fr.pairs_over_64 > 0
+    for cut in (1, 8):
+        ctx, src = context(pkg, cut, lobes=bool(MODES[mode][0] & LOBES))
+        check_mode_frame(pkg, ctx, src, fr, mode, depth)
+
+
+@pytest.mark.parametrize("variant", ["deterministic", "device_tree", "one_band"])
+@pytest.mark.parametrize("mode,depth", [("uniform", 8), ("lobes", 4)])
+def test_variants_of_the_mode_frames(pkg, mode, depth, variant):
+    """deterministic deposits (gain 1e6), a tree built on the device, one band.  With one band the uniform frame is band 0 of the
+    four; the lobe frame is a frame of its own, since the lobe probabilities are band means"""
+    lobes = bool(MODES[mode][0] & LOBES)
+    bands = 1 if variant == "one_band" else 4
+    fr = mode_expected(mode, depth, bands=bands if lobes else 4)
+    for cut in (1, 8):
+        ctx, src = context(pkg, cut, fast=variant == "device_tree", bands=bands, lobes=lobes)
+        check_mode_frame(pkg, ctx, src, fr, mode, depth, flags=DET if variant == "deterministic" else 0,
+                         gain=1e6 if variant == "deterministic" else GAIN, bands=bands)
+
+
+@pytest.mark.parametrize("pipelining", [0, 1], ids=["walk_kernel", "fused_launch"])
+def test_dense_waves_in_the_modes(pkg, monkeypatch, pipelining):
+    """the dense walk's stores of positions, normals and lobe bits: FS_WALK_RAYS_PER_WAVE=64 as in test_dense_waves"""
+    monkeypatch.setenv("FS_WALK_RAYS_PER_WAVE", "64")
+    for mode, depth in (("uniform", 8), ("lobes", 4)):
+        fr = mode_expected(mode, depth)
+        for cut in (1, 8):
+            ctx, src = context(pkg, cut, pipelining=pipelining, tag="dense", lobes=bool(MODES[mode][0] & LOBES))
+            check_mode_frame(pkg, ctx, src, fr, mode, depth)

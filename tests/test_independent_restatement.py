@@ -11,6 +11,9 @@ with a margin), the walk and the connection:
   GeneratePath                 Private/AudioRayTracingSubsystem.cpp:279-355   step by step on uncapped walks
   ConnectSubpaths              Private/AudioRayTracingSubsystem.cpp:235-277   verdicts; node order through whole pairs
 
+and the three modes the build owns (FS_FLAG_ALL_CONNECTIONS, FS_FLAG_MIS_BALANCE, FS_FLAG_MATERIAL_LOBES), which the model restates
+from include/frequensee.h and DESIGN.md section 8: whole frames, pair by pair, every contribution (i, j) with its own flag.
+
 The reference ships no golden vectors for this path ("parity unpinned"): what pins the oracle is hand-derived KATs
 (tests/test_oracle_kat.py) and this second, differently written implementation — two restatements that agree on
 random data are much less likely to share a misreading than one is to contain it.  The oracle computes in fp32 like
@@ -309,3 +312,244 @@ def test_whole_pairs_against_the_model(oracle_mod, depth, roulette, cosine):
         assert len(fr.flagged) <= 0.02 * 1024
         assert 100 < fr.deposits < 900
     assert worst_ratio < 1.0
+
+
+# ---- the build-owned modes: all prefixes, balance-heuristic weights, lobes in the walk -------------------------------------------------------
+# Transmission / Scattering of the test scene's two materials (its Absorption: 0.85 0.7 0.55 0.4 / 0.3 0.45 0.6 0.75).  Lobe
+# probabilities (diffuse, specular, transmitted): 0.289 0.267 0.444 and 0.316 0.297 0.387, all >= 0.2; material 1 has tau = 0.5 >
+# alpha = 0.3 in band 0, where the clamp Refl + tau <= 1 cuts it to 0.3
+LOBE_TAU = [[0.3, 0.3, 0.3, 0.3], [0.5, 0.4, 0.3, 0.2]]
+LOBE_SIGMA = [[0.4, 0.5, 0.6, 0.5], [0.6, 0.5, 0.4, 0.5]]
+
+ALLC, MIS, LOBES, COSINE = 16, 32, 64, 4       # FS_FLAG_ALL_CONNECTIONS, _MIS_BALANCE, _MATERIAL_LOBES, _COSINE_SAMPLING
+# mode -> (flags, 4 x the largest relative difference per (pair, band, bin) between oracle and model that test_mode_frames_against_
+# _the_model and test_unbounded_depth_against_the_model measure over their frames on the CPU, see the former's docstring)
+MODES = {
+    "uniform": (ALLC, 3.0e-4),             # 7.65e-5: depth 8, seed 303
+    "balance": (MIS, 6.9e-4),              # 1.73e-4: depth 8, seed 202
+    "lobes": (LOBES, 1.2e-3),              # 3.11e-4: depth 8 without roulette, seed 101
+    "lobes_all": (LOBES | ALLC, 1.1e-4),   # 2.96e-5: depth 8, seed 303
+    "lobes_cosine": (LOBES | COSINE, 2.3e-4),   # 5.89e-5: depth 8, seed 202
+}
+
+
+def mode_rtol(mode):
+    return MODES[mode][1]
+
+
+def mode_scene(oracle_mod, mode, cut=1):
+    """(the model's scene, the oracle's) with the lobe arrays where the mode has them"""
+    sc = rw.make_test_scene()
+    tri, mat = sc.triangles(cut)
+    lobes = bool(MODES[mode][0] & LOBES)
+    if lobes:
+        sc.set_lobes(LOBE_TAU, LOBE_SIGMA)
+    return sc, oracle_mod.Scene(np.asarray(tri, np.float32), np.asarray(mat, np.uint16), np.asarray(sc.absorption, np.float32),
+                                transmission=LOBE_TAU if lobes else None, scattering=LOBE_SIGMA if lobes else None)
+
+
+_mode_frames = {}
+
+
+def mode_frame(mode, depth, roulette, seed, num_pairs=1024, gain=10.0, keep_pairs=False, bands=4):
+    """the model's frame of the test scene in one of MODES, cached: the GPU tests share them.  All-prefix modes give a
+    rw.PrefixFrame, the end-to-end lobe modes a rw.Frame; both have H, count, deposits, steps, connections, lobes.  bands: the
+    first so many of the scene's four (the lobe probabilities are band means: fewer bands are another walk)"""
+    key = (mode, depth, roulette, seed, num_pairs, gain, bands)
+    if key not in _mode_frames or (keep_pairs and not _mode_frames[key].pairs):
+        flags = MODES[mode][0]
+        sc = rw.make_test_scene()
+        sc = rw.Scene(sc.rects, [row[:bands] for row in sc.absorption])
+        if flags & LOBES:
+            sc.set_lobes([row[:bands] for row in LOBE_TAU], [row[:bands] for row in LOBE_SIGMA])
+        prm = rw.Params(bands=bands, seed=seed, depth=depth, russian_roulette=roulette, cosine=bool(flags & COSINE), lobes=bool(flags & LOBES),
+                        energy_gain=gain, axis_bounds=True)
+        if flags & (ALLC | MIS):
+            fr = rw.PrefixFrame(sc, prm, rw.SOURCE, rw.LISTENER, num_pairs, balance=bool(flags & MIS), keep_pairs=keep_pairs)
+        else:
+            fr = rw.Frame(sc, prm, rw.SOURCE, rw.LISTENER, num_pairs, keep_pairs=keep_pairs)
+        _mode_frames[key] = fr
+    return _mode_frames[key]
+
+
+def flagged_contributions(fr):
+    return fr.flagged if isinstance(fr, rw.PrefixFrame) else len(fr.flagged)
+
+
+def test_strategy_counts_by_hand():
+    """N(t) = #{(i', j') in [0, D]^2, i' + j' = t}: t + 1 while the cap cuts nothing, 2 D - t + 1 beyond D, t + 1 for depth 0"""
+    assert [rw.strategies(t, 2) for t in range(5)] == [1, 2, 3, 2, 1]
+    assert [rw.strategies(t, 4) for t in range(9)] == [1, 2, 3, 4, 5, 4, 3, 2, 1]
+    assert [rw.strategies(t, 8) for t in (0, 7, 8, 9, 16)] == [1, 8, 9, 8, 1]
+    assert [rw.strategies(t, 0) for t in (0, 5, 8, 9, 100)] == [1, 6, 9, 10, 101]
+    assert rw.strategy_range(5, 4) == (1, 4) and rw.strategy_range(3, 4) == (0, 3) and rw.strategy_range(9, 0) == (0, 9)
+    for D in (1, 2, 5, 8):
+        for t in range(2 * D + 1):
+            assert rw.strategies(t, D) == sum(1 for i in range(D + 1) for j in range(D + 1) if i + j == t)
+
+
+def test_lobe_table_by_hand():
+    """alpha = 0.3, tau = 0.5, sigma = 0.6: Refl = 0.7, tau cut to 0.3, diffuse 0.42, specular 0.28, transmitted 0.3; the rows of the
+    test's arrays; a material that reflects and transmits nothing keeps the diffuse lobe; the pick's intervals and margins"""
+    sc = rw.make_test_scene()
+    sc.set_lobes(LOBE_TAU, LOBE_SIGMA)
+    g = sc.lobe_gain[1]
+    assert [g[lobe][0] for lobe in range(3)] == pytest.approx([0.42, 0.28, 0.3], rel=1e-6)      # the clamp acts
+    assert [g[lobe][3] for lobe in range(3)] == pytest.approx([0.125, 0.125, 0.2], rel=1e-6)    # and here it does not
+    assert sc.lobe_prob[0] == pytest.approx([0.195 / 0.675, 0.18 / 0.675, 0.3 / 0.675], rel=1e-6)
+    assert sc.lobe_prob[1] == pytest.approx([0.245 / 0.775, 0.23 / 0.775, 0.3 / 0.775], rel=1e-6)
+    assert all(p >= 0.2 for row in sc.lobe_prob for p in row)
+    for m in range(2):
+        for b in range(4):
+            assert sum(sc.lobe_gain[m][lobe][b] for lobe in range(3)) <= 1.0 + 1e-12
+    dead = rw.Scene(sc.rects, [[1.0, 1.0]])
+    dead.set_lobes([[0.0, 0.0]], [[0.5, 0.5]])
+    assert dead.lobe_prob == [[1.0, 0.0, 0.0]] and dead.lobe_gain[0] == [[0.0, 0.0]] * 3
+    pd, ps, pt = sc.lobe_prob[0]
+    assert sc.pick_lobe(0, 0.0) == (rw.LOBE_DIFFUSE, pd, False) and sc.pick_lobe(0, pd + 0.5 * ps) == (rw.LOBE_SPECULAR, ps, False)
+    assert sc.pick_lobe(0, 1.0 - 2.0 ** -24) == (rw.LOBE_TRANSMIT, pt, False)
+    assert sc.pick_lobe(0, pd - 1e-7)[::2] == (rw.LOBE_DIFFUSE, True) and sc.pick_lobe(0, pd + ps + 1e-7)[::2] == (rw.LOBE_TRANSMIT, True)
+
+
+def test_balance_weights_of_one_path_sum_to_one():
+    """the model's weight alone: t = 1 by hand (floor z = -100, source (0, 0, 0), vertex (50, 0, -100), listener (200, 0, 0): p_1 =
+    cos / (4 pi L0^2), p_0 = cos' / (4 pi L1^2), w_1 = L1^3 / (L0^3 + L1^3)); the weights of a path's strategies sum to 1 with and
+    without the cap cutting strategies; both fallbacks"""
+    up = (0.0, 0.0, 1.0)
+    path = [rw.Node((0.0, 0.0, 0.0), None, None, 1.0), rw.Node((50.0, 0.0, -100.0), up, 0, 1.0), rw.Node((200.0, 0.0, 0.0), None, None, 1.0)]
+    L0, L1 = math.sqrt(12500.0), math.sqrt(32500.0)
+    w1 = L1 ** 3 / (L0 ** 3 + L1 ** 3)
+    assert rw.balance_weight(path, 1, 8) == (pytest.approx(w1, rel=1e-14), None, False)
+    assert rw.balance_weight(path, 0, 8)[0] == pytest.approx(1.0 - w1, rel=1e-14)
+    assert rw.balance_weight(path, 1, 0)[0] == pytest.approx(w1, rel=1e-14)
+    assert rw.balance_weight([path[0], path[2]], 0, 8) == (1.0, None, False)
+    # a zigzag between floor z = 0 and ceiling z = 300: every vertex sees both neighbours, every strategy has a density
+    zig = [rw.Node((0.0, 0.0, 100.0), None, None, 1.0)]
+    for k in range(1, 7):
+        zig.append(rw.Node((150.0 * k, 40.0 * k * k, 300.0 * (k % 2)), (0.0, 0.0, -1.0) if k % 2 else up, 0, 1.0))
+    zig.append(rw.Node((1100.0, 500.0, 150.0), None, None, 1.0))
+    for D in (0, 8, 6, 5, 4, 3):          # t = 6: D = 5, 4, 3 leave 5, 3, 1 of its 7 strategies
+        lo, hi = rw.strategy_range(6, D)
+        ws = [rw.balance_weight(zig, s, D) for s in range(lo, hi + 1)]
+        assert len(ws) == rw.strategies(6, D) and all(w[1] is None and not w[2] and 0.0 < w[0] <= 1.0 for w in ws)
+        assert sum(w[0] for w in ws) == pytest.approx(1.0, rel=1e-12)
+    assert rw.balance_weight(zig, 3, 3)[0] == 1.0 and rw.balance_weight(zig, 3, 8)[0] < 0.9
+    # the duplicate node of a missed step: the uniform weight; a segment of 1e-4 cm decides the same, but fragile
+    dup = [path[0], path[1], rw.Node(path[1].pos, up, 0, 1.0), path[2]]
+    assert rw.balance_weight(dup, 1, 8) == (1.0 / 3.0, "segment", False) and rw.balance_weight(dup, 1, 1) == (1.0, "segment", False)
+    dup[2] = rw.Node((50.0, 0.00001, -100.0), up, 0, 1.0)
+    assert rw.balance_weight(dup, 1, 8) == (1.0 / 3.0, "segment", True)
+    # vertex 1 faces away from vertex 2: the forward walk cannot have left it that way, so strategy 2 has density 0 -> uniform
+    back = [path[0], rw.Node((100.0, 0.0, -100.0), up, 0, 1.0), rw.Node((200.0, 0.0, -200.0), up, 0, 1.0), rw.Node((300.0, 0.0, 0.0), None, None, 1.0)]
+    assert rw.balance_weight(back, 2, 8)[:2] == (1.0 / 3.0, "ratio")
+    assert rw.balance_weight(back, 0, 8)[0] + rw.balance_weight(back, 1, 8)[0] == pytest.approx(1.0)
+
+
+def compare_mode_frame(oracle_mod, osc, mode, fr, depth, roulette, seed, num_pairs):
+    """pair by pair the oracle's compute_energy(pair_begin = i, pair_end = i + 1) against the model's contributions -> the largest
+    relative difference of a (band, bin) entry.  Every pair: step and connection counters.  Every pair without a flagged contribution:
+    the deposit count, the occupied bins, every (band, bin) energy to the mode's tolerance."""
+    flags, rtol = MODES[mode]
+    p = oracle_mod.default_params(num_pairs=num_pairs, depth=depth, seed=seed, russian_roulette=int(roulette), flags=flags)
+    prefix = isinstance(fr, rw.PrefixFrame)
+    worst, steps, connections, compared = 0.0, 0, 0, 0
+    for i, r in enumerate(fr.pairs):
+        e32, e64, cnt = osc.compute_energy(p, rw.SOURCE, rw.LISTENER, pair_begin=i, pair_end=i + 1)
+        steps += cnt.closest_rays
+        connections += cnt.any_rays
+        assert cnt.closest_rays == r.steps and cnt.path_nodes == len(r.fwd) + len(r.bwd), (seed, i)
+        assert cnt.any_rays == (r.connections if prefix else 1), (seed, i)
+        H = np.zeros((4, 1000))
+        if prefix:
+            if r.flagged:
+                continue
+            deposits = 0
+            for c in r.contributions:
+                if c.visible:
+                    deposits += 1
+                    H[:, c.bin] += c.energy
+        else:
+            if r.fragile:
+                continue
+            deposits = int(r.visible)
+            if r.visible:
+                H[:, r.bin] += r.energy
+        compared += 1
+        assert cnt.deposits == deposits, (seed, i)
+        assert np.array_equal(e64 != 0.0, H != 0.0), (seed, i)
+        nz = H != 0.0
+        if nz.any():
+            d = float(np.abs(e64[nz] / H[nz] - 1.0).max())
+            worst = max(worst, d)
+            assert d <= rtol, (seed, i, d)
+    assert steps == fr.steps and connections == fr.connections
+    return worst, compared
+
+
+FRAMES = [(2, True, 1024), (4, True, 1024), (8, True, 1024), (8, False, 256)]
+
+
+@pytest.mark.parametrize("depth,roulette,num_pairs", FRAMES, ids=["d2", "d4", "d8", "d8_norr"])
+@pytest.mark.parametrize("mode", list(MODES))
+def test_mode_frames_against_the_model(oracle_mod, mode, depth, roulette, num_pairs):
+    """The oracle in the three build-owned modes against the model's restatement of DESIGN.md section 8: seeds 101, 202, 303,
+    1024 pairs at depth 2, 4, 8 with roulette and 256 pairs at depth 8 without.  Conditions on
+    a frame, asserted: at most 2 % of its connections tested are flagged; the balance-heuristic frames fall back on degenerate
+    segments (the `ratio` fallback cannot occur under a depth cap: a strategy's own density is a product of densities the walks
+    sampled, all positive; test_unbounded_depth_against_the_model has it); every lobe frame picks each lobe 100 times or more; the
+    all-prefix frames of depth 8 have pairs of more than 64 prefix combinations.
+    Measured (CPU, oracle against model; the constants of MODES are 4 x the largest of a mode, the depth-0 frames included):
+
+      mode           flagged, depth 2 / 4 / 8 / 8 without roulette                 largest relative difference, same order
+      uniform        0.01 % / 0.02-0.06 % / 0.06-0.19 % / 0.09-0.34 %              4.9e-6 / 1.1e-5 / 7.6e-5 / 4.6e-5
+      balance        0.01 % / 0.02-0.06 % / 0.06-0.20 % / 0.09-0.38 %              4.9e-5 / 7.7e-5 / 1.7e-4 / 5.1e-5
+      lobes          0-0.39 % / 0.10-0.39 % / 0.10-0.29 % / 0.39-1.56 %            2.0e-6 / 6.0e-6 / 3.7e-5 / 3.1e-4
+      lobes_all      0-0.15 % / 0.09-0.18 % / 0.24-0.28 % / 0.24-0.43 %            2.0e-6 / 5.8e-6 / 3.0e-5 / 1.7e-5
+      lobes_cosine   0-0.39 % / 0.10-0.39 % / 0.20-0.78 % / 0-1.56 %               1.3e-6 / 2.8e-6 / 5.9e-5 / 1.2e-5
+
+    No pair without a flagged contribution disagreed in any frame.  The balance heuristic's differences are those of grazing
+    cosines (a factor of the weight whose relative float32 error is large); they stay within a few 1e-4, so no floor on the cosine is
+    used beyond rw.COSINE_FLOOR.  The lobe mode's 3.1e-4 is one pair of seed 101 without roulette: drift through a chain of specular
+    bounces, where no cone sample renews the direction.  81 prefix combinations at most: 214 ... 256 pairs of a depth-8 frame have
+    more than 64."""
+    sc, osc = mode_scene(oracle_mod, mode)
+    flags = MODES[mode][0]
+    for seed in (101, 202, 303):
+        fr = mode_frame(mode, depth, roulette, seed, num_pairs, keep_pairs=True)
+        nfr = flagged_contributions(fr)
+        worst, compared = compare_mode_frame(oracle_mod, osc, mode, fr, depth, roulette, seed, num_pairs)
+        print(f"{mode} depth {depth} roulette {roulette} seed {seed}: flagged {nfr} of {fr.connections} ({nfr / fr.connections:.2%}) pairs compared "
+              f"{compared} deposits {fr.deposits} lobes {fr.lobes} worst energy {worst:.3e}"
+              + (f" fallbacks {fr.fallbacks} pairs over 64 combinations {fr.pairs_over_64}" if isinstance(fr, rw.PrefixFrame) else ""))
+        assert nfr <= 0.02 * fr.connections
+        assert compared >= 0.8 * num_pairs and fr.deposits > num_pairs // 10
+        if flags & LOBES:
+            assert min(fr.lobes) >= 100
+        if flags & MIS:
+            assert fr.fallbacks["segment"] > 0
+        if flags & (ALLC | MIS) and depth == 8:
+            assert fr.pairs_over_64 > 0 and 64 < fr.most_combinations <= 81
+
+
+UNBOUNDED_SEED = 128
+
+
+@pytest.mark.parametrize("mode", ["uniform", "balance"])
+def test_unbounded_depth_against_the_model(oracle_mod, mode):
+    """depth 0 (while (true): D is infinite, N(t) = t + 1, every strategy counts), 256 pairs, the two all-prefix modes.  Seed 128:
+    the first from 101 on whose frame meets both conditions, at most 2 % of the connections flagged and both fallbacks of the
+    weight (of the seeds 101 ... 220 six meet the first: a frame's connections are mostly those of its longest walks, and from
+    turn 25 ... 45 on even the per-axis bound calls a walk's decisions fragile, as the float32 walk's drift of up to 1 cm there
+    warrants; seed 101 has 9 % flagged, a walk of 84 nodes among them).  The `ratio` fallback occurs only here, where the product
+    of more than 40 densities underflows; the model flags those contributions.
+    Measured: 407 (uniform) and 411 (balance) of 22 623 connections flagged (1.8 %), 228 pairs compared, largest relative difference
+    4.7e-5 in both modes; 9 489 `segment` and 13 `ratio` fallbacks; 660 prefix combinations in one pair."""
+    sc, osc = mode_scene(oracle_mod, mode)
+    fr = mode_frame(mode, 0, True, UNBOUNDED_SEED, 256, keep_pairs=True)
+    worst, compared = compare_mode_frame(oracle_mod, osc, mode, fr, 0, True, UNBOUNDED_SEED, 256)
+    print(f"{mode} depth 0: flagged {fr.flagged} of {fr.connections} ({fr.flagged / fr.connections:.2%}) pairs compared {compared} "
+          f"worst energy {worst:.3e} fallbacks {fr.fallbacks} most combinations {fr.most_combinations}")
+    assert compared > 128 and fr.most_combinations > 81
+    if mode == "balance":
+        assert fr.fallbacks["segment"] > 0 and fr.fallbacks["ratio"] > 0
+    assert fr.flagged <= 0.02 * fr.connections
