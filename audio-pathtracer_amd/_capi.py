@@ -54,6 +54,7 @@ EXPORTS = [
     "fs_scene_commit_fast", "fs_comm_unique_id", "fs_comm_init", "fs_comm_attach", "fs_comm_detach", "fs_comm_info", "fs_comm_enable_oneshot", "fs_shard_range",
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
     "fs_set_band_edges", "fs_source_set_orientation", "fs_source_set_directivity", "fs_get_room_parameters",
+    "fs_source_set_order_window", "fs_source_get_order_window",
     "fs_direct_params_default", "fs_direct_sample_offsets", "fs_update_direct_paths",
     "fs_reflection_params_default", "fs_update_reflection_paths",
     "fs_diffraction_params_default", "fs_update_diffraction_paths",
@@ -63,6 +64,7 @@ EXPORTS = [
     "fs_reflection_render_init", "fs_reflection_render_release", "fs_reflection_render_process_batch",
 ]
 MAX_DIRECTIVITY_SAMPLES = 181   # FS_MAX_DIRECTIVITY_SAMPLES: 1 degree steps
+ORDER_UNBOUNDED = 0x7fffffff    # FS_ORDER_UNBOUNDED: no upper end of a source's order window
 COMM_ID_BYTES = 128
 ERR_COMM = 8
 ERR_OVERFLOW = 9
@@ -469,6 +471,8 @@ def load():
         "fs_listener_set_object": (C.c_int, [vp, C.c_uint32]),
         "fs_source_set_orientation": (C.c_int, [vp, i32, C.POINTER(C.c_float)]),
         "fs_source_set_directivity": (C.c_int, [vp, i32, f32p, i32, i32]),
+        "fs_source_set_order_window": (C.c_int, [vp, i32, i32, i32]),
+        "fs_source_get_order_window": (C.c_int, [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "fs_compute_energy_response": (C.c_int, [vp, i32, C.POINTER(Params), f32p]),
         "fs_compute_energy_response_async": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "fs_compute_energy_response_batch_async": (C.c_int, [vp, C.POINTER(C.c_int32), i32, C.POINTER(Params)]),

@@ -253,6 +253,18 @@ class Context:
             raise ValueError("gains must be [bands][samples]")
         self.check(self.lib.fs_source_set_directivity(self.h, int(src), g.ctypes.data, g.shape[0], g.shape[1]))
 
+    def set_source_order_window(self, src, min_order=0, max_order=None):
+        """fs_source_set_order_window: the source's traced frames deposit only the paths with min_order .. max_order nodes
+        made by a hit (both included); max_order None = unbounded, (0, None) = off"""
+        hi = _capi.ORDER_UNBOUNDED if max_order is None else int(max_order)
+        self.check(self.lib.fs_source_set_order_window(self.h, int(src), int(min_order), hi))
+
+    def source_order_window(self, src):
+        """fs_source_get_order_window: (min_order, max_order), max_order None when unbounded"""
+        lo, hi = C.c_int32(0), C.c_int32(0)
+        self.check(self.lib.fs_source_get_order_window(self.h, int(src), C.byref(lo), C.byref(hi)))
+        return int(lo.value), (None if hi.value == _capi.ORDER_UNBOUNDED else int(hi.value))
+
     def compute_energy_response_batch_async(self, sources, params):
         """several sources in one traced frame (UpdateSource over ActiveSources): same result per source as separate calls"""
         arr = (C.c_int32 * len(sources))(*[int(x) for x in sources])
@@ -700,6 +712,14 @@ class FrequenSeeAudioComponent:
     def SetDirectivity(self, gains=None):
         """per-band gains [bands][samples] over 0 .. 180 degrees from the forward vector; None = omnidirectional"""
         self._ctx().set_source_directivity(self._src, gains)
+
+    def SetOrderWindow(self, min_order=0, max_order=None):
+        """traced frames keep only the paths of min_order .. max_order hits (None: unbounded); (0, None) = everything.  With the
+        direct renderer alone min_order = 1, with first-order voices too 2, with second-order voices too 3"""
+        self._ctx().set_source_order_window(self._src, min_order, max_order)
+
+    def GetOrderWindow(self):
+        return self._ctx().source_order_window(self._src)
 
     @property
     def EnergyBuffer(self):

@@ -36,7 +36,7 @@ struct Frame {
     KParams kp{};
     int B = 1, levels = 0;
     bool batch = false, unbounded = false, all_conn = false, mis = false, fixed = false, accumulate = false, pipe_ok = false;
-    bool dir = false;                   // some source of the frame has a directivity table: the directional connect kernels run
+    bool dir = false;                   // some source of the frame has a directivity table or an order window: the directional connect kernels run
     DirArgs dargs{};                    // ... with these descriptors (the orientations and tables in force at the frame's call)
     std::vector<WalkStage> stages;      // the walk in one piece, or the stages of a pipelined depth = 0 frame
     int lane_len = 0;                   // a waited-for staged frame: walks of this many steps or more take the long-walk lane (0: none)
@@ -134,7 +134,7 @@ void frame_describe(fs_context* ctx, Frame& f) {
     f.fixed = (p->flags & FS_FLAG_DETERMINISTIC) != 0;
     f.accumulate = (p->flags & FS_FLAG_ACCUMULATE_ENERGY) != 0;
     f.dir = false;
-    for (int i = 0; i < f.count; ++i) if (f.srcs[i]->d_dir) f.dir = true;
+    for (int i = 0; i < f.count; ++i) if (f.srcs[i]->ext_connect()) f.dir = true;
     f.dargs.one = s->directivity();
     f.dargs.tab = nullptr;
     // Pipelined frames: this frame's passes are held back (to be launched with the next frames') when the frame has the
@@ -145,7 +145,7 @@ void frame_describe(fs_context* ctx, Frame& f) {
     // launch carries one frame's worth of work and no chain longer than a stage.
     const bool plain_walk = !(p->flags & (FS_FLAG_MATERIAL_LOBES | FS_FLAG_MIS_BALANCE | FS_FLAG_ALL_CONNECTIONS | FS_FLAG_ACCUMULATE_ENERGY |
                                           FS_FLAG_DOUBLE_POSITIONS));
-    // (a directional source: its connect pass has no fused form — the frame runs on its own, like FS_FLAG_DOUBLE_POSITIONS
+    // (a directional or windowed source: its connect pass has no fused form — the frame runs on its own, like FS_FLAG_DOUBLE_POSITIONS
     // frames; its walk is any other's, staged too when it is waited for)
     const bool plain = plain_walk && !f.dir;
     // (a walk that ignores the actor it starts from — what the reference's GeneratePath always does, ARTS.cpp:322-327 — is held
@@ -776,6 +776,29 @@ int fs_source_set_directivity(fs_context* ctx, fs_source h, const float* gains, 
     return FS_OK;
 }
 
+int fs_source_set_order_window(fs_context* ctx, fs_source h, int32_t min_order, int32_t max_order) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (min_order < 0) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_source_set_order_window: min_order must be >= 0");
+    if (max_order < min_order) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_source_set_order_window: max_order < min_order");
+    if (min_order == s->min_order && max_order == s->max_order) return FS_OK;
+    FS_FLUSH(ctx);   // frames collected for a grouped launch were asked for with the old setting
+    s->min_order = min_order;
+    s->max_order = max_order;
+    return FS_OK;
+}
+
+int fs_source_get_order_window(fs_context* ctx, fs_source h, int32_t* min_order, int32_t* max_order) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (!min_order || !max_order) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_source_get_order_window: null out pointer");
+    *min_order = s->min_order;
+    *max_order = s->max_order;
+    return FS_OK;
+}
+
 int fs_listener_set_object(fs_context* ctx, uint32_t object_id) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     if (object_id != ctx->listener_object) FS_FLUSH(ctx);
@@ -801,7 +824,7 @@ int fs_compute_energy_response_async(fs_context* ctx, fs_source h, const fs_para
     fs_params def;
     const fs_params* q = p;
     if (!q) { fs_params_default(&def); q = &def; }
-    if (q->struct_size == sizeof(fs_params) && groupable(ctx, q) && !s->d_dir) {   // (a directional source's frames are never held)
+    if (q->struct_size == sizeof(fs_params) && groupable(ctx, q) && !s->ext_connect()) {   // (a directional or windowed source's frames are never held)
         if (!ctx->group.empty() && (!same_but_seed(ctx->group[0].p, *q) || std::memcmp(ctx->group[0].lis, ctx->listener, sizeof(ctx->listener)) != 0)) {
             const int gr = dispatch_group(ctx);   // (a batched frame has ONE listener position)
             if (gr) return gr;

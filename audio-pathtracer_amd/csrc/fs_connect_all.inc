@@ -2,7 +2,8 @@
 // (FS_CONNECT_ALL_DIR 1), included twice by fs_connect.hip.  The body is written out in each kernel rather than inlined from
 // a shared device function: as an inlined function it changes the plain kernel's schedule (and its code is kept as it was).
 // DIR: the source's directivity (fs_source_set_directivity) — w_e of (i, j) is the walk's emitting ray if F_0..F_i has left
-// the source, else the direction of the connection F_i -> B_j; D_b(w_e) is the deposit's last factor.
+// the source, else the direction of the connection F_i -> B_j; D_b(w_e) is the deposit's last factor.  The same entry applies
+// the source's order window (fs_source_set_order_window): (i, j) whose hits among F1..Fi and B1..Bj lie outside it is dropped.
 #if FS_CONNECT_ALL_DIR
 template <int B>
 __global__ __launch_bounds__(kBlock) void connect_all_dir_kernel(DeviceScene sc, KParams kp, SubpathState st,
@@ -81,14 +82,16 @@ __global__ __launch_bounds__(kBlock) void connect_all_kernel(DeviceScene sc, KPa
             }
             const bool hit = trav_any_shared(sc, has_ray, ray, tmax, &s_stack[threadIdx.x], s_share);
             if (!active || hit || sphere_blocked) continue;
-            ++my_deposits;
+            if constexpr (!DIR) ++my_deposits;
             float E[Bands<B>::kMax];
 #pragma unroll
             for (int b = 0; b < Bands<B>::kMax; ++b) E[b] = 1.0f;
             float sd = 0.0f;
+            [[maybe_unused]] int order = 0;   // DIR: the hits among F1..Fi and B1..Bj, counted as their records go by
             for (int a = 0; a < i; ++a) {                                 // F_a -> F_a+1
                 const float2 np = load_np(st, total, a, sf);
                 sd += np.x;
+                if constexpr (DIR) order += order_hit(np.x);
                 apply_segment<B>(E, np.x, load_mat(st, total, a, sf), np.y, kp, sc);
             }
             {                                                             // Fi -> Bj
@@ -99,9 +102,16 @@ __global__ __launch_bounds__(kBlock) void connect_all_kernel(DeviceScene sc, KPa
             for (int a = j - 1; a >= 0; --a) {                            // B_a+1 -> B_a
                 const float2 np = load_np(st, total, a, sl);
                 sd += np.x;
+                if constexpr (DIR) order += order_hit(np.x);
                 uint32_t bmat = load_mat(st, total, a, sl);
                 if (a == j - 1) bmat &= 0xFFFFu;                          // Bj is the other connection vertex
                 apply_segment<B>(E, np.x, bmat, np.y, kp, sc);
+            }
+            [[maybe_unused]] const Directivity* dsc = nullptr;
+            if constexpr (DIR) {   // the order window: (i, j) outside it deposits nothing; strategy counts and densities below are everybody's
+                dsc = dir.tab ? &dir.tab[li / kp.pairs_per_source] : &dir.one;
+                if (order < dsc->min_order || order > dsc->max_order) continue;
+                ++my_deposits;
             }
             const int t = i + j, D = kp.mis_depth;
             const int lo_t = t - D > 0 ? t - D : 0, hi_t = t < D ? t : D;
@@ -109,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void connect_all_kernel(DeviceScene sc, KPa
             if (kp.mis) w = mis_weight(kp, st, total, sf, sl, i, j);
             [[maybe_unused]] DirLookup dl;
             if constexpr (DIR) {
-                const Directivity& d = dir.tab ? dir.tab[li / kp.pairs_per_source] : dir.one;
+                const Directivity& d = *dsc;
                 const bool left = ke >= 0 && ke < i;
                 dl = dir_lookup(d, left ? ex : dx * inv, left ? ey : dy * inv, left ? ez : dz * inv);
             }

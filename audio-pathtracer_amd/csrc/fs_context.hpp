@@ -93,7 +93,17 @@ struct Source {
     float fwd[3] = {1.0f, 0.0f, 0.0f};
     float* d_dir = nullptr;
     int32_t dir_samples = 0;
-    fs::Directivity directivity() const { fs::Directivity d; std::memcpy(d.fwd, fwd, sizeof(d.fwd)); d.samples = dir_samples; d.table = d_dir; return d; }
+    // order window (fs_source_set_order_window), both ends included; (0, FS_ORDER_UNBOUNDED) = off.  It rides in the
+    // directivity descriptor, by value with every launch
+    int32_t min_order = 0, max_order = FS_ORDER_UNBOUNDED;
+    bool windowed() const { return min_order != 0 || max_order != FS_ORDER_UNBOUNDED; }
+    bool ext_connect() const { return d_dir != nullptr || windowed(); }   // its frames take the directional connect entries
+    fs::Directivity directivity() const {
+        fs::Directivity d;
+        std::memcpy(d.fwd, fwd, sizeof(d.fwd)); d.samples = dir_samples; d.table = d_dir;
+        d.min_order = min_order; d.max_order = max_order;
+        return d;
+    }
     // Two energy buffers [B][bins], alternating per frame: while the tail stream still reduces /
     // reconstructs frame f from one of them, the compute stream already traces frame f+1 into the other.
     float* d_energy[kEnergyBufs] = {};

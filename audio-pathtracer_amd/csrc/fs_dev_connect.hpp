@@ -29,6 +29,12 @@ __device__ __forceinline__ void emission_ray(const KParams& kp, uint32_t li, int
     const uint4 r = philox(pair, bs, 0, seed, kp.seed_hi);
     sample_sphere(pair, bs, r, seed, kp.seed_hi, wx, wy, wz);
 }
+// Order window (fs_source_set_order_window): the order of a path is the number of its nodes that a walk step's HIT made.  A
+// step that misses leaves the walk where it is: its record has the length 0 exactly (q = p above, sqrtf(0) / divisor).  A
+// step that hits moves the node by t d + offset n with n . d <= 0: squared length t^2 + offset^2 + 2 t offset (n . d) >=
+// (t - offset)^2, zero only for a ray that meets a surface head-on (d = -n in every bit) at exactly t = offset — see DESIGN.md
+// section 8, "Order window".  So the records tell the hits apart, as emission_step above reads them.
+__device__ __forceinline__ int order_hit(float nd) { return nd != 0.0f ? 1 : 0; }
 // theta = atan2f(|w x f|, w . f) (well-conditioned near 0 and pi, unlike acosf of the dot); x = theta (K - 1) / pi,
 // k = min((int)x, K - 2), t = x - k.  (A zero-length connection of a walk that never left has no direction: theta = 0.)
 struct DirLookup { const float* row; int K, k; float t; };
@@ -68,7 +74,8 @@ __device__ __forceinline__ float dir_gain(const DirLookup& L, int b) {
 // walk lie a whole level apart ([step][slot]): one at a time, every segment of a 100-segment path waited for its own miss.
 // (Also measured: the paths of 40 segments or more evaluated by the whole wave, as a sparse wave does for every path — no gain
 // on top of this: 88 -> 92 us at cfg3's size.  With the records ahead the longest path is no longer what the pass waits for.)
-// DIR (connect_dir_kernel only): the source's directivity, `dir` — the pair's own lane weights its deposits by D_b(w_e).
+// DIR (connect_dir_kernel only): the source's directivity, `dir` — the pair's own lane weights its deposits by D_b(w_e) —
+// and its order window: the evaluation counts the records a hit made, a path outside [min_order, max_order] deposits nothing.
 template <int B, int LOBES, bool BATCH, bool COUNT, bool EXT = false, int AHEAD = 1, bool DIR = false>
 __device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t nblocks, const DeviceScene& sc,
                                              const KParams& kp, const SubpathState& st, float* __restrict__ energy,
@@ -157,6 +164,7 @@ __device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t 
 #pragma unroll
         for (int b = 0; b < Bands<B>::kMax; ++b) E[b] = 1.0f;
         float sd = 0.0f;
+        [[maybe_unused]] int order = 0;   // DIR: the path's nodes that a hit made (see order_hit)
         // one lane evaluates its pair's connected path alone: EvaluatePath over F0..Fk, Bm..B0 (ARTS.cpp:262-267, 360-420), in path order
         auto eval_alone = [&]() {
         const int kf = (int)Fm.y, kl = (int)Lm.y;
@@ -168,12 +176,13 @@ __device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t 
                 for (int u = 0; u < AHEAD; ++u) { const int j = min(j0 + u, kf - 1); np[u] = load_np(st, total, j, sf); mt[u] = load_mat(st, total, j, sf); }
 #pragma unroll
                 for (int u = 0; u < AHEAD; ++u)
-                    if (j0 + u < kf) { sd += np[u].x; apply_segment<B, LOBES>(E, np[u].x, mt[u], np[u].y, kp, sc); }
+                    if (j0 + u < kf) { sd += np[u].x; if (DIR) order += order_hit(np[u].x); apply_segment<B, LOBES>(E, np[u].x, mt[u], np[u].y, kp, sc); }
             }
         } else
         for (int j = 0; j < kf; ++j) {                                // source-side segments F_j -> F_j+1
             const float2 np = load_np(st, total, j, sf);
             sd += np.x;                                               // ARTS.cpp:374
+            if (DIR) order += order_hit(np.x);
             apply_segment<B, LOBES>(E, np.x, load_mat(st, total, j, sf), np.y, kp, sc);
         }
         {                                                             // connection segment: F_k's material/prob
@@ -190,12 +199,13 @@ __device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t 
                 for (int u = 0; u < AHEAD; ++u) { const int j = max(j0 - u, 0); np[u] = load_np(st, total, j, sl); mt[u] = load_mat(st, total, j, sl); }
 #pragma unroll
                 for (int u = 0; u < AHEAD; ++u)
-                    if (j0 - u >= 0) { sd += np[u].x; apply_segment<B, LOBES>(E, np[u].x, mt[u], np[u].y, kp, sc); }
+                    if (j0 - u >= 0) { sd += np[u].x; if (DIR) order += order_hit(np[u].x); apply_segment<B, LOBES>(E, np[u].x, mt[u], np[u].y, kp, sc); }
             }
         } else
         for (int j = kl - 1; j >= 0; --j) {                           // listener-side segments B_j+1 -> B_j
             const float2 np = load_np(st, total, j, sl);
             sd += np.x;
+            if (DIR) order += order_hit(np.x);
             apply_segment<B, LOBES>(E, np.x, load_mat(st, total, j, sl), np.y, kp, sc);
         }
         };
@@ -223,6 +233,7 @@ __device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t 
 #pragma unroll
                 for (int b = 0; b < Bands<B>::kMax; ++b) Et[b] = 1.0f;
                 float sdt = 0.0f;
+                [[maybe_unused]] int ordt = 0;
                 for (int base = 0; base < segs; base += 64) {
                     const int i = base + (int)lane;
                     float nd = 0.0f, prob = 1.0f;
@@ -237,6 +248,8 @@ __device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t 
                         const float2 np = load_np(st, total, j, usl);
                         nd = np.x; prob = np.y; mat = load_mat(st, total, j, usl);
                     }
+                    // (DIR) the walk records among this round's segments that a hit made: every one but the connection segment
+                    if (DIR) ordt += __popcll(__ballot(i < segs && i != kf && order_hit(nd) != 0));
                     SegFactors<B> f;
                     segment_factors<B, LOBES>(f, nd, mat, prob, kp, sc);
                     const int cnt = min(64, segs - base);
@@ -261,24 +274,32 @@ __device__ __forceinline__ void connect_body(const uint32_t bid, const uint32_t 
 #pragma unroll
                     for (int b = 0; b < Bands<B>::kMax; ++b) E[b] = Et[b];
                     sd = sdt;
+                    if (DIR) order = ordt;
                 }
             }
             if (!go) return;
-            ++my_deposits;
+            if (!DIR) ++my_deposits;
         } else {
         if (!active || hit || sphere_blocked) return;
         // depth = 0 only: a walk that outlived the record store has raised the overflow word — the frame is void and will
         // be traced again (FS_ERR_OVERFLOW); its pair must not be evaluated, the records it would read do not exist
         if (st.over_levels && !(rec_fits(st, (int)Fm.y - 1, sf) && rec_fits(st, (int)Lm.y - 1, sl))) return;
-        ++my_deposits;
+        if (!DIR) ++my_deposits;
         eval_alone();
         }
         DirLookup dl;
-        if (DIR) {   // w_e: the ray the source's walk left by, else (it never left) the connection ray as computed above
+        if (DIR) {
             const Directivity& d = dir.tab ? dir.tab[lc / kp.pairs_per_source] : dir.one;
+            // the source's order window: a path outside it deposits nothing and is not counted — after the shared visibility
+            // query and the evaluation, which every lane of the wave went through alike
+            if (order < d.min_order || order > d.max_order) return;
+            ++my_deposits;
+            // w_e: the ray the source's walk left by, else (it never left) the connection ray as computed above
             float wx = ux, wy = uy, wz = uz;
-            const int ke = emission_step(st, total, sf, (int)Fm.y);
-            if (ke >= 0) emission_ray(kp, lc, ke, wx, wy, wz);
+            if (d.table) {   // (a window alone: no table, factor 1 — the emission ray is not needed)
+                const int ke = emission_step(st, total, sf, (int)Fm.y);
+                if (ke >= 0) emission_ray(kp, lc, ke, wx, wy, wz);
+            }
             dl = dir_lookup(d, wx, wy, wz);
         }
         float delay = sd / kp.sound_speed;                            // ARTS.cpp:419

@@ -194,10 +194,13 @@ constexpr uint32_t kPlanCoopMax = 32768, kPlanCoopMaxUncapped = 1u << 17;   // K
 
 // Source directivity (fs_source_set_directivity): a kernel argument of the directional connect kernels only — KParams,
 // ten times in the fused frame kernel's 4 KB of arguments, does not grow.  table == null: omnidirectional (factor 1).
+// The same descriptor carries the source's order window (fs_source_set_order_window): a deposit whose path has fewer than
+// min_order or more than max_order nodes made by a hit is dropped.  (0, FS_ORDER_UNBOUNDED): no window.
 struct Directivity {
     float fwd[3];            // unit forward vector
     int32_t samples;         // K: samples per band
     const float* table;      // device [bands][K], or null
+    int32_t min_order = 0, max_order = 0x7fffffff;   // order window, both ends included
 };
 struct DirArgs {
     Directivity one;         // the frame's source

@@ -51,6 +51,11 @@ public:
     // 0 .. 180 degrees from it (empty: omnidirectional again) — fs_source_set_orientation / fs_source_set_directivity
     void SetForwardVector(FVector F);
     void SetDirectivity(const std::vector<float>& Gains, int Samples);
+    // order window: traced frames keep only the paths with MinOrder .. MaxOrder nodes made by a hit (both included;
+    // (0, FS_ORDER_UNBOUNDED): everything).  Direct renderer alone: MinOrder = 1; first-order voices too: 2; second-order too: 3
+    // — fs_source_set_order_window / fs_source_get_order_window
+    void SetOrderWindow(int MinOrder, int MaxOrder = FS_ORDER_UNBOUNDED);
+    void GetOrderWindow(int& MinOrder, int& MaxOrder) const;
 
     int NumBins() const;      // FrequenSeeAudioComponent.h:137
     int NumSamples() const;   // :138
@@ -322,6 +327,14 @@ inline void FrequenSeeAudioComponent::SetDirectivity(const std::vector<float>& G
     if (Gains.empty()) { SubSys_->Check(fs_source_set_directivity(SubSys_->Ctx_, Handle_, nullptr, 0, 0)); return; }
     const int Bands = Samples > 0 ? (int)(Gains.size() / (size_t)Samples) : 0;
     SubSys_->Check(fs_source_set_directivity(SubSys_->Ctx_, Handle_, Gains.data(), Bands, Samples));
+}
+inline void FrequenSeeAudioComponent::SetOrderWindow(int MinOrder, int MaxOrder) {
+    SubSys_->Check(fs_source_set_order_window(SubSys_->Ctx_, Handle_, (int32_t)MinOrder, (int32_t)MaxOrder));
+}
+inline void FrequenSeeAudioComponent::GetOrderWindow(int& MinOrder, int& MaxOrder) const {
+    int32_t Lo = 0, Hi = 0;
+    SubSys_->Check(fs_source_get_order_window(SubSys_->Ctx_, Handle_, &Lo, &Hi));
+    MinOrder = (int)Lo; MaxOrder = (int)Hi;
 }
 inline int FrequenSeeAudioComponent::NumBins() const { return fs_num_bins(SubSys_->Ctx_); }
 inline int FrequenSeeAudioComponent::NumSamples() const { return fs_num_samples(SubSys_->Ctx_); }

@@ -53,6 +53,7 @@
  *             fs_reverb_init fs_reverb_process fs_reverb_process_batch fs_reverb_release fs_reverb_set_crossfade fs_reverb_set_engine fs_apply_material_fd
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
  *             fs_source_set_orientation fs_source_set_directivity fs_get_room_parameters
+ *             fs_source_set_order_window fs_source_get_order_window
  *             fs_direct_params_default fs_direct_sample_offsets fs_update_direct_paths
  *             fs_reflection_params_default fs_update_reflection_paths
  *             fs_diffraction_params_default fs_update_diffraction_paths
@@ -366,6 +367,38 @@ int fs_listener_set_object(fs_context* ctx, uint32_t object_id);
 int fs_source_set_orientation(fs_context* ctx, fs_source src, const float forward[3]);
 int fs_source_set_directivity(fs_context* ctx, fs_source src, const float* gains /* [bands][samples] */, int32_t bands,
                               int32_t samples);
+
+/* ---- order window (EXTENDED): a source's traced frames deposit only the paths of some orders -------------------------
+ * The traced histogram holds EVERY connected path of the frame: the direct path, the first reflections, the tail.  A host
+ * that renders the direct sound (fs_update_direct_paths) and discrete early reflections (fs_update_*_paths) by their own
+ * renderers and the traced response as the late field would play those paths twice; the window takes them out of the trace.
+ * The ORDER of a contribution is the number of its path's nodes that a walk step's HIT made.  End-to-end connection (the
+ * default mode) of F_0..F_k and B_m..B_0: the hits among F_1..F_k plus the hits among B_1..B_m.  Contribution (i, j) of
+ * FS_FLAG_ALL_CONNECTIONS / FS_FLAG_MIS_BALANCE: the hits among F_1..F_i plus the hits among B_1..B_j.  A step that misses
+ * pushes a duplicate node and adds nothing: (1, 0) over a missed first step is of order 0, like (0, 0) —
+ * the order is NOT the step count.  A step that hits an end point's collision sphere (listener_radius, source_radius) is a
+ * hit; so is a step of any lobe under FS_FLAG_MATERIAL_LOBES, if it hit.
+ * A contribution whose order lies outside [min_order, max_order] (both included) deposits nothing.  Nothing else changes:
+ * the walks, the RNG use, the plan pass, the visibility query of every pair or (i, j) and the weights are those of the frame
+ * without a window — the uniform weight 1 / N(i + j) and the balance heuristic still count all strategies: the window
+ * selects paths, it does not re-normalise.  fs_stats.segments, planned_segments and connections_tested are as without a
+ * window; fs_stats.deposits counts what was deposited.  The window depends only on the pair's own walks: not on batching,
+ * on the route, or on how pairs are sharded over ranks.  With every flag the window filters what the frame would deposit:
+ * FS_FLAG_DETERMINISTIC sums the kept deposits in fixed point, FS_FLAG_ACCUMULATE_ENERGY adds them to the buffer,
+ * FS_FLAG_DOUBLE_POSITIONS and FS_FLAG_COSINE_SAMPLING change the walk and not the count; a directivity table weights what
+ * is kept.  Reconstruct, FS_FLAG_ROOM_PARAMETERS, the reverb and the text export read the histogram they are given:
+ * fs_get_room_parameters of a source with min_order >= 1 describes the response without the direct spike.
+ * Default (0, FS_ORDER_UNBOUNDED) = off: today's kernels and results, frames held by fs_set_pipelining as before.  Frames
+ * of a source with any other window are never held (held frames drain first; the frame runs on its own, like a directional
+ * source's) and may share a batch with plain and directional sources, whose results do not change.  A frame uses the
+ * window in force at its call (also an _async frame whose fs_synchronize comes after a later set call).  A new source
+ * handle starts at the default.
+ * Errors: FS_ERR_BAD_HANDLE for a bad handle; FS_ERR_INVALID_ARGUMENT for min_order < 0, max_order < min_order or a NULL
+ * out pointer; a refused call changes nothing.  Which window goes with which renderers: INTEGRATION.md.
+ * Not applied by fs_update_sound, fs_trace_rays or the fs_update_*_paths queries. */
+#define FS_ORDER_UNBOUNDED 0x7fffffff
+int fs_source_set_order_window(fs_context* ctx, fs_source src, int32_t min_order, int32_t max_order);
+int fs_source_get_order_window(fs_context* ctx, fs_source src, int32_t* min_order, int32_t* max_order);
 
 /* ---- the hot path ------------------------------------------------------------------------------- */
 /* ComputeEnergyResponse() == UpdateSource up to the deposit (ARTS.cpp:128-173): GenerateFullPaths
