@@ -60,6 +60,7 @@ EXPORTS = [
     "fs_diffraction_params_default", "fs_update_diffraction_paths",
     "fs_reflection2_params_default", "fs_update_reflection2_paths",
     "fs_diffraction2_params_default", "fs_update_diffraction2_paths",
+    "fs_mixed_params_default", "fs_update_mixed_paths",
     "fs_direct_band_kernels", "fs_direct_render_init", "fs_direct_render_release", "fs_direct_render_process_batch",
     "fs_reflection_render_init", "fs_reflection_render_release", "fs_reflection_render_process_batch",
 ]
@@ -99,6 +100,13 @@ MAX_DIFFRACTION2_BATCH = 256
 DIFFRACTION2_OVERFLOW = 1
 DIFFRACTION2_NEAR_OVERFLOW = 2
 DIFFRACTION2_VOICE_TAG = 0x20000000   # a second-order diffraction voice's key: 0x20000000 | (((kp * 2654435761 + kq) mod 2^32) >> 3), k = 4 triangle + edge
+MAX_MIXED_PATHS = 16
+MAX_MIXED_NEAR = 32768
+MAX_MIXED_CANDIDATES = 2048
+MAX_MIXED_BATCH = 256
+MIXED_OVERFLOW = 1
+MIXED_NEAR_OVERFLOW = 2
+MIXED_VOICE_TAG = 0xC0000000   # a mixed voice's key: 0xC0000000 | (((m * 2654435761 + 4 (2 (4 i + j) + end)) mod 2^32) >> 2)
 DIRECT_RENDER_MAX_TAPS = 2047
 MAX_REFLECTION_VOICES = 32
 MAX_REFLECTION_RENDER_BATCH = 256
@@ -405,6 +413,49 @@ class Diffraction2Row(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("near", "candidates", "confirmed", "found", "returned", "flags")]
 
 
+class MixedParams(C.Structure):
+    """fs_mixed_params (include/frequensee.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("max_paths", C.c_int32),
+        ("max_near", C.c_int32),
+        ("max_candidates", C.c_int32),
+        ("max_length", C.c_float),
+        ("max_detour", C.c_float),
+        ("margin", C.c_float),
+        ("offset", C.c_float),
+        ("merge", C.c_float),
+        ("step", C.c_float),
+        ("pullback", C.c_float),
+        ("dist_divisor", C.c_float),
+        ("sound_speed", C.c_float),
+    ]
+
+
+class MixedPath(C.Structure):
+    """fs_mixed_path (include/frequensee.h): one path off a reflector and round an edge of one source, an array element (no struct_size)"""
+    _fields_ = [
+        ("length", C.c_float),
+        ("delay", C.c_float),
+        ("detour", C.c_float),
+        ("bend_detour", C.c_float),
+        ("cos_bend", C.c_float),
+        ("apex", C.c_float * 3),
+        ("point", C.c_float * 3),
+        ("direction", C.c_float * 3),
+        ("end", C.c_uint32),
+        ("triangle", C.c_uint32 * 2),
+        ("edge", C.c_uint32),
+        ("material", C.c_uint32 * 2),
+        ("gain", C.c_float * MAX_BANDS),
+    ]
+
+
+class MixedRow(C.Structure):
+    """fs_mixed_row (include/frequensee.h): one source's counts, an array element (no struct_size)"""
+    _fields_ = [(k, C.c_uint32) for k in ("near", "candidates", "confirmed", "found", "returned", "flags")]
+
+
 class DirectRenderTarget(C.Structure):
     """fs_direct_render_target (include/frequensee.h): one source's target of a callback, an array element (no struct_size)"""
     _fields_ = [
@@ -547,6 +598,8 @@ def load():
         "fs_update_reflection2_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(Reflection2Params), C.c_void_p, C.c_void_p]),
         "fs_diffraction2_params_default": (None, [C.POINTER(Diffraction2Params)]),
         "fs_update_diffraction2_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(Diffraction2Params), C.c_void_p, C.c_void_p]),
+        "fs_mixed_params_default": (None, [C.POINTER(MixedParams)]),
+        "fs_update_mixed_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(MixedParams), C.c_void_p, C.c_void_p]),
         "fs_direct_band_kernels": (C.c_int, [i32, f32p, i32, i32, f32p]),
         "fs_direct_render_init": (C.c_int, [vp, i32, i32, i32, C.c_float]),
         "fs_direct_render_release": (C.c_int, [vp, i32]),
@@ -600,6 +653,10 @@ def default_reflection2_params(**kw) -> Reflection2Params:
 
 def default_diffraction2_params(**kw) -> Diffraction2Params:
     return _defaults(Diffraction2Params, "fs_diffraction2_params_default", kw)
+
+
+def default_mixed_params(**kw) -> MixedParams:
+    return _defaults(MixedParams, "fs_mixed_params_default", kw)
 
 
 def default_params(**kw) -> Params:

@@ -401,7 +401,7 @@ class Context:
         return out
 
     def _rows_and_paths(self, update, p, row_dtype, path_dtype, sources):
-        """the body of the four rows-and-paths queries: `update` (fs_update_*_paths) with the params p into fresh
+        """the body of the five rows-and-paths queries: `update` (fs_update_*_paths) with the params p into fresh
         (rows [count], paths [count][max_paths]) of the two dtypes"""
         srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
         rows = np.zeros(srcs.shape[0], dtype=row_dtype)
@@ -471,6 +471,24 @@ class Context:
         merge, step, pullback, dist_divisor, sound_speed)"""
         return self._rows_and_paths(self.lib.fs_update_diffraction2_paths, _capi.default_diffraction2_params(**params), self.DIFFRACTION2_ROW_DTYPE,
                                     self.DIFFRACTION2_DTYPE, sources)
+
+    # ---- mixed paths: one specular reflection and one edge diffraction of every source of a tick ----
+    MIXED_ROW_DTYPE = np.dtype([("near", np.uint32), ("candidates", np.uint32), ("confirmed", np.uint32), ("found", np.uint32),
+                                ("returned", np.uint32), ("flags", np.uint32)])
+    MIXED_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("detour", np.float32), ("bend_detour", np.float32),
+                            ("cos_bend", np.float32), ("apex", np.float32, (3,)), ("point", np.float32, (3,)), ("direction", np.float32, (3,)),
+                            ("end", np.uint32), ("triangle", np.uint32, (2,)), ("edge", np.uint32), ("material", np.uint32, (2,)),
+                            ("gain", np.float32, (_capi.MAX_BANDS,))])
+
+    def mixed_paths(self, sources, **params):
+        """fs_update_mixed_paths: (rows [count], paths [count][max_paths]) as structured arrays — per listed source the counts
+        (near, candidates, confirmed, found, returned, flags) and its `returned` shortest paths off one reflector and round one
+        edge (length cm, delay s, detour cm, bend_detour cm, cos_bend, apex E, point R, direction from the listener, end — 0: the
+        reflector is next to the listener, 1: next to the source —, triangle [reflector, the edge's], edge, material [2], gain [8];
+        entries beyond `returned` are zero); params = the fields of fs_mixed_params (max_paths, max_near, max_candidates,
+        max_length, max_detour, margin, offset, merge, step, pullback, dist_divisor, sound_speed)"""
+        return self._rows_and_paths(self.lib.fs_update_mixed_paths, _capi.default_mixed_params(**params), self.MIXED_ROW_DTYPE, self.MIXED_DTYPE,
+                                    sources)
 
     # ---- the audio callbacks: what the three *_process_batch mirrors share ----
     def _callback_open(self, sources, blocks, frames, want_out, want_mix):
@@ -948,6 +966,17 @@ class AudioRayTracingSubsystem:
         parts = [self.ctx.diffraction2_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
         return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
 
+    def UpdateMixedPaths(self, **params):
+        """the paths off one reflector and round one edge of all active sources: (rows, paths), row i and paths[i] for
+        ActiveSources[i] (Context.mixed_paths; more than 256 sources take one call per 256)"""
+        srcs = [s._src for s in self.ActiveSources]
+        if not srcs:
+            return np.zeros(0, dtype=Context.MIXED_ROW_DTYPE), np.zeros((0, 0), dtype=Context.MIXED_DTYPE)
+        self._commit()
+        step = _capi.MAX_MIXED_BATCH
+        parts = [self.ctx.mixed_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
+        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
+
     def SetPipelining(self, depth):
         """fs_set_pipelining: Tick then updates the sources one after the other like the reference's loop (ARTS.cpp:60-68),
         streamed — every call launches one kernel that plans this source's frame, walks the previous source's and
@@ -1095,7 +1124,14 @@ class FrequenSeeAudioReflectionPlugin:
         kp, kq = 4 * int(triangle[0]) + int(edge[0]), 4 * int(triangle[1]) + int(edge[1])
         return _capi.DIFFRACTION2_VOICE_TAG | (((kp * 2654435761 + kq) & 0xFFFFFFFF) >> 3)
 
-    def Voices(self, row, paths, right=None, reference_length=None, diffraction=None, second=None, diffraction2=None):
+    @staticmethod
+    def MixedKey(triangle, edge, end):
+        """the key of the voice of a path off the reflector triangle[0] and round the edge record (triangle[1], edge) with the
+        reflector at `end`: 0xC0000000 | (h >> 2) with h = (m * 2654435761 + 4 (2 (4 i + j) + end)) mod 2^32 — above every first-order
+        diffraction key (0x80000000 | (4 triangle + edge)) of a scene of fewer than 2^28 triangles"""
+        return _capi.MIXED_VOICE_TAG | (((int(triangle[0]) * 2654435761 + 4 * (2 * (4 * int(triangle[1]) + int(edge)) + int(end))) & 0xFFFFFFFF) >> 2)
+
+    def Voices(self, row, paths, right=None, reference_length=None, diffraction=None, second=None, diffraction2=None, mixed=None):
         """one source's entries from its UpdateReflectionPaths result (row: its counts, paths: its path array), over the first
         row["returned"] paths: key = triangle, band_gain = reflectance, delay = the path's arrival time less the filter's own
         latency of (Taps - 1) / 2 samples, not below 0.  channel_gain = (1, 1); with `right` (the listener's unit right vector) the
@@ -1108,25 +1144,31 @@ class FrequenSeeAudioReflectionPlugin:
         of the row whose keys collide: the earlier in the row — the shorter, ties by (a, b) — is kept and the other dropped (the
         renderer refuses duplicate keys).  diffraction2 = (row, paths) of the same source from UpdateDiffraction2Paths appends, last,
         one voice per returned path round two edges — band_gain = gain, key = Diffraction2Key(triangle, edge); on colliding keys
-        the earlier in the row is kept likewise."""
+        the earlier in the row is kept likewise.  mixed = (row, paths) of the same source from UpdateMixedPaths appends, after
+        those, one voice per returned path off a reflector and round an edge — band_gain = gain, key = MixedKey(triangle, edge,
+        end), colliding keys likewise; with it a diffraction path's triangle must stay below 2^28, which is checked."""
         n = int(row["returned"])
         m = 0 if diffraction is None else int(diffraction[0]["returned"])
         k = 0 if second is None else int(second[0]["returned"])
         k2 = 0 if diffraction2 is None else int(diffraction2[0]["returned"])
-        tagged = diffraction is not None or second is not None or diffraction2 is not None
-        v = np.zeros(n + m + k + k2, dtype=Context.REFLECTION_VOICE_DTYPE)
+        k3 = 0 if mixed is None else int(mixed[0]["returned"])
+        tagged = diffraction is not None or second is not None or diffraction2 is not None or mixed is not None
+        v = np.zeros(n + m + k + k2 + k3, dtype=Context.REFLECTION_VOICE_DTYPE)
         latency = ((self.Taps - 1) // 2) / float(self.ctx.cfg.sample_rate)
         r = None if right is None else np.asarray(right, np.float64).reshape(3)
         seen, kept = set(), 0
-        for i in range(n + m + k + k2):
-            p = paths[i] if i < n else (diffraction[1][i - n] if i < n + m else (second[1][i - n - m] if i < n + m + k else
-                                                                                 diffraction2[1][i - n - m - k]))
+        for i in range(n + m + k + k2 + k3):
+            p = paths[i] if i < n else (diffraction[1][i - n] if i < n + m else (second[1][i - n - m] if i < n + m + k else (
+                diffraction2[1][i - n - m - k] if i < n + m + k + k2 else mixed[1][i - n - m - k - k2])))
             if i < n + m:
                 if tagged and int(p["triangle"]) >= _capi.REFLECTION2_VOICE_TAG >> 1:
                     raise ValueError("Voices: triangle index 2^29 or above: the keys of the path kinds would collide")
+                if mixed is not None and i >= n and int(p["triangle"]) >= _capi.MIXED_VOICE_TAG >> 4:
+                    raise ValueError("Voices: a diffraction path's triangle index is 2^28 or above: its key would collide with the mixed paths' keys")
                 key = int(p["triangle"]) if i < n else _capi.DIFFRACTION_VOICE_TAG | (int(p["triangle"]) * 4 + int(p["edge"]))
             else:
-                key = self.SecondOrderKey(p["triangle"][0], p["triangle"][1]) if i < n + m + k else self.Diffraction2Key(p["triangle"], p["edge"])
+                key = self.SecondOrderKey(p["triangle"][0], p["triangle"][1]) if i < n + m + k else (
+                    self.Diffraction2Key(p["triangle"], p["edge"]) if i < n + m + k + k2 else self.MixedKey(p["triangle"], p["edge"], p["end"]))
                 if key in seen:
                     continue
                 seen.add(key)
@@ -1145,15 +1187,16 @@ class FrequenSeeAudioReflectionPlugin:
         return v[:kept]
 
     def ProcessAudio(self, components, buffers, rows, paths, right=None, reference_length=None, want_out=True, want_mix=False,
-                     diffraction=None, second=None, diffraction2=None):
+                     diffraction=None, second=None, diffraction2=None, mixed=None):
         """buffers[i] is components[i]'s block, rows[i] / paths[i] its results of UpdateReflectionPaths; diffraction = the (rows,
         paths) of UpdateDiffractionPaths, second = the (rows, paths) of UpdateReflection2Paths, diffraction2 = the (rows, paths) of
-        UpdateDiffraction2Paths, or None.  Returns what
+        UpdateDiffraction2Paths, mixed = the (rows, paths) of UpdateMixedPaths, or None.  Returns what
         Context.reflection_render_process_batch does."""
         voices = [self.Voices(rows[i], paths[i], right, reference_length,
                               None if diffraction is None else (diffraction[0][i], diffraction[1][i]),
                               None if second is None else (second[0][i], second[1][i]),
-                              None if diffraction2 is None else (diffraction2[0][i], diffraction2[1][i])) for i in range(len(components))]
+                              None if diffraction2 is None else (diffraction2[0][i], diffraction2[1][i]),
+                              None if mixed is None else (mixed[0][i], mixed[1][i])) for i in range(len(components))]
         return self.ctx.reflection_render_process_batch([c._src for c in components], buffers, voices,
                                                         want_out=want_out, want_mix=want_mix)
 

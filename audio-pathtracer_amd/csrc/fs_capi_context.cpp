@@ -652,7 +652,7 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->fft_graph) (void)hipGraphExecDestroy(ctx->fft_graph);
         if (ctx->h_fft_stage) (void)hipHostFree(ctx->h_fft_stage);
         for (float2* w : ctx->d_rev_tw) if (w) (void)hipFree(w);
-        for (PathStaging* st : {&ctx->direct_stage, &ctx->reflect_stage, &ctx->diffract_stage, &ctx->reflect2_stage, &ctx->diffract2_stage}) st->release();
+        for (PathStaging* st : {&ctx->direct_stage, &ctx->reflect_stage, &ctx->diffract_stage, &ctx->reflect2_stage, &ctx->diffract2_stage, &ctx->mixed_stage}) st->release();
         if (ctx->d_direct_off) (void)hipFree(ctx->d_direct_off);
         for (CallbackStage* st : {&ctx->rev_stage, &ctx->dr_stage, &ctx->rr_stage}) st->release();
         for (const auto& t : ctx->dr_tables) if (t.d) (void)hipFree(t.d);

@@ -1,7 +1,8 @@
 // fs_capi_paths.cpp — the path queries of a tick, each one call for all its sources: fs_update_direct_paths (fs_direct.hip) with the
 // sample offsets it uses, fs_update_reflection_paths (fs_reflect.hip), fs_update_diffraction_paths (fs_diffract.hip),
-// fs_update_reflection2_paths (fs_reflect2.hip) and fs_update_diffraction2_paths (fs_diffract2.hip), their defaults, and what the
-// five share on the host: the prologue, the staging and its layout, the packing of the sources and, for the four that return rows
+// fs_update_reflection2_paths (fs_reflect2.hip), fs_update_diffraction2_paths (fs_diffract2.hip) and fs_update_mixed_paths
+// (fs_mixed.hip), their defaults, and what the
+// six share on the host: the prologue, the staging and its layout, the packing of the sources and, for the five that return rows
 // and paths, one driver from the argument checks to the copy back (update_rows_paths).
 #include "fs_context.hpp"
 
@@ -24,6 +25,14 @@ static_assert(offsetof(fs_diffraction2_path, detour) == 8 && offsetof(fs_diffrac
                   offsetof(fs_diffraction2_path, material) == 76 && offsetof(fs_diffraction2_path, gain) == 84,
               "fs_diffraction2_path: the offsets of include/frequensee.h");
 static_assert(sizeof(fs_diffraction2_row) == 24, "fs_diffraction2_row: six words");
+static_assert(sizeof(fs_mixed_params) == 52, "fs_mixed_params: thirteen words");
+static_assert(sizeof(fs_mixed_path) == 112, "fs_mixed_path: twenty words and the bands");
+static_assert(offsetof(fs_mixed_path, detour) == 8 && offsetof(fs_mixed_path, bend_detour) == 12 && offsetof(fs_mixed_path, cos_bend) == 16 &&
+                  offsetof(fs_mixed_path, apex) == 20 && offsetof(fs_mixed_path, point) == 32 && offsetof(fs_mixed_path, direction) == 44 &&
+                  offsetof(fs_mixed_path, end) == 56 && offsetof(fs_mixed_path, triangle) == 60 && offsetof(fs_mixed_path, edge) == 68 &&
+                  offsetof(fs_mixed_path, material) == 72 && offsetof(fs_mixed_path, gain) == 80,
+              "fs_mixed_path: the offsets of include/frequensee.h");
+static_assert(sizeof(fs_mixed_row) == 24, "fs_mixed_row: six words");
 
 int PathStaging::grow(fs_context* ctx, int count, const PathLayout& pinned_layout, const PathLayout& device_layout) {
     pinned = pinned_layout;
@@ -123,7 +132,7 @@ bool params_or_default(const Params*& p, Params& def, void (*defaults)(Params*))
     return p->struct_size == sizeof(Params);
 }
 
-// What one of the four rows-and-paths queries is, beyond its kernels: its messages, its staging and the sizes the staging is laid
+// What one of the five rows-and-paths queries is, beyond its kernels: its messages, its staging and the sizes the staging is laid
 // out for (per row: counter arrays, near-list and candidate entries, bytes of a confirmed record, paths).
 template <typename Params, typename KP>
 struct RowsPathsQuery {
@@ -408,6 +417,49 @@ int fs_update_diffraction2_paths(fs_context* ctx, const fs_source* sources, int3
         dp.offset = p.offset;
         dp.merge = p.merge;
         band_factors(ctx, p.sound_speed, p.dist_divisor, dp.k, dp.lam5);
+    });
+}
+
+// ---- mixed paths: one reflection and one edge diffraction --------------------------------------------------------------------
+void fs_mixed_params_default(fs_mixed_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = sizeof(fs_mixed_params);
+    p->max_paths = 8;
+    p->max_near = 16384;
+    p->max_candidates = 1024;
+    p->max_length = 500.f;    // (at 750 a fifth of the old_mine rows overflow max_near, near counting a triangle up to four times: DESIGN.md "Mixed paths")
+    p->max_detour = 1000.f;   // the first-order call's: here it bounds no list
+    p->margin = 1e-3f;
+    p->offset = 0.1f;
+    p->merge = 1.0f;
+    p->step = 0.1f;
+    p->pullback = 0.1f;
+    p->dist_divisor = 1000.f;
+    p->sound_speed = 343.f;
+}
+
+int fs_update_mixed_paths(fs_context* ctx, const fs_source* sources, int32_t count, const fs_mixed_params* p, fs_mixed_row* rows,
+                          fs_mixed_path* paths) {
+    static const RowsPathsQuery<fs_mixed_params, MixedKParams> q = {
+        FS_MAX_MIXED_BATCH, "count out of range (1 .. FS_MAX_MIXED_BATCH)", "fs_mixed_params.struct_size mismatch",
+        "bad mixed-path params", fs_mixed_params_default, &fs_context::mixed_stage,
+        2, FS_MAX_MIXED_NEAR, FS_MAX_MIXED_CANDIDATES, sizeof(MixedRecord), FS_MAX_MIXED_PATHS, launch_mixed_paths};
+    return update_rows_paths(q, ctx, sources, count, p, rows, paths, [](const fs_mixed_params& p) {
+        return p.max_paths >= 1 && p.max_paths <= FS_MAX_MIXED_PATHS && p.max_near >= 1 && p.max_near <= FS_MAX_MIXED_NEAR &&
+               p.max_candidates >= 1 && p.max_candidates <= FS_MAX_MIXED_CANDIDATES && finite_above_zero(p.max_length) &&
+               finite_above_zero(p.max_detour) && finite_at_least_zero(p.margin) && finite_at_least_zero(p.offset) &&
+               finite_at_least_zero(p.merge) && finite_at_least_zero(p.step) && finite_at_least_zero(p.pullback) &&
+               finite_above_zero(p.dist_divisor) && finite_above_zero(p.sound_speed);
+    }, [ctx](MixedKParams& mp, const fs_mixed_params& p, const PathStaging& st) {
+        mp.l = staged_pair_lists(st, p.max_near, p.max_candidates);
+        mp.conf = reinterpret_cast<MixedRecord*>(st.dev(kSegConf));
+        mp.max_length = p.max_length;
+        mp.max_detour = p.max_detour;
+        mp.margin = p.margin;
+        mp.offset = p.offset;
+        mp.merge = p.merge;
+        band_factors(ctx, p.sound_speed, p.dist_divisor, mp.k, nullptr);
     });
 }
 

@@ -373,7 +373,7 @@ struct fs_context {
     // [FS_MAX_DIRECT_SAMPLES][FS_MAX_DIRECT_SAMPLES][3] by n - 1, each uploaded at its first use.
     // diffract_f: the band centres f_b of the edges in force (diffract_f_edges, diffract_f_bands: what they were built from; rebuilt
     // when fs_set_band_edges has changed them), shared by the two diffraction queries.
-    PathStaging direct_stage, reflect_stage, diffract_stage, reflect2_stage, diffract2_stage;
+    PathStaging direct_stage, reflect_stage, diffract_stage, reflect2_stage, diffract2_stage, mixed_stage;
     float* d_direct_off = nullptr;
     uint64_t direct_off_have = 0;
     double diffract_f[FS_MAX_BANDS] = {};

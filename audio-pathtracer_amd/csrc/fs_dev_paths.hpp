@@ -1,4 +1,4 @@
-// fs_dev_paths.hpp — what the five path queries (fs_direct.hip, fs_reflect.hip, fs_diffract.hip, fs_reflect2.hip, fs_diffract2.hip)
+// fs_dev_paths.hpp — what the six path queries (fs_direct.hip, fs_reflect.hip, fs_diffract.hip, fs_reflect2.hip, fs_diffract2.hip, fs_mixed.hip)
 // share on the device: the own-actor test, chain(o, d, len) of include/frequensee.h as one wave-convergent loop, the unpacking of a
 // triangle record and of its edges against a source and the listener, the scan and the pair kernels' scaffolds, the confirm kernels'
 // common pieces and the launches.  Nothing here knows which query calls it: what differs between them arrives as a callable.  Every fp32 operation stands where the header's rules put it (the files are built
@@ -12,7 +12,7 @@ namespace fs {
 namespace {
 
 static_assert(FS_MAX_REFLECTION_BATCH == FS_MAX_DIFFRACTION_BATCH && FS_MAX_REFLECTION_BATCH == FS_MAX_REFLECTION2_BATCH &&
-                  FS_MAX_REFLECTION_BATCH == FS_MAX_DIFFRACTION2_BATCH,
+                  FS_MAX_REFLECTION_BATCH == FS_MAX_DIFFRACTION2_BATCH && FS_MAX_REFLECTION_BATCH == FS_MAX_MIXED_BATCH,
               "the scan kernels stage a call's rows in one LDS array size");
 constexpr int kPathBatch = FS_MAX_REFLECTION_BATCH;
 constexpr int kRowsPerBlock = kBlock / 64;   // the wave-per-row kernels: a workgroup serves kBlock / 64 rows
@@ -191,6 +191,9 @@ __device__ __forceinline__ void scan_records(const DeviceScene& sc, const PathKH
 // read entry after entry at one address for the whole wave (an LDS broadcast).  test(held, the four float4, source) settles an
 // ordered pair; a survivor takes a place in the row's candidate list by atomicAdd (the counter keeps counting past the cap) as its
 // two near-list slots, 15 + 15 bits.  The row's source is read behind the early return and handed to the callables.
+//   A query that pairs two kinds of record keeps both in the one near list, the kind in the code, and its test answers with a mask
+// in place of a bool: bit b set = the pair is a candidate in variant b (fs_mixed.hip: the path's end), one list entry each, b in the
+// two bits above the slots (pair_variant).
 //   The grid is (tile of held entries, share of the LDS tiles, row): blockIdx.y strides over the LDS tiles, kPairSplit ways at most.
 // With (tile, row) alone a call for one source in a 5 000-triangle room is 20 workgroups on a chip of 256 compute units; split 16
 // ways it is 320.  The near count is known on the device only, so the grid is sized for the cap and a workgroup beyond the row's
@@ -198,7 +201,18 @@ __device__ __forceinline__ void scan_records(const DeviceScene& sc, const PathKH
 constexpr int kPairTile = kBlock;   // entries per LDS tile: one per thread
 constexpr int kPairSplit = 16;      // the LDS tiles of a row are shared among at most this many workgroups per tile of held entries
 constexpr int kSlotBits = 15;       // a candidate = slot of the held entry << 15 | slot of the streamed one
-static_assert(FS_MAX_REFLECTION2_NEAR <= 1 << kSlotBits && FS_MAX_DIFFRACTION2_NEAR <= 1 << kSlotBits, "a candidate is two near-list slots of 15 bits");
+static_assert(FS_MAX_REFLECTION2_NEAR <= 1 << kSlotBits && FS_MAX_DIFFRACTION2_NEAR <= 1 << kSlotBits && FS_MAX_MIXED_NEAR <= 1 << kSlotBits,
+              "a candidate is two near-list slots of 15 bits");
+// a test's verdict: emit(b << 2 kSlotBits) for the pair (bool) or for every variant b of its mask (uint32_t: two variants)
+template <typename Emit>
+__device__ __forceinline__ void for_each_verdict(bool passed, Emit&& emit) {
+    if (passed) emit(0u);
+}
+template <typename Emit>
+__device__ __forceinline__ void for_each_verdict(uint32_t mask, Emit&& emit) {
+    if (mask & 1u) emit(0u);
+    if (mask & 2u) emit(1u << (2 * kSlotBits));
+}
 struct PairRow {
     float4 a, b, c, d;
 };
@@ -229,15 +243,18 @@ __device__ __forceinline__ void pair_records(const PathKHead& h, const NearPairL
 #pragma unroll 1
         for (int j = 0; j < n; ++j) {   // (j is the same in every lane: each read below is one address per wave)
             const PairRow r = {s_tile[0][j], s_tile[1][j], s_tile[2][j], s_tile[3][j]};
-            if (first + j != slot && test(held, r, s4)) {
-                const uint32_t k = atomicAdd(&l.counters[row], 1u);
-                if (k < (uint32_t)l.max_candidates) l.cand[(size_t)row * l.max_candidates + k] = ((uint32_t)slot << kSlotBits) | (uint32_t)(first + j);
-            }
+            if (first + j != slot)
+                for_each_verdict(test(held, r, s4), [&](uint32_t variant) {
+                    const uint32_t k = atomicAdd(&l.counters[row], 1u);
+                    if (k < (uint32_t)l.max_candidates)
+                        l.cand[(size_t)row * l.max_candidates + k] = variant | ((uint32_t)slot << kSlotBits) | (uint32_t)(first + j);
+                });
         }
     }
 }
-// the two near-list entries of a candidate
-__device__ __forceinline__ uint32_t pair_held(const uint32_t* list, uint32_t code) { return list[code >> kSlotBits]; }
+// the two near-list entries of a candidate, and its variant
+__device__ __forceinline__ uint32_t pair_held(const uint32_t* list, uint32_t code) { return list[(code >> kSlotBits) & ((1u << kSlotBits) - 1u)]; }
+__device__ __forceinline__ uint32_t pair_variant(uint32_t code) { return code >> (2 * kSlotBits); }
 __device__ __forceinline__ uint32_t pair_streamed(const uint32_t* list, uint32_t code) { return list[code & ((1u << kSlotBits) - 1u)]; }
 
 // ---- the confirm kernels ----------------------------------------------------------------------------------------------------

@@ -521,6 +521,28 @@ struct Diffract2KParams {
     float lam5[FS_MAX_BANDS];   // lam5_b = 5 sound_speed dist_divisor / f_b
 };
 void launch_diffraction2_paths(const DeviceScene& sc, const Diffract2KParams& dp, hipStream_t s);
+// fs_mixed.hip (fs_update_mixed_paths): near scan, filter (edge record held, face streamed, both ends) and confirm.  A near code is
+// leaf position * 4 + edge for an edge record and leaf position * 4 + 3 for a face; a candidate carries its end above the two slots.
+// The arrays as Reflect2KParams.
+struct MixedRecord {
+    uint32_t length_bits, end, m, kr;   // m = the reflector's input index, kr = input index * 4 + edge of the edge record
+    float apex[3], point[3], direction[3];
+    float detour, bend_detour, cos_bend;
+    uint32_t material[2];
+    uint32_t kept;
+};
+static_assert(sizeof(MixedRecord) == 76, "MixedRecord: nineteen words");
+struct MixedKParams {
+    PathKHead h;
+    MixedRecord* conf;
+    fs_mixed_row* rows;
+    fs_mixed_path* paths;
+    int32_t max_paths;
+    NearPairLists l;
+    float max_length, max_detour, margin, offset, merge;
+    float k[FS_MAX_BANDS];      // k_b = 40 f_b / (sound_speed dist_divisor)
+};
+void launch_mixed_paths(const DeviceScene& sc, const MixedKParams& mp, hipStream_t s);
 constexpr int kReverbRing = 65536;   // per-channel history ring (floats), matches kRevRing in the kernels
 // fs_reverb.hip (the reverb callback): one descriptor per row of the call, in list order, read by every kernel of the callback.
 struct ReverbItem {

@@ -202,7 +202,7 @@ public:
             Check(fs_update_direct_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_DIRECT_BATCH), P, Out.data() + i));
         return Out;
     }
-    // The four rows-and-paths queries of every active source: Rows[i] and Paths[i * MaxPaths .. ) for ActiveSources[i]; MaxPaths =
+    // The five rows-and-paths queries of every active source: Rows[i] and Paths[i * MaxPaths .. ) for ActiveSources[i]; MaxPaths =
     // P->max_paths, the default's without P; one call per FS_MAX_*_BATCH sources.
     // the first-order specular reflections (fs_update_reflection_paths)
     struct ReflectionPaths { int32_t MaxPaths = 0; std::vector<fs_reflection_row> Rows; std::vector<fs_reflection_path> Paths; };
@@ -225,6 +225,11 @@ public:
     Diffraction2Paths UpdateDiffraction2Paths(const fs_diffraction2_params* P = nullptr) {
         return UpdateRowsPaths<Diffraction2Paths>(P, fs_diffraction2_params_default, fs_update_diffraction2_paths, FS_MAX_DIFFRACTION2_PATHS,
                                                   FS_MAX_DIFFRACTION2_BATCH);
+    }
+    // the paths off one reflector and round one edge (fs_update_mixed_paths)
+    struct MixedPaths { int32_t MaxPaths = 0; std::vector<fs_mixed_row> Rows; std::vector<fs_mixed_path> Paths; };
+    MixedPaths UpdateMixedPaths(const fs_mixed_params* P = nullptr) {
+        return UpdateRowsPaths<MixedPaths>(P, fs_mixed_params_default, fs_update_mixed_paths, FS_MAX_MIXED_PATHS, FS_MAX_MIXED_BATCH);
     }
 private:
     template <typename Result, typename Params, typename Row, typename Path>
@@ -507,27 +512,43 @@ public:
     // law as above, key = SecondOrderKey(a, b).  Two second-order paths of the row whose keys collide: the earlier in the row — the
     // shorter, ties by (a, b) — is kept and the other dropped (the renderer refuses duplicate keys).  TRow / TPaths (the same
     // source's row and paths of fs_update_diffraction2_paths) append, last, one voice per returned path round two edges: band_gain =
-    // gain, key = Diffraction2Key(triangle, edge); on colliding keys the earlier in the row is kept likewise
+    // gain, key = Diffraction2Key(triangle, edge); on colliding keys the earlier in the row is kept likewise.  MRow / MPaths (the
+    // same source's row and paths of fs_update_mixed_paths) append, after those, one voice per returned path off a reflector and
+    // round an edge: band_gain = gain, key = MixedKey(triangle, edge, end), colliding keys likewise; with them a diffraction path's
+    // triangle must stay below 2^28, or its key would reach the mixed paths' range
     static uint32_t SecondOrderKey(uint32_t A, uint32_t B) { return 0x40000000u | ((A * 2654435761u + B) >> 2); }
     static uint32_t Diffraction2Key(const uint32_t (&Triangle)[2], const uint32_t (&Edge)[2]) {
         return 0x20000000u | (((4u * Triangle[0] + Edge[0]) * 2654435761u + (4u * Triangle[1] + Edge[1])) >> 3);
+    }
+    static uint32_t MixedKey(const uint32_t (&Triangle)[2], uint32_t Edge, uint32_t End) {
+        return 0xC0000000u | ((Triangle[0] * 2654435761u + 4u * (2u * (4u * Triangle[1] + Edge) + End)) >> 2);
     }
     std::vector<fs_reflection_voice> Voices(const fs_reflection_row& Row, const fs_reflection_path* Paths, const FVector* Right = nullptr,
                                             float ReferenceLength = 0.0f, const fs_diffraction_row* DRow = nullptr,
                                             const fs_diffraction_path* DPaths = nullptr, const fs_reflection2_row* SRow = nullptr,
                                             const fs_reflection2_path* SPaths = nullptr, const fs_diffraction2_row* TRow = nullptr,
-                                            const fs_diffraction2_path* TPaths = nullptr) const {
+                                            const fs_diffraction2_path* TPaths = nullptr, const fs_mixed_row* MRow = nullptr,
+                                            const fs_mixed_path* MPaths = nullptr) const {
         const size_t NR = (size_t)Row.returned, ND = DRow && DPaths ? (size_t)DRow->returned : 0, NS = SRow && SPaths ? (size_t)SRow->returned : 0;
-        const size_t NT = TRow && TPaths ? (size_t)TRow->returned : 0;
+        const size_t NT = TRow && TPaths ? (size_t)TRow->returned : 0, NM = MRow && MPaths ? (size_t)MRow->returned : 0;
         std::vector<fs_reflection_voice> V;
-        V.reserve(NR + ND + NS + NT);
-        for (size_t i = 0; i < NR + ND + NS + NT; ++i) {
+        V.reserve(NR + ND + NS + NT + NM);
+        for (size_t i = 0; i < NR + ND + NS + NT + NM; ++i) {
+            if (i >= NR + ND + NS + NT) {   // a mixed path: every field it needs under one name
+                const fs_mixed_path& M = MPaths[i - NR - ND - NS - NT];
+                const uint32_t Key = MixedKey(M.triangle, M.edge, M.end);
+                if (std::any_of(V.begin() + (std::ptrdiff_t)(NR + ND), V.end(), [&](const fs_reflection_voice& X) { return X.key == Key; })) continue;
+                V.push_back(Voice(Key, M.delay, M.gain, M.direction, M.length, Right, ReferenceLength));
+                continue;
+            }
             const bool Refl = i < NR, Second = i >= NR + ND && i < NR + ND + NS, Thick = i >= NR + ND + NS;
             const fs_reflection2_path* S = Second ? SPaths + (i - NR - ND) : nullptr;
             const fs_diffraction2_path* T = Thick ? TPaths + (i - NR - ND - NS) : nullptr;
             const uint32_t Tri = Refl ? Paths[i].triangle : (Second || Thick ? 0u : DPaths[i - NR].triangle);
             if ((ND || (SRow && SPaths) || (TRow && TPaths)) && Tri >= (0x80000000u >> 2))
                 throw std::runtime_error("FrequenSee: triangle index 2^29 or above: the keys of the path kinds would collide");
+            if (MRow && MPaths && !Refl && !Second && !Thick && Tri >= (0x80000000u >> 3))
+                throw std::runtime_error("FrequenSee: a diffraction path's triangle index is 2^28 or above: its key would collide with the mixed paths' keys");
             const float* Dir = Refl ? Paths[i].direction : (Second ? S->direction : (Thick ? T->direction : DPaths[i - NR].direction));
             const float* Gain = Refl ? Paths[i].reflectance : (Second ? S->reflectance : (Thick ? T->gain : DPaths[i - NR].gain));
             const float Delay = Refl ? Paths[i].delay : (Second ? S->delay : (Thick ? T->delay : DPaths[i - NR].delay));
@@ -535,24 +556,29 @@ public:
             const uint32_t Key = Refl ? Tri : (Second ? SecondOrderKey(S->triangle[0], S->triangle[1])
                                                       : (Thick ? Diffraction2Key(T->triangle, T->edge) : (0x80000000u | (Tri * 4u + DPaths[i - NR].edge))));
             if ((Second || Thick) && std::any_of(V.begin() + (std::ptrdiff_t)(NR + ND), V.end(), [&](const fs_reflection_voice& X) { return X.key == Key; })) continue;
-            V.emplace_back();
-            const size_t Slot = V.size() - 1;
-            V[Slot].key = Key;
-            V[Slot].delay = TargetDelay(Delay);
-            for (int b = 0; b < FS_MAX_BANDS; ++b) V[Slot].band_gain[b] = Gain[b];
-            double L = 1.0, R = 1.0;
-            if (Right) {
-                const double Dot = (double)Dir[0] * Right->X + (double)Dir[1] * Right->Y + (double)Dir[2] * Right->Z;
-                const double T = (Dot + 1.0) * 3.14159265358979323846 / 4.0;
-                L = std::cos(T); R = std::sin(T);
-            }
-            if (ReferenceLength > 0.0f) {
-                const double G = std::min(1.0, (double)ReferenceLength / (double)Length);
-                L *= G; R *= G;
-            }
-            V[Slot].channel_gain[0] = (float)L;
-            V[Slot].channel_gain[1] = (float)R;
+            V.push_back(Voice(Key, Delay, Gain, Dir, Length, Right, ReferenceLength));
         }
+        return V;
+    }
+    // one voice: the key, the target delay, the band gains, and the pan and distance law of Voices
+    fs_reflection_voice Voice(uint32_t Key, float Delay, const float* Gain, const float* Dir, float Length, const FVector* Right,
+                              float ReferenceLength) const {
+        fs_reflection_voice V{};
+        V.key = Key;
+        V.delay = TargetDelay(Delay);
+        for (int b = 0; b < FS_MAX_BANDS; ++b) V.band_gain[b] = Gain[b];
+        double L = 1.0, R = 1.0;
+        if (Right) {
+            const double Dot = (double)Dir[0] * Right->X + (double)Dir[1] * Right->Y + (double)Dir[2] * Right->Z;
+            const double T = (Dot + 1.0) * 3.14159265358979323846 / 4.0;
+            L = std::cos(T); R = std::sin(T);
+        }
+        if (ReferenceLength > 0.0f) {
+            const double G = std::min(1.0, (double)ReferenceLength / (double)Length);
+            L *= G; R *= G;
+        }
+        V.channel_gain[0] = (float)L;
+        V.channel_gain[1] = (float)R;
         return V;
     }
     // In [count][FrameSize * 2] interleaved stereo, row i for Sources[i], Rows[i] and Paths[i * MaxPaths ..] (the arrays
@@ -560,23 +586,28 @@ public:
     // fp32 sum of the rows in list order) or nullptr, Counts [count] or nullptr; Diffraction = UpdateDiffractionPaths' result for the
     // same sources (its voices follow each source's reflections) or nullptr; Second = UpdateReflection2Paths' result for the same
     // sources (its voices follow those) or nullptr; Thick = UpdateDiffraction2Paths' result for the same sources (its voices come
-    // last) or nullptr.  A source's table has MaxPaths + Diffraction->MaxPaths + Second->MaxPaths + Thick->MaxPaths entries,
-    // FS_MAX_REFLECTION_VOICES (32) at most: the four defaults of 8, 4, 16 and 4 fit, 16 + 16 + 16 is refused
+    // after those) or nullptr; Mixed = UpdateMixedPaths' result for the same sources (its voices come last) or nullptr.  A source's
+    // table has MaxPaths + Diffraction->MaxPaths + Second->MaxPaths + Thick->MaxPaths + Mixed->MaxPaths entries,
+    // FS_MAX_REFLECTION_VOICES (32) at most: the first four defaults of 8, 4, 16 and 4 fit, with the mixed paths' 8 a host lowers one
+    // of them; 16 + 16 + 16 is refused
     void ProcessAudio(const std::vector<FrequenSeeAudioComponent*>& Sources, const float* In, const std::vector<fs_reflection_row>& Rows,
                       const std::vector<fs_reflection_path>& Paths, int MaxPaths, float* Out, float* Mix = nullptr,
                       const FVector* Right = nullptr, float ReferenceLength = 0.0f, fs_reflection_render_row* Counts = nullptr,
                       const AudioRayTracingSubsystem::DiffractionPaths* Diffraction = nullptr,
                       const AudioRayTracingSubsystem::Reflection2Paths* Second = nullptr,
-                      const AudioRayTracingSubsystem::Diffraction2Paths* Thick = nullptr) {
+                      const AudioRayTracingSubsystem::Diffraction2Paths* Thick = nullptr,
+                      const AudioRayTracingSubsystem::MixedPaths* Mixed = nullptr) {
         const int DMax = Diffraction ? Diffraction->MaxPaths : 0, SMax = Second ? Second->MaxPaths : 0, TMax = Thick ? Thick->MaxPaths : 0;
-        const int Stride = MaxPaths + DMax + SMax + TMax;
+        const int MMax = Mixed ? Mixed->MaxPaths : 0;
+        const int Stride = MaxPaths + DMax + SMax + TMax + MMax;
         if (Stride > FS_MAX_REFLECTION_VOICES)
             throw std::runtime_error("FrequenSee: max_paths of the reflections, the diffraction paths and the second-order paths add up to " +
                                      std::to_string(Stride) + " voices per source, more than FS_MAX_REFLECTION_VOICES");
-        if (Rows.size() != Sources.size() || Paths.size() != Sources.size() * (size_t)MaxPaths || MaxPaths < 1 || DMax < 0 || SMax < 0 || TMax < 0 ||
+        if (Rows.size() != Sources.size() || Paths.size() != Sources.size() * (size_t)MaxPaths || MaxPaths < 1 || DMax < 0 || SMax < 0 || TMax < 0 || MMax < 0 ||
             (Diffraction && (Diffraction->Rows.size() != Sources.size() || Diffraction->Paths.size() != Sources.size() * (size_t)DMax)) ||
             (Second && (Second->Rows.size() != Sources.size() || Second->Paths.size() != Sources.size() * (size_t)SMax)) ||
-            (Thick && (Thick->Rows.size() != Sources.size() || Thick->Paths.size() != Sources.size() * (size_t)TMax)))
+            (Thick && (Thick->Rows.size() != Sources.size() || Thick->Paths.size() != Sources.size() * (size_t)TMax)) ||
+            (Mixed && (Mixed->Rows.size() != Sources.size() || Mixed->Paths.size() != Sources.size() * (size_t)MMax)))
             throw std::runtime_error("FrequenSee: one row and MaxPaths paths per source");
         std::vector<fs_source> H;
         std::vector<fs_reflection_voice> All(Sources.size() * (size_t)Stride);
@@ -589,7 +620,9 @@ public:
                                                               Second ? &Second->Rows[i] : nullptr,
                                                               Second ? Second->Paths.data() + i * (size_t)SMax : nullptr,
                                                               Thick ? &Thick->Rows[i] : nullptr,
-                                                              Thick ? Thick->Paths.data() + i * (size_t)TMax : nullptr);
+                                                              Thick ? Thick->Paths.data() + i * (size_t)TMax : nullptr,
+                                                              Mixed ? &Mixed->Rows[i] : nullptr,
+                                                              Mixed ? Mixed->Paths.data() + i * (size_t)MMax : nullptr);
             std::copy(V.begin(), V.end(), All.begin() + (std::ptrdiff_t)(i * (size_t)Stride));
             N.push_back((int32_t)V.size());
         }

@@ -59,6 +59,7 @@
  *             fs_diffraction_params_default fs_update_diffraction_paths
  *             fs_reflection2_params_default fs_update_reflection2_paths
  *             fs_diffraction2_params_default fs_update_diffraction2_paths
+ *             fs_mixed_params_default fs_update_mixed_paths
  *             fs_direct_band_kernels fs_direct_render_init fs_direct_render_release fs_direct_render_process_batch
  *             fs_reflection_render_init fs_reflection_render_release fs_reflection_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
@@ -1067,6 +1068,124 @@ void fs_diffraction2_params_default(fs_diffraction2_params* p);
 int fs_update_diffraction2_paths(fs_context* ctx, const fs_source* sources, int32_t count,
                                  const fs_diffraction2_params* params /* NULL = defaults */,
                                  fs_diffraction2_row* rows /* [count] */, fs_diffraction2_path* paths /* [count][max_paths] */);
+
+/* ---- mixed paths (EXTENDED): one specular reflection and one edge diffraction of every source of a tick ---------------------
+ * The last kind of early path of total order two: a path that reflects off one triangle and bends round one edge.  It is what is
+ * left of the early reflections of a source that has stepped behind a partition — the reflection off the wall behind it, the floor
+ * and the ceiling bounce still reach the listener round the rim, a few dB down and a little later — so that occluded reflections
+ * fade rather than vanish.  A path runs listener L -> ... -> source S over one reflector triangle m and one edge record
+ * r = (triangle i, edge j) of "second-order diffraction paths"; `end` says where the reflector sits, index 0 the listener's end as
+ * everywhere else:
+ *   end = 0:  L -> R on m -> E on r -> S          end = 1:  L -> E on r -> R on m -> S
+ * A is the end next to the reflector (L for end = 0, S for end = 1), Z the other.  Exhaustive: no sampling, no seed, no edge
+ * adjacency.  Specified to the bit with the conventions of "diffraction paths" and "second-order reflection paths"
+ * (-ffp-contract=off, every fp32 operation rounded on its own in the order written, fmaf fused, a.b = (a.x b.x + a.y b.y) + a.z b.z,
+ * cross = product, product, subtract; divide and sqrtf correctly rounded; the records v0, e1, e2; own actors by the ids so / lo).
+ * Every marginal decision beyond the filters is taken by the closest-hit query fs_trace_rays answers.
+ *   Per source at S, listener at L:
+ *   0. Near set (part of the definition; it bounds the cost).  Triangle k is a near FACE by step 0 of "second-order reflection
+ *      paths" with this call's max_length.  Edge record r is a near EDGE iff nn != 0, ww != 0, oo != 0, its triangle is not an own
+ *      actor's and ((sqrtf(rS.rS) + sqrtf(rL.rL)) - (reach + reach)) <= max_length with rS = S - a, rL = L - a, reach = sqrtf(ww).
+ *      near = the number of near faces plus the number of near edges: one cap covers both.  near > max_near:
+ *      flags = FS_MIXED_NEAR_OVERFLOW, every other count is 0 and nothing else of the row is computed.
+ *   1. Filter, for every near face m, near edge r = (i, j) and end = 0, 1; a triple is rejected at the first test it fails.
+ *      i == m: rejected (compared as triangles: an edge never pairs with its own triangle).
+ *      Image: hA = (A - v0_m).n_m; hA == 0: rejected.  k = (2 hA) / nn_m; A' = A - k n_m per component.
+ *      Diffraction filter: step 1 of "diffraction paths" for the edge record r, operation by operation, with S := A' for end = 1
+ *      and L := A' for end = 0, the other end unchanged (own actors and nn, ww, oo are settled by the near set): hS, hL strictly
+ *      opposite, tS, tL, dS, dL, sum != 0, t within margin, E = fmaf(t, w, a), u = S - E, v = E - L, lS, lL != 0, length = lS + lL,
+ *      and the shadow-zone test (X - E).o <= 0 with s = hS / (hS - hL), X = fmaf(s, L - S, S).  The rule's `distance` of the
+ *      substituted ends, sqrtf(g.g) with g = S - L, is here called unfolded = |A' - Z|; bend_detour = length - unfolded.  Kept
+ *      iff bend_detour <= max_detour && length <= max_length.
+ *      Reflection point: D = A' - E per component; MT(E, D, m) of "second-order reflection paths" passes with this call's margin.
+ *      candidates = the number of (m, r, end) that pass (exact even where the list is capped).  candidates > max_candidates:
+ *      flags = FS_MIXED_OVERFLOW, confirmed = found = returned = 0.
+ *   2. Confirmation, per candidate: four legs.  hZ = (Z - v0_i).n_i, the rule's hS or hL of the end that is not imaged.  The
+ *      first-order rule's construction at the apex with nh the unit normal of the edge's triangle towards Z: io = 1.0f / sqrtf(oo),
+ *      oh = o io; in = 1.0f / sqrtf(nn); nh = n in if hZ > 0 else n (-in); Eo = fmaf(offset, oh, E); EZ = fmaf(offset, nh, Eo);
+ *      EA = fmaf(-offset, nh, Eo).
+ *      Leg 1: e = Z - EZ, len = sqrtf(e.e); chain(EZ, e (1.0f / len), len - pullback) of "direct paths" with max_surfaces = 0 and
+ *      this call's step; len == 0: reached.
+ *      Leg 2: chain(EZ, -nh, 2.0f offset): the short leg that rejects the interior edges of tessellated surfaces.
+ *      Leg 3: D3 = A' - EA; len3 = sqrtf(D3.D3); d = D3 (1.0f / len3); the first-order reflection rule's leg 1 from o = EA along d
+ *      with rem = len3: own actors are passed by adv = t + step, the first other triangle hit must be m.  It yields
+ *      R = fmaf(t, d, o) per component.  No hit, any other triangle, out of queries: rejected.
+ *      Leg 4: e = A - R; len4 = sqrtf(e.e); len4 == 0: rejected.  d4 = e (1.0f / len4);
+ *      chain(fmaf(offset, d4, R), d4, (len4 - offset) - pullback) likewise.
+ *      CONFIRMED iff legs 1, 2 and 4 reached with crossed == 0 and leg 3 hit m.  confirmed = the number confirmed.
+ *   3. Merge.  A convex corner is found once from each of its faces.  key = (length as fp32 bits, end, m, 4 i + j), compared as a
+ *      tuple (m, i input indices).  A confirmed entry is DROPPED iff some confirmed entry of the row with a smaller key — dropped
+ *      itself or not — has the same end, the same m and q = E - E', q.q < merge merge.  found = the number kept.
+ *   4. Row.  The kept entries are ordered by key ascending; the first returned = min(found, max_paths) are written, the entries
+ *      beyond `returned` (all of them for an overflowed row) as all-zero bytes.  delay = (length / dist_divisor) / sound_speed;
+ *      detour = length - sqrtf(g.g) with g = S - L of the real ends; bend_detour as above; cos_bend = (u.v) / (lS lL) of the filter
+ *      (at E in the unfolded space; 1 = no bend); apex = E; point = R; direction = the unit vector from the listener towards the
+ *      first point of the path: v (1.0f / lL) for end = 1 (towards E), -d4 per component for end = 0 (towards R); triangle[0] = m,
+ *      triangle[1] = i; edge = j; material[0], material[1] their material ids;
+ *      gain[b] = gm[b] * (1.0f / sqrtf(3.0f + k_b bend_detour)) for b < num_bands and 0 beyond, gm the reflector's specular gain
+ *      of "reflection paths" (1 for a surface without a material), k_b the table of "diffraction paths": the barrier estimate
+ *      times the specular gain.  It is an estimate a host is free to ignore — no uniform theory of diffraction — and it contains
+ *      no distance law.  Out of scope: more than one reflection with a diffraction, two diffractions with a reflection.
+ *      Nothing depends on which builder made the tree, on the order of collection or on count.  An empty committed scene gives
+ *      rows of zeros.
+ *   The key a host gives the voice of such a path (fs_reflection_render_process_batch) is 0xC0000000 | (h >> 2) with
+ *   h = (m * 2654435761 + 4 (2 (4 i + j) + end)) mod 2^32 (the factor 4 keeps the edge and the end above the shift: the two ends of
+ *   one reflector and edge record, which a source and a listener either side of a partition both have, get two keys): disjoint from the reflections' keys (below 2^29), the second-order keys
+ *   (0x20000000 | ..., 0x40000000 | ...) and, in a scene of fewer than 2^28 triangles, from the first-order diffraction keys
+ *   (0x80000000 | (4 triangle + edge) stays below 0xC0000000 there).  Two paths of one row may share a key: a host keeps the
+ *   earlier in the row and drops the other.
+ *   Errors, ordering, refusals and staging: as fs_update_diffraction2_paths, with FS_MAX_MIXED_BATCH — the source table's upload,
+ *   one clear (of both counter arrays), THREE launches on the compute stream (the near scan of all triangles against all rows; the
+ *   filter over every row's near list; the confirmation, a wave per row), one copy back and one wait, whatever count is; staging
+ *   of its own, grown only at the first call with a larger count.  max_length and max_detour must be finite and > 0.
+ *   Cost: (near edges) x (near faces) x 2 filter tests per row, at most near^2 / 2, near counting a triangle up to four times.  The
+ *   default max_length keeps near below the default max_near around a listener in a mine of 100 000 triangles (at most 8 472 of
+ *   16 384 for sources within 600 cm; at 750 cm 27 of 128 such rows overflow, at 1000 cm 126, at 1500 cm all: measured on the
+ *   MI355X, DESIGN.md "Mixed paths").  A room of a few thousand triangles affords 1500 and more. */
+#define FS_MAX_MIXED_PATHS         16
+#define FS_MAX_MIXED_NEAR       32768
+#define FS_MAX_MIXED_CANDIDATES  2048
+#define FS_MAX_MIXED_BATCH        256
+#define FS_MIXED_OVERFLOW          1u   /* fs_mixed_row.flags: more candidates than max_candidates */
+#define FS_MIXED_NEAR_OVERFLOW     2u   /* fs_mixed_row.flags: more near faces and edges than max_near */
+typedef struct fs_mixed_params {
+    uint32_t struct_size;     /* = sizeof(fs_mixed_params) */
+    int32_t  max_paths;       /* 1 .. FS_MAX_MIXED_PATHS, default 8: rows of `paths` per source */
+    int32_t  max_near;        /* 1 .. FS_MAX_MIXED_NEAR, default 16384 */
+    int32_t  max_candidates;  /* 1 .. FS_MAX_MIXED_CANDIDATES, default 1024 */
+    float    max_length;      /* cm, > 0, finite; default 500: the longest path looked for; it bounds near, and with it the cost */
+    float    max_detour;      /* cm, > 0, finite; default 1000: the largest bend_detour, as fs_diffraction_params */
+    float    margin;          /* slack of the apex's edge parameter and of the reflection point's barycentrics, >= 0; default 1e-3 */
+    float    offset;          /* cm the legs' ends stand off the edge and the reflector, >= 0; default 0.1 */
+    float    merge;           /* cm within which two apexes are one path, >= 0; default 1.0 */
+    float    step;            /* as fs_diffraction_params, default 0.1 */
+    float    pullback;        /* cm legs 1 and 4 stop short of their ends, >= 0; default 0.1 */
+    float    dist_divisor;    /* 1000, as fs_params */
+    float    sound_speed;     /* 343, as fs_params */
+} fs_mixed_params;
+
+typedef struct fs_mixed_path {
+    float    length;          /* cm, the whole path: |A' - E| + |E - Z| */
+    float    delay;           /* s, on the impulse response's time axis: (length / dist_divisor) / sound_speed */
+    float    detour;          /* cm, length - |S - L| */
+    float    bend_detour;     /* cm, length - |A' - Z|: what the bend alone adds to the reflection's unfolded segment */
+    float    cos_bend;        /* cosine of the angle the unfolded path turns by at the apex; 1 = straight on */
+    float    apex[3];         /* E */
+    float    point[3];        /* R, the reflection point */
+    float    direction[3];    /* unit, from the listener towards R (end 0) or E (end 1): what a host pans by */
+    uint32_t end;             /* 0: the reflector is next to the listener; 1: next to the source */
+    uint32_t triangle[2];     /* input indices of the reflector m and of the triangle i the edge belongs to */
+    uint32_t edge;            /* 0: v0 -> v1, 1: v1 -> v2, 2: v2 -> v0 */
+    uint32_t material[2];     /* their material ids (FS_NO_MATERIAL possible) */
+    float    gain[FS_MAX_BANDS]; /* specular gain x barrier estimate; bands beyond num_bands: 0 */
+} fs_mixed_path;              /* an array element: no struct_size; 112 bytes */
+
+typedef struct fs_mixed_row { uint32_t near, candidates, confirmed, found, returned, flags; } fs_mixed_row;
+
+void fs_mixed_params_default(fs_mixed_params* p);
+int fs_update_mixed_paths(fs_context* ctx, const fs_source* sources, int32_t count,
+                          const fs_mixed_params* params /* NULL = defaults */,
+                          fs_mixed_row* rows /* [count] */, fs_mixed_path* paths /* [count][max_paths] */);
 
 /* ---- engine line trace the BVH kernel replaces (UWorld::LineTraceSingleByObjectType; call sites
  *      ARTS.cpp:252-254 any-hit, :340-342 closest-hit). Batch query, host arrays. ------------------- */
