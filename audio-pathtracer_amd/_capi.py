@@ -63,6 +63,8 @@ EXPORTS = [
     "fs_mixed_params_default", "fs_update_mixed_paths",
     "fs_direct_band_kernels", "fs_direct_render_init", "fs_direct_render_release", "fs_direct_render_process_batch",
     "fs_reflection_render_init", "fs_reflection_render_release", "fs_reflection_render_process_batch",
+    "fs_hrtf_set", "fs_hrtf_info", "fs_hrtf_spherical_head",
+    "fs_binaural_render_init", "fs_binaural_render_release", "fs_binaural_render_process_batch",
 ]
 MAX_DIRECTIVITY_SAMPLES = 181   # FS_MAX_DIRECTIVITY_SAMPLES: 1 degree steps
 ORDER_UNBOUNDED = 0x7fffffff    # FS_ORDER_UNBOUNDED: no upper end of a source's order window
@@ -110,6 +112,11 @@ MIXED_VOICE_TAG = 0xC0000000   # a mixed voice's key: 0xC0000000 | (((m * 265443
 DIRECT_RENDER_MAX_TAPS = 2047
 MAX_REFLECTION_VOICES = 32
 MAX_REFLECTION_RENDER_BATCH = 256
+MAX_HRTF_DIRECTIONS = 4096
+MAX_HRTF_TAPS = 512
+HRTF_DEFAULT_RADIUS_CM = 8.75
+HRTF_DEFAULT_SOUND_SPEED_CM_S = 34300.0
+BINAURAL_DIRECT_KEY = 0x1FFFFFFF   # the direct sound's voice: a first-order key (a triangle index) no scene below 2^29 - 1 triangles uses
 
 
 class SoundParams(C.Structure):
@@ -479,6 +486,34 @@ class ReflectionRenderRow(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("sounding", "started", "ended", "dropped")]
 
 
+class HrtfDesc(C.Structure):
+    """fs_hrtf_desc (include/frequensee.h): the HRIR set handed to fs_hrtf_set"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("directions", C.c_int32),
+        ("taps", C.c_int32),
+        ("sample_rate", C.c_int32),
+        ("dirs", C.c_void_p),
+        ("hrir", C.c_void_p),
+    ]
+
+
+class BinauralVoice(C.Structure):
+    """fs_binaural_voice (include/frequensee.h): one entry of a source's voice list, an array element (no struct_size)"""
+    _fields_ = [
+        ("key", C.c_uint32),
+        ("delay", C.c_float),
+        ("band_gain", C.c_float * MAX_BANDS),
+        ("gain", C.c_float),
+        ("direction", C.c_float * 3),
+    ]
+
+
+class BinauralRenderRow(C.Structure):
+    """fs_binaural_render_row (include/frequensee.h): one source's counts of a callback, an array element (no struct_size)"""
+    _fields_ = [(k, C.c_uint32) for k in ("sounding", "started", "ended", "dropped")]
+
+
 class FrequenSeeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"frequensee status {code}: {msg}")
@@ -607,6 +642,12 @@ def load():
         "fs_reflection_render_init": (C.c_int, [vp, i32, i32, i32, i32, C.c_float]),
         "fs_reflection_render_release": (C.c_int, [vp, i32]),
         "fs_reflection_render_process_batch": (C.c_int, [vp, C.c_void_p, i32, f32p, C.c_void_p, C.c_void_p, i32, f32p, f32p, C.c_void_p]),
+        "fs_hrtf_set": (C.c_int, [vp, C.POINTER(HrtfDesc)]),
+        "fs_hrtf_info": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "fs_hrtf_spherical_head": (C.c_int, [i32, C.c_float, C.c_float, i32, i32, f32p, f32p]),
+        "fs_binaural_render_init": (C.c_int, [vp, i32, i32, i32, i32, C.c_float]),
+        "fs_binaural_render_release": (C.c_int, [vp, i32]),
+        "fs_binaural_render_process_batch": (C.c_int, [vp, C.c_void_p, i32, f32p, C.c_void_p, C.c_void_p, i32, f32p, f32p, C.c_void_p]),
         "fs_gather_energy": (C.c_int, [vp, i32, f32p, i32]),
         "fs_gather_energy_async": (C.c_int, [vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     }

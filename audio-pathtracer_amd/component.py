@@ -597,6 +597,90 @@ class Context:
                                                                mix.ctypes.data if want_mix else None, rows.ctypes.data))
         return self._callback_close(out, mix, rows)
 
+    # ---- binaural voices on the audio thread: the voice bank with a direction per voice and an HRIR set per context ----
+    BINAURAL_VOICE_DTYPE = np.dtype([("key", np.uint32), ("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,)),
+                                     ("gain", np.float32), ("direction", np.float32, (3,))])
+    BINAURAL_RENDER_ROW_DTYPE = np.dtype([("sounding", np.uint32), ("started", np.uint32), ("ended", np.uint32), ("dropped", np.uint32)])
+
+    @staticmethod
+    def hrtf_spherical_head(sample_rate, directions, taps, radius_cm=_capi.HRTF_DEFAULT_RADIUS_CM,
+                            sound_speed_cm_s=_capi.HRTF_DEFAULT_SOUND_SPEED_CM_S):
+        """fs_hrtf_spherical_head: (dirs [directions][3], hrir [directions][2][taps]) of the header's spherical-head model — a
+        model: interaural delay and level difference, no pinna"""
+        n, H = max(int(directions), 0), max(int(taps), 0)
+        dirs, hrir = np.zeros((n, 3), np.float32), np.zeros((n, 2, H), np.float32)
+        rc = _capi.load().fs_hrtf_spherical_head(int(sample_rate), float(radius_cm), float(sound_speed_cm_s), int(directions), int(taps),
+                                                 dirs.ctypes.data if dirs.size else None, hrir.ctypes.data if hrir.size else None)
+        if rc != _capi.OK:
+            raise FrequenSeeError(rc, "fs_hrtf_spherical_head: directions 1 .. 4096, taps 1 .. 512 and at least ceil((a / c)(1 + pi / 2) fs) + 2, "
+                                      "positive finite radius and sound speed")
+        return dirs, hrir
+
+    def hrtf_set(self, dirs, hrir, sample_rate=None):
+        """fs_hrtf_set: dirs [n][3] unit vectors in the head frame (x forward, y right, z up), hrir [n][2][H] (ear 0 left);
+        dirs = None clears the set.  Not concurrent with a callback; every held binaural voice starts anew afterwards"""
+        if dirs is None:
+            self.check(self.lib.fs_hrtf_set(self.h, None))
+            return
+        d = np.ascontiguousarray(dirs, dtype=np.float32)
+        h = np.ascontiguousarray(hrir, dtype=np.float32)
+        if d.ndim != 2 or d.shape[1] != 3 or h.ndim != 3 or h.shape[:2] != (d.shape[0], 2):
+            raise ValueError("dirs must be [n][3] and hrir [n][2][H]")
+        desc = _capi.HrtfDesc()
+        desc.struct_size = C.sizeof(_capi.HrtfDesc)
+        desc.directions, desc.taps = d.shape[0], h.shape[2]
+        desc.sample_rate = int(self.cfg.sample_rate if sample_rate is None else sample_rate)
+        desc.dirs, desc.hrir = d.ctypes.data, h.ctypes.data
+        self.check(self.lib.fs_hrtf_set(self.h, C.byref(desc)))
+
+    def hrtf_info(self):
+        """(directions, taps) of the set in force, (0, 0) without one"""
+        n, H = C.c_int32(-1), C.c_int32(-1)
+        self.check(self.lib.fs_hrtf_info(self.h, C.byref(n), C.byref(H)))
+        return n.value, H.value
+
+    def binaural_render_init(self, src, frame_size=1024, taps=255, voices=32, max_delay_seconds=1.0):
+        self.check(self.lib.fs_binaural_render_init(self.h, src, int(frame_size), int(taps), int(voices), float(max_delay_seconds)))
+        self._br_frame = getattr(self, "_br_frame", {})
+        self._br_frame[src] = int(frame_size)
+
+    def binaural_render_release(self, src):
+        self.check(self.lib.fs_binaural_render_release(self.h, src))
+
+    def binaural_render_process_batch(self, sources, blocks, voices, stride=None, want_out=True, want_mix=False):
+        """the binaural voices of several sources as one set of launches (include/frequensee.h
+        fs_binaural_render_process_batch): blocks [count][frame_size * 2]; voices one list per source, each a
+        BINAURAL_VOICE_DTYPE array or (key, delay, band_gain, gain, direction) tuples; stride = the row length handed to the
+        library (default: the longest list, at least 1) -> (out [count][frame_size * 2] (want_out), mix [frame_size * 2]
+        (want_mix), rows [count] BINAURAL_RENDER_ROW_DTYPE); what was not asked for is left out of the tuple"""
+        srcs, count, a, out, mix = self._callback_open(sources, blocks, getattr(self, "_br_frame", {}), want_out, want_mix)
+        if len(voices) != count:
+            raise ValueError("voices must have one list per source")
+        if stride is None:
+            stride = max([len(v) for v in voices] + [1])
+        stride = int(stride)
+        if any(len(v) > stride for v in voices):
+            raise ValueError("a voice list is longer than stride")
+        table = np.zeros((count, max(stride, 1)), dtype=self.BINAURAL_VOICE_DTYPE)
+        counts = np.zeros(count, np.int32)
+        for i, lst in enumerate(voices):
+            counts[i] = len(lst)
+            if isinstance(lst, np.ndarray) and lst.dtype == self.BINAURAL_VOICE_DTYPE:
+                table[i, :len(lst)] = lst
+                continue
+            for e, (key, delay, gains, gain, direction) in enumerate(lst):
+                g = np.asarray(gains, np.float32).reshape(-1)
+                table[i, e]["key"] = key
+                table[i, e]["delay"] = delay
+                table[i, e]["band_gain"][:g.shape[0]] = g
+                table[i, e]["gain"] = gain
+                table[i, e]["direction"] = direction
+        rows = np.zeros(count, dtype=self.BINAURAL_RENDER_ROW_DTYPE)
+        self.check(self.lib.fs_binaural_render_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data, table.ctypes.data,
+                                                             counts.ctypes.data, stride, out.ctypes.data if want_out else None,
+                                                             mix.ctypes.data if want_mix else None, rows.ctypes.data))
+        return self._callback_close(out, mix, rows)
+
     # ---- row f2: reverb plugin convolution ----
     def reverb_init(self, src, frame_size=1024):
         self.check(self.lib.fs_reverb_init(self.h, src, frame_size))
@@ -1147,16 +1231,33 @@ class FrequenSeeAudioReflectionPlugin:
         the earlier in the row is kept likewise.  mixed = (row, paths) of the same source from UpdateMixedPaths appends, after
         those, one voice per returned path off a reflector and round an edge — band_gain = gain, key = MixedKey(triangle, edge,
         end), colliding keys likewise; with it a diffraction path's triangle must stay below 2^28, which is checked."""
+        entries = self._path_entries(row, paths, diffraction, second, diffraction2, mixed)
+        v = np.zeros(len(entries), dtype=Context.REFLECTION_VOICE_DTYPE)
+        latency = ((self.Taps - 1) // 2) / float(self.ctx.cfg.sample_rate)
+        r = None if right is None else np.asarray(right, np.float64).reshape(3)
+        for o, (key, p, band_gain) in zip(v, entries):
+            o["key"] = key
+            o["delay"] = max(float(p["delay"]) - latency, 0.0)
+            o["band_gain"] = band_gain
+            left_right = np.ones(2, np.float64)
+            if r is not None:
+                t = (float(np.dot(np.asarray(p["direction"], np.float64), r)) + 1.0) * np.pi / 4.0
+                left_right = np.array([np.cos(t), np.sin(t)])
+            if reference_length is not None:
+                left_right = left_right * min(1.0, float(reference_length) / float(p["length"]))
+            o["channel_gain"] = left_right
+        return v
+
+    def _path_entries(self, row, paths, diffraction=None, second=None, diffraction2=None, mixed=None):
+        """what Voices() keeps of a source's path records, in its order, as (key, path record, band gains): the keys, their range
+        checks and the dropping of colliding keys as Voices() documents them"""
         n = int(row["returned"])
         m = 0 if diffraction is None else int(diffraction[0]["returned"])
         k = 0 if second is None else int(second[0]["returned"])
         k2 = 0 if diffraction2 is None else int(diffraction2[0]["returned"])
         k3 = 0 if mixed is None else int(mixed[0]["returned"])
         tagged = diffraction is not None or second is not None or diffraction2 is not None or mixed is not None
-        v = np.zeros(n + m + k + k2 + k3, dtype=Context.REFLECTION_VOICE_DTYPE)
-        latency = ((self.Taps - 1) // 2) / float(self.ctx.cfg.sample_rate)
-        r = None if right is None else np.asarray(right, np.float64).reshape(3)
-        seen, kept = set(), 0
+        seen, kept = set(), []
         for i in range(n + m + k + k2 + k3):
             p = paths[i] if i < n else (diffraction[1][i - n] if i < n + m else (second[1][i - n - m] if i < n + m + k else (
                 diffraction2[1][i - n - m - k] if i < n + m + k + k2 else mixed[1][i - n - m - k - k2])))
@@ -1172,19 +1273,8 @@ class FrequenSeeAudioReflectionPlugin:
                 if key in seen:
                     continue
                 seen.add(key)
-            o = v[kept]
-            kept += 1
-            o["key"] = key
-            o["delay"] = max(float(p["delay"]) - latency, 0.0)
-            o["band_gain"] = p["gain"] if n <= i < n + m or i >= n + m + k else p["reflectance"]
-            left_right = np.ones(2, np.float64)
-            if r is not None:
-                t = (float(np.dot(np.asarray(p["direction"], np.float64), r)) + 1.0) * np.pi / 4.0
-                left_right = np.array([np.cos(t), np.sin(t)])
-            if reference_length is not None:
-                left_right = left_right * min(1.0, float(reference_length) / float(p["length"]))
-            o["channel_gain"] = left_right
-        return v[:kept]
+            kept.append((key, p, p["gain"] if n <= i < n + m or i >= n + m + k else p["reflectance"]))
+        return kept
 
     def ProcessAudio(self, components, buffers, rows, paths, right=None, reference_length=None, want_out=True, want_mix=False,
                      diffraction=None, second=None, diffraction2=None, mixed=None):
@@ -1199,6 +1289,74 @@ class FrequenSeeAudioReflectionPlugin:
                               None if mixed is None else (mixed[0][i], mixed[1][i])) for i in range(len(components))]
         return self.ctx.reflection_render_process_batch([c._src for c in components], buffers, voices,
                                                         want_out=want_out, want_mix=want_mix)
+
+
+class FrequenSeeAudioBinauralPlugin(FrequenSeeAudioReflectionPlugin):
+    """Not in the reference: the reflection plugin with every voice rendered from its arrival direction through a head-related
+    impulse response set (fs_binaural_render_process_batch) instead of a pan: interaural delay and head shadow come out of the
+    set.  The direct sound becomes a voice of the same call.  The listener's orientation (forward, right) is the host's, and so
+    is any measured HRIR set (SetHrtf); without one SetHrtf() installs the library's spherical-head model."""
+
+    DirectKey = _capi.BINAURAL_DIRECT_KEY   # a first-order key (a triangle index) no scene of fewer than 2^29 - 1 triangles uses
+
+    def SetHrtf(self, dirs=None, hrir=None, directions=1024, taps=128):
+        """the context's HRIR set: dirs [n][3] (head frame: x forward, y right, z up) and hrir [n][2][H], or the spherical-head
+        model of `directions` and `taps`.  Before OnInitSource; not concurrent with ProcessAudio"""
+        if dirs is None:
+            dirs, hrir = Context.hrtf_spherical_head(self.ctx.cfg.sample_rate, directions, taps)
+        self.ctx.hrtf_set(dirs, hrir)
+
+    def OnInitSource(self, component: FrequenSeeAudioComponent):
+        self.ctx.binaural_render_init(component._src, self.FrameSize, self.Taps, self.VoiceCount, self.MaxDelaySeconds)
+
+    def OnReleaseSource(self, component: FrequenSeeAudioComponent):
+        self.ctx.binaural_render_release(component._src)
+
+    def Voices(self, row, paths, forward, right, reference_length=None, direct=None, diffraction=None, second=None, diffraction2=None,
+               mixed=None):
+        """one source's entries: keys, delays (less the band filter's latency of (Taps - 1) / 2 samples, not below 0) and band
+        gains exactly as FrequenSeeAudioReflectionPlugin.Voices builds them, from the same arguments; gain = min(1,
+        reference_length / length) with reference_length (cm), else 1; direction = the path's arrival direction d in the head
+        frame, (d . forward, d . right, d . up) with up = (f.y r.z - f.z r.y, f.z r.x - f.x r.z, f.x r.y - f.y r.x) — for forward
+        = +x and right = +y that is up = +z.  direct = (the source's row of UpdateDirectPaths, the vector from the listener to the
+        source in world space, any length but zero) puts the direct sound in front as one more voice: key = DirectKey (0x1FFFFFFF:
+        a triangle index no scene of fewer than 2^29 - 1 triangles has, which is checked against the first-order keys), band_gain =
+        transmission, length = distance."""
+        f = np.asarray(forward, np.float64).reshape(3)
+        r = np.asarray(right, np.float64).reshape(3)
+        up = np.array([f[1] * r[2] - f[2] * r[1], f[2] * r[0] - f[0] * r[2], f[0] * r[1] - f[1] * r[0]])
+        latency = ((self.Taps - 1) // 2) / float(self.ctx.cfg.sample_rate)
+        entries = []   # (key, delay, band gains, length, world direction)
+        if direct is not None:
+            d_row, to_source = direct
+            entries.append((self.DirectKey, d_row["delay"], d_row["transmission"], d_row["distance"], to_source))
+        for key, p, band_gain in self._path_entries(row, paths, diffraction, second, diffraction2, mixed):
+            if direct is not None and key == self.DirectKey:
+                raise ValueError("Voices: triangle index 2^29 - 1: its key is the direct sound's")
+            entries.append((key, p["delay"], band_gain, p["length"], p["direction"]))
+        v = np.zeros(len(entries), dtype=Context.BINAURAL_VOICE_DTYPE)
+        for o, (key, delay, band_gain, length, d) in zip(v, entries):
+            d = np.asarray(d, np.float64).reshape(3)
+            o["key"] = key
+            o["delay"] = max(float(delay) - latency, 0.0)
+            o["band_gain"] = band_gain
+            o["gain"] = 1.0 if reference_length is None else min(1.0, float(reference_length) / float(length))
+            o["direction"] = [np.dot(d, f), np.dot(d, r), np.dot(d, up)]
+        return v
+
+    def ProcessAudio(self, components, buffers, rows, paths, forward, right, reference_length=None, want_out=True, want_mix=False,
+                     direct=None, diffraction=None, second=None, diffraction2=None, mixed=None):
+        """buffers[i] is components[i]'s block, rows[i] / paths[i] its results of UpdateReflectionPaths; direct = (the rows of
+        UpdateDirectPaths, the listener's location) or None; the other path kinds as FrequenSeeAudioReflectionPlugin.ProcessAudio
+        takes them.  Returns what Context.binaural_render_process_batch does."""
+        def pick(pair, i):
+            return None if pair is None else (pair[0][i], pair[1][i])
+        voices = []
+        for i, c in enumerate(components):
+            d = None if direct is None else (direct[0][i], np.asarray(c.GetComponentLocation(), np.float64) - np.asarray(direct[1], np.float64))
+            voices.append(self.Voices(rows[i], paths[i], forward, right, reference_length, d, pick(diffraction, i), pick(second, i),
+                                      pick(diffraction2, i), pick(mixed, i)))
+        return self.ctx.binaural_render_process_batch([c._src for c in components], buffers, voices, want_out=want_out, want_mix=want_mix)
 
 
 class MaterialAcousticProcessor:

@@ -13,28 +13,24 @@ void rr_free_slots(Source* s) {
     for (int j = 0; j < FS_MAX_REFLECTION_VOICES; ++j) { s->rr_held[j] = false; s->rr_key[j] = 0; }
 }
 
-// what one row's matching decides: the slots' ops, the table afterwards, the counts
-struct RrMatch {
-    int8_t op[FS_MAX_REFLECTION_VOICES];
-    bool held[FS_MAX_REFLECTION_VOICES];
-    uint32_t key[FS_MAX_REFLECTION_VOICES];
-    fs_reflection_render_row row;
-};
+}  // namespace
+
+namespace fsi {
 
 // Rule 1 of the header: held slots continue or end by their key; the other entries start, in list order, on the lowest slot that
 // was free when the callback began; what finds none is dropped.  (n entries with distinct keys: checked by the caller.)
-RrMatch rr_match(const Source* s, const fs_reflection_voice* v, int n) {
-    RrMatch m{};
-    const int V = s->rr_voices;
+VoiceMatch voice_match(const bool* held, const uint32_t* key, int V, const void* voices, size_t voice_bytes, int n) {
+    VoiceMatch m{};
+    auto key_of = [&](int e) { uint32_t k; std::memcpy(&k, (const char*)voices + (size_t)e * voice_bytes, sizeof(k)); return k; };
     bool taken[FS_MAX_REFLECTION_VOICES] = {};   // entries a held slot continues with
     for (int j = 0; j < FS_MAX_REFLECTION_VOICES; ++j) m.op[j] = (int8_t)kReflectIdle;
     for (int j = 0; j < V; ++j) {
-        if (!s->rr_held[j]) continue;
+        if (!held[j]) continue;
         int e = 0;
-        while (e < n && v[e].key != s->rr_key[j]) ++e;
+        while (e < n && key_of(e) != key[j]) ++e;
         if (e < n) {
             m.op[j] = (int8_t)(kReflectContinue + e);
-            m.held[j] = true; m.key[j] = s->rr_key[j];
+            m.held[j] = true; m.key[j] = key[j];
             taken[e] = true;
         } else {
             m.op[j] = (int8_t)kReflectEnd;
@@ -45,17 +41,17 @@ RrMatch rr_match(const Source* s, const fs_reflection_voice* v, int n) {
     int next = 0;   // the lowest slot not looked at yet
     for (int e = 0; e < n; ++e) {
         if (taken[e]) continue;
-        while (next < V && s->rr_held[next]) ++next;   // (an ending slot is held during this callback)
+        while (next < V && held[next]) ++next;   // (an ending slot is held during this callback)
         if (next == V) { m.row.dropped++; continue; }
         m.op[next] = (int8_t)(kReflectStart + e);
-        m.held[next] = true; m.key[next] = v[e].key;
+        m.held[next] = true; m.key[next] = key_of(e);
         m.row.started++; m.row.sounding++;
         ++next;
     }
     return m;
 }
 
-}  // namespace
+}  // namespace fsi
 
 extern "C" {
 
@@ -126,10 +122,10 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
     { const int rc = ctx->rr_stage.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
     char* hs = ctx->rr_stage.h; char* ds = ctx->rr_stage.d;
     ReflectRenderItem* items = (ReflectRenderItem*)(hs + l.up[kItems]);
-    std::vector<RrMatch> matches((size_t)count);
+    std::vector<VoiceMatch> matches((size_t)count);
     for (int32_t i = 0; i < count; ++i) {
         const Source* s = srcs[(size_t)i];
-        RrMatch& m = matches[(size_t)i] = rr_match(s, voices + (size_t)i * (size_t)stride, voice_counts[i]);
+        VoiceMatch& m = matches[(size_t)i] = voice_match(s->rr_held, s->rr_key, s->rr_voices, voices + (size_t)i * (size_t)stride, sizeof(fs_reflection_voice), voice_counts[i]);
         ReflectRenderItem& it = items[i];
         std::memset(&it, 0, sizeof(it));
         it.state = (ReflectRenderState*)s->rr.d;

@@ -184,6 +184,12 @@ struct Source {
     int rr_voices = 0;
     bool rr_held[FS_MAX_REFLECTION_VOICES] = {};
     uint32_t rr_key[FS_MAX_REFLECTION_VOICES] = {};
+    // binaural voices (header: BinauralRenderState, kBinauralRenderHeader bytes): the reflection fields' counterparts.  br.taps = T;
+    // the rings were sized for T + H - 1 taps of the set in force at fs_binaural_render_init
+    RenderSetup br;
+    int br_voices = 0;
+    bool br_held[FS_MAX_REFLECTION_VOICES] = {};
+    uint32_t br_key[FS_MAX_REFLECTION_VOICES] = {};
     float occlusion = 1.0f;            // OcclusionAttenuation FSAC.h:130 (1.f until the first UpdateSound)
 };
 
@@ -286,7 +292,7 @@ struct CallbackStage {
 struct CallbackLayout {
     size_t up[3] = {}, in = 0, up_bytes = 0;
     size_t h_out = 0, h_mix = 0, host_bytes = 0;
-    size_t scratch[2] = {}, d_out = 0, d_mix = 0, dev_bytes = 0;
+    size_t scratch[3] = {}, d_out = 0, d_mix = 0, dev_bytes = 0;
     size_t rows = 0, row = 0;   // the bytes of in and of out, and of mix
 };
 
@@ -358,7 +364,12 @@ struct fs_context {
     // dr_stage (fs_direct_render_process_batch): up, items [count]; scratch, the plans [count]
     // rr_stage (fs_reflection_render_process_batch): up, items [count] | voices [count][stride]; scratch, the counters [count] |
     //   the plans [count][FS_MAX_REFLECTION_VOICES]
-    CallbackStage rev_stage, dr_stage, rr_stage;
+    // br_stage (fs_binaural_render_process_batch): up, items [count] | voices [count][stride] | the sounding slots' list; scratch,
+    //   the counters [count] | the plans [count][FS_MAX_REFLECTION_VOICES] | the folded tables [sum of the rows' V][2][Tc]
+    CallbackStage rev_stage, dr_stage, rr_stage, br_stage;
+    // the HRIR set in force (fs_hrtf_set; the audio thread's): one device block, dirs [n][3] | hrir [n][2][H]; n == 0: none
+    float* d_hrtf = nullptr;
+    int hrtf_dirs = 0, hrtf_taps = 0;
     // the partitioned engine's twiddles, W[k] = exp(-2 pi i k / N), k < N / 2, per n = log2 N <= 12: built by the first
     // fs_reverb_init that needs the size, freed with the context
     float2* d_rev_tw[13] = {};
@@ -597,6 +608,17 @@ Source* render_row(fs_context* ctx, fs_source h, RenderSetup Source::*which, con
 // a target's or a voice's (`whose`) delay and band gains against the source's set-up
 int render_aim_check(fs_context* ctx, const char* whose, float delay, const float* band_gain, const RenderSetup& r);
 int render_no_duplicates(fs_context* ctx, const std::vector<Source*>& srcs);   // "a source appears twice in the batch"
+// ---- fs_capi_reflect_render.cpp: what the binaural renderer shares with the reflection one ----------------------------
+// what one row's matching decides: the slots' ops (kReflectIdle ...), the slot table afterwards, the counts
+struct VoiceMatch {
+    int8_t op[FS_MAX_REFLECTION_VOICES];
+    bool held[FS_MAX_REFLECTION_VOICES];
+    uint32_t key[FS_MAX_REFLECTION_VOICES];
+    fs_reflection_render_row row;
+};
+// rule 1 of the reflection renderer on a source's slot table (held, key) [V]: `voices` = the row's n entries, voice_bytes apart,
+// each beginning with its key
+VoiceMatch voice_match(const bool* held, const uint32_t* key, int V, const void* voices, size_t voice_bytes, int n);
 // ---- fs_capi_context.cpp ------------------------------------------------------------------------------------------
 Source* get_source(fs_context* ctx, fs_source h);
 hipError_t wait_energy_readers(fs_context* ctx, Source* s);            // before the compute stream writes the current energy buffer

@@ -1,7 +1,8 @@
-// fs_dev_render.hpp — what the two render kernels of the audio thread (fs_direct_render.hip, fs_reflect_render.hip) share on the
-// device: one voice's block — a time-varying fractional delay and a linear-phase FIR whose taps ramp from sum_b g0_b k_b to
-// sum_b g1_b k_b — as pieces a kernel puts together: the delay of an output sample and its slew clamp, the tap table and the
-// tile's read window in LDS, the tap loop of one output sample, the output store with the ring append.  The rule is
+// fs_dev_render.hpp — what the three render kernels of the audio thread (fs_direct_render.hip, fs_reflect_render.hip,
+// fs_binaural_render.hip) share on the device: one voice's block — a time-varying fractional delay and a linear-phase FIR whose
+// taps ramp from sum_b g0_b k_b to sum_b g1_b k_b — as pieces a kernel puts together: the delay of an output sample and its slew
+// clamp, the tap table and the tile's read window in LDS, the tap loop of one output sample, the output store with the ring append.
+// The rule is
 // include/frequensee.h's, to the bit: every fp32 operation stands where the header puts it (the files are built with
 // -ffp-contract=off and the tests compare bits).  No piece holds a barrier or a return: each says which barrier its caller owes.
 // The LDS arrays travel as references to arrays, so that after inlining the tap loop still reads them with LDS instructions.
@@ -132,6 +133,12 @@ __device__ __forceinline__ void render_store(float* __restrict__ out_all, float*
                                              const float* __restrict__ in, int r, int ch, unsigned n0, int s, int frame, float y) {
     out_all[(size_t)r * 2 * (size_t)frame + 2 * (size_t)s + ch] = y;
     ring[(n0 + (unsigned)s) & mask] = in[2 * s + ch];
+}
+
+// {c0[t], dc[t]} of a voice whose taps an earlier launch left in global memory (fs_binaural_render.hip: the band FIR with an
+// HRIR folded in), `folded` [taps], into s_cd.  In render_build_taps' place, under the same barriers.
+__device__ __forceinline__ void render_load_taps(RenderTaps& s_cd, const float2* __restrict__ folded, int taps, int tid) {
+    for (int t = tid; t < taps; t += kRenderTile) s_cd[t] = folded[t];
 }
 
 }  // namespace

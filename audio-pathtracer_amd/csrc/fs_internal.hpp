@@ -708,6 +708,68 @@ struct ReflectRenderBatch {
 };
 // the plan pass, the render pass (which also appends the blocks to the rings), the mix (when b.mix)
 void launch_reflect_render(const ReflectRenderBatch& b, hipStream_t s);
+// fs_binaural_render.hip (the binaural-voice callback).  A source's state is one device block (Source::br.d): this header, then at
+// kBinauralRenderHeader bytes the two history rings [2][ring], shared by the source's slots; zeroed = every slot free, nothing heard.
+struct BinauralRenderSlot {
+    int32_t held;          // the device's record of the slot table; the matching itself runs on the host's copy (Source::br_held / br_key)
+    uint32_t key;
+    float d0;              // the delay the slot's last output sample used, in samples
+    float g0[FS_MAX_BANDS];   // ... its band gains
+    float w0;              // ... its gain
+    int32_t q0;            // ... its HRIR index
+    int32_t pad[3];
+};
+static_assert(sizeof(BinauralRenderSlot) == 64, "BinauralRenderSlot: sixteen words");
+struct BinauralRenderState {
+    unsigned n0;           // absolute index of the next block's first sample (wraps; the ring index is n & mask)
+    int32_t pad[15];
+    BinauralRenderSlot slot[FS_MAX_REFLECTION_VOICES];
+};
+constexpr size_t kBinauralRenderHeader = 2304;
+static_assert(sizeof(BinauralRenderState) == 2112 && sizeof(BinauralRenderState) <= kBinauralRenderHeader && kBinauralRenderHeader % 256 == 0,
+              "BinauralRenderState: the counter's line and the slots in front of the rings");
+// one descriptor per row of the call, in list order: the host's staging layout.  op: the reflection renderer's codes (kReflectIdle ...);
+// first = the index in the call's folded tables of the row's lowest sounding slot, the others follow in ascending slot number
+struct BinauralRenderItem {
+    BinauralRenderState* state;
+    float* ring;           // [2][mask + 1]
+    const float* table;    // the band kernels [bands][taps] the source was initialised with
+    unsigned mask;
+    int32_t slots;         // V
+    int8_t op[FS_MAX_REFLECTION_VOICES];
+    int32_t first;
+    int32_t pad;
+};
+static_assert(sizeof(BinauralRenderItem) == 72, "BinauralRenderItem: three pointers, two words, a byte per slot, two words: the host's staging layout");
+// what the plan pass fixes for a sounding slot: where this callback ramps from, the slew-limited change of the delay, the gains
+// it ramps between, the gain's start and change, the HRIR indices it fades between, its index in the folded tables
+struct BinauralRenderPlan {
+    float d0, e;
+    float g0[FS_MAX_BANDS], g1[FS_MAX_BANDS];
+    float w0, dw;
+    int32_t q0, q1;
+    int32_t index;
+    int32_t pad;
+};
+static_assert(sizeof(BinauralRenderPlan) == 96, "BinauralRenderPlan: twenty-four words");
+struct BinauralRenderBatch {
+    const BinauralRenderItem* items;    // [count]
+    const fs_binaural_voice* voices;    // [count][stride]
+    const uint16_t* sounding;           // [n_sounding]: row * FS_MAX_REFLECTION_VOICES + slot of every sounding slot, rows then slots ascending
+    BinauralRenderPlan* plans;          // [count][FS_MAX_REFLECTION_VOICES] scratch
+    unsigned* n0;                       // [count] scratch: every row's counter before this callback
+    float2* folded;                     // [n_sounding][2 ears][tc] scratch: {C0[u], dC[u]}
+    const float* dirs;                  // the set in force: [n_dirs][3] ...
+    const float* hrir;                  // ... [n_dirs][2][h_taps]
+    int n_dirs, h_taps;
+    int count, stride, frame, taps, tc, bands, n_sounding;
+    float fs;                           // the sample rate: an entry's d1 = delay * fs
+    const float* in;                    // [count][2 * frame] interleaved
+    float* out;                         // [count][2 * frame] interleaved
+    float* mix;                         // [2 * frame], or null
+};
+// the plan pass, the fold of the HRIRs into the band FIRs, the render pass (which also appends the blocks to the rings), the mix (when b.mix)
+void launch_binaural_render(const BinauralRenderBatch& b, hipStream_t s);
 void launch_add_energy(float* energy_row, int num_bins, float delay_s, float e, hipStream_t s);
 // dynamic LDS the traversal kernels of a frame need for a tree with `stack_rows` stack rows: the larger of the walk
 // kernel (stack + work-sharing area) and the connect kernels (stack + [bands][bins] histogram + work-sharing area)

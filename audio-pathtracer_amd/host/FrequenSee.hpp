@@ -87,6 +87,7 @@ private:
     friend class AudioRayTracingSubsystem;
     friend class FrequenSeeAudioOcclusionPlugin;
     friend class FrequenSeeAudioReflectionPlugin;
+    friend class FrequenSeeAudioBinauralPlugin;
     FVector Location_;
     AudioRayTracingSubsystem* SubSys_ = nullptr;
     fs_source Handle_ = -1;
@@ -316,6 +317,7 @@ private:
     friend class MaterialAcousticProcessor;
     friend class FrequenSeeAudioOcclusionPlugin;
     friend class FrequenSeeAudioReflectionPlugin;
+    friend class FrequenSeeAudioBinauralPlugin;
 };
 
 inline FrequenSeeAudioComponent::~FrequenSeeAudioComponent() { OnUnregister(); }
@@ -529,16 +531,30 @@ public:
                                             const fs_reflection2_path* SPaths = nullptr, const fs_diffraction2_row* TRow = nullptr,
                                             const fs_diffraction2_path* TPaths = nullptr, const fs_mixed_row* MRow = nullptr,
                                             const fs_mixed_path* MPaths = nullptr) const {
+        std::vector<fs_reflection_voice> V;
+        ForEachVoice(Row, Paths, DRow, DPaths, SRow, SPaths, TRow, TPaths, MRow, MPaths,
+                     [&](uint32_t Key, float Delay, const float* Gain, const float* Dir, float Length) {
+                         V.push_back(Voice(Key, Delay, Gain, Dir, Length, Right, ReferenceLength));
+                     });
+        return V;
+    }
+    // what Voices keeps of a source's path records, in its order: Fn(key, arrival time, band gains, arrival direction, length) per
+    // voice, with the keys, their range checks and the dropping of colliding keys as described above
+    template <class F>
+    void ForEachVoice(const fs_reflection_row& Row, const fs_reflection_path* Paths, const fs_diffraction_row* DRow, const fs_diffraction_path* DPaths,
+                      const fs_reflection2_row* SRow, const fs_reflection2_path* SPaths, const fs_diffraction2_row* TRow,
+                      const fs_diffraction2_path* TPaths, const fs_mixed_row* MRow, const fs_mixed_path* MPaths, F&& Fn) const {
         const size_t NR = (size_t)Row.returned, ND = DRow && DPaths ? (size_t)DRow->returned : 0, NS = SRow && SPaths ? (size_t)SRow->returned : 0;
         const size_t NT = TRow && TPaths ? (size_t)TRow->returned : 0, NM = MRow && MPaths ? (size_t)MRow->returned : 0;
-        std::vector<fs_reflection_voice> V;
-        V.reserve(NR + ND + NS + NT + NM);
+        std::vector<uint32_t> Keys;   // of the voices kept so far
+        Keys.reserve(NR + ND + NS + NT + NM);
         for (size_t i = 0; i < NR + ND + NS + NT + NM; ++i) {
             if (i >= NR + ND + NS + NT) {   // a mixed path: every field it needs under one name
                 const fs_mixed_path& M = MPaths[i - NR - ND - NS - NT];
                 const uint32_t Key = MixedKey(M.triangle, M.edge, M.end);
-                if (std::any_of(V.begin() + (std::ptrdiff_t)(NR + ND), V.end(), [&](const fs_reflection_voice& X) { return X.key == Key; })) continue;
-                V.push_back(Voice(Key, M.delay, M.gain, M.direction, M.length, Right, ReferenceLength));
+                if (std::find(Keys.begin() + (std::ptrdiff_t)(NR + ND), Keys.end(), Key) != Keys.end()) continue;
+                Keys.push_back(Key);
+                Fn(Key, M.delay, M.gain, M.direction, M.length);
                 continue;
             }
             const bool Refl = i < NR, Second = i >= NR + ND && i < NR + ND + NS, Thick = i >= NR + ND + NS;
@@ -555,10 +571,10 @@ public:
             const float Length = Refl ? Paths[i].length : (Second ? S->length : (Thick ? T->length : DPaths[i - NR].length));
             const uint32_t Key = Refl ? Tri : (Second ? SecondOrderKey(S->triangle[0], S->triangle[1])
                                                       : (Thick ? Diffraction2Key(T->triangle, T->edge) : (0x80000000u | (Tri * 4u + DPaths[i - NR].edge))));
-            if ((Second || Thick) && std::any_of(V.begin() + (std::ptrdiff_t)(NR + ND), V.end(), [&](const fs_reflection_voice& X) { return X.key == Key; })) continue;
-            V.push_back(Voice(Key, Delay, Gain, Dir, Length, Right, ReferenceLength));
+            if ((Second || Thick) && std::find(Keys.begin() + (std::ptrdiff_t)(NR + ND), Keys.end(), Key) != Keys.end()) continue;
+            Keys.push_back(Key);
+            Fn(Key, Delay, Gain, Dir, Length);
         }
-        return V;
     }
     // one voice: the key, the target delay, the band gains, and the pan and distance law of Voices
     fs_reflection_voice Voice(uint32_t Key, float Delay, const float* Gain, const float* Dir, float Length, const FVector* Right,
@@ -631,6 +647,103 @@ public:
     }
 
     int VoiceCount = FS_MAX_REFLECTION_VOICES;
+};
+
+// Not in the reference: the reflection plugin with every voice rendered from its arrival direction through a head-related impulse
+// response set — fs_binaural_render_process_batch, one call for all sources — instead of a pan: interaural delay and head shadow
+// come out of the set.  The direct sound becomes a voice of the same call.  The listener's orientation (Forward, Right) is the
+// host's, and so is any measured HRIR set (SetHrtf); without one SetHrtf() installs the library's spherical-head model.
+class FrequenSeeAudioBinauralPlugin : public FrequenSeeAudioReflectionPlugin {
+public:
+    explicit FrequenSeeAudioBinauralPlugin(AudioRayTracingSubsystem& SubSys) : FrequenSeeAudioReflectionPlugin(SubSys) {}
+    // the context's set: Dirs [n][3] (head frame: x forward, y right, z up), Hrir [n][2][H].  Before OnInitSource; not concurrent
+    // with ProcessAudio
+    void SetHrtf(const std::vector<float>& Dirs, const std::vector<float>& Hrir, int HrirTaps) {
+        fs_hrtf_desc D{};
+        D.struct_size = sizeof(D);
+        D.directions = (int32_t)(Dirs.size() / 3);
+        D.taps = HrirTaps;
+        D.sample_rate = SampleRate;
+        D.dirs = Dirs.data();
+        D.hrir = Hrir.data();
+        if (HrirTaps < 1 || Dirs.size() % 3 != 0 || Hrir.size() != Dirs.size() / 3 * 2 * (size_t)HrirTaps)
+            throw std::runtime_error("FrequenSee: an HRIR set is dirs [n][3] and hrir [n][2][taps]");
+        SubSys_->Check(fs_hrtf_set(SubSys_->Ctx_, &D));
+    }
+    // ... or the spherical-head model (a model: interaural delay and level difference, no pinna)
+    void SetHrtf(int Directions = 1024, int HrirTaps = 128) {
+        std::vector<float> Dirs((size_t)std::max(Directions, 0) * 3), Hrir((size_t)std::max(Directions, 0) * 2 * (size_t)std::max(HrirTaps, 0));
+        if (fs_hrtf_spherical_head(SampleRate, FS_HRTF_DEFAULT_RADIUS_CM, FS_HRTF_DEFAULT_SOUND_SPEED_CM_S, Directions, HrirTaps, Dirs.data(),
+                                   Hrir.data()) != FS_OK)
+            throw std::runtime_error("FrequenSee: fs_hrtf_spherical_head refused the directions or the taps");
+        SetHrtf(Dirs, Hrir, HrirTaps);
+    }
+    void OnInitSource(const FrequenSeeAudioComponent& C) {
+        SubSys_->Check(fs_binaural_render_init(SubSys_->Ctx_, C.Handle_, FrameSize, Taps, VoiceCount, MaxDelaySeconds));
+    }
+    void OnReleaseSource(const FrequenSeeAudioComponent& C) { SubSys_->Check(fs_binaural_render_release(SubSys_->Ctx_, C.Handle_)); }
+    // One source's entries: keys, delays and band gains exactly as FrequenSeeAudioReflectionPlugin::Voices builds them, from the same
+    // arguments; gain = min(1, ReferenceLength / length) with ReferenceLength > 0 (cm), else 1; direction = the path's arrival
+    // direction d in the head frame, (d . Forward, d . Right, d . Up) with Up = (F.Y R.Z - F.Z R.Y, F.Z R.X - F.X R.Z, F.X R.Y - F.Y R.X)
+    // — for Forward = +x and Right = +y that is +z.  Direct (the source's row of fs_update_direct_paths) with ToSource (the vector from
+    // the listener to the source, world space, any length but zero) puts the direct sound in front as one more voice: key =
+    // FS_BINAURAL_DIRECT_KEY (a triangle index no scene of fewer than 2^29 - 1 triangles has: a first-order path with it is refused),
+    // band_gain = transmission, length = distance
+    std::vector<fs_binaural_voice> Voices(const fs_reflection_row& Row, const fs_reflection_path* Paths, const FVector& Forward, const FVector& Right,
+                                          float ReferenceLength = 0.0f, const fs_direct_path* Direct = nullptr, const FVector* ToSource = nullptr,
+                                          const fs_diffraction_row* DRow = nullptr, const fs_diffraction_path* DPaths = nullptr,
+                                          const fs_reflection2_row* SRow = nullptr, const fs_reflection2_path* SPaths = nullptr,
+                                          const fs_diffraction2_row* TRow = nullptr, const fs_diffraction2_path* TPaths = nullptr,
+                                          const fs_mixed_row* MRow = nullptr, const fs_mixed_path* MPaths = nullptr) const {
+        const double F[3] = {Forward.X, Forward.Y, Forward.Z}, R[3] = {Right.X, Right.Y, Right.Z};
+        const double U[3] = {F[1] * R[2] - F[2] * R[1], F[2] * R[0] - F[0] * R[2], F[0] * R[1] - F[1] * R[0]};
+        std::vector<fs_binaural_voice> V;
+        auto Add = [&](uint32_t Key, float Delay, const float* Gain, const double* Dir, float Length) {
+            fs_binaural_voice O{};
+            O.key = Key;
+            O.delay = TargetDelay(Delay);
+            for (int b = 0; b < FS_MAX_BANDS; ++b) O.band_gain[b] = Gain[b];
+            O.gain = ReferenceLength > 0.0f ? (float)std::min(1.0, (double)ReferenceLength / (double)Length) : 1.0f;
+            O.direction[0] = (float)(Dir[0] * F[0] + Dir[1] * F[1] + Dir[2] * F[2]);
+            O.direction[1] = (float)(Dir[0] * R[0] + Dir[1] * R[1] + Dir[2] * R[2]);
+            O.direction[2] = (float)(Dir[0] * U[0] + Dir[1] * U[1] + Dir[2] * U[2]);
+            V.push_back(O);
+        };
+        const bool WithDirect = Direct && ToSource;
+        if (WithDirect) {
+            const double D[3] = {ToSource->X, ToSource->Y, ToSource->Z};
+            Add(FS_BINAURAL_DIRECT_KEY, Direct->delay, Direct->transmission, D, Direct->distance);
+        }
+        ForEachVoice(Row, Paths, DRow, DPaths, SRow, SPaths, TRow, TPaths, MRow, MPaths,
+                     [&](uint32_t Key, float Delay, const float* Gain, const float* Dir, float Length) {
+                         if (WithDirect && Key == FS_BINAURAL_DIRECT_KEY)
+                             throw std::runtime_error("FrequenSee: triangle index 2^29 - 1: its key is the direct sound's");
+                         const double D[3] = {Dir[0], Dir[1], Dir[2]};
+                         Add(Key, Delay, Gain, D, Length);
+                     });
+        return V;
+    }
+    // In [count][FrameSize * 2] interleaved stereo (a mono source in both channels), row i for Sources[i] and Voices[i] (what Voices
+    // returned for it: FS_MAX_REFLECTION_VOICES entries at most); Out [count][FrameSize * 2] or nullptr, Mix [FrameSize * 2] or
+    // nullptr, Counts [count] or nullptr
+    void ProcessAudio(const std::vector<FrequenSeeAudioComponent*>& Sources, const float* In, const std::vector<std::vector<fs_binaural_voice>>& Voices,
+                      float* Out, float* Mix = nullptr, fs_binaural_render_row* Counts = nullptr) {
+        if (Voices.size() != Sources.size()) throw std::runtime_error("FrequenSee: one voice list per source");
+        size_t Stride = 1;
+        for (const auto& V : Voices) Stride = std::max(Stride, V.size());
+        if (Stride > FS_MAX_REFLECTION_VOICES)
+            throw std::runtime_error("FrequenSee: " + std::to_string(Stride) + " voices for one source, more than FS_MAX_REFLECTION_VOICES");
+        std::vector<fs_source> H;
+        std::vector<fs_binaural_voice> All(Sources.size() * Stride);
+        std::vector<int32_t> N;
+        for (size_t i = 0; i < Sources.size(); ++i) {
+            H.push_back(Sources[i]->Handle_);
+            std::copy(Voices[i].begin(), Voices[i].end(), All.begin() + (std::ptrdiff_t)(i * Stride));
+            N.push_back((int32_t)Voices[i].size());
+        }
+        SubSys_->Check(fs_binaural_render_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, All.data(), N.data(), (int32_t)Stride, Out,
+                                                        Mix, Counts));
+    }
 };
 
 }  // namespace frequensee

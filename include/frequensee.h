@@ -62,6 +62,8 @@
  *             fs_mixed_params_default fs_update_mixed_paths
  *             fs_direct_band_kernels fs_direct_render_init fs_direct_render_release fs_direct_render_process_batch
  *             fs_reflection_render_init fs_reflection_render_release fs_reflection_render_process_batch
+ *             fs_hrtf_set fs_hrtf_info fs_hrtf_spherical_head
+ *             fs_binaural_render_init fs_binaural_render_release fs_binaural_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
  * Environment variables (FS_*) are tuning and diagnostic knobs only; all of them are read ONCE — at fs_context_create, at a
  * scene commit (builder knobs) or at the first launch of a kernel family — never per frame.
@@ -1441,6 +1443,111 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
                                        const fs_reflection_voice* voices /* [count][stride] */, const int32_t* voice_counts /* [count] */,
                                        int32_t stride, float* out /* [count][F * 2] or NULL */, float* mix /* [F * 2] or NULL */,
                                        fs_reflection_render_row* rows /* [count] or NULL */);
+
+/* ---- binaural voices on the audio thread (EXTENDED): every discrete path rendered from its arrival direction -------------------
+ *      Not in the reference.  The reflection renderer above with the per-channel gain pair replaced by ONE scalar gain and a
+ *      direction in the head frame: each ear convolves the voice with the head-related impulse response (HRIR) of the nearest
+ *      direction of a host-supplied set, folded into the voice's band FIR.  Convolution is linear in the taps, so the fold is the
+ *      same tap loop on a longer table, and a change of the nearest direction is a block-long crossfade between two tables —
+ *      the ramp the loop already applies.  Interaural delay, head shadow and whatever else the set encodes come out of the set;
+ *      the library interpolates nothing between the set's directions.
+ *   Head frame.  x forward, y right, z up (the reference's Unreal convention); ear 0 is the left ear, ear 1 the right.
+ *   fs_hrtf_set.  n = directions, H = taps, dirs [n][3], hrir [n][2][H] (direction, ear, tap).  Accepted when struct_size is this
+ *   library's, 1 <= n <= FS_MAX_HRTF_DIRECTIONS, 1 <= H <= FS_MAX_HRTF_TAPS, sample_rate == the context's, dirs and hrir are not
+ *   NULL, every direction is finite with |x^2 + y^2 + z^2 - 1| <= 1e-3 (in double) and every tap is finite: otherwise
+ *   FS_ERR_INVALID_ARGUMENT, and a refused call changes nothing.  desc == NULL clears the set.  The audio thread's contract: not
+ *   concurrent with a callback.  The call waits for the reverb stream, uploads the set in one copy and frees every held binaural
+ *   slot of every source of the context; the histories are kept.  So the next callback's voices START — they fade in from
+ *   silence over one block — and nothing ever ramps from an index of the old set.  (A HIP failure after the upload is no refusal:
+ *   it is reported with the new set in force and every source's slots freed on the host's copy, so every voice still starts.)  A source initialised under a set of another H
+ *   stays initialised; fs_binaural_render_process_batch refuses it while D + Tc + 1 + F exceeds its ring or Tc exceeds
+ *   FS_DIRECT_RENDER_MAX_TAPS (below), and fs_binaural_render_init sizes it anew.
+ *   fs_hrtf_info: *directions = n and *taps = H of the set in force, 0 and 0 without one (either pointer may be NULL).
+ *   fs_hrtf_spherical_head.  A set for hosts that have none; host only, no context, no device.  A MODEL: a rigid sphere's
+ *   interaural delay and level difference, NO pinna — no elevation cue and no front/back cue beyond what the delay gives.
+ *   a = radius_cm, c = sound_speed_cm_s (real physics, cm/s: NOT the trace's dist_divisor time axis), fs = sample_rate; suggested
+ *   a = FS_HRTF_DEFAULT_RADIUS_CM, c = FS_HRTF_DEFAULT_SOUND_SPEED_CM_S.  Computed in double, rounded to float once.
+ *     Directions, k = 0 .. n-1:  z = 1 - (2k + 1) / n;  rho = sqrt(1 - z^2);  phi = k pi (3 - sqrt 5);
+ *       p_k = (rho cos phi, rho sin phi, z)    (a Fibonacci spiral from the zenith down).
+ *     Per ear, axis e = (0, -1, 0) left, (0, +1, 0) right:  theta = acos(clamp(p . e, -1, 1)).
+ *       Onset (Woodworth's delay, offset so that it is never negative):
+ *         tau = (a / c) (1 - cos theta) for theta <= pi / 2, else tau = (a / c) (1 + theta - pi / 2).
+ *       Shadow (Brown and Duda's one-pole, one-zero filter):  alpha = (1 + alpha_min / 2) + (1 - alpha_min / 2) cos(theta pi /
+ *         theta_min), alpha_min = 0.1, theta_min = 5 pi / 6;  kappa = fs a / c;  g = the impulse response of the bilinear
+ *         transform ((1 + alpha kappa) + (1 - alpha kappa) z^-1) / ((1 + kappa) + (1 - kappa) z^-1):
+ *         g[0] = b0, g[1] = b1 - a1 g[0], g[m] = -a1 g[m-1], with b0 = (1 + alpha kappa) / (1 + kappa), b1 = (1 - alpha kappa) /
+ *         (1 + kappa), a1 = (1 - kappa) / (1 + kappa).
+ *       Taps:  i = floor(tau fs), f = tau fs - i;  h[k] = (1 - f) g[k - i] + f g[k - i - 1], g = 0 at negative indices.
+ *     FS_ERR_INVALID_ARGUMENT: dirs or hrir NULL, sample_rate < 1, a or c not finite or not > 0, n outside
+ *     1 .. FS_MAX_HRTF_DIRECTIONS, H outside 1 .. FS_MAX_HRTF_TAPS, or H < ceil((a / c) (1 + pi / 2) fs) + 2 (the latest onset
+ *     plus the filter's first two taps would not fit).
+ *   fs_binaural_render_init.  Needs a set in force.  F, T, D and V under fs_reflection_render_init's limits with Tc = T + H - 1
+ *   wherever the ring is sized: 16 <= F <= 16384; T odd, 1 .. FS_DIRECT_RENDER_MAX_TAPS; Tc <= FS_DIRECT_RENDER_MAX_TAPS; the ring
+ *   is the smallest power of two >= D + Tc + 1 + F floats and D + Tc + 1 + F <= 2^20; edges in force inside (0, fs / 2);
+ *   1 <= V <= FS_MAX_REFLECTION_VOICES: otherwise FS_ERR_INVALID_ARGUMENT.  The state is the binaural renderer's own — a source may
+ *   hold direct, reflection and binaural state side by side: a zeroed history ring per channel, n0, and V slots {held, key, d0,
+ *   g0[bands], w0, q0}, all free; the host-side copy of (held, key) as above.  fs_binaural_render_release: history := 0, every slot
+ *   free (a source without fs_binaural_render_init: nothing to do, FS_OK).
+ *   One callback, per row.  fp32 throughout, every operation rounded on its own, in the order written.
+ *     1. Match.  Rule 1 of the reflection renderer, verbatim, with w1 = gain (one scalar) and w0 := 0 at a start.
+ *     2. HRIR index.  For an entry with direction d: q1 = the LOWEST index j that maximises (d.x p_j.x + d.y p_j.y) + d.z p_j.z
+ *        over the set's directions (d need not be unit).  A slot holds q0, the index its last callback ended with.  A starting
+ *        slot takes q0 := q1; an ending slot q1 := q0.
+ *     3. Taps.  fA[t], A = 0, 1, t = 0 .. T-1: the direct renderer's cA[t] from g0 and g1.  Per ear, u = 0 .. Tc-1:
+ *        CA[u] = the sum from acc = 0 over k ascending from max(0, u - T + 1) to min(H - 1, u) of acc = acc + h[qA][ear][k] *
+ *        fA[u - k];  dC[u] = C1[u] - C0[u].
+ *     4. Voice output.  "Output s" of the direct renderer with Tc taps and the coefficient C0[u] + a * dC[u]: the same delay,
+ *        slew limit (e = clamp(d1 - d0, -F/2, +F/2)) and four accumulators.  Ear ch reads input channel ch of the source's shared
+ *        history followed by this block: a mono source is given in both channels.
+ *     5. Sum, over the sounding slots in ascending slot number, from acc = 0: dw = w1 - w0; w = w0 + a * dw; acc = acc + w * y_j —
+ *        the same scalar w for both ears.  Not clamped.  A row without a sounding slot gives zeros.
+ *     6. Afterwards a continuing or started slot holds d0 + e, g1 (0 beyond num_bands), w1 and q1; an ended slot is free; the
+ *        block enters the history; n0 += F.  rows[i] as the reflection renderer's.
+ *     Consequence: with a set of H = 1 whose taps are all 1.0f the output equals fs_reflection_render_process_batch's with
+ *     channel_gain = (gain, gain).  The output is late by (T - 1) / 2 samples plus whatever onset the set's HRIRs carry.
+ *   fs_binaural_render_process_batch.  Arguments, refusals and batch rules of fs_reflection_render_process_batch, read for this
+ *   call, and further FS_ERR_INVALID_ARGUMENT for: no set in force; a gain that is not finite; a direction with a component that
+ *   is not finite or with all three zero; a source without fs_binaural_render_init; sources that do not share F and T (hence Tc);
+ *   a source whose ring the set in force has outgrown (fs_hrtf_set above).  Staging of its own (pinned + device), which holds the
+ *   folded tables {C0, dC} [sum of the listed sources' V][2][Tc] beside the rest and grows at the first call that needs more; a call
+ *   of a shape the context has seen allocates nothing.  One copy up, four launches whatever the count (plan, taps, render, mix),
+ *   one copy back, one wait on the reverb stream.  ONE audio render thread runs all callbacks of a context.
+ *   A key for the direct sound: FS_BINAURAL_DIRECT_KEY, a first-order key (a triangle index) no scene of fewer than 2^29 - 1
+ *   triangles uses.
+ *   fs_source_destroy and fs_context_destroy free everything. */
+#define FS_MAX_HRTF_DIRECTIONS 4096
+#define FS_MAX_HRTF_TAPS       512
+#define FS_HRTF_DEFAULT_RADIUS_CM          8.75f
+#define FS_HRTF_DEFAULT_SOUND_SPEED_CM_S   34300.0f
+#define FS_BINAURAL_DIRECT_KEY 0x1FFFFFFFu
+typedef struct fs_hrtf_desc {
+    uint32_t struct_size;
+    int32_t  directions;              /* n */
+    int32_t  taps;                    /* H */
+    int32_t  sample_rate;             /* the rate the taps were sampled at: the context's */
+    const float* dirs;                /* [n][3] unit vectors, head frame */
+    const float* hrir;                /* [n][2][H]: direction, ear (0 left, 1 right), tap */
+} fs_hrtf_desc;
+typedef struct fs_binaural_voice {
+    uint32_t key;                     /* identity from callback to callback, as fs_reflection_voice.key */
+    float    delay;                   /* s, >= 0: the path's delay, less whatever latency the host compensates */
+    float    band_gain[FS_MAX_BANDS]; /* finite, >= 0; entries beyond num_bands ignored */
+    float    gain;                    /* finite, any sign: the host's distance law */
+    float    direction[3];            /* head frame, towards where the sound arrives from: finite, not all zero, any length */
+} fs_binaural_voice;                  /* an array element: no struct_size; 56 bytes */
+typedef struct fs_binaural_render_row {
+    uint32_t sounding, started, ended, dropped;
+} fs_binaural_render_row;             /* 16 bytes */
+int fs_hrtf_set(fs_context* ctx, const fs_hrtf_desc* desc /* NULL: clear */);
+int fs_hrtf_info(fs_context* ctx, int32_t* directions, int32_t* taps);
+int fs_hrtf_spherical_head(int32_t sample_rate, float radius_cm, float sound_speed_cm_s, int32_t directions, int32_t taps,
+                           float* dirs /* [directions][3] */, float* hrir /* [directions][2][taps] */);
+int fs_binaural_render_init(fs_context* ctx, fs_source src, int32_t frame_size, int32_t taps, int32_t voices, float max_delay_seconds);
+int fs_binaural_render_release(fs_context* ctx, fs_source src);
+int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in /* [count][F * 2] */,
+                                     const fs_binaural_voice* voices /* [count][stride] */, const int32_t* voice_counts /* [count] */,
+                                     int32_t stride, float* out /* [count][F * 2] or NULL */, float* mix /* [F * 2] or NULL */,
+                                     fs_binaural_render_row* rows /* [count] or NULL */);
 
 /* ---- row f4: frequency-dependent material response of one audio block ------------------------------------
  *      UMaterialAcousticProcessor::ApplyMaterialFD (Private/MaterialAcousticProcessor.cpp:8-107, MAP.cpp):
