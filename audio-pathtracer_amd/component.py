@@ -507,6 +507,33 @@ class Context:
         got = tuple(x for x in results if x is not None)
         return got if len(got) > 1 else got[0]
 
+    @staticmethod
+    def _voice_table(voices, count, stride, dtype, write):
+        """a voice-bank callback's (table [count][stride] of dtype, counts [count], stride) from one list per source, each an
+        array of dtype or tuples; write(entry, tuple) puts what the renderer's tuple holds beyond (key, delay, band_gain) into the
+        entry and returns those three"""
+        if len(voices) != count:
+            raise ValueError("voices must have one list per source")
+        if stride is None:
+            stride = max([len(v) for v in voices] + [1])
+        stride = int(stride)
+        if any(len(v) > stride for v in voices):
+            raise ValueError("a voice list is longer than stride")
+        table = np.zeros((count, max(stride, 1)), dtype=dtype)
+        counts = np.zeros(count, np.int32)
+        for i, lst in enumerate(voices):
+            counts[i] = len(lst)
+            if isinstance(lst, np.ndarray) and lst.dtype == dtype:
+                table[i, :len(lst)] = lst
+                continue
+            for e, entry in enumerate(lst):
+                key, delay, gains = write(table[i, e], entry)
+                g = np.asarray(gains, np.float32).reshape(-1)
+                table[i, e]["key"] = key
+                table[i, e]["delay"] = delay
+                table[i, e]["band_gain"][:g.shape[0]] = g
+        return table, counts, stride
+
     # ---- direct sound on the audio thread: fractional delay + band FIR for all sources of a callback ----
     RENDER_TARGET_DTYPE = np.dtype([("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,))])
 
@@ -571,26 +598,13 @@ class Context:
         (default: the longest list, at least 1) -> (out [count][frame_size * 2] (want_out), mix [frame_size * 2] (want_mix), rows
         [count] REFLECTION_RENDER_ROW_DTYPE); what was not asked for is left out of the tuple"""
         srcs, count, a, out, mix = self._callback_open(sources, blocks, getattr(self, "_rr_frame", {}), want_out, want_mix)
-        if len(voices) != count:
-            raise ValueError("voices must have one list per source")
-        if stride is None:
-            stride = max([len(v) for v in voices] + [1])
-        stride = int(stride)
-        if any(len(v) > stride for v in voices):
-            raise ValueError("a voice list is longer than stride")
-        table = np.zeros((count, max(stride, 1)), dtype=self.REFLECTION_VOICE_DTYPE)
-        counts = np.zeros(count, np.int32)
-        for i, lst in enumerate(voices):
-            counts[i] = len(lst)
-            if isinstance(lst, np.ndarray) and lst.dtype == self.REFLECTION_VOICE_DTYPE:
-                table[i, :len(lst)] = lst
-                continue
-            for e, (key, delay, gains, chan) in enumerate(lst):
-                g = np.asarray(gains, np.float32).reshape(-1)
-                table[i, e]["key"] = key
-                table[i, e]["delay"] = delay
-                table[i, e]["band_gain"][:g.shape[0]] = g
-                table[i, e]["channel_gain"] = chan
+
+        def write(entry, voice):
+            key, delay, gains, chan = voice
+            entry["channel_gain"] = chan
+            return key, delay, gains
+
+        table, counts, stride = self._voice_table(voices, count, stride, self.REFLECTION_VOICE_DTYPE, write)
         rows = np.zeros(count, dtype=self.REFLECTION_RENDER_ROW_DTYPE)
         self.check(self.lib.fs_reflection_render_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data, table.ctypes.data,
                                                                counts.ctypes.data, stride, out.ctypes.data if want_out else None,
@@ -654,27 +668,14 @@ class Context:
         library (default: the longest list, at least 1) -> (out [count][frame_size * 2] (want_out), mix [frame_size * 2]
         (want_mix), rows [count] BINAURAL_RENDER_ROW_DTYPE); what was not asked for is left out of the tuple"""
         srcs, count, a, out, mix = self._callback_open(sources, blocks, getattr(self, "_br_frame", {}), want_out, want_mix)
-        if len(voices) != count:
-            raise ValueError("voices must have one list per source")
-        if stride is None:
-            stride = max([len(v) for v in voices] + [1])
-        stride = int(stride)
-        if any(len(v) > stride for v in voices):
-            raise ValueError("a voice list is longer than stride")
-        table = np.zeros((count, max(stride, 1)), dtype=self.BINAURAL_VOICE_DTYPE)
-        counts = np.zeros(count, np.int32)
-        for i, lst in enumerate(voices):
-            counts[i] = len(lst)
-            if isinstance(lst, np.ndarray) and lst.dtype == self.BINAURAL_VOICE_DTYPE:
-                table[i, :len(lst)] = lst
-                continue
-            for e, (key, delay, gains, gain, direction) in enumerate(lst):
-                g = np.asarray(gains, np.float32).reshape(-1)
-                table[i, e]["key"] = key
-                table[i, e]["delay"] = delay
-                table[i, e]["band_gain"][:g.shape[0]] = g
-                table[i, e]["gain"] = gain
-                table[i, e]["direction"] = direction
+
+        def write(entry, voice):
+            key, delay, gains, gain, direction = voice
+            entry["gain"] = gain
+            entry["direction"] = direction
+            return key, delay, gains
+
+        table, counts, stride = self._voice_table(voices, count, stride, self.BINAURAL_VOICE_DTYPE, write)
         rows = np.zeros(count, dtype=self.BINAURAL_RENDER_ROW_DTYPE)
         self.check(self.lib.fs_binaural_render_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data, table.ctypes.data,
                                                              counts.ctypes.data, stride, out.ctypes.data if want_out else None,

@@ -1,10 +1,10 @@
 // fs_capi_binaural_render.cpp — binaural voices on the audio thread: the HRIR set of the context (fs_hrtf_set / fs_hrtf_info), a
-// set for hosts that have none (fs_hrtf_spherical_head, host only), the per-source set-up (fs_binaural_render_init / _release)
-// and the callback of all sources (fs_binaural_render_process_batch: everything validated, the voices matched to the slots on
-// the host's copy of the slot table by the reflection renderer's voice_match, one copy up, the launches of
-// fs_binaural_render.hip, one copy back, one wait).  The band kernels and their per-context cache are the direct renderer's
-// (fs_capi_direct_render.cpp).  The reference has no slot for it.
-#include "fs_context.hpp"
+// set for hosts that have none (fs_hrtf_spherical_head, host only), and what the renderer is beyond its voice bank
+// (fs_capi_voice_bank.hpp: the callback; fs_capi_reflect_render.cpp: the set-up and its release): the refusals that name the
+// set, an entry's gain and direction, the list of sounding slots and the folded tables of fs_binaural_render.hip's launches.
+// The band kernels and their per-context cache are the direct renderer's (fs_capi_direct_render.cpp).  The reference has no slot
+// for it.
+#include "fs_capi_voice_bank.hpp"
 
 static_assert(sizeof(fs_binaural_voice) == 56, "fs_binaural_voice: the key, the delay, the bands, the gain, the direction");
 static_assert(sizeof(fs_binaural_render_row) == 16, "fs_binaural_render_row: four counts");
@@ -13,10 +13,6 @@ static_assert(FS_MAX_REFLECTION_RENDER_BATCH * FS_MAX_REFLECTION_VOICES <= 65536
 namespace {
 
 constexpr double kPi = 3.14159265358979323846;
-
-void br_free_slots(Source* s) {
-    for (int j = 0; j < FS_MAX_REFLECTION_VOICES; ++j) { s->br_held[j] = false; s->br_key[j] = 0; }
-}
 
 // the header's spherical-head model for one ear at angle theta from the ear's axis, in double: h[0 .. H)
 void head_taps(double theta, double a_over_c, double fs, int H, double* h) {
@@ -112,11 +108,11 @@ int fs_hrtf_set(fs_context* ctx, const fs_hrtf_desc* d) {
     // on, so no source is left out: the host's copies — what the matching reads, so every voice starts — all go first, and a
     // failed clear of a device copy (which a start overwrites anyway) is reported only after every source has had its turn.
     for (Source* s : ctx->sources)
-        if (s && s->alive && s->br.d) br_free_slots(s);
+        if (s && s->alive && s->br.r.d) s->br.free_slots();
     hipError_t clear_err = hipSuccess;
     for (Source* s : ctx->sources) {
-        if (!s || !s->alive || !s->br.d) continue;
-        const hipError_t e = hipMemsetAsync(s->br.d + offsetof(BinauralRenderState, slot), 0, sizeof(BinauralRenderState::slot), ctx->rev_stream);
+        if (!s || !s->alive || !s->br.r.d) continue;
+        const hipError_t e = hipMemsetAsync(s->br.r.d + offsetof(BinauralRenderState, slot), 0, sizeof(BinauralRenderState::slot), ctx->rev_stream);
         if (e != hipSuccess && clear_err == hipSuccess) clear_err = e;
     }
     if (clear_err != hipSuccess) return ctx->hip_fail(clear_err, "fs_hrtf_set (clearing the slots)");
@@ -132,139 +128,59 @@ int fs_hrtf_info(fs_context* ctx, int32_t* directions, int32_t* taps) {
 
 int fs_binaural_render_init(fs_context* ctx, fs_source h, int32_t frame_size, int32_t taps, int32_t voices, float max_delay_seconds) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
-    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
-    Source* s = get_source(ctx, h);
-    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-    if (ctx->hrtf_dirs == 0) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_binaural_render_init: no HRIR set in force (fs_hrtf_set)");
-    if (frame_size < 16 || frame_size > 16384 || !direct_render_taps_ok(taps) || voices < 1 || voices > FS_MAX_REFLECTION_VOICES ||
-        !std::isfinite(max_delay_seconds) || !(max_delay_seconds >= 0.0f))
-        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_binaural_render_init: frame size outside 16 .. 16384, taps even or outside 1 .. 2047, voices outside 1 .. 32, or a bad max delay");
-    const int tc = taps + ctx->hrtf_taps - 1;
-    if (tc > FS_DIRECT_RENDER_MAX_TAPS)
-        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_binaural_render_init: taps + the set's taps - 1 exceed 2047");
-    const double d_max = std::ceil((double)max_delay_seconds * (double)ctx->cfg.sample_rate);
-    const double need = d_max + (double)tc + 1.0 + (double)frame_size;
-    if (need > 1048576.0)
-        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_binaural_render_init: max delay + folded taps + 1 + frame size exceed 1 048 576 samples");
-    const int rc = render_setup(ctx, s->br, kBinauralRenderHeader, frame_size, taps, d_max, need);
-    if (rc) return rc;   // (without a set-up, or with the old one untouched)
-    s->br_voices = voices;
-    br_free_slots(s);
-    return FS_OK;
+    return voice_bank_init(ctx, h, &Source::br, ctx->hrtf_dirs ? ctx->hrtf_taps - 1 : -1,
+                           {"fs_binaural_render_init: no HRIR set in force (fs_hrtf_set)",
+                            "fs_binaural_render_init: frame size outside 16 .. 16384, taps even or outside 1 .. 2047, voices outside 1 .. 32, or a bad max delay",
+                            "fs_binaural_render_init: taps + the set's taps - 1 exceed 2047",
+                            "fs_binaural_render_init: max delay + folded taps + 1 + frame size exceed 1 048 576 samples"},
+                           frame_size, taps, voices, max_delay_seconds);
 }
 
 int fs_binaural_render_release(fs_context* ctx, fs_source h) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
-    Source* s = get_source(ctx, h);
-    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-    const int rc = render_clear(ctx, s->br, kBinauralRenderHeader);   // history := 0 ...
-    if (rc == FS_OK) br_free_slots(s);                                 // ... every slot free
-    return rc;
+    return voice_bank_release(ctx, h, &Source::br);
 }
 
 int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in,
                                      const fs_binaural_voice* voices, const int32_t* voice_counts, int32_t stride, float* out,
                                      float* mix, fs_binaural_render_row* rows) {
-    if (!ctx || !sources || !in || !voices || !voice_counts || (!out && !mix)) return FS_ERR_INVALID_ARGUMENT;
-    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
-    if (count < 1 || count > FS_MAX_REFLECTION_RENDER_BATCH)
-        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_REFLECTION_RENDER_BATCH)");
-    if (stride < 1 || stride > FS_MAX_REFLECTION_VOICES)
-        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "stride out of range (1 .. FS_MAX_REFLECTION_VOICES)");
-    if (ctx->hrtf_dirs == 0) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_binaural_render_process_batch: no HRIR set in force (fs_hrtf_set)");
-    // Everything is validated before the first state change or enqueue: a refused call changes nothing.
-    const int B = ctx->cfg.num_bands;
-    const int H = ctx->hrtf_taps;
-    const float fs_f = (float)ctx->cfg.sample_rate;
-    std::vector<Source*> srcs((size_t)count);
-    size_t slots_total = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        int rc;
-        Source* s = srcs[(size_t)i] = render_row(ctx, sources[i], &Source::br, "fs_binaural_render_init has not been called for this source", i ? srcs[0] : nullptr, &rc);
-        if (rc) return rc;
-        const int tc = s->br.taps + H - 1;
-        if (tc > FS_DIRECT_RENDER_MAX_TAPS || (double)s->br.max_delay + (double)tc + 1.0 + (double)s->br.frame > (double)s->br.ring)
-            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the HRIR set in force has outgrown this source's history: call fs_binaural_render_init again");
-        slots_total += (size_t)s->br_voices;
-        const int32_t n = voice_counts[i];
-        if (n < 0 || n > stride) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a voice count outside 0 .. stride");
-        const fs_binaural_voice* v = voices + (size_t)i * (size_t)stride;
-        for (int32_t e = 0; e < n; ++e) {
-            for (int32_t f = 0; f < e; ++f)
-                if (v[f].key == v[e].key) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a key appears twice in one row");
-            rc = render_aim_check(ctx, "voice", v[e].delay, v[e].band_gain, s->br);
-            if (rc) return rc;
-            if (!std::isfinite(v[e].gain)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a voice's gain is not finite");
-            const float* dir = v[e].direction;
+    static const VoiceBankRenderer<BinauralRenderBatch> q = {&Source::br, &fs_context::br_stage, "fs_binaural_render_init has not been called for this source",
+                                                             "fs_binaural_render_process_batch: no HRIR set in force (fs_hrtf_set)", launch_binaural_render};
+    const int H = ctx ? ctx->hrtf_taps : 0;
+    return voice_bank_process(
+        q, ctx, sources, count, in, voices, voice_counts, stride, out, mix, rows,
+        [&](const fs_binaural_voice& v) {
+            if (!std::isfinite(v.gain)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a voice's gain is not finite");
+            const float* dir = v.direction;
             if (!std::isfinite(dir[0]) || !std::isfinite(dir[1]) || !std::isfinite(dir[2]) || (dir[0] == 0.0f && dir[1] == 0.0f && dir[2] == 0.0f))
                 return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a voice's direction is not finite or is the zero vector");
-        }
-    }
-    { const int rc = render_no_duplicates(ctx, srcs); if (rc) return rc; }
-    const int frame = srcs[0]->br.frame, taps = srcs[0]->br.taps, tc = taps + H - 1;
-    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    hipStream_t rs = ctx->rev_stream;
-    enum { kItems, kVoices, kSounding, kN0 = 0, kPlans, kFolded };   // CallbackLayout::up and ::scratch
-    // (the list and the folded tables are sized by the rows' slots, not by how many sound in this call: a shape allocates once)
-    const CallbackLayout l = callback_layout(count, frame,
-                                             {sizeof(BinauralRenderItem) * (size_t)count, sizeof(fs_binaural_voice) * (size_t)count * (size_t)stride,
-                                              sizeof(uint16_t) * slots_total},
-                                             {sizeof(unsigned) * (size_t)count, sizeof(BinauralRenderPlan) * (size_t)count * FS_MAX_REFLECTION_VOICES,
-                                              sizeof(float2) * slots_total * 2 * (size_t)tc});
-    { const int rc = ctx->br_stage.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
-    char* hs = ctx->br_stage.h; char* ds = ctx->br_stage.d;
-    BinauralRenderItem* items = (BinauralRenderItem*)(hs + l.up[kItems]);
-    uint16_t* sounding = (uint16_t*)(hs + l.up[kSounding]);
-    int n_sounding = 0;
-    std::vector<VoiceMatch> matches((size_t)count);
-    for (int32_t i = 0; i < count; ++i) {
-        const Source* s = srcs[(size_t)i];
-        VoiceMatch& m = matches[(size_t)i] = voice_match(s->br_held, s->br_key, s->br_voices, voices + (size_t)i * (size_t)stride, sizeof(fs_binaural_voice), voice_counts[i]);
-        BinauralRenderItem& it = items[i];
-        std::memset(&it, 0, sizeof(it));
-        it.state = (BinauralRenderState*)s->br.d;
-        it.ring = (float*)(s->br.d + kBinauralRenderHeader);
-        it.table = s->br.table;
-        it.mask = s->br.ring - 1u;
-        it.slots = s->br_voices;
-        std::memcpy(it.op, m.op, sizeof(it.op));
-        it.first = n_sounding;
-        for (int j = 0; j < s->br_voices; ++j)
-            if (m.op[j] != kReflectIdle) sounding[n_sounding++] = (uint16_t)(i * FS_MAX_REFLECTION_VOICES + j);
-    }
-    std::memcpy(hs + l.up[kVoices], voices, sizeof(fs_binaural_voice) * (size_t)count * (size_t)stride);
-    std::memcpy(hs + l.in, in, l.rows);
-    FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, rs));
-    BinauralRenderBatch b{};
-    b.items = (const BinauralRenderItem*)(ds + l.up[kItems]);
-    b.voices = (const fs_binaural_voice*)(ds + l.up[kVoices]);
-    b.sounding = (const uint16_t*)(ds + l.up[kSounding]);
-    b.plans = (BinauralRenderPlan*)(ds + l.scratch[kPlans]);
-    b.n0 = (unsigned*)(ds + l.scratch[kN0]);
-    b.folded = (float2*)(ds + l.scratch[kFolded]);
-    b.dirs = ctx->d_hrtf;
-    b.hrir = ctx->d_hrtf + (size_t)ctx->hrtf_dirs * 3;
-    b.n_dirs = ctx->hrtf_dirs; b.h_taps = H;
-    b.count = count; b.stride = stride; b.frame = frame; b.taps = taps; b.tc = tc; b.bands = B; b.n_sounding = n_sounding;
-    b.fs = fs_f;
-    b.in = (const float*)(ds + l.in);
-    b.out = (float*)(ds + l.d_out);
-    b.mix = mix ? (float*)(ds + l.d_mix) : nullptr;
-    launch_binaural_render(b, rs);
-    FS_HIP(ctx, hipGetLastError());
-    for (int32_t i = 0; i < count; ++i) {   // the plan pass is on its way: the slot tables are what it leaves behind
-        Source* s = srcs[(size_t)i];
-        std::memcpy(s->br_held, matches[(size_t)i].held, sizeof(s->br_held));
-        std::memcpy(s->br_key, matches[(size_t)i].key, sizeof(s->br_key));
-    }
-    { const int rc = callback_finish(ctx, ctx->br_stage, l, out != nullptr, mix); if (rc) return rc; }
-    if (out) std::memcpy(out, hs + l.h_out, l.rows);
-    if (rows)
-        for (int32_t i = 0; i < count; ++i) {
-            const fs_reflection_render_row& r = matches[(size_t)i].row;
-            rows[i] = fs_binaural_render_row{r.sounding, r.started, r.ended, r.dropped};
-        }
-    return FS_OK;
+            return (int)FS_OK;
+        },
+        [&](const VoiceBank& bank) {
+            const int tc = bank.r.taps + H - 1;
+            if (tc > FS_DIRECT_RENDER_MAX_TAPS || (double)bank.r.max_delay + (double)tc + 1.0 + (double)bank.r.frame > (double)bank.r.ring)
+                return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the HRIR set in force has outgrown this source's history: call fs_binaural_render_init again");
+            return (int)FS_OK;
+        },
+        // the sounding slots' list | the folded tables (sized by the rows' slots, not by how many sound in this call: a shape
+        // allocates once)
+        [&](size_t slots, const RenderSetup& shape) {
+            return std::array<size_t, 2>{sizeof(uint16_t) * slots, sizeof(float2) * slots * 2 * (size_t)(shape.taps + H - 1)};
+        },
+        [&](BinauralRenderBatch& b, BinauralRenderItem* items, char* h_sounding, char* d_sounding, char* d_folded) {
+            uint16_t* sounding = (uint16_t*)h_sounding;
+            for (int i = 0; i < b.count; ++i) {
+                items[i].first = b.n_sounding;
+                for (int j = 0; j < items[i].slots; ++j)
+                    if (items[i].op[j] != kVoiceIdle) sounding[b.n_sounding++] = (uint16_t)(i * kVoiceSlots + j);
+            }
+            b.sounding = (const uint16_t*)d_sounding;
+            b.folded = (float2*)d_folded;
+            b.dirs = ctx->d_hrtf;
+            b.hrir = ctx->d_hrtf + (size_t)ctx->hrtf_dirs * 3;
+            b.n_dirs = ctx->hrtf_dirs; b.h_taps = H;
+            b.tc = b.taps + H - 1;
+        });
 }
 
 }  // extern "C"

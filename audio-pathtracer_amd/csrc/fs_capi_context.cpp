@@ -164,7 +164,7 @@ void free_source(fs_context* ctx, Source* s) {
         if (s->d_ring) (void)hipFree(s->d_ring);
         if (s->d_fade_from) (void)hipFree(s->d_fade_from);
         if (s->d_fade_to) (void)hipFree(s->d_fade_to);
-        for (RenderSetup* r : {&s->dr, &s->rr, &s->br}) if (r->d) (void)hipFree(r->d);
+        for (RenderSetup* r : {&s->dr, &s->rr.r, &s->br.r}) if (r->d) (void)hipFree(r->d);
         if (s->d_dir) (void)hipFree(s->d_dir);   // (the callers have synchronised the compute stream)
     }
     delete s;

@@ -93,16 +93,6 @@ int render_clear(fs_context* ctx, const RenderSetup& r, size_t header) {
     return FS_OK;
 }
 
-Source* render_row(fs_context* ctx, fs_source h, RenderSetup Source::*which, const char* no_setup, const Source* first, int* rc) {
-    Source* s = get_source(ctx, h);
-    if (!s) *rc = ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-    else if (!(s->*which).d) *rc = ctx->fail(FS_ERR_INVALID_ARGUMENT, no_setup);
-    else if (first && ((s->*which).frame != (first->*which).frame || (s->*which).taps != (first->*which).taps))
-        *rc = ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size and one tap count");
-    else *rc = FS_OK;
-    return *rc ? nullptr : s;
-}
-
 int render_aim_check(fs_context* ctx, const char* whose, float delay, const float* band_gain, const RenderSetup& r) {
     if (!std::isfinite(delay) || !(delay >= 0.0f) || delay * (float)ctx->cfg.sample_rate > (float)r.max_delay)
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, std::string("a ") + whose + "'s delay is negative, not finite or beyond the source's max delay");
@@ -168,7 +158,7 @@ int fs_direct_render_process_batch(fs_context* ctx, const fs_source* sources, in
     std::vector<Source*> srcs((size_t)count);
     for (int32_t i = 0; i < count; ++i) {
         int rc;
-        srcs[(size_t)i] = render_row(ctx, sources[i], &Source::dr, "fs_direct_render_init has not been called for this source", i ? srcs[0] : nullptr, &rc);
+        srcs[(size_t)i] = render_row(ctx, sources[i], [](const Source& s) -> const RenderSetup& { return s.dr; }, "fs_direct_render_init has not been called for this source", i ? srcs[0] : nullptr, &rc);
         if (!rc) rc = render_aim_check(ctx, "target", targets[i].delay, targets[i].band_gain, srcs[(size_t)i]->dr);
         if (rc) return rc;
     }

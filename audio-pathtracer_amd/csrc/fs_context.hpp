@@ -82,6 +82,18 @@ struct RenderSetup {
     unsigned ring = 0;
     const float* table = nullptr;
 };
+// A renderer's voice bank on a source (fs_reflection_render_init / fs_binaural_render_init): the set-up — its header is a
+// VoiceBankState, kVoiceBankHeader bytes; the rings are shared by the `voices` slots — and the slot table the callback matches
+// against, the host's copy (the device's is in the state block)
+struct VoiceBank {
+    RenderSetup r;
+    int voices = 0;
+    bool held[FS_MAX_REFLECTION_VOICES] = {};
+    uint32_t key[FS_MAX_REFLECTION_VOICES] = {};
+    void free_slots() {
+        for (int j = 0; j < FS_MAX_REFLECTION_VOICES; ++j) { held[j] = false; key[j] = 0; }
+    }
+};
 
 struct Source {
     bool alive = false;
@@ -177,19 +189,10 @@ struct Source {
     int32_t fade_len = 0, fade_pos = 0;
     bool fading = false, fade_primed = false;
     uint64_t fade_gen = 0;
-    // direct sound (header: DirectRenderState, kDirectRenderHeader bytes) and early reflections (header: ReflectRenderState,
-    // kReflectRenderHeader bytes; the rings are shared by the rr_voices slots); rr_held / rr_key: the slot table the reflection
-    // callback matches against, the host's copy
-    RenderSetup dr, rr;
-    int rr_voices = 0;
-    bool rr_held[FS_MAX_REFLECTION_VOICES] = {};
-    uint32_t rr_key[FS_MAX_REFLECTION_VOICES] = {};
-    // binaural voices (header: BinauralRenderState, kBinauralRenderHeader bytes): the reflection fields' counterparts.  br.taps = T;
-    // the rings were sized for T + H - 1 taps of the set in force at fs_binaural_render_init
-    RenderSetup br;
-    int br_voices = 0;
-    bool br_held[FS_MAX_REFLECTION_VOICES] = {};
-    uint32_t br_key[FS_MAX_REFLECTION_VOICES] = {};
+    // direct sound (header: DirectRenderState, kDirectRenderHeader bytes), and the voice banks of the early reflections and of the
+    // binaural voices.  br.r.taps = T; its rings were sized for T + H - 1 taps of the set in force at fs_binaural_render_init
+    RenderSetup dr;
+    VoiceBank rr, br;
     float occlusion = 1.0f;            // OcclusionAttenuation FSAC.h:130 (1.f until the first UpdateSound)
 };
 
@@ -595,30 +598,49 @@ CallbackLayout callback_layout(int count, int frame, std::initializer_list<size_
 // The tail of a callback whose launches are enqueued on the reverb stream: the copy back (out | mix in one when both are wanted,
 // else mix alone), the wait, mix copied out.  The rows of out are then in st.h + l.h_out: the caller's to copy.
 int callback_finish(fs_context* ctx, const CallbackStage& st, const CallbackLayout& l, bool want_out, float* mix);
-// ---- fs_capi_direct_render.cpp: what the reflection renderer shares with the direct one -----------------------------
+// ---- fs_capi_direct_render.cpp: what the voice bank's renderers share with the direct one (render_row: defined here) ----
 bool direct_render_taps_ok(int32_t taps);
 // What both inits do once the arguments are found good (need = d_max + taps + 1 + frame samples, the ring's least size): the
 // table of (taps, edges in force), the wait for the callbacks' stream, the old state block freed, a zeroed new one of
 // header bytes + the rings.  A failure before the wait changes nothing; one after it leaves the source without a set-up.
 int render_setup(fs_context* ctx, RenderSetup& r, size_t header, int frame, int taps, double d_max, double need);
 int render_clear(fs_context* ctx, const RenderSetup& r, size_t header);   // the releases: history := 0 (enqueued), where there is a set-up
-// a row's first checks, in this order: the handle, the set-up (`which` of the source's two; no_setup: the message), the batch's
-// one shape (first: row 0's source, nullptr in row 0).  *rc = FS_OK and the source, or the failure reported and nullptr.
-Source* render_row(fs_context* ctx, fs_source h, RenderSetup Source::*which, const char* no_setup, const Source* first, int* rc);
+// a row's first checks, in this order: the handle, the set-up (which(source): the one of the source's three that the callback
+// renders with; no_setup: the message), the batch's one shape (first: row 0's source, nullptr in row 0).  *rc = FS_OK and the
+// source, or the failure reported and nullptr.
+Source* get_source(fs_context* ctx, fs_source h);   // (fs_capi_context.cpp)
+template <typename Which>
+Source* render_row(fs_context* ctx, fs_source h, Which&& which, const char* no_setup, const Source* first, int* rc) {
+    Source* s = get_source(ctx, h);
+    if (!s) *rc = ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    else if (!which(*s).d) *rc = ctx->fail(FS_ERR_INVALID_ARGUMENT, no_setup);
+    else if (first && (which(*s).frame != which(*first).frame || which(*s).taps != which(*first).taps))
+        *rc = ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size and one tap count");
+    else *rc = FS_OK;
+    return *rc ? nullptr : s;
+}
 // a target's or a voice's (`whose`) delay and band gains against the source's set-up
 int render_aim_check(fs_context* ctx, const char* whose, float delay, const float* band_gain, const RenderSetup& r);
 int render_no_duplicates(fs_context* ctx, const std::vector<Source*>& srcs);   // "a source appears twice in the batch"
-// ---- fs_capi_reflect_render.cpp: what the binaural renderer shares with the reflection one ----------------------------
-// what one row's matching decides: the slots' ops (kReflectIdle ...), the slot table afterwards, the counts
+// ---- fs_capi_reflect_render.cpp: the voice bank's host side, the reflection and the binaural renderer's alike ----------
+// (the callback itself is fs_capi_voice_bank.hpp's voice_bank_process)
+// what one row's matching decides: the slots' ops (kVoiceIdle ...), the slot table afterwards, the counts
 struct VoiceMatch {
     int8_t op[FS_MAX_REFLECTION_VOICES];
     bool held[FS_MAX_REFLECTION_VOICES];
     uint32_t key[FS_MAX_REFLECTION_VOICES];
     fs_reflection_render_row row;
 };
-// rule 1 of the reflection renderer on a source's slot table (held, key) [V]: `voices` = the row's n entries, voice_bytes apart,
-// each beginning with its key
-VoiceMatch voice_match(const bool* held, const uint32_t* key, int V, const void* voices, size_t voice_bytes, int n);
+// rule 1 of the reflection renderer on a source's slot table: `voices` = the row's n entries, voice_bytes apart, each beginning
+// with its key
+VoiceMatch voice_match(const VoiceBank& bank, const void* voices, size_t voice_bytes, int n);
+// What fs_reflection_render_init and fs_binaural_render_init do with their arguments: `which` = the source's bank; fold_taps = the
+// taps a voice's filter grows by (H - 1 of the set in force; 0: the reflection renderer's), a negative one = no set in force;
+// the texts are the entry point's own refusals: no set, the arguments' ranges, too many folded taps, too long a history.
+struct VoiceBankInitTexts { const char *no_set, *ranges, *folded, *ring; };
+int voice_bank_init(fs_context* ctx, fs_source h, VoiceBank Source::*which, int fold_taps, const VoiceBankInitTexts& t, int32_t frame_size,
+                    int32_t taps, int32_t voices, float max_delay_seconds);
+int voice_bank_release(fs_context* ctx, fs_source h, VoiceBank Source::*which);   // history := 0, every slot free
 // ---- fs_capi_context.cpp ------------------------------------------------------------------------------------------
 Source* get_source(fs_context* ctx, fs_source h);
 hipError_t wait_energy_readers(fs_context* ctx, Source* s);            // before the compute stream writes the current energy buffer

@@ -2,10 +2,14 @@
 // fs_binaural_render.hip) share on the device: one voice's block — a time-varying fractional delay and a linear-phase FIR whose
 // taps ramp from sum_b g0_b k_b to sum_b g1_b k_b — as pieces a kernel puts together: the delay of an output sample and its slew
 // clamp, the tap table and the tile's read window in LDS, the tap loop of one output sample, the output store with the ring append.
+// Behind them the voice bank, which the reflection and the binaural renderer are: the plan pass and the render pass of a callback
+// whose rows hold a table of voices, with what a renderer's voices carry beyond a delay and band gains, and where their taps
+// come from, handed in.
 // The rule is
 // include/frequensee.h's, to the bit: every fp32 operation stands where the header puts it (the files are built with
-// -ffp-contract=off and the tests compare bits).  No piece holds a barrier or a return: each says which barrier its caller owes.
-// The LDS arrays travel as references to arrays, so that after inlining the tap loop still reads them with LDS instructions.
+// -ffp-contract=off and the tests compare bits).  No piece of a voice's block holds a barrier or a return: each says which barrier
+// its caller owes.  The LDS arrays travel as references to arrays, so that after inlining the tap loop still reads them with LDS
+// instructions.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -139,6 +143,125 @@ __device__ __forceinline__ void render_store(float* __restrict__ out_all, float*
 // HRIR folded in), `folded` [taps], into s_cd.  In render_build_taps' place, under the same barriers.
 __device__ __forceinline__ void render_load_taps(RenderTaps& s_cd, const float2* __restrict__ folded, int taps, int tid) {
     for (int t = tid; t < taps; t += kRenderTile) s_cd[t] = folded[t];
+}
+
+// ---- the voice bank (fs_internal.hpp: VoiceBankState, VoiceBankItem): the two passes of a callback whose rows are banks of voices.
+// Unlike the pieces above each is a kernel's whole body, returns and barriers included.  What a renderer's voices carry beyond a
+// delay and band gains — their aim — is the renderer's to say.
+
+// The plan pass, one thread per (row, slot): reads the slot's device-resident state and the entry the host matched it with
+// (Item::op), fixes what this callback ramps from and by how much in the slot's plan record, and writes the state the callback
+// leaves behind; the thread of slot 0 also moves the row's sample counter on.  R, the renderer:
+//   R::Aim                      what a voice aims at beyond its delay and band gains
+//   R::read(v, set...)          ... of entry v (set: what the kernel passes through for it)
+//   R::fade_out(st)             ... of an ending slot
+//   R::from_silence(st, aim)    a starting slot's state: what it rises from
+//   R::plan(pl, st, aim, it, slot)   the record's part of it: from st to aim
+//   R::keep(st, aim)            the state's part of it after the callback
+template <typename R, typename Item, typename Voice, typename Plan, typename... Set>
+__device__ __forceinline__ void voice_bank_plan(const Item* __restrict__ items, const Voice* __restrict__ voices, Plan* __restrict__ plans,
+                                                unsigned* __restrict__ n0_out, int count, int stride, int frame, int bands, float fs_f,
+                                                Set... set) {
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = id / kVoiceSlots, slot = id % kVoiceSlots;
+    if (r >= count) return;
+    const Item& it = items[r];
+    if (slot == 0) {
+        const unsigned n0 = it.state->n0;
+        n0_out[r] = n0;
+        it.state->n0 = n0 + (unsigned)frame;
+    }
+    if (slot >= it.slots) return;
+    const int op = it.op[slot];
+    if (op == kVoiceIdle) return;
+    auto st = it.state->slot[slot];
+    Plan pl;
+    float d1, g1[FS_MAX_BANDS];
+    typename R::Aim aim;
+    if (op == kVoiceEnd) {   // the delay freezes, the gains stay
+        d1 = st.d0;
+        for (int b = 0; b < FS_MAX_BANDS; ++b) g1[b] = st.g0[b];
+        aim = R::fade_out(st);
+    } else {
+        const bool start = op >= kVoiceStart;
+        const Voice v = voices[(size_t)r * (size_t)stride + (size_t)(start ? op - kVoiceStart : op - kVoiceContinue)];
+        d1 = v.delay * fs_f;
+        for (int b = 0; b < FS_MAX_BANDS; ++b) g1[b] = v.band_gain[b];
+        aim = R::read(v, set...);
+        if (start) {   // from its target, out of silence
+            st.d0 = d1;
+            for (int b = 0; b < FS_MAX_BANDS; ++b) st.g0[b] = g1[b];
+            R::from_silence(st, aim);
+        }
+        st.key = v.key;
+    }
+    const float e = render_slew(d1 - st.d0, frame);
+    pl.d0 = st.d0;
+    pl.e = e;
+    for (int b = 0; b < FS_MAX_BANDS; ++b) { pl.g0[b] = st.g0[b]; pl.g1[b] = g1[b]; }
+    R::plan(pl, st, aim, it, slot);
+    plans[(size_t)r * kVoiceSlots + slot] = pl;
+    if (op == kVoiceEnd) {
+        st = decltype(st){};   // free
+    } else {
+        st.held = 1;
+        st.d0 = pl.d0 + e;   // what the last output sample used: a == 1 there
+        for (int b = 0; b < FS_MAX_BANDS; ++b) st.g0[b] = b < bands ? g1[b] : 0.0f;
+        R::keep(st, aim);
+    }
+    it.state->slot[slot] = st;
+}
+
+// The render pass, a grid of (frame / kRenderTile output tiles) x 2 channels x rows.  A workgroup loops over its row's sounding
+// slots in ascending order — the trip count and every branch around a barrier depend on the row only — and per slot puts the taps
+// {c0[t], dc[t]} and the tile's read window into LDS (the window is per slot: every slot has a delay of its own), runs the
+// four-accumulator tap loop of one output sample per thread and adds w * y to a register.  A thread past the frame's end keeps
+// filling tables and windows and skips only the tap loop and the stores: nobody leaves before the last barrier.  After the last
+// slot the thread stores its output and appends its input sample to the ring (render_store).  The renderer:
+//   load_taps(s_cd, table, plp, ch, tid)   the slot's `taps` taps into s_cd (table: the row's band kernels), under render_build_taps' barriers
+//   weight(plp, ch)                        {w0, dw} of the slot in channel ch
+template <typename Item, typename Plan, typename LoadTaps, typename Weight>
+__device__ __forceinline__ void voice_bank_render(const Item* __restrict__ items, const Plan* __restrict__ plans,
+                                                  const unsigned* __restrict__ n0_all, const float* __restrict__ in_all,
+                                                  float* __restrict__ out_all, int frame, int taps, LoadTaps&& load_taps, Weight&& weight) {
+    __shared__ RenderTaps s_cd;      // of the slot in hand
+    __shared__ RenderWindow s_win;   // likewise: every slot has a delay of its own
+    const int r = blockIdx.z;
+    struct { float* ring; const float* table; unsigned mask; int slots; } it = {items[r].ring, items[r].table, items[r].mask, items[r].slots};
+    const int8_t* __restrict__ ops = items[r].op;
+    const unsigned n0 = n0_all[r];
+    const int ch = blockIdx.y;
+    const int s_a = blockIdx.x * kRenderTile;
+    const int s_b = min(s_a + kRenderTile, frame) - 1;
+    const int tid = threadIdx.x;
+    const int s = s_a + tid;
+    const bool live = s < frame;
+    const float* __restrict__ in = in_all + (size_t)r * 2 * (size_t)frame;
+    float* __restrict__ ring = it.ring + (size_t)ch * ((size_t)it.mask + 1);
+    const float frame_f = (float)frame;
+    float out = 0.0f;
+
+    for (int slot = 0; slot < it.slots; ++slot) {   // (uniform over the workgroup: the row's)
+        if (ops[slot] == kVoiceIdle) continue;
+        const Plan* __restrict__ plp = plans + (size_t)r * kVoiceSlots + slot;
+        // (the scalars by value, the gain arrays through the record: indexing a copy by the band would put it in scratch)
+        const float2 w0_dw = weight(plp, ch);
+        struct { float d0, e, w0, dw; } pl = {plp->d0, plp->e, w0_dw.x, w0_dw.y};
+
+        load_taps(s_cd, it.table, plp, ch, tid);
+        const int i_hi = render_stage_window(s_win, ring, it.mask, in, ch, n0, pl.d0, pl.e, s_a, s_b, frame, frame_f, taps, tid);
+        __syncthreads();
+
+        if (live) {
+            float a;
+            const float y = render_sample(s_cd, s_win, pl.d0, pl.e, s, s_a, i_hi, frame_f, taps, &a);
+            const float w = pl.w0 + a * pl.dw;
+            out = out + w * y;
+        }
+        __syncthreads();   // the next slot rebuilds the LDS
+    }
+    if (!live) return;
+    render_store(out_all, ring, it.mask, in, r, ch, n0, s, frame, out);
 }
 
 }  // namespace

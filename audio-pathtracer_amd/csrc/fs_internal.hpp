@@ -654,10 +654,35 @@ struct DirectRenderBatch {
 };
 // the plan pass, the render pass (which also appends the blocks to the rings), the mix (when b.mix)
 void launch_direct_render(const DirectRenderBatch& b, hipStream_t s);
-// fs_reflect_render.hip (the early-reflection callback).  A source's state is one device block (Source::rr.d): this header, then at
-// kReflectRenderHeader bytes the two history rings [2][ring], shared by the source's slots; zeroed = every slot free, nothing heard.
+// The voice bank (fs_dev_render.hpp: its two passes; fs_capi_voice_bank.hpp: its host side), which the early-reflection and the
+// binaural callback are built on: per source a table of kVoiceSlots slots, each a voice — a delay, band gains and what the renderer's
+// voices carry beyond them — held from callback to callback.  A source's state is one device block (Source::rr.r.d / br.r.d): a
+// VoiceBankState of the renderer's slot record, then at kVoiceBankHeader bytes the two history rings [2][ring], shared by the
+// source's slots; zeroed = every slot free, nothing heard.
+constexpr int kVoiceSlots = FS_MAX_REFLECTION_VOICES;
+template <typename Slot>
+struct VoiceBankState {
+    unsigned n0;           // absolute index of the next block's first sample (wraps; the ring index is n & mask)
+    int32_t pad[15];
+    Slot slot[kVoiceSlots];
+};
+constexpr size_t kVoiceBankHeader = 2304;
+// what the host's matching decided for a slot in this callback (VoiceBankItem::op): idle, ending, or continuing / starting
+// with entry e of the row as kVoiceContinue + e / kVoiceStart + e
+constexpr int kVoiceIdle = -1, kVoiceEnd = -2, kVoiceContinue = 0, kVoiceStart = kVoiceSlots;
+// one descriptor per row of the call, in list order: the host's staging layout
+template <typename Slot>
+struct VoiceBankItem {
+    VoiceBankState<Slot>* state;
+    float* ring;           // [2][mask + 1]
+    const float* table;    // the band kernels [bands][taps] the source was initialised with
+    unsigned mask;
+    int32_t slots;         // V
+    int8_t op[kVoiceSlots];
+};
+// fs_reflect_render.hip (the early-reflection callback): a voice carries a pair of channel gains
 struct ReflectRenderSlot {
-    int32_t held;          // the device's record of the slot table; the matching itself runs on the host's copy (Source::rr_held / rr_key)
+    int32_t held;          // the device's record of the slot table; the matching itself runs on the host's copy (VoiceBank::held / key)
     uint32_t key;
     float d0;              // the delay the slot's last output sample used, in samples
     float g0[FS_MAX_BANDS];   // ... its band gains
@@ -665,26 +690,10 @@ struct ReflectRenderSlot {
     int32_t pad[3];
 };
 static_assert(sizeof(ReflectRenderSlot) == 64, "ReflectRenderSlot: sixteen words");
-struct ReflectRenderState {
-    unsigned n0;           // absolute index of the next block's first sample (wraps; the ring index is n & mask)
-    int32_t pad[15];
-    ReflectRenderSlot slot[FS_MAX_REFLECTION_VOICES];
-};
-constexpr size_t kReflectRenderHeader = 2304;
-static_assert(sizeof(ReflectRenderState) == 2112 && sizeof(ReflectRenderState) <= kReflectRenderHeader && kReflectRenderHeader % 256 == 0,
-              "ReflectRenderState: the counter's line and the slots in front of the rings");
-// what the host's matching decided for a slot in this callback (ReflectRenderItem::op): idle, ending, or continuing / starting
-// with entry e of the row as kReflectContinue + e / kReflectStart + e
-constexpr int kReflectIdle = -1, kReflectEnd = -2, kReflectContinue = 0, kReflectStart = FS_MAX_REFLECTION_VOICES;
-// one descriptor per row of the call, in list order: the host's staging layout
-struct ReflectRenderItem {
-    ReflectRenderState* state;
-    float* ring;           // [2][mask + 1]
-    const float* table;    // the band kernels [bands][taps] the source was initialised with
-    unsigned mask;
-    int32_t slots;         // V
-    int8_t op[FS_MAX_REFLECTION_VOICES];
-};
+using ReflectRenderState = VoiceBankState<ReflectRenderSlot>;
+static_assert(sizeof(ReflectRenderState) == 2112 && sizeof(ReflectRenderState) <= kVoiceBankHeader && kVoiceBankHeader % 256 == 0,
+              "VoiceBankState: the counter's line and the slots in front of the rings");
+struct ReflectRenderItem : VoiceBankItem<ReflectRenderSlot> {};
 static_assert(sizeof(ReflectRenderItem) == 64, "ReflectRenderItem: three pointers, two words and a byte per slot, the host's staging layout");
 // what the plan pass fixes for a sounding slot: where this callback ramps from, the slew-limited change of the delay, the gains
 // it ramps between and the channel gains' start and change
@@ -698,7 +707,7 @@ static_assert(sizeof(ReflectRenderPlan) == 96, "ReflectRenderPlan: twenty-four w
 struct ReflectRenderBatch {
     const ReflectRenderItem* items;     // [count]
     const fs_reflection_voice* voices;  // [count][stride]
-    ReflectRenderPlan* plans;           // [count][FS_MAX_REFLECTION_VOICES] scratch
+    ReflectRenderPlan* plans;           // [count][kVoiceSlots] scratch
     unsigned* n0;                       // [count] scratch: every row's counter before this callback
     int count, stride, frame, taps, bands;
     float fs;                           // the sample rate: an entry's d1 = delay * fs
@@ -708,10 +717,9 @@ struct ReflectRenderBatch {
 };
 // the plan pass, the render pass (which also appends the blocks to the rings), the mix (when b.mix)
 void launch_reflect_render(const ReflectRenderBatch& b, hipStream_t s);
-// fs_binaural_render.hip (the binaural-voice callback).  A source's state is one device block (Source::br.d): this header, then at
-// kBinauralRenderHeader bytes the two history rings [2][ring], shared by the source's slots; zeroed = every slot free, nothing heard.
+// fs_binaural_render.hip (the binaural-voice callback): a voice carries one gain and the index of its HRIR
 struct BinauralRenderSlot {
-    int32_t held;          // the device's record of the slot table; the matching itself runs on the host's copy (Source::br_held / br_key)
+    int32_t held;          // as ReflectRenderSlot's
     uint32_t key;
     float d0;              // the delay the slot's last output sample used, in samples
     float g0[FS_MAX_BANDS];   // ... its band gains
@@ -720,27 +728,15 @@ struct BinauralRenderSlot {
     int32_t pad[3];
 };
 static_assert(sizeof(BinauralRenderSlot) == 64, "BinauralRenderSlot: sixteen words");
-struct BinauralRenderState {
-    unsigned n0;           // absolute index of the next block's first sample (wraps; the ring index is n & mask)
-    int32_t pad[15];
-    BinauralRenderSlot slot[FS_MAX_REFLECTION_VOICES];
-};
-constexpr size_t kBinauralRenderHeader = 2304;
-static_assert(sizeof(BinauralRenderState) == 2112 && sizeof(BinauralRenderState) <= kBinauralRenderHeader && kBinauralRenderHeader % 256 == 0,
-              "BinauralRenderState: the counter's line and the slots in front of the rings");
-// one descriptor per row of the call, in list order: the host's staging layout.  op: the reflection renderer's codes (kReflectIdle ...);
+using BinauralRenderState = VoiceBankState<BinauralRenderSlot>;
+static_assert(sizeof(BinauralRenderState) == 2112, "VoiceBankState: one layout, whatever the sixteen words of a slot hold");
 // first = the index in the call's folded tables of the row's lowest sounding slot, the others follow in ascending slot number
-struct BinauralRenderItem {
-    BinauralRenderState* state;
-    float* ring;           // [2][mask + 1]
-    const float* table;    // the band kernels [bands][taps] the source was initialised with
-    unsigned mask;
-    int32_t slots;         // V
-    int8_t op[FS_MAX_REFLECTION_VOICES];
+struct BinauralRenderItem : VoiceBankItem<BinauralRenderSlot> {
     int32_t first;
     int32_t pad;
 };
-static_assert(sizeof(BinauralRenderItem) == 72, "BinauralRenderItem: three pointers, two words, a byte per slot, two words: the host's staging layout");
+static_assert(sizeof(VoiceBankItem<BinauralRenderSlot>) == 64 && sizeof(BinauralRenderItem) == 72,
+              "BinauralRenderItem: three pointers, two words, a byte per slot, two words: the host's staging layout");
 // what the plan pass fixes for a sounding slot: where this callback ramps from, the slew-limited change of the delay, the gains
 // it ramps between, the gain's start and change, the HRIR indices it fades between, its index in the folded tables
 struct BinauralRenderPlan {
@@ -755,8 +751,8 @@ static_assert(sizeof(BinauralRenderPlan) == 96, "BinauralRenderPlan: twenty-four
 struct BinauralRenderBatch {
     const BinauralRenderItem* items;    // [count]
     const fs_binaural_voice* voices;    // [count][stride]
-    const uint16_t* sounding;           // [n_sounding]: row * FS_MAX_REFLECTION_VOICES + slot of every sounding slot, rows then slots ascending
-    BinauralRenderPlan* plans;          // [count][FS_MAX_REFLECTION_VOICES] scratch
+    const uint16_t* sounding;           // [n_sounding]: row * kVoiceSlots + slot of every sounding slot, rows then slots ascending
+    BinauralRenderPlan* plans;          // [count][kVoiceSlots] scratch
     unsigned* n0;                       // [count] scratch: every row's counter before this callback
     float2* folded;                     // [n_sounding][2 ears][tc] scratch: {C0[u], dC[u]}
     const float* dirs;                  // the set in force: [n_dirs][3] ...
