@@ -177,6 +177,11 @@ void free_scene(fs_context* ctx) {
     if (ctx->d_coop_levels) (void)hipFree(ctx->d_coop_levels);
     ctx->d_coop = nullptr; ctx->coop_cap = 0; ctx->d_coop16 = nullptr; ctx->coop16_cap = 0; ctx->d_coop_levels = nullptr;
     ctx->coop16_nodes = 0; ctx->coop_levels = 0;
+    for (void* v : {(void*)ctx->d_view, (void*)ctx->d_view_nrm, (void*)ctx->d_view_scan, (void*)ctx->d_view_of_node, (void*)ctx->d_view_of_leaf,
+                    (void*)ctx->d_view_bad})
+        if (v) (void)hipFree(v);
+    ctx->d_view = nullptr; ctx->d_view_nrm = nullptr; ctx->d_view_scan = nullptr; ctx->d_view_of_node = nullptr; ctx->d_view_of_leaf = nullptr;
+    ctx->d_view_bad = nullptr; ctx->view_cap_nodes = 0; ctx->view_cap_tris = 0; ctx->view_ok = false;
     if (ctx->d_tris) (void)hipFree(ctx->d_tris);
     if (ctx->d_tris48) (void)hipFree(ctx->d_tris48);
     if (ctx->d_tri_nrm) (void)hipFree(ctx->d_tri_nrm);

@@ -253,6 +253,56 @@ static int refresh_coop_nodes(fs_context* ctx, bool topology_changed) {
     return FS_OK;
 }
 
+// The 48-byte node view of the chip-filling frame kernel (fs_internal.hpp: ViewRec), called wherever refresh_coop_nodes is
+// (behind it: that one resets coop_info).  The layout follows the topology: computed behind a commit and kept across refits;
+// the contents are re-derived from the arrays as they stand in the stream.  A scene whose view does not fit the request's
+// offsets, or one of whose grid steps is no power of two, stays without a view: launch_frame takes another route for it.
+// The only wait is the commit's (a refit adds none): the fill's verdict is read once, where the stream is drained anyway.
+static int refresh_node_view(fs_context* ctx, bool topology_changed) {
+    const size_t n = ctx->bvh.nodes.size(), T = (size_t)ctx->T;
+    ctx->coop_info.view = NodeView{};
+    ctx->scene.coop_info = &ctx->coop_info;
+    if (topology_changed) ctx->view_ok = false;
+    if (n == 0 || ctx->view_off || !node_view_fits(n, T)) { ctx->view_ok = false; return FS_OK; }
+    if (!topology_changed && !ctx->view_ok) return FS_OK;
+    if (topology_changed) {
+        if (n > ctx->view_cap_nodes || T > ctx->view_cap_tris) {
+            FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            for (void* v : {(void*)ctx->d_view, (void*)ctx->d_view_nrm, (void*)ctx->d_view_scan, (void*)ctx->d_view_of_node, (void*)ctx->d_view_of_leaf})
+                if (v) (void)hipFree(v);
+            ctx->d_view = nullptr; ctx->d_view_nrm = nullptr; ctx->d_view_scan = nullptr; ctx->d_view_of_node = nullptr; ctx->d_view_of_leaf = nullptr;
+            ctx->view_cap_nodes = 0; ctx->view_cap_tris = 0;
+            const size_t cn = std::max(n, ctx->fast_cap_tris), ct = std::max(T, ctx->fast_cap_tris);   // (a fast commit keeps room for the next registration)
+            FS_HIP(ctx, hipMalloc((void**)&ctx->d_view, sizeof(ViewRec) * (cn + ct)));
+            FS_HIP(ctx, hipMalloc((void**)&ctx->d_view_nrm, sizeof(float4) * (cn + ct)));
+            FS_HIP(ctx, hipMalloc((void**)&ctx->d_view_scan, sizeof(uint32_t) * (cn + 1)));
+            FS_HIP(ctx, hipMalloc((void**)&ctx->d_view_of_node, sizeof(uint32_t) * cn));
+            FS_HIP(ctx, hipMalloc((void**)&ctx->d_view_of_leaf, sizeof(uint32_t) * std::max<size_t>(ct, 1)));
+            ctx->view_cap_nodes = cn; ctx->view_cap_tris = ct;
+        }
+        if (!ctx->d_view_bad) FS_HIP(ctx, hipMalloc((void**)&ctx->d_view_bad, sizeof(uint32_t)));
+        FS_HIP(ctx, hipMemsetAsync(ctx->d_view_bad, 0, sizeof(uint32_t), ctx->stream));
+        FS_HIP(ctx, hipMemsetAsync(ctx->d_view_nrm, 0, sizeof(float4) * (n + T), ctx->stream));   // (node slots: unused, but handed out by the snapshot)
+        launch_node_view_layout(ctx->d_nodes, (int)n, (int)T, ctx->d_view_scan, ctx->d_view_of_node, ctx->d_view_of_leaf, ctx->stream);
+    }
+    launch_node_view_fill(ctx->d_nodes, (int)n, ctx->d_tris48, ctx->d_tri_nrm, (int)T, ctx->d_view_scan, ctx->d_view_of_node, ctx->d_view_of_leaf,
+                          ctx->d_view, ctx->d_view_nrm, ctx->d_view_bad, ctx->stream);
+    FS_HIP(ctx, hipGetLastError());
+    if (topology_changed) {   // every record placed exactly once <=> the blocks hold nodes - 1 + triangles records and none was reported
+        uint32_t verdict[2] = {1u, 0u};
+        FS_HIP(ctx, hipMemcpyAsync(&verdict[0], ctx->d_view_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        FS_HIP(ctx, hipMemcpyAsync(&verdict[1], ctx->d_view_scan + n, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->view_ok = verdict[0] == 0u && (size_t)verdict[1] + 1 == n + T;
+    }
+    if (ctx->view_ok) ctx->coop_info.view = NodeView{ctx->d_view, ctx->d_view_nrm};
+    return FS_OK;
+}
+// what fs_scene_update_triangles and fs_scene_set_object_transforms hand their kernels: the view's copies follow in place
+static ViewTris view_tris(const fs_context* ctx) {
+    return ctx->view_ok ? ViewTris{ctx->d_view, ctx->d_view_nrm, ctx->d_view_of_leaf} : ViewTris{nullptr, nullptr, nullptr};
+}
+
 static int finish_commit(fs_context* ctx, size_t scene_bytes) {
     // the traversal's requests carry 32-bit byte offsets into the node and triangle records (DeviceScene, fs_internal.hpp)
     if ((uint64_t)ctx->bvh.nodes.size() * sizeof(NodeQ4) > 0xFFFFFFFFull || (uint64_t)ctx->T * sizeof(Tri48) > 0xFFFFFFFFull)
@@ -297,6 +347,7 @@ static int finish_commit(fs_context* ctx, size_t scene_bytes) {
     ctx->stats.scene_bytes = scene_bytes;
     ctx->scene.coop_info = nullptr;
     { const int cr = refresh_coop_nodes(ctx, true); if (cr) return cr; }
+    { const int vr = refresh_node_view(ctx, true); if (vr) return vr; }
     ctx->committed = true;
     return FS_OK;
 }
@@ -544,7 +595,7 @@ static int update_triangles(fs_context* ctx, int32_t first, int32_t count, const
     for (size_t i = 0; i < 9 * (size_t)count; ++i) ctx->amax = std::max(ctx->amax, std::fabs(xyz[i]));
     // the staging buffer may still be read by the previous update's kernel: same stream, so ordered
     FS_HIP(ctx, hipMemcpyAsync(ctx->d_move, xyz, sizeof(float) * 9 * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
-    launch_update_triangles(ctx->d_tris, ctx->d_tris48, ctx->d_tri_nrm, ctx->d_leaf_pos, first, count, ctx->d_move, ctx->stream);
+    launch_update_triangles(ctx->d_tris, ctx->d_tris48, ctx->d_tri_nrm, ctx->d_leaf_pos, first, count, ctx->d_move, view_tris(ctx), ctx->stream);
     FS_HIP(ctx, hipGetLastError());
     if (mv && mv->on_device)   // the device's copy of the rest pose follows
         FS_HIP(ctx, hipMemcpyAsync(mv->d_rest + 9 * (size_t)first, ctx->d_move, sizeof(float) * 9 * (size_t)count, hipMemcpyDeviceToDevice, ctx->stream));
@@ -683,7 +734,7 @@ int fs_scene_set_object_transforms(fs_context* ctx, const uint32_t* object_ids, 
     const float* dm = reinterpret_cast<const float*>(st.d);
     const uint32_t* dp = reinterpret_cast<const uint32_t*>(st.d) + 12 * n;
     launch_transform_objects(ctx->d_tris, ctx->d_tris48, ctx->d_tri_nrm, ctx->d_leaf_pos, mv->d_rest, mv->d_idx, dp, dp + (n + 1), dm,
-                             (int)n, (uint32_t)total, mv->d_amax, ctx->stream);
+                             (int)n, (uint32_t)total, mv->d_amax, view_tris(ctx), ctx->stream);
     FS_HIP(ctx, hipGetLastError());
     FS_HIP(ctx, hipEventRecord(st.ev, ctx->stream));
     st.used = true;
@@ -707,7 +758,8 @@ int fs_scene_refit(fs_context* ctx) {
     launch_refit(ctx->d_nodes, ctx->d_tris, ctx->d_node_box, ctx->bvh.level_begin.data(),
                  (int)ctx->bvh.level_begin.size() - 1, pad, ctx->stream);
     FS_HIP(ctx, hipGetLastError());
-    return refresh_coop_nodes(ctx, false);
+    { const int cr = refresh_coop_nodes(ctx, false); if (cr) return cr; }
+    return refresh_node_view(ctx, false);
 }
 
 // Debug entry (not in include/frequensee.h; tests/tree_check.py reads the committed tree through it): one array of the
@@ -716,7 +768,9 @@ int fs_scene_refit(fs_context* ctx) {
 // nothing is launched.  what: 0 header {nodes, triangles, levels, stack_need, bvh.pad, amax, coop16_nodes, coop_levels,
 // refit_pending, arrays of a fast commit, 0, 0} (12 x 4 B) | 1 NodeQ4[nodes] | 2 Tri64[T] | 3 Tri48[T] | 4 normals[T] |
 // 5 leaf_pos[T] | 6 level_begin[levels + 1] (host copy) | 7 CoopChild[4 nodes] | 8 CoopChild[16 coop16_nodes] |
-// 9 d_coop_levels [2][kMaxBuildLevels + 2] | 10 node_box[nodes][2].  cap too small: FS_ERR_SIZE_MISMATCH, *bytes = the size.
+// 9 d_coop_levels [2][kMaxBuildLevels + 2] | 10 node_box[nodes][2] | 11 ViewRec[nodes + T] (the 48-byte node view; no bytes
+// if the scene has none) | 12 its normals[nodes + T] | 13 leaf order -> view record [T].  cap too small: FS_ERR_SIZE_MISMATCH,
+// *bytes = the size.
 __attribute__((visibility("default"))) int fs_debug_scene_snapshot(fs_context* ctx, int32_t what, void* out, size_t cap, size_t* bytes) {
     if (!ctx || !bytes) return FS_ERR_INVALID_ARGUMENT;
     *bytes = 0;
@@ -748,6 +802,9 @@ __attribute__((visibility("default"))) int fs_debug_scene_snapshot(fs_context* c
         case 8: src = ctx->d_coop16; need = 16 * (size_t)ctx->coop16_nodes * sizeof(CoopChild); break;
         case 9: src = ctx->d_coop_levels; need = ctx->d_coop_levels ? 2 * (size_t)(kMaxBuildLevels + 2) * sizeof(int32_t) : 0; break;
         case 10: src = ctx->d_node_box; need = 2 * nodes * sizeof(float4); break;
+        case 11: src = ctx->d_view; need = ctx->view_ok ? (nodes + T) * sizeof(ViewRec) : 0; break;
+        case 12: src = ctx->d_view_nrm; need = ctx->view_ok ? (nodes + T) * sizeof(float4) : 0; break;
+        case 13: src = ctx->d_view_of_leaf; need = ctx->view_ok ? T * sizeof(uint32_t) : 0; break;
         default: return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_debug_scene_snapshot: no such array");
     }
     *bytes = need;
@@ -758,6 +815,24 @@ __attribute__((visibility("default"))) int fs_debug_scene_snapshot(fs_context* c
     else std::memcpy(out, src, need);
     return FS_OK;
 }
+
+// Debug entry (not in include/frequensee.h): on = 0 — the committed scene loses its 48-byte node view and later commits build
+// none, so that fused frames take the route of a scene that cannot have one (launch_frame, fs_frame.hip); on = 1 — commits
+// build it again (the scene in place gets it back with its next commit).
+__attribute__((visibility("default"))) int fs_debug_set_node_view(fs_context* ctx, int32_t on) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
+    ctx->view_off = on == 0;
+    if (ctx->view_off) { ctx->view_ok = false; ctx->coop_info.view = NodeView{}; }
+    return FS_OK;
+}
+
+// Debug entry: the view's size rule (fs_internal.hpp: node_view_fits), for the tests of its boundary.  Host arithmetic only.
+__attribute__((visibility("default"))) int fs_debug_node_view_fits(uint64_t nodes, uint64_t triangles) {
+    return node_view_fits(nodes, triangles) ? 1 : 0;
+}
+static_assert(node_view_fits(1, 0xFFFFFFFFull / sizeof(ViewRec) - 1) && !node_view_fits(1, 0xFFFFFFFFull / sizeof(ViewRec)),
+              "the last record's byte offset must fit 32 bits");
 
 int fs_scene_set_objects(fs_context* ctx, const uint32_t* object_id, int32_t T) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;

@@ -327,6 +327,15 @@ struct fs_context {
     size_t coop16_cap = 0;
     int32_t* d_coop_levels = nullptr; // [2][kMaxBuildLevels + 2]: level_begin | dense index of every even level (uploaded at commit)
     int coop16_nodes = 0, coop_levels = 0;
+    // the 48-byte node view of the chip-filling frame kernel (fs_internal.hpp: ViewRec), rebuilt behind every commit and refit
+    ViewRec* d_view = nullptr;        // [nodes + triangles] node and triangle records, every node's children one block
+    float4* d_view_nrm = nullptr;     // [nodes + triangles] unit normals of the triangle records
+    uint32_t* d_view_scan = nullptr;  // [nodes + 1] records before each node's child block, less the root's (the layout: topology only)
+    uint32_t* d_view_of_node = nullptr, *d_view_of_leaf = nullptr;   // node index / leaf-order position -> record
+    uint32_t* d_view_bad = nullptr;   // raised by the fill: the tree cannot be restated (a step that is no power of two)
+    size_t view_cap_nodes = 0, view_cap_tris = 0;
+    bool view_ok = false;             // the committed scene has a view
+    bool view_off = false;            // fs_debug_set_node_view(0): commits leave the scene without one (tests of the fallback)
     CoopInfo coop_info;               // what DeviceScene.coop_info points at
     float stage_margin = 1.3f;        // KParams.stage_margin
     DeepStore deep;                   // HBM spill area of the bounded LDS traversal stacks (DeviceScene.deep)

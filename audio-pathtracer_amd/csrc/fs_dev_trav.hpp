@@ -18,11 +18,12 @@ namespace {
 
 struct Trav {
     int cur;        // next node: >= 0 inner index, < 0 leaf code (~cur = first*4 + count-1), kDone = none
+                    // (FS_NODE_VIEW: a view reference turned right by 3 — leaf bit | count-1 | record number — see view_cursor)
     int sp;         // stack top (entries live in [sb, sp))
     int sb;         // stack bottom: 0 unless entries were given away from the bottom (wave work sharing)
     int tri_i, tri_n;  // pending triangles [tri_i, tri_n) of the current leaf
     float t;        // closest hit so far (init: tmax)
-    int leaf_index; // hit triangle (leaf order), -1 = none
+    int leaf_index; // hit triangle (leaf order; FS_NODE_VIEW: its record number in the view), -1 = none
     uint32_t id;    // its input index (tie-break key)
     uint32_t nv, nt;   // COUNT instantiations only (fs_set_profiling level 3): node records / triangle records this lane fetched
     uint32_t ni, nl, nd;   // ... and (one lane per wave) node-request instructions, their active lanes, the distinct records among those
@@ -64,7 +65,20 @@ __device__ __forceinline__ int lanes_below(unsigned long long m) {
 // sinks the first arithmetic on the loaded words into the block of the loads, i.e. waits for one record before it
 // requests the other: 448 lane-loads per wave iteration for 207 useful ones.)
 typedef float v4f __attribute__((ext_vector_type(4)));
+// FS_NODE_VIEW (defined by the narrow flavours of the fused frame kernel, fs_frame.hip): sc.nodes and sc.tris are ONE array
+// of 48-byte records, the node view of fs_internal.hpp (ViewRec) — a node takes three requests instead of four and its
+// child references are  cb8 + the slot's byte  (record x 8 | leaf bit 2 | count - 1), formed behind the sort.  On the stack,
+// in the donation boxes and in the deep store a reference stays that opaque word; the cursor T.cur holds it turned right by
+// 3, so that the leaf bit is the sign and every mask of the step is the one compare it is without the view: an inner
+// record number >= 0, a leaf (bit 31 | count - 1 at 30:29 | first record) < 0.  kDone (bit 31 alone) would be a one-triangle
+// leaf at record 0, which is the root: never a reference.
+#ifdef FS_NODE_VIEW
+struct NodeRegs { v4f q0, q1, q2; };
+__device__ __forceinline__ int view_cursor(int ref) { return (int)__builtin_rotateright32((uint32_t)ref, 3u); }
+#else
 struct NodeRegs { v4f q0, q1, q2, q3; };
+__device__ __forceinline__ int view_cursor(int ref) { return ref; }
+#endif
 struct TriRegs { v4f a, b, c; };
 
 // ---- bounded LDS stack with a deep store in HBM (DeviceScene.deep, fs_internal.hpp) ---------------------------
@@ -126,15 +140,20 @@ __device__ __forceinline__ void trav_maintain(const DeviceScene& sc, Trav& T, in
 }
 // next pending entry into T.cur (kDone: none left)
 __device__ __forceinline__ void trav_pop(const DeviceScene& sc, Trav& T, int* stack) {
-    if (T.sp > T.sb) { --T.sp; T.cur = stack[T.sp * kBlock]; }
+    if (T.sp > T.sb) { --T.sp; T.cur = view_cursor(stack[T.sp * kBlock]); }
     else T.cur = kDone;
 }
 
 __device__ __forceinline__ void trav_settle(const DeviceScene& sc, Trav& T, int* stack) {
     if (T.tri_i >= T.tri_n && T.cur < 0 && T.cur != kDone) {
+#ifdef FS_NODE_VIEW
+        T.tri_i = T.cur & 0x1FFFFFFF;
+        T.tri_n = T.tri_i + ((T.cur >> 29) & 3) + 1;
+#else
         const int code = ~T.cur;
         T.tri_i = code >> 2;
         T.tri_n = T.tri_i + (code & 3) + 1;
+#endif
         trav_pop(sc, T, stack);
     }
 }
@@ -152,6 +171,8 @@ __device__ __forceinline__ void trav_settle(const DeviceScene& sc, Trav& T, int*
 // instruction's own offset — `global_load_dwordx4 vdst, voff, s[base:base+1] offset:n`.  No 64-bit vector arithmetic
 // and no address pairs in a kernel held to 128 registers; fs_scene_commit refuses a scene whose record arrays exceed
 // 4 GiB (DeviceScene, fs_internal.hpp).
+// FS_NODE_VIEW: three node loads instead of four, both groups from the one array of 48-byte records (sc.nodes == sc.tris there),
+// both offsets (record x 3) << 4.
 // (No cache-policy bits on these requests: measured, none helps — DESIGN.md section 5.)
 __device__ __forceinline__ void trav_issue(const DeviceScene& sc, Trav& T, NodeRegs& N, TriRegs& X) {
     // (the compare is made on the register: what the compiler knows of tri_i < tri_n from the branches behind it is a
@@ -161,8 +182,14 @@ __device__ __forceinline__ void trav_issue(const DeviceScene& sc, Trav& T, NodeR
     const int ti = T.tri_i;
     const unsigned long long mn = lane_mask(T.cur >= 0), mt = lane_mask(ti < T.tri_n);   // subsets of EXEC
     // (offsets of lanes that want nothing are never dereferenced)
-    static_assert(sizeof(NodeQ4) == 64 && sizeof(Tri48) == 48, "the request's byte offsets");
+    static_assert(sizeof(NodeQ4) == 64 && sizeof(Tri48) == 48 && sizeof(ViewRec) == 48, "the request's byte offsets");
+#ifdef FS_NODE_VIEW
+    uint32_t no = ((uint32_t)T.cur << 1) + (uint32_t)T.cur;   // both offsets (record x 3) << 4, see `to`
+    asm("" : "+v"(no));
+    no <<= 4;
+#else
     const uint32_t no = (uint32_t)T.cur << 6;
+#endif
     uint32_t to = ((uint32_t)ti << 1) + (uint32_t)ti;   // * 48 as a shift-add and a shift (left alone the compiler
     asm("" : "+v"(to));                                 //   makes it one quarter-rate v_mul_lo_u32)
     to <<= 4;
@@ -172,7 +199,9 @@ __device__ __forceinline__ void trav_issue(const DeviceScene& sc, Trav& T, NodeR
                  "global_load_dwordx4 %[q0], %[no], %[nb]\n\t"
                  "global_load_dwordx4 %[q1], %[no], %[nb] offset:16\n\t"
                  "global_load_dwordx4 %[q2], %[no], %[nb] offset:32\n\t"
+#ifndef FS_NODE_VIEW
                  "global_load_dwordx4 %[q3], %[no], %[nb] offset:48\n\t"
+#endif
                  "s_mov_b64 exec, %[mt]\n\t"
                  "s_cbranch_execz 1f\n\t"      // one wave step in four has no lane with a pending triangle
                  "global_load_dwordx4 %[ta], %[to], %[tb_]\n\t"
@@ -180,14 +209,21 @@ __device__ __forceinline__ void trav_issue(const DeviceScene& sc, Trav& T, NodeR
                  "global_load_dwordx4 %[tc], %[to], %[tb_] offset:32\n"
                  "1:\n\t"
                  "s_mov_b64 exec, %[sv]"
-                 : [q0] "+&v"(N.q0), [q1] "+&v"(N.q1), [q2] "+&v"(N.q2), [q3] "+&v"(N.q3),
+                 : [q0] "+&v"(N.q0), [q1] "+&v"(N.q1), [q2] "+&v"(N.q2),
+#ifndef FS_NODE_VIEW
+                   [q3] "+&v"(N.q3),
+#endif
                    [ta] "+&v"(X.a), [tb] "+&v"(X.b), [tc] "+&v"(X.c), [sv] "=&s"(sv)
                  : [no] "v"(no), [to] "v"(to), [nb] "s"(sc.nodes), [tb_] "s"(sc.tris), [mn] "s"(mn), [mt] "s"(mt)
                  : "memory");
 }
 
 __device__ __forceinline__ void trav_wait(NodeRegs& N, TriRegs& X) {
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(N.q0), "+v"(N.q1), "+v"(N.q2), "+v"(N.q3), "+v"(X.a), "+v"(X.b), "+v"(X.c));
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(N.q0), "+v"(N.q1), "+v"(N.q2),
+#ifndef FS_NODE_VIEW
+                                        "+v"(N.q3),
+#endif
+                                        "+v"(X.a), "+v"(X.b), "+v"(X.c));
 }
 
 // the triangle that arrived with this step (leaf-order index `tested`): Moeller-Trumbore, closest-hit update as selects
@@ -244,17 +280,43 @@ __device__ __forceinline__ float min_canonical(float a, float b) {
 }
 
 // the lane's inner node (T.cur >= 0): 4 child boxes, near-first order, far children to the stack, next node
+#ifdef FS_NODE_VIEW
+// grid step K of a view record: exponent byte K of E moved to the float's exponent, (E >> 8 K & 0xFF) << 23, as ONE
+// instruction (the byte select is the operand's own; written as a shift and a mask it is two per step)
+template <int K>
+__device__ __forceinline__ float view_step(uint32_t E) {
+    static_assert(K >= 0 && K < 3, "three steps");
+    float out;
+    if (K == 0) asm("v_lshlrev_b32_sdwa %0, 23, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(out) : "v"(E));
+    else if (K == 1) asm("v_lshlrev_b32_sdwa %0, 23, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(out) : "v"(E));
+    else asm("v_lshlrev_b32_sdwa %0, 23, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(out) : "v"(E));
+    return out;
+}
+#endif
 __device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray& r, const RaySigns& sg, Trav& T, int* stack,
                                                const NodeRegs& N) {
     const float4 q0 = make_float4(N.q0.x, N.q0.y, N.q0.z, N.q0.w), q1 = make_float4(N.q1.x, N.q1.y, N.q1.z, N.q1.w),
-                 q2 = make_float4(N.q2.x, N.q2.y, N.q2.z, N.q2.w), q3 = make_float4(N.q3.x, N.q3.y, N.q3.z, N.q3.w);
+                 q2 = make_float4(N.q2.x, N.q2.y, N.q2.z, N.q2.w);
     // ---- 4-wide node, child boxes on the node's 8-bit grid: plane distance = fma(q, step*inv, (origin-o)*inv)
+#ifdef FS_NODE_VIEW
+    // the view's record (fs_internal.hpp: ViewRec): origin, lox | loy, loz, hix, hiy | hiz, G, cb8, E.  The steps come back
+    // from their exponent bytes bit for bit; everything from here to the keys is the arithmetic of the NodeQ4 path.
+    const uint32_t E = __float_as_uint(q2.w), G = __float_as_uint(q2.y), cb8 = __float_as_uint(q2.z);
+    const float sx = view_step<0>(E) * r.ix, sy = view_step<1>(E) * r.iy, sz = view_step<2>(E) * r.iz;
+#else
+    const float4 q3 = make_float4(N.q3.x, N.q3.y, N.q3.z, N.q3.w);
     const float sx = q0.w * r.ix, sy = q2.z * r.iy, sz = q2.w * r.iz;   // grid step (a power of two) / direction
+#endif
     const float bx = fmaf(q0.x, r.ix, r.nox);
     const float by = fmaf(q0.y, r.iy, r.noy);
     const float bz = fmaf(q0.z, r.iz, r.noz);
+#ifdef FS_NODE_VIEW
+    const uint32_t lox = __float_as_uint(q0.w), loy = __float_as_uint(q1.x), loz = __float_as_uint(q1.y);
+    const uint32_t hix = __float_as_uint(q1.z), hiy = __float_as_uint(q1.w), hiz = __float_as_uint(q2.x);
+#else
     const uint32_t lox = __float_as_uint(q1.x), loy = __float_as_uint(q1.y), loz = __float_as_uint(q1.z);
     const uint32_t hix = __float_as_uint(q1.w), hiy = __float_as_uint(q2.x), hiz = __float_as_uint(q2.y);
+#endif
     // the ray's direction signs pick the entry / exit plane words once per node
     const uint32_t nxw = lane_select(sg.x, hix, lox), fxw = lane_select(sg.x, lox, hix);
     const uint32_t nyw = lane_select(sg.y, hiy, loy), fyw = lane_select(sg.y, loy, hiy);
@@ -273,6 +335,21 @@ __device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray&
         const bool h = tn <= tf;
         // entry distance (>= 0, so its bits order like an integer) with the slot in the low 2 bits; a missed child
         // sorts behind every hit one (kMissKey | slot)
+#ifdef FS_NODE_VIEW
+        // ... with the slot's reference byte in the low 8 bits instead (one v_perm_b32: bytes 3 - 1 of the distance, byte c of
+        // G): the reference then comes OUT of the sort — cb8 + the sorted key's low byte — and nothing is dragged through it.
+        // The order of near-equal children may differ from the NodeQ4 path's; a closest hit does not depend on the order of
+        // the visits and an any-hit answer is a boolean.
+        key[c] = h ? __builtin_amdgcn_perm(__float_as_uint(tn), G, 0x07060500u + (uint32_t)c) : 0xFFFFFFFFu;
+    }
+    // the same 5-comparator network as below, on the keys alone
+#define FS_KEYSWAP(a, b) { const uint32_t lo_ = min(key[a], key[b]), hi_ = max(key[a], key[b]); key[a] = lo_; key[b] = hi_; }
+    FS_KEYSWAP(0, 1) FS_KEYSWAP(2, 3) FS_KEYSWAP(0, 2) FS_KEYSWAP(1, 3) FS_KEYSWAP(1, 2)
+#undef FS_KEYSWAP
+    const int ref0 = (int)(cb8 + (key[0] & 0xFFu)), ref1 = (int)(cb8 + (key[1] & 0xFFu)), ref2 = (int)(cb8 + (key[2] & 0xFFu)),
+              ref3 = (int)(cb8 + (key[3] & 0xFFu));
+    constexpr uint32_t kMiss = kMissKeyView;
+#else
         key[c] = h ? ((__float_as_uint(tn) & ~3u) | (uint32_t)c) : (kMissKey | (uint32_t)c);
     }
     int ref0 = __float_as_int(q3.x), ref1 = __float_as_int(q3.y), ref2 = __float_as_int(q3.z),
@@ -287,8 +364,10 @@ __device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray&
                          ref##a = ra_; ref##b = rb_; }
     FS_CSWAP(0, 1) FS_CSWAP(2, 3) FS_CSWAP(0, 2) FS_CSWAP(1, 3) FS_CSWAP(1, 2)
 #undef FS_CSWAP
+    constexpr uint32_t kMiss = kMissKey;
+#endif
     // the number of children hit, read off the sorted keys: at least k + 1 <=> key[k] is a hit
-    const bool h1 = key[0] < kMissKey, h2 = key[1] < kMissKey, h3 = key[2] < kMissKey, h4 = key[3] < kMissKey;
+    const bool h1 = key[0] < kMiss, h2 = key[1] < kMiss, h3 = key[2] < kMiss, h4 = key[3] < kMiss;
 #ifdef FS_TRAV_STATS
     atomicAdd(&g_trav_stats[5 + (h2 ? 2 : (h1 ? 1 : 0))], 1ull);   // [5] visits with no child hit, [6] one, [7] two or more
 #endif
@@ -304,7 +383,7 @@ __device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray&
     stack[p2 * kBlock] = ref2;
     stack[p1 * kBlock] = ref1;
     T.sp = p1 + (h2 ? 1 : 0);
-    if (h1) T.cur = ref0;
+    if (h1) T.cur = view_cursor(ref0);
     else trav_pop(sc, T, stack);
 }
 
@@ -366,8 +445,11 @@ __device__ __forceinline__ void trav_advance(const DeviceScene& sc, const Ray& r
 // Before a traversal returns, every record it has requested must have landed: the compiler knows nothing of loads in
 // flight and would hand their destination registers to other values (an any-hit query ends with requests outstanding).
 __device__ __forceinline__ void trav_drain(NodeRegs& N, TriRegs& X, TriRegs& Y) {
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(N.q0), "+v"(N.q1), "+v"(N.q2), "+v"(N.q3), "+v"(X.a), "+v"(X.b), "+v"(X.c),
-                                        "+v"(Y.a), "+v"(Y.b), "+v"(Y.c));
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(N.q0), "+v"(N.q1), "+v"(N.q2),
+#ifndef FS_NODE_VIEW
+                                        "+v"(N.q3),
+#endif
+                                        "+v"(X.a), "+v"(X.b), "+v"(X.c), "+v"(Y.a), "+v"(Y.b), "+v"(Y.c));
 }
 
 // one ray per lane without work sharing (tests, tools, diagnostic builds); returns the number of steps taken
@@ -550,7 +632,7 @@ __device__ __forceinline__ bool trav_shared(const DeviceScene& sc, bool has_ray,
                         wr.nox = -(wr.ox * wr.ix); wr.noy = -(wr.oy * wr.iy); wr.noz = -(wr.oz * wr.iz);   // as make_ray
                     }
                     if (IGN) wign = A.rign[owner];
-                    T.cur = e; T.sp = 0; T.sb = 0; T.tri_i = 0; T.tri_n = 0;
+                    T.cur = view_cursor(e); T.sp = 0; T.sb = 0; T.tri_i = 0; T.tri_n = 0;
                     T.t = canonical_bound(bound); T.leaf_index = -1; T.id = 0xFFFFFFFFu;
                     trav_deep_reset(sc, stack);   // (an any-hit query that ended early may have left entries there)
                     trav_settle(sc, T, stack);

@@ -31,6 +31,12 @@
 #else
 #define FS_LAUNCH_FRAME launch_frame_narrow
 #endif
+// The narrow flavours walk the 48-byte node view (fs_internal.hpp: ViewRec; fs_dev_trav.hpp): three node requests per visit
+// instead of four, child references out of the sort instead of through it.  launch_frame hands them a scene whose nodes,
+// tris and tri_nrm point at the view.
+#ifndef FS_FRAME_WIDE
+#define FS_NODE_VIEW 1
+#endif
 #include "fs_dev_walk.hpp"
 #include "fs_dev_coop.hpp"
 #include "fs_dev_connect.hpp"
@@ -250,13 +256,25 @@ bool launch_frame(int B, const DeviceScene& sc, const FrameParts& f, hipStream_t
     if (dbg) std::fprintf(stderr, "[launch_frame] blocks %u stack_worst %d rows %d limit %d\n", blocks, sc.stack_worst, sc.stack_rows, sc.stack_limit);
     bool dense = f.num_walk == 0;
     for (int i = 0; i < f.num_walk; ++i) dense = dense || !(f.walk[i].wl.rays_per_wave > 0 && f.walk[i].wl.rays_per_wave < 64);
-    if (sc.stack_worst > 0 && (blocks < kFrameNarrowFromBlocks || !dense)) {
+    // The narrow flavour walks the 48-byte node view (FS_NODE_VIEW below the top of this file; fs_internal.hpp: ViewRec).  A
+    // scene without one — too large for the view's offsets, a grid step that is no power of two — takes the wide flavour where
+    // its worst-case stack fits LDS, and otherwise leaves the launch to the callers' unfused passes: the same results, at
+    // another rate.
+    const NodeView view = sc.coop_info ? sc.coop_info->view : NodeView{};
+    const bool no_view = !view.rec && sc.num_nodes > 0;   // (an empty scene requests no record at all)
+    if (sc.stack_worst > 0 && (blocks < kFrameNarrowFromBlocks || !dense || no_view)) {
         DeviceScene w = sc;
         w.stack_rows = sc.stack_worst; w.stack_limit = sc.stack_worst; w.stack_attn = 0x7FFFFFFFu;
         w.deep = nullptr; w.deep_lanes = 0; w.deep_owner = nullptr;
         return wide(B, w, f, s, nullptr);
     }
-    return narrow(B, sc, f, s, nullptr);
+    if (no_view) return false;
+    if (!view.rec) return narrow(B, sc, f, s, nullptr);
+    DeviceScene v = sc;   // record 0 of the view is the root; triangle indices are record numbers from here on
+    v.nodes = reinterpret_cast<const NodeQ4*>(view.rec);
+    v.tris = reinterpret_cast<const Tri48*>(view.rec);
+    v.tri_nrm = view.nrm;
+    return narrow(B, v, f, s, nullptr);
 }
 #endif
 

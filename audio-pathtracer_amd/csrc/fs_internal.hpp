@@ -80,7 +80,31 @@ struct CoopView {
     int32_t lds_nodes, nodes;
     int16_t wshift, stack_need;
 };
-struct CoopInfo { CoopView wide16{}, wide4{}; };
+// The chip-filling flavour of the fused frame kernel walks a derived VIEW of the tree instead (fs_refit.hip: the view
+// kernels; fs_dev_trav.hpp: FS_NODE_VIEW): inner nodes and triangle records together in ONE array of 48-byte records, every
+// node's children — its inner children's node records and each leaf child's 1 - 4 triangle records, in slot order — one
+// consecutive block, the root record 0.  A node record is three 16-byte quarters,
+//   q0 = (origin.x, origin.y, origin.z, lox)   q1 = (loy, loz, hix, hiy)   q2 = (hiz, G, cb8, E)
+// the six plane words of its NodeQ4 verbatim; E = the float exponent bytes of the three grid steps (sx | sy << 8 | sz << 16:
+// the steps are powers of two, as_float(byte << 23) is the step bit for bit); cb8 = 8 x the record number of the first child
+// record; G = one byte per slot, 8 x (the slot's first record relative to the child block, <= 12) + 4 x leaf + (triangles - 1).
+// A reference is cb8 + the slot's byte: record number x 8 | leaf bit | count - 1.  The normals of the triangle records lie
+// in a parallel float4 array indexed by record number (node slots unused).  Rebuilt on the device behind every commit and
+// refit like CoopChild; NodeQ4 / Tri48 stay the tree format of everything else.
+struct alignas(16) ViewRec {
+    float4 q0, q1, q2;
+};
+static_assert(sizeof(ViewRec) == sizeof(Tri48), "the view holds node and triangle records at one stride");
+// The size rule of the view: the request carries record x 48 as a 32-bit byte offset, and a reference (record x 8 + 7 at
+// most) must stay below 2^30 (fs_dev_trav.hpp keeps the leaf bit in the sign after a rotate by 3).
+constexpr bool node_view_fits(uint64_t nodes, uint64_t tris) {
+    return (nodes + tris) * sizeof(ViewRec) <= 0xFFFFFFFFull && nodes + tris <= (1ull << 27);
+}
+struct NodeView {           // host bookkeeping; rec == null: the scene has no view (too large, a step that is no power of two)
+    const ViewRec* rec = nullptr;      // [nodes + triangles]
+    const float4* nrm = nullptr;       // [nodes + triangles]
+};
+struct CoopInfo { CoopView wide16{}, wide4{}; NodeView view{}; };
 constexpr float kCoopMaxCoordinate = 16384.0f;   // largest |coordinate| (UE units) of a scene whose small frames use the cooperative traversal (fp16 ulp 8 there)
 
 // Per-lane traversal stack in LDS: DeviceScene.stack_rows rows of kBlock ints, sized at run time from the committed
@@ -147,7 +171,7 @@ struct DeviceScene {
                               //   lane to trav_maintain at the top of a step (fs_dev_trav.hpp)
     int32_t stack_worst;      // rows of a stack that cannot overflow (worst case + 1) if a workgroup may have that much LDS, else
                               //   0: what the wide flavour of the frame kernel runs with (fs_frame.hip)
-    const struct CoopInfo* coop_info;   // host bookkeeping: the cooperative traversal's node arrays (CoopView below); unused on the device
+    const struct CoopInfo* coop_info;   // host bookkeeping: the cooperative traversal's node arrays (CoopView above) and the 48-byte node view; unused on the device
     int32_t* deep;
     uint32_t deep_lanes;
     struct DeepStore* deep_owner;   // host bookkeeping (grows the store when a launch has more lanes); unused on the device
@@ -787,20 +811,29 @@ void launch_oneshot_reduce(const OneShotView& v, void* buffer, int words, bool u
 // row f4 (fs_refit.hip): moving geometry without a rebuild.  xyz = `count` new triangles [count][3][3] on the
 // device, written to the leaf-order records through leaf_pos; then one refit launch per tree level, deepest
 // first (node_box = scratch [num_nodes][2] float4 holding each node's fp32 bounds).
+// view: the 48-byte node view's copies of the records follow (rec / nrm by record number, rec_of_leaf: leaf order -> record), or all null
+struct ViewTris { ViewRec* rec; float4* nrm; const uint32_t* rec_of_leaf; };
 void launch_update_triangles(Tri64* tris, Tri48* packed, float4* nrm, const uint32_t* leaf_pos, int first, int count,
-                             const float* xyz, hipStream_t s);
+                             const float* xyz, const ViewTris& view, hipStream_t s);
 // fs_scene_set_object_transforms: every triangle of the n listed objects placed at its matrix applied to its rest position
 // (rest [T][9] input order; csr / start: the objects' lists of input indices; prefix [n + 1]: running triangle counts;
 // *amax_bits: bit pattern of the largest |coordinate| written, kept up by atomicMax)
 void launch_transform_objects(Tri64* tris, Tri48* packed, float4* nrm, const uint32_t* leaf_pos, const float* rest,
                               const uint32_t* csr, const uint32_t* prefix, const uint32_t* start, const float* m, int n,
-                              uint32_t total, uint32_t* amax_bits, hipStream_t s);
+                              uint32_t total, uint32_t* amax_bits, const ViewTris& view, hipStream_t s);
 void launch_pack_triangles(const Tri64* tris, int count, Tri48* packed, float4* nrm, hipStream_t s);
 void launch_refit(NodeQ4* nodes, const Tri64* tris, float4* node_box, const int32_t* level_begin, int levels, float pad,
                   hipStream_t s);
 void launch_coop_nodes(const NodeQ4* nodes, int n, CoopChild* out, hipStream_t s);   // per-child records of the current 4-wide nodes
 // ... folded two levels at a time into 16-wide nodes in the dense order of the even levels (fs_refit.hip)
 void launch_coop16(const CoopChild* in, const int32_t* level_begin_dev, const int32_t* dense_dev, int levels, int n16, CoopChild* out, hipStream_t s);
+// The 48-byte node view (ViewRec above).  launch_node_view_layout (topology only: behind a commit): block[n] = records of
+// node n's child block -> exclusive scan -> rec_of_node / rec_of_leaf.  launch_node_view_fill (every commit and refit): the
+// records from nodes / tris48 / nrm as they stand in the stream; *bad is raised if a grid step is no encodable power of two.
+// block: [nodes + 1] scratch that holds the scan afterwards (kept across refits).
+void launch_node_view_layout(const NodeQ4* nodes, int n, int T, uint32_t* block, uint32_t* rec_of_node, uint32_t* rec_of_leaf, hipStream_t s);
+void launch_node_view_fill(const NodeQ4* nodes, int n, const Tri48* tris, const float4* nrm, int T, const uint32_t* block,
+                           const uint32_t* rec_of_node, const uint32_t* rec_of_leaf, ViewRec* rec, float4* rec_nrm, uint32_t* bad, hipStream_t s);
 // fs_build.hip: the acceleration structure built on the device (Morton codes, radix sort, Karras' binary radix tree,
 // breadth-first collapse to 4-wide nodes); launch_refit then derives the quantised boxes.  DeviceBuildInfo is what the
 // host reads back: levels < 0 = the tree is deeper than kMaxBuildLevels or ran out of node space (use the host build).

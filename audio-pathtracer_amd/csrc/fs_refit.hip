@@ -9,6 +9,7 @@
 // vertices: the bytes may differ from a host build's, tests/tree_check.py), so they equal a fresh build's bit for bit.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "fs_internal.hpp"
@@ -20,8 +21,9 @@ constexpr int kRefitBlock = 256;
 
 // new vertex positions p[9] -> Tri64 {v0, e1, e2, unit normal} at leaf-order position pos; material, input index and
 // actor id are kept.  Same fp32 operation order as the host build (fs_bvh.cpp) — the normal is part of the hit-normal spec.
+// view: the 48-byte node view's copy of the record follows (fs_internal.hpp: ViewRec), if the scene has one
 __device__ __forceinline__ void write_record(Tri64* __restrict__ tris, Tri48* __restrict__ packed, float4* __restrict__ nrm,
-                                             uint32_t pos, const float* p) {
+                                             uint32_t pos, const float* p, const ViewTris& view) {
     Tri64& r = tris[pos];
     const float e1x = p[3] - p[0], e1y = p[4] - p[1], e1z = p[5] - p[2];
     const float e2x = p[6] - p[0], e2y = p[7] - p[1], e2z = p[8] - p[2];
@@ -36,17 +38,22 @@ __device__ __forceinline__ void write_record(Tri64* __restrict__ tris, Tri48* __
     r.d = make_float4(nx * inv, ny * inv, nz * inv, 0.f);
     packed[pos] = Tri48{r.a, r.b, r.c};
     nrm[pos] = r.d;
+    if (view.rec) {
+        const uint32_t v = view.rec_of_leaf[pos];
+        view.rec[v] = ViewRec{r.a, r.b, r.c};
+        view.nrm[v] = r.d;
+    }
 }
 
 __global__ __launch_bounds__(kRefitBlock) void update_tris_kernel(Tri64* __restrict__ tris, Tri48* __restrict__ packed,
                                                                   float4* __restrict__ nrm,
                                                                   const uint32_t* __restrict__ leaf_pos, int first,
-                                                                  int count, const float* __restrict__ xyz) {
+                                                                  int count, const float* __restrict__ xyz, ViewTris view) {
     const int i = blockIdx.x * kRefitBlock + threadIdx.x;
     if (i >= count) return;
     const float* p = xyz + 9 * (size_t)i;
     const uint32_t pos = leaf_pos[first + i];
-    write_record(tris, packed, nrm, pos, p);
+    write_record(tris, packed, nrm, pos, p, view);
 }
 
 // fs_scene_set_object_transforms: one thread per (listed object, triangle of it) pair, all objects of the call in one
@@ -63,7 +70,7 @@ __global__ __launch_bounds__(kRefitBlock) void transform_objects_kernel(Tri64* _
                                                                         const uint32_t* __restrict__ prefix,
                                                                         const uint32_t* __restrict__ start,
                                                                         const float* __restrict__ m, int n, uint32_t total,
-                                                                        uint32_t* __restrict__ amax_bits) {
+                                                                        uint32_t* __restrict__ amax_bits, ViewTris view) {
     const uint32_t g = blockIdx.x * (uint32_t)kRefitBlock + threadIdx.x;
     float mx = 0.f;
     if (g < total) {
@@ -84,7 +91,7 @@ __global__ __launch_bounds__(kRefitBlock) void transform_objects_kernel(Tri64* _
                 mx = fmaxf(mx, fabsf(w));
             }
         }
-        write_record(tris, packed, nrm, leaf_pos[tri], p);
+        write_record(tris, packed, nrm, leaf_pos[tri], p, view);
     }
     for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
     if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(amax_bits, __float_as_uint(mx));
@@ -265,7 +272,124 @@ __global__ __launch_bounds__(kRefitBlock) void coop16_kernel(const CoopChild* __
     out[i] = r;
 }
 
+// ---- the chip-filling frame kernel's view of the tree (fs_internal.hpp: ViewRec) ------------------------------------
+// a used slot as the refit knows it (an empty one carries lo = 255 > hi = 0) and the records it takes in the child block
+__device__ __forceinline__ uint32_t view_slot_records(const NodeQ4& q, int c) {
+    if (((q.lox >> (8 * c)) & 0xFFu) > ((q.hix >> (8 * c)) & 0xFFu)) return 0u;
+    return q.child[c] >= 0 ? 1u : (uint32_t)((~q.child[c]) & 3) + 1u;
+}
+__global__ __launch_bounds__(kRefitBlock) void view_block_kernel(const NodeQ4* __restrict__ nodes, int n, uint32_t* __restrict__ block) {
+    const int i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= n) return;
+    const NodeQ4 q = nodes[i];
+    uint32_t sum = 0;
+    for (int c = 0; c < 4; ++c) sum += view_slot_records(q, c);
+    block[i] = sum;
+}
+// block[0, n) -> its exclusive scan, block[n] = the total.  One workgroup: every thread sums a run of consecutive entries,
+// the runs' sums are scanned in LDS.  (Behind a commit only: the layout follows the topology.)
+constexpr int kViewScanBlock = 1024;
+__global__ __launch_bounds__(kViewScanBlock) void view_scan_kernel(uint32_t* __restrict__ block, int n) {
+    __shared__ uint32_t part[kViewScanBlock];
+    const int t = threadIdx.x, per = (n + kViewScanBlock - 1) / kViewScanBlock;
+    const int b = min(n, t * per), e = min(n, b + per);
+    uint32_t sum = 0;
+    for (int i = b; i < e; ++i) sum += block[i];
+    part[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < kViewScanBlock; d <<= 1) {
+        const uint32_t add = t >= d ? part[t - d] : 0u;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - sum;
+    for (int i = b; i < e; ++i) { const uint32_t v = block[i]; block[i] = run; run += v; }
+    if (t == kViewScanBlock - 1) block[n] = part[t];
+}
+// parents place their children: node n's child block begins at record 1 + scan[n] (the root is record 0)
+__global__ __launch_bounds__(kRefitBlock) void view_place_kernel(const NodeQ4* __restrict__ nodes, int n, const uint32_t* __restrict__ scan,
+                                                                 uint32_t* __restrict__ rec_of_node, uint32_t* __restrict__ rec_of_leaf, int T) {
+    const int i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= n) return;
+    if (i == 0) rec_of_node[0] = 0u;   // (links outside the arrays are left alone: their records stay unplaced, which the fill reports)
+    const NodeQ4 q = nodes[i];
+    uint32_t at = 1u + scan[i];
+    for (int c = 0; c < 4; ++c) {
+        const uint32_t k = view_slot_records(q, c);
+        if (k == 0u) continue;
+        if (q.child[c] >= 0) { if (q.child[c] < n) rec_of_node[q.child[c]] = at; }
+        else {
+            const uint32_t first = (uint32_t)(~q.child[c]) >> 2;
+            for (uint32_t j = 0; j < k; ++j) if (first + j < (uint32_t)T) rec_of_leaf[first + j] = at + j;
+        }
+        at += k;
+    }
+}
+// one thread per node: its record from the NodeQ4 as it stands
+__global__ __launch_bounds__(kRefitBlock) void view_nodes_kernel(const NodeQ4* __restrict__ nodes, int n, const uint32_t* __restrict__ scan,
+                                                                 const uint32_t* __restrict__ rec_of_node, ViewRec* __restrict__ rec,
+                                                                 uint32_t cap, uint32_t* __restrict__ bad) {
+    const int i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= n) return;
+    const NodeQ4 q = nodes[i];
+    uint32_t G = 0, off = 0;
+    for (int c = 0; c < 4; ++c) {
+        const uint32_t k = view_slot_records(q, c);
+        if (k == 0u) continue;
+        G |= (8u * off + (q.child[c] >= 0 ? 0u : 4u + (k - 1u))) << (8 * c);
+        off += k;
+    }
+    // a step is as_float(exponent byte << 23): a positive normal power of two
+    const uint32_t sb[3] = {__float_as_uint(q.sx), __float_as_uint(q.sy), __float_as_uint(q.sz)};
+    uint32_t E = 0;
+    for (int k = 0; k < 3; ++k) {
+        const uint32_t e = sb[k] >> 23;
+        if ((sb[k] & 0x807FFFFFu) != 0u || e == 0u || e == 255u) *bad = 1u;
+        E |= (e & 0xFFu) << (8 * k);
+    }
+    const uint32_t cb8 = 8u * (1u + scan[i]);
+    ViewRec r;
+    r.q0 = make_float4(q.ox, q.oy, q.oz, __uint_as_float(q.lox));
+    r.q1 = make_float4(__uint_as_float(q.loy), __uint_as_float(q.loz), __uint_as_float(q.hix), __uint_as_float(q.hiy));
+    r.q2 = make_float4(__uint_as_float(q.hiz), __uint_as_float(G), __uint_as_float(cb8), __uint_as_float(E));
+    const uint32_t v = rec_of_node[i];
+    if (v < cap) rec[v] = r; else *bad = 1u;   // (a node no parent placed: not a tree the view can restate)
+}
+// one thread per triangle record (leaf order): its copy and its normal at its place in the view
+__global__ __launch_bounds__(kRefitBlock) void view_tris_kernel(const Tri48* __restrict__ tris, const float4* __restrict__ nrm, int T,
+                                                                const uint32_t* __restrict__ rec_of_leaf, ViewRec* __restrict__ rec,
+                                                                float4* __restrict__ rec_nrm, uint32_t cap, uint32_t* __restrict__ bad) {
+    const int i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= T) return;
+    const Tri48 x = tris[i];
+    const uint32_t v = rec_of_leaf[i];
+    if (v >= cap) { *bad = 1u; return; }
+    rec[v] = ViewRec{x.a, x.b, x.c};
+    rec_nrm[v] = nrm[i];
+}
+
 }  // namespace
+
+void launch_node_view_layout(const NodeQ4* nodes, int n, int T, uint32_t* block, uint32_t* rec_of_node, uint32_t* rec_of_leaf, hipStream_t s) {
+    if (n <= 0) return;
+    (void)hipMemsetAsync(rec_of_node, 0xFF, sizeof(uint32_t) * (size_t)n, s);   // unplaced: no record
+    if (T > 0) (void)hipMemsetAsync(rec_of_leaf, 0xFF, sizeof(uint32_t) * (size_t)T, s);
+    const dim3 grid((unsigned)((n + kRefitBlock - 1) / kRefitBlock));
+    hipLaunchKernelGGL(view_block_kernel, grid, dim3(kRefitBlock), 0, s, nodes, n, block);
+    hipLaunchKernelGGL(view_scan_kernel, dim3(1), dim3(kViewScanBlock), 0, s, block, n);
+    hipLaunchKernelGGL(view_place_kernel, grid, dim3(kRefitBlock), 0, s, nodes, n, block, rec_of_node, rec_of_leaf, T);
+}
+void launch_node_view_fill(const NodeQ4* nodes, int n, const Tri48* tris, const float4* nrm, int T, const uint32_t* block,
+                           const uint32_t* rec_of_node, const uint32_t* rec_of_leaf, ViewRec* rec, float4* rec_nrm, uint32_t* bad, hipStream_t s) {
+    if (n <= 0) return;
+    const uint32_t cap = (uint32_t)n + (uint32_t)std::max(T, 0);
+    hipLaunchKernelGGL(view_nodes_kernel, dim3((unsigned)((n + kRefitBlock - 1) / kRefitBlock)), dim3(kRefitBlock), 0, s, nodes, n, block,
+                       rec_of_node, rec, cap, bad);
+    if (T > 0)
+        hipLaunchKernelGGL(view_tris_kernel, dim3((unsigned)((T + kRefitBlock - 1) / kRefitBlock)), dim3(kRefitBlock), 0, s, tris, nrm, T,
+                           rec_of_leaf, rec, rec_nrm, cap, bad);
+}
 
 void launch_coop_nodes(const NodeQ4* nodes, int n, CoopChild* out, hipStream_t s) {
     if (n <= 0) return;
@@ -278,18 +402,18 @@ void launch_coop16(const CoopChild* in, const int32_t* level_begin_dev, const in
 }
 
 void launch_update_triangles(Tri64* tris, Tri48* packed, float4* nrm, const uint32_t* leaf_pos, int first, int count,
-                             const float* xyz, hipStream_t s) {
+                             const float* xyz, const ViewTris& view, hipStream_t s) {
     if (count <= 0) return;
     hipLaunchKernelGGL(update_tris_kernel, dim3((unsigned)((count + kRefitBlock - 1) / kRefitBlock)), dim3(kRefitBlock),
-                       0, s, tris, packed, nrm, leaf_pos, first, count, xyz);
+                       0, s, tris, packed, nrm, leaf_pos, first, count, xyz, view);
 }
 
 void launch_transform_objects(Tri64* tris, Tri48* packed, float4* nrm, const uint32_t* leaf_pos, const float* rest,
                               const uint32_t* csr, const uint32_t* prefix, const uint32_t* start, const float* m, int n,
-                              uint32_t total, uint32_t* amax_bits, hipStream_t s) {
+                              uint32_t total, uint32_t* amax_bits, const ViewTris& view, hipStream_t s) {
     if (n <= 0 || total == 0) return;
     hipLaunchKernelGGL(transform_objects_kernel, dim3((total + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, s,
-                       tris, packed, nrm, leaf_pos, rest, csr, prefix, start, m, n, total, amax_bits);
+                       tris, packed, nrm, leaf_pos, rest, csr, prefix, start, m, n, total, amax_bits, view);
 }
 
 void launch_pack_triangles(const Tri64* tris, int count, Tri48* packed, float4* nrm, hipStream_t s) {
