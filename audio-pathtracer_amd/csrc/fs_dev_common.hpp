@@ -24,8 +24,6 @@ constexpr uint32_t kNoMat = FS_NO_MATERIAL;
 constexpr uint32_t kLobeDiffuse = 0u, kLobeSpecular = 1u, kLobeTransmit = 2u;
 constexpr int kLobeShift = 16;   // segment record: material id | lobe << 16
 constexpr int kDone = (int)0x80000000;  // traversal cursor: nothing left
-constexpr uint32_t kMissKey = 0xFFFFFFFCu;   // node test: sort key of a child the ray misses (| slot)
-constexpr uint32_t kMissKeyView = 0xFFFFFF00u;   // ... walking the 48-byte node view (FS_NODE_VIEW): the key's low byte is the slot's reference byte
 constexpr double kFixedScale = 1099511627776.0;   // 2^40: quantum of the deterministic (fixed-point) energy sum
 #ifdef FS_WAVE_TIMELINE   // diagnostic build only (tools/wave_timeline.py): when every walk wave ran and what it spent its cycles on
 __device__ unsigned long long* g_wave_buf;       // [waves][8]: start, end (100 MHz), cycles in traversal, cycles in all, iterations, segments, hw id, slot

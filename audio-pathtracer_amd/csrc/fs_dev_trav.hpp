@@ -17,13 +17,13 @@ namespace {
 // ---------------------------------------------------------------------------------------------------
 
 struct Trav {
-    int cur;        // next node: >= 0 inner index, < 0 leaf code (~cur = first*4 + count-1), kDone = none
-                    // (FS_NODE_VIEW: a view reference turned right by 3 — leaf bit | count-1 | record number — see view_cursor)
+    int cur;        // next node, as NodeLayout::cursor(child reference): >= 0 inner (node index / view record), < 0 leaf (decoded by
+                    // NodeLayout::leaf_range alone), kDone = none
     int sp;         // stack top (entries live in [sb, sp))
     int sb;         // stack bottom: 0 unless entries were given away from the bottom (wave work sharing)
     int tri_i, tri_n;  // pending triangles [tri_i, tri_n) of the current leaf
     float t;        // closest hit so far (init: tmax)
-    int leaf_index; // hit triangle (leaf order; FS_NODE_VIEW: its record number in the view), -1 = none
+    int leaf_index; // hit triangle: its index in the array the layout's leaf_range counts in (sc.tris as bound by the launcher), -1 = none
     uint32_t id;    // its input index (tie-break key)
     uint32_t nv, nt;   // COUNT instantiations only (fs_set_profiling level 3): node records / triangle records this lane fetched
     uint32_t ni, nl, nd;   // ... and (one lane per wave) node-request instructions, their active lanes, the distinct records among those
@@ -65,21 +65,190 @@ __device__ __forceinline__ int lanes_below(unsigned long long m) {
 // sinks the first arithmetic on the loaded words into the block of the loads, i.e. waits for one record before it
 // requests the other: 448 lane-loads per wave iteration for 207 useful ones.)
 typedef float v4f __attribute__((ext_vector_type(4)));
-// FS_NODE_VIEW (defined by the narrow flavours of the fused frame kernel, fs_frame.hip): sc.nodes and sc.tris are ONE array
-// of 48-byte records, the node view of fs_internal.hpp (ViewRec) — a node takes three requests instead of four and its
-// child references are  cb8 + the slot's byte  (record x 8 | leaf bit 2 | count - 1), formed behind the sort.  On the stack,
-// in the donation boxes and in the deep store a reference stays that opaque word; the cursor T.cur holds it turned right by
-// 3, so that the leaf bit is the sign and every mask of the step is the one compare it is without the view: an inner
-// record number >= 0, a leaf (bit 31 | count - 1 at 30:29 | first record) < 0.  kDone (bit 31 alone) would be a one-triangle
-// leaf at record 0, which is the root: never a reference.
-#ifdef FS_NODE_VIEW
-struct NodeRegs { v4f q0, q1, q2; };
-__device__ __forceinline__ int view_cursor(int ref) { return (int)__builtin_rotateright32((uint32_t)ref, 3u); }
-#else
-struct NodeRegs { v4f q0, q1, q2, q3; };
-__device__ __forceinline__ int view_cursor(int ref) { return ref; }
-#endif
 struct TriRegs { v4f a, b, c; };
+// what the box arithmetic of a node visit needs, whichever record it came from: the origin, grid step x the ray's reciprocal
+// direction per axis, the six plane words (byte c = child c's plane on the node's 8-bit grid)
+struct NodeBox { float ox, oy, oz, sx, sy, sz; uint32_t lox, loy, loz, hix, hiy, hiz; };
+// record index x 48 as a shift-add and a shift (left alone the compiler makes it one quarter-rate v_mul_lo_u32)
+__device__ __forceinline__ uint32_t offset48(uint32_t i) {
+    uint32_t o = (i << 1) + i;
+    asm("" : "+v"(o));
+    return o << 4;
+}
+
+// The request.  ONE asm statement, executed by every lane that reaches it, with every destination register tied in and
+// out ("+v"): the lanes that want a record are selected by writing their ballot to EXEC inside the statement.  Both
+// matter.  (1) The compiler does not know that the destinations are still being written until the next wait; with
+// conditionally executed "=v" outputs the old and the new value meet in a phi, and register allocation is free to
+// resolve that phi with copies placed right behind the request — reading registers whose data has not arrived (round 3
+// lost a day's first build to exactly that; tools/check_isa_hazards.py now proves the absence of such accesses on the
+// final ISA).  A tied operand chain issue -> wait -> use has no phi to resolve.  (2) Every wave executes the same
+// number of vector memory instructions per step whatever its lanes need, so counted waits stay possible.
+// Addresses: the record arrays' bases are wave-uniform and stay in scalar registers; a lane supplies only its 32-bit
+// byte offset (the layout's node_offset, triangle index * 48) and the 16-byte quarters are the instruction's own
+// offset — `global_load_dwordx4 vdst, voff, s[base:base+1] offset:n`.  No 64-bit vector arithmetic and no address pairs
+// in a kernel held to 128 registers; fs_scene_commit refuses a scene whose record arrays exceed 4 GiB (DeviceScene,
+// fs_internal.hpp).  (No cache-policy bits on these requests: measured, none helps — DESIGN.md section 5.)
+// The statement exists once per layout, because the operand lists differ; its text — EXEC saved, set and restored, the
+// three node quarters both layouts have, the triangle half — and the operands common to both are written here.
+#define FS_REQUEST_ASM(MORE_NODE_LOADS)                                                                         \
+    "s_mov_b64 %[sv], exec\n\t"                                                                                 \
+    "s_mov_b64 exec, %[mn]\n\t"                                                                                 \
+    "global_load_dwordx4 %[q0], %[no], %[nb]\n\t"                                                               \
+    "global_load_dwordx4 %[q1], %[no], %[nb] offset:16\n\t"                                                     \
+    "global_load_dwordx4 %[q2], %[no], %[nb] offset:32\n\t" MORE_NODE_LOADS                                     \
+    "s_mov_b64 exec, %[mt]\n\t"                                                                                 \
+    "s_cbranch_execz 1f\n\t" /* one wave step in four has no lane with a pending triangle */                    \
+    "global_load_dwordx4 %[ta], %[to], %[tb_]\n\t"                                                              \
+    "global_load_dwordx4 %[tb], %[to], %[tb_] offset:16\n\t"                                                    \
+    "global_load_dwordx4 %[tc], %[to], %[tb_] offset:32\n"                                                      \
+    "1:\n\t"                                                                                                    \
+    "s_mov_b64 exec, %[sv]"
+#define FS_REQUEST_NODE_OUT [q0] "+&v"(N.q0), [q1] "+&v"(N.q1), [q2] "+&v"(N.q2)
+#define FS_REQUEST_TRI_OUT [ta] "+&v"(X.a), [tb] "+&v"(X.b), [tc] "+&v"(X.c), [sv] "=&s"(sv)
+#define FS_REQUEST_IN [no] "v"(no), [to] "v"(to), [nb] "s"(sc.nodes), [tb_] "s"(sc.tris), [mn] "s"(mn), [mt] "s"(mt)
+// the wait for everything requested: every register in flight is listed, tied in and out like the request's
+#define FS_WAIT(...) asm volatile("s_waitcnt vmcnt(0)" : __VA_ARGS__)
+#define FS_NODE3(N) "+v"(N.q0), "+v"(N.q1), "+v"(N.q2)
+#define FS_TRI3(X) "+v"(X.a), "+v"(X.b), "+v"(X.c)
+
+// ---- the two record formats a traversal can walk.  A translation unit walks ONE (NodeLayout below); everything in this
+// file that differs between them is in these two structs, each to be read top to bottom on its own. ----------------------
+
+// NodeQ4 and Tri48 (fs_internal.hpp), two arrays: a 64-byte node in four requests, child references NodeQ4::child as they are.
+struct NodeLayoutQ4 {
+    static constexpr bool kIsView = false;
+    struct Regs { v4f q0, q1, q2, q3; };   // the node quarters in flight
+    static constexpr uint32_t kMiss = 0xFFFFFFFCu;   // node test: sort key of a child the ray misses (| slot)
+    static __device__ __forceinline__ int cursor(int ref) { return ref; }   // >= 0 inner index, < 0 leaf code
+    static __device__ __forceinline__ void leaf_range(int cur, int& first, int& end) {   // ~cur = first * 4 + count - 1
+        const int code = ~cur; first = code >> 2; end = first + (code & 3) + 1;
+    }
+    static_assert(sizeof(NodeQ4) == 64 && sizeof(Tri48) == 48, "the request's byte offsets");
+    static __device__ __forceinline__ uint32_t node_offset(int cur) { return (uint32_t)cur << 6; }
+    static __device__ __forceinline__ void request(const DeviceScene& sc, Regs& N, TriRegs& X, uint32_t no, uint32_t to,
+                                                   unsigned long long mn, unsigned long long mt) {
+        unsigned long long sv;
+        asm volatile(FS_REQUEST_ASM("global_load_dwordx4 %[q3], %[no], %[nb] offset:48\n\t")
+                     : FS_REQUEST_NODE_OUT, [q3] "+&v"(N.q3), FS_REQUEST_TRI_OUT : FS_REQUEST_IN : "memory");
+    }
+    static __device__ __forceinline__ void wait(Regs& N, TriRegs& X) { FS_WAIT(FS_NODE3(N), "+v"(N.q3), FS_TRI3(X)); }
+    static __device__ __forceinline__ void drain(Regs& N, TriRegs& X, TriRegs& Y) { FS_WAIT(FS_NODE3(N), "+v"(N.q3), FS_TRI3(X), FS_TRI3(Y)); }
+    // the record (fs_internal.hpp: NodeQ4): origin, sx | lox, loy, loz, hix | hiy, hiz, sy, sz | child[4]
+    static __device__ __forceinline__ NodeBox decode(const Regs& N, const Ray& r) {
+        return NodeBox{N.q0.x, N.q0.y, N.q0.z, N.q0.w * r.ix, N.q2.z * r.iy, N.q2.w * r.iz,   // grid step (a power of two) / direction
+                       __float_as_uint(N.q1.x), __float_as_uint(N.q1.y), __float_as_uint(N.q1.z),
+                       __float_as_uint(N.q1.w), __float_as_uint(N.q2.x), __float_as_uint(N.q2.y)};
+    }
+    // a hit child's key: the entry distance (>= 0, so its bits order like an integer) with the slot in the low 2 bits; a missed
+    // child sorts behind every hit one (kMiss | slot)
+    static __device__ __forceinline__ uint32_t hit_key(const Regs&, float tn, int c) { return (__float_as_uint(tn) & ~3u) | (uint32_t)c; }
+    static __device__ __forceinline__ uint32_t miss_key(int c) { return kMiss | (uint32_t)c; }
+    // sort the 4 (key, child reference) pairs, nearest first: 5-comparator network, branch-free.  (Measured in
+    // round 2: choosing only the nearest child and pushing the rest in slot order — also no ordering at all for
+    // visibility rays — saves a dozen instructions per visit and costs as much in extra visits: walk 0.356 ->
+    // 0.361 ms, connect 0.075 -> 0.078 ms.)
+    static __device__ __forceinline__ void order(const Regs& N, uint32_t (&key)[4], int& ref0, int& ref1, int& ref2, int& ref3) {
+        ref0 = __float_as_int(N.q3.x); ref1 = __float_as_int(N.q3.y); ref2 = __float_as_int(N.q3.z); ref3 = __float_as_int(N.q3.w);
+#define FS_CSWAP(a, b) { const bool sw_ = key[b] < key[a]; const uint32_t lo_ = min(key[a], key[b]); \
+                         const uint32_t hi_ = max(key[a], key[b]); key[a] = lo_; key[b] = hi_; \
+                         const int ra_ = sw_ ? ref##b : ref##a; const int rb_ = sw_ ? ref##a : ref##b; \
+                         ref##a = ra_; ref##b = rb_; }
+        FS_CSWAP(0, 1) FS_CSWAP(2, 3) FS_CSWAP(0, 2) FS_CSWAP(1, 3) FS_CSWAP(1, 2)
+#undef FS_CSWAP
+    }
+    static bool bind(DeviceScene&) { return true; }   // (host) DeviceScene's arrays are this layout's
+};
+
+// The 48-byte node view (fs_internal.hpp: ViewRec and the view_* word formats): sc.nodes and sc.tris are ONE array of
+// 48-byte records — a node takes three requests instead of four and its child references are  cb8 + the slot's byte,
+// formed behind the sort.  On the stack, in the donation boxes and in the deep store a reference stays that opaque word;
+// the cursor holds it turned (view_cursor), so that the leaf bit is the sign and every mask of the step is the one
+// compare it is without the view.
+struct NodeLayoutView {
+    static constexpr bool kIsView = true;
+    struct Regs { v4f q0, q1, q2; };   // the node quarters in flight
+    static constexpr uint32_t kMiss = 0xFFFFFF00u;   // node test: a missed child's key is ~0; the low byte of a hit one is its slot byte
+    static_assert(view_is_leaf(kDone) && view_count(kDone) == 1 && view_record(kDone) == 0,
+                  "kDone decodes as a one-triangle leaf at record 0, which is the root: never a reference");
+    static __device__ __forceinline__ int cursor(int ref) { return view_cursor((uint32_t)ref); }
+    static __device__ __forceinline__ void leaf_range(int cur, int& first, int& end) { first = view_record(cur); end = first + view_count(cur); }
+    static_assert(sizeof(ViewRec) == 48 && sizeof(Tri48) == 48, "the request's byte offsets: both (record x 3) << 4");
+    static __device__ __forceinline__ uint32_t node_offset(int cur) { return offset48((uint32_t)cur); }
+    static __device__ __forceinline__ void request(const DeviceScene& sc, Regs& N, TriRegs& X, uint32_t no, uint32_t to,
+                                                   unsigned long long mn, unsigned long long mt) {
+        unsigned long long sv;   // (sc.nodes == sc.tris here: both groups from the one array)
+        asm volatile(FS_REQUEST_ASM("") : FS_REQUEST_NODE_OUT, FS_REQUEST_TRI_OUT : FS_REQUEST_IN : "memory");
+    }
+    static __device__ __forceinline__ void wait(Regs& N, TriRegs& X) { FS_WAIT(FS_NODE3(N), FS_TRI3(X)); }
+    static __device__ __forceinline__ void drain(Regs& N, TriRegs& X, TriRegs& Y) { FS_WAIT(FS_NODE3(N), FS_TRI3(X), FS_TRI3(Y)); }
+    // grid step K of a record: exponent byte K of E moved to the float's exponent (view_step_bits), as ONE instruction
+    // (the byte select is the operand's own; written as a shift and a mask it is two per step)
+    template <int K>
+    static __device__ __forceinline__ float step(uint32_t E) {
+        static_assert(K >= 0 && K < 3, "three steps");
+        float out;
+        if (K == 0) asm("v_lshlrev_b32_sdwa %0, 23, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(out) : "v"(E));
+        else if (K == 1) asm("v_lshlrev_b32_sdwa %0, 23, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(out) : "v"(E));
+        else asm("v_lshlrev_b32_sdwa %0, 23, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(out) : "v"(E));
+        return out;
+    }
+    // the record (fs_internal.hpp: ViewRec): origin, lox | loy, loz, hix, hiy | hiz, G, cb8, E.  The steps come back from
+    // their exponent bytes bit for bit; the box arithmetic is then the NodeQ4 path's.
+    static __device__ __forceinline__ NodeBox decode(const Regs& N, const Ray& r) {
+        const uint32_t E = __float_as_uint(N.q2.w);
+        return NodeBox{N.q0.x, N.q0.y, N.q0.z, step<0>(E) * r.ix, step<1>(E) * r.iy, step<2>(E) * r.iz,
+                       __float_as_uint(N.q0.w), __float_as_uint(N.q1.x), __float_as_uint(N.q1.y),
+                       __float_as_uint(N.q1.z), __float_as_uint(N.q1.w), __float_as_uint(N.q2.x)};
+    }
+    // entry distance with the slot's byte of G in the low 8 bits (one v_perm_b32: bytes 3 - 1 of the distance, byte c of G):
+    // the reference then comes OUT of the sort — cb8 + the sorted key's low byte — and nothing is dragged through it.
+    // The order of near-equal children may differ from the NodeQ4 path's; a closest hit does not depend on the order of
+    // the visits and an any-hit answer is a boolean.
+    static __device__ __forceinline__ uint32_t hit_key(const Regs& N, float tn, int c) {
+        return __builtin_amdgcn_perm(__float_as_uint(tn), __float_as_uint(N.q2.y), 0x07060500u + (uint32_t)c);
+    }
+    static __device__ __forceinline__ uint32_t miss_key(int) { return 0xFFFFFFFFu; }
+    // the same 5-comparator network as NodeLayoutQ4's (why there is a sort at all: there), on the keys alone
+    static __device__ __forceinline__ void order(const Regs& N, uint32_t (&key)[4], int& ref0, int& ref1, int& ref2, int& ref3) {
+#define FS_KEYSWAP(a, b) { const uint32_t lo_ = min(key[a], key[b]), hi_ = max(key[a], key[b]); key[a] = lo_; key[b] = hi_; }
+        FS_KEYSWAP(0, 1) FS_KEYSWAP(2, 3) FS_KEYSWAP(0, 2) FS_KEYSWAP(1, 3) FS_KEYSWAP(1, 2)
+#undef FS_KEYSWAP
+        const uint32_t cb8 = __float_as_uint(N.q2.z);
+        ref0 = (int)view_ref(cb8, key[0] & 0xFFu); ref1 = (int)view_ref(cb8, key[1] & 0xFFu);
+        ref2 = (int)view_ref(cb8, key[2] & 0xFFu); ref3 = (int)view_ref(cb8, key[3] & 0xFFu);
+    }
+    // (host) A unit of this layout reads ONE array: record 0 is the root, a hit's leaf_index is a record number (hit_surface
+    // reads that record as the Tri48 it is, its normal from the view's parallel array).  DeviceScene keeps the pointer types
+    // every other unit walks, so the array is handed over under both names; no code of this layout reads a NodeQ4 from it.
+    // false: the scene has no view (too large, a step that is no power of two) and is not empty (that requests no record).
+    static bool bind(DeviceScene& sc) {
+        const NodeView view = sc.coop_info ? sc.coop_info->view : NodeView{};
+        if (!view.rec) return sc.num_nodes <= 0;
+        sc.nodes = reinterpret_cast<const NodeQ4*>(view.rec);
+        sc.tris = reinterpret_cast<const Tri48*>(view.rec);
+        sc.tri_nrm = view.nrm;
+        return true;
+    }
+};
+#undef FS_REQUEST_ASM
+#undef FS_REQUEST_NODE_OUT
+#undef FS_REQUEST_TRI_OUT
+#undef FS_REQUEST_IN
+#undef FS_WAIT
+#undef FS_NODE3
+#undef FS_TRI3
+
+// The layout of this translation unit.  A macro and not a template parameter: a parameter would thread through some twenty
+// templates (walk_shared_body, connect_body, ...) for the sake of a unit that holds both, and no product unit does.  It
+// must be settled before this header is first seen: FS_TRAV_LAYOUT_CHOSEN lets a unit that tries later refuse to compile.
+#define FS_TRAV_LAYOUT_CHOSEN 1
+#ifdef FS_NODE_VIEW   // (fs_frame.hip: the narrow flavours of the fused frame kernel)
+using NodeLayout = NodeLayoutView;
+#else
+using NodeLayout = NodeLayoutQ4;
+#endif
+using NodeRegs = NodeLayout::Regs;
 
 // ---- bounded LDS stack with a deep store in HBM (DeviceScene.deep, fs_internal.hpp) ---------------------------
 // The logical stack of a lane is  deep[0, count)  followed by  LDS rows [sb, sp).  Entries move between the two in
@@ -140,40 +309,18 @@ __device__ __forceinline__ void trav_maintain(const DeviceScene& sc, Trav& T, in
 }
 // next pending entry into T.cur (kDone: none left)
 __device__ __forceinline__ void trav_pop(const DeviceScene& sc, Trav& T, int* stack) {
-    if (T.sp > T.sb) { --T.sp; T.cur = view_cursor(stack[T.sp * kBlock]); }
+    if (T.sp > T.sb) { --T.sp; T.cur = NodeLayout::cursor(stack[T.sp * kBlock]); }
     else T.cur = kDone;
 }
 
 __device__ __forceinline__ void trav_settle(const DeviceScene& sc, Trav& T, int* stack) {
     if (T.tri_i >= T.tri_n && T.cur < 0 && T.cur != kDone) {
-#ifdef FS_NODE_VIEW
-        T.tri_i = T.cur & 0x1FFFFFFF;
-        T.tri_n = T.tri_i + ((T.cur >> 29) & 3) + 1;
-#else
-        const int code = ~T.cur;
-        T.tri_i = code >> 2;
-        T.tri_n = T.tri_i + (code & 3) + 1;
-#endif
+        NodeLayout::leaf_range(T.cur, T.tri_i, T.tri_n);
         trav_pop(sc, T, stack);
     }
 }
 
-// The request.  ONE asm statement, executed by every lane that reaches it, with every destination register tied in and
-// out ("+v"): the lanes that want a record are selected by writing their ballot to EXEC inside the statement.  Both
-// matter.  (1) The compiler does not know that the destinations are still being written until the next trav_wait; with
-// conditionally executed "=v" outputs the old and the new value meet in a phi, and register allocation is free to
-// resolve that phi with copies placed right behind the request — reading registers whose data has not arrived (round 3
-// lost a day's first build to exactly that; tools/check_isa_hazards.py now proves the absence of such accesses on the
-// final ISA).  A tied operand chain issue -> wait -> use has no phi to resolve.  (2) Every wave executes the same
-// number of vector memory instructions per step whatever its lanes need, so counted waits stay possible.
-// Addresses: the record arrays' bases are wave-uniform and stay in scalar registers; a lane supplies only its 32-bit
-// byte offset (node index << 6, triangle index * 48 as a shift-add and a shift) and the 16-byte quarters are the
-// instruction's own offset — `global_load_dwordx4 vdst, voff, s[base:base+1] offset:n`.  No 64-bit vector arithmetic
-// and no address pairs in a kernel held to 128 registers; fs_scene_commit refuses a scene whose record arrays exceed
-// 4 GiB (DeviceScene, fs_internal.hpp).
-// FS_NODE_VIEW: three node loads instead of four, both groups from the one array of 48-byte records (sc.nodes == sc.tris there),
-// both offsets (record x 3) << 4.
-// (No cache-policy bits on these requests: measured, none helps — DESIGN.md section 5.)
+// which lanes request what, and where: the statement itself is the layout's (NodeLayout::request)
 __device__ __forceinline__ void trav_issue(const DeviceScene& sc, Trav& T, NodeRegs& N, TriRegs& X) {
     // (the compare is made on the register: what the compiler knows of tri_i < tri_n from the branches behind it is a
     // lane mask spread over several scalar registers, which it would turn into 0 / 1 per lane and compare again)
@@ -182,49 +329,15 @@ __device__ __forceinline__ void trav_issue(const DeviceScene& sc, Trav& T, NodeR
     const int ti = T.tri_i;
     const unsigned long long mn = lane_mask(T.cur >= 0), mt = lane_mask(ti < T.tri_n);   // subsets of EXEC
     // (offsets of lanes that want nothing are never dereferenced)
-    static_assert(sizeof(NodeQ4) == 64 && sizeof(Tri48) == 48 && sizeof(ViewRec) == 48, "the request's byte offsets");
-#ifdef FS_NODE_VIEW
-    uint32_t no = ((uint32_t)T.cur << 1) + (uint32_t)T.cur;   // both offsets (record x 3) << 4, see `to`
-    asm("" : "+v"(no));
-    no <<= 4;
-#else
-    const uint32_t no = (uint32_t)T.cur << 6;
-#endif
-    uint32_t to = ((uint32_t)ti << 1) + (uint32_t)ti;   // * 48 as a shift-add and a shift (left alone the compiler
-    asm("" : "+v"(to));                                 //   makes it one quarter-rate v_mul_lo_u32)
-    to <<= 4;
-    unsigned long long sv;
-    asm volatile("s_mov_b64 %[sv], exec\n\t"
-                 "s_mov_b64 exec, %[mn]\n\t"
-                 "global_load_dwordx4 %[q0], %[no], %[nb]\n\t"
-                 "global_load_dwordx4 %[q1], %[no], %[nb] offset:16\n\t"
-                 "global_load_dwordx4 %[q2], %[no], %[nb] offset:32\n\t"
-#ifndef FS_NODE_VIEW
-                 "global_load_dwordx4 %[q3], %[no], %[nb] offset:48\n\t"
-#endif
-                 "s_mov_b64 exec, %[mt]\n\t"
-                 "s_cbranch_execz 1f\n\t"      // one wave step in four has no lane with a pending triangle
-                 "global_load_dwordx4 %[ta], %[to], %[tb_]\n\t"
-                 "global_load_dwordx4 %[tb], %[to], %[tb_] offset:16\n\t"
-                 "global_load_dwordx4 %[tc], %[to], %[tb_] offset:32\n"
-                 "1:\n\t"
-                 "s_mov_b64 exec, %[sv]"
-                 : [q0] "+&v"(N.q0), [q1] "+&v"(N.q1), [q2] "+&v"(N.q2),
-#ifndef FS_NODE_VIEW
-                   [q3] "+&v"(N.q3),
-#endif
-                   [ta] "+&v"(X.a), [tb] "+&v"(X.b), [tc] "+&v"(X.c), [sv] "=&s"(sv)
-                 : [no] "v"(no), [to] "v"(to), [nb] "s"(sc.nodes), [tb_] "s"(sc.tris), [mn] "s"(mn), [mt] "s"(mt)
-                 : "memory");
+    const uint32_t no = NodeLayout::node_offset(T.cur);
+    const uint32_t to = offset48((uint32_t)ti);
+    NodeLayout::request(sc, N, X, no, to, mn, mt);
 }
 
-__device__ __forceinline__ void trav_wait(NodeRegs& N, TriRegs& X) {
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(N.q0), "+v"(N.q1), "+v"(N.q2),
-#ifndef FS_NODE_VIEW
-                                        "+v"(N.q3),
-#endif
-                                        "+v"(X.a), "+v"(X.b), "+v"(X.c));
-}
+__device__ __forceinline__ void trav_wait(NodeRegs& N, TriRegs& X) { NodeLayout::wait(N, X); }
+// Before a traversal returns, every record it has requested must have landed: the compiler knows nothing of loads in
+// flight and would hand their destination registers to other values (an any-hit query ends with requests outstanding).
+__device__ __forceinline__ void trav_drain(NodeRegs& N, TriRegs& X, TriRegs& Y) { NodeLayout::drain(N, X, Y); }
 
 // the triangle that arrived with this step (leaf-order index `tested`): Moeller-Trumbore, closest-hit update as selects
 template <bool ANY, bool IGN = false>
@@ -280,92 +393,33 @@ __device__ __forceinline__ float min_canonical(float a, float b) {
 }
 
 // the lane's inner node (T.cur >= 0): 4 child boxes, near-first order, far children to the stack, next node
-#ifdef FS_NODE_VIEW
-// grid step K of a view record: exponent byte K of E moved to the float's exponent, (E >> 8 K & 0xFF) << 23, as ONE
-// instruction (the byte select is the operand's own; written as a shift and a mask it is two per step)
-template <int K>
-__device__ __forceinline__ float view_step(uint32_t E) {
-    static_assert(K >= 0 && K < 3, "three steps");
-    float out;
-    if (K == 0) asm("v_lshlrev_b32_sdwa %0, 23, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(out) : "v"(E));
-    else if (K == 1) asm("v_lshlrev_b32_sdwa %0, 23, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(out) : "v"(E));
-    else asm("v_lshlrev_b32_sdwa %0, 23, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(out) : "v"(E));
-    return out;
-}
-#endif
 __device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray& r, const RaySigns& sg, Trav& T, int* stack,
                                                const NodeRegs& N) {
-    const float4 q0 = make_float4(N.q0.x, N.q0.y, N.q0.z, N.q0.w), q1 = make_float4(N.q1.x, N.q1.y, N.q1.z, N.q1.w),
-                 q2 = make_float4(N.q2.x, N.q2.y, N.q2.z, N.q2.w);
     // ---- 4-wide node, child boxes on the node's 8-bit grid: plane distance = fma(q, step*inv, (origin-o)*inv)
-#ifdef FS_NODE_VIEW
-    // the view's record (fs_internal.hpp: ViewRec): origin, lox | loy, loz, hix, hiy | hiz, G, cb8, E.  The steps come back
-    // from their exponent bytes bit for bit; everything from here to the keys is the arithmetic of the NodeQ4 path.
-    const uint32_t E = __float_as_uint(q2.w), G = __float_as_uint(q2.y), cb8 = __float_as_uint(q2.z);
-    const float sx = view_step<0>(E) * r.ix, sy = view_step<1>(E) * r.iy, sz = view_step<2>(E) * r.iz;
-#else
-    const float4 q3 = make_float4(N.q3.x, N.q3.y, N.q3.z, N.q3.w);
-    const float sx = q0.w * r.ix, sy = q2.z * r.iy, sz = q2.w * r.iz;   // grid step (a power of two) / direction
-#endif
-    const float bx = fmaf(q0.x, r.ix, r.nox);
-    const float by = fmaf(q0.y, r.iy, r.noy);
-    const float bz = fmaf(q0.z, r.iz, r.noz);
-#ifdef FS_NODE_VIEW
-    const uint32_t lox = __float_as_uint(q0.w), loy = __float_as_uint(q1.x), loz = __float_as_uint(q1.y);
-    const uint32_t hix = __float_as_uint(q1.z), hiy = __float_as_uint(q1.w), hiz = __float_as_uint(q2.x);
-#else
-    const uint32_t lox = __float_as_uint(q1.x), loy = __float_as_uint(q1.y), loz = __float_as_uint(q1.z);
-    const uint32_t hix = __float_as_uint(q1.w), hiy = __float_as_uint(q2.x), hiz = __float_as_uint(q2.y);
-#endif
+    const NodeBox n = NodeLayout::decode(N, r);
+    const float bx = fmaf(n.ox, r.ix, r.nox);
+    const float by = fmaf(n.oy, r.iy, r.noy);
+    const float bz = fmaf(n.oz, r.iz, r.noz);
     // the ray's direction signs pick the entry / exit plane words once per node
-    const uint32_t nxw = lane_select(sg.x, hix, lox), fxw = lane_select(sg.x, lox, hix);
-    const uint32_t nyw = lane_select(sg.y, hiy, loy), fyw = lane_select(sg.y, loy, hiy);
-    const uint32_t nzw = lane_select(sg.z, hiz, loz), fzw = lane_select(sg.z, loz, hiz);
+    const uint32_t nxw = lane_select(sg.x, n.hix, n.lox), fxw = lane_select(sg.x, n.lox, n.hix);
+    const uint32_t nyw = lane_select(sg.y, n.hiy, n.loy), fyw = lane_select(sg.y, n.loy, n.hiy);
+    const uint32_t nzw = lane_select(sg.z, n.hiz, n.loz), fzw = lane_select(sg.z, n.loz, n.hiz);
     uint32_t key[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         // entry and exit plane distances per axis: six plain fmas.  (As three v_pk_fma_f32 — twelve instructions fewer
         // per visit — the frame is 1.4 % slower: a packed f32 operation costs more than the two it replaces and wants
         // its operands in aligned register pairs.  DESIGN.md section 5.)
-        const float tnx = fmaf((float)((nxw >> (8 * c)) & 0xFFu), sx, bx), tfx = fmaf((float)((fxw >> (8 * c)) & 0xFFu), sx, bx);
-        const float tny = fmaf((float)((nyw >> (8 * c)) & 0xFFu), sy, by), tfy = fmaf((float)((fyw >> (8 * c)) & 0xFFu), sy, by);
-        const float tnz = fmaf((float)((nzw >> (8 * c)) & 0xFFu), sz, bz), tfz = fmaf((float)((fzw >> (8 * c)) & 0xFFu), sz, bz);
+        const float tnx = fmaf((float)((nxw >> (8 * c)) & 0xFFu), n.sx, bx), tfx = fmaf((float)((fxw >> (8 * c)) & 0xFFu), n.sx, bx);
+        const float tny = fmaf((float)((nyw >> (8 * c)) & 0xFFu), n.sy, by), tfy = fmaf((float)((fyw >> (8 * c)) & 0xFFu), n.sy, by);
+        const float tnz = fmaf((float)((nzw >> (8 * c)) & 0xFFu), n.sz, bz), tfz = fmaf((float)((fzw >> (8 * c)) & 0xFFu), n.sz, bz);
         const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, 0.0f));
         const float tf = fminf(fminf(tfx, tfy), min_canonical(tfz, T.t));
-        const bool h = tn <= tf;
-        // entry distance (>= 0, so its bits order like an integer) with the slot in the low 2 bits; a missed child
-        // sorts behind every hit one (kMissKey | slot)
-#ifdef FS_NODE_VIEW
-        // ... with the slot's reference byte in the low 8 bits instead (one v_perm_b32: bytes 3 - 1 of the distance, byte c of
-        // G): the reference then comes OUT of the sort — cb8 + the sorted key's low byte — and nothing is dragged through it.
-        // The order of near-equal children may differ from the NodeQ4 path's; a closest hit does not depend on the order of
-        // the visits and an any-hit answer is a boolean.
-        key[c] = h ? __builtin_amdgcn_perm(__float_as_uint(tn), G, 0x07060500u + (uint32_t)c) : 0xFFFFFFFFu;
+        key[c] = tn <= tf ? NodeLayout::hit_key(N, tn, c) : NodeLayout::miss_key(c);
     }
-    // the same 5-comparator network as below, on the keys alone
-#define FS_KEYSWAP(a, b) { const uint32_t lo_ = min(key[a], key[b]), hi_ = max(key[a], key[b]); key[a] = lo_; key[b] = hi_; }
-    FS_KEYSWAP(0, 1) FS_KEYSWAP(2, 3) FS_KEYSWAP(0, 2) FS_KEYSWAP(1, 3) FS_KEYSWAP(1, 2)
-#undef FS_KEYSWAP
-    const int ref0 = (int)(cb8 + (key[0] & 0xFFu)), ref1 = (int)(cb8 + (key[1] & 0xFFu)), ref2 = (int)(cb8 + (key[2] & 0xFFu)),
-              ref3 = (int)(cb8 + (key[3] & 0xFFu));
-    constexpr uint32_t kMiss = kMissKeyView;
-#else
-        key[c] = h ? ((__float_as_uint(tn) & ~3u) | (uint32_t)c) : (kMissKey | (uint32_t)c);
-    }
-    int ref0 = __float_as_int(q3.x), ref1 = __float_as_int(q3.y), ref2 = __float_as_int(q3.z),
-        ref3 = __float_as_int(q3.w);
-    // sort the 4 (key, child reference) pairs, nearest first: 5-comparator network, branch-free.  (Measured in
-    // round 2: choosing only the nearest child and pushing the rest in slot order — also no ordering at all for
-    // visibility rays — saves a dozen instructions per visit and costs as much in extra visits: walk 0.356 ->
-    // 0.361 ms, connect 0.075 -> 0.078 ms.)
-#define FS_CSWAP(a, b) { const bool sw_ = key[b] < key[a]; const uint32_t lo_ = min(key[a], key[b]); \
-                         const uint32_t hi_ = max(key[a], key[b]); key[a] = lo_; key[b] = hi_; \
-                         const int ra_ = sw_ ? ref##b : ref##a; const int rb_ = sw_ ? ref##a : ref##b; \
-                         ref##a = ra_; ref##b = rb_; }
-    FS_CSWAP(0, 1) FS_CSWAP(2, 3) FS_CSWAP(0, 2) FS_CSWAP(1, 3) FS_CSWAP(1, 2)
-#undef FS_CSWAP
-    constexpr uint32_t kMiss = kMissKey;
-#endif
+    int ref0, ref1, ref2, ref3;   // the children's references, nearest first
+    NodeLayout::order(N, key, ref0, ref1, ref2, ref3);
+    constexpr uint32_t kMiss = NodeLayout::kMiss;
     // the number of children hit, read off the sorted keys: at least k + 1 <=> key[k] is a hit
     const bool h1 = key[0] < kMiss, h2 = key[1] < kMiss, h3 = key[2] < kMiss, h4 = key[3] < kMiss;
 #ifdef FS_TRAV_STATS
@@ -383,7 +437,7 @@ __device__ __forceinline__ void trav_node_part(const DeviceScene& sc, const Ray&
     stack[p2 * kBlock] = ref2;
     stack[p1 * kBlock] = ref1;
     T.sp = p1 + (h2 ? 1 : 0);
-    if (h1) T.cur = view_cursor(ref0);
+    if (h1) T.cur = NodeLayout::cursor(ref0);
     else trav_pop(sc, T, stack);
 }
 
@@ -440,16 +494,6 @@ __device__ __forceinline__ void trav_advance(const DeviceScene& sc, const Ray& r
     // otherwise move in front of the (to it unrelated) load instructions — and then fold the two register sets into one
     asm volatile("" : "+v"(cur.a), "+v"(cur.b), "+v"(cur.c));
     if (has_tri) trav_tri_part<ANY, IGN>(r, T, cur, tested, ignore_object);
-}
-
-// Before a traversal returns, every record it has requested must have landed: the compiler knows nothing of loads in
-// flight and would hand their destination registers to other values (an any-hit query ends with requests outstanding).
-__device__ __forceinline__ void trav_drain(NodeRegs& N, TriRegs& X, TriRegs& Y) {
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(N.q0), "+v"(N.q1), "+v"(N.q2),
-#ifndef FS_NODE_VIEW
-                                        "+v"(N.q3),
-#endif
-                                        "+v"(X.a), "+v"(X.b), "+v"(X.c), "+v"(Y.a), "+v"(Y.b), "+v"(Y.c));
 }
 
 // one ray per lane without work sharing (tests, tools, diagnostic builds); returns the number of steps taken
@@ -632,7 +676,7 @@ __device__ __forceinline__ bool trav_shared(const DeviceScene& sc, bool has_ray,
                         wr.nox = -(wr.ox * wr.ix); wr.noy = -(wr.oy * wr.iy); wr.noz = -(wr.oz * wr.iz);   // as make_ray
                     }
                     if (IGN) wign = A.rign[owner];
-                    T.cur = view_cursor(e); T.sp = 0; T.sb = 0; T.tri_i = 0; T.tri_n = 0;
+                    T.cur = NodeLayout::cursor(e); T.sp = 0; T.sb = 0; T.tri_i = 0; T.tri_n = 0;
                     T.t = canonical_bound(bound); T.leaf_index = -1; T.id = 0xFFFFFFFFu;
                     trav_deep_reset(sc, stack);   // (an any-hit query that ended early may have left entries there)
                     trav_settle(sc, T, stack);

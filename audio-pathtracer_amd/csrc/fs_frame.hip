@@ -31,10 +31,15 @@
 #else
 #define FS_LAUNCH_FRAME launch_frame_narrow
 #endif
-// The narrow flavours walk the 48-byte node view (fs_internal.hpp: ViewRec; fs_dev_trav.hpp): three node requests per visit
-// instead of four, child references out of the sort instead of through it.  launch_frame hands them a scene whose nodes,
-// tris and tri_nrm point at the view.
-#ifndef FS_FRAME_WIDE
+// The narrow flavours walk the 48-byte node view (fs_internal.hpp: ViewRec; fs_dev_trav.hpp: NodeLayoutView): three node
+// requests per visit instead of four, child references out of the sort instead of through it.  The macro only selects this
+// unit's NodeLayout; the launcher below, compiled with the kernel, binds the scene's arrays to whatever that layout walks.
+// The one-unit diagnostic build (fs_kernels_all.hip) has chosen its layout before it reaches this file: its narrow flavour
+// walks NodeQ4 like the rest of that unit.
+#if !defined(FS_FRAME_WIDE) && !defined(FS_KERNELS_ALL)
+#ifdef FS_TRAV_LAYOUT_CHOSEN
+#error "fs_frame.hip would define FS_NODE_VIEW after fs_dev_trav.hpp has been included: this unit's node layout is already chosen, and the kernel would not walk what its launcher binds"
+#endif
 #define FS_NODE_VIEW 1
 #endif
 #include "fs_dev_walk.hpp"
@@ -135,10 +140,12 @@ __global__ __launch_bounds__(kBlock, FS_FRAME_MIN_WAVES) void frame_kernel(Devic
     }
 }
 
+// false: the scene lacks the arrays this unit's layout walks (NodeLayoutView::bind); nothing is launched
 template <int B, bool SPECTRAL>
-void launch_frame_t(const DeviceScene& sc_in, uint32_t blocks, size_t lds, const FrameArgs& a, bool batch, hipStream_t s) {
+bool launch_frame_t(const DeviceScene& sc_in, uint32_t blocks, size_t lds, const FrameArgs& a, bool batch, hipStream_t s) {
     DeviceScene sc = sc_in;
-    if (!attach_deep(sc, blocks)) return;
+    if (!NodeLayout::bind(sc)) return false;
+    if (!attach_deep(sc, blocks)) return true;
     if (batch) {
         allow_lds(frame_kernel<B, true, SPECTRAL>, lds);
         hipLaunchKernelGGL((frame_kernel<B, true, SPECTRAL>), dim3(blocks), dim3(kBlock), lds, s, sc, a);
@@ -146,11 +153,11 @@ void launch_frame_t(const DeviceScene& sc_in, uint32_t blocks, size_t lds, const
         allow_lds(frame_kernel<B, false, SPECTRAL>, lds);
         hipLaunchKernelGGL((frame_kernel<B, false, SPECTRAL>), dim3(blocks), dim3(kBlock), lds, s, sc, a);
     }
+    return true;
 }
 template <int B>
-void launch_frame_b(const DeviceScene& sc, uint32_t blocks, size_t lds, const FrameArgs& a, bool batch, bool spectral, hipStream_t s) {
-    if (spectral) launch_frame_t<B, true>(sc, blocks, lds, a, batch, s);
-    else launch_frame_t<B, false>(sc, blocks, lds, a, batch, s);
+bool launch_frame_b(const DeviceScene& sc, uint32_t blocks, size_t lds, const FrameArgs& a, bool batch, bool spectral, hipStream_t s) {
+    return spectral ? launch_frame_t<B, true>(sc, blocks, lds, a, batch, s) : launch_frame_t<B, false>(sc, blocks, lds, a, batch, s);
 }
 
 }  // namespace
@@ -228,12 +235,11 @@ bool FS_LAUNCH_FRAME(int B, const DeviceScene& sc, const FrameParts& f, hipStrea
     const bool batch = f.has_connect && f.energy_tab;
     const bool spectral = f.num_recon > 0 && f.recon_carrier != nullptr;
     switch (B) {   // the band counts in use; 0 = kp.num_bands at run time (fs_connect.hip)
-        case 1: launch_frame_b<1>(sc, blocks, lds, a, batch, spectral, s); break;
-        case 4: launch_frame_b<4>(sc, blocks, lds, a, batch, spectral, s); break;
-        case 8: launch_frame_b<8>(sc, blocks, lds, a, batch, spectral, s); break;
-        default: launch_frame_b<0>(sc, blocks, lds, a, batch, spectral, s); break;
+        case 1: return launch_frame_b<1>(sc, blocks, lds, a, batch, spectral, s);
+        case 4: return launch_frame_b<4>(sc, blocks, lds, a, batch, spectral, s);
+        case 8: return launch_frame_b<8>(sc, blocks, lds, a, batch, spectral, s);
+        default: return launch_frame_b<0>(sc, blocks, lds, a, batch, spectral, s);
     }
-    return true;
 }
 
 #if !defined(FS_FRAME_WIDE) && !defined(FS_FRAME_EXT)
@@ -256,25 +262,19 @@ bool launch_frame(int B, const DeviceScene& sc, const FrameParts& f, hipStream_t
     if (dbg) std::fprintf(stderr, "[launch_frame] blocks %u stack_worst %d rows %d limit %d\n", blocks, sc.stack_worst, sc.stack_rows, sc.stack_limit);
     bool dense = f.num_walk == 0;
     for (int i = 0; i < f.num_walk; ++i) dense = dense || !(f.walk[i].wl.rays_per_wave > 0 && f.walk[i].wl.rays_per_wave < 64);
-    // The narrow flavour walks the 48-byte node view (FS_NODE_VIEW below the top of this file; fs_internal.hpp: ViewRec).  A
+    // Where the narrow flavour walks the 48-byte node view (this unit's NodeLayout: the narrow launchers bind it themselves), a
     // scene without one — too large for the view's offsets, a grid step that is no power of two — takes the wide flavour where
-    // its worst-case stack fits LDS, and otherwise leaves the launch to the callers' unfused passes: the same results, at
-    // another rate.
-    const NodeView view = sc.coop_info ? sc.coop_info->view : NodeView{};
-    const bool no_view = !view.rec && sc.num_nodes > 0;   // (an empty scene requests no record at all)
+    // its worst-case stack fits LDS, and otherwise leaves the launch to the callers' unfused passes (the narrow launcher
+    // refuses it): the same results, at another rate.
+    DeviceScene bound = sc;   // (asked of the layout itself, on a copy: the one definition of what a narrow launcher refuses)
+    const bool no_view = NodeLayout::kIsView && !NodeLayout::bind(bound);
     if (sc.stack_worst > 0 && (blocks < kFrameNarrowFromBlocks || !dense || no_view)) {
         DeviceScene w = sc;
         w.stack_rows = sc.stack_worst; w.stack_limit = sc.stack_worst; w.stack_attn = 0x7FFFFFFFu;
         w.deep = nullptr; w.deep_lanes = 0; w.deep_owner = nullptr;
         return wide(B, w, f, s, nullptr);
     }
-    if (no_view) return false;
-    if (!view.rec) return narrow(B, sc, f, s, nullptr);
-    DeviceScene v = sc;   // record 0 of the view is the root; triangle indices are record numbers from here on
-    v.nodes = reinterpret_cast<const NodeQ4*>(view.rec);
-    v.tris = reinterpret_cast<const Tri48*>(view.rec);
-    v.tri_nrm = view.nrm;
-    return narrow(B, v, f, s, nullptr);
+    return narrow(B, sc, f, s, nullptr);
 }
 #endif
 

@@ -81,25 +81,55 @@ struct CoopView {
     int16_t wshift, stack_need;
 };
 // The chip-filling flavour of the fused frame kernel walks a derived VIEW of the tree instead (fs_refit.hip: the view
-// kernels; fs_dev_trav.hpp: FS_NODE_VIEW): inner nodes and triangle records together in ONE array of 48-byte records, every
+// kernels; fs_dev_trav.hpp: NodeLayoutView): inner nodes and triangle records together in ONE array of 48-byte records, every
 // node's children — its inner children's node records and each leaf child's 1 - 4 triangle records, in slot order — one
 // consecutive block, the root record 0.  A node record is three 16-byte quarters,
 //   q0 = (origin.x, origin.y, origin.z, lox)   q1 = (loy, loz, hix, hiy)   q2 = (hiz, G, cb8, E)
-// the six plane words of its NodeQ4 verbatim; E = the float exponent bytes of the three grid steps (sx | sy << 8 | sz << 16:
-// the steps are powers of two, as_float(byte << 23) is the step bit for bit); cb8 = 8 x the record number of the first child
-// record; G = one byte per slot, 8 x (the slot's first record relative to the child block, <= 12) + 4 x leaf + (triangles - 1).
-// A reference is cb8 + the slot's byte: record number x 8 | leaf bit | count - 1.  The normals of the triangle records lie
-// in a parallel float4 array indexed by record number (node slots unused).  Rebuilt on the device behind every commit and
-// refit like CoopChild; NodeQ4 / Tri48 stay the tree format of everything else.
+// the six plane words of its NodeQ4 verbatim; E = one exponent byte per grid step (x | y << 8 | z << 16), cb8 = the reference
+// base of the child block, G = one slot byte per child; the words' formats are the view_* helpers below and nowhere else.
+// The normals of the triangle records lie in a parallel float4 array indexed by record number (node slots unused).  Rebuilt
+// on the device behind every commit and refit like CoopChild; NodeQ4 / Tri48 stay the tree format of everything else.
 struct alignas(16) ViewRec {
     float4 q0, q1, q2;
 };
 static_assert(sizeof(ViewRec) == sizeof(Tri48), "the view holds node and triangle records at one stride");
-// The size rule of the view: the request carries record x 48 as a 32-bit byte offset, and a reference (record x 8 + 7 at
-// most) must stay below 2^30 (fs_dev_trav.hpp keeps the leaf bit in the sign after a rotate by 3).
+// The size rule of the view: the request carries record x 48 as a 32-bit byte offset, and a reference must stay below 2^30
+// (the cursor keeps the leaf bit in the sign after the turn by kViewTurn).
 constexpr bool node_view_fits(uint64_t nodes, uint64_t tris) {
     return (nodes + tris) * sizeof(ViewRec) <= 0xFFFFFFFFull && nodes + tris <= (1ull << 27);
 }
+// The view's word formats (the builder, fs_refit.hip: view_nodes_kernel, and the step, fs_dev_trav.hpp: NodeLayoutView, both
+// use these; tests/tree_check.py restates them independently).
+//   slot byte (byte c of G)   8 x (the slot's first record relative to the child block, <= 12) + 4 x leaf + (triangles - 1)
+//   reference                 cb8 + the slot byte = record number x 8 | leaf bit | count - 1, where cb8 = 8 x the block's first record
+//   cursor (Trav::cur)        the reference turned right by 3: leaf bit 31 | count - 1 at 30:29 | record number — inner or
+//                             leaf is the sign, as it is for a NodeQ4 child
+//   exponent byte             bits 30:23 of a grid step, a positive normal power of two: as_float(byte << 23) is the step bit for bit
+constexpr uint32_t kViewTurn = 3, kViewLeaf = 1u << (kViewTurn - 1), kViewRecordBits = 32 - kViewTurn;
+constexpr uint32_t view_slot_byte(uint32_t offset, bool leaf, uint32_t count) {
+    return (offset << kViewTurn) + (leaf ? kViewLeaf + (count - 1u) : 0u);
+}
+constexpr uint32_t view_ref_base(uint32_t first_record) { return first_record << kViewTurn; }
+constexpr uint32_t view_ref(uint32_t cb8, uint32_t slot_byte) { return cb8 + slot_byte; }
+constexpr int32_t view_cursor(uint32_t ref) { return (int32_t)((ref >> kViewTurn) | (ref << kViewRecordBits)); }   // (one v_alignbit_b32)
+constexpr bool view_is_leaf(int32_t cur) { return cur < 0; }
+constexpr int32_t view_record(int32_t cur) { return cur & (int32_t)((1u << kViewRecordBits) - 1u); }
+constexpr int32_t view_count(int32_t cur) { return ((cur >> kViewRecordBits) & (int32_t)(kViewLeaf - 1u)) + 1; }
+constexpr uint32_t view_exp_byte(uint32_t step_bits) { return (step_bits >> 23) & 0xFFu; }
+constexpr uint32_t view_step_bits(uint32_t exp_byte) { return exp_byte << 23; }
+constexpr bool view_round_trip(uint32_t block, uint32_t offset, bool leaf, uint32_t count) {
+    const int32_t cur = view_cursor(view_ref(view_ref_base(block), view_slot_byte(offset, leaf, count)));
+    return view_is_leaf(cur) == leaf && view_record(cur) == (int32_t)(block + offset) && (!leaf || view_count(cur) == (int32_t)count);
+}
+static_assert(view_round_trip(0, 0, false, 1) && view_round_trip(0, 0, true, 1) && view_round_trip(0, 12, true, 4) &&
+              view_round_trip((1u << 27) - 13, 12, false, 1) && view_round_trip((1u << 27) - 1, 0, true, 4) &&
+              view_round_trip((1u << 27) - 13, 12, true, 1), "reference -> cursor at records 0 and 2^27 - 1, counts 1 and 4, offsets 0 and 12");
+static_assert(view_slot_byte(12, true, 4) <= 0xFFu, "a slot byte is a byte");
+static_assert(!node_view_fits((1u << 27) + 1, 0) && !node_view_fits(0, (1u << 27) + 1) &&
+              view_ref(view_ref_base((1u << 27) - 1), view_slot_byte(0, true, 4)) < (1u << 30),
+              "node_view_fits admits no record past 2^27 - 1, and the largest reference to that one stays below 2^30");
+static_assert(view_step_bits(view_exp_byte(0x3F800000u)) == 0x3F800000u && view_step_bits(view_exp_byte(0x00800000u)) == 0x00800000u &&
+              view_step_bits(view_exp_byte(0x7F000000u)) == 0x7F000000u, "a power-of-two step comes back from its exponent byte");
 struct NodeView {           // host bookkeeping; rec == null: the scene has no view (too large, a step that is no power of two)
     const ViewRec* rec = nullptr;      // [nodes + triangles]
     const float4* nrm = nullptr;       // [nodes + triangles]
@@ -146,8 +176,10 @@ constexpr int kUnboundedDepth = 1 << 24;   // the weights' depth cap when the wa
 constexpr int kOverLevels = 448;            // second-tier walk steps of depth = 0 frames (64 + 448 = 512 steps)
 
 // The traversal addresses `nodes` and `tris` by a scalar base and a 32-bit byte offset per lane (fs_dev_trav.hpp:
-// trav_issue): num_nodes * sizeof(NodeQ4) and num_tris * sizeof(Tri48) fit 32 bits in every view — a larger scene is
-// refused at commit (fs_capi_scene.cpp: finish_commit).
+// trav_issue): num_nodes * sizeof(NodeQ4) and num_tris * sizeof(Tri48) fit 32 bits — a larger scene is refused at commit
+// (fs_capi_scene.cpp: finish_commit).  What the three record arrays hold is the business of the kernel's node layout
+// (fs_dev_trav.hpp: NodeLayout): a launcher whose unit walks the 48-byte view binds its copy of the scene to the view's
+// arrays (NodeLayoutView::bind: nodes == tris == the ViewRec array, tri_nrm the view's normals); nobody else touches them.
 struct DeviceScene {
     const NodeQ4* nodes;
     const Tri48* tris;        // traversal records, leaf order

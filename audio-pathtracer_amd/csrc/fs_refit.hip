@@ -337,10 +337,11 @@ __global__ __launch_bounds__(kRefitBlock) void view_nodes_kernel(const NodeQ4* _
     for (int c = 0; c < 4; ++c) {
         const uint32_t k = view_slot_records(q, c);
         if (k == 0u) continue;
-        G |= (8u * off + (q.child[c] >= 0 ? 0u : 4u + (k - 1u))) << (8 * c);
+        G |= view_slot_byte(off, q.child[c] < 0, k) << (8 * c);
         off += k;
     }
-    // a step is as_float(exponent byte << 23): a positive normal power of two
+    // a step must come back from its exponent byte bit for bit (fs_internal.hpp: view_exp_byte / view_step_bits): a positive
+    // normal power of two.  (e keeps the sign bit above the byte: one shift serves the test and the byte.)
     const uint32_t sb[3] = {__float_as_uint(q.sx), __float_as_uint(q.sy), __float_as_uint(q.sz)};
     uint32_t E = 0;
     for (int k = 0; k < 3; ++k) {
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(kRefitBlock) void view_nodes_kernel(const NodeQ4* _
         if ((sb[k] & 0x807FFFFFu) != 0u || e == 0u || e == 255u) *bad = 1u;
         E |= (e & 0xFFu) << (8 * k);
     }
-    const uint32_t cb8 = 8u * (1u + scan[i]);
+    const uint32_t cb8 = view_ref_base(1u + scan[i]);
     ViewRec r;
     r.q0 = make_float4(q.ox, q.oy, q.oz, __uint_as_float(q.lox));
     r.q1 = make_float4(__uint_as_float(q.loy), __uint_as_float(q.loz), __uint_as_float(q.hix), __uint_as_float(q.hiy));
