@@ -13,7 +13,8 @@
 //   frame_resources  everything that allocates, waits or copies: state arrays, fixed-point buffers, batch tables —
 //                    works on the buffers the frame WILL use, without making them current
 //   frame_commit     the rotation: frame index, the sources' current energy buffer, batch table slot (cannot fail)
-//   frame_launch     the passes (or the fused launch of pipelined frames) and the bookkeeping
+//   frame_launch     the frame's passes as structs, then launch_held_frame (a pipelined frame: one fused-launch round,
+//                    fs_capi_pipeline.cpp) or launch_waited_frame (kernels of its own); the statistics
 namespace {
 
 // energy buffer b of the source exists (those beyond kEnergyBufsBase are allocated when the rotation first reaches them)
@@ -72,6 +73,19 @@ static bool sync_lane_plan(const fs_context* ctx, const KParams& kp, int* len, i
     if (b < 2 || (double)b + 4.0 > L) return false;
     *len = (int)std::lround(L); *bound = b;
     return true;
+}
+
+// May the pipeline hold a frame with these parameters (frame_describe; its sources permitting: no directivity, no order window)?
+// The default shape only — the fused launch has no form for anything else.
+// (a walk that ignores the actor it starts from — what the reference's GeneratePath always does, ARTS.cpp:322-327 — is held
+// like any other: the fused launch has a flavour whose walk parts carry the ignored actor, fs_frame_ext.hip)
+bool holdable(const fs_context* ctx, const fs_params* p) {
+    if (ctx->pipelining < 1 || ctx->profiling >= 2) return false;
+    if (p->flags & (FS_FLAG_MATERIAL_LOBES | FS_FLAG_MIS_BALANCE | FS_FLAG_ALL_CONNECTIONS | FS_FLAG_ACCUMULATE_ENERGY | FS_FLAG_DOUBLE_POSITIONS))
+        return false;
+    if (p->listener_radius > 0.0f || p->source_radius > 0.0f) return false;
+    const bool unbounded = p->depth == 0 && p->russian_roulette && p->rr_prob < 1.0f;
+    return p->depth > 0 || (unbounded && ctx->pipelining >= 2);
 }
 
 void frame_describe(fs_context* ctx, Frame& f) {
@@ -147,11 +161,7 @@ void frame_describe(fs_context* ctx, Frame& f) {
                                           FS_FLAG_DOUBLE_POSITIONS));
     // (a directional or windowed source: its connect pass has no fused form — the frame runs on its own, like FS_FLAG_DOUBLE_POSITIONS
     // frames; its walk is any other's, staged too when it is waited for)
-    const bool plain = plain_walk && !f.dir;
-    // (a walk that ignores the actor it starts from — what the reference's GeneratePath always does, ARTS.cpp:322-327 — is held
-    // like any other: the fused launch has a flavour whose walk parts carry the ignored actor, fs_frame_ext.hip)
-    f.pipe_ok = ctx->pipelining > 0 && ctx->profiling < 2 && plain && !(p->listener_radius > 0.0f || p->source_radius > 0.0f) &&
-                (p->depth > 0 || (f.unbounded && ctx->pipelining >= 2));
+    f.pipe_ok = holdable(ctx, p) && !f.dir;
     kp.plan_coop = (2ull * kp.num_local <= kPlanCoopMax || (f.unbounded && !f.pipe_ok && 2ull * kp.num_local <= kPlanCoopMaxUncapped)) ? 1 : 0;
     f.stages.clear();
     f.lane_len = 0;
@@ -326,7 +336,7 @@ int frame_resources(fs_context* ctx, Frame& f) {
             auto in_use = [&](int k) {
                 const char* dk = ctx->d_batch + (size_t)k * ctx->batch_cap;
                 for (const fs_context::PipeFrame& q : ctx->held)
-                    if (reinterpret_cast<const char*>(q.energy_tab) == dk) return true;
+                    if (reinterpret_cast<const char*>(q.connect.energy_tab) == dk) return true;
                 return false;
             };
             for (int tries = 0; tries < fs_context::kBatchSlots && in_use(slot); ++tries) {
@@ -365,134 +375,54 @@ void frame_commit(fs_context* ctx, Frame& f) {
     }
 }
 
-int frame_launch(fs_context* ctx, Frame& f) {
-    KParams& kp = f.kp;
-    SubpathState& st = f.st;
-    Source* s = f.srcs[0];
-    Source* const* srcs = f.srcs;
-    const int B = f.B, count = f.count;
-    const bool fixed = f.fixed, accumulate = f.accumulate;
-    unsigned* const scratch = f.scratch;
-    uint32_t* const perm_buf = f.perm_buf;
-    float* const* energy_tab = f.energy_tab;
-    unsigned long long* const* fixed_tab = f.fixed_tab;
-
+// What frame_launch prepares for either way a frame goes on: its three passes, and the event pair of a timed frame.
+struct FramePasses {
+    PlanPass plan;
+    bool plan_held = false;   // depth 2: the plan pass joins the fused launch (else it has been launched, or the frame has none)
+    WalkPart walk;            // (stage: the walk in one piece)
+    ConnectPass connect;
     TimedFrame tf{};
-    // level 1 may sample: events around every profile_interval-th frame only (an event pair costs the frame a few
-    // microseconds of queue bubbles — bench.py times every 8th frame of its timed region)
-    bool timed_frame = ctx->profiling && (ctx->profiling >= 2 || ctx->profile_interval <= 1 ||
-                                                (ctx->profile_tick++ % (unsigned)ctx->profile_interval) == 0);
-    if (timed_frame) {
-        resolve_completed_timings(ctx);
-        for (int i = 0; i < 5; ++i) tf.e[i] = nullptr;
-        tf.e[0] = take_event(ctx);
-        tf.e[1] = take_event(ctx);
-        if (ctx->profiling >= 2) tf.e[2] = take_event(ctx);
+    bool timed = false;
+};
+
+// A frame the pipeline holds (anything else has flushed the held frames before): it joins `held`, and one fused-launch round
+// (fs_capi_pipeline.cpp) carries its plan pass, or — depth 1 — its walk already.
+int launch_held_frame(fs_context* ctx, const Frame& f, FramePasses& ps) {
+    fs_context::PipeFrame me;
+    me.walk = ps.walk; me.connect = ps.connect; me.stages = f.stages; me.fixed = f.fixed;
+    me.items.resize((size_t)f.count);
+    for (int i = 0; i < f.count; ++i) {
+        me.items[(size_t)i].s = f.srcs[i]; me.items[(size_t)i].cur = f.cur_of[i];
+        if (f.group && f.group[i].want_recon) { me.items[(size_t)i].want_recon = true; me.items[(size_t)i].recon = f.group[i].recon; }
     }
-    // FlushEnergyBuffer ARTS.cpp:157-161 is folded into the plan pass (one launch); plain memset otherwise.
-    // Deterministic mode zeroes the fixed-point histogram instead (the fp32 buffer is rewritten from it).
-    float* zero_ptr = accumulate ? nullptr : (fixed ? reinterpret_cast<float*>(s->d_fixed[s->cur]) : s->energy());
-    const int zero_words = (fixed ? 2 : 1) * B * ctx->num_bins;
-    float* const* zero_tab = nullptr;   // batched frame: the table of buffers the plan pass zeroes
-    if (f.batch) {
-        zero_ptr = nullptr;
-        if (!accumulate) zero_tab = fixed ? reinterpret_cast<float* const*>(fixed_tab) : energy_tab;
+    FrameParts fp;
+    if (ps.plan_held) { fp.has_plan = true; fp.plan = ps.plan; }
+    // when the frame joins `held`: at depth 1 before the round — the plan pass ran on its own, the first stage of its walk goes
+    // now —, at depth 2 after it: planned by this launch, walked by the next ones
+    if (!ps.plan_held) ctx->held.push_back(std::move(me));
+    RoundCarried carried;
+    const int rc = fused_round(ctx, fp, /*draining=*/false, ps.timed ? ps.tf.e[1] : nullptr, &carried);   // (more frames follow: reconstructs may ride in their launches)
+    if (rc) return rc;
+    if (ps.plan_held) ctx->held.push_back(std::move(me));
+    if (ps.timed && !(carried.walk && carried.connect)) {
+        // a pipeline-fill launch (not every part yet) is not a sample of the frame kernel: the first event (recorded in front of
+        // the passes) drops out of the stream's timing, the round has not recorded the second; both go back to the pool unused
+        for (int i = 0; i < 3; ++i) if (ps.tf.e[i]) { ctx->free_events.push_back(ps.tf.e[i]); ps.tf.e[i] = nullptr; }
+        ps.timed = false;
     }
-    WalkLaunch wplan = ctx->walk;
-    wplan.queue_head = scratch;
-    wplan.perm = perm_buf;
-    bool sort = false;
-    const bool plan_runs = plan_shape(kp, wplan, nullptr, &sort);   // the plan pass (and the flush with it) runs for this frame
-    // (the second record tier relies on the schedule: the longest walks own the lowest slots)
-    const uint32_t* perm = plan_runs && sort ? perm_buf : nullptr;
-    if (!perm) st.slot_of = nullptr;   // no schedule: slot == subpath index
-    const bool plan_held = f.pipe_ok && ctx->pipelining >= 2 && plan_runs;   // depth 2: the pass joins the fused launch below
-    if (plan_runs && !plan_held)
-        (void)launch_plan(kp, wplan, zero_ptr, (zero_ptr || zero_tab) ? zero_words : 0, zero_tab, count, ctx->stream);
-    if (!plan_runs) {
-        if (zero_ptr) FS_HIP(ctx, hipMemsetAsync(zero_ptr, 0, sizeof(float) * (size_t)zero_words, ctx->stream));
-        for (int i = 0; i < count && zero_tab; ++i) {
-            float* zp = fixed ? reinterpret_cast<float*>(srcs[i]->d_fixed[f.cur_of[i]]) : srcs[i]->d_energy[f.cur_of[i]];
-            FS_HIP(ctx, hipMemsetAsync(zp, 0, sizeof(float) * (size_t)zero_words, ctx->stream));
-        }
-    }
-    if (!kp.russian_roulette) ctx->host_segments += 2ull * kp.num_local * (unsigned long long)kp.depth;   // no plan pass to count them
-    if (timed_frame) FS_HIP(ctx, hipEventRecord(tf.e[0], ctx->stream));
-    WalkLaunch wl = ctx->walk;
-    wl.queue_head = scratch;
-    // (a staged walk's first stage is a frame of walks of at most stages[0].end steps)
-    wl.rays_per_wave = ctx->walk_rays_per_wave > 0 ? ctx->walk_rays_per_wave
-                                                   : auto_rays_per_wave(2ull * kp.num_local, std::min(kp.depth, f.stages[0].end));
-    const int ppw = auto_pairs_per_wave(kp.num_local);
-    if (f.pipe_ok) {   // (anything else has flushed the held frames before)
-        fs_context::PipeFrame me;
-        me.kp = kp; me.st = st; me.wl = wl; me.perm = perm; me.stages = f.stages; me.next_stage = 0; me.fixed = fixed; me.ppw = ppw;
-        me.items.resize((size_t)count);
-        for (int i = 0; i < count; ++i) {
-            me.items[(size_t)i].s = srcs[i]; me.items[(size_t)i].cur = f.cur_of[i];
-            if (f.group && f.group[i].want_recon) { me.items[(size_t)i].want_recon = true; me.items[(size_t)i].recon = f.group[i].recon; }
-        }
-        me.energy_tab = energy_tab; me.fixed_tab = fixed_tab;
-        FrameParts fp;
-        // ONE launch: the plan pass of this frame (depth 2), the next walk stage of every held frame — oldest frame, i.e.
-        // latest stage, first: the few long walks that are left have the longest way to go — and the connect pass of the
-        // frame whose walk is complete.  Depth 1: the plan pass ran above, this frame's walk joins the launch right away.
-        if (plan_held) {
-            fp.has_plan = true; fp.kpp = kp; fp.wl_p = wplan; fp.scratch_p = scratch; fp.perm_p = sort ? perm_buf : nullptr;
-            fp.zero_p = zero_ptr; fp.zero_words_p = (zero_ptr || zero_tab) ? zero_words : 0; fp.zero_tab_p = zero_tab; fp.zero_count_p = count;
-        }
-        if (!plan_held) ctx->held.push_back(me);   // its first stage goes now
-        bool connects = false;
-        std::vector<size_t> advanced;
-        for (size_t k = 0; k < ctx->held.size(); ++k) {
-            fs_context::PipeFrame& q = ctx->held[k];
-            if (q.next_stage < (int)q.stages.size()) {
-                if (held_walk_part(ctx, q, fp)) advanced.push_back(k);
-            } else if (k == 0 && !connects) {
-                held_connect_part(q, fp);
-                connects = true;
-            }
-        }
-        if (timed_frame && !(fp.num_walk > 0 && fp.has_connect)) {
-            // a pipeline-fill launch (not every part yet) is not a sample of the frame kernel: take the first event back out
-            // of the stream's timing (it was recorded above; both go back to the pool unused)
-            for (int i = 0; i < 3; ++i) if (tf.e[i]) { ctx->free_events.push_back(tf.e[i]); tf.e[i] = nullptr; }
-            timed_frame = false;
-        }
-        OwedLaunch owed;   // the reconstructs of the frames the previous launch connected ride in this one
-        { const int orc = owed_prepare(ctx, fp, owed); if (orc) return orc; }
-        bool fused_launch = false;
-        if (fp.num_walk > 0 || fp.has_connect || fp.has_plan || fp.num_recon > 0) {
-            fused_launch = launch_frame(B, ctx->scene, fp, ctx->stream);
-            ctx->dbg.launches++;
-            if (!fused_launch) {   // no fused form: the same passes one after the other
-                if (fp.has_connect) launch_connect(B, ctx->scene, fp.kpc, fp.stc, fp.energy, fp.fixed, fp.scratch_c, fp.ppw, fp.energy_tab, fp.fixed_tab, ctx->stream);
-                for (int i = 0; i < fp.num_walk; ++i)
-                    launch_walk(ctx->scene, fp.walk[i].kp, fp.walk[i].st, fp.walk[i].wl, fp.walk[i].perm, ctx->stream, fp.walk[i].stage);
-                if (fp.has_plan) (void)launch_plan(kp, wplan, zero_ptr, (zero_ptr || zero_tab) ? zero_words : 0, zero_tab, count, ctx->stream);
-            }
-        }
-        if (timed_frame) FS_HIP(ctx, hipEventRecord(tf.e[1], ctx->stream));
-        FS_HIP(ctx, hipGetLastError());
-        const bool tail_behind = !owed.owed.empty();   // owed_publish makes the tail stream wait for this launch
-        { const int prc = owed_publish(ctx, owed, fused_launch); if (prc) return prc; }
-        for (size_t k : advanced) ctx->held[k].next_stage++;
-        if (connects) {
-            const fs_context::PipeFrame done = ctx->held.front();
-            ctx->held.pop_front();
-            const int rc = finish_held_frame(ctx, done, /*may_defer_recon=*/true, tail_behind);
-            if (rc) return rc;
-        }
-        if (plan_held) ctx->held.push_back(me);   // planned by this launch, walked by the next ones
-        if (timed_frame) { tf.has_trace = true; ctx->pending.push_back(tf); }
-        ctx->stats.frames += f.group ? (uint64_t)count : 1;
-        ctx->stats.pairs += kp.num_local;
-        ctx->stats.rays += 2ull * kp.num_local;
-        return FS_OK;
-    }
-    if (f.stages.size() > 1) {   // a staged walk that is waited for: its stages back to back
+    if (ps.timed) { ps.tf.has_trace = true; ctx->pending.push_back(ps.tf); }
+    return FS_OK;
+}
+
+// A frame that is waited for: its walk — in one piece, or the stages of a depth = 0 walk back to back — and its connect pass on
+// kernels of their own, the sum over the ranks behind them.
+int launch_waited_frame(fs_context* ctx, const Frame& f, FramePasses& ps) {
+    const KParams& kp = f.kp;
+    const uint32_t* const perm = ps.walk.perm;
+    TimedFrame& tf = ps.tf;
+    if (f.stages.size() > 1) {   // a staged walk: its stages back to back
         auto stage_launch_of = [&](size_t k) {
-            WalkLaunch wk = wl;
+            WalkLaunch wk = ps.walk.wl;
             if (ctx->walk_rays_per_wave <= 0)
                 // (profiles/r04_sync_stage_sweep4.jsonl: the first stage — everybody, at most `bound` steps — does best on waves of 16
                 // subpaths up to 64 000 of them and of 32 beyond: 0.80 / 0.94 ms per tick of 32 sources, 1.37 / 1.65 ms of 128,
@@ -513,9 +443,10 @@ int frame_launch(fs_context* ctx, Frame& f) {
             for (size_t k = 2; k < f.stages.size(); ++k)   // (the stages behind the second only have to SKIP the lane: any kernel but the dense one can)
                 if (stage_launch_of(k).rays_per_wave >= 64) lane_cap = 0;
         }
+        WalkPart w = ps.walk;
         for (size_t k = 0; k < f.stages.size(); ++k) {
-            WalkLaunch wk = stage_launch_of(k);
-            WalkStage sr = f.stages[k];
+            w.wl = stage_launch_of(k);
+            w.stage = f.stages[k];
             WalkLane ln;
             if (lane_cap > 0) {
                 ln.len = lane_len; ln.cap = lane_cap;
@@ -524,34 +455,96 @@ int frame_launch(fs_context* ctx, Frame& f) {
                 else if (k == 1 && split < (1 << 30)) { ln.begin = split; ln.end = 1 << 30; ln.mode = kLaneBoth; }
                 else ln.mode = kLaneSkip;
             }
-            launch_walk(ctx->scene, kp, st, wk, perm, ctx->stream, sr, ln);
+            launch_walk(ctx->scene, w, ctx->stream, ln);
         }
     } else {
-        launch_walk(ctx->scene, kp, st, wl, perm, ctx->stream);
+        launch_walk(ctx->scene, ps.walk, ctx->stream);
     }
-    if (timed_frame) FS_HIP(ctx, hipEventRecord(tf.e[1], ctx->stream));
-    if (f.all_conn)
-        launch_connect_all(B, ctx->scene, kp, st, s->energy(), fixed ? s->d_fixed[s->cur] : nullptr, scratch, ctx->stream,
-                           f.dir ? &f.dargs : nullptr);
-    else
-        launch_connect(B, ctx->scene, kp, st, s->energy(), fixed ? s->d_fixed[s->cur] : nullptr, scratch, ppw,
-                       energy_tab, fixed_tab, ctx->stream, f.dir ? &f.dargs : nullptr);
-    if (fixed)
-        for (int i = 0; i < count; ++i)
-            launch_fixed_to_energy(srcs[i]->d_fixed[srcs[i]->cur], srcs[i]->energy(), B * ctx->num_bins, ctx->stream);
+    if (ps.timed) FS_HIP(ctx, hipEventRecord(tf.e[1], ctx->stream));
+    const DirArgs* const dir = f.dir ? &f.dargs : nullptr;
+    if (f.all_conn) launch_connect_all(f.B, ctx->scene, ps.connect, ctx->stream, dir);
+    else launch_connect(f.B, ctx->scene, ps.connect, ctx->stream, dir);
+    if (f.fixed)
+        for (int i = 0; i < f.count; ++i)
+            launch_fixed_to_energy(f.srcs[i]->d_fixed[f.srcs[i]->cur], f.srcs[i]->energy(), f.B * ctx->num_bins, ctx->stream);
     FS_HIP(ctx, hipGetLastError());
-    if (timed_frame) {
+    if (ps.timed) {
         if (tf.e[2]) FS_HIP(ctx, hipEventRecord(tf.e[2], ctx->stream));
         tf.has_trace = true;
         ctx->pending.push_back(tf);
     }
-    ctx->stats.frames++;
-    ctx->stats.pairs += kp.num_local;
-    ctx->stats.rays += 2ull * kp.num_local;
     // multi-GPU: the sum over the ranks (ARTS.cpp:164-173 deposits ALL pairs into the one buffer) runs on the tail
     // stream right behind the deposit, concurrently with whatever the compute stream traces next
     if (ctx->comm)
-        for (int i = 0; i < count; ++i) { const int rr = reduce_energy(ctx, srcs[i]); if (rr) return rr; }
+        for (int i = 0; i < f.count; ++i) { const int rr = reduce_energy(ctx, f.srcs[i]); if (rr) return rr; }
+    return FS_OK;
+}
+
+int frame_launch(fs_context* ctx, Frame& f) {
+    const KParams& kp = f.kp;
+    Source* s = f.srcs[0];
+    const int cur = f.cur_of[0];   // (== s->cur, except where a grouped frame has a later item of the same source)
+    const bool fixed = f.fixed;
+    FramePasses ps;
+    TimedFrame& tf = ps.tf;
+    // level 1 may sample: events around every profile_interval-th frame only (an event pair costs the frame a few
+    // microseconds of queue bubbles — bench.py times every 8th frame of its timed region)
+    ps.timed = ctx->profiling && (ctx->profiling >= 2 || ctx->profile_interval <= 1 ||
+                                  (ctx->profile_tick++ % (unsigned)ctx->profile_interval) == 0);
+    if (ps.timed) {
+        resolve_completed_timings(ctx);
+        for (int i = 0; i < 5; ++i) tf.e[i] = nullptr;
+        tf.e[0] = take_event(ctx);
+        tf.e[1] = take_event(ctx);
+        if (ctx->profiling >= 2) tf.e[2] = take_event(ctx);
+    }
+    // FlushEnergyBuffer ARTS.cpp:157-161 is folded into the plan pass (one launch); plain memset otherwise.
+    // Deterministic mode zeroes the fixed-point histogram instead (the fp32 buffer is rewritten from it).
+    PlanPass& plan = ps.plan;
+    plan.kp = kp;
+    plan.wl = ctx->walk;
+    plan.wl.queue_head = f.scratch;
+    plan.wl.perm = f.perm_buf;
+    plan.zero_count = f.count;
+    if (!f.accumulate) {
+        if (f.batch) plan.zero_tab = fixed ? reinterpret_cast<float* const*>(f.fixed_tab) : f.energy_tab;   // batched frame: the table of buffers the plan pass zeroes
+        else plan.zero = fixed ? reinterpret_cast<float*>(s->d_fixed[cur]) : s->d_energy[cur];
+    }
+    const int zero_words = (fixed ? 2 : 1) * f.B * ctx->num_bins;
+    plan.zero_words = (plan.zero || plan.zero_tab) ? zero_words : 0;
+    bool sort = false;
+    const bool plan_runs = plan_shape(kp, plan.wl, nullptr, &sort);   // the plan pass (and the flush with it) runs for this frame
+    // (the second record tier relies on the schedule: the longest walks own the lowest slots)
+    const uint32_t* perm = plan_runs && sort ? f.perm_buf : nullptr;
+    if (!perm) f.st.slot_of = nullptr;   // no schedule: slot == subpath index
+    ps.plan_held = f.pipe_ok && ctx->pipelining >= 2 && plan_runs;   // depth 2: the pass joins the fused launch
+    if (plan_runs && !ps.plan_held) (void)launch_plan(plan, ctx->stream);
+    if (!plan_runs) {
+        if (plan.zero) FS_HIP(ctx, hipMemsetAsync(plan.zero, 0, sizeof(float) * (size_t)zero_words, ctx->stream));
+        for (int i = 0; i < f.count && plan.zero_tab; ++i) {
+            float* zp = fixed ? reinterpret_cast<float*>(f.srcs[i]->d_fixed[f.cur_of[i]]) : f.srcs[i]->d_energy[f.cur_of[i]];
+            FS_HIP(ctx, hipMemsetAsync(zp, 0, sizeof(float) * (size_t)zero_words, ctx->stream));
+        }
+    }
+    if (!kp.russian_roulette) ctx->host_segments += 2ull * kp.num_local * (unsigned long long)kp.depth;   // no plan pass to count them
+    if (ps.timed) FS_HIP(ctx, hipEventRecord(tf.e[0], ctx->stream));
+    WalkPart& walk = ps.walk;
+    walk.kp = kp; walk.st = f.st; walk.perm = perm;
+    walk.wl = ctx->walk;
+    walk.wl.queue_head = f.scratch;
+    // (a staged walk's first stage is a frame of walks of at most stages[0].end steps)
+    walk.wl.rays_per_wave = ctx->walk_rays_per_wave > 0 ? ctx->walk_rays_per_wave
+                                                        : auto_rays_per_wave(2ull * kp.num_local, std::min(kp.depth, f.stages[0].end));
+    ConnectPass& connect = ps.connect;
+    connect.kp = kp; connect.st = f.st;
+    connect.energy = s->d_energy[cur]; connect.fixed = fixed ? s->d_fixed[cur] : nullptr;
+    connect.scratch = f.scratch; connect.pairs_per_wave = auto_pairs_per_wave(kp.num_local);
+    connect.energy_tab = f.energy_tab; connect.fixed_tab = f.fixed_tab;
+    const int rc = f.pipe_ok ? launch_held_frame(ctx, f, ps) : launch_waited_frame(ctx, f, ps);
+    if (rc) return rc;
+    ctx->stats.frames += f.group ? (uint64_t)f.count : 1;
+    ctx->stats.pairs += kp.num_local;
+    ctx->stats.rays += 2ull * kp.num_local;
     return FS_OK;
 }
 
@@ -573,16 +566,10 @@ int trace_sources(fs_context* ctx, Source* const* srcs, int count, const fs_para
     return frame_launch(ctx, f);
 }
 
-// may a frame with these parameters wait in the group (fs_set_frames_per_launch)?  Exactly what frame_describe lets the
-// pipeline hold, and small enough for 32-bit subpath indices when frames_per_launch of them share a launch
+// may a frame with these parameters wait in the group (fs_set_frames_per_launch)?  What the pipeline can hold, and small
+// enough for 32-bit subpath indices when frames_per_launch of them share a launch
 bool groupable(const fs_context* ctx, const fs_params* p) {
-    if (ctx->frames_per_launch < 2 || ctx->pipelining < 1 || ctx->profiling >= 2) return false;
-    if (p->flags & (FS_FLAG_MATERIAL_LOBES | FS_FLAG_MIS_BALANCE | FS_FLAG_ALL_CONNECTIONS | FS_FLAG_ACCUMULATE_ENERGY | FS_FLAG_DOUBLE_POSITIONS))
-        return false;
-    if (p->listener_radius > 0.0f || p->source_radius > 0.0f) return false;
-    const bool unbounded = p->depth == 0 && p->russian_roulette && p->rr_prob < 1.0f;
-    if (!(p->depth > 0 || (unbounded && ctx->pipelining >= 2))) return false;
-    return (uint64_t)ctx->frames_per_launch * (p->num_rays / 2) <= (1ull << 29);
+    return ctx->frames_per_launch >= 2 && holdable(ctx, p) && (uint64_t)ctx->frames_per_launch * (p->num_rays / 2) <= (1ull << 29);
 }
 // the same frame but for the low seed word?
 bool same_but_seed(const fs_params& a, const fs_params& b) {

@@ -1,6 +1,7 @@
 // fs_capi_pipeline.cpp — pipelined frames (fs_set_pipelining / fs_set_frames_per_launch): what a held frame still owes once its
-// connect pass has been enqueued, the parts a held frame contributes to a fused launch, and the flush — the pipeline drained
-// through fused launches (drain_fused) or, where that does not apply, every held frame on kernels of its own.
+// connect pass has been enqueued, the parts a held frame contributes to a fused launch, the ONE round that assembles and issues
+// such a launch (fused_round: the hot call's, fs_capi_frame.cpp, and the drain's), and the flush — the pipeline drained through
+// such rounds (drain_fused) or, where that does not apply, every held frame on kernels of its own.
 // Split out of fs_capi_frame.cpp in round 5; the reconstruct / publish machinery is fs_capi_publish.cpp.
 #include "fs_context.hpp"
 
@@ -44,12 +45,13 @@ int check_overflow(fs_context* ctx) {
 // What a held frame still owes once its connect pass has been enqueued: the fixed-point -> fp32 rounding, the sum over
 // the ranks, and the reconstruct the caller asked for in the meantime.  The source may already have moved on to later
 // frames (cur rotated): the per-frame fields are switched back for the duration.
-int finish_held_frame(fs_context* ctx, const fs_context::PipeFrame& q, bool may_defer_recon, bool tail_waits_already, bool draining) {
+int finish_held_frame(fs_context* ctx, const fs_context::PipeFrame& q, bool may_defer_recon, bool draining) {
     // the items of a frame were connected by ONE launch: once the tail stream waits behind it (the first item's handoff),
     // the other items' reconstructs are ordered too — no further event pairs on the compute stream (each is a bubble
     // between its launches).  Not in deterministic mode: every item's fixed-point rounding runs on the compute stream first.
-    // (tail_waits_already: the publishes of this very launch's reconstruct parts made the tail stream wait behind it)
-    bool tail_behind_launch = tail_waits_already;
+    // (Nothing but that handoff orders the tail stream behind the launch: the reconstruct parts it carried publish through the
+    // host word, owed_prepare / owed_publish enqueue nothing on the tail stream — so the first item always hands over.)
+    bool tail_behind_launch = false;
     const bool flushing = !may_defer_recon || draining;   // called by flush_pending: nothing will be launched behind this frame that its reconstructs could overlap
     // the reconstructs of a frame ride in the next launch all together or not at all (a tail-stream reconstruct in between
     // would have to run the deferred ones first, to keep the IRs in frame order)
@@ -58,11 +60,7 @@ int finish_held_frame(fs_context* ctx, const fs_context::PipeFrame& q, bool may_
     if (wanted + (int)ctx->recon_owed.size() > kMaxReconParts) may_defer_recon = false;   // (256: one table slot)
     for (const fs_context::PipeFrame::Item& it : q.items) {
         Source* s = it.s;
-        const bool moved_on = s->cur != it.cur;
-        const int cur = s->cur;
-        const bool cur_fixed = s->cur_fixed, reduced = s->reduced, handed_off = s->handed_off, tail_ordered = s->tail_ordered;
-        s->cur = it.cur; s->cur_fixed = q.fixed; s->reduced = false; s->handed_off = false;
-        s->tail_ordered = tail_behind_launch && !q.fixed;
+        const SourceFrameScope frame(s, it.cur, q.fixed, /*reduced=*/false, tail_behind_launch && !q.fixed, /*keep_if_current=*/true);
         int rc = FS_OK;
         if (q.fixed) launch_fixed_to_energy(s->d_fixed[s->cur], s->energy(), ctx->cfg.num_bands * ctx->num_bins, ctx->stream);
         if (ctx->comm) { rc = reduce_energy(ctx, s); if (!rc && s->tail_ordered) tail_behind_launch = true; }
@@ -85,39 +83,79 @@ int finish_held_frame(fs_context* ctx, const fs_context::PipeFrame& q, bool may_
                 if (!rc && s->tail_ordered) tail_behind_launch = true;
             }
         }
-        if (moved_on) { s->cur = cur; s->cur_fixed = cur_fixed; s->reduced = reduced; s->handed_off = handed_off; s->tail_ordered = tail_ordered; }
         if (rc) return rc;
     }
     return FS_OK;
 }
 
-void held_connect_part(const fs_context::PipeFrame& q, FrameParts& f) {
-    const fs_context::PipeFrame::Item& it = q.items[0];
-    f.has_connect = true; f.kpc = q.kp; f.stc = q.st; f.energy = it.s->d_energy[it.cur];
-    f.fixed = q.fixed ? it.s->d_fixed[it.cur] : nullptr; f.scratch_c = q.wl.queue_head; f.ppw = q.ppw;
-    f.energy_tab = q.energy_tab; f.fixed_tab = q.fixed_tab;
+// a held frame's connect pass as a part of the launch
+static void held_connect_part(const fs_context::PipeFrame& q, FrameParts& f) {
+    f.has_connect = true;
+    f.connect = q.connect;
 }
 
-// rays per wave of a walk stage: by the number of walks it still has and the steps they have left at most
+// the next stage of a held frame's walk as a part of the launch; false: the launch has no room for more walk parts
 constexpr uint32_t kStageDenseFrom = 4096;   // stages with at least this many (provisioned) walks use dense waves
-WalkLaunch stage_launch(const fs_context* ctx, const fs_context::PipeFrame& q, int stage) {
-    WalkLaunch wl = q.wl;
-    const WalkStage& sr = q.stages[(size_t)stage];
+static bool held_walk_part(const fs_context* ctx, const fs_context::PipeFrame& q, FrameParts& f) {
+    if (f.num_walk >= kMaxWalkParts) return false;
+    WalkPart& w = f.walk[f.num_walk++];
+    w = q.walk;
+    w.stage = q.stages[(size_t)q.next_stage];
+    // rays per wave of a later stage: by the number of walks it still has and the steps they have left at most.
     // inside a fused launch the chip is full: dense waves for every stage that still has a few thousand walks, sparse
     // waves (the other lanes help with every query) only for the few long walks of the late stages, whose chain of
     // dependent bounces is what matters (profiles/r03_stage_sweep.log: the stand-alone frames' rule — ~4096 sparse waves
     // for mid-size frames — costs 0.87 instead of 0.63 ms per frame here; raising the late stages' wave priority: nothing)
-    if (sr.begin > 0 && ctx->walk_rays_per_wave <= 0)
-        wl.rays_per_wave = walk_stage_slots(q.kp, sr.begin) >= kStageDenseFrom ? 64 : 16;
-    return wl;
+    if (w.stage.begin > 0 && ctx->walk_rays_per_wave <= 0)
+        w.wl.rays_per_wave = walk_stage_slots(w.kp, w.stage.begin) >= kStageDenseFrom ? 64 : 16;
+    return true;
 }
 
-// the next stage of a held frame's walk as a part of the fused launch; false: the launch has no room for more walk parts
-bool held_walk_part(const fs_context* ctx, const fs_context::PipeFrame& q, FrameParts& f) {
-    if (f.num_walk >= kMaxWalkParts) return false;
-    WalkPart& w = f.walk[f.num_walk++];
-    w.kp = q.kp; w.st = q.st; w.wl = stage_launch(ctx, q, q.next_stage); w.perm = q.perm; w.stage = q.stages[(size_t)q.next_stage];
-    return true;
+// The passes of a launch one after the other on the compute stream: what a round does when the fused launch has no form for its
+// parts, and how flush_pending finishes a held frame on kernels of its own.  The connect part first — in a round it belongs to the
+// oldest frame —, then the walks, then the newest frame's plan pass.
+static void launch_unfused(fs_context* ctx, const FrameParts& fp) {
+    if (fp.has_connect) launch_connect(ctx->cfg.num_bands, ctx->scene, fp.connect, ctx->stream);
+    for (int i = 0; i < fp.num_walk; ++i) launch_walk(ctx->scene, fp.walk[i], ctx->stream);
+    if (fp.has_plan) (void)launch_plan(fp.plan, ctx->stream);
+}
+
+// ONE launch: the parts the caller has preset (the plan pass of the frame call's own frame at depth 2), the next walk stage of
+// every held frame — oldest frame, i.e. latest stage, first: the few long walks that are left have the longest way to go —, the
+// connect pass of the frame whose walk is complete, and the reconstructs of the frames the previous launch connected.
+int fused_round(fs_context* ctx, FrameParts& fp, bool draining, hipEvent_t end_event, RoundCarried* carried) {
+    bool connects = false;
+    size_t advanced[kMaxWalkParts];
+    int num_advanced = 0;
+    for (size_t k = 0; k < ctx->held.size(); ++k) {
+        const fs_context::PipeFrame& q = ctx->held[k];
+        if (q.next_stage < (int)q.stages.size()) {
+            if (held_walk_part(ctx, q, fp)) advanced[num_advanced++] = k;
+        } else if (k == 0 && !connects) {
+            held_connect_part(q, fp);
+            connects = true;
+        }
+    }
+    carried->walk = fp.num_walk > 0; carried->connect = fp.has_connect;
+    OwedLaunch owed;   // the reconstructs of the frames the previous launch connected ride in this one
+    { const int orc = owed_prepare(ctx, fp, owed); if (orc) return orc; }
+    carried->any = fp.num_walk > 0 || fp.has_connect || fp.has_plan || fp.num_recon > 0;
+    if (!carried->any) return FS_OK;
+    const bool fused = launch_frame(ctx->cfg.num_bands, ctx->scene, fp, ctx->stream);
+    ctx->dbg.launches++;
+    if (!fused) launch_unfused(ctx, fp);   // no fused form: the same passes one after the other
+    // (a pipeline-fill launch — not every part yet — is not a sample of the frame kernel)
+    if (end_event && carried->walk && carried->connect) FS_HIP(ctx, hipEventRecord(end_event, ctx->stream));
+    FS_HIP(ctx, hipGetLastError());
+    { const int prc = owed_publish(ctx, owed, fused); if (prc) return prc; }
+    for (int i = 0; i < num_advanced; ++i) ctx->held[advanced[i]].next_stage++;
+    if (connects) {
+        const fs_context::PipeFrame done = std::move(ctx->held.front());
+        ctx->held.pop_front();
+        const int rc = finish_held_frame(ctx, done, /*may_defer_recon=*/true, draining);
+        if (rc) return rc;
+    }
+    return FS_OK;
 }
 
 // A flush on one GPU drains the pipeline through the SAME fused launches the stream of frames uses, only without a newest frame:
@@ -126,45 +164,19 @@ bool held_walk_part(const fs_context* ctx, const fs_context::PipeFrame& q, Frame
 // (Until round 5 every held frame finished on kernels of its own, one after the other: walk, connect, reconstruct, walk, ... —
 // six kernels in a row behind a stream of cfg3 frames, 0.4 ms of the driver's 5.9 ms timed region.)
 static int drain_fused(fs_context* ctx) {
-    const int B = ctx->cfg.num_bands;
     bool counted = false;
     for (int guard = 0; (!ctx->held.empty() || !ctx->recon_owed.empty()) && guard < 8 * (kMaxWalkParts + 4); ++guard) {
         if (!counted && !ctx->held.empty()) { ctx->dbg.flushes++; ctx->dbg.flushed_frames += ctx->held.size(); counted = true; }
-        FrameParts fp;
-        bool connects = false;
-        std::vector<size_t> advanced;
-        for (size_t k = 0; k < ctx->held.size(); ++k) {
-            fs_context::PipeFrame& q = ctx->held[k];
-            if (q.next_stage < (int)q.stages.size()) {
-                if (held_walk_part(ctx, q, fp)) advanced.push_back(k);
-            } else if (k == 0 && !connects) {
-                held_connect_part(q, fp);
-                connects = true;
-            }
-        }
-        OwedLaunch owed;
-        { const int orc = owed_prepare(ctx, fp, owed); if (orc) return orc; }
-        if (!(fp.num_walk > 0 || fp.has_connect || fp.num_recon > 0)) {
+        FrameParts fp;   // nothing preset: a drain has no newest frame
+        RoundCarried carried;
+        // (draining: nothing will be launched behind the last round that a connected frame's reconstruct could overlap; no timed frame)
+        const int rc = fused_round(ctx, fp, /*draining=*/true, nullptr, &carried);
+        if (rc) return rc;
+        if (!carried.any) {
             // nothing a launch could carry.  With a communicator the reconstructs of the frames just summed become due one round
             // later (ReconOwed::age, raised by owed_prepare): go round again; anything else is left to the loop in flush_pending.
             if (!ctx->recon_owed.empty() && ctx->recon_owed.front().reduced && ctx->recon_owed.front().age >= 1) continue;
             break;
-        }
-        const bool fused = launch_frame(B, ctx->scene, fp, ctx->stream);
-        ctx->dbg.launches++;
-        if (!fused) {   // no fused form: the same passes one after the other
-            if (fp.has_connect) launch_connect(B, ctx->scene, fp.kpc, fp.stc, fp.energy, fp.fixed, fp.scratch_c, fp.ppw, fp.energy_tab, fp.fixed_tab, ctx->stream);
-            for (int i = 0; i < fp.num_walk; ++i)
-                launch_walk(ctx->scene, fp.walk[i].kp, fp.walk[i].st, fp.walk[i].wl, fp.walk[i].perm, ctx->stream, fp.walk[i].stage);
-        }
-        FS_HIP(ctx, hipGetLastError());
-        { const int prc = owed_publish(ctx, owed, fused); if (prc) return prc; }
-        for (size_t k : advanced) ctx->held[k].next_stage++;
-        if (connects) {
-            const fs_context::PipeFrame done = ctx->held.front();
-            ctx->held.pop_front();
-            const int rc = finish_held_frame(ctx, done, /*may_defer_recon=*/true, false, /*draining=*/true);
-            if (rc) return rc;
         }
     }
     return FS_OK;
@@ -192,15 +204,17 @@ int flush_pending(fs_context* ctx) {
     ctx->dbg.flushes++; ctx->dbg.flushed_frames += ctx->held.size();
     long us_launch = 0, us_finish = 0;
     while (!ctx->held.empty()) {
-        const fs_context::PipeFrame q = ctx->held.front();
+        fs_context::PipeFrame q = ctx->held.front();
         ctx->held.pop_front();
         clk::time_point a, b, c;
         if (dbg) a = clk::now();
-        for (int k = q.next_stage; k < (int)q.stages.size(); ++k)
-            launch_walk(ctx->scene, q.kp, q.st, stage_launch(ctx, q, k), q.perm, ctx->stream, q.stages[(size_t)k]);
-        launch_connect(ctx->cfg.num_bands, ctx->scene, q.kp, q.st, q.items[0].s->d_energy[q.items[0].cur],
-                       q.fixed ? q.items[0].s->d_fixed[q.items[0].cur] : nullptr, q.wl.queue_head, q.ppw, q.energy_tab, q.fixed_tab,
-                       ctx->stream);
+        // (the frame's OWN connect pass follows its walk: two sets of parts, the stages that are left, then the connect pass)
+        FrameParts fp;
+        for (; q.next_stage < (int)q.stages.size(); ++q.next_stage) (void)held_walk_part(ctx, q, fp);   // (a frame has at most kMaxWalkParts stages)
+        launch_unfused(ctx, fp);
+        fp.num_walk = 0;
+        held_connect_part(q, fp);
+        launch_unfused(ctx, fp);
         FS_HIP(ctx, hipGetLastError());
         if (dbg) b = clk::now();
         const int rc = finish_held_frame(ctx, q);

@@ -282,13 +282,9 @@ int run_owed_reconstructs(fs_context* ctx) {
     owed.swap(ctx->recon_owed);
     ctx->dbg.owed_on_tail += owed.size();
     for (const fs_context::ReconOwed& o : owed) {
-        Source* s = o.s;
-        const int cur = s->cur;
-        const bool cur_fixed = s->cur_fixed, reduced = s->reduced, handed_off = s->handed_off, tail_ordered = s->tail_ordered;
-        s->cur = o.cur; s->cur_fixed = o.fixed; s->reduced = o.reduced; s->handed_off = false;
-        s->tail_ordered = o.reduced;   // (the tail stream is behind the all-reduce, which is behind the launch)
-        const int rc = flush_reconstruct(ctx, s, &o.p);
-        s->cur = cur; s->cur_fixed = cur_fixed; s->reduced = reduced; s->handed_off = handed_off; s->tail_ordered = tail_ordered;
+        // (tail_ordered = o.reduced: the tail stream is behind the all-reduce, which is behind the launch)
+        const SourceFrameScope frame(o.s, o.cur, o.fixed, o.reduced, /*tail_ordered=*/o.reduced, /*keep_if_current=*/false);
+        const int rc = flush_reconstruct(ctx, o.s, &o.p);
         if (rc) return rc;
     }
     return FS_OK;

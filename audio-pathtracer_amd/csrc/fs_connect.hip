@@ -111,17 +111,17 @@ __global__ __launch_bounds__(kBlock) void fixed_to_energy_kernel(const unsigned 
 constexpr int kConnectAhead = 4;
 
 template <int B>
-void launch_connect_t(const DeviceScene& sc_in, const KParams& kp, const SubpathState& st, float* energy,
-                      unsigned long long* fixed, unsigned* queue_head, int pairs_per_wave, float* const* energy_tab,
-                      unsigned long long* const* fixed_tab, hipStream_t s, const DirArgs* dir) {
+void launch_connect_t(const DeviceScene& sc_in, const ConnectPass& c, hipStream_t s, const DirArgs* dir) {
+    // (the kernels' arguments, in their order)
+    const KParams& kp = c.kp;
+    const SubpathState& st = c.st;
+    float* const energy = c.energy; unsigned long long* const fixed = c.fixed; unsigned* const queue_head = c.scratch;
+    float* const* const energy_tab = c.energy_tab; unsigned long long* const* const fixed_tab = c.fixed_tab;
     if (kp.num_local == 0) return;
     DeviceScene sc = sc_in;
-    if (pairs_per_wave < 1 || pairs_per_wave > 64) pairs_per_wave = 64;
-    const uint32_t per_block = (uint32_t)pairs_per_wave * (kBlock / 64);
+    const int pairs_per_wave = c.pairs_per_wave < 1 || c.pairs_per_wave > 64 ? 64 : c.pairs_per_wave;
     const bool batch = energy_tab != nullptr;
-    uint32_t blocks = batch ? (kp.num_local / kp.pairs_per_source) * ((kp.pairs_per_source + per_block - 1) / per_block)
-                            : (kp.num_local + per_block - 1) / per_block;
-    if (blocks > 1024) blocks = 1024;
+    const uint32_t blocks = std::min<uint32_t>(connect_blocks_wanted(kp.num_local, kp.pairs_per_source, pairs_per_wave, batch), 1024u);
     if (!attach_deep(sc, blocks)) return;
     size_t lds = stack_bytes(sc) + sizeof(float) * (size_t)kp.num_bands * (size_t)kp.hist_window + kShareAnyLdsBytes;
 #define FS_LAUNCH_CONNECT(L, BT, CN)                                                                                 \
@@ -132,7 +132,7 @@ void launch_connect_t(const DeviceScene& sc_in, const KParams& kp, const Subpath
     } while (0)
     // a directional source: the EXT pass's shape (run-time band count and lobes) through the directional entry
     if (dir) {
-        if (B != 0) return launch_connect_t<0>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir);
+        if (B != 0) return launch_connect_t<0>(sc, c, s, dir);
         if (batch) {
             allow_lds(connect_dir_kernel<0, -1, true, false, true>, lds);
             hipLaunchKernelGGL((connect_dir_kernel<0, -1, true, false, true>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed,
@@ -146,7 +146,7 @@ void launch_connect_t(const DeviceScene& sc_in, const KParams& kp, const Subpath
     }
     // FS_FLAG_DOUBLE_POSITIONS / end-point collision spheres: one instantiation pair with the run-time band count and run-time lobes
     if (kp.dpos || kp.listener_radius > 0.0f || kp.source_radius > 0.0f) {
-        if (B != 0) return launch_connect_t<0>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir);
+        if (B != 0) return launch_connect_t<0>(sc, c, s, dir);
         if (batch) {
             allow_lds(connect_kernel<0, -1, true, false, true>, lds);
             hipLaunchKernelGGL((connect_kernel<0, -1, true, false, true>), dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed,
@@ -181,8 +181,9 @@ void launch_connect_t(const DeviceScene& sc_in, const KParams& kp, const Subpath
 }
 
 template <int B>
-void launch_connect_all_t(const DeviceScene& sc_in, const KParams& kp, const SubpathState& st, float* energy,
-                          unsigned long long* fixed, unsigned* queue_head, hipStream_t s, const DirArgs* dir) {
+void launch_connect_all_t(const DeviceScene& sc_in, const ConnectPass& c, hipStream_t s, const DirArgs* dir) {
+    const KParams& kp = c.kp;
+    const SubpathState& st = c.st;
     if (kp.num_local == 0) return;
     DeviceScene sc = sc_in;
     uint32_t blocks = (kp.num_local + 3) / 4;   // one wave per pair, 4 waves per workgroup
@@ -191,35 +192,32 @@ void launch_connect_all_t(const DeviceScene& sc_in, const KParams& kp, const Sub
     size_t lds = stack_bytes(sc) + sizeof(float) * (size_t)kp.num_bands * (size_t)kp.hist_window + kShareAnyLdsBytes;
     if (dir) {
         allow_lds(connect_all_dir_kernel<B>, lds);
-        hipLaunchKernelGGL(connect_all_dir_kernel<B>, dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed, queue_head, *dir);
+        hipLaunchKernelGGL(connect_all_dir_kernel<B>, dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, c.energy, c.fixed, c.scratch, *dir);
         return;
     }
     allow_lds(connect_all_kernel<B>, lds);
-    hipLaunchKernelGGL(connect_all_kernel<B>, dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, energy, fixed, queue_head);
+    hipLaunchKernelGGL(connect_all_kernel<B>, dim3(blocks), dim3(kBlock), lds, s, sc, kp, st, c.energy, c.fixed, c.scratch);
 }
 
 }  // namespace
 
-void launch_connect(int B, const DeviceScene& sc, const KParams& kp, const SubpathState& st, float* energy,
-                    unsigned long long* fixed, unsigned* queue_head, int pairs_per_wave, float* const* energy_tab,
-                    unsigned long long* const* fixed_tab, hipStream_t s, const DirArgs* dir) {
+void launch_connect(int B, const DeviceScene& sc, const ConnectPass& c, hipStream_t s, const DirArgs* dir) {
     // instantiated for the band counts in use (the reference: 1; BASELINE.json's configurations: 4 and 8); B = 0 reads
     // kp.num_bands at run time
     switch (B) {
-        case 1: launch_connect_t<1>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir); break;
-        case 4: launch_connect_t<4>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir); break;
-        case 8: launch_connect_t<8>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir); break;
-        default: launch_connect_t<0>(sc, kp, st, energy, fixed, queue_head, pairs_per_wave, energy_tab, fixed_tab, s, dir); break;
+        case 1: launch_connect_t<1>(sc, c, s, dir); break;
+        case 4: launch_connect_t<4>(sc, c, s, dir); break;
+        case 8: launch_connect_t<8>(sc, c, s, dir); break;
+        default: launch_connect_t<0>(sc, c, s, dir); break;
     }
 }
 
-void launch_connect_all(int B, const DeviceScene& sc, const KParams& kp, const SubpathState& st, float* energy,
-                        unsigned long long* fixed, unsigned* queue_head, hipStream_t s, const DirArgs* dir) {
+void launch_connect_all(int B, const DeviceScene& sc, const ConnectPass& c, hipStream_t s, const DirArgs* dir) {
     switch (B) {
-        case 1: launch_connect_all_t<1>(sc, kp, st, energy, fixed, queue_head, s, dir); break;
-        case 4: launch_connect_all_t<4>(sc, kp, st, energy, fixed, queue_head, s, dir); break;
-        case 8: launch_connect_all_t<8>(sc, kp, st, energy, fixed, queue_head, s, dir); break;
-        default: launch_connect_all_t<0>(sc, kp, st, energy, fixed, queue_head, s, dir); break;
+        case 1: launch_connect_all_t<1>(sc, c, s, dir); break;
+        case 4: launch_connect_all_t<4>(sc, c, s, dir); break;
+        case 8: launch_connect_all_t<8>(sc, c, s, dir); break;
+        default: launch_connect_all_t<0>(sc, c, s, dir); break;
     }
 }
 

@@ -195,6 +195,24 @@ struct Source {
     VoiceBank rr, br;
     float occlusion = 1.0f;            // OcclusionAttenuation FSAC.h:130 (1.f until the first UpdateSound)
 };
+// The per-frame fields of a source switched to those of an EARLIER frame (energy buffer `cur`) for a scope: what a held frame or
+// an owed reconstruct still has to do runs through code that works on "the source's current frame", while the source may have
+// moved on to later frames (cur rotated).  At the end of the scope the fields come back — unless keep_if_current and the frame
+// still is the source's current one: then what the scope did to it (reduced, handed over, ordered behind the tail) is its state.
+struct SourceFrameScope {
+    Source* const s;
+    const int cur;
+    const bool cur_fixed, reduced, handed_off, tail_ordered, restore;
+    SourceFrameScope(Source* src, int frame_cur, bool fixed, bool frame_reduced, bool frame_tail_ordered, bool keep_if_current)
+        : s(src), cur(src->cur), cur_fixed(src->cur_fixed), reduced(src->reduced), handed_off(src->handed_off),
+          tail_ordered(src->tail_ordered), restore(!keep_if_current || src->cur != frame_cur) {
+        s->cur = frame_cur; s->cur_fixed = fixed; s->reduced = frame_reduced; s->handed_off = false; s->tail_ordered = frame_tail_ordered;
+    }
+    ~SourceFrameScope() {
+        if (restore) { s->cur = cur; s->cur_fixed = cur_fixed; s->reduced = reduced; s->handed_off = handed_off; s->tail_ordered = tail_ordered; }
+    }
+    SourceFrameScope(const SourceFrameScope&) = delete;
+};
 
 struct TimedFrame {
     hipEvent_t e[5];  // walk begin, walk end == connect begin, connect end | reconstruct begin, end
@@ -444,13 +462,12 @@ struct fs_context {
     // the walk of frame f + 1 as ONE kernel; depth 2: the walk is held back as well — call f launches {plan of f, walk of
     // f - 1, connect of f - 2} as one kernel.  Anything that needs a held frame's result lets it finish alone (flush_pending).
     struct PipeFrame {
-        KParams kp; SubpathState st;
-        WalkLaunch wl;               // queue_head = the frame's scratch set, rays_per_wave of its first stage
-        const uint32_t* perm = nullptr;   // its schedule (nullptr: none)
+        WalkPart walk;               // its walk as the launchers take it: wl.rays_per_wave of its first stage; `stage` is set per launch
+        ConnectPass connect;         // its connect pass (energy / fixed: the first item's buffers; a batched frame: the per-frame device
+                                     //   tables — kBatchSlots of them rotate, a held frame is connected kMaxWalkParts + 1 calls later at most)
         std::vector<WalkStage> stages;    // the walk in one piece ({0, depth}) or the stages of a staged depth = 0 walk
         int next_stage = 0;          // stages [0, next_stage) have been launched; == stages.size(): only the connect pass is owed
         bool fixed = false;
-        int ppw = 64;
         struct Item {                // one per source of the frame (a batched frame has several)
             Source* s = nullptr;
             int cur = 0;             // which of the source's energy buffers the frame deposits into
@@ -458,8 +475,6 @@ struct fs_context {
             fs_params recon;
         };
         std::vector<Item> items;
-        float* const* energy_tab = nullptr;               // batched frame: the per-frame device tables (kBatchSlots of them
-        unsigned long long* const* fixed_tab = nullptr;   // rotate; a held frame is connected kMaxWalkParts + 1 calls later at most)
     };
     std::deque<PipeFrame> held;
     // fs_set_frames_per_launch(n > 1): plain pipelinable frames are collected until n are waiting, then traced as ONE
@@ -701,10 +716,13 @@ int dispatch_group(fs_context* ctx);         // the frames collected by fs_set_f
 int flush_pending(fs_context* ctx);          // pipelined frames: drain the pipeline (fused launches, or every held frame on its own kernels)
 int check_overflow(fs_context* ctx);         // depth = 0: did a record miss both tiers?  (stream just synchronised)
 // what a held frame still owes once its connect pass has been enqueued (fixed-point rounding, the sum over the ranks, its reconstruct)
-int finish_held_frame(fs_context* ctx, const fs_context::PipeFrame& q, bool may_defer_recon = false, bool tail_waits_already = false, bool draining = false);
-void held_connect_part(const fs_context::PipeFrame& q, FrameParts& f);                         // a held frame's connect pass as a part of the fused launch
-bool held_walk_part(const fs_context* ctx, const fs_context::PipeFrame& q, FrameParts& f);   // ... its next walk stage (false: no room for more walk parts)
-WalkLaunch stage_launch(const fs_context* ctx, const fs_context::PipeFrame& q, int stage);
+int finish_held_frame(fs_context* ctx, const fs_context::PipeFrame& q, bool may_defer_recon = false, bool draining = false);
+// One fused-launch round: the parts the caller has preset in `fp` (the frame call: its plan part; the drain: nothing), the next
+// walk stage of every held frame, the connect pass of the oldest complete one and the owed reconstructs as ONE launch, and what
+// follows it (the publishes, the stages advanced, the connected frame finished).  end_event: a timed frame's second event,
+// recorded right behind the launch if it carried a walk and a connect part.
+struct RoundCarried { bool any = false, walk = false, connect = false; };   // any == false: there was nothing a launch could carry
+int fused_round(fs_context* ctx, FrameParts& fp, bool draining, hipEvent_t end_event, RoundCarried* carried);
 
 // ---- fs_capi_publish.cpp ------------------------------------------------------------------------------------------
 // The reconstruct parts of a fused launch: owed_prepare turns the owed reconstructs into parts of the launch being assembled (and

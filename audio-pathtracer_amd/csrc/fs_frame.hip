@@ -1,5 +1,5 @@
 // fs_frame.hip — pipelined frames: ONE launch for the walk of one frame, the connect pass of an older one and the plan
-// pass of the newest (fs_set_pipelining; fs_capi_frame.cpp: frame_launch, fs_capi_pipeline.cpp: drain_fused).
+// pass of the newest (fs_set_pipelining; fs_capi_pipeline.cpp: fused_round, for the hot call and for the drain).
 //
 // Compiled twice (Makefile): as it stands — the kernel limited to 128 VGPRs and the LDS stack capped, so that four
 // workgroups share a CU, for launches that fill the chip — and through fs_frame_wide.hip with FS_FRAME_WIDE defined:
@@ -176,19 +176,14 @@ bool FS_LAUNCH_FRAME(int B, const DeviceScene& sc, const FrameParts& f, hipStrea
         WalkArgs& w = a.walk[a.num_walk++];
         w.kp = p.kp; w.st = p.st; w.scratch = p.wl.queue_head; w.perm = p.perm; w.stage = p.stage;
         w.rays_per_wave = p.wl.rays_per_wave > 0 && p.wl.rays_per_wave < 64 ? p.wl.rays_per_wave : 64;
-        if (w.stage.begin > 0 && w.stage.slots_cap == 0xFFFFFFFFu) w.stage.slots_cap = walk_stage_slots(p.kp, w.stage.begin);
-        const uint32_t lanes = w.stage.begin > 0 ? w.stage.slots_cap : 2u * p.kp.num_local;
-        const uint32_t waves = (lanes + (uint32_t)w.rays_per_wave - 1) / (uint32_t)w.rays_per_wave;
-        blocks += (waves + kBlock / 64 - 1) / (kBlock / 64);
+        blocks += walk_blocks(walk_part_lanes(p.kp, w.stage), w.rays_per_wave);
         w.block_end = blocks;
         lds = std::max(lds, stack_bytes(sc) + (FS_FRAME_EXT_ON ? kShareIgnLdsBytes : kShareLdsBytes));
     }
     if (f.has_connect) {
-        if (f.kpc.lobes || f.kpc.count || f.kpc.dpos || f.kpc.num_local == 0 || f.ppw < 1 || f.ppw > 64) return false;
-        const uint32_t per_block = (uint32_t)f.ppw * (kBlock / 64);
-        const uint32_t want = f.energy_tab ? (f.kpc.num_local / f.kpc.pairs_per_source) * ((f.kpc.pairs_per_source + per_block - 1) / per_block)
-                                           : (f.kpc.num_local + per_block - 1) / per_block;
-        a.connect_blocks = std::min<uint32_t>(want, 1024u);
+        const ConnectPass& c = f.connect;
+        if (c.kp.lobes || c.kp.count || c.kp.dpos || c.kp.num_local == 0 || c.pairs_per_wave < 1 || c.pairs_per_wave > 64) return false;
+        a.connect_blocks = std::min<uint32_t>(connect_blocks_wanted(c.kp.num_local, c.kp.pairs_per_source, c.pairs_per_wave, c.energy_tab != nullptr), 1024u);
         // Where the connect workgroups sit in the grid (tools/launch_timeline.py, profiles/r03_launch_timeline_*.json,
         // profiles/r03_connect_first.log).  Behind the walks, the connect pass starts when the last walk workgroup has been
         // dispatched and is the launch's tail: 55 of 597 us at 40 % of the wave slots when two frames share the launch.  A
@@ -203,17 +198,18 @@ bool FS_LAUNCH_FRAME(int B, const DeviceScene& sc, const FrameParts& f, hipStrea
             a.connect_blocks = std::min<uint32_t>(a.connect_blocks, 384u);
             a.connect_first = 1u;
         }
-        a.kpc = f.kpc; a.stc = f.stc; a.energy = f.energy; a.fixed = f.fixed; a.scratch_c = f.scratch_c; a.pairs_per_wave = f.ppw;
-        a.energy_tab = f.energy_tab; a.fixed_tab = f.fixed_tab;
+        a.kpc = c.kp; a.stc = c.st; a.energy = c.energy; a.fixed = c.fixed; a.scratch_c = c.scratch; a.pairs_per_wave = c.pairs_per_wave;
+        a.energy_tab = c.energy_tab; a.fixed_tab = c.fixed_tab;
         blocks += a.connect_blocks;
-        lds = std::max(lds, stack_bytes(sc) + sizeof(float) * (size_t)B * (size_t)f.kpc.hist_window + kShareAnyLdsBytes);
+        lds = std::max(lds, stack_bytes(sc) + sizeof(float) * (size_t)B * (size_t)c.kp.hist_window + kShareAnyLdsBytes);
     }
     if (f.has_plan) {
+        const PlanPass& p = f.plan;
         uint32_t pb = 0;
         bool sort = false;
-        if (!plan_shape(f.kpp, f.wl_p, &pb, &sort)) return false;
-        a.kpp = f.kpp; a.scratch_p = f.scratch_p; a.perm_p = f.perm_p; a.zero_p = f.zero_p; a.zero_words_p = f.zero_words_p;
-        a.zero_tab_p = f.zero_tab_p; a.zero_count_p = f.zero_count_p;
+        if (!plan_shape(p.kp, p.wl, &pb, &sort)) return false;
+        a.kpp = p.kp; a.scratch_p = p.wl.queue_head; a.perm_p = sort ? p.wl.perm : nullptr; a.zero_p = p.zero; a.zero_words_p = p.zero_words;
+        a.zero_tab_p = p.zero_tab; a.zero_count_p = p.zero_count;
         a.plan_blocks = pb;
         blocks += pb;
     }
@@ -232,7 +228,7 @@ bool FS_LAUNCH_FRAME(int B, const DeviceScene& sc, const FrameParts& f, hipStrea
     }
     if (blocks == 0) return false;
     if (blocks_only) { *blocks_only = blocks; return true; }
-    const bool batch = f.has_connect && f.energy_tab;
+    const bool batch = f.has_connect && f.connect.energy_tab;
     const bool spectral = f.num_recon > 0 && f.recon_carrier != nullptr;
     switch (B) {   // the band counts in use; 0 = kp.num_bands at run time (fs_connect.hip)
         case 1: return launch_frame_b<1>(sc, blocks, lds, a, batch, spectral, s);

@@ -377,12 +377,31 @@ constexpr int kCounterWord = (kScratchWords + 1) & ~1;
 constexpr int kNumCounters = 12;  // walk segments (observed), connections tested, deposits | level 3: walk node / triangle records, any-hit node / triangle records |
                                   // planned segments | level 3: node-record request instructions of the walk, their active lanes, the distinct 64-B records among those | spare
 constexpr int kScratchAllocWords = kCounterWord + 2 * kNumCounters;
-// plan pass (length-bucketed schedule + FlushEnergyBuffer); returns the bucket array to walk through, or
-// nullptr when no plan applies (the caller then clears the energy buffer itself)
-// energy / energy_words: buffer the pass zeroes (FlushEnergyBuffer); energy_tab / energy_count: a device table of such
-// buffers instead (batched frame).  Returns nullptr — and zeroes nothing — when there is no roulette to plan for.
-const uint32_t* launch_plan(const KParams& kp, const WalkLaunch& wl, float* energy, int energy_words,
-                            float* const* energy_tab, int energy_count, hipStream_t s);
+// The three passes of a frame as the host hands them around (host only: every launcher unpacks its struct to the arguments of
+// its kernel).  A pass launched alone and the same pass as a part of the fused launch are described by the same struct.
+// The plan pass: the length-bucketed schedule + FlushEnergyBuffer.  wl.queue_head = the frame's scratch set, wl.perm = the
+// schedule the pass writes (plan_shape says whether it does: the counts alone otherwise).  The flush: `zero`, or for a batched
+// frame the device table zero_tab of zero_count such buffers, of zero_words words each — 0 when there is nothing to flush.
+struct PlanPass {
+    KParams kp; WalkLaunch wl;
+    float* zero = nullptr; float* const* zero_tab = nullptr; int zero_count = 0, zero_words = 0;
+};
+// The connect pass.  fixed != nullptr: deterministic mode, deposits go to the [B][bins] u64 fixed-point histogram instead;
+// scratch = the frame's scratch set (re-armed by the pass); energy_tab / fixed_tab: per-source buffers of a batched frame (device
+// arrays of kp.num_local / kp.pairs_per_source pointers), null for one source (`energy` / `fixed` are used).
+struct ConnectPass {
+    KParams kp; SubpathState st;
+    float* energy = nullptr; unsigned long long* fixed = nullptr; unsigned* scratch = nullptr; int pairs_per_wave = 64;
+    float* const* energy_tab = nullptr; unsigned long long* const* fixed_tab = nullptr;
+};
+struct WalkPart {   // a frame's walks from step stage.begin up to step stage.end
+    KParams kp; SubpathState st; WalkLaunch wl;   // wl.queue_head = the frame's scratch set, wl.rays_per_wave
+    const uint32_t* perm = nullptr;               // its schedule (nullptr: none)
+    WalkStage stage;
+};
+// returns the bucket array to walk through, or nullptr — and zeroes nothing — when there is no roulette to plan for (the caller
+// then clears the energy buffer itself)
+const uint32_t* launch_plan(const PlanPass& p, hipStream_t s);
 // Pipelined frames: ONE launch with several parts — walks (or walk stages) of frames planned before, the connect pass
 // of an older one (walked before), the plan pass of the newest.  false = no fused form for this shape (lobes, counting
 // instantiations, experiment walk variants, nothing to do): the caller launches the kernels one after the other.
@@ -390,20 +409,13 @@ constexpr int kMaxWalkParts = 8;   // walk parts of one fused launch = stages of
 constexpr int kSlotMaskOffsetWords = 16;  // the mask table starts this many 32-bit words behind the ticket cell (one device allocation)
 constexpr int kMaxMaskSources = 1024;     // sources (by handle) whose ring slots have zero-block masks; later ones always write every block
 struct PublishWord { unsigned* tickets = nullptr; unsigned long long* host_word = nullptr; unsigned long long id = 0; };
-struct WalkPart {   // a frame's walks from step stage.begin up to step stage.end
-    KParams kp; SubpathState st; WalkLaunch wl;   // wl.queue_head = the frame's scratch set, wl.rays_per_wave
-    const uint32_t* perm = nullptr;               // its schedule (nullptr: none)
-    WalkStage stage;
-};
 struct FrameParts {
     int num_walk = 0;           // walk parts, in grid order
     WalkPart walk[kMaxWalkParts];
-    bool has_connect = false;   // kpc, stc, energy / fixed, scratch_c (re-armed by the pass), ppw
-    KParams kpc; SubpathState stc; float* energy = nullptr; unsigned long long* fixed = nullptr; unsigned* scratch_c = nullptr; int ppw = 64;
-    float* const* energy_tab = nullptr; unsigned long long* const* fixed_tab = nullptr;   // batched frame: per-source buffers
-    bool has_plan = false;      // kpp, wl_p (plan switch), scratch_p, perm_p (the schedule to write, nullptr: counts only), zero_p / zero_words_p (the flush)
-    KParams kpp; WalkLaunch wl_p; unsigned* scratch_p = nullptr; uint32_t* perm_p = nullptr; float* zero_p = nullptr; int zero_words_p = 0;
-    float* const* zero_tab_p = nullptr; int zero_count_p = 0;                              // batched frame: the buffers to flush
+    bool has_connect = false;
+    ConnectPass connect;
+    bool has_plan = false;
+    PlanPass plan;
     // reconstruct parts: ReconstructImpulseResponse of the frames the PREVIOUS launch connected (single GPU; a sharded
     // frame is reduced on the tail stream first and reconstructed there)
     // a table of ReconItem in pinned host memory (fs_context::h_recon_tab: the parts read their item across the bus, as the batch
@@ -420,24 +432,18 @@ struct FrameParts {
 bool launch_frame(int B, const DeviceScene& sc, const FrameParts& f, hipStream_t s);
 // does this frame have a plan pass (roulette on, not empty)?  blocks / sort: its grid and whether it writes the schedule
 bool plan_shape(const KParams& kp, const WalkLaunch& wl, uint32_t* blocks, bool* sort);
-void launch_walk(const DeviceScene& sc, const KParams& kp, const SubpathState& st, const WalkLaunch& wl,
-                 const uint32_t* perm, hipStream_t s, const WalkStage& stage = WalkStage(), const WalkLane& lane = WalkLane());
+void launch_walk(const DeviceScene& sc, const WalkPart& w, hipStream_t s, const WalkLane& lane = WalkLane());
 // can a staged frame whose first stage launches like `first` and whose later ones like `late` have a long-walk lane
 // (WalkLane)?  (sparse first stage, cooperative later stages, a cooperative view of the tree for one walk per wave)
 bool walk_lane_possible(const DeviceScene& sc, const KParams& kp, const WalkLaunch& first, const WalkLaunch& late, const uint32_t* perm);
 // lanes a walk stage needs: all subpaths for a stage that starts at step 0, else the expected number of walks longer than
 // stage.begin under the roulette (x1.3 + 1024: the count is binomial, the margin is hundreds of standard deviations)
 uint32_t walk_stage_slots(const KParams& kp, int begin);
-// fixed != nullptr: deterministic mode, deposits go to the [B][bins] u64 fixed-point histogram instead
-// energy_tab / fixed_tab: per-source buffers of a batched frame (device arrays of kp.num_local / kp.pairs_per_source
-// pointers), null for one source (`energy` / `fixed` are used)
-void launch_connect(int B, const DeviceScene& sc, const KParams& kp, const SubpathState& st, float* energy,
-                    unsigned long long* fixed, unsigned* queue_head, int pairs_per_wave, float* const* energy_tab,
-                    unsigned long long* const* fixed_tab, hipStream_t s, const DirArgs* dir = nullptr);
-// row f3: every forward prefix x every backward prefix of each pair (one wave per pair), uniform MIS weights
 // dir != nullptr: a directional source (the directional entries, connect_dir_kernel / connect_all_dir_kernel)
-void launch_connect_all(int B, const DeviceScene& sc, const KParams& kp, const SubpathState& st, float* energy,
-                        unsigned long long* fixed, unsigned* queue_head, hipStream_t s, const DirArgs* dir = nullptr);
+void launch_connect(int B, const DeviceScene& sc, const ConnectPass& c, hipStream_t s, const DirArgs* dir = nullptr);
+// row f3: every forward prefix x every backward prefix of each pair (one wave per pair), uniform MIS weights — of ONE source:
+// the pass's pairs per wave and tables are not read
+void launch_connect_all(int B, const DeviceScene& sc, const ConnectPass& c, hipStream_t s, const DirArgs* dir = nullptr);
 void launch_fixed_to_energy(const unsigned long long* fixed, float* energy, int words, hipStream_t s);
 // carrier != nullptr (FS_FLAG_SPECTRAL_IR): row B is the spectral channel from the [B][carrier_stride] carrier set (fs_dev_recon.hpp:
 // reconstruct_spectral_row); the band rows are the same either way

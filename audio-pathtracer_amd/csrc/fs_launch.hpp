@@ -1,5 +1,5 @@
-// fs_launch.hpp — host-side helpers of the kernel launchers: LDS sizes and limits, the deep store, the cooperative
-// traversal's node arrays.
+// fs_launch.hpp — host-side helpers of the kernel launchers: LDS sizes and limits, the deep store, the passes' grid rules, the
+// cooperative traversal's node arrays.
 #pragma once
 
 #include "fs_dev_coop.hpp"   // (the cooperative kernels' LDS layout: kCoopCap, kCoopWaveBytes)
@@ -34,6 +34,23 @@ inline bool attach_deep(DeviceScene& sc, uint32_t blocks) {
     }
     sc.deep = d->buf; sc.deep_lanes = (uint32_t)d->lanes;
     return true;
+}
+// ---- one grid rule per pass: the stand-alone launchers and the fused one (fs_frame.hip) ask here; each keeps its own cap ----
+// workgroups the connect pass wants: a wave steps through pairs_per_wave pairs at a time; the sources of a batched frame
+// (per-source buffers) each start on workgroups of their own
+inline uint32_t connect_blocks_wanted(uint32_t num_local, uint32_t pairs_per_source, int pairs_per_wave, bool batch) {
+    const uint32_t per_block = (uint32_t)pairs_per_wave * (kBlock / 64);
+    return batch ? (num_local / pairs_per_source) * ((pairs_per_source + per_block - 1) / per_block) : (num_local + per_block - 1) / per_block;
+}
+// lanes of a walk part — a later stage only has lanes for the walks still alive (its slots_cap is filled in here) — and the
+// workgroups of four waves that walk them on sparse (rays_per_wave < 64: the other lanes help) or dense (64) waves
+inline uint32_t walk_part_lanes(const KParams& kp, WalkStage& stage) {
+    if (stage.begin > 0 && stage.slots_cap == 0xFFFFFFFFu) stage.slots_cap = walk_stage_slots(kp, stage.begin);
+    return stage.begin > 0 ? stage.slots_cap : 2u * kp.num_local;
+}
+inline uint32_t walk_blocks(uint32_t lanes, int rays_per_wave) {
+    const uint32_t waves = (lanes + (uint32_t)rays_per_wave - 1) / (uint32_t)rays_per_wave;
+    return (waves + kBlock / 64 - 1) / (kBlock / 64);
 }
 constexpr int kMaxDevices = 64;
 // LDS one workgroup may have on the current device (MI355X: all 160 KB of its CU)

@@ -109,17 +109,16 @@ __global__ __launch_bounds__(kBlock) void walk_kernel_lane(DeviceScene sc, CoopV
 
 }  // namespace
 
-const uint32_t* launch_plan(const KParams& kp, const WalkLaunch& wl, float* energy, int energy_words,
-                            float* const* energy_tab, int energy_count, hipStream_t s) {
+const uint32_t* launch_plan(const PlanPass& p, hipStream_t s) {
     // Without roulette every walk takes kp.depth segments: nothing to sort, and the caller counts the segments on
     // the host.  With roulette the pass always runs — it is also what counts the frame's walk segments — but it
     // only produces the length-sorted schedule when that is enabled and can matter.
     uint32_t full = 0;
     bool sort = false;
-    if (!plan_shape(kp, wl, &full, &sort)) return nullptr;
-    hipLaunchKernelGGL(plan_kernel, dim3(full), dim3(kBlock), 0, s, kp, wl.queue_head, sort ? wl.perm : nullptr, energy,
-                       energy_words, energy_tab, energy_count);
-    return sort ? wl.perm : nullptr;
+    if (!plan_shape(p.kp, p.wl, &full, &sort)) return nullptr;
+    hipLaunchKernelGGL(plan_kernel, dim3(full), dim3(kBlock), 0, s, p.kp, p.wl.queue_head, sort ? p.wl.perm : nullptr, p.zero,
+                       p.zero_words, p.zero_tab, p.zero_count);
+    return sort ? p.wl.perm : nullptr;
 }
 
 bool plan_shape(const KParams& kp, const WalkLaunch& wl, uint32_t* blocks, bool* sort) {
@@ -147,15 +146,17 @@ bool walk_lane_possible(const DeviceScene& sc, const KParams& kp, const WalkLaun
     return coop_view(sc, 1) != nullptr && coop_view(sc, late.rays_per_wave) != nullptr;
 }
 
-void launch_walk(const DeviceScene& sc_in, const KParams& kp, const SubpathState& st, const WalkLaunch& wl,
-                 const uint32_t* perm, hipStream_t s, const WalkStage& stage_in, const WalkLane& lane_in) {
+void launch_walk(const DeviceScene& sc_in, const WalkPart& w, hipStream_t s, const WalkLane& lane_in) {
+    const KParams& kp = w.kp;
+    const SubpathState& st = w.st;
+    const WalkLaunch& wl = w.wl;
+    const uint32_t* const perm = w.perm;
     DeviceScene sc = sc_in;
-    WalkStage stage = stage_in;
+    WalkStage stage = w.stage;
     WalkLane lane = lane_in;
-    if (stage.begin > 0 && stage.slots_cap == 0xFFFFFFFFu) stage.slots_cap = walk_stage_slots(kp, stage.begin);
-    uint32_t lanes = stage.begin > 0 ? stage.slots_cap : 2u * kp.num_local;   // a later stage only has lanes for the walks still alive
+    const uint32_t lanes = walk_part_lanes(kp, stage);
     if (lanes == 0) return;
-    uint32_t full = (lanes + kBlock - 1) / kBlock;
+    const uint32_t full = walk_blocks(lanes, 64);
     const bool shared = FS_SHARED_WALK(wl);
     // record-fetch counting (fs_set_profiling level 3) exists for the default walk only (no lobes)
 #define FS_LAUNCH_WALK(K, GRID, ...)                                                                        \
@@ -171,8 +172,7 @@ void launch_walk(const DeviceScene& sc_in, const KParams& kp, const SubpathState
             CoopView cv = *lv;
             const size_t lds_walk = stack_bytes(sc) + kShareLdsBytes, lds_walk_ext = stack_bytes(sc) + kShareIgnLdsBytes;
             const uint32_t lane_blocks = (lane.cap + kBlock / 64 - 1) / (kBlock / 64);
-            const uint32_t waves = (lanes + (uint32_t)wl.rays_per_wave - 1) / (uint32_t)wl.rays_per_wave;
-            const uint32_t blocks = lane_blocks + (waves + kBlock / 64 - 1) / (kBlock / 64);
+            const uint32_t blocks = lane_blocks + walk_blocks(lanes, wl.rays_per_wave);
             // the lane's resident records: what fits into the LDS the sparse workgroups of the launch take anyway
             const size_t lane_fixed = kCoopWaveBytes * (size_t)(kBlock / 64);
             cv.lds_nodes = lds_walk > lane_fixed ? (int)std::min<size_t>((size_t)std::max(cv.nodes, 0), (lds_walk - lane_fixed) / ((size_t)16 << cv.wshift)) : 0;
@@ -206,8 +206,7 @@ void launch_walk(const DeviceScene& sc_in, const KParams& kp, const SubpathState
     }
     if (shared && wl.rays_per_wave > 0 && wl.rays_per_wave < 64) {   // small frame: sparse waves, idle lanes help
         const size_t lds = stack_bytes(sc) + kShareLdsBytes, lds_ext = stack_bytes(sc) + kShareIgnLdsBytes;   // (EXT: + the ignored actor per ray)
-        const uint32_t waves = (lanes + (uint32_t)wl.rays_per_wave - 1) / (uint32_t)wl.rays_per_wave;
-        const uint32_t blocks = (waves + kBlock / 64 - 1) / (kBlock / 64);
+        const uint32_t blocks = walk_blocks(lanes, wl.rays_per_wave);
         if (!attach_deep(sc, blocks)) return;
         FS_LAUNCH_WALK(walk_kernel_sparse, blocks, sc, kp, st, wl.queue_head, perm, wl.rays_per_wave, stage, lane);
         return;

@@ -95,6 +95,19 @@ for k, seed in enumerate((911, 912, 913, 914)):
 ctx.synchronize()
 res["ir_run"] = ctx.impulse_response(src, 0).copy()
 res["energy_run"] = ctx.energy_buffer(src).copy()
+if os.environ.get("FS_TEST_PIPELINE") == "1" and FPL == 1:
+    # What orders the all-reduce behind the connect pass: a stream of fp32 frames into the empty pipeline (depth 2: call k connects the
+    # frame of call k - 2), counted between the first call and the last — nothing in between flushes.  Five calls: the frame
+    # connected by the fifth is the first whose launch also carries a reconstruct part (a summed frame's rides two launches later).
+    STREAM = 5
+    ops0 = ctx.pipeline_counters()["tail_stream_ops"]
+    for k in range(STREAM):
+        ps = pkg.default_params(num_rays=8192, depth=8, seed=921 + k)
+        ctx.compute_energy_response_async(src, ps)
+        ctx.reconstruct_impulse_response_async(src, ps)
+    res["stream_tail_ops"] = np.int64(ctx.pipeline_counters()["tail_stream_ops"] - ops0)
+    res["stream_connected"] = np.int64(STREAM - 2)
+    ctx.synchronize()
 p = pkg.default_params(num_rays=16384, depth=8, seed=77)
 res["energy"] = ctx.compute_energy_response(src, p).copy()        # the helpers read the summed buffer
 rng = np.random.default_rng(5)

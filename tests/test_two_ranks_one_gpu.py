@@ -89,6 +89,13 @@ def test_every_rank_publishes_the_single_rank_ir(pkg, fake_rccl, tmp_path, world
     for r, rk in enumerate(ranks):
         assert np.array_equal(rk["energy_run"], ctx.energy_buffer(src)), r
         assert np.array_equal(rk["ir_run"], ctx.impulse_response(src, 0)), r
+    if pipelined and fpl == 1:
+        # every frame a call of the stream connected is handed over to the tail stream before its sum is enqueued there: one
+        # hand-over, then the collective and its event — the collective never runs unordered beside the connect pass it sums
+        for r, rk in enumerate(ranks):
+            ops, connected = int(rk["stream_tail_ops"]), int(rk["stream_connected"])
+            print(f"rank {r}: {ops} tail-stream commands for {connected} connected frames")
+            assert connected >= 3 and ops >= 3 * connected, (r, ops, connected)
     p = pkg.default_params(num_rays=16384, depth=8, seed=77)
     want_e = ctx.compute_energy_response(src, p)
     rng = np.random.default_rng(5)
