@@ -50,6 +50,7 @@ EXPORTS = [
     "fs_sound_params_default", "fs_scene_set_objects", "fs_update_sound", "fs_get_occlusion_attenuation",
     "fs_save_array_to_file", "fs_load_float_array", "fs_save_impulse_response",
     "fs_reverb_init", "fs_reverb_process", "fs_reverb_process_batch", "fs_reverb_release", "fs_reverb_set_crossfade", "fs_reverb_set_engine",
+    "fs_reverb_ears_default", "fs_reverb_ears_set", "fs_reverb_ears_info", "fs_reverb_set_ears", "fs_reverb_copy_ear_impulse_responses",
     "fs_apply_material_fd", "fs_energy_handoff", "fs_scene_update_triangles", "fs_scene_refit", "fs_scene_set_object_transforms", "fs_set_impulse_response",
     "fs_scene_commit_fast", "fs_comm_unique_id", "fs_comm_init", "fs_comm_attach", "fs_comm_detach", "fs_comm_info", "fs_comm_enable_oneshot", "fs_shard_range",
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
@@ -498,6 +499,15 @@ class HrtfDesc(C.Structure):
     ]
 
 
+class ReverbEarsDesc(C.Structure):
+    """fs_reverb_ears_desc (include/frequensee.h): the head of fs_reverb_ears_set's diffuse-field coherence"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("radius_cm", C.c_float),
+        ("sound_speed_cm_s", C.c_float),
+    ]
+
+
 class BinauralVoice(C.Structure):
     """fs_binaural_voice (include/frequensee.h): one entry of a source's voice list, an array element (no struct_size)"""
     _fields_ = [
@@ -604,6 +614,11 @@ def load():
         "fs_reverb_release": (C.c_int, [vp, i32]),
         "fs_reverb_set_crossfade": (C.c_int, [vp, i32, i32]),
         "fs_reverb_set_engine": (C.c_int, [vp, i32, i32]),
+        "fs_reverb_ears_default": (None, [C.POINTER(ReverbEarsDesc)]),
+        "fs_reverb_ears_set": (C.c_int, [vp, C.POINTER(ReverbEarsDesc)]),
+        "fs_reverb_ears_info": (C.c_int, [vp, f32p, f32p, C.c_void_p]),
+        "fs_reverb_set_ears": (C.c_int, [vp, i32, i32]),
+        "fs_reverb_copy_ear_impulse_responses": (C.c_int, [vp, i32, f32p, f32p, i32]),
         "fs_apply_material_fd": (C.c_int, [vp, f32p, i32, f32p, f32p, f32p, i32, f32p, f32p, f32p]),
         "fs_comm_unique_id": (C.c_int, [vp, C.c_size_t]),
         "fs_comm_init": (C.c_int, [vp, vp, C.c_size_t]),
@@ -674,6 +689,10 @@ def default_config(**kw) -> Config:
 
 def default_sound_params(**kw) -> SoundParams:
     return _defaults(SoundParams, "fs_sound_params_default", kw)
+
+
+def default_reverb_ears(**kw) -> ReverbEarsDesc:
+    return _defaults(ReverbEarsDesc, "fs_reverb_ears_default", kw)
 
 
 def default_direct_params(**kw) -> DirectParams:

@@ -729,6 +729,37 @@ class Context:
         grows with the IR; include/frequensee.h fs_reverb_set_engine)"""
         self.check(self.lib.fs_reverb_set_engine(self.h, src, int(engine)))
 
+    def reverb_ears_set(self, radius_cm=None, sound_speed_cm_s=None, clear=False):
+        """fs_reverb_ears_set: build and install the two-ear reverb's carriers (diffuse-field coherence of two points 2 radius_cm
+        apart; None = the spherical head's defaults), or clear the set (include/frequensee.h "Two-ear late reverb")"""
+        if clear:
+            self.check(self.lib.fs_reverb_ears_set(self.h, None))
+            return
+        kw = {}
+        if radius_cm is not None:
+            kw["radius_cm"] = float(radius_cm)
+        if sound_speed_cm_s is not None:
+            kw["sound_speed_cm_s"] = float(sound_speed_cm_s)
+        d = _capi.default_reverb_ears(**kw)
+        self.check(self.lib.fs_reverb_ears_set(self.h, C.byref(d)))
+
+    def reverb_ears_info(self):
+        """fs_reverb_ears_info -> (radius_cm, sound_speed_cm_s, installed)"""
+        r, c, on = C.c_float(0.0), C.c_float(0.0), C.c_int32(0)
+        self.check(self.lib.fs_reverb_ears_info(self.h, C.addressof(r), C.addressof(c), C.addressof(on)))
+        return float(r.value), float(c.value), bool(on.value)
+
+    def reverb_set_ears(self, src, on):
+        """ears for the source's next reverb_init (needs the partitioned engine and an installed set there)"""
+        self.check(self.lib.fs_reverb_set_ears(self.h, src, 1 if on else 0))
+
+    def reverb_ear_impulse_responses(self, src):
+        """fs_reverb_copy_ear_impulse_responses -> (left, right): h_L and h_R of the source's newest device-resident IR"""
+        left = np.empty(self.num_samples, dtype=np.float32)
+        right = np.empty(self.num_samples, dtype=np.float32)
+        self.check(self.lib.fs_reverb_copy_ear_impulse_responses(self.h, src, left.ctypes.data, right.ctypes.data, left.shape[0]))
+        return left, right
+
     def apply_material_fd(self, in_buffer, absorption, transmission, scattering):
         """UMaterialAcousticProcessor::ApplyMaterialFD (MAP.cpp:8-107) -> (specular, diffuse, transmitted)"""
         x = np.ascontiguousarray(in_buffer, dtype=np.float32).reshape(-1)
@@ -1107,11 +1138,17 @@ class FrequenSeeAudioReverbPlugin:
     def __init__(self, subsystem: AudioRayTracingSubsystem):
         self.ctx = subsystem.ctx
         self.FrameSize = 1024      # AudioCallbackBufferFrameSize, Config/DefaultEngine.ini:13
+        self.Ears = False          # not in the reference: a two-ear late field (Context.reverb_ears_set installs the set first)
 
     def Initialize(self, BufferLength=1024):
         self.FrameSize = int(BufferLength)
 
     def OnInitSource(self, component: FrequenSeeAudioComponent):
+        # Ears need the partitioned engine: both are the next init's.  Ears = False only takes the ears away: the engine stays
+        # whatever SetEngine (or an earlier init with ears) chose — switch back with SetEngine(component, REVERB_ENGINE_DIRECT).
+        if self.Ears:
+            self.ctx.reverb_set_engine(component._src, _capi.REVERB_ENGINE_PARTITIONED)
+        self.ctx.reverb_set_ears(component._src, self.Ears)
         self.ctx.reverb_init(component._src, self.FrameSize)
 
     def OnReleaseSource(self, component: FrequenSeeAudioComponent):

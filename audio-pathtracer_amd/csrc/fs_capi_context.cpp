@@ -665,6 +665,7 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->d_batch) (void)hipFree(ctx->d_batch);
         if (ctx->d_build) (void)hipFree(ctx->d_build);
         if (ctx->d_carrier) (void)hipFree(ctx->d_carrier);
+        if (ctx->d_ear_carrier) (void)hipFree(ctx->d_ear_carrier);
         if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
         for (hipEvent_t e : ctx->ev_batch) if (e) (void)hipEventDestroy(e);
         for (const fs_context::RetiredTable& r : ctx->retired_tables) { (void)hipFree(r.p); (void)hipEventDestroy(r.ev); }

@@ -170,12 +170,20 @@ int fs_set_band_edges(fs_context* ctx, const float* edges_hz, int32_t count) {
         const int rc = check_band_edges(ctx, edges.data(), "fs_set_band_edges");
         if (rc) return rc;
     }
+    float* ear_set = nullptr;
     if (ctx->device_ok) {
         const int rc = fs_synchronize(ctx);
         if (rc) return rc;
+        if (ctx->d_ear_carrier) {   // fs_reverb_ears_set's set follows the edges: built for them now, under that call's contract,
+            std::swap(ctx->band_edges, edges);   // before anything of the context changes (the default edges are checked in there)
+            const int br = build_ear_carriers(ctx, ctx->ear_radius_cm, ctx->ear_speed_cm_s, "fs_set_band_edges", &ear_set);
+            std::swap(ctx->band_edges, edges);
+            if (br) return br;   // (refused: the edges, the spectral carriers and the ear set in force stay)
+        }
         if (ctx->d_carrier) { FS_HIP(ctx, hipFree(ctx->d_carrier)); ctx->d_carrier = nullptr; }
     }
     ctx->band_edges = edges;
+    if (ear_set) return install_ear_carriers(ctx, ear_set, ctx->ear_radius_cm, ctx->ear_speed_cm_s);
     return FS_OK;
 }
 

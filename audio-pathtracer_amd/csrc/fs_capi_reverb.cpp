@@ -14,7 +14,8 @@ bool partitioned(const Source* s) { return s->rev_engine == FS_REVERB_ENGINE_PAR
 // the direct engine, partition spectra for the partitioned one, which needs the one it convolves (h_to) without a fade too
 // (both == false)
 int alloc_fade(fs_context* ctx, Source* s, bool both) {
-    const size_t bytes = partitioned(s) ? sizeof(float2) * ((size_t)s->part_K << s->part_n) : sizeof(float) * (size_t)ctx->num_samples;
+    const size_t bytes = partitioned(s) ? sizeof(float2) * ((size_t)s->part_K << s->part_n) * (s->rev_ears ? 2 : 1)   // (ears: M_p, then S_p)
+                                        : sizeof(float) * (size_t)ctx->num_samples;
     if (both && !s->d_fade_from) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_from, bytes));
     if (!s->d_fade_to) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_to, bytes));
     return FS_OK;
@@ -33,7 +34,8 @@ int part_twiddles(fs_context* ctx, int n) {
 }
 
 // the reverb callback's own blocks in its staging (fs_context::rev_stage): CallbackLayout::up; scratch[0] = the mono tails cur
-enum { kRevItems, kRevPartItems, kRevLists };
+// kRevEarLists: the three lists of the rows with ears — zero bytes in a call without such a row, so every other offset stays
+enum { kRevItems, kRevPartItems, kRevLists, kRevEarLists };
 
 // the bytes of Source::d_ring: the direct engine's two history rings, or the partitioned engine's state block
 size_t reverb_state_bytes(const Source* s) {
@@ -50,13 +52,15 @@ const char* const kNoFadeBuffers = "the crossfade's impulse-response buffers are
 // only then does it wait for the write and make the next one wait for it.  *takes: this callback is such a one.
 // The partitioned engine (pit is the row's descriptor then, and `it` says only whose row it is) convolves spectra of its own with
 // or without a crossfade, so it takes in the same way in both cases: H_to from d_ir_mono, when a newer IR is there.
+// A source with ears (fs_reverb_set_ears) is such a row whose spectra come from the band rows — written by the same launches as
+// d_ir_mono, under the same events — and the context's ear carriers: it also takes when that set was replaced (ear_set_gen).
 int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbItem& it, ReverbPartItem& pit, bool* takes) {
     it.apply = 1;
     it.engine = s->rev_engine;
     const bool part = partitioned(s);
     const bool xfade = s->fade_len > 0;
     const bool own = xfade || part;   // the callback convolves copies of its own
-    const bool tk = *takes = own && (!s->fade_primed || s->ir_gen != s->fade_gen);
+    const bool tk = *takes = own && (!s->fade_primed || s->ir_gen != s->fade_gen || (s->rev_ears && s->ear_gen != ctx->ear_set_gen));
     if ((!own || tk) && s->last_rec >= 0) {
         const int buf = s->last_rec;
         // (a finished reconstruct needs no barrier packet on the stream: S of them are most of a short batch)
@@ -75,10 +79,11 @@ int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbIte
             s->fading = true;
             s->fade_pos = 0;
         }
-        if (part) { pit.take_from = (float2*)s->d_fade_from; pit.take_to = (float2*)s->d_fade_to; pit.take_ir = s->d_ir_mono; pit.take_a = a; }
+        if (part) { pit.take_from = (float2*)s->d_fade_from; pit.take_to = (float2*)s->d_fade_to; pit.take_ir = s->rev_ears ? s->d_ir_bands : s->d_ir_mono; pit.take_a = a; }
         else { it.take_from = s->d_fade_from; it.take_to = s->d_fade_to; it.take_ir = s->d_ir_mono; it.take_a = a; }
         s->fade_primed = true;
         s->fade_gen = s->ir_gen;
+        s->ear_gen = ctx->ear_set_gen;
     }
     if (!own || tk) s->rev_recorded = true;
     if (part) {
@@ -114,7 +119,10 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
     const size_t row = 2 * (size_t)frame;   // floats
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     hipStream_t rs = ctx->rev_stream;
-    const CallbackLayout l = callback_layout(count, frame, {sizeof(ReverbItem) * (size_t)count, sizeof(ReverbPartItem) * (size_t)count, sizeof(int) * 6 * (size_t)count},
+    bool ears = false;
+    for (int32_t i = 0; i < count; ++i) ears = ears || (srcs[i]->rev_ears && (!apply_reverb || apply_reverb[i]));
+    const CallbackLayout l = callback_layout(count, frame, {sizeof(ReverbItem) * (size_t)count, sizeof(ReverbPartItem) * (size_t)count, sizeof(int) * 6 * (size_t)count,
+                                                            ears ? sizeof(int) * 3 * (size_t)count : 0},
                                              {sizeof(float) * row * (size_t)count});
     { const int rc = ctx->rev_stage.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
     char* hs = ctx->rev_stage.h; char* ds = ctx->rev_stage.d;
@@ -122,7 +130,8 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
     ReverbPartItem* pitems = (ReverbPartItem*)(hs + l.up[kRevPartItems]);
     int* plain = (int*)(hs + l.up[kRevLists]); int* fade = plain + count; int* take = fade + count;
     int* pplain = take + count; int* pfade = pplain + count; int* ptake = pfade + count;   // the partitioned engine's three
-    int n_plain = 0, n_fade = 0, n_take = 0, n_pplain = 0, n_pfade = 0, n_ptake = 0, n_bypass = 0;
+    int* eplain = (int*)(hs + l.up[kRevEarLists]); int* efade = eplain + count; int* etake = efade + count;   // (only with ears)
+    int n_plain = 0, n_fade = 0, n_take = 0, n_pplain = 0, n_pfade = 0, n_ptake = 0, n_bypass = 0, n_eplain = 0, n_efade = 0, n_etake = 0;
     const Source* part_src = nullptr;
     float* h_in = (float*)(hs + l.in);
     for (int32_t i = 0; i < count; ++i)   // (a bypassed row goes up only for the mix)
@@ -142,7 +151,12 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
             bool takes = false;
             const int rc = reverb_step(ctx, srcs[i], rs, frame, items[i], pitems[i], &takes);
             if (rc) return rc;
-            if (pitems[i].active) {
+            if (pitems[i].active && srcs[i]->rev_ears) {
+                part_src = srcs[i];
+                if (takes) etake[n_etake++] = i;
+                if (pitems[i].h_to) efade[n_efade++] = i;
+                else eplain[n_eplain++] = i;
+            } else if (pitems[i].active) {
                 part_src = srcs[i];
                 if (takes) ptake[n_ptake++] = i;
                 if (pitems[i].h_to) pfade[n_pfade++] = i;
@@ -172,6 +186,17 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
                 launch_reverb_part_take(b.pitems, d_plain + 5 * count, n_ptake, b.part, rs);
                 FS_HIP(ctx, hipGetLastError());
                 for (int k = 0; k < n_ptake; ++k) FS_HIP(ctx, hipEventRecord(srcs[ptake[k]]->ev_rev, rs));
+            }
+            if (ears) {
+                const int* d_ear = (const int*)(ds + l.up[kRevEarLists]);
+                b.part.ear_plain = d_ear; b.part.n_ear_plain = n_eplain;
+                b.part.ear_fade = d_ear + count; b.part.n_ear_fade = n_efade;
+                if (n_etake) {
+                    const ReverbEars e{ctx->d_ear_carrier, ctx->cfg.num_bands, carrier_stride(ctx->num_samples)};
+                    launch_reverb_ears_take(b.pitems, d_ear + 2 * count, n_etake, b.part, e, rs);
+                    FS_HIP(ctx, hipGetLastError());
+                    for (int k = 0; k < n_etake; ++k) FS_HIP(ctx, hipEventRecord(srcs[etake[k]]->ev_rev, rs));
+                }
             }
         }
         b.n_direct = n_plain + n_fade + n_bypass;
@@ -269,6 +294,10 @@ int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
             return ctx->fail(FS_ERR_INVALID_ARGUMENT, "partitioned reverb: frame size outside 16 .. 2048 / IR longer than 1 048 576 samples");
     } else if (frame_size < 1 || frame_size > 16384 || ctx->num_samples - 1 > kReverbRing)
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad reverb frame size / IR longer than the history ring");
+    if (s->rev_ears_next && !part)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init: ears are on (fs_reverb_set_ears) but the source's engine is not FS_REVERB_ENGINE_PARTITIONED");
+    if (s->rev_ears_next && !ctx->d_ear_carrier)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init: ears are on (fs_reverb_set_ears) but no ear set is installed (fs_reverb_ears_set)");
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     // Reconstructs on the compute stream record an event for the callbacks only for a source that has a reverb: the ones
     // already in flight finish before this source gets one.
@@ -280,6 +309,7 @@ int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
     if (s->d_fade_to) (void)hipFree(s->d_fade_to);
     s->d_ring = s->d_fade_from = s->d_fade_to = nullptr;
     s->rev_engine = s->rev_engine_next;
+    s->rev_ears = s->rev_ears_next;
     if (part) {   // N = the smallest power of two >= 2 F, K = ceil(num_samples / F)
         s->part_n = 5;
         while ((1 << s->part_n) < 2 * frame_size) ++s->part_n;
@@ -306,6 +336,77 @@ int fs_reverb_set_engine(fs_context* ctx, fs_source h, int32_t engine) {
     if (engine != FS_REVERB_ENGINE_DIRECT && engine != FS_REVERB_ENGINE_PARTITIONED)
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "unknown reverb engine (FS_REVERB_ENGINE_DIRECT, FS_REVERB_ENGINE_PARTITIONED)");
     s->rev_engine_next = engine;   // (the next fs_reverb_init's)
+    return FS_OK;
+}
+
+void fs_reverb_ears_default(fs_reverb_ears_desc* d) {
+    if (!d) return;
+    d->struct_size = (uint32_t)sizeof(fs_reverb_ears_desc);
+    d->radius_cm = FS_HRTF_DEFAULT_RADIUS_CM;
+    d->sound_speed_cm_s = FS_HRTF_DEFAULT_SOUND_SPEED_CM_S;
+}
+
+int fs_reverb_ears_set(fs_context* ctx, const fs_reverb_ears_desc* desc) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    if (!desc) {   // clear
+        for (const Source* s : ctx->sources)
+            if (s && s->alive && s->d_ring && s->rev_ears)
+                return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_ears_set: the set cannot be cleared while a source is initialised with ears (fs_reverb_init it without them first)");
+        if (!ctx->d_ear_carrier) return FS_OK;
+        FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+        return fsi::install_ear_carriers(ctx, nullptr, 0.0f, 0.0f);
+    }
+    if (desc->struct_size != sizeof(fs_reverb_ears_desc)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_ears_desc.struct_size mismatch");
+    if (!std::isfinite(desc->radius_cm) || desc->radius_cm < 0.0f)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_ears_set: radius_cm must be finite and >= 0");
+    if (!std::isfinite(desc->sound_speed_cm_s) || !(desc->sound_speed_cm_s > 0.0f))
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_ears_set: sound_speed_cm_s must be finite and > 0");
+    { const int rc = fsi::check_band_edges(ctx, nullptr, "fs_reverb_ears_set"); if (rc) return rc; }
+    { const int rc = fs_synchronize(ctx); if (rc) return rc; }   // (the build runs on the compute stream, behind everything in flight)
+    float* set = nullptr;
+    const int rc = fsi::build_ear_carriers(ctx, desc->radius_cm, desc->sound_speed_cm_s, "fs_reverb_ears_set", &set);
+    if (rc) return rc;
+    return fsi::install_ear_carriers(ctx, set, desc->radius_cm, desc->sound_speed_cm_s);
+}
+
+int fs_reverb_ears_info(fs_context* ctx, float* radius_cm, float* sound_speed_cm_s, int32_t* installed) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (radius_cm) *radius_cm = ctx->ear_radius_cm;
+    if (sound_speed_cm_s) *sound_speed_cm_s = ctx->ear_speed_cm_s;
+    if (installed) *installed = ctx->d_ear_carrier ? 1 : 0;
+    return FS_OK;
+}
+
+int fs_reverb_set_ears(fs_context* ctx, fs_source h, int32_t on) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    s->rev_ears_next = on != 0;   // (the next fs_reverb_init's)
+    return FS_OK;
+}
+
+int fs_reverb_copy_ear_impulse_responses(fs_context* ctx, fs_source h, float* left, float* right, int32_t n) {
+    if (!ctx || !left || !right) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (n != ctx->num_samples) return ctx->fail(FS_ERR_SIZE_MISMATCH, "n != num_samples");
+    if (!ctx->d_ear_carrier) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_copy_ear_impulse_responses: no ear set is installed (fs_reverb_ears_set)");
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    FS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));   // the reconstruct runs on the tail stream
+    float* d = nullptr;
+    FS_HIP(ctx, hipMalloc((void**)&d, sizeof(float) * 2 * (size_t)n));
+    const ReverbEars e{ctx->d_ear_carrier, ctx->cfg.num_bands, carrier_stride(ctx->num_samples)};
+    launch_reverb_ears_ir(s->d_ir_bands, e, n, d, d + n, ctx->stream);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemcpyAsync(left, d, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(right, d + n, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    if (err != hipSuccess) return ctx->hip_fail(err, "fs_reverb_copy_ear_impulse_responses");
     return FS_OK;
 }
 

@@ -181,6 +181,10 @@ struct Source {
     // every callback convolves its own spectra, taken like a crossfade's h_to (fade_primed, fade_gen).
     int32_t rev_engine_next = FS_REVERB_ENGINE_DIRECT, rev_engine = FS_REVERB_ENGINE_DIRECT;
     int part_n = 0, part_K = 0, part_slot = 0;
+    // fs_reverb_set_ears: the choice for the next fs_reverb_init / what the source was initialised with.  With ears, d_fade_to /
+    // d_fade_from are [2][part_K][N] (M_p, then S_p), taken from the band rows and the context's ear carriers of generation ear_gen.
+    bool rev_ears_next = false, rev_ears = false;
+    uint64_t ear_gen = 0;
     // crossfade between successive IRs (fs_reverb_set_crossfade; the callback's own state, audio thread): fade_len L samples
     // (0: off), the callback's copies of the IRs it fades between (h_to = the newest it took, generation fade_gen),
     // fade_pos = samples output since the running fade began; fading == false: h_to alone is heard.
@@ -311,7 +315,7 @@ struct CallbackStage {
 // it the host holds what comes back, out [count][2 frame] | mix [2 frame]; the device holds the call's scratch blocks (scratch[k]),
 // then out | mix, adjacent as on the host: one copy back.
 struct CallbackLayout {
-    size_t up[3] = {}, in = 0, up_bytes = 0;
+    size_t up[4] = {}, in = 0, up_bytes = 0;
     size_t h_out = 0, h_mix = 0, host_bytes = 0;
     size_t scratch[3] = {}, d_out = 0, d_mix = 0, dev_bytes = 0;
     size_t rows = 0, row = 0;   // the bytes of in and of out, and of mix
@@ -408,6 +412,11 @@ struct fs_context {
     std::vector<double> band_edges;
     float* d_carrier = nullptr;          // [B][carrier_stride(num_samples)] fp32
     float carrier_build_ms = 0.0f;       // device time of the last build (HIP events)
+    // fs_reverb_ears_set: the two-ear reverb's carrier set (null: none installed), what it was built from, and its generation —
+    // bumped by every replacement, so that a source with ears takes again (Source::ear_gen)
+    float* d_ear_carrier = nullptr;      // [2][B][carrier_stride(num_samples)] fp32: the mid rows cm_b, then the side rows cs_b
+    float ear_radius_cm = 0.0f, ear_speed_cm_s = 0.0f;
+    uint64_t ear_set_gen = 0;
     // The path queries' staging (fs_capi_paths.cpp), one per query: the queries share no buffer.  Each is sized for its query's
     // largest max_paths, max_near and max_candidates, so that only a larger count grows it; its segments are the query's PathLayout.
     // direct_stage: the kernel reads the pinned sources in place.  d_direct_off: the sample-offset tables
@@ -701,6 +710,10 @@ int check_band_edges(fs_context* ctx, const double* edges, const char* what);
 int check_spectral(fs_context* ctx, const fs_params* p);
 // the carrier set a reconstruct with these params uses: nullptr without FS_FLAG_SPECTRAL_IR; built (and waited for) on first use
 int carrier_for(fs_context* ctx, const fs_params* p, const float** out);
+// fs_reverb_ears_set's build for the band edges in force: a new [2][B][carrier_stride] set on the compute stream, waited for
+int build_ear_carriers(fs_context* ctx, float radius_cm, float speed_cm_s, const char* what, float** out);
+// ... and its installation in place of the one in force (nullptr: none), behind the reverb stream
+int install_ear_carriers(fs_context* ctx, float* set, float radius_cm, float speed_cm_s);
 
 // ---- fs_capi_scene.cpp --------------------------------------------------------------------------------------------
 // fs_scene_commit_progressive: swap the finished background tree in; drop / wait for a background build

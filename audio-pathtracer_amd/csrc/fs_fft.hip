@@ -192,6 +192,52 @@ __global__ __launch_bounds__(kFftBlock) void carrier_normalise(float* __restrict
     for (int i = threadIdx.x; i < ld; i += kFftBlock) row[i] = i < N ? row[i] * g : 0.0f;
 }
 
+// ---- fs_reverb_ears_set: the mid and side carriers (launch_build_ear_carriers).  blockIdx.y = row: [0, B) mid, [B, 2B) side ----
+// As carrier_spectrum, with the diffuse-field weight: gamma_k = sin(x_k) / x_k, x_k = 2 pi f_k (2 radius) / c, f_k = k fs / K; the mid
+// row gets a_k exp(i phi_k), a_k = sqrt((1 + gamma_k) / 2), the side row b_k exp(i psi_k), b_k = sqrt((1 - gamma_k) / 2), psi_k from
+// kEarSideSeed.  Everything in double, each product rounded to float once.
+__global__ __launch_bounds__(kFftBlock) void ear_carrier_spectrum(float2* __restrict__ X, int n, int B, CarrierBands bands, double fs,
+                                                                  double radius_cm, double speed_cm_s) {
+    const uint32_t p = blockIdx.x * kFftBlock + threadIdx.x;
+    if (p >= (1u << n)) return;
+    const int row = blockIdx.y;
+    const bool side = row >= B;
+    const int b = side ? row - B : row;
+    const uint32_t k = __brev(p) >> (32 - n);
+    float2 v = make_float2(0.0f, 0.0f);
+    if ((int)k >= bands.lo[b] && (int)k < bands.lo[b + 1]) {
+        const double f = (double)k * fs / (double)(1u << n);
+        const double x = 2.0 * 3.14159265358979323846 * f * (2.0 * radius_cm) / speed_cm_s;
+        const double gamma = x == 0.0 ? 1.0 : sin(x) / x;
+        const double wgt = side ? sqrt((1.0 - gamma) / 2.0) : sqrt((1.0 + gamma) / 2.0);
+        const double turns = (double)(uint32_t)(splitmix64((side ? kEarSideSeed : kCarrierSeed) + k) >> 40) * 0x1p-24;   // (exact)
+        double sn, cs;
+        sincospi(2.0 * turns, &sn, &cs);
+        v = make_float2((float)(wgt * cs), (float)(wgt * sn));
+    }
+    X[((size_t)row << n) + p] = v;
+}
+// One scale for the band's two rows: g_b = sqrt(N / sum_{n<N} (r^M_b[n]^2 + r^S_b[n]^2)), the sum in double, one workgroup per band;
+// both rows in place, their padding up to ld zeroed.  c: [2][B][ld].
+__global__ __launch_bounds__(kFftBlock) void ear_carrier_normalise(float* __restrict__ c, int B, int N, int ld) {
+    __shared__ double s_sum[kFftBlock];
+    float* mid = c + (size_t)blockIdx.x * ld;
+    float* sid = c + ((size_t)B + blockIdx.x) * ld;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < N; i += kFftBlock) acc += (double)mid[i] * (double)mid[i] + (double)sid[i] * (double)sid[i];
+    s_sum[threadIdx.x] = acc;
+    for (int w = kFftBlock / 2; w > 0; w >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < w) s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+    }
+    __syncthreads();
+    const float g = s_sum[0] > 0.0 ? (float)sqrt((double)N / s_sum[0]) : 0.0f;
+    for (int i = threadIdx.x; i < ld; i += kFftBlock) {
+        mid[i] = i < N ? mid[i] * g : 0.0f;
+        sid[i] = i < N ? sid[i] * g : 0.0f;
+    }
+}
+
 }  // namespace
 
 // x: [N] complex work buffer, y: [3][N], W: [max(N/2,1)] twiddles, resp: absorption | transmission | scattering
@@ -239,6 +285,25 @@ void launch_build_carriers(int B, int n, int N, int ld, const CarrierBands& band
     for (int ls = c; ls < n; ++ls)
         hipLaunchKernelGGL(fft_dit_global, dim3(half_blocks, (unsigned)B), dim3(kFftBlock), 0, s, y, W, n, ls, ld, out, 1.0f);
     hipLaunchKernelGGL(carrier_normalise, dim3((unsigned)B), dim3(kFftBlock), 0, s, out, N, ld);
+}
+
+// The two-ear reverb's carriers (fs_reverb_ears_set; definition: DESIGN.md section 8, "Two-ear late reverb"): 2B rows through the same
+// passes — rows [0, B) the mid carriers cm_b, rows [B, 2B) the side carriers cs_b — and one scale per band over its two rows.
+// X, y: [2B][K] complex work buffers; W, zeros as above; out: [2][B][ld].
+void launch_build_ear_carriers(int B, int n, int N, int ld, const CarrierBands& bands, double fs, double radius_cm, double speed_cm_s,
+                               float2* X, float2* y, const float2* W, const float* zeros, float* out, hipStream_t s) {
+    const int K = 1 << n;
+    const int c = n < kFftChunkLog ? n : kFftChunkLog;
+    const size_t lds = sizeof(float2) << c;
+    hipLaunchKernelGGL(ear_carrier_spectrum, dim3((unsigned)((K + kFftBlock - 1) / kFftBlock), (unsigned)(2 * B)), dim3(kFftBlock), 0, s, X,
+                       n, B, bands, fs, radius_cm, speed_cm_s);
+    for (int r = 0; r < 2 * B; ++r)
+        hipLaunchKernelGGL(fft_dit_local, dim3(1u << (n - c), 1), dim3(kFftBlock), lds, s, X + ((size_t)r << n), y + ((size_t)r << n),
+                           zeros, zeros, zeros, W, n, c, ld, out + (size_t)r * ld, 1.0f);
+    const unsigned half_blocks = (unsigned)(((K >> 1) + kFftBlock - 1) / kFftBlock);
+    for (int ls = c; ls < n; ++ls)
+        hipLaunchKernelGGL(fft_dit_global, dim3(half_blocks, (unsigned)(2 * B)), dim3(kFftBlock), 0, s, y, W, n, ls, ld, out, 1.0f);
+    hipLaunchKernelGGL(ear_carrier_normalise, dim3((unsigned)B), dim3(kFftBlock), 0, s, out, B, N, ld);
 }
 
 }  // namespace fs

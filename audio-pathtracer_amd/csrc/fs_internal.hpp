@@ -650,6 +650,15 @@ struct ReverbPart {
     const int* fade; int n_fade;    // ... and with two
     const float2* W;                // twiddles of N = 1 << n
     int n, K, frame, ir_size;
+    // the rows of sources with ears (fs_reverb_set_ears): partitioned rows with lists of their own and two spectrum sets per IR
+    // copy — ReverbPartItem::h, h_to, take_from, take_to each [2][K][N], M_p then S_p; take_ir = the source's B band rows
+    const int* ear_plain; int n_ear_plain;
+    const int* ear_fade; int n_ear_fade;
+};
+// fs_reverb_ears_set's carrier set, as the ear kernels read it: c [2][B][ld] fp32 (mid rows, then side rows)
+struct ReverbEars {
+    const float* c;
+    int B, ld;
 };
 struct ReverbBatch {
     const ReverbItem* items;        // [count]
@@ -674,7 +683,10 @@ void launch_reverb_batch(const ReverbBatch& b, hipStream_t s);
 void launch_callback_mix(const float* out, int count, int frame, float* mix, hipStream_t s);
 // take: the partitioned rows that take a newer IR in this callback (n_take >= 1)
 void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, hipStream_t s);
-// the window transforms, the products of the two lists (each launched only when it has rows), the inverse and epilogue
+void launch_reverb_ears_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, const ReverbEars& e, hipStream_t s);
+// fs_reverb_copy_ear_impulse_responses: left = m + s, right = m - s of the B band rows `bands` ([B][n]), with the take's expression
+void launch_reverb_ears_ir(const float* bands, const ReverbEars& e, int n, float* left, float* right, hipStream_t s);
+// the window transforms, the products of the four lists (each launched only when it has rows), the inverse and epilogue
 void launch_reverb_part(const ReverbPartItem* items, const ReverbPart& p, int count, int literal_tail, const float* in, float* out,
                         hipStream_t s);
 // fs_direct_render.hip (the direct-sound callback).  A source's state is one device block (Source::dr.d): this header, then at
@@ -893,11 +905,14 @@ void launch_apply_material_fd(const float* in, int L, int n, float2* x, float2* 
 // K = 2^n point spectrum belongs to band b when lo[b] <= k < lo[b + 1] (host-side, from the band edges in double); its phase is
 // 2 pi (splitmix64(kCarrierSeed + k) >> 40) 2^-24.  out: [B][ld] fp32, ld = carrier_stride(N) (below)
 constexpr uint64_t kCarrierSeed = 0x5EED;
+constexpr uint64_t kEarSideSeed = 0x5EED0EA2;   // fs_reverb_ears_set: the side carriers' phases psi_k
 constexpr int kCarrierMaxLog = 24;   // K <= 2^24 (the material filter's largest transform)
 struct CarrierBands { int32_t lo[FS_MAX_BANDS + 1]; };
 // a carrier row's length: N rounded up to 64 samples (a whole number of the reconstruct's chunks: 16-byte loads of a thread's own)
 __host__ __device__ constexpr int carrier_stride(int num_samples) { return (num_samples + 63) / 64 * 64; }
 void launch_build_carriers(int B, int n, int N, int ld, const CarrierBands& bands, float2* X, float2* y, const float2* W,
                            const float* zeros, float* out, hipStream_t s);
+void launch_build_ear_carriers(int B, int n, int N, int ld, const CarrierBands& bands, double fs, double radius_cm, double speed_cm_s,
+                               float2* X, float2* y, const float2* W, const float* zeros, float* out, hipStream_t s);
 
 }  // namespace fs

@@ -18,6 +18,9 @@
 // Every kernel finds its row through a table of ReverbPartItem (fs_internal.hpp), the rows of a call side by side in the grid;
 // nothing a row computes depends on the other rows, so a source gets the same bits alone or in any batch.  The file is built
 // with -ffp-contract=off: what is fused is written as fmaf.
+//
+// A source with ears (fs_reverb_set_ears) is such a row with two spectrum sets per IR copy and a take and a product of its own
+// (reverb_ears_take_kernel, reverb_ears_mac_kernel, at the end of the kernels); the window, delay line, inverse and fade are shared.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -30,6 +33,7 @@ namespace {
 constexpr int kPartBlock = 256;
 constexpr int kMacBins = 64;                        // bins per multiply-accumulate workgroup: one wavefront wide
 constexpr int kMacWaves = kPartBlock / kMacBins;    // its wavefronts share the partitions: wave w takes p = w, w + 4, ...
+constexpr uint32_t kEarsMaxFrame = 2048;            // the engine's largest frame (fs_reverb_init), N <= 2 * kEarsMaxFrame
 
 __device__ __forceinline__ float2 padd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 psub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
@@ -225,7 +229,147 @@ __global__ __launch_bounds__(kPartBlock) void reverb_part_inverse_kernel(const R
     }
 }
 
+// ---- sources with ears (fs_reverb_set_ears; definition: DESIGN.md section 8, "Two-ear late reverb") ----
+// h_L = m + s, h_R = m - s with m[i] = (1/sqrt(B)) sum_b env_b[i] cm_b[i], s[i] likewise with cs_b: the left channel is convolved
+// with h_L and the right with h_R in the one packed transform, Y[k] = M_p[k] X[k] + S_p[k] conj(X[(N - k) mod N]).
+//
+// (m[i], s[i]): fp32, the bands in ascending order, each product rounded before it is added, the scale last — THE expression of both
+// kernels that form them (the take and the copy)
+__device__ __forceinline__ float2 ears_mid_side(const float* __restrict__ env, const ReverbEars e, int num_samples, uint32_t i) {
+    float m = 0.0f, s = 0.0f;
+    const float* __restrict__ cm = e.c + i;
+    const float* __restrict__ cs = e.c + (size_t)e.B * (size_t)e.ld + i;
+    for (int b = 0; b < e.B; ++b) {
+        const float v = env[(size_t)b * (size_t)num_samples + i];
+        m = m + v * cm[(size_t)b * (size_t)e.ld];
+        s = s + v * cs[(size_t)b * (size_t)e.ld];
+    }
+    const float g = 1.0f / sqrtf((float)e.B);
+    return make_float2(m * g, s * g);
+}
+// acc + s conj(x), each component two fused steps in a fixed order
+__device__ __forceinline__ float2 pmac_conj(float2 acc, float2 s, float2 x) {
+    return make_float2(fmaf(s.x, x.x, fmaf(s.y, x.y, acc.x)), fmaf(s.y, x.x, fmaf(-s.x, x.y, acc.y)));
+}
+
+// reverb_part_take_kernel for the rows with ears: workgroup (p, k) owns partition p of row take[k], in both spectrum sets of a copy
+// ([2][K][N]: M, then S).  The fold of a cut-short fade on both sets, then M_p := FFT_N(m[pF .. pF + F) zero-padded) and S_p likewise
+// from the row's B band rows (take_ir) and the carrier set.
+__global__ __launch_bounds__(kPartBlock) void reverb_ears_take_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ take,
+                                                                      const float2* __restrict__ W, int n, int K, int frame, int ir_size,
+                                                                      ReverbEars e) {
+    extern __shared__ __attribute__((aligned(16))) float2 sh[];
+    const ReverbPartItem it = items[take[blockIdx.y]];
+    const uint32_t N = 1u << n;
+    const uint32_t p = blockIdx.x;
+    const size_t set = (size_t)K << n;   // from M to S
+    float2* __restrict__ h_to = it.take_to + (size_t)p * N;
+    const float a = it.take_a;
+    if (a > 0.0f) {
+        float2* __restrict__ h_from = it.take_from + (size_t)p * N;
+        for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) {
+            const float2 f = h_from[i], t = h_to[i];
+            h_from[i] = make_float2((1.0f - a) * f.x + a * t.x, (1.0f - a) * f.y + a * t.y);
+            const float2 fs = h_from[set + i], ts = h_to[set + i];
+            h_from[set + i] = make_float2((1.0f - a) * fs.x + a * ts.x, (1.0f - a) * fs.y + a * ts.y);
+        }
+    }
+    const uint32_t k0 = p * (uint32_t)frame;
+    float side[kEarsMaxFrame / kPartBlock];   // s of the thread's samples of the partition, kept while m is transformed
+#pragma unroll
+    for (uint32_t q = 0; q < kEarsMaxFrame / kPartBlock; ++q) {
+        const uint32_t i = threadIdx.x + q * kPartBlock;
+        float2 ms = make_float2(0.0f, 0.0f);
+        if (i < (uint32_t)frame && k0 + i < (uint32_t)ir_size) ms = ears_mid_side(it.take_ir, e, ir_size, k0 + i);
+        side[q] = ms.y;
+        if (i < N) sh[i] = make_float2(ms.x, 0.0f);
+    }
+    for (uint32_t i = kEarsMaxFrame + threadIdx.x; i < N; i += kPartBlock) sh[i] = make_float2(0.0f, 0.0f);   // (N = 4096: the upper half)
+    lds_fft_dif(sh, W, n);
+    for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) h_to[i] = sh[i];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t q = 0; q < kEarsMaxFrame / kPartBlock; ++q) {
+        const uint32_t i = threadIdx.x + q * kPartBlock;
+        if (i < N) sh[i] = make_float2(side[q], 0.0f);
+    }
+    for (uint32_t i = kEarsMaxFrame + threadIdx.x; i < N; i += kPartBlock) sh[i] = make_float2(0.0f, 0.0f);
+    lds_fft_dif(sh, W, n);
+    for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) h_to[set + i] = sh[i];
+}
+
+// reverb_part_mac_kernel for the rows with ears: the same tiling and the same order of sums, with a second H stream and the
+// mirrored X.  Position j of the bit-reversed storage holds bin brev(j); the bin N - brev(j) (mod N) lives at
+// jm = brev((N - brev(j)) mod N).  The mirrors of a 64-aligned block of positions are one 64-aligned block (read in descending
+// order, except block 0's), so a wavefront's mirrored load is 512 contiguous bytes too.  Per partition: acc += M_p X, then
+// acc += S_p conj(X_mirror).
+template <bool FADE>
+__global__ __launch_bounds__(kPartBlock) void reverb_ears_mac_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ list,
+                                                                     int n, int K, int literal) {
+    __shared__ float2 s_sum[FADE ? 2 : 1][kMacWaves][kMacBins];
+    const ReverbPartItem it = items[list[blockIdx.y]];
+    const uint32_t N = 1u << n;
+    const uint32_t lane = threadIdx.x & (kMacBins - 1), w = threadIdx.x / kMacBins;
+    const uint32_t b = blockIdx.x * kMacBins + lane;
+    const bool live = b < N;   // (N = 32: half a wavefront)
+    const uint32_t bm = __brev((N - (__brev(b) >> (32 - n))) & (N - 1u)) >> (32 - n);   // (live: < N)
+    const size_t set = (size_t)K << n;
+    const float2* __restrict__ H = it.h;
+    const float2* __restrict__ H_to = it.h_to;
+    const float2* __restrict__ xring = part_xring(it.state, n);
+    const float2* __restrict__ xnow = part_xnow(it.state, n);
+    float2 acc = make_float2(0.0f, 0.0f), acc_to = make_float2(0.0f, 0.0f);
+    if (live) {
+#pragma unroll 4
+        for (int p = (int)w; p < K; p += kMacWaves) {
+            int sp = it.slot - p;
+            sp += sp < 0 ? K : 0;
+            const float2* __restrict__ X = (p == 0 && literal) ? xnow : xring + ((size_t)sp << n);
+            const float2 x = X[b], xm = X[bm];
+            const size_t at = ((size_t)p << n) + b;
+            acc = pmac_conj(pmac(acc, H[at], x), H[set + at], xm);
+            if (FADE) acc_to = pmac_conj(pmac(acc_to, H_to[at], x), H_to[set + at], xm);
+        }
+    }
+    s_sum[0][w][lane] = acc;
+    if (FADE) s_sum[FADE ? 1 : 0][w][lane] = acc_to;
+    __syncthreads();
+    if (w == 0 && live) {
+        float2* __restrict__ Y = part_y(it.state, n);
+        float2 v = s_sum[0][0][lane];
+#pragma unroll
+        for (int k = 1; k < kMacWaves; ++k) v = padd(v, s_sum[0][k][lane]);
+        Y[b] = v;
+        if (FADE) {
+            float2 u = s_sum[FADE ? 1 : 0][0][lane];
+#pragma unroll
+            for (int k = 1; k < kMacWaves; ++k) u = padd(u, s_sum[FADE ? 1 : 0][k][lane]);
+            Y[N + b] = u;
+        }
+    }
+}
+
+// fs_reverb_copy_ear_impulse_responses: the ear IRs of one source's band rows, sample by sample
+__global__ __launch_bounds__(kPartBlock) void reverb_ears_ir_kernel(const float* __restrict__ bands, ReverbEars e, int num_samples,
+                                                                    float* __restrict__ left, float* __restrict__ right) {
+    const uint32_t i = blockIdx.x * kPartBlock + threadIdx.x;
+    if (i >= (uint32_t)num_samples) return;
+    const float2 ms = ears_mid_side(bands, e, num_samples, i);
+    left[i] = ms.x + ms.y;
+    right[i] = ms.x - ms.y;
+}
+
 }  // namespace
+
+void launch_reverb_ears_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, const ReverbEars& e, hipStream_t s) {
+    hipLaunchKernelGGL(reverb_ears_take_kernel, dim3((unsigned)p.K, (unsigned)n_take), dim3(kPartBlock), sizeof(float2) << p.n, s, items,
+                       take, p.W, p.n, p.K, p.frame, p.ir_size, e);
+}
+
+void launch_reverb_ears_ir(const float* bands, const ReverbEars& e, int n, float* left, float* right, hipStream_t s) {
+    hipLaunchKernelGGL(reverb_ears_ir_kernel, dim3((unsigned)((n + kPartBlock - 1) / kPartBlock)), dim3(kPartBlock), 0, s, bands, e, n, left,
+                       right);
+}
 
 void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, hipStream_t s) {
     hipLaunchKernelGGL(reverb_part_take_kernel, dim3((unsigned)p.K, (unsigned)n_take), dim3(kPartBlock), sizeof(float2) << p.n, s, items,
@@ -245,6 +389,12 @@ void launch_reverb_part(const ReverbPartItem* items, const ReverbPart& p, int co
     if (p.n_fade > 0)
         hipLaunchKernelGGL(reverb_part_mac_kernel<true>, dim3(tiles, (unsigned)p.n_fade), dim3(kPartBlock), 0, s, items, p.fade, p.n, p.K,
                            literal_tail);
+    if (p.n_ear_plain > 0)
+        hipLaunchKernelGGL(reverb_ears_mac_kernel<false>, dim3(tiles, (unsigned)p.n_ear_plain), dim3(kPartBlock), 0, s, items, p.ear_plain, p.n,
+                           p.K, literal_tail);
+    if (p.n_ear_fade > 0)
+        hipLaunchKernelGGL(reverb_ears_mac_kernel<true>, dim3(tiles, (unsigned)p.n_ear_fade), dim3(kPartBlock), 0, s, items, p.ear_fade, p.n,
+                           p.K, literal_tail);
     hipLaunchKernelGGL(reverb_part_inverse_kernel, dim3((unsigned)count), dim3(kPartBlock), lds + sizeof(float2) * (size_t)p.frame, s, items,
                        p.W, p.n, p.frame, out);
 }

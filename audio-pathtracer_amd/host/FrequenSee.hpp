@@ -85,6 +85,7 @@ public:
 
 private:
     friend class AudioRayTracingSubsystem;
+    friend class FrequenSeeAudioReverbPlugin;
     friend class FrequenSeeAudioOcclusionPlugin;
     friend class FrequenSeeAudioReflectionPlugin;
     friend class FrequenSeeAudioBinauralPlugin;
@@ -315,6 +316,7 @@ private:
     bool Streamed_ = false;
     friend class FrequenSeeAudioComponent;
     friend class MaterialAcousticProcessor;
+    friend class FrequenSeeAudioReverbPlugin;
     friend class FrequenSeeAudioOcclusionPlugin;
     friend class FrequenSeeAudioReflectionPlugin;
     friend class FrequenSeeAudioBinauralPlugin;
@@ -432,6 +434,48 @@ public:
                                             (int32_t)Props.Absorption.size(), Out.Specular.data(), Out.Diffuse.data(),
                                             Out.Transmitted.data()));
         return Out;
+    }
+
+private:
+    AudioRayTracingSubsystem* SubSys_;
+};
+
+// FFrequenSeeAudioReverbPlugin (Private/FrequenSeeAudioReverbPlugin.cpp:74-213): per audio callback every source's block is
+// convolved with its impulse response — fs_reverb_process_batch, one call for all sources.  Not in the reference: Engine (the
+// partitioned FFT engine) and Ears, a two-ear late field with the interaural coherence of a diffuse field (SetEars installs the
+// context's ear set; a source gets ears at its OnInitSource, which then also selects the partitioned engine).
+class FrequenSeeAudioReverbPlugin {
+public:
+    int FrameSize = 1024;   // AudioCallbackBufferFrameSize, Config/DefaultEngine.ini:13
+    int Engine = FS_REVERB_ENGINE_DIRECT;
+    bool Ears = false;
+    explicit FrequenSeeAudioReverbPlugin(AudioRayTracingSubsystem& SubSys) : SubSys_(&SubSys) {}
+    void Initialize(int BufferLength = 1024) { FrameSize = BufferLength; }
+    void SetEars(float RadiusCm = FS_HRTF_DEFAULT_RADIUS_CM, float SoundSpeedCmS = FS_HRTF_DEFAULT_SOUND_SPEED_CM_S) {
+        fs_reverb_ears_desc D;
+        fs_reverb_ears_default(&D);
+        D.radius_cm = RadiusCm; D.sound_speed_cm_s = SoundSpeedCmS;
+        SubSys_->Check(fs_reverb_ears_set(SubSys_->Ctx_, &D));
+        Ears = true;
+    }
+    void OnInitSource(const FrequenSeeAudioComponent& C) {
+        SubSys_->Check(fs_reverb_set_engine(SubSys_->Ctx_, C.Handle_, Ears ? FS_REVERB_ENGINE_PARTITIONED : Engine));
+        SubSys_->Check(fs_reverb_set_ears(SubSys_->Ctx_, C.Handle_, Ears ? 1 : 0));
+        SubSys_->Check(fs_reverb_init(SubSys_->Ctx_, C.Handle_, FrameSize));
+    }
+    void OnReleaseSource(const FrequenSeeAudioComponent& C) { SubSys_->Check(fs_reverb_release(SubSys_->Ctx_, C.Handle_)); }
+    // In [count][FrameSize * 2] interleaved stereo, row i for Sources[i]; Out [count][FrameSize * 2] or nullptr, Mix [FrameSize * 2] or nullptr
+    void ProcessAudio(const std::vector<FrequenSeeAudioComponent*>& Sources, const float* In, float* Out, float* Mix = nullptr) {
+        std::vector<fs_source> H;
+        std::vector<int32_t> On;
+        for (const auto* s : Sources) { H.push_back(s->Handle_); On.push_back(s->bApplyReverb ? 1 : 0); }
+        SubSys_->Check(fs_reverb_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, Out, On.data(), 0u, Mix));
+    }
+    // h_L and h_R of the source's newest impulse response, for a host with a convolver of its own
+    void EarImpulseResponses(const FrequenSeeAudioComponent& C, std::vector<float>& Left, std::vector<float>& Right) const {
+        const int n = fs_num_samples(SubSys_->Ctx_);
+        Left.assign((size_t)n, 0.0f); Right.assign((size_t)n, 0.0f);
+        SubSys_->Check(fs_reverb_copy_ear_impulse_responses(SubSys_->Ctx_, C.Handle_, Left.data(), Right.data(), n));
     }
 
 private:

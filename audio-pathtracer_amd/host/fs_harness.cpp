@@ -73,12 +73,33 @@ int main(int argc, char** argv) {
         AcousticOutputs Fd = Proc.ApplyMaterialFD(Block, Props);
         double fd_err = 0;
         for (int i = 0; i < n; ++i) fd_err = std::fmax(fd_err, std::fabs(Fd.Diffuse[(size_t)i] - 0.5 * ir[i]));
+        // the reverb plugin with ears: a half-scale unit impulse in both channels comes back as 0.5 h_L | 0.5 h_R of an installed,
+        // alternating and decaying IR (everything above has been computed from the traced one)
+        FrequenSeeAudioReverbPlugin Reverb(SubSys);
+        const int F = 256;
+        std::vector<float> Installed((size_t)n);
+        for (int i = 0; i < n; ++i) Installed[(size_t)i] = (i % 2 ? -0.5f : 0.5f) * std::exp(-(float)i / 100.0f);
+        Comp.SetImpulseResponse(Installed);
+        Reverb.Initialize(F);
+        Reverb.SetEars();
+        Reverb.OnInitSource(Comp);
+        std::vector<float> In(2 * (size_t)F, 0.0f), Out(2 * (size_t)F, 0.0f), Left, Right;
+        In[0] = In[1] = 0.5f;
+        Reverb.ProcessAudio({&Comp}, In.data(), Out.data());
+        Reverb.EarImpulseResponses(Comp, Left, Right);
+        double ears_err = 0, ears_peak = 0, ears_diff = 0;
+        for (int i = 0; i < F && i < n; ++i) {
+            ears_err = std::fmax(ears_err, std::fmax(std::fabs(Out[2 * (size_t)i] - 0.5 * Left[(size_t)i]), std::fabs(Out[2 * (size_t)i + 1] - 0.5 * Right[(size_t)i])));
+            ears_peak = std::fmax(ears_peak, std::fmax(std::fabs(0.5 * Left[(size_t)i]), std::fabs(0.5 * Right[(size_t)i])));
+            ears_diff = std::fmax(ears_diff, std::fabs((double)Left[(size_t)i] - (double)Right[(size_t)i]));
+        }
+        Reverb.OnReleaseSource(Comp);
         std::printf("{\"frames\": %d, \"pairs\": %d, \"depth\": %d, \"frames_per_s\": %.1f, \"rays_per_s\": %.0f, "
                     "\"energy_sum_first_frame\": %.6f, \"ir_samples\": %d, \"ir_peak\": %.6f, "
                     "\"occlusion_attenuation\": %.6f, \"legacy_rays_reaching\": %u, \"material_fd_max_err\": %.3g, "
-                    "\"saved\": \"%s\"}\n",
+                    "\"ears_max_err\": %.3g, \"ears_peak\": %.6g, \"ears_left_right_max_diff\": %.6g, \"saved\": \"%s\"}\n",
                     frames, pairs, depth, frames / s, 2.0 * pairs * frames / s, e, n, peak,
-                    snd.occlusion_attenuation, snd.rays_reaching_listener, fd_err, out.c_str());
+                    snd.occlusion_attenuation, snd.rays_reaching_listener, fd_err, ears_err, ears_peak, ears_diff, out.c_str());
     } catch (const std::exception& ex) {
         std::fprintf(stderr, "fs_harness: %s\n", ex.what());
         return 1;

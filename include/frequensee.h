@@ -51,6 +51,7 @@
  *             fs_copy_band_impulse_response fs_set_impulse_response fs_trace_rays
  *             fs_save_array_to_file fs_load_float_array fs_save_impulse_response
  *             fs_reverb_init fs_reverb_process fs_reverb_process_batch fs_reverb_release fs_reverb_set_crossfade fs_reverb_set_engine fs_apply_material_fd
+ *             fs_reverb_ears_default fs_reverb_ears_set fs_reverb_ears_info fs_reverb_set_ears fs_reverb_copy_ear_impulse_responses
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
  *             fs_source_set_orientation fs_source_set_directivity fs_get_room_parameters
  *             fs_source_set_order_window fs_source_get_order_window
@@ -1297,6 +1298,56 @@ int fs_reverb_set_crossfade(fs_context* ctx, fs_source src, int32_t samples);
 #define FS_REVERB_ENGINE_DIRECT      0   /* the tap-by-tap kernels, the default */
 #define FS_REVERB_ENGINE_PARTITIONED 1
 int fs_reverb_set_engine(fs_context* ctx, fs_source src, int32_t engine);
+/* Two-ear late reverb (EXTENDED; DESIGN.md section 8, "Two-ear late reverb").  A reconstruct publishes one channel row, and the
+ * callback convolves both input channels with it: the tail of a mono source sits inside the head.  A source with EARS convolves
+ * the left input with h_L and the right with h_R, two IRs with the interaural coherence of a diffuse field — the late field has no
+ * direction, only the coherence gamma(f) of two points a head's width apart.  Nothing in the trace or the reconstruct changes.
+ *
+ * The ear carriers are context-wide and use the bands, the bin assignment and K (the smallest power of two >= num_samples) of
+ * FS_FLAG_SPECTRAL_IR, fs_set_band_edges included:
+ *   1. bin k in [1, K/2), in double: f_k = k fs / K;  x_k = 2 pi f_k (2 radius_cm) / sound_speed_cm_s;
+ *      gamma_k = sin(x_k) / x_k (1 at x_k = 0);  a_k = sqrt((1 + gamma_k) / 2),  b_k = sqrt((1 - gamma_k) / 2).
+ *   2. mid spectrum of band b: a_k exp(i phi_k) on the band's bins, phi_k = 2 pi (splitmix64(0x5EED + k) >> 40) 2^-24 (the
+ *      spectral IR's phase);
+ *   3. side spectrum of band b: b_k exp(i psi_k), psi_k = 2 pi (splitmix64(0x5EED0EA2 + k) >> 40) 2^-24;
+ *   4. each product of 2 and 3 is formed in double and rounded to float once;
+ *   5. r^M_b, r^S_b = the real inverse transforms of those spectra (the spectral IR's inverse passes);
+ *   6. one scale per band for both rows: g_b = sqrt(N / sum_{n<N} (r^M_b[n]^2 + r^S_b[n]^2)), the sum in double;
+ *      cm_b = g_b r^M_b, cs_b = g_b r^S_b;
+ *   7. the left carrier is cm_b + cs_b, the right cm_b - cs_b: mean power (L^2 + R^2) / 2 = 1 over the IR, coherence
+ *      a_k^2 - b_k^2 = gamma_k per bin.
+ * Per source:
+ *   8. m[n] = (1/sqrt(B)) sum_b env_b[n] cm_b[n], s[n] likewise with cs_b; env_b = the source's device-resident band row b
+ *      (what fs_copy_band_impulse_response copies), whatever flags the reconstruct had; after fs_set_impulse_response every band
+ *      row is the installed IR;
+ *   9. the sums are fp32 in ascending band order (the exact expression: DESIGN.md);
+ *  10. h_L = m + s, h_R = m - s.
+ * The callback of a source with ears gives out_L = clamp(h_L * u_L), out_R = clamp(h_R * u_R), u exactly what the partitioned
+ * engine convolves (FS_REVERB_LITERAL_TAIL included); every rule of fs_reverb_process_batch, fs_reverb_set_crossfade and
+ * fs_reverb_set_engine holds with "the IR" read as the pair.
+ *
+ * fs_reverb_ears_set (game thread; desc == NULL: clear) builds the set on the compute stream and waits for it.  Threading
+ * contract of fs_reverb_init: never concurrent with a callback.  radius_cm >= 0 (0: gamma = 1, s = 0, the two ears are equal),
+ * sound_speed_cm_s > 0, both finite, struct_size as fs_reverb_ears_default fills it; the band edges in force must give every band
+ * a bin (FS_FLAG_SPECTRAL_IR's condition and text) — else FS_ERR_INVALID_ARGUMENT and nothing changes.  Replacing a set makes
+ * every source initialised with ears take again at its next callback (through its crossfade, if it has one); clearing is
+ * FS_ERR_INVALID_ARGUMENT while such a source exists.  fs_set_band_edges with a set installed rebuilds it, under the same contract.
+ * fs_reverb_set_ears records the choice like fs_reverb_set_engine: it takes effect at the source's next fs_reverb_init, which is
+ * FS_ERR_INVALID_ARGUMENT with ears on when the source's engine is not FS_REVERB_ENGINE_PARTITIONED or no set is installed (the
+ * message says which).  That init allocates the second spectrum set ([2][K][N] per IR copy): the callback allocates nothing.
+ * fs_reverb_copy_ear_impulse_responses (game thread, ordered like fs_copy_band_impulse_response; needs an installed set, not
+ * fs_reverb_init) copies h_L and h_R of the source's newest device-resident IR, n = fs_num_samples each — for hosts with a
+ * convolver of their own. */
+typedef struct fs_reverb_ears_desc {
+    uint32_t struct_size;
+    float    radius_cm;          /* FS_HRTF_DEFAULT_RADIUS_CM */
+    float    sound_speed_cm_s;   /* FS_HRTF_DEFAULT_SOUND_SPEED_CM_S (real physics, as fs_hrtf_spherical_head) */
+} fs_reverb_ears_desc;
+void fs_reverb_ears_default(fs_reverb_ears_desc* desc);
+int fs_reverb_ears_set(fs_context* ctx, const fs_reverb_ears_desc* desc /* NULL: clear */);
+int fs_reverb_ears_info(fs_context* ctx, float* radius_cm, float* sound_speed_cm_s, int32_t* installed); /* any pointer may be NULL */
+int fs_reverb_set_ears(fs_context* ctx, fs_source src, int32_t on);
+int fs_reverb_copy_ear_impulse_responses(fs_context* ctx, fs_source src, float* left, float* right, int32_t n);
 
 /* ---- direct sound on the audio thread (EXTENDED): what fs_update_direct_paths' rows are rendered with ---------------------
  *      The reference's slot is FFrequenSeeAudioOcclusionPlugin::ProcessAudio (Private/FrequenSeeAudioOcclusionPlugin.cpp:33-50),
