@@ -9,12 +9,12 @@ sharding (multi-GPU pair partition).
 from . import _capi, scenes, sharding  # noqa: F401
 from ._capi import FrequenSeeError, default_config, default_params  # noqa: F401
 from .component import (AudioRayTracingSubsystem, Context, FrequenSeeAudioComponent,  # noqa: F401
-                        FrequenSeeAudioBinauralPlugin, FrequenSeeAudioOcclusionPlugin, FrequenSeeAudioReflectionPlugin,
+                        FrequenSeeAudioAmbisonicPlugin, FrequenSeeAudioBinauralPlugin, FrequenSeeAudioOcclusionPlugin, FrequenSeeAudioReflectionPlugin,
                         FrequenSeeAudioReverbPlugin,
                         MaterialAcousticProcessor)
 
 __all__ = ["AudioRayTracingSubsystem", "FrequenSeeAudioComponent", "FrequenSeeAudioReverbPlugin", "FrequenSeeAudioOcclusionPlugin",
-           "FrequenSeeAudioReflectionPlugin", "FrequenSeeAudioBinauralPlugin",
+           "FrequenSeeAudioReflectionPlugin", "FrequenSeeAudioBinauralPlugin", "FrequenSeeAudioAmbisonicPlugin",
            "MaterialAcousticProcessor", "Context",
            "FrequenSeeError",
            "default_config", "default_params", "scenes", "sharding"]

@@ -66,6 +66,7 @@ EXPORTS = [
     "fs_reflection_render_init", "fs_reflection_render_release", "fs_reflection_render_process_batch",
     "fs_hrtf_set", "fs_hrtf_info", "fs_hrtf_spherical_head",
     "fs_binaural_render_init", "fs_binaural_render_release", "fs_binaural_render_process_batch",
+    "fs_ambisonic_encode", "fs_ambisonic_render_init", "fs_ambisonic_render_release", "fs_ambisonic_render_process_batch",
 ]
 MAX_DIRECTIVITY_SAMPLES = 181   # FS_MAX_DIRECTIVITY_SAMPLES: 1 degree steps
 ORDER_UNBOUNDED = 0x7fffffff    # FS_ORDER_UNBOUNDED: no upper end of a source's order window
@@ -117,6 +118,7 @@ MAX_HRTF_DIRECTIONS = 4096
 MAX_HRTF_TAPS = 512
 HRTF_DEFAULT_RADIUS_CM = 8.75
 HRTF_DEFAULT_SOUND_SPEED_CM_S = 34300.0
+MAX_AMBISONIC_ORDER = 3   # FS_MAX_AMBISONIC_ORDER: the bus has (order + 1)^2 channels, ACN order, SN3D normalisation
 BINAURAL_DIRECT_KEY = 0x1FFFFFFF   # the direct sound's voice: a first-order key (a triangle index) no scene below 2^29 - 1 triangles uses
 
 
@@ -524,6 +526,14 @@ class BinauralRenderRow(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("sounding", "started", "ended", "dropped")]
 
 
+AmbisonicVoice = BinauralVoice   # fs_ambisonic_voice: the same record
+
+
+class AmbisonicRenderRow(C.Structure):
+    """fs_ambisonic_render_row (include/frequensee.h): one source's counts of a callback, an array element (no struct_size)"""
+    _fields_ = [(k, C.c_uint32) for k in ("sounding", "started", "ended", "dropped")]
+
+
 class FrequenSeeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"frequensee status {code}: {msg}")
@@ -663,6 +673,10 @@ def load():
         "fs_binaural_render_init": (C.c_int, [vp, i32, i32, i32, i32, C.c_float]),
         "fs_binaural_render_release": (C.c_int, [vp, i32]),
         "fs_binaural_render_process_batch": (C.c_int, [vp, C.c_void_p, i32, f32p, C.c_void_p, C.c_void_p, i32, f32p, f32p, C.c_void_p]),
+        "fs_ambisonic_encode": (C.c_int, [i32, f32p, f32p]),
+        "fs_ambisonic_render_init": (C.c_int, [vp, i32, i32, i32, i32, C.c_float, i32]),
+        "fs_ambisonic_render_release": (C.c_int, [vp, i32]),
+        "fs_ambisonic_render_process_batch": (C.c_int, [vp, C.c_void_p, i32, f32p, C.c_void_p, C.c_void_p, i32, f32p, f32p, C.c_void_p]),
         "fs_gather_energy": (C.c_int, [vp, i32, f32p, i32]),
         "fs_gather_energy_async": (C.c_int, [vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     }

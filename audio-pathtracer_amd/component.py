@@ -682,6 +682,59 @@ class Context:
                                                              mix.ctypes.data if want_mix else None, rows.ctypes.data))
         return self._callback_close(out, mix, rows)
 
+    # ---- ambisonic voices on the audio thread: the voice bank with a direction per voice, rendered into a soundfield ----
+    AMBISONIC_VOICE_DTYPE = BINAURAL_VOICE_DTYPE   # fs_ambisonic_voice is fs_binaural_voice
+    AMBISONIC_RENDER_ROW_DTYPE = np.dtype([("sounding", np.uint32), ("started", np.uint32), ("ended", np.uint32), ("dropped", np.uint32)])
+
+    @staticmethod
+    def ambisonic_encode(order, direction):
+        """fs_ambisonic_encode: the (order + 1)^2 channel gains of a direction in the head frame (x forward, y right, z up), ACN
+        order and SN3D normalisation, fp32 — the bits the renderer's plan pass computes on the device"""
+        d = np.ascontiguousarray(direction, dtype=np.float32).reshape(-1)
+        if d.shape[0] != 3:
+            raise ValueError("direction must hold three components")
+        out = np.zeros((min(max(int(order), 0), _capi.MAX_AMBISONIC_ORDER) + 1) ** 2, np.float32)
+        rc = _capi.load().fs_ambisonic_encode(int(order), d.ctypes.data, out.ctypes.data)
+        if rc != _capi.OK:
+            raise FrequenSeeError(rc, "fs_ambisonic_encode: order 0 .. 3, a finite direction whose squared length lies in 1e-30 .. 1e30")
+        return out
+
+    def ambisonic_render_init(self, src, frame_size=1024, taps=255, voices=32, max_delay_seconds=1.0, order=1):
+        self.check(self.lib.fs_ambisonic_render_init(self.h, src, int(frame_size), int(taps), int(voices), float(max_delay_seconds), int(order)))
+        self._ar_frame = getattr(self, "_ar_frame", {})
+        self._ar_order = getattr(self, "_ar_order", {})
+        self._ar_frame[src] = int(frame_size)
+        self._ar_order[src] = int(order)
+
+    def ambisonic_render_release(self, src):
+        self.check(self.lib.fs_ambisonic_render_release(self.h, src))
+
+    def ambisonic_render_process_batch(self, sources, blocks, voices, stride=None, want_out=True, want_mix=False):
+        """the ambisonic voices of several sources as one set of launches (include/frequensee.h
+        fs_ambisonic_render_process_batch): blocks [count][frame_size * 2]; voices one list per source, each an
+        AMBISONIC_VOICE_DTYPE array or (key, delay, band_gain, gain, direction) tuples; stride = the row length handed to the
+        library (default: the longest list, at least 1) -> (out [count][frame_size][C] (want_out), mix [frame_size][C]
+        (want_mix), rows [count] AMBISONIC_RENDER_ROW_DTYPE), C = (order + 1)^2 of the order the first source was initialised
+        with; what was not asked for is left out of the tuple"""
+        srcs, count, a, _, _ = self._callback_open(sources, blocks, getattr(self, "_ar_frame", {}), False, False)
+        order = max([getattr(self, "_ar_order", {}).get(int(s), 0) for s in srcs] + [0])   # (sources of unlike orders are refused)
+        frame, channels = a.shape[1] // 2, (order + 1) ** 2
+        out = np.empty((count, frame, channels), np.float32) if want_out else None
+        mix = np.empty((frame, channels), np.float32) if want_mix else None
+
+        def write(entry, voice):
+            key, delay, gains, gain, direction = voice
+            entry["gain"] = gain
+            entry["direction"] = direction
+            return key, delay, gains
+
+        table, counts, stride = self._voice_table(voices, count, stride, self.AMBISONIC_VOICE_DTYPE, write)
+        rows = np.zeros(count, dtype=self.AMBISONIC_RENDER_ROW_DTYPE)
+        self.check(self.lib.fs_ambisonic_render_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data, table.ctypes.data,
+                                                              counts.ctypes.data, stride, out.ctypes.data if want_out else None,
+                                                              mix.ctypes.data if want_mix else None, rows.ctypes.data))
+        return self._callback_close(out, mix, rows)
+
     # ---- row f2: reverb plugin convolution ----
     def reverb_init(self, src, frame_size=1024):
         self.check(self.lib.fs_reverb_init(self.h, src, frame_size))
@@ -1394,7 +1447,29 @@ class FrequenSeeAudioBinauralPlugin(FrequenSeeAudioReflectionPlugin):
             d = None if direct is None else (direct[0][i], np.asarray(c.GetComponentLocation(), np.float64) - np.asarray(direct[1], np.float64))
             voices.append(self.Voices(rows[i], paths[i], forward, right, reference_length, d, pick(diffraction, i), pick(second, i),
                                       pick(diffraction2, i), pick(mixed, i)))
+        return self._render(components, buffers, voices, want_out, want_mix)
+
+    def _render(self, components, buffers, voices, want_out, want_mix):
         return self.ctx.binaural_render_process_batch([c._src for c in components], buffers, voices, want_out=want_out, want_mix=want_mix)
+
+
+class FrequenSeeAudioAmbisonicPlugin(FrequenSeeAudioBinauralPlugin):
+    """Not in the reference: the binaural plugin's voices — the same entries, Voices() unchanged — rendered into an ambisonic bus
+    of (Order + 1)^2 channels, ACN order and SN3D normalisation (fs_ambisonic_render_process_batch), instead of two ears: for
+    loudspeakers, for an engine's soundfield submix, for a host's own binaural decoder.  No HRIR set is needed.  Rotation (the bus
+    is rendered in the head frame given to Voices(); a head tracker may rotate it later) and decoding are the host's."""
+
+    Order = 1
+
+    def OnInitSource(self, component: FrequenSeeAudioComponent):
+        self.ctx.ambisonic_render_init(component._src, self.FrameSize, self.Taps, self.VoiceCount, self.MaxDelaySeconds, self.Order)
+
+    def OnReleaseSource(self, component: FrequenSeeAudioComponent):
+        self.ctx.ambisonic_render_release(component._src)
+
+    def _render(self, components, buffers, voices, want_out, want_mix):
+        """ProcessAudio is the binaural plugin's; returns what Context.ambisonic_render_process_batch does"""
+        return self.ctx.ambisonic_render_process_batch([c._src for c in components], buffers, voices, want_out=want_out, want_mix=want_mix)
 
 
 class MaterialAcousticProcessor:

@@ -138,7 +138,7 @@ void launch_binaural_render(const BinauralRenderBatch& b, hipStream_t s) {
     const int tiles = (b.frame + kRenderTile - 1) / kRenderTile;
     hipLaunchKernelGGL(binaural_render_kernel, dim3(tiles, 2, b.count), dim3(kRenderTile), 0, s, b.items, b.plans, b.folded, b.n0, b.in,
                        b.out, b.frame, b.tc);
-    if (b.mix) launch_callback_mix(b.out, b.count, b.frame, b.mix, s);
+    if (b.mix) launch_callback_mix(b.out, b.count, 2 * b.frame, b.mix, s);
 }
 
 }  // namespace fs

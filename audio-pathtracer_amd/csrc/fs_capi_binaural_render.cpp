@@ -133,19 +133,19 @@ int fs_binaural_render_init(fs_context* ctx, fs_source h, int32_t frame_size, in
                             "fs_binaural_render_init: frame size outside 16 .. 16384, taps even or outside 1 .. 2047, voices outside 1 .. 32, or a bad max delay",
                             "fs_binaural_render_init: taps + the set's taps - 1 exceed 2047",
                             "fs_binaural_render_init: max delay + folded taps + 1 + frame size exceed 1 048 576 samples"},
-                           frame_size, taps, voices, max_delay_seconds);
+                           frame_size, taps, voices, max_delay_seconds, kVoiceBankHeader, 2);
 }
 
 int fs_binaural_render_release(fs_context* ctx, fs_source h) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
-    return voice_bank_release(ctx, h, &Source::br);
+    return voice_bank_release(ctx, h, &Source::br, kVoiceBankHeader, 2);
 }
 
 int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in,
                                      const fs_binaural_voice* voices, const int32_t* voice_counts, int32_t stride, float* out,
                                      float* mix, fs_binaural_render_row* rows) {
     static const VoiceBankRenderer<BinauralRenderBatch> q = {&Source::br, &fs_context::br_stage, "fs_binaural_render_init has not been called for this source",
-                                                             "fs_binaural_render_process_batch: no HRIR set in force (fs_hrtf_set)", launch_binaural_render};
+                                                             "fs_binaural_render_process_batch: no HRIR set in force (fs_hrtf_set)", launch_binaural_render, kVoiceBankHeader};
     const int H = ctx ? ctx->hrtf_taps : 0;
     return voice_bank_process(
         q, ctx, sources, count, in, voices, voice_counts, stride, out, mix, rows,
@@ -165,7 +165,7 @@ int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, 
         // the sounding slots' list | the folded tables (sized by the rows' slots, not by how many sound in this call: a shape
         // allocates once)
         [&](size_t slots, const RenderSetup& shape) {
-            return std::array<size_t, 2>{sizeof(uint16_t) * slots, sizeof(float2) * slots * 2 * (size_t)(shape.taps + H - 1)};
+            return std::array<size_t, 3>{sizeof(uint16_t) * slots, sizeof(float2) * slots * 2 * (size_t)(shape.taps + H - 1), 2 * (size_t)shape.frame};
         },
         [&](BinauralRenderBatch& b, BinauralRenderItem* items, char* h_sounding, char* d_sounding, char* d_folded) {
             uint16_t* sounding = (uint16_t*)h_sounding;

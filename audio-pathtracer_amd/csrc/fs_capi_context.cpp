@@ -164,7 +164,7 @@ void free_source(fs_context* ctx, Source* s) {
         if (s->d_ring) (void)hipFree(s->d_ring);
         if (s->d_fade_from) (void)hipFree(s->d_fade_from);
         if (s->d_fade_to) (void)hipFree(s->d_fade_to);
-        for (RenderSetup* r : {&s->dr, &s->rr.r, &s->br.r}) if (r->d) (void)hipFree(r->d);
+        for (RenderSetup* r : {&s->dr, &s->rr.r, &s->br.r, &s->ar.r}) if (r->d) (void)hipFree(r->d);
         if (s->d_dir) (void)hipFree(s->d_dir);   // (the callers have synchronised the compute stream)
     }
     delete s;
@@ -659,7 +659,7 @@ int fs_context_destroy(fs_context* ctx) {
         for (float2* w : ctx->d_rev_tw) if (w) (void)hipFree(w);
         for (PathStaging* st : {&ctx->direct_stage, &ctx->reflect_stage, &ctx->diffract_stage, &ctx->reflect2_stage, &ctx->diffract2_stage, &ctx->mixed_stage}) st->release();
         if (ctx->d_direct_off) (void)hipFree(ctx->d_direct_off);
-        for (CallbackStage* st : {&ctx->rev_stage, &ctx->dr_stage, &ctx->rr_stage, &ctx->br_stage}) st->release();
+        for (CallbackStage* st : {&ctx->rev_stage, &ctx->dr_stage, &ctx->rr_stage, &ctx->br_stage, &ctx->ar_stage}) st->release();
         if (ctx->d_hrtf) (void)hipFree(ctx->d_hrtf);
         for (const auto& t : ctx->dr_tables) if (t.d) (void)hipFree(t.d);
         if (ctx->d_batch) (void)hipFree(ctx->d_batch);

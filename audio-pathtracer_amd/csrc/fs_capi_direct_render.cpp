@@ -69,7 +69,7 @@ int direct_render_table_for(fs_context* ctx, int taps, const float** out) {
     return FS_OK;
 }
 
-int render_setup(fs_context* ctx, RenderSetup& r, size_t header, int frame, int taps, double d_max, double need) {
+int render_setup(fs_context* ctx, RenderSetup& r, size_t header, int rings, int frame, int taps, double d_max, double need) {
     unsigned ring = 1;
     while ((double)ring < need) ring <<= 1;
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
@@ -79,16 +79,16 @@ int render_setup(fs_context* ctx, RenderSetup& r, size_t header, int frame, int 
     FS_HIP(ctx, hipStreamSynchronize(ctx->rev_stream));
     if (r.d) (void)hipFree(r.d);
     r = RenderSetup{nullptr, frame, taps, (int)d_max, ring, table};
-    const size_t bytes = header + sizeof(float) * 2 * (size_t)ring;
+    const size_t bytes = header + sizeof(float) * (size_t)rings * (size_t)ring;
     FS_HIP(ctx, hipMalloc((void**)&r.d, bytes));
     FS_HIP(ctx, hipMemsetAsync(r.d, 0, bytes, ctx->rev_stream));
     return FS_OK;
 }
 
-int render_clear(fs_context* ctx, const RenderSetup& r, size_t header) {
+int render_clear(fs_context* ctx, const RenderSetup& r, size_t header, int rings) {
     if (r.d && ctx->device_ok) {
         FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
-        FS_HIP(ctx, hipMemsetAsync(r.d, 0, header + sizeof(float) * 2 * (size_t)r.ring, ctx->rev_stream));
+        FS_HIP(ctx, hipMemsetAsync(r.d, 0, header + sizeof(float) * (size_t)rings * (size_t)r.ring, ctx->rev_stream));
     }
     return FS_OK;
 }
@@ -136,14 +136,14 @@ int fs_direct_render_init(fs_context* ctx, fs_source h, int32_t frame_size, int3
     const double need = d_max + (double)taps + 1.0 + (double)frame_size;
     if (need > 1048576.0)
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_direct_render_init: max delay + taps + 1 + frame size exceed 1 048 576 samples");
-    return render_setup(ctx, s->dr, kDirectRenderHeader, frame_size, taps, d_max, need);
+    return render_setup(ctx, s->dr, kDirectRenderHeader, 2, frame_size, taps, d_max, need);
 }
 
 int fs_direct_render_release(fs_context* ctx, fs_source h) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     Source* s = get_source(ctx, h);
     if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-    return render_clear(ctx, s->dr, kDirectRenderHeader);   // history := 0, not primed
+    return render_clear(ctx, s->dr, kDirectRenderHeader, 2);   // history := 0, not primed
 }
 
 int fs_direct_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in,
@@ -165,7 +165,7 @@ int fs_direct_render_process_batch(fs_context* ctx, const fs_source* sources, in
     { const int rc = render_no_duplicates(ctx, srcs); if (rc) return rc; }
     const int frame = srcs[0]->dr.frame;
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    const CallbackLayout l = callback_layout(count, frame, {sizeof(DirectRenderItem) * (size_t)count}, {sizeof(DirectRenderPlan) * (size_t)count});
+    const CallbackLayout l = callback_layout(count, frame, 2 * (size_t)frame, {sizeof(DirectRenderItem) * (size_t)count}, {sizeof(DirectRenderPlan) * (size_t)count});
     { const int rc = ctx->dr_stage.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
     char* hs = ctx->dr_stage.h; char* ds = ctx->dr_stage.d;
     DirectRenderItem* items = (DirectRenderItem*)(hs + l.up[0]);
@@ -180,7 +180,7 @@ int fs_direct_render_process_batch(fs_context* ctx, const fs_source* sources, in
         it.d1 = targets[i].delay * fs_f;
         for (int b = 0; b < B; ++b) it.g1[b] = targets[i].band_gain[b];
     }
-    std::memcpy(hs + l.in, in, l.rows);
+    std::memcpy(hs + l.in, in, l.in_rows);
     FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, ctx->rev_stream));
     DirectRenderBatch b{};
     b.items = (const DirectRenderItem*)(ds + l.up[0]);

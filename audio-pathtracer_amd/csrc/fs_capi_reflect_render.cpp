@@ -1,7 +1,7 @@
 // fs_capi_reflect_render.cpp — the early reflections on the audio thread, and the host side of the voice bank they and the
 // binaural voices (fs_capi_binaural_render.cpp) are built on: the matching of a row's entries to the slots (voice_match), the
-// per-source set-up and its release (voice_bank_init / _release, behind fs_reflection_render_init / _release and
-// fs_binaural_render_init / _release).  The callback of all sources, fs_reflection_render_process_batch, is
+// per-source set-up and its release (voice_bank_init / _release, behind fs_reflection_render_init / _release,
+// fs_binaural_render_init / _release and fs_ambisonic_render_init / _release).  The callback of all sources, fs_reflection_render_process_batch, is
 // fs_capi_voice_bank.hpp's voice_bank_process with the channel gains as an entry's own fields and fs_reflect_render.hip's
 // launches.  The band kernels and their per-context cache are the direct renderer's (fs_capi_direct_render.cpp).  The reference
 // has no slot for it.
@@ -48,7 +48,7 @@ VoiceMatch voice_match(const VoiceBank& bank, const void* voices, size_t voice_b
 }
 
 int voice_bank_init(fs_context* ctx, fs_source h, VoiceBank Source::*which, int fold_taps, const VoiceBankInitTexts& t, int32_t frame_size,
-                    int32_t taps, int32_t voices, float max_delay_seconds) {
+                    int32_t taps, int32_t voices, float max_delay_seconds, size_t header, int rings) {
     if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
     Source* s = get_source(ctx, h);
     if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
@@ -62,17 +62,17 @@ int voice_bank_init(fs_context* ctx, fs_source h, VoiceBank Source::*which, int 
     const double need = d_max + (double)tc + 1.0 + (double)frame_size;
     if (need > 1048576.0) return ctx->fail(FS_ERR_INVALID_ARGUMENT, t.ring);
     VoiceBank& bank = s->*which;
-    const int rc = render_setup(ctx, bank.r, kVoiceBankHeader, frame_size, taps, d_max, need);
+    const int rc = render_setup(ctx, bank.r, header, rings, frame_size, taps, d_max, need);
     if (rc) return rc;   // (without a set-up, or with the old one untouched)
     bank.voices = voices;
     bank.free_slots();
     return FS_OK;
 }
 
-int voice_bank_release(fs_context* ctx, fs_source h, VoiceBank Source::*which) {
+int voice_bank_release(fs_context* ctx, fs_source h, VoiceBank Source::*which, size_t header, int rings) {
     Source* s = get_source(ctx, h);
     if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-    const int rc = render_clear(ctx, (s->*which).r, kVoiceBankHeader);   // history := 0 ...
+    const int rc = render_clear(ctx, (s->*which).r, header, rings);   // history := 0 ...
     if (rc == FS_OK) (s->*which).free_slots();                            // ... every slot free
     return rc;
 }
@@ -87,19 +87,19 @@ int fs_reflection_render_init(fs_context* ctx, fs_source h, int32_t frame_size, 
     return voice_bank_init(ctx, h, &Source::rr, 0,
                            {nullptr, "fs_reflection_render_init: frame size outside 16 .. 16384, taps even or outside 1 .. 2047, voices outside 1 .. 32, or a bad max delay",
                             nullptr, "fs_reflection_render_init: max delay + taps + 1 + frame size exceed 1 048 576 samples"},
-                           frame_size, taps, voices, max_delay_seconds);
+                           frame_size, taps, voices, max_delay_seconds, kVoiceBankHeader, 2);
 }
 
 int fs_reflection_render_release(fs_context* ctx, fs_source h) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
-    return voice_bank_release(ctx, h, &Source::rr);
+    return voice_bank_release(ctx, h, &Source::rr, kVoiceBankHeader, 2);
 }
 
 int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in,
                                        const fs_reflection_voice* voices, const int32_t* voice_counts, int32_t stride, float* out,
                                        float* mix, fs_reflection_render_row* rows) {
     static const VoiceBankRenderer<ReflectRenderBatch> q = {&Source::rr, &fs_context::rr_stage, "fs_reflection_render_init has not been called for this source",
-                                                            nullptr, launch_reflect_render};
+                                                            nullptr, launch_reflect_render, kVoiceBankHeader};
     return voice_bank_process(
         q, ctx, sources, count, in, voices, voice_counts, stride, out, mix, rows,
         [&](const fs_reflection_voice& v) {
@@ -107,7 +107,7 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
                 return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a voice's channel gain is not finite");
             return (int)FS_OK;
         },
-        [](const VoiceBank&) { return (int)FS_OK; }, [](size_t, const RenderSetup&) { return std::array<size_t, 2>{0, 0}; },
+        [](const VoiceBank&) { return (int)FS_OK; }, [](size_t, const RenderSetup& shape) { return std::array<size_t, 3>{0, 0, 2 * (size_t)shape.frame}; },
         [](ReflectRenderBatch&, ReflectRenderItem*, char*, char*, char*) {});
 }
 

@@ -121,7 +121,7 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
     hipStream_t rs = ctx->rev_stream;
     bool ears = false;
     for (int32_t i = 0; i < count; ++i) ears = ears || (srcs[i]->rev_ears && (!apply_reverb || apply_reverb[i]));
-    const CallbackLayout l = callback_layout(count, frame, {sizeof(ReverbItem) * (size_t)count, sizeof(ReverbPartItem) * (size_t)count, sizeof(int) * 6 * (size_t)count,
+    const CallbackLayout l = callback_layout(count, frame, 2 * (size_t)frame, {sizeof(ReverbItem) * (size_t)count, sizeof(ReverbPartItem) * (size_t)count, sizeof(int) * 6 * (size_t)count,
                                                             ears ? sizeof(int) * 3 * (size_t)count : 0},
                                              {sizeof(float) * row * (size_t)count});
     { const int rc = ctx->rev_stage.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
@@ -249,16 +249,18 @@ void CallbackStage::release() {
 
 namespace fsi {
 
-CallbackLayout callback_layout(int count, int frame, std::initializer_list<size_t> up_blocks, std::initializer_list<size_t> scratch_blocks) {
+CallbackLayout callback_layout(int count, int frame, size_t out_row, std::initializer_list<size_t> up_blocks,
+                               std::initializer_list<size_t> scratch_blocks) {
     auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
     CallbackLayout l;
-    l.row = sizeof(float) * 2 * (size_t)frame;
+    l.in_rows = sizeof(float) * 2 * (size_t)frame * (size_t)count;
+    l.row = sizeof(float) * out_row;
     l.rows = l.row * (size_t)count;
     int k = 0;
     for (size_t bytes : up_blocks) { l.up[k++] = l.in; l.in += align(bytes); }
-    l.up_bytes = l.in + l.rows;
+    l.up_bytes = l.in + l.in_rows;
     l.h_out = align(l.up_bytes);
-    l.h_mix = l.h_out + l.rows;   // (adjacent to out: rows is a multiple of 8 bytes)
+    l.h_mix = l.h_out + l.rows;   // (adjacent to out: rows is a multiple of 4 bytes)
     l.host_bytes = l.h_mix + l.row;
     l.d_out = align(l.up_bytes);
     k = 0;

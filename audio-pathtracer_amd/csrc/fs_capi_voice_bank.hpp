@@ -1,5 +1,5 @@
 // fs_capi_voice_bank.hpp — the callback of a renderer whose sources hold a voice bank (fs_reflection_render_process_batch,
-// fs_binaural_render_process_batch), from its arguments to the caller's arrays: everything validated, the voices matched to the
+// fs_binaural_render_process_batch, fs_ambisonic_render_process_batch), from its arguments to the caller's arrays: everything validated, the voices matched to the
 // slots on the host's copy of the slot table (voice_match), one copy up, the renderer's launches, one copy back, one wait.  What a
 // renderer is beyond that arrives as a descriptor and four callables.  Host code only; the bank's other half — the matching, the
 // inits and the releases — is fs_capi_reflect_render.cpp's, the device's fs_dev_render.hpp's.
@@ -12,21 +12,24 @@
 
 namespace fsi {
 
-// What one of the two renderers is, beyond its kernels: its bank on a source, its staging, its messages (no_set: the refusal
-// while no HRIR set is in force; nullptr: it needs none) and its launches.
+// What one of the three renderers is, beyond its kernels: its bank on a source, its staging, its messages (no_set: the refusal
+// while no HRIR set is in force; nullptr: it needs none), its launches and the bytes of its bank's header, behind which the
+// history begins.
 template <typename Batch>
 struct VoiceBankRenderer {
     VoiceBank Source::*bank;
     CallbackStage fs_context::*stage;
     const char *no_setup, *no_set;
     void (*launch)(const Batch&, hipStream_t);
+    size_t header;
 };
 
 // A voice-bank callback, every check in the order the header gives.
 //   entry_ok(v)      an entry's own fields, behind its key, delay and band gains: FS_OK, or the failure reported
 //   row_ok(bank)     a row's own check, between its first checks (render_row) and its voice count: likewise
-//   extra(slots, shape)   {up, scratch}: the bytes of the renderer's own upload and scratch block (CallbackLayout::up[kOwn] and
-//                    ::scratch[kOwn]; 0: none), slots = the sum of the rows' slot counts, shape = the set-up the rows share
+//   extra(slots, shape)   {up, scratch, row}: the bytes of the renderer's own upload and scratch block (CallbackLayout::up[kOwn]
+//                    and ::scratch[kOwn]; 0: none) and the floats of an output row, slots = the sum of the rows' slot counts,
+//                    shape = the set-up the rows share
 //   fill(b, items, h_up, d_up, d_scratch)   what the launches read beyond the bank's part of b, and what goes up in the renderer's
 //                    own block: called with the items filled (items: the host's) and before the copy up; the three pointers
 //                    are the own blocks — the upload's two sides and the scratch
@@ -72,8 +75,8 @@ int voice_bank_process(const VoiceBankRenderer<Batch>& q, fs_context* ctx, const
     hipStream_t rs = ctx->rev_stream;
     enum { kItems, kVoices, kOwn, kN0 = 0, kPlans };   // CallbackLayout::up and ::scratch (kOwn: of both)
     const size_t voices_bytes = sizeof(Voice) * (size_t)count * (size_t)stride;
-    const std::array<size_t, 2> own = extra(slots_total, shape);
-    const CallbackLayout l = callback_layout(count, shape.frame, {sizeof(Item) * (size_t)count, voices_bytes, own[0]},
+    const std::array<size_t, 3> own = extra(slots_total, shape);
+    const CallbackLayout l = callback_layout(count, shape.frame, own[2], {sizeof(Item) * (size_t)count, voices_bytes, own[0]},
                                              {sizeof(unsigned) * (size_t)count, sizeof(Plan) * (size_t)count * kVoiceSlots, own[1]});
     CallbackStage& st = ctx->*q.stage;
     { const int rc = st.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
@@ -86,14 +89,14 @@ int voice_bank_process(const VoiceBankRenderer<Batch>& q, fs_context* ctx, const
         Item& it = items[i];
         std::memset(&it, 0, sizeof(it));
         it.state = (decltype(it.state))bank.r.d;
-        it.ring = (float*)(bank.r.d + kVoiceBankHeader);
+        it.ring = (float*)(bank.r.d + q.header);
         it.table = bank.r.table;
         it.mask = bank.r.ring - 1u;
         it.slots = bank.voices;
         std::memcpy(it.op, m.op, sizeof(it.op));
     }
     std::memcpy(hs + l.up[kVoices], voices, voices_bytes);
-    std::memcpy(hs + l.in, in, l.rows);
+    std::memcpy(hs + l.in, in, l.in_rows);
     Batch b{};
     b.items = (const Item*)(ds + l.up[kItems]);
     b.voices = (const Voice*)(ds + l.up[kVoices]);

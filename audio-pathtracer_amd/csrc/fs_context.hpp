@@ -82,12 +82,14 @@ struct RenderSetup {
     unsigned ring = 0;
     const float* table = nullptr;
 };
-// A renderer's voice bank on a source (fs_reflection_render_init / fs_binaural_render_init): the set-up — its header is a
-// VoiceBankState, kVoiceBankHeader bytes; the rings are shared by the `voices` slots — and the slot table the callback matches
-// against, the host's copy (the device's is in the state block)
+// A renderer's voice bank on a source (fs_reflection_render_init / fs_binaural_render_init / fs_ambisonic_render_init): the
+// set-up — its header is a VoiceBankState, kVoiceBankHeader bytes (the ambisonic renderer's: kAmbisonicBankHeader); the rings
+// (two; the ambisonic renderer's: one) are shared by the `voices` slots — and the slot table the callback matches against, the
+// host's copy (the device's is in the state block)
 struct VoiceBank {
     RenderSetup r;
     int voices = 0;
+    int order = 0;   // (the ambisonic renderer's: what fs_ambisonic_render_init was given)
     bool held[FS_MAX_REFLECTION_VOICES] = {};
     uint32_t key[FS_MAX_REFLECTION_VOICES] = {};
     void free_slots() {
@@ -194,9 +196,10 @@ struct Source {
     bool fading = false, fade_primed = false;
     uint64_t fade_gen = 0;
     // direct sound (header: DirectRenderState, kDirectRenderHeader bytes), and the voice banks of the early reflections and of the
-    // binaural voices.  br.r.taps = T; its rings were sized for T + H - 1 taps of the set in force at fs_binaural_render_init
+    // binaural voices.  br.r.taps = T; its rings were sized for T + H - 1 taps of the set in force at fs_binaural_render_init.
+    // ar: the ambisonic voices' bank, with one ring and 128-byte slots (kAmbisonicBankHeader)
     RenderSetup dr;
-    VoiceBank rr, br;
+    VoiceBank rr, br, ar;
     float occlusion = 1.0f;            // OcclusionAttenuation FSAC.h:130 (1.f until the first UpdateSound)
 };
 // The per-frame fields of a source switched to those of an EARLIER frame (energy buffer `cur`) for a scope: what a held frame or
@@ -312,13 +315,14 @@ struct CallbackStage {
 };
 // Where a callback of `count` rows of `frame` samples keeps what in its staging pair, every block 256-byte aligned.  What goes up in
 // one copy has the same offsets on both sides: the call's own blocks (up[k], in the order given), then in [count][2 frame].  Behind
-// it the host holds what comes back, out [count][2 frame] | mix [2 frame]; the device holds the call's scratch blocks (scratch[k]),
-// then out | mix, adjacent as on the host: one copy back.
+// it the host holds what comes back, out [count][row] | mix [row], row = the floats of an output row (2 frame; the ambisonic
+// bus: C frame); the device holds the call's scratch blocks (scratch[k]), then out | mix, adjacent as on the host: one copy back.
 struct CallbackLayout {
     size_t up[4] = {}, in = 0, up_bytes = 0;
     size_t h_out = 0, h_mix = 0, host_bytes = 0;
     size_t scratch[3] = {}, d_out = 0, d_mix = 0, dev_bytes = 0;
-    size_t rows = 0, row = 0;   // the bytes of in and of out, and of mix
+    size_t in_rows = 0;         // the bytes of in
+    size_t rows = 0, row = 0;   // the bytes of out, and of mix
 };
 
 struct fs_context {
@@ -400,7 +404,8 @@ struct fs_context {
     //   the plans [count][FS_MAX_REFLECTION_VOICES]
     // br_stage (fs_binaural_render_process_batch): up, items [count] | voices [count][stride] | the sounding slots' list; scratch,
     //   the counters [count] | the plans [count][FS_MAX_REFLECTION_VOICES] | the folded tables [sum of the rows' V][2][Tc]
-    CallbackStage rev_stage, dr_stage, rr_stage, br_stage;
+    // ar_stage (fs_ambisonic_render_process_batch): rr_stage's blocks, with plans of 256 bytes and out [count][C frame] | mix [C frame]
+    CallbackStage rev_stage, dr_stage, rr_stage, br_stage, ar_stage;
     // the HRIR set in force (fs_hrtf_set; the audio thread's): one device block, dirs [n][3] | hrir [n][2][H]; n == 0: none
     float* d_hrtf = nullptr;
     int hrtf_dirs = 0, hrtf_taps = 0;
@@ -626,8 +631,10 @@ constexpr float kMaxUnboundedRr = 0.95f;   // depth = 0 (uncapped walks): the st
 namespace fsi {
 
 // ---- fs_capi_reverb.cpp: what the three audio callbacks share ------------------------------------------------------
-// the layout of a call: up_blocks / scratch_blocks = the bytes of its own blocks (CallbackLayout::up / scratch), in order
-CallbackLayout callback_layout(int count, int frame, std::initializer_list<size_t> up_blocks, std::initializer_list<size_t> scratch_blocks);
+// the layout of a call: out_row = the floats of an output row; up_blocks / scratch_blocks = the bytes of its own blocks
+// (CallbackLayout::up / scratch), in order
+CallbackLayout callback_layout(int count, int frame, size_t out_row, std::initializer_list<size_t> up_blocks,
+                               std::initializer_list<size_t> scratch_blocks);
 // The tail of a callback whose launches are enqueued on the reverb stream: the copy back (out | mix in one when both are wanted,
 // else mix alone), the wait, mix copied out.  The rows of out are then in st.h + l.h_out: the caller's to copy.
 int callback_finish(fs_context* ctx, const CallbackStage& st, const CallbackLayout& l, bool want_out, float* mix);
@@ -635,9 +642,9 @@ int callback_finish(fs_context* ctx, const CallbackStage& st, const CallbackLayo
 bool direct_render_taps_ok(int32_t taps);
 // What both inits do once the arguments are found good (need = d_max + taps + 1 + frame samples, the ring's least size): the
 // table of (taps, edges in force), the wait for the callbacks' stream, the old state block freed, a zeroed new one of
-// header bytes + the rings.  A failure before the wait changes nothing; one after it leaves the source without a set-up.
-int render_setup(fs_context* ctx, RenderSetup& r, size_t header, int frame, int taps, double d_max, double need);
-int render_clear(fs_context* ctx, const RenderSetup& r, size_t header);   // the releases: history := 0 (enqueued), where there is a set-up
+// header bytes + the `rings` rings.  A failure before the wait changes nothing; one after it leaves the source without a set-up.
+int render_setup(fs_context* ctx, RenderSetup& r, size_t header, int rings, int frame, int taps, double d_max, double need);
+int render_clear(fs_context* ctx, const RenderSetup& r, size_t header, int rings);   // the releases: history := 0 (enqueued), where there is a set-up
 // a row's first checks, in this order: the handle, the set-up (which(source): the one of the source's three that the callback
 // renders with; no_setup: the message), the batch's one shape (first: row 0's source, nullptr in row 0).  *rc = FS_OK and the
 // source, or the failure reported and nullptr.
@@ -667,13 +674,14 @@ struct VoiceMatch {
 // rule 1 of the reflection renderer on a source's slot table: `voices` = the row's n entries, voice_bytes apart, each beginning
 // with its key
 VoiceMatch voice_match(const VoiceBank& bank, const void* voices, size_t voice_bytes, int n);
-// What fs_reflection_render_init and fs_binaural_render_init do with their arguments: `which` = the source's bank; fold_taps = the
-// taps a voice's filter grows by (H - 1 of the set in force; 0: the reflection renderer's), a negative one = no set in force;
-// the texts are the entry point's own refusals: no set, the arguments' ranges, too many folded taps, too long a history.
+// What fs_reflection_render_init, fs_binaural_render_init and fs_ambisonic_render_init do with their arguments: `which` = the
+// source's bank; fold_taps = the taps a voice's filter grows by (H - 1 of the set in force; 0: none), a negative one = no set in
+// force; the texts are the entry point's own refusals: no set, the arguments' ranges, too many folded taps, too long a history;
+// header, rings = the bytes of the bank's header and the number of history rings behind it.
 struct VoiceBankInitTexts { const char *no_set, *ranges, *folded, *ring; };
 int voice_bank_init(fs_context* ctx, fs_source h, VoiceBank Source::*which, int fold_taps, const VoiceBankInitTexts& t, int32_t frame_size,
-                    int32_t taps, int32_t voices, float max_delay_seconds);
-int voice_bank_release(fs_context* ctx, fs_source h, VoiceBank Source::*which);   // history := 0, every slot free
+                    int32_t taps, int32_t voices, float max_delay_seconds, size_t header, int rings);
+int voice_bank_release(fs_context* ctx, fs_source h, VoiceBank Source::*which, size_t header, int rings);   // history := 0, every slot free
 // ---- fs_capi_context.cpp ------------------------------------------------------------------------------------------
 Source* get_source(fs_context* ctx, fs_source h);
 hipError_t wait_energy_readers(fs_context* ctx, Source* s);            // before the compute stream writes the current energy buffer

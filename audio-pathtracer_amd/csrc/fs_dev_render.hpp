@@ -1,10 +1,10 @@
-// fs_dev_render.hpp — what the three render kernels of the audio thread (fs_direct_render.hip, fs_reflect_render.hip,
-// fs_binaural_render.hip) share on the device: one voice's block — a time-varying fractional delay and a linear-phase FIR whose
+// fs_dev_render.hpp — what the four render kernels of the audio thread (fs_direct_render.hip, fs_reflect_render.hip,
+// fs_binaural_render.hip, fs_ambisonic_render.hip) share on the device: one voice's block — a time-varying fractional delay and a linear-phase FIR whose
 // taps ramp from sum_b g0_b k_b to sum_b g1_b k_b — as pieces a kernel puts together: the delay of an output sample and its slew
 // clamp, the tap table and the tile's read window in LDS, the tap loop of one output sample, the output store with the ring append.
-// Behind them the voice bank, which the reflection and the binaural renderer are: the plan pass and the render pass of a callback
-// whose rows hold a table of voices, with what a renderer's voices carry beyond a delay and band gains, and where their taps
-// come from, handed in.
+// Behind them the voice bank, which the reflection, the binaural and the ambisonic renderer are: the plan pass and the render pass
+// of a callback whose rows hold a table of voices, with what a renderer's voices carry beyond a delay and band gains, and where
+// their taps come from, handed in (the ambisonic renderer has a render pass of its own: one voice evaluation for all channels).
 // The rule is
 // include/frequensee.h's, to the bit: every fp32 operation stands where the header puts it (the files are built with
 // -ffp-contract=off and the tests compare bits).  No piece of a voice's block holds a barrier or a return: each says which barrier
@@ -59,12 +59,25 @@ __device__ __forceinline__ void render_build_taps(RenderTaps& s_cd, const float*
     }
 }
 
-// The read window of the tile's outputs [s_a, s_b] of channel ch into s_win, from the ring (samples before n0) and the
-// block (from n0 on; past the block's end: 0).  Returns i_hi, the largest whole delay of the tile, which places a sample's taps
+// What a ring holds of a row's interleaved stereo block `in`, as sample rel of the block: one of its channels (the direct, the
+// reflection and the binaural renderer: a ring per channel), or the downmix of a mono source (the ambisonic renderer: one ring)
+struct RenderChannel {
+    const float* __restrict__ in;
+    int ch;
+    __device__ __forceinline__ float operator()(int rel) const { return in[2 * rel + ch]; }
+};
+struct RenderDownmix {
+    const float* __restrict__ in;
+    __device__ __forceinline__ float operator()(int rel) const { return 0.5f * (in[2 * rel] + in[2 * rel + 1]); }
+};
+
+// The read window of the tile's outputs [s_a, s_b] into s_win, from the ring (samples before n0) and the block (from n0 on, read
+// through x_in; past the block's end: 0).  Returns i_hi, the largest whole delay of the tile, which places a sample's taps
 // in the window (render_sample).  The same barriers as render_build_taps.
-__device__ __forceinline__ int render_stage_window(RenderWindow& s_win, const float* __restrict__ ring, unsigned mask,
-                                                   const float* __restrict__ in, int ch, unsigned n0, float d0, float e, int s_a, int s_b, int frame,
-                                                   float frame_f, int taps, int tid) {
+template <typename In>
+__device__ __forceinline__ int render_stage_window(RenderWindow& s_win, const float* __restrict__ ring, unsigned mask, const In& x_in,
+                                                   unsigned n0, float d0, float e, int s_a, int s_b, int frame, float frame_f, int taps,
+                                                   int tid) {
     // d is monotone in s (every rounding is), so the tile's whole delays lie between those of its first and last output
     float a_unused;
     const int i_a = (int)floorf(render_delay(d0, e, s_a, frame_f, &a_unused));
@@ -77,10 +90,16 @@ __device__ __forceinline__ int render_stage_window(RenderWindow& s_win, const fl
         const int rel = (int)(p - n0);   // >= 0: a sample of this block
         float v = 0.0f;
         if (rel < 0) v = ring[p & mask];
-        else if (rel < frame) v = in[2 * rel + ch];
+        else if (rel < frame) v = x_in(rel);
         s_win[j] = v;
     }
     return i_hi;
+}
+// ... of channel ch of the block
+__device__ __forceinline__ int render_stage_window(RenderWindow& s_win, const float* __restrict__ ring, unsigned mask,
+                                                   const float* __restrict__ in, int ch, unsigned n0, float d0, float e, int s_a, int s_b, int frame,
+                                                   float frame_f, int taps, int tid) {
+    return render_stage_window(s_win, ring, mask, RenderChannel{in, ch}, n0, d0, e, s_a, s_b, frame, frame_f, taps, tid);
 }
 
 // Output sample s < frame of the voice whose taps and window the LDS holds: the four-accumulator tap loop, (acc0 + acc1) +
@@ -131,12 +150,18 @@ __device__ __forceinline__ float render_sample(const RenderTaps& s_cd, const Ren
     return (acc0 + acc1) + (acc2 + acc3);
 }
 
-// Output sample s < frame of row r: y into out, the input sample into the ring.  A callback reads ring positions [n0 - D - T, n0)
-// and writes [n0, n0 + F), disjoint modulo the ring because it holds D + T + 1 + F or more: no barrier.
+// Sample s < frame of the block, read through x_in, into the ring.  A callback reads ring positions [n0 - D - T, n0) and writes
+// [n0, n0 + F), disjoint modulo the ring because it holds D + T + 1 + F or more: no barrier.
+template <typename In>
+__device__ __forceinline__ void render_append(float* __restrict__ ring, unsigned mask, const In& x_in, unsigned n0, int s) {
+    ring[(n0 + (unsigned)s) & mask] = x_in(s);
+}
+
+// Output sample s < frame of row r: y into out, the input sample of channel ch into the ring.
 __device__ __forceinline__ void render_store(float* __restrict__ out_all, float* __restrict__ ring, unsigned mask,
                                              const float* __restrict__ in, int r, int ch, unsigned n0, int s, int frame, float y) {
     out_all[(size_t)r * 2 * (size_t)frame + 2 * (size_t)s + ch] = y;
-    ring[(n0 + (unsigned)s) & mask] = in[2 * s + ch];
+    render_append(ring, mask, RenderChannel{in, ch}, n0, s);
 }
 
 // {c0[t], dc[t]} of a voice whose taps an earlier launch left in global memory (fs_binaural_render.hip: the band FIR with an

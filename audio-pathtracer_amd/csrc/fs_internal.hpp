@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -678,9 +679,9 @@ void launch_reverb_batch_fade_start(const ReverbItem* items, const int* take, in
 // prepare (+ push, where the ring allows), the convolutions of the two lists (each launched only when it has rows), the push
 // (where it could not ride in front), the partitioned engine's rows (launch_reverb_part, when b.pitems), the mix (when b.mix)
 void launch_reverb_batch(const ReverbBatch& b, hipStream_t s);
-// the mix of the three audio callbacks (the reverb's, the direct sound's, the early reflections'): mix [2 * frame] = the fp32 sum
-// of out [count][2 * frame] over the rows, in list order
-void launch_callback_mix(const float* out, int count, int frame, float* mix, hipStream_t s);
+// the mix of the audio callbacks (the reverb's, the direct sound's, the voice banks'): mix [row] = the fp32 sum of out [count][row]
+// over the rows, in list order; row = a row's length in floats (2 * frame, or C * frame of the ambisonic bus)
+void launch_callback_mix(const float* out, int count, int row, float* mix, hipStream_t s);
 // take: the partitioned rows that take a newer IR in this callback (n_take >= 1)
 void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, hipStream_t s);
 void launch_reverb_ears_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, const ReverbEars& e, hipStream_t s);
@@ -840,6 +841,82 @@ struct BinauralRenderBatch {
 };
 // the plan pass, the fold of the HRIRs into the band FIRs, the render pass (which also appends the blocks to the rings), the mix (when b.mix)
 void launch_binaural_render(const BinauralRenderBatch& b, hipStream_t s);
+// fs_ambisonic_render.hip (the ambisonic-voice callback): a voice carries the gains of the C = (order + 1)^2 channels of an
+// ambisonic bus, ACN order and SN3D normalisation, up to order 3.  A source's state block is a VoiceBankState of 128-byte slots,
+// then at kAmbisonicBankHeader bytes ONE history ring [ring]: a point source is mono, x(n) = 0.5f * (left + right).
+constexpr int kAmbisonicChannels = 16;
+// The header's encoding, to the bit, for the host (fs_ambisonic_encode) and the device (the plan pass) alike: every operation is
+// fp32, rounded on its own, in the order written; division and square root are correctly rounded on both.  y [kAmbisonicChannels]:
+// the (order + 1)^2 first are written.  The head frame has y to the right, AmbiX to the left: y is negated.
+__host__ __device__ inline void ambisonic_encode(int order, const float* d, float* y_out) {
+    const float len = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    const float x = d[0] / len, y = -(d[1] / len), z = d[2] / len;
+    y_out[0] = 1.0f;
+    if (order < 1) return;
+    y_out[1] = y;
+    y_out[2] = z;
+    y_out[3] = x;
+    if (order < 2) return;
+    const float xx = x * x, yy = y * y, zz = z * z;
+    const float K3 = (float)1.7320508075688772, K3h = (float)0.8660254037844386;   // sqrt(3), sqrt(3) / 2
+    y_out[4] = K3 * (x * y);
+    y_out[5] = K3 * (y * z);
+    y_out[6] = 1.5f * zz - 0.5f;
+    y_out[7] = K3 * (x * z);
+    y_out[8] = K3h * (xx - yy);
+    if (order < 3) return;
+    const float K58 = (float)0.7905694150420949, K15 = (float)3.872983346207417;   // sqrt(5 / 8), sqrt(15)
+    const float K38 = (float)0.6123724356957945, K15h = (float)1.9364916731037085;   // sqrt(3 / 8), sqrt(15) / 2
+    y_out[9] = K58 * (y * (3.0f * xx - yy));
+    y_out[10] = K15 * ((x * y) * z);
+    y_out[11] = K38 * (y * (5.0f * zz - 1.0f));
+    y_out[12] = z * (2.5f * zz - 1.5f);
+    y_out[13] = K38 * (x * (5.0f * zz - 1.0f));
+    y_out[14] = K15h * (z * (xx - yy));
+    y_out[15] = K58 * (x * (xx - 3.0f * yy));
+}
+// what the entry points accept as a direction: finite components and an fp32 squared length, summed as above, in [1e-30, 1e30]
+inline bool ambisonic_direction_ok(const float* d) {
+    if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) return false;
+    const float len2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+    return std::isfinite(len2) && len2 >= 1e-30f && len2 <= 1e30f;
+}
+struct AmbisonicRenderSlot {
+    int32_t held;          // as ReflectRenderSlot's
+    uint32_t key;
+    float d0;              // the delay the slot's last output sample used, in samples
+    float g0[FS_MAX_BANDS];   // ... its band gains
+    float w0[kAmbisonicChannels];   // ... its channel gains (0 beyond C)
+    int32_t pad[5];
+};
+static_assert(sizeof(AmbisonicRenderSlot) == 128, "AmbisonicRenderSlot: thirty-two words");
+using AmbisonicRenderState = VoiceBankState<AmbisonicRenderSlot>;
+constexpr size_t kAmbisonicBankHeader = 4352;
+static_assert(sizeof(AmbisonicRenderState) == 4160 && sizeof(AmbisonicRenderState) <= kAmbisonicBankHeader && kAmbisonicBankHeader % 256 == 0,
+              "VoiceBankState: the counter's line and 32 slots of 128 bytes in front of the ring");
+struct AmbisonicRenderItem : VoiceBankItem<AmbisonicRenderSlot> {};
+static_assert(sizeof(AmbisonicRenderItem) == 64, "AmbisonicRenderItem: ReflectRenderItem's layout (ring: [mask + 1], one ring)");
+// what the plan pass fixes for a sounding slot: ReflectRenderPlan's, with sixteen channel gains' start and change
+struct AmbisonicRenderPlan {
+    float d0, e;
+    float g0[FS_MAX_BANDS], g1[FS_MAX_BANDS];
+    float w0[kAmbisonicChannels], dw[kAmbisonicChannels];
+    int32_t pad[14];
+};
+static_assert(sizeof(AmbisonicRenderPlan) == 256, "AmbisonicRenderPlan: sixty-four words");
+struct AmbisonicRenderBatch {
+    const AmbisonicRenderItem* items;   // [count]
+    const fs_ambisonic_voice* voices;   // [count][stride]
+    AmbisonicRenderPlan* plans;         // [count][kVoiceSlots] scratch
+    unsigned* n0;                       // [count] scratch: every row's counter before this callback
+    int count, stride, frame, taps, bands, order;
+    float fs;                           // the sample rate: an entry's d1 = delay * fs
+    const float* in;                    // [count][2 * frame] interleaved stereo
+    float* out;                         // [count][frame][C]
+    float* mix;                         // [frame][C], or null
+};
+// the plan pass, the render pass (which also appends the blocks' downmix to the rings), the mix (when b.mix)
+void launch_ambisonic_render(const AmbisonicRenderBatch& b, hipStream_t s);
 void launch_add_energy(float* energy_row, int num_bins, float delay_s, float e, hipStream_t s);
 // dynamic LDS the traversal kernels of a frame need for a tree with `stack_rows` stack rows: the larger of the walk
 // kernel (stack + work-sharing area) and the connect kernels (stack + [bands][bins] histogram + work-sharing area)

@@ -60,7 +60,7 @@ void launch_reflect_render(const ReflectRenderBatch& b, hipStream_t s) {
     const int tiles = (b.frame + kRenderTile - 1) / kRenderTile;
     hipLaunchKernelGGL(reflect_render_kernel, dim3(tiles, 2, b.count), dim3(kRenderTile), 0, s, b.items, b.plans, b.n0, b.in, b.out, b.frame,
                        b.taps, b.bands);
-    if (b.mix) launch_callback_mix(b.out, b.count, b.frame, b.mix, s);
+    if (b.mix) launch_callback_mix(b.out, b.count, 2 * b.frame, b.mix, s);
 }
 
 }  // namespace fs

@@ -170,9 +170,9 @@ __global__ void callback_mix_kernel(const float* __restrict__ out_all, int count
 
 }  // namespace
 
-void launch_callback_mix(const float* out, int count, int frame, float* mix, hipStream_t s) {
+void launch_callback_mix(const float* out, int count, int row, float* mix, hipStream_t s) {
     const int tb = 256;
-    hipLaunchKernelGGL(callback_mix_kernel, dim3((2 * frame + tb - 1) / tb), dim3(tb), 0, s, out, count, 2 * frame, mix);
+    hipLaunchKernelGGL(callback_mix_kernel, dim3((row + tb - 1) / tb), dim3(tb), 0, s, out, count, row, mix);
 }
 
 void launch_reverb_batch_fade_start(const ReverbItem* items, const int* take, int n_take, int n, hipStream_t s) {
@@ -201,7 +201,7 @@ void launch_reverb_batch(const ReverbBatch& b, hipStream_t s) {
     if (!fused && b.n_plain + b.n_fade > 0)
         hipLaunchKernelGGL(reverb_batch_prepare_kernel, rows, dim3(tb), 0, s, b.items, b.in, b.cur, b.out, b.frame, b.literal_tail, kRevPush);
     if (b.pitems) launch_reverb_part(b.pitems, b.part, b.count, b.literal_tail, b.in, b.out, s);
-    if (b.mix) launch_callback_mix(b.out, b.count, b.frame, b.mix, s);
+    if (b.mix) launch_callback_mix(b.out, b.count, 2 * b.frame, b.mix, s);
 }
 
 }  // namespace fs

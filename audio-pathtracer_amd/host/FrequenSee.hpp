@@ -89,6 +89,7 @@ private:
     friend class FrequenSeeAudioOcclusionPlugin;
     friend class FrequenSeeAudioReflectionPlugin;
     friend class FrequenSeeAudioBinauralPlugin;
+    friend class FrequenSeeAudioAmbisonicPlugin;
     FVector Location_;
     AudioRayTracingSubsystem* SubSys_ = nullptr;
     fs_source Handle_ = -1;
@@ -320,6 +321,7 @@ private:
     friend class FrequenSeeAudioOcclusionPlugin;
     friend class FrequenSeeAudioReflectionPlugin;
     friend class FrequenSeeAudioBinauralPlugin;
+    friend class FrequenSeeAudioAmbisonicPlugin;
 };
 
 inline FrequenSeeAudioComponent::~FrequenSeeAudioComponent() { OnUnregister(); }
@@ -772,6 +774,16 @@ public:
     // nullptr, Counts [count] or nullptr
     void ProcessAudio(const std::vector<FrequenSeeAudioComponent*>& Sources, const float* In, const std::vector<std::vector<fs_binaural_voice>>& Voices,
                       float* Out, float* Mix = nullptr, fs_binaural_render_row* Counts = nullptr) {
+        PackVoices(Sources, Voices, [&](const std::vector<fs_source>& H, const std::vector<fs_binaural_voice>& All, const std::vector<int32_t>& N, size_t Stride) {
+            SubSys_->Check(fs_binaural_render_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, All.data(), N.data(), (int32_t)Stride,
+                                                            Out, Mix, Counts));
+        });
+    }
+
+protected:
+    // the handles, the voice table [count][Stride] and the counts a voice-bank callback takes, handed to Call
+    template <typename CallT>
+    void PackVoices(const std::vector<FrequenSeeAudioComponent*>& Sources, const std::vector<std::vector<fs_binaural_voice>>& Voices, CallT&& Call) {
         if (Voices.size() != Sources.size()) throw std::runtime_error("FrequenSee: one voice list per source");
         size_t Stride = 1;
         for (const auto& V : Voices) Stride = std::max(Stride, V.size());
@@ -785,8 +797,32 @@ public:
             std::copy(Voices[i].begin(), Voices[i].end(), All.begin() + (std::ptrdiff_t)(i * Stride));
             N.push_back((int32_t)Voices[i].size());
         }
-        SubSys_->Check(fs_binaural_render_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, All.data(), N.data(), (int32_t)Stride, Out,
-                                                        Mix, Counts));
+        Call(H, All, N, Stride);
+    }
+};
+
+// Not in the reference: the binaural plugin's voices — the same entries, Voices() inherited unchanged — rendered into an ambisonic
+// bus of (Order + 1)^2 channels, ACN order and SN3D normalisation (fs_ambisonic_render_process_batch, one call for all sources),
+// instead of two ears: for loudspeakers, for an engine's soundfield submix, for a host's own binaural decoder.  No HRIR set is
+// needed.  The bus is rendered in the head frame given to Voices(); rotating it later (a head tracker) and decoding it are the host's.
+class FrequenSeeAudioAmbisonicPlugin : public FrequenSeeAudioBinauralPlugin {
+public:
+    explicit FrequenSeeAudioAmbisonicPlugin(AudioRayTracingSubsystem& SubSys) : FrequenSeeAudioBinauralPlugin(SubSys) {}
+    int Order = 1;   // 0 .. FS_MAX_AMBISONIC_ORDER; before OnInitSource
+    int Channels() const { return (Order + 1) * (Order + 1); }
+    void OnInitSource(const FrequenSeeAudioComponent& C) {
+        SubSys_->Check(fs_ambisonic_render_init(SubSys_->Ctx_, C.Handle_, FrameSize, Taps, VoiceCount, MaxDelaySeconds, Order));
+    }
+    void OnReleaseSource(const FrequenSeeAudioComponent& C) { SubSys_->Check(fs_ambisonic_render_release(SubSys_->Ctx_, C.Handle_)); }
+    // In [count][FrameSize * 2] interleaved stereo (a mono source in both channels; the renderer takes their mean), row i for
+    // Sources[i] and Voices[i]; Out [count][FrameSize][Channels()] or nullptr, Mix [FrameSize][Channels()] or nullptr, Counts
+    // [count] or nullptr
+    void ProcessAudio(const std::vector<FrequenSeeAudioComponent*>& Sources, const float* In, const std::vector<std::vector<fs_ambisonic_voice>>& Voices,
+                      float* Out, float* Mix = nullptr, fs_ambisonic_render_row* Counts = nullptr) {
+        PackVoices(Sources, Voices, [&](const std::vector<fs_source>& H, const std::vector<fs_ambisonic_voice>& All, const std::vector<int32_t>& N, size_t Stride) {
+            SubSys_->Check(fs_ambisonic_render_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, All.data(), N.data(), (int32_t)Stride,
+                                                             Out, Mix, Counts));
+        });
     }
 };
 

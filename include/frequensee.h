@@ -65,6 +65,7 @@
  *             fs_reflection_render_init fs_reflection_render_release fs_reflection_render_process_batch
  *             fs_hrtf_set fs_hrtf_info fs_hrtf_spherical_head
  *             fs_binaural_render_init fs_binaural_render_release fs_binaural_render_process_batch
+ *             fs_ambisonic_encode fs_ambisonic_render_init fs_ambisonic_render_release fs_ambisonic_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
  * Environment variables (FS_*) are tuning and diagnostic knobs only; all of them are read ONCE — at fs_context_create, at a
  * scene commit (builder knobs) or at the first launch of a kernel family — never per frame.
@@ -1599,6 +1600,80 @@ int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, 
                                      const fs_binaural_voice* voices /* [count][stride] */, const int32_t* voice_counts /* [count] */,
                                      int32_t stride, float* out /* [count][F * 2] or NULL */, float* mix /* [F * 2] or NULL */,
                                      fs_binaural_render_row* rows /* [count] or NULL */);
+
+/* ---- ambisonic voices on the audio thread (EXTENDED): every discrete path rendered into a soundfield -----------------------------
+ *      Not in the reference.  The reflection renderer above with the per-channel gain pair replaced by ONE scalar gain and a
+ *      direction in the head frame, as the binaural renderer's entries, and the two output channels replaced by the
+ *      C = (order + 1)^2 channels of an ambisonic bus: ACN channel order, SN3D normalisation (AmbiX), orders 0 .. 3.  The bus feeds
+ *      loudspeakers through a decoder, rotates with one small matrix per order — a head tracker may run faster than the audio
+ *      block — and decodes to a host's own binaural decoder.  Rotation and decoding stay the host's; the library renders the voice
+ *      bank: the delay with its Doppler shift, the band FIR, the keyed one-block fades.  A voice's filter is evaluated ONCE, not
+ *      once per output channel, and fanned out to the C channels by ramping gains.
+ *   Signal.  A point source is mono: a source has ONE history ring, and x(n) = 0.5f * (in[2n] + in[2n + 1]) is what enters it.
+ *   A mono source given in both channels — what the other renderers ask for — is x to the bit.
+ *   Encoding, of a direction d in the head frame (x forward, y right, z up; AmbiX has y to the left, so y is negated).  fp32,
+ *   every operation rounded on its own, in the order written; division and square root correctly rounded:
+ *     len = sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z);  x = d.x/len;  y = -(d.y/len);  z = d.z/len;  xx = x*x;  yy = y*y;  zz = z*z;
+ *     K3 = (float)sqrt(3.0), K3h = (float)(sqrt(3.0)/2), K58 = (float)sqrt(5.0/8), K15 = (float)sqrt(15.0),
+ *     K38 = (float)sqrt(3.0/8), K15h = (float)(sqrt(15.0)/2)   (the double values rounded to float once)
+ *     Y0 = 1
+ *     Y1 = y               Y2 = z                           Y3 = x
+ *     Y4 = K3*(x*y)        Y5 = K3*(y*z)                    Y6 = 1.5f*zz - 0.5f    Y7 = K3*(x*z)    Y8 = K3h*(xx - yy)
+ *     Y9 = K58*(y*(3.0f*xx - yy))    Y10 = K15*((x*y)*z)    Y11 = K38*(y*(5.0f*zz - 1.0f))    Y12 = z*(2.5f*zz - 1.5f)
+ *     Y13 = K38*(x*(5.0f*zz - 1.0f)) Y14 = K15h*(z*(xx - yy))   Y15 = K58*(x*(xx - 3.0f*yy))
+ *   These are sqrt((2 - delta_m0) (n - |m|)! / (n + |m|)!) P_n^|m|(z) {cos, sin}(|m| az) without the Condon-Shortley phase, channel
+ *   n (n + 1) + m; each order's squares sum to 1.  A direction is legal when its components are finite and its fp32 squared length
+ *   (d.x*d.x + d.y*d.y) + d.z*d.z is finite and lies in [1e-30f, 1e30f].
+ *   fs_ambisonic_encode writes Y_0 .. Y_{C-1} of a direction; host only, no context, no device: for hosts that encode other beds
+ *   into the same bus.  The plan pass on the device gives the same bits.  FS_ERR_INVALID_ARGUMENT: order outside
+ *   0 .. FS_MAX_AMBISONIC_ORDER, direction or out NULL, a direction that is not legal.
+ *   fs_ambisonic_render_init.  F, T, D and V under fs_reflection_render_init's limits, 0 <= order <= FS_MAX_AMBISONIC_ORDER:
+ *   otherwise FS_ERR_INVALID_ARGUMENT.  The state is the ambisonic renderer's own — a source may hold direct, reflection, binaural
+ *   and ambisonic state side by side: ONE zeroed history ring (the smallest power of two >= D + T + 1 + F floats), n0, and V slots
+ *   {held, key, d0, g0[bands], w0[16]}, all free; the host-side copy of (held, key) as the reflection renderer's.  Calling init
+ *   again re-initialises the source with the new F, T, V, D and order.  fs_ambisonic_render_release: history := 0, every slot free
+ *   (a source without fs_ambisonic_render_init: nothing to do, FS_OK).
+ *   One callback, per row.  fp32 throughout, every operation rounded on its own, in the order written.
+ *     1. Match.  Rule 1 of the reflection renderer, verbatim, with w1[c] = gain * Y_c(direction) for c < C — the aim of an entry —
+ *        w1 := 0 at an END and w0 := 0 at a START.
+ *     2. Voice output.  For every sounding slot j, y_j(s) is "Output s" of the direct renderer, verbatim, on x(n) — the source's
+ *        one history followed by this block's downmix — with this slot's (d0, e, g0, g1).  One value per sample, not one per
+ *        channel.
+ *     3. Sum, over the sounding slots in ascending slot number, from acc = 0, per channel c < C: dw = w1[c] - w0[c];
+ *        w = w0[c] + a * dw;  acc = acc + w * y_j.  out(s, c) = acc, not clamped.  A row without a sounding slot gives zeros.
+ *     4. Afterwards a continuing or started slot holds d0 + e, g1 (0 beyond num_bands) and w1; an ended slot is free; the block's
+ *        downmix enters the history; n0 += F.  rows[i] as the reflection renderer's.
+ *     Consequences.  At order 0 with a mono source in both channels the output equals channel 0 of
+ *     fs_reflection_render_process_batch with channel_gain = (gain, gain).  At any order channels (c, c') equal the reflection
+ *     renderer's two channels with channel_gain = (gain * Y_c, gain * Y_c') from fs_ambisonic_encode, to the bit.
+ *   fs_ambisonic_render_process_batch.
+ *     in  [count][frame_size * 2]  interleaved stereo, host; row i belongs to sources[i]
+ *     out [count][frame_size * C]  or NULL; interleaved by sample: element s * C + c
+ *     mix [frame_size * C]         or NULL; out == NULL && mix == NULL is FS_ERR_INVALID_ARGUMENT
+ *   voices, voice_counts, stride and rows as fs_reflection_render_process_batch's.  Its refusals and batch rules, read for this
+ *   call, and further FS_ERR_INVALID_ARGUMENT for: a gain that is not finite; a direction that is not legal (above); a source
+ *   without fs_ambisonic_render_init; sources that do not share F, T and order.  A refused call changes nothing.  A source gives
+ *   the same bits and the same state served alone, in any batch or in a permuted batch; mix is the fp32 sum in list order,
+ *   computed on the device, and with out == NULL only mix comes back — at order 3 a row of out is 8 times a stereo row, so a host
+ *   that wants the bus asks for mix alone.  Staging of its own (pinned + device), grown at the first call that needs more; a call
+ *   of a shape the context has seen allocates nothing.  One copy up, three launches whatever the count (plan, render, mix), one
+ *   copy back, one wait on the reverb stream.  ONE audio render thread runs all callbacks of a context.
+ *   The output is late by (T - 1) / 2 samples.  Not here: a decoder or rotator, orders above 3, an ambisonic late reverb (a host
+ *   adds fs_reverb_process_batch's mono output to channel 0, or plays the two-ear reverb beside a decoded bus).
+ *   fs_source_destroy and fs_context_destroy free everything. */
+#define FS_MAX_AMBISONIC_ORDER 3
+typedef fs_binaural_voice fs_ambisonic_voice;      /* key, delay, band_gain, gain, direction (head frame): 56 bytes */
+typedef struct fs_ambisonic_render_row {
+    uint32_t sounding, started, ended, dropped;
+} fs_ambisonic_render_row;            /* 16 bytes */
+int fs_ambisonic_encode(int32_t order, const float* direction /* [3] */, float* out /* [(order + 1)^2] */);
+int fs_ambisonic_render_init(fs_context* ctx, fs_source src, int32_t frame_size, int32_t taps, int32_t voices, float max_delay_seconds,
+                             int32_t order);
+int fs_ambisonic_render_release(fs_context* ctx, fs_source src);
+int fs_ambisonic_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in /* [count][F * 2] */,
+                                      const fs_ambisonic_voice* voices /* [count][stride] */, const int32_t* voice_counts /* [count] */,
+                                      int32_t stride, float* out /* [count][F * C] or NULL */, float* mix /* [F * C] or NULL */,
+                                      fs_ambisonic_render_row* rows /* [count] or NULL */);
 
 /* ---- row f4: frequency-dependent material response of one audio block ------------------------------------
  *      UMaterialAcousticProcessor::ApplyMaterialFD (Private/MaterialAcousticProcessor.cpp:8-107, MAP.cpp):
