@@ -10,11 +10,12 @@ from . import _capi, scenes, sharding  # noqa: F401
 from ._capi import FrequenSeeError, default_config, default_params  # noqa: F401
 from .component import (AudioRayTracingSubsystem, Context, FrequenSeeAudioComponent,  # noqa: F401
                         FrequenSeeAudioAmbisonicPlugin, FrequenSeeAudioBinauralPlugin, FrequenSeeAudioOcclusionPlugin, FrequenSeeAudioReflectionPlugin,
-                        FrequenSeeAudioReverbPlugin,
+                        FrequenSeeAudioReverbPlugin, FrequenSeeAudioSoundfieldReverbPlugin,
                         MaterialAcousticProcessor)
 
 __all__ = ["AudioRayTracingSubsystem", "FrequenSeeAudioComponent", "FrequenSeeAudioReverbPlugin", "FrequenSeeAudioOcclusionPlugin",
            "FrequenSeeAudioReflectionPlugin", "FrequenSeeAudioBinauralPlugin", "FrequenSeeAudioAmbisonicPlugin",
+           "FrequenSeeAudioSoundfieldReverbPlugin",
            "MaterialAcousticProcessor", "Context",
            "FrequenSeeError",
            "default_config", "default_params", "scenes", "sharding"]

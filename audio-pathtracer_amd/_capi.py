@@ -51,6 +51,8 @@ EXPORTS = [
     "fs_save_array_to_file", "fs_load_float_array", "fs_save_impulse_response",
     "fs_reverb_init", "fs_reverb_process", "fs_reverb_process_batch", "fs_reverb_release", "fs_reverb_set_crossfade", "fs_reverb_set_engine",
     "fs_reverb_ears_default", "fs_reverb_ears_set", "fs_reverb_ears_info", "fs_reverb_set_ears", "fs_reverb_copy_ear_impulse_responses",
+    "fs_reverb_soundfield_set", "fs_reverb_soundfield_info", "fs_reverb_set_soundfield", "fs_reverb_copy_soundfield_impulse_responses",
+    "fs_reverb_soundfield_process_batch",
     "fs_apply_material_fd", "fs_energy_handoff", "fs_scene_update_triangles", "fs_scene_refit", "fs_scene_set_object_transforms", "fs_set_impulse_response",
     "fs_scene_commit_fast", "fs_comm_unique_id", "fs_comm_init", "fs_comm_attach", "fs_comm_detach", "fs_comm_info", "fs_comm_enable_oneshot", "fs_shard_range",
     "fs_peers_init", "fs_peers_detach", "fs_gather_energy", "fs_gather_energy_async", "fs_set_pipelining", "fs_set_walk_stages", "fs_set_frames_per_launch", "fs_submit", "fs_scene_commit_progressive", "fs_scene_refine_pending", "fs_scene_refine_wait",
@@ -629,6 +631,11 @@ def load():
         "fs_reverb_ears_info": (C.c_int, [vp, f32p, f32p, C.c_void_p]),
         "fs_reverb_set_ears": (C.c_int, [vp, i32, i32]),
         "fs_reverb_copy_ear_impulse_responses": (C.c_int, [vp, i32, f32p, f32p, i32]),
+        "fs_reverb_soundfield_set": (C.c_int, [vp, i32]),
+        "fs_reverb_soundfield_info": (C.c_int, [vp, C.c_void_p, C.c_void_p]),
+        "fs_reverb_set_soundfield": (C.c_int, [vp, i32, i32]),
+        "fs_reverb_copy_soundfield_impulse_responses": (C.c_int, [vp, i32, f32p, i32]),
+        "fs_reverb_soundfield_process_batch": (C.c_int, [vp, C.c_void_p, i32, f32p, C.c_void_p, C.c_uint32, C.c_void_p]),
         "fs_apply_material_fd": (C.c_int, [vp, f32p, i32, f32p, f32p, f32p, i32, f32p, f32p, f32p]),
         "fs_comm_unique_id": (C.c_int, [vp, C.c_size_t]),
         "fs_comm_init": (C.c_int, [vp, vp, C.c_size_t]),

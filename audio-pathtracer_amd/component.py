@@ -813,6 +813,45 @@ class Context:
         self.check(self.lib.fs_reverb_copy_ear_impulse_responses(self.h, src, left.ctypes.data, right.ctypes.data, left.shape[0]))
         return left, right
 
+    def reverb_soundfield_set(self, order=1, clear=False):
+        """fs_reverb_soundfield_set: build and install the soundfield reverb's carriers for an ACN/SN3D bus of (order + 1)^2
+        channels, or clear the set (include/frequensee.h "soundfield late reverb")"""
+        self.check(self.lib.fs_reverb_soundfield_set(self.h, -1 if clear else int(order)))
+
+    def reverb_soundfield_info(self):
+        """fs_reverb_soundfield_info -> (order, installed); order is -1 with no set installed"""
+        order, on = C.c_int32(0), C.c_int32(0)
+        self.check(self.lib.fs_reverb_soundfield_info(self.h, C.addressof(order), C.addressof(on)))
+        return int(order.value), bool(on.value)
+
+    def reverb_set_soundfield(self, src, on):
+        """the soundfield for the source's next reverb_init (needs the partitioned engine, an installed set and no ears there)"""
+        self.check(self.lib.fs_reverb_set_soundfield(self.h, src, 1 if on else 0))
+
+    def reverb_soundfield_impulse_responses(self, src):
+        """fs_reverb_copy_soundfield_impulse_responses -> [C][num_samples]: h_c of the source's newest device-resident IR"""
+        order, on = self.reverb_soundfield_info()
+        out = np.empty(((order + 1) ** 2 if on else 1, self.num_samples), dtype=np.float32)
+        self.check(self.lib.fs_reverb_copy_soundfield_impulse_responses(self.h, src, out.ctypes.data, out.shape[1]))
+        return out
+
+    def reverb_soundfield_process_batch(self, sources, blocks, want_out=True, want_mix=False, flags=0):
+        """the soundfield callbacks of several sources as one set of launches (include/frequensee.h
+        fs_reverb_soundfield_process_batch): blocks [count][frame_size * 2] -> out [count][frame_size][C] (want_out), mix
+        [frame_size][C] (want_mix: the fp32 sum of the outputs in list order), or the pair when both are asked for; C = (order +
+        1)^2 of the set installed"""
+        srcs, count, a, _, _ = self._callback_open(sources, blocks, getattr(self, "_rev_frame", {}), False, False)
+        order, _ = self.reverb_soundfield_info()
+        frame, channels = a.shape[1] // 2, (max(order, 0) + 1) ** 2
+        out = np.empty((count, frame, channels), np.float32) if want_out else None
+        mix = np.empty((frame, channels), np.float32) if want_mix else None
+        self.check(self.lib.fs_reverb_soundfield_process_batch(self.h, srcs.ctypes.data, count, a.ctypes.data,
+                                                               out.ctypes.data if want_out else None, int(flags),
+                                                               mix.ctypes.data if want_mix else None))
+        if out is None and mix is None:
+            return None
+        return self._callback_close(out, mix)
+
     def apply_material_fd(self, in_buffer, absorption, transmission, scattering):
         """UMaterialAcousticProcessor::ApplyMaterialFD (MAP.cpp:8-107) -> (specular, diffuse, transmitted)"""
         x = np.ascontiguousarray(in_buffer, dtype=np.float32).reshape(-1)
@@ -1224,6 +1263,41 @@ class FrequenSeeAudioReverbPlugin:
     def SetEngine(self, component: FrequenSeeAudioComponent, engine):
         """not in the reference: the convolution engine of the source's next OnInitSource (_capi.REVERB_ENGINE_*)"""
         self.ctx.reverb_set_engine(component._src, engine)
+
+
+class FrequenSeeAudioSoundfieldReverbPlugin(FrequenSeeAudioReverbPlugin):
+    """Not in the reference: the reverb plugin with the late field on an ambisonic bus of (Order + 1)^2 channels, ACN order and SN3D
+    normalisation (fs_reverb_soundfield_process_batch) — the diffuse counterpart of FrequenSeeAudioAmbisonicPlugin's voices, whose
+    mix it is summed with.  SetOrder installs the context's carrier set; OnInitSource selects the partitioned engine and the
+    soundfield.  The output is not clamped and bApplyReverb is not read: the call has no bypass row."""
+
+    def __init__(self, subsystem: AudioRayTracingSubsystem):
+        super().__init__(subsystem)
+        self.Order = 1   # 0 .. MAX_AMBISONIC_ORDER; SetOrder before OnInitSource
+
+    def SetOrder(self, Order=1):
+        self.ctx.reverb_soundfield_set(int(Order))
+        self.Order = int(Order)
+
+    def OnInitSource(self, component: FrequenSeeAudioComponent):
+        self.ctx.reverb_set_engine(component._src, _capi.REVERB_ENGINE_PARTITIONED)
+        self.ctx.reverb_set_ears(component._src, False)
+        self.ctx.reverb_set_soundfield(component._src, True)
+        self.ctx.reverb_init(component._src, self.FrameSize)
+
+    def ProcessAudio(self, components, buffers, want_out=True, want_mix=False):
+        """buffers[i] is components[i]'s stereo block -> what Context.reverb_soundfield_process_batch returns"""
+        return self.ctx.reverb_soundfield_process_batch([c._src for c in components], buffers, want_out=want_out, want_mix=want_mix)
+
+    def ProcessSourceAudio(self, component: FrequenSeeAudioComponent, AudioBuffer, literal_tail=False):
+        return self.ProcessAudio([component], [AudioBuffer])[0]
+
+    def ProcessSourcesAudio(self, components, buffers, literal_tail=False, want_out=True, want_mix=False):
+        return self.ProcessAudio(components, buffers, want_out=want_out, want_mix=want_mix)
+
+    def ImpulseResponses(self, component: FrequenSeeAudioComponent):
+        """h_c [C][num_samples] of the source's newest impulse response, for a host with a convolver of its own"""
+        return self.ctx.reverb_soundfield_impulse_responses(component._src)
 
 
 class FrequenSeeAudioOcclusionPlugin:

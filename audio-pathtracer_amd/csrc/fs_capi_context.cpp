@@ -659,13 +659,14 @@ int fs_context_destroy(fs_context* ctx) {
         for (float2* w : ctx->d_rev_tw) if (w) (void)hipFree(w);
         for (PathStaging* st : {&ctx->direct_stage, &ctx->reflect_stage, &ctx->diffract_stage, &ctx->reflect2_stage, &ctx->diffract2_stage, &ctx->mixed_stage}) st->release();
         if (ctx->d_direct_off) (void)hipFree(ctx->d_direct_off);
-        for (CallbackStage* st : {&ctx->rev_stage, &ctx->dr_stage, &ctx->rr_stage, &ctx->br_stage, &ctx->ar_stage}) st->release();
+        for (CallbackStage* st : {&ctx->rev_stage, &ctx->dr_stage, &ctx->rr_stage, &ctx->br_stage, &ctx->ar_stage, &ctx->sf_stage}) st->release();
         if (ctx->d_hrtf) (void)hipFree(ctx->d_hrtf);
         for (const auto& t : ctx->dr_tables) if (t.d) (void)hipFree(t.d);
         if (ctx->d_batch) (void)hipFree(ctx->d_batch);
         if (ctx->d_build) (void)hipFree(ctx->d_build);
         if (ctx->d_carrier) (void)hipFree(ctx->d_carrier);
         if (ctx->d_ear_carrier) (void)hipFree(ctx->d_ear_carrier);
+        if (ctx->d_sf_carrier) (void)hipFree(ctx->d_sf_carrier);
         if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
         for (hipEvent_t e : ctx->ev_batch) if (e) (void)hipEventDestroy(e);
         for (const fs_context::RetiredTable& r : ctx->retired_tables) { (void)hipFree(r.p); (void)hipEventDestroy(r.ev); }

@@ -171,6 +171,7 @@ int fs_set_band_edges(fs_context* ctx, const float* edges_hz, int32_t count) {
         if (rc) return rc;
     }
     float* ear_set = nullptr;
+    float* sf_set = nullptr;
     if (ctx->device_ok) {
         const int rc = fs_synchronize(ctx);
         if (rc) return rc;
@@ -180,11 +181,25 @@ int fs_set_band_edges(fs_context* ctx, const float* edges_hz, int32_t count) {
             std::swap(ctx->band_edges, edges);
             if (br) return br;   // (refused: the edges, the spectral carriers and the ear set in force stay)
         }
+        if (ctx->d_sf_carrier) {   // fs_reverb_soundfield_set's set likewise
+            std::swap(ctx->band_edges, edges);
+            const int br = build_soundfield_carriers(ctx, ctx->sf_order, "fs_set_band_edges", &sf_set);
+            std::swap(ctx->band_edges, edges);
+            if (br) {
+                if (ear_set) (void)hipFree(ear_set);
+                return br;
+            }
+        }
         if (ctx->d_carrier) { FS_HIP(ctx, hipFree(ctx->d_carrier)); ctx->d_carrier = nullptr; }
     }
     ctx->band_edges = edges;
-    if (ear_set) return install_ear_carriers(ctx, ear_set, ctx->ear_radius_cm, ctx->ear_speed_cm_s);
-    return FS_OK;
+    int rc = FS_OK;
+    if (ear_set) rc = install_ear_carriers(ctx, ear_set, ctx->ear_radius_cm, ctx->ear_speed_cm_s);
+    if (sf_set) {
+        const int sr = install_soundfield_carriers(ctx, sf_set, ctx->sf_order);
+        if (!rc) rc = sr;
+    }
+    return rc;
 }
 
 int fs_synchronize(fs_context* ctx) {

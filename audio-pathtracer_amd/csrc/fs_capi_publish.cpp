@@ -229,6 +229,59 @@ int install_ear_carriers(fs_context* ctx, float* set, float radius_cm, float spe
     return FS_OK;
 }
 
+// fs_reverb_soundfield_set: the same steps for C channels of B rows (fs_fft.hip: launch_build_soundfield_carriers); the work buffers
+// are those of one channel
+int build_soundfield_carriers(fs_context* ctx, int32_t order, const char* what, float** set) {
+    *set = nullptr;
+    const int C = (order + 1) * (order + 1);
+    const int B = ctx->cfg.num_bands, n = carrier_log(ctx), N = ctx->num_samples, ld = carrier_stride(N);
+    const size_t K = (size_t)1 << n;
+    const std::vector<double> edges = effective_edges(ctx);
+    CarrierBands bands{};
+    if (!band_bins(ctx, edges.data(), &bands)) return check_band_edges(ctx, nullptr, what);
+    std::vector<float2> w(std::max<size_t>(K / 2, 1));   // W[k] = exp(-2 pi i k / K) in double
+    for (size_t k = 0; k < K / 2; ++k) {
+        const double a = -2.0 * 3.14159265358979323846 * (double)k / (double)K;
+        w[k] = make_float2((float)std::cos(a), (float)std::sin(a));
+    }
+    if (K < 2) w[0] = make_float2(1.f, 0.f);
+    float2 *X = nullptr, *y = nullptr, *W = nullptr;
+    float *zeros = nullptr, *out = nullptr;
+    hipError_t e = hipSetDevice(ctx->cfg.device);
+    if (e == hipSuccess) e = hipMalloc((void**)&out, sizeof(float) * (size_t)C * (size_t)B * (size_t)ld);
+    if (e == hipSuccess) e = hipMalloc((void**)&X, sizeof(float2) * (size_t)B * K);
+    if (e == hipSuccess) e = hipMalloc((void**)&y, sizeof(float2) * (size_t)B * K);
+    if (e == hipSuccess) e = hipMalloc((void**)&W, sizeof(float2) * w.size());
+    if (e == hipSuccess) e = hipMalloc((void**)&zeros, sizeof(float) * (K / 2 + 1));
+    if (e == hipSuccess) e = hipMemcpyAsync(W, w.data(), sizeof(float2) * w.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(zeros, 0, sizeof(float) * (K / 2 + 1), ctx->stream);
+    if (e == hipSuccess) {
+        launch_build_soundfield_carriers(C, B, n, N, ld, bands, X, y, W, zeros, out, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (w is a local; the work buffers go next)
+    for (void* q : {(void*)X, (void*)y, (void*)W, (void*)zeros}) if (q) (void)hipFree(q);
+    if (e != hipSuccess) {
+        if (out) (void)hipFree(out);
+        return ctx->hip_fail(e, (std::string(what) + ": building the soundfield carriers").c_str());
+    }
+    *set = out;
+    return FS_OK;
+}
+
+int install_soundfield_carriers(fs_context* ctx, float* set, int32_t order) {
+    hipError_t e = hipStreamSynchronize(ctx->rev_stream);   // (no callback's launches still read the set in force)
+    if (e == hipSuccess && ctx->d_sf_carrier) e = hipFree(ctx->d_sf_carrier);
+    if (e != hipSuccess) {   // (the set in force stays; the new one is not kept)
+        if (set) (void)hipFree(set);
+        return ctx->hip_fail(e, "installing the soundfield carriers");
+    }
+    ctx->d_sf_carrier = set;
+    ctx->sf_order = set ? order : -1;
+    ctx->sf_set_gen++;
+    return FS_OK;
+}
+
 int carrier_for(fs_context* ctx, const fs_params* p, const float** out) {
     *out = nullptr;
     if (!(p->flags & FS_FLAG_SPECTRAL_IR)) return FS_OK;

@@ -1,7 +1,8 @@
 // fs_capi_reverb.cpp — row f2, the reverb plugin's per-callback convolution (RVB.cpp:74-213) behind the C ABI: per-source set-up
 // (fs_reverb_init / _set_engine / _set_crossfade / _release) and the audio callback.  There is ONE callback path, reverb_rows: a
 // list of rows served by one set of launches (fs_reverb.hip, and fs_reverb_part.hip for the rows of the partitioned engine);
-// fs_reverb_process is that list with one row.
+// fs_reverb_process is that list with one row.  The soundfield sources (fs_reverb_set_soundfield) have a callback of their own,
+// soundfield_rows behind fs_reverb_soundfield_process_batch: the same per-source step, rows of C frame floats.
 #include <cmath>
 
 #include "fs_context.hpp"
@@ -14,7 +15,7 @@ bool partitioned(const Source* s) { return s->rev_engine == FS_REVERB_ENGINE_PAR
 // the direct engine, partition spectra for the partitioned one, which needs the one it convolves (h_to) without a fade too
 // (both == false)
 int alloc_fade(fs_context* ctx, Source* s, bool both) {
-    const size_t bytes = partitioned(s) ? sizeof(float2) * ((size_t)s->part_K << s->part_n) * (s->rev_ears ? 2 : 1)   // (ears: M_p, then S_p)
+    const size_t bytes = partitioned(s) ? sizeof(float2) * ((size_t)s->part_K << s->part_n) * (s->rev_sf ? (size_t)s->sf_P : s->rev_ears ? 2 : 1)   // (ears: M_p, then S_p; soundfield: the P pairs)
                                         : sizeof(float) * (size_t)ctx->num_samples;
     if (both && !s->d_fade_from) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_from, bytes));
     if (!s->d_fade_to) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_to, bytes));
@@ -39,10 +40,12 @@ enum { kRevItems, kRevPartItems, kRevLists, kRevEarLists };
 
 // the bytes of Source::d_ring: the direct engine's two history rings, or the partitioned engine's state block
 size_t reverb_state_bytes(const Source* s) {
+    if (s->rev_sf) return sizeof(float2) * sf_state_elems(s->part_n, s->part_K, s->sf_P);
     return partitioned(s) ? sizeof(float2) * part_state_elems(s->part_n, s->part_K) : sizeof(float) * 2 * kReverbRing;
 }
 
 const char* const kNoFadeBuffers = "the crossfade's impulse-response buffers are missing: call fs_reverb_init again";
+const char* const kSoundfieldSource = "the source is initialised with the soundfield (fs_reverb_set_soundfield): its callback is fs_reverb_soundfield_process_batch";
 
 // One convolved source's step of a callback, under its ir_mu.  The callback has its own stream: it is never queued behind a traced
 // frame on the compute stream.  The device-resident IR is written by reconstructs on the tail stream: read it behind the newest one
@@ -54,13 +57,16 @@ const char* const kNoFadeBuffers = "the crossfade's impulse-response buffers are
 // or without a crossfade, so it takes in the same way in both cases: H_to from d_ir_mono, when a newer IR is there.
 // A source with ears (fs_reverb_set_ears) is such a row whose spectra come from the band rows — written by the same launches as
 // d_ir_mono, under the same events — and the context's ear carriers: it also takes when that set was replaced (ear_set_gen).
+// A soundfield source (fs_reverb_set_soundfield) is the same with the soundfield carriers (sf_set_gen); its callback is
+// soundfield_rows, which reads pit alone.
 int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbItem& it, ReverbPartItem& pit, bool* takes) {
     it.apply = 1;
     it.engine = s->rev_engine;
     const bool part = partitioned(s);
     const bool xfade = s->fade_len > 0;
     const bool own = xfade || part;   // the callback convolves copies of its own
-    const bool tk = *takes = own && (!s->fade_primed || s->ir_gen != s->fade_gen || (s->rev_ears && s->ear_gen != ctx->ear_set_gen));
+    const bool tk = *takes = own && (!s->fade_primed || s->ir_gen != s->fade_gen || (s->rev_ears && s->ear_gen != ctx->ear_set_gen) ||
+                                   (s->rev_sf && s->sf_gen != ctx->sf_set_gen));
     if ((!own || tk) && s->last_rec >= 0) {
         const int buf = s->last_rec;
         // (a finished reconstruct needs no barrier packet on the stream: S of them are most of a short batch)
@@ -79,11 +85,12 @@ int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbIte
             s->fading = true;
             s->fade_pos = 0;
         }
-        if (part) { pit.take_from = (float2*)s->d_fade_from; pit.take_to = (float2*)s->d_fade_to; pit.take_ir = s->rev_ears ? s->d_ir_bands : s->d_ir_mono; pit.take_a = a; }
+        if (part) { pit.take_from = (float2*)s->d_fade_from; pit.take_to = (float2*)s->d_fade_to; pit.take_ir = (s->rev_ears || s->rev_sf) ? s->d_ir_bands : s->d_ir_mono; pit.take_a = a; }
         else { it.take_from = s->d_fade_from; it.take_to = s->d_fade_to; it.take_ir = s->d_ir_mono; it.take_a = a; }
         s->fade_primed = true;
         s->fade_gen = s->ir_gen;
         s->ear_gen = ctx->ear_set_gen;
+        s->sf_gen = ctx->sf_set_gen;
     }
     if (!own || tk) s->rev_recorded = true;
     if (part) {
@@ -227,6 +234,79 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
     return FS_OK;
 }
 
+// what the soundfield kernels read of the set in force
+ReverbSoundfield soundfield_set(const fs_context* ctx) {
+    ReverbSoundfield e{};
+    e.c = ctx->d_sf_carrier;
+    e.B = ctx->cfg.num_bands;
+    e.ld = carrier_stride(ctx->num_samples);
+    e.C = (ctx->sf_order + 1) * (ctx->sf_order + 1);
+    for (int l = 0; l < 4; ++l) e.w[l] = 1.0f / sqrtf((float)(2 * l + 1));   // (w[0] = 1.0f exactly)
+    return e;
+}
+
+// sf_stage's own blocks
+enum { kSfItems, kSfLists };
+
+// reverb_rows for `count` validated soundfield sources of one frame size (fs_reverb_soundfield_process_batch, audio thread): the
+// same steps (reverb_step), locks and events, with rows of C frame floats coming back and no bypass, literal tail or clamp.
+int soundfield_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float* in, float* out, float* mix) {
+    std::vector<int32_t> order((size_t)count);   // rows by ascending Source*: the one locking order of every thread
+    for (int32_t i = 0; i < count; ++i) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return srcs[a] < srcs[b]; });
+    for (int32_t k = 1; k < count; ++k)   // (still before the first state change or enqueue)
+        if (srcs[order[(size_t)k]] == srcs[order[(size_t)k - 1]])
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a source appears twice in the batch");
+    const int frame = srcs[0]->rev_frame;
+    const ReverbSoundfield e = soundfield_set(ctx);
+    const size_t in_row = 2 * (size_t)frame, row = (size_t)e.C * (size_t)frame;   // floats
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    hipStream_t rs = ctx->rev_stream;
+    const CallbackLayout l = callback_layout(count, frame, row, {sizeof(ReverbPartItem) * (size_t)count, sizeof(int) * 3 * (size_t)count}, {});
+    { const int rc = ctx->sf_stage.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
+    char* hs = ctx->sf_stage.h; char* ds = ctx->sf_stage.d;
+    ReverbPartItem* pitems = (ReverbPartItem*)(hs + l.up[kSfItems]);
+    int* plain = (int*)(hs + l.up[kSfLists]); int* fade = plain + count; int* take = fade + count;
+    int n_plain = 0, n_fade = 0, n_take = 0;
+    std::memcpy(hs + l.in, in, sizeof(float) * in_row * (size_t)count);
+    {
+        std::vector<std::unique_lock<std::mutex>> locks;   // held while the work is enqueued, not longer (reverb_rows)
+        locks.reserve((size_t)count);
+        for (int32_t i : order) locks.emplace_back(srcs[i]->ir_mu);
+        for (int32_t i = 0; i < count; ++i) {
+            ReverbItem unused{};
+            std::memset(&pitems[i], 0, sizeof(ReverbPartItem));
+            bool takes = false;
+            const int rc = reverb_step(ctx, srcs[i], rs, frame, unused, pitems[i], &takes);
+            if (rc) return rc;
+            if (takes) take[n_take++] = i;
+            if (pitems[i].h_to) fade[n_fade++] = i;
+            else plain[n_plain++] = i;
+        }
+        FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, rs));
+        const int* d_plain = (const int*)(ds + l.up[kSfLists]);
+        ReverbSoundfieldBatch b{};
+        b.items = (const ReverbPartItem*)(ds + l.up[kSfItems]);
+        b.plain = d_plain; b.n_plain = n_plain;
+        b.fade = d_plain + count; b.n_fade = n_fade;
+        b.n = srcs[0]->part_n; b.K = srcs[0]->part_K; b.frame = frame; b.ir_size = ctx->num_samples; b.count = count;
+        b.W = ctx->d_rev_tw[srcs[0]->part_n];
+        b.in = (const float*)(ds + l.in);
+        b.out = (float*)(ds + l.d_out);
+        b.mix = mix ? (float*)(ds + l.d_mix) : nullptr;
+        if (n_take) {
+            launch_reverb_soundfield_take(b, d_plain + 2 * count, n_take, e, rs);
+            FS_HIP(ctx, hipGetLastError());
+            for (int k = 0; k < n_take; ++k) FS_HIP(ctx, hipEventRecord(srcs[take[k]]->ev_rev, rs));
+        }
+        launch_reverb_soundfield(b, e, rs);
+        FS_HIP(ctx, hipGetLastError());
+    }
+    { const int rc = callback_finish(ctx, ctx->sf_stage, l, out != nullptr, mix); if (rc) return rc; }
+    if (out) std::memcpy(out, hs + l.h_out, sizeof(float) * row * (size_t)count);
+    return FS_OK;
+}
+
 }  // namespace
 
 int CallbackStage::fit(fs_context* ctx, size_t host_bytes, size_t dev_bytes) {
@@ -300,6 +380,12 @@ int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init: ears are on (fs_reverb_set_ears) but the source's engine is not FS_REVERB_ENGINE_PARTITIONED");
     if (s->rev_ears_next && !ctx->d_ear_carrier)
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init: ears are on (fs_reverb_set_ears) but no ear set is installed (fs_reverb_ears_set)");
+    if (s->rev_sf_next && !part)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init: the soundfield is on (fs_reverb_set_soundfield) but the source's engine is not FS_REVERB_ENGINE_PARTITIONED");
+    if (s->rev_sf_next && !ctx->d_sf_carrier)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init: the soundfield is on (fs_reverb_set_soundfield) but no soundfield set is installed (fs_reverb_soundfield_set)");
+    if (s->rev_sf_next && s->rev_ears_next)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init: the soundfield (fs_reverb_set_soundfield) and ears (fs_reverb_set_ears) are both on: a source has one of them");
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     // Reconstructs on the compute stream record an event for the callbacks only for a source that has a reverb: the ones
     // already in flight finish before this source gets one.
@@ -312,6 +398,8 @@ int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
     s->d_ring = s->d_fade_from = s->d_fade_to = nullptr;
     s->rev_engine = s->rev_engine_next;
     s->rev_ears = s->rev_ears_next;
+    s->rev_sf = s->rev_sf_next;
+    s->sf_P = s->rev_sf ? ((ctx->sf_order + 1) * (ctx->sf_order + 1) + 1) / 2 : 0;
     if (part) {   // N = the smallest power of two >= 2 F, K = ceil(num_samples / F)
         s->part_n = 5;
         while ((1 << s->part_n) < 2 * frame_size) ++s->part_n;
@@ -412,6 +500,86 @@ int fs_reverb_copy_ear_impulse_responses(fs_context* ctx, fs_source h, float* le
     return FS_OK;
 }
 
+int fs_reverb_soundfield_set(fs_context* ctx, int32_t order) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    if (order < -1 || order > FS_MAX_AMBISONIC_ORDER)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_soundfield_set: order outside 0 .. FS_MAX_AMBISONIC_ORDER (-1: clear)");
+    if (order == ctx->sf_order) return FS_OK;   // (the order installed, or nothing to clear: nothing changes)
+    for (const Source* s : ctx->sources)
+        if (s && s->alive && s->d_ring && s->rev_sf)
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_soundfield_set: the set cannot be cleared or change its order while a source is initialised with the soundfield (fs_reverb_init it without first)");
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    if (order < 0) return fsi::install_soundfield_carriers(ctx, nullptr, -1);
+    { const int rc = fsi::check_band_edges(ctx, nullptr, "fs_reverb_soundfield_set"); if (rc) return rc; }
+    { const int rc = fs_synchronize(ctx); if (rc) return rc; }   // (the build runs on the compute stream, behind everything in flight)
+    float* set = nullptr;
+    const int rc = fsi::build_soundfield_carriers(ctx, order, "fs_reverb_soundfield_set", &set);
+    if (rc) return rc;
+    return fsi::install_soundfield_carriers(ctx, set, order);
+}
+
+int fs_reverb_soundfield_info(fs_context* ctx, int32_t* order, int32_t* installed) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (order) *order = ctx->sf_order;
+    if (installed) *installed = ctx->d_sf_carrier ? 1 : 0;
+    return FS_OK;
+}
+
+int fs_reverb_set_soundfield(fs_context* ctx, fs_source h, int32_t on) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    s->rev_sf_next = on != 0;   // (the next fs_reverb_init's)
+    return FS_OK;
+}
+
+int fs_reverb_copy_soundfield_impulse_responses(fs_context* ctx, fs_source h, float* out, int32_t n) {
+    if (!ctx || !out) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (n != ctx->num_samples) return ctx->fail(FS_ERR_SIZE_MISMATCH, "n != num_samples");
+    if (!ctx->d_sf_carrier)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_copy_soundfield_impulse_responses: no soundfield set is installed (fs_reverb_soundfield_set)");
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    FS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));   // the reconstruct runs on the tail stream
+    const ReverbSoundfield e = soundfield_set(ctx);
+    const size_t bytes = sizeof(float) * (size_t)e.C * (size_t)n;
+    float* d = nullptr;
+    FS_HIP(ctx, hipMalloc((void**)&d, bytes));
+    launch_reverb_soundfield_ir(s->d_ir_bands, e, n, d, ctx->stream);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    if (err != hipSuccess) return ctx->hip_fail(err, "fs_reverb_copy_soundfield_impulse_responses");
+    return FS_OK;
+}
+
+int fs_reverb_soundfield_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in, float* out,
+                                       uint32_t flags, float* mix) {
+    if (!ctx || !sources || !in || (!out && !mix)) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    if (flags != 0) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_soundfield_process_batch: flags must be 0");
+    if (count < 1 || count > FS_MAX_REVERB_BATCH)
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_REVERB_BATCH)");
+    // Everything is validated before the first state change or enqueue: a refused call changes nothing.
+    std::vector<Source*> srcs((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        Source* s = srcs[(size_t)i] = get_source(ctx, sources[i]);
+        if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+        if (!s->d_ring) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init has not been called for this source");
+        if (!s->rev_sf)
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the source is not initialised with the soundfield (fs_reverb_set_soundfield, then fs_reverb_init)");
+        if (s->rev_frame != srcs[0]->rev_frame) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size");
+        if (!s->d_fade_to || (s->fade_len > 0 && !s->d_fade_from)) return ctx->fail(FS_ERR_OUT_OF_MEMORY, kNoFadeBuffers);
+    }
+    return soundfield_rows(ctx, srcs.data(), count, in, out, mix);
+}
+
 int fs_reverb_set_crossfade(fs_context* ctx, fs_source h, int32_t samples) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
@@ -436,6 +604,7 @@ int fs_reverb_process(fs_context* ctx, fs_source h, const float* in, float* out,
     Source* s = get_source(ctx, h);
     if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
     if (!s->d_ring) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init has not been called for this source");
+    if (s->rev_sf) return ctx->fail(FS_ERR_INVALID_ARGUMENT, kSoundfieldSource);
     if (!apply_reverb) {   // bApplyReverb == false: RVB.cpp:128-132 (neither the device nor any state; in == out is allowed)
         if (out != in) std::memmove(out, in, sizeof(float) * 2 * (size_t)s->rev_frame);
         return FS_OK;
@@ -457,6 +626,7 @@ int fs_reverb_process_batch(fs_context* ctx, const fs_source* sources, int32_t c
         Source* s = srcs[(size_t)i] = get_source(ctx, sources[i]);
         if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
         if (!s->d_ring) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init has not been called for this source");
+        if (s->rev_sf) return ctx->fail(FS_ERR_INVALID_ARGUMENT, kSoundfieldSource);
         if (s->rev_frame != srcs[0]->rev_frame) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size");
         if ((!apply_reverb || apply_reverb[i]) && s->fade_len > 0 && (!s->d_fade_from || !s->d_fade_to))
             return ctx->fail(FS_ERR_OUT_OF_MEMORY, kNoFadeBuffers);

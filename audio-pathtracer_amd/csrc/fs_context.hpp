@@ -187,6 +187,12 @@ struct Source {
     // d_fade_from are [2][part_K][N] (M_p, then S_p), taken from the band rows and the context's ear carriers of generation ear_gen.
     bool rev_ears_next = false, rev_ears = false;
     uint64_t ear_gen = 0;
+    // fs_reverb_set_soundfield: likewise.  A soundfield source is a partitioned one whose d_ring is the soundfield state block (float2
+    // [sf_state_elems(part_n, part_K, P)], P = ceil(C / 2) of the set installed at its init) and whose d_fade_to / d_fade_from are
+    // [P][part_K][N], taken from the band rows and the context's soundfield carriers of generation sf_gen
+    bool rev_sf_next = false, rev_sf = false;
+    int sf_P = 0;
+    uint64_t sf_gen = 0;
     // crossfade between successive IRs (fs_reverb_set_crossfade; the callback's own state, audio thread): fade_len L samples
     // (0: off), the callback's copies of the IRs it fades between (h_to = the newest it took, generation fade_gen),
     // fade_pos = samples output since the running fade began; fading == false: h_to alone is heard.
@@ -405,7 +411,9 @@ struct fs_context {
     // br_stage (fs_binaural_render_process_batch): up, items [count] | voices [count][stride] | the sounding slots' list; scratch,
     //   the counters [count] | the plans [count][FS_MAX_REFLECTION_VOICES] | the folded tables [sum of the rows' V][2][Tc]
     // ar_stage (fs_ambisonic_render_process_batch): rr_stage's blocks, with plans of 256 bytes and out [count][C frame] | mix [C frame]
-    CallbackStage rev_stage, dr_stage, rr_stage, br_stage, ar_stage;
+    // sf_stage (fs_reverb_soundfield_process_batch): up, items [count] | plain, fade, take lists [3][count]; out [count][C frame] |
+    //   mix [C frame]
+    CallbackStage rev_stage, dr_stage, rr_stage, br_stage, ar_stage, sf_stage;
     // the HRIR set in force (fs_hrtf_set; the audio thread's): one device block, dirs [n][3] | hrir [n][2][H]; n == 0: none
     float* d_hrtf = nullptr;
     int hrtf_dirs = 0, hrtf_taps = 0;
@@ -422,6 +430,11 @@ struct fs_context {
     float* d_ear_carrier = nullptr;      // [2][B][carrier_stride(num_samples)] fp32: the mid rows cm_b, then the side rows cs_b
     float ear_radius_cm = 0.0f, ear_speed_cm_s = 0.0f;
     uint64_t ear_set_gen = 0;
+    // fs_reverb_soundfield_set: the soundfield reverb's carrier set (null: none installed), its order, and its generation, bumped
+    // by every replacement (Source::sf_gen)
+    float* d_sf_carrier = nullptr;       // [C][B][carrier_stride(num_samples)] fp32, C = (sf_order + 1)^2
+    int32_t sf_order = -1;
+    uint64_t sf_set_gen = 0;
     // The path queries' staging (fs_capi_paths.cpp), one per query: the queries share no buffer.  Each is sized for its query's
     // largest max_paths, max_near and max_candidates, so that only a larger count grows it; its segments are the query's PathLayout.
     // direct_stage: the kernel reads the pinned sources in place.  d_direct_off: the sample-offset tables
@@ -722,6 +735,10 @@ int carrier_for(fs_context* ctx, const fs_params* p, const float** out);
 int build_ear_carriers(fs_context* ctx, float radius_cm, float speed_cm_s, const char* what, float** out);
 // ... and its installation in place of the one in force (nullptr: none), behind the reverb stream
 int install_ear_carriers(fs_context* ctx, float* set, float radius_cm, float speed_cm_s);
+// fs_reverb_soundfield_set's build for the band edges in force, a new [C][B][carrier_stride] set of C = (order + 1)^2 channels, and
+// its installation (nullptr: none, order -1), under the same two contracts
+int build_soundfield_carriers(fs_context* ctx, int32_t order, const char* what, float** out);
+int install_soundfield_carriers(fs_context* ctx, float* set, int32_t order);
 
 // ---- fs_capi_scene.cpp --------------------------------------------------------------------------------------------
 // fs_scene_commit_progressive: swap the finished background tree in; drop / wait for a background build

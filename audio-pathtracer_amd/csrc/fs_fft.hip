@@ -238,6 +238,25 @@ __global__ __launch_bounds__(kFftBlock) void ear_carrier_normalise(float* __rest
     }
 }
 
+// ---- fs_reverb_soundfield_set: channel c's band carriers (launch_build_soundfield_carriers).  blockIdx.y = band ----
+// As carrier_spectrum with the channel's seed, kCarrierSeed + (c << 32): channel 0 has the spectral IR's phases, and the streams
+// seed_c + k (k < 2^24) of two channels never meet
+__global__ __launch_bounds__(kFftBlock) void soundfield_carrier_spectrum(float2* __restrict__ X, int n, int c, CarrierBands bands) {
+    const uint32_t p = blockIdx.x * kFftBlock + threadIdx.x;
+    if (p >= (1u << n)) return;
+    const int b = blockIdx.y;
+    const uint32_t k = __brev(p) >> (32 - n);
+    float2 v = make_float2(0.0f, 0.0f);
+    if ((int)k >= bands.lo[b] && (int)k < bands.lo[b + 1]) {
+        const uint64_t seed = kCarrierSeed + ((uint64_t)(uint32_t)c << 32);
+        const double turns = (double)(uint32_t)(splitmix64(seed + k) >> 40) * 0x1p-24;   // (exact)
+        double sn, cs;
+        sincospi(2.0 * turns, &sn, &cs);
+        v = make_float2((float)cs, (float)sn);
+    }
+    X[((size_t)b << n) + p] = v;
+}
+
 }  // namespace
 
 // x: [N] complex work buffer, y: [3][N], W: [max(N/2,1)] twiddles, resp: absorption | transmission | scattering
@@ -304,6 +323,28 @@ void launch_build_ear_carriers(int B, int n, int N, int ld, const CarrierBands& 
     for (int ls = c; ls < n; ++ls)
         hipLaunchKernelGGL(fft_dit_global, dim3(half_blocks, (unsigned)(2 * B)), dim3(kFftBlock), 0, s, y, W, n, ls, ld, out, 1.0f);
     hipLaunchKernelGGL(ear_carrier_normalise, dim3((unsigned)B), dim3(kFftBlock), 0, s, out, B, N, ld);
+}
+
+// The soundfield reverb's carriers (fs_reverb_soundfield_set; definition: DESIGN.md section 8, "Soundfield late reverb"): the band
+// carriers' passes once per channel, with the channel's phases, through one pair of [B][K] work buffers (the stream orders the
+// channels); then every one of the C B rows gets the scale of a row of its own, g_{c,b} = sqrt(N / sum r_{c,b}^2).  out: [C][B][ld].
+void launch_build_soundfield_carriers(int C, int B, int n, int N, int ld, const CarrierBands& bands, float2* X, float2* y, const float2* W,
+                                      const float* zeros, float* out, hipStream_t s) {
+    const int K = 1 << n;
+    const int c = n < kFftChunkLog ? n : kFftChunkLog;
+    const size_t lds = sizeof(float2) << c;
+    const unsigned half_blocks = (unsigned)(((K >> 1) + kFftBlock - 1) / kFftBlock);
+    for (int ch = 0; ch < C; ++ch) {
+        float* rows = out + (size_t)ch * (size_t)B * (size_t)ld;
+        hipLaunchKernelGGL(soundfield_carrier_spectrum, dim3((unsigned)((K + kFftBlock - 1) / kFftBlock), (unsigned)B), dim3(kFftBlock), 0, s,
+                           X, n, ch, bands);
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(fft_dit_local, dim3(1u << (n - c), 1), dim3(kFftBlock), lds, s, X + ((size_t)b << n), y + ((size_t)b << n),
+                               zeros, zeros, zeros, W, n, c, ld, rows + (size_t)b * ld, 1.0f);
+        for (int ls = c; ls < n; ++ls)
+            hipLaunchKernelGGL(fft_dit_global, dim3(half_blocks, (unsigned)B), dim3(kFftBlock), 0, s, y, W, n, ls, ld, rows, 1.0f);
+    }
+    hipLaunchKernelGGL(carrier_normalise, dim3((unsigned)(C * B)), dim3(kFftBlock), 0, s, out, N, ld);
 }
 
 }  // namespace fs

@@ -661,6 +661,30 @@ struct ReverbEars {
     const float* c;
     int B, ld;
 };
+// fs_reverb_soundfield_set's carrier set, as the soundfield kernels read it: c [C][B][ld] fp32, channel c's B rows car_{c,b};
+// w[l] = 1.0f / sqrtf((float)(2 l + 1)), the SN3D diffuse-field weight of degree l, rounded on the host
+struct ReverbSoundfield {
+    const float* c;
+    int B, ld, C;
+    float w[4];
+};
+// A soundfield source's state (Source::d_ring), in float2: hist [N / 2] — the mono window history ring as N floats — | Y [2][P][N]
+// the products (G, G_to) of the P = ceil(C / 2) channel pairs | xring [K][N] the delay line of the mono window's spectra
+__host__ __device__ inline float* sf_hist(float2* state) { return (float*)state; }
+__host__ __device__ inline float2* sf_y(float2* state, int n) { return state + ((size_t)1 << (n - 1)); }
+__host__ __device__ inline float2* sf_xring(float2* state, int n, int P) { return state + ((size_t)1 << (n - 1)) + ((size_t)(2 * P) << n); }
+constexpr size_t sf_state_elems(int n, int K, int P) { return ((size_t)1 << (n - 1)) + ((size_t)(2 * P + K) << n); }
+// fs_reverb_soundfield_process_batch: every row of the call is a soundfield row of one frame size, order and (n, K)
+struct ReverbSoundfieldBatch {
+    const ReverbPartItem* items;    // [count]: h, h_to, take_from, take_to each [P][K][N]; take_ir = the source's B band rows
+    const int* plain; int n_plain;  // rows with one product per pair ...
+    const int* fade; int n_fade;    // ... and with two
+    const float2* W;                // twiddles of N = 1 << n
+    int n, K, frame, ir_size, count;
+    const float* in;                // [count][2 * frame] interleaved stereo
+    float* out;                     // [count][frame * C], element s * C + c
+    float* mix;                     // [frame * C], or null
+};
 struct ReverbBatch {
     const ReverbItem* items;        // [count]
     const int* plain; int n_plain;  // rows convolved with one IR ...
@@ -687,6 +711,12 @@ void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n
 void launch_reverb_ears_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, const ReverbEars& e, hipStream_t s);
 // fs_reverb_copy_ear_impulse_responses: left = m + s, right = m - s of the B band rows `bands` ([B][n]), with the take's expression
 void launch_reverb_ears_ir(const float* bands, const ReverbEars& e, int n, float* left, float* right, hipStream_t s);
+// the soundfield rows (fs_reverb_soundfield_process_batch): the take of the rows that take in this callback (n_take >= 1) ...
+void launch_reverb_soundfield_take(const ReverbSoundfieldBatch& b, const int* take, int n_take, const ReverbSoundfield& e, hipStream_t s);
+// ... the mono window transforms, the products of the two lists, the P inverses per row and the mix (when b.mix)
+void launch_reverb_soundfield(const ReverbSoundfieldBatch& b, const ReverbSoundfield& e, hipStream_t s);
+// fs_reverb_copy_soundfield_impulse_responses: out [C][n] = h_c of the B band rows `bands` ([B][n]), with the take's expression
+void launch_reverb_soundfield_ir(const float* bands, const ReverbSoundfield& e, int n, float* out, hipStream_t s);
 // the window transforms, the products of the four lists (each launched only when it has rows), the inverse and epilogue
 void launch_reverb_part(const ReverbPartItem* items, const ReverbPart& p, int count, int literal_tail, const float* in, float* out,
                         hipStream_t s);
@@ -991,5 +1021,9 @@ void launch_build_carriers(int B, int n, int N, int ld, const CarrierBands& band
                            const float* zeros, float* out, hipStream_t s);
 void launch_build_ear_carriers(int B, int n, int N, int ld, const CarrierBands& bands, double fs, double radius_cm, double speed_cm_s,
                                float2* X, float2* y, const float2* W, const float* zeros, float* out, hipStream_t s);
+// fs_reverb_soundfield_set: C channels of B rows each, channel c's phases from kCarrierSeed + (c << 32) + k.  X, y: [B][K] work
+// buffers, used channel after channel; out: [C][B][ld]
+void launch_build_soundfield_carriers(int C, int B, int n, int N, int ld, const CarrierBands& bands, float2* X, float2* y, const float2* W,
+                                      const float* zeros, float* out, hipStream_t s);
 
 }  // namespace fs

@@ -21,6 +21,10 @@
 //
 // A source with ears (fs_reverb_set_ears) is such a row with two spectrum sets per IR copy and a take and a product of its own
 // (reverb_ears_take_kernel, reverb_ears_mac_kernel, at the end of the kernels); the window, delay line, inverse and fade are shared.
+//
+// A soundfield source (fs_reverb_set_soundfield) has a callback and a state block of its own: a mono window, ceil(C / 2) complex
+// IRs that each carry two channels of the ambisonic bus, and one inverse per pair (the reverb_soundfield_* kernels, behind the
+// ear kernels); of the kernels above it uses the two LDS transforms and the order of the product's sums.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -359,7 +363,238 @@ __global__ __launch_bounds__(kPartBlock) void reverb_ears_ir_kernel(const float*
     right[i] = ms.x - ms.y;
 }
 
+// ---- soundfield rows (fs_reverb_soundfield_process_batch; definition: DESIGN.md section 8, "Soundfield late reverb") ----
+// Channel c of the ACN/SN3D bus is the source's mono downmix convolved with h_c, an IR of its own: the band rows times channel c's
+// carriers, weighted for its degree.  The input is real, so channels 2q and 2q + 1 ride in one complex IR: with P = ceil(C / 2)
+//   G_{q,p} = FFT_N(h_{2q}[pF .. pF + F) + i h_{2q+1}[pF .. pF + F))        reverb_soundfield_take_kernel
+//   X_t     = FFT_N(w + 0 i), w = the mono window                           reverb_soundfield_forward_kernel -> the ring of K spectra
+//   Y_q     = sum_p G_{q,p} X_{t-p}, every X read once for all P pairs      reverb_soundfield_mac_kernel
+//   IFFT_N(Y_q): the last F samples' real part is channel 2q, the imaginary part channel 2q + 1   reverb_soundfield_inverse_kernel
+// (the product of a complex IR spectrum with a real signal's spectrum is the spectrum of the complex convolution: no mirror term).
+//
+// the degree l of ACN channel c, c < 16
+__device__ __forceinline__ int sf_degree(int c) { return c >= 9 ? 3 : (c >= 4 ? 2 : (c >= 1 ? 1 : 0)); }
+// h_c[i]: fp32, the bands in ascending order, each product rounded before it is added, the two scales last — THE expression of both
+// kernels that form it (the take and the copy)
+__device__ __forceinline__ float sf_channel(const float* __restrict__ env, const ReverbSoundfield& e, int num_samples, int c, uint32_t i) {
+    float m = 0.0f;
+    const float* __restrict__ car = e.c + (size_t)c * (size_t)e.B * (size_t)e.ld + i;
+    for (int b = 0; b < e.B; ++b) m = m + env[(size_t)b * (size_t)num_samples + i] * car[(size_t)b * (size_t)e.ld];
+    m = m * (1.0f / sqrtf((float)e.B));
+    return m * e.w[sf_degree(c)];
+}
+
+// reverb_part_take_kernel for the soundfield rows: workgroup (p, k) owns partition p of row take[k] in all P spectrum sets of a copy
+// ([P][K][N]).  The fold of a cut-short fade on all sets first, then G_{q,p} for q < P from the row's B band rows (take_ir) and the
+// carrier set; at odd C the last pair's imaginary part is zero.
+__global__ __launch_bounds__(kPartBlock) void reverb_soundfield_take_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ take,
+                                                                            const float2* __restrict__ W, int n, int K, int frame,
+                                                                            int ir_size, ReverbSoundfield e) {
+    extern __shared__ __attribute__((aligned(16))) float2 sh[];
+    const ReverbPartItem it = items[take[blockIdx.y]];
+    const uint32_t N = 1u << n;
+    const uint32_t p = blockIdx.x;
+    const int P = (e.C + 1) >> 1;
+    const size_t set = (size_t)K << n;   // from one pair's spectra to the next's
+    float2* __restrict__ h_to = it.take_to + (size_t)p * N;
+    const float a = it.take_a;
+    if (a > 0.0f) {
+        float2* __restrict__ h_from = it.take_from + (size_t)p * N;
+        for (int q = 0; q < P; ++q)
+            for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) {
+                const float2 f = h_from[q * set + i], t = h_to[q * set + i];
+                h_from[q * set + i] = make_float2((1.0f - a) * f.x + a * t.x, (1.0f - a) * f.y + a * t.y);
+            }
+    }
+    const uint32_t k0 = p * (uint32_t)frame;
+    for (int q = 0; q < P; ++q) {
+        for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) {
+            float2 v = make_float2(0.0f, 0.0f);
+            if (i < (uint32_t)frame && k0 + i < (uint32_t)ir_size) {
+                v.x = sf_channel(it.take_ir, e, ir_size, 2 * q, k0 + i);
+                if (2 * q + 1 < e.C) v.y = sf_channel(it.take_ir, e, ir_size, 2 * q + 1, k0 + i);
+            }
+            sh[i] = v;
+        }
+        lds_fft_dif(sh, W, n);
+        for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) h_to[q * set + i] = sh[i];
+        __syncthreads();   // (sh is read out before the next pair fills it)
+    }
+}
+
+// reverb_part_forward_kernel for the soundfield rows: row r = blockIdx.x, the transform of its mono window.  The history ring holds
+// N floats, d(n) = 0.5f * (in[2n] + in[2n + 1]); the window's first N - F samples come from it, the last F are this block's d, which
+// enter it.  The positions written, [head, head + F), are not among those read, [head + F, head + N).
+__global__ __launch_bounds__(kPartBlock) void reverb_soundfield_forward_kernel(const ReverbPartItem* __restrict__ items,
+                                                                               const float* __restrict__ in_all, const float2* __restrict__ W,
+                                                                               int n, int frame, int P) {
+    extern __shared__ __attribute__((aligned(16))) float2 sh[];
+    const int r = blockIdx.x;
+    const ReverbPartItem it = items[r];
+    const uint32_t N = 1u << n;
+    const float* __restrict__ in = in_all + (size_t)r * 2 * (size_t)frame;
+    float* __restrict__ hist = sf_hist(it.state);
+    const uint32_t old = N - (uint32_t)frame;
+    for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) {
+        float v;
+        if (j < old) {
+            v = hist[(it.head + (uint32_t)frame + j) & (N - 1u)];
+        } else {
+            const uint32_t i = j - old;
+            v = 0.5f * (in[2 * i] + in[2 * i + 1]);
+            hist[(it.head + i) & (N - 1u)] = v;
+        }
+        sh[j] = make_float2(v, 0.0f);
+    }
+    lds_fft_dif(sh, W, n);
+    float2* __restrict__ dst = sf_xring(it.state, n, P) + ((size_t)it.slot << n);
+    for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) dst[j] = sh[j];
+}
+
+// reverb_part_mac_kernel for the soundfield rows: the same tiling and the same order of sums, with P spectrum streams against the
+// one X — each X_{t-p}[b] is loaded once and multiplied into the P (FADE: 2 P) accumulators of the pairs, which stay in registers
+// because P is a template argument.  Y: [2][P][N], the products with G, then (FADE) with G_to.
+template <int P, bool FADE>
+__global__ __launch_bounds__(kPartBlock) void reverb_soundfield_mac_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ list,
+                                                                           int n, int K) {
+    __shared__ float2 s_sum[FADE ? 2 : 1][P][kMacWaves][kMacBins];
+    const ReverbPartItem it = items[list[blockIdx.y]];
+    const uint32_t N = 1u << n;
+    const uint32_t lane = threadIdx.x & (kMacBins - 1), w = threadIdx.x / kMacBins;
+    const uint32_t b = blockIdx.x * kMacBins + lane;
+    const bool live = b < N;   // (N = 32: half a wavefront)
+    const size_t set = (size_t)K << n;
+    const float2* __restrict__ H = it.h;
+    const float2* __restrict__ H_to = it.h_to;
+    const float2* __restrict__ xring = sf_xring(it.state, n, P);
+    float2 acc[P], acc_to[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) acc[q] = acc_to[q] = make_float2(0.0f, 0.0f);
+    if (live) {
+#pragma unroll 2
+        for (int p = (int)w; p < K; p += kMacWaves) {
+            int sp = it.slot - p;
+            sp += sp < 0 ? K : 0;
+            const float2 x = xring[((size_t)sp << n) + b];
+            const size_t at = ((size_t)p << n) + b;
+#pragma unroll
+            for (int q = 0; q < P; ++q) {
+                acc[q] = pmac(acc[q], H[q * set + at], x);
+                if (FADE) acc_to[q] = pmac(acc_to[q], H_to[q * set + at], x);
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        s_sum[0][q][w][lane] = acc[q];
+        if (FADE) s_sum[FADE ? 1 : 0][q][w][lane] = acc_to[q];
+    }
+    __syncthreads();
+    if (w == 0 && live) {
+        float2* __restrict__ Y = sf_y(it.state, n);
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            float2 v = s_sum[0][q][0][lane];
+#pragma unroll
+            for (int k = 1; k < kMacWaves; ++k) v = padd(v, s_sum[0][q][k][lane]);
+            Y[((size_t)q << n) + b] = v;
+            if (FADE) {
+                float2 u = s_sum[FADE ? 1 : 0][q][0][lane];
+#pragma unroll
+                for (int k = 1; k < kMacWaves; ++k) u = padd(u, s_sum[FADE ? 1 : 0][q][k][lane]);
+                Y[((size_t)(P + q) << n) + b] = u;
+            }
+        }
+    }
+}
+
+// reverb_part_inverse_kernel for the soundfield rows: workgroup (r, q) inverts pair q of row r — y = IFFT_N(Y_q) / N, the last F
+// samples, real part channel 2q and imaginary part channel 2q + 1 of the row's [F][C] block, NOT clamped (a bus is summed and
+// decoded before it reaches a converter).  A fading row inverts both products and mixes per output sample with the engine's expression.
+__global__ __launch_bounds__(kPartBlock) void reverb_soundfield_inverse_kernel(const ReverbPartItem* __restrict__ items,
+                                                                               const float2* __restrict__ W, int n, int frame, int P, int C,
+                                                                               float* __restrict__ out_all) {
+    extern __shared__ __attribute__((aligned(16))) float2 sh[];
+    const int r = blockIdx.x;
+    const int q = blockIdx.y;
+    const ReverbPartItem it = items[r];
+    const uint32_t N = 1u << n;
+    const float scale = 1.0f / (float)N;   // (a power of two: exact)
+    const float2* __restrict__ Y = sf_y(it.state, n) + ((size_t)q << n);
+    const float2* __restrict__ Y_to = Y + ((size_t)P << n);
+    float2* keep = sh + N;
+    float* __restrict__ out = out_all + (size_t)r * (size_t)C * (size_t)frame;
+    const uint32_t old = N - (uint32_t)frame;
+    for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) sh[j] = Y[j];
+    lds_fft_dit(sh, W, n);
+    const bool fade = it.h_to != nullptr;
+    if (fade) {
+        for (uint32_t s = threadIdx.x; s < (uint32_t)frame; s += kPartBlock) keep[s] = sh[old + s];
+        __syncthreads();
+        for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) sh[j] = Y_to[j];
+        lds_fft_dit(sh, W, n);
+    }
+    const bool partner = 2 * q + 1 < C;
+    for (uint32_t s = threadIdx.x; s < (uint32_t)frame; s += kPartBlock) {
+        float2 v = sh[old + s];
+        v = make_float2(v.x * scale, v.y * scale);
+        if (fade) {
+            const float2 f = make_float2(keep[s].x * scale, keep[s].y * scale);
+            const int p = it.fade_pos + (int)s;
+            const float g = p < it.fade_len ? (float)(p + 1) / (float)it.fade_len : 1.0f;
+            v = make_float2((1.0f - g) * f.x + g * v.x, (1.0f - g) * f.y + g * v.y);
+        }
+        out[(size_t)s * (size_t)C + 2 * q] = v.x;
+        if (partner) out[(size_t)s * (size_t)C + 2 * q + 1] = v.y;
+    }
+}
+
+// fs_reverb_copy_soundfield_impulse_responses: channel blockIdx.y's IR of one source's band rows, sample by sample
+__global__ __launch_bounds__(kPartBlock) void reverb_soundfield_ir_kernel(const float* __restrict__ bands, ReverbSoundfield e, int num_samples,
+                                                                          float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kPartBlock + threadIdx.x;
+    if (i >= (uint32_t)num_samples) return;
+    const int c = blockIdx.y;
+    out[(size_t)c * (size_t)num_samples + i] = sf_channel(bands, e, num_samples, c, i);
+}
+
+template <int P>
+void launch_soundfield_mac(const ReverbSoundfieldBatch& b, hipStream_t s) {
+    const unsigned tiles = ((1u << b.n) + kMacBins - 1) / kMacBins;
+    if (b.n_plain > 0)
+        hipLaunchKernelGGL((reverb_soundfield_mac_kernel<P, false>), dim3(tiles, (unsigned)b.n_plain), dim3(kPartBlock), 0, s, b.items, b.plain,
+                           b.n, b.K);
+    if (b.n_fade > 0)
+        hipLaunchKernelGGL((reverb_soundfield_mac_kernel<P, true>), dim3(tiles, (unsigned)b.n_fade), dim3(kPartBlock), 0, s, b.items, b.fade,
+                           b.n, b.K);
+}
+
 }  // namespace
+
+void launch_reverb_soundfield_take(const ReverbSoundfieldBatch& b, const int* take, int n_take, const ReverbSoundfield& e, hipStream_t s) {
+    hipLaunchKernelGGL(reverb_soundfield_take_kernel, dim3((unsigned)b.K, (unsigned)n_take), dim3(kPartBlock), sizeof(float2) << b.n, s,
+                       b.items, take, b.W, b.n, b.K, b.frame, b.ir_size, e);
+}
+
+void launch_reverb_soundfield(const ReverbSoundfieldBatch& b, const ReverbSoundfield& e, hipStream_t s) {
+    const size_t lds = sizeof(float2) << b.n;
+    const int P = (e.C + 1) / 2;
+    hipLaunchKernelGGL(reverb_soundfield_forward_kernel, dim3((unsigned)b.count), dim3(kPartBlock), lds, s, b.items, b.in, b.W, b.n, b.frame, P);
+    switch (P) {   // (C = 1, 4, 9, 16)
+        case 1: launch_soundfield_mac<1>(b, s); break;
+        case 2: launch_soundfield_mac<2>(b, s); break;
+        case 5: launch_soundfield_mac<5>(b, s); break;
+        default: launch_soundfield_mac<8>(b, s); break;
+    }
+    hipLaunchKernelGGL(reverb_soundfield_inverse_kernel, dim3((unsigned)b.count, (unsigned)P), dim3(kPartBlock),
+                       lds + sizeof(float2) * (size_t)b.frame, s, b.items, b.W, b.n, b.frame, P, e.C, b.out);
+    if (b.mix) launch_callback_mix(b.out, b.count, b.frame * e.C, b.mix, s);
+}
+
+void launch_reverb_soundfield_ir(const float* bands, const ReverbSoundfield& e, int n, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(reverb_soundfield_ir_kernel, dim3((unsigned)((n + kPartBlock - 1) / kPartBlock), (unsigned)e.C), dim3(kPartBlock), 0, s,
+                       bands, e, n, out);
+}
 
 void launch_reverb_ears_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, const ReverbEars& e, hipStream_t s) {
     hipLaunchKernelGGL(reverb_ears_take_kernel, dim3((unsigned)p.K, (unsigned)n_take), dim3(kPartBlock), sizeof(float2) << p.n, s, items,

@@ -86,6 +86,7 @@ public:
 private:
     friend class AudioRayTracingSubsystem;
     friend class FrequenSeeAudioReverbPlugin;
+    friend class FrequenSeeAudioSoundfieldReverbPlugin;
     friend class FrequenSeeAudioOcclusionPlugin;
     friend class FrequenSeeAudioReflectionPlugin;
     friend class FrequenSeeAudioBinauralPlugin;
@@ -318,6 +319,7 @@ private:
     friend class FrequenSeeAudioComponent;
     friend class MaterialAcousticProcessor;
     friend class FrequenSeeAudioReverbPlugin;
+    friend class FrequenSeeAudioSoundfieldReverbPlugin;
     friend class FrequenSeeAudioOcclusionPlugin;
     friend class FrequenSeeAudioReflectionPlugin;
     friend class FrequenSeeAudioBinauralPlugin;
@@ -480,8 +482,42 @@ public:
         SubSys_->Check(fs_reverb_copy_ear_impulse_responses(SubSys_->Ctx_, C.Handle_, Left.data(), Right.data(), n));
     }
 
-private:
+protected:
     AudioRayTracingSubsystem* SubSys_;
+};
+
+// Not in the reference: the reverb plugin with the late field on an ambisonic bus of (Order + 1)^2 channels, ACN order and SN3D
+// normalisation — fs_reverb_soundfield_process_batch, the diffuse counterpart of FrequenSeeAudioAmbisonicPlugin's voices, whose Mix
+// it is summed with.  SetOrder installs the context's carrier set; OnInitSource selects the partitioned engine and the soundfield.
+// The output is not clamped and bApplyReverb is not read: the call has no bypass row.
+class FrequenSeeAudioSoundfieldReverbPlugin : public FrequenSeeAudioReverbPlugin {
+public:
+    int Order = 1;   // 0 .. FS_MAX_AMBISONIC_ORDER; SetOrder before OnInitSource
+    explicit FrequenSeeAudioSoundfieldReverbPlugin(AudioRayTracingSubsystem& SubSys) : FrequenSeeAudioReverbPlugin(SubSys) {}
+    int Channels() const { return (Order + 1) * (Order + 1); }
+    void SetOrder(int NewOrder = 1) {
+        SubSys_->Check(fs_reverb_soundfield_set(SubSys_->Ctx_, NewOrder));
+        Order = NewOrder;
+    }
+    void OnInitSource(const FrequenSeeAudioComponent& C) {
+        SubSys_->Check(fs_reverb_set_engine(SubSys_->Ctx_, C.Handle_, FS_REVERB_ENGINE_PARTITIONED));
+        SubSys_->Check(fs_reverb_set_ears(SubSys_->Ctx_, C.Handle_, 0));
+        SubSys_->Check(fs_reverb_set_soundfield(SubSys_->Ctx_, C.Handle_, 1));
+        SubSys_->Check(fs_reverb_init(SubSys_->Ctx_, C.Handle_, FrameSize));
+    }
+    // In [count][FrameSize * 2] interleaved stereo, row i for Sources[i]; Out [count][FrameSize * Channels()] or nullptr,
+    // Mix [FrameSize * Channels()] or nullptr: element s * Channels() + c
+    void ProcessAudio(const std::vector<FrequenSeeAudioComponent*>& Sources, const float* In, float* Out, float* Mix = nullptr) {
+        std::vector<fs_source> H;
+        for (const auto* s : Sources) H.push_back(s->Handle_);
+        SubSys_->Check(fs_reverb_soundfield_process_batch(SubSys_->Ctx_, H.data(), (int32_t)H.size(), In, Out, 0u, Mix));
+    }
+    // h_c [Channels()][fs_num_samples] of the source's newest impulse response, for a host with a convolver of its own
+    void ImpulseResponses(const FrequenSeeAudioComponent& C, std::vector<float>& Irs) const {
+        const int n = fs_num_samples(SubSys_->Ctx_);
+        Irs.assign((size_t)Channels() * (size_t)n, 0.0f);
+        SubSys_->Check(fs_reverb_copy_soundfield_impulse_responses(SubSys_->Ctx_, C.Handle_, Irs.data(), n));
+    }
 };
 
 // What the two render plugins below share: the shape of their callback and a path's arrival time as the delay of a target or a voice

@@ -94,12 +94,32 @@ int main(int argc, char** argv) {
             ears_diff = std::fmax(ears_diff, std::fabs((double)Left[(size_t)i] - (double)Right[(size_t)i]));
         }
         Reverb.OnReleaseSource(Comp);
+        // the soundfield reverb plugin at order 1: the same block (downmix 0.5 at sample 0) comes back as 0.5 h_c in channel c
+        FrequenSeeAudioSoundfieldReverbPlugin Field(SubSys);
+        Field.Initialize(F);
+        Field.SetOrder(1);
+        Field.OnInitSource(Comp);
+        const int Ch = Field.Channels();
+        std::vector<float> Bus((size_t)F * (size_t)Ch, 0.0f), Irs;
+        Field.ProcessAudio({&Comp}, In.data(), Bus.data());
+        Field.ImpulseResponses(Comp, Irs);
+        double field_err = 0, field_peak = 0, field_pair_diff = 0;
+        for (int i = 0; i < F && i < n; ++i)
+            for (int c = 0; c < Ch; ++c) {
+                const double want = 0.5 * Irs[(size_t)c * (size_t)n + (size_t)i];
+                field_err = std::fmax(field_err, std::fabs(Bus[(size_t)i * (size_t)Ch + (size_t)c] - want));
+                field_peak = std::fmax(field_peak, std::fabs(want));
+                if (c) field_pair_diff = std::fmax(field_pair_diff, std::fabs((double)Irs[(size_t)c * (size_t)n + (size_t)i] - (double)Irs[(size_t)i]));
+            }
+        Field.OnReleaseSource(Comp);
         std::printf("{\"frames\": %d, \"pairs\": %d, \"depth\": %d, \"frames_per_s\": %.1f, \"rays_per_s\": %.0f, "
                     "\"energy_sum_first_frame\": %.6f, \"ir_samples\": %d, \"ir_peak\": %.6f, "
                     "\"occlusion_attenuation\": %.6f, \"legacy_rays_reaching\": %u, \"material_fd_max_err\": %.3g, "
-                    "\"ears_max_err\": %.3g, \"ears_peak\": %.6g, \"ears_left_right_max_diff\": %.6g, \"saved\": \"%s\"}\n",
+                    "\"ears_max_err\": %.3g, \"ears_peak\": %.6g, \"ears_left_right_max_diff\": %.6g, "
+                    "\"soundfield_max_err\": %.3g, \"soundfield_peak\": %.6g, \"soundfield_channel_max_diff\": %.6g, \"saved\": \"%s\"}\n",
                     frames, pairs, depth, frames / s, 2.0 * pairs * frames / s, e, n, peak,
-                    snd.occlusion_attenuation, snd.rays_reaching_listener, fd_err, ears_err, ears_peak, ears_diff, out.c_str());
+                    snd.occlusion_attenuation, snd.rays_reaching_listener, fd_err, ears_err, ears_peak, ears_diff, field_err, field_peak,
+                    field_pair_diff, out.c_str());
     } catch (const std::exception& ex) {
         std::fprintf(stderr, "fs_harness: %s\n", ex.what());
         return 1;

@@ -52,6 +52,8 @@
  *             fs_save_array_to_file fs_load_float_array fs_save_impulse_response
  *             fs_reverb_init fs_reverb_process fs_reverb_process_batch fs_reverb_release fs_reverb_set_crossfade fs_reverb_set_engine fs_apply_material_fd
  *             fs_reverb_ears_default fs_reverb_ears_set fs_reverb_ears_info fs_reverb_set_ears fs_reverb_copy_ear_impulse_responses
+ *             fs_reverb_soundfield_set fs_reverb_soundfield_info fs_reverb_set_soundfield
+ *             fs_reverb_copy_soundfield_impulse_responses fs_reverb_soundfield_process_batch
  *             fs_set_profiling fs_set_profiling_interval fs_get_pipeline_counters fs_get_streams
  *             fs_source_set_orientation fs_source_set_directivity fs_get_room_parameters
  *             fs_source_set_order_window fs_source_get_order_window
@@ -1658,8 +1660,8 @@ int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, 
  *   that wants the bus asks for mix alone.  Staging of its own (pinned + device), grown at the first call that needs more; a call
  *   of a shape the context has seen allocates nothing.  One copy up, three launches whatever the count (plan, render, mix), one
  *   copy back, one wait on the reverb stream.  ONE audio render thread runs all callbacks of a context.
- *   The output is late by (T - 1) / 2 samples.  Not here: a decoder or rotator, orders above 3, an ambisonic late reverb (a host
- *   adds fs_reverb_process_batch's mono output to channel 0, or plays the two-ear reverb beside a decoded bus).
+ *   The output is late by (T - 1) / 2 samples.  Not here: a decoder or rotator, orders above 3.  The late field of this bus is
+ *   fs_reverb_soundfield_process_batch's (below): a host sums the two mix rows.
  *   fs_source_destroy and fs_context_destroy free everything. */
 #define FS_MAX_AMBISONIC_ORDER 3
 typedef fs_binaural_voice fs_ambisonic_voice;      /* key, delay, band_gain, gain, direction (head frame): 56 bytes */
@@ -1674,6 +1676,72 @@ int fs_ambisonic_render_process_batch(fs_context* ctx, const fs_source* sources,
                                       const fs_ambisonic_voice* voices /* [count][stride] */, const int32_t* voice_counts /* [count] */,
                                       int32_t stride, float* out /* [count][F * C] or NULL */, float* mix /* [F * C] or NULL */,
                                       fs_ambisonic_render_row* rows /* [count] or NULL */);
+
+/* ---- soundfield late reverb (EXTENDED; DESIGN.md section 8, "Soundfield late reverb"): the late field on the ambisonic bus ----
+ * A partitioned reverb source initialised with the SOUNDFIELD convolves its mono downmix with one impulse response per channel of
+ * an ACN/SN3D bus of C = (order + 1)^2 channels.  A diffuse field has no direction, only a covariance across the channels, and that
+ * is diagonal: with unit power in W (channel 0), every channel of degree l carries power 1 / (2 l + 1), and distinct channels are
+ * uncorrelated.  So channel c (degree l(c) = floor(sqrt(c))) gets an IR of its own, built the way the ear IRs are — band envelope
+ * times band-limited noise carrier, summed over the bands — with carriers that are independent from channel to channel.  Nothing
+ * in the trace, the reconstruct or the publish path changes.
+ *
+ * The carriers are context-wide and use the bands, the bin assignment and K (the smallest power of two >= num_samples) of
+ * FS_FLAG_SPECTRAL_IR, fs_set_band_edges included.  For channel c < C and bin k in [1, K/2):
+ *   1. seed_c = 0x5EED + (c << 32), in 64 bits: channel 0 has the spectral IR's phases, the streams seed_c + k of two channels
+ *      never meet, and none meets the ears' side seed 0x5EED0EA2 + k;
+ *      phi_{c,k} = 2 pi (splitmix64(seed_c + k) >> 40) 2^-24;
+ *   2. the spectrum of (c, band b) is exp(i phi_{c,k}) on the band's bins, cosine and sine formed in double and rounded to float once;
+ *   3. r_{c,b} = its real inverse transform (the spectral IR's inverse passes);
+ *   4. g_{c,b} = sqrt(N / sum_{n<N} r_{c,b}[n]^2), the sum in double; car_{c,b} = g_{c,b} r_{c,b}: unit mean power over the IR.
+ * Per source, env_b = the source's device-resident band row b (what fs_copy_band_impulse_response copies), whatever flags the
+ * reconstruct had; after fs_set_impulse_response every band row is the installed IR:
+ *   5. m = 0.0f;  for (b = 0; b < B; ++b) m = m + env_b[n] * car_{c,b}[n];      fp32, no contraction, ascending b
+ *      m = m * (1.0f / sqrtf((float)B));
+ *      h_c[n] = m * w_l;      w_l = 1.0f / sqrtf((float)(2 l(c) + 1)), w_0 = 1.0f exactly.
+ * Consequence: h_0 has the same bits as h_L of the two-ear reverb with an ear set of radius_cm = 0 on the same band rows.
+ * The signal: a point source is mono, as in the ambisonic renderer — d(n) = 0.5f * (in[2n] + in[2n + 1]) is what the source's
+ * history holds.  The callback gives out(s, c) = (h_c * u)[s], u = the history followed by this block's d; interleaved by sample,
+ * element s * C + c, like the ambisonic renderer's rows.  Unlike fs_reverb_process_batch the output is NOT clamped (a bus is
+ * summed and decoded before it reaches a converter; the +-1 clamp is the reference's stereo callback's), there is no bypass row
+ * (no apply_reverb), and flags must be 0 (FS_REVERB_LITERAL_TAIL is a reference quirk of the stereo path).
+ * The engine is the partitioned one: channels 2q and 2q + 1 ride in one complex IR, G_{q,p} = FFT_N(h_{2q} + i h_{2q+1}) per
+ * partition p, P = ceil(C / 2) pairs (at odd C the last pair's imaginary part is zero); the mono window is transformed once,
+ * every window spectrum is read once for all P pairs, and each pair's inverse gives channel 2q in its real and channel 2q + 1 in
+ * its imaginary part.  All of fs_reverb_set_crossfade holds with "the IR" read as the C-tuple.
+ *
+ * fs_reverb_soundfield_set (game thread, never concurrent with a callback; order -1: clear) builds [C][B][carrier_stride] on the
+ * compute stream and waits for it (32 MB at order 3, 8 bands and one second).  The band edges in force must give every band a bin
+ * (FS_FLAG_SPECTRAL_IR's condition and text).  Installing the order already installed is FS_OK and changes nothing; clearing, or
+ * installing another order, is FS_ERR_INVALID_ARGUMENT while a source is initialised with the soundfield.  fs_set_band_edges
+ * with a set installed rebuilds it, and every soundfield source takes again at its next callback (through its crossfade, if it
+ * has one).  fs_reverb_soundfield_info: the order installed (-1: none).
+ * fs_reverb_set_soundfield records the choice like fs_reverb_set_ears: it takes effect at the source's next fs_reverb_init, which
+ * is FS_ERR_INVALID_ARGUMENT with the soundfield on when the source's engine is not FS_REVERB_ENGINE_PARTITIONED, when no set is
+ * installed, or when ears are on as well (the message says which).  That init allocates everything — [P][K][N] spectra per IR copy
+ * and the state of one mono window — so the callback allocates nothing.
+ * fs_reverb_soundfield_process_batch: the rules of fs_reverb_process_batch, read for rows of F * C floats.
+ *     in  [count][frame_size * 2]  interleaved stereo, host; row i belongs to sources[i]
+ *     out [count][frame_size * C]  or NULL
+ *     mix [frame_size * C]         or NULL; out == NULL && mix == NULL is FS_ERR_INVALID_ARGUMENT
+ *   One set of launches whatever the count; 1 <= count <= FS_MAX_REVERB_BATCH and no handle twice; every source initialised with
+ *   the soundfield at one frame size, else FS_ERR_INVALID_ARGUMENT — as is a soundfield source listed in fs_reverb_process or
+ *   fs_reverb_process_batch.  A refused call changes nothing.  A source gives the same bits alone, in any batch and in a permuted
+ *   batch; mix is the fp32 sum in list order, computed on the device, and with out == NULL only mix comes back — at order 3 a row
+ *   of out is 8 times a stereo row, so a host that wants the bus asks for mix alone and adds it to the ambisonic renderer's mix.
+ *   Reverb stream, ONE audio render thread, the per-source lock held only while work is enqueued; staging of its own, and a call of
+ *   a shape the context has seen allocates nothing.
+ * LATENCY: the ambisonic voices are late by (T - 1) / 2 samples and this reverb is not.  Aligning the two stays the host's, as the
+ * direct renderer's text says for `delay`.
+ * fs_reverb_copy_soundfield_impulse_responses (game thread, ordered like fs_copy_band_impulse_response; needs an installed set,
+ * not fs_reverb_init) copies h_c, c < C, of the source's newest device-resident IR into out [C][n], n = fs_num_samples — for hosts
+ * with a convolver of their own.  Not here: a directional late field, a decoder or rotator, the direct engine, per-source carrier
+ * sets, orders above 3. */
+int fs_reverb_soundfield_set(fs_context* ctx, int32_t order /* 0 .. FS_MAX_AMBISONIC_ORDER; -1: clear */);
+int fs_reverb_soundfield_info(fs_context* ctx, int32_t* order, int32_t* installed); /* any pointer may be NULL */
+int fs_reverb_set_soundfield(fs_context* ctx, fs_source src, int32_t on);
+int fs_reverb_copy_soundfield_impulse_responses(fs_context* ctx, fs_source src, float* out /* [C][n] */, int32_t n);
+int fs_reverb_soundfield_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in /* [count][F * 2] */,
+                                       float* out /* [count][F * C] or NULL */, uint32_t flags /* 0 */, float* mix /* [F * C] or NULL */);
 
 /* ---- row f4: frequency-dependent material response of one audio block ------------------------------------
  *      UMaterialAcousticProcessor::ApplyMaterialFD (Private/MaterialAcousticProcessor.cpp:8-107, MAP.cpp):
