@@ -64,6 +64,8 @@ EXPORTS = [
     "fs_reflection2_params_default", "fs_update_reflection2_paths",
     "fs_diffraction2_params_default", "fs_update_diffraction2_paths",
     "fs_mixed_params_default", "fs_update_mixed_paths",
+    "fs_pathing_set_probes", "fs_pathing_bake_params_default", "fs_pathing_bake", "fs_pathing_info", "fs_pathing_copy_graph",
+    "fs_pathing_params_default", "fs_update_pathing_paths",
     "fs_direct_band_kernels", "fs_direct_render_init", "fs_direct_render_release", "fs_direct_render_process_batch",
     "fs_reflection_render_init", "fs_reflection_render_release", "fs_reflection_render_process_batch",
     "fs_hrtf_set", "fs_hrtf_info", "fs_hrtf_spherical_head",
@@ -113,6 +115,16 @@ MAX_MIXED_BATCH = 256
 MIXED_OVERFLOW = 1
 MIXED_NEAR_OVERFLOW = 2
 MIXED_VOICE_TAG = 0xC0000000   # a mixed voice's key: 0xC0000000 | (((m * 2654435761 + 4 (2 (4 i + j) + end)) mod 2^32) >> 2)
+MAX_PATHING_PROBES = 1024
+MAX_PATHING_NODES = 16
+MAX_PATHING_BATCH = 256
+PATHING_MIN_EDGE = 1.0
+PATHING_MAX_LENGTH = 1048576.0
+PATHING_FOUND = 1
+PATHING_DIRECT = 2
+PATHING_STALE = 4
+PATHING_NO_PROBE = 0xFFFFFFFF
+PATHING_VOICE_KEY = 0x80000003   # a pathing voice's key: a first-order diffraction key 0x80000000 | (4 triangle + edge) never ends in binary 11
 DIRECT_RENDER_MAX_TAPS = 2047
 MAX_REFLECTION_VOICES = 32
 MAX_REFLECTION_RENDER_BATCH = 256
@@ -468,6 +480,43 @@ class MixedRow(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("near", "candidates", "confirmed", "found", "returned", "flags")]
 
 
+class PathingBakeParams(C.Structure):
+    """fs_pathing_bake_params (include/frequensee.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_edge", C.c_float), ("step", C.c_float)]
+
+
+class PathingParams(C.Structure):
+    """fs_pathing_params (include/frequensee.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("validate", C.c_int32),
+        ("max_attach", C.c_float),
+        ("max_length", C.c_float),
+        ("step", C.c_float),
+        ("pullback", C.c_float),
+        ("dist_divisor", C.c_float),
+        ("sound_speed", C.c_float),
+    ]
+
+
+class PathingPath(C.Structure):
+    """fs_pathing_path (include/frequensee.h): one source's route through the probe graph, an array element (no struct_size)"""
+    _fields_ = [
+        ("length", C.c_float),
+        ("delay", C.c_float),
+        ("detour", C.c_float),
+        ("distance", C.c_float),
+        ("direction", C.c_float * 3),
+        ("departure", C.c_float * 3),
+        ("hops", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("first_probe", C.c_uint32),
+        ("last_probe", C.c_uint32),
+        ("probes", C.c_uint32 * MAX_PATHING_NODES),
+        ("gain", C.c_float * MAX_BANDS),
+    ]
+
+
 class DirectRenderTarget(C.Structure):
     """fs_direct_render_target (include/frequensee.h): one source's target of a callback, an array element (no struct_size)"""
     _fields_ = [
@@ -667,6 +716,13 @@ def load():
         "fs_update_diffraction2_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(Diffraction2Params), C.c_void_p, C.c_void_p]),
         "fs_mixed_params_default": (None, [C.POINTER(MixedParams)]),
         "fs_update_mixed_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(MixedParams), C.c_void_p, C.c_void_p]),
+        "fs_pathing_set_probes": (C.c_int, [vp, C.c_void_p, i32]),
+        "fs_pathing_bake_params_default": (None, [C.POINTER(PathingBakeParams)]),
+        "fs_pathing_bake": (C.c_int, [vp, C.POINTER(PathingBakeParams)]),
+        "fs_pathing_info": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "fs_pathing_copy_graph": (C.c_int, [vp, C.c_void_p, i32]),
+        "fs_pathing_params_default": (None, [C.POINTER(PathingParams)]),
+        "fs_update_pathing_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(PathingParams), C.c_void_p]),
         "fs_direct_band_kernels": (C.c_int, [i32, f32p, i32, i32, f32p]),
         "fs_direct_render_init": (C.c_int, [vp, i32, i32, i32, C.c_float]),
         "fs_direct_render_release": (C.c_int, [vp, i32]),
@@ -738,6 +794,14 @@ def default_diffraction2_params(**kw) -> Diffraction2Params:
 
 def default_mixed_params(**kw) -> MixedParams:
     return _defaults(MixedParams, "fs_mixed_params_default", kw)
+
+
+def default_pathing_bake_params(**kw) -> PathingBakeParams:
+    return _defaults(PathingBakeParams, "fs_pathing_bake_params_default", kw)
+
+
+def default_pathing_params(**kw) -> PathingParams:
+    return _defaults(PathingParams, "fs_pathing_params_default", kw)
 
 
 def default_params(**kw) -> Params:

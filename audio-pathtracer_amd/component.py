@@ -490,6 +490,49 @@ class Context:
         return self._rows_and_paths(self.lib.fs_update_mixed_paths, _capi.default_mixed_params(**params), self.MIXED_ROW_DTYPE, self.MIXED_DTYPE,
                                     sources)
 
+    # ---- pathing: round several corners by a probe graph ----
+    PATHING_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("detour", np.float32), ("distance", np.float32),
+                              ("direction", np.float32, (3,)), ("departure", np.float32, (3,)), ("hops", np.uint32), ("flags", np.uint32),
+                              ("first_probe", np.uint32), ("last_probe", np.uint32), ("probes", np.uint32, (_capi.MAX_PATHING_NODES,)),
+                              ("gain", np.float32, (_capi.MAX_BANDS,))])
+
+    def pathing_set_probes(self, xyz=None):
+        """fs_pathing_set_probes: the probe set, [count][3] points in free air (cm); None or an empty array clears it.  Drops any bake"""
+        a = np.zeros((0, 3), np.float32) if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        self.check(self.lib.fs_pathing_set_probes(self.h, a.ctypes.data if a.size else None, int(a.shape[0])))
+
+    def pathing_bake(self, **params):
+        """fs_pathing_bake: which pairs of probes see each other; params = the fields of fs_pathing_bake_params (max_edge, step).
+        Returns the number of undirected edges"""
+        p = _capi.default_pathing_bake_params(**params)
+        self.check(self.lib.fs_pathing_bake(self.h, C.byref(p)))
+        return self.pathing_info()["edges"]
+
+    def pathing_info(self):
+        """fs_pathing_info: dict(probes, edges, baked, scene_changed)"""
+        v = [C.c_int32() for _ in range(4)]
+        self.check(self.lib.fs_pathing_info(self.h, *[C.byref(x) for x in v]))
+        return dict(probes=v[0].value, edges=v[1].value, baked=bool(v[2].value), scene_changed=bool(v[3].value))
+
+    def pathing_graph(self):
+        """fs_pathing_copy_graph: the baked graph as uint32 [N][ceil(N / 32)], bit (j & 31) of word (j >> 5) of row i = {i, j} is an edge"""
+        n = self.pathing_info()["probes"]
+        out = np.zeros((n, (n + 31) // 32), np.uint32)
+        self.check(self.lib.fs_pathing_copy_graph(self.h, out.ctypes.data if out.size else None, int(out.size)))
+        return out
+
+    def pathing_paths(self, sources, **params):
+        """fs_update_pathing_paths: one row per listed source as a structured array — length (cm), delay (s), detour, distance,
+        direction (from the listener towards the first probe), departure (from the source towards the last), hops, flags
+        (PATHING_FOUND | PATHING_DIRECT | PATHING_STALE), first_probe, last_probe, probes [16] from the listener's end, gain [8];
+        params = the fields of fs_pathing_params (validate, max_attach, max_length, step, pullback, dist_divisor, sound_speed)"""
+        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        p = _capi.default_pathing_params(**params)
+        out = np.zeros(srcs.shape[0], dtype=self.PATHING_DTYPE)
+        self.check(self.lib.fs_update_pathing_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
+                                                    out.ctypes.data if out.size else None))
+        return out
+
     # ---- the audio callbacks: what the three *_process_batch mirrors share ----
     def _callback_open(self, sources, blocks, frames, want_out, want_mix):
         """the opening of a callback: (handles, count, blocks [count][frame_size * 2], out or None, mix or None); frames = the
@@ -1185,6 +1228,28 @@ class AudioRayTracingSubsystem:
         parts = [self.ctx.mixed_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
         return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
 
+    def SetPathingProbes(self, xyz=None, **bake_params):
+        """the probe graph of the registered geometry: the probes (Context.pathing_set_probes) and, with any, the bake
+        (Context.pathing_bake); returns the number of edges.  Bake again when a door has moved (PathingInfo()["scene_changed"])"""
+        self.ctx.pathing_set_probes(xyz)
+        if not self.ctx.pathing_info()["probes"]:
+            return 0
+        self._commit()
+        return self.ctx.pathing_bake(**bake_params)
+
+    def PathingInfo(self):
+        return self.ctx.pathing_info()
+
+    def UpdatePathingPaths(self, **params):
+        """the route through the probe graph of all active sources: row i for ActiveSources[i] (Context.pathing_paths; more than
+        256 sources take one call per 256)"""
+        srcs = [s._src for s in self.ActiveSources]
+        if not srcs:
+            return np.zeros(0, dtype=Context.PATHING_DTYPE)
+        self._commit()
+        step = _capi.MAX_PATHING_BATCH
+        return np.concatenate([self.ctx.pathing_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)])
+
     def SetPipelining(self, depth):
         """fs_set_pipelining: Tick then updates the sources one after the other like the reference's loop (ARTS.cpp:60-68),
         streamed — every call launches one kernel that plans this source's frame, walks the previous source's and
@@ -1380,7 +1445,8 @@ class FrequenSeeAudioReflectionPlugin:
         diffraction key (0x80000000 | (4 triangle + edge)) of a scene of fewer than 2^28 triangles"""
         return _capi.MIXED_VOICE_TAG | (((int(triangle[0]) * 2654435761 + 4 * (2 * (4 * int(triangle[1]) + int(edge)) + int(end))) & 0xFFFFFFFF) >> 2)
 
-    def Voices(self, row, paths, right=None, reference_length=None, diffraction=None, second=None, diffraction2=None, mixed=None):
+    def Voices(self, row, paths, right=None, reference_length=None, diffraction=None, second=None, diffraction2=None, mixed=None,
+               pathing=None):
         """one source's entries from its UpdateReflectionPaths result (row: its counts, paths: its path array), over the first
         row["returned"] paths: key = triangle, band_gain = reflectance, delay = the path's arrival time less the filter's own
         latency of (Taps - 1) / 2 samples, not below 0.  channel_gain = (1, 1); with `right` (the listener's unit right vector) the
@@ -1395,8 +1461,11 @@ class FrequenSeeAudioReflectionPlugin:
         one voice per returned path round two edges — band_gain = gain, key = Diffraction2Key(triangle, edge); on colliding keys
         the earlier in the row is kept likewise.  mixed = (row, paths) of the same source from UpdateMixedPaths appends, after
         those, one voice per returned path off a reflector and round an edge — band_gain = gain, key = MixedKey(triangle, edge,
-        end), colliding keys likewise; with it a diffraction path's triangle must stay below 2^28, which is checked."""
-        entries = self._path_entries(row, paths, diffraction, second, diffraction2, mixed)
+        end), colliding keys likewise; with it a diffraction path's triangle must stay below 2^28, which is checked.  pathing = the
+        source's row of UpdatePathingPaths appends, last, one voice if the row is FOUND and not DIRECT — band_gain = gain, delay,
+        pan (from `direction`, towards the first probe) and distance law as for a diffraction path, key = PATHING_VOICE_KEY
+        (0x80000003: no diffraction key, whose low bits are an edge 0 .. 2)."""
+        entries = self._path_entries(row, paths, diffraction, second, diffraction2, mixed, pathing)
         v = np.zeros(len(entries), dtype=Context.REFLECTION_VOICE_DTYPE)
         latency = ((self.Taps - 1) // 2) / float(self.ctx.cfg.sample_rate)
         r = None if right is None else np.asarray(right, np.float64).reshape(3)
@@ -1413,7 +1482,7 @@ class FrequenSeeAudioReflectionPlugin:
             o["channel_gain"] = left_right
         return v
 
-    def _path_entries(self, row, paths, diffraction=None, second=None, diffraction2=None, mixed=None):
+    def _path_entries(self, row, paths, diffraction=None, second=None, diffraction2=None, mixed=None, pathing=None):
         """what Voices() keeps of a source's path records, in its order, as (key, path record, band gains): the keys, their range
         checks and the dropping of colliding keys as Voices() documents them"""
         n = int(row["returned"])
@@ -1439,19 +1508,22 @@ class FrequenSeeAudioReflectionPlugin:
                     continue
                 seen.add(key)
             kept.append((key, p, p["gain"] if n <= i < n + m or i >= n + m + k else p["reflectance"]))
+        if pathing is not None and int(pathing["flags"]) & (_capi.PATHING_FOUND | _capi.PATHING_DIRECT) == _capi.PATHING_FOUND:
+            kept.append((_capi.PATHING_VOICE_KEY, pathing, pathing["gain"]))
         return kept
 
     def ProcessAudio(self, components, buffers, rows, paths, right=None, reference_length=None, want_out=True, want_mix=False,
-                     diffraction=None, second=None, diffraction2=None, mixed=None):
+                     diffraction=None, second=None, diffraction2=None, mixed=None, pathing=None):
         """buffers[i] is components[i]'s block, rows[i] / paths[i] its results of UpdateReflectionPaths; diffraction = the (rows,
         paths) of UpdateDiffractionPaths, second = the (rows, paths) of UpdateReflection2Paths, diffraction2 = the (rows, paths) of
-        UpdateDiffraction2Paths, mixed = the (rows, paths) of UpdateMixedPaths, or None.  Returns what
-        Context.reflection_render_process_batch does."""
+        UpdateDiffraction2Paths, mixed = the (rows, paths) of UpdateMixedPaths, pathing = the rows of UpdatePathingPaths, or None.
+        Returns what Context.reflection_render_process_batch does."""
         voices = [self.Voices(rows[i], paths[i], right, reference_length,
                               None if diffraction is None else (diffraction[0][i], diffraction[1][i]),
                               None if second is None else (second[0][i], second[1][i]),
                               None if diffraction2 is None else (diffraction2[0][i], diffraction2[1][i]),
-                              None if mixed is None else (mixed[0][i], mixed[1][i])) for i in range(len(components))]
+                              None if mixed is None else (mixed[0][i], mixed[1][i]),
+                              None if pathing is None else pathing[i]) for i in range(len(components))]
         return self.ctx.reflection_render_process_batch([c._src for c in components], buffers, voices,
                                                         want_out=want_out, want_mix=want_mix)
 
@@ -1478,7 +1550,7 @@ class FrequenSeeAudioBinauralPlugin(FrequenSeeAudioReflectionPlugin):
         self.ctx.binaural_render_release(component._src)
 
     def Voices(self, row, paths, forward, right, reference_length=None, direct=None, diffraction=None, second=None, diffraction2=None,
-               mixed=None):
+               mixed=None, pathing=None):
         """one source's entries: keys, delays (less the band filter's latency of (Taps - 1) / 2 samples, not below 0) and band
         gains exactly as FrequenSeeAudioReflectionPlugin.Voices builds them, from the same arguments; gain = min(1,
         reference_length / length) with reference_length (cm), else 1; direction = the path's arrival direction d in the head
@@ -1486,7 +1558,8 @@ class FrequenSeeAudioBinauralPlugin(FrequenSeeAudioReflectionPlugin):
         = +x and right = +y that is up = +z.  direct = (the source's row of UpdateDirectPaths, the vector from the listener to the
         source in world space, any length but zero) puts the direct sound in front as one more voice: key = DirectKey (0x1FFFFFFF:
         a triangle index no scene of fewer than 2^29 - 1 triangles has, which is checked against the first-order keys), band_gain =
-        transmission, length = distance."""
+        transmission, length = distance.  pathing = the source's row of UpdatePathingPaths: one more voice, as the reflection plugin
+        appends it, heard from the row's `direction`."""
         f = np.asarray(forward, np.float64).reshape(3)
         r = np.asarray(right, np.float64).reshape(3)
         up = np.array([f[1] * r[2] - f[2] * r[1], f[2] * r[0] - f[0] * r[2], f[0] * r[1] - f[1] * r[0]])
@@ -1495,7 +1568,7 @@ class FrequenSeeAudioBinauralPlugin(FrequenSeeAudioReflectionPlugin):
         if direct is not None:
             d_row, to_source = direct
             entries.append((self.DirectKey, d_row["delay"], d_row["transmission"], d_row["distance"], to_source))
-        for key, p, band_gain in self._path_entries(row, paths, diffraction, second, diffraction2, mixed):
+        for key, p, band_gain in self._path_entries(row, paths, diffraction, second, diffraction2, mixed, pathing):
             if direct is not None and key == self.DirectKey:
                 raise ValueError("Voices: triangle index 2^29 - 1: its key is the direct sound's")
             entries.append((key, p["delay"], band_gain, p["length"], p["direction"]))
@@ -1510,7 +1583,7 @@ class FrequenSeeAudioBinauralPlugin(FrequenSeeAudioReflectionPlugin):
         return v
 
     def ProcessAudio(self, components, buffers, rows, paths, forward, right, reference_length=None, want_out=True, want_mix=False,
-                     direct=None, diffraction=None, second=None, diffraction2=None, mixed=None):
+                     direct=None, diffraction=None, second=None, diffraction2=None, mixed=None, pathing=None):
         """buffers[i] is components[i]'s block, rows[i] / paths[i] its results of UpdateReflectionPaths; direct = (the rows of
         UpdateDirectPaths, the listener's location) or None; the other path kinds as FrequenSeeAudioReflectionPlugin.ProcessAudio
         takes them.  Returns what Context.binaural_render_process_batch does."""
@@ -1520,7 +1593,7 @@ class FrequenSeeAudioBinauralPlugin(FrequenSeeAudioReflectionPlugin):
         for i, c in enumerate(components):
             d = None if direct is None else (direct[0][i], np.asarray(c.GetComponentLocation(), np.float64) - np.asarray(direct[1], np.float64))
             voices.append(self.Voices(rows[i], paths[i], forward, right, reference_length, d, pick(diffraction, i), pick(second, i),
-                                      pick(diffraction2, i), pick(mixed, i)))
+                                      pick(diffraction2, i), pick(mixed, i), None if pathing is None else pathing[i]))
         return self._render(components, buffers, voices, want_out, want_mix)
 
     def _render(self, components, buffers, voices, want_out, want_mix):

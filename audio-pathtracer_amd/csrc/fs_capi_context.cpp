@@ -657,7 +657,9 @@ int fs_context_destroy(fs_context* ctx) {
         if (ctx->fft_graph) (void)hipGraphExecDestroy(ctx->fft_graph);
         if (ctx->h_fft_stage) (void)hipHostFree(ctx->h_fft_stage);
         for (float2* w : ctx->d_rev_tw) if (w) (void)hipFree(w);
-        for (PathStaging* st : {&ctx->direct_stage, &ctx->reflect_stage, &ctx->diffract_stage, &ctx->reflect2_stage, &ctx->diffract2_stage, &ctx->mixed_stage}) st->release();
+        for (PathStaging* st : {&ctx->direct_stage, &ctx->reflect_stage, &ctx->diffract_stage, &ctx->reflect2_stage, &ctx->diffract2_stage, &ctx->mixed_stage,
+                                 &ctx->pathing_stage}) st->release();
+        if (ctx->pathing.d_block) (void)hipFree(ctx->pathing.d_block);
         if (ctx->d_direct_off) (void)hipFree(ctx->d_direct_off);
         for (CallbackStage* st : {&ctx->rev_stage, &ctx->dr_stage, &ctx->rr_stage, &ctx->br_stage, &ctx->ar_stage, &ctx->sf_stage}) st->release();
         if (ctx->d_hrtf) (void)hipFree(ctx->d_hrtf);

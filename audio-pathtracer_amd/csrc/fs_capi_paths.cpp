@@ -1,8 +1,8 @@
 // fs_capi_paths.cpp — the path queries of a tick, each one call for all its sources: fs_update_direct_paths (fs_direct.hip) with the
 // sample offsets it uses, fs_update_reflection_paths (fs_reflect.hip), fs_update_diffraction_paths (fs_diffract.hip),
 // fs_update_reflection2_paths (fs_reflect2.hip), fs_update_diffraction2_paths (fs_diffract2.hip) and fs_update_mixed_paths
-// (fs_mixed.hip), their defaults, and what the
-// six share on the host: the prologue, the staging and its layout, the packing of the sources and, for the five that return rows
+// (fs_mixed.hip), their defaults, the probe graph's calls (fs_pathing_*, fs_update_pathing_paths: fs_pathing.hip), and what the
+// queries share on the host: the prologue, the staging and its layout, the packing of the sources and, for the five that return rows
 // and paths, one driver from the argument checks to the copy back (update_rows_paths).
 #include "fs_context.hpp"
 
@@ -33,6 +33,11 @@ static_assert(offsetof(fs_mixed_path, detour) == 8 && offsetof(fs_mixed_path, be
                   offsetof(fs_mixed_path, material) == 72 && offsetof(fs_mixed_path, gain) == 80,
               "fs_mixed_path: the offsets of include/frequensee.h");
 static_assert(sizeof(fs_mixed_row) == 24, "fs_mixed_row: six words");
+static_assert(sizeof(fs_pathing_bake_params) == 12 && sizeof(fs_pathing_params) == 32, "the pathing params: three and eight words");
+static_assert(sizeof(fs_pathing_path) == 152 && offsetof(fs_pathing_path, distance) == 12 && offsetof(fs_pathing_path, direction) == 16 &&
+                  offsetof(fs_pathing_path, departure) == 28 && offsetof(fs_pathing_path, hops) == 40 && offsetof(fs_pathing_path, flags) == 44 &&
+                  offsetof(fs_pathing_path, probes) == 56 && offsetof(fs_pathing_path, gain) == 120,
+              "fs_pathing_path: the offsets of include/frequensee.h");
 
 int PathStaging::grow(fs_context* ctx, int count, const PathLayout& pinned_layout, const PathLayout& device_layout) {
     pinned = pinned_layout;
@@ -187,6 +192,24 @@ uint32_t* staged_words(const PathStaging& st, int seg) { return reinterpret_cast
 NearPairLists staged_pair_lists(const PathStaging& st, int32_t max_near, int32_t max_candidates) {
     return NearPairLists{staged_words(st, kSegCounters), staged_words(st, kSegCounters) + st.cap, staged_words(st, kSegNear), staged_words(st, kSegCand),
                          max_near, max_candidates};
+}
+
+// the probe set's device block (fs_context::Pathing), laid out for FS_MAX_PATHING_PROBES: probes | upper | graph | dL | d | pred
+constexpr size_t kPathingMatrixBytes = sizeof(uint32_t) * (size_t)FS_MAX_PATHING_PROBES * (size_t)kPathingStrideWords;
+constexpr size_t kPathingBlockBytes = sizeof(float4) * (size_t)FS_MAX_PATHING_PROBES + 2 * kPathingMatrixBytes +
+                                      (2 * sizeof(float) + sizeof(uint32_t)) * (size_t)FS_MAX_PATHING_PROBES;
+PathingSet pathing_set(const fs_context* ctx) {
+    PathingSet g{};
+    char* b = ctx->pathing.d_block;
+    g.probes = reinterpret_cast<const float4*>(b); b += sizeof(float4) * (size_t)FS_MAX_PATHING_PROBES;
+    g.upper = reinterpret_cast<uint32_t*>(b); b += kPathingMatrixBytes;
+    g.graph = reinterpret_cast<uint32_t*>(b); b += kPathingMatrixBytes;
+    g.dL = reinterpret_cast<float*>(b); b += sizeof(float) * (size_t)FS_MAX_PATHING_PROBES;
+    g.d = reinterpret_cast<float*>(b); b += sizeof(float) * (size_t)FS_MAX_PATHING_PROBES;
+    g.pred = reinterpret_cast<uint32_t*>(b);
+    g.n = (int32_t)(ctx->pathing.xyz.size() / 3);
+    g.stride = 2 * ((g.n + 63) / 64);
+    return g;
 }
 
 }  // namespace
@@ -461,6 +484,142 @@ int fs_update_mixed_paths(fs_context* ctx, const fs_source* sources, int32_t cou
         mp.merge = p.merge;
         band_factors(ctx, p.sound_speed, p.dist_divisor, mp.k, nullptr);
     });
+}
+
+// ---- pathing: round several corners by a probe graph -------------------------------------------------------------------------
+void fs_pathing_bake_params_default(fs_pathing_bake_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = sizeof(fs_pathing_bake_params);
+    p->max_edge = 1000.f;
+    p->step = 0.1f;
+}
+
+void fs_pathing_params_default(fs_pathing_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = sizeof(fs_pathing_params);
+    p->validate = 1;
+    p->max_attach = 1000.f;
+    p->max_length = 10000.f;
+    p->step = 0.1f;
+    p->pullback = 0.1f;
+    p->dist_divisor = 1000.f;
+    p->sound_speed = 343.f;
+}
+
+int fs_pathing_set_probes(fs_context* ctx, const float* xyz, int32_t count) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (count < 0 || count > FS_MAX_PATHING_PROBES) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (0 .. FS_MAX_PATHING_PROBES)");
+    if (!xyz) count = 0;
+    for (size_t i = 0; i < 3 * (size_t)count; ++i)
+        if (!std::isfinite(xyz[i])) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "non-finite probe coordinate");
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    fs_context::Pathing& pa = ctx->pathing;
+    if (count > 0) {
+        FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+        if (!pa.d_block) FS_HIP(ctx, hipMalloc((void**)&pa.d_block, kPathingBlockBytes));
+        std::vector<float4> packed((size_t)count);
+        for (int32_t k = 0; k < count; ++k) packed[(size_t)k] = make_float4(xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2], 0.0f);
+        // (every earlier call has been waited for: nothing in the stream reads the old probes)
+        FS_HIP(ctx, hipMemcpy(pa.d_block, packed.data(), sizeof(float4) * (size_t)count, hipMemcpyHostToDevice));
+    }
+    pa.xyz.assign(xyz, xyz + 3 * (size_t)count);
+    pa.graph.clear();
+    pa.edges = 0;
+    pa.baked = false;
+    return FS_OK;
+}
+
+int fs_pathing_bake(fs_context* ctx, const fs_pathing_bake_params* p) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    fs_pathing_bake_params def;
+    if (!params_or_default(p, def, fs_pathing_bake_params_default)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_pathing_bake_params.struct_size mismatch");
+    if (!finite_above_zero(p->max_edge) || !finite_at_least_zero(p->step)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad pathing bake params");
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    fs_context::Pathing& pa = ctx->pathing;
+    if (pa.xyz.empty()) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "no probes (fs_pathing_set_probes)");
+    { int pr = paths_prologue(ctx, nullptr, 0); if (pr) return pr; }
+    PathingBakeKParams bp{};
+    bp.h.lis_object = FS_NO_OBJECT;
+    bp.h.num_bands = ctx->cfg.num_bands;
+    bp.h.step = p->step;
+    bp.g = pathing_set(ctx);
+    bp.max_edge = p->max_edge;
+    const int n = bp.g.n, words = (n + 31) / 32;
+    pa.baked = false;
+    std::vector<uint32_t> wide((size_t)n * (size_t)bp.g.stride);
+    launch_pathing_bake(ctx->scene, bp, ctx->stream);
+    FS_HIP(ctx, hipGetLastError());
+    FS_HIP(ctx, hipMemcpyAsync(wide.data(), bp.g.graph, sizeof(uint32_t) * wide.size(), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    pa.graph.resize((size_t)n * (size_t)words);
+    size_t bits = 0;
+    for (int i = 0; i < n; ++i)
+        for (int w = 0; w < words; ++w) {
+            const uint32_t v = wide[(size_t)i * (size_t)bp.g.stride + (size_t)w];
+            pa.graph[(size_t)i * (size_t)words + (size_t)w] = v;
+            bits += (size_t)__builtin_popcount(v);
+        }
+    pa.edges = (int32_t)(bits / 2);
+    pa.baked = true;
+    pa.baked_gen = ctx->scene_gen;
+    return FS_OK;
+}
+
+int fs_pathing_info(fs_context* ctx, int32_t* probes, int32_t* edges, int32_t* baked, int32_t* scene_changed) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    const fs_context::Pathing& pa = ctx->pathing;
+    if (probes) *probes = (int32_t)(pa.xyz.size() / 3);
+    if (edges) *edges = pa.baked ? pa.edges : 0;
+    if (baked) *baked = pa.baked ? 1 : 0;
+    if (scene_changed) *scene_changed = pa.baked && pa.baked_gen != ctx->scene_gen ? 1 : 0;
+    return FS_OK;
+}
+
+int fs_pathing_copy_graph(fs_context* ctx, uint32_t* bits, int32_t words) {
+    if (!ctx || !bits) return FS_ERR_INVALID_ARGUMENT;
+    const fs_context::Pathing& pa = ctx->pathing;
+    if (!pa.baked) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "no baked graph (fs_pathing_bake)");
+    if (words < 0 || (size_t)words != pa.graph.size()) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "words is not N ceil(N / 32)");
+    std::memcpy(bits, pa.graph.data(), sizeof(uint32_t) * pa.graph.size());
+    return FS_OK;
+}
+
+int fs_update_pathing_paths(fs_context* ctx, const fs_source* sources, int32_t count, const fs_pathing_params* p, fs_pathing_path* out) {
+    if (!ctx || !sources || !out) return FS_ERR_INVALID_ARGUMENT;
+    if (count < 1 || count > FS_MAX_PATHING_BATCH) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_PATHING_BATCH)");
+    fs_pathing_params def;
+    if (!params_or_default(p, def, fs_pathing_params_default)) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_pathing_params.struct_size mismatch");
+    if ((p->validate != 0 && p->validate != 1) || !finite_above_zero(p->max_attach) ||!finite_above_zero(p->max_length) || p->max_length > FS_PATHING_MAX_LENGTH ||
+        !finite_at_least_zero(p->step) || !finite_at_least_zero(p->pullback) || !finite_above_zero(p->dist_divisor) || !finite_above_zero(p->sound_speed))
+        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "bad pathing params");
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    if (!ctx->pathing.baked) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "no baked graph (fs_pathing_bake)");
+    { int pr = paths_prologue(ctx, sources, count); if (pr) return pr; }
+    PathStaging& st = ctx->pathing_stage;
+    const PathLayout layout{{sizeof(float4), 0, 0, 0, 0, sizeof(fs_pathing_path)}};
+    { int gr = st.grow(ctx, count, layout, layout); if (gr) return gr; }
+    float4* h_src = reinterpret_cast<float4*>(st.host(kSegSources));
+    float4* d_src = reinterpret_cast<float4*>(st.dev(kSegSources));
+    fs_pathing_path* h_out = reinterpret_cast<fs_pathing_path*>(st.host(kSegOut));
+    fs_pathing_path* d_out = reinterpret_cast<fs_pathing_path*>(st.dev(kSegOut));
+    pack_sources(ctx, sources, count, h_src);
+    PathingKParams pp{};
+    pp.h = path_head(ctx, d_src, count, p->step, p->pullback, p->dist_divisor, p->sound_speed);
+    pp.g = pathing_set(ctx);
+    pp.out = d_out;
+    pp.validate = p->validate;
+    pp.max_attach = p->max_attach;
+    pp.max_length = p->max_length;
+    band_factors(ctx, p->sound_speed, p->dist_divisor, pp.k, nullptr);
+    FS_HIP(ctx, hipMemcpyAsync(d_src, h_src, sizeof(float4) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+    launch_pathing_paths(ctx->scene, pp, ctx->stream);
+    FS_HIP(ctx, hipGetLastError());
+    FS_HIP(ctx, hipMemcpyAsync(h_out, d_out, sizeof(fs_pathing_path) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(out, h_out, sizeof(fs_pathing_path) * (size_t)count);
+    return FS_OK;
 }
 
 }  // extern "C"

@@ -101,14 +101,15 @@ int maybe_install_refined(fs_context* ctx) {
     ctx->moved_since_refine = false;
     if (j->T != ctx->T || !ctx->committed) return FS_OK;
     ctx->prebuilt = &j->bvh;
-    const int rc = fs_scene_commit(ctx);
+    const uint64_t gen = ctx->scene_gen;   // a better tree over the same triangles: no change of the scene (fs_pathing_info)
+    int rc = fs_scene_commit(ctx);
     ctx->prebuilt = nullptr;
-    if (rc) return rc;
-    if (moved) {   // (the commit has brought h_xyz up to the world positions; the rest pose is not touched)
+    if (!rc && moved) {   // (the commit has brought h_xyz up to the world positions; the rest pose is not touched)
         const std::vector<float> now = ctx->h_xyz;
-        return update_triangles(ctx, 0, ctx->T, now.data(), false);
+        rc = update_triangles(ctx, 0, ctx->T, now.data(), false);
     }
-    return FS_OK;
+    ctx->scene_gen = gen;
+    return rc;
 }
 
 }  // namespace fsi
@@ -349,6 +350,7 @@ static int finish_commit(fs_context* ctx, size_t scene_bytes) {
     { const int cr = refresh_coop_nodes(ctx, true); if (cr) return cr; }
     { const int vr = refresh_node_view(ctx, true); if (vr) return vr; }
     ctx->committed = true;
+    ctx->scene_gen += 1;
     return FS_OK;
 }
 
@@ -601,6 +603,7 @@ static int update_triangles(fs_context* ctx, int32_t first, int32_t count, const
         FS_HIP(ctx, hipMemcpyAsync(mv->d_rest + 9 * (size_t)first, ctx->d_move, sizeof(float) * 9 * (size_t)count, hipMemcpyDeviceToDevice, ctx->stream));
     FS_HIP(ctx, hipStreamSynchronize(ctx->stream));   // xyz is the caller's memory
     ctx->refit_pending = true;
+    ctx->scene_gen += 1;
     return FS_OK;
 }
 
@@ -742,6 +745,7 @@ int fs_scene_set_object_transforms(fs_context* ctx, const uint32_t* object_ids, 
     FS_HIP(ctx, hipEventRecord(mv->ev_amax, ctx->stream));
     mv->amax_pending = true;
     ctx->refit_pending = true;
+    ctx->scene_gen += 1;
     return FS_OK;
 }
 
@@ -751,7 +755,7 @@ int fs_scene_refit(fs_context* ctx) {
     FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
     if (!ctx->committed) return ctx->fail(FS_ERR_NOT_COMMITTED, "scene not committed");
     ctx->refit_pending = false;
-    if (ctx->bvh.nodes.empty()) return FS_OK;
+    if (ctx->bvh.nodes.empty()) { ctx->scene_gen += 1; return FS_OK; }
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     FS_HIP(ctx, fold_moved_amax(ctx));   // objects moved by transform: the device knows how far
     const float pad = std::max(std::max(0.01f, ctx->amax * 3.8146973e-06f), ctx->bvh.pad);   // as fs_bvh.cpp; never shrinks
@@ -759,7 +763,9 @@ int fs_scene_refit(fs_context* ctx) {
                  (int)ctx->bvh.level_begin.size() - 1, pad, ctx->stream);
     FS_HIP(ctx, hipGetLastError());
     { const int cr = refresh_coop_nodes(ctx, false); if (cr) return cr; }
-    return refresh_node_view(ctx, false);
+    { const int vr = refresh_node_view(ctx, false); if (vr) return vr; }
+    ctx->scene_gen += 1;
+    return FS_OK;
 }
 
 // Debug entry (not in include/frequensee.h; tests/tree_check.py reads the committed tree through it): one array of the

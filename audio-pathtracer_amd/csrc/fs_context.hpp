@@ -441,7 +441,20 @@ struct fs_context {
     // [FS_MAX_DIRECT_SAMPLES][FS_MAX_DIRECT_SAMPLES][3] by n - 1, each uploaded at its first use.
     // diffract_f: the band centres f_b of the edges in force (diffract_f_edges, diffract_f_bands: what they were built from; rebuilt
     // when fs_set_band_edges has changed them), shared by the two diffraction queries.
-    PathStaging direct_stage, reflect_stage, diffract_stage, reflect2_stage, diffract2_stage, mixed_stage;
+    PathStaging direct_stage, reflect_stage, diffract_stage, reflect2_stage, diffract2_stage, mixed_stage, pathing_stage;
+    // Pathing (fs_capi_paths.cpp): the probe set, its device block (allocated by the first fs_pathing_set_probes for
+    // FS_MAX_PATHING_PROBES: probes | upper | graph | dL | d | pred, PathingSet of fs_internal.hpp) and the baked graph's host copy
+    // [n][ceil(n / 32)].  scene_gen counts the commits, triangle updates, refits and object moves of the context; baked_gen is
+    // its value at the bake: fs_pathing_info's scene_changed compares the two, nothing else reads them.
+    struct Pathing {
+        std::vector<float> xyz;
+        char* d_block = nullptr;
+        std::vector<uint32_t> graph;
+        int32_t edges = 0;
+        bool baked = false;
+        uint64_t baked_gen = 0;
+    } pathing;
+    uint64_t scene_gen = 0;
     float* d_direct_off = nullptr;
     uint64_t direct_off_have = 0;
     double diffract_f[FS_MAX_BANDS] = {};

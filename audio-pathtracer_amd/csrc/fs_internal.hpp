@@ -606,6 +606,37 @@ struct MixedKParams {
     float k[FS_MAX_BANDS];      // k_b = 40 f_b / (sound_speed dist_divisor)
 };
 void launch_mixed_paths(const DeviceScene& sc, const MixedKParams& mp, hipStream_t s);
+// fs_pathing.hip (fs_pathing_bake, fs_update_pathing_paths).  The probe set on the device: probes [n] as xyz0; upper and graph, two
+// bit matrices [n][stride] with stride = 2 ceil(n / 64) words (a row is whole 64-bit ballots) — the bake's first kernel writes the
+// pieces of `upper` on and above the diagonal's block, the mirror kernel reads them and writes every word of `graph`; dL [n], d [n]
+// and pred [n] = the listener's attach distances, distances and predecessors of the update in flight.
+constexpr int kPathingStrideWords = 2 * ((FS_MAX_PATHING_PROBES + 63) / 64);
+struct PathingSet {
+    const float4* probes;
+    uint32_t* upper;
+    uint32_t* graph;
+    float* dL;
+    float* d;
+    uint32_t* pred;
+    int32_t n, stride;
+};
+// the bake: h.step is the bake's, both actor ids FS_NO_OBJECT
+struct PathingBakeKParams {
+    PathKHead h;
+    PathingSet g;
+    float max_edge;
+};
+void launch_pathing_bake(const DeviceScene& sc, const PathingBakeKParams& bp, hipStream_t s);
+// the update: h as the other queries' (src on the device), out [count] = the device staging the copy back reads
+struct PathingKParams {
+    PathKHead h;
+    PathingSet g;
+    fs_pathing_path* out;
+    int32_t validate;
+    float max_attach, max_length;
+    float k[FS_MAX_BANDS];      // k_b = 40 f_b / (sound_speed dist_divisor)
+};
+void launch_pathing_paths(const DeviceScene& sc, const PathingKParams& pp, hipStream_t s);
 constexpr int kReverbRing = 65536;   // per-channel history ring (floats), matches kRevRing in the kernels
 // fs_reverb.hip (the reverb callback): one descriptor per row of the call, in list order, read by every kernel of the callback.
 struct ReverbItem {

@@ -235,6 +235,34 @@ public:
     MixedPaths UpdateMixedPaths(const fs_mixed_params* P = nullptr) {
         return UpdateRowsPaths<MixedPaths>(P, fs_mixed_params_default, fs_update_mixed_paths, FS_MAX_MIXED_PATHS, FS_MAX_MIXED_BATCH);
     }
+    // The probe graph (fs_pathing_*): Probes [count][3] in free air, the host's choice (a nav-mesh sample, a grid); the bake links
+    // the pairs that see each other and returns the number of edges.  Bake again when PathingSceneChanged() says that a door has moved.
+    int32_t SetPathingProbes(const std::vector<float>& Probes, const fs_pathing_bake_params* P = nullptr) {
+        Check(fs_pathing_set_probes(Ctx_, Probes.data(), (int32_t)(Probes.size() / 3)));
+        return Probes.size() < 3 ? 0 : BakePathing(P);
+    }
+    int32_t BakePathing(const fs_pathing_bake_params* P = nullptr) {
+        Commit();
+        Check(fs_pathing_bake(Ctx_, P));
+        int32_t Edges = 0;
+        Check(fs_pathing_info(Ctx_, nullptr, &Edges, nullptr, nullptr));
+        return Edges;
+    }
+    bool PathingSceneChanged() const {
+        int32_t Changed = 0;
+        return fs_pathing_info(Ctx_, nullptr, nullptr, nullptr, &Changed) == FS_OK && Changed != 0;
+    }
+    // the route through the probe graph of every active source: row i for ActiveSources[i] (fs_update_pathing_paths)
+    std::vector<fs_pathing_path> UpdatePathingPaths(const fs_pathing_params* P = nullptr) {
+        std::vector<fs_pathing_path> Out(ActiveSources.size());
+        if (Out.empty()) return Out;
+        Commit();
+        std::vector<fs_source> H;
+        for (auto* s : ActiveSources) H.push_back(s->Handle_);
+        for (size_t i = 0; i < H.size(); i += FS_MAX_PATHING_BATCH)
+            Check(fs_update_pathing_paths(Ctx_, H.data() + i, (int32_t)std::min<size_t>(H.size() - i, FS_MAX_PATHING_BATCH), P, Out.data() + i));
+        return Out;
+    }
 private:
     template <typename Result, typename Params, typename Row, typename Path>
     Result UpdateRowsPaths(const Params* P, void (*Defaults)(Params*), int (*Update)(fs_context*, const fs_source*, int32_t, const Params*, Row*, Path*),
@@ -657,6 +685,15 @@ public:
             Keys.push_back(Key);
             Fn(Key, Delay, Gain, Dir, Length);
         }
+    }
+    // The voice of a source's row of UpdatePathingPaths, appended by the host to what Voices returned: true and *Out filled iff the
+    // row is FS_PATHING_FOUND and not FS_PATHING_DIRECT (a source in plain sight is spoken for by the direct sound and the early
+    // paths).  key = FS_PATHING_VOICE_KEY (0x80000003: no diffraction key, whose low bits are an edge 0 .. 2), band_gain = gain,
+    // delay, pan (from `direction`, towards the first probe) and distance law as a diffraction path's
+    bool PathingVoice(const fs_pathing_path& P, fs_reflection_voice* Out, const FVector* Right = nullptr, float ReferenceLength = 0.0f) const {
+        if ((P.flags & (FS_PATHING_FOUND | FS_PATHING_DIRECT)) != FS_PATHING_FOUND) return false;
+        *Out = Voice(FS_PATHING_VOICE_KEY, P.delay, P.gain, P.direction, P.length, Right, ReferenceLength);
+        return true;
     }
     // one voice: the key, the target delay, the band gains, and the pan and distance law of Voices
     fs_reflection_voice Voice(uint32_t Key, float Delay, const float* Gain, const float* Dir, float Length, const FVector* Right,

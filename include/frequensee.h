@@ -63,6 +63,8 @@
  *             fs_reflection2_params_default fs_update_reflection2_paths
  *             fs_diffraction2_params_default fs_update_diffraction2_paths
  *             fs_mixed_params_default fs_update_mixed_paths
+ *             fs_pathing_set_probes fs_pathing_bake_params_default fs_pathing_bake fs_pathing_info fs_pathing_copy_graph
+ *             fs_pathing_params_default fs_update_pathing_paths
  *             fs_direct_band_kernels fs_direct_render_init fs_direct_render_release fs_direct_render_process_batch
  *             fs_reflection_render_init fs_reflection_render_release fs_reflection_render_process_batch
  *             fs_hrtf_set fs_hrtf_info fs_hrtf_spherical_head
@@ -1192,6 +1194,120 @@ void fs_mixed_params_default(fs_mixed_params* p);
 int fs_update_mixed_paths(fs_context* ctx, const fs_source* sources, int32_t count,
                           const fs_mixed_params* params /* NULL = defaults */,
                           fs_mixed_row* rows /* [count] */, fs_mixed_path* paths /* [count][max_paths] */);
+
+/* ---- pathing (EXTENDED): round several corners by a probe graph ------------------------------------------------------------------
+ * A source in the next room but one — down a corridor and through a door, round an S-bend — is answered by none of the six path
+ * queries above, and the traced impulse response has no direction.  The host scatters PROBES in free air (a nav-mesh sample, a
+ * grid); a BAKE finds which pairs see each other; per tick the shortest route listener -> probes -> source gives a length, the
+ * direction the sound arrives from at the listener (which door) and a detour to attenuate by: one more voice per source.
+ * Specified to the bit with the conventions of "direct paths": -ffp-contract=off, every fp32 operation rounded on its own in the
+ * order written, a.b = (a.x b.x + a.y b.y) + a.z b.z, divide and sqrtf correctly rounded, fmaf fused.  chain(o, d, len) is that
+ * section's chain with max_surfaces = 0: it ends `reached` or blocked (at the first triangle that is not an own actor's, or out
+ * of queries).  No random numbers; nothing depends on which builder made the tree, on count or on the order of the sources.
+ *   Probes.  fs_pathing_set_probes copies count points p_0 .. p_{count-1} (cm, finite; 1 .. FS_MAX_PATHING_PROBES) and drops any
+ * bake; count == 0 or xyz == NULL clears the set.  It needs no committed scene.
+ *   Bake.  For every pair i < j: e = p_j - p_i per component, w = sqrtf(e.e).  The pair is a CANDIDATE iff
+ * w >= FS_PATHING_MIN_EDGE && w <= max_edge.  d = e (1.0f / w) per component.  A candidate is an EDGE iff chain(p_i, d, w) reached,
+ * with no own actors (both ids FS_NO_OBJECT) and the bake's step: the ray always runs from the lower index.  The graph is the
+ * symmetric bit matrix [N][ceil(N / 32)]: bit (j & 31) of word (j >> 5) of row i says that {i, j} is an edge; the diagonal and the
+ * padding bits are zero.  `edges` counts undirected edges.  The bake needs a committed scene (FS_ERR_NOT_COMMITTED) and at least
+ * one probe; like fs_update_direct_paths it installs a finished progressive build and runs a pending refit first; it runs on the
+ * compute stream (two launches: the upper triangle, a wave per row and block of 64 columns; the mirror), copies the graph back and
+ * waits; held frames are not flushed; no collective.  fs_pathing_info: probes, edges (0 before a bake), baked (0 / 1) and
+ * scene_changed = 1 iff, since the bake, a commit, fs_scene_update_triangles, fs_scene_refit or fs_scene_set_object_transforms has
+ * succeeded (the library installing a progressive build's better tree over unchanged triangles is none of these); 0 before a
+ * bake.  It is a report: the library itself never looks at it, the host decides when to bake again.
+ *   Update, once per call.  Listener L, its actor id lo.  For every probe k: e = p_k - L, a = sqrtf(e.e); dL[k] = +inf if
+ * a > max_attach; 0 if a == 0; else a if chain(L, e (1.0f / a), a) reached with own actor {lo}, +inf if not.
+ * d is the fixed point of  d[i] = min(dL[i], min over j adjacent to i of c(j, i)),  c(j, i) = d[j] + w_ji, a c > max_length
+ * counting as +inf; w_ji is recomputed as in the bake (it is symmetric: only squares of the components enter).  The fixed point
+ * is UNIQUE and reached from d = dL in at most N rounds in any relaxation order (Jacobi, in place, in parallel: the same bits):
+ * fp32 addition is monotone in each operand, so each round of any order keeps every d[i] between the fixed point and the value
+ * Jacobi has after as many rounds; and with w >= FS_PATHING_MIN_EDGE = 1 and a finite d <= max_length <= FS_PATHING_MAX_LENGTH =
+ * 2^20 (half an ulp of d is at most 2^-5), d + w > d strictly, so a route never repeats a probe, has at most N - 1 edges, and
+ * Jacobi is done after N rounds.  Two fixed points cannot differ: at the probe where they differ with the smallest value v, v is
+ * either dL there (then the other is <= v) or d[j] + w of a neighbour with d[j] < v, on which both agree (then the other is <= v).
+ * pred[i] = LISTENER if d[i] == dL[i], else the smallest adjacent j with c(j, i) == d[i].
+ *   Update, per source at S with actor id so.  g = S - L per component, distance = sqrtf(g.g).  FS_PATHING_DIRECT is set iff
+ * distance == 0 or the centre ray of "direct paths" is free: chain(S, (-g) (1.0f / distance), distance - pullback) reached with own
+ * actors {so, lo}.  Probe k with d[k] < +inf QUALIFIES iff e = p_k - S, a = sqrtf(e.e), a <= max_attach and (a == 0 or
+ * chain(S, e (1.0f / a), a) reached with own actors {so, lo}); total_k = d[k] + a, kept iff total_k <= max_length.  The path is
+ * the smallest total, ties to the smallest k.  None: the row is all-zero bytes except `distance` and the DIRECT bit.  Else
+ * flags |= FS_PATHING_FOUND; length = total; delay = (length / dist_divisor) / sound_speed; detour = length - distance;
+ * last_probe = k; following pred from k to LISTENER visits `hops` probes, the last of them first_probe (the one next to the
+ * listener); with n_0 = first_probe, ..., n_{hops-1} = last_probe, probes[m] = n_m for m < min(hops, FS_MAX_PATHING_NODES) and
+ * FS_PATHING_NO_PROBE beyond.  direction = v (1.0f / |v|) with v = P - L, |v| = sqrtf(v.v), P the first point of the sequence
+ * (n_0, n_1, ..., S) with |v| != 0; zeros if there is none.  departure likewise from S with v = P - S over (n_{hops-1}, ..., n_0, L).
+ * gain[b] = 1.0f / sqrtf(3.0f + k_b detour) with the k_b table of "diffraction paths", 0 beyond num_bands: the barrier estimate of
+ * the whole detour, an estimate a host is free to ignore; no distance law.  With validate != 0 each of the hops - 1 baked legs
+ * {n_m, n_{m+1}} is run again by the bake's rule with this call's step, from the lower index; a blocked one sets FS_PATHING_STALE
+ * and the path is returned all the same (a door has shut since the bake: the host mutes the voice or bakes again).
+ *   Out of scope: string-pulling (the route runs through the probes, so length and detour are upper bounds of the taut route's)
+ * and more than one path per source.
+ *   The key a host gives the voice of such a path is FS_PATHING_VOICE_KEY = 0x80000003: a first-order diffraction key is
+ * 0x80000000 | (4 triangle + edge) with edge <= 2, so its low bits are never 11; the mixed keys start at 0xC0000000, the other
+ * kinds stay below 0x80000000.  A host renders one voice per FOUND row that is not DIRECT (while the source is in plain sight the
+ * direct sound and the early paths speak for it).
+ *   Errors.  FS_ERR_INVALID_ARGUMENT: ctx NULL; a count outside its range; a non-finite probe; a struct_size that is not this
+ * library's; max_edge, max_attach or max_length not finite and > 0, max_length > FS_PATHING_MAX_LENGTH, step or pullback not finite
+ * and >= 0, dist_divisor or sound_speed not finite and > 0; sources or out NULL; a bake without probes; an update or
+ * fs_pathing_copy_graph before a bake (also after fs_pathing_set_probes dropped it), or with words != N ceil(N / 32).
+ * FS_ERR_NO_DEVICE, FS_ERR_BAD_HANDLE, FS_ERR_NOT_COMMITTED as elsewhere.  A handle may appear twice.  A refused call writes nothing
+ * and changes nothing.
+ *   Ordering and cost of an update: as fs_update_direct_paths — the source table's upload, THREE launches on the compute stream (the
+ * listener's attach chains, a thread per probe; the relaxation, one workgroup with the probes and d in LDS and a hard cap of N
+ * rounds, then pred; the sources', one workgroup per row), one copy back and one wait, whatever count is.  The probe set's device arrays are
+ * allocated by the first fs_pathing_set_probes for FS_MAX_PATHING_PROBES; staging grows only at the first call with a larger count. */
+#define FS_MAX_PATHING_PROBES 1024
+#define FS_MAX_PATHING_NODES    16      /* probes of a path that are reported */
+#define FS_MAX_PATHING_BATCH   256
+#define FS_PATHING_MIN_EDGE   1.0f      /* cm */
+#define FS_PATHING_MAX_LENGTH 1048576.0f
+#define FS_PATHING_FOUND 1u
+#define FS_PATHING_DIRECT 2u
+#define FS_PATHING_STALE 4u
+#define FS_PATHING_NO_PROBE 0xFFFFFFFFu
+#define FS_PATHING_VOICE_KEY 0x80000003u
+typedef struct fs_pathing_bake_params {
+    uint32_t struct_size;     /* = sizeof(fs_pathing_bake_params) */
+    float    max_edge;        /* cm, > 0, finite; default 1000: the longest pair that is tested */
+    float    step;            /* as fs_direct_params, default 0.1 */
+} fs_pathing_bake_params;
+
+typedef struct fs_pathing_params {
+    uint32_t struct_size;     /* = sizeof(fs_pathing_params) */
+    int32_t  validate;        /* 0 / 1, default 1: run the path's baked legs again */
+    float    max_attach;      /* cm, > 0, finite; default 1000: the farthest probe the listener or a source attaches to */
+    float    max_length;      /* cm, > 0, <= FS_PATHING_MAX_LENGTH; default 10000 */
+    float    step;            /* as fs_direct_params, default 0.1 */
+    float    pullback;        /* cm the DIRECT ray stops short of the listener, >= 0; default 0.1 */
+    float    dist_divisor;    /* 1000, as fs_params */
+    float    sound_speed;     /* 343, as fs_params */
+} fs_pathing_params;
+
+typedef struct fs_pathing_path {
+    float    length;          /* cm, listener -> probes -> source */
+    float    delay;           /* s, on the impulse response's time axis */
+    float    detour;          /* cm, length - distance */
+    float    distance;        /* cm, |S - L|: written for every row */
+    float    direction[3];    /* unit, from the listener towards the first probe: what a host pans by */
+    float    departure[3];    /* unit, from the source towards the last probe */
+    uint32_t hops;            /* probes on the path */
+    uint32_t flags;           /* FS_PATHING_FOUND | FS_PATHING_DIRECT | FS_PATHING_STALE */
+    uint32_t first_probe;     /* the probe next to the listener */
+    uint32_t last_probe;      /* the probe next to the source */
+    uint32_t probes[FS_MAX_PATHING_NODES]; /* from the listener's end; FS_PATHING_NO_PROBE beyond hops */
+    float    gain[FS_MAX_BANDS]; /* barrier estimate of the detour; bands beyond num_bands: 0 */
+} fs_pathing_path;            /* an array element: no struct_size; 152 bytes */
+
+int fs_pathing_set_probes(fs_context* ctx, const float* xyz /* [count][3] */, int32_t count /* 0 or xyz NULL: clear */);
+void fs_pathing_bake_params_default(fs_pathing_bake_params* p);
+int fs_pathing_bake(fs_context* ctx, const fs_pathing_bake_params* params /* NULL = defaults */);
+int fs_pathing_info(fs_context* ctx, int32_t* probes, int32_t* edges, int32_t* baked, int32_t* scene_changed); /* any pointer may be NULL */
+int fs_pathing_copy_graph(fs_context* ctx, uint32_t* bits /* [N][ceil(N / 32)] */, int32_t words);
+void fs_pathing_params_default(fs_pathing_params* p);
+int fs_update_pathing_paths(fs_context* ctx, const fs_source* sources, int32_t count,
+                            const fs_pathing_params* params /* NULL = defaults */, fs_pathing_path* out /* [count] */);
 
 /* ---- engine line trace the BVH kernel replaces (UWorld::LineTraceSingleByObjectType; call sites
  *      ARTS.cpp:252-254 any-hit, :340-342 closest-hit). Batch query, host arrays. ------------------- */
