@@ -235,12 +235,7 @@ int fs_apply_material_fd(fs_context* ctx, const float* in, int32_t L, const floa
         ctx->fft_cap_n = cn; ctx->fft_cap_l = (int)CN;
     }
     if (ctx->fft_n != n) {   // twiddles in double precision: W[k] = exp(-2 pi i k / N)
-        std::vector<float2> w(std::max(N / 2, 1));
-        for (int k = 0; k < N / 2; ++k) {
-            const double a = -2.0 * 3.14159265358979323846 * (double)k / (double)N;
-            w[(size_t)k] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-        if (N < 2) w[0] = make_float2(1.f, 0.f);
+        const std::vector<float2> w = fsi::host_twiddles((size_t)N);
         FS_HIP(ctx, hipMemcpyAsync(ctx->d_fft_w, w.data(), sizeof(float2) * w.size(), hipMemcpyHostToDevice, ctx->stream));
         FS_HIP(ctx, hipStreamSynchronize(ctx->stream));   // w is a stack-owned staging buffer
         ctx->fft_n = n;

@@ -130,155 +130,117 @@ int check_spectral(fs_context* ctx, const fs_params* p) {
     return check_band_edges(ctx, nullptr, "FS_FLAG_SPECTRAL_IR");
 }
 
-// The build: on the compute stream, waited for here (once per context and band-edge setting; the work buffers are freed behind it)
-static int build_carriers(fs_context* ctx) {
-    const int B = ctx->cfg.num_bands, n = carrier_log(ctx), N = ctx->num_samples, ld = carrier_stride(N);
+std::vector<float2> host_twiddles(size_t N) {
+    std::vector<float2> w(std::max<size_t>(N / 2, 1));
+    for (size_t k = 0; k < N / 2; ++k) {
+        const double a = -2.0 * 3.14159265358979323846 * (double)k / (double)N;
+        w[k] = make_float2((float)std::cos(a), (float)std::sin(a));
+    }
+    if (N < 2) w[0] = make_float2(1.f, 0.f);
+    return w;
+}
+
+// The build of a carrier set of `rows` rows [rows][ld] through `work_rows` rows of complex work buffers: on the compute stream,
+// waited for here (the work buffers are freed behind it).  launch(n, N, ld, bands, X, y, W, zeros, out) enqueues the set's passes
+// (fs_fft.hip); what: whose build it is, for the messages; ms (or null): the device time of the passes.
+template <class Launch>
+static int build_carrier_set(fs_context* ctx, size_t rows, size_t work_rows, const char* what, const char* building, float** set, float* ms,
+                             Launch launch) {
+    *set = nullptr;
+    const int n = carrier_log(ctx), N = ctx->num_samples, ld = carrier_stride(N);
     const size_t K = (size_t)1 << n;
     const std::vector<double> edges = effective_edges(ctx);
     CarrierBands bands{};
-    if (!band_bins(ctx, edges.data(), &bands)) return check_band_edges(ctx, nullptr, "FS_FLAG_SPECTRAL_IR");
-    std::vector<float2> w(std::max<size_t>(K / 2, 1));   // W[k] = exp(-2 pi i k / K) in double
-    for (size_t k = 0; k < K / 2; ++k) {
-        const double a = -2.0 * 3.14159265358979323846 * (double)k / (double)K;
-        w[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    if (K < 2) w[0] = make_float2(1.f, 0.f);
+    if (!band_bins(ctx, edges.data(), &bands)) return check_band_edges(ctx, nullptr, what);
+    const std::vector<float2> w = host_twiddles(K);
     float2 *X = nullptr, *y = nullptr, *W = nullptr;
     float *zeros = nullptr, *out = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
     hipError_t e = hipSetDevice(ctx->cfg.device);
-    if (e == hipSuccess) e = hipMalloc((void**)&out, sizeof(float) * (size_t)B * (size_t)ld);
-    if (e == hipSuccess) e = hipMalloc((void**)&X, sizeof(float2) * (size_t)B * K);
-    if (e == hipSuccess) e = hipMalloc((void**)&y, sizeof(float2) * (size_t)B * K);
+    if (e == hipSuccess) e = hipMalloc((void**)&out, sizeof(float) * rows * (size_t)ld);
+    if (e == hipSuccess) e = hipMalloc((void**)&X, sizeof(float2) * work_rows * K);
+    if (e == hipSuccess) e = hipMalloc((void**)&y, sizeof(float2) * work_rows * K);
     if (e == hipSuccess) e = hipMalloc((void**)&W, sizeof(float2) * w.size());
     if (e == hipSuccess) e = hipMalloc((void**)&zeros, sizeof(float) * (K / 2 + 1));
-    if (e == hipSuccess) e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    for (hipEvent_t& v : ev) if (ms && e == hipSuccess) e = hipEventCreate(&v);
     if (e == hipSuccess) e = hipMemcpyAsync(W, w.data(), sizeof(float2) * w.size(), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(zeros, 0, sizeof(float) * (K / 2 + 1), ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], ctx->stream);
+    if (ms && e == hipSuccess) e = hipEventRecord(ev[0], ctx->stream);
     if (e == hipSuccess) {
-        launch_build_carriers(B, n, N, ld, bands, X, y, W, zeros, out, ctx->stream);
+        launch(n, N, ld, bands, X, y, W, zeros, out);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
+    if (ms && e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (w is a local; the work buffers go next)
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    if (ms && e == hipSuccess) e = hipEventElapsedTime(ms, ev[0], ev[1]);
     for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
     for (void* q : {(void*)X, (void*)y, (void*)W, (void*)zeros}) if (q) (void)hipFree(q);
     if (e != hipSuccess) {
         if (out) (void)hipFree(out);
-        return ctx->hip_fail(e, "FS_FLAG_SPECTRAL_IR: building the band carriers");
+        return ctx->hip_fail(e, (std::string(what) + ": building the " + building).c_str());
     }
-    ctx->d_carrier = out;
-    ctx->carrier_build_ms = ms;
+    *set = out;
     return FS_OK;
 }
 
-// fs_reverb_ears_set: build_carriers' steps for the 2B mid and side rows (fs_fft.hip: launch_build_ear_carriers)
+// FS_FLAG_SPECTRAL_IR's B band carriers: once per context and band-edge setting
+static int build_carriers(fs_context* ctx) {
+    const size_t B = (size_t)ctx->cfg.num_bands;
+    float ms = 0.0f;
+    const int rc = build_carrier_set(ctx, B, B, "FS_FLAG_SPECTRAL_IR", "band carriers", &ctx->d_carrier, &ms,
+                                     [&](int n, int N, int ld, const CarrierBands& bands, float2* X, float2* y, const float2* W, const float* zeros, float* out) {
+                                         launch_build_carriers((int)B, n, N, ld, bands, X, y, W, zeros, out, ctx->stream);
+                                     });
+    if (rc == FS_OK) ctx->carrier_build_ms = ms;
+    return rc;
+}
+
+// fs_reverb_ears_set: the 2B mid and side rows (fs_fft.hip: launch_build_ear_carriers)
 int build_ear_carriers(fs_context* ctx, float radius_cm, float speed_cm_s, const char* what, float** set) {
-    *set = nullptr;
-    const int B = ctx->cfg.num_bands, n = carrier_log(ctx), N = ctx->num_samples, ld = carrier_stride(N);
-    const size_t K = (size_t)1 << n;
-    const std::vector<double> edges = effective_edges(ctx);
-    CarrierBands bands{};
-    if (!band_bins(ctx, edges.data(), &bands)) return check_band_edges(ctx, nullptr, what);
-    std::vector<float2> w(std::max<size_t>(K / 2, 1));   // W[k] = exp(-2 pi i k / K) in double
-    for (size_t k = 0; k < K / 2; ++k) {
-        const double a = -2.0 * 3.14159265358979323846 * (double)k / (double)K;
-        w[k] = make_float2((float)std::cos(a), (float)std::sin(a));
+    const size_t B = (size_t)ctx->cfg.num_bands;
+    return build_carrier_set(ctx, 2 * B, 2 * B, what, "ear carriers", set, nullptr,
+                             [&](int n, int N, int ld, const CarrierBands& bands, float2* X, float2* y, const float2* W, const float* zeros, float* out) {
+                                 launch_build_ear_carriers((int)B, n, N, ld, bands, (double)ctx->cfg.sample_rate, (double)radius_cm, (double)speed_cm_s,
+                                                           X, y, W, zeros, out, ctx->stream);
+                             });
+}
+
+// fs_reverb_soundfield_set: C channels of B rows (fs_fft.hip: launch_build_soundfield_carriers); the work buffers are those of
+// one channel
+int build_soundfield_carriers(fs_context* ctx, int32_t order, const char* what, float** set) {
+    const int C = (order + 1) * (order + 1);
+    const size_t B = (size_t)ctx->cfg.num_bands;
+    return build_carrier_set(ctx, (size_t)C * B, B, what, "soundfield carriers", set, nullptr,
+                             [&](int n, int N, int ld, const CarrierBands& bands, float2* X, float2* y, const float2* W, const float* zeros, float* out) {
+                                 launch_build_soundfield_carriers(C, (int)B, n, N, ld, bands, X, y, W, zeros, out, ctx->stream);
+                             });
+}
+
+// The installation of an ear or soundfield set in place of the one in force (*slot; set == nullptr: none), behind the reverb stream
+static int install_carrier_set(fs_context* ctx, float** slot, uint64_t* gen, float* set, const char* what) {
+    hipError_t e = hipStreamSynchronize(ctx->rev_stream);   // (no callback's launches still read the set in force)
+    if (e == hipSuccess && *slot) e = hipFree(*slot);
+    if (e != hipSuccess) {   // (the set in force stays; the new one is not kept)
+        if (set) (void)hipFree(set);
+        return ctx->hip_fail(e, what);
     }
-    if (K < 2) w[0] = make_float2(1.f, 0.f);
-    float2 *X = nullptr, *y = nullptr, *W = nullptr;
-    float *zeros = nullptr, *out = nullptr;
-    hipError_t e = hipSetDevice(ctx->cfg.device);
-    if (e == hipSuccess) e = hipMalloc((void**)&out, sizeof(float) * 2 * (size_t)B * (size_t)ld);
-    if (e == hipSuccess) e = hipMalloc((void**)&X, sizeof(float2) * 2 * (size_t)B * K);
-    if (e == hipSuccess) e = hipMalloc((void**)&y, sizeof(float2) * 2 * (size_t)B * K);
-    if (e == hipSuccess) e = hipMalloc((void**)&W, sizeof(float2) * w.size());
-    if (e == hipSuccess) e = hipMalloc((void**)&zeros, sizeof(float) * (K / 2 + 1));
-    if (e == hipSuccess) e = hipMemcpyAsync(W, w.data(), sizeof(float2) * w.size(), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(zeros, 0, sizeof(float) * (K / 2 + 1), ctx->stream);
-    if (e == hipSuccess) {
-        launch_build_ear_carriers(B, n, N, ld, bands, (double)ctx->cfg.sample_rate, (double)radius_cm, (double)speed_cm_s, X, y, W, zeros, out,
-                                  ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (w is a local; the work buffers go next)
-    for (void* q : {(void*)X, (void*)y, (void*)W, (void*)zeros}) if (q) (void)hipFree(q);
-    if (e != hipSuccess) {
-        if (out) (void)hipFree(out);
-        return ctx->hip_fail(e, (std::string(what) + ": building the ear carriers").c_str());
-    }
-    *set = out;
+    *slot = set;
+    ++*gen;
     return FS_OK;
 }
 
 int install_ear_carriers(fs_context* ctx, float* set, float radius_cm, float speed_cm_s) {
-    hipError_t e = hipStreamSynchronize(ctx->rev_stream);   // (no callback's launches still read the set in force)
-    if (e == hipSuccess && ctx->d_ear_carrier) e = hipFree(ctx->d_ear_carrier);
-    if (e != hipSuccess) {   // (the set in force stays; the new one is not kept)
-        if (set) (void)hipFree(set);
-        return ctx->hip_fail(e, "installing the ear carriers");
-    }
-    ctx->d_ear_carrier = set;
+    const int rc = install_carrier_set(ctx, &ctx->d_ear_carrier, &ctx->ear_set_gen, set, "installing the ear carriers");
+    if (rc) return rc;
     ctx->ear_radius_cm = set ? radius_cm : 0.0f;
     ctx->ear_speed_cm_s = set ? speed_cm_s : 0.0f;
-    ctx->ear_set_gen++;
-    return FS_OK;
-}
-
-// fs_reverb_soundfield_set: the same steps for C channels of B rows (fs_fft.hip: launch_build_soundfield_carriers); the work buffers
-// are those of one channel
-int build_soundfield_carriers(fs_context* ctx, int32_t order, const char* what, float** set) {
-    *set = nullptr;
-    const int C = (order + 1) * (order + 1);
-    const int B = ctx->cfg.num_bands, n = carrier_log(ctx), N = ctx->num_samples, ld = carrier_stride(N);
-    const size_t K = (size_t)1 << n;
-    const std::vector<double> edges = effective_edges(ctx);
-    CarrierBands bands{};
-    if (!band_bins(ctx, edges.data(), &bands)) return check_band_edges(ctx, nullptr, what);
-    std::vector<float2> w(std::max<size_t>(K / 2, 1));   // W[k] = exp(-2 pi i k / K) in double
-    for (size_t k = 0; k < K / 2; ++k) {
-        const double a = -2.0 * 3.14159265358979323846 * (double)k / (double)K;
-        w[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    if (K < 2) w[0] = make_float2(1.f, 0.f);
-    float2 *X = nullptr, *y = nullptr, *W = nullptr;
-    float *zeros = nullptr, *out = nullptr;
-    hipError_t e = hipSetDevice(ctx->cfg.device);
-    if (e == hipSuccess) e = hipMalloc((void**)&out, sizeof(float) * (size_t)C * (size_t)B * (size_t)ld);
-    if (e == hipSuccess) e = hipMalloc((void**)&X, sizeof(float2) * (size_t)B * K);
-    if (e == hipSuccess) e = hipMalloc((void**)&y, sizeof(float2) * (size_t)B * K);
-    if (e == hipSuccess) e = hipMalloc((void**)&W, sizeof(float2) * w.size());
-    if (e == hipSuccess) e = hipMalloc((void**)&zeros, sizeof(float) * (K / 2 + 1));
-    if (e == hipSuccess) e = hipMemcpyAsync(W, w.data(), sizeof(float2) * w.size(), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(zeros, 0, sizeof(float) * (K / 2 + 1), ctx->stream);
-    if (e == hipSuccess) {
-        launch_build_soundfield_carriers(C, B, n, N, ld, bands, X, y, W, zeros, out, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (w is a local; the work buffers go next)
-    for (void* q : {(void*)X, (void*)y, (void*)W, (void*)zeros}) if (q) (void)hipFree(q);
-    if (e != hipSuccess) {
-        if (out) (void)hipFree(out);
-        return ctx->hip_fail(e, (std::string(what) + ": building the soundfield carriers").c_str());
-    }
-    *set = out;
     return FS_OK;
 }
 
 int install_soundfield_carriers(fs_context* ctx, float* set, int32_t order) {
-    hipError_t e = hipStreamSynchronize(ctx->rev_stream);   // (no callback's launches still read the set in force)
-    if (e == hipSuccess && ctx->d_sf_carrier) e = hipFree(ctx->d_sf_carrier);
-    if (e != hipSuccess) {   // (the set in force stays; the new one is not kept)
-        if (set) (void)hipFree(set);
-        return ctx->hip_fail(e, "installing the soundfield carriers");
-    }
-    ctx->d_sf_carrier = set;
+    const int rc = install_carrier_set(ctx, &ctx->d_sf_carrier, &ctx->sf_set_gen, set, "installing the soundfield carriers");
+    if (rc) return rc;
     ctx->sf_order = set ? order : -1;
-    ctx->sf_set_gen++;
     return FS_OK;
 }
 

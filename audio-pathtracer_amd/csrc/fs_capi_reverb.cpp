@@ -15,7 +15,7 @@ bool partitioned(const Source* s) { return s->rev_engine == FS_REVERB_ENGINE_PAR
 // the direct engine, partition spectra for the partitioned one, which needs the one it convolves (h_to) without a fade too
 // (both == false)
 int alloc_fade(fs_context* ctx, Source* s, bool both) {
-    const size_t bytes = partitioned(s) ? sizeof(float2) * ((size_t)s->part_K << s->part_n) * (s->rev_sf ? (size_t)s->sf_P : s->rev_ears ? 2 : 1)   // (ears: M_p, then S_p; soundfield: the P pairs)
+    const size_t bytes = partitioned(s) ? sizeof(float2) * ((size_t)s->part_K << s->part_n) * (size_t)s->part_sets
                                         : sizeof(float) * (size_t)ctx->num_samples;
     if (both && !s->d_fade_from) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_from, bytes));
     if (!s->d_fade_to) FS_HIP(ctx, hipMalloc((void**)&s->d_fade_to, bytes));
@@ -25,23 +25,21 @@ int alloc_fade(fs_context* ctx, Source* s, bool both) {
 // the partitioned engine's twiddle table of N = 1 << n, in double on the host (as fs_apply_material_fd's); init time only
 int part_twiddles(fs_context* ctx, int n) {
     if (ctx->d_rev_tw[n]) return FS_OK;
-    const size_t half = (size_t)1 << (n - 1);
-    std::vector<float2> w(half);
-    const double step = -2.0 * M_PI / (double)(half * 2);
-    for (size_t k = 0; k < half; ++k) w[k] = make_float2((float)std::cos(step * (double)k), (float)std::sin(step * (double)k));
-    FS_HIP(ctx, hipMalloc((void**)&ctx->d_rev_tw[n], sizeof(float2) * half));
-    FS_HIP(ctx, hipMemcpy(ctx->d_rev_tw[n], w.data(), sizeof(float2) * half, hipMemcpyHostToDevice));
+    const std::vector<float2> w = fsi::host_twiddles((size_t)1 << n);
+    FS_HIP(ctx, hipMalloc((void**)&ctx->d_rev_tw[n], sizeof(float2) * w.size()));
+    FS_HIP(ctx, hipMemcpy(ctx->d_rev_tw[n], w.data(), sizeof(float2) * w.size(), hipMemcpyHostToDevice));
     return FS_OK;
 }
 
 // the reverb callback's own blocks in its staging (fs_context::rev_stage): CallbackLayout::up; scratch[0] = the mono tails cur
+// kRevLists: the three lists of the direct engine's rows, then those of the partitioned engine's
 // kRevEarLists: the three lists of the rows with ears — zero bytes in a call without such a row, so every other offset stays
 enum { kRevItems, kRevPartItems, kRevLists, kRevEarLists };
 
 // the bytes of Source::d_ring: the direct engine's two history rings, or the partitioned engine's state block
 size_t reverb_state_bytes(const Source* s) {
-    if (s->rev_sf) return sizeof(float2) * sf_state_elems(s->part_n, s->part_K, s->sf_P);
-    return partitioned(s) ? sizeof(float2) * part_state_elems(s->part_n, s->part_K) : sizeof(float) * 2 * kReverbRing;
+    if (!partitioned(s)) return sizeof(float) * 2 * kReverbRing;
+    return sizeof(float2) * part_state_elems(s->part_n, s->part_K, !s->rev_sf, s->rev_sf ? s->part_sets : 1);
 }
 
 const char* const kNoFadeBuffers = "the crossfade's impulse-response buffers are missing: call fs_reverb_init again";
@@ -53,16 +51,14 @@ const char* const kSoundfieldSource = "the source is initialised with the soundf
 // caller records ev_rev behind the launch that reads d_ir_mono, still under the lock).  With a crossfade (fs_reverb_set_crossfade)
 // the callback convolves its own copies of the IR: it reads d_ir_mono only when a newer IR is there (ir_gen), once, into h_to —
 // only then does it wait for the write and make the next one wait for it.  *takes: this callback is such a one.
-// The partitioned engine (pit is the row's descriptor then, and `it` says only whose row it is) convolves spectra of its own with
-// or without a crossfade, so it takes in the same way in both cases: H_to from d_ir_mono, when a newer IR is there.
+// The step fills the row's descriptor: `it` of a direct row, `pit` of a partitioned one (the other is null).
+// The partitioned engine convolves spectra of its own with or without a crossfade, so it takes in the same way in both cases: H_to
+// from d_ir_mono, when a newer IR is there.
 // A source with ears (fs_reverb_set_ears) is such a row whose spectra come from the band rows — written by the same launches as
 // d_ir_mono, under the same events — and the context's ear carriers: it also takes when that set was replaced (ear_set_gen).
-// A soundfield source (fs_reverb_set_soundfield) is the same with the soundfield carriers (sf_set_gen); its callback is
-// soundfield_rows, which reads pit alone.
-int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbItem& it, ReverbPartItem& pit, bool* takes) {
-    it.apply = 1;
-    it.engine = s->rev_engine;
-    const bool part = partitioned(s);
+// A soundfield source (fs_reverb_set_soundfield) is the same with the soundfield carriers (sf_set_gen).
+int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbItem* it, ReverbPartItem* pit, bool* takes) {
+    const bool part = pit != nullptr;
     const bool xfade = s->fade_len > 0;
     const bool own = xfade || part;   // the callback convolves copies of its own
     const bool tk = *takes = own && (!s->fade_primed || s->ir_gen != s->fade_gen || (s->rev_ears && s->ear_gen != ctx->ear_set_gen) ||
@@ -85,8 +81,8 @@ int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbIte
             s->fading = true;
             s->fade_pos = 0;
         }
-        if (part) { pit.take_from = (float2*)s->d_fade_from; pit.take_to = (float2*)s->d_fade_to; pit.take_ir = (s->rev_ears || s->rev_sf) ? s->d_ir_bands : s->d_ir_mono; pit.take_a = a; }
-        else { it.take_from = s->d_fade_from; it.take_to = s->d_fade_to; it.take_ir = s->d_ir_mono; it.take_a = a; }
+        if (part) { pit->take_from = (float2*)s->d_fade_from; pit->take_to = (float2*)s->d_fade_to; pit->take_ir = (s->rev_ears || s->rev_sf) ? s->d_ir_bands : s->d_ir_mono; pit->take_a = a; }
+        else { it->take_from = s->d_fade_from; it->take_to = s->d_fade_to; it->take_ir = s->d_ir_mono; it->take_a = a; }
         s->fade_primed = true;
         s->fade_gen = s->ir_gen;
         s->ear_gen = ctx->ear_set_gen;
@@ -94,122 +90,132 @@ int reverb_step(fs_context* ctx, Source* s, hipStream_t rs, int frame, ReverbIte
     }
     if (!own || tk) s->rev_recorded = true;
     if (part) {
-        pit.active = 1;
-        pit.state = (float2*)s->d_ring;
-        pit.head = s->rev_head;
-        pit.slot = s->part_slot;
-        if (s->fading) { pit.h = (const float2*)s->d_fade_from; pit.h_to = (const float2*)s->d_fade_to; pit.fade_pos = s->fade_pos; pit.fade_len = s->fade_len; }
-        else pit.h = (const float2*)s->d_fade_to;
+        pit->active = 1;
+        pit->state = (float2*)s->d_ring;
+        pit->head = s->rev_head;
+        pit->slot = s->part_slot;
+        if (s->fading) { pit->h = (const float2*)s->d_fade_from; pit->h_to = (const float2*)s->d_fade_to; pit->fade_pos = s->fade_pos; pit->fade_len = s->fade_len; }
+        else pit->h = (const float2*)s->d_fade_to;
         if (++s->part_slot == s->part_K) s->part_slot = 0;
     } else {
-        it.ring = s->d_ring;
-        it.head = s->rev_head;
-        if (!xfade) it.ir = s->d_ir_mono;
-        else if (s->fading) { it.ir = s->d_fade_from; it.ir_to = s->d_fade_to; it.fade_pos = s->fade_pos; it.fade_len = s->fade_len; }
-        else it.ir = s->d_fade_to;
+        it->ring = s->d_ring;
+        it->head = s->rev_head;
+        if (!xfade) it->ir = s->d_ir_mono;
+        else if (s->fading) { it->ir = s->d_fade_from; it->ir_to = s->d_fade_to; it->fade_pos = s->fade_pos; it->fade_len = s->fade_len; }
+        else it->ir = s->d_fade_to;
     }
     s->rev_head += (unsigned)frame;
     if (s->fading && (s->fade_pos += frame) >= s->fade_len) s->fading = false;   // complete: h_from := h_to, one convolution again
     return FS_OK;
 }
 
+// The pieces the two callbacks (reverb_rows, soundfield_rows) are built from.
+// The rows by ascending Source*: the one locking order of every thread (fs_capi_publish.cpp).  A source that appears twice is
+// refused, still before the first state change or enqueue.
+int lock_order(fs_context* ctx, Source* const* srcs, int32_t count, std::vector<int32_t>* order) {
+    order->resize((size_t)count);
+    for (int32_t i = 0; i < count; ++i) (*order)[(size_t)i] = i;
+    std::sort(order->begin(), order->end(), [&](int32_t a, int32_t b) { return srcs[a] < srcs[b]; });
+    for (int32_t k = 1; k < count; ++k)
+        if (srcs[(*order)[(size_t)k]] == srcs[(*order)[(size_t)k - 1]])
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a source appears twice in the batch");
+    return FS_OK;
+}
+// The locks of all convolved sources (apply_reverb: null = every row), taken in that order.  They are held while the work is
+// enqueued (a reconstruct that found one free would not wait for a read this call has yet to record), not longer.
+std::vector<std::unique_lock<std::mutex>> lock_rows(Source* const* srcs, const std::vector<int32_t>& order, const int32_t* apply_reverb) {
+    std::vector<std::unique_lock<std::mutex>> locks;
+    locks.reserve(order.size());
+    for (int32_t i : order)
+        if (!apply_reverb || apply_reverb[i]) locks.emplace_back(srcs[i]->ir_mu);
+    return locks;
+}
+// One row kind's three lists in a staging block, [3][count] ints at `off` bytes on both sides: the rows with one product (or
+// convolution), those with two, and those that take a newer IR in this callback.
+struct RowLists {
+    int* h; const int* d;
+    int count, n_plain = 0, n_fade = 0, n_take = 0;
+    RowLists(const CallbackStage& st, size_t off, int count_) : h((int*)(st.h + off)), d((const int*)(st.d + off)), count(count_) {}
+    void add(int i, bool takes, bool fading) {
+        if (takes) h[2 * count + n_take++] = i;
+        if (fading) h[count + n_fade++] = i;
+        else h[n_plain++] = i;
+    }
+    ReverbLists dev() const { return {d, n_plain, d + count, n_fade}; }
+};
+// launch(take, n_take) enqueues the take of the list's rows (when it has any); then every taken row's ev_rev is recorded behind it
+template <class Launch>
+int take_rows(fs_context* ctx, Source* const* srcs, const RowLists& l, hipStream_t rs, Launch launch) {
+    if (!l.n_take) return FS_OK;
+    launch(l.d + 2 * l.count, l.n_take);
+    FS_HIP(ctx, hipGetLastError());
+    for (int k = 0; k < l.n_take; ++k) FS_HIP(ctx, hipEventRecord(srcs[l.h[2 * l.count + k]]->ev_rev, rs));
+    return FS_OK;
+}
+
 // The callback of `count` validated sources of one frame size (audio thread): one copy up, the launches, one copy back.
 int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float* in, float* out, const int32_t* apply_reverb,
                 uint32_t flags, float* mix) {
-    std::vector<int32_t> order((size_t)count);   // rows by ascending Source*: the one locking order of every thread (fs_capi_publish.cpp)
-    for (int32_t i = 0; i < count; ++i) order[(size_t)i] = i;
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return srcs[a] < srcs[b]; });
-    for (int32_t k = 1; k < count; ++k)   // (still before the first state change or enqueue)
-        if (srcs[order[(size_t)k]] == srcs[order[(size_t)k - 1]])
-            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a source appears twice in the batch");
+    std::vector<int32_t> order;
+    { const int rc = lock_order(ctx, srcs, count, &order); if (rc) return rc; }
     const int frame = srcs[0]->rev_frame;
     const size_t row = 2 * (size_t)frame;   // floats
     FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
     hipStream_t rs = ctx->rev_stream;
     bool ears = false;
     for (int32_t i = 0; i < count; ++i) ears = ears || (srcs[i]->rev_ears && (!apply_reverb || apply_reverb[i]));
-    const CallbackLayout l = callback_layout(count, frame, 2 * (size_t)frame, {sizeof(ReverbItem) * (size_t)count, sizeof(ReverbPartItem) * (size_t)count, sizeof(int) * 6 * (size_t)count,
-                                                            ears ? sizeof(int) * 3 * (size_t)count : 0},
+    const size_t lists = sizeof(int) * 3 * (size_t)count;
+    const CallbackLayout l = callback_layout(count, frame, 2 * (size_t)frame, {sizeof(ReverbItem) * (size_t)count, sizeof(ReverbPartItem) * (size_t)count, 2 * lists,
+                                                            ears ? lists : 0},
                                              {sizeof(float) * row * (size_t)count});
     { const int rc = ctx->rev_stage.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
     char* hs = ctx->rev_stage.h; char* ds = ctx->rev_stage.d;
     ReverbItem* items = (ReverbItem*)(hs + l.up[kRevItems]);
     ReverbPartItem* pitems = (ReverbPartItem*)(hs + l.up[kRevPartItems]);
-    int* plain = (int*)(hs + l.up[kRevLists]); int* fade = plain + count; int* take = fade + count;
-    int* pplain = take + count; int* pfade = pplain + count; int* ptake = pfade + count;   // the partitioned engine's three
-    int* eplain = (int*)(hs + l.up[kRevEarLists]); int* efade = eplain + count; int* etake = efade + count;   // (only with ears)
-    int n_plain = 0, n_fade = 0, n_take = 0, n_pplain = 0, n_pfade = 0, n_ptake = 0, n_bypass = 0, n_eplain = 0, n_efade = 0, n_etake = 0;
+    RowLists direct(ctx->rev_stage, l.up[kRevLists], count), part(ctx->rev_stage, l.up[kRevLists] + lists, count);
+    RowLists ear(ctx->rev_stage, l.up[kRevEarLists], count);   // (rows only with ears)
+    int n_bypass = 0;
     const Source* part_src = nullptr;
     float* h_in = (float*)(hs + l.in);
     for (int32_t i = 0; i < count; ++i)   // (a bypassed row goes up only for the mix)
         if (mix || !apply_reverb || apply_reverb[i])
             std::memcpy(h_in + (size_t)i * row, in + (size_t)i * row, sizeof(float) * row);
     {
-        // The steps in list order; the locks of all convolved sources are held while the work is enqueued (a reconstruct that found
-        // one free would not wait for a read this call has yet to record), not longer.
-        std::vector<std::unique_lock<std::mutex>> locks;
-        locks.reserve((size_t)count);
-        for (int32_t i : order)
-            if (!apply_reverb || apply_reverb[i]) locks.emplace_back(srcs[i]->ir_mu);
-        for (int32_t i = 0; i < count; ++i) {
+        const auto locks = lock_rows(srcs, order, apply_reverb);
+        for (int32_t i = 0; i < count; ++i) {   // the steps in list order
             std::memset(&items[i], 0, sizeof(ReverbItem));
             std::memset(&pitems[i], 0, sizeof(ReverbPartItem));
             if (apply_reverb && !apply_reverb[i]) { ++n_bypass; continue; }   // the bypass touches no state
+            Source* s = srcs[i];
+            const bool p = partitioned(s);
+            items[i].apply = 1;
+            items[i].engine = s->rev_engine;   // (of a partitioned row's ReverbItem the kernels read these two only)
             bool takes = false;
-            const int rc = reverb_step(ctx, srcs[i], rs, frame, items[i], pitems[i], &takes);
+            const int rc = reverb_step(ctx, s, rs, frame, p ? nullptr : &items[i], p ? &pitems[i] : nullptr, &takes);
             if (rc) return rc;
-            if (pitems[i].active && srcs[i]->rev_ears) {
-                part_src = srcs[i];
-                if (takes) etake[n_etake++] = i;
-                if (pitems[i].h_to) efade[n_efade++] = i;
-                else eplain[n_eplain++] = i;
-            } else if (pitems[i].active) {
-                part_src = srcs[i];
-                if (takes) ptake[n_ptake++] = i;
-                if (pitems[i].h_to) pfade[n_pfade++] = i;
-                else pplain[n_pplain++] = i;
-            } else {
-                if (takes) take[n_take++] = i;
-                if (items[i].ir_to) fade[n_fade++] = i;
-                else plain[n_plain++] = i;
-            }
+            if (p) part_src = s;
+            if (!p) direct.add(i, takes, items[i].ir_to != nullptr);
+            else (s->rev_ears ? ear : part).add(i, takes, pitems[i].h_to != nullptr);
         }
         FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, rs));
-        const ReverbItem* d_items = (const ReverbItem*)(ds + l.up[kRevItems]);
-        const int* d_plain = (const int*)(ds + l.up[kRevLists]);
-        if (n_take) {
-            launch_reverb_batch_fade_start(d_items, d_plain + 2 * count, n_take, ctx->num_samples, rs);
-            FS_HIP(ctx, hipGetLastError());
-            for (int k = 0; k < n_take; ++k) FS_HIP(ctx, hipEventRecord(srcs[take[k]]->ev_rev, rs));
-        }
         ReverbBatch b{};
+        b.items = (const ReverbItem*)(ds + l.up[kRevItems]);
+        { const int rc = take_rows(ctx, srcs, direct, rs, [&](const int* take, int n) { launch_reverb_batch_fade_start(b.items, take, n, ctx->num_samples, rs); }); if (rc) return rc; }
         if (part_src) {   // (one frame size and one context: N and K are those of every partitioned row)
             b.pitems = (const ReverbPartItem*)(ds + l.up[kRevPartItems]);
-            b.part.plain = d_plain + 3 * count; b.part.n_plain = n_pplain;
-            b.part.fade = d_plain + 4 * count; b.part.n_fade = n_pfade;
-            b.part.n = part_src->part_n; b.part.K = part_src->part_K; b.part.frame = frame; b.part.ir_size = ctx->num_samples;
-            b.part.W = ctx->d_rev_tw[part_src->part_n];
-            if (n_ptake) {
-                launch_reverb_part_take(b.pitems, d_plain + 5 * count, n_ptake, b.part, rs);
-                FS_HIP(ctx, hipGetLastError());
-                for (int k = 0; k < n_ptake; ++k) FS_HIP(ctx, hipEventRecord(srcs[ptake[k]]->ev_rev, rs));
-            }
+            b.part = ReverbShape{ctx->d_rev_tw[part_src->part_n], part_src->part_n, part_src->part_K, frame, ctx->num_samples};
+            b.part_rows = part.dev();
+            { const int rc = take_rows(ctx, srcs, part, rs, [&](const int* take, int n) { launch_reverb_part_take(b.pitems, take, n, b.part, rs); }); if (rc) return rc; }
             if (ears) {
-                const int* d_ear = (const int*)(ds + l.up[kRevEarLists]);
-                b.part.ear_plain = d_ear; b.part.n_ear_plain = n_eplain;
-                b.part.ear_fade = d_ear + count; b.part.n_ear_fade = n_efade;
-                if (n_etake) {
-                    const ReverbEars e{ctx->d_ear_carrier, ctx->cfg.num_bands, carrier_stride(ctx->num_samples)};
-                    launch_reverb_ears_take(b.pitems, d_ear + 2 * count, n_etake, b.part, e, rs);
-                    FS_HIP(ctx, hipGetLastError());
-                    for (int k = 0; k < n_etake; ++k) FS_HIP(ctx, hipEventRecord(srcs[etake[k]]->ev_rev, rs));
-                }
+                b.ear_rows = ear.dev();
+                const ReverbEars e{ctx->d_ear_carrier, ctx->cfg.num_bands, carrier_stride(ctx->num_samples)};
+                const int rc = take_rows(ctx, srcs, ear, rs, [&](const int* take, int n) { launch_reverb_ears_take(b.pitems, take, n, b.part, e, rs); });
+                if (rc) return rc;
             }
         }
-        b.n_direct = n_plain + n_fade + n_bypass;
-        b.items = d_items;
-        b.plain = d_plain; b.n_plain = n_plain;
-        b.fade = d_plain + count; b.n_fade = n_fade;
+        b.n_direct = direct.n_plain + direct.n_fade + n_bypass;
+        b.plain = direct.dev().plain; b.n_plain = direct.n_plain;
+        b.fade = direct.dev().fade; b.n_fade = direct.n_fade;
         b.count = count; b.frame = frame; b.ir_size = ctx->num_samples;
         b.literal_tail = (flags & FS_REVERB_LITERAL_TAIL) ? 1 : 0;
         b.in = (const float*)(ds + l.in);
@@ -218,8 +224,8 @@ int reverb_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float
         b.mix = mix ? (float*)(ds + l.d_mix) : nullptr;
         launch_reverb_batch(b, rs);
         FS_HIP(ctx, hipGetLastError());
-        for (int k = 0; k < n_plain; ++k) {   // without a crossfade the convolution itself reads d_ir_mono
-            Source* s = srcs[plain[k]];
+        for (int k = 0; k < direct.n_plain; ++k) {   // without a crossfade the convolution itself reads d_ir_mono
+            Source* s = srcs[direct.h[k]];
             if (s->fade_len == 0) FS_HIP(ctx, hipEventRecord(s->ev_rev, rs));
         }
     }
@@ -249,14 +255,10 @@ ReverbSoundfield soundfield_set(const fs_context* ctx) {
 enum { kSfItems, kSfLists };
 
 // reverb_rows for `count` validated soundfield sources of one frame size (fs_reverb_soundfield_process_batch, audio thread): the
-// same steps (reverb_step), locks and events, with rows of C frame floats coming back and no bypass, literal tail or clamp.
+// same steps, locks and events, with rows of C frame floats coming back and no bypass, literal tail or clamp.
 int soundfield_rows(fs_context* ctx, Source* const* srcs, int32_t count, const float* in, float* out, float* mix) {
-    std::vector<int32_t> order((size_t)count);   // rows by ascending Source*: the one locking order of every thread
-    for (int32_t i = 0; i < count; ++i) order[(size_t)i] = i;
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return srcs[a] < srcs[b]; });
-    for (int32_t k = 1; k < count; ++k)   // (still before the first state change or enqueue)
-        if (srcs[order[(size_t)k]] == srcs[order[(size_t)k - 1]])
-            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "a source appears twice in the batch");
+    std::vector<int32_t> order;
+    { const int rc = lock_order(ctx, srcs, count, &order); if (rc) return rc; }
     const int frame = srcs[0]->rev_frame;
     const ReverbSoundfield e = soundfield_set(ctx);
     const size_t in_row = 2 * (size_t)frame, row = (size_t)e.C * (size_t)frame;   // floats
@@ -266,44 +268,74 @@ int soundfield_rows(fs_context* ctx, Source* const* srcs, int32_t count, const f
     { const int rc = ctx->sf_stage.fit(ctx, l.host_bytes, l.dev_bytes); if (rc) return rc; }
     char* hs = ctx->sf_stage.h; char* ds = ctx->sf_stage.d;
     ReverbPartItem* pitems = (ReverbPartItem*)(hs + l.up[kSfItems]);
-    int* plain = (int*)(hs + l.up[kSfLists]); int* fade = plain + count; int* take = fade + count;
-    int n_plain = 0, n_fade = 0, n_take = 0;
+    RowLists rows(ctx->sf_stage, l.up[kSfLists], count);
     std::memcpy(hs + l.in, in, sizeof(float) * in_row * (size_t)count);
     {
-        std::vector<std::unique_lock<std::mutex>> locks;   // held while the work is enqueued, not longer (reverb_rows)
-        locks.reserve((size_t)count);
-        for (int32_t i : order) locks.emplace_back(srcs[i]->ir_mu);
+        const auto locks = lock_rows(srcs, order, nullptr);
         for (int32_t i = 0; i < count; ++i) {
-            ReverbItem unused{};
             std::memset(&pitems[i], 0, sizeof(ReverbPartItem));
             bool takes = false;
-            const int rc = reverb_step(ctx, srcs[i], rs, frame, unused, pitems[i], &takes);
+            const int rc = reverb_step(ctx, srcs[i], rs, frame, nullptr, &pitems[i], &takes);
             if (rc) return rc;
-            if (takes) take[n_take++] = i;
-            if (pitems[i].h_to) fade[n_fade++] = i;
-            else plain[n_plain++] = i;
+            rows.add(i, takes, pitems[i].h_to != nullptr);
         }
         FS_HIP(ctx, hipMemcpyAsync(ds, hs, l.up_bytes, hipMemcpyHostToDevice, rs));
-        const int* d_plain = (const int*)(ds + l.up[kSfLists]);
-        ReverbSoundfieldBatch b{};
-        b.items = (const ReverbPartItem*)(ds + l.up[kSfItems]);
-        b.plain = d_plain; b.n_plain = n_plain;
-        b.fade = d_plain + count; b.n_fade = n_fade;
-        b.n = srcs[0]->part_n; b.K = srcs[0]->part_K; b.frame = frame; b.ir_size = ctx->num_samples; b.count = count;
-        b.W = ctx->d_rev_tw[srcs[0]->part_n];
-        b.in = (const float*)(ds + l.in);
-        b.out = (float*)(ds + l.d_out);
-        b.mix = mix ? (float*)(ds + l.d_mix) : nullptr;
-        if (n_take) {
-            launch_reverb_soundfield_take(b, d_plain + 2 * count, n_take, e, rs);
-            FS_HIP(ctx, hipGetLastError());
-            for (int k = 0; k < n_take; ++k) FS_HIP(ctx, hipEventRecord(srcs[take[k]]->ev_rev, rs));
-        }
-        launch_reverb_soundfield(b, e, rs);
+        const ReverbPartItem* d_items = (const ReverbPartItem*)(ds + l.up[kSfItems]);
+        const ReverbShape shape{ctx->d_rev_tw[srcs[0]->part_n], srcs[0]->part_n, srcs[0]->part_K, frame, ctx->num_samples};
+        { const int rc = take_rows(ctx, srcs, rows, rs, [&](const int* take, int n) { launch_reverb_soundfield_take(d_items, take, n, shape, e, rs); }); if (rc) return rc; }
+        launch_reverb_soundfield(d_items, shape, rows.dev(), e, count, (const float*)(ds + l.in), (float*)(ds + l.d_out),
+                                 mix ? (float*)(ds + l.d_mix) : nullptr, rs);
         FS_HIP(ctx, hipGetLastError());
     }
     { const int rc = callback_finish(ctx, ctx->sf_stage, l, out != nullptr, mix); if (rc) return rc; }
     if (out) std::memcpy(out, hs + l.h_out, sizeof(float) * row * (size_t)count);
+    return FS_OK;
+}
+
+// The per-row validation of the two batch entry points: soundfield says whose rows the call takes.  Everything is validated before
+// the first state change or enqueue: a refused call changes nothing.
+int batch_sources(fs_context* ctx, const fs_source* sources, int32_t count, bool soundfield, const int32_t* apply_reverb,
+                  std::vector<Source*>* srcs) {
+    srcs->resize((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        Source* s = (*srcs)[(size_t)i] = get_source(ctx, sources[i]);
+        if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+        if (!s->d_ring) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init has not been called for this source");
+        if (s->rev_sf != soundfield)
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, soundfield ? "the source is not initialised with the soundfield (fs_reverb_set_soundfield, then fs_reverb_init)"
+                                                                 : kSoundfieldSource);
+        if (s->rev_frame != (*srcs)[0]->rev_frame) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size");
+        const bool missing = soundfield ? !s->d_fade_to || (s->fade_len > 0 && !s->d_fade_from)
+                                        : (!apply_reverb || apply_reverb[i]) && s->fade_len > 0 && (!s->d_fade_from || !s->d_fade_to);
+        if (missing) return ctx->fail(FS_ERR_OUT_OF_MEMORY, kNoFadeBuffers);
+    }
+    return FS_OK;
+}
+
+// The two IR-copy entry points: launch(bands, d) writes the source's IRs, `floats` of them, to the device block d; they come back
+// as dst[k] <- d [k * each .. (k + 1) * each)
+template <class Launch>
+int copy_irs(fs_context* ctx, fs_source h, int32_t n, const float* carriers, const char* what, const char* no_set, size_t floats,
+             std::initializer_list<float*> dst, Launch launch) {
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
+    Source* s = get_source(ctx, h);
+    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
+    if (n != ctx->num_samples) return ctx->fail(FS_ERR_SIZE_MISMATCH, "n != num_samples");
+    if (!carriers) return ctx->fail(FS_ERR_INVALID_ARGUMENT, std::string(what) + no_set);
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    FS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));   // the reconstruct runs on the tail stream
+    float* d = nullptr;
+    FS_HIP(ctx, hipMalloc((void**)&d, sizeof(float) * floats));
+    launch(s->d_ir_bands, d);
+    hipError_t err = hipGetLastError();
+    const size_t each = floats / dst.size();
+    size_t k = 0;
+    for (float* to : dst)
+        if (err == hipSuccess) err = hipMemcpyAsync(to, d + each * k++, sizeof(float) * each, hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    if (err != hipSuccess) return ctx->hip_fail(err, what);
     return FS_OK;
 }
 
@@ -399,7 +431,7 @@ int fs_reverb_init(fs_context* ctx, fs_source h, int32_t frame_size) {
     s->rev_engine = s->rev_engine_next;
     s->rev_ears = s->rev_ears_next;
     s->rev_sf = s->rev_sf_next;
-    s->sf_P = s->rev_sf ? ((ctx->sf_order + 1) * (ctx->sf_order + 1) + 1) / 2 : 0;
+    s->part_sets = s->rev_sf ? ((ctx->sf_order + 1) * (ctx->sf_order + 1) + 1) / 2 : s->rev_ears ? 2 : 1;
     if (part) {   // N = the smallest power of two >= 2 F, K = ceil(num_samples / F)
         s->part_n = 5;
         while ((1 << s->part_n) < 2 * frame_size) ++s->part_n;
@@ -479,25 +511,9 @@ int fs_reverb_set_ears(fs_context* ctx, fs_source h, int32_t on) {
 
 int fs_reverb_copy_ear_impulse_responses(fs_context* ctx, fs_source h, float* left, float* right, int32_t n) {
     if (!ctx || !left || !right) return FS_ERR_INVALID_ARGUMENT;
-    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
-    FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
-    Source* s = get_source(ctx, h);
-    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-    if (n != ctx->num_samples) return ctx->fail(FS_ERR_SIZE_MISMATCH, "n != num_samples");
-    if (!ctx->d_ear_carrier) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_copy_ear_impulse_responses: no ear set is installed (fs_reverb_ears_set)");
-    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    FS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));   // the reconstruct runs on the tail stream
-    float* d = nullptr;
-    FS_HIP(ctx, hipMalloc((void**)&d, sizeof(float) * 2 * (size_t)n));
     const ReverbEars e{ctx->d_ear_carrier, ctx->cfg.num_bands, carrier_stride(ctx->num_samples)};
-    launch_reverb_ears_ir(s->d_ir_bands, e, n, d, d + n, ctx->stream);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemcpyAsync(left, d, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(right, d + n, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    if (err != hipSuccess) return ctx->hip_fail(err, "fs_reverb_copy_ear_impulse_responses");
-    return FS_OK;
+    return copy_irs(ctx, h, n, e.c, "fs_reverb_copy_ear_impulse_responses", ": no ear set is installed (fs_reverb_ears_set)", 2 * (size_t)n,
+                    {left, right}, [&](const float* bands, float* d) { launch_reverb_ears_ir(bands, e, n, d, d + n, ctx->stream); });
 }
 
 int fs_reverb_soundfield_set(fs_context* ctx, int32_t order) {
@@ -537,26 +553,9 @@ int fs_reverb_set_soundfield(fs_context* ctx, fs_source h, int32_t on) {
 
 int fs_reverb_copy_soundfield_impulse_responses(fs_context* ctx, fs_source h, float* out, int32_t n) {
     if (!ctx || !out) return FS_ERR_INVALID_ARGUMENT;
-    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
-    FS_FLUSH(ctx);   // pipelined frames: a held-back connect pass goes first
-    Source* s = get_source(ctx, h);
-    if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-    if (n != ctx->num_samples) return ctx->fail(FS_ERR_SIZE_MISMATCH, "n != num_samples");
-    if (!ctx->d_sf_carrier)
-        return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_copy_soundfield_impulse_responses: no soundfield set is installed (fs_reverb_soundfield_set)");
-    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    FS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));   // the reconstruct runs on the tail stream
     const ReverbSoundfield e = soundfield_set(ctx);
-    const size_t bytes = sizeof(float) * (size_t)e.C * (size_t)n;
-    float* d = nullptr;
-    FS_HIP(ctx, hipMalloc((void**)&d, bytes));
-    launch_reverb_soundfield_ir(s->d_ir_bands, e, n, d, ctx->stream);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    if (err != hipSuccess) return ctx->hip_fail(err, "fs_reverb_copy_soundfield_impulse_responses");
-    return FS_OK;
+    return copy_irs(ctx, h, n, e.c, "fs_reverb_copy_soundfield_impulse_responses", ": no soundfield set is installed (fs_reverb_soundfield_set)",
+                    (size_t)e.C * (size_t)n, {out}, [&](const float* bands, float* d) { launch_reverb_soundfield_ir(bands, e, n, d, ctx->stream); });
 }
 
 int fs_reverb_soundfield_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in, float* out,
@@ -566,17 +565,8 @@ int fs_reverb_soundfield_process_batch(fs_context* ctx, const fs_source* sources
     if (flags != 0) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_soundfield_process_batch: flags must be 0");
     if (count < 1 || count > FS_MAX_REVERB_BATCH)
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_REVERB_BATCH)");
-    // Everything is validated before the first state change or enqueue: a refused call changes nothing.
-    std::vector<Source*> srcs((size_t)count);
-    for (int32_t i = 0; i < count; ++i) {
-        Source* s = srcs[(size_t)i] = get_source(ctx, sources[i]);
-        if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-        if (!s->d_ring) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init has not been called for this source");
-        if (!s->rev_sf)
-            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the source is not initialised with the soundfield (fs_reverb_set_soundfield, then fs_reverb_init)");
-        if (s->rev_frame != srcs[0]->rev_frame) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size");
-        if (!s->d_fade_to || (s->fade_len > 0 && !s->d_fade_from)) return ctx->fail(FS_ERR_OUT_OF_MEMORY, kNoFadeBuffers);
-    }
+    std::vector<Source*> srcs;
+    { const int rc = batch_sources(ctx, sources, count, true, nullptr, &srcs); if (rc) return rc; }
     return soundfield_rows(ctx, srcs.data(), count, in, out, mix);
 }
 
@@ -620,17 +610,8 @@ int fs_reverb_process_batch(fs_context* ctx, const fs_source* sources, int32_t c
     if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
     if (count < 1 || count > FS_MAX_REVERB_BATCH)
         return ctx->fail(FS_ERR_INVALID_ARGUMENT, "count out of range (1 .. FS_MAX_REVERB_BATCH)");
-    // Everything is validated before the first state change or enqueue: a refused call changes nothing.
-    std::vector<Source*> srcs((size_t)count);
-    for (int32_t i = 0; i < count; ++i) {
-        Source* s = srcs[(size_t)i] = get_source(ctx, sources[i]);
-        if (!s) return ctx->fail(FS_ERR_BAD_HANDLE, "bad source handle");
-        if (!s->d_ring) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_reverb_init has not been called for this source");
-        if (s->rev_sf) return ctx->fail(FS_ERR_INVALID_ARGUMENT, kSoundfieldSource);
-        if (s->rev_frame != srcs[0]->rev_frame) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "the sources of a batch share one frame size");
-        if ((!apply_reverb || apply_reverb[i]) && s->fade_len > 0 && (!s->d_fade_from || !s->d_fade_to))
-            return ctx->fail(FS_ERR_OUT_OF_MEMORY, kNoFadeBuffers);
-    }
+    std::vector<Source*> srcs;
+    { const int rc = batch_sources(ctx, sources, count, false, apply_reverb, &srcs); if (rc) return rc; }
     return reverb_rows(ctx, srcs.data(), count, in, out, apply_reverb, flags, mix);
 }
 

@@ -178,20 +178,20 @@ struct Source {
     unsigned rev_head = 0; int rev_frame = 0;
     // fs_reverb_set_engine: the engine the next fs_reverb_init gives the source / the one it was initialised with.  PARTITIONED
     // (fs_reverb_part.hip): d_ring is the engine's state block (ReverbPartItem: window history, products, delay line), float2
-    // [part_state_elems(part_n, part_K)]; N = 1 << part_n the transform, part_K partitions, part_slot the delay line's next slot;
-    // d_fade_to / d_fade_from below are partition spectra [part_K][N] float2, and d_fade_to exists without a fade length too:
-    // every callback convolves its own spectra, taken like a crossfade's h_to (fade_primed, fade_gen).
+    // [part_state_elems]; N = 1 << part_n the transform, part_K partitions, part_slot the delay line's next slot;
+    // d_fade_to / d_fade_from below are partition spectra [part_sets][part_K][N] float2, and d_fade_to exists without a fade length
+    // too: every callback convolves its own spectra, taken like a crossfade's h_to (fade_primed, fade_gen).
+    // part_sets: the spectrum sets of an IR copy — 1, with ears 2 (M_p, then S_p), a soundfield source's P = ceil(C / 2) channel pairs
     int32_t rev_engine_next = FS_REVERB_ENGINE_DIRECT, rev_engine = FS_REVERB_ENGINE_DIRECT;
-    int part_n = 0, part_K = 0, part_slot = 0;
-    // fs_reverb_set_ears: the choice for the next fs_reverb_init / what the source was initialised with.  With ears, d_fade_to /
-    // d_fade_from are [2][part_K][N] (M_p, then S_p), taken from the band rows and the context's ear carriers of generation ear_gen.
+    int part_n = 0, part_K = 0, part_slot = 0, part_sets = 0;
+    // fs_reverb_set_ears: the choice for the next fs_reverb_init / what the source was initialised with.  With ears, the spectra are
+    // taken from the band rows and the context's ear carriers of generation ear_gen.
     bool rev_ears_next = false, rev_ears = false;
     uint64_t ear_gen = 0;
-    // fs_reverb_set_soundfield: likewise.  A soundfield source is a partitioned one whose d_ring is the soundfield state block (float2
-    // [sf_state_elems(part_n, part_K, P)], P = ceil(C / 2) of the set installed at its init) and whose d_fade_to / d_fade_from are
-    // [P][part_K][N], taken from the band rows and the context's soundfield carriers of generation sf_gen
+    // fs_reverb_set_soundfield: likewise.  A soundfield source is a partitioned one whose d_ring is the state block of a mono row
+    // with P products (P of the set installed at its init) and whose spectra are taken from the band rows and the context's
+    // soundfield carriers of generation sf_gen
     bool rev_sf_next = false, rev_sf = false;
-    int sf_P = 0;
     uint64_t sf_gen = 0;
     // crossfade between successive IRs (fs_reverb_set_crossfade; the callback's own state, audio thread): fade_len L samples
     // (0: off), the callback's copies of the IRs it fades between (h_to = the newest it took, generation fade_gen),
@@ -744,6 +744,8 @@ int check_band_edges(fs_context* ctx, const double* edges, const char* what);
 int check_spectral(fs_context* ctx, const fs_params* p);
 // the carrier set a reconstruct with these params uses: nullptr without FS_FLAG_SPECTRAL_IR; built (and waited for) on first use
 int carrier_for(fs_context* ctx, const fs_params* p, const float** out);
+// W[k] = exp(-2 pi i k / N), k < N / 2, computed in double: the twiddle table of every N-point transform (N a power of two; N < 2: [1])
+std::vector<float2> host_twiddles(size_t N);
 // fs_reverb_ears_set's build for the band edges in force: a new [2][B][carrier_stride] set on the compute stream, waited for
 int build_ear_carriers(fs_context* ctx, float radius_cm, float speed_cm_s, const char* what, float** out);
 // ... and its installation in place of the one in force (nullptr: none), behind the reverb stream

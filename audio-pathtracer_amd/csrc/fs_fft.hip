@@ -161,15 +161,18 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     return z ^ (z >> 31);
 }
 // the band's one-sided spectrum in bit-reversed order: position p holds bin k = brev(p); bins [lo_b, lo_{b+1}) of the band
-// get exp(i phi_k), phi_k = 2 pi (splitmix64(kCarrierSeed + k) >> 40) 2^-24 (cos / sin in double), every other bin 0
-__global__ __launch_bounds__(kFftBlock) void carrier_spectrum(float2* __restrict__ X, int n, CarrierBands bands) {
+// get exp(i phi_k), phi_k = 2 pi (splitmix64(seed + k) >> 40) 2^-24 (cos / sin in double), every other bin 0.  seed = kCarrierSeed +
+// (c << 32) for channel c of the soundfield reverb, c = 0 for the spectral IR: channel 0 has its phases, and the streams seed + k
+// (k < 2^24) of two channels never meet
+__global__ __launch_bounds__(kFftBlock) void carrier_spectrum(float2* __restrict__ X, int n, int c, CarrierBands bands) {
     const uint32_t p = blockIdx.x * kFftBlock + threadIdx.x;
     if (p >= (1u << n)) return;
     const int b = blockIdx.y;
     const uint32_t k = __brev(p) >> (32 - n);
     float2 v = make_float2(0.0f, 0.0f);
     if ((int)k >= bands.lo[b] && (int)k < bands.lo[b + 1]) {
-        const double turns = (double)(uint32_t)(splitmix64(kCarrierSeed + k) >> 40) * 0x1p-24;   // (exact)
+        const uint64_t seed = kCarrierSeed + ((uint64_t)(uint32_t)c << 32);
+        const double turns = (double)(uint32_t)(splitmix64(seed + k) >> 40) * 0x1p-24;   // (exact)
         double sn, cs;
         sincospi(2.0 * turns, &sn, &cs);
         v = make_float2((float)cs, (float)sn);
@@ -238,24 +241,21 @@ __global__ __launch_bounds__(kFftBlock) void ear_carrier_normalise(float* __rest
     }
 }
 
-// ---- fs_reverb_soundfield_set: channel c's band carriers (launch_build_soundfield_carriers).  blockIdx.y = band ----
-// As carrier_spectrum with the channel's seed, kCarrierSeed + (c << 32): channel 0 has the spectral IR's phases, and the streams
-// seed_c + k (k < 2^24) of two channels never meet
-__global__ __launch_bounds__(kFftBlock) void soundfield_carrier_spectrum(float2* __restrict__ X, int n, int c, CarrierBands bands) {
-    const uint32_t p = blockIdx.x * kFftBlock + threadIdx.x;
-    if (p >= (1u << n)) return;
-    const int b = blockIdx.y;
-    const uint32_t k = __brev(p) >> (32 - n);
-    float2 v = make_float2(0.0f, 0.0f);
-    if ((int)k >= bands.lo[b] && (int)k < bands.lo[b + 1]) {
-        const uint64_t seed = kCarrierSeed + ((uint64_t)(uint32_t)c << 32);
-        const double turns = (double)(uint32_t)(splitmix64(seed + k) >> 40) * 0x1p-24;   // (exact)
-        double sn, cs;
-        sincospi(2.0 * turns, &sn, &cs);
-        v = make_float2((float)cs, (float)sn);
-    }
-    X[((size_t)b << n) + p] = v;
+// The real part of the inverse transform of `rows` spectra X [rows][K] (K = 2^n, bit-reversed order) through the material filter's
+// own inverse passes, unscaled: gains all 1 (alpha = sigma = 0 from `zeros`; which = 0 per row for the LDS pass, whose input is one
+// array; the global passes batched over the rows on blockIdx.y).  y: [rows][K] work buffer; out: [rows][ld], the first ld samples.
+void inverse_rows(int rows, int n, int ld, const float2* X, float2* y, const float2* W, const float* zeros, float* out, hipStream_t s) {
+    const int K = 1 << n;
+    const int c = n < kFftChunkLog ? n : kFftChunkLog;
+    const size_t lds = sizeof(float2) << c;
+    for (int r = 0; r < rows; ++r)
+        hipLaunchKernelGGL(fft_dit_local, dim3(1u << (n - c), 1), dim3(kFftBlock), lds, s, X + ((size_t)r << n), y + ((size_t)r << n),
+                           zeros, zeros, zeros, W, n, c, ld, out + (size_t)r * ld, 1.0f);
+    const unsigned half_blocks = (unsigned)(((K >> 1) + kFftBlock - 1) / kFftBlock);
+    for (int ls = c; ls < n; ++ls)
+        hipLaunchKernelGGL(fft_dit_global, dim3(half_blocks, (unsigned)rows), dim3(kFftBlock), 0, s, y, W, n, ls, ld, out, 1.0f);
 }
+unsigned spectrum_blocks(int n) { return (unsigned)(((1 << n) + kFftBlock - 1) / kFftBlock); }
 
 }  // namespace
 
@@ -286,23 +286,13 @@ void launch_apply_material_fd(const float* in, int L, int n, float2* x, float2* 
 namespace fs {
 
 // The band carriers of FS_FLAG_SPECTRAL_IR: r_b[t] = sum_{k in band b} cos(2 pi k t / K + phi_k), t < N, K = 2^n >= N — the real
-// part of the inverse DFT of the band's unit-magnitude random-phase one-sided spectrum — through the material filter's own inverse
-// passes (gains all 1: alpha = sigma = 0 from `zeros`; which = 0 per band for the LDS pass, whose input is one array; the global
-// passes batched over the bands on blockIdx.y), then scaled to a mean square of 1 over the IR.  X, y: [B][K] complex work buffers,
-// W: [max(K/2,1)] twiddles (exp(-2 pi i k / K), double precision on the host), zeros: [K/2 + 1], out: [B][ld] (ld >= N, ld <= K or
-// the row is zero-padded).
+// part of the inverse DFT of the band's unit-magnitude random-phase one-sided spectrum (inverse_rows) — then scaled to a mean square
+// of 1 over the IR.  X, y: [B][K] complex work buffers, W: [max(K/2,1)] twiddles (exp(-2 pi i k / K), double precision on the host),
+// zeros: [K/2 + 1], out: [B][ld] (ld >= N, ld <= K or the row is zero-padded).
 void launch_build_carriers(int B, int n, int N, int ld, const CarrierBands& bands, float2* X, float2* y, const float2* W,
                            const float* zeros, float* out, hipStream_t s) {
-    const int K = 1 << n;
-    const int c = n < kFftChunkLog ? n : kFftChunkLog;
-    const size_t lds = sizeof(float2) << c;
-    hipLaunchKernelGGL(carrier_spectrum, dim3((unsigned)((K + kFftBlock - 1) / kFftBlock), (unsigned)B), dim3(kFftBlock), 0, s, X, n, bands);
-    for (int b = 0; b < B; ++b)
-        hipLaunchKernelGGL(fft_dit_local, dim3(1u << (n - c), 1), dim3(kFftBlock), lds, s, X + ((size_t)b << n), y + ((size_t)b << n),
-                           zeros, zeros, zeros, W, n, c, ld, out + (size_t)b * ld, 1.0f);
-    const unsigned half_blocks = (unsigned)(((K >> 1) + kFftBlock - 1) / kFftBlock);
-    for (int ls = c; ls < n; ++ls)
-        hipLaunchKernelGGL(fft_dit_global, dim3(half_blocks, (unsigned)B), dim3(kFftBlock), 0, s, y, W, n, ls, ld, out, 1.0f);
+    hipLaunchKernelGGL(carrier_spectrum, dim3(spectrum_blocks(n), (unsigned)B), dim3(kFftBlock), 0, s, X, n, 0, bands);
+    inverse_rows(B, n, ld, X, y, W, zeros, out, s);
     hipLaunchKernelGGL(carrier_normalise, dim3((unsigned)B), dim3(kFftBlock), 0, s, out, N, ld);
 }
 
@@ -311,17 +301,9 @@ void launch_build_carriers(int B, int n, int N, int ld, const CarrierBands& band
 // X, y: [2B][K] complex work buffers; W, zeros as above; out: [2][B][ld].
 void launch_build_ear_carriers(int B, int n, int N, int ld, const CarrierBands& bands, double fs, double radius_cm, double speed_cm_s,
                                float2* X, float2* y, const float2* W, const float* zeros, float* out, hipStream_t s) {
-    const int K = 1 << n;
-    const int c = n < kFftChunkLog ? n : kFftChunkLog;
-    const size_t lds = sizeof(float2) << c;
-    hipLaunchKernelGGL(ear_carrier_spectrum, dim3((unsigned)((K + kFftBlock - 1) / kFftBlock), (unsigned)(2 * B)), dim3(kFftBlock), 0, s, X,
-                       n, B, bands, fs, radius_cm, speed_cm_s);
-    for (int r = 0; r < 2 * B; ++r)
-        hipLaunchKernelGGL(fft_dit_local, dim3(1u << (n - c), 1), dim3(kFftBlock), lds, s, X + ((size_t)r << n), y + ((size_t)r << n),
-                           zeros, zeros, zeros, W, n, c, ld, out + (size_t)r * ld, 1.0f);
-    const unsigned half_blocks = (unsigned)(((K >> 1) + kFftBlock - 1) / kFftBlock);
-    for (int ls = c; ls < n; ++ls)
-        hipLaunchKernelGGL(fft_dit_global, dim3(half_blocks, (unsigned)(2 * B)), dim3(kFftBlock), 0, s, y, W, n, ls, ld, out, 1.0f);
+    hipLaunchKernelGGL(ear_carrier_spectrum, dim3(spectrum_blocks(n), (unsigned)(2 * B)), dim3(kFftBlock), 0, s, X, n, B, bands, fs, radius_cm,
+                       speed_cm_s);
+    inverse_rows(2 * B, n, ld, X, y, W, zeros, out, s);
     hipLaunchKernelGGL(ear_carrier_normalise, dim3((unsigned)B), dim3(kFftBlock), 0, s, out, B, N, ld);
 }
 
@@ -330,19 +312,9 @@ void launch_build_ear_carriers(int B, int n, int N, int ld, const CarrierBands& 
 // channels); then every one of the C B rows gets the scale of a row of its own, g_{c,b} = sqrt(N / sum r_{c,b}^2).  out: [C][B][ld].
 void launch_build_soundfield_carriers(int C, int B, int n, int N, int ld, const CarrierBands& bands, float2* X, float2* y, const float2* W,
                                       const float* zeros, float* out, hipStream_t s) {
-    const int K = 1 << n;
-    const int c = n < kFftChunkLog ? n : kFftChunkLog;
-    const size_t lds = sizeof(float2) << c;
-    const unsigned half_blocks = (unsigned)(((K >> 1) + kFftBlock - 1) / kFftBlock);
     for (int ch = 0; ch < C; ++ch) {
-        float* rows = out + (size_t)ch * (size_t)B * (size_t)ld;
-        hipLaunchKernelGGL(soundfield_carrier_spectrum, dim3((unsigned)((K + kFftBlock - 1) / kFftBlock), (unsigned)B), dim3(kFftBlock), 0, s,
-                           X, n, ch, bands);
-        for (int b = 0; b < B; ++b)
-            hipLaunchKernelGGL(fft_dit_local, dim3(1u << (n - c), 1), dim3(kFftBlock), lds, s, X + ((size_t)b << n), y + ((size_t)b << n),
-                               zeros, zeros, zeros, W, n, c, ld, rows + (size_t)b * ld, 1.0f);
-        for (int ls = c; ls < n; ++ls)
-            hipLaunchKernelGGL(fft_dit_global, dim3(half_blocks, (unsigned)B), dim3(kFftBlock), 0, s, y, W, n, ls, ld, rows, 1.0f);
+        hipLaunchKernelGGL(carrier_spectrum, dim3(spectrum_blocks(n), (unsigned)B), dim3(kFftBlock), 0, s, X, n, ch, bands);
+        inverse_rows(B, n, ld, X, y, W, zeros, out + (size_t)ch * (size_t)B * (size_t)ld, s);
     }
     hipLaunchKernelGGL(carrier_normalise, dim3((unsigned)(C * B)), dim3(kFftBlock), 0, s, out, N, ld);
 }

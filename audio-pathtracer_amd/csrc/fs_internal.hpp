@@ -656,8 +656,8 @@ struct ReverbItem {
 static_assert(sizeof(ReverbItem) == 72, "ReverbItem: six pointers and six words, the host's staging layout");
 // fs_reverb_part.hip (FS_REVERB_ENGINE_PARTITIONED): the descriptor of row i of the call is pitems[i]; active == 0 for every row
 // that is not a convolved row of this engine.  A source's state is one block of float2 (Source::d_ring), all spectra in the
-// transforms' bit-reversed order:  hist [N] the window history ring (left + i right) | x_now [N] the literal-tail window's
-// spectrum | Y [2][N] the products (H, H_to) | xring [K][N] the delay line of window spectra;  N = 1 << n.
+// transforms' bit-reversed order: the window history ring (left + i right, or the mono downmix), the literal-tail window's spectrum,
+// the products and the delay line of window spectra (the accessors below).
 struct ReverbPartItem {
     const float2* h;       // partition spectra [K][N] (H_from while a crossfade runs) ...
     const float2* h_to;    // ... and those it fades to (null: one product)
@@ -672,20 +672,28 @@ struct ReverbPartItem {
     int32_t active;
 };
 static_assert(sizeof(ReverbPartItem) == 72, "ReverbPartItem: six pointers and six words, the host's staging layout");
-__host__ __device__ inline float2* part_hist(float2* state, int n) { return state; }
+// The engine's rows come in two kinds.  A STEREO row (plain or with ears) keeps a float2 history and the literal tail's x_now; a
+// mono row (the soundfield bus) keeps a float history, N floats = N / 2 float2, and no x_now.  `acc` is the number of
+// products a row keeps per IR copy: 1 for a stereo row, P = ceil(C / 2) channel pairs for the bus.  The regions, in float2:
+//   hist [N or N / 2] | x_now [N] (stereo) | Y [2][acc][N] the products (H, H_to) | xring [K][N] the delay line;  N = 1 << n.
+__host__ __device__ inline float2* part_hist(float2* state) { return state; }   // (mono: read as N floats)
 __host__ __device__ inline float2* part_xnow(float2* state, int n) { return state + ((size_t)1 << n); }
-__host__ __device__ inline float2* part_y(float2* state, int n) { return state + ((size_t)2 << n); }
-__host__ __device__ inline float2* part_xring(float2* state, int n) { return state + ((size_t)4 << n); }
-constexpr size_t part_state_elems(int n, int K) { return ((size_t)4 + (size_t)K) << n; }
-struct ReverbPart {
-    const int* plain; int n_plain;  // rows with one product ...
-    const int* fade; int n_fade;    // ... and with two
+__host__ __device__ inline float2* part_y(float2* state, int n, bool stereo) { return state + (stereo ? (size_t)2 << n : (size_t)1 << (n - 1)); }
+__host__ __device__ inline float2* part_xring(float2* state, int n, bool stereo, int acc) {
+    return stereo ? state + ((size_t)(2 + 2 * acc) << n) : state + ((size_t)1 << (n - 1)) + ((size_t)(2 * acc) << n);
+}
+constexpr size_t part_state_elems(int n, int K, bool stereo, int acc) {
+    return stereo ? (size_t)(2 + 2 * acc + K) << n : ((size_t)1 << (n - 1)) + ((size_t)(2 * acc + K) << n);
+}
+// the engine's shape in one call: every partitioned row of a call has one frame size and one context, so one N and K
+struct ReverbShape {
     const float2* W;                // twiddles of N = 1 << n
     int n, K, frame, ir_size;
-    // the rows of sources with ears (fs_reverb_set_ears): partitioned rows with lists of their own and two spectrum sets per IR
-    // copy — ReverbPartItem::h, h_to, take_from, take_to each [2][K][N], M_p then S_p; take_ir = the source's B band rows
-    const int* ear_plain; int n_ear_plain;
-    const int* ear_fade; int n_ear_fade;
+};
+// the rows of one kind (plain, ears, bus) in a call, by what their product is
+struct ReverbLists {
+    const int* plain; int n_plain;  // rows with one product ...
+    const int* fade; int n_fade;    // ... and with two
 };
 // fs_reverb_ears_set's carrier set, as the ear kernels read it: c [2][B][ld] fp32 (mid rows, then side rows)
 struct ReverbEars {
@@ -699,23 +707,6 @@ struct ReverbSoundfield {
     int B, ld, C;
     float w[4];
 };
-// A soundfield source's state (Source::d_ring), in float2: hist [N / 2] — the mono window history ring as N floats — | Y [2][P][N]
-// the products (G, G_to) of the P = ceil(C / 2) channel pairs | xring [K][N] the delay line of the mono window's spectra
-__host__ __device__ inline float* sf_hist(float2* state) { return (float*)state; }
-__host__ __device__ inline float2* sf_y(float2* state, int n) { return state + ((size_t)1 << (n - 1)); }
-__host__ __device__ inline float2* sf_xring(float2* state, int n, int P) { return state + ((size_t)1 << (n - 1)) + ((size_t)(2 * P) << n); }
-constexpr size_t sf_state_elems(int n, int K, int P) { return ((size_t)1 << (n - 1)) + ((size_t)(2 * P + K) << n); }
-// fs_reverb_soundfield_process_batch: every row of the call is a soundfield row of one frame size, order and (n, K)
-struct ReverbSoundfieldBatch {
-    const ReverbPartItem* items;    // [count]: h, h_to, take_from, take_to each [P][K][N]; take_ir = the source's B band rows
-    const int* plain; int n_plain;  // rows with one product per pair ...
-    const int* fade; int n_fade;    // ... and with two
-    const float2* W;                // twiddles of N = 1 << n
-    int n, K, frame, ir_size, count;
-    const float* in;                // [count][2 * frame] interleaved stereo
-    float* out;                     // [count][frame * C], element s * C + c
-    float* mix;                     // [frame * C], or null
-};
 struct ReverbBatch {
     const ReverbItem* items;        // [count]
     const int* plain; int n_plain;  // rows convolved with one IR ...
@@ -727,7 +718,10 @@ struct ReverbBatch {
     float* mix;                     // [2 * frame], or null
     int n_direct;                   // convolved rows of the direct engine + bypassed rows: what the prepare pass serves
     const ReverbPartItem* pitems;   // [count]: the rows of the partitioned engine (null: none in this call)
-    ReverbPart part;
+    ReverbShape part;
+    // its plain rows, and the rows of sources with ears (fs_reverb_set_ears): two spectrum sets per IR copy — ReverbPartItem::h,
+    // h_to, take_from, take_to each [2][K][N], M_p then S_p; take_ir = the source's B band rows
+    ReverbLists part_rows, ear_rows;
 };
 // take: the rows whose crossfade starts in this callback (n_take >= 1), n = IR samples
 void launch_reverb_batch_fade_start(const ReverbItem* items, const int* take, int n_take, int n, hipStream_t s);
@@ -737,20 +731,23 @@ void launch_reverb_batch(const ReverbBatch& b, hipStream_t s);
 // the mix of the audio callbacks (the reverb's, the direct sound's, the voice banks'): mix [row] = the fp32 sum of out [count][row]
 // over the rows, in list order; row = a row's length in floats (2 * frame, or C * frame of the ambisonic bus)
 void launch_callback_mix(const float* out, int count, int row, float* mix, hipStream_t s);
-// take: the partitioned rows that take a newer IR in this callback (n_take >= 1)
-void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, hipStream_t s);
-void launch_reverb_ears_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, const ReverbEars& e, hipStream_t s);
+// take: the partitioned rows that take a newer IR in this callback (n_take >= 1), one launcher per row kind
+void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbShape& p, hipStream_t s);
+void launch_reverb_ears_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbShape& p, const ReverbEars& e, hipStream_t s);
+void launch_reverb_soundfield_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbShape& p, const ReverbSoundfield& e,
+                                   hipStream_t s);
 // fs_reverb_copy_ear_impulse_responses: left = m + s, right = m - s of the B band rows `bands` ([B][n]), with the take's expression
 void launch_reverb_ears_ir(const float* bands, const ReverbEars& e, int n, float* left, float* right, hipStream_t s);
-// the soundfield rows (fs_reverb_soundfield_process_batch): the take of the rows that take in this callback (n_take >= 1) ...
-void launch_reverb_soundfield_take(const ReverbSoundfieldBatch& b, const int* take, int n_take, const ReverbSoundfield& e, hipStream_t s);
-// ... the mono window transforms, the products of the two lists, the P inverses per row and the mix (when b.mix)
-void launch_reverb_soundfield(const ReverbSoundfieldBatch& b, const ReverbSoundfield& e, hipStream_t s);
 // fs_reverb_copy_soundfield_impulse_responses: out [C][n] = h_c of the B band rows `bands` ([B][n]), with the take's expression
 void launch_reverb_soundfield_ir(const float* bands, const ReverbSoundfield& e, int n, float* out, hipStream_t s);
-// the window transforms, the products of the four lists (each launched only when it has rows), the inverse and epilogue
-void launch_reverb_part(const ReverbPartItem* items, const ReverbPart& p, int count, int literal_tail, const float* in, float* out,
-                        hipStream_t s);
+// the stereo rows: the window transforms, the products of the four lists (each launched only when it has rows), the inverse and epilogue
+void launch_reverb_part(const ReverbPartItem* items, const ReverbShape& p, const ReverbLists& rows, const ReverbLists& ears, int count,
+                        int literal_tail, const float* in, float* out, hipStream_t s);
+// the soundfield rows (fs_reverb_soundfield_process_batch: every row of the call is one, items [count] with h, h_to, take_from, take_to
+// each [P][K][N]): the mono window transforms, the products of the two lists, the P inverses per row and the mix (when mix).
+// in [count][2 * frame] interleaved stereo; out [count][frame * C], element s * C + c; mix [frame * C], or null
+void launch_reverb_soundfield(const ReverbPartItem* items, const ReverbShape& p, const ReverbLists& rows, const ReverbSoundfield& e, int count,
+                              const float* in, float* out, float* mix, hipStream_t s);
 // fs_direct_render.hip (the direct-sound callback).  A source's state is one device block (Source::dr.d): this header, then at
 // kDirectRenderHeader bytes the two history rings [2][ring] (ring a power of two); zeroed = not primed, nothing heard yet.
 struct DirectRenderState {

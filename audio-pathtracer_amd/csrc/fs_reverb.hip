@@ -200,7 +200,7 @@ void launch_reverb_batch(const ReverbBatch& b, hipStream_t s) {
                            b.cur, b.frame, b.out);
     if (!fused && b.n_plain + b.n_fade > 0)
         hipLaunchKernelGGL(reverb_batch_prepare_kernel, rows, dim3(tb), 0, s, b.items, b.in, b.cur, b.out, b.frame, b.literal_tail, kRevPush);
-    if (b.pitems) launch_reverb_part(b.pitems, b.part, b.count, b.literal_tail, b.in, b.out, s);
+    if (b.pitems) launch_reverb_part(b.pitems, b.part, b.part_rows, b.ear_rows, b.count, b.literal_tail, b.in, b.out, s);
     if (b.mix) launch_callback_mix(b.out, b.count, 2 * b.frame, b.mix, s);
 }
 

@@ -4,7 +4,7 @@
 // With frame F, N = the smallest power of two >= 2F and K = ceil(ir_size / F):
 //   H_p = FFT_N(h[pF .. pF + F) zero-padded), p < K                      reverb_part_take_kernel (only when a newer IR is taken)
 //   X_t = FFT_N(w_L + i w_R), w = the last N samples ending in this block  reverb_part_forward_kernel -> a ring of K spectra
-//   Y   = sum_{p < K} H_p X_{t-p}                                         reverb_part_mac_kernel
+//   Y   = sum_{p < K} H_p X_{t-p}                                         reverb_product_kernel
 //   y   = IFFT_N(Y); out = the last F of y, real part left, imaginary part right   reverb_part_inverse_kernel
 // The IR is real and mono, so one complex transform carries both channels.  The cost of a callback is K N complex MACs and
 // three N-point transforms (0.1 M MACs at F = 1024 and 48 000 taps; the direct form needs 98 M), and the history is one window
@@ -19,12 +19,14 @@
 // nothing a row computes depends on the other rows, so a source gets the same bits alone or in any batch.  The file is built
 // with -ffp-contract=off: what is fused is written as fmaf.
 //
-// A source with ears (fs_reverb_set_ears) is such a row with two spectrum sets per IR copy and a take and a product of its own
-// (reverb_ears_take_kernel, reverb_ears_mac_kernel, at the end of the kernels); the window, delay line, inverse and fade are shared.
-//
-// A soundfield source (fs_reverb_set_soundfield) has a callback and a state block of its own: a mono window, ceil(C / 2) complex
-// IRs that each carry two channels of the ambisonic bus, and one inverse per pair (the reverb_soundfield_* kernels, behind the
-// ear kernels); of the kernels above it uses the two LDS transforms and the order of the product's sums.
+// ONE engine, three kinds of row.  They share the delay line, the product's scaffold (reverb_product_kernel: tiling, slot walk,
+// order of sums), the inverse with its fade (reverb_part_inverse_kernel) and the fold of a cut-short fade (fold_cut_short); a kind
+// says how many products a row keeps, what one partition adds to each and how its state block is laid out (PlainRow, EarRow, BusRow):
+//   plain   one spectrum set per IR copy, from the mono IR; a stereo window (left + i right)         reverb_part_take_kernel
+//   ears    (fs_reverb_set_ears) two sets, M_p and S_p, from the band rows and the ear carriers; the product adds the mirrored
+//           bin's term; window, delay line and inverse are the plain row's                          reverb_ears_take_kernel
+//   bus     (fs_reverb_set_soundfield) P = ceil(C / 2) sets, complex IRs that each carry two channels of the ambisonic bus; a
+//           mono window (reverb_soundfield_forward_kernel), P products and one inverse per pair     reverb_soundfield_take_kernel
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -83,8 +85,19 @@ __device__ __forceinline__ void lds_fft_dit(float2* sh, const float2* __restrict
     __syncthreads();
 }
 
-// The rows of `take` get a newer IR: workgroup (p, k) owns partition p of row take[k].  First the fold of a fade that is cut
-// short, H_from[p] := (1 - a) H_from[p] + a H_to[p] (a = p0 / L > 0; exact on the spectra, the transform is linear), then
+// The fold of a fade that is cut short, on partition p of `sets` spectrum sets (h_from, h_to: the partition in the first set, `set`
+// float2 from one set to the next): H_from[p] := (1 - a) H_from[p] + a H_to[p], a = p0 / L > 0 — exact on the spectra, the transform
+// is linear.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void fold_cut_short(float2* __restrict__ h_from, const float2* __restrict__ h_to, size_t set, int sets, float a,
+                                               uint32_t N) {
+    for (int q = 0; q < sets; ++q)
+        for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) {
+            const float2 f = h_from[q * set + i], t = h_to[q * set + i];
+            h_from[q * set + i] = make_float2((1.0f - a) * f.x + a * t.x, (1.0f - a) * f.y + a * t.y);
+        }
+}
+
+// The rows of `take` get a newer IR: workgroup (p, k) owns partition p of row take[k].  First the fold (when take_a > 0), then
 // H_to[p] := FFT_N(ir[pF .. pF + F) zero-padded).
 __global__ __launch_bounds__(kPartBlock) void reverb_part_take_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ take,
                                                                       const float2* __restrict__ W, int n, int frame, int ir_size) {
@@ -93,14 +106,7 @@ __global__ __launch_bounds__(kPartBlock) void reverb_part_take_kernel(const Reve
     const uint32_t N = 1u << n;
     const uint32_t p = blockIdx.x;
     float2* __restrict__ h_to = it.take_to + (size_t)p * N;
-    const float a = it.take_a;
-    if (a > 0.0f) {
-        float2* __restrict__ h_from = it.take_from + (size_t)p * N;
-        for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) {
-            const float2 f = h_from[i], t = h_to[i];
-            h_from[i] = make_float2((1.0f - a) * f.x + a * t.x, (1.0f - a) * f.y + a * t.y);
-        }
-    }
+    if (it.take_a > 0.0f) fold_cut_short(it.take_from + (size_t)p * N, h_to, 0, 1, it.take_a, N);
     const float* __restrict__ ir = it.take_ir;
     const uint32_t k0 = p * (uint32_t)frame;
     for (uint32_t i = threadIdx.x; i < N; i += kPartBlock)
@@ -124,7 +130,7 @@ __global__ __launch_bounds__(kPartBlock) void reverb_part_forward_kernel(const R
     const uint32_t N = 1u << n;
     const bool literal = blockIdx.y != 0;
     const float* __restrict__ in = in_all + (size_t)r * 2 * (size_t)frame;
-    float2* __restrict__ hist = part_hist(it.state, n);
+    float2* __restrict__ hist = part_hist(it.state);
     const uint32_t old = N - (uint32_t)frame;
     for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) {
         float2 v;
@@ -142,71 +148,137 @@ __global__ __launch_bounds__(kPartBlock) void reverb_part_forward_kernel(const R
         sh[j] = v;
     }
     lds_fft_dif(sh, W, n);
-    float2* __restrict__ dst = literal ? part_xnow(it.state, n) : part_xring(it.state, n) + ((size_t)it.slot << n);
+    float2* __restrict__ dst = literal ? part_xnow(it.state, n) : part_xring(it.state, n, true, 1) + ((size_t)it.slot << n);
     for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) dst[j] = sh[j];
 }
 
-// The product of row list[blockIdx.y] over the delay line: Y[b] = sum_p H_p[b] X_{t-p}[b], X_{t-p} = spectrum ring slot
-// (slot - p) mod K (p = 0: x_now in a literal-tail callback).  A workgroup owns 64 adjacent bins, so every load of a wavefront is
-// 512 contiguous bytes; its four wavefronts take p = w, w + 4, ... in ascending order and their sums meet in LDS as
-// ((s0 + s1) + s2) + s3 — an order fixed by K alone.  FADE: the same X against H_from and H_to, two sums (Y[0], Y[1]).
-template <bool FADE>
-__global__ __launch_bounds__(kPartBlock) void reverb_part_mac_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ list,
-                                                                     int n, int K, int literal) {
-    __shared__ float2 s_sum[FADE ? 2 : 1][kMacWaves][kMacBins];
+// acc + s conj(x), each component two fused steps in a fixed order
+__device__ __forceinline__ float2 pmac_conj(float2 acc, float2 s, float2 x) {
+    return make_float2(fmaf(s.x, x.x, fmaf(s.y, x.y, acc.x)), fmaf(s.y, x.x, fmaf(-s.x, x.y, acc.y)));
+}
+
+// The three kinds of row, as the product sees them: kAcc products per IR copy, kStereo (the state block's layout, and whether a
+// literal tail exists), kMirror (whether step reads the window's mirrored bin too), the unroll of the partition loop, and step — what
+// partition p adds to one product: H the bin in partition p of the product's first spectrum set, `set` float2 from a set to the
+// next, x the window spectrum's bin and xm its mirror's.
+struct PlainRow {   // acc += H_p X
+    static constexpr int kAcc = 1, kUnroll = 4;
+    static constexpr bool kStereo = true, kMirror = false;
+    static __device__ __forceinline__ float2 step(float2 acc, const float2* __restrict__ H, size_t set, float2 x, float2 xm) {
+        return pmac(acc, H[0], x);
+    }
+};
+// Both channels through the one packed transform: Y[k] = M_p[k] X[k] + S_p[k] conj(X[(N - k) mod N]).  Position j of the bit-reversed
+// storage holds bin brev(j); the bin N - brev(j) (mod N) lives at jm = brev((N - brev(j)) mod N).  The mirrors of a 64-aligned block
+// of positions are one 64-aligned block (read in descending order, except block 0's), so a wavefront's mirrored load is 512
+// contiguous bytes too.
+struct EarRow {     // acc += M_p X, then acc += S_p conj(X_mirror)
+    static constexpr int kAcc = 1, kUnroll = 4;
+    static constexpr bool kStereo = true, kMirror = true;
+    static __device__ __forceinline__ float2 step(float2 acc, const float2* __restrict__ H, size_t set, float2 x, float2 xm) {
+        return pmac_conj(pmac(acc, H[0], x), H[set], xm);
+    }
+};
+// P spectrum streams against the one X: each X_{t-p}[b] is loaded once and multiplied into the P (FADE: 2 P) products of the pairs,
+// which stay in registers because P is a template argument
+template <int P>
+struct BusRow : PlainRow {
+    static constexpr int kAcc = P, kUnroll = 2;
+    static constexpr bool kStereo = false;
+};
+
+// The product of row list[blockIdx.y] over the delay line: Y_q[b] = sum_p H_{q,p}[b] X_{t-p}[b] (Row::step), X_{t-p} = spectrum ring
+// slot (slot - p) mod K (p = 0 of a stereo row: x_now in a literal-tail callback).  A workgroup owns 64 adjacent bins, so every load
+// of a wavefront is 512 contiguous bytes; its four wavefronts take p = w, w + 4, ... in ascending order and their sums meet in LDS
+// as ((s0 + s1) + s2) + s3 — an order fixed by K alone.  FADE: the same X against H_from and H_to, two sums per product.
+// Y: [2][kAcc][N], the products with H, then (FADE) with H_to.
+template <class Row, bool FADE>
+__global__ __launch_bounds__(kPartBlock) void reverb_product_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ list,
+                                                                    int n, int K, int literal) {
+    constexpr int A = Row::kAcc;
+    __shared__ float2 s_sum[FADE ? 2 : 1][A][kMacWaves][kMacBins];
     const ReverbPartItem it = items[list[blockIdx.y]];
     const uint32_t N = 1u << n;
     const uint32_t lane = threadIdx.x & (kMacBins - 1), w = threadIdx.x / kMacBins;
     const uint32_t b = blockIdx.x * kMacBins + lane;
     const bool live = b < N;   // (N = 32: half a wavefront)
+    const uint32_t bm = __brev((N - (__brev(b) >> (32 - n))) & (N - 1u)) >> (32 - n);   // (live: < N; the ear row's)
+    const size_t set = (size_t)K << n;
     const float2* __restrict__ H = it.h;
     const float2* __restrict__ H_to = it.h_to;
-    const float2* __restrict__ xring = part_xring(it.state, n);
+    const float2* __restrict__ xring = part_xring(it.state, n, Row::kStereo, A);
     const float2* __restrict__ xnow = part_xnow(it.state, n);
-    float2 acc = make_float2(0.0f, 0.0f), acc_to = make_float2(0.0f, 0.0f);
+    float2 acc[A], acc_to[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) acc[q] = acc_to[q] = make_float2(0.0f, 0.0f);
     if (live) {
-#pragma unroll 4
+#pragma unroll Row::kUnroll
         for (int p = (int)w; p < K; p += kMacWaves) {
             int sp = it.slot - p;
             sp += sp < 0 ? K : 0;
-            const float2 x = (p == 0 && literal) ? xnow[b] : xring[((size_t)sp << n) + b];
-            acc = pmac(acc, H[((size_t)p << n) + b], x);
-            if (FADE) acc_to = pmac(acc_to, H_to[((size_t)p << n) + b], x);
+            const bool now = Row::kStereo && p == 0 && literal;
+            const size_t slot = (size_t)sp << n;
+            float2 x, xm;
+            if (Row::kMirror) {   // two bins of one spectrum: choose the spectrum
+                const float2* __restrict__ X = now ? xnow : xring + slot;
+                x = X[b], xm = X[bm];
+            } else {              // one bin: choose the value (a branch round one load keeps fewer addresses live than a select of them)
+                x = xm = now ? xnow[b] : xring[slot + b];
+            }
+            const size_t at = ((size_t)p << n) + b;
+#pragma unroll
+            for (int q = 0; q < A; ++q) {
+                acc[q] = Row::step(acc[q], H + (q * set + at), set, x, xm);
+                if (FADE) acc_to[q] = Row::step(acc_to[q], H_to + (q * set + at), set, x, xm);
+            }
         }
     }
-    s_sum[0][w][lane] = acc;
-    if (FADE) s_sum[FADE ? 1 : 0][w][lane] = acc_to;
+#pragma unroll
+    for (int q = 0; q < A; ++q) {
+        s_sum[0][q][w][lane] = acc[q];
+        if (FADE) s_sum[FADE ? 1 : 0][q][w][lane] = acc_to[q];
+    }
     __syncthreads();
     if (w == 0 && live) {
-        float2* __restrict__ Y = part_y(it.state, n);
-        float2 v = s_sum[0][0][lane];
+        float2* __restrict__ Y = part_y(it.state, n, Row::kStereo);
 #pragma unroll
-        for (int k = 1; k < kMacWaves; ++k) v = padd(v, s_sum[0][k][lane]);
-        Y[b] = v;
-        if (FADE) {
-            float2 u = s_sum[FADE ? 1 : 0][0][lane];
+        for (int q = 0; q < A; ++q) {
+            float2 v = s_sum[0][q][0][lane];
 #pragma unroll
-            for (int k = 1; k < kMacWaves; ++k) u = padd(u, s_sum[FADE ? 1 : 0][k][lane]);
-            Y[N + b] = u;
+            for (int k = 1; k < kMacWaves; ++k) v = padd(v, s_sum[0][q][k][lane]);
+            Y[((size_t)q << n) + b] = v;
+            if (FADE) {
+                float2 u = s_sum[FADE ? 1 : 0][q][0][lane];
+#pragma unroll
+                for (int k = 1; k < kMacWaves; ++k) u = padd(u, s_sum[FADE ? 1 : 0][q][k][lane]);
+                Y[((size_t)(A + q) << n) + b] = u;
+            }
         }
     }
 }
 
-// Row r = blockIdx.x (as above): y = IFFT_N(Y) / N, the last F samples, real part left and imaginary part right, clamped
-// (FMath::Clamp RVB.cpp:165-167, MixAlpha = 1) into the interleaved out row.  A fading row (h_to) inverts both sums and mixes per
-// output sample, (1 - g) y_from + g y_to, g = (p + 1) / L while p = fade_pos + s < L, else 1 — the direct engine's expression.
+// Workgroup (r, q) inverts product q of row r: y = IFFT_N(Y_q) / N, the last F samples, the real part into channel 2q and the
+// imaginary part into channel 2q + 1 of the row's [F][C] block.  A fading row (h_to) inverts both sums and mixes per output sample,
+// (1 - g) y_from + g y_to, g = (p + 1) / L while p = fade_pos + s < L, else 1 — the direct engine's expression.
+// STEREO: one product and C = 2 (left, right), whatever P and C say; rows that are not convolved rows of this engine are left at
+// once; the output is clamped (FMath::Clamp RVB.cpp:165-167, MixAlpha = 1).  The bus: P products per row, the last one without a
+// partner at odd C, NOT clamped (a bus is summed and decoded before it reaches a converter).
 // LDS: the transform [N] and, for the fade, y_from's kept samples [F].
+template <bool STEREO>
 __global__ __launch_bounds__(kPartBlock) void reverb_part_inverse_kernel(const ReverbPartItem* __restrict__ items, const float2* __restrict__ W,
-                                                                         int n, int frame, float* __restrict__ out_all) {
+                                                                         int n, int frame, int P_bus, int C_bus, float* __restrict__ out_all) {
     extern __shared__ __attribute__((aligned(16))) float2 sh[];
     const int r = blockIdx.x;
+    const int q = STEREO ? 0 : (int)blockIdx.y;
+    const int P = STEREO ? 1 : P_bus, C = STEREO ? 2 : C_bus;
     const ReverbPartItem it = items[r];
-    if (!it.active) return;
+    if (STEREO && !it.active) return;
     const uint32_t N = 1u << n;
     const float scale = 1.0f / (float)N;   // (a power of two: exact)
-    const float2* __restrict__ Y = part_y(it.state, n);
+    const float2* __restrict__ Y = part_y(it.state, n, STEREO) + ((size_t)q << n);
+    const float2* __restrict__ Y_to = Y + ((size_t)P << n);
     float2* keep = sh + N;
-    float* __restrict__ out = out_all + (size_t)r * 2 * (size_t)frame;
+    float* __restrict__ out = out_all + (size_t)r * (size_t)C * (size_t)frame;
     const uint32_t old = N - (uint32_t)frame;
     for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) sh[j] = Y[j];
     lds_fft_dit(sh, W, n);
@@ -214,9 +286,10 @@ __global__ __launch_bounds__(kPartBlock) void reverb_part_inverse_kernel(const R
     if (fade) {
         for (uint32_t s = threadIdx.x; s < (uint32_t)frame; s += kPartBlock) keep[s] = sh[old + s];
         __syncthreads();
-        for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) sh[j] = Y[N + j];
+        for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) sh[j] = Y_to[j];
         lds_fft_dit(sh, W, n);
     }
+    const bool partner = STEREO || 2 * q + 1 < C;
     for (uint32_t s = threadIdx.x; s < (uint32_t)frame; s += kPartBlock) {
         float2 v = sh[old + s];
         v = make_float2(v.x * scale, v.y * scale);
@@ -226,16 +299,18 @@ __global__ __launch_bounds__(kPartBlock) void reverb_part_inverse_kernel(const R
             const float g = p < it.fade_len ? (float)(p + 1) / (float)it.fade_len : 1.0f;
             v = make_float2((1.0f - g) * f.x + g * v.x, (1.0f - g) * f.y + g * v.y);
         }
-        v.x = v.x < -1.0f ? -1.0f : (v.x > 1.0f ? 1.0f : v.x);
-        v.y = v.y < -1.0f ? -1.0f : (v.y > 1.0f ? 1.0f : v.y);
-        out[2 * s] = v.x;
-        out[2 * s + 1] = v.y;
+        if (STEREO) {
+            v.x = v.x < -1.0f ? -1.0f : (v.x > 1.0f ? 1.0f : v.x);
+            v.y = v.y < -1.0f ? -1.0f : (v.y > 1.0f ? 1.0f : v.y);
+        }
+        out[(size_t)s * (size_t)C + 2 * q] = v.x;
+        if (partner) out[(size_t)s * (size_t)C + 2 * q + 1] = v.y;
     }
 }
 
 // ---- sources with ears (fs_reverb_set_ears; definition: DESIGN.md section 8, "Two-ear late reverb") ----
 // h_L = m + s, h_R = m - s with m[i] = (1/sqrt(B)) sum_b env_b[i] cm_b[i], s[i] likewise with cs_b: the left channel is convolved
-// with h_L and the right with h_R in the one packed transform, Y[k] = M_p[k] X[k] + S_p[k] conj(X[(N - k) mod N]).
+// with h_L and the right with h_R in the one packed transform (EarRow).
 //
 // (m[i], s[i]): fp32, the bands in ascending order, each product rounded before it is added, the scale last — THE expression of both
 // kernels that form them (the take and the copy)
@@ -251,11 +326,6 @@ __device__ __forceinline__ float2 ears_mid_side(const float* __restrict__ env, c
     const float g = 1.0f / sqrtf((float)e.B);
     return make_float2(m * g, s * g);
 }
-// acc + s conj(x), each component two fused steps in a fixed order
-__device__ __forceinline__ float2 pmac_conj(float2 acc, float2 s, float2 x) {
-    return make_float2(fmaf(s.x, x.x, fmaf(s.y, x.y, acc.x)), fmaf(s.y, x.x, fmaf(-s.x, x.y, acc.y)));
-}
-
 // reverb_part_take_kernel for the rows with ears: workgroup (p, k) owns partition p of row take[k], in both spectrum sets of a copy
 // ([2][K][N]: M, then S).  The fold of a cut-short fade on both sets, then M_p := FFT_N(m[pF .. pF + F) zero-padded) and S_p likewise
 // from the row's B band rows (take_ir) and the carrier set.
@@ -268,16 +338,7 @@ __global__ __launch_bounds__(kPartBlock) void reverb_ears_take_kernel(const Reve
     const uint32_t p = blockIdx.x;
     const size_t set = (size_t)K << n;   // from M to S
     float2* __restrict__ h_to = it.take_to + (size_t)p * N;
-    const float a = it.take_a;
-    if (a > 0.0f) {
-        float2* __restrict__ h_from = it.take_from + (size_t)p * N;
-        for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) {
-            const float2 f = h_from[i], t = h_to[i];
-            h_from[i] = make_float2((1.0f - a) * f.x + a * t.x, (1.0f - a) * f.y + a * t.y);
-            const float2 fs = h_from[set + i], ts = h_to[set + i];
-            h_from[set + i] = make_float2((1.0f - a) * fs.x + a * ts.x, (1.0f - a) * fs.y + a * ts.y);
-        }
-    }
+    if (it.take_a > 0.0f) fold_cut_short(it.take_from + (size_t)p * N, h_to, set, 2, it.take_a, N);
     const uint32_t k0 = p * (uint32_t)frame;
     float side[kEarsMaxFrame / kPartBlock];   // s of the thread's samples of the partition, kept while m is transformed
 #pragma unroll
@@ -302,57 +363,6 @@ __global__ __launch_bounds__(kPartBlock) void reverb_ears_take_kernel(const Reve
     for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) h_to[set + i] = sh[i];
 }
 
-// reverb_part_mac_kernel for the rows with ears: the same tiling and the same order of sums, with a second H stream and the
-// mirrored X.  Position j of the bit-reversed storage holds bin brev(j); the bin N - brev(j) (mod N) lives at
-// jm = brev((N - brev(j)) mod N).  The mirrors of a 64-aligned block of positions are one 64-aligned block (read in descending
-// order, except block 0's), so a wavefront's mirrored load is 512 contiguous bytes too.  Per partition: acc += M_p X, then
-// acc += S_p conj(X_mirror).
-template <bool FADE>
-__global__ __launch_bounds__(kPartBlock) void reverb_ears_mac_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ list,
-                                                                     int n, int K, int literal) {
-    __shared__ float2 s_sum[FADE ? 2 : 1][kMacWaves][kMacBins];
-    const ReverbPartItem it = items[list[blockIdx.y]];
-    const uint32_t N = 1u << n;
-    const uint32_t lane = threadIdx.x & (kMacBins - 1), w = threadIdx.x / kMacBins;
-    const uint32_t b = blockIdx.x * kMacBins + lane;
-    const bool live = b < N;   // (N = 32: half a wavefront)
-    const uint32_t bm = __brev((N - (__brev(b) >> (32 - n))) & (N - 1u)) >> (32 - n);   // (live: < N)
-    const size_t set = (size_t)K << n;
-    const float2* __restrict__ H = it.h;
-    const float2* __restrict__ H_to = it.h_to;
-    const float2* __restrict__ xring = part_xring(it.state, n);
-    const float2* __restrict__ xnow = part_xnow(it.state, n);
-    float2 acc = make_float2(0.0f, 0.0f), acc_to = make_float2(0.0f, 0.0f);
-    if (live) {
-#pragma unroll 4
-        for (int p = (int)w; p < K; p += kMacWaves) {
-            int sp = it.slot - p;
-            sp += sp < 0 ? K : 0;
-            const float2* __restrict__ X = (p == 0 && literal) ? xnow : xring + ((size_t)sp << n);
-            const float2 x = X[b], xm = X[bm];
-            const size_t at = ((size_t)p << n) + b;
-            acc = pmac_conj(pmac(acc, H[at], x), H[set + at], xm);
-            if (FADE) acc_to = pmac_conj(pmac(acc_to, H_to[at], x), H_to[set + at], xm);
-        }
-    }
-    s_sum[0][w][lane] = acc;
-    if (FADE) s_sum[FADE ? 1 : 0][w][lane] = acc_to;
-    __syncthreads();
-    if (w == 0 && live) {
-        float2* __restrict__ Y = part_y(it.state, n);
-        float2 v = s_sum[0][0][lane];
-#pragma unroll
-        for (int k = 1; k < kMacWaves; ++k) v = padd(v, s_sum[0][k][lane]);
-        Y[b] = v;
-        if (FADE) {
-            float2 u = s_sum[FADE ? 1 : 0][0][lane];
-#pragma unroll
-            for (int k = 1; k < kMacWaves; ++k) u = padd(u, s_sum[FADE ? 1 : 0][k][lane]);
-            Y[N + b] = u;
-        }
-    }
-}
-
 // fs_reverb_copy_ear_impulse_responses: the ear IRs of one source's band rows, sample by sample
 __global__ __launch_bounds__(kPartBlock) void reverb_ears_ir_kernel(const float* __restrict__ bands, ReverbEars e, int num_samples,
                                                                     float* __restrict__ left, float* __restrict__ right) {
@@ -368,8 +378,8 @@ __global__ __launch_bounds__(kPartBlock) void reverb_ears_ir_kernel(const float*
 // carriers, weighted for its degree.  The input is real, so channels 2q and 2q + 1 ride in one complex IR: with P = ceil(C / 2)
 //   G_{q,p} = FFT_N(h_{2q}[pF .. pF + F) + i h_{2q+1}[pF .. pF + F))        reverb_soundfield_take_kernel
 //   X_t     = FFT_N(w + 0 i), w = the mono window                           reverb_soundfield_forward_kernel -> the ring of K spectra
-//   Y_q     = sum_p G_{q,p} X_{t-p}, every X read once for all P pairs      reverb_soundfield_mac_kernel
-//   IFFT_N(Y_q): the last F samples' real part is channel 2q, the imaginary part channel 2q + 1   reverb_soundfield_inverse_kernel
+//   Y_q     = sum_p G_{q,p} X_{t-p}, every X read once for all P pairs      reverb_product_kernel<BusRow<P>>
+//   IFFT_N(Y_q): the last F samples' real part is channel 2q, the imaginary part channel 2q + 1   reverb_part_inverse_kernel<false>
 // (the product of a complex IR spectrum with a real signal's spectrum is the spectrum of the complex convolution: no mirror term).
 //
 // the degree l of ACN channel c, c < 16
@@ -397,15 +407,7 @@ __global__ __launch_bounds__(kPartBlock) void reverb_soundfield_take_kernel(cons
     const int P = (e.C + 1) >> 1;
     const size_t set = (size_t)K << n;   // from one pair's spectra to the next's
     float2* __restrict__ h_to = it.take_to + (size_t)p * N;
-    const float a = it.take_a;
-    if (a > 0.0f) {
-        float2* __restrict__ h_from = it.take_from + (size_t)p * N;
-        for (int q = 0; q < P; ++q)
-            for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) {
-                const float2 f = h_from[q * set + i], t = h_to[q * set + i];
-                h_from[q * set + i] = make_float2((1.0f - a) * f.x + a * t.x, (1.0f - a) * f.y + a * t.y);
-            }
-    }
+    if (it.take_a > 0.0f) fold_cut_short(it.take_from + (size_t)p * N, h_to, set, P, it.take_a, N);
     const uint32_t k0 = p * (uint32_t)frame;
     for (int q = 0; q < P; ++q) {
         for (uint32_t i = threadIdx.x; i < N; i += kPartBlock) {
@@ -433,7 +435,7 @@ __global__ __launch_bounds__(kPartBlock) void reverb_soundfield_forward_kernel(c
     const ReverbPartItem it = items[r];
     const uint32_t N = 1u << n;
     const float* __restrict__ in = in_all + (size_t)r * 2 * (size_t)frame;
-    float* __restrict__ hist = sf_hist(it.state);
+    float* __restrict__ hist = (float*)part_hist(it.state);
     const uint32_t old = N - (uint32_t)frame;
     for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) {
         float v;
@@ -447,106 +449,8 @@ __global__ __launch_bounds__(kPartBlock) void reverb_soundfield_forward_kernel(c
         sh[j] = make_float2(v, 0.0f);
     }
     lds_fft_dif(sh, W, n);
-    float2* __restrict__ dst = sf_xring(it.state, n, P) + ((size_t)it.slot << n);
+    float2* __restrict__ dst = part_xring(it.state, n, false, P) + ((size_t)it.slot << n);
     for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) dst[j] = sh[j];
-}
-
-// reverb_part_mac_kernel for the soundfield rows: the same tiling and the same order of sums, with P spectrum streams against the
-// one X — each X_{t-p}[b] is loaded once and multiplied into the P (FADE: 2 P) accumulators of the pairs, which stay in registers
-// because P is a template argument.  Y: [2][P][N], the products with G, then (FADE) with G_to.
-template <int P, bool FADE>
-__global__ __launch_bounds__(kPartBlock) void reverb_soundfield_mac_kernel(const ReverbPartItem* __restrict__ items, const int* __restrict__ list,
-                                                                           int n, int K) {
-    __shared__ float2 s_sum[FADE ? 2 : 1][P][kMacWaves][kMacBins];
-    const ReverbPartItem it = items[list[blockIdx.y]];
-    const uint32_t N = 1u << n;
-    const uint32_t lane = threadIdx.x & (kMacBins - 1), w = threadIdx.x / kMacBins;
-    const uint32_t b = blockIdx.x * kMacBins + lane;
-    const bool live = b < N;   // (N = 32: half a wavefront)
-    const size_t set = (size_t)K << n;
-    const float2* __restrict__ H = it.h;
-    const float2* __restrict__ H_to = it.h_to;
-    const float2* __restrict__ xring = sf_xring(it.state, n, P);
-    float2 acc[P], acc_to[P];
-#pragma unroll
-    for (int q = 0; q < P; ++q) acc[q] = acc_to[q] = make_float2(0.0f, 0.0f);
-    if (live) {
-#pragma unroll 2
-        for (int p = (int)w; p < K; p += kMacWaves) {
-            int sp = it.slot - p;
-            sp += sp < 0 ? K : 0;
-            const float2 x = xring[((size_t)sp << n) + b];
-            const size_t at = ((size_t)p << n) + b;
-#pragma unroll
-            for (int q = 0; q < P; ++q) {
-                acc[q] = pmac(acc[q], H[q * set + at], x);
-                if (FADE) acc_to[q] = pmac(acc_to[q], H_to[q * set + at], x);
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < P; ++q) {
-        s_sum[0][q][w][lane] = acc[q];
-        if (FADE) s_sum[FADE ? 1 : 0][q][w][lane] = acc_to[q];
-    }
-    __syncthreads();
-    if (w == 0 && live) {
-        float2* __restrict__ Y = sf_y(it.state, n);
-#pragma unroll
-        for (int q = 0; q < P; ++q) {
-            float2 v = s_sum[0][q][0][lane];
-#pragma unroll
-            for (int k = 1; k < kMacWaves; ++k) v = padd(v, s_sum[0][q][k][lane]);
-            Y[((size_t)q << n) + b] = v;
-            if (FADE) {
-                float2 u = s_sum[FADE ? 1 : 0][q][0][lane];
-#pragma unroll
-                for (int k = 1; k < kMacWaves; ++k) u = padd(u, s_sum[FADE ? 1 : 0][q][k][lane]);
-                Y[((size_t)(P + q) << n) + b] = u;
-            }
-        }
-    }
-}
-
-// reverb_part_inverse_kernel for the soundfield rows: workgroup (r, q) inverts pair q of row r — y = IFFT_N(Y_q) / N, the last F
-// samples, real part channel 2q and imaginary part channel 2q + 1 of the row's [F][C] block, NOT clamped (a bus is summed and
-// decoded before it reaches a converter).  A fading row inverts both products and mixes per output sample with the engine's expression.
-__global__ __launch_bounds__(kPartBlock) void reverb_soundfield_inverse_kernel(const ReverbPartItem* __restrict__ items,
-                                                                               const float2* __restrict__ W, int n, int frame, int P, int C,
-                                                                               float* __restrict__ out_all) {
-    extern __shared__ __attribute__((aligned(16))) float2 sh[];
-    const int r = blockIdx.x;
-    const int q = blockIdx.y;
-    const ReverbPartItem it = items[r];
-    const uint32_t N = 1u << n;
-    const float scale = 1.0f / (float)N;   // (a power of two: exact)
-    const float2* __restrict__ Y = sf_y(it.state, n) + ((size_t)q << n);
-    const float2* __restrict__ Y_to = Y + ((size_t)P << n);
-    float2* keep = sh + N;
-    float* __restrict__ out = out_all + (size_t)r * (size_t)C * (size_t)frame;
-    const uint32_t old = N - (uint32_t)frame;
-    for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) sh[j] = Y[j];
-    lds_fft_dit(sh, W, n);
-    const bool fade = it.h_to != nullptr;
-    if (fade) {
-        for (uint32_t s = threadIdx.x; s < (uint32_t)frame; s += kPartBlock) keep[s] = sh[old + s];
-        __syncthreads();
-        for (uint32_t j = threadIdx.x; j < N; j += kPartBlock) sh[j] = Y_to[j];
-        lds_fft_dit(sh, W, n);
-    }
-    const bool partner = 2 * q + 1 < C;
-    for (uint32_t s = threadIdx.x; s < (uint32_t)frame; s += kPartBlock) {
-        float2 v = sh[old + s];
-        v = make_float2(v.x * scale, v.y * scale);
-        if (fade) {
-            const float2 f = make_float2(keep[s].x * scale, keep[s].y * scale);
-            const int p = it.fade_pos + (int)s;
-            const float g = p < it.fade_len ? (float)(p + 1) / (float)it.fade_len : 1.0f;
-            v = make_float2((1.0f - g) * f.x + g * v.x, (1.0f - g) * f.y + g * v.y);
-        }
-        out[(size_t)s * (size_t)C + 2 * q] = v.x;
-        if (partner) out[(size_t)s * (size_t)C + 2 * q + 1] = v.y;
-    }
 }
 
 // fs_reverb_copy_soundfield_impulse_responses: channel blockIdx.y's IR of one source's band rows, sample by sample
@@ -558,47 +462,34 @@ __global__ __launch_bounds__(kPartBlock) void reverb_soundfield_ir_kernel(const 
     out[(size_t)c * (size_t)num_samples + i] = sf_channel(bands, e, num_samples, c, i);
 }
 
-template <int P>
-void launch_soundfield_mac(const ReverbSoundfieldBatch& b, hipStream_t s) {
-    const unsigned tiles = ((1u << b.n) + kMacBins - 1) / kMacBins;
-    if (b.n_plain > 0)
-        hipLaunchKernelGGL((reverb_soundfield_mac_kernel<P, false>), dim3(tiles, (unsigned)b.n_plain), dim3(kPartBlock), 0, s, b.items, b.plain,
-                           b.n, b.K);
-    if (b.n_fade > 0)
-        hipLaunchKernelGGL((reverb_soundfield_mac_kernel<P, true>), dim3(tiles, (unsigned)b.n_fade), dim3(kPartBlock), 0, s, b.items, b.fade,
-                           b.n, b.K);
+// the products of one kind's two lists, each launched only when it has rows
+template <class Row>
+void launch_products(const ReverbPartItem* items, const ReverbShape& p, const ReverbLists& l, int literal_tail, hipStream_t s) {
+    const unsigned tiles = ((1u << p.n) + kMacBins - 1) / kMacBins;
+    if (l.n_plain > 0)
+        hipLaunchKernelGGL((reverb_product_kernel<Row, false>), dim3(tiles, (unsigned)l.n_plain), dim3(kPartBlock), 0, s, items, l.plain, p.n,
+                           p.K, literal_tail);
+    if (l.n_fade > 0)
+        hipLaunchKernelGGL((reverb_product_kernel<Row, true>), dim3(tiles, (unsigned)l.n_fade), dim3(kPartBlock), 0, s, items, l.fade, p.n,
+                           p.K, literal_tail);
 }
 
 }  // namespace
 
-void launch_reverb_soundfield_take(const ReverbSoundfieldBatch& b, const int* take, int n_take, const ReverbSoundfield& e, hipStream_t s) {
-    hipLaunchKernelGGL(reverb_soundfield_take_kernel, dim3((unsigned)b.K, (unsigned)n_take), dim3(kPartBlock), sizeof(float2) << b.n, s,
-                       b.items, take, b.W, b.n, b.K, b.frame, b.ir_size, e);
+void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbShape& p, hipStream_t s) {
+    hipLaunchKernelGGL(reverb_part_take_kernel, dim3((unsigned)p.K, (unsigned)n_take), dim3(kPartBlock), sizeof(float2) << p.n, s, items,
+                       take, p.W, p.n, p.frame, p.ir_size);
 }
 
-void launch_reverb_soundfield(const ReverbSoundfieldBatch& b, const ReverbSoundfield& e, hipStream_t s) {
-    const size_t lds = sizeof(float2) << b.n;
-    const int P = (e.C + 1) / 2;
-    hipLaunchKernelGGL(reverb_soundfield_forward_kernel, dim3((unsigned)b.count), dim3(kPartBlock), lds, s, b.items, b.in, b.W, b.n, b.frame, P);
-    switch (P) {   // (C = 1, 4, 9, 16)
-        case 1: launch_soundfield_mac<1>(b, s); break;
-        case 2: launch_soundfield_mac<2>(b, s); break;
-        case 5: launch_soundfield_mac<5>(b, s); break;
-        default: launch_soundfield_mac<8>(b, s); break;
-    }
-    hipLaunchKernelGGL(reverb_soundfield_inverse_kernel, dim3((unsigned)b.count, (unsigned)P), dim3(kPartBlock),
-                       lds + sizeof(float2) * (size_t)b.frame, s, b.items, b.W, b.n, b.frame, P, e.C, b.out);
-    if (b.mix) launch_callback_mix(b.out, b.count, b.frame * e.C, b.mix, s);
-}
-
-void launch_reverb_soundfield_ir(const float* bands, const ReverbSoundfield& e, int n, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(reverb_soundfield_ir_kernel, dim3((unsigned)((n + kPartBlock - 1) / kPartBlock), (unsigned)e.C), dim3(kPartBlock), 0, s,
-                       bands, e, n, out);
-}
-
-void launch_reverb_ears_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, const ReverbEars& e, hipStream_t s) {
+void launch_reverb_ears_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbShape& p, const ReverbEars& e, hipStream_t s) {
     hipLaunchKernelGGL(reverb_ears_take_kernel, dim3((unsigned)p.K, (unsigned)n_take), dim3(kPartBlock), sizeof(float2) << p.n, s, items,
                        take, p.W, p.n, p.K, p.frame, p.ir_size, e);
+}
+
+void launch_reverb_soundfield_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbShape& p, const ReverbSoundfield& e,
+                                   hipStream_t s) {
+    hipLaunchKernelGGL(reverb_soundfield_take_kernel, dim3((unsigned)p.K, (unsigned)n_take), dim3(kPartBlock), sizeof(float2) << p.n, s,
+                       items, take, p.W, p.n, p.K, p.frame, p.ir_size, e);
 }
 
 void launch_reverb_ears_ir(const float* bands, const ReverbEars& e, int n, float* left, float* right, hipStream_t s) {
@@ -606,32 +497,36 @@ void launch_reverb_ears_ir(const float* bands, const ReverbEars& e, int n, float
                        right);
 }
 
-void launch_reverb_part_take(const ReverbPartItem* items, const int* take, int n_take, const ReverbPart& p, hipStream_t s) {
-    hipLaunchKernelGGL(reverb_part_take_kernel, dim3((unsigned)p.K, (unsigned)n_take), dim3(kPartBlock), sizeof(float2) << p.n, s, items,
-                       take, p.W, p.n, p.frame, p.ir_size);
+void launch_reverb_soundfield_ir(const float* bands, const ReverbSoundfield& e, int n, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(reverb_soundfield_ir_kernel, dim3((unsigned)((n + kPartBlock - 1) / kPartBlock), (unsigned)e.C), dim3(kPartBlock), 0, s,
+                       bands, e, n, out);
 }
 
-void launch_reverb_part(const ReverbPartItem* items, const ReverbPart& p, int count, int literal_tail, const float* in, float* out,
-                        hipStream_t s) {
+void launch_reverb_part(const ReverbPartItem* items, const ReverbShape& p, const ReverbLists& rows, const ReverbLists& ears, int count,
+                        int literal_tail, const float* in, float* out, hipStream_t s) {
     const size_t lds = sizeof(float2) << p.n;
-    const unsigned N = 1u << p.n;
     hipLaunchKernelGGL(reverb_part_forward_kernel, dim3((unsigned)count, literal_tail ? 2u : 1u), dim3(kPartBlock), lds, s, items, in, p.W,
                        p.n, p.frame);
-    const unsigned tiles = (N + kMacBins - 1) / kMacBins;
-    if (p.n_plain > 0)
-        hipLaunchKernelGGL(reverb_part_mac_kernel<false>, dim3(tiles, (unsigned)p.n_plain), dim3(kPartBlock), 0, s, items, p.plain, p.n, p.K,
-                           literal_tail);
-    if (p.n_fade > 0)
-        hipLaunchKernelGGL(reverb_part_mac_kernel<true>, dim3(tiles, (unsigned)p.n_fade), dim3(kPartBlock), 0, s, items, p.fade, p.n, p.K,
-                           literal_tail);
-    if (p.n_ear_plain > 0)
-        hipLaunchKernelGGL(reverb_ears_mac_kernel<false>, dim3(tiles, (unsigned)p.n_ear_plain), dim3(kPartBlock), 0, s, items, p.ear_plain, p.n,
-                           p.K, literal_tail);
-    if (p.n_ear_fade > 0)
-        hipLaunchKernelGGL(reverb_ears_mac_kernel<true>, dim3(tiles, (unsigned)p.n_ear_fade), dim3(kPartBlock), 0, s, items, p.ear_fade, p.n,
-                           p.K, literal_tail);
-    hipLaunchKernelGGL(reverb_part_inverse_kernel, dim3((unsigned)count), dim3(kPartBlock), lds + sizeof(float2) * (size_t)p.frame, s, items,
-                       p.W, p.n, p.frame, out);
+    launch_products<PlainRow>(items, p, rows, literal_tail, s);
+    launch_products<EarRow>(items, p, ears, literal_tail, s);
+    hipLaunchKernelGGL(reverb_part_inverse_kernel<true>, dim3((unsigned)count), dim3(kPartBlock), lds + sizeof(float2) * (size_t)p.frame, s,
+                       items, p.W, p.n, p.frame, 1, 2, out);
+}
+
+void launch_reverb_soundfield(const ReverbPartItem* items, const ReverbShape& p, const ReverbLists& rows, const ReverbSoundfield& e, int count,
+                              const float* in, float* out, float* mix, hipStream_t s) {
+    const size_t lds = sizeof(float2) << p.n;
+    const int P = (e.C + 1) / 2;
+    hipLaunchKernelGGL(reverb_soundfield_forward_kernel, dim3((unsigned)count), dim3(kPartBlock), lds, s, items, in, p.W, p.n, p.frame, P);
+    switch (P) {   // (C = 1, 4, 9, 16)
+        case 1: launch_products<BusRow<1>>(items, p, rows, 0, s); break;
+        case 2: launch_products<BusRow<2>>(items, p, rows, 0, s); break;
+        case 5: launch_products<BusRow<5>>(items, p, rows, 0, s); break;
+        default: launch_products<BusRow<8>>(items, p, rows, 0, s); break;
+    }
+    hipLaunchKernelGGL(reverb_part_inverse_kernel<false>, dim3((unsigned)count, (unsigned)P), dim3(kPartBlock),
+                       lds + sizeof(float2) * (size_t)p.frame, s, items, p.W, p.n, p.frame, P, e.C, out);
+    if (mix) launch_callback_mix(out, count, p.frame * e.C, mix, s);
 }
 
 }  // namespace fs
