@@ -5,7 +5,9 @@ call raises.  The product never imports oracle/.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -585,6 +587,45 @@ class AmbisonicRenderRow(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("sounding", "started", "ended", "dropped")]
 
 
+# one path query of include/frequensee.h; row None: an out-only query, one path record per source and no counts
+PathQuery = collections.namedtuple("PathQuery", "kind params row path max_batch default update")
+
+
+def _path_query(kind, params, row, path, max_batch):
+    return PathQuery(kind, params, row, path, max_batch, f"fs_{kind}_params_default", f"fs_update_{kind}_paths")
+
+
+# The path queries, in the order they were added.  What is the same for all of them — the binding's signatures and defaults
+# (below), Context's and AudioRayTracingSubsystem's methods (component.py), the tests' contract (tests/path_query_contract.py)
+# — is written once and reads its row here.
+PATH_QUERIES = (
+    _path_query("direct", DirectParams, None, DirectPath, MAX_DIRECT_BATCH),
+    _path_query("reflection", ReflectionParams, ReflectionRow, ReflectionPath, MAX_REFLECTION_BATCH),
+    _path_query("diffraction", DiffractionParams, DiffractionRow, DiffractionPath, MAX_DIFFRACTION_BATCH),
+    _path_query("reflection2", Reflection2Params, Reflection2Row, Reflection2Path, MAX_REFLECTION2_BATCH),
+    _path_query("diffraction2", Diffraction2Params, Diffraction2Row, Diffraction2Path, MAX_DIFFRACTION2_BATCH),
+    _path_query("mixed", MixedParams, MixedRow, MixedPath, MAX_MIXED_BATCH),
+    _path_query("pathing", PathingParams, None, PathingPath, MAX_PATHING_BATCH),
+)
+PATH_QUERY = {q.kind: q for q in PATH_QUERIES}
+
+
+@functools.lru_cache(maxsize=None)
+def record_dtype(struct):
+    """the numpy dtype of a ctypes structure: the same field names, offsets and itemsize; an array of arrays such as
+    (c_float * 3) * 2 is one field of shape (2, 3)"""
+    import numpy as np
+    names, formats, offsets = [], [], []
+    for name, ctype in struct._fields_:
+        shape = ()
+        while hasattr(ctype, "_length_"):
+            shape, ctype = shape + (ctype._length_,), ctype._type_
+        names.append(name)
+        formats.append((np.dtype(ctype), shape))
+        offsets.append(getattr(struct, name).offset)
+    return np.dtype(dict(names=names, formats=formats, offsets=offsets, itemsize=C.sizeof(struct)))
+
+
 class FrequenSeeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"frequensee status {code}: {msg}")
@@ -703,26 +744,12 @@ def load():
         "fs_scene_commit_progressive": (C.c_int, [vp]),
         "fs_scene_refine_pending": (C.c_int, [vp, C.POINTER(i32)]),
         "fs_scene_refine_wait": (C.c_int, [vp]),
-        "fs_direct_params_default": (None, [C.POINTER(DirectParams)]),
         "fs_direct_sample_offsets": (C.c_int, [i32, f32p]),
-        "fs_update_direct_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(DirectParams), C.c_void_p]),
-        "fs_reflection_params_default": (None, [C.POINTER(ReflectionParams)]),
-        "fs_update_reflection_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(ReflectionParams), C.c_void_p, C.c_void_p]),
-        "fs_diffraction_params_default": (None, [C.POINTER(DiffractionParams)]),
-        "fs_update_diffraction_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(DiffractionParams), C.c_void_p, C.c_void_p]),
-        "fs_reflection2_params_default": (None, [C.POINTER(Reflection2Params)]),
-        "fs_update_reflection2_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(Reflection2Params), C.c_void_p, C.c_void_p]),
-        "fs_diffraction2_params_default": (None, [C.POINTER(Diffraction2Params)]),
-        "fs_update_diffraction2_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(Diffraction2Params), C.c_void_p, C.c_void_p]),
-        "fs_mixed_params_default": (None, [C.POINTER(MixedParams)]),
-        "fs_update_mixed_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(MixedParams), C.c_void_p, C.c_void_p]),
         "fs_pathing_set_probes": (C.c_int, [vp, C.c_void_p, i32]),
         "fs_pathing_bake_params_default": (None, [C.POINTER(PathingBakeParams)]),
         "fs_pathing_bake": (C.c_int, [vp, C.POINTER(PathingBakeParams)]),
         "fs_pathing_info": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "fs_pathing_copy_graph": (C.c_int, [vp, C.c_void_p, i32]),
-        "fs_pathing_params_default": (None, [C.POINTER(PathingParams)]),
-        "fs_update_pathing_paths": (C.c_int, [vp, C.c_void_p, i32, C.POINTER(PathingParams), C.c_void_p]),
         "fs_direct_band_kernels": (C.c_int, [i32, f32p, i32, i32, f32p]),
         "fs_direct_render_init": (C.c_int, [vp, i32, i32, i32, C.c_float]),
         "fs_direct_render_release": (C.c_int, [vp, i32]),
@@ -743,6 +770,9 @@ def load():
         "fs_gather_energy": (C.c_int, [vp, i32, f32p, i32]),
         "fs_gather_energy_async": (C.c_int, [vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     }
+    for q in PATH_QUERIES:   # fs_update_*_paths(ctx, sources, count, params, rows (not the out-only queries), paths)
+        sig[q.default] = (None, [C.POINTER(q.params)])
+        sig[q.update] = (C.c_int, [vp, C.c_void_p, i32, C.POINTER(q.params)] + [C.c_void_p] * (1 if q.row is None else 2))
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -772,36 +802,19 @@ def default_reverb_ears(**kw) -> ReverbEarsDesc:
     return _defaults(ReverbEarsDesc, "fs_reverb_ears_default", kw)
 
 
-def default_direct_params(**kw) -> DirectParams:
-    return _defaults(DirectParams, "fs_direct_params_default", kw)
-
-
-def default_reflection_params(**kw) -> ReflectionParams:
-    return _defaults(ReflectionParams, "fs_reflection_params_default", kw)
-
-
-def default_diffraction_params(**kw) -> DiffractionParams:
-    return _defaults(DiffractionParams, "fs_diffraction_params_default", kw)
-
-
-def default_reflection2_params(**kw) -> Reflection2Params:
-    return _defaults(Reflection2Params, "fs_reflection2_params_default", kw)
-
-
-def default_diffraction2_params(**kw) -> Diffraction2Params:
-    return _defaults(Diffraction2Params, "fs_diffraction2_params_default", kw)
-
-
-def default_mixed_params(**kw) -> MixedParams:
-    return _defaults(MixedParams, "fs_mixed_params_default", kw)
-
-
 def default_pathing_bake_params(**kw) -> PathingBakeParams:
     return _defaults(PathingBakeParams, "fs_pathing_bake_params_default", kw)
 
 
-def default_pathing_params(**kw) -> PathingParams:
-    return _defaults(PathingParams, "fs_pathing_params_default", kw)
+def default_path_params(kind, **kw):
+    """the params of the path query `kind` (PATH_QUERY) as its fs_*_params_default fills them, then the caller's fields"""
+    q = PATH_QUERY[kind]
+    return _defaults(q.params, q.default, kw)
+
+
+# default_<kind>_params(**kw), one per row of PATH_QUERIES in its order
+(default_direct_params, default_reflection_params, default_diffraction_params, default_reflection2_params, default_diffraction2_params,
+ default_mixed_params, default_pathing_params) = (functools.partial(default_path_params, q.kind) for q in PATH_QUERIES)
 
 
 def default_params(**kw) -> Params:

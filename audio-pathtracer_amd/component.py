@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import FrequenSeeError
+from ._capi import FrequenSeeError, record_dtype
 
 
 def _f3(v):
@@ -324,7 +324,7 @@ class Context:
         self.check(self.lib.fs_get_impulse_response_sequence(self.h, src, C.byref(n)))
         return int(n.value)
 
-    ROOM_DTYPE = np.dtype([(k, np.float32) for k, _ in _capi.RoomParameters._fields_])
+    ROOM_DTYPE = record_dtype(_capi.RoomParameters)
 
     def room_parameters(self, src):
         """FS_FLAG_ROOM_PARAMETERS (fs_get_room_parameters): (sequence, structured array [bands] of energy, onset, edt, t20, t30,
@@ -376,8 +376,7 @@ class Context:
         return float(v.value)
 
     # ---- direct paths: the direct sound of every source of a tick in one launch ----
-    DIRECT_DTYPE = np.dtype([("distance", np.float32), ("delay", np.float32), ("visibility", np.float32), ("surfaces", np.uint32),
-                             ("samples_valid", np.uint32), ("transmission", np.float32, (_capi.MAX_BANDS,))])
+    DIRECT_DTYPE = record_dtype(_capi.DirectPath)
 
     @staticmethod
     def direct_sample_offsets(n):
@@ -392,43 +391,46 @@ class Context:
         """fs_update_direct_paths: one row per listed source — distance (cm), delay (s), visibility, surfaces the centre ray
         crossed, samples_valid, transmission [8] (bands beyond num_bands: 0) — as a structured array; params = the fields of
         fs_direct_params (samples, source_radius, max_surfaces, step, pullback, dist_divisor, sound_speed)"""
+        return self._out_only("direct", sources, params, out)
+
+    def _out_only(self, kind, sources, params, out=None):
+        """the body of the out-only queries (PATH_QUERIES rows without a row record): fs_update_<kind>_paths with the given fields
+        of its params into `out` or a fresh array [count] of its path record"""
+        q = _capi.PATH_QUERY[kind]
         srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
-        p = _capi.default_direct_params(**params)
+        p = _capi.default_path_params(kind, **params)
         if out is None:
-            out = np.zeros(srcs.shape[0], dtype=self.DIRECT_DTYPE)
-        self.check(self.lib.fs_update_direct_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
-                                                   out.ctypes.data if out.size else None))
+            out = np.zeros(srcs.shape[0], dtype=record_dtype(q.path))
+        self.check(getattr(self.lib, q.update)(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
+                                               out.ctypes.data if out.size else None))
         return out
 
-    def _rows_and_paths(self, update, p, row_dtype, path_dtype, sources):
-        """the body of the five rows-and-paths queries: `update` (fs_update_*_paths) with the params p into fresh
-        (rows [count], paths [count][max_paths]) of the two dtypes"""
+    def _rows_and_paths(self, kind, sources, params):
+        """the body of the rows-and-paths queries: fs_update_<kind>_paths with the given fields of its params into fresh
+        (rows [count], paths [count][max_paths]) of its two records"""
+        q = _capi.PATH_QUERY[kind]
         srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
-        rows = np.zeros(srcs.shape[0], dtype=row_dtype)
-        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=path_dtype)
-        self.check(update(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
-                          rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
+        p = _capi.default_path_params(kind, **params)
+        rows = np.zeros(srcs.shape[0], dtype=record_dtype(q.row))
+        paths = np.zeros((srcs.shape[0], max(int(p.max_paths), 0)), dtype=record_dtype(q.path))
+        self.check(getattr(self.lib, q.update)(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
+                                               rows.ctypes.data if rows.size else None, paths.ctypes.data if paths.size else None))
         return rows, paths
 
     # ---- reflection paths: the first-order specular reflections of every source of a tick ----
-    REFLECTION_ROW_DTYPE = np.dtype([("candidates", np.uint32), ("found", np.uint32), ("returned", np.uint32), ("flags", np.uint32)])
-    REFLECTION_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("point", np.float32, (3,)), ("direction", np.float32, (3,)),
-                                 ("triangle", np.uint32), ("material", np.uint32), ("reflectance", np.float32, (_capi.MAX_BANDS,))])
+    REFLECTION_ROW_DTYPE = record_dtype(_capi.ReflectionRow)
+    REFLECTION_DTYPE = record_dtype(_capi.ReflectionPath)
 
     def reflection_paths(self, sources, **params):
         """fs_update_reflection_paths: (rows [count], paths [count][max_paths]) as structured arrays — per listed source the counts
         (candidates, found, returned, flags) and its `returned` shortest reflections (length cm, delay s, point, direction from the
         listener, triangle, material, reflectance [8]; entries beyond `returned` are zero); params = the fields of
         fs_reflection_params (max_paths, max_candidates, margin, step, offset, pullback, dist_divisor, sound_speed)"""
-        return self._rows_and_paths(self.lib.fs_update_reflection_paths, _capi.default_reflection_params(**params), self.REFLECTION_ROW_DTYPE,
-                                    self.REFLECTION_DTYPE, sources)
+        return self._rows_and_paths("reflection", sources, params)
 
     # ---- diffraction paths: the first-order edge diffraction of every source of a tick ----
-    DIFFRACTION_ROW_DTYPE = np.dtype([("candidates", np.uint32), ("confirmed", np.uint32), ("found", np.uint32), ("returned", np.uint32),
-                                      ("flags", np.uint32)])
-    DIFFRACTION_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("detour", np.float32), ("cos_bend", np.float32),
-                                  ("apex", np.float32, (3,)), ("direction", np.float32, (3,)), ("triangle", np.uint32), ("edge", np.uint32),
-                                  ("material", np.uint32), ("gain", np.float32, (_capi.MAX_BANDS,))])
+    DIFFRACTION_ROW_DTYPE = record_dtype(_capi.DiffractionRow)
+    DIFFRACTION_DTYPE = record_dtype(_capi.DiffractionPath)
 
     def diffraction_paths(self, sources, **params):
         """fs_update_diffraction_paths: (rows [count], paths [count][max_paths]) as structured arrays — per listed source the counts
@@ -436,14 +438,11 @@ class Context:
         cm, cos_bend, apex, direction from the listener, triangle, edge, material, gain [8]; entries beyond `returned` are zero);
         params = the fields of fs_diffraction_params (max_paths, max_candidates, margin, max_detour, offset, merge, step, pullback,
         dist_divisor, sound_speed)"""
-        return self._rows_and_paths(self.lib.fs_update_diffraction_paths, _capi.default_diffraction_params(**params), self.DIFFRACTION_ROW_DTYPE,
-                                    self.DIFFRACTION_DTYPE, sources)
+        return self._rows_and_paths("diffraction", sources, params)
 
     # ---- second-order reflection paths: the specular reflections off two triangles of every source of a tick ----
-    REFLECTION2_ROW_DTYPE = np.dtype([("near", np.uint32), ("candidates", np.uint32), ("found", np.uint32), ("returned", np.uint32),
-                                      ("flags", np.uint32)])
-    REFLECTION2_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("point", np.float32, (2, 3)), ("direction", np.float32, (3,)),
-                                  ("triangle", np.uint32, (2,)), ("material", np.uint32, (2,)), ("reflectance", np.float32, (_capi.MAX_BANDS,))])
+    REFLECTION2_ROW_DTYPE = record_dtype(_capi.Reflection2Row)
+    REFLECTION2_DTYPE = record_dtype(_capi.Reflection2Path)
 
     def reflection2_paths(self, sources, **params):
         """fs_update_reflection2_paths: (rows [count], paths [count][max_paths]) as structured arrays — per listed source the counts
@@ -451,16 +450,11 @@ class Context:
         -> source (length cm, delay s, point [PA, PB], direction from the listener, triangle [a, b], material [2], reflectance [8];
         entries beyond `returned` are zero); params = the fields of fs_reflection2_params (max_paths, max_near, max_candidates,
         max_length, margin, step, offset, pullback, dist_divisor, sound_speed)"""
-        return self._rows_and_paths(self.lib.fs_update_reflection2_paths, _capi.default_reflection2_params(**params), self.REFLECTION2_ROW_DTYPE,
-                                    self.REFLECTION2_DTYPE, sources)
+        return self._rows_and_paths("reflection2", sources, params)
 
     # ---- second-order diffraction paths: the diffraction round thick obstacles of every source of a tick ----
-    DIFFRACTION2_ROW_DTYPE = np.dtype([("near", np.uint32), ("candidates", np.uint32), ("confirmed", np.uint32), ("found", np.uint32),
-                                       ("returned", np.uint32), ("flags", np.uint32)])
-    DIFFRACTION2_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("detour", np.float32), ("gap", np.float32),
-                                   ("cos_bend", np.float32, (2,)), ("apex", np.float32, (2, 3)), ("direction", np.float32, (3,)),
-                                   ("triangle", np.uint32, (2,)), ("edge", np.uint32, (2,)), ("material", np.uint32, (2,)),
-                                   ("gain", np.float32, (_capi.MAX_BANDS,))])
+    DIFFRACTION2_ROW_DTYPE = record_dtype(_capi.Diffraction2Row)
+    DIFFRACTION2_DTYPE = record_dtype(_capi.Diffraction2Path)
 
     def diffraction2_paths(self, sources, **params):
         """fs_update_diffraction2_paths: (rows [count], paths [count][max_paths]) as structured arrays — per listed source the counts
@@ -469,16 +463,11 @@ class Context:
         triangle [2], edge [2], material [2], gain [8]; index 0 is the listener's end; entries beyond `returned` are zero);
         params = the fields of fs_diffraction2_params (max_paths, max_near, max_candidates, margin, max_detour, min_parallel, offset,
         merge, step, pullback, dist_divisor, sound_speed)"""
-        return self._rows_and_paths(self.lib.fs_update_diffraction2_paths, _capi.default_diffraction2_params(**params), self.DIFFRACTION2_ROW_DTYPE,
-                                    self.DIFFRACTION2_DTYPE, sources)
+        return self._rows_and_paths("diffraction2", sources, params)
 
     # ---- mixed paths: one specular reflection and one edge diffraction of every source of a tick ----
-    MIXED_ROW_DTYPE = np.dtype([("near", np.uint32), ("candidates", np.uint32), ("confirmed", np.uint32), ("found", np.uint32),
-                                ("returned", np.uint32), ("flags", np.uint32)])
-    MIXED_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("detour", np.float32), ("bend_detour", np.float32),
-                            ("cos_bend", np.float32), ("apex", np.float32, (3,)), ("point", np.float32, (3,)), ("direction", np.float32, (3,)),
-                            ("end", np.uint32), ("triangle", np.uint32, (2,)), ("edge", np.uint32), ("material", np.uint32, (2,)),
-                            ("gain", np.float32, (_capi.MAX_BANDS,))])
+    MIXED_ROW_DTYPE = record_dtype(_capi.MixedRow)
+    MIXED_DTYPE = record_dtype(_capi.MixedPath)
 
     def mixed_paths(self, sources, **params):
         """fs_update_mixed_paths: (rows [count], paths [count][max_paths]) as structured arrays — per listed source the counts
@@ -487,14 +476,10 @@ class Context:
         reflector is next to the listener, 1: next to the source —, triangle [reflector, the edge's], edge, material [2], gain [8];
         entries beyond `returned` are zero); params = the fields of fs_mixed_params (max_paths, max_near, max_candidates,
         max_length, max_detour, margin, offset, merge, step, pullback, dist_divisor, sound_speed)"""
-        return self._rows_and_paths(self.lib.fs_update_mixed_paths, _capi.default_mixed_params(**params), self.MIXED_ROW_DTYPE, self.MIXED_DTYPE,
-                                    sources)
+        return self._rows_and_paths("mixed", sources, params)
 
     # ---- pathing: round several corners by a probe graph ----
-    PATHING_DTYPE = np.dtype([("length", np.float32), ("delay", np.float32), ("detour", np.float32), ("distance", np.float32),
-                              ("direction", np.float32, (3,)), ("departure", np.float32, (3,)), ("hops", np.uint32), ("flags", np.uint32),
-                              ("first_probe", np.uint32), ("last_probe", np.uint32), ("probes", np.uint32, (_capi.MAX_PATHING_NODES,)),
-                              ("gain", np.float32, (_capi.MAX_BANDS,))])
+    PATHING_DTYPE = record_dtype(_capi.PathingPath)
 
     def pathing_set_probes(self, xyz=None):
         """fs_pathing_set_probes: the probe set, [count][3] points in free air (cm); None or an empty array clears it.  Drops any bake"""
@@ -526,12 +511,7 @@ class Context:
         direction (from the listener towards the first probe), departure (from the source towards the last), hops, flags
         (PATHING_FOUND | PATHING_DIRECT | PATHING_STALE), first_probe, last_probe, probes [16] from the listener's end, gain [8];
         params = the fields of fs_pathing_params (validate, max_attach, max_length, step, pullback, dist_divisor, sound_speed)"""
-        srcs = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
-        p = _capi.default_pathing_params(**params)
-        out = np.zeros(srcs.shape[0], dtype=self.PATHING_DTYPE)
-        self.check(self.lib.fs_update_pathing_paths(self.h, srcs.ctypes.data if srcs.size else None, int(srcs.shape[0]), C.byref(p),
-                                                    out.ctypes.data if out.size else None))
-        return out
+        return self._out_only("pathing", sources, params)
 
     # ---- the audio callbacks: what the three *_process_batch mirrors share ----
     def _callback_open(self, sources, blocks, frames, want_out, want_mix):
@@ -578,7 +558,7 @@ class Context:
         return table, counts, stride
 
     # ---- direct sound on the audio thread: fractional delay + band FIR for all sources of a callback ----
-    RENDER_TARGET_DTYPE = np.dtype([("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,))])
+    RENDER_TARGET_DTYPE = record_dtype(_capi.DirectRenderTarget)
 
     @staticmethod
     def direct_band_kernels(sample_rate, bands, taps, edges=None):
@@ -622,9 +602,8 @@ class Context:
         return self._callback_close(out, mix)
 
     # ---- early reflections on the audio thread: a bank of delayed, filtered, panned voices per source ----
-    REFLECTION_VOICE_DTYPE = np.dtype([("key", np.uint32), ("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,)),
-                                       ("channel_gain", np.float32, (2,))])
-    REFLECTION_RENDER_ROW_DTYPE = np.dtype([("sounding", np.uint32), ("started", np.uint32), ("ended", np.uint32), ("dropped", np.uint32)])
+    REFLECTION_VOICE_DTYPE = record_dtype(_capi.ReflectionVoice)
+    REFLECTION_RENDER_ROW_DTYPE = record_dtype(_capi.ReflectionRenderRow)
 
     def reflection_render_init(self, src, frame_size=1024, taps=255, voices=32, max_delay_seconds=1.0):
         self.check(self.lib.fs_reflection_render_init(self.h, src, int(frame_size), int(taps), int(voices), float(max_delay_seconds)))
@@ -655,9 +634,8 @@ class Context:
         return self._callback_close(out, mix, rows)
 
     # ---- binaural voices on the audio thread: the voice bank with a direction per voice and an HRIR set per context ----
-    BINAURAL_VOICE_DTYPE = np.dtype([("key", np.uint32), ("delay", np.float32), ("band_gain", np.float32, (_capi.MAX_BANDS,)),
-                                     ("gain", np.float32), ("direction", np.float32, (3,))])
-    BINAURAL_RENDER_ROW_DTYPE = np.dtype([("sounding", np.uint32), ("started", np.uint32), ("ended", np.uint32), ("dropped", np.uint32)])
+    BINAURAL_VOICE_DTYPE = record_dtype(_capi.BinauralVoice)
+    BINAURAL_RENDER_ROW_DTYPE = record_dtype(_capi.BinauralRenderRow)
 
     @staticmethod
     def hrtf_spherical_head(sample_rate, directions, taps, radius_cm=_capi.HRTF_DEFAULT_RADIUS_CM,
@@ -727,7 +705,7 @@ class Context:
 
     # ---- ambisonic voices on the audio thread: the voice bank with a direction per voice, rendered into a soundfield ----
     AMBISONIC_VOICE_DTYPE = BINAURAL_VOICE_DTYPE   # fs_ambisonic_voice is fs_binaural_voice
-    AMBISONIC_RENDER_ROW_DTYPE = np.dtype([("sounding", np.uint32), ("started", np.uint32), ("ended", np.uint32), ("dropped", np.uint32)])
+    AMBISONIC_RENDER_ROW_DTYPE = record_dtype(_capi.AmbisonicRenderRow)
 
     @staticmethod
     def ambisonic_encode(order, direction):
@@ -1163,70 +1141,50 @@ class AudioRayTracingSubsystem:
         self._commit()
         self.ctx.update_sources([s._src for s in srcs], self.params)
 
+    def _update_paths(self, kind, **params):
+        """the body of the Update*Paths methods: Context.<kind>_paths over the active sources, PATH_QUERY[kind].max_batch at a time;
+        without sources empty arrays — (rows [0], paths [0][0]), or rows [0] of an out-only query"""
+        q = _capi.PATH_QUERY[kind]
+        srcs = [s._src for s in self.ActiveSources]
+        if not srcs:
+            empty = np.zeros(0, dtype=record_dtype(q.path))
+            return empty if q.row is None else (np.zeros(0, dtype=record_dtype(q.row)), empty.reshape(0, 0))
+        self._commit()
+        query = getattr(self.ctx, kind + "_paths")
+        parts = [query(srcs[i:i + q.max_batch], **params) for i in range(0, len(srcs), q.max_batch)]
+        if q.row is None:
+            return np.concatenate(parts)
+        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
+
     def UpdateDirectPaths(self, **params):
         """the direct sound of all active sources in one launch: a structured array, row i for ActiveSources[i]
         (Context.direct_paths; more than 256 sources take one launch per 256)"""
-        srcs = [s._src for s in self.ActiveSources]
-        if not srcs:
-            return np.zeros(0, dtype=Context.DIRECT_DTYPE)
-        self._commit()
-        step = _capi.MAX_DIRECT_BATCH
-        return np.concatenate([self.ctx.direct_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)])
+        return self._update_paths("direct", **params)
 
     def UpdateReflectionPaths(self, **params):
         """the first-order specular reflections of all active sources: (rows, paths), row i and paths[i] for ActiveSources[i]
         (Context.reflection_paths; more than 256 sources take one call per 256)"""
-        srcs = [s._src for s in self.ActiveSources]
-        if not srcs:
-            return np.zeros(0, dtype=Context.REFLECTION_ROW_DTYPE), np.zeros((0, 0), dtype=Context.REFLECTION_DTYPE)
-        self._commit()
-        step = _capi.MAX_REFLECTION_BATCH
-        parts = [self.ctx.reflection_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
-        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
+        return self._update_paths("reflection", **params)
 
     def UpdateDiffractionPaths(self, **params):
         """the first-order edge diffraction of all active sources: (rows, paths), row i and paths[i] for ActiveSources[i]
         (Context.diffraction_paths; more than 256 sources take one call per 256)"""
-        srcs = [s._src for s in self.ActiveSources]
-        if not srcs:
-            return np.zeros(0, dtype=Context.DIFFRACTION_ROW_DTYPE), np.zeros((0, 0), dtype=Context.DIFFRACTION_DTYPE)
-        self._commit()
-        step = _capi.MAX_DIFFRACTION_BATCH
-        parts = [self.ctx.diffraction_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
-        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
+        return self._update_paths("diffraction", **params)
 
     def UpdateReflection2Paths(self, **params):
         """the second-order specular reflections of all active sources: (rows, paths), row i and paths[i] for ActiveSources[i]
         (Context.reflection2_paths; more than 256 sources take one call per 256)"""
-        srcs = [s._src for s in self.ActiveSources]
-        if not srcs:
-            return np.zeros(0, dtype=Context.REFLECTION2_ROW_DTYPE), np.zeros((0, 0), dtype=Context.REFLECTION2_DTYPE)
-        self._commit()
-        step = _capi.MAX_REFLECTION2_BATCH
-        parts = [self.ctx.reflection2_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
-        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
+        return self._update_paths("reflection2", **params)
 
     def UpdateDiffraction2Paths(self, **params):
         """the diffraction round thick obstacles of all active sources: (rows, paths), row i and paths[i] for ActiveSources[i]
         (Context.diffraction2_paths; more than 256 sources take one call per 256)"""
-        srcs = [s._src for s in self.ActiveSources]
-        if not srcs:
-            return np.zeros(0, dtype=Context.DIFFRACTION2_ROW_DTYPE), np.zeros((0, 0), dtype=Context.DIFFRACTION2_DTYPE)
-        self._commit()
-        step = _capi.MAX_DIFFRACTION2_BATCH
-        parts = [self.ctx.diffraction2_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
-        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
+        return self._update_paths("diffraction2", **params)
 
     def UpdateMixedPaths(self, **params):
         """the paths off one reflector and round one edge of all active sources: (rows, paths), row i and paths[i] for
         ActiveSources[i] (Context.mixed_paths; more than 256 sources take one call per 256)"""
-        srcs = [s._src for s in self.ActiveSources]
-        if not srcs:
-            return np.zeros(0, dtype=Context.MIXED_ROW_DTYPE), np.zeros((0, 0), dtype=Context.MIXED_DTYPE)
-        self._commit()
-        step = _capi.MAX_MIXED_BATCH
-        parts = [self.ctx.mixed_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)]
-        return np.concatenate([r for r, _ in parts]), np.concatenate([p for _, p in parts])
+        return self._update_paths("mixed", **params)
 
     def SetPathingProbes(self, xyz=None, **bake_params):
         """the probe graph of the registered geometry: the probes (Context.pathing_set_probes) and, with any, the bake
@@ -1243,12 +1201,7 @@ class AudioRayTracingSubsystem:
     def UpdatePathingPaths(self, **params):
         """the route through the probe graph of all active sources: row i for ActiveSources[i] (Context.pathing_paths; more than
         256 sources take one call per 256)"""
-        srcs = [s._src for s in self.ActiveSources]
-        if not srcs:
-            return np.zeros(0, dtype=Context.PATHING_DTYPE)
-        self._commit()
-        step = _capi.MAX_PATHING_BATCH
-        return np.concatenate([self.ctx.pathing_paths(srcs[i:i + step], **params) for i in range(0, len(srcs), step)])
+        return self._update_paths("pathing", **params)
 
     def SetPipelining(self, depth):
         """fs_set_pipelining: Tick then updates the sources one after the other like the reference's loop (ARTS.cpp:60-68),
@@ -1482,35 +1435,56 @@ class FrequenSeeAudioReflectionPlugin:
             o["channel_gain"] = left_right
         return v
 
+    # The kinds of path Voices() walks, in its order: (name, key of a path record, band-gain field, are colliding keys dropped).
+    # The pathing voice, one record and no list, comes after them.
+    _KINDS = (
+        ("reflection", lambda self, p: int(p["triangle"]), "reflectance", False),
+        ("diffraction", lambda self, p: _capi.DIFFRACTION_VOICE_TAG | (int(p["triangle"]) * 4 + int(p["edge"])), "gain", False),
+        ("second", lambda self, p: self.SecondOrderKey(p["triangle"][0], p["triangle"][1]), "reflectance", True),
+        ("diffraction2", lambda self, p: self.Diffraction2Key(p["triangle"], p["edge"]), "gain", True),
+        ("mixed", lambda self, p: self.MixedKey(p["triangle"], p["edge"], p["end"]), "gain", True),
+    )
+    # The range checks, in the order they are made on a path: (the kinds whose triangle is checked, the kinds whose presence arms
+    # the check, the limit, the error)
+    _RANGE_CHECKS = (
+        (("reflection", "diffraction"), ("diffraction", "second", "diffraction2", "mixed"), _capi.REFLECTION2_VOICE_TAG >> 1,
+         "Voices: triangle index 2^29 or above: the keys of the path kinds would collide"),
+        (("diffraction",), ("mixed",), _capi.MIXED_VOICE_TAG >> 4,
+         "Voices: a diffraction path's triangle index is 2^28 or above: its key would collide with the mixed paths' keys"),
+    )
+
     def _path_entries(self, row, paths, diffraction=None, second=None, diffraction2=None, mixed=None, pathing=None):
         """what Voices() keeps of a source's path records, in its order, as (key, path record, band gains): the keys, their range
         checks and the dropping of colliding keys as Voices() documents them"""
-        n = int(row["returned"])
-        m = 0 if diffraction is None else int(diffraction[0]["returned"])
-        k = 0 if second is None else int(second[0]["returned"])
-        k2 = 0 if diffraction2 is None else int(diffraction2[0]["returned"])
-        k3 = 0 if mixed is None else int(mixed[0]["returned"])
-        tagged = diffraction is not None or second is not None or diffraction2 is not None or mixed is not None
+        given = dict(reflection=(row, paths), diffraction=diffraction, second=second, diffraction2=diffraction2, mixed=mixed)
         seen, kept = set(), []
-        for i in range(n + m + k + k2 + k3):
-            p = paths[i] if i < n else (diffraction[1][i - n] if i < n + m else (second[1][i - n - m] if i < n + m + k else (
-                diffraction2[1][i - n - m - k] if i < n + m + k + k2 else mixed[1][i - n - m - k - k2])))
-            if i < n + m:
-                if tagged and int(p["triangle"]) >= _capi.REFLECTION2_VOICE_TAG >> 1:
-                    raise ValueError("Voices: triangle index 2^29 or above: the keys of the path kinds would collide")
-                if mixed is not None and i >= n and int(p["triangle"]) >= _capi.MIXED_VOICE_TAG >> 4:
-                    raise ValueError("Voices: a diffraction path's triangle index is 2^28 or above: its key would collide with the mixed paths' keys")
-                key = int(p["triangle"]) if i < n else _capi.DIFFRACTION_VOICE_TAG | (int(p["triangle"]) * 4 + int(p["edge"]))
-            else:
-                key = self.SecondOrderKey(p["triangle"][0], p["triangle"][1]) if i < n + m + k else (
-                    self.Diffraction2Key(p["triangle"], p["edge"]) if i < n + m + k + k2 else self.MixedKey(p["triangle"], p["edge"], p["end"]))
-                if key in seen:
-                    continue
-                seen.add(key)
-            kept.append((key, p, p["gain"] if n <= i < n + m or i >= n + m + k else p["reflectance"]))
+        for name, key_of, gain_field, drop_collisions in self._KINDS:
+            if given[name] is None:
+                continue
+            k_row, k_paths = given[name]
+            checks = [(limit, text) for kinds, armed_by, limit, text in self._RANGE_CHECKS
+                      if name in kinds and any(given[a] is not None for a in armed_by)]
+            for p in k_paths[:int(k_row["returned"])]:
+                for limit, text in checks:
+                    if int(p["triangle"]) >= limit:
+                        raise ValueError(text)
+                key = key_of(self, p)
+                if drop_collisions:
+                    if key in seen:
+                        continue
+                    seen.add(key)
+                kept.append((key, p, p[gain_field]))
         if pathing is not None and int(pathing["flags"]) & (_capi.PATHING_FOUND | _capi.PATHING_DIRECT) == _capi.PATHING_FOUND:
             kept.append((_capi.PATHING_VOICE_KEY, pathing, pathing["gain"]))
         return kept
+
+    @staticmethod
+    def _pick(i, diffraction, second, diffraction2, mixed, pathing):
+        """source i's share of the optional path kinds ProcessAudio takes, as the keywords Voices() takes"""
+        def pair(x):
+            return None if x is None else (x[0][i], x[1][i])
+        return dict(diffraction=pair(diffraction), second=pair(second), diffraction2=pair(diffraction2), mixed=pair(mixed),
+                    pathing=None if pathing is None else pathing[i])
 
     def ProcessAudio(self, components, buffers, rows, paths, right=None, reference_length=None, want_out=True, want_mix=False,
                      diffraction=None, second=None, diffraction2=None, mixed=None, pathing=None):
@@ -1518,12 +1492,8 @@ class FrequenSeeAudioReflectionPlugin:
         paths) of UpdateDiffractionPaths, second = the (rows, paths) of UpdateReflection2Paths, diffraction2 = the (rows, paths) of
         UpdateDiffraction2Paths, mixed = the (rows, paths) of UpdateMixedPaths, pathing = the rows of UpdatePathingPaths, or None.
         Returns what Context.reflection_render_process_batch does."""
-        voices = [self.Voices(rows[i], paths[i], right, reference_length,
-                              None if diffraction is None else (diffraction[0][i], diffraction[1][i]),
-                              None if second is None else (second[0][i], second[1][i]),
-                              None if diffraction2 is None else (diffraction2[0][i], diffraction2[1][i]),
-                              None if mixed is None else (mixed[0][i], mixed[1][i]),
-                              None if pathing is None else pathing[i]) for i in range(len(components))]
+        voices = [self.Voices(rows[i], paths[i], right, reference_length, **self._pick(i, diffraction, second, diffraction2, mixed, pathing))
+                  for i in range(len(components))]
         return self.ctx.reflection_render_process_batch([c._src for c in components], buffers, voices,
                                                         want_out=want_out, want_mix=want_mix)
 
@@ -1587,13 +1557,11 @@ class FrequenSeeAudioBinauralPlugin(FrequenSeeAudioReflectionPlugin):
         """buffers[i] is components[i]'s block, rows[i] / paths[i] its results of UpdateReflectionPaths; direct = (the rows of
         UpdateDirectPaths, the listener's location) or None; the other path kinds as FrequenSeeAudioReflectionPlugin.ProcessAudio
         takes them.  Returns what Context.binaural_render_process_batch does."""
-        def pick(pair, i):
-            return None if pair is None else (pair[0][i], pair[1][i])
         voices = []
         for i, c in enumerate(components):
             d = None if direct is None else (direct[0][i], np.asarray(c.GetComponentLocation(), np.float64) - np.asarray(direct[1], np.float64))
-            voices.append(self.Voices(rows[i], paths[i], forward, right, reference_length, d, pick(diffraction, i), pick(second, i),
-                                      pick(diffraction2, i), pick(mixed, i), None if pathing is None else pathing[i]))
+            voices.append(self.Voices(rows[i], paths[i], forward, right, reference_length, d,
+                                      **self._pick(i, diffraction, second, diffraction2, mixed, pathing)))
         return self._render(components, buffers, voices, want_out, want_mix)
 
     def _render(self, components, buffers, voices, want_out, want_mix):

@@ -14,9 +14,12 @@ import os
 import numpy as np
 import pytest
 
+pytest.register_assert_rewrite("path_query_contract")
+import path_query_contract as contract  # noqa: E402
+from path_query_contract import assert_equal  # noqa: E402
 from test_diffraction_paths import BLIS, BSRC, Diffraction, fmaf_arrays
 from test_diffraction_paths import box_world as corner_box_world
-from test_reflection_paths import (ALPHA, HI, LO, NO_MATERIAL, NO_OBJECT, OPAQUE, SCAT, TAU, F, World, bits, box, cross, device_free_bytes,
+from test_reflection_paths import (ALPHA, HI, LO, NO_MATERIAL, NO_OBJECT, OPAQUE, SCAT, TAU, F, World, bits, box, cross,
                                    dot, fmaf, place, quad_grid, shoebox_world)
 
 DEFAULTS = dict(max_paths=4, max_near=16384, max_candidates=1024, margin=1e-3, max_detour=250.0, min_parallel=0.999, offset=0.1, merge=1.0,
@@ -235,19 +238,6 @@ class Diffraction2(Diffraction):
         return rows, paths
 
 
-def assert_equal(got, want, where=""):
-    (grows, gpaths), (wrows, wpaths) = got, want
-    assert grows.shape == wrows.shape and gpaths.shape == wpaths.shape, where
-    for i in range(len(wrows)):
-        for k in wrows.dtype.names:
-            assert grows[i][k] == wrows[i][k], f"{where} row {i}: {k}: got {grows[i][k]!r}, restatement {wrows[i][k]!r}"
-        for j in range(wpaths.shape[1]):
-            for k in wpaths.dtype.names:
-                g, y = np.atleast_1d(gpaths[i, j][k]), np.atleast_1d(wpaths[i, j][k])
-                assert g.tobytes() == y.tobytes(), f"{where} row {i} path {j}: {k}: got {g!r}, restatement {y!r}"
-    assert grows.tobytes() == wrows.tobytes() and gpaths.tobytes() == wpaths.tobytes(), where
-
-
 # ---- the scene ------------------------------------------------------------------------------------------------------
 SRC, LIS = [300.0, 200.0, 120.0], [720.0, 260.0, 110.0]          # either side of the thick box
 BOX = ([450.0, 0.0, 0.0], [550.0, 400.0, 200.0])                 # flush with the y = 0 wall, 100 cm thick, below the ceiling
@@ -345,45 +335,11 @@ def test_struct_sizes_and_defaults(pkg):
 
 
 def test_exported_in_one_tier(pkg):
-    cap = pkg._capi
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "frequensee.h")).read()
-    opening = header[:header.index("#ifndef FREQUENSEE_H")]
-    core = opening[opening.index("CORE:"):opening.index("EXTENDED =")]
-    extended = opening[opening.index("EXTENDED:"):]
-    for name in ("fs_diffraction2_params_default", "fs_update_diffraction2_paths"):
-        assert name in cap.EXPORTS and hasattr(cap.load(), name)
-        assert name in extended.split() and name not in core.split()
-        assert opening.split().count(name) == 1
+    contract.exported_in_one_tier(pkg, ("fs_diffraction2_params_default", "fs_update_diffraction2_paths"))
 
 
 def test_null_context_and_no_device(pkg):
-    cap = pkg._capi
-    lib = cap.load()
-    src = (C.c_int32 * 1)(0)
-    rows = np.full(1, 7, dtype=pkg.Context.DIFFRACTION2_ROW_DTYPE)
-    paths = np.full((1, 4), 7, dtype=pkg.Context.DIFFRACTION2_DTYPE)
-    before = rows.tobytes(), paths.tobytes()
-    assert lib.fs_update_diffraction2_paths(None, src, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    lib.fs_diffraction2_params_default(None)   # tolerated, like the other *_default calls
-    import torch
-    if not torch.cuda.is_available():
-        h = C.c_void_p()
-        cfg = cap.default_config(num_bands=1)
-        assert lib.fs_context_create(C.byref(cfg), C.byref(h)) == cap.ERR_NO_DEVICE and h
-        try:
-            assert lib.fs_update_diffraction2_paths(h, src, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_NO_DEVICE
-            assert b"no CPU fallback" in lib.fs_last_error(h)
-            assert lib.fs_update_diffraction2_paths(h, None, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_diffraction2_paths(h, src, 1, None, None, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_diffraction2_paths(h, src, 1, None, rows.ctypes.data, None) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_diffraction2_paths(h, src, 0, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_diffraction2_paths(h, src, 257, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            for kw in (dict(max_detour=0.0), dict(min_parallel=0.0), dict(min_parallel=1.5), dict(max_near=0)):
-                q = cap.default_diffraction2_params(**kw)
-                assert lib.fs_update_diffraction2_paths(h, src, 1, C.byref(q), rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-        finally:
-            lib.fs_context_destroy(h)
-    assert (rows.tobytes(), paths.tobytes()) == before
+    contract.null_context_and_no_device(pkg, QUERY)
 
 
 def test_reference_figures():
@@ -488,10 +444,7 @@ def test_restatement_rotated_box(pkg, oracle_mod):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------
-def check(pkg, ctx, y, handles, positions, listener, where, src_obj=None, lis_obj=NO_OBJECT, **params):
-    got = ctx.diffraction2_paths(handles, **params)
-    assert_equal(got, y.expect(pkg, positions, listener, src_obj, lis_obj, **params), where)
-    return got
+check = contract.checker("diffraction2")
 
 
 @pytest.mark.gpu
@@ -724,15 +677,7 @@ def test_rooms(pkg, oracle_mod, fast):
     h = place(ctx, rc["pos"])
     rows, paths = got = ctx.diffraction2_paths(h, max_detour=ROOMS_DETOUR)
     assert_equal(got, rc["want"], f"rooms fast={fast}")
-    if not fast:
-        ones = [ctx.diffraction2_paths([x], max_detour=ROOMS_DETOUR) for x in h]
-        assert np.concatenate([r for r, _ in ones]).tobytes() == rows.tobytes(), "count = 8 differs from 8 calls with count = 1"
-        assert np.concatenate([p for _, p in ones]).tobytes() == paths.tobytes(), "count = 8 differs from 8 calls with count = 1"
-    perm = np.random.default_rng(7).permutation(8)
-    prows, ppaths = ctx.diffraction2_paths([h[i] for i in perm], max_detour=ROOMS_DETOUR)
-    assert prows.tobytes() == rows[perm].tobytes() and ppaths.tobytes() == paths[perm].tobytes(), "a permuted list"
-    frows, fpaths = ctx.diffraction2_paths(h[:5], max_detour=ROOMS_DETOUR)   # one confirm workgroup with idle waves beside a full one
-    assert frows.tobytes() == rows[:5].tobytes() and fpaths.tobytes() == paths[:5].tobytes()
+    contract.batch_agrees(ctx.diffraction2_paths, h, got, singles=not fast, max_detour=ROOMS_DETOUR)
     ctx.close()
 
 
@@ -748,12 +693,8 @@ def test_mover(pkg, oracle_mod):
     rows, _ = check(pkg, ctx, Diffraction2(oracle_mod, w), h, [SRC], LIS, "door shut")
     assert rows[0]["found"] == 0
     aside = np.array([[1, 0, 0, 0], [0, 1, 0, 500], [0, 0, 1, 0]], np.float32)
-    moved = w.tri.copy()
-    idx = w.obj == 5
-    p = moved[idx]
-    moved[idx] = np.stack([((aside[k, 0] * p[..., 0] + aside[k, 1] * p[..., 1]) + aside[k, 2] * p[..., 2]) + aside[k, 3] for k in range(3)], axis=-1)
     ctx.set_object_transforms([5], aside[None])
-    rows, paths = check(pkg, ctx, Diffraction2(oracle_mod, w, moved), h, [SRC], LIS, "door aside, no explicit refit")   # the call refits first
+    rows, paths = check(pkg, ctx, Diffraction2(oracle_mod, w, contract.transformed(w, 5, aside)), h, [SRC], LIS, "door aside, no explicit refit")   # the call refits first
     assert rows[0]["found"] == 1 and abs(float(paths[0][0]["apex"][0][1]) - 400.0) < 1e-3
     ctx.set_object_transforms([5], np.eye(3, 4, dtype=np.float32)[None])
     rows, _ = check(pkg, ctx, Diffraction2(oracle_mod, w), h, [SRC], LIS, "door back")
@@ -761,94 +702,45 @@ def test_mover(pkg, oracle_mod):
     ctx.close()
 
 
-@pytest.mark.gpu
-def test_errors_and_untouched_state(pkg, oracle_mod):
-    cap = pkg._capi
-    lib = cap.load()
-    w = box_world(1)
-    ctx = pkg.Context(num_bands=4)
-    src = ctx.create_source(SRC)
-    arr = (C.c_int32 * 2)(src, src)
-    rows = np.full(2, 7, dtype=pkg.Context.DIFFRACTION2_ROW_DTYPE)
-    paths = np.full((2, 16), 7, dtype=pkg.Context.DIFFRACTION2_DTYPE)
-    sentinel = rows.tobytes(), paths.tobytes()
+def _defaults_found(t, oracle_mod, want):
+    assert_equal(want, Diffraction2(oracle_mod, t.w).expect(t.pkg, [SRC, SRC], LIS), "defaults, one handle twice")
+    assert tuple(want[0][0])[3:] == (2, 2, 0)
 
-    def call(sources=arr, count=2, params=None, r=rows, p=paths, **kw):
-        q = cap.default_diffraction2_params(**kw) if (kw or params is None) else params
-        return lib.fs_update_diffraction2_paths(ctx.h, sources, count, C.byref(q), r.ctypes.data if r is not None else None,
-                                                p.ctypes.data if p is not None else None)
 
-    assert call() == cap.ERR_NOT_COMMITTED
-    ctx.set_scene(w.tri, w.mat, w.absorption, w.transmission, w.scattering, object_ids=w.obj)
-    ctx.set_listener(LIS)
-    assert call(sources=None) == cap.ERR_INVALID_ARGUMENT
-    assert call(r=None) == cap.ERR_INVALID_ARGUMENT
-    assert call(p=None) == cap.ERR_INVALID_ARGUMENT
-    assert lib.fs_update_diffraction2_paths(None, arr, 2, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    many = (C.c_int32 * 257)(*([src] * 257))
-    for bad in (0, -1, 257):
-        assert call(sources=many, count=bad) == cap.ERR_INVALID_ARGUMENT
-    q = cap.default_diffraction2_params()
-    q.struct_size = 44
-    assert call(params=q) == cap.ERR_INVALID_ARGUMENT
-    inf, nan = float("inf"), float("nan")
-    for kw in (dict(max_paths=0), dict(max_paths=17), dict(max_near=0), dict(max_near=32769), dict(max_candidates=0), dict(max_candidates=2049),
-               dict(margin=-1e-3), dict(margin=nan), dict(margin=inf), dict(max_detour=0.0), dict(max_detour=-1.0), dict(max_detour=nan),
-               dict(max_detour=inf), dict(min_parallel=0.0), dict(min_parallel=-0.5), dict(min_parallel=1.0001), dict(min_parallel=nan),
-               dict(min_parallel=inf), dict(offset=-0.1), dict(offset=nan), dict(offset=inf), dict(merge=-1.0), dict(merge=nan), dict(merge=inf),
-               dict(step=-0.1), dict(step=nan), dict(step=inf), dict(pullback=-1.0), dict(pullback=nan), dict(pullback=inf),
-               dict(dist_divisor=0.0), dict(dist_divisor=-1.0), dict(dist_divisor=nan), dict(dist_divisor=inf), dict(sound_speed=0.0),
-               dict(sound_speed=-1.0), dict(sound_speed=nan), dict(sound_speed=inf)):
-        assert call(**kw) == cap.ERR_INVALID_ARGUMENT, kw
-    assert call(sources=(C.c_int32 * 2)(src, 12345)) == cap.ERR_BAD_HANDLE
-    assert call(sources=(C.c_int32 * 2)(-1, src)) == cap.ERR_BAD_HANDLE
-    assert (rows.tobytes(), paths.tobytes()) == sentinel, "a refused call wrote"
-    # NULL params = the defaults; extreme but legal values are taken
-    r4, p4 = np.full(2, 7, dtype=rows.dtype), np.full((2, 4), 7, dtype=paths.dtype)
-    assert lib.fs_update_diffraction2_paths(ctx.h, arr, 2, None, r4.ctypes.data, p4.ctypes.data) == cap.OK
-    want = ctx.diffraction2_paths([src, src])
-    assert r4.tobytes() == want[0].tobytes() and p4.tobytes() == want[1].tobytes()
-    assert_equal(want, Diffraction2(oracle_mod, w).expect(pkg, [SRC, SRC], LIS), "defaults, one handle twice")
-    assert tuple(r4[0])[3:] == (2, 2, 0)
-    assert call(max_paths=16, max_near=32768, max_candidates=2048, margin=0.0, min_parallel=1.0, offset=0.0, merge=0.0, step=0.0, pullback=0.0) == cap.OK
-    assert call(max_paths=16, max_candidates=1) == cap.OK
+def _legal_found(rows):
     assert tuple(rows[0])[2:] == (0, 0, 0, OVERFLOW) and rows[0]["candidates"] > 1
 
-    # a successful call leaves the sources alone: energy, IR publish number, occlusion scalar
-    fp = pkg.default_params(num_rays=512, depth=4, seed=3)
-    ctx.compute_energy_response(src, fp)
-    ctx.reconstruct_impulse_response(src, fp)
-    ctx.update_sound(src, cap.default_sound_params(raycasts_per_tick=64))
-    before = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    ctx.diffraction2_paths([src])
-    after = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    assert before == after
-    ctx.close()
-    # an empty committed scene: rows of zeros
-    e = World([], ALPHA, TAU, 4, SCAT)
-    ctx = e.context(pkg)
-    ctx.set_listener(LIS)
-    rows, paths = check(pkg, ctx, Diffraction2(oracle_mod, e), place(ctx, [SRC, LIS]), [SRC, LIS], LIS, "empty")
-    assert np.all(rows.view(np.uint8) == 0) and np.all(paths.view(np.uint8) == 0)
-    ctx.close()
+
+def _steady_found(ctx, h, first, fewer):
+    assert np.all(first[0]["found"] == 2)
+
+
+inf, nan = float("inf"), float("nan")
+QUERY = contract.Query(
+    kind="diffraction2", dtypes=("DIFFRACTION2_ROW_DTYPE", "DIFFRACTION2_DTYPE"), world=lambda: box_world(1), src=SRC, lis=LIS, wrong_struct_size=44,
+    null_paths=4, refused_without_device=(dict(max_detour=0.0), dict(min_parallel=0.0), dict(min_parallel=1.5), dict(max_near=0)),
+    refused=(dict(max_paths=0), dict(max_paths=17), dict(max_near=0), dict(max_near=32769), dict(max_candidates=0), dict(max_candidates=2049),
+             dict(margin=-1e-3), dict(margin=nan), dict(margin=inf), dict(max_detour=0.0), dict(max_detour=-1.0), dict(max_detour=nan),
+             dict(max_detour=inf), dict(min_parallel=0.0), dict(min_parallel=-0.5), dict(min_parallel=1.0001), dict(min_parallel=nan),
+             dict(min_parallel=inf), dict(offset=-0.1), dict(offset=nan), dict(offset=inf), dict(merge=-1.0), dict(merge=nan), dict(merge=inf),
+             dict(step=-0.1), dict(step=nan), dict(step=inf), dict(pullback=-1.0), dict(pullback=nan), dict(pullback=inf),
+             dict(dist_divisor=0.0), dict(dist_divisor=-1.0), dict(dist_divisor=nan), dict(dist_divisor=inf), dict(sound_speed=0.0),
+             dict(sound_speed=-1.0), dict(sound_speed=nan), dict(sound_speed=inf)),
+    defaults_found=_defaults_found,
+    legal=(dict(max_paths=16, max_near=32768, max_candidates=2048, margin=0.0, min_parallel=1.0, offset=0.0, merge=0.0, step=0.0, pullback=0.0),
+           dict(max_paths=16, max_candidates=1)),
+    legal_found=_legal_found, yardstick=Diffraction2, empty_world=lambda: World([], ALPHA, TAU, 4, SCAT),
+    fewer=dict(max_paths=16, max_near=32768, max_candidates=2048), steady_found=_steady_found)
+
+
+@pytest.mark.gpu
+def test_errors_and_untouched_state(pkg, oracle_mod):
+    contract.errors_and_untouched_state(pkg, oracle_mod, QUERY)
 
 
 @pytest.mark.gpu
 def test_steady_state_allocates_nothing(pkg):
-    w = box_world(1)
-    ctx = w.context(pkg)
-    ctx.set_listener(LIS)
-    h = place(ctx, [SRC] * 40)
-    first = ctx.diffraction2_paths(h)
-    free0 = device_free_bytes()
-    for _ in range(20):
-        again = ctx.diffraction2_paths(h)
-    fewer = ctx.diffraction2_paths(h[:7], max_paths=16, max_near=32768, max_candidates=2048)   # a smaller count, larger caps: fits what is there
-    assert device_free_bytes() >= free0
-    assert again[0].tobytes() == first[0].tobytes() and again[1].tobytes() == first[1].tobytes()
-    assert np.all(first[0]["found"] == 2)
-    assert fewer[0].tobytes() == first[0][:7].tobytes() and fewer[1][:, :4].tobytes() == first[1][:7].tobytes()
-    ctx.close()
+    contract.steady_state_allocates_nothing(pkg, QUERY)
 
 
 def interleaved_positions():
@@ -872,28 +764,9 @@ def test_queries_interleaved_on_one_context(pkg):
         ctx.set_listener(LIS)
         return ctx, place(ctx, pos)
 
-    def run(ctx, h, query, count):
-        if query == "direct":
-            return (ctx.direct_paths(h[:count], samples=16, source_radius=30.0),)
-        if query == "reflection2":
-            return ctx.reflection2_paths(h[:count], max_length=1e6)
-        return getattr(ctx, query + "_paths")(h[:count])
-
     calls = [("diffraction2", 5), ("reflection2", 5), ("diffraction", 5), ("direct", 33), ("reflection", 5), ("diffraction2", 33), ("reflection2", 33),
              ("diffraction", 33), ("reflection", 33), ("direct", 5), ("diffraction2", 5), ("reflection2", 5), ("diffraction", 5), ("reflection", 5)]
-    ctx, h = fresh()
-    got = [run(ctx, h, query, count) for query, count in calls]
-    ctx.close()
-    first = {}
-    for i, ((query, count), g) in enumerate(zip(calls, got)):
-        if (query, count) not in first:
-            one, h1 = fresh()
-            first[query, count] = run(one, h1, query, count)
-            one.close()
-        want = first[query, count]
-        assert len(g) == len(want) and all(len(a) == count for a in g)
-        for a, b in zip(g, want):
-            assert a.tobytes() == b.tobytes(), f"call {i} ({query}, count {count}) differs from the same call on a fresh context"
+    got = contract.queries_interleaved_on_one_context(fresh, calls, dict(reflection2=dict(max_length=1e6)))
     # the comparison is not of zeros
     assert np.any(got[5][0]["returned"] > 0) and np.any(got[6][0]["returned"] > 0) and np.any(got[8][0]["returned"] > 0)
     assert got[0][0][0]["found"] == 2

@@ -9,11 +9,14 @@ crossings sorted by t) on the samples whose float64 crossings are not marginal.
 """
 import ctypes as C
 import math
-import os
 import struct
 
 import numpy as np
 import pytest
+
+pytest.register_assert_rewrite("path_query_contract")
+import path_query_contract as contract  # noqa: E402
+from path_query_contract import device_free_bytes, place  # noqa: E402,F401  (other test files import device_free_bytes from here)
 
 F = np.float32
 NO_OBJECT = 0xFFFFFFFF
@@ -209,26 +212,7 @@ def test_struct_sizes_and_defaults(pkg):
 
 
 def test_null_context_and_no_device(pkg):
-    cap = pkg._capi
-    lib = cap.load()
-    src = (C.c_int32 * 1)(0)
-    out = np.full(1, 7, dtype=pkg.Context.DIRECT_DTYPE)
-    before = out.tobytes()
-    assert lib.fs_update_direct_paths(None, src, 1, None, out.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    lib.fs_direct_params_default(None)   # tolerated, like the other *_default calls
-    import torch
-    if not torch.cuda.is_available():
-        h = C.c_void_p()
-        cfg = cap.default_config(num_bands=1)
-        assert lib.fs_context_create(C.byref(cfg), C.byref(h)) == cap.ERR_NO_DEVICE and h
-        try:
-            assert lib.fs_update_direct_paths(h, src, 1, None, out.ctypes.data) == cap.ERR_NO_DEVICE
-            assert b"no CPU fallback" in lib.fs_last_error(h)
-            assert lib.fs_update_direct_paths(h, None, 1, None, out.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_direct_paths(h, src, 0, None, out.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-        finally:
-            lib.fs_context_destroy(h)
-    assert out.tobytes() == before
+    contract.null_context_and_no_device(pkg, QUERY)
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 16, 64])
@@ -365,10 +349,6 @@ def test_yardstick_against_float64_brute_force(pkg, oracle_mod, name):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------
-def place(ctx, positions):
-    return [ctx.create_source(p) for p in positions]
-
-
 def check_rows(ctx, y, handles, positions, listener, off, where, src_obj=None, lis_obj=NO_OBJECT, **params):
     rows = ctx.direct_paths(handles, **params)
     for i, S in enumerate(positions):
@@ -553,12 +533,8 @@ def test_movers(pkg, oracle_mod):
     rows = check_rows(ctx, Yardstick(oracle_mod, w), h, [SRC], LIS, off, "door shut", **params)
     assert rows[0]["visibility"] == 0 and rows[0]["surfaces"] == 1
     aside = np.array([[1, 0, 0, 0], [0, 1, 0, 350], [0, 0, 1, 0]], np.float32)
-    moved = w.tri.copy()
-    idx = w.obj == 5
-    p = moved[idx]
-    moved[idx] = np.stack([((aside[k, 0] * p[..., 0] + aside[k, 1] * p[..., 1]) + aside[k, 2] * p[..., 2]) + aside[k, 3] for k in range(3)], axis=-1)
     ctx.set_object_transforms([5], aside[None])
-    rows = check_rows(ctx, Yardstick(oracle_mod, w, moved), h, [SRC], LIS, off, "door aside, no explicit refit", **params)   # the call refits first
+    rows = check_rows(ctx, Yardstick(oracle_mod, w, contract.transformed(w, 5, aside)), h, [SRC], LIS, off, "door aside, no explicit refit", **params)   # the call refits first
     assert rows[0]["visibility"] == 1 and rows[0]["surfaces"] == 0 and rows[0]["transmission"][0] == 1
     ctx.set_object_transforms([5], np.eye(3, 4, dtype=np.float32)[None])
     rows = check_rows(ctx, Yardstick(oracle_mod, w), h, [SRC], LIS, off, "door back", **params)
@@ -566,88 +542,29 @@ def test_movers(pkg, oracle_mod):
     ctx.close()
 
 
+def _defaults_found(t, oracle_mod, want):
+    assert want[0][0]["surfaces"] == 2
+
+
+inf, nan = float("inf"), float("nan")
+QUERY = contract.Query(
+    kind="direct", dtypes=("DIRECT_DTYPE",), world=partition_world, src=SRC, lis=LIS, wrong_struct_size=28,
+    refused=(dict(samples=0), dict(samples=65), dict(source_radius=-1.0), dict(source_radius=inf), dict(source_radius=nan),
+             dict(max_surfaces=0), dict(max_surfaces=32), dict(step=-0.1), dict(step=nan), dict(step=inf), dict(pullback=-1.0),
+             dict(pullback=nan), dict(pullback=inf), dict(dist_divisor=0.0), dict(dist_divisor=-1.0), dict(dist_divisor=nan),
+             dict(dist_divisor=inf), dict(sound_speed=0.0), dict(sound_speed=nan), dict(sound_speed=inf)),
+    defaults_found=_defaults_found, legal=(dict(samples=64, source_radius=1.0, max_surfaces=31, step=0.0, pullback=0.0),),
+    untouched=contract.DIRECT_SPHERE, steady=contract.DIRECT_SPHERE)
+
+
 @pytest.mark.gpu
 def test_errors_and_untouched_state(pkg):
-    cap = pkg._capi
-    lib = cap.load()
-    w = partition_world()
-    ctx = pkg.Context(num_bands=4)
-    src = ctx.create_source(SRC)
-    arr = (C.c_int32 * 2)(src, src)
-    out = np.full(2, 7, dtype=pkg.Context.DIRECT_DTYPE)
-    sentinel = out.tobytes()
-
-    def call(sources=arr, count=2, params=None, dest=out, **kw):
-        p = cap.default_direct_params(**kw) if (kw or params is None) else params
-        return lib.fs_update_direct_paths(ctx.h, sources, count, C.byref(p), dest.ctypes.data if dest is not None else None)
-
-    assert call() == cap.ERR_NOT_COMMITTED
-    ctx.set_scene(w.tri, w.mat, w.absorption, w.transmission, object_ids=w.obj)
-    ctx.set_listener(LIS)
-    assert call(sources=None) == cap.ERR_INVALID_ARGUMENT
-    assert call(dest=None) == cap.ERR_INVALID_ARGUMENT
-    assert lib.fs_update_direct_paths(None, arr, 2, None, out.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    many = (C.c_int32 * 257)(*([src] * 257))
-    big = np.full(257, 7, dtype=pkg.Context.DIRECT_DTYPE)
-    for bad in (0, -1, 257):
-        assert call(sources=many, count=bad, dest=big) == cap.ERR_INVALID_ARGUMENT
-    assert big.tobytes() == np.full(257, 7, dtype=pkg.Context.DIRECT_DTYPE).tobytes()
-    p = cap.default_direct_params()
-    p.struct_size = 28
-    assert call(params=p) == cap.ERR_INVALID_ARGUMENT
-    inf, nan = float("inf"), float("nan")
-    for kw in (dict(samples=0), dict(samples=65), dict(source_radius=-1.0), dict(source_radius=inf), dict(source_radius=nan),
-               dict(max_surfaces=0), dict(max_surfaces=32), dict(step=-0.1), dict(step=nan), dict(step=inf), dict(pullback=-1.0),
-               dict(pullback=nan), dict(pullback=inf), dict(dist_divisor=0.0), dict(dist_divisor=-1.0), dict(dist_divisor=nan),
-               dict(dist_divisor=inf), dict(sound_speed=0.0), dict(sound_speed=nan), dict(sound_speed=inf)):
-        assert call(**kw) == cap.ERR_INVALID_ARGUMENT, kw
-    assert call(sources=(C.c_int32 * 2)(src, 12345)) == cap.ERR_BAD_HANDLE
-    assert call(sources=(C.c_int32 * 2)(-1, src)) == cap.ERR_BAD_HANDLE
-    assert out.tobytes() == sentinel, "a refused call wrote rows"
-    # NULL params = the defaults; extreme but legal values are taken
-    assert lib.fs_update_direct_paths(ctx.h, arr, 2, None, out.ctypes.data) == cap.OK
-    assert out.tobytes() == ctx.direct_paths([src, src]).tobytes() and out[0]["surfaces"] == 2
-    assert call(samples=64, source_radius=1.0, max_surfaces=31, step=0.0, pullback=0.0) == cap.OK
-
-    # a successful call leaves the sources alone: energy, IR publish number, occlusion scalar
-    fp = pkg.default_params(num_rays=512, depth=4, seed=3)
-    ctx.compute_energy_response(src, fp)
-    ctx.reconstruct_impulse_response(src, fp)
-    ctx.update_sound(src, cap.default_sound_params(raycasts_per_tick=64))
-    before = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    ctx.direct_paths([src], samples=16, source_radius=30.0)
-    after = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    assert before == after
-    ctx.close()
-
-
-def device_free_bytes():
-    """hipMemGetInfo of the HIP runtime the library itself runs on (the copy of libamdhip64 already mapped into this process: a
-    second runtime, such as the one torch brings along, finds no device once this one holds it)"""
-    import sys
-    torch_dir = os.path.dirname(sys.modules["torch"].__file__) if "torch" in sys.modules else None
-    paths = [line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line]
-    path = next(p for p in paths if torch_dir is None or not p.startswith(torch_dir))
-    hip = C.CDLL(path)
-    free, total = C.c_size_t(), C.c_size_t()
-    assert hip.hipDeviceSynchronize() == 0
-    assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
-    return free.value
+    contract.errors_and_untouched_state(pkg, None, QUERY)
 
 
 @pytest.mark.gpu
 def test_steady_state_allocates_nothing(pkg):
-    w = partition_world()
-    ctx = w.context(pkg)
-    ctx.set_listener(LIS)
-    h = place(ctx, [SRC] * 40)
-    first = ctx.direct_paths(h, samples=16, source_radius=30.0)
-    free0 = device_free_bytes()
-    second = ctx.direct_paths(h, samples=16, source_radius=30.0)
-    third = ctx.direct_paths(h[:7], samples=16, source_radius=30.0)   # a smaller count fits what is there
-    assert device_free_bytes() >= free0
-    assert second.tobytes() == first.tobytes() and third.tobytes() == first[:7].tobytes()
-    ctx.close()
+    contract.steady_state_allocates_nothing(pkg, QUERY)
 
 
 @pytest.mark.gpu

@@ -27,10 +27,13 @@ import os
 import numpy as np
 import pytest
 
+pytest.register_assert_rewrite("path_query_contract")
+import path_query_contract as contract  # noqa: E402
+from path_query_contract import assert_equal  # noqa: E402
 from test_diffraction_paths import fmaf_arrays
 from test_diffraction2_paths import Diffraction2
 from test_reflection_paths import (ALPHA, FREE, NO_MATERIAL, NO_OBJECT, OPAQUE, SCAT, TARGET, TAU, WALLS, F, World, bits, box, cross,
-                                   device_free_bytes, dot, fmaf, place, quad_grid)
+                                   dot, fmaf, place, quad_grid)
 
 DEFAULTS = dict(max_paths=8, max_near=16384, max_candidates=1024, max_length=500.0, max_detour=1000.0, margin=1e-3, offset=0.1, merge=1.0,
                 step=0.1, pullback=0.1, dist_divisor=1000.0, sound_speed=343.0)
@@ -216,19 +219,6 @@ class Mixed(Diffraction2):
                 for k in paths.dtype.names:
                     paths[i, j][k] = y[k]
         return rows, paths
-
-
-def assert_equal(got, want, where=""):
-    (grows, gpaths), (wrows, wpaths) = got, want
-    assert grows.shape == wrows.shape and gpaths.shape == wpaths.shape, where
-    for i in range(len(wrows)):
-        for k in wrows.dtype.names:
-            assert grows[i][k] == wrows[i][k], f"{where} row {i}: {k}: got {grows[i][k]!r}, restatement {wrows[i][k]!r}"
-        for j in range(wpaths.shape[1]):
-            for k in wpaths.dtype.names:
-                g, y = np.atleast_1d(gpaths[i, j][k]), np.atleast_1d(wpaths[i, j][k])
-                assert g.tobytes() == y.tobytes(), f"{where} row {i} path {j}: {k}: got {g!r}, restatement {y!r}"
-    assert grows.tobytes() == wrows.tobytes() and gpaths.tobytes() == wpaths.tobytes(), where
 
 
 # ---- the scene ------------------------------------------------------------------------------------------------------
@@ -424,45 +414,11 @@ def test_struct_sizes_and_defaults(pkg):
 
 
 def test_exported_in_one_tier(pkg):
-    cap = pkg._capi
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "frequensee.h")).read()
-    opening = header[:header.index("#ifndef FREQUENSEE_H")]
-    core = opening[opening.index("CORE:"):opening.index("EXTENDED =")]
-    extended = opening[opening.index("EXTENDED:"):]
-    for name in ("fs_mixed_params_default", "fs_update_mixed_paths"):
-        assert name in cap.EXPORTS and hasattr(cap.load(), name)
-        assert name in extended.split() and name not in core.split()
-        assert opening.split().count(name) == 1
+    contract.exported_in_one_tier(pkg, ("fs_mixed_params_default", "fs_update_mixed_paths"))
 
 
 def test_null_context_and_no_device(pkg):
-    cap = pkg._capi
-    lib = cap.load()
-    src = (C.c_int32 * 1)(0)
-    rows = np.full(1, 7, dtype=pkg.Context.MIXED_ROW_DTYPE)
-    paths = np.full((1, 8), 7, dtype=pkg.Context.MIXED_DTYPE)
-    before = rows.tobytes(), paths.tobytes()
-    assert lib.fs_update_mixed_paths(None, src, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    lib.fs_mixed_params_default(None)   # tolerated, like the other *_default calls
-    import torch
-    if not torch.cuda.is_available():
-        h = C.c_void_p()
-        cfg = cap.default_config(num_bands=1)
-        assert lib.fs_context_create(C.byref(cfg), C.byref(h)) == cap.ERR_NO_DEVICE and h
-        try:
-            assert lib.fs_update_mixed_paths(h, src, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_NO_DEVICE
-            assert b"no CPU fallback" in lib.fs_last_error(h)
-            assert lib.fs_update_mixed_paths(h, None, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_mixed_paths(h, src, 1, None, None, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_mixed_paths(h, src, 1, None, rows.ctypes.data, None) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_mixed_paths(h, src, 0, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_mixed_paths(h, src, 257, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            for kw in (dict(max_detour=0.0), dict(max_length=0.0), dict(max_near=0), dict(max_paths=17)):
-                q = cap.default_mixed_params(**kw)
-                assert lib.fs_update_mixed_paths(h, src, 1, C.byref(q), rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-        finally:
-            lib.fs_context_destroy(h)
-    assert (rows.tobytes(), paths.tobytes()) == before
+    contract.null_context_and_no_device(pkg, QUERY)
 
 
 def test_model_figures():
@@ -528,10 +484,7 @@ def test_restatement_partition_to_full_width(pkg, oracle_mod):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------
-def check(pkg, ctx, y, handles, positions, listener, where, src_obj=None, lis_obj=NO_OBJECT, **params):
-    got = ctx.mixed_paths(handles, **params)
-    assert_equal(got, y.expect(pkg, positions, listener, src_obj, lis_obj, **params), where)
-    return got
+check = contract.checker("mixed")
 
 
 def identities(paths):
@@ -807,15 +760,7 @@ def test_both_tree_builders(pkg, oracle_mod, fast):
     h = place(ctx, bc["pos"])
     rows, paths = got = ctx.mixed_paths(h, max_length=1500.0)
     assert_equal(got, bc["want"], f"builders fast={fast}")
-    if not fast:
-        ones = [ctx.mixed_paths([x], max_length=1500.0) for x in h]
-        assert np.concatenate([r for r, _ in ones]).tobytes() == rows.tobytes(), "count = 9 differs from 9 calls with count = 1"
-        assert np.concatenate([p for _, p in ones]).tobytes() == paths.tobytes(), "count = 9 differs from 9 calls with count = 1"
-    perm = np.random.default_rng(7).permutation(9)
-    prows, ppaths = ctx.mixed_paths([h[i] for i in perm], max_length=1500.0)
-    assert prows.tobytes() == rows[perm].tobytes() and ppaths.tobytes() == paths[perm].tobytes(), "a permuted list"
-    frows, fpaths = ctx.mixed_paths(h[:5], max_length=1500.0)   # one confirm workgroup with idle waves beside a full one
-    assert frows.tobytes() == rows[:5].tobytes() and fpaths.tobytes() == paths[:5].tobytes()
+    contract.batch_agrees(ctx.mixed_paths, h, got, singles=not fast, max_length=1500.0)
     ctx.close()
 
 
@@ -831,12 +776,8 @@ def test_mover(pkg, oracle_mod):
     rows, _ = check(pkg, ctx, Mixed(oracle_mod, w), h, [SRC], LIS, "door shut", **REACH)
     assert rows[0]["found"] == 0
     aside = np.array([[1, 0, 0, 0], [0, 1, 0, 2000], [0, 0, 1, 0]], np.float32)
-    moved = w.tri.copy()
-    idx = w.obj == 5
-    p = moved[idx]
-    moved[idx] = np.stack([((aside[k, 0] * p[..., 0] + aside[k, 1] * p[..., 1]) + aside[k, 2] * p[..., 2]) + aside[k, 3] for k in range(3)], axis=-1)
     ctx.set_object_transforms([5], aside[None])
-    rows, _ = check(pkg, ctx, Mixed(oracle_mod, w, moved), h, [SRC], LIS, "door aside, no explicit refit", **REACH)   # the call refits first
+    rows, _ = check(pkg, ctx, Mixed(oracle_mod, w, contract.transformed(w, 5, aside)), h, [SRC], LIS, "door aside, no explicit refit", **REACH)   # the call refits first
     assert rows[0]["found"] == 4
     ctx.set_object_transforms([5], np.eye(3, 4, dtype=np.float32)[None])
     rows, _ = check(pkg, ctx, Mixed(oracle_mod, w), h, [SRC], LIS, "door back", **REACH)
@@ -844,94 +785,50 @@ def test_mover(pkg, oracle_mod):
     ctx.close()
 
 
-@pytest.mark.gpu
-def test_errors_and_untouched_state(pkg, oracle_mod):
-    cap = pkg._capi
-    lib = cap.load()
-    w = scene_world(1)
-    ctx = pkg.Context(num_bands=4)
-    src = ctx.create_source(SRC)
-    arr = (C.c_int32 * 2)(src, src)
-    rows = np.full(2, 7, dtype=pkg.Context.MIXED_ROW_DTYPE)
-    paths = np.full((2, 16), 7, dtype=pkg.Context.MIXED_DTYPE)
-    sentinel = rows.tobytes(), paths.tobytes()
+def _defaults_found(t, oracle_mod, want):
+    y = Mixed(oracle_mod, t.w)
+    assert_equal(want, y.expect(t.pkg, [SRC, SRC], LIS), "defaults, one handle twice")
+    assert_equal(t.ctx.mixed_paths([t.src, t.src], **REACH), y.expect(t.pkg, [SRC, SRC], LIS, **REACH), "one handle twice")
 
-    def call(sources=arr, count=2, params=None, r=rows, p=paths, **kw):
-        q = cap.default_mixed_params(**dict(REACH, **kw)) if (kw or params is None) else params
-        return lib.fs_update_mixed_paths(ctx.h, sources, count, C.byref(q), r.ctypes.data if r is not None else None,
-                                         p.ctypes.data if p is not None else None)
 
-    assert call() == cap.ERR_NOT_COMMITTED
-    ctx.set_scene(w.tri, w.mat, w.absorption, w.transmission, w.scattering, object_ids=w.obj)
-    ctx.set_listener(LIS)
-    assert call(sources=None) == cap.ERR_INVALID_ARGUMENT
-    assert call(r=None) == cap.ERR_INVALID_ARGUMENT
-    assert call(p=None) == cap.ERR_INVALID_ARGUMENT
-    assert lib.fs_update_mixed_paths(None, arr, 2, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    many = (C.c_int32 * 257)(*([src] * 257))
-    for bad in (0, -1, 257):
-        assert call(sources=many, count=bad) == cap.ERR_INVALID_ARGUMENT
-    q = cap.default_mixed_params()
-    q.struct_size = 44
-    assert call(params=q) == cap.ERR_INVALID_ARGUMENT
-    inf, nan = float("inf"), float("nan")
-    for kw in (dict(max_paths=0), dict(max_paths=17), dict(max_near=0), dict(max_near=32769), dict(max_candidates=0), dict(max_candidates=2049),
-               dict(max_length=0.0), dict(max_length=-1.0), dict(max_length=nan), dict(max_length=inf), dict(max_detour=0.0), dict(max_detour=-1.0),
-               dict(max_detour=nan), dict(max_detour=inf), dict(margin=-1e-3), dict(margin=nan), dict(margin=inf), dict(offset=-0.1), dict(offset=nan),
-               dict(offset=inf), dict(merge=-1.0), dict(merge=nan), dict(merge=inf), dict(step=-0.1), dict(step=nan), dict(step=inf),
-               dict(pullback=-1.0), dict(pullback=nan), dict(pullback=inf), dict(dist_divisor=0.0), dict(dist_divisor=-1.0), dict(dist_divisor=nan),
-               dict(dist_divisor=inf), dict(sound_speed=0.0), dict(sound_speed=-1.0), dict(sound_speed=nan), dict(sound_speed=inf)):
-        assert call(**kw) == cap.ERR_INVALID_ARGUMENT, kw
-    assert call(sources=(C.c_int32 * 2)(src, 12345)) == cap.ERR_BAD_HANDLE
-    assert call(sources=(C.c_int32 * 2)(-1, src)) == cap.ERR_BAD_HANDLE
-    assert (rows.tobytes(), paths.tobytes()) == sentinel, "a refused call wrote"
-    # NULL params = the defaults; extreme but legal values are taken
-    r8, p8 = np.full(2, 7, dtype=rows.dtype), np.full((2, 8), 7, dtype=paths.dtype)
-    assert lib.fs_update_mixed_paths(ctx.h, arr, 2, None, r8.ctypes.data, p8.ctypes.data) == cap.OK
-    want = ctx.mixed_paths([src, src])
-    assert r8.tobytes() == want[0].tobytes() and p8.tobytes() == want[1].tobytes()
-    y = Mixed(oracle_mod, w)
-    assert_equal(want, y.expect(pkg, [SRC, SRC], LIS), "defaults, one handle twice")
-    assert_equal(ctx.mixed_paths([src, src], **REACH), y.expect(pkg, [SRC, SRC], LIS, **REACH), "one handle twice")
-    assert call(max_paths=16, max_near=32768, max_candidates=2048, margin=0.0, offset=0.0, merge=0.0, step=0.0, pullback=0.0) == cap.OK
-    assert call(max_paths=16, max_candidates=1) == cap.OK
+def _legal_found(rows):
     assert tuple(rows[0])[2:] == (0, 0, 0, OVERFLOW) and rows[0]["candidates"] > 1
 
-    # a successful call leaves the sources alone: energy, IR publish number, occlusion scalar
-    fp = pkg.default_params(num_rays=512, depth=4, seed=3)
-    ctx.compute_energy_response(src, fp)
-    ctx.reconstruct_impulse_response(src, fp)
-    ctx.update_sound(src, cap.default_sound_params(raycasts_per_tick=64))
-    before = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    assert ctx.mixed_paths([src], **REACH)[0][0]["found"] == 4
-    after = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    assert before == after
-    ctx.close()
-    # an empty committed scene: rows of zeros
-    e = World([], ALPHA, TAU, 4, SCAT)
-    ctx = e.context(pkg)
-    ctx.set_listener(LIS)
-    rows, paths = check(pkg, ctx, Mixed(oracle_mod, e), place(ctx, [SRC, LIS]), [SRC, LIS], LIS, "empty", **REACH)
-    assert np.all(rows.view(np.uint8) == 0) and np.all(paths.view(np.uint8) == 0)
-    ctx.close()
+
+def _untouched_found(got):
+    assert got[0][0]["found"] == 4
+
+
+def _steady_found(ctx, h, first, fewer):
+    assert np.all(first[0]["found"] == 4)
+
+
+inf, nan = float("inf"), float("nan")
+QUERY = contract.Query(
+    kind="mixed", dtypes=("MIXED_ROW_DTYPE", "MIXED_DTYPE"), world=lambda: scene_world(1), src=SRC, lis=LIS, wrong_struct_size=44, reach=REACH,
+    refused_without_device=(dict(max_detour=0.0), dict(max_length=0.0), dict(max_near=0), dict(max_paths=17)),
+    refused=(dict(max_paths=0), dict(max_paths=17), dict(max_near=0), dict(max_near=32769), dict(max_candidates=0), dict(max_candidates=2049),
+             dict(max_length=0.0), dict(max_length=-1.0), dict(max_length=nan), dict(max_length=inf), dict(max_detour=0.0), dict(max_detour=-1.0),
+             dict(max_detour=nan), dict(max_detour=inf), dict(margin=-1e-3), dict(margin=nan), dict(margin=inf), dict(offset=-0.1), dict(offset=nan),
+             dict(offset=inf), dict(merge=-1.0), dict(merge=nan), dict(merge=inf), dict(step=-0.1), dict(step=nan), dict(step=inf),
+             dict(pullback=-1.0), dict(pullback=nan), dict(pullback=inf), dict(dist_divisor=0.0), dict(dist_divisor=-1.0), dict(dist_divisor=nan),
+             dict(dist_divisor=inf), dict(sound_speed=0.0), dict(sound_speed=-1.0), dict(sound_speed=nan), dict(sound_speed=inf)),
+    defaults_found=_defaults_found,
+    legal=(dict(max_paths=16, max_near=32768, max_candidates=2048, margin=0.0, offset=0.0, merge=0.0, step=0.0, pullback=0.0),
+           dict(max_paths=16, max_candidates=1)),
+    legal_found=_legal_found, untouched=REACH, untouched_found=_untouched_found, yardstick=Mixed,
+    empty_world=lambda: World([], ALPHA, TAU, 4, SCAT),
+    steady=REACH, fewer=dict(max_paths=16, max_near=32768, max_candidates=2048), steady_found=_steady_found)
+
+
+@pytest.mark.gpu
+def test_errors_and_untouched_state(pkg, oracle_mod):
+    contract.errors_and_untouched_state(pkg, oracle_mod, QUERY)
 
 
 @pytest.mark.gpu
 def test_steady_state_allocates_nothing(pkg):
-    w = scene_world(1)
-    ctx = w.context(pkg)
-    ctx.set_listener(LIS)
-    h = place(ctx, [SRC] * 40)
-    first = ctx.mixed_paths(h, **REACH)
-    free0 = device_free_bytes()
-    for _ in range(20):
-        again = ctx.mixed_paths(h, **REACH)
-    fewer = ctx.mixed_paths(h[:7], max_paths=16, max_near=32768, max_candidates=2048, **REACH)   # a smaller count, larger caps: fits what is there
-    assert device_free_bytes() >= free0
-    assert again[0].tobytes() == first[0].tobytes() and again[1].tobytes() == first[1].tobytes()
-    assert np.all(first[0]["found"] == 4)
-    assert fewer[0].tobytes() == first[0][:7].tobytes() and fewer[1][:, :8].tobytes() == first[1][:7].tobytes()
-    ctx.close()
+    contract.steady_state_allocates_nothing(pkg, QUERY)
 
 
 @pytest.mark.gpu
@@ -949,32 +846,10 @@ def test_queries_interleaved_on_one_context(pkg):
         ctx.set_listener(LIS)
         return ctx, place(ctx, pos)
 
-    def run(ctx, h, query, count):
-        if query == "direct":
-            return (ctx.direct_paths(h[:count], samples=16, source_radius=30.0),)
-        if query == "reflection2":
-            return ctx.reflection2_paths(h[:count], max_length=1e6)
-        if query == "diffraction2":
-            return ctx.diffraction2_paths(h[:count], max_detour=1000.0)
-        if query == "mixed":
-            return ctx.mixed_paths(h[:count], **REACH)
-        return getattr(ctx, query + "_paths")(h[:count])
-
     kinds = ("mixed", "diffraction2", "reflection2", "diffraction", "reflection", "direct")
     calls = [(k, 5) for k in kinds] + [(k, 33) for k in reversed(kinds)] + [(k, 5) for k in kinds]
-    ctx, h = fresh()
-    got = [run(ctx, h, query, count) for query, count in calls]
-    ctx.close()
-    first = {}
-    for i, ((query, count), g) in enumerate(zip(calls, got)):
-        if (query, count) not in first:
-            one, h1 = fresh()
-            first[query, count] = run(one, h1, query, count)
-            one.close()
-        want = first[query, count]
-        assert len(g) == len(want) and all(len(a) == count for a in g)
-        for a, b in zip(g, want):
-            assert a.tobytes() == b.tobytes(), f"call {i} ({query}, count {count}) differs from the same call on a fresh context"
+    got = contract.queries_interleaved_on_one_context(fresh, calls, dict(reflection2=dict(max_length=1e6), diffraction2=dict(max_detour=1000.0),
+                                                                         mixed=REACH))
     # the comparison is not of zeros
     by = {c: g for c, g in zip(calls, got)}
     assert by["mixed", 5][0][0]["found"] == 4 and np.any(by["mixed", 33][0]["returned"] > 0)

@@ -14,8 +14,10 @@ import os
 import numpy as np
 import pytest
 
+pytest.register_assert_rewrite("path_query_contract")
+import path_query_contract as contract  # noqa: E402
 from test_diffraction_paths import band_centres
-from test_reflection_paths import (ALPHA, FREE, NO_OBJECT, OPAQUE, SCAT, TAU, WALLS, F, Restatement, World, bits, box, device_free_bytes, dot,
+from test_reflection_paths import (ALPHA, FREE, NO_OBJECT, OPAQUE, SCAT, TAU, WALLS, F, Restatement, World, bits, box, dot,
                                    place, quad_grid)
 
 DEFAULTS = dict(validate=1, max_attach=1000.0, max_length=10000.0, step=0.1, pullback=0.1, dist_divisor=1000.0, sound_speed=343.0)
@@ -278,33 +280,21 @@ NAMES = ("fs_pathing_set_probes", "fs_pathing_bake_params_default", "fs_pathing_
 
 
 def test_exported_in_one_tier(pkg):
-    cap = pkg._capi
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "frequensee.h")).read()
-    opening = header[:header.index("#ifndef FREQUENSEE_H")]
-    core = opening[opening.index("CORE:"):opening.index("EXTENDED =")]
-    extended = opening[opening.index("EXTENDED:"):]
-    for name in NAMES:
-        assert name in cap.EXPORTS and hasattr(cap.load(), name)
-        assert name in extended.split() and name not in core.split()
-        assert opening.split().count(name) == 1
+    contract.exported_in_one_tier(pkg, NAMES)
 
 
 def test_null_context_and_no_device(pkg):
     cap = pkg._capi
     lib = cap.load()
-    src = (C.c_int32 * 1)(0)
     xyz = np.zeros((2, 3), np.float32)
-    out = np.full(1, 7, dtype=pkg.Context.PATHING_DTYPE)
     words = np.full(2, 7, np.uint32)
-    before = out.tobytes(), words.tobytes()
+    before = words.tobytes()
     i32 = [C.c_int32(7) for _ in range(4)]
     assert lib.fs_pathing_set_probes(None, xyz.ctypes.data, 2) == cap.ERR_INVALID_ARGUMENT
     assert lib.fs_pathing_bake(None, None) == cap.ERR_INVALID_ARGUMENT
     assert lib.fs_pathing_info(None, *[C.byref(x) for x in i32]) == cap.ERR_INVALID_ARGUMENT
     assert lib.fs_pathing_copy_graph(None, words.ctypes.data, 2) == cap.ERR_INVALID_ARGUMENT
-    assert lib.fs_update_pathing_paths(None, src, 1, None, out.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    lib.fs_pathing_params_default(None)        # tolerated, like the other *_default calls
-    lib.fs_pathing_bake_params_default(None)
+    lib.fs_pathing_bake_params_default(None)   # tolerated, like the other *_default calls
     import torch
     if not torch.cuda.is_available():
         h = C.c_void_p()
@@ -316,17 +306,14 @@ def test_null_context_and_no_device(pkg):
             assert lib.fs_pathing_set_probes(h, xyz.ctypes.data, 1025) == cap.ERR_INVALID_ARGUMENT
             assert lib.fs_pathing_set_probes(h, xyz.ctypes.data, -1) == cap.ERR_INVALID_ARGUMENT
             assert lib.fs_pathing_bake(h, None) == cap.ERR_NO_DEVICE
-            assert lib.fs_update_pathing_paths(h, src, 1, None, out.ctypes.data) == cap.ERR_NO_DEVICE
-            assert lib.fs_update_pathing_paths(h, None, 1, None, out.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_pathing_paths(h, src, 1, None, None) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_pathing_paths(h, src, 0, None, out.ctypes.data) == cap.ERR_INVALID_ARGUMENT
             assert lib.fs_pathing_copy_graph(h, words.ctypes.data, 2) == cap.ERR_INVALID_ARGUMENT   # nothing baked
             assert lib.fs_pathing_copy_graph(h, None, 2) == cap.ERR_INVALID_ARGUMENT
             assert lib.fs_pathing_info(h, *[C.byref(x) for x in i32]) == cap.OK and [x.value for x in i32] == [0, 0, 0, 0]
             assert lib.fs_pathing_info(h, None, None, None, None) == cap.OK
         finally:
             lib.fs_context_destroy(h)
-    assert (out.tobytes(), words.tobytes()) == before
+    assert words.tobytes() == before
+    contract.null_context_and_no_device(pkg, QUERY)   # fs_pathing_params_default and fs_update_pathing_paths
 
 
 def dijkstra64(y, dL):
@@ -631,23 +618,29 @@ def test_door(pkg, oracle_mod):
     ctx.close()
 
 
+inf, nan = float("inf"), float("nan")
+QUERY = contract.Query(
+    kind="pathing", dtypes=("PATHING_DTYPE",), world=three_rooms, src=SRC, lis=LIS, wrong_struct_size=28,
+    refused=(dict(validate=2), dict(validate=-1), dict(max_attach=0.0), dict(max_attach=-1.0), dict(max_attach=nan), dict(max_attach=inf),
+             dict(max_length=0.0), dict(max_length=-1.0), dict(max_length=nan), dict(max_length=inf), dict(max_length=1048577.0), dict(step=-0.1),
+             dict(step=nan), dict(step=inf), dict(pullback=-1.0), dict(pullback=nan), dict(pullback=inf), dict(dist_divisor=0.0),
+             dict(dist_divisor=-1.0), dict(dist_divisor=nan), dict(dist_divisor=inf), dict(sound_speed=0.0), dict(sound_speed=-1.0),
+             dict(sound_speed=nan), dict(sound_speed=inf)),
+    fewer=dict(validate=0))
+
+
 @pytest.mark.gpu
 def test_errors_and_untouched_state(pkg, oracle_mod):
     cap = pkg._capi
     lib = cap.load()
-    w, y = rooms_case(oracle_mod)
+    _, y = rooms_case(oracle_mod)
     pts = room_probes()
-    ctx = pkg.Context(num_bands=4)
+    call = contract.Calls(pkg, QUERY)
+    ctx, src, out = call.ctx, call.src, call.bufs[0]
     twin = pkg.Context(num_bands=4)   # never sees a refused call
-    src, tsrc = ctx.create_source(SRC), twin.create_source(SRC)
-    arr = (C.c_int32 * 2)(src, src)
-    out = np.full(2, 7, dtype=pkg.Context.PATHING_DTYPE)
+    tsrc = twin.create_source(SRC)
     words = np.full(30, 7, np.uint32)
-    sentinel = out.tobytes(), words.tobytes()
-
-    def call(sources=arr, count=2, params=None, o=out, **kw):
-        q = cap.default_pathing_params(**kw) if params is None else params
-        return lib.fs_update_pathing_paths(ctx.h, sources, count, C.byref(q), o.ctypes.data if o is not None else None)
+    sentinel = words.tobytes()
 
     def bake(**kw):
         return lib.fs_pathing_bake(ctx.h, C.byref(cap.default_pathing_bake_params(**dict(ROOMS_BAKE, **kw))))
@@ -658,7 +651,6 @@ def test_errors_and_untouched_state(pkg, oracle_mod):
             assert np.array_equal(ctx.pathing_graph(), twin.pathing_graph()), where
             assert ctx.pathing_paths([src, src]).tobytes() == twin.pathing_paths([tsrc, tsrc]).tobytes(), where
 
-    inf, nan = float("inf"), float("nan")
     bad_pts = pts.copy()
     bad_pts[17, 1] = nan
     assert bake() == cap.ERR_INVALID_ARGUMENT                                       # no probes
@@ -670,8 +662,7 @@ def test_errors_and_untouched_state(pkg, oracle_mod):
         c.pathing_set_probes(pts)
     assert bake() == cap.ERR_NOT_COMMITTED and call() == cap.ERR_INVALID_ARGUMENT   # (nothing baked)
     for c in (ctx, twin):
-        c.set_scene(w.tri, w.mat, w.absorption, w.transmission, w.scattering, object_ids=w.obj)
-        c.set_listener(LIS)
+        call.commit(c)
     assert call() == cap.ERR_INVALID_ARGUMENT and lib.fs_pathing_copy_graph(ctx.h, words.ctypes.data, 30) == cap.ERR_INVALID_ARGUMENT
     for kw in (dict(max_edge=0.0), dict(max_edge=-1.0), dict(max_edge=nan), dict(max_edge=inf), dict(step=-0.1), dict(step=nan), dict(step=inf)):
         assert bake(**kw) == cap.ERR_INVALID_ARGUMENT, kw
@@ -680,29 +671,15 @@ def test_errors_and_untouched_state(pkg, oracle_mod):
     assert lib.fs_pathing_bake(ctx.h, C.byref(q)) == cap.ERR_INVALID_ARGUMENT
     same_as_twin("refused bakes")
     assert bake() == cap.OK and twin.pathing_bake(**ROOMS_BAKE) == y.edges()
-    assert call(sources=None) == cap.ERR_INVALID_ARGUMENT and call(o=None) == cap.ERR_INVALID_ARGUMENT
-    many = (C.c_int32 * 257)(*([src] * 257))
-    for bad in (0, -1, 257):
-        assert call(sources=many, count=bad) == cap.ERR_INVALID_ARGUMENT
-    q = cap.default_pathing_params()
-    q.struct_size = 28
-    assert call(params=q) == cap.ERR_INVALID_ARGUMENT
-    for kw in (dict(validate=2), dict(validate=-1), dict(max_attach=0.0), dict(max_attach=-1.0), dict(max_attach=nan), dict(max_attach=inf),
-               dict(max_length=0.0), dict(max_length=-1.0), dict(max_length=nan), dict(max_length=inf), dict(max_length=1048577.0), dict(step=-0.1),
-               dict(step=nan), dict(step=inf), dict(pullback=-1.0), dict(pullback=nan), dict(pullback=inf), dict(dist_divisor=0.0),
-               dict(dist_divisor=-1.0), dict(dist_divisor=nan), dict(dist_divisor=inf), dict(sound_speed=0.0), dict(sound_speed=-1.0),
-               dict(sound_speed=nan), dict(sound_speed=inf)):
-        assert call(**kw) == cap.ERR_INVALID_ARGUMENT, kw
-    assert call(sources=(C.c_int32 * 2)(src, 12345)) == cap.ERR_BAD_HANDLE
-    assert call(sources=(C.c_int32 * 2)(-1, src)) == cap.ERR_BAD_HANDLE
+    call.refusals()
     for n in (29, 31, 0, -1):
         assert lib.fs_pathing_copy_graph(ctx.h, words.ctypes.data, n) == cap.ERR_INVALID_ARGUMENT
     assert lib.fs_pathing_copy_graph(ctx.h, None, 30) == cap.ERR_INVALID_ARGUMENT
-    assert (out.tobytes(), words.tobytes()) == sentinel, "a refused call wrote"
+    assert words.tobytes() == sentinel, "a refused call wrote"
+    call.unwritten()
     same_as_twin("refused updates")
     # NULL params = the defaults; one handle twice; extreme but legal values are taken
-    assert lib.fs_update_pathing_paths(ctx.h, arr, 2, None, out.ctypes.data) == cap.OK
-    assert_rows(out, y.expect(pkg, [SRC, SRC]), "defaults, one handle twice")
+    assert_rows(call.null_params_are_the_defaults()[0], y.expect(pkg, [SRC, SRC]), "defaults, one handle twice")
     assert call(max_length=1048576.0, step=0.0, pullback=0.0, validate=0) == cap.OK and out[0]["flags"] == FOUND
     assert lib.fs_pathing_bake(ctx.h, None) == cap.OK and ctx.pathing_info()["edges"] > y.edges()
     # new probes drop the bake; clearing them too
@@ -716,15 +693,11 @@ def test_errors_and_untouched_state(pkg, oracle_mod):
     same_as_twin("set again")
 
     # a successful call leaves the sources alone: energy, IR publish number, occlusion scalar
-    fp = pkg.default_params(num_rays=512, depth=4, seed=3)
-    ctx.compute_energy_response(src, fp)
-    ctx.reconstruct_impulse_response(src, fp)
-    ctx.update_sound(src, cap.default_sound_params(raycasts_per_tick=64))
-    before = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    ctx.pathing_bake(**ROOMS_BAKE)
-    assert ctx.pathing_paths([src])[0]["flags"] == FOUND
-    after = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    assert before == after
+    def query():
+        ctx.pathing_bake(**ROOMS_BAKE)
+        assert ctx.pathing_paths([src])[0]["flags"] == FOUND
+
+    contract.leaves_sources_alone(pkg, ctx, src, query)
     ctx.close()
     twin.close()
     # an empty committed scene: every pair within max_edge is an edge, every line is free
@@ -741,21 +714,20 @@ def test_steady_state_allocates_nothing(pkg, oracle_mod):
     w, _ = rooms_case(oracle_mod)
     ctx, _ = open_rooms(pkg, w, room_probes(), **ROOMS_BAKE)
     h = place(ctx, rooms_sources()[:40])
-    first = ctx.pathing_paths(h)
     graph = graph_of(ctx)
-    free0 = device_free_bytes()
-    for _ in range(20):
-        again = ctx.pathing_paths(h)
-    fewer = ctx.pathing_paths(h[:7], validate=0)
-    ctx.pathing_bake(**ROOMS_BAKE)
-    ctx.pathing_set_probes(room_probes()[::-1])
-    ctx.pathing_bake(**ROOMS_BAKE)
-    ctx.pathing_set_probes(room_probes())
-    ctx.pathing_bake(**ROOMS_BAKE)
-    assert device_free_bytes() >= free0
-    assert again.tobytes() == first.tobytes() and np.array_equal(graph_of(ctx), graph) and ctx.pathing_paths(h).tobytes() == first.tobytes()
-    assert np.any(first["flags"] & FOUND) and not np.any(first["flags"] & STALE) and fewer.tobytes() == first[:7].tobytes()
-    ctx.close()
+
+    def churn(ctx):
+        ctx.pathing_bake(**ROOMS_BAKE)
+        ctx.pathing_set_probes(room_probes()[::-1])
+        ctx.pathing_bake(**ROOMS_BAKE)
+        ctx.pathing_set_probes(room_probes())
+        ctx.pathing_bake(**ROOMS_BAKE)
+
+    def found(ctx, h, first, fewer):
+        assert np.array_equal(graph_of(ctx), graph) and ctx.pathing_paths(h).tobytes() == first[0].tobytes()
+        assert np.any(first[0]["flags"] & FOUND) and not np.any(first[0]["flags"] & STALE)
+
+    contract.steady_state_allocates_nothing(pkg, QUERY, opened=(ctx, h), churn=churn, found=found)
 
 
 @pytest.mark.gpu
@@ -769,30 +741,9 @@ def test_queries_interleaved_on_one_context(pkg, oracle_mod):
         ctx, _ = open_rooms(pkg, w, room_probes(), **ROOMS_BAKE)
         return ctx, place(ctx, pos)
 
-    def run(ctx, h, query, count):
-        if query == "pathing":
-            return (ctx.pathing_paths(h[:count]),)
-        if query == "direct":
-            return (ctx.direct_paths(h[:count], samples=16, source_radius=30.0),)
-        if query == "mixed":
-            return ctx.mixed_paths(h[:count], max_length=1000.0)
-        if query == "diffraction2":
-            return ctx.diffraction2_paths(h[:count], max_detour=1000.0)
-        return getattr(ctx, query + "_paths")(h[:count])
-
     kinds = ("pathing", "mixed", "diffraction2", "reflection2", "pathing", "reflection", "diffraction", "direct", "pathing")
     calls = [(k, 5) for k in kinds] + [(k, 33) for k in reversed(kinds)] + [(k, 5) for k in kinds]
-    ctx, h = fresh()
-    got = [run(ctx, h, query, count) for query, count in calls]
-    ctx.close()
-    first = {}
-    for i, ((query, count), g) in enumerate(zip(calls, got)):
-        if (query, count) not in first:
-            one, h1 = fresh()
-            first[query, count] = run(one, h1, query, count)
-            one.close()
-        for a, b in zip(g, first[query, count]):
-            assert a.tobytes() == b.tobytes(), f"call {i} ({query}, count {count}) differs from the same call on a fresh context"
+    got = contract.queries_interleaved_on_one_context(fresh, calls, dict(mixed=dict(max_length=1000.0), diffraction2=dict(max_detour=1000.0)))
     # the comparison is not of zeros
     by = {c: g for c, g in zip(calls, got)}
     assert np.any(got[0][0]["flags"] & FOUND)

@@ -8,13 +8,15 @@ without a GPU against the float64 image-source lattice of a shoebox whose reflec
 triangle edge.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+pytest.register_assert_rewrite("path_query_contract")
+import path_query_contract as contract  # noqa: E402
+from path_query_contract import assert_equal  # noqa: E402
 from test_reflection_paths import (ALPHA, BLOCKED, FREE, HI, LIS, LO, NO_MATERIAL, NO_OBJECT, OPAQUE, SCAT, SLAB, SRC, TARGET, TAU, WALLS, F,
-                                   Restatement, World, bits, box, cross, device_free_bytes, dot, fmaf, margin64, place, shoebox_world)
+                                   Restatement, World, bits, box, cross, dot, fmaf, margin64, place, shoebox_world)
 
 DEFAULTS = dict(max_paths=16, max_near=16384, max_candidates=256, max_length=1500.0, margin=1e-3, step=0.1, offset=0.1, pullback=0.1,
                 dist_divisor=1000.0, sound_speed=343.0)
@@ -168,23 +170,7 @@ class Reflection2(Restatement):
         return rows, paths
 
 
-def assert_equal(got, want, where=""):
-    (grows, gpaths), (wrows, wpaths) = got, want
-    assert grows.shape == wrows.shape and gpaths.shape == wpaths.shape, where
-    for i in range(len(wrows)):
-        for k in wrows.dtype.names:
-            assert grows[i][k] == wrows[i][k], f"{where} row {i}: {k}: got {grows[i][k]!r}, restatement {wrows[i][k]!r}"
-        for j in range(wpaths.shape[1]):
-            for k in wpaths.dtype.names:
-                g, x = np.atleast_1d(gpaths[i, j][k]), np.atleast_1d(wpaths[i, j][k])
-                assert g.tobytes() == x.tobytes(), f"{where} row {i} path {j}: {k}: got {g!r}, restatement {x!r}"
-    assert grows.tobytes() == wrows.tobytes() and gpaths.tobytes() == wpaths.tobytes(), where
-
-
-def check(pkg, ctx, y, handles, positions, listener, where, src_obj=None, lis_obj=NO_OBJECT, **params):
-    got = ctx.reflection2_paths(handles, **params)
-    assert_equal(got, y.expect(pkg, positions, listener, src_obj, lis_obj, **params), where)
-    return got
+check = contract.checker("reflection2")
 
 
 # ---- the float64 image-source lattice of the shoebox --------------------------------------------------------------------------
@@ -253,45 +239,12 @@ def test_struct_sizes_and_defaults(pkg):
 
 
 def test_exported_in_one_tier(pkg):
-    cap = pkg._capi
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "frequensee.h")).read()
-    opening = header[:header.index("#ifndef FREQUENSEE_H")]
-    core = opening[opening.index("CORE:"):opening.index("EXTENDED =")]
-    extended = opening[opening.index("EXTENDED:"):]
-    for name in ("fs_reflection2_params_default", "fs_update_reflection2_paths"):
-        assert name in cap.EXPORTS and hasattr(cap.load(), name)
-        assert name in extended.split() and name not in core.split()
-        assert opening.split().count(name) == 1
+    extended = contract.exported_in_one_tier(pkg, ("fs_reflection2_params_default", "fs_update_reflection2_paths"))
     assert "fs_update_reflection_paths" in extended.split()   # the tier of the first-order call
 
 
 def test_null_context_and_no_device(pkg):
-    cap = pkg._capi
-    lib = cap.load()
-    src = (C.c_int32 * 1)(0)
-    rows = np.full(1, 7, dtype=pkg.Context.REFLECTION2_ROW_DTYPE)
-    paths = np.full((1, 16), 7, dtype=pkg.Context.REFLECTION2_DTYPE)
-    before = rows.tobytes(), paths.tobytes()
-    assert lib.fs_update_reflection2_paths(None, src, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    lib.fs_reflection2_params_default(None)   # tolerated, like the other *_default calls
-    import torch
-    if not torch.cuda.is_available():
-        h = C.c_void_p()
-        cfg = cap.default_config(num_bands=1)
-        assert lib.fs_context_create(C.byref(cfg), C.byref(h)) == cap.ERR_NO_DEVICE and h
-        try:
-            assert lib.fs_update_reflection2_paths(h, src, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_NO_DEVICE
-            assert b"no CPU fallback" in lib.fs_last_error(h)
-            assert lib.fs_update_reflection2_paths(h, None, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_reflection2_paths(h, src, 1, None, None, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_reflection2_paths(h, src, 1, None, rows.ctypes.data, None) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_reflection2_paths(h, src, 0, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_reflection2_paths(h, src, 257, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            q = cap.default_reflection2_params(max_length=0.0)
-            assert lib.fs_update_reflection2_paths(h, src, 1, C.byref(q), rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-        finally:
-            lib.fs_context_destroy(h)
-    assert (rows.tobytes(), paths.tobytes()) == before
+    contract.null_context_and_no_device(pkg, QUERY)
 
 
 @pytest.mark.parametrize("n", [1, 4], ids=["12_triangles", "192_triangles"])
@@ -619,15 +572,7 @@ def test_rooms(pkg, oracle_mod, fast):
     h = place(ctx, rc["pos"])
     rows, paths = got = ctx.reflection2_paths(h, max_length=FAR)
     assert_equal(got, rc["want"], f"rooms fast={fast}")
-    if not fast:
-        ones = [ctx.reflection2_paths([x], max_length=FAR) for x in h]
-        assert np.concatenate([r for r, _ in ones]).tobytes() == rows.tobytes(), "count = 8 differs from 8 calls with count = 1"
-        assert np.concatenate([p for _, p in ones]).tobytes() == paths.tobytes(), "count = 8 differs from 8 calls with count = 1"
-    perm = np.random.default_rng(7).permutation(8)
-    prows, ppaths = ctx.reflection2_paths([h[i] for i in perm], max_length=FAR)
-    assert prows.tobytes() == rows[perm].tobytes() and ppaths.tobytes() == paths[perm].tobytes(), "a permuted list"
-    frows, fpaths = ctx.reflection2_paths(h[:5], max_length=FAR)   # one confirm workgroup with idle waves beside a full one
-    assert frows.tobytes() == rows[:5].tobytes() and fpaths.tobytes() == paths[:5].tobytes()
+    contract.batch_agrees(ctx.reflection2_paths, h, got, singles=not fast, max_length=FAR)
     ctx.close()
 
 
@@ -643,12 +588,8 @@ def test_mover(pkg, oracle_mod):
     shut = paths[0][:rows[0]["returned"]].copy()
     assert np.any(shut["triangle"] >= 12), "the door does not reflect"
     aside = np.array([[1, 0, 0, 0], [0, 1, 0, -290], [0, 0, 1, 0]], np.float32)
-    moved = w.tri.copy()
-    idx = w.obj == 5
-    p = moved[idx]
-    moved[idx] = np.stack([((aside[k, 0] * p[..., 0] + aside[k, 1] * p[..., 1]) + aside[k, 2] * p[..., 2]) + aside[k, 3] for k in range(3)], axis=-1)
     ctx.set_object_transforms([5], aside[None])
-    rows, paths = check(pkg, ctx, Reflection2(oracle_mod, w, moved), h, [SRC2], LIS2, "door aside, no explicit refit", max_paths=32, max_length=FAR)
+    rows, paths = check(pkg, ctx, Reflection2(oracle_mod, w, contract.transformed(w, 5, aside)), h, [SRC2], LIS2, "door aside, no explicit refit", max_paths=32, max_length=FAR)
     assert paths[0][:rows[0]["returned"]].tobytes() != shut.tobytes(), "the door moved and nothing changed"
     ctx.set_object_transforms([5], np.eye(3, 4, dtype=np.float32)[None])
     rows, paths = check(pkg, ctx, Reflection2(oracle_mod, w), h, [SRC2], LIS2, "door back", max_paths=32, max_length=FAR)
@@ -656,93 +597,45 @@ def test_mover(pkg, oracle_mod):
     ctx.close()
 
 
-@pytest.mark.gpu
-def test_errors_and_untouched_state(pkg, oracle_mod):
-    cap = pkg._capi
-    lib = cap.load()
-    w = shoebox_world()
-    ctx = pkg.Context(num_bands=4)
-    src = ctx.create_source(SRC2)
-    arr = (C.c_int32 * 2)(src, src)
-    rows = np.full(2, 7, dtype=pkg.Context.REFLECTION2_ROW_DTYPE)
-    paths = np.full((2, 32), 7, dtype=pkg.Context.REFLECTION2_DTYPE)
-    sentinel = rows.tobytes(), paths.tobytes()
+def _defaults_found(t, oracle_mod, want):
+    """the defaults' max_length leaves some of the 18 paths out"""
+    assert_equal(want, Reflection2(oracle_mod, t.w).expect(t.pkg, [SRC2, SRC2], LIS2), "defaults, one handle twice")
+    assert 0 < want[0][0]["found"] < 18 and want[0][0]["flags"] == 0
 
-    def call(sources=arr, count=2, params=None, r=rows, p=paths, **kw):
-        q = cap.default_reflection2_params(**kw) if (kw or params is None) else params
-        return lib.fs_update_reflection2_paths(ctx.h, sources, count, C.byref(q), r.ctypes.data if r is not None else None,
-                                               p.ctypes.data if p is not None else None)
 
-    assert call() == cap.ERR_NOT_COMMITTED
-    ctx.set_scene(w.tri, w.mat, w.absorption, w.transmission, w.scattering, object_ids=w.obj)
-    ctx.set_listener(LIS2)
-    assert call(sources=None) == cap.ERR_INVALID_ARGUMENT
-    assert call(r=None) == cap.ERR_INVALID_ARGUMENT
-    assert call(p=None) == cap.ERR_INVALID_ARGUMENT
-    assert lib.fs_update_reflection2_paths(None, arr, 2, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    many = (C.c_int32 * 257)(*([src] * 257))
-    for bad in (0, -1, 257):
-        assert call(sources=many, count=bad) == cap.ERR_INVALID_ARGUMENT
-    q = cap.default_reflection2_params()
-    q.struct_size = 36
-    assert call(params=q) == cap.ERR_INVALID_ARGUMENT
-    inf, nan = float("inf"), float("nan")
-    for kw in (dict(max_paths=0), dict(max_paths=33), dict(max_near=0), dict(max_near=32769), dict(max_candidates=0), dict(max_candidates=1025),
-               dict(max_length=0.0), dict(max_length=-1.0), dict(max_length=nan), dict(max_length=inf), dict(margin=-1e-3), dict(margin=nan),
-               dict(margin=inf), dict(step=-0.1), dict(step=nan), dict(step=inf), dict(offset=-0.1), dict(offset=nan), dict(offset=inf),
-               dict(pullback=-1.0), dict(pullback=nan), dict(pullback=inf), dict(dist_divisor=0.0), dict(dist_divisor=-1.0),
-               dict(dist_divisor=nan), dict(dist_divisor=inf), dict(sound_speed=0.0), dict(sound_speed=-1.0), dict(sound_speed=nan),
-               dict(sound_speed=inf)):
-        assert call(**kw) == cap.ERR_INVALID_ARGUMENT, kw
-    assert call(sources=(C.c_int32 * 2)(src, 12345)) == cap.ERR_BAD_HANDLE
-    assert call(sources=(C.c_int32 * 2)(-1, src)) == cap.ERR_BAD_HANDLE
-    assert (rows.tobytes(), paths.tobytes()) == sentinel, "a refused call wrote"
-    # NULL params = the defaults (whose max_length leaves some of the 18 paths out); extreme but legal values are taken
-    r16, p16 = np.full(2, 7, dtype=rows.dtype), np.full((2, 16), 7, dtype=paths.dtype)
-    assert lib.fs_update_reflection2_paths(ctx.h, arr, 2, None, r16.ctypes.data, p16.ctypes.data) == cap.OK
-    want = ctx.reflection2_paths([src, src])
-    assert r16.tobytes() == want[0].tobytes() and p16.tobytes() == want[1].tobytes()
-    assert_equal(want, Reflection2(oracle_mod, w).expect(pkg, [SRC2, SRC2], LIS2), "defaults, one handle twice")
-    assert 0 < r16[0]["found"] < 18 and r16[0]["flags"] == 0
-    assert call(max_paths=32, max_near=32768, max_candidates=1, max_length=1e30, margin=0.0, step=0.0, offset=0.0, pullback=0.0) == cap.OK
+def _legal_found(rows):
     assert tuple(rows[0]) == (12, 18, 0, 0, 1)
 
-    # a successful call leaves the sources alone: energy, IR publish number, occlusion scalar
-    fp = pkg.default_params(num_rays=512, depth=4, seed=3)
-    ctx.compute_energy_response(src, fp)
-    ctx.reconstruct_impulse_response(src, fp)
-    ctx.update_sound(src, cap.default_sound_params(raycasts_per_tick=64))
-    before = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    ctx.reflection2_paths([src])
-    after = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    assert before == after
-    ctx.close()
-    # an empty committed scene: rows of zeros
-    e = World([], ALPHA, TAU, 4, SCAT)
-    ctx = e.context(pkg)
-    ctx.set_listener(LIS2)
-    rows, paths = check(pkg, ctx, Reflection2(oracle_mod, e), place(ctx, [SRC2, LIS2]), [SRC2, LIS2], LIS2, "empty")
-    assert np.all(rows.view(np.uint8) == 0) and np.all(paths.view(np.uint8) == 0)
-    ctx.close()
+
+def _steady_found(ctx, h, first, fewer):
+    assert np.all(first[0]["found"] == 18) and np.all(first[0]["returned"] == 16) and np.all(fewer[0]["returned"] == 18)
+
+
+inf, nan = float("inf"), float("nan")
+QUERY = contract.Query(
+    kind="reflection2", dtypes=("REFLECTION2_ROW_DTYPE", "REFLECTION2_DTYPE"), world=shoebox_world, src=SRC2, lis=LIS2, wrong_struct_size=36,
+    sentinel_paths=32, null_paths=16, refused_without_device=(dict(max_length=0.0),),
+    refused=(dict(max_paths=0), dict(max_paths=33), dict(max_near=0), dict(max_near=32769), dict(max_candidates=0), dict(max_candidates=1025),
+             dict(max_length=0.0), dict(max_length=-1.0), dict(max_length=nan), dict(max_length=inf), dict(margin=-1e-3), dict(margin=nan),
+             dict(margin=inf), dict(step=-0.1), dict(step=nan), dict(step=inf), dict(offset=-0.1), dict(offset=nan), dict(offset=inf),
+             dict(pullback=-1.0), dict(pullback=nan), dict(pullback=inf), dict(dist_divisor=0.0), dict(dist_divisor=-1.0),
+             dict(dist_divisor=nan), dict(dist_divisor=inf), dict(sound_speed=0.0), dict(sound_speed=-1.0), dict(sound_speed=nan),
+             dict(sound_speed=inf)),
+    defaults_found=_defaults_found,
+    legal=(dict(max_paths=32, max_near=32768, max_candidates=1, max_length=1e30, margin=0.0, step=0.0, offset=0.0, pullback=0.0),),
+    legal_found=_legal_found, yardstick=Reflection2, empty_world=lambda: World([], ALPHA, TAU, 4, SCAT),
+    steady=dict(max_length=FAR), fewer=dict(max_paths=32, max_near=32768, max_candidates=1024), fewer_differs_in=("returned",),
+    steady_found=_steady_found)
+
+
+@pytest.mark.gpu
+def test_errors_and_untouched_state(pkg, oracle_mod):
+    contract.errors_and_untouched_state(pkg, oracle_mod, QUERY)
 
 
 @pytest.mark.gpu
 def test_steady_state_allocates_nothing(pkg):
-    w = shoebox_world()
-    ctx = w.context(pkg)
-    ctx.set_listener(LIS2)
-    h = place(ctx, [SRC2] * 40)
-    first = ctx.reflection2_paths(h, max_length=FAR)
-    free0 = device_free_bytes()
-    for _ in range(20):
-        again = ctx.reflection2_paths(h, max_length=FAR)
-    fewer = ctx.reflection2_paths(h[:7], max_paths=32, max_near=32768, max_candidates=1024, max_length=FAR)   # a smaller count, larger caps: fits what is there
-    assert device_free_bytes() >= free0
-    assert again[0].tobytes() == first[0].tobytes() and again[1].tobytes() == first[1].tobytes()
-    assert all(np.array_equal(fewer[0][k], first[0][k][:7]) for k in ("near", "candidates", "found", "flags"))
-    assert np.all(first[0]["found"] == 18) and np.all(first[0]["returned"] == 16) and np.all(fewer[0]["returned"] == 18)
-    assert fewer[1][:, :16].tobytes() == first[1][:7].tobytes()
-    ctx.close()
+    contract.steady_state_allocates_nothing(pkg, QUERY)
 
 
 @pytest.mark.gpu
@@ -759,25 +652,9 @@ def test_queries_interleaved_on_one_context(pkg):
         ctx.set_listener(LIS)
         return ctx, place(ctx, pos)
 
-    def run(ctx, h, query, count):
-        if query == "direct":
-            return (ctx.direct_paths(h[:count], samples=16, source_radius=30.0),)
-        if query == "reflection2":
-            return ctx.reflection2_paths(h[:count], max_length=FAR)
-        return getattr(ctx, query + "_paths")(h[:count])
-
     calls = [("reflection2", 5), ("diffraction", 5), ("direct", 33), ("reflection", 1), ("reflection2", 33), ("diffraction", 33), ("reflection", 33),
              ("reflection2", 1), ("direct", 5), ("reflection", 5), ("reflection2", 5), ("diffraction", 1)]
-    ctx, h = fresh()
-    got = [run(ctx, h, query, count) for query, count in calls]
-    ctx.close()
-    for i, ((query, count), g) in enumerate(zip(calls, got)):
-        one, h1 = fresh()
-        want = run(one, h1, query, count)
-        one.close()
-        assert len(g) == len(want) and all(len(a) == count for a in g)
-        for a, b in zip(g, want):
-            assert a.tobytes() == b.tobytes(), f"call {i} ({query}, count {count}) differs from the same call on a fresh context"
+    got = contract.queries_interleaved_on_one_context(fresh, calls, dict(reflection2=dict(max_length=FAR)))
     # the comparison is not of zeros
     assert np.any(got[4][0]["returned"] > 0) and np.any(got[5][0]["returned"] > 0) and np.any(got[6][0]["returned"] > 0)
     assert got[0][0].tobytes() == got[10][0].tobytes() and got[0][1].tobytes() == got[10][1].tobytes()

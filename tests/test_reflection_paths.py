@@ -10,11 +10,15 @@ reflection points are, by assertion, nowhere near a triangle edge.
 """
 import ctypes as C
 import math
-import os
 import struct
 
 import numpy as np
 import pytest
+
+pytest.register_assert_rewrite("path_query_contract")
+import path_query_contract as contract  # noqa: E402
+from path_query_contract import assert_equal  # noqa: E402
+from path_query_contract import device_free_bytes, place  # noqa: E402,F401  (other test files import them from here)
 
 F = np.float32
 NO_OBJECT = 0xFFFFFFFF
@@ -216,19 +220,6 @@ class Restatement:
         return rows, paths
 
 
-def assert_equal(got, want, where=""):
-    (grows, gpaths), (wrows, wpaths) = got, want
-    assert grows.shape == wrows.shape and gpaths.shape == wpaths.shape, where
-    for i in range(len(wrows)):
-        for k in wrows.dtype.names:
-            assert grows[i][k] == wrows[i][k], f"{where} row {i}: {k}: got {grows[i][k]!r}, restatement {wrows[i][k]!r}"
-        for j in range(wpaths.shape[1]):
-            for k in wpaths.dtype.names:
-                g, x = np.atleast_1d(gpaths[i, j][k]), np.atleast_1d(wpaths[i, j][k])
-                assert g.tobytes() == x.tobytes(), f"{where} row {i} path {j}: {k}: got {g!r}, restatement {x!r}"
-    assert grows.tobytes() == wrows.tobytes() and gpaths.tobytes() == wpaths.tobytes(), where
-
-
 # ---- the scenes -----------------------------------------------------------------------------------------------------
 LO, HI = [0.0, 0.0, 0.0], [1000.0, 800.0, 300.0]
 ALPHA = [[0.5, 0.4, 0.3, 0.2], [0.6, 0.5, 0.7, 0.4], [0.9, 0.9, 0.9, 0.9], [1.0, 1.0, 1.0, 1.0]]
@@ -282,41 +273,11 @@ def test_struct_sizes_and_defaults(pkg):
 
 
 def test_exported_in_one_tier(pkg):
-    cap = pkg._capi
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "frequensee.h")).read()
-    opening = header[:header.index("#ifndef FREQUENSEE_H")]
-    core = opening[opening.index("CORE:"):opening.index("EXTENDED =")]
-    extended = opening[opening.index("EXTENDED:"):]
-    for name in ("fs_reflection_params_default", "fs_update_reflection_paths"):
-        assert name in cap.EXPORTS and hasattr(cap.load(), name)
-        assert name in extended.split() and name not in core.split()
-        assert opening.split().count(name) == 1
+    contract.exported_in_one_tier(pkg, ("fs_reflection_params_default", "fs_update_reflection_paths"))
 
 
 def test_null_context_and_no_device(pkg):
-    cap = pkg._capi
-    lib = cap.load()
-    src = (C.c_int32 * 1)(0)
-    rows = np.full(1, 7, dtype=pkg.Context.REFLECTION_ROW_DTYPE)
-    paths = np.full((1, 8), 7, dtype=pkg.Context.REFLECTION_DTYPE)
-    before = rows.tobytes(), paths.tobytes()
-    assert lib.fs_update_reflection_paths(None, src, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    lib.fs_reflection_params_default(None)   # tolerated, like the other *_default calls
-    import torch
-    if not torch.cuda.is_available():
-        h = C.c_void_p()
-        cfg = cap.default_config(num_bands=1)
-        assert lib.fs_context_create(C.byref(cfg), C.byref(h)) == cap.ERR_NO_DEVICE and h
-        try:
-            assert lib.fs_update_reflection_paths(h, src, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_NO_DEVICE
-            assert b"no CPU fallback" in lib.fs_last_error(h)
-            assert lib.fs_update_reflection_paths(h, None, 1, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_reflection_paths(h, src, 1, None, None, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_reflection_paths(h, src, 1, None, rows.ctypes.data, None) == cap.ERR_INVALID_ARGUMENT
-            assert lib.fs_update_reflection_paths(h, src, 0, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-        finally:
-            lib.fs_context_destroy(h)
-    assert (rows.tobytes(), paths.tobytes()) == before
+    contract.null_context_and_no_device(pkg, QUERY)
 
 
 @pytest.mark.parametrize("n", [1, 4], ids=["12_triangles", "192_triangles"])
@@ -353,14 +314,7 @@ def test_restatement_against_image_sources(pkg, oracle_mod, n):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------
-def place(ctx, positions):
-    return [ctx.create_source(p) for p in positions]
-
-
-def check(pkg, ctx, y, handles, positions, listener, where, src_obj=None, lis_obj=NO_OBJECT, **params):
-    got = ctx.reflection_paths(handles, **params)
-    assert_equal(got, y.expect(pkg, positions, listener, src_obj, lis_obj, **params), where)
-    return got
+check = contract.checker("reflection")
 
 
 @pytest.mark.gpu
@@ -512,15 +466,7 @@ def test_rooms(pkg, oracle_mod, fast):
     rows, paths = got = ctx.reflection_paths(h)
     assert_equal(got, rc["want"], f"rooms fast={fast}")
     assert len(set(rows["found"])) > 2 and np.any(rows["found"] < rows["candidates"])   # the case is not trivial
-    if not fast:
-        ones = [ctx.reflection_paths([x]) for x in h]
-        assert np.concatenate([r for r, _ in ones]).tobytes() == rows.tobytes(), "count = 64 differs from 64 calls with count = 1"
-        assert np.concatenate([p for _, p in ones]).tobytes() == paths.tobytes(), "count = 64 differs from 64 calls with count = 1"
-    perm = np.random.default_rng(7).permutation(64)
-    prows, ppaths = ctx.reflection_paths([h[i] for i in perm])
-    assert prows.tobytes() == rows[perm].tobytes() and ppaths.tobytes() == paths[perm].tobytes(), "a permuted list"
-    frows, fpaths = ctx.reflection_paths(h[:5])   # one confirm workgroup with idle waves beside a full one
-    assert frows.tobytes() == rows[:5].tobytes() and fpaths.tobytes() == paths[:5].tobytes()
+    contract.batch_agrees(ctx.reflection_paths, h, got, singles=not fast)
     ctx.close()
 
 
@@ -537,12 +483,8 @@ def test_mover(pkg, oracle_mod):
     shut = set(int(t) for t in paths[0]["triangle"][:rows[0]["returned"]])
     assert not shut & {2, 3} and any(t >= 12 for t in shut), "the wall behind the door reflects, or the door does not"
     aside = np.array([[1, 0, 0, 0], [0, 1, 0, -350], [0, 0, 1, 0]], np.float32)
-    moved = w.tri.copy()
-    idx = w.obj == 5
-    p = moved[idx]
-    moved[idx] = np.stack([((aside[k, 0] * p[..., 0] + aside[k, 1] * p[..., 1]) + aside[k, 2] * p[..., 2]) + aside[k, 3] for k in range(3)], axis=-1)
     ctx.set_object_transforms([5], aside[None])
-    rows, paths = check(pkg, ctx, Restatement(oracle_mod, w, moved), h, [SRC], LIS, "door aside, no explicit refit")   # the call refits first
+    rows, paths = check(pkg, ctx, Restatement(oracle_mod, w, contract.transformed(w, 5, aside)), h, [SRC], LIS, "door aside, no explicit refit")   # the call refits first
     opened = set(int(t) for t in paths[0]["triangle"][:rows[0]["returned"]])
     assert opened & {2, 3}, "the reflection the door uncovered did not appear"
     ctx.set_object_transforms([5], np.eye(3, 4, dtype=np.float32)[None])
@@ -551,101 +493,35 @@ def test_mover(pkg, oracle_mod):
     ctx.close()
 
 
-@pytest.mark.gpu
-def test_errors_and_untouched_state(pkg, oracle_mod):
-    cap = pkg._capi
-    lib = cap.load()
-    w = shoebox_world()
-    ctx = pkg.Context(num_bands=4)
-    src = ctx.create_source(SRC)
-    arr = (C.c_int32 * 2)(src, src)
-    rows = np.full(2, 7, dtype=pkg.Context.REFLECTION_ROW_DTYPE)
-    paths = np.full((2, 16), 7, dtype=pkg.Context.REFLECTION_DTYPE)
-    sentinel = rows.tobytes(), paths.tobytes()
+def _defaults_found(t, oracle_mod, want):
+    assert tuple(want[0][0]) == (6, 6, 6, 0)
 
-    def call(sources=arr, count=2, params=None, r=rows, p=paths, **kw):
-        q = cap.default_reflection_params(**kw) if (kw or params is None) else params
-        return lib.fs_update_reflection_paths(ctx.h, sources, count, C.byref(q), r.ctypes.data if r is not None else None,
-                                              p.ctypes.data if p is not None else None)
 
-    assert call() == cap.ERR_NOT_COMMITTED
-    ctx.set_scene(w.tri, w.mat, w.absorption, w.transmission, w.scattering, object_ids=w.obj)
-    ctx.set_listener(LIS)
-    assert call(sources=None) == cap.ERR_INVALID_ARGUMENT
-    assert call(r=None) == cap.ERR_INVALID_ARGUMENT
-    assert call(p=None) == cap.ERR_INVALID_ARGUMENT
-    assert lib.fs_update_reflection_paths(None, arr, 2, None, rows.ctypes.data, paths.ctypes.data) == cap.ERR_INVALID_ARGUMENT
-    many = (C.c_int32 * 257)(*([src] * 257))
-    for bad in (0, -1, 257):
-        assert call(sources=many, count=bad) == cap.ERR_INVALID_ARGUMENT
-    q = cap.default_reflection_params()
-    q.struct_size = 32
-    assert call(params=q) == cap.ERR_INVALID_ARGUMENT
-    inf, nan = float("inf"), float("nan")
-    for kw in (dict(max_paths=0), dict(max_paths=17), dict(max_candidates=0), dict(max_candidates=257), dict(margin=-1e-3), dict(margin=nan),
-               dict(margin=inf), dict(step=-0.1), dict(step=nan), dict(step=inf), dict(offset=-0.1), dict(offset=nan), dict(offset=inf),
-               dict(pullback=-1.0), dict(pullback=nan), dict(pullback=inf), dict(dist_divisor=0.0), dict(dist_divisor=-1.0),
-               dict(dist_divisor=nan), dict(dist_divisor=inf), dict(sound_speed=0.0), dict(sound_speed=-1.0), dict(sound_speed=nan),
-               dict(sound_speed=inf)):
-        assert call(**kw) == cap.ERR_INVALID_ARGUMENT, kw
-    assert call(sources=(C.c_int32 * 2)(src, 12345)) == cap.ERR_BAD_HANDLE
-    assert call(sources=(C.c_int32 * 2)(-1, src)) == cap.ERR_BAD_HANDLE
-    assert (rows.tobytes(), paths.tobytes()) == sentinel, "a refused call wrote"
-    # NULL params = the defaults; extreme but legal values are taken
-    r8, p8 = np.full(2, 7, dtype=rows.dtype), np.full((2, 8), 7, dtype=paths.dtype)
-    assert lib.fs_update_reflection_paths(ctx.h, arr, 2, None, r8.ctypes.data, p8.ctypes.data) == cap.OK
-    want = ctx.reflection_paths([src, src])
-    assert r8.tobytes() == want[0].tobytes() and p8.tobytes() == want[1].tobytes() and tuple(r8[0]) == (6, 6, 6, 0)
-    assert call(max_paths=16, max_candidates=1, margin=0.0, step=0.0, offset=0.0, pullback=0.0) == cap.OK
+def _legal_found(rows):
     assert tuple(rows[0]) == (6, 0, 0, 1)
 
-    # a successful call leaves the sources alone: energy, IR publish number, occlusion scalar
-    fp = pkg.default_params(num_rays=512, depth=4, seed=3)
-    ctx.compute_energy_response(src, fp)
-    ctx.reconstruct_impulse_response(src, fp)
-    ctx.update_sound(src, cap.default_sound_params(raycasts_per_tick=64))
-    before = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    ctx.reflection_paths([src])
-    after = (ctx.energy_buffer(src).tobytes(), ctx.impulse_response_sequence(src), ctx.occlusion_attenuation(src), ctx.impulse_response(src).tobytes())
-    assert before == after
-    ctx.close()
-    # an empty committed scene: rows of zeros
-    e = World([], ALPHA, TAU, 4, SCAT)
-    ctx = e.context(pkg)
-    ctx.set_listener(LIS)
-    rows, paths = check(pkg, ctx, Restatement(oracle_mod, e), place(ctx, [SRC, LIS]), [SRC, LIS], LIS, "empty")
-    assert np.all(rows.view(np.uint8) == 0) and np.all(paths.view(np.uint8) == 0)
-    ctx.close()
+
+inf, nan = float("inf"), float("nan")
+QUERY = contract.Query(
+    kind="reflection", dtypes=("REFLECTION_ROW_DTYPE", "REFLECTION_DTYPE"), world=shoebox_world, src=SRC, lis=LIS, wrong_struct_size=32,
+    refused=(dict(max_paths=0), dict(max_paths=17), dict(max_candidates=0), dict(max_candidates=257), dict(margin=-1e-3), dict(margin=nan),
+             dict(margin=inf), dict(step=-0.1), dict(step=nan), dict(step=inf), dict(offset=-0.1), dict(offset=nan), dict(offset=inf),
+             dict(pullback=-1.0), dict(pullback=nan), dict(pullback=inf), dict(dist_divisor=0.0), dict(dist_divisor=-1.0),
+             dict(dist_divisor=nan), dict(dist_divisor=inf), dict(sound_speed=0.0), dict(sound_speed=-1.0), dict(sound_speed=nan),
+             dict(sound_speed=inf)),
+    defaults_found=_defaults_found, legal=(dict(max_paths=16, max_candidates=1, margin=0.0, step=0.0, offset=0.0, pullback=0.0),),
+    legal_found=_legal_found, yardstick=Restatement, empty_world=lambda: World([], ALPHA, TAU, 4, SCAT),
+    fewer=dict(max_paths=16))   # a smaller count, more paths: fits what is there
 
 
-def device_free_bytes():
-    """hipMemGetInfo of the HIP runtime the library itself runs on (the copy of libamdhip64 already mapped into this process: a
-    second runtime, such as the one torch brings along, finds no device once this one holds it)"""
-    import sys
-    torch_dir = os.path.dirname(sys.modules["torch"].__file__) if "torch" in sys.modules else None
-    paths = [line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line]
-    path = next(p for p in paths if torch_dir is None or not p.startswith(torch_dir))
-    hip = C.CDLL(path)
-    free, total = C.c_size_t(), C.c_size_t()
-    assert hip.hipDeviceSynchronize() == 0
-    assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
-    return free.value
+@pytest.mark.gpu
+def test_errors_and_untouched_state(pkg, oracle_mod):
+    contract.errors_and_untouched_state(pkg, oracle_mod, QUERY)
 
 
 @pytest.mark.gpu
 def test_steady_state_allocates_nothing(pkg):
-    w = shoebox_world()
-    ctx = w.context(pkg)
-    ctx.set_listener(LIS)
-    h = place(ctx, [SRC] * 40)
-    first = ctx.reflection_paths(h)
-    free0 = device_free_bytes()
-    second = ctx.reflection_paths(h)
-    third = ctx.reflection_paths(h[:7], max_paths=16)   # a smaller count, more paths: fits what is there
-    assert device_free_bytes() >= free0
-    assert second[0].tobytes() == first[0].tobytes() and second[1].tobytes() == first[1].tobytes()
-    assert third[0].tobytes() == first[0][:7].tobytes() and third[1][:, :8].tobytes() == first[1][:7].tobytes()
-    ctx.close()
+    contract.steady_state_allocates_nothing(pkg, QUERY)
 
 
 @pytest.mark.gpu
