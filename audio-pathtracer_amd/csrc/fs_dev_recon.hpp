@@ -183,8 +183,16 @@ __device__ __forceinline__ void recon_amplitudes(const int row, const float* __r
         s_amp[i] = a;
     }
 }
+// Where sample i of s_x lives.  PAD: one spare word behind every kChunk samples.  A thread's chain starts at a multiple of kChunk,
+// so without the pad the lanes of a wave are kChunk = 16 words apart in every read of the filter and every write of the
+// interpolation: two of the 32 banks of a ds_read_b32 / ds_write_b32, 16 lanes on each.  A kernel that only reconstructs does not
+// notice (nobody else wants its CU's LDS); a reconstruct workgroup of the fused frame kernel shares its CU with walk waves whose
+// stack pushes and pops are on their critical chain.  17 words apart, the 32 lanes of a half wave hit 32 banks.
+template <bool PAD> __device__ __forceinline__ constexpr int recon_x_pos(int i) { return PAD ? i + i / kChunk : i; }
+static_assert(kWarm % kChunk == 0, "a filter chain starts at a multiple of kChunk samples of s_x");
 // phase 1: the interpolated samples x[base - kWarm .. base + kBlock * kChunk) -> s_x[0 ..): thread t its own kChunk, and the
 // first kWarm threads one sample each of the run-in (samples before 0 do not exist: never read)
+template <bool PAD = false>
 __device__ __forceinline__ void recon_interpolate(const int base, int nb, int spb, const float* s_amp, float* s_x) {
     const float fspb = (float)spb;
     auto interp = [&](int i) {
@@ -213,34 +221,40 @@ __device__ __forceinline__ void recon_interpolate(const int base, int nb, int sp
             const float b = wgt * cur;
             x = a + b;
         }
-        s_x[kWarm + (int)threadIdx.x * kChunk + e] = x;
+        s_x[recon_x_pos<PAD>(kWarm + (int)threadIdx.x * kChunk) + e] = x;
         if (++bs == spb) { bs = 0; ++bin; prev = cur; cur = bin < nb ? s_amp[bin] : 0.0f; }
     }
     if ((int)threadIdx.x < kWarm) {
         const int i = base - kWarm + (int)threadIdx.x;
-        s_x[threadIdx.x] = i >= 0 ? interp(i) : 0.0f;
+        s_x[recon_x_pos<PAD>((int)threadIdx.x)] = i >= 0 ? interp(i) : 0.0f;
     }
 }
-// phase 2: the one-pole filter over this thread's kChunk samples behind a run-in of kWarm (0.75^96 ~ 1e-12); `my` = the thread's row
-// of kChunk outputs
+// phase 2: the one-pole filter over this thread's kChunk samples behind a run-in of kWarm (0.75^96 ~ 1e-12); `my` = the thread's
+// kChunk outputs: a row of LDS, or — every index a constant — an array that stays in registers.  The chain is read in groups of
+// kChunk samples (whole groups: s0 and kWarm are multiples of kChunk), each at constant offsets from the group's position.
+template <bool PAD = false>
 __device__ __forceinline__ void recon_filter(const int base, const float* s_x, float* my) {
     const int s0 = base + (int)threadIdx.x * kChunk;
     const int i0 = max(s0 - kWarm, 0);                           // global index of the first sample of the chain
-    const float* xs = s_x + (i0 - (base - kWarm));               // x[i0] in LDS
-    float y = 0.0f;
+    const int at = i0 - (base - kWarm);                          // x[i0] is sample `at` of s_x
     const int run = s0 - i0;                                     // kWarm, less at the very beginning of the IR
-    int e = 0;
-    if (i0 == 0) {                                               // Filtered[0] = IR[0] FSAC.cpp:371 (the first threads of the first block)
-        y = xs[0];
-        if (run == 0) my[0] = y;
-        e = 1;
+    float y = 0.0f;
+    bool first = i0 == 0;                                        // Filtered[0] = IR[0] FSAC.cpp:371 (the first threads of the first block)
+    for (int g = 0; g < run; g += kChunk) {
+        const float* xs = s_x + recon_x_pos<PAD>(at + g);
+#pragma unroll
+        for (int k = 0; k < kChunk; ++k) {
+            const float a = 0.25f * xs[k]; const float b = (1.0f - 0.25f) * y; const float f = a + b;   // FSAC.cpp:374
+            y = (k == 0 && first) ? xs[0] : f;
+        }
+        first = false;
     }
-#pragma unroll 8
-    for (; e < run; ++e) { const float a = 0.25f * xs[e]; const float b = (1.0f - 0.25f) * y; y = a + b; }   // FSAC.cpp:374
-#pragma unroll 4
-    for (; e < run + kChunk; ++e) {
-        const float a = 0.25f * xs[e]; const float b = (1.0f - 0.25f) * y; y = a + b;
-        my[e - run] = y;
+    const float* own = s_x + recon_x_pos<PAD>(at + run);         // the thread's own samples
+#pragma unroll
+    for (int k = 0; k < kChunk; ++k) {
+        const float a = 0.25f * own[k]; const float b = (1.0f - 0.25f) * y; const float f = a + b;
+        y = (k == 0 && first) ? own[0] : f;                      // (sample 0 of the IR is its own output)
+        my[k] = y;
     }
 }
 // the block's kBlock * kChunk consecutive samples from s_stage, 16 bytes per lane: the device array, and the channel row to the host slot
@@ -284,6 +298,35 @@ __device__ __forceinline__ void reconstruct_body_fast(const int row, const int c
     recon_store(base, num_samples, s_stage, out, to_host, host_out);
 }
 
+// The two phases for the reconstruct part of the narrow fused frame kernels (fs_frame.hip), in hardly more LDS than the one-phase
+// body took there (reconstruct_body_fast's 38 KB would have been the launch's largest part): the filter's kChunk outputs wait in
+// registers until every chain of the workgroup has read its samples, and the staging rows then take the place of the
+// interpolated samples.  The same phases as reconstruct_body_fast: the same bits.
+// LDS: s_amp [nb] | s_x [kBlock * kChunk + kWarm] with a pad word per kChunk (recon_x_pos), later s_stage [kBlock][kChunk + 1]:
+// fs_internal.hpp: frame_recon_lds_bytes.
+__device__ __forceinline__ void reconstruct_body_staged(const int row, const int chunk_block, const float* __restrict__ energy, int B, int nb,
+                                                        int num_samples, int spb, float* __restrict__ ir_bands, float* __restrict__ ir_mono,
+                                                        float* s_amp, float* host_out, uint32_t* __restrict__ slot_mask = nullptr) {
+    float* s_x = s_amp + nb;
+    if (ir_bands == nullptr && (row < B || host_out == nullptr)) return;   // (uniform) a superseded frame: only its channel row, for the host
+    recon_amplitudes(row, energy, B, nb, s_amp);
+    __syncthreads();
+    bool to_host = host_out != nullptr && row == B;         // (uniform for the workgroup)
+    float* out = ir_bands == nullptr ? nullptr : (row < B ? ir_bands + (size_t)row * num_samples : ir_mono);
+    const int base = chunk_block * kBlock * kChunk;          // the block's first sample
+    if (to_host) to_host = host_block_wanted(s_amp, nb, spb, base, chunk_block, slot_mask);
+    recon_interpolate<true>(base, nb, spb, s_amp, s_x);
+    __syncthreads();
+    float y[kChunk];
+    recon_filter<true>(base, s_x, y);
+    __syncthreads();                                         // (every chain has read its samples: the area becomes the staging rows)
+    float* my = s_x + threadIdx.x * (kChunk + 1);            // (+ 1: conflict-free rows)
+#pragma unroll
+    for (int e = 0; e < kChunk; ++e) my[e] = y[e];
+    __syncthreads();
+    recon_store(base, num_samples, s_x, out, to_host, host_out);
+}
+
 // FS_FLAG_SPECTRAL_IR: the channel row (row B) as y[n] = (1/sqrt(B)) sum_b env_b[n] c_b[n] — env_b = band row b, bit for bit (the
 // phases above), c_b = the band's unit-power noise carrier ([B][carrier_stride(num_samples)] fp32, fs_fft.hip: launch_build_carriers).
 // The workgroup computes every band's envelope for its own block (no other workgroup's band row is read: the rows' workgroups are
@@ -291,20 +334,21 @@ __device__ __forceinline__ void reconstruct_body_fast(const int row, const int c
 // read as 16-byte loads of the thread's kChunk samples.  Zero blocks: a block is non-zero if ANY band's amplitude in its reach is
 // (one band above the 1e-6 cut can leave the band MEAN below it); where every envelope is zero the output is an exact zero.
 // Used by the fused frame kernel and by the reconstruct-only kernels alike: the same bits on every route.
-// LDS: reconstruct_body_fast's layout.
+// LDS: reconstruct_body_staged's layout (a band's envelope goes from the filter to the products in registers; the staging rows
+// are written once, behind the last band's barrier, where the interpolated samples were).
 __device__ __forceinline__ void reconstruct_spectral_row(const int chunk_block, const float* __restrict__ energy, int B, int nb,
                                                          int num_samples, int spb, float* __restrict__ ir_bands, float* __restrict__ ir_mono,
                                                          float* s_amp, float* host_out, uint32_t* __restrict__ slot_mask,
                                                          const float* __restrict__ carrier) {
     float* s_x = s_amp + nb;
-    float* s_stage = s_x + kBlock * kChunk + kWarm;
+    float* s_stage = s_x;
     if (ir_bands == nullptr && host_out == nullptr) return;   // (uniform) nobody wants this row
     float* out = ir_bands == nullptr ? nullptr : ir_mono;
     const int base = chunk_block * kBlock * kChunk;
     const int s0 = base + (int)threadIdx.x * kChunk;
     const size_t ld = (size_t)carrier_stride(num_samples);
     float* my = s_stage + threadIdx.x * (kChunk + 1);
-    float acc[kChunk];
+    float acc[kChunk], env[kChunk];
 #pragma unroll
     for (int e = 0; e < kChunk; ++e) acc[e] = 0.0f;
     bool nz = false;
@@ -312,18 +356,18 @@ __device__ __forceinline__ void reconstruct_spectral_row(const int chunk_block, 
         recon_amplitudes(band, energy, B, nb, s_amp);
         __syncthreads();
         nz = nz || block_reach_nonzero(s_amp, nb, spb, base);
-        recon_interpolate(base, nb, spb, s_amp, s_x);
+        recon_interpolate<true>(base, nb, spb, s_amp, s_x);
         __syncthreads();
-        recon_filter(base, s_x, my);                            // env_b of the thread's kChunk samples (its own row: no barrier)
+        recon_filter<true>(base, s_x, env);                          // env_b of the thread's kChunk samples
         if (s0 < num_samples) {
             const float4* c = reinterpret_cast<const float4*>(carrier + (size_t)band * ld + s0);   // (ld and s0: multiples of kChunk: 16-byte aligned)
 #pragma unroll
             for (int q = 0; q < kChunk / 4; ++q) {
                 const float4 cv = c[q];
-                acc[4 * q + 0] = acc[4 * q + 0] + my[4 * q + 0] * cv.x;
-                acc[4 * q + 1] = acc[4 * q + 1] + my[4 * q + 1] * cv.y;
-                acc[4 * q + 2] = acc[4 * q + 2] + my[4 * q + 2] * cv.z;
-                acc[4 * q + 3] = acc[4 * q + 3] + my[4 * q + 3] * cv.w;
+                acc[4 * q + 0] = acc[4 * q + 0] + env[4 * q + 0] * cv.x;
+                acc[4 * q + 1] = acc[4 * q + 1] + env[4 * q + 1] * cv.y;
+                acc[4 * q + 2] = acc[4 * q + 2] + env[4 * q + 2] * cv.z;
+                acc[4 * q + 3] = acc[4 * q + 3] + env[4 * q + 3] * cv.w;
             }
         }
         __syncthreads();                                        // (the next band rewrites s_amp and s_x)

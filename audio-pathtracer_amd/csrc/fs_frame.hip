@@ -86,6 +86,12 @@ static_assert(sizeof(FrameArgs) + sizeof(DeviceScene) <= 4096, "kernel arguments
 #ifndef FS_FRAME_MIN_WAVES
 #define FS_FRAME_MIN_WAVES 4
 #endif
+// which body the plain rows of the reconstruct part run (see there)
+#ifdef FS_FRAME_WIDE
+template <bool BATCH> constexpr bool kReconStaged = false;
+#else
+template <bool BATCH> constexpr bool kReconStaged = BATCH;
+#endif
 // SPECTRAL: some reconstruct item has a carrier set (FS_FLAG_SPECTRAL_IR): its channel row is reconstruct_spectral_row, as in the
 // reconstruct-only kernels.  An instantiation of its own: the default ones keep their registers, LDS and code.
 template <int B, bool BATCH, bool SPECTRAL>
@@ -134,8 +140,18 @@ __global__ __launch_bounds__(kBlock, FS_FRAME_MIN_WAVES) void frame_kernel(Devic
             publish_arrive(a.pub.tickets, (uint32_t)a.num_recon * per_item, a.pub.host_word, a.pub.id);
             return;
         }
-        reconstruct_body((int)(in_item / a.recon_cb), (int)(in_item % a.recon_cb), it.energy, a.recon_B, a.recon_nb, a.recon_samples, it.spb,
-                         it.ir_bands, it.ir_mono, s_amp, it.host, s_amp + a.recon_nb, it.mask);
+        // A launch of several frames (BATCH: the connect part first, the reconstruct workgroups start while two frames' walks run)
+        // reconstructs in two phases: every interpolated sample of the block once, not by each of the seven chains that read it —
+        // 2 % of the launch's vector instructions, + 2.4 % on the headline.  A launch of one frame keeps the one-phase body: its
+        // reconstruct workgroups run beside the thin connect tail, where the vector units idle anyway, and measured 0.6 % slower
+        // in two phases (1 002 -> 996 M rays/s; DESIGN.md section 5, profiles/lds_budget_ab.jsonl).  So does the wide
+        // flavour, whose launches are too small for either to matter.  The same bits either way.
+        if (kReconStaged<BATCH>)
+            reconstruct_body_staged((int)(in_item / a.recon_cb), (int)(in_item % a.recon_cb), it.energy, a.recon_B, a.recon_nb, a.recon_samples,
+                                    it.spb, it.ir_bands, it.ir_mono, s_amp, it.host, it.mask);
+        else
+            reconstruct_body((int)(in_item / a.recon_cb), (int)(in_item % a.recon_cb), it.energy, a.recon_B, a.recon_nb, a.recon_samples, it.spb,
+                             it.ir_bands, it.ir_mono, s_amp, it.host, s_amp + a.recon_nb, it.mask);
         publish_arrive(a.pub.tickets, (uint32_t)a.num_recon * per_item, a.pub.host_word, a.pub.id);
     }
 }
@@ -223,8 +239,14 @@ bool FS_LAUNCH_FRAME(int B, const DeviceScene& sc, const FrameParts& f, hipStrea
         a.recon_cb = (chunks + kBlock - 1) / kBlock;
         blocks += (uint32_t)f.num_recon * (uint32_t)(f.recon_B + 1) * a.recon_cb;
         a.recon_carrier = f.recon_carrier;
-        // reconstruct_body: the amplitudes | the block's samples staged for 16-byte stores; reconstruct_spectral_row: reconstruct_body_fast's layout
+#ifdef FS_FRAME_WIDE
+        // reconstruct_body: the amplitudes | the block's samples staged for 16-byte stores; reconstruct_spectral_row: within reconstruct_body_fast's layout
         lds = std::max(lds, recon_lds_bytes(f.recon_nb, f.recon_carrier != nullptr));
+#else
+        // reconstruct_body_staged's layout, the spectral row's too — and no less than reconstruct_body's: 21.8 KB at 1000 bins,
+        // below the walk and connect parts' 37 KB
+        lds = std::max(lds, frame_recon_lds_bytes(f.recon_nb));
+#endif
     }
     if (blocks == 0) return false;
     if (blocks_only) { *blocks_only = blocks; return true; }

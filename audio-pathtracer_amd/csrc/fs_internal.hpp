@@ -159,6 +159,15 @@ constexpr int kWarm = 96;                             // samples of filter run-i
 constexpr size_t recon_lds_bytes(int num_bins, bool fast = true) {
     return sizeof(float) * ((size_t)num_bins + (fast ? (size_t)kReconBlockSamples + kWarm : 0) + (size_t)kBlock * (kChunk + 1));
 }
+// The same two phases in the narrow fused frame kernels (reconstruct_body_staged, and the spectral row everywhere): the amplitudes
+// [num_bins] | ONE area that first holds the interpolated samples, a pad word behind every kChunk of them (recon_x_pos), and then
+// — the filter's outputs having waited in registers behind a barrier — the staged outputs
+constexpr size_t frame_recon_lds_bytes(int num_bins) {
+    const size_t x = (size_t)kReconBlockSamples + kWarm, x_padded = x + x / kChunk, stage = (size_t)kBlock * (kChunk + 1);
+    return sizeof(float) * ((size_t)num_bins + (x_padded > stage ? x_padded : stage));
+}
+static_assert(frame_recon_lds_bytes(0) <= recon_lds_bytes(0), "the spectral row of the reconstruct-only kernels runs in recon_lds_bytes");
+static_assert(frame_recon_lds_bytes(0) >= recon_lds_bytes(0, false), "a narrow fused launch of one frame runs reconstruct_body in the same LDS");
 // Room left next to it for the static LDS of the kernels that run a reconstruct (the fused frame kernels: 1 888 B on gfx950; the
 // batch kernel: 256 B for its workgroup vote).  A workgroup's static and dynamic LDS together must fit the device's limit.
 constexpr size_t kReconStaticLdsReserve = 4096;

@@ -2,7 +2,9 @@
 // (audio-pathtracer_amd/csrc/fs_bvh.cpp) over a triangle file and walks seeded diffuse rays through it with the
 // kernels' visiting rule (4 quantised child boxes per node visit, hits sorted by entry distance, nearest first, the
 // others pushed; popped entries are visited unconditionally; closest hit shrinks the interval), counting node
-// visits and triangle tests per ray.  Used to compare builder variants without a GPU:
+// visits and triangle tests per ray — and how many pending stack entries a ray holds, per ray (its most) and per step:
+// what a cap on the kernels' LDS stack rows (FS_STACK_ROWS_CAP, DeviceScene.stack_limit) sends to the deep store.
+// Used to compare builder variants, and to judge such a cap, without a GPU:
 //
 //   python -c "import __graft_entry__ as g, numpy as np; np.asarray(g.load_package().scenes.old_mine(8).triangles, np.float32).tofile('/tmp/mine.f32')"
 //   g++ -O2 -std=c++17 -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o /tmp/tree_cost tools/tree_cost.cpp \
@@ -39,11 +41,16 @@ static bool tri_hit(const Tri64& t, const Ray& r, float tmax, float& tt) {
     return true;
 }
 
-struct Counts { double nodes = 0, tris = 0, steps = 0, pops = 0, late = 0, late_leaf = 0; };
+constexpr int kMaxPending = 128;
+struct Counts {
+    double nodes = 0, tris = 0, steps = 0, pops = 0, late = 0, late_leaf = 0;
+    double ray_most[kMaxPending + 1] = {};   // rays by the most pending entries they ever held
+    double step_has[kMaxPending + 1] = {};   // steps (a node visit or a leaf) by the pending entries behind them
+};
 
 static int closest(const HostBVH& b, const Ray& r, float& tbest, Counts& c) {
-    int stack[128], sp = 0, cur = 0, hit = -1;
-    float stack_t[128], cur_t = 0.f;
+    int stack[kMaxPending], sp = 0, cur = 0, hit = -1, most = 0;
+    float stack_t[kMaxPending], cur_t = 0.f;
     float tmax = 1e30f;
     int tri_i = 0, tri_n = 0;
     while (true) {
@@ -70,12 +77,15 @@ static int closest(const HostBVH& b, const Ray& r, float& tbest, Counts& c) {
             for (int i = 1; i < nh; ++i)
                 for (int j = i; j > 0 && te[j] < te[j - 1]; --j) { std::swap(te[j], te[j - 1]); std::swap(ord[j], ord[j - 1]); }
             for (int i = nh - 1; i >= 1; --i) { stack_t[sp] = te[i]; stack[sp++] = n.child[ord[i]]; }
+            most = std::max(most, sp);
+            c.step_has[sp] += 1;
             if (nh) { cur = n.child[ord[0]]; cur_t = te[0]; }
             else if (sp) { c.pops += 1; cur = stack[--sp]; cur_t = stack_t[sp]; if (cur_t >= tmax) { (cur >= 0 ? c.late : c.late_leaf) += 1; } }
             else cur = INT32_MIN;
         } else if (cur != INT32_MIN) {   // a leaf
             const int code = ~cur;
             tri_i = code >> 2; tri_n = tri_i + (code & 3) + 1;
+            c.step_has[sp] += 1;
             for (; tri_i < tri_n; ++tri_i) {
                 c.tris += 1;
                 float tt;
@@ -85,6 +95,7 @@ static int closest(const HostBVH& b, const Ray& r, float& tbest, Counts& c) {
             else cur = INT32_MIN;
         } else break;
     }
+    c.ray_most[most] += 1;
     tbest = tmax;
     return hit;
 }
@@ -148,5 +159,19 @@ int main(int argc, char** argv) {
                 "cost (124 v per node + 52 v per tri) %.0f | hit fraction %.3f | popped behind the hit: %.3f nodes, %.3f leaves per ray\n",
                 T, bvh.nodes.size(), bvh.stack_need, bvh.max_depth, build_ms, c.nodes / rays, c.tris / rays,
                 (124.0 * c.nodes + 52.0 * c.tris) / rays, hits / rays, c.late / rays, c.late_leaf / rays);
+    // the distribution of pending stack entries: of the rays, the share whose most was n and the share that ever held n or more;
+    // of the steps, the share taken with n or more entries pending
+    double traced = 0, steps = 0;
+    for (int n = 0; n <= kMaxPending; ++n) { traced += c.ray_most[n]; steps += c.step_has[n]; }
+    int top = kMaxPending;
+    while (top > 0 && c.ray_most[top] == 0 && c.step_has[top] == 0) --top;
+    std::printf("pending stack entries (%.0f rays, %.0f steps; worst case of the tree %d):\n   n   rays with most = n   rays with n or more   steps with n or more\n",
+                traced, steps, bvh.stack_need);
+    double rays_ge = traced, steps_ge = steps;
+    for (int n = 0; n <= top; ++n) {
+        std::printf("%4d   %17.5f %%   %17.5f %%   %17.5f %%\n", n, 100.0 * c.ray_most[n] / std::max(traced, 1.0), 100.0 * rays_ge / std::max(traced, 1.0),
+                    100.0 * steps_ge / std::max(steps, 1.0));
+        rays_ge -= c.ray_most[n]; steps_ge -= c.step_has[n];
+    }
     return 0;
 }
