@@ -53,12 +53,31 @@ Whether a deposit of next to no energy is there at all (float32's range ends at 
 scalar rule above multiplies by 1 / cos at every hit and passes the room's size after 10 ... 14 turns, the per-axis rule follows
 the float32 walk's real drift (1e-3 cm after 30 turns) closely enough for walks of 30 ... 40 turns.  The default mode keeps the
 scalar rule, and with it its results bit for bit.
+
+What a source's descriptor does (apply_source) and the actors a walk ignores are written from the prose of include/frequensee.h
+alone — the comments of fs_source_set_orientation / fs_source_set_directivity, of fs_source_set_object / fs_listener_set_object
+and of fs_source_set_order_window — and share with the build exactly this:
+
+  directivity         f = orientation / |orientation| from the float32 values; the emission direction w of a path = the ray with
+                      which the source's walk first HIT something (Node.arrive of the first hit-made node among F1..Fi: the
+                      model's own float64 ray, nothing is drawn again), without one the unit direction of the connection Fi -> Bj;
+                      theta = atan2(|w x f|, w . f), x = theta (K - 1) / pi, k = min(floor x, K - 2), D_b = T[b][k] + (x - k)
+                      (T[b][k+1] - T[b][k]) on the float32 table; D_b is the LAST factor of the contribution's energy
+  order window        order = the number of the path's nodes that a hit made; outside [lo, hi] nothing is deposited, nothing else
+                      changes
+  ignored actors      a rectangle has an actor id (Rect.object, Scene.object_ids); the rays of a walk do not see the rectangles of
+                      the actor the walk starts from; the connection's query sees every rectangle
+
+D is continuous in w, so it adds no discrete decision and no flag of the kind above; apply_source leaves out the contributions
+whose D is too steep for the direction's error (d_flagged, see there).  A frame without table, window and ignored actor is what
+it was, bit for bit.
 """
 import math
 import struct
 
 MASK = 0xFFFFFFFF
 NO_MATERIAL = None
+NO_OBJECT = None                # a rectangle of no registered actor; a walk that ignores no actor
 LOBE_DIFFUSE, LOBE_SPECULAR, LOBE_TRANSMIT = 0, 1, 2
 
 
@@ -119,14 +138,15 @@ class Params:
 # ---- the world ------------------------------------------------------------------------------------------------------------------------
 class Rect:
     """the rectangle {x[axis] = coord, lo[0] <= x[u] <= hi[0], lo[1] <= x[v] <= hi[1]}, u = axis + 1, v = axis + 2 (mod 3)"""
-    __slots__ = ("axis", "coord", "u", "v", "ulo", "uhi", "vlo", "vhi", "material")
+    __slots__ = ("axis", "coord", "u", "v", "ulo", "uhi", "vlo", "vhi", "material", "object")
 
-    def __init__(self, axis, coord, lo, hi, material=NO_MATERIAL):
+    def __init__(self, axis, coord, lo, hi, material=NO_MATERIAL, object_id=NO_OBJECT):
         self.axis, self.coord = axis, float(coord)
         self.u, self.v = (axis + 1) % 3, (axis + 2) % 3
         self.ulo, self.vlo = float(lo[0]), float(lo[1])
         self.uhi, self.vhi = float(hi[0]), float(hi[1])
         self.material = material
+        self.object = object_id         # the registered actor the rectangle belongs to (fs_scene_set_objects)
 
 
 # the winding normal e1 x e2 of Scene.triangles' cells is +axis with +0 zeros; a flipped normal has -0 zeros
@@ -189,18 +209,23 @@ class Scene:
                     mats += [0xFFFF if r.material is NO_MATERIAL else r.material] * 2
         return tris, mats
 
-    def _candidates(self, o, d, tmax, e, own=None, e_far=None, far_own=None):
+    def object_ids(self, n=1):
+        """the actor id of every triangle of triangles(n), in its order; 0xFFFFFFFF (FS_NO_OBJECT) for a rectangle of no actor"""
+        return [0xFFFFFFFF if r.object is NO_OBJECT else r.object for r in self.rects for _ in range(2 * n * n)]
+
+    def _candidates(self, o, d, tmax, e, own=None, e_far=None, far_own=None, ignore=NO_OBJECT):
         """per rectangle the ray's plane meets: (t, rectangle, hit by the model's own arithmetic, robust hit, robust miss, threshold,
         bound at the hit).  e: the bound of the node at o, own: the axis of that node's normal (ACROSS its own wall a node is
         coord +- offset, wrong by float32 rounding only, at most 1e-3 cm at these sizes: the bound is an in-plane matter);
-        e_far, far_own: the same for the node the segment ends at (a connection), None for a ray that just ends at tmax"""
+        e_far, far_own: the same for the node the segment ends at (a connection), None for a ray that just ends at tmax;
+        ignore: the actor whose rectangles the ray does not see at all (a walk's own actor)"""
         if isinstance(e, tuple):
-            return self._candidates_by_axis(o, d, tmax, e, e_far)
+            return self._candidates_by_axis(o, d, tmax, e, e_far, ignore)
         out = []
         e_all = e + (e_far or 0.0)
         for r in self.rects:
             da = d[r.axis]
-            if da == 0.0:
+            if da == 0.0 or (ignore is not NO_OBJECT and r.object == ignore):
                 continue
             t = (r.coord - o[r.axis]) / da
             pu, pv = o[r.u] + t * d[r.u], o[r.v] + t * d[r.v]
@@ -220,7 +245,7 @@ class Scene:
                         (clear and s0 * s1 > 0.0) or m < -thr, thr, e_hit))
         return out
 
-    def _candidates_by_axis(self, o, d, tmax, E, E_far):
+    def _candidates_by_axis(self, o, d, tmax, E, E_far, ignore=NO_OBJECT):
         """_candidates with a bound PER AXIS, E = (Ex, Ey, Ez) (Params.axis_bounds).  The scalar rule divides the whole bound by
         |d . n| at every hit, the worst case of every bounce at once, and so passes the room's size after 10 ... 14 turns while
         the float32 walk is still within 1e-3 cm of this one.  To first order a node displaced by delta, its ray's direction
@@ -237,7 +262,7 @@ class Scene:
         for r in self.rects:
             a, u, v = r.axis, r.u, r.v
             da = d[a]
-            if da == 0.0:
+            if da == 0.0 or (ignore is not NO_OBJECT and r.object == ignore):
                 continue
             t = (r.coord - o[a]) / da
             pu, pv = o[u] + t * d[u], o[v] + t * d[v]
@@ -257,13 +282,14 @@ class Scene:
                         (clear and s0 * s1 > 0.0) or mu < -tu or mv < -tv, thr, tuple(bound)))
         return out
 
-    def closest(self, o, d, tmax, e=0.0, own=None):
+    def closest(self, o, d, tmax, e=0.0, own=None, ignore=NO_OBJECT):
         """the closest hit: smallest t in (0, tmax] whose in-plane point lies inside the extent -> (rectangle or None, t,
         fragile, bound at the hit).  Fragile: a rectangle that is neither a robust hit nor a robust miss lies no farther than
-        the first robust hit, or two robust hits are closer than the threshold."""
+        the first robust hit, or two robust hits are closer than the threshold.  ignore: the actor of the walk the ray belongs
+        to, whose rectangles it passes; any_hit, the connection's query, has no such argument: it ignores nothing."""
         best = None
         robust = []
-        cands = self._candidates(o, d, tmax, e, own)
+        cands = self._candidates(o, d, tmax, e, own, ignore=ignore)
         for c in cands:
             if c[2] and (best is None or c[0] < best[0]):
                 best = c
@@ -352,14 +378,14 @@ def own_axis(node):
     return None if node.normal is None else max(range(3), key=lambda i: abs(node.normal[i]))
 
 
-def step(scene, prm, pair, side, k, node):
+def step(scene, prm, pair, side, k, node, ignore=NO_OBJECT):
     """one turn of the loop BEHIND the push of `node` as node k (ARTS.cpp:300-353): None when the roulette ends the walk, else
     (the state the next turn pushes, fragile, hit).  On a miss the state is kept and only the probability changes."""
     words = draw(prm.seed, pair, side, k, 0)
     if prm.russian_roulette and not (u01(words[0]) < prm.rr_prob):       # :301-302, :349-353
         return None
     if prm.lobes and node.arrive is not None and node.material is not NO_MATERIAL:
-        return _lobe_step(scene, prm, words, node)       # (an end point, a vertex without material and the duplicate node do not pick)
+        return _lobe_step(scene, prm, words, node, ignore)       # (an end point, a vertex without material and the duplicate node do not pick)
     if node.normal is None:                                              # CurrentNormal.IsNearlyZero() :306
         d, fragile = sample_sphere(prm.seed, pair, side, k, words)
         prob = prm.rr_prob / (4.0 * math.pi)                             # :309-310
@@ -367,11 +393,11 @@ def step(scene, prm, pair, side, k, node):
         d, cos_theta = sample_cone(node.normal, u01(words[1]), u01(words[2]), prm.cosine)
         fragile = False
         prob = prm.rr_prob * cos_theta / math.pi                         # :316-317
-    return _trace(scene, prm, node, node.pos, d, prob, fragile)
+    return _trace(scene, prm, node, node.pos, d, prob, fragile, ignore)
 
 
-def _trace(scene, prm, node, origin, d, prob, fragile):
-    rect, t, fr, bound = scene.closest(origin, d, prm.max_trace_dist, node.bound, own_axis(node))   # :340-342
+def _trace(scene, prm, node, origin, d, prob, fragile, ignore=NO_OBJECT):
+    rect, t, fr, bound = scene.closest(origin, d, prm.max_trace_dist, node.bound, own_axis(node), ignore)   # :340-342, :322-327
     fragile = fragile or fr
     if rect is None:
         return Node(node.pos, node.normal, node.material, prob, node.bound), fragile, False
@@ -380,7 +406,7 @@ def _trace(scene, prm, node, origin, d, prob, fragile):
     return Node(pos, n, rect.material, prob, bound, arrive=d), fragile, True   # :346-347
 
 
-def _lobe_step(scene, prm, words, node):
+def _lobe_step(scene, prm, words, node, ignore=NO_OBJECT):
     """the turn behind a vertex that a hit on a material made, in lobe mode: word 3 (the cone sample leaves it unused) picks
     the lobe the walk leaves `node` by, and the node keeps it for EvaluatePath"""
     node.lobe, lobe_prob, fragile = scene.pick_lobe(node.material, u01(words[3]))
@@ -401,13 +427,14 @@ def _lobe_step(scene, prm, words, node):
             # wall's plane the origin is the node, with the node's bound
             d = a
             origin = tuple(node.pos[i] - 2.0 * prm.surface_offset * n[i] for i in range(3))
-    return _trace(scene, prm, node, origin, d, prob, fragile)
+    return _trace(scene, prm, node, origin, d, prob, fragile, ignore)
 
 
-def walk(scene, prm, pair, side, start, turns=None):
+def walk(scene, prm, pair, side, start, turns=None, ignore=NO_OBJECT):
     """ARTS.cpp:279-355 -> (nodes, fragile).  Node k is pushed with the probability the PREVIOUS turn computed (:297), before
     the cap and the roulette; a turn that misses pushes the same place again.  turns: a list that receives, per turn k (the
-    one that makes node k + 1), whether a decision of it was fragile."""
+    one that makes node k + 1), whether a decision of it was fragile.  ignore: the actor the walk starts from (fs_source_set_object
+    for side 0, fs_listener_set_object for side 1): every ray of THIS walk passes its rectangles (AddIgnoredActor, :322-327)."""
     node = Node(tuple(float(x) for x in start), None, NO_MATERIAL, 1.0, (0.0, 0.0, 0.0) if prm.axis_bounds else 0.0)  # :287-291
     nodes, fragile, k = [], False, 0
     cap = prm.depth if prm.depth > 0 else (None if prm.russian_roulette and prm.rr_prob < 1.0 else 64)
@@ -415,7 +442,7 @@ def walk(scene, prm, pair, side, start, turns=None):
         nodes.append(node)                                               # :297-298
         if cap is not None and k >= cap:
             break
-        nxt = step(scene, prm, pair, side, k, node)
+        nxt = step(scene, prm, pair, side, k, node, ignore)
         if nxt is None:
             break
         node, fr, _ = nxt
@@ -596,14 +623,14 @@ class PrefixPair:
     __slots__ = ("fwd", "bwd", "steps", "connections", "contributions", "flagged")
 
 
-def prefix_pair(scene, prm, idx, src, lis, num_pairs, balance=False):
+def prefix_pair(scene, prm, idx, src, lis, num_pairs, balance=False, ignore=(NO_OBJECT, NO_OBJECT)):
     """a pair of the all-prefix mode: every (i, j) is the candidate path F0..Fi, Bj..B0 — connect and evaluate as for the end-to-end
     connection, energy = Gain x weight / pairs.  Contribution (i, j) is flagged iff a turn below i of the forward walk, a turn below
     j of the backward walk, its connection, a MinSeg or bin-edge test of its path or a weight fallback is fragile."""
     r = PrefixPair()
     tf, tb = [], []
-    r.fwd, _ = walk(scene, prm, idx, 0, src, tf)
-    r.bwd, _ = walk(scene, prm, idx, 1, lis, tb)
+    r.fwd, _ = walk(scene, prm, idx, 0, src, tf, ignore[0])
+    r.bwd, _ = walk(scene, prm, idx, 1, lis, tb, ignore[1])
     r.steps = len(r.fwd) + len(r.bwd) - 2
     r.connections = len(r.fwd) * len(r.bwd)
     r.contributions, r.flagged = [], 0
@@ -635,7 +662,7 @@ class PrefixFrame:
     connections = sum over the pairs of (kf + 1)(km + 1) and steps = the rays of all walks (both exact); what the frame
     exercised: fallbacks by kind, lobes picked by kind, the largest number of prefix combinations of a pair"""
 
-    def __init__(self, scene, prm, src, lis, num_pairs, balance=False, keep_pairs=False):
+    def __init__(self, scene, prm, src, lis, num_pairs, balance=False, keep_pairs=False, ignore=(NO_OBJECT, NO_OBJECT)):
         self.H = [[0.0] * prm.num_bins for _ in range(scene.bands)]
         self.count = [0] * prm.num_bins
         self.flagged, self.deposits, self.steps, self.connections, self.pairs = 0, 0, 0, 0, []
@@ -643,7 +670,7 @@ class PrefixFrame:
         self.lobes = [0, 0, 0]
         self.most_combinations = self.pairs_over_64 = 0
         for i in range(num_pairs):
-            r = prefix_pair(scene, prm, i, src, lis, num_pairs, balance)
+            r = prefix_pair(scene, prm, i, src, lis, num_pairs, balance, ignore)
             self.steps += r.steps
             self.connections += r.connections
             self.flagged += r.flagged
@@ -673,12 +700,12 @@ class Pair:
     __slots__ = ("fwd", "bwd", "steps", "visible", "fragile", "delay", "bin", "energy")
 
 
-def pair(scene, prm, i, src, lis, num_pairs):
+def pair(scene, prm, i, src, lis, num_pairs, ignore=(NO_OBJECT, NO_OBJECT)):
     """GenerateFullPaths' loop body (ARTS.cpp:217-229) and the pair's deposit (:164-171): the source's walk (side 0), the
     listener's (side 1), the connection of their last nodes, the path F0..Fk, Bm..B0 (:262-267), energy = Gain / pairs"""
     r = Pair()
-    r.fwd, ff = walk(scene, prm, i, 0, src)
-    r.bwd, fb = walk(scene, prm, i, 1, lis)
+    r.fwd, ff = walk(scene, prm, i, 0, src, ignore=ignore[0])
+    r.bwd, fb = walk(scene, prm, i, 1, lis, ignore=ignore[1])
     r.steps = len(r.fwd) + len(r.bwd) - 2
     r.visible, fc = connect(scene, prm, r.fwd[-1], r.bwd[-1])
     r.fragile = ff or fb or fc
@@ -702,13 +729,13 @@ class Frame:
     flagged = their indices, deposits = the visible ones among the others, steps = the rays of all walks (exact: the
     roulette is integer arithmetic)"""
 
-    def __init__(self, scene, prm, src, lis, num_pairs, keep_pairs=False):
+    def __init__(self, scene, prm, src, lis, num_pairs, keep_pairs=False, ignore=(NO_OBJECT, NO_OBJECT)):
         self.H = [[0.0] * prm.num_bins for _ in range(scene.bands)]
         self.count = [0] * prm.num_bins                     # deposits per bin behind H
         self.flagged, self.deposits, self.steps, self.pairs = [], 0, 0, []
         self.connections, self.lobes = num_pairs, [0, 0, 0]      # (lobe mode: the lobes picked, by kind)
         for i in range(num_pairs):
-            r = pair(scene, prm, i, src, lis, num_pairs)
+            r = pair(scene, prm, i, src, lis, num_pairs, ignore)
             self.steps += r.steps
             count_lobes(self.lobes, r.fwd + r.bwd)
             if keep_pairs:
@@ -722,8 +749,106 @@ class Frame:
                     self.H[b][r.bin] += r.energy[b]
 
 
+# ---- what a source's descriptor does to a frame: directivity table, orientation, order window ------------------------------------------------
+WALK_RAY_ERROR = 3e-7       # the float32 direction's error of a walk's ray (the figure of the walk's bound)
+
+
+def emission(fwd, b):
+    """the direction a path left the source in: fwd = F0..Fi, the nodes of the source's walk that are on the path, b = the node of
+    the listener's walk that Fi is connected to -> (unit direction, its error delta in radians, whether it is the walk's ray).
+    The `arrive` of the first node among F1..Fi that a hit made, the exact ray the walk traced; without one (every step so far
+    missed: the walk is still at the source) the unit direction of the connection Fi -> Bj, wrong by the two nodes' bounds and a
+    coordinate's rounding over its length."""
+    for n in fwd[1:]:
+        if n.arrive is not None:
+            return n.arrive, WALK_RAY_ERROR, True
+    f = fwd[-1]
+    diff = [b.pos[i] - f.pos[i] for i in range(3)]
+    length = math.sqrt(diff[0] * diff[0] + diff[1] * diff[1] + diff[2] * diff[2])
+    if not length > 0.0:
+        return None, math.inf, False
+    return (diff[0] / length, diff[1] / length, diff[2] / length), (scalar_bound(f.bound) + scalar_bound(b.bound) + 2e-4) / length, False
+
+
+def directivity(table, orientation, w):
+    """D_b of the emission direction w for the table T[b][k] (K samples, sample k at k pi / (K - 1) from the orientation), in
+    float64 on the float32 values the library is given -> ([D_b], [|dD_b / dtheta|] of the interval, k)"""
+    f = [f32(x) for x in orientation]
+    fl = math.sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2])
+    f = [x / fl for x in f]
+    cx, cy, cz = w[1] * f[2] - w[2] * f[1], w[2] * f[0] - w[0] * f[2], w[0] * f[1] - w[1] * f[0]
+    theta = math.atan2(math.sqrt(cx * cx + cy * cy + cz * cz), w[0] * f[0] + w[1] * f[1] + w[2] * f[2])
+    K = len(table[0])
+    x = theta * (K - 1) / math.pi
+    k = min(int(math.floor(x)), K - 2)
+    t = x - k
+    D, slope = [], []
+    for row in table:
+        lo, hi = f32(row[k]), f32(row[k + 1])
+        D.append(lo + t * (hi - lo))
+        slope.append(abs(hi - lo) * (K - 1) / math.pi)
+    return D, slope, k
+
+
+def order_of(fwd, bwd):
+    """the ORDER of the path F0..Fi, Bj..B0: the number of its nodes that a walk step's hit made"""
+    return sum(n.arrive is not None for n in fwd) + sum(n.arrive is not None for n in bwd)
+
+
+class Applied:
+    """what a frame deposits for a source with a table, an orientation and an order window, by the model: H, count and deposits
+    over the contributions that are not flagged, whose order lies in the window and whose factor D is not fragile; flagged = the
+    frame's flagged contributions + d_flagged, the contributions left out for D alone; steps and connections are the frame's
+    (the descriptor changes no walk and no visibility query); walk_ray / connection_ray: how many of the deposits took which"""
+
+
+def apply_source(fr, table=None, orientation=(1.0, 0.0, 0.0), lo=0, hi=None, rtol=0.0, pair_range=None):
+    """A frame built with keep_pairs = True under a source descriptor, without walking again (the walks do not depend on it).
+    D_b is the last factor of a contribution's energy: after the clamp, the gain, 1 / pairs and the weight.  D is continuous in
+    the direction, so it adds no discrete decision, but where it is small and steep its relative error is large: a
+    contribution is left out (d_flagged) when |T[b][k+1] - T[b][k]| (K - 1) / pi x delta exceeds rtol / 4 x D_b in some band,
+    delta the direction's error (emission), rtol the tolerance the frame is judged with.  pair_range = (begin, end): those pairs
+    of the frame alone (flagged, steps and connections are then theirs)."""
+    assert fr.pairs, "the frame was built without keep_pairs"
+    a = Applied()
+    B, bins = len(fr.H), len(fr.H[0])
+    a.H = [[0.0] * bins for _ in range(B)]
+    a.count = [0] * bins
+    a.deposits = a.d_flagged = a.walk_ray = a.connection_ray = a.flagged = a.steps = a.connections = 0
+    for r in fr.pairs if pair_range is None else fr.pairs[pair_range[0]:pair_range[1]]:
+        a.steps += r.steps
+        if isinstance(r, PrefixPair):
+            a.connections += r.connections
+            items = [(r.fwd[:c.i + 1], r.bwd[:c.j + 1], c.visible, c.fragile, c.bin, c.energy) for c in r.contributions]
+        else:
+            a.connections += 1
+            items = [(r.fwd, r.bwd, r.visible, r.fragile, r.bin, r.energy)]
+        for fwd, bwd, visible, fragile, b, energy in items:
+            a.flagged += bool(fragile)
+            if not visible or fragile or not lo <= order_of(fwd, bwd) <= (math.inf if hi is None else hi):
+                continue
+            if table is not None:
+                w, delta, walked = emission(fwd, bwd[-1])
+                if w is None:
+                    a.d_flagged += 1
+                    continue
+                D, slope, _ = directivity(table, orientation, w)
+                if any(s * delta > 0.25 * rtol * d for s, d in zip(slope, D)):
+                    a.d_flagged += 1
+                    continue
+                energy = [e * d for e, d in zip(energy, D)]
+                a.walk_ray += walked
+                a.connection_ray += not walked
+            a.deposits += 1
+            a.count[b] += 1
+            for k in range(B):
+                a.H[k][b] += energy[k]
+    a.flagged += a.d_flagged
+    return a
+
+
 # ---- the test scene ------------------------------------------------------------------------------------------------------------------------
-SOURCE = (700.0, 600.0, 300.0)
+SOURCE =(700.0, 600.0, 300.0)
 LISTENER = (2300.0, 1400.0, 500.0)
 
 

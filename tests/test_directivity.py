@@ -72,8 +72,9 @@ def emission(lib, op, pair, fwd_nodes):
     return -1, None
 
 
-def restate(oracle_mod, osc, op, src, lis, table=None, fwd=(1.0, 0.0, 0.0), pairs=None, num_bins=1000, max_nodes=600):
-    """UpdateSource up to the deposit, pair by pair, with the directivity factor last; returns (e32, e64)"""
+def restate(oracle_mod, osc, op, src, lis, table=None, fwd=(1.0, 0.0, 0.0), pairs=None, num_bins=1000, max_nodes=600, pair_begin=0):
+    """UpdateSource up to the deposit, pair by pair, with the directivity factor last; returns (e32, e64).  The pairs
+    [pair_begin, pairs) are restated (pairs None: to the frame's last)"""
     lib, B = osc.lib, osc.B
     e32 = np.zeros((B, num_bins), np.float32)
     e64 = np.zeros((B, num_bins), np.float64)
@@ -82,7 +83,7 @@ def restate(oracle_mod, osc, op, src, lis, table=None, fwd=(1.0, 0.0, 0.0), pair
     allc = op.flags & (ALLC | MIS)
     D = op.depth
     assert D > 0 or not allc
-    for i in range(op.num_pairs if pairs is None else pairs):
+    for i in range(pair_begin, op.num_pairs if pairs is None else pairs):
         fw = osc.generate_path(op, i, 0, src, max_nodes)
         bw = osc.generate_path(op, i, 1, lis, max_nodes)
         assert len(fw) < max_nodes and len(bw) < max_nodes
@@ -117,10 +118,10 @@ def restate(oracle_mod, osc, op, src, lis, table=None, fwd=(1.0, 0.0, 0.0), pair
     return e32, e64
 
 
-def cardioid(bands, K=37):
+def cardioid(bands, K=37, floor=0.02):
     """a cardioid whose power rises with the band: narrower at high frequencies"""
     th = np.arange(K) * np.pi / (K - 1)
-    return np.stack([(0.5 * (1.0 + np.cos(th))) ** (1 + 1.5 * b) + 0.02 for b in range(bands)]).astype(np.float32)
+    return np.stack([(0.5 * (1.0 + np.cos(th))) ** (1 + 1.5 * b) + floor for b in range(bands)]).astype(np.float32)
 
 
 def cone(bands, K=181):

@@ -78,7 +78,7 @@ def expected(depth, roulette=True, cosine=False, pairs=1024):
     return fr
 
 
-def check_frame(pkg, ctx, src, fr, pairs, depth, roulette=True, flags=0, gain=GAIN, bands=4, rtol=ENERGY_RTOL):
+def check_frame(pkg, ctx, src, fr, pairs, depth, roulette=True, flags=0, gain=GAIN, bands=4, rtol=ENERGY_RTOL, two_sided=False, peak=1.0):
     """fr: a frame of the model, of one contribution per pair (rw.Frame: C = pairs) or of many (rw.PrefixFrame: C = the sum of
     (kf + 1)(km + 1)); nfr = its flagged contributions, each of which can only ADD one deposit of at most gain clamp / pairs (a
     weight is at most 1) somewhere"""
@@ -86,10 +86,20 @@ def check_frame(pkg, ctx, src, fr, pairs, depth, roulette=True, flags=0, gain=GA
     ctx.reset_stats()
     G = ctx.compute_energy_response(src, p).astype(np.float64)
     st = ctx.stats()
-    nfr = flagged_contributions(fr)
     assert st["segments"] == st["planned_segments"] == fr.steps
     assert st["connections_tested"] == fr.connections
-    assert abs(st["deposits"] - fr.deposits) <= nfr, (st["deposits"], fr.deposits, nfr)
+    check_histogram(G, st["deposits"], fr, pairs, flags=flags, gain=gain, bands=bands, rtol=rtol, two_sided=two_sided, peak=peak,
+                    what=f"pairs {pairs} depth {depth} roulette {roulette} flags {flags}")
+
+
+def check_histogram(G, deposits, fr, pairs, flags=0, gain=GAIN, bands=4, rtol=ENERGY_RTOL, two_sided=False, peak=1.0, what=""):
+    """check_frame's rule for a histogram G and a deposit count that the caller got from the library (one source of a batched frame:
+    deposits None, the counters are the batch's).  two_sided: the frame has an order window, where a flagged contribution whose
+    hit count the library and the model disagree on can also take a deposit away: the cap applies to |R| (tests/test_order_window.py).
+    peak: the largest gain of the source's directivity table where it exceeds 1 (the table's factor comes after the clamp)"""
+    nfr = flagged_contributions(fr)
+    if deposits is not None:
+        assert abs(deposits - fr.deposits) <= nfr, (deposits, fr.deposits, nfr)
     H = np.asarray(fr.H, np.float64)[:bands] * (gain / GAIN)           # (the gain is the last factor of a deposit: H is linear in it)
     allow = rtol * H + 1e-30
     if flags & DET:   # every deposit is rounded to the nearest multiple of 2^-40 (include/frequensee.h): half a quantum each
@@ -98,11 +108,14 @@ def check_frame(pkg, ctx, src, fr, pairs, depth, roulette=True, flags=0, gain=GA
     bad = np.abs(R) > allow
     ok = ~bad & (H > 0.0)
     worst = float((np.abs(R)[ok] / H[ok]).max()) if ok.any() else 0.0
-    print(f"pairs {pairs} depth {depth} roulette {roulette} flags {flags}: flagged {nfr} deposits {st['deposits']} / {fr.deposits} "
+    print(f"{what}: flagged {nfr} deposits {deposits} / {fr.deposits} "
           f"bad bins {int(bad.any(axis=0).sum())} worst relative difference {worst:.3e}")
     assert bad.any(axis=0).sum() <= nfr, np.flatnonzero(bad.any(axis=0))
-    cap = nfr * gain * 1.0 / pairs * (1.0 + 1e-5)
-    assert ((R[bad] > 0.0) & (R[bad] <= cap)).all(), (R[bad], cap)
+    cap = nfr * gain * 1.0 / pairs * (1.0 + 1e-5) * peak
+    if two_sided:
+        assert (np.abs(R[bad]) <= cap).all(), (R[bad], cap)
+    else:
+        assert ((R[bad] > 0.0) & (R[bad] <= cap)).all(), (R[bad], cap)
     assert G.sum() > 0.0
 
 

@@ -332,6 +332,13 @@ MODES = {
     "lobes_cosine": (LOBES | COSINE, 2.3e-4),   # 5.89e-5: depth 8, seed 202
 }
 
+# (mode (None: end to end), depth) -> the tolerance of its frames with a directivity table, where the mode's own does not do: 4 x the
+# largest relative difference per (pair, band, bin) between the model and the oracle-built restatement with a table that
+# tests/test_restatement_sources.py measures on the CPU (a mode and depth without an entry stayed within a quarter of its tolerance)
+DIRECTIONAL_RTOL = {
+    (None, 8): 2.2e-4,     # 5.28e-5: end to end, depth 8, 1 024 pairs, seed 101, the two-sample table (5.2e-5 without a table)
+}
+
 
 def mode_rtol(mode):
     return MODES[mode][1]
@@ -373,7 +380,7 @@ def mode_frame(mode, depth, roulette, seed, num_pairs=1024, gain=10.0, keep_pair
 
 
 def flagged_contributions(fr):
-    return fr.flagged if isinstance(fr, rw.PrefixFrame) else len(fr.flagged)
+    return fr.flagged if isinstance(fr.flagged, int) else len(fr.flagged)      # (rw.PrefixFrame and rw.Applied count, rw.Frame lists)
 
 
 def test_strategy_counts_by_hand():
