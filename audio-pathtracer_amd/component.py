@@ -674,6 +674,65 @@ class Context:
         self.check(self.lib.fs_hrtf_info(self.h, C.byref(n), C.byref(H)))
         return n.value, H.value
 
+    @staticmethod
+    def hrtf_triangulate(dirs):
+        """fs_hrtf_triangulate: tri [2n - 4][3] int32, the convex hull of dirs [n][3] as a mesh fs_hrtf_mesh_rows accepts (host only)"""
+        d = np.ascontiguousarray(dirs, dtype=np.float32)
+        if d.ndim != 2 or d.shape[1] != 3:
+            raise ValueError("dirs must be [n][3]")
+        n = d.shape[0]
+        tri = np.zeros((max(2 * n - 4, 0), 3), np.int32)
+        m = C.c_int32(0)
+        rc = _capi.load().fs_hrtf_triangulate(d.ctypes.data if d.size else None, n, tri.ctypes.data if tri.size else None, tri.shape[0], C.byref(m))
+        if rc != _capi.OK:
+            raise FrequenSeeError(rc, "fs_hrtf_triangulate: 4 .. 4096 finite, distinct directions that surround the origin")
+        return tri[:m.value]
+
+    @staticmethod
+    def hrtf_mesh_rows(dirs, tri):
+        """fs_hrtf_mesh_rows: rows [m][3][3] float32 of the mesh tri [m][3] on dirs [n][3] — r_i . d are the coefficients of d in
+        the triangle's corners; raises where the mesh is refused (host only)"""
+        d = np.ascontiguousarray(dirs, dtype=np.float32)
+        t = np.ascontiguousarray(tri, dtype=np.int32)
+        if d.ndim != 2 or d.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("dirs must be [n][3] and tri [m][3]")
+        rows = np.zeros((t.shape[0], 3, 3), np.float32)
+        rc = _capi.load().fs_hrtf_mesh_rows(d.ctypes.data if d.size else None, d.shape[0], t.ctypes.data if t.size else None, t.shape[0],
+                                            rows.ctypes.data if rows.size else None)
+        if rc != _capi.OK:
+            raise FrequenSeeError(rc, "fs_hrtf_mesh_rows: not a closed, outward-facing triangulation of 2n - 4 triangles on all n directions")
+        return rows
+
+    @staticmethod
+    def hrtf_mesh_locate(rows, direction):
+        """fs_hrtf_mesh_locate: (t, b [3] float32) — the triangle a direction falls in and its weights, the bits the device computes"""
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        d = np.ascontiguousarray(direction, dtype=np.float32).reshape(-1)
+        if r.ndim != 3 or r.shape[1:] != (3, 3) or d.shape[0] != 3:
+            raise ValueError("rows must be [m][3][3] and direction hold three components")
+        t, b = C.c_int32(-1), np.zeros(3, np.float32)
+        rc = _capi.load().fs_hrtf_mesh_locate(r.ctypes.data if r.size else None, r.shape[0], d.ctypes.data, C.byref(t), b.ctypes.data)
+        if rc != _capi.OK:
+            raise FrequenSeeError(rc, "fs_hrtf_mesh_locate: at least one triangle")
+        return t.value, b
+
+    def hrtf_set_mesh(self, tri):
+        """fs_hrtf_set_mesh: tri [m][3] on the set in force, validated as fs_hrtf_mesh_rows does; None clears the mesh.  Not
+        concurrent with a callback; every held binaural voice starts anew afterwards"""
+        if tri is None:
+            self.check(self.lib.fs_hrtf_set_mesh(self.h, None, 0))
+            return
+        t = np.ascontiguousarray(tri, dtype=np.int32)
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("tri must be [m][3]")
+        self.check(self.lib.fs_hrtf_set_mesh(self.h, t.ctypes.data if t.size else None, t.shape[0]))
+
+    def hrtf_mesh_info(self):
+        """the triangles of the mesh in force, 0 without one"""
+        m = C.c_int32(-1)
+        self.check(self.lib.fs_hrtf_mesh_info(self.h, C.byref(m)))
+        return m.value
+
     def binaural_render_init(self, src, frame_size=1024, taps=255, voices=32, max_delay_seconds=1.0):
         self.check(self.lib.fs_binaural_render_init(self.h, src, int(frame_size), int(taps), int(voices), float(max_delay_seconds)))
         self._br_frame = getattr(self, "_br_frame", {})
@@ -1506,12 +1565,16 @@ class FrequenSeeAudioBinauralPlugin(FrequenSeeAudioReflectionPlugin):
 
     DirectKey = _capi.BINAURAL_DIRECT_KEY   # a first-order key (a triangle index) no scene of fewer than 2^29 - 1 triangles uses
 
-    def SetHrtf(self, dirs=None, hrir=None, directions=1024, taps=128):
+    def SetHrtf(self, dirs=None, hrir=None, directions=1024, taps=128, interpolate=False):
         """the context's HRIR set: dirs [n][3] (head frame: x forward, y right, z up) and hrir [n][2][H], or the spherical-head
-        model of `directions` and `taps`.  Before OnInitSource; not concurrent with ProcessAudio"""
+        model of `directions` and `taps`.  interpolate: triangulate the set and install the mesh (fs_hrtf_set_mesh) — every
+        voice's HRIR is then the blend of the three round its direction, not the nearest one.  Before OnInitSource; not
+        concurrent with ProcessAudio"""
         if dirs is None:
             dirs, hrir = Context.hrtf_spherical_head(self.ctx.cfg.sample_rate, directions, taps)
         self.ctx.hrtf_set(dirs, hrir)
+        if interpolate:
+            self.ctx.hrtf_set_mesh(Context.hrtf_triangulate(dirs))
 
     def OnInitSource(self, component: FrequenSeeAudioComponent):
         self.ctx.binaural_render_init(component._src, self.FrameSize, self.Taps, self.VoiceCount, self.MaxDelaySeconds)

@@ -1,9 +1,13 @@
 // fs_capi_binaural_render.cpp — binaural voices on the audio thread: the HRIR set of the context (fs_hrtf_set / fs_hrtf_info), a
-// set for hosts that have none (fs_hrtf_spherical_head, host only), and what the renderer is beyond its voice bank
+// set for hosts that have none (fs_hrtf_spherical_head, host only), the mesh on the set that turns the nearest direction into a
+// blend of three (fs_hrtf_triangulate, fs_hrtf_mesh_rows, fs_hrtf_mesh_locate: host only; fs_hrtf_set_mesh / fs_hrtf_mesh_info),
+// and what the renderer is beyond its voice bank
 // (fs_capi_voice_bank.hpp: the callback; fs_capi_reflect_render.cpp: the set-up and its release): the refusals that name the
 // set, an entry's gain and direction, the list of sounding slots and the folded tables of fs_binaural_render.hip's launches.
 // The band kernels and their per-context cache are the direct renderer's (fs_capi_direct_render.cpp).  The reference has no slot
 // for it.
+#include <algorithm>
+
 #include "fs_capi_voice_bank.hpp"
 
 static_assert(sizeof(fs_binaural_voice) == 56, "fs_binaural_voice: the key, the delay, the bands, the gain, the direction");
@@ -36,6 +40,149 @@ void head_taps(double theta, double a_over_c, double fs, int H, double* h) {
         else g = -a1 * g_prev;
         h[k] = (1.0 - f) * g + f * g_prev;
     }
+}
+
+// ---- the mesh on a set: the header's "fs_hrtf_mesh_rows" clauses, in double from the float directions as given.  True: the mesh
+// is accepted and rows [m][3][3] (when not null) holds r_0, r_1, r_2 of every triangle, each component rounded to float once.
+bool mesh_rows(const float* dirs, int n, const int32_t* tri, int m, float* rows) {
+    if (!dirs || !tri || n < 4 || n > FS_MAX_HRTF_DIRECTIONS || m != 2 * n - 4) return false;
+    std::vector<int64_t> edges((size_t)m * 3);
+    std::vector<char> used((size_t)n, 0);
+    for (int j = 0; j < m; ++j) {
+        const int32_t* t = tri + (size_t)j * 3;
+        for (int i = 0; i < 3; ++i)
+            if (t[i] < 0 || t[i] >= n) return false;
+        if (t[0] == t[1] || t[1] == t[2] || t[2] == t[0]) return false;
+        for (int i = 0; i < 3; ++i) {
+            used[(size_t)t[i]] = 1;
+            edges[(size_t)j * 3 + (size_t)i] = (int64_t)t[i] * n + t[(i + 1) % 3];
+        }
+    }
+    for (int k = 0; k < n; ++k)
+        if (!used[(size_t)k]) return false;
+    std::sort(edges.begin(), edges.end());
+    if (std::adjacent_find(edges.begin(), edges.end()) != edges.end()) return false;   // a directed edge in two triangles
+    for (const int64_t e : edges)
+        if (!std::binary_search(edges.begin(), edges.end(), (e % n) * n + e / n)) return false;   // ... or without its reverse
+    std::vector<float> out(rows ? (size_t)m * 9 : 0);
+    for (int j = 0; j < m; ++j) {
+        double p[3][3];
+        for (int i = 0; i < 3; ++i)
+            for (int c = 0; c < 3; ++c) p[i][c] = (double)dirs[(size_t)tri[(size_t)j * 3 + (size_t)i] * 3 + (size_t)c];
+        double x[3][3];   // x[i] = p[i + 1] x p[i + 2]
+        for (int i = 0; i < 3; ++i) {
+            const double* a = p[(i + 1) % 3];
+            const double* b = p[(i + 2) % 3];
+            x[i][0] = a[1] * b[2] - a[2] * b[1];
+            x[i][1] = a[2] * b[0] - a[0] * b[2];
+            x[i][2] = a[0] * b[1] - a[1] * b[0];
+        }
+        const double det = p[0][0] * x[0][0] + p[0][1] * x[0][1] + p[0][2] * x[0][2];
+        if (!(det >= 1e-6) || !std::isfinite(det)) return false;
+        if (rows)
+            for (int i = 0; i < 3; ++i)
+                for (int c = 0; c < 3; ++c) out[((size_t)j * 3 + (size_t)i) * 3 + (size_t)c] = (float)(x[i][c] / det);
+    }
+    if (rows) std::memcpy(rows, out.data(), sizeof(float) * out.size());
+    return true;
+}
+
+// The convex hull of n points in double, incrementally with brute-force visibility: a tetrahedron of four points far apart, then
+// every other point in index order — the faces whose plane it lies above by more than kHullEps go, and the rim they leave (the
+// directed edges whose reverse is not among them) is joined to the point.  A point within kHullEps of a face's plane leaves the
+// face in place and extends its facet in that plane: co-circular directions (a lat-long grid, a cube) split their facet one way or
+// another.  tri [2n - 4][3]; false when no tetrahedron is found or the faces do not come to 2n - 4 (mesh_rows judges the rest).
+constexpr double kHullEps = 1e-12;
+struct HullFace { int v[3]; double n[3], off; };   // unit normal, n . x = off on the plane
+bool hull_face(const double* pts, int a, int b, int c, HullFace* f) {
+    const double *pa = pts + 3 * (size_t)a, *pb = pts + 3 * (size_t)b, *pc = pts + 3 * (size_t)c;
+    const double u[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]}, w[3] = {pc[0] - pa[0], pc[1] - pa[1], pc[2] - pa[2]};
+    double nx = u[1] * w[2] - u[2] * w[1], ny = u[2] * w[0] - u[0] * w[2], nz = u[0] * w[1] - u[1] * w[0];
+    const double len = std::sqrt(nx * nx + ny * ny + nz * nz);
+    if (!(len > 0.0)) return false;
+    nx /= len; ny /= len; nz /= len;
+    *f = {{a, b, c}, {nx, ny, nz}, nx * pa[0] + ny * pa[1] + nz * pa[2]};
+    return true;
+}
+inline double hull_height(const HullFace& f, const double* p) { return f.n[0] * p[0] + f.n[1] * p[1] + f.n[2] * p[2] - f.off; }
+bool convex_hull(const double* pts, int n, int32_t* tri) {
+    auto dist2 = [&](int a, int b) {
+        double s = 0.0;
+        for (int c = 0; c < 3; ++c) { const double d = pts[3 * (size_t)a + c] - pts[3 * (size_t)b + c]; s += d * d; }
+        return s;
+    };
+    int i0 = 0, i1 = 0, i2 = -1, i3 = -1;
+    for (int k = 1; k < n; ++k)
+        if (dist2(0, k) > dist2(0, i1)) i1 = k;
+    if (i1 == 0) return false;
+    double best = 0.0;
+    HullFace f;
+    for (int k = 0; k < n; ++k) {   // the widest triangle on (i0, i1)
+        if (k == i0 || k == i1 || !hull_face(pts, i0, i1, k, &f)) continue;
+        const double *pa = pts + 3 * (size_t)i0, *pb = pts + 3 * (size_t)i1, *pc = pts + 3 * (size_t)k;
+        const double u[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]}, w[3] = {pc[0] - pa[0], pc[1] - pa[1], pc[2] - pa[2]};
+        const double cx = u[1] * w[2] - u[2] * w[1], cy = u[2] * w[0] - u[0] * w[2], cz = u[0] * w[1] - u[1] * w[0];
+        const double area2 = cx * cx + cy * cy + cz * cz;
+        if (area2 > best) { best = area2; i2 = k; }
+    }
+    if (i2 < 0 || !(best > 1e-12) || !hull_face(pts, i0, i1, i2, &f)) return false;
+    best = 0.0;
+    for (int k = 0; k < n; ++k) {   // the point farthest from its plane
+        const double h = std::fabs(hull_height(f, pts + 3 * (size_t)k));
+        if (h > best) { best = h; i3 = k; }
+    }
+    if (i3 < 0 || !(best > 1e-9)) return false;   // (all in one plane: a great circle)
+    if (hull_height(f, pts + 3 * (size_t)i3) > 0.0) std::swap(i1, i2);   // (i0, i1, i2) seen counter-clockwise from outside: i3 below
+    std::vector<HullFace> faces;
+    faces.reserve((size_t)2 * (size_t)n);
+    const int first[4][3] = {{i0, i1, i2}, {i0, i3, i1}, {i1, i3, i2}, {i2, i3, i0}};
+    for (const auto& t : first) {
+        if (!hull_face(pts, t[0], t[1], t[2], &f)) return false;
+        faces.push_back(f);
+    }
+    std::vector<int64_t> rim, gone;
+    for (int k = 0; k < n; ++k) {
+        if (k == i0 || k == i1 || k == i2 || k == i3) continue;
+        const double* p = pts + 3 * (size_t)k;
+        gone.clear();
+        size_t kept = 0;
+        for (size_t j = 0; j < faces.size(); ++j) {
+            if (hull_height(faces[j], p) > kHullEps) {
+                for (int i = 0; i < 3; ++i) gone.push_back((int64_t)faces[j].v[i] * n + faces[j].v[(i + 1) % 3]);
+            } else {
+                faces[kept++] = faces[j];
+            }
+        }
+        if (gone.empty()) continue;   // inside or on the hull so far: left out (a duplicate; mesh_rows will miss it)
+        faces.resize(kept);
+        std::sort(gone.begin(), gone.end());
+        rim.clear();
+        for (const int64_t e : gone)
+            if (!std::binary_search(gone.begin(), gone.end(), (e % n) * n + e / n)) rim.push_back(e);
+        for (const int64_t e : rim) {
+            if (!hull_face(pts, (int)(e / n), (int)(e % n), k, &f)) return false;
+            faces.push_back(f);
+        }
+    }
+    if (faces.size() != (size_t)(2 * n - 4)) return false;
+    for (size_t j = 0; j < faces.size(); ++j)
+        for (int i = 0; i < 3; ++i) tri[j * 3 + (size_t)i] = faces[j].v[i];
+    return true;
+}
+
+// what fs_hrtf_set and fs_hrtf_set_mesh do to the voices: every held slot is free, on both copies of the slot tables; the rings and
+// the counters stay.  The host's copies — what the matching reads, so every voice starts — all go first, and a failed clear of a
+// device copy (which a start overwrites anyway) is reported only after every source has had its turn.
+hipError_t free_binaural_slots(fs_context* ctx) {
+    for (Source* s : ctx->sources)
+        if (s && s->alive && s->br.r.d) s->br.free_slots();
+    hipError_t clear_err = hipSuccess;
+    for (Source* s : ctx->sources) {
+        if (!s || !s->alive || !s->br.r.d) continue;
+        const hipError_t e = hipMemsetAsync(s->br.r.d + offsetof(BinauralRenderState, slot), 0, sizeof(BinauralRenderState::slot), ctx->rev_stream);
+        if (e != hipSuccess && clear_err == hipSuccess) clear_err = e;
+    }
+    return clear_err;
 }
 
 }  // namespace
@@ -104,18 +251,78 @@ int fs_hrtf_set(fs_context* ctx, const fs_hrtf_desc* d) {
     ctx->d_hrtf = fresh;
     ctx->hrtf_dirs = d ? d->directions : 0;
     ctx->hrtf_taps = d ? d->taps : 0;
-    // Every held slot is free, on both copies of the slot tables; the rings and the counters stay.  The set is in force from here
-    // on, so no source is left out: the host's copies — what the matching reads, so every voice starts — all go first, and a
-    // failed clear of a device copy (which a start overwrites anyway) is reported only after every source has had its turn.
-    for (Source* s : ctx->sources)
-        if (s && s->alive && s->br.r.d) s->br.free_slots();
-    hipError_t clear_err = hipSuccess;
-    for (Source* s : ctx->sources) {
-        if (!s || !s->alive || !s->br.r.d) continue;
-        const hipError_t e = hipMemsetAsync(s->br.r.d + offsetof(BinauralRenderState, slot), 0, sizeof(BinauralRenderState::slot), ctx->rev_stream);
-        if (e != hipSuccess && clear_err == hipSuccess) clear_err = e;
-    }
+    if (d) ctx->hrtf_dirs_host.assign(d->dirs, d->dirs + n_dir); else ctx->hrtf_dirs_host.clear();
+    if (ctx->d_hrtf_mesh) (void)hipFree(ctx->d_hrtf_mesh);   // a mesh is of the set it was given for
+    ctx->d_hrtf_mesh = nullptr;
+    ctx->hrtf_tris = 0;
+    // The set is in force from here on, so no source is left out
+    const hipError_t clear_err = free_binaural_slots(ctx);
     if (clear_err != hipSuccess) return ctx->hip_fail(clear_err, "fs_hrtf_set (clearing the slots)");
+    return FS_OK;
+}
+
+int fs_hrtf_triangulate(const float* dirs, int32_t n, int32_t* tri, int32_t cap, int32_t* m) {
+    if (!dirs || !tri || !m || n < 4 || n > FS_MAX_HRTF_DIRECTIONS || cap < 2 * n - 4) return FS_ERR_INVALID_ARGUMENT;
+    std::vector<double> pts((size_t)n * 3);
+    for (size_t k = 0; k < pts.size(); ++k) {
+        if (!std::isfinite(dirs[k])) return FS_ERR_INVALID_ARGUMENT;
+        pts[k] = (double)dirs[k];
+    }
+    std::vector<int32_t> faces((size_t)(2 * n - 4) * 3);
+    if (!convex_hull(pts.data(), n, faces.data()) || !mesh_rows(dirs, n, faces.data(), 2 * n - 4, nullptr)) return FS_ERR_INVALID_ARGUMENT;
+    std::memcpy(tri, faces.data(), sizeof(int32_t) * faces.size());
+    *m = 2 * n - 4;
+    return FS_OK;
+}
+
+int fs_hrtf_mesh_rows(const float* dirs, int32_t n, const int32_t* tri, int32_t m, float* rows) {
+    return mesh_rows(dirs, n, tri, m, rows) ? FS_OK : FS_ERR_INVALID_ARGUMENT;
+}
+
+int fs_hrtf_mesh_locate(const float* rows, int32_t m, const float d[3], int32_t* t, float b[3]) {
+    if (!rows || !d || !t || !b || m < 1) return FS_ERR_INVALID_ARGUMENT;
+    const HrtfMeshRowsHost r = {rows};
+    const HrtfMeshBest best = hrtf_mesh_scan(r, m, d, 0, 1);
+    *t = best.j;
+    hrtf_mesh_weights(r, best.j, d, b);
+    return FS_OK;
+}
+
+int fs_hrtf_set_mesh(fs_context* ctx, const int32_t* tri, int32_t m) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    if (ctx->hrtf_dirs == 0) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_hrtf_set_mesh: no HRIR set in force (fs_hrtf_set)");
+    const bool clear = !tri || m == 0;
+    std::vector<float4> block;
+    if (!clear) {
+        std::vector<float> rows((size_t)(m > 0 ? m : 0) * 9);
+        if (m < 0 || !mesh_rows(ctx->hrtf_dirs_host.data(), ctx->hrtf_dirs, tri, m, rows.data()))
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_hrtf_set_mesh: not a closed, outward-facing triangulation of the set's directions (fs_hrtf_mesh_rows)");
+        block.resize((size_t)m * 3);
+        for (size_t k = 0; k < block.size(); ++k) {
+            float4& q = block[k];
+            q.x = rows[k * 3]; q.y = rows[k * 3 + 1]; q.z = rows[k * 3 + 2];
+            const uint32_t v = (uint32_t)tri[k];
+            std::memcpy(&q.w, &v, sizeof(v));
+        }
+    }
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    float4* fresh = nullptr;
+    if (!clear) FS_HIP(ctx, hipMalloc((void**)&fresh, sizeof(float4) * block.size()));   // (a failure here has changed nothing)
+    hipError_t err = hipStreamSynchronize(ctx->rev_stream);   // no callback reads the old mesh any more
+    if (err == hipSuccess && !clear) err = hipMemcpy(fresh, block.data(), sizeof(float4) * block.size(), hipMemcpyHostToDevice);
+    if (err != hipSuccess) { if (fresh) (void)hipFree(fresh); return ctx->hip_fail(err, "fs_hrtf_set_mesh (upload)"); }
+    if (ctx->d_hrtf_mesh) (void)hipFree(ctx->d_hrtf_mesh);
+    ctx->d_hrtf_mesh = fresh;
+    ctx->hrtf_tris = clear ? 0 : m;
+    const hipError_t clear_err = free_binaural_slots(ctx);   // nothing ramps from an index of the other mode
+    if (clear_err != hipSuccess) return ctx->hip_fail(clear_err, "fs_hrtf_set_mesh (clearing the slots)");
+    return FS_OK;
+}
+
+int fs_hrtf_mesh_info(fs_context* ctx, int32_t* triangles) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (triangles) *triangles = ctx->hrtf_tris;
     return FS_OK;
 }
 
@@ -147,6 +354,7 @@ int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, 
     static const VoiceBankRenderer<BinauralRenderBatch> q = {&Source::br, &fs_context::br_stage, "fs_binaural_render_init has not been called for this source",
                                                              "fs_binaural_render_process_batch: no HRIR set in force (fs_hrtf_set)", launch_binaural_render, kVoiceBankHeader};
     const int H = ctx ? ctx->hrtf_taps : 0;
+    const bool mesh = ctx && ctx->hrtf_tris > 0;
     return voice_bank_process(
         q, ctx, sources, count, in, voices, voice_counts, stride, out, mix, rows,
         [&](const fs_binaural_voice& v) {
@@ -163,9 +371,11 @@ int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, 
             return (int)FS_OK;
         },
         // the sounding slots' list | the folded tables (sized by the rows' slots, not by how many sound in this call: a shape
-        // allocates once)
+        // allocates once), with a mesh followed by its plans and what the locate pass finds, [count][kVoiceSlots] each
         [&](size_t slots, const RenderSetup& shape) {
-            return std::array<size_t, 3>{sizeof(uint16_t) * slots, sizeof(float2) * slots * 2 * (size_t)(shape.taps + H - 1), 2 * (size_t)shape.frame};
+            const size_t folded = sizeof(float2) * slots * 2 * (size_t)(shape.taps + H - 1);
+            const size_t located = mesh ? (sizeof(BinauralMeshPlan) + sizeof(float4)) * (size_t)count * kVoiceSlots : 0;
+            return std::array<size_t, 3>{sizeof(uint16_t) * slots, (folded + 15) / 16 * 16 + located, 2 * (size_t)shape.frame};
         },
         [&](BinauralRenderBatch& b, BinauralRenderItem* items, char* h_sounding, char* d_sounding, char* d_folded) {
             uint16_t* sounding = (uint16_t*)h_sounding;
@@ -180,6 +390,15 @@ int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, 
             b.hrir = ctx->d_hrtf + (size_t)ctx->hrtf_dirs * 3;
             b.n_dirs = ctx->hrtf_dirs; b.h_taps = H;
             b.tc = b.taps + H - 1;
+            if (mesh) {
+                size_t slots = 0;
+                for (int i = 0; i < b.count; ++i) slots += (size_t)items[i].slots;
+                char* behind = d_folded + (sizeof(float2) * slots * 2 * (size_t)b.tc + 15) / 16 * 16;
+                b.mesh_plans = (BinauralMeshPlan*)behind;
+                b.located = (float4*)(behind + sizeof(BinauralMeshPlan) * (size_t)b.count * kVoiceSlots);
+                b.mesh = ctx->d_hrtf_mesh;
+                b.n_tris = ctx->hrtf_tris;
+            }
         });
 }
 

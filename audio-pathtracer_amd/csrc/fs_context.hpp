@@ -409,7 +409,8 @@ struct fs_context {
     // rr_stage (fs_reflection_render_process_batch): up, items [count] | voices [count][stride]; scratch, the counters [count] |
     //   the plans [count][FS_MAX_REFLECTION_VOICES]
     // br_stage (fs_binaural_render_process_batch): up, items [count] | voices [count][stride] | the sounding slots' list; scratch,
-    //   the counters [count] | the plans [count][FS_MAX_REFLECTION_VOICES] | the folded tables [sum of the rows' V][2][Tc]
+    //   the counters [count] | the plans [count][FS_MAX_REFLECTION_VOICES] | the folded tables [sum of the rows' V][2][Tc], with a
+    //   mesh in force followed by its wider plans and what the locate pass finds, [count][FS_MAX_REFLECTION_VOICES] each
     // ar_stage (fs_ambisonic_render_process_batch): rr_stage's blocks, with plans of 256 bytes and out [count][C frame] | mix [C frame]
     // sf_stage (fs_reverb_soundfield_process_batch): up, items [count] | plain, fade, take lists [3][count]; out [count][C frame] |
     //   mix [C frame]
@@ -417,6 +418,11 @@ struct fs_context {
     // the HRIR set in force (fs_hrtf_set; the audio thread's): one device block, dirs [n][3] | hrir [n][2][H]; n == 0: none
     float* d_hrtf = nullptr;
     int hrtf_dirs = 0, hrtf_taps = 0;
+    // ... the host's copy of its directions (what fs_hrtf_set_mesh validates against), and the mesh on it (fs_hrtf_set_mesh; dropped
+    // by every fs_hrtf_set): one device block [m][3] float4 {row r_i of the triangle, the bits of its corner v_i}; m == 0: none
+    std::vector<float> hrtf_dirs_host;
+    float4* d_hrtf_mesh = nullptr;
+    int hrtf_tris = 0;
     // the partitioned engine's twiddles, W[k] = exp(-2 pi i k / N), k < N / 2, per n = log2 N <= 12: built by the first
     // fs_reverb_init that needs the size, freed with the context
     float2* d_rev_tw[13] = {};

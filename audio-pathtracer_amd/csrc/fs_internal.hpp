@@ -890,7 +890,68 @@ struct BinauralRenderPlan {
     int32_t pad;
 };
 static_assert(sizeof(BinauralRenderPlan) == 96, "BinauralRenderPlan: twenty-four words");
+// The mesh on the HRIR set in force (fs_hrtf_set_mesh): the header's locate rule, to the bit, for the host (fs_hrtf_mesh_locate)
+// and the device (the locate pass) alike — every operation fp32, rounded on its own, in the order written.  Rows r_0, r_1, r_2 of
+// triangle j come through `rows(j, i)`: the host reads the caller's [m][3][3], the device the mesh
+// block's [m][3] float4 {r_i.x, r_i.y, r_i.z, the bits of corner v_i}: a lane's triangle is three 16-byte requests, and a wave's 64
+// triangles are 3 KiB in one piece.
+struct HrtfMeshBest { float mu; int j; };
+struct HrtfMeshRow { float x, y, z; };
+struct HrtfMeshRowsHost {
+    const float* rows;   // [m][3][3]
+    __host__ __device__ HrtfMeshRow operator()(int j, int i) const {
+        const float* r = rows + ((size_t)j * 3 + (size_t)i) * 3;
+        return {r[0], r[1], r[2]};
+    }
+};
+struct HrtfMeshRowsDevice {
+    const float4* mesh;  // [m][3]
+    __host__ __device__ HrtfMeshRow operator()(int j, int i) const {
+        const float4 q = mesh[(size_t)j * 3 + (size_t)i];
+        return {q.x, q.y, q.z};
+    }
+};
+__host__ __device__ inline float hrtf_mesh_g(const HrtfMeshRow& r, const float* d) { return (d[0] * r.x + d[1] * r.y) + d[2] * r.z; }
+// does a replace b as the best triangle: the larger mu, among equals the lower index
+__host__ __device__ inline bool hrtf_mesh_better(const HrtfMeshBest& a, const HrtfMeshBest& b) {
+    return a.mu > b.mu || (a.mu == b.mu && a.j < b.j);
+}
+// steps 1 and 2 over triangles first, first + step, ... < m, from best = (-infinity, 0): the host walks all of them (0, 1), lane l
+// of a wave every 64th (l, 64); hrtf_mesh_better merges the lanes' answers into the host's — a mu that is not a number is never taken
+template <typename Rows>
+__host__ __device__ inline HrtfMeshBest hrtf_mesh_scan(const Rows& rows, int m, const float* d, int first, int step) {
+    HrtfMeshBest best = {-INFINITY, 0};
+#pragma unroll 4   // (the device: four triangles' rows in flight per lane; the comparisons stay in ascending j)
+    for (int j = first; j < m; j += step) {
+        const float g0 = hrtf_mesh_g(rows(j, 0), d), g1 = hrtf_mesh_g(rows(j, 1), d), g2 = hrtf_mesh_g(rows(j, 2), d);
+        float mu = g0;
+        if (g1 < mu) mu = g1;
+        if (g2 < mu) mu = g2;
+        if (mu > best.mu) { best.mu = mu; best.j = j; }   // (ascending j: an equal later one does not replace it)
+    }
+    return best;
+}
+// step 3 for triangle t
+template <typename Rows>
+__host__ __device__ inline void hrtf_mesh_weights(const Rows& rows, int t, const float* d, float* b) {
+    const float g0 = hrtf_mesh_g(rows(t, 0), d), g1 = hrtf_mesh_g(rows(t, 1), d), g2 = hrtf_mesh_g(rows(t, 2), d);
+    const float c0 = g0 > 0.0f ? g0 : 0.0f, c1 = g1 > 0.0f ? g1 : 0.0f, c2 = g2 > 0.0f ? g2 : 0.0f;
+    const float s = (c0 + c1) + c2;
+    if (s > 0.0f) { b[0] = c0 / s; b[1] = c1 / s; b[2] = c2 / s; }
+    else { b[0] = 1.0f; b[1] = 0.0f; b[2] = 0.0f; }
+}
+// With a mesh in force a slot's q0, pad[3] hold t0 and the bits of b0[3] (BinauralRenderSlot keeps its layout), and the plan is a
+// wider record: BinauralRenderPlan's twenty-four words (q0, q1 unused), then the triangles and weights the callback fades between.
+struct BinauralMeshPlan : BinauralRenderPlan {
+    int32_t t0, t1;
+    float b0[3], b1[3];
+};
+static_assert(sizeof(BinauralMeshPlan) == 128, "BinauralMeshPlan: thirty-two words");
 struct BinauralRenderBatch {
+    const float4* mesh;                 // the mesh in force: [n_tris][3] {r_i, corner v_i}; null: nearest mode, and the three below unused
+    int n_tris;
+    float4* located;                    // [count][kVoiceSlots] scratch: {the bits of t1, b1[3]} of every slot with an entry
+    BinauralMeshPlan* mesh_plans;       // [count][kVoiceSlots] scratch: in `plans`' place
     const BinauralRenderItem* items;    // [count]
     const fs_binaural_voice* voices;    // [count][stride]
     const uint16_t* sounding;           // [n_sounding]: row * kVoiceSlots + slot of every sounding slot, rows then slots ascending
@@ -906,7 +967,8 @@ struct BinauralRenderBatch {
     float* out;                         // [count][2 * frame] interleaved
     float* mix;                         // [2 * frame], or null
 };
-// the plan pass, the fold of the HRIRs into the band FIRs, the render pass (which also appends the blocks to the rings), the mix (when b.mix)
+// (with b.mesh: the locate pass,) the plan pass, the fold of the HRIRs into the band FIRs, the render pass (which also appends the
+// blocks to the rings), the mix (when b.mix)
 void launch_binaural_render(const BinauralRenderBatch& b, hipStream_t s);
 // fs_ambisonic_render.hip (the ambisonic-voice callback): a voice carries the gains of the C = (order + 1)^2 channels of an
 // ambisonic bus, ACN order and SN3D normalisation, up to order 3.  A source's state block is a VoiceBankState of 128-byte slots,

@@ -775,9 +775,10 @@ public:
 class FrequenSeeAudioBinauralPlugin : public FrequenSeeAudioReflectionPlugin {
 public:
     explicit FrequenSeeAudioBinauralPlugin(AudioRayTracingSubsystem& SubSys) : FrequenSeeAudioReflectionPlugin(SubSys) {}
-    // the context's set: Dirs [n][3] (head frame: x forward, y right, z up), Hrir [n][2][H].  Before OnInitSource; not concurrent
-    // with ProcessAudio
-    void SetHrtf(const std::vector<float>& Dirs, const std::vector<float>& Hrir, int HrirTaps) {
+    // the context's set: Dirs [n][3] (head frame: x forward, y right, z up), Hrir [n][2][H].  Interpolate: triangulate the set and
+    // install the mesh (fs_hrtf_set_mesh) — every voice's HRIR is then the blend of the three round its direction, not the nearest
+    // one.  Before OnInitSource; not concurrent with ProcessAudio
+    void SetHrtf(const std::vector<float>& Dirs, const std::vector<float>& Hrir, int HrirTaps, bool Interpolate = false) {
         fs_hrtf_desc D{};
         D.struct_size = sizeof(D);
         D.directions = (int32_t)(Dirs.size() / 3);
@@ -788,14 +789,20 @@ public:
         if (HrirTaps < 1 || Dirs.size() % 3 != 0 || Hrir.size() != Dirs.size() / 3 * 2 * (size_t)HrirTaps)
             throw std::runtime_error("FrequenSee: an HRIR set is dirs [n][3] and hrir [n][2][taps]");
         SubSys_->Check(fs_hrtf_set(SubSys_->Ctx_, &D));
+        if (!Interpolate) return;
+        std::vector<int32_t> Tri((size_t)std::max(2 * D.directions - 4, 1) * 3);
+        int32_t Triangles = 0;
+        if (fs_hrtf_triangulate(Dirs.data(), D.directions, Tri.data(), (int32_t)(Tri.size() / 3), &Triangles) != FS_OK)
+            throw std::runtime_error("FrequenSee: fs_hrtf_triangulate needs 4 .. 4096 distinct directions that surround the listener");
+        SubSys_->Check(fs_hrtf_set_mesh(SubSys_->Ctx_, Tri.data(), Triangles));
     }
     // ... or the spherical-head model (a model: interaural delay and level difference, no pinna)
-    void SetHrtf(int Directions = 1024, int HrirTaps = 128) {
+    void SetHrtf(int Directions = 1024, int HrirTaps = 128, bool Interpolate = false) {
         std::vector<float> Dirs((size_t)std::max(Directions, 0) * 3), Hrir((size_t)std::max(Directions, 0) * 2 * (size_t)std::max(HrirTaps, 0));
         if (fs_hrtf_spherical_head(SampleRate, FS_HRTF_DEFAULT_RADIUS_CM, FS_HRTF_DEFAULT_SOUND_SPEED_CM_S, Directions, HrirTaps, Dirs.data(),
                                    Hrir.data()) != FS_OK)
             throw std::runtime_error("FrequenSee: fs_hrtf_spherical_head refused the directions or the taps");
-        SetHrtf(Dirs, Hrir, HrirTaps);
+        SetHrtf(Dirs, Hrir, HrirTaps, Interpolate);
     }
     void OnInitSource(const FrequenSeeAudioComponent& C) {
         SubSys_->Check(fs_binaural_render_init(SubSys_->Ctx_, C.Handle_, FrameSize, Taps, VoiceCount, MaxDelaySeconds));

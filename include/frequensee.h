@@ -68,6 +68,7 @@
  *             fs_direct_band_kernels fs_direct_render_init fs_direct_render_release fs_direct_render_process_batch
  *             fs_reflection_render_init fs_reflection_render_release fs_reflection_render_process_batch
  *             fs_hrtf_set fs_hrtf_info fs_hrtf_spherical_head
+ *             fs_hrtf_triangulate fs_hrtf_mesh_rows fs_hrtf_mesh_locate fs_hrtf_set_mesh fs_hrtf_mesh_info
  *             fs_binaural_render_init fs_binaural_render_release fs_binaural_render_process_batch
  *             fs_ambisonic_encode fs_ambisonic_render_init fs_ambisonic_render_release fs_ambisonic_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
@@ -1620,7 +1621,7 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
  *      direction of a host-supplied set, folded into the voice's band FIR.  Convolution is linear in the taps, so the fold is the
  *      same tap loop on a longer table, and a change of the nearest direction is a block-long crossfade between two tables —
  *      the ramp the loop already applies.  Interaural delay, head shadow and whatever else the set encodes come out of the set;
- *      the library interpolates nothing between the set's directions.
+ *      without a mesh on the set (fs_hrtf_set_mesh, below) the library interpolates nothing between the set's directions.
  *   Head frame.  x forward, y right, z up (the reference's Unreal convention); ear 0 is the left ear, ear 1 the right.
  *   fs_hrtf_set.  n = directions, H = taps, dirs [n][3], hrir [n][2][H] (direction, ear, tap).  Accepted when struct_size is this
  *   library's, 1 <= n <= FS_MAX_HRTF_DIRECTIONS, 1 <= H <= FS_MAX_HRTF_TAPS, sample_rate == the context's, dirs and hrir are not
@@ -1628,7 +1629,8 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
  *   FS_ERR_INVALID_ARGUMENT, and a refused call changes nothing.  desc == NULL clears the set.  The audio thread's contract: not
  *   concurrent with a callback.  The call waits for the reverb stream, uploads the set in one copy and frees every held binaural
  *   slot of every source of the context; the histories are kept.  So the next callback's voices START — they fade in from
- *   silence over one block — and nothing ever ramps from an index of the old set.  (A HIP failure after the upload is no refusal:
+ *   silence over one block — and nothing ever ramps from an index of the old set.  The call, whether given a set or NULL, also
+ *   drops the mesh (fs_hrtf_set_mesh).  (A HIP failure after the upload is no refusal:
  *   it is reported with the new set in force and every source's slots freed on the host's copy, so every voice still starts.)  A source initialised under a set of another H
  *   stays initialised; fs_binaural_render_process_batch refuses it while D + Tc + 1 + F exceeds its ring or Tc exceeds
  *   FS_DIRECT_RENDER_MAX_TAPS (below), and fs_binaural_render_init sizes it anew.
@@ -1651,6 +1653,40 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
  *     FS_ERR_INVALID_ARGUMENT: dirs or hrir NULL, sample_rate < 1, a or c not finite or not > 0, n outside
  *     1 .. FS_MAX_HRTF_DIRECTIONS, H outside 1 .. FS_MAX_HRTF_TAPS, or H < ceil((a / c) (1 + pi / 2) fs) + 2 (the latest onset
  *     plus the filter's first two taps would not fit).
+ *   The mesh (optional): a triangulation of the set's directions, over which a voice's HRIR is the barycentric blend of the three
+ *   at the corners of the spherical triangle its direction falls in — a source walking round the listener no longer hops from one
+ *   measured direction to the next.  Without a mesh everything above and below is as it stands, to the bit.  The blend is of the
+ *   time-domain HRIRs as given: neighbours whose onsets differ comb slightly; onset-aligned (ITD-separated) interpolation,
+ *   near-field sets and more than one mesh per context are not offered.
+ *   fs_hrtf_mesh_rows.  Host only, no context, no device: the validator and the one definition of the mesh data.  dirs [n][3],
+ *   tri [m][3] indices into dirs.  Accepted when 4 <= n <= FS_MAX_HRTF_DIRECTIONS and m == 2n - 4; every index lies in 0 .. n-1;
+ *   the three indices of a triangle are distinct; every directed edge a->b occurs in exactly one triangle and b->a in exactly one
+ *   (a closed, consistently oriented surface); every direction is a corner of some triangle; and for every triangle (a, b, c)
+ *   det = p_a . (p_b x p_c) >= 1e-6, in double from the float directions as given (counter-clockwise seen from outside, the
+ *   origin on its inner side).  Then, in double, each component rounded to float once:
+ *     r_0 = (p_b x p_c) / det,  r_1 = (p_c x p_a) / det,  r_2 = (p_a x p_b) / det   into rows [m][3][3],
+ *   so that g_i = r_i . d are the coefficients of d = sum g_i p_i.  rows == NULL only validates.  Anything else (a NULL dirs or
+ *   tri among it): FS_ERR_INVALID_ARGUMENT, and nothing is written.
+ *   fs_hrtf_triangulate.  Host only.  The convex hull of the directions — for points on a sphere the Delaunay triangulation — as
+ *   such a mesh: *m = 2n - 4 triangles into tri [cap][3].  Computed in double.  Where four or more directions lie on one circle
+ *   (a lat-long grid) the split of their facet is free: the output is specified by its properties — it passes fs_hrtf_mesh_rows
+ *   and no direction lies above a triangle's plane — not to the bit.  FS_ERR_INVALID_ARGUMENT, nothing written: dirs, tri or m
+ *   NULL, n outside 4 .. FS_MAX_HRTF_DIRECTIONS, cap < 2n - 4, a component that is not finite, or a result fs_hrtf_mesh_rows
+ *   would refuse (all directions in one hemisphere or on one great circle, a direction given twice).
+ *   fs_hrtf_mesh_locate.  Host only.  The rule the callback applies on the device, by the same function: fp32, every operation
+ *   rounded on its own, in the order written.  rows [m][3][3] as fs_hrtf_mesh_rows gives them, m >= 1, d [3] any length.
+ *     1. For each triangle j: g_i = (d.x r_i.x + d.y r_i.y) + d.z r_i.z, i = 0, 1, 2;  mu_j = g_0; if (g_1 < mu_j) mu_j = g_1;
+ *        if (g_2 < mu_j) mu_j = g_2.
+ *     2. *t = the LOWEST j that maximises mu_j: from best = -infinity and t = 0, j ascending, mu_j replaces best where
+ *        mu_j > best (an equal later one does not; one that is not a number never does).
+ *     3. c_i = g_i > 0 ? g_i : 0.0f (of triangle t);  s = (c_0 + c_1) + c_2;  b_i = c_i / s;  if !(s > 0): b = (1, 0, 0).
+ *     FS_ERR_INVALID_ARGUMENT, nothing written: a NULL pointer or m < 1.
+ *   fs_hrtf_set_mesh.  Needs a set in force.  tri [m][3] is validated by fs_hrtf_mesh_rows' code against the set's directions;
+ *   otherwise (or m < 0, or without a set) FS_ERR_INVALID_ARGUMENT, and a refused call changes nothing.  tri == NULL or m == 0
+ *   clears the mesh.  Either way the call then behaves as fs_hrtf_set: not concurrent with a callback; it waits for the reverb
+ *   stream, uploads the triangles and their rows in one copy and frees every held binaural slot of every source, the histories
+ *   kept — every voice starts from silence, and nothing ramps from an index of the other mode.  Tc and the ring sizes do not
+ *   depend on the mesh.  fs_hrtf_mesh_info: *triangles = m of the mesh in force, 0 without one (the pointer may be NULL).
  *   fs_binaural_render_init.  Needs a set in force.  F, T, D and V under fs_reflection_render_init's limits with Tc = T + H - 1
  *   wherever the ring is sized: 16 <= F <= 16384; T odd, 1 .. FS_DIRECT_RENDER_MAX_TAPS; Tc <= FS_DIRECT_RENDER_MAX_TAPS; the ring
  *   is the smallest power of two >= D + Tc + 1 + F floats and D + Tc + 1 + F <= 2^20; edges in force inside (0, fs / 2);
@@ -1673,6 +1709,14 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
  *        the same scalar w for both ears.  Not clamped.  A row without a sounding slot gives zeros.
  *     6. Afterwards a continuing or started slot holds d0 + e, g1 (0 beyond num_bands), w1 and q1; an ended slot is free; the
  *        block enters the history; n0 += F.  rows[i] as the reflection renderer's.
+ *     With a mesh in force rules 2, 3 and 6 read:
+ *     2'. Locate.  An entry with direction d gets (t1, b1[3]) from fs_hrtf_mesh_locate on the mesh's rows.  A slot holds
+ *        (t0, b0[3]) from the end of its last callback.  A starting slot takes (t0, b0) := (t1, b1); an ending slot
+ *        (t1, b1) := (t0, b0).
+ *     3'. Taps.  With (v_0, v_1, v_2) = tri[tA], per ear:  hA[k] = (bA_0 * h[v_0][ear][k] + bA_1 * h[v_1][ear][k]) +
+ *        bA_2 * h[v_2][ear][k];  CA[u] as in rule 3 with hA[k] in the place of h[qA][ear][k].
+ *     6'. A continuing or started slot holds (t1, b1) in q1's place.
+ *     (Where t0 == t1, b0 and b1 have the same bits and so have g0 and g1, C1 has C0's bits either way.)
  *     Consequence: with a set of H = 1 whose taps are all 1.0f the output equals fs_reflection_render_process_batch's with
  *     channel_gain = (gain, gain).  The output is late by (T - 1) / 2 samples plus whatever onset the set's HRIRs carry.
  *   fs_binaural_render_process_batch.  Arguments, refusals and batch rules of fs_reflection_render_process_batch, read for this
@@ -1680,13 +1724,16 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
  *   is not finite or with all three zero; a source without fs_binaural_render_init; sources that do not share F and T (hence Tc);
  *   a source whose ring the set in force has outgrown (fs_hrtf_set above).  Staging of its own (pinned + device), which holds the
  *   folded tables {C0, dC} [sum of the listed sources' V][2][Tc] beside the rest and grows at the first call that needs more; a call
- *   of a shape the context has seen allocates nothing.  One copy up, four launches whatever the count (plan, taps, render, mix),
+ *   of a shape the context has seen allocates nothing (with a mesh the staging also holds what the locate pass finds; a shape
+ *   is a shape under one mode).  One copy up, four launches whatever the count (plan, taps, render, mix) — five with a mesh
+ *   (locate first: one wave of 64 lanes per voice with an entry, striding over the triangles) —
  *   one copy back, one wait on the reverb stream.  ONE audio render thread runs all callbacks of a context.
  *   A key for the direct sound: FS_BINAURAL_DIRECT_KEY, a first-order key (a triangle index) no scene of fewer than 2^29 - 1
  *   triangles uses.
  *   fs_source_destroy and fs_context_destroy free everything. */
 #define FS_MAX_HRTF_DIRECTIONS 4096
 #define FS_MAX_HRTF_TAPS       512
+#define FS_MAX_HRTF_TRIANGLES (2 * FS_MAX_HRTF_DIRECTIONS - 4)
 #define FS_HRTF_DEFAULT_RADIUS_CM          8.75f
 #define FS_HRTF_DEFAULT_SOUND_SPEED_CM_S   34300.0f
 #define FS_BINAURAL_DIRECT_KEY 0x1FFFFFFFu
@@ -1712,6 +1759,11 @@ int fs_hrtf_set(fs_context* ctx, const fs_hrtf_desc* desc /* NULL: clear */);
 int fs_hrtf_info(fs_context* ctx, int32_t* directions, int32_t* taps);
 int fs_hrtf_spherical_head(int32_t sample_rate, float radius_cm, float sound_speed_cm_s, int32_t directions, int32_t taps,
                            float* dirs /* [directions][3] */, float* hrir /* [directions][2][taps] */);
+int fs_hrtf_triangulate(const float* dirs /* [n][3] */, int32_t n, int32_t* tri /* [cap][3] */, int32_t cap, int32_t* m);
+int fs_hrtf_mesh_rows(const float* dirs /* [n][3] */, int32_t n, const int32_t* tri /* [m][3] */, int32_t m, float* rows /* [m][3][3] or NULL */);
+int fs_hrtf_mesh_locate(const float* rows /* [m][3][3] */, int32_t m, const float d[3], int32_t* t, float b[3]);
+int fs_hrtf_set_mesh(fs_context* ctx, const int32_t* tri /* [m][3]; NULL or m == 0: clear */, int32_t m);
+int fs_hrtf_mesh_info(fs_context* ctx, int32_t* triangles);
 int fs_binaural_render_init(fs_context* ctx, fs_source src, int32_t frame_size, int32_t taps, int32_t voices, float max_delay_seconds);
 int fs_binaural_render_release(fs_context* ctx, fs_source src);
 int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in /* [count][F * 2] */,

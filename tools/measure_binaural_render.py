@@ -4,8 +4,10 @@
 every callback, the copies up and back and the stream wait included, mix requested) for {1, 32, 256} sources x {4, 16} voices.
 Beside it, in the same process and at the same shapes: fs_reflection_render_process_batch, which the binaural renderer is with a
 gain pair in the HRIRs' place.  The C entry points are called with prepared arrays: the numbers are the library's, not the Python
-wrapper's.
-usage: python tools/measure_binaural_render.py [reps] [output.json]"""
+wrapper's.  With --interpolate the set carries its mesh (fs_hrtf_triangulate, fs_hrtf_set_mesh: 2044 triangles) and every voice's HRIR
+is the blend of three: the same shapes, one more launch (the locate pass).
+--directions=N measures a set of another size (the table's is 1024).
+usage: python tools/measure_binaural_render.py [--interpolate] [--directions=N] [reps] [output.json]"""
 import json
 import os
 import sys
@@ -17,6 +19,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as graft  # noqa: E402
 
 FRAME, TAPS, BANDS, HRIR_TAPS, DIRECTIONS, SOURCES, VOICES = 1024, 255, 8, 128, 1024, (1, 32, 256), (4, 16)
+INTERPOLATE = "--interpolate" in sys.argv
+for a in sys.argv:
+    if a.startswith("--directions="):
+        DIRECTIONS = int(a.split("=", 1)[1])
+sys.argv = [a for a in sys.argv if not a.startswith("--")]
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 pkg = graft.load_package()
 cap = pkg._capi
@@ -36,14 +43,17 @@ def median_ms(call):
 
 
 ctx = pkg.Context(num_bands=BANDS)
-ctx.hrtf_set(*pkg.Context.hrtf_spherical_head(ctx.cfg.sample_rate, DIRECTIONS, HRIR_TAPS))
+the_set = pkg.Context.hrtf_spherical_head(ctx.cfg.sample_rate, DIRECTIONS, HRIR_TAPS)
+ctx.hrtf_set(*the_set)
+if INTERPOLATE:
+    ctx.hrtf_set_mesh(pkg.Context.hrtf_triangulate(the_set[0]))
 binaural = [ctx.create_source() for _ in range(max(SOURCES))]
 reflect = [ctx.create_source() for _ in range(max(SOURCES))]
 blocks = rng.uniform(-1, 1, (max(SOURCES), 2 * FRAME)).astype(np.float32)
 out = np.empty_like(blocks)
 mix = np.empty(2 * FRAME, np.float32)
 result = {"callback": f"{FRAME} stereo frames per source, {BANDS} bands, T = {TAPS}, H = {HRIR_TAPS}, {DIRECTIONS} directions", "reps": reps,
-          "realtime_budget_ms": FRAME / 48.0, "rows": []}
+          "mode": "interpolated" if INTERPOLATE else "nearest", "triangles": ctx.hrtf_mesh_info(), "realtime_budget_ms": FRAME / 48.0, "rows": []}
 for voices in VOICES:
     for s in binaural:
         ctx.binaural_render_init(s, FRAME, TAPS, voices, 0.1)
@@ -84,7 +94,7 @@ for voices in VOICES:
         b_ms, r_ms = median_ms(binaural_call), median_ms(reflection_call)
         for rows in (brows, rrows):
             assert int(rows["sounding"].min()) == voices and int(rows["dropped"].max()) == 0 and int(rows["started"].max()) == 0
-        row = {"sources": n, "voices": voices, "binaural_render_ms": b_ms, "reflection_render_ms": r_ms, "ratio": b_ms / r_ms,
+        row = {"sources": n, "voices": voices, "mode": result["mode"], "binaural_render_ms": b_ms, "reflection_render_ms": r_ms, "ratio": b_ms / r_ms,
                "folded_taps": TAPS + HRIR_TAPS - 1, "fits_the_block": b_ms <= FRAME / 48.0}
         result["rows"].append(row)
         print(json.dumps(row), flush=True)
