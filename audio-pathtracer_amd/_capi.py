@@ -72,6 +72,7 @@ EXPORTS = [
     "fs_reflection_render_init", "fs_reflection_render_release", "fs_reflection_render_process_batch",
     "fs_hrtf_set", "fs_hrtf_info", "fs_hrtf_spherical_head",
     "fs_hrtf_triangulate", "fs_hrtf_mesh_rows", "fs_hrtf_mesh_locate", "fs_hrtf_set_mesh", "fs_hrtf_mesh_info",
+    "fs_hrtf_set_onsets", "fs_hrtf_onsets_info", "fs_hrtf_delay", "fs_hrtf_split_onsets", "fs_hrtf_spherical_head_split",
     "fs_binaural_render_init", "fs_binaural_render_release", "fs_binaural_render_process_batch",
     "fs_ambisonic_encode", "fs_ambisonic_render_init", "fs_ambisonic_render_release", "fs_ambisonic_render_process_batch",
 ]
@@ -766,6 +767,11 @@ def load():
         "fs_hrtf_mesh_locate": (C.c_int, [f32p, i32, f32p, C.POINTER(C.c_int32), f32p]),
         "fs_hrtf_set_mesh": (C.c_int, [vp, C.c_void_p, i32]),
         "fs_hrtf_mesh_info": (C.c_int, [vp, C.POINTER(C.c_int32)]),
+        "fs_hrtf_set_onsets": (C.c_int, [vp, f32p]),
+        "fs_hrtf_onsets_info": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "fs_hrtf_delay": (C.c_int, [f32p, i32, C.c_float, f32p, i32]),
+        "fs_hrtf_split_onsets": (C.c_int, [f32p, i32, i32, C.c_float, i32, f32p, f32p]),
+        "fs_hrtf_spherical_head_split": (C.c_int, [i32, C.c_float, C.c_float, i32, i32, f32p, f32p, f32p]),
         "fs_binaural_render_init": (C.c_int, [vp, i32, i32, i32, i32, C.c_float]),
         "fs_binaural_render_release": (C.c_int, [vp, i32]),
         "fs_binaural_render_process_batch": (C.c_int, [vp, C.c_void_p, i32, f32p, C.c_void_p, C.c_void_p, i32, f32p, f32p, C.c_void_p]),

@@ -733,6 +733,66 @@ class Context:
         self.check(self.lib.fs_hrtf_mesh_info(self.h, C.byref(m)))
         return m.value
 
+    def hrtf_set_onsets(self, onsets):
+        """fs_hrtf_set_onsets: onsets [n][2] in samples on the set in force, whose HRIRs are then read as aligned — a voice's HRIR
+        is delayed by its own onset, with a mesh the blend of the corners'; None clears them.  Not concurrent with a callback;
+        every held binaural voice starts anew afterwards"""
+        if onsets is None:
+            self.check(self.lib.fs_hrtf_set_onsets(self.h, None))
+            return
+        o = np.ascontiguousarray(onsets, dtype=np.float32)
+        if o.ndim != 2 or o.shape != (self.hrtf_info()[0], 2):
+            raise ValueError("onsets must be [n][2] for the n directions of the set in force")
+        self.check(self.lib.fs_hrtf_set_onsets(self.h, o.ctypes.data if o.size else None))
+
+    def hrtf_onsets_info(self):
+        """(installed, extra_taps): whether onsets are in force, and O = (int)omax + 1 — a delayed HRIR has H + O taps"""
+        on, extra = C.c_int32(-1), C.c_int32(-1)
+        self.check(self.lib.fs_hrtf_onsets_info(self.h, C.byref(on), C.byref(extra)))
+        return bool(on.value), extra.value
+
+    @staticmethod
+    def hrtf_delay(h, tau, taps=None):
+        """fs_hrtf_delay: h [H] delayed by tau samples with the header's linear fractional delay, as `taps` taps (by default
+        H + (int)tau + 1, the fewest that hold it) — the bits the device computes (host only)"""
+        x = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
+        tau = float(np.float32(tau))   # (what the library is handed)
+        if taps is None:
+            taps = x.shape[0] + int(tau) + 1 if np.isfinite(tau) and 0.0 <= tau < 2.0 ** 30 else 0
+        out = np.zeros(max(int(taps), 0), np.float32)
+        rc = _capi.load().fs_hrtf_delay(x.ctypes.data if x.size else None, x.shape[0], tau, out.ctypes.data if out.size else None, int(taps))
+        if rc != _capi.OK:
+            raise FrequenSeeError(rc, "fs_hrtf_delay: at least one tap, a finite delay >= 0 and room for H + (int)tau + 1 taps")
+        return out
+
+    @staticmethod
+    def hrtf_split_onsets(hrir, threshold=0.1, lead=0):
+        """fs_hrtf_split_onsets: (aligned [n][2][H], onsets [n][2]) of a set that comes without delays — per direction and ear the
+        onset is the first tap at `threshold` of the peak, less `lead`, and the HRIR is moved up by it (host only)"""
+        h = np.ascontiguousarray(hrir, dtype=np.float32)
+        if h.ndim != 3 or h.shape[1] != 2:
+            raise ValueError("hrir must be [n][2][H]")
+        aligned, onsets = np.zeros_like(h), np.zeros(h.shape[:2], np.float32)
+        rc = _capi.load().fs_hrtf_split_onsets(h.ctypes.data if h.size else None, h.shape[0], h.shape[2], float(threshold), int(lead),
+                                               aligned.ctypes.data if aligned.size else None, onsets.ctypes.data if onsets.size else None)
+        if rc != _capi.OK:
+            raise FrequenSeeError(rc, "fs_hrtf_split_onsets: at least one direction and tap, threshold in (0, 1], lead >= 0")
+        return aligned, onsets
+
+    @staticmethod
+    def hrtf_spherical_head_split(sample_rate, directions, taps, radius_cm=_capi.HRTF_DEFAULT_RADIUS_CM,
+                                  sound_speed_cm_s=_capi.HRTF_DEFAULT_SOUND_SPEED_CM_S):
+        """fs_hrtf_spherical_head_split: (dirs [directions][3], hrir [directions][2][taps], onsets [directions][2]) — the
+        spherical-head model with the shadow filter and the onset handed out apart, for fs_hrtf_set and fs_hrtf_set_onsets"""
+        n, H = max(int(directions), 0), max(int(taps), 0)
+        dirs, hrir, onsets = np.zeros((n, 3), np.float32), np.zeros((n, 2, H), np.float32), np.zeros((n, 2), np.float32)
+        rc = _capi.load().fs_hrtf_spherical_head_split(int(sample_rate), float(radius_cm), float(sound_speed_cm_s), int(directions), int(taps),
+                                                       dirs.ctypes.data if dirs.size else None, hrir.ctypes.data if hrir.size else None,
+                                                       onsets.ctypes.data if onsets.size else None)
+        if rc != _capi.OK:
+            raise FrequenSeeError(rc, "fs_hrtf_spherical_head_split: directions 1 .. 4096, taps 2 .. 512, positive finite radius and sound speed")
+        return dirs, hrir, onsets
+
     def binaural_render_init(self, src, frame_size=1024, taps=255, voices=32, max_delay_seconds=1.0):
         self.check(self.lib.fs_binaural_render_init(self.h, src, int(frame_size), int(taps), int(voices), float(max_delay_seconds)))
         self._br_frame = getattr(self, "_br_frame", {})
@@ -1565,16 +1625,29 @@ class FrequenSeeAudioBinauralPlugin(FrequenSeeAudioReflectionPlugin):
 
     DirectKey = _capi.BINAURAL_DIRECT_KEY   # a first-order key (a triangle index) no scene of fewer than 2^29 - 1 triangles uses
 
-    def SetHrtf(self, dirs=None, hrir=None, directions=1024, taps=128, interpolate=False):
+    def SetHrtf(self, dirs=None, hrir=None, directions=1024, taps=128, interpolate=False, align=False, onsets=None):
         """the context's HRIR set: dirs [n][3] (head frame: x forward, y right, z up) and hrir [n][2][H], or the spherical-head
         model of `directions` and `taps`.  interpolate: triangulate the set and install the mesh (fs_hrtf_set_mesh) — every
-        voice's HRIR is then the blend of the three round its direction, not the nearest one.  Before OnInitSource; not
-        concurrent with ProcessAudio"""
+        voice's HRIR is then the blend of the three round its direction, not the nearest one.  align: carry the HRIRs' onsets
+        apart (fs_hrtf_set_onsets), so that the blend is of aligned HRIRs and of their delays — `onsets` [n][2] where the host
+        has them (hrir is then the aligned set), else split off the set given (fs_hrtf_split_onsets: threshold 0.1, lead 0);
+        without a set, the spherical head with its two halves apart.  Before OnInitSource; not concurrent with ProcessAudio"""
+        if onsets is not None and (not align or dirs is None):
+            raise ValueError("onsets go with align=True and a host set: they are the delays of its aligned HRIRs")
+        if onsets is not None and np.shape(onsets) != (np.shape(dirs)[0], 2):
+            raise ValueError("onsets must be [n][2] for the n directions of the set")
         if dirs is None:
-            dirs, hrir = Context.hrtf_spherical_head(self.ctx.cfg.sample_rate, directions, taps)
+            if align:
+                dirs, hrir, onsets = Context.hrtf_spherical_head_split(self.ctx.cfg.sample_rate, directions, taps)
+            else:
+                dirs, hrir = Context.hrtf_spherical_head(self.ctx.cfg.sample_rate, directions, taps)
+        elif align and onsets is None:
+            hrir, onsets = Context.hrtf_split_onsets(hrir, 0.1, 0)
         self.ctx.hrtf_set(dirs, hrir)
         if interpolate:
             self.ctx.hrtf_set_mesh(Context.hrtf_triangulate(dirs))
+        if align:
+            self.ctx.hrtf_set_onsets(onsets)
 
     def OnInitSource(self, component: FrequenSeeAudioComponent):
         self.ctx.binaural_render_init(component._src, self.FrameSize, self.Taps, self.VoiceCount, self.MaxDelaySeconds)

@@ -22,8 +22,11 @@
 //           into the call's folded tables (with a mesh: h_A = (bA_0 h[v_0] + bA_1 h[v_1]) + bA_2 h[v_2] as LDS is filled, the loop
 //           as it is).  Lanes of a wave read one h[k] (a broadcast) and neighbouring f[u - k]; where the lower
 //           bound of k differs between lanes the h reads are neighbours too: no bank conflicts either way.  A slot whose band gains
-//           and HRIR index did not change folds once: C1 has C0's bits.
-//   render  voice_bank_render, loading s_cd from the folded table of (slot, ear), with Tc = T + H - 1 taps; ear ch reads channel
+//           and HRIR index did not change folds once: C1 has C0's bits.  With onsets on the set (fs_hrtf_set_onsets) h_A is the
+//           HRIR delayed by the end's onset, of He = H + (int)omax + 1 taps (fs_internal.hpp's hrtf_delay_tap as LDS is filled, two
+//           more instantiations — four in all —, the loop as it is, on He taps).
+//   render  voice_bank_render, loading s_cd from the folded table of (slot, ear), with Tc = T + H - 1 taps (He in H's place with
+//           onsets: the host's b.tc); ear ch reads channel
 //           ch of the ring and of the block.
 //   mix     one thread per sample, rows in list order (launch_callback_mix, fs_reverb.hip: the audio callbacks' one mix).
 #include "fs_dev_render.hpp"
@@ -103,7 +106,7 @@ struct BinauralMeshVoices {
 // both ends — compared by bits, so that -0 is not +0), and tap k of end A for the LDS fill.
 struct FoldNearest {
     int q0, q1;
-    __device__ __forceinline__ FoldNearest(const BinauralRenderPlan* __restrict__ plp, const float4* __restrict__) : q0(plp->q0), q1(plp->q1) {}
+    __device__ __forceinline__ FoldNearest(const BinauralRenderPlan* __restrict__ plp, const float4* __restrict__, int) : q0(plp->q0), q1(plp->q1) {}
     __device__ __forceinline__ bool same() const { return q0 == q1; }
     __device__ __forceinline__ float2 tap(const float* __restrict__ hrir, int ear, int h_taps, int k) const {
         return make_float2(hrir[((size_t)q0 * 2 + (size_t)ear) * (size_t)h_taps + k], hrir[((size_t)q1 * 2 + (size_t)ear) * (size_t)h_taps + k]);
@@ -112,7 +115,7 @@ struct FoldNearest {
 struct FoldMesh {
     int t[2], v[2][3];
     float b[2][3];
-    __device__ __forceinline__ FoldMesh(const BinauralMeshPlan* __restrict__ plp, const float4* __restrict__ mesh) {
+    __device__ __forceinline__ FoldMesh(const BinauralMeshPlan* __restrict__ plp, const float4* __restrict__ mesh, int) {
         t[0] = plp->t0; t[1] = plp->t1;
         for (int i = 0; i < 3; ++i) {
             b[0][i] = plp->b0[i]; b[1][i] = plp->b1[i];
@@ -133,6 +136,57 @@ struct FoldMesh {
     }
     __device__ __forceinline__ float2 tap(const float* __restrict__ hrir, int ear, int h_taps, int k) const {
         return make_float2(end(hrir, ear, h_taps, k, 0), end(hrir, ear, h_taps, k, 1));
+    }
+};
+
+// ... and with onsets on the set (fs_hrtf_set_onsets): the set's HRIRs are read as aligned, of `set_taps` taps, and tap k of end A
+// is that of the HRIR delayed by tauA — the onset of qA, or with a mesh the blend of the three corners' onsets, clamped to omax —
+// for k up to h_taps = He.  The aligned HRIR is evaluated at the two indices a tap reads (hrtf_delay_tap), 0.0f outside the set's
+// taps: no second LDS array and no further barrier; neighbouring k read neighbouring addresses, so the requests stay coalesced.
+// Equal q, or equal (t, b) bits, give equal tau bits: same() is the mode's own.
+struct FoldNearestOnsets : FoldNearest {
+    HrtfDelay d[2];
+    int set_taps;
+    __device__ __forceinline__ FoldNearestOnsets(const BinauralRenderPlan* __restrict__ plp, const float4* __restrict__ mesh, int ear,
+                                                 const float* __restrict__ onsets, float omax, int set_taps_)
+        : FoldNearest(plp, mesh, ear), set_taps(set_taps_) {
+        const int q[2] = {q0, q1};
+        for (int A = 0; A < 2; ++A) {
+            float tau = onsets[(size_t)q[A] * 2 + (size_t)ear];
+            if (tau > omax) tau = omax;
+            d[A] = hrtf_delay_of(tau);
+        }
+    }
+    __device__ __forceinline__ float end(const float* __restrict__ hrir, int ear, int k, int A) const {
+        const float* __restrict__ h = hrir + ((size_t)(A ? q1 : q0) * 2 + (size_t)ear) * (size_t)set_taps;
+        const int H = set_taps;
+        return hrtf_delay_tap(d[A], k, [=](int j) { return j >= 0 && j < H ? h[j] : 0.0f; });
+    }
+    __device__ __forceinline__ float2 tap(const float* __restrict__ hrir, int ear, int, int k) const {
+        return make_float2(end(hrir, ear, k, 0), end(hrir, ear, k, 1));
+    }
+};
+struct FoldMeshOnsets : FoldMesh {
+    HrtfDelay d[2];
+    int set_taps;
+    __device__ __forceinline__ FoldMeshOnsets(const BinauralMeshPlan* __restrict__ plp, const float4* __restrict__ mesh, int ear,
+                                              const float* __restrict__ onsets, float omax, int set_taps_)
+        : FoldMesh(plp, mesh, ear), set_taps(set_taps_) {
+        for (int A = 0; A < 2; ++A) {
+            const float o0 = onsets[(size_t)v[A][0] * 2 + (size_t)ear], o1 = onsets[(size_t)v[A][1] * 2 + (size_t)ear];
+            const float o2 = onsets[(size_t)v[A][2] * 2 + (size_t)ear];
+            float tau = (b[A][0] * o0 + b[A][1] * o1) + b[A][2] * o2;
+            if (tau > omax) tau = omax;   // (the weights sum to 1 only within 2 ulp: the last tap stays inside He)
+            d[A] = hrtf_delay_of(tau);
+        }
+    }
+    __device__ __forceinline__ float2 tap(const float* __restrict__ hrir, int ear, int, int k) const {
+        const int H = set_taps;
+        const FoldMesh& blend = *this;
+        float2 out;
+        out.x = hrtf_delay_tap(d[0], k, [&](int j) { return j >= 0 && j < H ? blend.end(hrir, ear, H, j, 0) : 0.0f; });
+        out.y = hrtf_delay_tap(d[1], k, [&](int j) { return j >= 0 && j < H ? blend.end(hrir, ear, H, j, 1) : 0.0f; });
+        return out;
     }
 };
 
@@ -175,12 +229,15 @@ __global__ void binaural_render_mesh_plan_kernel(const BinauralRenderItem* __res
     voice_bank_plan<BinauralMeshVoices>(items, voices, plans, n0_out, count, stride, frame, bands, fs_f, located);
 }
 
-template <typename Ends, typename Plan>
+// (h_taps: the taps of the HRIRs the fold runs on — H, with onsets He; Extra: what the Ends of a mode with onsets read beyond the
+// plan and the mesh — the onsets, omax and the set's own H —, nothing in the two modes without)
+template <typename Ends, typename Plan, typename... Extra>
 __global__ __launch_bounds__(kBrFoldThreads) void binaural_render_fold_kernel(const BinauralRenderItem* __restrict__ items,
                                                                                const uint16_t* __restrict__ sounding,
                                                                                const Plan* __restrict__ plans,
                                                                                const float* __restrict__ hrir, const float4* __restrict__ mesh,
-                                                                               float2* __restrict__ folded, int taps, int h_taps, int bands) {
+                                                                               float2* __restrict__ folded, int taps, int h_taps, int bands,
+                                                                               Extra... extra) {
     __shared__ float s_f[2][kRenderMaxTaps];        // f0, f1
     __shared__ float s_h[2][FS_MAX_HRTF_TAPS];      // h_0, h_1: h[q0][ear], h[q1][ear], or the blends
     const int which = sounding[blockIdx.x];
@@ -188,7 +245,7 @@ __global__ __launch_bounds__(kBrFoldThreads) void binaural_render_fold_kernel(co
     const int tid = threadIdx.x;
     const Plan* __restrict__ plp = plans + which;   // (which = row * kVoiceSlots + slot: the plans' own index)
     const float* __restrict__ table = items[which / kVoiceSlots].table;
-    const Ends ends(plp, mesh);
+    const Ends ends(plp, mesh, ear, extra...);
     // (uniform over the workgroup) nothing ramps: one fold serves both ends — compared by bits, so that -0 is not +0
     bool same = ends.same();
     for (int b = 0; b < bands; ++b) same = same && __float_as_uint(plp->g0[b]) == __float_as_uint(plp->g1[b]);
@@ -242,11 +299,15 @@ __global__ __launch_bounds__(kRenderTile) void binaural_render_kernel(const Bina
 
 }  // namespace
 
-template <typename Ends, typename Plan>
+template <typename Ends, typename EndsOnsets, typename Plan>
 static void launch_fold_render(const BinauralRenderBatch& b, const Plan* plans, hipStream_t s) {
-    if (b.n_sounding > 0)   // (a callback of silent rows folds nothing)
+    if (b.n_sounding > 0 && !b.onsets)   // (a callback of silent rows folds nothing)
         hipLaunchKernelGGL((binaural_render_fold_kernel<Ends, Plan>), dim3(b.n_sounding, 2), dim3(kBrFoldThreads), 0, s, b.items, b.sounding,
                            plans, b.hrir, b.mesh, b.folded, b.taps, b.h_taps, b.bands);
+    else if (b.n_sounding > 0)
+        hipLaunchKernelGGL((binaural_render_fold_kernel<EndsOnsets, Plan, const float*, float, int>), dim3(b.n_sounding, 2),
+                           dim3(kBrFoldThreads), 0, s, b.items, b.sounding, plans, b.hrir, b.mesh, b.folded, b.taps, b.h_eff, b.bands,
+                           b.onsets, b.omax, b.h_taps);
     const int tiles = (b.frame + kRenderTile - 1) / kRenderTile;
     hipLaunchKernelGGL(binaural_render_kernel<Plan>, dim3(tiles, 2, b.count), dim3(kRenderTile), 0, s, b.items, plans, b.folded, b.n0, b.in,
                        b.out, b.frame, b.tc);
@@ -260,11 +321,11 @@ void launch_binaural_render(const BinauralRenderBatch& b, hipStream_t s) {
                                dim3(kBrLocateThreads), 0, s, b.items, b.sounding, b.voices, b.mesh, b.n_tris, b.located, b.n_sounding, b.stride);
         hipLaunchKernelGGL(binaural_render_mesh_plan_kernel, dim3((b.count * kVoiceSlots + tb - 1) / tb), dim3(tb), 0, s, b.items, b.voices,
                            b.located, b.mesh_plans, b.n0, b.count, b.stride, b.frame, b.bands, b.fs);
-        launch_fold_render<FoldMesh>(b, (const BinauralMeshPlan*)b.mesh_plans, s);
+        launch_fold_render<FoldMesh, FoldMeshOnsets>(b, (const BinauralMeshPlan*)b.mesh_plans, s);
     } else {
         hipLaunchKernelGGL(binaural_render_plan_kernel, dim3((b.count * kVoiceSlots + tb - 1) / tb), dim3(tb), 0, s, b.items, b.voices, b.dirs,
                            b.n_dirs, b.plans, b.n0, b.count, b.stride, b.frame, b.bands, b.fs);
-        launch_fold_render<FoldNearest>(b, (const BinauralRenderPlan*)b.plans, s);
+        launch_fold_render<FoldNearest, FoldNearestOnsets>(b, (const BinauralRenderPlan*)b.plans, s);
     }
     if (b.mix) launch_callback_mix(b.out, b.count, 2 * b.frame, b.mix, s);
 }

@@ -1,6 +1,8 @@
 // fs_capi_binaural_render.cpp — binaural voices on the audio thread: the HRIR set of the context (fs_hrtf_set / fs_hrtf_info), a
 // set for hosts that have none (fs_hrtf_spherical_head, host only), the mesh on the set that turns the nearest direction into a
 // blend of three (fs_hrtf_triangulate, fs_hrtf_mesh_rows, fs_hrtf_mesh_locate: host only; fs_hrtf_set_mesh / fs_hrtf_mesh_info),
+// the onsets on the set that turn the blend of HRIRs into a blend of aligned HRIRs and of their delays (fs_hrtf_delay,
+// fs_hrtf_split_onsets, fs_hrtf_spherical_head_split: host only; fs_hrtf_set_onsets / fs_hrtf_onsets_info),
 // and what the renderer is beyond its voice bank
 // (fs_capi_voice_bank.hpp: the callback; fs_capi_reflect_render.cpp: the set-up and its release): the refusals that name the
 // set, an entry's gain and direction, the list of sounding slots and the folded tables of fs_binaural_render.hip's launches.
@@ -18,13 +20,20 @@ namespace {
 
 constexpr double kPi = 3.14159265358979323846;
 
-// the header's spherical-head model for one ear at angle theta from the ear's axis, in double: h[0 .. H)
-void head_taps(double theta, double a_over_c, double fs, int H, double* h) {
+// the header's spherical-head model for one ear at angle theta from the ear's axis, in double: the onset tau and the shadow
+// filter's b0, b1, a1 ...
+struct HeadEar { double tau, b0, b1, a1; };
+HeadEar head_ear(double theta, double a_over_c, double fs) {
     const double tau = theta <= kPi / 2.0 ? a_over_c * (1.0 - std::cos(theta)) : a_over_c * (1.0 + theta - kPi / 2.0);
     const double alpha_min = 0.1, theta_min = 5.0 * kPi / 6.0;
     const double alpha = (1.0 + alpha_min / 2.0) + (1.0 - alpha_min / 2.0) * std::cos(theta * kPi / theta_min);
     const double kappa = fs * a_over_c;
-    const double b0 = (1.0 + alpha * kappa) / (1.0 + kappa), b1 = (1.0 - alpha * kappa) / (1.0 + kappa), a1 = (1.0 - kappa) / (1.0 + kappa);
+    return {tau, (1.0 + alpha * kappa) / (1.0 + kappa), (1.0 - alpha * kappa) / (1.0 + kappa), (1.0 - kappa) / (1.0 + kappa)};
+}
+// ... its taps h[0 .. H) ...
+void head_taps(double theta, double a_over_c, double fs, int H, double* h) {
+    const HeadEar e = head_ear(theta, a_over_c, fs);
+    const double tau = e.tau, b0 = e.b0, b1 = e.b1, a1 = e.a1;
     const double pos = tau * fs;
     const double fl = std::floor(pos);
     const int i = (int)fl;
@@ -40,6 +49,45 @@ void head_taps(double theta, double a_over_c, double fs, int H, double* h) {
         else g = -a1 * g_prev;
         h[k] = (1.0 - f) * g + f * g_prev;
     }
+}
+// ... and the two halves apart (fs_hrtf_spherical_head_split): g[0 .. H), the shadow filter alone
+void head_filter(const HeadEar& e, int H, double* g) {
+    for (int m = 0; m < H; ++m) g[m] = m == 0 ? e.b0 : m == 1 ? e.b1 - e.a1 * g[0] : -e.a1 * g[m - 1];
+}
+
+// fs_hrtf_spherical_head (onsets == nullptr) and fs_hrtf_spherical_head_split: the directions, and per ear the taps — with the
+// onset in them, or beside them
+int spherical_head(int32_t sample_rate, float radius_cm, float sound_speed_cm_s, int32_t directions, int32_t taps, float* dirs, float* hrir,
+                   float* onsets, bool split) {
+    if (!dirs || !hrir || (split && !onsets) || sample_rate < 1 || !std::isfinite(radius_cm) || !(radius_cm > 0.0f) ||
+        !std::isfinite(sound_speed_cm_s) || !(sound_speed_cm_s > 0.0f) || directions < 1 || directions > FS_MAX_HRTF_DIRECTIONS ||
+        taps < (split ? 2 : 1) || taps > FS_MAX_HRTF_TAPS)
+        return FS_ERR_INVALID_ARGUMENT;
+    const double fs = (double)sample_rate, a_over_c = (double)radius_cm / (double)sound_speed_cm_s;
+    if (!split && (double)taps < std::ceil(a_over_c * (1.0 + kPi / 2.0) * fs) + 2.0) return FS_ERR_INVALID_ARGUMENT;
+    const int n = directions, H = taps;
+    std::vector<double> h((size_t)H);
+    for (int k = 0; k < n; ++k) {
+        const double z = 1.0 - (2.0 * (double)k + 1.0) / (double)n;
+        const double rho = std::sqrt(1.0 - z * z);
+        const double phi = (double)k * kPi * (3.0 - std::sqrt(5.0));
+        const double p[3] = {rho * std::cos(phi), rho * std::sin(phi), z};
+        for (int c = 0; c < 3; ++c) dirs[(size_t)k * 3 + c] = (float)p[c];
+        for (int ear = 0; ear < 2; ++ear) {
+            const double dot = ear == 0 ? -p[1] : p[1];   // p . e, e = (0, -+1, 0)
+            const double theta = std::acos(std::min(std::max(dot, -1.0), 1.0));
+            if (split) {
+                const HeadEar e = head_ear(theta, a_over_c, fs);
+                head_filter(e, H, h.data());
+                onsets[(size_t)k * 2 + (size_t)ear] = (float)(e.tau * fs);
+            } else {
+                head_taps(theta, a_over_c, fs, H, h.data());
+            }
+            float* out = hrir + ((size_t)k * 2 + (size_t)ear) * (size_t)H;
+            for (int t = 0; t < H; ++t) out[t] = (float)h[(size_t)t];
+        }
+    }
+    return FS_OK;
 }
 
 // ---- the mesh on a set: the header's "fs_hrtf_mesh_rows" clauses, in double from the float directions as given.  True: the mesh
@@ -191,26 +239,36 @@ extern "C" {
 
 int fs_hrtf_spherical_head(int32_t sample_rate, float radius_cm, float sound_speed_cm_s, int32_t directions, int32_t taps, float* dirs,
                            float* hrir) {
-    if (!dirs || !hrir || sample_rate < 1 || !std::isfinite(radius_cm) || !(radius_cm > 0.0f) || !std::isfinite(sound_speed_cm_s) ||
-        !(sound_speed_cm_s > 0.0f) || directions < 1 || directions > FS_MAX_HRTF_DIRECTIONS || taps < 1 || taps > FS_MAX_HRTF_TAPS)
+    return spherical_head(sample_rate, radius_cm, sound_speed_cm_s, directions, taps, dirs, hrir, nullptr, false);
+}
+
+int fs_hrtf_spherical_head_split(int32_t sample_rate, float radius_cm, float sound_speed_cm_s, int32_t directions, int32_t taps, float* dirs,
+                                 float* hrir, float* onsets) {
+    return spherical_head(sample_rate, radius_cm, sound_speed_cm_s, directions, taps, dirs, hrir, onsets, true);
+}
+
+int fs_hrtf_delay(const float* h, int32_t H, float tau, float* out, int32_t He) {
+    if (!h || !out || H < 1 || !std::isfinite(tau) || !(tau >= 0.0f) || tau >= 2147483520.0f || (int64_t)He < (int64_t)H + (int64_t)tau + 1)
         return FS_ERR_INVALID_ARGUMENT;
-    const double fs = (double)sample_rate, a_over_c = (double)radius_cm / (double)sound_speed_cm_s;
-    if ((double)taps < std::ceil(a_over_c * (1.0 + kPi / 2.0) * fs) + 2.0) return FS_ERR_INVALID_ARGUMENT;
-    const int n = directions, H = taps;
-    std::vector<double> h((size_t)H);
-    for (int k = 0; k < n; ++k) {
-        const double z = 1.0 - (2.0 * (double)k + 1.0) / (double)n;
-        const double rho = std::sqrt(1.0 - z * z);
-        const double phi = (double)k * kPi * (3.0 - std::sqrt(5.0));
-        const double p[3] = {rho * std::cos(phi), rho * std::sin(phi), z};
-        for (int c = 0; c < 3; ++c) dirs[(size_t)k * 3 + c] = (float)p[c];
-        for (int ear = 0; ear < 2; ++ear) {
-            const double dot = ear == 0 ? -p[1] : p[1];   // p . e, e = (0, -+1, 0)
-            const double theta = std::acos(std::min(std::max(dot, -1.0), 1.0));
-            head_taps(theta, a_over_c, fs, H, h.data());
-            float* out = hrir + ((size_t)k * 2 + (size_t)ear) * (size_t)H;
-            for (int t = 0; t < H; ++t) out[t] = (float)h[(size_t)t];
-        }
+    const HrtfDelay d = hrtf_delay_of(tau);
+    for (int k = 0; k < He; ++k) out[k] = hrtf_delay_tap(d, k, [=](int j) { return j >= 0 && j < H ? h[j] : 0.0f; });
+    return FS_OK;
+}
+
+int fs_hrtf_split_onsets(const float* hrir, int32_t n, int32_t H, float threshold, int32_t lead, float* aligned, float* onsets) {
+    if (!hrir || !aligned || !onsets || n < 1 || H < 1 || !(threshold > 0.0f) || !(threshold <= 1.0f) || lead < 0) return FS_ERR_INVALID_ARGUMENT;
+    for (size_t r = 0; r < (size_t)n * 2; ++r) {
+        const float* h = hrir + r * (size_t)H;
+        float* a = aligned + r * (size_t)H;
+        float peak = 0.0f;
+        for (int k = 0; k < H; ++k) peak = std::max(peak, std::fabs(h[k]));
+        const float level = threshold * peak;
+        int k0 = 0;
+        while (k0 < H && !(std::fabs(h[k0]) >= level)) ++k0;
+        if (k0 == H) k0 = 0;   // (taps that are not numbers)
+        const int onset = std::max(k0 - std::min(lead, k0), 0);
+        for (int k = 0; k < H; ++k) a[k] = k + onset < H ? h[k + onset] : 0.0f;   // (ascending: in place reads ahead of what it writes)
+        onsets[r] = (float)onset;
     }
     return FS_OK;
 }
@@ -255,6 +313,10 @@ int fs_hrtf_set(fs_context* ctx, const fs_hrtf_desc* d) {
     if (ctx->d_hrtf_mesh) (void)hipFree(ctx->d_hrtf_mesh);   // a mesh is of the set it was given for
     ctx->d_hrtf_mesh = nullptr;
     ctx->hrtf_tris = 0;
+    if (ctx->d_hrtf_onsets) (void)hipFree(ctx->d_hrtf_onsets);   // ... and so are onsets
+    ctx->d_hrtf_onsets = nullptr;
+    ctx->hrtf_omax = 0.0f;
+    ctx->hrtf_onset_taps = 0;
     // The set is in force from here on, so no source is left out
     const hipError_t clear_err = free_binaural_slots(ctx);
     if (clear_err != hipSuccess) return ctx->hip_fail(clear_err, "fs_hrtf_set (clearing the slots)");
@@ -326,6 +388,45 @@ int fs_hrtf_mesh_info(fs_context* ctx, int32_t* triangles) {
     return FS_OK;
 }
 
+int fs_hrtf_set_onsets(fs_context* ctx, const float* onsets) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (!ctx->device_ok) return ctx->fail(FS_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
+    if (ctx->hrtf_dirs == 0) return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_hrtf_set_onsets: no HRIR set in force (fs_hrtf_set)");
+    const size_t count = (size_t)ctx->hrtf_dirs * 2;
+    float omax = 0.0f;
+    int extra = 0;
+    if (onsets) {
+        for (size_t k = 0; k < count; ++k) {
+            if (!std::isfinite(onsets[k]) || !(onsets[k] >= 0.0f))
+                return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_hrtf_set_onsets: an onset is not finite or is negative");
+            omax = std::max(omax, onsets[k]);
+        }
+        if (!(omax < (float)FS_MAX_HRTF_TAPS) || ctx->hrtf_taps + (int)omax + 1 > FS_MAX_HRTF_TAPS)
+            return ctx->fail(FS_ERR_INVALID_ARGUMENT, "fs_hrtf_set_onsets: the set's taps + (int) the largest onset + 1 exceed 512");
+        extra = (int)omax + 1;
+    }
+    FS_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    float* fresh = nullptr;
+    if (onsets) FS_HIP(ctx, hipMalloc((void**)&fresh, sizeof(float) * count));   // (a failure here has changed nothing)
+    hipError_t err = hipStreamSynchronize(ctx->rev_stream);   // no callback reads the old onsets any more
+    if (err == hipSuccess && onsets) err = hipMemcpy(fresh, onsets, sizeof(float) * count, hipMemcpyHostToDevice);
+    if (err != hipSuccess) { if (fresh) (void)hipFree(fresh); return ctx->hip_fail(err, "fs_hrtf_set_onsets (upload)"); }
+    if (ctx->d_hrtf_onsets) (void)hipFree(ctx->d_hrtf_onsets);
+    ctx->d_hrtf_onsets = fresh;
+    ctx->hrtf_omax = omax;
+    ctx->hrtf_onset_taps = extra;
+    const hipError_t clear_err = free_binaural_slots(ctx);   // nothing ramps from a table of the other length
+    if (clear_err != hipSuccess) return ctx->hip_fail(clear_err, "fs_hrtf_set_onsets (clearing the slots)");
+    return FS_OK;
+}
+
+int fs_hrtf_onsets_info(fs_context* ctx, int32_t* installed, int32_t* extra_taps) {
+    if (!ctx) return FS_ERR_INVALID_ARGUMENT;
+    if (installed) *installed = ctx->d_hrtf_onsets ? 1 : 0;
+    if (extra_taps) *extra_taps = ctx->hrtf_onset_taps;
+    return FS_OK;
+}
+
 int fs_hrtf_info(fs_context* ctx, int32_t* directions, int32_t* taps) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
     if (directions) *directions = ctx->hrtf_dirs;
@@ -335,7 +436,7 @@ int fs_hrtf_info(fs_context* ctx, int32_t* directions, int32_t* taps) {
 
 int fs_binaural_render_init(fs_context* ctx, fs_source h, int32_t frame_size, int32_t taps, int32_t voices, float max_delay_seconds) {
     if (!ctx) return FS_ERR_INVALID_ARGUMENT;
-    return voice_bank_init(ctx, h, &Source::br, ctx->hrtf_dirs ? ctx->hrtf_taps - 1 : -1,
+    return voice_bank_init(ctx, h, &Source::br, ctx->hrtf_dirs ? ctx->hrtf_taps + ctx->hrtf_onset_taps - 1 : -1,   // (He - 1)
                            {"fs_binaural_render_init: no HRIR set in force (fs_hrtf_set)",
                             "fs_binaural_render_init: frame size outside 16 .. 16384, taps even or outside 1 .. 2047, voices outside 1 .. 32, or a bad max delay",
                             "fs_binaural_render_init: taps + the set's taps - 1 exceed 2047",
@@ -353,7 +454,7 @@ int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, 
                                      float* mix, fs_binaural_render_row* rows) {
     static const VoiceBankRenderer<BinauralRenderBatch> q = {&Source::br, &fs_context::br_stage, "fs_binaural_render_init has not been called for this source",
                                                              "fs_binaural_render_process_batch: no HRIR set in force (fs_hrtf_set)", launch_binaural_render, kVoiceBankHeader};
-    const int H = ctx ? ctx->hrtf_taps : 0;
+    const int H = ctx ? ctx->hrtf_taps + ctx->hrtf_onset_taps : 0;   // He: the taps of the HRIRs the fold runs on
     const bool mesh = ctx && ctx->hrtf_tris > 0;
     return voice_bank_process(
         q, ctx, sources, count, in, voices, voice_counts, stride, out, mix, rows,
@@ -388,7 +489,8 @@ int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, 
             b.folded = (float2*)d_folded;
             b.dirs = ctx->d_hrtf;
             b.hrir = ctx->d_hrtf + (size_t)ctx->hrtf_dirs * 3;
-            b.n_dirs = ctx->hrtf_dirs; b.h_taps = H;
+            b.n_dirs = ctx->hrtf_dirs; b.h_taps = ctx->hrtf_taps; b.h_eff = H;
+            b.onsets = ctx->d_hrtf_onsets; b.omax = ctx->hrtf_omax;
             b.tc = b.taps + H - 1;
             if (mesh) {
                 size_t slots = 0;

@@ -664,6 +664,7 @@ int fs_context_destroy(fs_context* ctx) {
         for (CallbackStage* st : {&ctx->rev_stage, &ctx->dr_stage, &ctx->rr_stage, &ctx->br_stage, &ctx->ar_stage, &ctx->sf_stage}) st->release();
         if (ctx->d_hrtf) (void)hipFree(ctx->d_hrtf);
         if (ctx->d_hrtf_mesh) (void)hipFree(ctx->d_hrtf_mesh);
+        if (ctx->d_hrtf_onsets) (void)hipFree(ctx->d_hrtf_onsets);
         for (const auto& t : ctx->dr_tables) if (t.d) (void)hipFree(t.d);
         if (ctx->d_batch) (void)hipFree(ctx->d_batch);
         if (ctx->d_build) (void)hipFree(ctx->d_build);

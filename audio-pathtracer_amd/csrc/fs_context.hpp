@@ -423,6 +423,11 @@ struct fs_context {
     std::vector<float> hrtf_dirs_host;
     float4* d_hrtf_mesh = nullptr;
     int hrtf_tris = 0;
+    // ... and the onsets on it (fs_hrtf_set_onsets; dropped by every fs_hrtf_set, kept by fs_hrtf_set_mesh): one device block
+    // [n][2] samples, the host's copy of the largest, and O = (int)omax + 1, the taps a delayed HRIR has beyond H; null and 0: none
+    float* d_hrtf_onsets = nullptr;
+    float hrtf_omax = 0.0f;
+    int hrtf_onset_taps = 0;
     // the partitioned engine's twiddles, W[k] = exp(-2 pi i k / N), k < N / 2, per n = log2 N <= 12: built by the first
     // fs_reverb_init that needs the size, freed with the context
     float2* d_rev_tw[13] = {};

@@ -947,7 +947,24 @@ struct BinauralMeshPlan : BinauralRenderPlan {
     float b0[3], b1[3];
 };
 static_assert(sizeof(BinauralMeshPlan) == 128, "BinauralMeshPlan: thirty-two words");
+// Onsets on the set in force (fs_hrtf_set_onsets): the header's delayed HRIR, to the bit, for the host (fs_hrtf_delay) and the
+// device (the fold's LDS fill) alike — every operation fp32, rounded on its own, in the order written.  tau = i + f, i = (int)tau;
+// tap k of the delayed HRIR is g * x(k - i) + f * x(k - i - 1) with g = 1.0f - f, where `x(j)` gives the aligned HRIR's tap j and
+// 0.0f outside 0 .. H-1: the host reads the caller's array, the device the set's — or, with a mesh, blends three as it reads.
+struct HrtfDelay { int i; float f, g; };
+__host__ __device__ inline HrtfDelay hrtf_delay_of(float tau) {
+    const int i = (int)tau;
+    const float f = tau - (float)i;
+    return {i, f, 1.0f - f};
+}
+template <typename X>
+__host__ __device__ inline float hrtf_delay_tap(const HrtfDelay& d, int k, const X& x) {
+    return d.g * x(k - d.i) + d.f * x(k - d.i - 1);
+}
 struct BinauralRenderBatch {
+    const float* onsets;                // the onsets in force: [n_dirs][2] samples; null: none, omax unused and h_eff == h_taps
+    float omax;                         // ... the largest of them
+    int h_eff;                          // He = h_taps + (int)omax + 1: the taps of a delayed HRIR — of the fold, tc = taps + h_eff - 1
     const float4* mesh;                 // the mesh in force: [n_tris][3] {r_i, corner v_i}; null: nearest mode, and the three below unused
     int n_tris;
     float4* located;                    // [count][kVoiceSlots] scratch: {the bits of t1, b1[3]} of every slot with an entry

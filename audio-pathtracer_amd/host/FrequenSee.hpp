@@ -777,32 +777,49 @@ public:
     explicit FrequenSeeAudioBinauralPlugin(AudioRayTracingSubsystem& SubSys) : FrequenSeeAudioReflectionPlugin(SubSys) {}
     // the context's set: Dirs [n][3] (head frame: x forward, y right, z up), Hrir [n][2][H].  Interpolate: triangulate the set and
     // install the mesh (fs_hrtf_set_mesh) — every voice's HRIR is then the blend of the three round its direction, not the nearest
-    // one.  Before OnInitSource; not concurrent with ProcessAudio
-    void SetHrtf(const std::vector<float>& Dirs, const std::vector<float>& Hrir, int HrirTaps, bool Interpolate = false) {
+    // one.  Align: carry the HRIRs' onsets apart (fs_hrtf_set_onsets), so that the blend is of aligned HRIRs and of their delays —
+    // Onsets [n][2] where the host has them (Hrir is then the aligned set), else split off the set given (fs_hrtf_split_onsets:
+    // threshold 0.1, lead 0).  Before OnInitSource; not concurrent with ProcessAudio
+    void SetHrtf(const std::vector<float>& Dirs, const std::vector<float>& Hrir, int HrirTaps, bool Interpolate = false, bool Align = false,
+                 const std::vector<float>* Onsets = nullptr) {
+        if (HrirTaps < 1 || Dirs.size() % 3 != 0 || Hrir.size() != Dirs.size() / 3 * 2 * (size_t)HrirTaps ||
+            (Onsets && (!Align || Onsets->size() != Dirs.size() / 3 * 2)))
+            throw std::runtime_error("FrequenSee: an HRIR set is dirs [n][3], hrir [n][2][taps] and, with Align, onsets [n][2]");
+        std::vector<float> Aligned, Split;
+        if (Align && !Onsets) {
+            Aligned.resize(Hrir.size());
+            Split.resize(Dirs.size() / 3 * 2);
+            if (fs_hrtf_split_onsets(Hrir.data(), (int32_t)(Dirs.size() / 3), HrirTaps, 0.1f, 0, Aligned.data(), Split.data()) != FS_OK)
+                throw std::runtime_error("FrequenSee: fs_hrtf_split_onsets refused the set");
+            Onsets = &Split;
+        }
         fs_hrtf_desc D{};
         D.struct_size = sizeof(D);
         D.directions = (int32_t)(Dirs.size() / 3);
         D.taps = HrirTaps;
         D.sample_rate = SampleRate;
         D.dirs = Dirs.data();
-        D.hrir = Hrir.data();
-        if (HrirTaps < 1 || Dirs.size() % 3 != 0 || Hrir.size() != Dirs.size() / 3 * 2 * (size_t)HrirTaps)
-            throw std::runtime_error("FrequenSee: an HRIR set is dirs [n][3] and hrir [n][2][taps]");
+        D.hrir = Aligned.empty() ? Hrir.data() : Aligned.data();
         SubSys_->Check(fs_hrtf_set(SubSys_->Ctx_, &D));
-        if (!Interpolate) return;
-        std::vector<int32_t> Tri((size_t)std::max(2 * D.directions - 4, 1) * 3);
-        int32_t Triangles = 0;
-        if (fs_hrtf_triangulate(Dirs.data(), D.directions, Tri.data(), (int32_t)(Tri.size() / 3), &Triangles) != FS_OK)
-            throw std::runtime_error("FrequenSee: fs_hrtf_triangulate needs 4 .. 4096 distinct directions that surround the listener");
-        SubSys_->Check(fs_hrtf_set_mesh(SubSys_->Ctx_, Tri.data(), Triangles));
+        if (Interpolate) {
+            std::vector<int32_t> Tri((size_t)std::max(2 * D.directions - 4, 1) * 3);
+            int32_t Triangles = 0;
+            if (fs_hrtf_triangulate(Dirs.data(), D.directions, Tri.data(), (int32_t)(Tri.size() / 3), &Triangles) != FS_OK)
+                throw std::runtime_error("FrequenSee: fs_hrtf_triangulate needs 4 .. 4096 distinct directions that surround the listener");
+            SubSys_->Check(fs_hrtf_set_mesh(SubSys_->Ctx_, Tri.data(), Triangles));
+        }
+        if (Align) SubSys_->Check(fs_hrtf_set_onsets(SubSys_->Ctx_, Onsets->data()));
     }
-    // ... or the spherical-head model (a model: interaural delay and level difference, no pinna)
-    void SetHrtf(int Directions = 1024, int HrirTaps = 128, bool Interpolate = false) {
+    // ... or the spherical-head model (a model: interaural delay and level difference, no pinna); Align: its two halves apart
+    void SetHrtf(int Directions = 1024, int HrirTaps = 128, bool Interpolate = false, bool Align = false) {
         std::vector<float> Dirs((size_t)std::max(Directions, 0) * 3), Hrir((size_t)std::max(Directions, 0) * 2 * (size_t)std::max(HrirTaps, 0));
-        if (fs_hrtf_spherical_head(SampleRate, FS_HRTF_DEFAULT_RADIUS_CM, FS_HRTF_DEFAULT_SOUND_SPEED_CM_S, Directions, HrirTaps, Dirs.data(),
-                                   Hrir.data()) != FS_OK)
-            throw std::runtime_error("FrequenSee: fs_hrtf_spherical_head refused the directions or the taps");
-        SetHrtf(Dirs, Hrir, HrirTaps, Interpolate);
+        std::vector<float> Onsets((size_t)std::max(Directions, 0) * 2);
+        const int Rc = Align ? fs_hrtf_spherical_head_split(SampleRate, FS_HRTF_DEFAULT_RADIUS_CM, FS_HRTF_DEFAULT_SOUND_SPEED_CM_S, Directions,
+                                                            HrirTaps, Dirs.data(), Hrir.data(), Onsets.data())
+                             : fs_hrtf_spherical_head(SampleRate, FS_HRTF_DEFAULT_RADIUS_CM, FS_HRTF_DEFAULT_SOUND_SPEED_CM_S, Directions, HrirTaps,
+                                                      Dirs.data(), Hrir.data());
+        if (Rc != FS_OK) throw std::runtime_error("FrequenSee: fs_hrtf_spherical_head refused the directions or the taps");
+        SetHrtf(Dirs, Hrir, HrirTaps, Interpolate, Align, Align ? &Onsets : nullptr);
     }
     void OnInitSource(const FrequenSeeAudioComponent& C) {
         SubSys_->Check(fs_binaural_render_init(SubSys_->Ctx_, C.Handle_, FrameSize, Taps, VoiceCount, MaxDelaySeconds));

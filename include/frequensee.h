@@ -69,6 +69,7 @@
  *             fs_reflection_render_init fs_reflection_render_release fs_reflection_render_process_batch
  *             fs_hrtf_set fs_hrtf_info fs_hrtf_spherical_head
  *             fs_hrtf_triangulate fs_hrtf_mesh_rows fs_hrtf_mesh_locate fs_hrtf_set_mesh fs_hrtf_mesh_info
+ *             fs_hrtf_set_onsets fs_hrtf_onsets_info fs_hrtf_delay fs_hrtf_split_onsets fs_hrtf_spherical_head_split
  *             fs_binaural_render_init fs_binaural_render_release fs_binaural_render_process_batch
  *             fs_ambisonic_encode fs_ambisonic_render_init fs_ambisonic_render_release fs_ambisonic_render_process_batch
  * (tests/test_capi_cpu.py checks that every exported symbol is in exactly one of the two lists.)
@@ -1656,8 +1657,8 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
  *   The mesh (optional): a triangulation of the set's directions, over which a voice's HRIR is the barycentric blend of the three
  *   at the corners of the spherical triangle its direction falls in — a source walking round the listener no longer hops from one
  *   measured direction to the next.  Without a mesh everything above and below is as it stands, to the bit.  The blend is of the
- *   time-domain HRIRs as given: neighbours whose onsets differ comb slightly; onset-aligned (ITD-separated) interpolation,
- *   near-field sets and more than one mesh per context are not offered.
+ *   time-domain HRIRs as given: neighbours whose onsets differ comb (two half-height arrivals, not one in between) unless the
+ *   set carries its onsets apart (fs_hrtf_set_onsets, below); near-field sets and more than one mesh per context are not offered.
  *   fs_hrtf_mesh_rows.  Host only, no context, no device: the validator and the one definition of the mesh data.  dirs [n][3],
  *   tri [m][3] indices into dirs.  Accepted when 4 <= n <= FS_MAX_HRTF_DIRECTIONS and m == 2n - 4; every index lies in 0 .. n-1;
  *   the three indices of a triangle are distinct; every directed edge a->b occurs in exactly one triangle and b->a in exactly one
@@ -1687,6 +1688,42 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
  *   stream, uploads the triangles and their rows in one copy and frees every held binaural slot of every source, the histories
  *   kept — every voice starts from silence, and nothing ramps from an index of the other mode.  Tc and the ring sizes do not
  *   depend on the mesh.  fs_hrtf_mesh_info: *triangles = m of the mesh in force, 0 without one (the pointer may be NULL).
+ *   Onsets (optional).  A set in force may carry onsets o[j][ear], one float per direction and ear, in samples; hrir[j][ear][.]
+ *   is then read as the HRIR with that onset removed ("aligned"), and a voice's HRIR is the aligned one — the nearest, or with a
+ *   mesh the blend — delayed by the voice's own onset — the nearest's, or the blend of the corners' onsets: the interaural delay
+ *   glides with the direction where blending the HRIRs as given would cross-fade between two arrivals.  Without onsets everything
+ *   above and below is as it stands, to the bit.  With onsets in force:
+ *     omax = the largest onset of the set (a float);  O = (int)omax + 1;  He = H + O;  and Tc = T + He - 1 wherever Tc stands:
+ *     the ring sizing of fs_binaural_render_init, the refusal of a source whose ring the set has outgrown, the folded tables and
+ *     the render pass.
+ *     The delay of end A, ear `ear`:  nearest mode: tauA = o[qA][ear];  with a mesh, (v_0, v_1, v_2) = tri[tA]:
+ *       tauA = (bA_0 * o[v_0][ear] + bA_1 * o[v_1][ear]) + bA_2 * o[v_2][ear];
+ *     then  if (tauA > omax) tauA = omax  (the weights sum to 1 only within 2 ulp: the clamp keeps the last tap inside He).  All
+ *     terms are >= 0, so tauA >= 0.
+ *     The delayed HRIR (fs_hrtf_delay: host only, the same function as the kernel's; fp32, every operation rounded on its own):
+ *       i = (int)tau;  f = tau - (float)i;  g = 1.0f - f;
+ *       hd[k] = g * x(k - i) + f * x(k - i - 1),  k = 0 .. He-1,  x(j) = hA[j] for 0 <= j < H, else 0.0f,
+ *     with hA = h[qA][ear] in nearest mode, or rule 3''s blend, rounded as there, with a mesh: the linear fractional delay
+ *     fs_hrtf_spherical_head specifies for its own onsets.  Rules 3 and 3' then read hd[k] in h's place, k up to min(He - 1, u).
+ *     Equal q, or equal (t, b) bits, give equal tau bits: where one fold serves both ends it still does.  A change of direction
+ *     stays a block-long ramp between two tap tables, not a delay that glides inside the block.
+ *   fs_hrtf_set_onsets.  Needs a set in force.  onsets [n][2]; every onset finite and >= 0, and H + (int)omax + 1 <=
+ *   FS_MAX_HRTF_TAPS: otherwise (or without a set) FS_ERR_INVALID_ARGUMENT, and a refused call changes nothing.  onsets == NULL
+ *   clears them.  Either way the call then behaves as fs_hrtf_set_mesh: not concurrent with a callback; it waits for the reverb
+ *   stream, uploads in one copy and frees every held binaural slot of every source, the histories kept.  It does not drop the
+ *   mesh, and fs_hrtf_set_mesh does not drop the onsets; fs_hrtf_set, given a set or NULL, drops both.  A source initialised
+ *   before the call is refused by the callback while its ring is too small for the new Tc, exactly as after a set of another H.
+ *   fs_hrtf_onsets_info: *installed = 1 with onsets in force, else 0; *extra_taps = O, 0 without (either pointer may be NULL).
+ *   fs_hrtf_delay.  Host only.  out[0 .. He) = hd of h[0 .. H) and tau by the rule above.  FS_ERR_INVALID_ARGUMENT, nothing
+ *   written: a NULL pointer, H < 1, tau not finite or negative, or He < H + (int)tau + 1.
+ *   fs_hrtf_split_onsets.  Host only: for hosts whose set comes without delays.  hrir [n][2][H]; threshold in (0, 1], lead >= 0,
+ *   n >= 1, H >= 1, no NULL pointer (else FS_ERR_INVALID_ARGUMENT, nothing written).  Per (direction, ear): peak = max |h[k]|;
+ *   k0 = the lowest k with |h[k]| >= threshold * peak (an fp32 product); onset = (float)max(k0 - lead, 0); aligned[k] =
+ *   h[k + onset] while k + onset < H, else 0.0f.  An all-zero HRIR gets onset 0.  aligned may be hrir.  Integer onsets only —
+ *   what a mesh blends between them is fractional.
+ *   fs_hrtf_spherical_head_split.  fs_hrtf_spherical_head with its two halves handed out apart: hrir[k] = g[k], the shadow
+ *   filter alone, and onsets [n][2] = tau fs; in double, each value rounded to float once.  Its refusals, with onsets NULL among
+ *   them and 2 <= H <= FS_MAX_HRTF_TAPS in the place of the bound on H (the onset needs no taps).
  *   fs_binaural_render_init.  Needs a set in force.  F, T, D and V under fs_reflection_render_init's limits with Tc = T + H - 1
  *   wherever the ring is sized: 16 <= F <= 16384; T odd, 1 .. FS_DIRECT_RENDER_MAX_TAPS; Tc <= FS_DIRECT_RENDER_MAX_TAPS; the ring
  *   is the smallest power of two >= D + Tc + 1 + F floats and D + Tc + 1 + F <= 2^20; edges in force inside (0, fs / 2);
@@ -1718,7 +1755,8 @@ int fs_reflection_render_process_batch(fs_context* ctx, const fs_source* sources
  *     6'. A continuing or started slot holds (t1, b1) in q1's place.
  *     (Where t0 == t1, b0 and b1 have the same bits and so have g0 and g1, C1 has C0's bits either way.)
  *     Consequence: with a set of H = 1 whose taps are all 1.0f the output equals fs_reflection_render_process_batch's with
- *     channel_gain = (gain, gain).  The output is late by (T - 1) / 2 samples plus whatever onset the set's HRIRs carry.
+ *     channel_gain = (gain, gain).  The output is late by (T - 1) / 2 samples plus whatever onset the set's HRIRs carry — with
+ *     onsets in force, plus the delayed HRIR's onset tauA.
  *   fs_binaural_render_process_batch.  Arguments, refusals and batch rules of fs_reflection_render_process_batch, read for this
  *   call, and further FS_ERR_INVALID_ARGUMENT for: no set in force; a gain that is not finite; a direction with a component that
  *   is not finite or with all three zero; a source without fs_binaural_render_init; sources that do not share F and T (hence Tc);
@@ -1764,6 +1802,13 @@ int fs_hrtf_mesh_rows(const float* dirs /* [n][3] */, int32_t n, const int32_t* 
 int fs_hrtf_mesh_locate(const float* rows /* [m][3][3] */, int32_t m, const float d[3], int32_t* t, float b[3]);
 int fs_hrtf_set_mesh(fs_context* ctx, const int32_t* tri /* [m][3]; NULL or m == 0: clear */, int32_t m);
 int fs_hrtf_mesh_info(fs_context* ctx, int32_t* triangles);
+int fs_hrtf_set_onsets(fs_context* ctx, const float* onsets /* [n][2]; NULL: clear */);
+int fs_hrtf_onsets_info(fs_context* ctx, int32_t* installed, int32_t* extra_taps /* O, 0 without */);
+int fs_hrtf_delay(const float* h /* [H] */, int32_t H, float tau, float* out /* [He] */, int32_t He);
+int fs_hrtf_split_onsets(const float* hrir /* [n][2][H] */, int32_t n, int32_t H, float threshold, int32_t lead,
+                         float* aligned /* [n][2][H], may be hrir */, float* onsets /* [n][2] */);
+int fs_hrtf_spherical_head_split(int32_t sample_rate, float radius_cm, float sound_speed_cm_s, int32_t directions, int32_t taps,
+                                 float* dirs /* [directions][3] */, float* hrir /* [directions][2][taps] */, float* onsets /* [directions][2] */);
 int fs_binaural_render_init(fs_context* ctx, fs_source src, int32_t frame_size, int32_t taps, int32_t voices, float max_delay_seconds);
 int fs_binaural_render_release(fs_context* ctx, fs_source src);
 int fs_binaural_render_process_batch(fs_context* ctx, const fs_source* sources, int32_t count, const float* in /* [count][F * 2] */,

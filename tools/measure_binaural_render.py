@@ -6,8 +6,11 @@ Beside it, in the same process and at the same shapes: fs_reflection_render_proc
 gain pair in the HRIRs' place.  The C entry points are called with prepared arrays: the numbers are the library's, not the Python
 wrapper's.  With --interpolate the set carries its mesh (fs_hrtf_triangulate, fs_hrtf_set_mesh: 2044 triangles) and every voice's HRIR
 is the blend of three: the same shapes, one more launch (the locate pass).
+With --onsets the set is the split spherical head (fs_hrtf_spherical_head_split, fs_hrtf_set_onsets), with or without --interpolate:
+every voice's HRIR is the aligned one delayed by the voice's own onset, He = H + (int)omax + 1 taps; --hrir-taps=N sets H (the split
+head at H = 96 has the He = 128 of the plain head's table).
 --directions=N measures a set of another size (the table's is 1024).
-usage: python tools/measure_binaural_render.py [--interpolate] [--directions=N] [reps] [output.json]"""
+usage: python tools/measure_binaural_render.py [--interpolate] [--onsets] [--hrir-taps=N] [--directions=N] [reps] [output.json]"""
 import json
 import os
 import sys
@@ -20,9 +23,12 @@ import __graft_entry__ as graft  # noqa: E402
 
 FRAME, TAPS, BANDS, HRIR_TAPS, DIRECTIONS, SOURCES, VOICES = 1024, 255, 8, 128, 1024, (1, 32, 256), (4, 16)
 INTERPOLATE = "--interpolate" in sys.argv
+ONSETS = "--onsets" in sys.argv
 for a in sys.argv:
     if a.startswith("--directions="):
         DIRECTIONS = int(a.split("=", 1)[1])
+    if a.startswith("--hrir-taps="):
+        HRIR_TAPS = int(a.split("=", 1)[1])
 sys.argv = [a for a in sys.argv if not a.startswith("--")]
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 pkg = graft.load_package()
@@ -43,17 +49,25 @@ def median_ms(call):
 
 
 ctx = pkg.Context(num_bands=BANDS)
-the_set = pkg.Context.hrtf_spherical_head(ctx.cfg.sample_rate, DIRECTIONS, HRIR_TAPS)
-ctx.hrtf_set(*the_set)
+if ONSETS:
+    the_set = pkg.Context.hrtf_spherical_head_split(ctx.cfg.sample_rate, DIRECTIONS, HRIR_TAPS)
+else:
+    the_set = pkg.Context.hrtf_spherical_head(ctx.cfg.sample_rate, DIRECTIONS, HRIR_TAPS)
+ctx.hrtf_set(*the_set[:2])
 if INTERPOLATE:
     ctx.hrtf_set_mesh(pkg.Context.hrtf_triangulate(the_set[0]))
+EXTRA_TAPS = 0
+if ONSETS:
+    ctx.hrtf_set_onsets(the_set[2])
+    EXTRA_TAPS = ctx.hrtf_onsets_info()[1]
 binaural = [ctx.create_source() for _ in range(max(SOURCES))]
 reflect = [ctx.create_source() for _ in range(max(SOURCES))]
 blocks = rng.uniform(-1, 1, (max(SOURCES), 2 * FRAME)).astype(np.float32)
 out = np.empty_like(blocks)
 mix = np.empty(2 * FRAME, np.float32)
 result = {"callback": f"{FRAME} stereo frames per source, {BANDS} bands, T = {TAPS}, H = {HRIR_TAPS}, {DIRECTIONS} directions", "reps": reps,
-          "mode": "interpolated" if INTERPOLATE else "nearest", "triangles": ctx.hrtf_mesh_info(), "realtime_budget_ms": FRAME / 48.0, "rows": []}
+          "mode": ("interpolated" if INTERPOLATE else "nearest") + (" with onsets" if ONSETS else ""), "delayed_hrir_taps": HRIR_TAPS + EXTRA_TAPS,
+          "triangles": ctx.hrtf_mesh_info(), "realtime_budget_ms": FRAME / 48.0, "rows": []}
 for voices in VOICES:
     for s in binaural:
         ctx.binaural_render_init(s, FRAME, TAPS, voices, 0.1)
@@ -95,7 +109,7 @@ for voices in VOICES:
         for rows in (brows, rrows):
             assert int(rows["sounding"].min()) == voices and int(rows["dropped"].max()) == 0 and int(rows["started"].max()) == 0
         row = {"sources": n, "voices": voices, "mode": result["mode"], "binaural_render_ms": b_ms, "reflection_render_ms": r_ms, "ratio": b_ms / r_ms,
-               "folded_taps": TAPS + HRIR_TAPS - 1, "fits_the_block": b_ms <= FRAME / 48.0}
+               "folded_taps": TAPS + HRIR_TAPS + EXTRA_TAPS - 1, "fits_the_block": b_ms <= FRAME / 48.0}
         result["rows"].append(row)
         print(json.dumps(row), flush=True)
 ctx.close()
